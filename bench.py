@@ -52,8 +52,10 @@ F64_OPS_PER_CHECK = 10458.0
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=2)
-    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed steps (default 2; --config pool1m without --steps: as many as --max-seconds holds)")
+    ap.add_argument("--warmup", type=int, default=None,
+                    help="untimed steps before them (default 1; --config pool1m without --warmup: cut to --max-seconds)")
     ap.add_argument("--pool", type=int, default=0, help="override the pool size (default 65536*sqrt(N))")
     ap.add_argument("--config", choices=["headline", "pool1m"], default="headline",
                     help="headline: 65,536 primers per GPU-equivalent (weak); pool1m: 1,048,576 primers in total (strong)")
@@ -66,15 +68,23 @@ def parse_args():
     ap.add_argument("--no-stage-b", dest="stage_b", action="store_false")
     ap.add_argument("--max-seconds", type=float, default=450.0,
                     help="--config pool1m only: budget of the WHOLE run after start-up (estimate pass + warm-up + timed "
-                         "region + CPU leg); the step counts are cut to fit it, never below one timed step "
-                         "(one step is 1.1e12 checks: about 8 minutes on one GPU, about a minute on eight)")
+                         "region + CPU leg); the step counts not given on the command line are cut to fit it, never "
+                         "below one timed step (one step is 1.1e12 checks: about 8 minutes on one GPU, about a minute "
+                         "on eight)")
     ap.add_argument("--small-pool", dest="small_pool", action="store_true", default=None,
                     help="also time the reference-sized screens: 2,000 random 13-mers and the stage-A winners of the "
                          "10,000-genome alignment (default: on at N = 1)")
     ap.add_argument("--no-small-pool", dest="small_pool", action="store_false")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the cpu_baseline leg")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/*.npy (see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup is not None and args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 def pool_size_for(n_gpus: int) -> int:
@@ -358,6 +368,35 @@ def stage_b_line(eng, device, cpu_seconds: float):
     return out
 
 
+DUMP_BYTES = 64_000_000        # --dump-outputs writes at most this much in all
+DUMP_ROWS = 128                # bitmap rows sampled (fewer when the pool is too wide for the budget)
+DUMP_SEED = 20260701
+
+
+def dump_outputs(out_dir: str, d_conf: torch.Tensor, d_bitmap: torch.Tensor | None, n: int, r0: int):
+    """--dump-outputs: what the timed path hands its caller after its last step, so that two builds can be compared
+    output for output on the same seeded pool.
+        row_conflicts.npy   float64 (n,)     merged per-primer conflict counts
+        bitmap_rows.npy     float64 (m,)     pool rows of the bitmap sample: fixed seeded draw from this rank's block
+        bitmap_sample.npy   float32 (m, n)   those rows' conflict decisions against every column, 0 / 1
+    The bitmap files are written only when the run keeps a bitmap; m keeps the files under DUMP_BYTES."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    np.save(out / "row_conflicts.npy", d_conf.cpu().numpy().astype(np.float64))
+    m = 0
+    if d_bitmap is not None:
+        m = min(DUMP_ROWS, d_bitmap.shape[0], (DUMP_BYTES - 8 * n - 8 * DUMP_ROWS - 1024) // (4 * n))
+    if m < 1:
+        for name in ("bitmap_rows.npy", "bitmap_sample.npy"):
+            (out / name).unlink(missing_ok=True)      # no stale sample from an earlier run in the same DIR
+        return
+    rows = np.sort(np.random.Generator(np.random.PCG64(DUMP_SEED)).choice(d_bitmap.shape[0], size=m, replace=False))
+    words = d_bitmap[torch.from_numpy(rows).to(d_bitmap.device)].cpu().numpy()
+    bits = np.unpackbits(words.view(np.uint8), axis=1, bitorder="little")[:, :n]
+    np.save(out / "bitmap_rows.npy", (rows + r0).astype(np.float64))
+    np.save(out / "bitmap_sample.npy", bits.astype(np.float32))
+
+
 def respawn_under_launcher(args):
     """`python bench.py --gpus N` with no launcher: start N ranks as a CHILD process (never exec from a
     process that may have touched the GPU; this one has not) and hand its exit status on."""
@@ -438,12 +477,14 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    steps, warmup = args.steps, args.warmup
+    steps = args.steps if args.steps is not None else 2
+    warmup = args.warmup if args.warmup is not None else 1
     t_start = time.perf_counter()
     if strong:
-        # One step of the 1,048,576 pool is 1.1e12 checks (minutes).  The step counts are cut so that the WHOLE run --
-        # this estimate, the warm-up, the timed region and the CPU leg -- fits --max-seconds (450 s: the driver's limit
-        # is 600 s), but never below one timed step (on one GPU a single step is about 8 minutes: no budget holds it).
+        # One step of the 1,048,576 pool is 1.1e12 checks (minutes).  The step counts not given on the command line are
+        # cut so that the WHOLE run -- this estimate, the warm-up, the timed region and the CPU leg -- fits --max-seconds
+        # (450 s: the driver's limit is 600 s), but never below one timed step (on one GPU a single step is about 8
+        # minutes: no budget holds it).
         # The estimate: 1/16 of the rank's rows against all columns, fenced (it also builds the tables and sizes the
         # lists: the first warm-up).  Every rank takes the slowest rank's estimate, so all run the same counts.
         fence()
@@ -458,8 +499,10 @@ def main():
         all_reduce(est, dist.ReduceOp.MAX)
         per_step = max(float(est.item()), 1e-3)
         left = args.max_seconds - (time.perf_counter() - t_start) - (0.0 if args.no_cpu_baseline else args.cpu_seconds + 5.0)
-        steps = max(1, min(args.steps, int(left / per_step)))
-        warmup = max(0, min(args.warmup, int((left - steps * per_step) / per_step)))
+        if args.steps is None:
+            steps = max(1, min(steps, int(left / per_step)))
+        if args.warmup is None:
+            warmup = max(0, min(warmup, int((left - steps * per_step) / per_step)))
         warmup_done = 0
         del d_pool0
         eng.last_overflow_pairs()      # the estimate's hand-overs and stage counters are not the steps'
@@ -476,7 +519,7 @@ def main():
         step()
     fence()
     elapsed = time.perf_counter() - t0
-    steps_requested, warmup_requested = args.steps, args.warmup
+    steps_requested, warmup_requested = args.steps, args.warmup     # None: not given on the command line
     args.steps, args.warmup = steps, warmup_done     # what ran: every figure below is per step that ran
     launches, kernel_ms = eng.profile_read()
     eng.profile_enable(False)
@@ -500,6 +543,8 @@ def main():
         # position-weighted sum of the merged per-primer counts: equal for every sharding of the same pool
         weights = torch.arange(1, n + 1, dtype=torch.int64, device=dev)
         conflict_checksum = int((d_conf.to(torch.int64) * weights).sum().item())
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, d_conf, d_bitmap, n, r0)
         # dominant kernel: the first-stage all-pairs kernel; one launch covers up to 2^29 checks of this rank's block
         checks_rank = float(shard) * float(n) * args.steps
         per_launch_checks = checks_rank / max(launches, 1)
@@ -609,7 +654,8 @@ def main():
         out["timed_region_s"] = elapsed
         if strong:
             out["steps_requested"], out["warmup_requested"] = steps_requested, warmup_requested
-            out["note"] = (f"pool1m: step counts cut to the --max-seconds {args.max_seconds:.0f} budget of the whole run "
+            out["note"] = (f"pool1m: step counts not given on the command line cut to the --max-seconds "
+                           f"{args.max_seconds:.0f} budget of the whole run "
                            f"({per_step:.1f} s per step estimated from 1/16 of the rows); steps / warmup are what ran")
         print(json.dumps(out))
     if world > 1:

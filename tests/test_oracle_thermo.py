@@ -3,7 +3,6 @@ import json
 import math
 
 import numpy as np
-import pytest
 
 from helpers import draw_dimer
 
@@ -12,13 +11,11 @@ def g6(x: float) -> str:
     return "%g" % x
 
 
-def test_tables_bundle_equals_primer3_dir(oracle):
-    """The shipped bundle and a Primer3-format directory load to identical tables (only checkable
-    where the reference tree exists, i.e. in the build container)."""
-    from pathlib import Path
-    ref = Path("/root/reference/od-msspe/primer3_config")
-    if not ref.is_dir():
-        pytest.skip("reference tree not present (GPU box)")
+def test_tables_bundle_equals_primer3_dir(oracle, golden_dir):
+    """The shipped bundle and a Primer3-format directory load to identical tables.  The directory is
+    golden/primer3_config: the sixteen parameter files of the reference's od-msspe/primer3_config
+    (Primer3 2.6.1) that the loader reads, stored as they are."""
+    ref = golden_dir / "primer3_config"
     import ctypes as C
     a, b = oracle.Tables(), oracle.Tables(ref)
     size = 4 * 2 * 625 * 8 + 4 * 125 * 8   # the dense tables at the head of orc_tables
