@@ -167,6 +167,39 @@ int msspe_cross_dimer_edges_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, i
 int msspe_cross_dimer_edges(msspe_ctx *ctx, const char *pool_ascii, int n, int k, const msspe_chem *chem,
                             float dg_threshold, msspe_edge *edges, uint64_t capacity, uint64_t *count_out);
 
+/* One pool screened against another (engine extension: the reference screens one pool of one --kmer-size,
+ * od-msspe/src/delta_g.rs:61-81; ntthal itself takes any two oligos).  Pool A: n_a oligos of k_a bases, oligo 1
+ * (the rows); pool B: n_b oligos of k_b bases, oligo 2 (the columns); k_a, k_b in 2..32 and free to differ.  Only
+ * the ordered pairs (A[i], B[j]), i in [row0,row1) of A, j in [col0,col1) of B, are evaluated: for (B[j], A[i])
+ * swap the pools.  Outputs, decision, +inf / 0 for no structure and the clearing of the bitmap block are those of
+ * msspe_cross_dimer_dev, with rows indexing A and columns indexing B (row_conflicts: uint32[n_a] +=).
+ * k_a == k_b runs the single-pool chain on A and B staged back to back in a context-owned buffer (same results by
+ * construction); k_a != k_b runs the rectangular chain.  Empty pools or blocks: MSSPE_OK. */
+int msspe_cross_dimer_ab_dev(msspe_ctx *ctx, const uint64_t *d_a, int n_a, int k_a, const uint64_t *d_b, int n_b,
+                             int k_b, const msspe_chem *chem, float dg_threshold, int row0, int row1, int col0,
+                             int col1, uint32_t *d_row_conflicts, uint64_t *d_bitmap, double *d_dg, double *d_tm);
+/* The same block as an edge list, contract of msspe_cross_dimer_edges_dev; an edge's a is an A index, b a B index. */
+int msspe_cross_dimer_ab_edges_dev(msspe_ctx *ctx, const uint64_t *d_a, int n_a, int k_a, const uint64_t *d_b,
+                                   int n_b, int k_b, const msspe_chem *chem, float dg_threshold, int row0, int row1,
+                                   int col0, int col1, uint32_t *d_row_conflicts, msspe_edge_dev *d_edges,
+                                   uint64_t capacity, uint64_t *d_count);
+/* Host-buffer convenience: whole pools (a_ascii: n_a x k_a chars, b_ascii: n_b x k_b chars, no separators);
+ * row_conflicts[n_a], bitmap[n_a * ceil(n_b/64)], dg / tm [n_a * n_b], each optional.  Non-ACGT: MSSPE_ERR_ARG. */
+int msspe_cross_dimer_ab(msspe_ctx *ctx, const char *a_ascii, int n_a, int k_a, const char *b_ascii, int n_b, int k_b,
+                         const msspe_chem *chem, float dg_threshold, uint32_t *row_conflicts, uint64_t *bitmap,
+                         double *dg, double *tm);
+/* The same pools as an edge list: a = A index, b = B index, sorted by (a, b), Edge::get_dg() rounding and the
+ * MSSPE_ERR_CAPACITY contract of msspe_cross_dimer_edges. */
+int msspe_cross_dimer_ab_edges(msspe_ctx *ctx, const char *a_ascii, int n_a, int k_a, const char *b_ascii, int n_b,
+                               int k_b, const msspe_chem *chem, float dg_threshold, msspe_edge *edges, uint64_t capacity,
+                               uint64_t *count_out);
+/* One pool whose oligos may differ in length (NUL-terminated, 2..32 bases each): every ordered pair, self pairs
+ * included, edges sorted by (a, b) with Edge::get_dg() rounding -- msspe_cross_dimer_edges for what ntthal
+ * accepts; same MSSPE_ERR_CAPACITY contract.  The oligos are grouped by length and every (row length, column
+ * length) block is screened as above; a pool of one length gives exactly msspe_cross_dimer_edges's list. */
+int msspe_cross_dimer_edges_mixed(msspe_ctx *ctx, const char *const *oligos, int n, const msspe_chem *chem,
+                                  float dg_threshold, msspe_edge *edges, uint64_t capacity, uint64_t *count_out);
+
 /* Number of pairs the last cross-dimer call routed to the generic (slow) kernel because their
  * DP did not fit the fast kernel's register-resident table. */
 int msspe_last_overflow_pairs(msspe_ctx *ctx, uint64_t *count_out);

@@ -95,6 +95,8 @@ struct msspe_ctx {
     uint32_t *d_perm = nullptr;
     void *d_sort_scratch = nullptr;    // keys, values and rocPRIM temporary storage of the composition sort
     size_t sort_cap = 0, sort_scratch_bytes = 0;
+    uint64_t *d_ab = nullptr;          // msspe_cross_dimer_ab*: pool A and pool B staged back to back, A first
+    size_t ab_cap = 0;
     std::string err;
     KmerStage kmer;
     KmerStage kmer_rev;                // direction 1 of msspe_kmer_candidates_both_packed_dev (its own buffers and loop graph)
@@ -461,6 +463,7 @@ void msspe_destroy(msspe_ctx *ctx)
         if (ctx->d_sorted) (void)hipFree(ctx->d_sorted);
         if (ctx->d_perm) (void)hipFree(ctx->d_perm);
         if (ctx->d_sort_scratch) (void)hipFree(ctx->d_sort_scratch);
+        if (ctx->d_ab) (void)hipFree(ctx->d_ab);
         if (ctx->d_tb) (void)hipFree(ctx->d_tb);
         for (auto &ev : ctx->prof_events) {
             (void)hipEventDestroy(ev.first);
@@ -534,7 +537,8 @@ void msspe_unpack_oligo(uint64_t packed, int k, char *ascii_out)
     ascii_out[k] = 0;
 }
 
-static int cross_dimer_impl(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const msspe_chem *chem,
+// k: length of the row oligos, k2: length of the column oligos (k2 != k: the rectangular chain, see below)
+static int cross_dimer_impl(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, int k2, const msspe_chem *chem,
                             float dg_threshold, int row0, int row1, int col0, int col1,
                             uint32_t *d_row_conflicts, uint64_t *d_bitmap, double *d_dg, double *d_tm,
                             EdgeRecord *d_edges, unsigned long long *d_edge_count, unsigned long long edge_cap);
@@ -544,7 +548,7 @@ int msspe_cross_dimer_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k,
                           int col0, int col1, uint32_t *d_row_conflicts, uint64_t *d_bitmap,
                           double *d_dg, double *d_tm)
 {
-    return cross_dimer_impl(ctx, d_pool, n, k, chem, dg_threshold, row0, row1, col0, col1, d_row_conflicts,
+    return cross_dimer_impl(ctx, d_pool, n, k, k, chem, dg_threshold, row0, row1, col0, col1, d_row_conflicts,
                             d_bitmap, d_dg, d_tm, nullptr, nullptr, 0);
 }
 
@@ -558,19 +562,19 @@ int msspe_cross_dimer_edges_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, i
     static_assert(sizeof(msspe_edge_dev) == sizeof(EdgeRecord), "edge record layouts differ");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipMemsetAsync(d_count, 0, sizeof(uint64_t), ctx->stream));
-    return cross_dimer_impl(ctx, d_pool, n, k, chem, dg_threshold, row0, row1, col0, col1, d_row_conflicts,
+    return cross_dimer_impl(ctx, d_pool, n, k, k, chem, dg_threshold, row0, row1, col0, col1, d_row_conflicts,
                             nullptr, nullptr, nullptr, reinterpret_cast<EdgeRecord *>(d_edges),
                             reinterpret_cast<unsigned long long *>(d_count), capacity);
 }
 
-static int cross_dimer_impl(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const msspe_chem *chem,
+static int cross_dimer_impl(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, int k2, const msspe_chem *chem,
                             float dg_threshold, int row0, int row1, int col0, int col1,
                             uint32_t *d_row_conflicts, uint64_t *d_bitmap, double *d_dg, double *d_tm,
                             EdgeRecord *d_edges, unsigned long long *d_edge_count, unsigned long long edge_cap)
 {
     if (!ctx) return MSSPE_ERR_ARG;
     if (!d_pool || !chem || n < 0) return fail(ctx, MSSPE_ERR_ARG, "null pool/chemistry");
-    if (k < 2 || k > 32) return fail(ctx, MSSPE_ERR_K, "oligo length must be 2..32");
+    if (k < 2 || k > 32 || k2 < 2 || k2 > 32) return fail(ctx, MSSPE_ERR_K, "oligo length must be 2..32");
     if (row0 < 0 || row1 > n || row0 > row1 || col0 < 0 || col1 > n || col0 > col1)
         return fail(ctx, MSSPE_ERR_ARG, "row/column range outside the pool");
     if (row0 == row1 || col0 == col1) return MSSPE_OK;
@@ -578,7 +582,7 @@ static int cross_dimer_impl(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k
     ChemEntry *ce = nullptr;
     int rc = chem_entry(ctx, *chem, dg_threshold, &ce);
     if (rc) return rc;
-    if ((rc = ensure_workspace(ctx, (size_t)k * (size_t)k))) return rc;
+    if ((rc = ensure_workspace(ctx, (size_t)k * (size_t)k2))) return rc;
     if ((rc = ensure_overflow(ctx, (long)(row1 - row0) * (long)(col1 - col0)))) return rc;
     const long kListCap = ctx->list_cap;
 
@@ -586,14 +590,23 @@ static int cross_dimer_impl(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k
     const int words = (ncols + 63) / 64;
     // long oligos: exact-integer kernel with a pair's table split over lanes (honours max_loop)
     // (also short oligos under a loop-size limit the register-table kernels do not implement)
-    const bool split = !ctx->opt.force_generic && !(ctx->opt.pair_kernel == 1) && k <= ce->split_max_k &&
-                       (k >= ctx->opt.split_min_k || chem->max_loop < 2 * k - 4);
+    // Row and column oligos of different lengths (k2 != k) take the rectangular chain: the split-table kernel
+    // where the longer of the two is within its proven range (a k x k2 table lies inside the square of its longer
+    // side, whose int32 bounds build_split_tables checked), else the wave kernel in matrix mode; then the wave
+    // list stage and the dense kernel.  split_min_k and pair_kernel do not apply there: the register-table,
+    // integer and row-specialised first stages are square-only.
+    const bool rect = k2 != k;
+    const int kmax = std::max(k, k2);
+    const bool split = !ctx->opt.force_generic && kmax <= ce->split_max_k &&
+                       (rect || (!(ctx->opt.pair_kernel == 1) && (k >= ctx->opt.split_min_k || chem->max_loop < 2 * k - 4)));
     // f64, one wave per pair: behind the split kernel, and as the first stage where neither the split
     // kernel nor the register-table chain applies (29 .. 32 bases, parameter files off the grid)
-    const bool wave_ok = !ctx->opt.force_generic && k <= ce->wave_max_k && ctx->opt.wave_kernel;
-    const bool wave_matrix = wave_ok && !split && (k > pairs_fast_max_k() || chem->max_loop < 2 * k - 4);
+    const bool wave_ok = !ctx->opt.force_generic && kmax <= ce->wave_max_k && ctx->opt.wave_kernel;
+    const bool wave_matrix = wave_ok && !split && (rect || k > pairs_fast_max_k() || chem->max_loop < 2 * k - 4);
+    // the register-table / integer / row first stages are square-only: a rectangle that neither the split nor the
+    // wave kernel takes goes to the dense kernel
     const bool fast = split || wave_matrix ||
-                      (!ctx->opt.force_generic && k <= pairs_fast_max_k() && ce->fast_ok &&
+                      (!rect && !ctx->opt.force_generic && k <= pairs_fast_max_k() && ce->fast_ok &&
                        chem->max_loop >= 2 * k - 4);   // the tuned kernel has no loop-size cut-off
     // the conflict bitmap is produced with atomic ORs: clear the caller's block first
     if (d_bitmap)
@@ -618,6 +631,7 @@ static int cross_dimer_impl(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k
     g.c[1] = ce->c[1];
     g.pool = d_pool;
     g.k = k;
+    g.k2 = k2;
     g.mode = 1;
     g.sinks = sinks;
     g.wsS = ctx->wsS;
@@ -661,7 +675,7 @@ static int cross_dimer_impl(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k
     const bool int_stage = !split && ce->int_ok && !(ctx->opt.pair_kernel == 1);
     if (!wave_matrix) {
         if ((rc = ensure_sort(ctx, (size_t)ncols))) return rc;
-        HIP_TRY(ctx, sort_columns_by_composition(d_pool, col0, ncols, k, ctx->d_sort_scratch,
+        HIP_TRY(ctx, sort_columns_by_composition(d_pool, col0, ncols, k2, ctx->d_sort_scratch,
                                                  ctx->sort_scratch_bytes, ctx->d_sorted, ctx->d_perm,
                                                  ctx->stream));
     }
@@ -680,6 +694,7 @@ static int cross_dimer_impl(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k
         a.ncols_sorted = 0;
         a.n = n;
         a.k = k;
+        a.k2 = k2;
         a.row0 = row0;
         a.row1 = row1;
         a.col0 = 0;
@@ -796,6 +811,7 @@ static int cross_dimer_impl(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k
             a.ncols_sorted = ncols;
             a.n = n;
             a.k = k;
+            a.k2 = k2;
             a.row0 = r;
             a.row1 = r_end;
             a.col0 = (int)q0;
@@ -902,19 +918,20 @@ int msspe_pair_stage_samples(msspe_ctx *ctx, uint64_t *out, int capacity, int *n
     return MSSPE_OK;
 }
 
-int msspe_cross_dimer(msspe_ctx *ctx, const char *pool_ascii, int n, int k,
-                      const msspe_chem *chem, float dg_threshold, uint32_t *row_conflicts,
-                      uint64_t *bitmap, double *dg, double *tm)
+}  // extern "C"
+
+namespace {
+
+// Host-buffer screens: `packed` (uploaded here) is the pool, rows [0, n_rows) of length k against columns
+// [col_base, col_base + n_cols) of length k2.  One pool: col_base 0, n_rows = n_cols = n.  Pool A + pool B back to
+// back: col_base = n_a.  Outputs are dense over the block as in msspe_cross_dimer.
+int cross_dimer_host(msspe_ctx *ctx, const std::vector<uint64_t> &packed, int n_rows, int k, int col_base, int n_cols,
+                     int k2, const msspe_chem *chem, float dg_threshold, uint32_t *row_conflicts, uint64_t *bitmap,
+                     double *dg, double *tm)
 {
-    if (!ctx) return MSSPE_ERR_ARG;
-    if (!pool_ascii || !chem || n < 0) return fail(ctx, MSSPE_ERR_ARG, "null pool/chemistry");
-    if (n == 0) return MSSPE_OK;
-    std::vector<uint64_t> packed((size_t)n);
-    int rc = msspe_pack_oligos(pool_ascii, n, k, packed.data());
-    if (rc) return fail(ctx, rc, rc == MSSPE_ERR_K ? "oligo length must be 1..32"
-                                                   : "pool holds characters other than ACGT");
+    const int n = (int)packed.size();
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t words = ((size_t)n + 63) / 64, nn = (size_t)n * (size_t)n;
+    const size_t words = ((size_t)n_cols + 63) / 64, nn = (size_t)n_rows * (size_t)n_cols;
     uint64_t *d_pool = nullptr, *d_bitmap = nullptr;
     uint32_t *d_rc = nullptr;
     double *d_dg = nullptr, *d_tm = nullptr;
@@ -936,17 +953,17 @@ int msspe_cross_dimer(msspe_ctx *ctx, const char *pool_ascii, int n, int k,
     TRY_OR_CLEAN(hipMalloc((void **)&d_pool, sizeof(uint64_t) * (size_t)n));
     TRY_OR_CLEAN(hipMemcpy(d_pool, packed.data(), sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice));
     if (row_conflicts) {
-        TRY_OR_CLEAN(hipMalloc((void **)&d_rc, sizeof(uint32_t) * (size_t)n));
-        TRY_OR_CLEAN(hipMemsetAsync(d_rc, 0, sizeof(uint32_t) * (size_t)n, ctx->stream));   // on the stream the kernels run on (it is non-blocking: the null stream does not order against it)
+        TRY_OR_CLEAN(hipMalloc((void **)&d_rc, sizeof(uint32_t) * (size_t)n_rows));
+        TRY_OR_CLEAN(hipMemsetAsync(d_rc, 0, sizeof(uint32_t) * (size_t)n_rows, ctx->stream));   // on the stream the kernels run on (it is non-blocking: the null stream does not order against it)
     }
     if (bitmap) {
-        TRY_OR_CLEAN(hipMalloc((void **)&d_bitmap, sizeof(uint64_t) * (size_t)n * words));
-        TRY_OR_CLEAN(hipMemsetAsync(d_bitmap, 0, sizeof(uint64_t) * (size_t)n * words, ctx->stream));
+        TRY_OR_CLEAN(hipMalloc((void **)&d_bitmap, sizeof(uint64_t) * (size_t)n_rows * words));
+        TRY_OR_CLEAN(hipMemsetAsync(d_bitmap, 0, sizeof(uint64_t) * (size_t)n_rows * words, ctx->stream));
     }
     if (dg) TRY_OR_CLEAN(hipMalloc((void **)&d_dg, sizeof(double) * nn));
     if (tm) TRY_OR_CLEAN(hipMalloc((void **)&d_tm, sizeof(double) * nn));
-    rc = msspe_cross_dimer_dev(ctx, d_pool, n, k, chem, dg_threshold, 0, n, 0, n, d_rc, d_bitmap,
-                               d_dg, d_tm);
+    int rc = cross_dimer_impl(ctx, d_pool, n, k, k2, chem, dg_threshold, 0, n_rows, col_base, col_base + n_cols, d_rc,
+                              d_bitmap, d_dg, d_tm, nullptr, nullptr, 0);
     if (rc) {
         cleanup();
         return rc;
@@ -957,27 +974,123 @@ int msspe_cross_dimer(msspe_ctx *ctx, const char *pool_ascii, int n, int k,
         return rc;
     }
     if (row_conflicts)
-        TRY_OR_CLEAN(hipMemcpy(row_conflicts, d_rc, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToHost));
+        TRY_OR_CLEAN(hipMemcpy(row_conflicts, d_rc, sizeof(uint32_t) * (size_t)n_rows, hipMemcpyDeviceToHost));
     if (bitmap)
-        TRY_OR_CLEAN(hipMemcpy(bitmap, d_bitmap, sizeof(uint64_t) * (size_t)n * words, hipMemcpyDeviceToHost));
+        TRY_OR_CLEAN(hipMemcpy(bitmap, d_bitmap, sizeof(uint64_t) * (size_t)n_rows * words, hipMemcpyDeviceToHost));
     if (dg) TRY_OR_CLEAN(hipMemcpy(dg, d_dg, sizeof(double) * nn, hipMemcpyDeviceToHost));
     if (tm) TRY_OR_CLEAN(hipMemcpy(tm, d_tm, sizeof(double) * nn, hipMemcpyDeviceToHost));
+#undef TRY_OR_CLEAN
     cleanup();
     return MSSPE_OK;
 }
 
-int msspe_cross_dimer_edges(msspe_ctx *ctx, const char *pool_ascii, int n, int k, const msspe_chem *chem,
-                            float dg_threshold, msspe_edge *edges, uint64_t capacity, uint64_t *count_out)
+// Host edge lists: the first `have` raw edges (indices already mapped by the caller) sorted by (a, b) as the
+// reference's nested loops emit them, with the value Edge::get_dg() yields; MSSPE_ERR_CAPACITY when count > capacity.
+int emit_sorted_edges(msspe_ctx *ctx, std::vector<msspe_edge_dev> &raw, uint64_t count, uint64_t capacity,
+                      msspe_edge *edges)
+{
+    std::sort(raw.begin(), raw.end(), [](const msspe_edge_dev &x, const msspe_edge_dev &y) {
+        return x.a != y.a ? x.a < y.a : x.b < y.b;
+    });
+    for (size_t e = 0; e < raw.size(); ++e) {
+        edges[e].a = raw[e].a;
+        edges[e].b = raw[e].b;
+        // what Edge::get_dg() returns: the %g text as f32, stored as "{:.2}", parsed again (delta_g.rs:10-15, 33-46)
+        edges[e].dg = round_fixed_f32((double)round_g_f32(raw[e].dg), 2);
+    }
+    if (count > capacity)
+        return fail(ctx, MSSPE_ERR_CAPACITY, "edge list: " + std::to_string(count) + " conflict edges, capacity " +
+                                                 std::to_string(capacity));
+    return MSSPE_OK;
+}
+
+// Pool A and pool B back to back in the context's buffer, A first: the single-pool chain then screens rows of A
+// against columns n_a + j.
+int stage_ab(msspe_ctx *ctx, const uint64_t *d_a, int n_a, const uint64_t *d_b, int n_b)
+{
+    const size_t need = (size_t)n_a + (size_t)n_b;
+    if (ctx->ab_cap < need) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // an earlier screen may still read the old buffer
+        if (ctx->d_ab) (void)hipFree(ctx->d_ab);
+        ctx->d_ab = nullptr;
+        ctx->ab_cap = 0;
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_ab, sizeof(uint64_t) * need));
+        ctx->ab_cap = need;
+    }
+    if (n_a)
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_ab, d_a, sizeof(uint64_t) * (size_t)n_a, hipMemcpyDeviceToDevice, ctx->stream));
+    if (n_b)
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->d_ab + n_a, d_b, sizeof(uint64_t) * (size_t)n_b, hipMemcpyDeviceToDevice,
+                                    ctx->stream));
+    return MSSPE_OK;
+}
+
+// The screen ran on the staged A + B pool: an edge's b is a pool index, n_a + (B index).
+__global__ void k_edges_shift_b(EdgeRecord *edges, const unsigned long long *count, unsigned long long cap,
+                                uint32_t shift)
+{
+    const unsigned long long n = *count < cap ? *count : cap;
+    for (unsigned long long e = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; e < n;
+         e += (unsigned long long)gridDim.x * blockDim.x)
+        edges[e].b -= shift;
+}
+
+int cross_dimer_ab_impl(msspe_ctx *ctx, const uint64_t *d_a, int n_a, int k_a, const uint64_t *d_b, int n_b, int k_b,
+                        const msspe_chem *chem, float dg_threshold, int row0, int row1, int col0, int col1,
+                        uint32_t *d_row_conflicts, uint64_t *d_bitmap, double *d_dg, double *d_tm, EdgeRecord *d_edges,
+                        unsigned long long *d_edge_count, unsigned long long edge_cap)
+{
+    if (!chem || n_a < 0 || n_b < 0 || (n_a && !d_a) || (n_b && !d_b))
+        return fail(ctx, MSSPE_ERR_ARG, "null pool/chemistry");
+    if (k_a < 2 || k_a > 32 || k_b < 2 || k_b > 32) return fail(ctx, MSSPE_ERR_K, "oligo length must be 2..32");
+    if (row0 < 0 || row1 > n_a || row0 > row1 || col0 < 0 || col1 > n_b || col0 > col1)
+        return fail(ctx, MSSPE_ERR_ARG, "row/column range outside pool A / pool B");
+    if ((long)n_a + (long)n_b > (long)INT32_MAX) return fail(ctx, MSSPE_ERR_ARG, "pools too large");
+    if (row0 == row1 || col0 == col1) return MSSPE_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    int rc = stage_ab(ctx, d_a, n_a, d_b, n_b);
+    if (rc) return rc;
+    // k_a == k_b: the single-pool chain as it is (the 13-mer A x B screen runs on the row kernel); otherwise the
+    // rectangular chain
+    rc = cross_dimer_impl(ctx, ctx->d_ab, n_a + n_b, k_a, k_b, chem, dg_threshold, row0, row1, n_a + col0, n_a + col1,
+                          d_row_conflicts, d_bitmap, d_dg, d_tm, d_edges, d_edge_count, edge_cap);
+    if (rc) return rc;
+    if (d_edges && edge_cap && n_a) {
+        hipLaunchKernelGGL(k_edges_shift_b, dim3(256), dim3(256), 0, ctx->stream, d_edges, d_edge_count, edge_cap,
+                           (uint32_t)n_a);
+        HIP_TRY(ctx, hipGetLastError());
+    }
+    return MSSPE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int msspe_cross_dimer(msspe_ctx *ctx, const char *pool_ascii, int n, int k,
+                      const msspe_chem *chem, float dg_threshold, uint32_t *row_conflicts,
+                      uint64_t *bitmap, double *dg, double *tm)
 {
     if (!ctx) return MSSPE_ERR_ARG;
-    if (!pool_ascii || !chem || !count_out || n < 0 || (capacity && !edges))
-        return fail(ctx, MSSPE_ERR_ARG, "null pool/chemistry/count, or a capacity without a buffer");
-    *count_out = 0;
+    if (!pool_ascii || !chem || n < 0) return fail(ctx, MSSPE_ERR_ARG, "null pool/chemistry");
     if (n == 0) return MSSPE_OK;
     std::vector<uint64_t> packed((size_t)n);
     int rc = msspe_pack_oligos(pool_ascii, n, k, packed.data());
     if (rc) return fail(ctx, rc, rc == MSSPE_ERR_K ? "oligo length must be 1..32"
                                                    : "pool holds characters other than ACGT");
+    return cross_dimer_host(ctx, packed, n, k, 0, n, k, chem, dg_threshold, row_conflicts, bitmap, dg, tm);
+}
+
+}  // extern "C"
+
+namespace {
+
+// Host edge lists over the same layout as cross_dimer_host: rows [0, n_rows) of length k against columns
+// [col_base, col_base + n_cols) of length k2; edge b = column index (pool index - col_base).
+int cross_dimer_edges_host(msspe_ctx *ctx, const std::vector<uint64_t> &packed, int n_rows, int k, int col_base,
+                           int n_cols, int k2, const msspe_chem *chem, float dg_threshold, msspe_edge *edges,
+                           uint64_t capacity, uint64_t *count_out)
+{
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     uint64_t *d_pool = nullptr, *d_count = nullptr;
     msspe_edge_dev *d_edges = nullptr;
@@ -994,12 +1107,15 @@ int msspe_cross_dimer_edges(msspe_ctx *ctx, const char *pool_ascii, int n, int k
             return hip_fail(ctx, e__, #expr);                      \
         }                                                          \
     } while (0)
+    const int n = (int)packed.size();
     TRY_OR_CLEAN2(hipMalloc((void **)&d_pool, sizeof(uint64_t) * (size_t)n));
     TRY_OR_CLEAN2(hipMemcpy(d_pool, packed.data(), sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice));
     TRY_OR_CLEAN2(hipMalloc((void **)&d_count, sizeof(uint64_t)));
     if (capacity) TRY_OR_CLEAN2(hipMalloc((void **)&d_edges, sizeof(msspe_edge_dev) * (size_t)capacity));
-    rc = msspe_cross_dimer_edges_dev(ctx, d_pool, n, k, chem, dg_threshold, 0, n, 0, n, nullptr, d_edges, capacity,
-                                     d_count);
+    TRY_OR_CLEAN2(hipMemsetAsync(d_count, 0, sizeof(uint64_t), ctx->stream));
+    int rc = cross_dimer_impl(ctx, d_pool, n, k, k2, chem, dg_threshold, 0, n_rows, col_base, col_base + n_cols, nullptr,
+                              nullptr, nullptr, nullptr, reinterpret_cast<EdgeRecord *>(d_edges),
+                              reinterpret_cast<unsigned long long *>(d_count), capacity);
     if (rc) {
         cleanup();
         return rc;
@@ -1017,20 +1133,177 @@ int msspe_cross_dimer_edges(msspe_ctx *ctx, const char *pool_ascii, int n, int k
     if (have) TRY_OR_CLEAN2(hipMemcpy(raw.data(), d_edges, sizeof(msspe_edge_dev) * have, hipMemcpyDeviceToHost));
     cleanup();
 #undef TRY_OR_CLEAN2
-    // the kernels append in no particular order: sort by (a, b) as the reference's nested loops emit them
-    std::sort(raw.begin(), raw.end(), [](const msspe_edge_dev &x, const msspe_edge_dev &y) {
-        return x.a != y.a ? x.a < y.a : x.b < y.b;
-    });
-    for (size_t e = 0; e < have; ++e) {
-        edges[e].a = raw[e].a;
-        edges[e].b = raw[e].b;
-        // what Edge::get_dg() returns: the %g text as f32, stored as "{:.2}", parsed again (delta_g.rs:10-15, 33-46)
-        edges[e].dg = round_fixed_f32((double)round_g_f32(raw[e].dg), 2);
+    for (auto &e : raw) e.b -= (uint32_t)col_base;   // pool index -> column index
+    // the kernels append in no particular order
+    return emit_sorted_edges(ctx, raw, count, capacity, edges);
+}
+
+}  // namespace
+
+extern "C" {
+
+int msspe_cross_dimer_edges(msspe_ctx *ctx, const char *pool_ascii, int n, int k, const msspe_chem *chem,
+                            float dg_threshold, msspe_edge *edges, uint64_t capacity, uint64_t *count_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!pool_ascii || !chem || !count_out || n < 0 || (capacity && !edges))
+        return fail(ctx, MSSPE_ERR_ARG, "null pool/chemistry/count, or a capacity without a buffer");
+    *count_out = 0;
+    if (n == 0) return MSSPE_OK;
+    std::vector<uint64_t> packed((size_t)n);
+    int rc = msspe_pack_oligos(pool_ascii, n, k, packed.data());
+    if (rc) return fail(ctx, rc, rc == MSSPE_ERR_K ? "oligo length must be 1..32"
+                                                   : "pool holds characters other than ACGT");
+    return cross_dimer_edges_host(ctx, packed, n, k, 0, n, k, chem, dg_threshold, edges, capacity, count_out);
+}
+
+int msspe_cross_dimer_ab_dev(msspe_ctx *ctx, const uint64_t *d_a, int n_a, int k_a, const uint64_t *d_b, int n_b,
+                             int k_b, const msspe_chem *chem, float dg_threshold, int row0, int row1, int col0,
+                             int col1, uint32_t *d_row_conflicts, uint64_t *d_bitmap, double *d_dg, double *d_tm)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    return cross_dimer_ab_impl(ctx, d_a, n_a, k_a, d_b, n_b, k_b, chem, dg_threshold, row0, row1, col0, col1,
+                               d_row_conflicts, d_bitmap, d_dg, d_tm, nullptr, nullptr, 0);
+}
+
+int msspe_cross_dimer_ab_edges_dev(msspe_ctx *ctx, const uint64_t *d_a, int n_a, int k_a, const uint64_t *d_b,
+                                   int n_b, int k_b, const msspe_chem *chem, float dg_threshold, int row0, int row1,
+                                   int col0, int col1, uint32_t *d_row_conflicts, msspe_edge_dev *d_edges,
+                                   uint64_t capacity, uint64_t *d_count)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!d_count || (capacity && !d_edges)) return fail(ctx, MSSPE_ERR_ARG, "edge list: null count or buffer");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMemsetAsync(d_count, 0, sizeof(uint64_t), ctx->stream));
+    return cross_dimer_ab_impl(ctx, d_a, n_a, k_a, d_b, n_b, k_b, chem, dg_threshold, row0, row1, col0, col1,
+                               d_row_conflicts, nullptr, nullptr, nullptr, reinterpret_cast<EdgeRecord *>(d_edges),
+                               reinterpret_cast<unsigned long long *>(d_count), capacity);
+}
+
+int msspe_cross_dimer_ab(msspe_ctx *ctx, const char *a_ascii, int n_a, int k_a, const char *b_ascii, int n_b, int k_b,
+                         const msspe_chem *chem, float dg_threshold, uint32_t *row_conflicts, uint64_t *bitmap,
+                         double *dg, double *tm)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!chem || n_a < 0 || n_b < 0 || (n_a && !a_ascii) || (n_b && !b_ascii))
+        return fail(ctx, MSSPE_ERR_ARG, "null pool/chemistry");
+    if (k_a < 2 || k_a > 32 || k_b < 2 || k_b > 32) return fail(ctx, MSSPE_ERR_K, "oligo length must be 2..32");
+    if ((long)n_a + (long)n_b > (long)INT32_MAX) return fail(ctx, MSSPE_ERR_ARG, "pools too large");
+    std::vector<uint64_t> packed((size_t)n_a + (size_t)n_b);
+    if (msspe_pack_oligos(a_ascii ? a_ascii : "", n_a, k_a, packed.data()) ||
+        msspe_pack_oligos(b_ascii ? b_ascii : "", n_b, k_b, packed.data() + n_a))
+        return fail(ctx, MSSPE_ERR_ARG, "pool holds characters other than ACGT");
+    if (n_a == 0) return MSSPE_OK;
+    if (n_b == 0) {   // no columns: no conflicts
+        if (row_conflicts) std::fill(row_conflicts, row_conflicts + n_a, 0u);
+        return MSSPE_OK;
     }
-    if (count > capacity)
-        return fail(ctx, MSSPE_ERR_CAPACITY, "edge list: " + std::to_string(count) + " conflict edges, capacity " +
-                                                 std::to_string(capacity));
-    return MSSPE_OK;
+    return cross_dimer_host(ctx, packed, n_a, k_a, n_a, n_b, k_b, chem, dg_threshold, row_conflicts, bitmap, dg, tm);
+}
+
+int msspe_cross_dimer_ab_edges(msspe_ctx *ctx, const char *a_ascii, int n_a, int k_a, const char *b_ascii, int n_b,
+                               int k_b, const msspe_chem *chem, float dg_threshold, msspe_edge *edges, uint64_t capacity,
+                               uint64_t *count_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!chem || !count_out || n_a < 0 || n_b < 0 || (n_a && !a_ascii) || (n_b && !b_ascii) || (capacity && !edges))
+        return fail(ctx, MSSPE_ERR_ARG, "null pool/chemistry/count, or a capacity without a buffer");
+    *count_out = 0;
+    if (k_a < 2 || k_a > 32 || k_b < 2 || k_b > 32) return fail(ctx, MSSPE_ERR_K, "oligo length must be 2..32");
+    if ((long)n_a + (long)n_b > (long)INT32_MAX) return fail(ctx, MSSPE_ERR_ARG, "pools too large");
+    std::vector<uint64_t> packed((size_t)n_a + (size_t)n_b);
+    if (msspe_pack_oligos(a_ascii ? a_ascii : "", n_a, k_a, packed.data()) ||
+        msspe_pack_oligos(b_ascii ? b_ascii : "", n_b, k_b, packed.data() + n_a))
+        return fail(ctx, MSSPE_ERR_ARG, "pool holds characters other than ACGT");
+    if (n_a == 0 || n_b == 0) return MSSPE_OK;
+    return cross_dimer_edges_host(ctx, packed, n_a, k_a, n_a, n_b, k_b, chem, dg_threshold, edges, capacity,
+                                  count_out);
+}
+
+int msspe_cross_dimer_edges_mixed(msspe_ctx *ctx, const char *const *oligos, int n, const msspe_chem *chem,
+                                  float dg_threshold, msspe_edge *edges, uint64_t capacity, uint64_t *count_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if ((n && !oligos) || !chem || !count_out || n < 0 || (capacity && !edges))
+        return fail(ctx, MSSPE_ERR_ARG, "null pool/chemistry/count, or a capacity without a buffer");
+    *count_out = 0;
+    // group the oligos by length: classes in ascending length, each class contiguous in one packed pool;
+    // orig[p] = caller's index of pool entry p
+    std::vector<int> len((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        if (!oligos[i]) return fail(ctx, MSSPE_ERR_ARG, "null oligo");
+        const size_t l = strnlen(oligos[i], 33);
+        if (l < 2 || l > 32) return fail(ctx, MSSPE_ERR_K, "oligo length must be 2..32");
+        len[i] = (int)l;
+    }
+    if (n == 0) return MSSPE_OK;
+    std::vector<uint32_t> orig((size_t)n);
+    for (int i = 0; i < n; ++i) orig[i] = (uint32_t)i;
+    std::stable_sort(orig.begin(), orig.end(), [&](uint32_t x, uint32_t y) { return len[x] < len[y]; });
+    std::vector<uint64_t> packed((size_t)n);
+    for (int p = 0; p < n; ++p)
+        if (msspe_pack_oligos(oligos[orig[p]], 1, len[orig[p]], &packed[p]))
+            return fail(ctx, MSSPE_ERR_ARG, "pool holds characters other than ACGT");
+    std::vector<int> cls_off, cls_len;   // class c: pool entries [cls_off[c], cls_off[c + 1])
+    for (int p = 0; p < n; ++p)
+        if (p == 0 || len[orig[p]] != len[orig[p - 1]]) {
+            cls_off.push_back(p);
+            cls_len.push_back(len[orig[p]]);
+        }
+    cls_off.push_back(n);
+    const int n_cls = (int)cls_len.size();
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    uint64_t *d_pool = nullptr, *d_count = nullptr;
+    msspe_edge_dev *d_edges = nullptr;
+    auto cleanup = [&]() {
+        if (d_pool) (void)hipFree(d_pool);
+        if (d_count) (void)hipFree(d_count);
+        if (d_edges) (void)hipFree(d_edges);
+    };
+#define TRY_OR_CLEAN3(expr)                                        \
+    do {                                                           \
+        hipError_t e__ = (expr);                                   \
+        if (e__ != hipSuccess) {                                   \
+            cleanup();                                             \
+            return hip_fail(ctx, e__, #expr);                      \
+        }                                                          \
+    } while (0)
+    TRY_OR_CLEAN3(hipMalloc((void **)&d_pool, sizeof(uint64_t) * (size_t)n));
+    TRY_OR_CLEAN3(hipMemcpy(d_pool, packed.data(), sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice));
+    TRY_OR_CLEAN3(hipMalloc((void **)&d_count, sizeof(uint64_t)));
+    TRY_OR_CLEAN3(hipMemsetAsync(d_count, 0, sizeof(uint64_t), ctx->stream));
+    if (capacity) TRY_OR_CLEAN3(hipMalloc((void **)&d_edges, sizeof(msspe_edge_dev) * (size_t)capacity));
+    // one block per (row class, column class), all appending to one list: the blocks of one pool need no staging,
+    // and an equal-length block (the diagonal) is the single-pool chain itself
+    for (int r = 0; r < n_cls; ++r)
+        for (int c = 0; c < n_cls; ++c) {
+            const int rc = cross_dimer_impl(ctx, d_pool, n, cls_len[r], cls_len[c], chem, dg_threshold, cls_off[r],
+                                            cls_off[r + 1], cls_off[c], cls_off[c + 1], nullptr, nullptr, nullptr,
+                                            nullptr, reinterpret_cast<EdgeRecord *>(d_edges),
+                                            reinterpret_cast<unsigned long long *>(d_count), capacity);
+            if (rc) {
+                cleanup();
+                return rc;
+            }
+        }
+    TRY_OR_CLEAN3(hipStreamSynchronize(ctx->stream));
+    if (int rc = check_list_overrun(ctx)) {
+        cleanup();
+        return rc;
+    }
+    uint64_t count = 0;
+    TRY_OR_CLEAN3(hipMemcpy(&count, d_count, sizeof count, hipMemcpyDeviceToHost));
+    *count_out = count;
+    const size_t have = (size_t)std::min<uint64_t>(count, capacity);
+    std::vector<msspe_edge_dev> raw(have);
+    if (have) TRY_OR_CLEAN3(hipMemcpy(raw.data(), d_edges, sizeof(msspe_edge_dev) * have, hipMemcpyDeviceToHost));
+    cleanup();
+#undef TRY_OR_CLEAN3
+    for (auto &e : raw) {   // pool entries -> the caller's indices
+        e.a = orig[e.a];
+        e.b = orig[e.b];
+    }
+    return emit_sorted_edges(ctx, raw, count, capacity, edges);
 }
 
 int msspe_thal_detail_pairs(msspe_ctx *ctx, const char *a_ascii, const char *b_ascii, int n, int k,
@@ -1076,6 +1349,7 @@ int msspe_thal_detail_pairs(msspe_ctx *ctx, const char *a_ascii, const char *b_a
     g.c[1] = ce->c[1];
     g.pool = d_pool;
     g.k = k;
+    g.k2 = k;
     g.mode = mode;
     g.list = d_list;
     g.n_work = n;
@@ -1142,6 +1416,7 @@ int msspe_oligo_stats_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k,
         g.c[1] = ce->c[1];
         g.pool = d_pool;
         g.k = k;
+        g.k2 = k;
         g.mode = pass == 0 ? 1 : 2;
         g.n_work = n;
         g.self_mode = 1;

@@ -54,7 +54,8 @@ struct GenericDimerArgs {
     const PairTables *pt;      // device, 2 entries
     ThalConsts c[2];
     const uint64_t *pool;
-    int k;
+    int k;                     // length of oligo 1 (the row, list .x)
+    int k2;                    // length of oligo 2 (the column, list .y); every caller sets it (= k for one pool)
     int mode;                  // kModeAny / kModeEnd1
     const uint2 *list;
     const uint32_t *list_count;   // optional device counter overriding n_work (overflow lists)
@@ -63,7 +64,7 @@ struct GenericDimerArgs {
     double *self_t;
     void *detail;              // optional ThalDetail[n_work] (list mode; thal_dense.hpp)
     PairSinks sinks;
-    double *wsS, *wsH;         // workspace planes, [cell][lane], lanes = ws_lanes
+    double *wsS, *wsH;         // workspace planes, [cell][lane], lanes = ws_lanes (k * k2 cells per lane)
     size_t ws_lanes;
 };
 hipError_t launch_dimer_generic(const GenericDimerArgs &a, hipStream_t stream);
@@ -98,6 +99,8 @@ struct PairKernelArgs {
     const uint32_t *perm;          // cols_sorted[q] == pool[perm[q]]
     int ncols_sorted;
     int n, k;
+    int k2;                        // column length: the split-table and wave kernels take k2 != k (a pool of row primers
+                                   // screened against one of column primers); every other first stage is square (k2 == k)
     int row0, row1, col0, col1;
     PairSinks sinks;
     uint2 *overflow_list;

@@ -45,13 +45,13 @@ __global__ void __launch_bounds__(256) k_dimer_generic(GenericDimerArgs a)
             col = a.sinks.col0 + (int)(w % a.sinks.ncols);
         }
         const uint64_t pa = a.pool[row], pb = a.pool[col];
-        const int sym = (self_complementary(pa, a.k) && self_complementary(pb, a.k)) ? 1 : 0;
+        const int sym = (self_complementary(pa, a.k) && self_complementary(pb, a.k2)) ? 1 : 0;
         DimerCtx ctx;
         ctx.pt = a.pt + sym;
         ctx.c = a.c[sym];
         ctx.s1 = Seq{pa, a.k};
-        ctx.s2 = Seq{reverse_packed(pb, a.k), a.k};
-        ctx.m = Planes{a.wsS + lane, a.wsH + lane, a.ws_lanes, a.k};
+        ctx.s2 = Seq{reverse_packed(pb, a.k2), a.k2};
+        ctx.m = Planes{a.wsS + lane, a.wsH + lane, a.ws_lanes, a.k2};
         ThalOut o;
         ThalDetail *det = a.detail ? (ThalDetail *)a.detail + w : nullptr;
         if (det) {

@@ -16,8 +16,9 @@ namespace {
 typedef SplitTables W_;
 
 struct SeqW {
-    unsigned long long s1, s2, lenmask;   // 2 bits per base; s2 = oligo 2 reversed
-    int len;
+    unsigned long long s1, s2;            // 2 bits per base; s2 = oligo 2 reversed
+    unsigned long long lenmask1, lenmask2;
+    int len1, len2;                       // oligo 1 (rows) and oligo 2 (columns) may differ in length
 };
 
 __device__ __forceinline__ unsigned long long spaced_mask64(unsigned long long s, int base,
@@ -34,20 +35,27 @@ __device__ __forceinline__ unsigned long long reverse2_64(unsigned long long s, 
     return r >> (64 - 2 * len);
 }
 
-__device__ __forceinline__ int setup_pair_w(uint64_t pa, uint64_t pb, int k, SeqW &q,
+__device__ __forceinline__ unsigned long long len_mask64(int k)
+{
+    return k == 32 ? ~0ull : ((1ull << (2 * k)) - 1ull);
+}
+
+// k1: length of oligo 1 (the rows, i < k1), k2: length of oligo 2 (the columns, j < k2).
+__device__ __forceinline__ int setup_pair_w(uint64_t pa, uint64_t pb, int k1, int k2, SeqW &q,
                                             unsigned long long &rowmask)
 {
-    const unsigned long long lenmask = k == 32 ? ~0ull : ((1ull << (2 * k)) - 1ull);
-    q.len = k;
-    q.lenmask = lenmask;
-    q.s1 = pa & lenmask;
-    q.s2 = reverse2_64(pb & lenmask, k);
+    q.len1 = k1;
+    q.len2 = k2;
+    q.lenmask1 = len_mask64(k1);
+    q.lenmask2 = len_mask64(k2);
+    q.s1 = pa & q.lenmask1;
+    q.s2 = reverse2_64(pb & q.lenmask2, k2);
     int n_cells = 0;
     rowmask = 0;
 #pragma unroll
     for (int x = 0; x < 4; ++x) {
-        const unsigned long long m1 = spaced_mask64(q.s1, x, lenmask);
-        const unsigned long long m2 = spaced_mask64(q.s2, 3 - x, lenmask);
+        const unsigned long long m1 = spaced_mask64(q.s1, x, q.lenmask1);
+        const unsigned long long m2 = spaced_mask64(q.s2, 3 - x, q.lenmask2);
         n_cells += __popcll(m1) * __popcll(m2);
         rowmask |= m2 ? m1 : 0ull;
     }
@@ -66,9 +74,9 @@ __device__ __forceinline__ CellS cell_s(const SeqW &q, int im1, int jm1)
     const int t1 = 2 * im1, t2 = 2 * jm1;
     b.a = (int)((q.s1 >> t1) & 3);
     const int oaL = im1 > 0 ? (int)((q.s1 >> ((t1 - 2) & 63)) & 3) : 4;
-    const int oaR = im1 < q.len - 1 ? (int)((q.s1 >> ((t1 + 2) & 63)) & 3) : 4;
+    const int oaR = im1 < q.len1 - 1 ? (int)((q.s1 >> ((t1 + 2) & 63)) & 3) : 4;
     const int obL = jm1 > 0 ? (int)((q.s2 >> ((t2 - 2) & 63)) & 3) : 4;
-    const int obR = jm1 < q.len - 1 ? (int)((q.s2 >> ((t2 + 2) & 63)) & 3) : 4;
+    const int obR = jm1 < q.len2 - 1 ? (int)((q.s2 >> ((t2 + 2) & 63)) & 3) : 4;
     b.idxL = W_::kEndL + b.a * 25 + oaL * 5 + obL;
     b.idxR = W_::kEndR + b.a * 25 + oaR * 5 + obR;
     const int ci = (((3 - b.a) * 4 + (obL & 3)) * 4 + (oaL & 3)) & 63;

@@ -756,6 +756,7 @@ hipError_t launch_self_lists(const FastTables *ft, const ThalConsts &c, const ui
     a.c = c;
     a.pool = pool;
     a.k = k;
+    a.k2 = k;
     a.overflow_cap = list_cap;
     a.overflow_list = list_b;
     a.overflow_count = counters + 1;

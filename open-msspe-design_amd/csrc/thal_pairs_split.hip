@@ -34,7 +34,7 @@ typedef int v32i __attribute__((ext_vector_type(32)));
 constexpr int kC = 4;               // slots per chunk
 constexpr int kLaneSlots = 64;      // register slots per lane (two planes of 32 + 32)
 constexpr int kThreadsS = 512;
-constexpr int kPathMaxS = 32;       // a path has at most k <= 32 cells
+constexpr int kPathMaxS = 32;       // a path has at most min(k1, k2) <= 32 cells
 constexpr int kEmptyS = 0x3ff;      // coordinates (31, 31): fails every geometry test
 constexpr int kNoCell = 0x3ff;      // "no predecessor"
 
@@ -221,7 +221,7 @@ __device__ __forceinline__ SplitResult run_pair_split(SharedS &sh, const ThalCon
         const bool newrow = mrem == 0;
         const int t = __ffsll((long long)Rrem) - 1;
         const int a_new = (int)((q.s1 >> (t & 63)) & 3);
-        const unsigned long long m_new = spaced_mask64(q.s2, 3 - a_new, q.lenmask);
+        const unsigned long long m_new = spaced_mask64(q.s2, 3 - a_new, q.lenmask2);
         im1 = newrow ? (t >> 1) : im1;
         Rrem = newrow ? (Rrem & (Rrem - 1)) : Rrem;
         mrem = newrow ? m_new : mrem;
@@ -449,7 +449,7 @@ struct SplitArgs {
     const uint64_t *pool;
     const uint64_t *cols_sorted;
     const uint32_t *perm;
-    int k;
+    int k, k2;                     // row (oligo 1) and column (oligo 2) lengths
     int row0, row1, col0, col1;
     PairSinks sinks;
     uint2 *ovf_list;
@@ -481,9 +481,12 @@ __device__ __forceinline__ void load_tables_s(SharedS &sh, const SplitArgs &a)
 // List mode (LIST): wave = 64 / Q consecutive entries of a hand-over list.  Entries that carry the tie mark are
 // passed on untouched (this kernel would meet the same tie); the others left the integer stages for their size
 // only, and two lanes per pair hold tables twice as large.
-template <int Q, bool LIST>
+// RECT: column oligos of a.k2 bases, row oligos of a.k (a pool screened against another); the square instances
+// keep one length (the second one costs a dword of spill in this 255-VGPR kernel).
+template <int Q, bool LIST, bool RECT = false>
 __global__ void __launch_bounds__(kThreadsS) k_pairs_split(SplitArgs a)
 {
+    const int k2 = RECT ? a.k2 : a.k;
     __shared__ SharedS sh;
     if (LIST && *a.in_count == 0u) return;   // nothing was handed on: not worth 53 KB of table loads per block
     load_tables_s(sh, a);
@@ -524,8 +527,8 @@ __global__ void __launch_bounds__(kThreadsS) k_pairs_split(SplitArgs a)
         const bool head = (lane & (Q - 1)) == 0;   // the lane that reports for its group
         SeqW q;
         unsigned long long rowmask;
-        int n_cells = setup_pair_w(pa, pb, a.k, q, rowmask);
-        const bool sym = self_complementary(pa, a.k) && self_complementary(pb, a.k);
+        int n_cells = setup_pair_w(pa, pb, a.k, k2, q, rowmask);
+        const bool sym = self_complementary(pa, a.k) && self_complementary(pb, k2);
         bool spill = inside & ((n_cells > kLaneSlots * Q) | sym | marked);
         if (!inside | spill) n_cells = 0;
         const int nmax = wave_max_s(n_cells);
@@ -591,6 +594,7 @@ hipError_t launch_pairs_split(const PairKernelArgs &a, const SplitTables *st, un
     x.cols_sorted = a.cols_sorted;
     x.perm = a.perm;
     x.k = a.k;
+    x.k2 = a.k2;
     x.row0 = a.row0;
     x.row1 = a.row1;
     x.col0 = a.col0;
@@ -602,13 +606,19 @@ hipError_t launch_pairs_split(const PairKernelArgs &a, const SplitTables *st, un
     x.reasons = reasons;
     x.work_counter = a.work_counter;
     if (hipError_t e = hipMemsetAsync(a.work_counter, 0, sizeof(unsigned), stream); e != hipSuccess) return e;
-    const int Q = (lanes == 2 || lanes == 4 || lanes == 8) ? lanes : pairs_split_lanes(a.k);   // option "split_lanes"
+    // option "split_lanes"; by default the longer oligo of the pair shape sets the lanes (a k1 x k2 table has no more
+    // cells than the square of its longer side)
+    const int Q = (lanes == 2 || lanes == 4 || lanes == 8) ? lanes : pairs_split_lanes(a.k > a.k2 ? a.k : a.k2);
     const long tiles = (long)((a.col1 - a.col0 + 64 / Q - 1) / (64 / Q)) * (long)((a.row1 - a.row0 + 7) / 8);
     if (tiles <= 0) return hipSuccess;
     const int grid = (int)(tiles < 256L ? tiles : 256L);   // one persistent block per CU (about 150 KB of LDS)
     x.in_list = nullptr;
     x.in_count = nullptr;
-    if (Q == 2) hipLaunchKernelGGL((k_pairs_split<2, false>), dim3(grid), dim3(kThreadsS), 0, stream, x);
+    if (a.k2 != a.k) {
+        if (Q == 2) hipLaunchKernelGGL((k_pairs_split<2, false, true>), dim3(grid), dim3(kThreadsS), 0, stream, x);
+        else if (Q == 4) hipLaunchKernelGGL((k_pairs_split<4, false, true>), dim3(grid), dim3(kThreadsS), 0, stream, x);
+        else hipLaunchKernelGGL((k_pairs_split<8, false, true>), dim3(grid), dim3(kThreadsS), 0, stream, x);
+    } else if (Q == 2) hipLaunchKernelGGL((k_pairs_split<2, false>), dim3(grid), dim3(kThreadsS), 0, stream, x);
     else if (Q == 4) hipLaunchKernelGGL((k_pairs_split<4, false>), dim3(grid), dim3(kThreadsS), 0, stream, x);
     else hipLaunchKernelGGL((k_pairs_split<8, false>), dim3(grid), dim3(kThreadsS), 0, stream, x);
     return hipGetLastError();
@@ -626,6 +636,7 @@ hipError_t launch_pairs_split_list(const PairKernelArgs &a, const SplitTables *s
     x.cols_sorted = nullptr;
     x.perm = nullptr;
     x.k = a.k;
+    x.k2 = a.k;   // the list mode serves the square chain only
     x.row0 = a.row0;
     x.row1 = a.row1;
     x.col0 = a.col0;

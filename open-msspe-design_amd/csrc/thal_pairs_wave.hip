@@ -44,7 +44,7 @@ struct WaveArgs {
     const SplitTables *st;
     ThalConsts c;
     const uint64_t *pool;
-    int k;
+    int k, k2;                       // row (oligo 1) and column (oligo 2) lengths
     int row0, row1, col0, col1;      // matrix mode (in_list == nullptr): the block of the pair matrix
     const uint2 *in_list;            // list mode: explicit pairs (bit 31 of .x is a mark, ignored)
     const uint32_t *in_count;
@@ -113,20 +113,21 @@ __device__ __forceinline__ CandW candidate(const SharedWv &sh, const CellS &b, i
 
 // thal.c fillMatrix() for one pair, computed by the whole wave: the cells' values in the wave's LDS table.
 // Returns the number of cells, or -1 when the pair does not fit the table.
-__device__ int fill_pair_wave(SharedWv &sh, int wave, const ThalConsts &K, uint64_t pa, uint64_t pb, int k, SeqW &q)
+__device__ int fill_pair_wave(SharedWv &sh, int wave, const ThalConsts &K, uint64_t pa, uint64_t pb, int k1, int k2,
+                              SeqW &q)
 {
     const int lane = threadIdx.x & 63;
     double *cS = sh.cS[wave];
     int *cH = sh.cH[wave];
     unsigned short *cW = sh.cW[wave];
     unsigned long long rowmask;
-    const int n = setup_pair_w(pa, pb, k, q, rowmask);
+    const int n = setup_pair_w(pa, pb, k1, k2, q, rowmask);
     if (n > kWaveCells) return -1;
     if (n == 0) return 0;
     // ---- the cells in row-major order: lane = row, exclusive scan of the row lengths
     {
         unsigned long long m = 0ull;
-        if (lane < k) m = spaced_mask64(q.s2, 3 - (int)((q.s1 >> (2 * lane)) & 3), q.lenmask);
+        if (lane < k1) m = spaced_mask64(q.s2, 3 - (int)((q.s1 >> (2 * lane)) & 3), q.lenmask2);
         const int cnt = __popcll(m);
         int incl = cnt;
         for (int off = 1; off < 64; off <<= 1) {
@@ -206,7 +207,7 @@ __device__ int fill_pair_wave(SharedWv &sh, int wave, const ThalConsts &K, uint6
 
 // Terminal pick (thal ANY, or END1: the last row only), thal.c's value-matching traceback and the totals over a
 // filled table of n > 0 cells.
-__device__ void finish_pair_wave(const SharedWv &sh, int wave, const ThalConsts &K, const SeqW &q, int k, int n, bool end1,
+__device__ void finish_pair_wave(const SharedWv &sh, int wave, const ThalConsts &K, const SeqW &q, int n, bool end1,
                                  WaveResult &out)
 {
     const int lane = threadIdx.x & 63;
@@ -226,7 +227,7 @@ __device__ void finish_pair_wave(const SharedWv &sh, int wave, const ThalConsts 
         const double rSn = sh.S[b.idxR] + kTiny, rHn = (double)sh.H[b.idxR] + kTiny;
         const double Gt = (((double)cH[p] + rHn) + K.init_H) - kT37 * ((cS[p] + rSn) + K.init_S);
         // thal END1: only structures that close on the 3' base of oligo 1 (the last row)
-        const bool pick = (Gt < pickG) & (!end1 | (((Wp >> 5) & 31) == k - 1));
+        const bool pick = (Gt < pickG) & (!end1 | (((Wp >> 5) & 31) == q.len1 - 1));
         pickG = pick ? Gt : pickG;
         pickSlot = pick ? p : pickSlot;
     }
@@ -324,19 +325,19 @@ __global__ void __launch_bounds__(kThreadsW) k_pairs_wave(WaveArgs a)
             col = a.col0 + (int)(w % ncols);
         }
         const uint64_t pa = a.pool[row], pb = a.pool[col];
-        const bool sym = self_complementary(pa, a.k) && self_complementary(pb, a.k);
+        const bool sym = self_complementary(pa, a.k) && self_complementary(pb, a.k2);
         WaveResult r;
         r.none = true;
         r.conflict = false;
         r.dG = INFINITY;
         r.t = 0.0;
         SeqW q;
-        const int n_cells = sym ? -1 : fill_pair_wave(sh, wave, a.c, pa, pb, a.k, q);   // wave-uniform
+        const int n_cells = sym ? -1 : fill_pair_wave(sh, wave, a.c, pa, pb, a.k, a.k2, q);   // wave-uniform
         const bool fits = n_cells >= 0;
         WaveResult r_end = r;
         if (n_cells > 0) {
-            if (!self || a.self_any) finish_pair_wave(sh, wave, a.c, q, a.k, n_cells, false, r);
-            if (self && a.self_end) finish_pair_wave(sh, wave, a.c, q, a.k, n_cells, true, r_end);
+            if (!self || a.self_any) finish_pair_wave(sh, wave, a.c, q, n_cells, false, r);
+            if (self && a.self_end) finish_pair_wave(sh, wave, a.c, q, n_cells, true, r_end);
         }
         // lane 0 reports; no lane may run ahead into the next fetch (readfirstlane reads the first
         // ACTIVE lane), so there is no early `continue` here: the wave reconverges at the loop's end
@@ -376,6 +377,7 @@ hipError_t launch_pairs_wave(const PairKernelArgs &a, const SplitTables *st, con
     x.c = a.c;
     x.pool = a.pool;
     x.k = a.k;
+    x.k2 = a.k2;
     x.row0 = a.row0;
     x.row1 = a.row1;
     x.col0 = a.col0;
@@ -410,6 +412,7 @@ hipError_t launch_self_wave(const SplitTables *st, const ThalConsts &c, const ui
     x.c = c;
     x.pool = pool;
     x.k = k;
+    x.k2 = k;
     x.row0 = row0;
     x.row1 = row1;
     x.col0 = 0;

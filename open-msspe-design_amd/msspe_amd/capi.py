@@ -17,6 +17,8 @@ EXPORTS = [
     "msspe_synchronize",
     "msspe_pack_oligos", "msspe_unpack_oligo", "msspe_cross_dimer_dev", "msspe_cross_dimer",
     "msspe_cross_dimer_edges_dev", "msspe_cross_dimer_edges",
+    "msspe_cross_dimer_ab_dev", "msspe_cross_dimer_ab_edges_dev", "msspe_cross_dimer_ab", "msspe_cross_dimer_ab_edges",
+    "msspe_cross_dimer_edges_mixed",
     "msspe_last_overflow_pairs", "msspe_pair_stage_stats", "msspe_pair_stage_samples", "msspe_host_pair_tables", "msspe_host_split_tables", "msspe_device_put_rows", "msspe_segment_coverage", "msspe_segment_coverage_dev",
     "msspe_device_put", "msspe_device_free", "msspe_thal_detail_pairs", "msspe_profile_enable", "msspe_profile_read",
     "msspe_oligo_stats_dev", "msspe_oligo_stats",
@@ -129,6 +131,16 @@ def load_library() -> C.CDLL:
                                           C.c_uint64, C.POINTER(C.c_uint64)]
     L.msspe_cross_dimer_edges_dev.argtypes = [vp, u64p, C.c_int, C.c_int, C.POINTER(Chem), C.c_float,
                                               C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_uint64, vp]
+    L.msspe_cross_dimer_ab_dev.argtypes = [vp, u64p, C.c_int, C.c_int, u64p, C.c_int, C.c_int, C.POINTER(Chem),
+                                           C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.msspe_cross_dimer_ab_edges_dev.argtypes = [vp, u64p, C.c_int, C.c_int, u64p, C.c_int, C.c_int, C.POINTER(Chem),
+                                                 C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_uint64, vp]
+    L.msspe_cross_dimer_ab.argtypes = [vp, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_int, C.c_int,
+                                       C.POINTER(Chem), C.c_float, vp, vp, vp, vp]
+    L.msspe_cross_dimer_ab_edges.argtypes = [vp, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_int, C.c_int,
+                                             C.POINTER(Chem), C.c_float, vp, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.msspe_cross_dimer_edges_mixed.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int, C.POINTER(Chem), C.c_float, vp,
+                                                C.c_uint64, C.POINTER(C.c_uint64)]
     L.msspe_last_overflow_pairs.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.msspe_pair_stage_stats.argtypes = [vp, C.POINTER(C.c_uint64)]   # out[16]
     L.msspe_pair_stage_samples.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int, C.POINTER(C.c_int)]
@@ -315,6 +327,82 @@ class Engine:
             self.ptr, C.c_void_p(d_pool), n, k, C.byref(chem), C.c_float(threshold),
             rows[0], rows[1], cols[0], cols[1], C.c_void_p(d_row_conflicts),
             C.c_void_p(d_bitmap), C.c_void_p(d_dg), C.c_void_p(d_tm)))
+
+    # ---- stage C, one pool against another (oligo lengths may differ) -------------------------
+    def cross_dimer_ab(self, a, b, chem: Chem | None = None, threshold: float = -9000.0,
+                       want_dg=True, want_tm=False, want_bitmap=True):
+        """Ordered pairs (A[i], B[j]) of two pools, each of one length (msspe_cross_dimer_ab): the dict of
+        cross_dimer with rows = A and columns = B (row_conflicts[n_a], bitmap (n_a, ceil(n_b/64)), dg / tm (n_a, n_b))."""
+        abuf, n_a, k_a = _ascii(a)
+        bbuf, n_b, k_b = _ascii(b)
+        k_a, k_b = k_a or k_b or 2, k_b or k_a or 2   # an empty pool's length does not matter
+        chem = chem or Chem.ntthal()
+        rc_ = np.zeros(n_a, dtype=np.uint32)
+        bm = np.zeros((n_a, (n_b + 63) // 64), dtype=np.uint64) if want_bitmap else None
+        dg = np.empty((n_a, n_b)) if want_dg else None
+        tm = np.empty((n_a, n_b)) if want_tm else None
+        self._check(self.L.msspe_cross_dimer_ab(
+            self.ptr, abuf, n_a, k_a, bbuf, n_b, k_b, C.byref(chem), C.c_float(threshold), rc_.ctypes.data,
+            bm.ctypes.data if want_bitmap else None, dg.ctypes.data if want_dg else None,
+            tm.ctypes.data if want_tm else None))
+        return {"row_conflicts": rc_, "bitmap": bm, "dg": dg, "tm": tm}
+
+    def cross_dimer_ab_dev(self, d_a: int, n_a: int, k_a: int, d_b: int, n_b: int, k_b: int, chem: Chem,
+                           threshold: float, rows: tuple[int, int], cols: tuple[int, int], d_row_conflicts: int = 0,
+                           d_bitmap: int = 0, d_dg: int = 0, d_tm: int = 0):
+        """Device-pointer call over rows [rows) of A x columns [cols) of B (msspe_cross_dimer_ab_dev); asynchronous."""
+        self._check(self.L.msspe_cross_dimer_ab_dev(
+            self.ptr, C.c_void_p(d_a), n_a, k_a, C.c_void_p(d_b), n_b, k_b, C.byref(chem), C.c_float(threshold),
+            rows[0], rows[1], cols[0], cols[1], C.c_void_p(d_row_conflicts), C.c_void_p(d_bitmap),
+            C.c_void_p(d_dg), C.c_void_p(d_tm)))
+
+    def cross_dimer_ab_edges_dev(self, d_a: int, n_a: int, k_a: int, d_b: int, n_b: int, k_b: int, chem: Chem,
+                                 threshold: float, rows: tuple[int, int], cols: tuple[int, int], d_edges: int,
+                                 capacity: int, d_count: int, d_row_conflicts: int = 0):
+        """Device-pointer edge list of a block of A x B (msspe_cross_dimer_ab_edges_dev: a = A index, b = B index);
+        asynchronous."""
+        self._check(self.L.msspe_cross_dimer_ab_edges_dev(
+            self.ptr, C.c_void_p(d_a), n_a, k_a, C.c_void_p(d_b), n_b, k_b, C.byref(chem), C.c_float(threshold),
+            rows[0], rows[1], cols[0], cols[1], C.c_void_p(d_row_conflicts), C.c_void_p(d_edges), capacity,
+            C.c_void_p(d_count)))
+
+    def cross_dimer_ab_edges(self, a, b, chem: Chem | None = None, threshold: float = -9000.0,
+                             capacity: int = 1 << 20):
+        """Edge list of A x B (msspe_cross_dimer_ab_edges): (edges [a, b, dg] sorted by (a, b), dg as Edge::get_dg()
+        reads it, count); raises MsspeError (MSSPE_ERR_CAPACITY, .count = edges needed) when the capacity is too
+        small."""
+        abuf, n_a, k_a = _ascii(a)
+        bbuf, n_b, k_b = _ascii(b)
+        k_a, k_b = k_a or k_b or 2, k_b or k_a or 2   # an empty pool's length does not matter
+        chem = chem or Chem.ntthal()
+        edges = np.zeros(capacity, dtype=np.dtype([("a", np.uint32), ("b", np.uint32), ("dg", np.float32)]))
+        count = C.c_uint64()
+        rc = self.L.msspe_cross_dimer_ab_edges(self.ptr, abuf, n_a, k_a, bbuf, n_b, k_b, C.byref(chem),
+                                               C.c_float(threshold), edges.ctypes.data, capacity, C.byref(count))
+        if rc:
+            err = MsspeError(rc, self.L.msspe_last_error(self.ptr).decode())
+            err.count = int(count.value)
+            err.edges = edges
+            raise err
+        return edges[:count.value], int(count.value)
+
+    def cross_dimer_edges_mixed(self, oligos, chem: Chem | None = None, threshold: float = -9000.0,
+                                capacity: int = 1 << 20):
+        """Edge list over every ordered pair of a pool whose oligos may differ in length (msspe_cross_dimer_edges_mixed):
+        (edges [a, b, dg] sorted by (a, b), count), indices into `oligos`; capacity errors as cross_dimer_edges."""
+        enc = [o.encode() for o in oligos]
+        arr = (C.c_char_p * max(len(enc), 1))(*enc)
+        chem = chem or Chem.ntthal()
+        edges = np.zeros(capacity, dtype=np.dtype([("a", np.uint32), ("b", np.uint32), ("dg", np.float32)]))
+        count = C.c_uint64()
+        rc = self.L.msspe_cross_dimer_edges_mixed(self.ptr, arr, len(enc), C.byref(chem), C.c_float(threshold),
+                                                  edges.ctypes.data, capacity, C.byref(count))
+        if rc:
+            err = MsspeError(rc, self.L.msspe_last_error(self.ptr).decode())
+            err.count = int(count.value)
+            err.edges = edges
+            raise err
+        return edges[:count.value], int(count.value)
 
     def profile_enable(self, on: bool = True):
         self._check(self.L.msspe_profile_enable(self.ptr, int(on)))
