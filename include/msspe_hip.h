@@ -200,6 +200,58 @@ int msspe_cross_dimer_ab_edges(msspe_ctx *ctx, const char *a_ascii, int n_a, int
 int msspe_cross_dimer_edges_mixed(msspe_ctx *ctx, const char *const *oligos, int n, const msspe_chem *chem,
                                   float dg_threshold, msspe_edge *edges, uint64_t capacity, uint64_t *count_out);
 
+/* ---- stage C, 3'-end dimers: thal END1 for every ordered pair (ntthal -a END1 / -a END2) ------ */
+
+/*
+ * The END screen: Primer3 2.6.1 thal type END1 (structures that close on the 3' base of oligo 1 = the row; without
+ * one, thal's fallback to cell (1, 1)) for every ORDERED pair of the block, self pairs included -- the pair
+ * analogue of the SELF_END_TH filter od-msspe applies to each primer (od-msspe/src/main.rs:498-499).  END2(a, b) is
+ * END1(b, a): one screen answers both 3' ends, and max(T, T^T) of its t plane T is the per-pair maximum.
+ * Decision: a pair conflicts iff !(round_fixed_f32(t_end, 2) < tm_threshold), t_end = max(0, t), 0 without a
+ * structure (od-msspe's SELF_END rule); tm_threshold <= 0: every pair conflicts.  The kernels test
+ * t_end > msspe_t_cut(tm_threshold).
+ * Outputs as msspe_cross_dimer_dev: row_conflicts +=, bitmap block cleared by the call, dg = raw dG (+inf without a
+ * structure), tm = raw t (0 without a structure).  A call without planes gives the same bits (the f64 kernels settle
+ * terminal-pick ties in Primer3's order).
+ * Kernels: the f64 register-table kernel (equal lengths, k <= 16, max_loop >= 2k - 4), else the one-wave-per-pair
+ * kernel, then the dense kernel.  Options force_generic, wave_kernel and list_cap_log2 apply;
+ * pair_kernel, split_min_k, split_lanes and row_oob do not (there is no integer END stage).
+ * Argument errors return the statuses of the thal ANY sibling.
+ */
+int msspe_cross_dimer_end_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const msspe_chem *chem,
+                              float tm_threshold, int row0, int row1, int col0, int col1, uint32_t *d_row_conflicts,
+                              uint64_t *d_bitmap, double *d_dg, double *d_tm);
+/* Host-buffer convenience: packs, uploads, runs the full n x n matrix, downloads (as msspe_cross_dimer). */
+int msspe_cross_dimer_end(msspe_ctx *ctx, const char *pool_ascii, int n, int k, const msspe_chem *chem,
+                          float tm_threshold, uint32_t *row_conflicts, uint64_t *bitmap, double *dg, double *tm);
+/* The END screen as an edge list.
+ *   _dev: contract of msspe_cross_dimer_edges_dev; a record carries the raw double t of the pair.
+ *   host: whole pool, edges sorted by (a, b), t = round_fixed_f32(t_end, 2) (the "%.2f" value the decision reads),
+ *         MSSPE_ERR_CAPACITY contract of msspe_cross_dimer_edges. */
+typedef struct {
+    uint32_t a, b;   /* pool indices of the ordered pair (a = oligo 1, the anchored 3' end) */
+    double t;        /* Celsius, unrounded (0 without a structure) */
+} msspe_end_edge_dev;
+typedef struct {
+    uint32_t a, b;
+    float t;
+} msspe_end_edge;
+int msspe_cross_dimer_end_edges_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const msspe_chem *chem,
+                                    float tm_threshold, int row0, int row1, int col0, int col1,
+                                    uint32_t *d_row_conflicts, msspe_end_edge_dev *d_edges, uint64_t capacity,
+                                    uint64_t *d_count);
+int msspe_cross_dimer_end_edges(msspe_ctx *ctx, const char *pool_ascii, int n, int k, const msspe_chem *chem,
+                                float tm_threshold, msspe_end_edge *edges, uint64_t capacity, uint64_t *count_out);
+/* Pool A (oligo 1, the anchored 3' end) against pool B (oligo 2), lengths 2..32 and free to differ: the END screen
+ * over the pairs (A[i], B[j]) with the staging, block and output conventions of msspe_cross_dimer_ab_dev /
+ * msspe_cross_dimer_ab.  END2 of (A[i], B[j]): swap the pools. */
+int msspe_cross_dimer_end_ab_dev(msspe_ctx *ctx, const uint64_t *d_a, int n_a, int k_a, const uint64_t *d_b, int n_b,
+                                 int k_b, const msspe_chem *chem, float tm_threshold, int row0, int row1, int col0,
+                                 int col1, uint32_t *d_row_conflicts, uint64_t *d_bitmap, double *d_dg, double *d_tm);
+int msspe_cross_dimer_end_ab(msspe_ctx *ctx, const char *a_ascii, int n_a, int k_a, const char *b_ascii, int n_b,
+                             int k_b, const msspe_chem *chem, float tm_threshold, uint32_t *row_conflicts,
+                             uint64_t *bitmap, double *dg, double *tm);
+
 /* Number of pairs the last cross-dimer call routed to the generic (slow) kernel because their
  * DP did not fit the fast kernel's register-resident table. */
 int msspe_last_overflow_pairs(msspe_ctx *ctx, uint64_t *count_out);
@@ -403,6 +455,9 @@ float msspe_round_fixed_f32(double x, int decimals);/* "%.Nf" -> f32 (od-msspe/s
 /* Largest double X such that msspe_round_g_f32(x) < threshold  <=>  x <= X (the decision cut the
  * kernels compare against; exact by construction, found by bisection over doubles). */
 double msspe_g_cut(float threshold);
+/* Largest double X such that msspe_round_fixed_f32(x, 2) < tm_threshold  <=>  x <= X: the END screen's cut (a pair
+ * conflicts iff t_end > X); below 0 when tm_threshold <= 0, so that every pair conflicts. */
+double msspe_t_cut(float tm_threshold);
 
 #ifdef __cplusplus
 }

@@ -32,6 +32,7 @@ namespace {
 struct ChemEntry {
     msspe_chem chem;
     float threshold;
+    bool end = false;             // the END screen's entry: c[].g_cut holds t_cut(threshold), not g_cut(threshold)
     ThalConsts c[2];
     PairTables *d_pt = nullptr;   // 2 entries: ordinary, both self-complementary
     FastTables *d_ft = nullptr;   // tables of the tuned all-pairs kernel (ordinary pairs)
@@ -145,10 +146,12 @@ bool same_chem(const msspe_chem &a, const msspe_chem &b)
            a.temp_c == b.temp_c && a.max_loop == b.max_loop;
 }
 
-int chem_entry(msspe_ctx *ctx, const msspe_chem &chem, float threshold, ChemEntry **out)
+// end: the entry of the END screen (msspe_cross_dimer_end*), whose cut is msspe_t_cut(threshold); it is cached apart
+// from the thal ANY entry of the same chemistry and threshold, so that neither call can pick up the other's cut.
+int chem_entry(msspe_ctx *ctx, const msspe_chem &chem, float threshold, ChemEntry **out, bool end = false)
 {
     for (auto &e : ctx->chem_cache)
-        if (same_chem(e.chem, chem) && (e.threshold == threshold ||
+        if (same_chem(e.chem, chem) && e.end == end && (e.threshold == threshold ||
                                         (std::isnan(e.threshold) && std::isnan(threshold)))) {
             *out = &e;
             return MSSPE_OK;
@@ -158,6 +161,7 @@ int chem_entry(msspe_ctx *ctx, const msspe_chem &chem, float threshold, ChemEntr
     ChemEntry e;
     e.chem = chem;
     e.threshold = threshold;
+    e.end = end;
     PairTables host_pt[2];
     for (int sym = 0; sym < 2; ++sym) {
         e.c[sym] = make_dimer_consts(chem.mv, chem.dv, chem.dntp, chem.dna_conc, chem.temp_c,
@@ -184,6 +188,8 @@ int chem_entry(msspe_ctx *ctx, const msspe_chem &chem, float threshold, ChemEntr
         HIP_TRY(ctx, hipMalloc((void **)&e.d_st, sizeof(SplitTables)));
         HIP_TRY(ctx, hipMemcpy(e.d_st, st.get(), sizeof(SplitTables), hipMemcpyHostToDevice));
     }
+    if (end)
+        for (auto &c : e.c) c.g_cut = t_cut(threshold);
     ctx->chem_cache.push_back(e);
     *out = &ctx->chem_cache.back();
     return MSSPE_OK;
@@ -567,47 +573,33 @@ int msspe_cross_dimer_edges_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, i
                             reinterpret_cast<unsigned long long *>(d_count), capacity);
 }
 
-static int cross_dimer_impl(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, int k2, const msspe_chem *chem,
-                            float dg_threshold, int row0, int row1, int col0, int col1,
-                            uint32_t *d_row_conflicts, uint64_t *d_bitmap, double *d_dg, double *d_tm,
-                            EdgeRecord *d_edges, unsigned long long *d_edge_count, unsigned long long edge_cap)
+// The stages of one screen, chosen by cross_dimer_impl (thal ANY) or cross_dimer_end_impl (thal END1).
+struct ChainRoute {
+    bool end1;          // the END screen: END1 instantiations of every stage and the t decision
+    bool fast;          // a first stage runs; otherwise the dense kernel takes the whole block
+    bool split;         // split-table first stage (ANY only)
+    bool wave_ok;       // the wave kernel may take a hand-over list
+    bool wave_matrix;   // the wave kernel is the first stage
+    bool int_stage;     // integer first stage and the integer list stages (ANY only)
+    bool short_chain;   // behind the integer list stage straight to the wave kernel
+};
+
+// Runs a routed screen over the block: launch splitting, column sort, the first stage, and the hand-over lists
+// flushed through the stages behind it.
+static int run_chain(msspe_ctx *ctx, ChemEntry *ce, const ChainRoute &route, const uint64_t *d_pool, int n, int k,
+                     int k2, int row0, int row1, int col0, int col1, uint32_t *d_row_conflicts, uint64_t *d_bitmap,
+                     double *d_dg, double *d_tm, EdgeRecord *d_edges, unsigned long long *d_edge_count,
+                     unsigned long long edge_cap)
 {
-    if (!ctx) return MSSPE_ERR_ARG;
-    if (!d_pool || !chem || n < 0) return fail(ctx, MSSPE_ERR_ARG, "null pool/chemistry");
-    if (k < 2 || k > 32 || k2 < 2 || k2 > 32) return fail(ctx, MSSPE_ERR_K, "oligo length must be 2..32");
-    if (row0 < 0 || row1 > n || row0 > row1 || col0 < 0 || col1 > n || col0 > col1)
-        return fail(ctx, MSSPE_ERR_ARG, "row/column range outside the pool");
-    if (row0 == row1 || col0 == col1) return MSSPE_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    ChemEntry *ce = nullptr;
-    int rc = chem_entry(ctx, *chem, dg_threshold, &ce);
-    if (rc) return rc;
+    const bool end1 = route.end1, fast = route.fast, split = route.split, wave_ok = route.wave_ok,
+               wave_matrix = route.wave_matrix, int_stage = route.int_stage, short_chain = route.short_chain;
+    int rc = 0;
     if ((rc = ensure_workspace(ctx, (size_t)k * (size_t)k2))) return rc;
     if ((rc = ensure_overflow(ctx, (long)(row1 - row0) * (long)(col1 - col0)))) return rc;
     const long kListCap = ctx->list_cap;
 
     const int ncols = col1 - col0;
     const int words = (ncols + 63) / 64;
-    // long oligos: exact-integer kernel with a pair's table split over lanes (honours max_loop)
-    // (also short oligos under a loop-size limit the register-table kernels do not implement)
-    // Row and column oligos of different lengths (k2 != k) take the rectangular chain: the split-table kernel
-    // where the longer of the two is within its proven range (a k x k2 table lies inside the square of its longer
-    // side, whose int32 bounds build_split_tables checked), else the wave kernel in matrix mode; then the wave
-    // list stage and the dense kernel.  split_min_k and pair_kernel do not apply there: the register-table,
-    // integer and row-specialised first stages are square-only.
-    const bool rect = k2 != k;
-    const int kmax = std::max(k, k2);
-    const bool split = !ctx->opt.force_generic && kmax <= ce->split_max_k &&
-                       (rect || (!(ctx->opt.pair_kernel == 1) && (k >= ctx->opt.split_min_k || chem->max_loop < 2 * k - 4)));
-    // f64, one wave per pair: behind the split kernel, and as the first stage where neither the split
-    // kernel nor the register-table chain applies (29 .. 32 bases, parameter files off the grid)
-    const bool wave_ok = !ctx->opt.force_generic && kmax <= ce->wave_max_k && ctx->opt.wave_kernel;
-    const bool wave_matrix = wave_ok && !split && (rect || k > pairs_fast_max_k() || chem->max_loop < 2 * k - 4);
-    // the register-table / integer / row first stages are square-only: a rectangle that neither the split nor the
-    // wave kernel takes goes to the dense kernel
-    const bool fast = split || wave_matrix ||
-                      (!rect && !ctx->opt.force_generic && k <= pairs_fast_max_k() && ce->fast_ok &&
-                       chem->max_loop >= 2 * k - 4);   // the tuned kernel has no loop-size cut-off
     // the conflict bitmap is produced with atomic ORs: clear the caller's block first
     if (d_bitmap)
         HIP_TRY(ctx, hipMemsetAsync(d_bitmap, 0, sizeof(uint64_t) * (size_t)(row1 - row0) * (size_t)words,
@@ -632,7 +624,7 @@ static int cross_dimer_impl(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k
     g.pool = d_pool;
     g.k = k;
     g.k2 = k2;
-    g.mode = 1;
+    g.mode = end1 ? kModeEnd1 : kModeAny;
     g.sinks = sinks;
     g.wsS = ctx->wsS;
     g.wsH = ctx->wsH;
@@ -668,11 +660,10 @@ static int cross_dimer_impl(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k
             if (gb.sinks.bitmap) gb.sinks.bitmap += roff * (size_t)words;
             if (gb.sinks.dg) gb.sinks.dg += roff * (size_t)ncols;
             if (gb.sinks.tm) gb.sinks.tm += roff * (size_t)ncols;
-            HIP_TRY(ctx, launch_dimer_generic(gb, ctx->stream));
+            HIP_TRY(ctx, launch_dimer_generic(gb, ctx->stream, end1));
         }
         return MSSPE_OK;
     }
-    const bool int_stage = !split && ce->int_ok && !(ctx->opt.pair_kernel == 1);
     if (!wave_matrix) {
         if ((rc = ensure_sort(ctx, (size_t)ncols))) return rc;
         HIP_TRY(ctx, sort_columns_by_composition(d_pool, col0, ncols, k2, ctx->d_sort_scratch,
@@ -682,8 +673,6 @@ static int cross_dimer_impl(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k
     // Overflow pairs are collected over several launches and finished together: the list kernels
     // have a fixed latency floor, and list_cap entries cannot be overrun by list_cap / kChunkPairs
     // launches even if every pair overflowed.
-    // small screens (the reference's are at most 2,000^2): the short chain behind the integer list stage
-    const bool short_chain = wave_ok && ctx->opt.short_chain && (long)(row1 - row0) * (long)ncols <= (1L << 23);
     auto flush = [&]() -> int {
         PairKernelArgs a;
         a.ft = ce->d_ft;
@@ -712,14 +701,14 @@ static int cross_dimer_impl(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k
                 a.overflow_list = out_list;
                 a.overflow_count = ctx->ovf_count + out_c;
                 a.overflow_cap = (uint32_t)kListCap;
-                HIP_TRY(ctx, launch_pairs_wave(a, ce->d_st, in_list, ctx->ovf_count + in_c, ctx->stream));
+                HIP_TRY(ctx, launch_pairs_wave(a, ce->d_st, in_list, ctx->ovf_count + in_c, ctx->stream, end1));
                 in_list = out_list;
                 in_c = out_c;
             }
             g.list = in_list;
             g.list_count = ctx->ovf_count + in_c;
             g.n_work = kListCap;
-            HIP_TRY(ctx, launch_dimer_generic(g, ctx->stream));
+            HIP_TRY(ctx, launch_dimer_generic(g, ctx->stream, end1));
             hipLaunchKernelGGL(k_accumulate_overflow, dim3(1), dim3(64), 0, ctx->stream, ctx->ovf_count,
                                ctx->d_ovf_total, (uint32_t)kListCap);
             HIP_TRY(ctx, hipMemsetAsync(ctx->ovf_count, 0, 8 * sizeof(uint32_t), ctx->stream));
@@ -746,11 +735,11 @@ static int cross_dimer_impl(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k
                 // 0.6 ms whatever its list holds, the wave kernel takes 0.13 ms + 16 ns per pair
                 a.overflow_list = out_list;
                 a.overflow_count = ctx->ovf_count + out_c;
-                HIP_TRY(ctx, launch_pairs_wave(a, ce->d_st, in_list, ctx->ovf_count + in_c, ctx->stream));
+                HIP_TRY(ctx, launch_pairs_wave(a, ce->d_st, in_list, ctx->ovf_count + in_c, ctx->stream, end1));
                 g.list = out_list;
                 g.list_count = ctx->ovf_count + out_c;
                 g.n_work = kListCap;
-                HIP_TRY(ctx, launch_dimer_generic(g, ctx->stream));
+                HIP_TRY(ctx, launch_dimer_generic(g, ctx->stream, end1));
                 hipLaunchKernelGGL(k_accumulate_overflow, dim3(1), dim3(64), 0, ctx->stream, ctx->ovf_count,
                                    ctx->d_ovf_total, (uint32_t)kListCap);
                 HIP_TRY(ctx, hipMemsetAsync(ctx->ovf_count, 0, 8 * sizeof(uint32_t), ctx->stream));
@@ -773,19 +762,19 @@ static int cross_dimer_impl(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k
         a.overflow_list = out_list;
         a.overflow_count = ctx->ovf_count + out_c;
         a.overflow_cap = (uint32_t)kListCap;
-        HIP_TRY(ctx, launch_pairs_wide(a, in_list, ctx->ovf_count + in_c, ctx->stream));
+        HIP_TRY(ctx, launch_pairs_wide(a, in_list, ctx->ovf_count + in_c, ctx->stream, end1));
         if (wave_ok) {
             // huge tables: one wave per pair, the table in LDS
             advance();
             a.overflow_list = out_list;
             a.overflow_count = ctx->ovf_count + out_c;
-            HIP_TRY(ctx, launch_pairs_wave(a, ce->d_st, in_list, ctx->ovf_count + in_c, ctx->stream));
+            HIP_TRY(ctx, launch_pairs_wave(a, ce->d_st, in_list, ctx->ovf_count + in_c, ctx->stream, end1));
         }
         // last stage: whatever is left (both-self-complementary pairs)
         g.list = out_list;
         g.list_count = ctx->ovf_count + out_c;
         g.n_work = kListCap;
-        HIP_TRY(ctx, launch_dimer_generic(g, ctx->stream));
+        HIP_TRY(ctx, launch_dimer_generic(g, ctx->stream, end1));
         hipLaunchKernelGGL(k_accumulate_overflow, dim3(1), dim3(64), 0, ctx->stream, ctx->ovf_count,
                            ctx->d_ovf_total, (uint32_t)kListCap);
         HIP_TRY(ctx, hipMemsetAsync(ctx->ovf_count, 0, 8 * sizeof(uint32_t), ctx->stream));
@@ -833,13 +822,13 @@ static int cross_dimer_impl(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k
             if (wave_matrix) {
                 a.col0 = col0 + (int)q0;   // pool columns, no composition sort
                 a.col1 = col0 + (int)q_end;
-                HIP_TRY(ctx, launch_pairs_wave(a, ce->d_st, nullptr, nullptr, ctx->stream));
+                HIP_TRY(ctx, launch_pairs_wave(a, ce->d_st, nullptr, nullptr, ctx->stream, end1));
             } else if (split) HIP_TRY(ctx, launch_pairs_split(a, ce->d_st, ctx->d_reasons, ctx->opt.split_lanes, ctx->stream));
             else if (int_stage && ce->row_ok && k <= pairs_row_max_k() && ctx->opt.pair_kernel != 2 &&
                      (k > pairs_row_oob_max_k() || (ctx->lds_reads_zero && ctx->opt.row_oob)))
                 HIP_TRY(ctx, launch_pairs_row(a, ce->d_it, ctx->d_reasons, ctx->n_cu, ctx->stream));
             else if (int_stage) HIP_TRY(ctx, launch_pairs_int(a, ce->d_it, ctx->d_reasons, ctx->n_cu, ctx->stream));
-            else HIP_TRY(ctx, launch_pairs_fast(a, ctx->stream));
+            else HIP_TRY(ctx, launch_pairs_fast(a, ctx->stream, end1));
             if (ctx->prof_on)
                 HIP_TRY(ctx, hipEventRecord(ctx->prof_events[ctx->prof_used++].second, ctx->stream));
             pending += launch_pairs;
@@ -847,6 +836,114 @@ static int cross_dimer_impl(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k
     }
     if (pending && (rc = flush())) return rc;
     return MSSPE_OK;
+}
+
+
+static int cross_dimer_impl(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, int k2, const msspe_chem *chem,
+                            float dg_threshold, int row0, int row1, int col0, int col1,
+                            uint32_t *d_row_conflicts, uint64_t *d_bitmap, double *d_dg, double *d_tm,
+                            EdgeRecord *d_edges, unsigned long long *d_edge_count, unsigned long long edge_cap)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!d_pool || !chem || n < 0) return fail(ctx, MSSPE_ERR_ARG, "null pool/chemistry");
+    if (k < 2 || k > 32 || k2 < 2 || k2 > 32) return fail(ctx, MSSPE_ERR_K, "oligo length must be 2..32");
+    if (row0 < 0 || row1 > n || row0 > row1 || col0 < 0 || col1 > n || col0 > col1)
+        return fail(ctx, MSSPE_ERR_ARG, "row/column range outside the pool");
+    if (row0 == row1 || col0 == col1) return MSSPE_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ChemEntry *ce = nullptr;
+    int rc = chem_entry(ctx, *chem, dg_threshold, &ce);
+    if (rc) return rc;
+    // long oligos: exact-integer kernel with a pair's table split over lanes (honours max_loop)
+    // (also short oligos under a loop-size limit the register-table kernels do not implement)
+    // Row and column oligos of different lengths (k2 != k) take the rectangular chain: the split-table kernel
+    // where the longer of the two is within its proven range (a k x k2 table lies inside the square of its longer
+    // side, whose int32 bounds build_split_tables checked), else the wave kernel in matrix mode; then the wave
+    // list stage and the dense kernel.  split_min_k and pair_kernel do not apply there: the register-table,
+    // integer and row-specialised first stages are square-only.
+    const bool rect = k2 != k;
+    const int kmax = std::max(k, k2);
+    const bool split = !ctx->opt.force_generic && kmax <= ce->split_max_k &&
+                       (rect || (!(ctx->opt.pair_kernel == 1) && (k >= ctx->opt.split_min_k || chem->max_loop < 2 * k - 4)));
+    // f64, one wave per pair: behind the split kernel, and as the first stage where neither the split
+    // kernel nor the register-table chain applies (29 .. 32 bases, parameter files off the grid)
+    const bool wave_ok = !ctx->opt.force_generic && kmax <= ce->wave_max_k && ctx->opt.wave_kernel;
+    const bool wave_matrix = wave_ok && !split && (rect || k > pairs_fast_max_k() || chem->max_loop < 2 * k - 4);
+    // the register-table / integer / row first stages are square-only: a rectangle that neither the split nor the
+    // wave kernel takes goes to the dense kernel
+    const bool fast = split || wave_matrix ||
+                      (!rect && !ctx->opt.force_generic && k <= pairs_fast_max_k() && ce->fast_ok &&
+                       chem->max_loop >= 2 * k - 4);   // the tuned kernel has no loop-size cut-off
+    ChainRoute route;
+    route.end1 = false;
+    route.fast = fast;
+    route.split = split;
+    route.wave_ok = wave_ok;
+    route.wave_matrix = wave_matrix;
+    route.int_stage = !split && ce->int_ok && !(ctx->opt.pair_kernel == 1);
+    // small screens (the reference's are at most 2,000^2): the short chain behind the integer list stage
+    route.short_chain = wave_ok && ctx->opt.short_chain && (long)(row1 - row0) * (long)(col1 - col0) <= (1L << 23);
+    return run_chain(ctx, ce, route, d_pool, n, k, k2, row0, row1, col0, col1, d_row_conflicts, d_bitmap, d_dg, d_tm,
+                     d_edges, d_edge_count, edge_cap);
+}
+
+// The END screen (thal END1 for every ordered pair of the block, conflict iff round_fixed_f32(max(0, t), 2) >=
+// tm_threshold): the f64 kernels only.  Equal lengths within the register-table kernels' conditions: k_pairs_fast
+// END1 over composition-sorted columns, then the wide list, the wave list and the dense kernel; everything else
+// (longer oligos, rectangles, small max_loop): the wave kernel in matrix mode where max(k, k2) is within its range,
+// then the dense kernel; where neither first stage applies, the dense kernel takes the block.
+static int cross_dimer_end_impl(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, int k2, const msspe_chem *chem,
+                                float tm_threshold, int row0, int row1, int col0, int col1, uint32_t *d_row_conflicts,
+                                uint64_t *d_bitmap, double *d_dg, double *d_tm, EdgeRecord *d_edges,
+                                unsigned long long *d_edge_count, unsigned long long edge_cap)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!d_pool || !chem || n < 0) return fail(ctx, MSSPE_ERR_ARG, "null pool/chemistry");
+    if (k < 2 || k > 32 || k2 < 2 || k2 > 32) return fail(ctx, MSSPE_ERR_K, "oligo length must be 2..32");
+    if (row0 < 0 || row1 > n || row0 > row1 || col0 < 0 || col1 > n || col0 > col1)
+        return fail(ctx, MSSPE_ERR_ARG, "row/column range outside the pool");
+    if (row0 == row1 || col0 == col1) return MSSPE_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    ChemEntry *ce = nullptr;
+    int rc = chem_entry(ctx, *chem, tm_threshold, &ce, true);
+    if (rc) return rc;
+    const bool reg = k2 == k && !ctx->opt.force_generic && k <= pairs_fast_max_k() && ce->fast_ok &&
+                     chem->max_loop >= 2 * k - 4;   // the tuned kernel has no loop-size cut-off
+    ChainRoute route;
+    route.end1 = true;
+    route.split = false;
+    route.int_stage = false;
+    route.short_chain = false;
+    route.wave_ok = !ctx->opt.force_generic && std::max(k, k2) <= ce->wave_max_k && ctx->opt.wave_kernel;
+    route.wave_matrix = route.wave_ok && !reg;
+    route.fast = reg || route.wave_matrix;
+    return run_chain(ctx, ce, route, d_pool, n, k, k2, row0, row1, col0, col1, d_row_conflicts, d_bitmap, d_dg, d_tm,
+                     d_edges, d_edge_count, edge_cap);
+}
+
+double msspe_t_cut(float tm_threshold) { return t_cut(tm_threshold); }
+
+int msspe_cross_dimer_end_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const msspe_chem *chem,
+                              float tm_threshold, int row0, int row1, int col0, int col1, uint32_t *d_row_conflicts,
+                              uint64_t *d_bitmap, double *d_dg, double *d_tm)
+{
+    return cross_dimer_end_impl(ctx, d_pool, n, k, k, chem, tm_threshold, row0, row1, col0, col1, d_row_conflicts,
+                                d_bitmap, d_dg, d_tm, nullptr, nullptr, 0);
+}
+
+int msspe_cross_dimer_end_edges_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const msspe_chem *chem,
+                                    float tm_threshold, int row0, int row1, int col0, int col1,
+                                    uint32_t *d_row_conflicts, msspe_end_edge_dev *d_edges, uint64_t capacity,
+                                    uint64_t *d_count)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!d_count || (capacity && !d_edges)) return fail(ctx, MSSPE_ERR_ARG, "edge list: null count or buffer");
+    static_assert(sizeof(msspe_end_edge_dev) == sizeof(EdgeRecord), "edge record layouts differ");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMemsetAsync(d_count, 0, sizeof(uint64_t), ctx->stream));
+    return cross_dimer_end_impl(ctx, d_pool, n, k, k, chem, tm_threshold, row0, row1, col0, col1, d_row_conflicts,
+                                nullptr, nullptr, nullptr, reinterpret_cast<EdgeRecord *>(d_edges),
+                                reinterpret_cast<unsigned long long *>(d_count), capacity);
 }
 
 int msspe_profile_enable(msspe_ctx *ctx, int on)
@@ -925,9 +1022,10 @@ namespace {
 // Host-buffer screens: `packed` (uploaded here) is the pool, rows [0, n_rows) of length k against columns
 // [col_base, col_base + n_cols) of length k2.  One pool: col_base 0, n_rows = n_cols = n.  Pool A + pool B back to
 // back: col_base = n_a.  Outputs are dense over the block as in msspe_cross_dimer.
+// end: the END screen (cross_dimer_end_impl, threshold = tm_threshold) instead of thal ANY.
 int cross_dimer_host(msspe_ctx *ctx, const std::vector<uint64_t> &packed, int n_rows, int k, int col_base, int n_cols,
                      int k2, const msspe_chem *chem, float dg_threshold, uint32_t *row_conflicts, uint64_t *bitmap,
-                     double *dg, double *tm)
+                     double *dg, double *tm, bool end = false)
 {
     const int n = (int)packed.size();
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -962,8 +1060,9 @@ int cross_dimer_host(msspe_ctx *ctx, const std::vector<uint64_t> &packed, int n_
     }
     if (dg) TRY_OR_CLEAN(hipMalloc((void **)&d_dg, sizeof(double) * nn));
     if (tm) TRY_OR_CLEAN(hipMalloc((void **)&d_tm, sizeof(double) * nn));
-    int rc = cross_dimer_impl(ctx, d_pool, n, k, k2, chem, dg_threshold, 0, n_rows, col_base, col_base + n_cols, d_rc,
-                              d_bitmap, d_dg, d_tm, nullptr, nullptr, 0);
+    int rc = (end ? cross_dimer_end_impl : cross_dimer_impl)(ctx, d_pool, n, k, k2, chem, dg_threshold, 0, n_rows,
+                                                             col_base, col_base + n_cols, d_rc, d_bitmap, d_dg, d_tm,
+                                                             nullptr, nullptr, 0);
     if (rc) {
         cleanup();
         return rc;
@@ -986,8 +1085,9 @@ int cross_dimer_host(msspe_ctx *ctx, const std::vector<uint64_t> &packed, int n_
 
 // Host edge lists: the first `have` raw edges (indices already mapped by the caller) sorted by (a, b) as the
 // reference's nested loops emit them, with the value Edge::get_dg() yields; MSSPE_ERR_CAPACITY when count > capacity.
+// end: END edges (raw t) as msspe_end_edge, t = round_fixed_f32(max(0, t), 2), the SELF_END text value.
 int emit_sorted_edges(msspe_ctx *ctx, std::vector<msspe_edge_dev> &raw, uint64_t count, uint64_t capacity,
-                      msspe_edge *edges)
+                      msspe_edge *edges, bool end = false)
 {
     std::sort(raw.begin(), raw.end(), [](const msspe_edge_dev &x, const msspe_edge_dev &y) {
         return x.a != y.a ? x.a < y.a : x.b < y.b;
@@ -996,7 +1096,8 @@ int emit_sorted_edges(msspe_ctx *ctx, std::vector<msspe_edge_dev> &raw, uint64_t
         edges[e].a = raw[e].a;
         edges[e].b = raw[e].b;
         // what Edge::get_dg() returns: the %g text as f32, stored as "{:.2}", parsed again (delta_g.rs:10-15, 33-46)
-        edges[e].dg = round_fixed_f32((double)round_g_f32(raw[e].dg), 2);
+        edges[e].dg = end ? round_fixed_f32(raw[e].dg > 0.0 ? raw[e].dg : 0.0, 2)
+                          : round_fixed_f32((double)round_g_f32(raw[e].dg), 2);
     }
     if (count > capacity)
         return fail(ctx, MSSPE_ERR_CAPACITY, "edge list: " + std::to_string(count) + " conflict edges, capacity " +
@@ -1035,10 +1136,11 @@ __global__ void k_edges_shift_b(EdgeRecord *edges, const unsigned long long *cou
         edges[e].b -= shift;
 }
 
+// end: the END screen (cross_dimer_end_impl: A = oligo 1, the anchored 3' end) instead of thal ANY.
 int cross_dimer_ab_impl(msspe_ctx *ctx, const uint64_t *d_a, int n_a, int k_a, const uint64_t *d_b, int n_b, int k_b,
                         const msspe_chem *chem, float dg_threshold, int row0, int row1, int col0, int col1,
                         uint32_t *d_row_conflicts, uint64_t *d_bitmap, double *d_dg, double *d_tm, EdgeRecord *d_edges,
-                        unsigned long long *d_edge_count, unsigned long long edge_cap)
+                        unsigned long long *d_edge_count, unsigned long long edge_cap, bool end = false)
 {
     if (!chem || n_a < 0 || n_b < 0 || (n_a && !d_a) || (n_b && !d_b))
         return fail(ctx, MSSPE_ERR_ARG, "null pool/chemistry");
@@ -1052,8 +1154,9 @@ int cross_dimer_ab_impl(msspe_ctx *ctx, const uint64_t *d_a, int n_a, int k_a, c
     if (rc) return rc;
     // k_a == k_b: the single-pool chain as it is (the 13-mer A x B screen runs on the row kernel); otherwise the
     // rectangular chain
-    rc = cross_dimer_impl(ctx, ctx->d_ab, n_a + n_b, k_a, k_b, chem, dg_threshold, row0, row1, n_a + col0, n_a + col1,
-                          d_row_conflicts, d_bitmap, d_dg, d_tm, d_edges, d_edge_count, edge_cap);
+    rc = (end ? cross_dimer_end_impl : cross_dimer_impl)(ctx, ctx->d_ab, n_a + n_b, k_a, k_b, chem, dg_threshold, row0,
+                                                         row1, n_a + col0, n_a + col1, d_row_conflicts, d_bitmap, d_dg,
+                                                         d_tm, d_edges, d_edge_count, edge_cap);
     if (rc) return rc;
     if (d_edges && edge_cap && n_a) {
         hipLaunchKernelGGL(k_edges_shift_b, dim3(256), dim3(256), 0, ctx->stream, d_edges, d_edge_count, edge_cap,
@@ -1087,9 +1190,10 @@ namespace {
 
 // Host edge lists over the same layout as cross_dimer_host: rows [0, n_rows) of length k against columns
 // [col_base, col_base + n_cols) of length k2; edge b = column index (pool index - col_base).
+// end: the END screen's edges (emit_sorted_edges).
 int cross_dimer_edges_host(msspe_ctx *ctx, const std::vector<uint64_t> &packed, int n_rows, int k, int col_base,
                            int n_cols, int k2, const msspe_chem *chem, float dg_threshold, msspe_edge *edges,
-                           uint64_t capacity, uint64_t *count_out)
+                           uint64_t capacity, uint64_t *count_out, bool end = false)
 {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     uint64_t *d_pool = nullptr, *d_count = nullptr;
@@ -1113,9 +1217,10 @@ int cross_dimer_edges_host(msspe_ctx *ctx, const std::vector<uint64_t> &packed, 
     TRY_OR_CLEAN2(hipMalloc((void **)&d_count, sizeof(uint64_t)));
     if (capacity) TRY_OR_CLEAN2(hipMalloc((void **)&d_edges, sizeof(msspe_edge_dev) * (size_t)capacity));
     TRY_OR_CLEAN2(hipMemsetAsync(d_count, 0, sizeof(uint64_t), ctx->stream));
-    int rc = cross_dimer_impl(ctx, d_pool, n, k, k2, chem, dg_threshold, 0, n_rows, col_base, col_base + n_cols, nullptr,
-                              nullptr, nullptr, nullptr, reinterpret_cast<EdgeRecord *>(d_edges),
-                              reinterpret_cast<unsigned long long *>(d_count), capacity);
+    int rc = (end ? cross_dimer_end_impl : cross_dimer_impl)(ctx, d_pool, n, k, k2, chem, dg_threshold, 0, n_rows,
+                                                             col_base, col_base + n_cols, nullptr, nullptr, nullptr,
+                                                             nullptr, reinterpret_cast<EdgeRecord *>(d_edges),
+                                                             reinterpret_cast<unsigned long long *>(d_count), capacity);
     if (rc) {
         cleanup();
         return rc;
@@ -1135,7 +1240,7 @@ int cross_dimer_edges_host(msspe_ctx *ctx, const std::vector<uint64_t> &packed, 
 #undef TRY_OR_CLEAN2
     for (auto &e : raw) e.b -= (uint32_t)col_base;   // pool index -> column index
     // the kernels append in no particular order
-    return emit_sorted_edges(ctx, raw, count, capacity, edges);
+    return emit_sorted_edges(ctx, raw, count, capacity, edges, end);
 }
 
 }  // namespace
@@ -1218,6 +1323,67 @@ int msspe_cross_dimer_ab_edges(msspe_ctx *ctx, const char *a_ascii, int n_a, int
     if (n_a == 0 || n_b == 0) return MSSPE_OK;
     return cross_dimer_edges_host(ctx, packed, n_a, k_a, n_a, n_b, k_b, chem, dg_threshold, edges, capacity,
                                   count_out);
+}
+
+int msspe_cross_dimer_end(msspe_ctx *ctx, const char *pool_ascii, int n, int k, const msspe_chem *chem,
+                          float tm_threshold, uint32_t *row_conflicts, uint64_t *bitmap, double *dg, double *tm)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!pool_ascii || !chem || n < 0) return fail(ctx, MSSPE_ERR_ARG, "null pool/chemistry");
+    if (n == 0) return MSSPE_OK;
+    std::vector<uint64_t> packed((size_t)n);
+    int rc = msspe_pack_oligos(pool_ascii, n, k, packed.data());
+    if (rc) return fail(ctx, rc, rc == MSSPE_ERR_K ? "oligo length must be 1..32"
+                                                   : "pool holds characters other than ACGT");
+    return cross_dimer_host(ctx, packed, n, k, 0, n, k, chem, tm_threshold, row_conflicts, bitmap, dg, tm, true);
+}
+
+int msspe_cross_dimer_end_edges(msspe_ctx *ctx, const char *pool_ascii, int n, int k, const msspe_chem *chem,
+                                float tm_threshold, msspe_end_edge *edges, uint64_t capacity, uint64_t *count_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!pool_ascii || !chem || !count_out || n < 0 || (capacity && !edges))
+        return fail(ctx, MSSPE_ERR_ARG, "null pool/chemistry/count, or a capacity without a buffer");
+    *count_out = 0;
+    if (n == 0) return MSSPE_OK;
+    std::vector<uint64_t> packed((size_t)n);
+    int rc = msspe_pack_oligos(pool_ascii, n, k, packed.data());
+    if (rc) return fail(ctx, rc, rc == MSSPE_ERR_K ? "oligo length must be 1..32"
+                                                   : "pool holds characters other than ACGT");
+    static_assert(sizeof(msspe_end_edge) == sizeof(msspe_edge), "edge record layouts differ");
+    return cross_dimer_edges_host(ctx, packed, n, k, 0, n, k, chem, tm_threshold,
+                                  reinterpret_cast<msspe_edge *>(edges), capacity, count_out, true);
+}
+
+int msspe_cross_dimer_end_ab_dev(msspe_ctx *ctx, const uint64_t *d_a, int n_a, int k_a, const uint64_t *d_b, int n_b,
+                                 int k_b, const msspe_chem *chem, float tm_threshold, int row0, int row1, int col0,
+                                 int col1, uint32_t *d_row_conflicts, uint64_t *d_bitmap, double *d_dg, double *d_tm)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    return cross_dimer_ab_impl(ctx, d_a, n_a, k_a, d_b, n_b, k_b, chem, tm_threshold, row0, row1, col0, col1,
+                               d_row_conflicts, d_bitmap, d_dg, d_tm, nullptr, nullptr, 0, true);
+}
+
+int msspe_cross_dimer_end_ab(msspe_ctx *ctx, const char *a_ascii, int n_a, int k_a, const char *b_ascii, int n_b,
+                             int k_b, const msspe_chem *chem, float tm_threshold, uint32_t *row_conflicts,
+                             uint64_t *bitmap, double *dg, double *tm)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!chem || n_a < 0 || n_b < 0 || (n_a && !a_ascii) || (n_b && !b_ascii))
+        return fail(ctx, MSSPE_ERR_ARG, "null pool/chemistry");
+    if (k_a < 2 || k_a > 32 || k_b < 2 || k_b > 32) return fail(ctx, MSSPE_ERR_K, "oligo length must be 2..32");
+    if ((long)n_a + (long)n_b > (long)INT32_MAX) return fail(ctx, MSSPE_ERR_ARG, "pools too large");
+    std::vector<uint64_t> packed((size_t)n_a + (size_t)n_b);
+    if (msspe_pack_oligos(a_ascii ? a_ascii : "", n_a, k_a, packed.data()) ||
+        msspe_pack_oligos(b_ascii ? b_ascii : "", n_b, k_b, packed.data() + n_a))
+        return fail(ctx, MSSPE_ERR_ARG, "pool holds characters other than ACGT");
+    if (n_a == 0) return MSSPE_OK;
+    if (n_b == 0) {   // no columns: no conflicts
+        if (row_conflicts) std::fill(row_conflicts, row_conflicts + n_a, 0u);
+        return MSSPE_OK;
+    }
+    return cross_dimer_host(ctx, packed, n_a, k_a, n_a, n_b, k_b, chem, tm_threshold, row_conflicts, bitmap, dg, tm,
+                            true);
 }
 
 int msspe_cross_dimer_edges_mixed(msspe_ctx *ctx, const char *const *oligos, int n, const msspe_chem *chem,

@@ -67,7 +67,10 @@ struct GenericDimerArgs {
     double *wsS, *wsH;         // workspace planes, [cell][lane], lanes = ws_lanes (k * k2 cells per lane)
     size_t ws_lanes;
 };
-hipError_t launch_dimer_generic(const GenericDimerArgs &a, hipStream_t stream);
+// end1: the END screen -- thal END1 on ordinary pairs (list or matrix mode, mode is ignored) and the t decision: conflict
+// iff max(0, t) > c[].g_cut, which then holds the t cut (msspe_t_cut); edges record the raw t.  Self and detail work
+// runs with end1 = false.
+hipError_t launch_dimer_generic(const GenericDimerArgs &a, hipStream_t stream, bool end1 = false);
 
 // Generic hairpin kernel: one lane per oligo; out_t[w] = max(0, t).
 struct HairpinArgs {
@@ -108,7 +111,8 @@ struct PairKernelArgs {
     uint32_t overflow_cap;
     uint32_t *work_counter;        // device word for the integer first stage's work queue (launch_pairs_int)
 };
-hipError_t launch_pairs_fast(const PairKernelArgs &a, hipStream_t stream);
+// end1 (here and in launch_pairs_wide / launch_pairs_wave): the END screen's instantiation, as launch_dimer_generic.
+hipError_t launch_pairs_fast(const PairKernelArgs &a, hipStream_t stream, bool end1 = false);
 // The main table over an explicit pair list (what the integer stage handed on); pairs that do not
 // fit are appended to a.overflow_list.
 hipError_t launch_pairs_main_list(const PairKernelArgs &a, const uint2 *in_list,
@@ -116,7 +120,7 @@ hipError_t launch_pairs_main_list(const PairKernelArgs &a, const uint2 *in_list,
 // Wide instantiation over an explicit pair list (the overflow list of launch_pairs_fast); pairs
 // that still do not fit are appended to a.overflow_list.
 hipError_t launch_pairs_wide(const PairKernelArgs &a, const uint2 *in_list,
-                             const uint32_t *in_count, hipStream_t stream);
+                             const uint32_t *in_count, hipStream_t stream, bool end1 = false);
 // Exact-integer first stage (thal_pairs_int.hip): same contract as launch_pairs_fast; pairs it does
 // not answer (ties, oversized tables) are appended to a.overflow_list.  reasons: optional device
 // counters [8] ([0] = pairs handed on because of a tie, [1 + b] = reason bit b, see the kernel).
@@ -146,7 +150,7 @@ int pairs_split_lanes(int k);
 // pool columns [a.col0, a.col1).  Pairs it does not take (two self-complementary oligos, oversized
 // tables) are appended to a.overflow_list for launch_dimer_generic.
 hipError_t launch_pairs_wave(const PairKernelArgs &a, const SplitTables *st, const uint2 *in_list,
-                             const uint32_t *in_count, hipStream_t stream);
+                             const uint32_t *in_count, hipStream_t stream, bool end1 = false);
 // Stage B on the same kernel: thal ANY and / or END1 of oligos with themselves from one fill per oligo,
 // self_any[row] / self_end[row] = max(0, t) (either may be null); the oligos are [row0, row1) or, with in_list, the
 // entries' .x; what it does not take is appended to list as (row, row).

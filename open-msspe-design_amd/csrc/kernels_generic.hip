@@ -25,7 +25,28 @@ __device__ __forceinline__ void sink_pair(const PairSinks &s, const ThalConsts &
     }
 }
 
-__global__ void __launch_bounds__(256) k_dimer_generic(GenericDimerArgs a)
+// The END screen's sink: thal END1 ran; conflict iff t_end = max(0, t), 0 without a structure, lies above the t
+// cut that arrives in c.g_cut (msspe_t_cut); an edge records the raw t.
+__device__ __forceinline__ void sink_pair_end(const PairSinks &s, const ThalConsts &c, int row, int col,
+                                              const ThalOut &o)
+{
+    const double t = o.none ? 0.0 : o.t;
+    const bool conflict = (t > 0.0 ? t : 0.0) > c.g_cut;
+    const size_t r = (size_t)(row - s.row0), q = (size_t)(col - s.col0);
+    if (s.dg) s.dg[r * (size_t)s.ncols + q] = o.none ? INFINITY : o.dG;
+    if (s.tm) s.tm[r * (size_t)s.ncols + q] = t;
+    if (conflict) {
+        if (s.row_conflicts) atomicAdd(&s.row_conflicts[row], 1u);
+        if (s.bitmap)
+            atomicOr((unsigned long long *)&s.bitmap[r * (size_t)s.words + (q >> 6)],
+                     1ull << (q & 63));
+        sink_edge(s, row, col, t);
+    }
+}
+
+// END: the END screen (cross pairs, mode kModeEnd1, sink_pair_end); otherwise a.mode and sink_pair
+template <bool END>
+__device__ __forceinline__ void dimer_generic_body(GenericDimerArgs a)
 {
     const size_t lane = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     long n_work = a.n_work;
@@ -57,7 +78,7 @@ __global__ void __launch_bounds__(256) k_dimer_generic(GenericDimerArgs a)
         if (det) {
             for (int q = 0; q < 32; ++q) det->ps1[q] = det->ps2[q] = 0;
         }
-        ctx.run(a.mode, o, det);
+        ctx.run(END ? kModeEnd1 : a.mode, o, det);
         if (det) {
             det->dS = o.dS;
             det->dH = o.dH;
@@ -67,11 +88,17 @@ __global__ void __launch_bounds__(256) k_dimer_generic(GenericDimerArgs a)
             det->n_pairs = o.n_pairs;
         } else if (a.self_mode) {
             a.self_t[row] = (o.none || o.t < 0.0) ? 0.0 : o.t;   // libprimer3 align_thermod()
+        } else if (END) {
+            sink_pair_end(a.sinks, ctx.c, row, col, o);
         } else {
             sink_pair(a.sinks, ctx.c, row, col, o);
         }
     }
 }
+
+__global__ void __launch_bounds__(256) k_dimer_generic(GenericDimerArgs a) { dimer_generic_body<false>(a); }
+
+__global__ void __launch_bounds__(256) k_dimer_generic_end(GenericDimerArgs a) { dimer_generic_body<true>(a); }
 
 __global__ void __launch_bounds__(256) k_hairpin_generic(HairpinArgs a)
 {
@@ -127,14 +154,15 @@ __global__ void __launch_bounds__(256) k_oligo_tm(const uint64_t *pool, int n, i
 
 }  // namespace
 
-hipError_t launch_dimer_generic(const GenericDimerArgs &a, hipStream_t stream)
+hipError_t launch_dimer_generic(const GenericDimerArgs &a, hipStream_t stream, bool end1)
 {
     if (a.n_work <= 0) return hipSuccess;
     const int block = 256;
     const long lanes = (long)a.ws_lanes;
     long want = a.n_work < lanes ? a.n_work : lanes;
     const int grid = (int)((want + block - 1) / block);
-    hipLaunchKernelGGL(k_dimer_generic, dim3(grid), dim3(block), 0, stream, a);
+    if (end1) hipLaunchKernelGGL(k_dimer_generic_end, dim3(grid), dim3(block), 0, stream, a);
+    else hipLaunchKernelGGL(k_dimer_generic, dim3(grid), dim3(block), 0, stream, a);
     return hipGetLastError();
 }
 

@@ -450,6 +450,24 @@ double g_cut(float threshold)
     return from_key(lo);
 }
 
+double t_cut(float threshold)
+{
+    // The END screen flags a pair unless the "%.2f" text of t_end, parsed as f32, is below the threshold (od-msspe's
+    // SELF_END rule, primer.rs:94-106 and main.rs:498-499, applied to a pair).  That rounding is monotone: return
+    // the largest double for which the text is below, so that the kernels can test t_end > cut.  Thresholds <= 0
+    // (and NaN) give a cut below 0: every pair conflicts.
+    auto below = [&](double x) { return round_fixed_f32(x, 2) < threshold; };
+    uint64_t lo = ordered_key(-DBL_MAX), hi = ordered_key(DBL_MAX);
+    if (!below(from_key(lo))) return -INFINITY;
+    if (below(from_key(hi))) return DBL_MAX;
+    while (hi - lo > 1) {   // invariant: below(lo) true, below(hi) false
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (below(from_key(mid))) lo = mid;
+        else hi = mid;
+    }
+    return from_key(lo);
+}
+
 // The compact S / H planes shared by FastTables and SplitTables (same layout, other loop-size
 // range): T provides the k* offsets, kMaxSz, S[] and H[].
 template <class T>

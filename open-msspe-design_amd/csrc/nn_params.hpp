@@ -42,7 +42,8 @@ struct ThalConsts {
     double RC;              // R ln(C/4e9) for duplexes of non-self-complementary oligos, 0 for hairpins
     double salt;            // 0.368 ln((mv + 120 sqrt(max(0, dv - dntp))) / 1000)
     double temp_k;          // temperature dG is reported at
-    double g_cut;           // conflict iff dG <= g_cut (== "%g -> f32 < threshold", exact)
+    double g_cut;           // conflict iff dG <= g_cut (== "%g -> f32 < threshold", exact); the END screen's
+                            // entries hold t_cut here: conflict iff max(0, t) > it
     int max_loop;
 };
 ThalConsts make_dimer_consts(double mv, double dv, double dntp, double dna_conc, double temp_c,
@@ -79,5 +80,6 @@ void end_term(const NNTables &t, const ThalConsts &c, int a, int b, int oa, int 
 float round_g_f32(double x);
 float round_fixed_f32(double x, int decimals);
 double g_cut(float threshold);
+double t_cut(float threshold);   // largest x with round_fixed_f32(x, 2) < threshold (the END screen's cut)
 
 }  // namespace msspe

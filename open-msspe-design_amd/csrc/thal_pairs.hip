@@ -423,14 +423,23 @@ __device__ __forceinline__ PairResult finish_pair(const Lds &T, const ThalConsts
     return r;
 }
 
-// The whole thal ANY computation for the lane's pair.
-template <int NREG, int NEXT>
+// The whole thal ANY (or END1) computation for the lane's pair.
+template <int NREG, int NEXT, bool END1 = false>
 __device__ __forceinline__ PairResult run_pair(const Lds &T, const ThalConsts &K, const SeqPair &q,
                                                unsigned rowmask, int n_cells, int nmax,
                                                Slots<NREG, NEXT> &st)
 {
     fill_pair<NREG, NEXT>(T, K, q, rowmask, nmax, st);
-    return finish_pair<NREG, NEXT, false>(T, K, q, n_cells, nmax, st);
+    return finish_pair<NREG, NEXT, END1>(T, K, q, n_cells, nmax, st);
+}
+
+// The END screen's decision (od-msspe's SELF_END rule applied to a pair): conflict iff t_end = max(0, t), 0 without
+// a structure, lies above the t cut, which the END kernels receive in K.g_cut (msspe_t_cut).  The value an END edge
+// records is the raw t.
+__device__ __forceinline__ bool end_conflict(const PairResult &r, const ThalConsts &K)
+{
+    const double t_end = (r.none || !(r.t > 0.0)) ? 0.0 : r.t;
+    return t_end > K.g_cut;
 }
 
 __device__ __forceinline__ void load_tables(Lds &T, const FastTables *ft)
@@ -444,8 +453,9 @@ __device__ __forceinline__ void load_tables(Lds &T, const FastTables *ft)
 
 // Matrix mode: wave = one row x 64 consecutive entries of the composition-sorted column list.
 // col0/col1 index that sorted list; perm[] maps an entry back to its pool index for the outputs.
-template <int NREG, int NEXT, int WAVES>
-__global__ void __launch_bounds__(256, WAVES) k_pairs_fast(FastArgs a)
+// END1: thal END1 pick and the t decision (end_conflict) instead of ANY and the dG decision.
+template <int NREG, int NEXT, bool END1>
+__device__ __forceinline__ void fast_body(FastArgs a)
 {
     // one LDS object with the tables FIRST: their byte offsets stay below 64 KB, so every table
     // gather folds its array base into the ds_read immediate offset
@@ -485,17 +495,17 @@ __global__ void __launch_bounds__(256, WAVES) k_pairs_fast(FastArgs a)
         }
         if (!inside | spill) n_cells = 0;
         const int nmax = wave_max(n_cells);
-        const PairResult r = run_pair<NREG, NEXT>(T, a.c, q, rowmask, n_cells, nmax, st);
+        const PairResult r = run_pair<NREG, NEXT, END1>(T, a.c, q, rowmask, n_cells, nmax, st);
         // ---- sinks (conflicts are rare: one atomic OR per conflicting pair, one add per wave)
         const bool live = inside & !spill;
-        const bool hit = live & r.conflict;
+        const bool hit = live & (END1 ? end_conflict(r, a.c) : r.conflict);
         const unsigned long long bits = __ballot(hit);
         const size_t orow = (size_t)(row - a.sinks.row0);
         const size_t ocol = (size_t)(col - a.sinks.col0);
         if (hit && a.sinks.bitmap)
             atomicOr((unsigned long long *)&a.sinks.bitmap[orow * (size_t)a.sinks.words + (ocol >> 6)],
                      1ull << (ocol & 63));
-        if (hit) sink_edge(a.sinks, row, col, r.dG);
+        if (hit) sink_edge(a.sinks, row, col, END1 ? r.t : r.dG);
         if (lane == 0 && a.sinks.row_conflicts && bits)
             atomicAdd(&a.sinks.row_conflicts[row], (unsigned)__popcll(bits));
         if (live) {
@@ -505,12 +515,25 @@ __global__ void __launch_bounds__(256, WAVES) k_pairs_fast(FastArgs a)
     }
 }
 
+template <int NREG, int NEXT, int WAVES>
+__global__ void __launch_bounds__(256, WAVES) k_pairs_fast(FastArgs a)
+{
+    fast_body<NREG, NEXT, false>(a);
+}
+
+template <int NREG, int NEXT, int WAVES>
+__global__ void __launch_bounds__(256, WAVES) k_pairs_fast_end(FastArgs a)
+{
+    fast_body<NREG, NEXT, true>(a);
+}
+
 // List mode: lane = one explicit pair (the list a previous stage left behind).  THREADS-wide
 // blocks: 40 register slots + NEXT * 8 LDS slots per lane, two blocks per CU.
 // SELF (stage B, od-msspe/src/primer.rs:143-166: PRIMER_LEFT_0_SELF_ANY_TH / SELF_END_TH of libprimer3's
 // oligo_compl_thermod): the entries are (i, i); ONE fill serves thal ANY and thal END1, each finished on its own
 // (finish_pair), self_any[i] / self_end[i] = max(0, t) (either may be null).
-template <int NREG, int NEXT, int THREADS, bool SELF>
+// END1 (cross pairs only): thal END1 pick and the t decision, as fast_body.
+template <int NREG, int NEXT, int THREADS, bool SELF, bool END1 = false>
 __device__ __forceinline__ void list_body(const FastArgs &a, double *self_any, double *self_end)
 {
     struct Shared {
@@ -629,18 +652,18 @@ __device__ __forceinline__ void list_body(const FastArgs &a, double *self_any, d
                 }
                 continue;
             }
-            const PairResult r = run_pair<NREG, NEXT>(T, a.c, q, rowmask, n_cells, nmax, st);
+            const PairResult r = run_pair<NREG, NEXT, END1>(T, a.c, q, rowmask, n_cells, nmax, st);
             if (inside & !spill) {
                 const size_t orow = (size_t)((int)pr.x - a.sinks.row0);
                 const size_t ocol = (size_t)((int)pr.y - a.sinks.col0);
                 if (a.sinks.dg) a.sinks.dg[orow * (size_t)a.sinks.ncols + ocol] = r.dG;
                 if (a.sinks.tm) a.sinks.tm[orow * (size_t)a.sinks.ncols + ocol] = r.t;
-                if (r.conflict) {
+                if (END1 ? end_conflict(r, a.c) : r.conflict) {
                     if (a.sinks.row_conflicts) atomicAdd(&a.sinks.row_conflicts[pr.x], 1u);
                     if (a.sinks.bitmap)
                         atomicOr((unsigned long long *)&a.sinks.bitmap[orow * (size_t)a.sinks.words + (ocol >> 6)],
                                  1ull << (ocol & 63));
-                    sink_edge(a.sinks, (int)pr.x, (int)pr.y, r.dG);
+                    sink_edge(a.sinks, (int)pr.x, (int)pr.y, END1 ? r.t : r.dG);
                 }
             }
         }
@@ -652,6 +675,12 @@ template <int NREG, int NEXT, int THREADS>
 __global__ void __launch_bounds__(THREADS, THREADS / 128) k_pairs_list(FastArgs a)
 {
     list_body<NREG, NEXT, THREADS, false>(a, nullptr, nullptr);
+}
+
+template <int NREG, int NEXT, int THREADS>
+__global__ void __launch_bounds__(THREADS, THREADS / 128) k_pairs_list_end(FastArgs a)
+{
+    list_body<NREG, NEXT, THREADS, false, true>(a, nullptr, nullptr);
 }
 
 template <int NREG, int NEXT, int THREADS>
@@ -681,7 +710,7 @@ int pairs_fast_max_k() { return 16; }
 int pairs_fast_main_slots() { return kNchMain * kChunk; }
 int pairs_fast_wide_slots() { return kNchWide * kChunk; }
 
-hipError_t launch_pairs_fast(const PairKernelArgs &a, hipStream_t stream)
+hipError_t launch_pairs_fast(const PairKernelArgs &a, hipStream_t stream, bool end1)
 {
     FastArgs f;
     f.ft = a.ft;
@@ -703,7 +732,8 @@ hipError_t launch_pairs_fast(const PairKernelArgs &a, hipStream_t stream)
     const long tiles = (long)((a.col1 - a.col0 + 63) / 64) * (long)((a.row1 - a.row0 + 3) / 4);
     if (tiles <= 0) return hipSuccess;
     const int grid = (int)(tiles < 256L * 8 ? tiles : 256L * 8);
-    hipLaunchKernelGGL((k_pairs_fast<kNregMain, kNextMain, 2>), dim3(grid), dim3(256), 0, stream, f);
+    if (end1) hipLaunchKernelGGL((k_pairs_fast_end<kNregMain, kNextMain, 2>), dim3(grid), dim3(256), 0, stream, f);
+    else hipLaunchKernelGGL((k_pairs_fast<kNregMain, kNextMain, 2>), dim3(grid), dim3(256), 0, stream, f);
     return hipGetLastError();
 }
 
@@ -770,7 +800,7 @@ hipError_t launch_self_lists(const FastTables *ft, const ThalConsts &c, const ui
 }
 
 hipError_t launch_pairs_wide(const PairKernelArgs &a, const uint2 *in_list,
-                             const uint32_t *in_count, hipStream_t stream)
+                             const uint32_t *in_count, hipStream_t stream, bool end1)
 {
     FastArgs f;
     f.ft = a.ft;
@@ -789,7 +819,8 @@ hipError_t launch_pairs_wide(const PairKernelArgs &a, const uint2 *in_list,
     f.ovf_cap = a.overflow_cap;
     f.in_list = in_list;
     f.in_count = in_count;
-    hipLaunchKernelGGL((k_pairs_list<kNregWide, kNextWide, 128>), dim3(256 * 4), dim3(128), 0, stream, f);
+    if (end1) hipLaunchKernelGGL((k_pairs_list_end<kNregWide, kNextWide, 128>), dim3(256 * 4), dim3(128), 0, stream, f);
+    else hipLaunchKernelGGL((k_pairs_list<kNregWide, kNextWide, 128>), dim3(256 * 4), dim3(128), 0, stream, f);
     return hipGetLastError();
 }
 

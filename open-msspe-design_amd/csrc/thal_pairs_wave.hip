@@ -294,7 +294,10 @@ __device__ void finish_pair_wave(const SharedWv &sh, int wave, const ThalConsts 
     }
 }
 
-__global__ void __launch_bounds__(kThreadsW) k_pairs_wave(WaveArgs a)
+// END1 (cross pairs; the END screen, msspe_cross_dimer_end*): thal END1 pick, and conflict iff t_end = max(0, t), 0
+// without a structure, lies above the t cut that arrives in a.c.g_cut; an edge records the raw t.
+template <bool END1>
+__device__ __forceinline__ void wave_body(WaveArgs a)
 {
     __shared__ SharedWv sh;
     for (int e = threadIdx.x; e < W_::kCount; e += kThreadsW) {
@@ -304,7 +307,7 @@ __global__ void __launch_bounds__(kThreadsW) k_pairs_wave(WaveArgs a)
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long ncols = a.col1 - a.col0;
-    const bool self = a.self_any || a.self_end;
+    const bool self = !END1 && (a.self_any || a.self_end);
     const long n_work = a.in_list ? (long)min(*a.in_count, a.in_cap)
                                   : (self ? (long)(a.row1 - a.row0) : (long)(a.row1 - a.row0) * ncols);
     for (;;) {
@@ -336,7 +339,7 @@ __global__ void __launch_bounds__(kThreadsW) k_pairs_wave(WaveArgs a)
         const bool fits = n_cells >= 0;
         WaveResult r_end = r;
         if (n_cells > 0) {
-            if (!self || a.self_any) finish_pair_wave(sh, wave, a.c, q, n_cells, false, r);
+            if (!self || a.self_any) finish_pair_wave(sh, wave, a.c, q, n_cells, END1, r);
             if (self && a.self_end) finish_pair_wave(sh, wave, a.c, q, n_cells, true, r_end);
         }
         // lane 0 reports; no lane may run ahead into the next fetch (readfirstlane reads the first
@@ -351,12 +354,13 @@ __global__ void __launch_bounds__(kThreadsW) k_pairs_wave(WaveArgs a)
             } else {
                 const size_t orow = (size_t)(row - a.sinks.row0);
                 const size_t ocol = (size_t)(col - a.sinks.col0);
+                if constexpr (END1) r.conflict = ((r.none || !(r.t > 0.0)) ? 0.0 : r.t) > a.c.g_cut;
                 if (r.conflict) {
                     if (a.sinks.bitmap)
                         atomicOr((unsigned long long *)&a.sinks.bitmap[orow * (size_t)a.sinks.words + (ocol >> 6)],
                                  1ull << (ocol & 63));
                     if (a.sinks.row_conflicts) atomicAdd(&a.sinks.row_conflicts[row], 1u);
-                    sink_edge(a.sinks, row, col, r.dG);
+                    sink_edge(a.sinks, row, col, END1 ? r.t : r.dG);
                 }
                 if (a.sinks.dg) a.sinks.dg[orow * (size_t)a.sinks.ncols + ocol] = r.dG;
                 if (a.sinks.tm) a.sinks.tm[orow * (size_t)a.sinks.ncols + ocol] = r.t;
@@ -366,11 +370,15 @@ __global__ void __launch_bounds__(kThreadsW) k_pairs_wave(WaveArgs a)
     }
 }
 
+__global__ void __launch_bounds__(kThreadsW) k_pairs_wave(WaveArgs a) { wave_body<false>(a); }
+
+__global__ void __launch_bounds__(kThreadsW) k_pairs_wave_end(WaveArgs a) { wave_body<true>(a); }
+
 }  // namespace
 
 // in_list == nullptr: matrix mode over rows [a.row0, a.row1) x pool columns [a.col0, a.col1).
 hipError_t launch_pairs_wave(const PairKernelArgs &a, const SplitTables *st, const uint2 *in_list,
-                             const uint32_t *in_count, hipStream_t stream)
+                             const uint32_t *in_count, hipStream_t stream, bool end1)
 {
     WaveArgs x;
     x.st = st;
@@ -393,7 +401,8 @@ hipError_t launch_pairs_wave(const PairKernelArgs &a, const SplitTables *st, con
     x.work_counter = a.work_counter;
     if (!in_list && ((long)(a.row1 - a.row0) * (long)(a.col1 - a.col0) <= 0)) return hipSuccess;
     if (hipError_t e = hipMemsetAsync(a.work_counter, 0, sizeof(unsigned), stream); e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_pairs_wave, dim3(256 * 2), dim3(kThreadsW), 0, stream, x);
+    if (end1) hipLaunchKernelGGL(k_pairs_wave_end, dim3(256 * 2), dim3(kThreadsW), 0, stream, x);
+    else hipLaunchKernelGGL(k_pairs_wave, dim3(256 * 2), dim3(kThreadsW), 0, stream, x);
     return hipGetLastError();
 }
 

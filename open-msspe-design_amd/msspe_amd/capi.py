@@ -19,6 +19,8 @@ EXPORTS = [
     "msspe_cross_dimer_edges_dev", "msspe_cross_dimer_edges",
     "msspe_cross_dimer_ab_dev", "msspe_cross_dimer_ab_edges_dev", "msspe_cross_dimer_ab", "msspe_cross_dimer_ab_edges",
     "msspe_cross_dimer_edges_mixed",
+    "msspe_cross_dimer_end_dev", "msspe_cross_dimer_end", "msspe_cross_dimer_end_edges_dev", "msspe_cross_dimer_end_edges",
+    "msspe_cross_dimer_end_ab_dev", "msspe_cross_dimer_end_ab", "msspe_t_cut",
     "msspe_last_overflow_pairs", "msspe_pair_stage_stats", "msspe_pair_stage_samples", "msspe_host_pair_tables", "msspe_host_split_tables", "msspe_device_put_rows", "msspe_segment_coverage", "msspe_segment_coverage_dev",
     "msspe_device_put", "msspe_device_free", "msspe_thal_detail_pairs", "msspe_profile_enable", "msspe_profile_read",
     "msspe_oligo_stats_dev", "msspe_oligo_stats",
@@ -141,6 +143,12 @@ def load_library() -> C.CDLL:
                                              C.POINTER(Chem), C.c_float, vp, C.c_uint64, C.POINTER(C.c_uint64)]
     L.msspe_cross_dimer_edges_mixed.argtypes = [vp, C.POINTER(C.c_char_p), C.c_int, C.POINTER(Chem), C.c_float, vp,
                                                 C.c_uint64, C.POINTER(C.c_uint64)]
+    L.msspe_cross_dimer_end_dev.argtypes = L.msspe_cross_dimer_dev.argtypes
+    L.msspe_cross_dimer_end.argtypes = L.msspe_cross_dimer.argtypes
+    L.msspe_cross_dimer_end_edges_dev.argtypes = L.msspe_cross_dimer_edges_dev.argtypes
+    L.msspe_cross_dimer_end_edges.argtypes = L.msspe_cross_dimer_edges.argtypes
+    L.msspe_cross_dimer_end_ab_dev.argtypes = L.msspe_cross_dimer_ab_dev.argtypes
+    L.msspe_cross_dimer_end_ab.argtypes = L.msspe_cross_dimer_ab.argtypes
     L.msspe_last_overflow_pairs.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.msspe_pair_stage_stats.argtypes = [vp, C.POINTER(C.c_uint64)]   # out[16]
     L.msspe_pair_stage_samples.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int, C.POINTER(C.c_int)]
@@ -168,6 +176,8 @@ def load_library() -> C.CDLL:
     L.msspe_round_fixed_f32.argtypes = [C.c_double, C.c_int]
     L.msspe_g_cut.restype = C.c_double
     L.msspe_g_cut.argtypes = [C.c_float]
+    L.msspe_t_cut.restype = C.c_double
+    L.msspe_t_cut.argtypes = [C.c_float]
     _lib = L
     return L
 
@@ -206,6 +216,15 @@ def round_fixed_f32(x: float, decimals: int) -> float:
 
 def g_cut(threshold: float) -> float:
     return float(load_library().msspe_g_cut(C.c_float(threshold)))
+
+
+def t_cut(tm_threshold: float) -> float:
+    """The END screen's cut: the largest x with round_fixed_f32(x, 2) < tm_threshold (msspe_t_cut)."""
+    return float(load_library().msspe_t_cut(C.c_float(tm_threshold)))
+
+
+# PRIMER_MAX_SELF_END_TH, the SELF_END limit od-msspe applies to each primer: the END screen's default
+END_TM_THRESHOLD = 47.0
 
 
 def _ascii(oligos):
@@ -403,6 +422,94 @@ class Engine:
             err.edges = edges
             raise err
         return edges[:count.value], int(count.value)
+
+    # ---- stage C, 3'-end dimers (thal END1 for every ordered pair; include/msspe_hip.h msspe_cross_dimer_end*) ------
+    def cross_dimer_end(self, pool, chem: Chem | None = None, tm_threshold: float = END_TM_THRESHOLD,
+                        want_dg=True, want_tm=True, want_bitmap=True):
+        """END screen of the whole pool (msspe_cross_dimer_end): dict(row_conflicts, bitmap, dg, tm); row i is oligo 1,
+        the anchored 3' end.  A pair conflicts iff round_fixed_f32(max(0, t), 2) >= tm_threshold."""
+        buf, n, k = _ascii(pool)
+        chem = chem or Chem.ntthal()
+        rc_ = np.zeros(n, dtype=np.uint32)
+        bm = np.zeros((n, (n + 63) // 64), dtype=np.uint64) if want_bitmap else None
+        dg = np.empty((n, n)) if want_dg else None
+        tm = np.empty((n, n)) if want_tm else None
+        self._check(self.L.msspe_cross_dimer_end(
+            self.ptr, buf, n, k, C.byref(chem), C.c_float(tm_threshold), rc_.ctypes.data,
+            bm.ctypes.data if want_bitmap else None, dg.ctypes.data if want_dg else None,
+            tm.ctypes.data if want_tm else None))
+        return {"row_conflicts": rc_, "bitmap": bm, "dg": dg, "tm": tm}
+
+    def cross_dimer_end_dev(self, d_pool: int, n: int, k: int, chem: Chem, tm_threshold: float,
+                            rows: tuple[int, int], cols: tuple[int, int], d_row_conflicts: int = 0,
+                            d_bitmap: int = 0, d_dg: int = 0, d_tm: int = 0):
+        """Device-pointer END screen of a block (msspe_cross_dimer_end_dev); asynchronous."""
+        self._check(self.L.msspe_cross_dimer_end_dev(
+            self.ptr, C.c_void_p(d_pool), n, k, C.byref(chem), C.c_float(tm_threshold),
+            rows[0], rows[1], cols[0], cols[1], C.c_void_p(d_row_conflicts),
+            C.c_void_p(d_bitmap), C.c_void_p(d_dg), C.c_void_p(d_tm)))
+
+    def cross_dimer_end_edges(self, pool, chem: Chem | None = None, tm_threshold: float = END_TM_THRESHOLD,
+                              capacity: int = 1 << 20):
+        """END edge list of the whole pool (msspe_cross_dimer_end_edges): (edges [a, b, t] sorted by (a, b), t =
+        round_fixed_f32(max(0, t), 2), count); raises MsspeError (MSSPE_ERR_CAPACITY, .count = edges needed) when
+        the capacity is too small."""
+        buf, n, k = _ascii(pool)
+        chem = chem or Chem.ntthal()
+        edges = np.zeros(capacity, dtype=np.dtype([("a", np.uint32), ("b", np.uint32), ("t", np.float32)]))
+        count = C.c_uint64()
+        rc = self.L.msspe_cross_dimer_end_edges(self.ptr, buf, n, k, C.byref(chem), C.c_float(tm_threshold),
+                                                edges.ctypes.data, capacity, C.byref(count))
+        if rc:
+            err = MsspeError(rc, self.L.msspe_last_error(self.ptr).decode())
+            err.count = int(count.value)
+            err.edges = edges
+            raise err
+        return edges[:count.value], int(count.value)
+
+    def cross_dimer_end_edges_dev(self, d_pool: int, n: int, k: int, chem: Chem, tm_threshold: float,
+                                  rows: tuple[int, int], cols: tuple[int, int], d_edges: int, capacity: int,
+                                  d_count: int, d_row_conflicts: int = 0):
+        """Device-pointer END edge list of a block (16-byte records a:u32, b:u32, t:f64 raw; *d_count may exceed the
+        capacity = truncated); asynchronous."""
+        self._check(self.L.msspe_cross_dimer_end_edges_dev(
+            self.ptr, C.c_void_p(d_pool), n, k, C.byref(chem), C.c_float(tm_threshold), rows[0], rows[1], cols[0],
+            cols[1], C.c_void_p(d_row_conflicts), C.c_void_p(d_edges), capacity, C.c_void_p(d_count)))
+
+    def cross_dimer_end_ab(self, a, b, chem: Chem | None = None, tm_threshold: float = END_TM_THRESHOLD,
+                           want_dg=True, want_tm=True, want_bitmap=True):
+        """END screen of the pairs (A[i], B[j]) (msspe_cross_dimer_end_ab): A is oligo 1, the anchored 3' end; the
+        lengths may differ.  The dict of cross_dimer_end with rows = A and columns = B."""
+        abuf, n_a, k_a = _ascii(a)
+        bbuf, n_b, k_b = _ascii(b)
+        k_a, k_b = k_a or k_b or 2, k_b or k_a or 2   # an empty pool's length does not matter
+        chem = chem or Chem.ntthal()
+        rc_ = np.zeros(n_a, dtype=np.uint32)
+        bm = np.zeros((n_a, (n_b + 63) // 64), dtype=np.uint64) if want_bitmap else None
+        dg = np.empty((n_a, n_b)) if want_dg else None
+        tm = np.empty((n_a, n_b)) if want_tm else None
+        self._check(self.L.msspe_cross_dimer_end_ab(
+            self.ptr, abuf, n_a, k_a, bbuf, n_b, k_b, C.byref(chem), C.c_float(tm_threshold), rc_.ctypes.data,
+            bm.ctypes.data if want_bitmap else None, dg.ctypes.data if want_dg else None,
+            tm.ctypes.data if want_tm else None))
+        return {"row_conflicts": rc_, "bitmap": bm, "dg": dg, "tm": tm}
+
+    def cross_dimer_end_ab_dev(self, d_a: int, n_a: int, k_a: int, d_b: int, n_b: int, k_b: int, chem: Chem,
+                               tm_threshold: float, rows: tuple[int, int], cols: tuple[int, int],
+                               d_row_conflicts: int = 0, d_bitmap: int = 0, d_dg: int = 0, d_tm: int = 0):
+        """Device-pointer END screen over rows [rows) of A x columns [cols) of B (msspe_cross_dimer_end_ab_dev);
+        asynchronous."""
+        self._check(self.L.msspe_cross_dimer_end_ab_dev(
+            self.ptr, C.c_void_p(d_a), n_a, k_a, C.c_void_p(d_b), n_b, k_b, C.byref(chem), C.c_float(tm_threshold),
+            rows[0], rows[1], cols[0], cols[1], C.c_void_p(d_row_conflicts), C.c_void_p(d_bitmap),
+            C.c_void_p(d_dg), C.c_void_p(d_tm)))
+
+    def pair_compl_end(self, pool, chem: Chem | None = None) -> np.ndarray:
+        """n x n float64: max(t_end(a, b), t_end(b, a)), t_end = max(0, thal END1 t) -- both 3' ends of every pair
+        (END2(a, b) = END1(b, a)), from one END screen and its transpose."""
+        t = self.cross_dimer_end(pool, chem, want_dg=False, want_tm=True, want_bitmap=False)["tm"]
+        t = np.maximum(t, 0.0)
+        return np.maximum(t, t.T)
 
     def profile_enable(self, on: bool = True):
         self._check(self.L.msspe_profile_enable(self.ptr, int(on)))
