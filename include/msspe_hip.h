@@ -391,6 +391,28 @@ int msspe_kmer_candidates_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, i
 int msspe_kmer_candidates_both_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
                                           const msspe_kmer_opt *opt, uint64_t *words_fwd, uint32_t *freq_fwd, int *n_fwd,
                                           uint64_t *words_rev, uint32_t *freq_rev, int *n_rev, int capacity);
+/* Stage A extending a panel (engine extension): the same calls, started from a state in which the seed words are
+ * already picked.  seed: n_seed HOST packed words (msspe_pack_oligos at opt->kmer_size) in the key space of the
+ * direction -- direction 0 the forward primer text, direction 1 the reverse primer as the CSV writes it (the word
+ * stage A returns for direction 1).  Before the first iteration every distinct seed word present in the direction's
+ * index gets main.rs:371-378's post-push update once: its segments become covered, and the coverage of each distinct
+ * partition among all its segments (covered ones included) goes up by one.  Seed order and duplicates do not
+ * matter; a seed absent from the index does nothing; seeds are never returned as winners.  The loop, its stop rules
+ * and max_iterations are unchanged; frequencies are live counts.  n_seed == 0 gives the unseeded call's output.
+ * MSSPE_ERR_ARG: seed == NULL with n_seed > 0, n_seed < 0, or a seed word with bits above 2 k. */
+int msspe_kmer_candidates_seeded(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len,
+                                 const msspe_kmer_opt *opt, int direction, const uint64_t *seed, int n_seed,
+                                 uint64_t *words_out, uint32_t *freq_out, int capacity, int *n_out);
+int msspe_kmer_candidates_seeded_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
+                                            const msspe_kmer_opt *opt, int direction, const uint64_t *seed,
+                                            int n_seed, uint64_t *words_out, uint32_t *freq_out, int capacity,
+                                            int *n_out);
+/* Both directions, each seeded with its own list, each on its own stream (as msspe_kmer_candidates_both_packed_dev). */
+int msspe_kmer_candidates_both_seeded_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
+                                                 const msspe_kmer_opt *opt, const uint64_t *seed_fwd, int n_fwd_seed,
+                                                 const uint64_t *seed_rev, int n_rev_seed, uint64_t *words_fwd,
+                                                 uint32_t *freq_fwd, int *n_fwd, uint64_t *words_rev,
+                                                 uint32_t *freq_rev, int *n_rev, int capacity);
 int msspe_segment_coverage_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
                                       const msspe_kmer_opt *opt, const uint64_t *fwd_words, int n_fwd,
                                       const uint64_t *rev_words, int n_rev, uint8_t *hit_out);

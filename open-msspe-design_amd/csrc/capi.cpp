@@ -1661,20 +1661,29 @@ int msspe_oligo_stats(msspe_ctx *ctx, const char *pool_ascii, int n, int k,
     return rc;
 }
 
-int msspe_kmer_candidates_dev(msspe_ctx *ctx, const uint8_t *d_seqs, int n_seq, size_t seq_len,
-                              const msspe_kmer_opt *opt, int direction, uint64_t *words_out,
-                              uint32_t *freq_out, int capacity, int *n_out)
+// stage A on a device byte alignment, optionally seeded (msspe_kmer_candidates_dev / _seeded)
+static int kmer_candidates_dev(msspe_ctx *ctx, const uint8_t *d_seqs, int n_seq, size_t seq_len,
+                               const msspe_kmer_opt *opt, int direction, const uint64_t *seed, int n_seed,
+                               uint64_t *words_out, uint32_t *freq_out, int capacity, int *n_out)
 {
     if (!ctx) return MSSPE_ERR_ARG;
-    if (!d_seqs || !opt || !words_out || !freq_out || !n_out || capacity < 0)
+    if (!d_seqs || !opt || !words_out || !freq_out || !n_out || capacity < 0 || n_seed < 0 || (n_seed && !seed))
         return fail(ctx, MSSPE_ERR_ARG, "null argument");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::string err;
     const SeqView view{d_seqs, nullptr, seq_len};
     const int rc = ctx->kmer.run(view, n_seq, seq_len, *opt, direction, words_out, freq_out,
-                                 capacity, n_out, ctx->stream, err);
+                                 capacity, n_out, ctx->stream, err, seed, n_seed);
     if (rc) return fail(ctx, rc, err);
     return MSSPE_OK;
+}
+
+int msspe_kmer_candidates_dev(msspe_ctx *ctx, const uint8_t *d_seqs, int n_seq, size_t seq_len,
+                              const msspe_kmer_opt *opt, int direction, uint64_t *words_out,
+                              uint32_t *freq_out, int capacity, int *n_out)
+{
+    return kmer_candidates_dev(ctx, d_seqs, n_seq, seq_len, opt, direction, nullptr, 0, words_out, freq_out, capacity,
+                               n_out);
 }
 
 int msspe_kmer_candidates_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
@@ -1693,12 +1702,40 @@ int msspe_kmer_candidates_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, i
     return MSSPE_OK;
 }
 
+int msspe_kmer_candidates_seeded_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
+                                            const msspe_kmer_opt *opt, int direction, const uint64_t *seed,
+                                            int n_seed, uint64_t *words_out, uint32_t *freq_out, int capacity,
+                                            int *n_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!d_packed || !opt || !words_out || !freq_out || !n_out || capacity < 0 || n_seed < 0 || (n_seed && !seed))
+        return fail(ctx, MSSPE_ERR_ARG, "null argument");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::string err;
+    const SeqView view{nullptr, d_packed, seq_len};
+    const int rc = ctx->kmer.run(view, n_seq, seq_len, *opt, direction, words_out, freq_out,
+                                 capacity, n_out, ctx->stream, err, seed, n_seed);
+    if (rc) return fail(ctx, rc, err);
+    return MSSPE_OK;
+}
+
 int msspe_kmer_candidates_both_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
                                           const msspe_kmer_opt *opt, uint64_t *words_fwd, uint32_t *freq_fwd, int *n_fwd,
                                           uint64_t *words_rev, uint32_t *freq_rev, int *n_rev, int capacity)
 {
+    return msspe_kmer_candidates_both_seeded_packed_dev(ctx, d_packed, n_seq, seq_len, opt, nullptr, 0, nullptr, 0,
+                                                        words_fwd, freq_fwd, n_fwd, words_rev, freq_rev, n_rev, capacity);
+}
+
+int msspe_kmer_candidates_both_seeded_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
+                                                 const msspe_kmer_opt *opt, const uint64_t *seed_fwd, int n_fwd_seed,
+                                                 const uint64_t *seed_rev, int n_rev_seed, uint64_t *words_fwd,
+                                                 uint32_t *freq_fwd, int *n_fwd, uint64_t *words_rev,
+                                                 uint32_t *freq_rev, int *n_rev, int capacity)
+{
     if (!ctx) return MSSPE_ERR_ARG;
-    if (!d_packed || !opt || !words_fwd || !freq_fwd || !n_fwd || !words_rev || !freq_rev || !n_rev || capacity < 0)
+    if (!d_packed || !opt || !words_fwd || !freq_fwd || !n_fwd || !words_rev || !freq_rev || !n_rev || capacity < 0 ||
+        n_fwd_seed < 0 || n_rev_seed < 0 || (n_fwd_seed && !seed_fwd) || (n_rev_seed && !seed_rev))
         return fail(ctx, MSSPE_ERR_ARG, "null argument");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (!ctx->stream_rev) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->stream_rev, hipStreamNonBlocking));
@@ -1717,9 +1754,11 @@ int msspe_kmer_candidates_both_packed_dev(msspe_ctx *ctx, const uint64_t *d_pack
             err1 = "hipSetDevice failed";
             return;
         }
-        rc1 = ctx->kmer_rev.run(view, n_seq, seq_len, *opt, 1, words_rev, freq_rev, capacity, n_rev, ctx->stream_rev, err1);
+        rc1 = ctx->kmer_rev.run(view, n_seq, seq_len, *opt, 1, words_rev, freq_rev, capacity, n_rev, ctx->stream_rev, err1,
+                                seed_rev, n_rev_seed);
     });
-    rc0 = ctx->kmer.run(view, n_seq, seq_len, *opt, 0, words_fwd, freq_fwd, capacity, n_fwd, ctx->stream, err0);
+    rc0 = ctx->kmer.run(view, n_seq, seq_len, *opt, 0, words_fwd, freq_fwd, capacity, n_fwd, ctx->stream, err0,
+                        seed_fwd, n_fwd_seed);
     rev.join();
     if (rc0) return fail(ctx, rc0, err0);
     if (rc1) return fail(ctx, rc1, "direction 1: " + err1);
@@ -1732,15 +1771,24 @@ int msspe_kmer_candidates(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t
                           const msspe_kmer_opt *opt, int direction, uint64_t *words_out,
                           uint32_t *freq_out, int capacity, int *n_out)
 {
+    return msspe_kmer_candidates_seeded(ctx, seqs, n_seq, seq_len, opt, direction, nullptr, 0, words_out, freq_out,
+                                        capacity, n_out);
+}
+
+int msspe_kmer_candidates_seeded(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len,
+                                 const msspe_kmer_opt *opt, int direction, const uint64_t *seed, int n_seed,
+                                 uint64_t *words_out, uint32_t *freq_out, int capacity, int *n_out)
+{
     if (!ctx) return MSSPE_ERR_ARG;
+    if (n_seed < 0 || (n_seed && !seed)) return fail(ctx, MSSPE_ERR_ARG, "null seed list");
     if (!seqs || n_seq < 0) return fail(ctx, MSSPE_ERR_ARG, "null sequences");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     uint8_t *d = nullptr;
     const size_t bytes = (size_t)n_seq * seq_len;
     HIP_TRY(ctx, hipMalloc((void **)&d, bytes ? bytes : 1));
     hipError_t e = hipMemcpy(d, seqs, bytes, hipMemcpyHostToDevice);
-    int rc = e == hipSuccess ? msspe_kmer_candidates_dev(ctx, d, n_seq, seq_len, opt, direction,
-                                                         words_out, freq_out, capacity, n_out)
+    int rc = e == hipSuccess ? kmer_candidates_dev(ctx, d, n_seq, seq_len, opt, direction, seed, n_seed,
+                                                   words_out, freq_out, capacity, n_out)
                              : hip_fail(ctx, e, "hipMemcpy");
     (void)hipFree(d);
     return rc;

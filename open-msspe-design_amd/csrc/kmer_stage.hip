@@ -2159,6 +2159,69 @@ __global__ void __launch_bounds__(1024) k_cover_multi(const PickState *ps, const
     }
 }
 
+// Seeding (a run that extends a panel): the post-push update of main.rs:371-378 for every distinct seed word in the
+// index, once, before the first iteration -- its segments become covered, and the coverage of each distinct
+// partition among ALL its postings goes up by one.  One block per seed (the seeds are sorted and distinct): its word
+// id by bisection of the sorted unique keys (absent: nothing happens), its partitions in an LDS bitmap (as
+// tie_score_wave's allp), its segments claimed with an atomic on the flag's 32-bit word (two seeds may share a
+// segment: whoever sets the byte covers it and takes the live counts of the segment's words down, as k_cover does).
+__global__ void __launch_bounds__(1024) k_seed(const uint64_t *seed, int n_seed, const uint64_t *ukeys, int M,
+                                               const uint32_t *post_off, const uint32_t *post, uint8_t *ignored,
+                                               uint32_t *coverage, int P, int G, int per, const int32_t *kid_of_inst,
+                                               int32_t *count)
+{
+    extern __shared__ unsigned char smem[];
+    unsigned *parts = (unsigned *)smem;
+    __shared__ int kid_sh;
+    const int words = (P + 31) / 32;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
+    for (int s = blockIdx.x; s < n_seed; s += gridDim.x) {   // block-uniform
+        if (threadIdx.x == 0) {
+            const uint64_t w = seed[s];
+            int lo = 0, hi = M;
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (ukeys[mid] < w) lo = mid + 1;
+                else hi = mid;
+            }
+            kid_sh = lo < M && ukeys[lo] == w ? lo : -1;
+        }
+        for (int i = threadIdx.x; i < words; i += blockDim.x) parts[i] = 0u;
+        __syncthreads();
+        const int kid = kid_sh;
+        if (kid >= 0) {   // block-uniform
+            const uint32_t b = post_off[kid], e = post_off[kid + 1];
+            for (uint32_t base = b + (uint32_t)wave * 64u; base < e; base += (uint32_t)n_waves * 64u) {   // wave-uniform
+                const uint32_t i = base + lane;
+                uint32_t row = 0;
+                int part = -1;
+                bool fresh = false;
+                if (i < e) {
+                    const uint32_t seg = post[i];
+                    part = (int)(seg % (uint32_t)P);
+                    row = (uint32_t)part * (uint32_t)G + seg / (uint32_t)P;
+                    const unsigned sh8 = 8u * (row & 3u);
+                    const unsigned old = atomicOr(reinterpret_cast<unsigned *>(ignored + (row & ~3u)), 1u << sh8);
+                    fresh = ((old >> sh8) & 0xffu) == 0u;
+                }
+                unsigned long long m = __ballot(part >= 0);
+                while (m) {   // one LDS atomic per distinct partition of the wave
+                    const int l = __ffsll((long long)m) - 1;
+                    const int pl = __builtin_amdgcn_readlane(part, l);
+                    m &= ~__ballot(part == pl);
+                    if (lane == l) atomicOr(&parts[pl >> 5], 1u << (pl & 31));
+                }
+                if (__ballot(fresh)) cover_wave(row, fresh, per, G, kid_of_inst, count);
+            }
+        }
+        __syncthreads();
+        if (kid >= 0)
+            for (int i = threadIdx.x; i < words; i += blockDim.x)
+                for (unsigned m = parts[i]; m; m &= m - 1u) atomicAdd(&coverage[i * 32 + __ffs((int)m) - 1], 1u);
+        __syncthreads();   // parts and kid_sh serve the block's next seed
+    }
+}
+
 // Coverage of the final primer set (main.rs:518-594): a segment is covered when its head window
 // holds one of the forward primers or its tail window holds the reverse complement of one of the
 // reverse primers.  One wave per segment, lane = window position; the primers are sorted packed
@@ -2281,7 +2344,7 @@ hipError_t launch_pack_rows(const uint8_t *d_ascii, int n_rows, size_t row_len, 
 
 int KmerStage::run(const SeqView &d_seqs, int n_seq, size_t seq_len, const msspe_kmer_opt &opt,
                    int direction, uint64_t *words_out, uint32_t *freq_out, int capacity,
-                   int *n_out, hipStream_t stream, std::string &err)
+                   int *n_out, hipStream_t stream, std::string &err, const uint64_t *seed, int n_seed)
 {
     *n_out = 0;
     const int k = opt.kmer_size, W = opt.search_window_size;
@@ -2294,6 +2357,21 @@ int KmerStage::run(const SeqView &d_seqs, int n_seq, size_t seq_len, const msspe
         err = "stage A: unsupported options (need 1 <= k <= 31, k <= window <= segment, stride >= 1)";
         return k < 1 || k > 31 ? MSSPE_ERR_K : MSSPE_ERR_ARG;
     }
+    if (n_seed < 0 || (n_seed > 0 && !seed)) {
+        err = "stage A: null seed list";
+        return MSSPE_ERR_ARG;
+    }
+    // the seeds as index keys (lexicographic code), sorted and distinct
+    std::vector<uint64_t> seed_keys((size_t)n_seed);
+    for (int i = 0; i < n_seed; ++i) {
+        if (seed[i] >> (2 * k)) {
+            err = "stage A: seed word " + std::to_string(i) + " has bits above 2k";
+            return MSSPE_ERR_ARG;
+        }
+        seed_keys[(size_t)i] = lex_to_packed(seed[i], k);   // (the base order reversal is its own inverse)
+    }
+    std::sort(seed_keys.begin(), seed_keys.end());
+    seed_keys.erase(std::unique(seed_keys.begin(), seed_keys.end()), seed_keys.end());
     const long P = seq_len < (size_t)opt.segment_size
                        ? 0
                        : (long)((seq_len - (size_t)opt.segment_size) / (size_t)opt.overlap_size) + 1;
@@ -2308,7 +2386,7 @@ int KmerStage::run(const SeqView &d_seqs, int n_seq, size_t seq_len, const msspe
     const size_t n_inst = (size_t)n_seg * per;
     const uint64_t sentinel = 1ull << (2 * k);
     int rc;
-    // buffers: 0/1 keys, 2/3 vals, 4 (unused), 5 first instances per index block and their scan, 6 kid_of_inst, 7 post, 8 post_off, 9 ukeys,
+    // buffers: 0/1 keys, 2/3 vals, 4 the seeds (index keys), 5 first instances per index block and their scan, 6 kid_of_inst, 7 post, 8 post_off, 9 ukeys,
     // 10 count+tied, 11 ignored, 12 coverage+stamp, 13 status/out, 14 cub temp, 16 the candidate-list loop's
     // PickState + per-word results (key, id, two partition bitmaps)
     if ((rc = ensure(0, n_inst * 8, err)) || (rc = ensure(1, n_inst * 8, err)) ||
@@ -2432,6 +2510,18 @@ int KmerStage::run(const SeqView &d_seqs, int n_seq, size_t seq_len, const msspe
     if (M == 0) return MSSPE_OK;
     hipLaunchKernelGGL(k_init_counts, dim3((M + 255) / 256), dim3(256), 0, stream, post_off, M, count);
     KM_TRY(hipGetLastError());
+    const bool seeded = !seed_keys.empty();
+    if (seeded) {
+        // the seeds' post-push updates, on the call's stream ahead of the loop (never part of a captured batch)
+        if ((rc = ensure(4, sizeof(uint64_t) * seed_keys.size(), err))) return rc;
+        KM_TRY(hipMemcpyAsync(buf_[4], seed_keys.data(), sizeof(uint64_t) * seed_keys.size(), hipMemcpyHostToDevice,
+                              stream));
+        const int ns = (int)seed_keys.size();
+        hipLaunchKernelGGL(k_seed, dim3((unsigned)std::min(ns, 2048)), dim3(1024), sizeof(unsigned) * pwords, stream,
+                           (const uint64_t *)buf_[4], ns, ukeys, M, post_off, post, ignored, coverage, (int)P, n_seq,
+                           per, kid_of_inst, count);
+        KM_TRY(hipGetLastError());
+    }
 
     // 3. greedy loop: one iteration = five launches with constant arguments, captured once into a
     //    hipGraph (kBatch iterations per graph) and replayed; the loop state (Status) lives on the
@@ -2464,7 +2554,7 @@ int KmerStage::run(const SeqView &d_seqs, int n_seq, size_t seq_len, const msspe
     // the candidate-list loop's three pieces.  A batch (graph) holds iterations only; the host looks at the flags
     // between batches and puts a list rebuild or one walking iteration in front of the next batch when asked to
     // (the remaining iterations of a batch that asked are no-ops)
-    bool first_list = true;
+    bool first_list = !seeded;   // seeded: segments are covered already, the first list is marked like any other
     auto enqueue_rebuild = [&](hipStream_t s_) {
         // the maximum, theta, the candidate list, the marked segments (and the stop decision)
         hipLaunchKernelGGL(k_max_count<true>, dim3(red_grid), dim3(256), 0, s_, count, M, st, 0, live_part, (int)P);

@@ -33,9 +33,12 @@ hipError_t launch_pack_rows(const uint8_t *d_ascii, int n_rows, size_t row_len, 
 class KmerStage {
 public:
     // d_seqs: device, n_seq x seq_len bytes.  words_out / freq_out / n_out: host buffers.
+    // seed / n_seed (host, optional): packed words (msspe_pack_oligos) of the direction's key space, taken as
+    // already picked -- their segments covered and their partitions' coverage bumped once each before the first
+    // iteration (main.rs:371-378); order and duplicates do not matter, words absent from the index do nothing
     int run(const SeqView &seqs, int n_seq, size_t seq_len, const msspe_kmer_opt &opt,
             int direction, uint64_t *words_out, uint32_t *freq_out, int capacity, int *n_out,
-            hipStream_t stream, std::string &err);
+            hipStream_t stream, std::string &err, const uint64_t *seed = nullptr, int n_seed = 0);
     // Segment coverage of a primer set (main.rs:518-594): hit_out[seq * P + partition] = 1 when the
     // segment's head window holds a forward primer or its tail window the reverse complement of a
     // reverse primer.  fwd_words / rev_words / hit_out: host buffers.

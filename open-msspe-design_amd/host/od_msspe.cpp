@@ -58,6 +58,7 @@ const OptSpec kOpts[] = {
     {"--delta-g-threshold", "DELTA_G_THRESHOLD", OptSpec::Float, OFF(delta_g_threshold)},
     {"--keep-all", "KEEP_ALL", OptSpec::Bool, OFF(keep_all)},
     {"--check-cross-dimers", "CHECK_CROSS_DIMERS", OptSpec::Bool, OFF(check_cross_dimers)},
+    {"--existing-primers", "EXISTING_PRIMERS", OptSpec::Str, OFF(existing_primers)},
     {"--check-self-dimers", "CHECK_SELF_DIMERS", OptSpec::Bool, OFF(check_self_dimers)},
     {"--check-hairpin", "CHECK_HAIRPIN", OptSpec::Bool, OFF(check_hairpin)},
     {"--tm-stddev", "TM_STDDEV", OptSpec::Float, OFF(tm_stddev)},
@@ -350,7 +351,8 @@ std::vector<KmerFrequency> find_candidates_kmers(Engine &eng, const DeviceAlignm
 // Both directions in one engine call (msspe_kmer_candidates_both_packed_dev: two streams, two host threads); what the
 // reference gets from its two find_candidates_kmers calls, main.rs:673-690.
 std::pair<std::vector<KmerFrequency>, std::vector<KmerFrequency>> find_candidates_kmers_both(
-    Engine &eng, const DeviceAlignment &aln, const ProgramConfig &cfg, int segment_size, int overlap_size, int window_size)
+    Engine &eng, const DeviceAlignment &aln, const ProgramConfig &cfg, int segment_size, int overlap_size, int window_size,
+    const std::vector<std::string> &seed_f, const std::vector<std::string> &seed_r)
 {
     if (overlap_size < window_size)   // main.rs:201-203
         throw Panic("Overlap windows size must be greater or equal than search windows size");
@@ -362,9 +364,26 @@ std::pair<std::vector<KmerFrequency>, std::vector<KmerFrequency>> find_candidate
     std::vector<uint64_t> words[2] = {std::vector<uint64_t>((size_t)cap), std::vector<uint64_t>((size_t)cap)};
     std::vector<uint32_t> freq[2] = {std::vector<uint32_t>((size_t)cap), std::vector<uint32_t>((size_t)cap)};
     int n[2] = {0, 0};
-    const int rc = msspe_kmer_candidates_both_packed_dev(eng.ctx(), aln.device(), aln.rows(), aln.length(), &opt,
-                                                         words[0].data(), freq[0].data(), &n[0], words[1].data(),
-                                                         freq[1].data(), &n[1], cap);
+    int rc;
+    if (seed_f.empty() && seed_r.empty()) {
+        rc = msspe_kmer_candidates_both_packed_dev(eng.ctx(), aln.device(), aln.rows(), aln.length(), &opt,
+                                                   words[0].data(), freq[0].data(), &n[0], words[1].data(),
+                                                   freq[1].data(), &n[1], cap);
+    } else {
+        std::vector<uint64_t> sw[2];
+        for (int d = 0; d < 2; ++d) {
+            const auto &seed = d ? seed_r : seed_f;
+            std::string flat;
+            for (const auto &w : seed) flat += w;
+            sw[d].resize(seed.size() + 1);
+            if (!seed.empty() && (rc = msspe_pack_oligos(flat.data(), (int)seed.size(), opt.kmer_size, sw[d].data())))
+                eng.fail(rc);
+        }
+        rc = msspe_kmer_candidates_both_seeded_packed_dev(eng.ctx(), aln.device(), aln.rows(), aln.length(), &opt,
+                                                          sw[0].data(), (int)seed_f.size(), sw[1].data(),
+                                                          (int)seed_r.size(), words[0].data(), freq[0].data(), &n[0],
+                                                          words[1].data(), freq[1].data(), &n[1], cap);
+    }
     if (rc) eng.fail(rc);
     std::vector<char> buf((size_t)opt.kmer_size + 1);
     for (int d = 0; d < 2; ++d) {
@@ -517,6 +536,19 @@ std::string format_ntthal_input(const std::vector<std::string> &primers, const P
     return out;
 }
 
+namespace {
+// the chemistry ntthal is called with: "{:.2}" strings of the f32 options (delta_g.rs:98-106)
+msspe_chem ntthal_chem(const NtthalOptions &opts)
+{
+    auto two = [](float v) {
+        char b[64];
+        std::snprintf(b, sizeof b, "%.2f", (double)v);
+        return std::strtod(b, nullptr);
+    };
+    return msspe_chem{two(opts.mv), two(opts.dv), two(opts.dntp), two(opts.conc), two(opts.t), 30};
+}
+}  // namespace
+
 ConflictGraph run_ntthal(Engine &eng, const std::vector<std::string> &primers,
                          const NtthalOptions &opts, const ProgramConfig &cfg)
 {
@@ -529,12 +561,7 @@ ConflictGraph run_ntthal(Engine &eng, const std::vector<std::string> &primers,
     const int n = (int)g.nodes.size(), k = (int)g.nodes[0].size();
     std::string flat;
     for (const auto &p : g.nodes) flat += p;
-    auto two = [](float v) {   // ntthal receives "{:.2}" strings of the f32 options (delta_g.rs:98-106)
-        char b[64];
-        std::snprintf(b, sizeof b, "%.2f", (double)v);
-        return std::strtod(b, nullptr);
-    };
-    msspe_chem chem{two(opts.mv), two(opts.dv), two(opts.dntp), two(opts.conc), two(opts.t), 30};
+    const msspe_chem chem = ntthal_chem(opts);
     // the conflict edges as a list (about 0.5 % of the ordered pairs at the default threshold), not the
     // dense n x n bitmap; if the first guess is too small the call says how many there are
     std::vector<msspe_edge> edges((size_t)std::max<uint64_t>(4096, (uint64_t)n * (uint64_t)n / 64));
@@ -559,6 +586,84 @@ ConflictGraph run_ntthal(Engine &eng, const std::vector<std::string> &primers,
         g.edges[a].insert(b);
     }
     return g;
+}
+
+// --existing-primers: the candidates (one length) with a conflict against any panel primer, in either order of the
+// pair -- run_ntthal's dG rule, screened as candidates x panel and panel x candidates (with --devices: on member 0;
+// the block is at most 2,000 x the panel)
+std::set<std::string> panel_conflicts(Engine &eng, const std::vector<std::string> &cands,
+                                      const std::vector<std::string> &panel, const NtthalOptions &opts)
+{
+    std::set<std::string> out;
+    if (cands.empty() || panel.empty()) return out;
+    const int k = (int)cands[0].size(), nc = (int)cands.size(), np = (int)panel.size();
+    std::string fc, fp;
+    for (const auto &p : cands) fc += p;
+    for (const auto &p : panel) fp += p;
+    const msspe_chem chem = ntthal_chem(opts);
+    for (int order = 0; order < 2; ++order) {   // 0: (candidate, panel), 1: (panel, candidate)
+        const std::string &a = order ? fp : fc, &b = order ? fc : fp;
+        const int na = order ? np : nc, nb = order ? nc : np;
+        std::vector<msspe_edge> edges(4096);
+        uint64_t count = 0;
+        auto screen = [&]() {
+            return msspe_cross_dimer_ab_edges(eng.ctx(), a.data(), na, k, b.data(), nb, k, &chem, opts.dg, edges.data(),
+                                              edges.size(), &count);
+        };
+        int rc = screen();
+        if (rc == MSSPE_ERR_CAPACITY) {
+            edges.resize((size_t)count);
+            rc = screen();
+        }
+        if (rc) eng.fail(rc);
+        for (uint64_t e = 0; e < count; ++e) out.insert(cands[order ? edges[(size_t)e].b : edges[(size_t)e].a]);
+    }
+    return out;
+}
+
+std::pair<std::vector<std::string>, std::vector<std::string>> read_panel(const std::string &path, int kmer_size)
+{
+    std::ifstream f(path, std::ios::binary);
+    if (!f) throw UsageError("error: cannot read '" + path + "' for '--existing-primers'");
+    std::pair<std::vector<std::string>, std::vector<std::string>> out;
+    std::string line;
+    size_t no = 0, col_dir = 0, col_primer = 2;
+    auto split = [](const std::string &l) {
+        std::vector<std::string> v;
+        size_t at = 0;
+        for (;;) {
+            const size_t c = l.find(',', at);
+            v.push_back(l.substr(at, c == std::string::npos ? std::string::npos : c - at));
+            if (c == std::string::npos) return v;
+            at = c + 1;
+        }
+    };
+    while (std::getline(f, line)) {
+        ++no;
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        const std::string where = "error: '--existing-primers' " + path + " line " + std::to_string(no) + ": ";
+        const auto fields = split(line);
+        if (no == 1) {   // the header names the columns (direction,name,primers,gc,avg,std,tm)
+            const auto d = std::find(fields.begin(), fields.end(), "direction");
+            const auto p = std::find(fields.begin(), fields.end(), "primers");
+            if (d == fields.end() || p == fields.end())
+                throw UsageError(where + "the header has no 'direction' and 'primers' columns");
+            col_dir = (size_t)(d - fields.begin());
+            col_primer = (size_t)(p - fields.begin());
+            continue;
+        }
+        if (line.empty()) continue;
+        if (fields.size() <= std::max(col_dir, col_primer)) throw UsageError(where + "too few fields");
+        const std::string &dir = fields[col_dir], &primer = fields[col_primer];
+        if (dir != "F" && dir != "R") throw UsageError(where + "direction '" + dir + "' is neither F nor R");
+        if (primer.size() != (size_t)kmer_size)
+            throw UsageError(where + "primer '" + primer + "' has " + std::to_string(primer.size()) +
+                             " bases, --kmer-size is " + std::to_string(kmer_size));
+        if (primer.find_first_not_of("ACGT") != std::string::npos)
+            throw UsageError(where + "primer '" + primer + "' holds characters other than A, C, G and T");
+        (dir == "F" ? out.first : out.second).push_back(primer);
+    }
+    return out;
 }
 
 std::set<std::string> vertex_cover(const std::vector<std::string> &primers, const ConflictGraph &g)
@@ -694,11 +799,12 @@ std::string coverage_report(Engine &eng, const DeviceAlignment &aln, const std::
     return out;
 }
 
-std::string primers_csv(const std::vector<KmerStat> &fwd, const std::vector<KmerStat> &rev)
+std::string primers_csv(const std::vector<KmerStat> &fwd, const std::vector<KmerStat> &rev, size_t first_f,
+                        size_t first_r)
 {
     std::string out = "direction,name,primers,gc,avg,std,tm\n";
     for (const auto *list : {&fwd, &rev}) {
-        size_t idx = 0;
+        size_t idx = list == &fwd ? first_f : first_r;
         for (const auto &p : *list) {
             const char *d = p.direction == SEQ_DIR_FWD ? "F" : "R";
             out += std::string(d) + ",Primer_" + std::to_string(idx++) + "_" + d + "," + p.word + "," +
@@ -772,6 +878,10 @@ std::string align_sequences(const std::string &filepath)
 int run(const Args &args, std::string &stdout_text)
 {
     PhaseTimer timer;
+    // --existing-primers: the panel this run extends (read first: a bad file is a usage error before any work)
+    std::pair<std::vector<std::string>, std::vector<std::string>> panel;
+    if (!args.existing_primers.empty()) panel = read_panel(args.existing_primers, args.kmer_size);
+    const auto &panel_f = panel.first, &panel_r = panel.second;
     std::vector<SequenceRecord> records;
     if (args.do_align == "true") {   // the reference's default (config.rs:131-138)
         const std::string aligned = align_sequences(args.input);
@@ -834,21 +944,34 @@ int run(const Args &args, std::string &stdout_text)
     Engine &eng = *eng_owner;
     const DeviceAlignment aln(eng, records);   // one upload for stage A (both directions) and the report
     timer.lap("engine + alignment upload");
+    // (with a panel: stage A starts from the state in which the panel's words are picked already)
     const auto cand_both = find_candidates_kmers_both(eng, aln, cfg, args.window_size, args.overlap_size,
-                                                      args.search_windows_size);
+                                                      args.search_windows_size, panel_f, panel_r);
     const auto &cand_f = cand_both.first, &cand_r = cand_both.second;
     timer.lap("stage A (both directions)");
     const auto stats_f = get_kmer_stats(eng, cand_f, cfg);
     const auto stats_r = get_kmer_stats(eng, cand_r, cfg);
-    const auto prim_f = cfg.keep_all ? stats_f : filter_kmers(stats_f, cfg);
-    const auto prim_r = cfg.keep_all ? stats_r : filter_kmers(stats_r, cfg);
+    auto prim_f = cfg.keep_all ? stats_f : filter_kmers(stats_f, cfg);
+    auto prim_r = cfg.keep_all ? stats_r : filter_kmers(stats_r, cfg);
 
     timer.lap("stage B + filter");
+    const NtthalOptions opts{args.mv_conc, args.dv_conc, args.dntp_conc, args.dna_conc,
+                             args.annealing_temp, args.delta_g_threshold};
+    if (cfg.check_cross_dimers && !cfg.keep_all && (!panel_f.empty() || !panel_r.empty())) {
+        // a new primer that dimerises with the panel is dropped before the vertex cover (the panel stays whole)
+        std::vector<std::string> cands, all_panel(panel_f);
+        all_panel.insert(all_panel.end(), panel_r.begin(), panel_r.end());
+        for (const auto *list : {&prim_f, &prim_r})
+            for (const auto &s : *list) cands.push_back(s.word);
+        const auto bad = panel_conflicts(eng, cands, all_panel, opts);
+        for (auto *list : {&prim_f, &prim_r})
+            list->erase(std::remove_if(list->begin(), list->end(), [&](const KmerStat &s) { return bad.count(s.word) != 0; }),
+                        list->end());
+        timer.lap("panel cross-dimer screen");
+    }
     std::vector<std::string> primers;
     for (const auto &s : prim_f) primers.push_back(s.word);
     for (const auto &s : prim_r) primers.push_back(s.word);
-    const NtthalOptions opts{args.mv_conc, args.dv_conc, args.dntp_conc, args.dna_conc,
-                             args.annealing_temp, args.delta_g_threshold};
     const ConflictGraph graph = run_ntthal(eng, primers, opts, cfg);
     const auto deleted = vertex_cover(primers, graph);
     std::vector<KmerStat> good_f, good_r;
@@ -858,11 +981,15 @@ int run(const Args &args, std::string &stdout_text)
         if (cfg.keep_all || !deleted.count(p.word)) good_r.push_back(p);
 
     timer.lap("stage C + vertex cover");
-    stdout_text = coverage_report(eng, aln, good_f, good_r, records, args.window_size, args.overlap_size,
+    // the report covers the panel and the new primers together; the CSV lists the new ones, numbered on from the panel
+    std::vector<KmerStat> rep_f = good_f, rep_r = good_r;
+    for (const auto &w : panel_f) rep_f.push_back(KmerStat{w, SEQ_DIR_FWD});
+    for (const auto &w : panel_r) rep_r.push_back(KmerStat{w, SEQ_DIR_REV});
+    stdout_text = coverage_report(eng, aln, rep_f, rep_r, records, args.window_size, args.overlap_size,
                                   args.search_windows_size, args.kmer_size);
     std::ofstream out(args.output, std::ios::binary);
     if (!out) throw std::runtime_error("cannot write " + args.output);
-    out << primers_csv(good_f, good_r);
+    out << primers_csv(good_f, good_r, panel_f.size(), panel_r.size());
     timer.lap("coverage report + csv");
     return 0;
 }

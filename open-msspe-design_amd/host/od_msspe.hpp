@@ -52,6 +52,7 @@ struct Args {
     int device = 0;
     std::string devices;           // "0,1,2,...": the N^2 pair loop and stage B run on a group of devices (msspe_group_*)
     std::string params_path;       // Primer3 config directory; empty = bundled tables
+    std::string existing_primers;  // a panel to extend: CSV in this tool's output format (direction and primers read)
     bool stddev_population = false;  // crate std-dev 0.1.0's divisor is unpinned
     static Args parse(int argc, const char *const *argv);   // throws UsageError
     static std::string usage();
@@ -152,8 +153,13 @@ private:
 std::vector<KmerFrequency> find_candidates_kmers(Engine &eng, const std::vector<SequenceRecord> &records,
                                                  uint8_t direction, const ProgramConfig &cfg,
                                                  int segment_size, int overlap_size, int window_size);
+// seed_f / seed_r (a panel being extended): words stage A takes as already picked, per direction
 std::pair<std::vector<KmerFrequency>, std::vector<KmerFrequency>> find_candidates_kmers_both(
-    Engine &eng, const DeviceAlignment &aln, const ProgramConfig &cfg, int segment_size, int overlap_size, int window_size);
+    Engine &eng, const DeviceAlignment &aln, const ProgramConfig &cfg, int segment_size, int overlap_size, int window_size,
+    const std::vector<std::string> &seed_f = {}, const std::vector<std::string> &seed_r = {});
+// --existing-primers: the F and R primers of a panel CSV (direction, name, primers, ...); throws UsageError naming
+// the line when a primer is not kmer_size bases of ACGT or the direction is not F / R
+std::pair<std::vector<std::string>, std::vector<std::string>> read_panel(const std::string &path, int kmer_size);
 std::vector<KmerFrequency> find_candidates_kmers(Engine &eng, const DeviceAlignment &aln, uint8_t direction,
                                                  const ProgramConfig &cfg, int segment_size,
                                                  int overlap_size, int window_size);
@@ -180,7 +186,9 @@ std::string coverage_report(Engine &eng, const std::vector<KmerStat> &fwd, const
                             const std::vector<SequenceRecord> &records, int segment_size,
                             int overlap_size, int window_size, int kmer_size);
 // main.rs:834-858
-std::string primers_csv(const std::vector<KmerStat> &fwd, const std::vector<KmerStat> &rev);
+// first_f / first_r: the number of the first row of each direction (a panel's extension continues its numbering)
+std::string primers_csv(const std::vector<KmerStat> &fwd, const std::vector<KmerStat> &rev, size_t first_f = 0,
+                        size_t first_r = 0);
 
 // main.rs:596-861 without the MAFFT call: returns the process exit code; report -> stdout
 int run(const Args &args, std::string &stdout_text);

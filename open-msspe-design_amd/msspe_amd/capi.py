@@ -27,6 +27,8 @@ EXPORTS = [
     "msspe_kmer_candidates", "msspe_kmer_candidates_dev", "msspe_round_g_f32",
     "msspe_packed_row_words", "msspe_device_put_rows_packed", "msspe_kmer_candidates_packed_dev",
     "msspe_kmer_candidates_both_packed_dev",
+    "msspe_kmer_candidates_seeded", "msspe_kmer_candidates_seeded_packed_dev",
+    "msspe_kmer_candidates_both_seeded_packed_dev",
     "msspe_segment_coverage_packed_dev",
     "msspe_round_fixed_f32", "msspe_g_cut",
     "msspe_group_create", "msspe_group_destroy", "msspe_group_last_error", "msspe_group_size",
@@ -162,6 +164,12 @@ def load_library() -> C.CDLL:
     L.msspe_kmer_candidates_packed_dev.argtypes = L.msspe_kmer_candidates.argtypes
     L.msspe_kmer_candidates_both_packed_dev.argtypes = [vp, vp, C.c_int, C.c_size_t, C.POINTER(KmerOpt), vp, vp,
                                                         C.POINTER(C.c_int), vp, vp, C.POINTER(C.c_int), C.c_int]
+    L.msspe_kmer_candidates_seeded.argtypes = [vp, vp, C.c_int, C.c_size_t, C.POINTER(KmerOpt), C.c_int, vp, C.c_int,
+                                               vp, vp, C.c_int, C.POINTER(C.c_int)]
+    L.msspe_kmer_candidates_seeded_packed_dev.argtypes = L.msspe_kmer_candidates_seeded.argtypes
+    L.msspe_kmer_candidates_both_seeded_packed_dev.argtypes = [vp, vp, C.c_int, C.c_size_t, C.POINTER(KmerOpt),
+                                                               vp, C.c_int, vp, C.c_int, vp, vp, C.POINTER(C.c_int),
+                                                               vp, vp, C.POINTER(C.c_int), C.c_int]
     L.msspe_packed_row_words.restype = C.c_size_t
     L.msspe_packed_row_words.argtypes = [C.c_size_t]
     L.msspe_device_put_rows_packed.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_size_t,
@@ -225,6 +233,22 @@ def t_cut(tm_threshold: float) -> float:
 
 # PRIMER_MAX_SELF_END_TH, the SELF_END limit od-msspe applies to each primer: the END screen's default
 END_TM_THRESHOLD = 47.0
+
+
+def _seed_words(seed, k: int) -> np.ndarray | None:
+    """A seed= list (strings of length k, ACGT) -> packed uint64 words; None when no seed was given."""
+    if seed is None:
+        return None
+    seed = list(seed)
+    for s in seed:
+        if not isinstance(s, str) or len(s) != k:
+            raise ValueError(f"seed word {s!r} is not a string of length {k} (the k-mer size)")
+    if not seed:
+        return np.zeros(0, dtype=np.uint64)
+    try:
+        return pack_oligos(seed)
+    except MsspeError as e:
+        raise ValueError(f"seed words must be ACGT only: {e}") from None
 
 
 def _ascii(oligos):
@@ -577,14 +601,25 @@ class Engine:
     # ---- stage A ---------------------------------------------------------------------------
     def kmer_candidates(self, seqs: np.ndarray, opt: KmerOpt, direction: int,
                         device_ptr: int | None = None, n_seq: int | None = None,
-                        seq_len: int | None = None, capacity: int | None = None):
+                        seq_len: int | None = None, capacity: int | None = None, *, seed=None):
         """seqs: uint8 (n_seq, L) host array (or pass device_ptr + shape).  Returns (words, freqs).
-        capacity: size of the output buffers (default: max_iterations, which always suffices)."""
+        capacity: size of the output buffers (default: max_iterations, which always suffices).
+        seed: words (strings of length kmer_size, in the direction's key space) taken as already picked
+        (msspe_kmer_candidates_seeded; host sequences only)."""
         cap = max(1, opt.max_iterations if capacity is None else capacity)
         words = np.zeros(cap, dtype=np.uint64)
         freqs = np.zeros(cap, dtype=np.uint32)
         n_out = C.c_int(0)
-        if device_ptr is None:
+        sw = _seed_words(seed, opt.kmer_size)
+        if sw is not None:
+            if device_ptr is not None:
+                raise ValueError("seed= needs host sequences (or kmer_candidates_packed on a packed alignment)")
+            a = np.ascontiguousarray(seqs, dtype=np.uint8)
+            n_seq, seq_len = a.shape
+            self._check(self.L.msspe_kmer_candidates_seeded(
+                self.ptr, a.ctypes.data, n_seq, seq_len, C.byref(opt), direction, sw.ctypes.data, len(sw),
+                words.ctypes.data, freqs.ctypes.data, cap, C.byref(n_out)))
+        elif device_ptr is None:
             a = np.ascontiguousarray(seqs, dtype=np.uint8)
             n_seq, seq_len = a.shape
             self._check(self.L.msspe_kmer_candidates(
@@ -613,29 +648,47 @@ class Engine:
         self._check(self.L.msspe_device_free(self.ptr, C.c_void_p(device_ptr)))
 
     def kmer_candidates_packed(self, d_packed: int, n_seq: int, seq_len: int, opt: KmerOpt, direction: int,
-                               capacity: int | None = None):
-        """Stage A on a packed alignment resident on the device (put_rows_packed).  Returns (words, freqs)."""
+                               capacity: int | None = None, *, seed=None):
+        """Stage A on a packed alignment resident on the device (put_rows_packed).  Returns (words, freqs).
+        seed: as for kmer_candidates (msspe_kmer_candidates_seeded_packed_dev)."""
         cap = max(1, opt.max_iterations if capacity is None else capacity)
         words = np.zeros(cap, dtype=np.uint64)
         freqs = np.zeros(cap, dtype=np.uint32)
         n_out = C.c_int(0)
-        self._check(self.L.msspe_kmer_candidates_packed_dev(
-            self.ptr, C.c_void_p(d_packed), n_seq, seq_len, C.byref(opt), direction,
-            words.ctypes.data, freqs.ctypes.data, cap, C.byref(n_out)))
+        sw = _seed_words(seed, opt.kmer_size)
+        if sw is not None:
+            self._check(self.L.msspe_kmer_candidates_seeded_packed_dev(
+                self.ptr, C.c_void_p(d_packed), n_seq, seq_len, C.byref(opt), direction, sw.ctypes.data, len(sw),
+                words.ctypes.data, freqs.ctypes.data, cap, C.byref(n_out)))
+        else:
+            self._check(self.L.msspe_kmer_candidates_packed_dev(
+                self.ptr, C.c_void_p(d_packed), n_seq, seq_len, C.byref(opt), direction,
+                words.ctypes.data, freqs.ctypes.data, cap, C.byref(n_out)))
         m = n_out.value
         return [unpack_oligo(w, opt.kmer_size) for w in words[:m]], freqs[:m].copy()
 
 
-def _both(self, d_packed: int, n_seq: int, seq_len: int, opt: KmerOpt, capacity: int | None = None):
+def _both(self, d_packed: int, n_seq: int, seq_len: int, opt: KmerOpt, capacity: int | None = None, *,
+          seed_fwd=None, seed_rev=None):
     """Stage A, both directions of a packed alignment at once (msspe_kmer_candidates_both_packed_dev).
-    Returns ((words, freqs) of direction 0, (words, freqs) of direction 1)."""
+    Returns ((words, freqs) of direction 0, (words, freqs) of direction 1).  seed_fwd / seed_rev: each direction's
+    seed words, as for kmer_candidates (msspe_kmer_candidates_both_seeded_packed_dev)."""
     cap = max(1, opt.max_iterations if capacity is None else capacity)
     w = [np.zeros(cap, dtype=np.uint64) for _ in range(2)]
     f = [np.zeros(cap, dtype=np.uint32) for _ in range(2)]
     n = [C.c_int(0), C.c_int(0)]
-    self._check(self.L.msspe_kmer_candidates_both_packed_dev(
-        self.ptr, C.c_void_p(d_packed), n_seq, seq_len, C.byref(opt), w[0].ctypes.data, f[0].ctypes.data, C.byref(n[0]),
-        w[1].ctypes.data, f[1].ctypes.data, C.byref(n[1]), cap))
+    sf, sr = _seed_words(seed_fwd, opt.kmer_size), _seed_words(seed_rev, opt.kmer_size)
+    if sf is not None or sr is not None:
+        sf = np.zeros(0, dtype=np.uint64) if sf is None else sf
+        sr = np.zeros(0, dtype=np.uint64) if sr is None else sr
+        self._check(self.L.msspe_kmer_candidates_both_seeded_packed_dev(
+            self.ptr, C.c_void_p(d_packed), n_seq, seq_len, C.byref(opt), sf.ctypes.data, len(sf), sr.ctypes.data,
+            len(sr), w[0].ctypes.data, f[0].ctypes.data, C.byref(n[0]), w[1].ctypes.data, f[1].ctypes.data,
+            C.byref(n[1]), cap))
+    else:
+        self._check(self.L.msspe_kmer_candidates_both_packed_dev(
+            self.ptr, C.c_void_p(d_packed), n_seq, seq_len, C.byref(opt), w[0].ctypes.data, f[0].ctypes.data,
+            C.byref(n[0]), w[1].ctypes.data, f[1].ctypes.data, C.byref(n[1]), cap))
     return tuple(([unpack_oligo(x, opt.kmer_size) for x in w[d][:n[d].value]], f[d][:n[d].value].copy()) for d in (0, 1))
 
 
