@@ -99,7 +99,10 @@ int msspe_set_option(msspe_ctx *ctx, const char *key, const char *value);
  *   "stage_a_fast_iterations" / "stage_a_general_iterations" / "stage_a_rebuilds" / "stage_a_idle_iterations"
  *                     the last msspe_kmer_candidates* call's greedy loop: iterations that recorded winners from the
  *                     partitions' leaders alone / after a walk over posting lists, candidate lists made, idle
- *                     iterations at the end of the last batch */
+ *                     iterations at the end of the last batch
+ *   "cover_rounds"    the last msspe_conflict_cover* call: rounds that deleted nodes
+ *   "cover_keys_us" / "cover_symmetrise_us" / "cover_rounds_us"
+ *                     the same call's device time of its phases: sort and keys, S = B | B^T, the rounds */
 int msspe_get_info(msspe_ctx *ctx, const char *key, long long *value_out);
 int msspe_set_stream(msspe_ctx *ctx, void *hip_stream);
 int msspe_reset_stream(msspe_ctx *ctx);
@@ -251,6 +254,33 @@ int msspe_cross_dimer_end_ab_dev(msspe_ctx *ctx, const uint64_t *d_a, int n_a, i
 int msspe_cross_dimer_end_ab(msspe_ctx *ctx, const char *a_ascii, int n_a, int k_a, const char *b_ascii, int n_b,
                              int k_b, const msspe_chem *chem, float tm_threshold, uint32_t *row_conflicts,
                              uint64_t *bitmap, double *dg, double *tm);
+
+/* ---- the greedy vertex cover of the conflict graph (replaces vertex_cover, od-msspe/src/main.rs:754-798) ---- */
+
+/*
+ * The primers the reference's cover removes: nodes are the oligos of the pool (distinct), v and u are neighbours when
+ * (v, u) or (u, v) conflicts (the graph is symmetrised: thal ANY is not symmetric), and a self conflict puts v among
+ * its own neighbours.  Repeatedly the node with the most live neighbours is deleted, ties going to the
+ * lexicographically greatest oligo, until no live node has a live neighbour.  The device computes the same set in
+ * rounds that delete every local maximum of the key (live degree, lexicographic rank) at once.
+ * drop_self_pairs: the reference's --check-self-dimers false -- the pairs (a, a) and (a, revcomp(a)) are never edges
+ * (od-msspe/src/delta_g.rs:64-69).
+ * Errors: the argument statuses of msspe_cross_dimer* (NULL pointers, k outside 2..32: MSSPE_ERR_K, non-ACGT), and
+ * MSSPE_ERR_ARG for duplicate oligos, a pool word with bits above 2 k, or n above 262,144 (the symmetrised bitmap the
+ * cover keeps in the context is n^2 / 8 bytes).  An allocation failure is MSSPE_ERR_DEVICE.  n == 0: MSSPE_OK, nothing
+ * deleted.  msspe_get_info "cover_rounds" gives the number of rounds of the last call.
+ *
+ * d_bitmap: n x ceil(n/64) words, the layout msspe_cross_dimer_dev writes for the full block [0,n) x [0,n) (read
+ * only).  d_deleted[n] (device bytes): 1 = removed by the cover.  Enqueues; synchronises once per batch of rounds.
+ * n_deleted_out (host, optional): number of deleted nodes. */
+int msspe_conflict_cover_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k,
+                             const uint64_t *d_bitmap, int drop_self_pairs,
+                             uint8_t *d_deleted, int *n_deleted_out);
+/* Host pool: screens the whole pool on the device (msspe_cross_dimer_dev, bitmap only, decisions path) and covers it
+ * there; no edge list is built.  deleted_out[n] host bytes. */
+int msspe_conflict_cover(msspe_ctx *ctx, const char *pool_ascii, int n, int k,
+                         const msspe_chem *chem, float dg_threshold, int drop_self_pairs,
+                         uint8_t *deleted_out, int *n_deleted_out);
 
 /* Number of pairs the last cross-dimer call routed to the generic (slow) kernel because their
  * DP did not fit the fast kernel's register-resident table. */

@@ -4,6 +4,7 @@
 //   msspe_cross_dimer*     run_ntthal            /root/reference/od-msspe/src/delta_g.rs:83-153
 //   msspe_oligo_stats*     check_primers         /root/reference/od-msspe/src/primer.rs:143-166
 //   msspe_kmer_candidates* get_segment_manager + find_candidates_kmers  src/main.rs:196-235,331-406
+//   msspe_conflict_cover*  vertex_cover (the greedy cover of the conflict graph)  src/main.rs:754-798
 // There is no CPU fallback: every compute entry point needs a gfx950 device.
 #include "../../include/msspe_hip.h"
 
@@ -20,6 +21,7 @@
 #include <thread>
 #include <vector>
 
+#include "conflict_cover.hpp"
 #include "kernels.hpp"
 #include "kmer_stage.hpp"
 #include "nn_params.hpp"
@@ -103,6 +105,7 @@ struct msspe_ctx {
     KmerStage kmer_rev;                // direction 1 of msspe_kmer_candidates_both_packed_dev (its own buffers and loop graph)
     hipStream_t stream_rev = nullptr;  // ... and its stream
     hipEvent_t ev_rev = nullptr;
+    CoverStage cover;                  // msspe_conflict_cover*: the symmetrised bitmap and the round state
     // optional profiling of the dominant kernel (k_pairs_fast) with HIP events on ctx->stream
     bool prof_on = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events;
@@ -426,6 +429,10 @@ int msspe_get_info(msspe_ctx *ctx, const char *key, long long *value_out)
     else if (k == "stage_a_general_iterations") *value_out = ctx->kmer.loop_stats()[1];
     else if (k == "stage_a_rebuilds") *value_out = ctx->kmer.loop_stats()[2];
     else if (k == "stage_a_idle_iterations") *value_out = ctx->kmer.loop_stats()[3];
+    else if (k == "cover_rounds") *value_out = ctx->cover.rounds();
+    else if (k == "cover_keys_us") *value_out = ctx->cover.phase_us()[0];
+    else if (k == "cover_symmetrise_us") *value_out = ctx->cover.phase_us()[1];
+    else if (k == "cover_rounds_us") *value_out = ctx->cover.phase_us()[2];
     else return fail(ctx, MSSPE_ERR_ARG, "msspe_get_info: unknown key '" + k + "'");
     return MSSPE_OK;
 }
@@ -447,6 +454,7 @@ void msspe_destroy(msspe_ctx *ctx)
         (void)hipStreamSynchronize(ctx->stream);
         ctx->kmer.release();
         ctx->kmer_rev.release();
+        ctx->cover.release();
         if (ctx->ev_rev) (void)hipEventDestroy(ctx->ev_rev);
         if (ctx->stream_rev) {
             (void)hipStreamSynchronize(ctx->stream_rev);
@@ -1182,6 +1190,83 @@ int msspe_cross_dimer(msspe_ctx *ctx, const char *pool_ascii, int n, int k,
     if (rc) return fail(ctx, rc, rc == MSSPE_ERR_K ? "oligo length must be 1..32"
                                                    : "pool holds characters other than ACGT");
     return cross_dimer_host(ctx, packed, n, k, 0, n, k, chem, dg_threshold, row_conflicts, bitmap, dg, tm);
+}
+
+int msspe_conflict_cover_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const uint64_t *d_bitmap,
+                             int drop_self_pairs, uint8_t *d_deleted, int *n_deleted_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (n_deleted_out) *n_deleted_out = 0;
+    if (n < 0 || (n && (!d_pool || !d_bitmap || !d_deleted)))
+        return fail(ctx, MSSPE_ERR_ARG, "conflict cover: null pool, bitmap or output");
+    if (k < 2 || k > 32) return fail(ctx, MSSPE_ERR_K, "oligo length must be 2..32");
+    if (n > kCoverMaxN)
+        return fail(ctx, MSSPE_ERR_ARG, "conflict cover: " + std::to_string(n) + " oligos, at most " +
+                                            std::to_string(kCoverMaxN) + " (the symmetrised bitmap is n^2 / 8 bytes)");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::string err;
+    const int rc = ctx->cover.run(d_pool, n, k, d_bitmap, drop_self_pairs != 0, d_deleted, n_deleted_out, ctx->n_cu,
+                                  ctx->stream, err);
+    return rc ? fail(ctx, rc, err) : MSSPE_OK;
+}
+
+int msspe_conflict_cover(msspe_ctx *ctx, const char *pool_ascii, int n, int k, const msspe_chem *chem,
+                         float dg_threshold, int drop_self_pairs, uint8_t *deleted_out, int *n_deleted_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (n_deleted_out) *n_deleted_out = 0;
+    if (!pool_ascii || !chem || !deleted_out || n < 0)
+        return fail(ctx, MSSPE_ERR_ARG, "conflict cover: null pool, chemistry or output");
+    if (n == 0) return MSSPE_OK;
+    if (k < 2 || k > 32) return fail(ctx, MSSPE_ERR_K, "oligo length must be 2..32");
+    if (n > kCoverMaxN)
+        return fail(ctx, MSSPE_ERR_ARG, "conflict cover: " + std::to_string(n) + " oligos, at most " +
+                                            std::to_string(kCoverMaxN) + " (the symmetrised bitmap is n^2 / 8 bytes)");
+    std::vector<uint64_t> packed((size_t)n);
+    if (msspe_pack_oligos(pool_ascii, n, k, packed.data()))
+        return fail(ctx, MSSPE_ERR_ARG, "pool holds characters other than ACGT");
+    {   // duplicates before the screen, not after it
+        std::vector<uint64_t> s(packed);
+        std::sort(s.begin(), s.end());
+        if (std::adjacent_find(s.begin(), s.end()) != s.end())
+            return fail(ctx, MSSPE_ERR_ARG, "conflict cover: the pool holds duplicate oligos");
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t words = ((size_t)n + 63) / 64;
+    uint64_t *d_pool = nullptr, *d_bitmap = nullptr;
+    uint8_t *d_deleted = nullptr;
+    auto cleanup = [&]() {
+        if (d_pool) (void)hipFree(d_pool);
+        if (d_bitmap) (void)hipFree(d_bitmap);
+        if (d_deleted) (void)hipFree(d_deleted);
+    };
+#define TRY_OR_CLEAN4(expr)                                        \
+    do {                                                           \
+        hipError_t e__ = (expr);                                   \
+        if (e__ != hipSuccess) {                                   \
+            cleanup();                                             \
+            return hip_fail(ctx, e__, #expr);                      \
+        }                                                          \
+    } while (0)
+    TRY_OR_CLEAN4(hipMalloc((void **)&d_pool, sizeof(uint64_t) * (size_t)n));
+    TRY_OR_CLEAN4(hipMalloc((void **)&d_bitmap, sizeof(uint64_t) * (size_t)n * words));
+    TRY_OR_CLEAN4(hipMalloc((void **)&d_deleted, (size_t)n));
+    TRY_OR_CLEAN4(hipMemcpyAsync(d_pool, packed.data(), sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice,
+                                 ctx->stream));
+    // the screen's decisions only: the bitmap is all the cover reads
+    int rc = msspe_cross_dimer_dev(ctx, d_pool, n, k, chem, dg_threshold, 0, n, 0, n, nullptr, d_bitmap, nullptr,
+                                   nullptr);
+    if (!rc) rc = msspe_conflict_cover_dev(ctx, d_pool, n, k, d_bitmap, drop_self_pairs, d_deleted, n_deleted_out);
+    if (!rc) rc = check_list_overrun(ctx);   // the cover has synchronised the stream
+    if (rc) {
+        cleanup();
+        return rc;
+    }
+    TRY_OR_CLEAN4(hipMemcpyAsync(deleted_out, d_deleted, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    TRY_OR_CLEAN4(hipStreamSynchronize(ctx->stream));
+#undef TRY_OR_CLEAN4
+    cleanup();
+    return MSSPE_OK;
 }
 
 }  // extern "C"

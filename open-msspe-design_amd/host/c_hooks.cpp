@@ -62,7 +62,7 @@ int odm_parse_args(int argc, const char *const *argv, char *out, size_t cap)
           << "\nsearch_windows_size=" << a.search_windows_size << "\nmv_conc=" << a.mv_conc
           << "\ndelta_g_threshold=" << a.delta_g_threshold << "\nkeep_all=" << a.keep_all
           << "\ncheck_hairpin=" << a.check_hairpin << "\ndo_align=" << a.do_align
-          << "\ntm_stddev=" << a.tm_stddev << "\n";
+          << "\ntm_stddev=" << a.tm_stddev << "\ncover_on_device=" << a.cover_on_device << "\n";
         emit(o.str(), out, cap);
         return 0;
     } catch (const UsageError &e) {

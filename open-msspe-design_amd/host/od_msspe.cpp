@@ -70,6 +70,7 @@ const OptSpec kOpts[] = {
     {"--params-path", "MSSPE_PARAMS_PATH", OptSpec::Str, OFF(params_path)},
     {"--device", "MSSPE_DEVICE", OptSpec::Int, OFF(device)},
     {"--devices", "MSSPE_DEVICES", OptSpec::Str, OFF(devices)},
+    {"--cover-on-device", "COVER_ON_DEVICE", OptSpec::Bool, OFF(cover_on_device)},
 };
 #undef OFF
 
@@ -709,6 +710,29 @@ std::set<std::string> vertex_cover(const std::vector<std::string> &primers, cons
     return deleted;
 }
 
+std::set<std::string> conflict_cover_on_device(Engine &eng, const std::vector<std::string> &primers,
+                                               const NtthalOptions &opts, const ProgramConfig &cfg)
+{
+    std::set<std::string> deleted;
+    std::vector<std::string> nodes;   // run_ntthal's node list: duplicates collapse
+    std::unordered_set<std::string> seen;
+    for (const auto &p : primers)
+        if (seen.insert(p).second) nodes.push_back(p);
+    if (!cfg.check_cross_dimers || nodes.empty()) return deleted;   // delta_g.rs:71-73: no edges at all
+    const int n = (int)nodes.size(), k = (int)nodes[0].size();
+    std::string flat;
+    for (const auto &p : nodes) flat += p;
+    const msspe_chem chem = ntthal_chem(opts);
+    std::vector<uint8_t> del((size_t)n);
+    // --check-self-dimers false: the pairs ntthal_pair_sent() never sends are no edges
+    const int rc = msspe_conflict_cover(eng.ctx(), flat.data(), n, k, &chem, opts.dg, cfg.check_self_dimers ? 0 : 1,
+                                        del.data(), nullptr);
+    if (rc) eng.fail(rc);
+    for (int i = 0; i < n; ++i)
+        if (del[(size_t)i]) deleted.insert(nodes[(size_t)i]);
+    return deleted;
+}
+
 // ---------------------------------------------------------------------------------------------
 // report + CSV (main.rs:518-594, 834-858): host-side text
 // ---------------------------------------------------------------------------------------------
@@ -939,6 +963,8 @@ int run(const Args &args, std::string &stdout_text)
         devices.push_back((int)d);
         at = comma + 1;
     }
+    if (!devices.empty() && args.cover_on_device == "true")
+        throw UsageError("error: '--cover-on-device true' runs on one device and cannot be combined with '--devices'");
     std::unique_ptr<Engine> eng_owner(devices.empty() ? new Engine(args.device, args.params_path)
                                                       : new Engine(devices, args.params_path));
     Engine &eng = *eng_owner;
@@ -972,8 +998,8 @@ int run(const Args &args, std::string &stdout_text)
     std::vector<std::string> primers;
     for (const auto &s : prim_f) primers.push_back(s.word);
     for (const auto &s : prim_r) primers.push_back(s.word);
-    const ConflictGraph graph = run_ntthal(eng, primers, opts, cfg);
-    const auto deleted = vertex_cover(primers, graph);
+    const auto deleted = args.cover_on_device == "true" ? conflict_cover_on_device(eng, primers, opts, cfg)
+                                                        : vertex_cover(primers, run_ntthal(eng, primers, opts, cfg));
     std::vector<KmerStat> good_f, good_r;
     for (const auto &p : prim_f)
         if (cfg.keep_all || !deleted.count(p.word)) good_f.push_back(p);

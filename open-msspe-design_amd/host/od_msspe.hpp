@@ -53,6 +53,7 @@ struct Args {
     std::string devices;           // "0,1,2,...": the N^2 pair loop and stage B run on a group of devices (msspe_group_*)
     std::string params_path;       // Primer3 config directory; empty = bundled tables
     std::string existing_primers;  // a panel to extend: CSV in this tool's output format (direction and primers read)
+    std::string cover_on_device = "false";   // "true": the screen and the vertex cover as one device call (msspe_conflict_cover)
     bool stddev_population = false;  // crate std-dev 0.1.0's divisor is unpinned
     static Args parse(int argc, const char *const *argv);   // throws UsageError
     static std::string usage();
@@ -177,6 +178,10 @@ ConflictGraph run_ntthal(Engine &eng, const std::vector<std::string> &primers,
                          const NtthalOptions &opts, const ProgramConfig &cfg);
 // main.rs:754-798: primers removed by the greedy vertex cover
 std::set<std::string> vertex_cover(const std::vector<std::string> &primers, const ConflictGraph &g);
+// --cover-on-device true: run_ntthal + vertex_cover as one msspe_conflict_cover call over the distinct primers (the
+// screen's bitmap and the cover stay on the device); the same set
+std::set<std::string> conflict_cover_on_device(Engine &eng, const std::vector<std::string> &primers,
+                                               const NtthalOptions &opts, const ProgramConfig &cfg);
 // main.rs:518-594 (text goes to `out`): the per-segment search runs on the device
 // (msspe_segment_coverage_dev), the totals per sequence / partition and the text on the host
 std::string coverage_report(Engine &eng, const DeviceAlignment &aln, const std::vector<KmerStat> &fwd,

@@ -21,6 +21,7 @@ EXPORTS = [
     "msspe_cross_dimer_edges_mixed",
     "msspe_cross_dimer_end_dev", "msspe_cross_dimer_end", "msspe_cross_dimer_end_edges_dev", "msspe_cross_dimer_end_edges",
     "msspe_cross_dimer_end_ab_dev", "msspe_cross_dimer_end_ab", "msspe_t_cut",
+    "msspe_conflict_cover_dev", "msspe_conflict_cover",
     "msspe_last_overflow_pairs", "msspe_pair_stage_stats", "msspe_pair_stage_samples", "msspe_host_pair_tables", "msspe_host_split_tables", "msspe_device_put_rows", "msspe_segment_coverage", "msspe_segment_coverage_dev",
     "msspe_device_put", "msspe_device_free", "msspe_thal_detail_pairs", "msspe_profile_enable", "msspe_profile_read",
     "msspe_oligo_stats_dev", "msspe_oligo_stats",
@@ -151,6 +152,9 @@ def load_library() -> C.CDLL:
     L.msspe_cross_dimer_end_edges.argtypes = L.msspe_cross_dimer_edges.argtypes
     L.msspe_cross_dimer_end_ab_dev.argtypes = L.msspe_cross_dimer_ab_dev.argtypes
     L.msspe_cross_dimer_end_ab.argtypes = L.msspe_cross_dimer_ab.argtypes
+    L.msspe_conflict_cover_dev.argtypes = [vp, u64p, C.c_int, C.c_int, u64p, C.c_int, vp, C.POINTER(C.c_int)]
+    L.msspe_conflict_cover.argtypes = [vp, C.c_char_p, C.c_int, C.c_int, C.POINTER(Chem), C.c_float, C.c_int, vp,
+                                       C.POINTER(C.c_int)]
     L.msspe_last_overflow_pairs.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.msspe_pair_stage_stats.argtypes = [vp, C.POINTER(C.c_uint64)]   # out[16]
     L.msspe_pair_stage_samples.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int, C.POINTER(C.c_int)]
@@ -446,6 +450,29 @@ class Engine:
             err.edges = edges
             raise err
         return edges[:count.value], int(count.value)
+
+    # ---- the greedy vertex cover of the conflict graph (od-msspe/src/main.rs:754-798; msspe_conflict_cover*) ------
+    def conflict_cover(self, pool, chem: Chem | None = None, threshold: float = -9000.0,
+                       drop_self_pairs: bool = False) -> np.ndarray:
+        """Screen a pool of distinct oligos of one length and cover its conflict graph on the device
+        (msspe_conflict_cover): bool[n], True = removed by the reference's greedy cover.  drop_self_pairs: the
+        reference's --check-self-dimers false.  Rounds of the call: info("cover_rounds")."""
+        buf, n, k = _ascii(pool)
+        chem = chem or Chem.ntthal()
+        out = np.zeros(n, dtype=np.uint8)
+        nd = C.c_int(0)
+        self._check(self.L.msspe_conflict_cover(self.ptr, buf, n, k or 2, C.byref(chem), C.c_float(threshold),
+                                                int(bool(drop_self_pairs)), out.ctypes.data, C.byref(nd)))
+        return out.astype(bool)
+
+    def conflict_cover_dev(self, d_pool: int, n: int, k: int, d_bitmap: int, d_deleted: int,
+                           drop_self_pairs: bool = False) -> int:
+        """Device-pointer cover (msspe_conflict_cover_dev): d_bitmap n x ceil(n/64) uint64 as cross_dimer_dev writes
+        the full block, d_deleted n bytes (1 = removed).  Returns the number of removed oligos; synchronises."""
+        nd = C.c_int(0)
+        self._check(self.L.msspe_conflict_cover_dev(self.ptr, C.c_void_p(d_pool), n, k, C.c_void_p(d_bitmap),
+                                                    int(bool(drop_self_pairs)), C.c_void_p(d_deleted), C.byref(nd)))
+        return int(nd.value)
 
     # ---- stage C, 3'-end dimers (thal END1 for every ordered pair; include/msspe_hip.h msspe_cross_dimer_end*) ------
     def cross_dimer_end(self, pool, chem: Chem | None = None, tm_threshold: float = END_TM_THRESHOLD,
