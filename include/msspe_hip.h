@@ -338,6 +338,8 @@ int msspe_profile_read(msspe_ctx *ctx, uint64_t *launches, double *total_ms);
  * against itself and of thal HAIRPIN -- PRIMER_LEFT_0_{TM,GC_PERCENT,SELF_ANY_TH,SELF_END_TH,
  * HAIRPIN_TH} (od-msspe/src/primer.rs:79-111).  Raw doubles; the text rounding primer3_core /
  * od-msspe apply (%.3f / %.2f -> f32) is msspe_round_fixed_f32().
+ * A negative chem->mv or dv, or a negative dntp with dv != 0, is MSSPE_ERR_ARG (oligotm's
+ * OLIGOTM_ERROR; with dv == 0 oligotm zeroes dntp before it checks it).
  */
 int msspe_oligo_stats_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k,
                           const msspe_chem *chem, double *d_tm, double *d_gc,

@@ -1623,6 +1623,11 @@ int msspe_oligo_stats_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k,
     if (!ctx) return MSSPE_ERR_ARG;
     if (!d_pool || !chem || n < 0) return fail(ctx, MSSPE_ERR_ARG, "null pool/chemistry");
     if (k < 2 || k > 32) return fail(ctx, MSSPE_ERR_K, "oligo length must be 2..32");
+    // oligotm.c divalent_to_monovalent() returns OLIGOTM_ERROR for a negative divalent or dNTP concentration, the
+    // dNTP one tested after "dv == 0 -> dntp = 0" (so dv 0 with any dNTP is valid); a negative monovalent one is
+    // refused as well.  (thal's own salt term clamps instead: the cross-dimer entry points accept them.)
+    if (!(chem->mv >= 0) || !(chem->dv >= 0) || !(chem->dv == 0 || chem->dntp >= 0))
+        return fail(ctx, MSSPE_ERR_ARG, "chemistry: stage B needs mv >= 0, dv >= 0 and (dv == 0 or dntp >= 0)");
     if (n == 0) return MSSPE_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     ChemEntry *ce = nullptr;

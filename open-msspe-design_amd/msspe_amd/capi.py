@@ -54,8 +54,8 @@ class Chem(C.Structure):
         return cls(mv, dv, dntp, dna_conc, temp_c, max_loop)
 
     @classmethod
-    def primer3(cls):
-        return cls(50.0, 1.5, 0.6, 50.0, 37.0, 30)
+    def primer3(cls, mv=50.0, dv=1.5, dntp=0.6, dna_conc=50.0, temp_c=37.0, max_loop=30):
+        return cls(mv, dv, dntp, dna_conc, temp_c, max_loop)
 
 
 class KmerOpt(C.Structure):

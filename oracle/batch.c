@@ -93,9 +93,19 @@ int orc_pool_op_stats(const orc_tables *t, const char *pool, int n, int k,
     return 0;
 }
 
-/* primer3_core view of a list of oligos (n x k chars). */
+/* primer3_core view of a list of oligos (n x k chars), at Primer3's defaults or at the chemistry a. */
 int orc_check_primers(const orc_tables *t, const char *pool, int n, int k, orc_primer_info *out);
+int orc_check_primers_args(const orc_tables *t, const char *pool, int n, int k, const orc_thal_args *a,
+                           orc_primer_info *out);
 int orc_check_primers(const orc_tables *t, const char *pool, int n, int k, orc_primer_info *out)
+{
+    orc_thal_args a;
+    orc_p3_default_args(&a);
+    return orc_check_primers_args(t, pool, n, k, &a, out);
+}
+
+int orc_check_primers_args(const orc_tables *t, const char *pool, int n, int k, const orc_thal_args *a,
+                           orc_primer_info *out)
 {
     if (k < 1 || k >= ORC_MAX_OLIGO) return -1;
     int rc = 0;
@@ -103,10 +113,10 @@ int orc_check_primers(const orc_tables *t, const char *pool, int n, int k, orc_p
 #pragma omp parallel for schedule(dynamic, 8)
 #endif
     for (int i = 0; i < n; i++) {
-        char a[ORC_MAX_OLIGO];
-        memcpy(a, pool + (size_t)i * k, (size_t)k);
-        a[k] = 0;
-        if (orc_check_primer(t, a, &out[i])) rc = -1;
+        char o[ORC_MAX_OLIGO];
+        memcpy(o, pool + (size_t)i * k, (size_t)k);
+        o[k] = 0;
+        if (orc_check_primer_args(t, o, a, &out[i])) rc = -1;
     }
     return rc;
 }

@@ -120,7 +120,10 @@ typedef struct {
     double tm, gc, self_any_th, self_end_th, hairpin_th;           /* raw f64           */
     float tm_f32, gc_f32, self_any_f32, self_end_f32, hairpin_f32; /* %.3f/%.2f -> f32  */
 } orc_primer_info;
-int orc_check_primer(const orc_tables *t, const char *oligo, orc_primer_info *out);
+int orc_check_primer(const orc_tables *t, const char *oligo, orc_primer_info *out);   /* Primer3's defaults */
+/* at the chemistry a: oligotm reads mv, dv, dntp, dna_conc; thal ANY / END1 / HAIRPIN all six fields */
+int orc_check_primer_args(const orc_tables *t, const char *oligo, const orc_thal_args *a,
+                          orc_primer_info *out);
 
 /* ------------------------------------------------------------------------------------------
  * Text rounding at the process boundary

@@ -171,16 +171,24 @@ float orc_round_fixed_f32(double x, int decimals)
 int orc_check_primer(const orc_tables *t, const char *oligo, orc_primer_info *out)
 {
     orc_thal_args a;
-    orc_thal_result r;
     orc_p3_default_args(&a);
+    return orc_check_primer_args(t, oligo, &a, out);
+}
+
+/* The same view at the chemistry of a record that sets PRIMER_SALT_MONOVALENT / _DIVALENT / PRIMER_DNTP_CONC /
+ * PRIMER_DNA_CONC (oligotm and thal read the same four values) and, for thal, its temperature and maxLoop. */
+int orc_check_primer_args(const orc_tables *t, const char *oligo, const orc_thal_args *a,
+                          orc_primer_info *out)
+{
+    orc_thal_result r;
     memset(out, 0, sizeof *out);
-    out->tm = orc_oligotm(oligo, a.dna_conc, a.mv, a.dv, a.dntp);
+    out->tm = orc_oligotm(oligo, a->dna_conc, a->mv, a->dv, a->dntp);
     out->gc = orc_gc_percent(oligo);
-    if (orc_thal_dimer(t, oligo, oligo, ORC_THAL_ANY, &a, &r)) return -1;
+    if (orc_thal_dimer(t, oligo, oligo, ORC_THAL_ANY, a, &r)) return -1;
     out->self_any_th = (r.no_structure || r.t < 0.0) ? 0.0 : r.t;
-    if (orc_thal_dimer(t, oligo, oligo, ORC_THAL_END1, &a, &r)) return -1;
+    if (orc_thal_dimer(t, oligo, oligo, ORC_THAL_END1, a, &r)) return -1;
     out->self_end_th = (r.no_structure || r.t < 0.0) ? 0.0 : r.t;
-    if (orc_thal_hairpin(t, oligo, &a, &r)) return -1;
+    if (orc_thal_hairpin(t, oligo, a, &r)) return -1;
     out->hairpin_th = (r.no_structure || r.t < 0.0) ? 0.0 : r.t;
     out->tm_f32 = orc_round_fixed_f32(out->tm, 3);
     out->gc_f32 = orc_round_fixed_f32(out->gc, 3);

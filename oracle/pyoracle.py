@@ -81,6 +81,9 @@ def lib() -> C.CDLL:
         L.orc_gc_percent.argtypes = [C.c_char_p]
         L.orc_check_primer.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(PrimerInfo)]
         L.orc_check_primers.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_void_p]
+        L.orc_check_primer_args.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(ThalArgs), C.POINTER(PrimerInfo)]
+        L.orc_check_primers_args.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(ThalArgs),
+                                             C.c_void_p]
         L.orc_round_g_f32.restype = C.c_float
         L.orc_round_g_f32.argtypes = [C.c_double]
         L.orc_round_fixed_f32.restype = C.c_float
@@ -147,8 +150,9 @@ def ntthal_args(mv=50.0, dv=3.0, dntp=0.0, dna_conc=250.0, temp_c=25.0, max_loop
     return ThalArgs(mv, dv, dntp, dna_conc, temp_c + 273.15, max_loop)
 
 
-def p3_args() -> ThalArgs:
-    return ThalArgs(50.0, 1.5, 0.6, 50.0, 310.15, 30)
+def p3_args(mv=50.0, dv=1.5, dntp=0.6, dna_conc=50.0, temp_c=37.0, max_loop=30) -> ThalArgs:
+    """primer3_core's chemistry (defaults: Primer3 2.6.1's)."""
+    return ThalArgs(mv, dv, dntp, dna_conc, temp_c + 273.15, max_loop)
 
 
 def thal(tables: Tables, a: str, b: str, mode: int = ANY, args: ThalArgs | None = None) -> ThalResult:
@@ -178,8 +182,9 @@ def check_primer(tables: Tables, oligo: str) -> PrimerInfo:
     return info
 
 
-def check_primers(tables: Tables, oligos: list[str]) -> np.ndarray:
-    """Returns a structured array with the PrimerInfo fields for every oligo."""
+def check_primers(tables: Tables, oligos: list[str], args: ThalArgs | None = None) -> np.ndarray:
+    """Returns a structured array with the PrimerInfo fields for every oligo, at the chemistry args
+    (None: Primer3's defaults, p3_args())."""
     n = len(oligos)
     k = len(oligos[0]) if n else 0
     dt = np.dtype([("tm", "f8"), ("gc", "f8"), ("self_any_th", "f8"), ("self_end_th", "f8"),
@@ -188,7 +193,9 @@ def check_primers(tables: Tables, oligos: list[str]) -> np.ndarray:
                    ("_pad", "f4")])
     assert dt.itemsize == C.sizeof(PrimerInfo)
     out = np.zeros(n, dtype=dt)
-    if n and lib().orc_check_primers(tables.ptr, "".join(oligos).encode(), n, k, out.ctypes.data):
+    args = args if args is not None else p3_args()
+    if n and lib().orc_check_primers_args(tables.ptr, "".join(oligos).encode(), n, k, C.byref(args),
+                                          out.ctypes.data):
         raise ValueError("oracle check_primers failed")
     return out
 

@@ -8,6 +8,8 @@ import json
 import numpy as np
 import pytest
 
+from helpers import with_stem_loops
+
 pytestmark = pytest.mark.gpu
 
 
@@ -191,6 +193,9 @@ def test_self_dimers_of_a_large_pool_one_lane_per_oligo(eng, m, oracle, oracle_t
     got = eng.oligo_stats(words)
     np.testing.assert_array_equal(got["self_any"], ref["self_any_th"])
     np.testing.assert_array_equal(got["self_end"], ref["self_end_th"])
+    np.testing.assert_array_equal(got["tm"], ref["tm"])
+    np.testing.assert_array_equal(got["gc"], ref["gc"])
+    np.testing.assert_array_equal(got["hairpin"], ref["hairpin_th"])
     assert (got["self_any"] > 0).sum() > n // 100 and (got["self_end"] > 0).sum() > n // 200
     # each statistic asked for alone (one finish per fill), on the device-pointer entry point
     d_pool = torch.from_numpy(m.pack_oligos(pool).view(np.int64)).cuda()
@@ -741,18 +746,7 @@ def test_hairpin_wave_kernel_bit_exact(m, oracle, oracle_tables, k, n):
     one-lane kernel over a global workspace (option force_generic)."""
     rng = np.random.default_rng(1000 + k)
     pool = m.synth.pool_strings(m.synth.random_pool(n, k, seed=3000 + k))
-    for q in range(n // 4):                                   # every fourth oligo: a designed hairpin
-        stem = int(rng.integers(4, 8))
-        loop = int(rng.integers(3, 7))
-        if 2 * stem + loop > k:
-            stem = (k - loop) // 2
-        left = "".join("ACGT"[x] for x in rng.integers(0, 4, stem))
-        mid = "".join("ACGT"[x] for x in rng.integers(0, 4, loop))
-        core = left + mid + oracle.reverse_complement(left)
-        pad = k - len(core)
-        off = int(rng.integers(0, pad + 1))
-        flank = "".join("ACGT"[x] for x in rng.integers(0, 4, pad))
-        pool[4 * q] = flank[:off] + core + flank[off:]
+    with_stem_loops(pool, k, rng)                              # every fourth oligo: a designed hairpin
     eng = m.Engine(0)
     try:
         got = eng.oligo_stats(pool)["hairpin"]
