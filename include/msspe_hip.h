@@ -450,6 +450,43 @@ int msspe_segment_coverage_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, 
                                       const uint64_t *rev_words, int n_rev, uint8_t *hit_out);
 int msspe_device_free(msspe_ctx *ctx, void *device);
 
+/* ---- coverage within N mismatches, the primer's 3' end exact (engine extension, no reference counterpart) ----
+ * Generalises the exact rule of coverage_report() (od-msspe/src/main.rs:518-594, msspe_segment_coverage*): the same
+ * segments (record r, partition j, P = (seq_len - segment_size) / overlap_size + 1) and windows.  For each position p
+ * in [0, W - k] (W = search_window_size, k = kmer_size, 1 <= k <= 31) the FORWARD candidate is the k bases of the head
+ * window at p, the REVERSE candidate the reverse complement of the k bases of the tail window at p.  A position that
+ * holds any base other than A / C / G / T ('-', N, IUPAC codes) is never a match, at any max_mismatches (main.rs:167;
+ * a gap column is not a base, so it is not a mismatch either).  A candidate w matches a primer word u of its direction
+ * (fwd_words / rev_words: msspe_pack_oligos form, a reverse word in primer orientation as the CSV writes it) when
+ *   - the number of base positions q in [0, k) where w and u differ is <= max_mismatches, and
+ *   - they agree at every q in [k - exact_3p, k): the primer's last exact_3p bases (its 3' end) match.
+ * best_out[r * P + j] (host, n_seq * P bytes): the smallest mismatch count over all matches in the segment, either
+ * direction; 255 when there is none.  primer_segments_out (host, optional, n_fwd + n_rev: forward primers first, then
+ * reverse, in the caller's order): the number of segments whose head (forward) / tail (reverse) window holds at least
+ * one match of that primer; duplicates are counted independently.  NULL: that work is not done.
+ * At max_mismatches 0, best_out == 0 exactly where msspe_segment_coverage's hit_out is 1, for every exact_3p.
+ * MSSPE_ERR_ARG: mm, best_out, or a primer list with a nonzero count NULL; max_mismatches or exact_3p outside 0..k;
+ * a primer word with bits above 2 k; window, segment or stride as msspe_segment_coverage.  MSSPE_ERR_K: k outside
+ * 1..31.  No segments: MSSPE_OK with primer_segments_out zeroed.  The *_dev / *_packed_dev forms read the alignment
+ * from the device (bytes as msspe_segment_coverage_dev, packed rows as msspe_device_put_rows_packed makes them). */
+typedef struct {
+    int max_mismatches;   /* 0 .. kmer_size */
+    int exact_3p;         /* 0 .. kmer_size: the primer's last exact_3p bases must match */
+} msspe_mismatch_opt;
+
+int msspe_segment_coverage_mm(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len,
+                              const msspe_kmer_opt *opt, const msspe_mismatch_opt *mm,
+                              const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
+                              uint8_t *best_out, uint32_t *primer_segments_out);
+int msspe_segment_coverage_mm_dev(msspe_ctx *ctx, const uint8_t *d_seqs, int n_seq, size_t seq_len,
+                                  const msspe_kmer_opt *opt, const msspe_mismatch_opt *mm,
+                                  const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
+                                  uint8_t *best_out, uint32_t *primer_segments_out);
+int msspe_segment_coverage_mm_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
+                                         const msspe_kmer_opt *opt, const msspe_mismatch_opt *mm,
+                                         const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
+                                         uint8_t *best_out, uint32_t *primer_segments_out);
+
 
 /* ---- several devices of one node ----------------------------------------------------------
  *

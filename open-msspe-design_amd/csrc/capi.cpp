@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "conflict_cover.hpp"
+#include "coverage_mm.hpp"
 #include "kernels.hpp"
 #include "kmer_stage.hpp"
 #include "nn_params.hpp"
@@ -105,6 +106,7 @@ struct msspe_ctx {
     KmerStage kmer_rev;                // direction 1 of msspe_kmer_candidates_both_packed_dev (its own buffers and loop graph)
     hipStream_t stream_rev = nullptr;  // ... and its stream
     hipEvent_t ev_rev = nullptr;
+    MismatchCoverage mm_cov;           // msspe_segment_coverage_mm*: primer words, counts, per-segment minima
     CoverStage cover;                  // msspe_conflict_cover*: the symmetrised bitmap and the round state
     // optional profiling of the dominant kernel (k_pairs_fast) with HIP events on ctx->stream
     bool prof_on = false;
@@ -455,6 +457,7 @@ void msspe_destroy(msspe_ctx *ctx)
         ctx->kmer.release();
         ctx->kmer_rev.release();
         ctx->cover.release();
+        ctx->mm_cov.release();
         if (ctx->ev_rev) (void)hipEventDestroy(ctx->ev_rev);
         if (ctx->stream_rev) {
             (void)hipStreamSynchronize(ctx->stream_rev);
@@ -1927,6 +1930,59 @@ int msspe_segment_coverage(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_
     if (rc) return rc;
     rc = msspe_segment_coverage_dev(ctx, (const uint8_t *)d, n_seq, seq_len, opt, fwd_words, n_fwd, rev_words,
                                     n_rev, hit_out);
+    (void)msspe_device_free(ctx, d);
+    return rc;
+}
+
+static int segment_coverage_mm_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t seq_len,
+                                    const msspe_kmer_opt *opt, const msspe_mismatch_opt *mm,
+                                    const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
+                                    uint8_t *best_out, uint32_t *primer_segments_out)
+{
+    if (!opt || !mm || !best_out || n_fwd < 0 || n_rev < 0 || (n_fwd && !fwd_words) || (n_rev && !rev_words))
+        return fail(ctx, MSSPE_ERR_ARG, "null argument");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::string err;
+    const int rc = ctx->mm_cov.run(view, n_seq, seq_len, *opt, mm->max_mismatches, mm->exact_3p, fwd_words, n_fwd,
+                                   rev_words, n_rev, best_out, primer_segments_out, ctx->stream, err);
+    if (rc) return fail(ctx, rc, err);
+    return MSSPE_OK;
+}
+
+int msspe_segment_coverage_mm_dev(msspe_ctx *ctx, const uint8_t *d_seqs, int n_seq, size_t seq_len,
+                                  const msspe_kmer_opt *opt, const msspe_mismatch_opt *mm,
+                                  const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
+                                  uint8_t *best_out, uint32_t *primer_segments_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!d_seqs) return fail(ctx, MSSPE_ERR_ARG, "null sequences");
+    return segment_coverage_mm_view(ctx, SeqView{d_seqs, nullptr, seq_len}, n_seq, seq_len, opt, mm, fwd_words,
+                                    n_fwd, rev_words, n_rev, best_out, primer_segments_out);
+}
+
+int msspe_segment_coverage_mm_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
+                                         const msspe_kmer_opt *opt, const msspe_mismatch_opt *mm,
+                                         const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
+                                         uint8_t *best_out, uint32_t *primer_segments_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!d_packed) return fail(ctx, MSSPE_ERR_ARG, "null sequences");
+    return segment_coverage_mm_view(ctx, SeqView{nullptr, d_packed, seq_len}, n_seq, seq_len, opt, mm, fwd_words,
+                                    n_fwd, rev_words, n_rev, best_out, primer_segments_out);
+}
+
+int msspe_segment_coverage_mm(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len,
+                              const msspe_kmer_opt *opt, const msspe_mismatch_opt *mm,
+                              const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
+                              uint8_t *best_out, uint32_t *primer_segments_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!seqs || n_seq < 0) return fail(ctx, MSSPE_ERR_ARG, "null sequences");
+    void *d = nullptr;
+    int rc = msspe_device_put(ctx, seqs, (size_t)n_seq * seq_len, &d);
+    if (rc) return rc;
+    rc = msspe_segment_coverage_mm_dev(ctx, (const uint8_t *)d, n_seq, seq_len, opt, mm, fwd_words, n_fwd, rev_words,
+                                       n_rev, best_out, primer_segments_out);
     (void)msspe_device_free(ctx, d);
     return rc;
 }

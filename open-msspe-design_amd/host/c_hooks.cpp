@@ -62,7 +62,8 @@ int odm_parse_args(int argc, const char *const *argv, char *out, size_t cap)
           << "\nsearch_windows_size=" << a.search_windows_size << "\nmv_conc=" << a.mv_conc
           << "\ndelta_g_threshold=" << a.delta_g_threshold << "\nkeep_all=" << a.keep_all
           << "\ncheck_hairpin=" << a.check_hairpin << "\ndo_align=" << a.do_align
-          << "\ntm_stddev=" << a.tm_stddev << "\ncover_on_device=" << a.cover_on_device << "\n";
+          << "\ntm_stddev=" << a.tm_stddev << "\ncover_on_device=" << a.cover_on_device
+          << "\ncoverage_mismatches=" << a.coverage_mismatches << "\ncoverage_3p_exact=" << a.coverage_3p_exact << "\n";
         emit(o.str(), out, cap);
         return 0;
     } catch (const UsageError &e) {
@@ -142,6 +143,29 @@ int odm_coverage_report(const char *records_nl, const char *fwd_nl, const char *
     } catch (const std::exception &e) {
         emit(e.what(), out, cap);
         return -2;   // no usable GPU: the text is the reason
+    }
+}
+
+// The block od-msspe-hip --coverage-mismatches N --coverage-3p-exact E prints after the exact report (the text of
+// odm_coverage_report): segments covered within max_mismatches, the last exact_3p bases exact (msspe_segment_coverage_mm)
+int odm_coverage_report_mm(const char *records_nl, const char *fwd_nl, const char *rev_nl, int segment, int stride,
+                           int window, int k, int max_mismatches, int exact_3p, char *out, size_t cap)
+{
+    std::vector<SequenceRecord> recs;
+    for (const auto &l : lines(records_nl)) {
+        const size_t t = l.find('\t');
+        recs.push_back({l.substr(0, t), l.substr(t + 1)});
+    }
+    std::vector<KmerStat> f, r;
+    for (const auto &w : lines(fwd_nl)) f.push_back({w, SEQ_DIR_FWD, 0, 0, 0, 0, true, 0, 0, 0, false});
+    for (const auto &w : lines(rev_nl)) r.push_back({w, SEQ_DIR_REV, 0, 0, 0, 0, true, 0, 0, 0, false});
+    try {
+        Engine eng(0, "");
+        return emit(coverage_report_mm(eng, f, r, recs, segment, stride, window, k, max_mismatches, exact_3p), out,
+                    cap);
+    } catch (const std::exception &e) {
+        emit(e.what(), out, cap);
+        return -2;   // no usable GPU (or an engine error): the text is the reason
     }
 }
 

@@ -71,6 +71,8 @@ const OptSpec kOpts[] = {
     {"--device", "MSSPE_DEVICE", OptSpec::Int, OFF(device)},
     {"--devices", "MSSPE_DEVICES", OptSpec::Str, OFF(devices)},
     {"--cover-on-device", "COVER_ON_DEVICE", OptSpec::Bool, OFF(cover_on_device)},
+    {"--coverage-mismatches", "COVERAGE_MISMATCHES", OptSpec::Int, OFF(coverage_mismatches)},
+    {"--coverage-3p-exact", "COVERAGE_3P_EXACT", OptSpec::Str, OFF(coverage_3p_exact_text)},
 };
 #undef OFF
 
@@ -154,6 +156,19 @@ Args Args::parse(int argc, const char *const *argv)
     if (a.input.empty() || a.output.empty())
         throw UsageError("error: the following required arguments were not provided:\n"
                          "  --input <INPUT>\n  --output <OUTPUT>\n\n" + usage());
+    if (a.coverage_mismatches > a.kmer_size)
+        throw UsageError("error: '--coverage-mismatches " + std::to_string(a.coverage_mismatches) +
+                         "' is larger than '--kmer-size " + std::to_string(a.kmer_size) + "'");
+    if (a.coverage_mismatches > 0) {
+        const std::string &v = a.coverage_3p_exact_text;
+        char *end = nullptr;
+        const long e = std::strtol(v.c_str(), &end, 10);
+        if (v.empty() || *end || e < 0) throw UsageError("error: invalid value '" + v + "' for '--coverage-3p-exact'");
+        if (e > a.kmer_size)
+            throw UsageError("error: '--coverage-3p-exact " + v + "' is larger than '--kmer-size " +
+                             std::to_string(a.kmer_size) + "'");
+        a.coverage_3p_exact = (int)e;
+    }
     return a;
 }
 
@@ -758,6 +773,56 @@ std::vector<uint64_t> pack_words(Engine &eng, const std::vector<KmerStat> &list,
 
 }  // namespace
 
+namespace {
+// The three lines of main.rs:574-593 under a heading: segments covered, sequences at >= 80 %, uncovered partitions.
+// covered_at(record * P + partition): the rule the caller counts by (segments past a short record's end are not
+// counted, as the reference's partitions of that record).
+template <typename Covered>
+std::string coverage_lines(const std::vector<SequenceRecord> &records, size_t P, int segment_size, int overlap_size,
+                           Covered covered_at)
+{
+    size_t total = 0, covered = 0;
+    std::map<std::string, std::pair<size_t, size_t>> seq_stats;        // name -> (covered, total)
+    std::map<uint16_t, std::pair<size_t, size_t>> partition_stats;
+    for (size_t ri = 0; ri < records.size(); ++ri) {
+        const auto &r = records[ri];
+        const size_t len = r.sequence.size();
+        auto &se = seq_stats[r.name];
+        for (size_t j = 0; (size_t)segment_size <= len && j * (size_t)overlap_size + (size_t)segment_size <= len; ++j) {
+            const bool h = covered_at(ri * P + j);
+            auto &pe = partition_stats[(uint16_t)j];
+            se.second += 1;
+            pe.second += 1;
+            total += 1;
+            if (h) {
+                se.first += 1;
+                pe.first += 1;
+                covered += 1;
+            }
+        }
+    }
+    float min_cov = INFINITY, max_cov = -INFINITY;
+    size_t well = 0;
+    for (const auto &kv : seq_stats) {
+        const float c = (float)kv.second.first / (float)kv.second.second * 100.0f;
+        min_cov = std::fmin(min_cov, c);
+        max_cov = std::fmax(max_cov, c);
+        if (c >= 80.0f) ++well;
+    }
+    std::string out = "  Segments:  " + std::to_string(covered) + "/" + std::to_string(total) + " covered (" +
+           fmt("%.1f", (double)(100.0f * (float)covered / (float)total)) + "%)\n";
+    out += "  Sequences: " + std::to_string(well) + "/" + std::to_string(seq_stats.size()) +
+           " at \xe2\x89\xa5" "80% coverage (min " + fmt("%.1f", (double)min_cov) + "%, max " +
+           fmt("%.1f", (double)max_cov) + "%)\n";
+    std::string unc;
+    for (const auto &kv : partition_stats)
+        if (kv.second.first == 0) unc += (unc.empty() ? "" : ", ") + std::to_string(kv.first);
+    if (unc.empty()) out += "  All partitions have primer coverage\n";
+    else out += "  Uncovered partitions: [" + unc + "]\n";
+    return out;
+}
+}  // namespace
+
 std::string coverage_report(Engine &eng, const std::vector<KmerStat> &fwd, const std::vector<KmerStat> &rev,
                             const std::vector<SequenceRecord> &records, int segment_size,
                             int overlap_size, int window_size, int kmer_size)
@@ -781,45 +846,51 @@ std::string coverage_report(Engine &eng, const DeviceAlignment &aln, const std::
                                                   (int)wf.size(), wr.data(), (int)wr.size(), hit.data());
         if (rc) eng.fail(rc);
     }
-    size_t total = 0, covered = 0;
-    std::map<std::string, std::pair<size_t, size_t>> seq_stats;        // name -> (covered, total)
-    std::map<uint16_t, std::pair<size_t, size_t>> partition_stats;
-    for (size_t ri = 0; ri < records.size(); ++ri) {
-        const auto &r = records[ri];
-        const size_t len = r.sequence.size();
-        auto &se = seq_stats[r.name];
-        for (size_t j = 0; (size_t)segment_size <= len && j * (size_t)overlap_size + (size_t)segment_size <= len; ++j) {
-            const bool h = hit[ri * P + j] != 0;
-            auto &pe = partition_stats[(uint16_t)j];
-            se.second += 1;
-            pe.second += 1;
-            total += 1;
-            if (h) {
-                se.first += 1;
-                pe.first += 1;
-                covered += 1;
-            }
-        }
-    }
-    float min_cov = INFINITY, max_cov = -INFINITY;
-    size_t well = 0;
-    for (const auto &kv : seq_stats) {
-        const float c = (float)kv.second.first / (float)kv.second.second * 100.0f;
-        min_cov = std::fmin(min_cov, c);
-        max_cov = std::fmax(max_cov, c);
-        if (c >= 80.0f) ++well;
-    }
     std::string out = "\nCoverage report:\n";
-    out += "  Segments:  " + std::to_string(covered) + "/" + std::to_string(total) + " covered (" +
-           fmt("%.1f", (double)(100.0f * (float)covered / (float)total)) + "%)\n";
-    out += "  Sequences: " + std::to_string(well) + "/" + std::to_string(seq_stats.size()) +
-           " at \xe2\x89\xa5" "80% coverage (min " + fmt("%.1f", (double)min_cov) + "%, max " +
-           fmt("%.1f", (double)max_cov) + "%)\n";
-    std::string unc;
-    for (const auto &kv : partition_stats)
-        if (kv.second.first == 0) unc += (unc.empty() ? "" : ", ") + std::to_string(kv.first);
-    if (unc.empty()) out += "  All partitions have primer coverage\n";
-    else out += "  Uncovered partitions: [" + unc + "]\n";
+    out += coverage_lines(records, P, segment_size, overlap_size, [&](size_t i) { return hit[i] != 0; });
+    return out;
+}
+
+std::string coverage_report_mm(Engine &eng, const std::vector<KmerStat> &fwd, const std::vector<KmerStat> &rev,
+                               const std::vector<SequenceRecord> &records, int segment_size, int overlap_size,
+                               int window_size, int kmer_size, int max_mismatches, int exact_3p)
+{
+    const DeviceAlignment aln(eng, records);
+    return coverage_report_mm(eng, aln, fwd, rev, records, segment_size, overlap_size, window_size, kmer_size,
+                              max_mismatches, exact_3p);
+}
+
+std::string coverage_report_mm(Engine &eng, const DeviceAlignment &aln, const std::vector<KmerStat> &fwd,
+                               const std::vector<KmerStat> &rev, const std::vector<SequenceRecord> &records,
+                               int segment_size, int overlap_size, int window_size, int kmer_size, int max_mismatches,
+                               int exact_3p)
+{
+    // per-segment best mismatch count on the device: best[record * P + partition], 255 = no match
+    const size_t L = aln.length();
+    const size_t P = L < (size_t)segment_size ? 0 : (L - (size_t)segment_size) / (size_t)overlap_size + 1;
+    std::vector<uint8_t> best(records.size() * P + 1, 255);
+    if (P) {
+        const auto wf = pack_words(eng, fwd, kmer_size), wr = pack_words(eng, rev, kmer_size);
+        const msspe_kmer_opt opt{segment_size, overlap_size, window_size, kmer_size, 0, 0};
+        const msspe_mismatch_opt mm{max_mismatches, exact_3p};
+        const int rc = msspe_segment_coverage_mm_packed_dev(eng.ctx(), aln.device(), aln.rows(), L, &opt, &mm,
+                                                            wf.data(), (int)wf.size(), wr.data(), (int)wr.size(),
+                                                            best.data(), nullptr);
+        if (rc) eng.fail(rc);
+    }
+    const auto n = (uint8_t)max_mismatches;
+    std::string out = "\nCoverage report (up to " + std::to_string(max_mismatches) + " mismatches, last " +
+                      std::to_string(exact_3p) + " bases exact):\n";
+    out += coverage_lines(records, P, segment_size, overlap_size, [&](size_t i) { return best[i] <= n; });
+    std::vector<size_t> by((size_t)max_mismatches + 2, 0);   // [0..N] mismatches, [N + 1] none
+    for (size_t ri = 0; ri < records.size(); ++ri) {
+        const size_t len = records[ri].sequence.size();
+        for (size_t j = 0; (size_t)segment_size <= len && j * (size_t)overlap_size + (size_t)segment_size <= len; ++j)
+            by[std::min<size_t>(best[ri * P + j], (size_t)max_mismatches + 1)] += 1;
+    }
+    out += "  Segments by best match:";
+    for (int m = 0; m <= max_mismatches; ++m) out += " " + std::to_string(m) + " mm " + std::to_string(by[(size_t)m]) + ",";
+    out += " none " + std::to_string(by.back()) + "\n";
     return out;
 }
 
@@ -1013,6 +1084,10 @@ int run(const Args &args, std::string &stdout_text)
     for (const auto &w : panel_r) rep_r.push_back(KmerStat{w, SEQ_DIR_REV});
     stdout_text = coverage_report(eng, aln, rep_f, rep_r, records, args.window_size, args.overlap_size,
                                   args.search_windows_size, args.kmer_size);
+    if (args.coverage_mismatches > 0)   // the same primers (panel included), matched within N mismatches
+        stdout_text += coverage_report_mm(eng, aln, rep_f, rep_r, records, args.window_size, args.overlap_size,
+                                          args.search_windows_size, args.kmer_size, args.coverage_mismatches,
+                                          args.coverage_3p_exact);
     std::ofstream out(args.output, std::ios::binary);
     if (!out) throw std::runtime_error("cannot write " + args.output);
     out << primers_csv(good_f, good_r, panel_f.size(), panel_r.size());

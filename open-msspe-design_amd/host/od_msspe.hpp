@@ -54,6 +54,11 @@ struct Args {
     std::string params_path;       // Primer3 config directory; empty = bundled tables
     std::string existing_primers;  // a panel to extend: CSV in this tool's output format (direction and primers read)
     std::string cover_on_device = "false";   // "true": the screen and the vertex cover as one device call (msspe_conflict_cover)
+    // > 0: after the exact report, a second one counting a segment covered when a primer matches within this many
+    // mismatches, its last coverage_3p_exact bases exact (msspe_segment_coverage_mm); 0: nothing changes
+    int coverage_mismatches = 0;
+    std::string coverage_3p_exact_text = "3";   // read (as an integer) only when coverage_mismatches > 0
+    int coverage_3p_exact = 3;
     bool stddev_population = false;  // crate std-dev 0.1.0's divisor is unpinned
     static Args parse(int argc, const char *const *argv);   // throws UsageError
     static std::string usage();
@@ -190,6 +195,15 @@ std::string coverage_report(Engine &eng, const DeviceAlignment &aln, const std::
 std::string coverage_report(Engine &eng, const std::vector<KmerStat> &fwd, const std::vector<KmerStat> &rev,
                             const std::vector<SequenceRecord> &records, int segment_size,
                             int overlap_size, int window_size, int kmer_size);
+// The mismatch-tolerant block (engine extension): "Coverage report (up to N mismatches, last E bases exact):", the
+// exact report's three lines with hit = best <= N, and the segments by best mismatch count (msspe_segment_coverage_mm)
+std::string coverage_report_mm(Engine &eng, const DeviceAlignment &aln, const std::vector<KmerStat> &fwd,
+                               const std::vector<KmerStat> &rev, const std::vector<SequenceRecord> &records,
+                               int segment_size, int overlap_size, int window_size, int kmer_size, int max_mismatches,
+                               int exact_3p);
+std::string coverage_report_mm(Engine &eng, const std::vector<KmerStat> &fwd, const std::vector<KmerStat> &rev,
+                               const std::vector<SequenceRecord> &records, int segment_size, int overlap_size,
+                               int window_size, int kmer_size, int max_mismatches, int exact_3p);
 // main.rs:834-858
 // first_f / first_r: the number of the first row of each direction (a panel's extension continues its numbering)
 std::string primers_csv(const std::vector<KmerStat> &fwd, const std::vector<KmerStat> &rev, size_t first_f = 0,

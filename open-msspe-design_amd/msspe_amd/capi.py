@@ -31,6 +31,7 @@ EXPORTS = [
     "msspe_kmer_candidates_seeded", "msspe_kmer_candidates_seeded_packed_dev",
     "msspe_kmer_candidates_both_seeded_packed_dev",
     "msspe_segment_coverage_packed_dev",
+    "msspe_segment_coverage_mm", "msspe_segment_coverage_mm_dev", "msspe_segment_coverage_mm_packed_dev",
     "msspe_round_fixed_f32", "msspe_g_cut",
     "msspe_group_create", "msspe_group_destroy", "msspe_group_last_error", "msspe_group_size",
     "msspe_group_transport", "msspe_group_transport_reason", "msspe_group_rccl_available", "msspe_group_member", "msspe_group_set_option", "msspe_group_rows",
@@ -63,6 +64,11 @@ class KmerOpt(C.Structure):
     _fields_ = [("segment_size", C.c_int), ("overlap_size", C.c_int),
                 ("search_window_size", C.c_int), ("kmer_size", C.c_int),
                 ("max_iterations", C.c_int), ("max_mismatch_segments", C.c_int)]
+
+
+class MismatchOpt(C.Structure):
+    """msspe_mismatch_opt: coverage within max_mismatches, the primer's last exact_3p bases exact."""
+    _fields_ = [("max_mismatches", C.c_int), ("exact_3p", C.c_int)]
 
 
 def lib_path() -> Path:
@@ -182,6 +188,10 @@ def load_library() -> C.CDLL:
                                          vp]
     L.msspe_segment_coverage_dev.argtypes = L.msspe_segment_coverage.argtypes
     L.msspe_segment_coverage_packed_dev.argtypes = L.msspe_segment_coverage.argtypes
+    L.msspe_segment_coverage_mm.argtypes = [vp, vp, C.c_int, C.c_size_t, C.POINTER(KmerOpt), C.POINTER(MismatchOpt),
+                                            vp, C.c_int, vp, C.c_int, vp, vp]
+    L.msspe_segment_coverage_mm_dev.argtypes = L.msspe_segment_coverage_mm.argtypes
+    L.msspe_segment_coverage_mm_packed_dev.argtypes = L.msspe_segment_coverage_mm.argtypes
     L.msspe_round_g_f32.restype = C.c_float
     L.msspe_round_g_f32.argtypes = [C.c_double]
     L.msspe_round_fixed_f32.restype = C.c_float
@@ -192,6 +202,13 @@ def load_library() -> C.CDLL:
     L.msspe_t_cut.argtypes = [C.c_float]
     _lib = L
     return L
+
+
+def _words(x) -> np.ndarray:
+    """Primer strings (or an array of packed words) -> contiguous uint64 packed words."""
+    if isinstance(x, np.ndarray) and x.dtype == np.uint64:
+        return np.ascontiguousarray(x)
+    return pack_oligos(list(x)) if len(x) else np.zeros(0, dtype=np.uint64)
 
 
 def pack_oligos(oligos) -> np.ndarray:
@@ -588,6 +605,39 @@ class Engine:
             self.ptr, a.ctypes.data, n_seq, seq_len, C.byref(opt), f.ctypes.data, len(f), r.ctypes.data, len(r),
             hit.ctypes.data))
         return hit
+
+    def segment_coverage_mm(self, seqs: np.ndarray, opt: KmerOpt, fwd, rev, max_mismatches: int, exact_3p: int,
+                            per_primer: bool = False):
+        """Coverage within max_mismatches, the primer's last exact_3p bases exact (msspe_segment_coverage_mm).
+        seqs: uint8 (n_seq, L) host array; fwd / rev: primer strings (rev as the CSV writes it) or packed uint64 words.
+        Returns best, uint8 (n_seq, P): the smallest mismatch count of a match in the segment, 255 when none; with
+        per_primer, (best, counts): counts uint32 (len(fwd) + len(rev)) of segments each primer matches in."""
+        a = np.ascontiguousarray(seqs, dtype=np.uint8)
+        n_seq, seq_len = a.shape
+        return self._coverage_mm(self.L.msspe_segment_coverage_mm, a.ctypes.data, n_seq, seq_len, opt, fwd, rev,
+                                 max_mismatches, exact_3p, per_primer)
+
+    def segment_coverage_mm_dev(self, d_seqs: int, n_seq: int, seq_len: int, opt: KmerOpt, fwd, rev,
+                                max_mismatches: int, exact_3p: int, per_primer: bool = False):
+        """As segment_coverage_mm on device bytes (n_seq x seq_len at address d_seqs)."""
+        return self._coverage_mm(self.L.msspe_segment_coverage_mm_dev, C.c_void_p(d_seqs), n_seq, seq_len, opt, fwd,
+                                 rev, max_mismatches, exact_3p, per_primer)
+
+    def segment_coverage_mm_packed(self, d_packed: int, n_seq: int, seq_len: int, opt: KmerOpt, fwd, rev,
+                                   max_mismatches: int, exact_3p: int, per_primer: bool = False):
+        """As segment_coverage_mm on a packed alignment resident on the device (the handle put_rows_packed returns)."""
+        return self._coverage_mm(self.L.msspe_segment_coverage_mm_packed_dev, C.c_void_p(d_packed), n_seq, seq_len,
+                                 opt, fwd, rev, max_mismatches, exact_3p, per_primer)
+
+    def _coverage_mm(self, fn, seqs_arg, n_seq, seq_len, opt, fwd, rev, max_mismatches, exact_3p, per_primer):
+        P = 0 if seq_len < opt.segment_size else (seq_len - opt.segment_size) // opt.overlap_size + 1
+        f, r = _words(fwd), _words(rev)
+        best = np.zeros((n_seq, P), dtype=np.uint8)
+        counts = np.zeros(len(f) + len(r), dtype=np.uint32)
+        mm = MismatchOpt(max_mismatches, exact_3p)
+        self._check(fn(self.ptr, seqs_arg, n_seq, seq_len, C.byref(opt), C.byref(mm), f.ctypes.data, len(f),
+                       r.ctypes.data, len(r), best.ctypes.data, counts.ctypes.data if per_primer else None))
+        return (best, counts) if per_primer else best
 
     def pair_stage_samples(self):
         """[(row, col, reason bits)] for up to 1024 pairs the integer stage handed on."""
