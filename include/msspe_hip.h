@@ -83,6 +83,8 @@ const char *msspe_version(void);
  *   "split_lanes"    "0" | "2" | "4" | "8"
  *   "split_list"     "0" | "1"    short oligos: tables too large for the integer list stage go to the split-table
  *                                 kernel's list mode (1) or straight to the f64 kernels (0)
+ *   "short_chain"    "0" | "1"    screen blocks of up to 2^23 pairs: the integer list stage hands straight to one wave
+ *                                 per pair (1), or the block takes the long chain of larger blocks (0)
  *   "row_oob"        "0" | "1"    the row-specialised first stage, which reads LDS beyond its allocation and takes the
  *                                 0 gfx950 returns there for "not available" (1; it also needs the per-engine probe to
  *                                 pass), or the general integer kernel, which never leaves its allocation (0: for
@@ -102,7 +104,27 @@ int msspe_set_option(msspe_ctx *ctx, const char *key, const char *value);
  *                     iterations at the end of the last batch
  *   "cover_rounds"    the last msspe_conflict_cover* call: rounds that deleted nodes
  *   "cover_keys_us" / "cover_symmetrise_us" / "cover_rounds_us"
- *                     the same call's device time of its phases: sort and keys, S = B | B^T, the rounds */
+ *                     the same call's device time of its phases: sort and keys, S = B | B^T, the rounds
+ *   "hand_over_list_0" .. "hand_over_list_6"
+ *                     pairs that entered hand-over list q of the cross-dimer calls (ANY and END) since the last read
+ *                     of that key; reading synchronises the context's stream and resets the key, as
+ *                     msspe_last_overflow_pairs does.  The first stage writes list 0; the stage that reads list q
+ *                     writes list q + 1.  Which stage reads list q depends on the route:
+ *                       long chain (integer first stage, up to 15 bases; blocks above 2^23 pairs, or short_chain 0),
+ *                       split_list 1 and the split tables cover the length:
+ *                         0 integer list stage, 1 split-table list mode, 2 f64 56-slot list stage, 3 wide table,
+ *                         4 one wave per pair, 5 dense kernel (wave_kernel 0: 4 dense kernel)
+ *                       long chain, split_list 0:
+ *                         0 integer list stage, 1 f64 56-slot list stage, 2 wide table, 3 one wave per pair,
+ *                         4 dense kernel (wave_kernel 0: 3 dense kernel)
+ *                       short chain (blocks of up to 2^23 pairs, short_chain 1, wave_kernel 1):
+ *                         0 integer list stage, 1 one wave per pair, 2 dense kernel
+ *                       register-table first stage (pair_kernel "f64", tables without an integer image, END screen):
+ *                         0 wide table, 1 one wave per pair, 2 dense kernel (wave_kernel 0: 1 dense kernel)
+ *                       split-table first stage (split_min_k and up, max_loop below 2k - 4, rectangles):
+ *                         0 one wave per pair, 1 dense kernel (wave_kernel 0: 0 dense kernel)
+ *                       one wave per pair as the first stage (matrix mode): 0 dense kernel
+ *                       force_generic: no list */
 int msspe_get_info(msspe_ctx *ctx, const char *key, long long *value_out);
 int msspe_set_stream(msspe_ctx *ctx, void *hip_stream);
 int msspe_reset_stream(msspe_ctx *ctx);

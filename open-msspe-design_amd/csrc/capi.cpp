@@ -58,6 +58,7 @@ constexpr long kListCapMax = 1L << 30;       // 8 GB per list (two of them, 6 % 
                                              // against it all the same.  The small kernels of a flush do not fill the card:
                                              // 2^28 -> 2^30 is 17 -> 5 flushes per 65,536^2 screen and 1.5 % of its time
 constexpr size_t kGenericLanes = 1u << 16;   // lanes of the generic kernels' workspace
+constexpr int kOvfTotals = 2 + 7;            // msspe_ctx::d_ovf_total: two flags / totals, then one total per hand-over list
 
 }  // namespace
 
@@ -93,7 +94,8 @@ struct msspe_ctx {
     uint32_t *ovf_count = nullptr;     // list counters of the stages (8): [0] first, [1] second, ...
     long list_cap = 0;                 // entries per hand-over list
     long list_cap_ceiling = 1L << 30;  // lowered when an allocation of that size failed (not tried again)
-    uint64_t *d_ovf_total = nullptr;   // [0] pairs handed on so far, [1] != 0: a list counter went past its capacity
+    uint64_t *d_ovf_total = nullptr;   // [0] pairs handed on so far, [1] != 0: a list counter went past its capacity,
+                                       // [2 + q] pairs that entered list q (msspe_get_info "hand_over_list_<q>")
     unsigned long long *d_reasons = nullptr;   // [8] statistics of the integer stage
     uint64_t *d_sorted = nullptr;      // column primers grouped by composition
     uint32_t *d_perm = nullptr;
@@ -225,8 +227,8 @@ int ensure_overflow(msspe_ctx *ctx, long total_pairs)
         HIP_TRY(ctx, hipMemsetAsync(ctx->ovf_count, 0, sizeof(uint32_t) * 8, ctx->stream));
     }
     if (!ctx->d_ovf_total) {
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_ovf_total, 2 * sizeof(uint64_t)));
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_ovf_total, 0, 2 * sizeof(uint64_t), ctx->stream));
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_ovf_total, kOvfTotals * sizeof(uint64_t)));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->d_ovf_total, 0, kOvfTotals * sizeof(uint64_t), ctx->stream));
     }
     if (!ctx->d_reasons) {
         HIP_TRY(ctx, hipMalloc((void **)&ctx->d_reasons, (9 + 1024 + 8) * sizeof(unsigned long long)));
@@ -283,15 +285,18 @@ int ensure_sort(msspe_ctx *ctx, size_t ncols)
     return MSSPE_OK;
 }
 
-// End of a flush: totals for the statistics, and the check that no stage's list counter went past the
-// capacity of its list (entries beyond it are not stored: the host sizes the flushes so that this cannot
-// happen, and a screen during which it did must not be trusted).
+// End of a flush: totals for the statistics (all pairs the first stage handed on, and per list the pairs that
+// entered it), and the check that no stage's list counter went past the capacity of its list (entries beyond it
+// are not stored: the host sizes the flushes so that this cannot happen, and a screen during which it did must not
+// be trusted).
 __global__ void k_accumulate_overflow(const uint32_t *count, uint64_t *total, uint32_t cap)
 {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
         total[0] += count[0];
-        for (int q = 0; q < 7; ++q)
+        for (int q = 0; q < 7; ++q) {
+            total[2 + q] += count[q];
             if (count[q] > cap) total[1] = 1;
+        }
     }
 }
 
@@ -435,6 +440,18 @@ int msspe_get_info(msspe_ctx *ctx, const char *key, long long *value_out)
     else if (k == "cover_keys_us") *value_out = ctx->cover.phase_us()[0];
     else if (k == "cover_symmetrise_us") *value_out = ctx->cover.phase_us()[1];
     else if (k == "cover_rounds_us") *value_out = ctx->cover.phase_us()[2];
+    else if (k.size() == 16 && k.compare(0, 15, "hand_over_list_") == 0 && k[15] >= '0' && k[15] <= '6') {
+        // pairs that entered list q since the last read of this key; reading resets it
+        *value_out = 0;
+        if (!ctx->d_ovf_total) return MSSPE_OK;
+        const size_t q = (size_t)(k[15] - '0');
+        uint64_t v = 0;
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        HIP_TRY(ctx, hipMemcpy(&v, ctx->d_ovf_total + 2 + q, sizeof v, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->d_ovf_total + 2 + q, 0, sizeof v, ctx->stream));
+        *value_out = (long long)v;
+    }
     else return fail(ctx, MSSPE_ERR_ARG, "msspe_get_info: unknown key '" + k + "'");
     return MSSPE_OK;
 }

@@ -593,6 +593,11 @@ class Engine:
         self._check(self.L.msspe_last_overflow_pairs(self.ptr, C.byref(v)))
         return int(v.value)
 
+    def hand_over_lists(self) -> list[int]:
+        """Pairs that entered each of the seven hand-over lists since the last read (msspe_get_info
+        "hand_over_list_<q>"; include/msspe_hip.h names the stage that reads list q on each route); resets them."""
+        return [self.info(f"hand_over_list_{q}") for q in range(7)]
+
     def segment_coverage(self, seqs: np.ndarray, opt: KmerOpt, fwd: list[str], rev: list[str]) -> np.ndarray:
         """uint8 (n_seq, P): 1 where the segment is covered by the primer set (main.rs:518-594)."""
         a = np.ascontiguousarray(seqs, dtype=np.uint8)

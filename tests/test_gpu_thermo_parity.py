@@ -121,6 +121,25 @@ def test_other_oligo_lengths(eng, m, oracle, oracle_tables, k):
     check_pool(eng, m, oracle, oracle_tables, pool)
 
 
+@pytest.mark.parametrize("chem_kw", [{}, dict(dv=1.5, dntp=0.6, dna_conc=50.0, temp_c=37.0)], ids=["ntthal", "primer3"])
+@pytest.mark.parametrize("k", range(2, 33))
+def test_every_oligo_length(eng, m, oracle, oracle_tables, k, chem_kw):
+    """Every length the engine takes, at ntthal's and at Primer3's defaults: 2 .. 13 the register-table / integer
+    chain, 14 and 15 the row-specialised first stage, 16 .. 28 the split-table kernel, 29 .. 32 one wave per pair as
+    the first stage.  Random oligos plus homopolymers (poly-A x poly-T: k^2 cells), dinucleotide repeats and
+    palindromes (self-complementary for even k), 157 in all."""
+    rng = np.random.default_rng(2000 + k)
+    pool = m.synth.pool_strings(m.synth.random_pool(125, k, seed=300 + k))
+    pool += [b * k for b in "ACGT"] + [(u * k)[:k] for u in ("AT", "TA", "GC", "CG", "AC", "GT")]
+    for _ in range(16):
+        half = "".join(rng.choice(list("ACGT"), k // 2))
+        pool.append(half + ("G" if k % 2 else "") + oracle.reverse_complement(half))
+    pool += ["".join(rng.choice(list("AT"), k)) for _ in range(6)]
+    assert len(pool) == 157
+    out, cnt = check_pool(eng, m, oracle, oracle_tables, pool, chem_kw, -300.0 * k)
+    assert np.isinf(out["dg"][125, 125]) and np.isfinite(out["dg"][125, 128])     # poly-A x poly-A, poly-A x poly-T
+
+
 @pytest.mark.parametrize("k,oligos,chem_kw,thr", [
     (14, ["GCGGCGGCCGCCGC", "GCCGGCCGGGCGGG", "GGCCGGCCGGGCGG"], dict(temp_c=37.0), -6000.0),
     (16, ["TCTAGACTAGCCAGCA", "TGAAGAAAGCTAAGTC"], dict(mv=200.0, dv=0.5, dntp=0.2), -1500.0)])
@@ -344,22 +363,35 @@ def test_pairs_without_a_complementary_cell(eng, m, oracle, oracle_tables, k, pa
 @pytest.mark.parametrize("split_list", [1, 0])
 def test_very_large_tables_of_short_oligos(eng, m, oracle, oracle_tables, split_list):
     """A/T-only and G/C-only 13-mers against each other: 60 ... 169 complementary cells per pair, far beyond the
-    integer stages' tables.  With split_list = 1 they go through the split-table kernel's list mode (two lanes
-    per pair, up to 128 cells; all-A against all-T is left to the one-wave-per-pair kernel), with 0 straight
-    to the f64 kernels: same planes, bit for bit, as the oracle's."""
+    integer stages' tables.  The pool (65,536 pairs) would take the short chain; short_chain = 0 sends it down the
+    long one, where with split_list = 1 the integer list stage hands them to the split-table kernel's list mode (two
+    lanes per pair, up to 128 cells; all-A against all-T is left to the one-wave-per-pair kernel), with 0 straight
+    to the f64 kernels (56-slot list stage, wide table, one wave per pair): same planes, bit for bit, as the
+    oracle's.  The hand-over counters show that the split list stage received pairs and answered some of them."""
     rng = np.random.default_rng(44)
     at = np.frombuffer(b"AT", dtype=np.uint8)[rng.integers(0, 2, (110, 13))]
     gc = np.frombuffer(b"GC", dtype=np.uint8)[rng.integers(0, 2, (90, 13))]
     homo = np.frombuffer(b"AAAAAAAAAAAAATTTTTTTTTTTTTGGGGGGGGGGGGGCCCCCCCCCCCCC", dtype=np.uint8).reshape(4, 13)
     pool = m.synth.pool_strings(np.concatenate([at, gc, homo, m.synth.random_pool(52, 13, seed=9)]))
     eng.set_option("split_list", split_list)
+    eng.set_option("short_chain", 0)
     try:
+        eng.hand_over_lists()
         out, cnt = check_pool(eng, m, oracle, oracle_tables, pool, threshold=-6000.0)
+        lists = eng.hand_over_lists()
         fast = eng.cross_dimer(pool, m.Chem.ntthal(), -6000.0, want_dg=False, want_tm=False)
     finally:
         eng.set_option("split_list", 1)
+        eng.set_option("short_chain", 1)
     np.testing.assert_array_equal(fast["bitmap"], out["bitmap"])
     assert cnt > 1000
+    # list q is read by: 0 the integer list stage, then (split_list = 1) 1 split list, 2 56-slot list, 3 wide table,
+    # 4 one wave per pair, 5 dense kernel; (split_list = 0) 1 56-slot list, 2 wide table, 3 wave, 4 dense kernel
+    assert lists[0] > 0 and lists[1] > 0, lists
+    if split_list:
+        assert lists[2] < lists[1], lists          # the split list stage answered pairs itself
+    else:
+        assert lists[5] == 0 and lists[6] == 0, lists   # no split list stage: the chain ends a list earlier
 
 
 def test_hand_over_lists_shrink_when_the_card_is_full(m):
