@@ -509,6 +509,56 @@ int msspe_segment_coverage_mm_packed_dev(msspe_ctx *ctx, const uint64_t *d_packe
                                          const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
                                          uint8_t *best_out, uint32_t *primer_segments_out);
 
+/* ---- off-target sites in a background (engine extension, no reference counterpart) --------------------------
+ * Where else do the primers land: a host genome, rRNA, a mitochondrion.  The BACKGROUND is a list of records
+ * (unaligned, of any lengths, empty ones allowed) seen as one STREAM: the records back to back with one invalid
+ * column between two records; record r starts at stream column start[r] = start[r - 1] + record_bytes[r - 1] + 1,
+ * start[0] = 0, and the stream is total_len = start[n_records - 1] + record_bytes[n_records - 1] columns long (0
+ * without records); total_len < 2^32.  Only upper-case A C G T are bases; every other byte (N, IUPAC codes, '-',
+ * lower case, the separator) is invalid, as in msspe_device_put_rows_packed -- a caller that wants lower case or U
+ * taken as bases normalises first.
+ * For every stream position p in [0, total_len - k] and every primer word u (words: n HOST words in
+ * msspe_pack_oligos form, primer orientation, the way the CSV writes forward and reverse primers alike; 1 <= k <= 31):
+ *   - PLUS-strand site: the k columns at p are all bases and, read as a word w, match u by the rule of
+ *     msspe_mismatch_opt: at most max_mismatches differing base positions, and equal on u's last exact_3p bases;
+ *   - MINUS-strand site: the same test with w = the reverse complement of the k columns at p.
+ * A window that holds an invalid column is never a site, so no site straddles two records.  Every primer is tested
+ * on both strands whatever its direction; a position can be a site on both strands for one primer (palindromes)
+ * and then counts twice.
+ * sites_out[2 * i + s] (uint64, HOST, 2 n): the sites of primer i on strand s (0 plus, 1 minus); duplicate primers
+ * are counted independently.  The optional SITE LIST follows the edge list's convention
+ * (msspe_cross_dimer_edges*): one msspe_site per site, appended with one atomic each in no particular order,
+ * capacity and count owned by the caller (the _packed_dev form adds to *d_count, which the caller zeroes; it keeps
+ * running past the capacity, so a truncated list is visible and nothing is written behind d_sites[capacity - 1]).
+ * pos is the stream position p; with record_start_out it becomes (record, offset).
+ *   msspe_device_put_stream_packed: uploads the records 16 MB at a time through pinned staging and packs each
+ *     chunk on the device into ONE packed row of msspe_packed_row_words(total_len) words (the host never builds the
+ *     concatenated copy).  record_start_out (optional, n_records): start[].  Free with msspe_device_free.
+ *   msspe_background_sites_packed_dev: the kernel call on a resident stream, on the context's stream; d_sites ==
+ *     NULL: no list (capacity and d_count are not read).  Work buffers grow on first use and are kept; the call
+ *     returns when sites_out is filled.
+ *   msspe_background_sites: host pointers throughout.  sites == NULL: no list.  Otherwise the first `capacity`
+ *     records to arrive, sorted by (primer, strand, pos), *count_out = the number of sites; when that exceeds
+ *     `capacity` the call returns MSSPE_ERR_CAPACITY (sites_out and count_out are valid: retry with count_out).
+ * MSSPE_ERR_ARG: mm, sites_out, words with n > 0, records with n_records > 0, or count_out with a list NULL;
+ * max_mismatches or exact_3p outside 0..k; a primer word with bits above 2 k; total_len >= 2^32.  MSSPE_ERR_K: k
+ * outside 1..31.  n == 0 or total_len < k: MSSPE_OK, sites_out zeroed, list count 0 (_packed_dev: unchanged). */
+typedef struct {
+    uint32_t primer;       /* index into words */
+    uint32_t pos;          /* stream position of the window's first column */
+    uint16_t mismatches;   /* differing base positions, 0 .. max_mismatches */
+    uint16_t strand;       /* 0 plus, 1 minus */
+} msspe_site;
+int msspe_device_put_stream_packed(msspe_ctx *ctx, const char *const *records, const size_t *record_bytes,
+                                   int n_records, void **device_out, size_t *total_len_out,
+                                   uint64_t *record_start_out);
+int msspe_background_sites_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, size_t total_len, int k,
+                                      const msspe_mismatch_opt *mm, const uint64_t *words, int n, uint64_t *sites_out,
+                                      msspe_site *d_sites, uint64_t capacity, uint64_t *d_count);
+int msspe_background_sites(msspe_ctx *ctx, const char *const *records, const size_t *record_bytes, int n_records,
+                           int k, const msspe_mismatch_opt *mm, const uint64_t *words, int n, uint64_t *sites_out,
+                           msspe_site *sites, uint64_t capacity, uint64_t *count_out, uint64_t *record_start_out);
+
 
 /* ---- several devices of one node ----------------------------------------------------------
  *

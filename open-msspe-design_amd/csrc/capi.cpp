@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "conflict_cover.hpp"
+#include "background.hpp"
 #include "coverage_mm.hpp"
 #include "kernels.hpp"
 #include "kmer_stage.hpp"
@@ -109,6 +110,7 @@ struct msspe_ctx {
     hipStream_t stream_rev = nullptr;  // ... and its stream
     hipEvent_t ev_rev = nullptr;
     MismatchCoverage mm_cov;           // msspe_segment_coverage_mm*: primer words, counts, per-segment minima
+    BackgroundSites background;        // msspe_background_sites*: primer words in plane form, per-primer counts
     CoverStage cover;                  // msspe_conflict_cover*: the symmetrised bitmap and the round state
     // optional profiling of the dominant kernel (k_pairs_fast) with HIP events on ctx->stream
     bool prof_on = false;
@@ -475,6 +477,7 @@ void msspe_destroy(msspe_ctx *ctx)
         ctx->kmer_rev.release();
         ctx->cover.release();
         ctx->mm_cov.release();
+        ctx->background.release();
         if (ctx->ev_rev) (void)hipEventDestroy(ctx->ev_rev);
         if (ctx->stream_rev) {
             (void)hipStreamSynchronize(ctx->stream_rev);
@@ -2125,6 +2128,151 @@ int msspe_device_free(msspe_ctx *ctx, void *device)
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     HIP_TRY(ctx, hipFree(device));
     return MSSPE_OK;
+}
+
+// The background as one packed row: the stream (records back to back, one '-' between two) passes 16 MB at a time
+// through two pinned buffers and two device landing zones; each chunk is packed on the device behind its copy.  A
+// chunk starts at a multiple of 64 columns, so its base and validity words are whole words of the packed row.
+int msspe_device_put_stream_packed(msspe_ctx *ctx, const char *const *records, const size_t *record_bytes,
+                                   int n_records, void **device_out, size_t *total_len_out,
+                                   uint64_t *record_start_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!device_out || !total_len_out || n_records < 0 || (n_records && (!records || !record_bytes)))
+        return fail(ctx, MSSPE_ERR_ARG, "null argument");
+    *device_out = nullptr;
+    *total_len_out = 0;
+    uint64_t total = 0;
+    for (int r = 0; r < n_records; ++r) {
+        if (record_bytes[r] && !records[r]) return fail(ctx, MSSPE_ERR_ARG, "null record");
+        if (r) total += 1;   // the separator
+        if (record_start_out) record_start_out[r] = total;
+        total += record_bytes[r];
+        if (total >= (1ull << 32))
+            return fail(ctx, MSSPE_ERR_ARG, "the background stream must be shorter than 2^32 columns");
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t L = (size_t)total, bw = (L + 31) / 32;
+    uint64_t *d = nullptr;
+    HIP_TRY(ctx, hipMalloc((void **)&d, std::max<size_t>(8, SeqView::row_words(L) * sizeof(uint64_t))));
+    *total_len_out = L;
+    if (!L) {
+        *device_out = d;
+        return MSSPE_OK;
+    }
+    const size_t chunk = std::min<size_t>((size_t)16u << 20, (L + 63) & ~(size_t)63);
+    char *stage[2] = {nullptr, nullptr};
+    char *dchunk[2] = {nullptr, nullptr};
+    hipEvent_t drained[2] = {nullptr, nullptr};
+    hipStream_t copy = nullptr;
+    hipError_t e = hipStreamCreateWithFlags(&copy, hipStreamNonBlocking);
+    for (int b = 0; b < 2 && e == hipSuccess; ++b) {
+        e = hipHostMalloc((void **)&stage[b], chunk, hipHostMallocDefault);
+        if (e == hipSuccess) e = hipMalloc((void **)&dchunk[b], chunk);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&drained[b], hipEventDisableTiming);
+    }
+    int rec = 0;          // the cursor: the next stream column is column `off` of record `rec`,
+    size_t off = 0;       // off == record_bytes[rec] being the separator behind it
+    int turn = 0;
+    for (size_t c0 = 0; c0 < L && e == hipSuccess; c0 += chunk, turn ^= 1) {
+        const size_t len = std::min(chunk, L - c0);
+        e = hipEventSynchronize(drained[turn]);   // the copy that last read this buffer (none: returns at once)
+        if (e != hipSuccess) break;
+        char *buf = stage[turn];
+        for (size_t at = 0; at < len;) {
+            if (off == record_bytes[rec]) {
+                buf[at++] = '-';
+                ++rec;
+                off = 0;
+                continue;
+            }
+            const size_t take = std::min(len - at, record_bytes[rec] - off);
+            std::memcpy(buf + at, records[rec] + off, take);
+            at += take;
+            off += take;
+        }
+        e = hipMemcpyAsync(dchunk[turn], buf, len, hipMemcpyHostToDevice, copy);
+        if (e == hipSuccess)
+            e = launch_pack_stream((const uint8_t *)dchunk[turn], len, d + c0 / 32, d + bw + c0 / 64, copy);
+        if (e == hipSuccess) e = hipEventRecord(drained[turn], copy);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(copy);
+    for (int b = 0; b < 2; ++b) {
+        if (drained[b]) (void)hipEventDestroy(drained[b]);
+        if (stage[b]) (void)hipHostFree(stage[b]);
+        if (dchunk[b]) (void)hipFree(dchunk[b]);
+    }
+    if (copy) (void)hipStreamDestroy(copy);
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        return hip_fail(ctx, e, "msspe_device_put_stream_packed");
+    }
+    *device_out = d;
+    return MSSPE_OK;
+}
+
+int msspe_background_sites_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, size_t total_len, int k,
+                                      const msspe_mismatch_opt *mm, const uint64_t *words, int n, uint64_t *sites_out,
+                                      msspe_site *d_sites, uint64_t capacity, uint64_t *d_count)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!d_packed || !mm || !sites_out || n < 0 || (n && !words) || (d_sites && !d_count))
+        return fail(ctx, MSSPE_ERR_ARG, "null argument");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::string err;
+    const int rc = ctx->background.run(d_packed, total_len, k, mm->max_mismatches, mm->exact_3p, words, n, sites_out,
+                                       d_sites, capacity, d_count, ctx->n_cu, ctx->stream, err);
+    if (rc) return fail(ctx, rc, err);
+    return MSSPE_OK;
+}
+
+int msspe_background_sites(msspe_ctx *ctx, const char *const *records, const size_t *record_bytes, int n_records,
+                           int k, const msspe_mismatch_opt *mm, const uint64_t *words, int n, uint64_t *sites_out,
+                           msspe_site *sites, uint64_t capacity, uint64_t *count_out, uint64_t *record_start_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!mm || !sites_out || n < 0 || (n && !words) || (sites && !count_out))
+        return fail(ctx, MSSPE_ERR_ARG, "null argument");
+    if (count_out) *count_out = 0;
+    void *d = nullptr;
+    size_t L = 0;
+    int rc = msspe_device_put_stream_packed(ctx, records, record_bytes, n_records, &d, &L, record_start_out);
+    if (rc) return rc;
+    msspe_site *d_sites = nullptr;   // the list and, behind it, its count
+    uint64_t *d_count = nullptr;
+    hipError_t e = hipSuccess;
+    if (sites) {
+        const size_t list_bytes = (sizeof(msspe_site) * (size_t)capacity + 7) & ~(size_t)7;
+        e = hipMalloc((void **)&d_sites, list_bytes + sizeof(uint64_t));
+        if (e == hipSuccess) {
+            d_count = (uint64_t *)((char *)d_sites + list_bytes);
+            e = hipMemsetAsync(d_count, 0, sizeof(uint64_t), ctx->stream);
+        }
+    }
+    if (e == hipSuccess) {
+        rc = msspe_background_sites_packed_dev(ctx, (const uint64_t *)d, L, k, mm, words, n, sites_out, d_sites,
+                                               capacity, d_count);
+        if (!rc && sites) {
+            uint64_t count = 0;
+            e = hipMemcpyAsync(&count, d_count, sizeof count, hipMemcpyDeviceToHost, ctx->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+            const uint64_t kept = std::min(count, capacity);
+            if (e == hipSuccess && kept) e = hipMemcpy(sites, d_sites, sizeof(msspe_site) * kept, hipMemcpyDeviceToHost);
+            if (e == hipSuccess) {
+                std::sort(sites, sites + kept, [](const msspe_site &a, const msspe_site &b) {
+                    if (a.primer != b.primer) return a.primer < b.primer;
+                    if (a.strand != b.strand) return a.strand < b.strand;
+                    return a.pos < b.pos;
+                });
+                *count_out = count;
+                if (count > capacity) rc = fail(ctx, MSSPE_ERR_CAPACITY, "site list capacity too small");
+            }
+        }
+    }
+    if (d_sites) (void)hipFree(d_sites);
+    (void)msspe_device_free(ctx, d);
+    if (e != hipSuccess) return hip_fail(ctx, e, "msspe_background_sites");
+    return rc;
 }
 
 int msspe_host_pair_tables(const char *params_path, const msspe_chem *chem, float dg_threshold,

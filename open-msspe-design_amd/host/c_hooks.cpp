@@ -63,7 +63,10 @@ int odm_parse_args(int argc, const char *const *argv, char *out, size_t cap)
           << "\ndelta_g_threshold=" << a.delta_g_threshold << "\nkeep_all=" << a.keep_all
           << "\ncheck_hairpin=" << a.check_hairpin << "\ndo_align=" << a.do_align
           << "\ntm_stddev=" << a.tm_stddev << "\ncover_on_device=" << a.cover_on_device
-          << "\ncoverage_mismatches=" << a.coverage_mismatches << "\ncoverage_3p_exact=" << a.coverage_3p_exact << "\n";
+          << "\ncoverage_mismatches=" << a.coverage_mismatches << "\ncoverage_3p_exact=" << a.coverage_3p_exact
+          << "\nbackground=" << a.background << "\nbackground_mismatches=" << a.background_mismatches
+          << "\nbackground_3p_exact=" << a.background_3p_exact << "\nmax_background_sites=" << a.max_background_sites
+          << "\n";
         emit(o.str(), out, cap);
         return 0;
     } catch (const UsageError &e) {

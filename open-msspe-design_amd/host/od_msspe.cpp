@@ -73,6 +73,10 @@ const OptSpec kOpts[] = {
     {"--cover-on-device", "COVER_ON_DEVICE", OptSpec::Bool, OFF(cover_on_device)},
     {"--coverage-mismatches", "COVERAGE_MISMATCHES", OptSpec::Int, OFF(coverage_mismatches)},
     {"--coverage-3p-exact", "COVERAGE_3P_EXACT", OptSpec::Str, OFF(coverage_3p_exact_text)},
+    {"--background", "BACKGROUND", OptSpec::Str, OFF(background)},
+    {"--background-mismatches", "BACKGROUND_MISMATCHES", OptSpec::OptInt, OFF(background_mismatches)},
+    {"--background-3p-exact", "BACKGROUND_3P_EXACT", OptSpec::OptInt, OFF(background_3p_exact)},
+    {"--max-background-sites", "MAX_BACKGROUND_SITES", OptSpec::OptInt, OFF(max_background_sites)},
 };
 #undef OFF
 
@@ -116,6 +120,8 @@ std::string Args::usage()
                     "  -i, --input <INPUT>\n  -o, --output <OUTPUT>\n";
     for (const auto &o : kOpts) u += std::string("      ") + o.flag + " <...>  [env: " + o.env + "=]\n";
     u += "      --stddev-population   divide the Tm variance by n instead of n-1\n";
+    u += "\n--background <FASTA> screens the primers against unaligned background records (a host genome, rRNA) for\n"
+         "off-target sites on both strands; with --devices it runs on the first device.\n";
     return u;
 }
 
@@ -169,6 +175,21 @@ Args Args::parse(int argc, const char *const *argv)
                              std::to_string(a.kmer_size) + "'");
         a.coverage_3p_exact = (int)e;
     }
+    if (a.background.empty()) {
+        for (const auto &given : {std::make_pair("--background-mismatches", a.background_mismatches),
+                                  std::make_pair("--background-3p-exact", a.background_3p_exact),
+                                  std::make_pair("--max-background-sites", a.max_background_sites)})
+            if (given.second >= 0)
+                throw UsageError(std::string("error: '") + given.first + "' needs '--background <FASTA>'");
+    }
+    if (a.background_mismatches > a.kmer_size)
+        throw UsageError("error: '--background-mismatches " + std::to_string(a.background_mismatches) +
+                         "' is larger than '--kmer-size " + std::to_string(a.kmer_size) + "'");
+    if (a.background_3p_exact > a.kmer_size)
+        throw UsageError("error: '--background-3p-exact " + std::to_string(a.background_3p_exact) +
+                         "' is larger than '--kmer-size " + std::to_string(a.kmer_size) + "'");
+    if (a.background_mismatches < 0) a.background_mismatches = std::min(2, a.kmer_size);
+    if (a.background_3p_exact < 0) a.background_3p_exact = std::min(3, a.kmer_size);
     return a;
 }
 
@@ -894,6 +915,64 @@ std::string coverage_report_mm(Engine &eng, const DeviceAlignment &aln, const st
     return out;
 }
 
+DeviceBackground::DeviceBackground(Engine &eng, const std::vector<SequenceRecord> &records) : eng_(eng)
+{
+    std::vector<const char *> rows(records.size());
+    std::vector<size_t> bytes(records.size());
+    for (size_t r = 0; r < records.size(); ++r) {
+        rows[r] = records[r].sequence.data();
+        bytes[r] = records[r].sequence.size();
+    }
+    const int rc = msspe_device_put_stream_packed(eng.ctx(), rows.data(), bytes.data(), (int)records.size(), &dev_,
+                                                  &len_, nullptr);
+    if (rc) eng.fail(rc);
+}
+
+DeviceBackground::~DeviceBackground()
+{
+    if (dev_) (void)msspe_device_free(eng_.ctx(), dev_);
+}
+
+std::vector<std::pair<uint64_t, uint64_t>> DeviceBackground::sites(const std::vector<std::string> &words,
+                                                                  int max_mismatches, int exact_3p) const
+{
+    std::vector<std::pair<uint64_t, uint64_t>> out(words.size());
+    std::map<size_t, std::vector<size_t>> by_length;   // a panel of mixed lengths: one length class per call
+    for (size_t i = 0; i < words.size(); ++i) by_length[words[i].size()].push_back(i);
+    for (const auto &cls : by_length) {
+        const int k = (int)cls.first, n = (int)cls.second.size();
+        std::string flat;
+        for (const size_t i : cls.second) flat += words[i];
+        std::vector<uint64_t> packed((size_t)n), counts(2 * (size_t)n);
+        int rc = msspe_pack_oligos(flat.data(), n, k, packed.data());
+        if (rc) eng_.fail(rc);
+        const msspe_mismatch_opt mm{std::min(max_mismatches, k), std::min(exact_3p, k)};
+        rc = msspe_background_sites_packed_dev(eng_.ctx(), static_cast<const uint64_t *>(dev_), len_, k, &mm,
+                                               packed.data(), n, counts.data(), nullptr, 0, nullptr);
+        if (rc) eng_.fail(rc);
+        for (int j = 0; j < n; ++j) out[cls.second[(size_t)j]] = {counts[2 * (size_t)j], counts[2 * (size_t)j + 1]};
+    }
+    return out;
+}
+
+std::string background_report(const std::vector<std::string> &names,
+                              const std::vector<std::pair<uint64_t, uint64_t>> &sites, int max_mismatches,
+                              int exact_3p)
+{
+    std::string out = "\nBackground sites (up to " + std::to_string(max_mismatches) + " mismatches, last " +
+                      std::to_string(exact_3p) + " bases exact):\n";
+    uint64_t plus = 0, minus = 0;
+    for (size_t i = 0; i < names.size(); ++i) {
+        out += "  " + names[i] + ": plus " + std::to_string(sites[i].first) + ", minus " +
+               std::to_string(sites[i].second) + "\n";
+        plus += sites[i].first;
+        minus += sites[i].second;
+    }
+    out += "  Total: " + std::to_string(names.size()) + " primers, plus " + std::to_string(plus) + ", minus " +
+           std::to_string(minus) + "\n";
+    return out;
+}
+
 std::string primers_csv(const std::vector<KmerStat> &fwd, const std::vector<KmerStat> &rev, size_t first_f,
                         size_t first_r)
 {
@@ -970,6 +1049,33 @@ std::string align_sequences(const std::string &filepath)
     return out;
 }
 
+namespace {
+// the records of a FASTA file: regular files are mapped and parsed in place (no copy of a multi-hundred-MB input);
+// anything else (pipes) is read through a stream
+std::vector<SequenceRecord> read_records(const std::string &path)
+{
+    const int fd = ::open(path.c_str(), O_RDONLY);
+    if (fd < 0) throw std::runtime_error("cannot read " + path);
+    struct stat st;
+    void *map = MAP_FAILED;
+    if (::fstat(fd, &st) == 0 && S_ISREG(st.st_mode) && st.st_size > 0)
+        map = ::mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+    if (map != MAP_FAILED) {
+        (void)::madvise(map, (size_t)st.st_size, MADV_SEQUENTIAL);
+        auto records = to_records(static_cast<const char *>(map), (size_t)st.st_size);
+        (void)::munmap(map, (size_t)st.st_size);
+        ::close(fd);
+        return records;
+    }
+    ::close(fd);
+    std::ifstream f(path, std::ios::binary);
+    if (!f) throw std::runtime_error("cannot read " + path);
+    std::ostringstream all;
+    all << f.rdbuf();
+    return to_records(all.str());
+}
+}  // namespace
+
 int run(const Args &args, std::string &stdout_text)
 {
     PhaseTimer timer;
@@ -983,27 +1089,7 @@ int run(const Args &args, std::string &stdout_text)
         records = to_records(aligned);
         timer.lap("mafft");
     } else {
-        // regular files are mapped and parsed in place (no copy of a multi-hundred-MB input);
-        // anything else (pipes) is read through a stream
-        const int fd = ::open(args.input.c_str(), O_RDONLY);
-        if (fd < 0) throw std::runtime_error("cannot read " + args.input);
-        struct stat st;
-        void *map = MAP_FAILED;
-        if (::fstat(fd, &st) == 0 && S_ISREG(st.st_mode) && st.st_size > 0)
-            map = ::mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
-        if (map != MAP_FAILED) {
-            (void)::madvise(map, (size_t)st.st_size, MADV_SEQUENTIAL);
-            records = to_records(static_cast<const char *>(map), (size_t)st.st_size);
-            (void)::munmap(map, (size_t)st.st_size);
-            ::close(fd);
-        } else {
-            ::close(fd);
-            std::ifstream f(args.input, std::ios::binary);
-            if (!f) throw std::runtime_error("cannot read " + args.input);
-            std::ostringstream all;
-            all << f.rdbuf();
-            records = to_records(all.str());
-        }
+        records = read_records(args.input);
     }
     if (records.empty()) throw Panic("No sequences found in the input file");
     timer.lap("read + to_records");
@@ -1052,6 +1138,26 @@ int run(const Args &args, std::string &stdout_text)
     auto prim_r = cfg.keep_all ? stats_r : filter_kmers(stats_r, cfg);
 
     timer.lap("stage B + filter");
+    // --background: uploaded once; candidates with too many off-target sites go before the cross-dimer screen, so the
+    // vertex cover never spends a removal on them (the panel is reported below but never dropped)
+    std::unique_ptr<DeviceBackground> background;
+    if (!args.background.empty()) {
+        const auto bg_records = read_records(args.background);
+        if (bg_records.empty()) throw Panic("No sequences found in the background file");
+        background.reset(new DeviceBackground(eng, bg_records));
+        if (args.max_background_sites >= 0 && !cfg.keep_all)
+            for (auto *list : {&prim_f, &prim_r}) {
+                std::vector<std::string> words;
+                for (const auto &s : *list) words.push_back(s.word);
+                const auto sites = background->sites(words, args.background_mismatches, args.background_3p_exact);
+                size_t kept = 0;
+                for (size_t i = 0; i < list->size(); ++i)
+                    if (sites[i].first + sites[i].second <= (uint64_t)args.max_background_sites)
+                        (*list)[kept++] = (*list)[i];
+                list->resize(kept);
+            }
+        timer.lap("background upload + screen");
+    }
     const NtthalOptions opts{args.mv_conc, args.dv_conc, args.dntp_conc, args.dna_conc,
                              args.annealing_temp, args.delta_g_threshold};
     if (cfg.check_cross_dimers && !cfg.keep_all && (!panel_f.empty() || !panel_r.empty())) {
@@ -1088,6 +1194,20 @@ int run(const Args &args, std::string &stdout_text)
         stdout_text += coverage_report_mm(eng, aln, rep_f, rep_r, records, args.window_size, args.overlap_size,
                                           args.search_windows_size, args.kmer_size, args.coverage_mismatches,
                                           args.coverage_3p_exact);
+    if (background) {   // the CSV's primers by their CSV names, the panel's by the numbers the CSV continues from
+        std::vector<std::string> names, words;
+        for (const auto *panel_list : {&panel_f, &panel_r}) {
+            const bool fwd = panel_list == &panel_f;
+            const auto &good = fwd ? good_f : good_r;
+            for (size_t i = 0; i < panel_list->size() + good.size(); ++i) {
+                names.push_back("Primer_" + std::to_string(i) + (fwd ? "_F" : "_R"));
+                words.push_back(i < panel_list->size() ? (*panel_list)[i] : good[i - panel_list->size()].word);
+            }
+        }
+        stdout_text += background_report(names, background->sites(words, args.background_mismatches,
+                                                                  args.background_3p_exact),
+                                         args.background_mismatches, args.background_3p_exact);
+    }
     std::ofstream out(args.output, std::ios::binary);
     if (!out) throw std::runtime_error("cannot write " + args.output);
     out << primers_csv(good_f, good_r, panel_f.size(), panel_r.size());

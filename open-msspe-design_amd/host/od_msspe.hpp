@@ -59,6 +59,12 @@ struct Args {
     int coverage_mismatches = 0;
     std::string coverage_3p_exact_text = "3";   // read (as an integer) only when coverage_mismatches > 0
     int coverage_3p_exact = 3;
+    // --background FASTA: after the coverage report, the off-target sites of every kept primer in these records (both
+    // strands, up to background_mismatches mismatches, the last background_3p_exact bases exact:
+    // msspe_background_sites); with max_background_sites >= 0 candidates with more sites are dropped before the
+    // cross-dimer screen.  Empty: nothing changes.  -1 = not given (resolved to 2 / 3 / no limit by parse()).
+    std::string background;
+    int background_mismatches = -1, background_3p_exact = -1, max_background_sites = -1;
     bool stddev_population = false;  // crate std-dev 0.1.0's divisor is unpinned
     static Args parse(int argc, const char *const *argv);   // throws UsageError
     static std::string usage();
@@ -204,6 +210,27 @@ std::string coverage_report_mm(Engine &eng, const DeviceAlignment &aln, const st
 std::string coverage_report_mm(Engine &eng, const std::vector<KmerStat> &fwd, const std::vector<KmerStat> &rev,
                                const std::vector<SequenceRecord> &records, int segment_size, int overlap_size,
                                int window_size, int kmer_size, int max_mismatches, int exact_3p);
+// --background (engine extension): the records as one packed stream on the device, uploaded once
+class DeviceBackground {
+public:
+    DeviceBackground(Engine &eng, const std::vector<SequenceRecord> &records);
+    ~DeviceBackground();
+    DeviceBackground(const DeviceBackground &) = delete;
+    DeviceBackground &operator=(const DeviceBackground &) = delete;
+    // (plus, minus) sites of each word, one msspe_background_sites_packed_dev call per word length
+    std::vector<std::pair<uint64_t, uint64_t>> sites(const std::vector<std::string> &words, int max_mismatches,
+                                                     int exact_3p) const;
+
+private:
+    Engine &eng_;
+    void *dev_ = nullptr;
+    size_t len_ = 0;
+};
+// "Background sites (up to M mismatches, last E bases exact):", one line per primer (name as in the CSV, plus-strand
+// and minus-strand sites) and a totals line
+std::string background_report(const std::vector<std::string> &names,
+                              const std::vector<std::pair<uint64_t, uint64_t>> &sites, int max_mismatches,
+                              int exact_3p);
 // main.rs:834-858
 // first_f / first_r: the number of the first row of each direction (a panel's extension continues its numbering)
 std::string primers_csv(const std::vector<KmerStat> &fwd, const std::vector<KmerStat> &rev, size_t first_f = 0,

@@ -32,6 +32,7 @@ EXPORTS = [
     "msspe_kmer_candidates_both_seeded_packed_dev",
     "msspe_segment_coverage_packed_dev",
     "msspe_segment_coverage_mm", "msspe_segment_coverage_mm_dev", "msspe_segment_coverage_mm_packed_dev",
+    "msspe_device_put_stream_packed", "msspe_background_sites_packed_dev", "msspe_background_sites",
     "msspe_round_fixed_f32", "msspe_g_cut",
     "msspe_group_create", "msspe_group_destroy", "msspe_group_last_error", "msspe_group_size",
     "msspe_group_transport", "msspe_group_transport_reason", "msspe_group_rccl_available", "msspe_group_member", "msspe_group_set_option", "msspe_group_rows",
@@ -64,6 +65,10 @@ class KmerOpt(C.Structure):
     _fields_ = [("segment_size", C.c_int), ("overlap_size", C.c_int),
                 ("search_window_size", C.c_int), ("kmer_size", C.c_int),
                 ("max_iterations", C.c_int), ("max_mismatch_segments", C.c_int)]
+
+
+# msspe_site: one off-target site of the list msspe_background_sites* makes
+SITE_DTYPE = np.dtype([("primer", np.uint32), ("pos", np.uint32), ("mismatches", np.uint16), ("strand", np.uint16)])
 
 
 class MismatchOpt(C.Structure):
@@ -192,6 +197,13 @@ def load_library() -> C.CDLL:
                                             vp, C.c_int, vp, C.c_int, vp, vp]
     L.msspe_segment_coverage_mm_dev.argtypes = L.msspe_segment_coverage_mm.argtypes
     L.msspe_segment_coverage_mm_packed_dev.argtypes = L.msspe_segment_coverage_mm.argtypes
+    L.msspe_device_put_stream_packed.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int,
+                                                 C.POINTER(vp), C.POINTER(C.c_size_t), vp]
+    L.msspe_background_sites_packed_dev.argtypes = [vp, vp, C.c_size_t, C.c_int, C.POINTER(MismatchOpt), u64p, C.c_int,
+                                                    vp, vp, C.c_uint64, vp]
+    L.msspe_background_sites.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int,
+                                         C.POINTER(MismatchOpt), u64p, C.c_int, vp, vp, C.c_uint64,
+                                         C.POINTER(C.c_uint64), vp]
     L.msspe_round_g_f32.restype = C.c_float
     L.msspe_round_g_f32.argtypes = [C.c_double]
     L.msspe_round_fixed_f32.restype = C.c_float
@@ -209,6 +221,18 @@ def _words(x) -> np.ndarray:
     if isinstance(x, np.ndarray) and x.dtype == np.uint64:
         return np.ascontiguousarray(x)
     return pack_oligos(list(x)) if len(x) else np.zeros(0, dtype=np.uint64)
+
+
+def _words_k(x, k: int | None):
+    """Primer strings of one length (k read off them), or packed words with k given -> (uint64 words, k)."""
+    if isinstance(x, np.ndarray) and x.dtype == np.uint64:
+        if k is None:
+            raise ValueError("packed primer words need k=")
+        return np.ascontiguousarray(x), k
+    x = list(x)
+    if not x and k is None:
+        raise ValueError("an empty primer list needs k=")
+    return _words(x), (len(x[0]) if x else k)
 
 
 def pack_oligos(oligos) -> np.ndarray:
@@ -643,6 +667,64 @@ class Engine:
         self._check(fn(self.ptr, seqs_arg, n_seq, seq_len, C.byref(opt), C.byref(mm), f.ctypes.data, len(f),
                        r.ctypes.data, len(r), best.ctypes.data, counts.ctypes.data if per_primer else None))
         return (best, counts) if per_primer else best
+
+    # ---- off-target sites in a background ------------------------------------------------------
+    @staticmethod
+    def _records(records):
+        recs = [r.encode() if isinstance(r, str) else bytes(r) for r in records]
+        n = len(recs)
+        ptrs = (C.c_char_p * max(n, 1))(*recs)
+        lens = (C.c_size_t * max(n, 1))(*[len(r) for r in recs])
+        return recs, ptrs, lens, n
+
+    def put_stream_packed(self, records):
+        """Upload a background (a list of str / bytes records of any lengths) as one packed stream, packed on the
+        device behind the copy (msspe_device_put_stream_packed).  Returns (device address, total_len, record starts
+        uint64); free the address with device_free()."""
+        _recs, ptrs, lens, n = self._records(records)
+        dev, total = C.c_void_p(), C.c_size_t(0)
+        starts = np.zeros(n, dtype=np.uint64)
+        self._check(self.L.msspe_device_put_stream_packed(self.ptr, ptrs, lens, n, C.byref(dev), C.byref(total),
+                                                          starts.ctypes.data))
+        return int(dev.value), int(total.value), starts
+
+    def background_sites_packed(self, d_packed: int, total_len: int, primers, max_mismatches: int, exact_3p: int,
+                                k: int | None = None, d_sites: int = 0, capacity: int = 0, d_count: int = 0):
+        """Sites of each primer (strings, or packed uint64 words with k=) on a resident stream
+        (msspe_background_sites_packed_dev).  Returns counts, uint64 (n, 2): [:, 0] plus strand, [:, 1] minus.
+        d_sites / capacity / d_count: raw device addresses of a SITE_DTYPE list and its uint64 count (added to, the
+        caller zeroes it); 0 = no list."""
+        w, k = _words_k(primers, k)
+        counts = np.zeros((len(w), 2), dtype=np.uint64)
+        mm = MismatchOpt(max_mismatches, exact_3p)
+        self._check(self.L.msspe_background_sites_packed_dev(
+            self.ptr, C.c_void_p(d_packed), total_len, k, C.byref(mm), w.ctypes.data, len(w), counts.ctypes.data,
+            C.c_void_p(d_sites), capacity, C.c_void_p(d_count)))
+        return counts
+
+    def background_sites(self, records, primers, max_mismatches: int, exact_3p: int, k: int | None = None,
+                         capacity: int | None = None):
+        """Host form (msspe_background_sites): returns (counts, starts), or with a list capacity
+        (counts, starts, sites) -- sites a SITE_DTYPE array sorted by (primer, strand, pos).  A capacity below the
+        number of sites raises MsspeError (MSSPE_ERR_CAPACITY) carrying .count, .counts and the truncated .sites."""
+        _recs, ptrs, lens, n = self._records(records)
+        w, k = _words_k(primers, k)
+        counts = np.zeros((len(w), 2), dtype=np.uint64)
+        starts = np.zeros(n, dtype=np.uint64)
+        mm = MismatchOpt(max_mismatches, exact_3p)
+        sites = np.zeros(max(capacity, 1), dtype=SITE_DTYPE) if capacity is not None else None
+        count = C.c_uint64(0)
+        rc = self.L.msspe_background_sites(
+            self.ptr, ptrs, lens, n, k, C.byref(mm), w.ctypes.data, len(w), counts.ctypes.data,
+            sites.ctypes.data if sites is not None else None, capacity or 0, C.byref(count), starts.ctypes.data)
+        if rc:
+            err = MsspeError(rc, self.L.msspe_last_error(self.ptr).decode())
+            err.count, err.counts = int(count.value), counts
+            err.sites = sites[:min(int(count.value), capacity or 0)] if sites is not None else None
+            raise err
+        if sites is None:
+            return counts, starts
+        return counts, starts, sites[:count.value]
 
     def pair_stage_samples(self):
         """[(row, col, reason bits)] for up to 1024 pairs the integer stage handed on."""
