@@ -80,6 +80,7 @@ const char *msspe_version(void);
  *   "split_min_k"    "2".."99"    shortest oligo that goes to the split-table kernel (16; 14- and 15-mers run the row-specialised first stage)
  *   "wave_kernel"    "0" | "1"    one-wave-per-pair f64 kernel in the chain (1)
  *   "list_cap_log2"  "0" | "20".."30"   fixed hand-over list size (0: sized by the call)
+ *   "site_list_cap_log2" "12".."26"  msspe_background_thal*: the work list holds 2^this sites (22)
  *   "split_lanes"    "0" | "2" | "4" | "8"
  *   "split_list"     "0" | "1"    short oligos: tables too large for the integer list stage go to the split-table
  *                                 kernel's list mode (1) or straight to the f64 kernels (0)
@@ -102,6 +103,10 @@ int msspe_set_option(msspe_ctx *ctx, const char *key, const char *value);
  *                     the last msspe_kmer_candidates* call's greedy loop: iterations that recorded winners from the
  *                     partitions' leaders alone / after a walk over posting lists, candidate lists made, idle
  *                     iterations at the end of the last batch
+ *   "site_list_cap_log2"  the option's current value
+ *   "background_thal_slabs" / "background_thal_redone"
+ *                     the last msspe_background_thal* call: slabs scored, and slabs whose sites did not fit the work
+ *                     list and were split and listed again
  *   "cover_rounds"    the last msspe_conflict_cover* call: rounds that deleted nodes
  *   "cover_keys_us" / "cover_symmetrise_us" / "cover_rounds_us"
  *                     the same call's device time of its phases: sort and keys, S = B | B^T, the rounds
@@ -558,6 +563,58 @@ int msspe_background_sites_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, 
 int msspe_background_sites(msspe_ctx *ctx, const char *const *records, const size_t *record_bytes, int n_records,
                            int k, const msspe_mismatch_opt *mm, const uint64_t *words, int n, uint64_t *sites_out,
                            msspe_site *sites, uint64_t capacity, uint64_t *count_out, uint64_t *record_start_out);
+
+/* ---- thal score of every background site (engine extension) --------------------------------------------------
+ * msspe_background_sites* says where a primer lands by a string rule; these calls say which of those sites would
+ * hold the primer.  Take a site {primer u, pos p, strand s} of the rule above and let w be the k columns at p.  The
+ * TEMPLATE OLIGO o2 is the strand the primer anneals to, written 5'->3':
+ *   strand 0 (plus):  o2 = revcomp(w);
+ *   strand 1 (minus): o2 = w  (the near-copy of u there is revcomp(w), whose partner strand is w itself).
+ * Both oligos are k bases long, and an exact site gives o2 = revcomp(u) on either strand.  Bases beyond the window
+ * (dangling ends) are not part of the score.
+ * The SITE SCORE is thal of (oligo 1 = u, oligo 2 = o2) under chem; mode is 1 for ANY and 2 for END1, the numbering of
+ * msspe_thal_detail_pairs (END1: structures that close on the primer's 3' base, the ones that can prime).  Raw dG is
+ * +inf without a structure and raw t is 0 without one.  t_site = max(0, t), and a site is STABLE iff
+ * !(msspe_round_fixed_f32(t_site, 2) < tm_threshold), which the kernels test as t_site > msspe_t_cut(tm_threshold):
+ * the END screen's rule and stage B's.  A threshold <= 0 makes every site stable.
+ *   sites_out[2 i + s]  (uint64, HOST, 2 n): as msspe_background_sites_packed_dev returns for the same arguments.
+ *   stable_out[2 i + s] (uint64, HOST, 2 n): the stable sites of primer i on strand s, exact however many sites
+ *     there are.
+ *   The optional list follows the edge list's convention: one msspe_scored_site per SITE, stable or not, dg and t raw,
+ *     in no particular order; capacity and count are the caller's (the _packed_dev form adds to *d_count, which the
+ *     caller zeroes and which runs past the capacity; nothing is written behind d_sites[capacity - 1]).  The host form
+ *     sorts by (primer, strand, pos) and returns MSSPE_ERR_CAPACITY with a valid count, as msspe_background_sites.
+ * Memory is bounded and nothing is dropped: the scores pass through a work list of 2^site_list_cap_log2 sites in
+ * the context (msspe_set_option "site_list_cap_log2", 12..26, default 22: 44 bytes per entry; msspe_get_info reports
+ * it).  The stream is worked through in slabs of runs of 2048 positions; a slab whose sites exceed the work list
+ * -- the site kernel's counter runs past the capacity -- is split and done again (runs first, then primers: one
+ * run against one primer has at most 4096 sites), and no count ever comes from a truncated list.  msspe_get_info
+ * "background_thal_slabs" / "background_thal_redone": slabs scored / slabs split by the last call.
+ * Routing is the END screen's, over the explicit pair list: k <= 16 with a chemistry the register-table kernels take
+ * and max_loop >= 2 k - 4: the 56-slot list kernel, the 72-slot one, one wave per pair, the dense kernel; otherwise
+ * one wave per pair, then the dense kernel.  Options force_generic, wave_kernel and list_cap_log2 apply as there.
+ * Errors: the statuses of msspe_background_sites*; MSSPE_ERR_K for k outside 2..31 (thal needs two bases);
+ * MSSPE_ERR_ARG for a NULL chem or stable_out or a mode outside {1, 2}.  n == 0 or total_len < k: MSSPE_OK, outputs
+ * zeroed, list count 0 (_packed_dev: unchanged). */
+typedef struct {
+    uint32_t primer;       /* index into words */
+    uint32_t pos;          /* stream position of the window's first column */
+    uint16_t mismatches;   /* differing base positions, 0 .. max_mismatches */
+    uint16_t strand;       /* 0 plus, 1 minus */
+    uint32_t stable;       /* 1 iff max(0, t) > msspe_t_cut(tm_threshold) */
+    double dg;             /* raw dG, +inf without a structure */
+    double t;              /* raw t, 0 without a structure */
+} msspe_scored_site;
+int msspe_background_thal_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, size_t total_len, int k,
+                                     const msspe_mismatch_opt *mm, const uint64_t *words, int n,
+                                     const msspe_chem *chem, int mode, float tm_threshold, uint64_t *sites_out,
+                                     uint64_t *stable_out, msspe_scored_site *d_sites, uint64_t capacity,
+                                     uint64_t *d_count);
+int msspe_background_thal(msspe_ctx *ctx, const char *const *records, const size_t *record_bytes, int n_records,
+                          int k, const msspe_mismatch_opt *mm, const uint64_t *words, int n, const msspe_chem *chem,
+                          int mode, float tm_threshold, uint64_t *sites_out, uint64_t *stable_out,
+                          msspe_scored_site *sites, uint64_t capacity, uint64_t *count_out,
+                          uint64_t *record_start_out);
 
 
 /* ---- several devices of one node ----------------------------------------------------------

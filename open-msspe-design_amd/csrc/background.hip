@@ -78,88 +78,29 @@ __global__ void __launch_bounds__(kThreads) k_background_sites(const uint64_t *p
                                                                unsigned long long *counts, msspe_site *sites,
                                                                unsigned long long capacity, unsigned long long *count)
 {
-    extern __shared__ __align__(16) unsigned char smem[];
-    __shared__ uint32_t s_lo[kRunWords], s_hi[kRunWords], s_ok[kRunWords];
-    T *tile = reinterpret_cast<T *>(smem);
-    uint32_t *scnt = reinterpret_cast<uint32_t *>(smem + (size_t)tile_cap * sizeof(T));   // [2 i + s]
-    const int tid = threadIdx.x;
-    const size_t bw = (total_len + 31) / 32, vw2 = 2 * ((total_len + 63) / 64);
-    const uint32_t *ok32 = reinterpret_cast<const uint32_t *>(packed + bw);   // validity, 32 columns per word
-    const uint32_t kmask = (uint32_t)((1ull << k) - 1ull);
-    const uint32_t run0 = (uint32_t)((uint64_t)blockIdx.x * n_runs / gridDim.x);
-    const uint32_t run1 = (uint32_t)((uint64_t)(blockIdx.x + 1) * n_runs / gridDim.x);
+#define BG_RUN_BASE
+#define BG_PRIMER_BASE
+#include "background_sites_body.inc"
+#undef BG_RUN_BASE
+#undef BG_PRIMER_BASE
+}
 
-    for (int t0 = 0; t0 < n; t0 += tile_cap) {
-        const int cnt = std::min(tile_cap, n - t0), cnt4 = (cnt + 3) & ~3;
-        __syncthreads();   // the previous tile's counters are out
-        for (int i = tid; i < cnt4; i += kThreads) tile[i] = words[t0 + std::min(i, cnt - 1)];   // pad: repeats
-        for (int i = tid; i < 2 * cnt4; i += kThreads) scnt[i] = 0u;
-        for (uint32_t run = run0; run < run1; ++run) {
-            const uint32_t r0 = run * kRun;   // n_runs * kRun <= 2^32: the last run's r0 fits
-            __syncthreads();                  // the previous run's windows are cut (and the tile is staged)
-            if (tid < kRunWords) {
-                const size_t wi = (size_t)(r0 >> 5) + (size_t)tid;
-                const uint64_t b = wi < bw ? packed[wi] : 0ull;
-                s_lo[tid] = even_bits(b);
-                s_hi[tid] = even_bits(b >> 1);
-                s_ok[tid] = wi < vw2 ? ok32[wi] : 0u;   // columns past the stream: not bases
-            }
-            __syncthreads();
-            uint2 w[2][kItems];   // [0] the window, [1] its reverse complement
-            uint32_t valid = 0;   // bit j: window j holds k bases
-#pragma unroll
-            for (int j = 0; j < kItems; ++j) {
-                const int pl = j * kThreads + tid, i = pl >> 5;
-                const uint32_t sh = (uint32_t)(pl & 31);
-                const uint32_t lo = __builtin_amdgcn_alignbit(s_lo[i + 1], s_lo[i], sh) & kmask;
-                const uint32_t hi = __builtin_amdgcn_alignbit(s_hi[i + 1], s_hi[i], sh) & kmask;
-                const uint32_t ok = __builtin_amdgcn_alignbit(s_ok[i + 1], s_ok[i], sh) & kmask;
-                valid |= (uint32_t)(ok == kmask) << j;
-                w[0][j] = make_word(lo, hi, T());
-                w[1][j] = make_word(~(__brev(lo) >> (32 - k)) & kmask, ~(__brev(hi) >> (32 - k)) & kmask, T());
-            }
-            for (int i = 0; i < cnt4; i += 4) {
-                uint2 u[4];
-                load4(tile, i, u);
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-#pragma unroll
-                    for (int s = 0; s < 2; ++s) {
-                        uint32_t m = 255u;
-#pragma unroll
-                        for (int j = 0; j < kItems; ++j) m = std::min(m, (uint32_t)__popc(diff_mask(w[s][j], u[q])));
-                        if (__any(m <= max_score)) {   // rare: some lane of the wave is within the mismatch count
-                            if (i + q < cnt) {
-#pragma unroll
-                                for (int j = 0; j < kItems; ++j) {
-                                    const uint32_t d = diff_mask(w[s][j], u[q]);
-                                    const uint32_t pc = (uint32_t)__popc(d);
-                                    if (((valid >> j) & 1u) && d <= lim && pc <= max_score) {
-                                        atomicAdd(&scnt[2 * (i + q) + s], 1u);
-                                        if (LIST) {
-                                            const unsigned long long at = atomicAdd(count, 1ull);
-                                            if (at < capacity) {
-                                                msspe_site rec;
-                                                rec.primer = (uint32_t)(t0 + i + q);
-                                                rec.pos = r0 + (uint32_t)(j * kThreads + tid);
-                                                rec.mismatches = (uint16_t)(pc / (uint32_t)scale);
-                                                rec.strand = (uint16_t)s;
-                                                sites[at] = rec;
-                                            }
-                                        }
-                                    }
-                                }
-                            }
-                        }
-                    }
-            }
-        }
-        __syncthreads();
-        for (int i = tid; i < 2 * cnt; i += kThreads) {
-            const uint32_t c = scnt[i];
-            if (c) atomicAdd(&counts[2 * (size_t)t0 + (size_t)i], (unsigned long long)c);
-        }
-    }
+// One slab for msspe_background_thal*: the runs [run_base, run_base + n_runs) against the n words at `words`, which
+// are the primers primer_base .. of the caller's list (a record carries the caller's index); always with the list,
+// whose counter says whether the slab fitted.
+template <typename T, bool LIST>
+__global__ void __launch_bounds__(kThreads) k_background_slab(const uint64_t *packed, size_t total_len, int k,
+                                                              const T *words, int n, int tile_cap, uint32_t lim,
+                                                              uint32_t max_score, int scale, uint32_t n_runs,
+                                                              unsigned long long *counts, msspe_site *sites,
+                                                              unsigned long long capacity, unsigned long long *count,
+                                                              uint32_t run_base, uint32_t primer_base)
+{
+#define BG_RUN_BASE run_base +
+#define BG_PRIMER_BASE primer_base +
+#include "background_sites_body.inc"
+#undef BG_RUN_BASE
+#undef BG_PRIMER_BASE
 }
 
 // one thread per output word: 32 columns of bases or 64 of validity
@@ -256,6 +197,24 @@ int launch(const uint64_t *d_packed, size_t total_len, int k, int M, int E, cons
     return MSSPE_OK;
 }
 
+template <typename T>
+void launch_slab(const uint64_t *d_packed, size_t total_len, int k, int M, int E, const T *d_words, int n,
+                 uint32_t primer_base, uint32_t run_base, uint32_t n_runs, unsigned long long *d_counts,
+                 msspe_site *d_sites, uint64_t capacity, uint64_t *d_count, int n_cu, hipStream_t stream)
+{
+    constexpr bool narrow = sizeof(T) == 4;
+    const int scale = narrow ? 2 : 1;
+    const int s = k - E;
+    const uint32_t lim = narrow ? (s >= 16 ? 0xffffffffu : (1u << (16 + s)) - 1u) : (uint32_t)((1ull << s) - 1ull);
+    const size_t per_word = sizeof(T) + 2 * sizeof(uint32_t);
+    const int tile_cap = std::max(4, std::min((int)(kTileBytes / per_word) & ~3, (n + 3) & ~3));
+    const size_t lds = (size_t)tile_cap * per_word;
+    const unsigned grid = (unsigned)std::min<uint64_t>(n_runs, (uint64_t)std::max(1, n_cu) * kBlocksPerCu);
+    hipLaunchKernelGGL((k_background_slab<T, true>), dim3(grid), dim3(kThreads), lds, stream, d_packed, total_len, k,
+                       d_words + primer_base, n, tile_cap, lim, (uint32_t)(M * scale), scale, n_runs, d_counts,
+                       d_sites, (unsigned long long)capacity, (unsigned long long *)d_count, run_base, primer_base);
+}
+
 }  // namespace
 
 hipError_t launch_pack_stream(const uint8_t *d_ascii, size_t n_cols, uint64_t *bases, uint64_t *valid,
@@ -290,6 +249,73 @@ void BackgroundSites::release()
         buf_[s] = nullptr;
         cap_[s] = 0;
     }
+}
+
+uint32_t BackgroundSites::n_runs(size_t total_len, int k)
+{
+    return (uint32_t)(((uint64_t)total_len - (uint64_t)k + 1 + kRun - 1) / kRun);
+}
+
+int BackgroundSites::check(size_t total_len, int k, int max_mismatches, int exact_3p, const uint64_t *words, int n,
+                           std::string &err)
+{
+    if (k < 1 || k > 31) {
+        err = "background_sites: unsupported k (need 1 <= k <= 31)";
+        return MSSPE_ERR_K;
+    }
+    if (max_mismatches < 0 || max_mismatches > k || exact_3p < 0 || exact_3p > k) {
+        err = "background_sites: max_mismatches and exact_3p must lie in 0..k";
+        return MSSPE_ERR_ARG;
+    }
+    if ((uint64_t)total_len >= (1ull << 32)) {
+        err = "background_sites: the stream must be shorter than 2^32 columns";
+        return MSSPE_ERR_ARG;
+    }
+    if (n < 0) {
+        err = "background_sites: null argument";
+        return MSSPE_ERR_ARG;
+    }
+    const uint64_t high = ~0ull << (2 * k);
+    for (int i = 0; i < n; ++i)
+        if (words[i] & high) {
+            err = "background_sites: a primer word has bits above 2 k";
+            return MSSPE_ERR_ARG;
+        }
+    return MSSPE_OK;
+}
+
+int BackgroundSites::prepare(int k, const uint64_t *words, int n, hipStream_t stream, std::string &err)
+{
+    const bool narrow = k <= 16;
+    int rc;
+    if ((rc = ensure(0, (narrow ? 4 : 8) * (size_t)n, err)) || (rc = ensure(1, sizeof(uint64_t) * 2 * (size_t)n, err)))
+        return rc;
+    w32_.clear();
+    w64_.clear();
+    if (narrow) {
+        to_planes<uint32_t>(words, n, w32_);
+        BG_TRY(hipMemcpyAsync(buf_[0], w32_.data(), sizeof(uint32_t) * w32_.size(), hipMemcpyHostToDevice, stream));
+    } else {
+        to_planes<uint2>(words, n, w64_);
+        BG_TRY(hipMemcpyAsync(buf_[0], w64_.data(), sizeof(uint2) * w64_.size(), hipMemcpyHostToDevice, stream));
+    }
+    return MSSPE_OK;
+}
+
+int BackgroundSites::list_slab(const uint64_t *d_packed, size_t total_len, int k, int max_mismatches, int exact_3p,
+                               int p0, int p1, uint32_t run0, uint32_t run1, msspe_site *d_sites, uint64_t capacity,
+                               uint64_t *d_count, int n_cu, hipStream_t stream, std::string &err)
+{
+    if (p1 <= p0 || run1 <= run0) return MSSPE_OK;
+    unsigned long long *scratch = (unsigned long long *)buf_[1] + 2 * (size_t)p0;   // per-slab counts: not read
+    if (k <= 16)
+        launch_slab<uint32_t>(d_packed, total_len, k, max_mismatches, exact_3p, (const uint32_t *)buf_[0], p1 - p0,
+                              (uint32_t)p0, run0, run1 - run0, scratch, d_sites, capacity, d_count, n_cu, stream);
+    else
+        launch_slab<uint2>(d_packed, total_len, k, max_mismatches, exact_3p, (const uint2 *)buf_[0], p1 - p0,
+                           (uint32_t)p0, run0, run1 - run0, scratch, d_sites, capacity, d_count, n_cu, stream);
+    BG_TRY(hipGetLastError());
+    return MSSPE_OK;
 }
 
 int BackgroundSites::run(const uint64_t *d_packed, size_t total_len, int k, int max_mismatches, int exact_3p,

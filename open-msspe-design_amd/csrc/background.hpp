@@ -29,6 +29,20 @@ public:
             uint64_t *d_count, int n_cu, hipStream_t stream, std::string &err);
     void release();
 
+    // The pieces msspe_background_thal* drives itself.  check: run()'s argument statuses.  prepare: the n primer
+    // words in plane form on the device (kept until the next prepare or run).  list_slab: the site list -- no
+    // counts -- of primers [p0, p1) over the runs [run0, run1) of the stream, n_runs() runs of 2048 positions in all;
+    // *d_count (zeroed by the caller) runs past the capacity, which is how a slab that did not fit is seen.  One
+    // run against one primer has at most kMaxSitesPerRunPrimer sites.
+    static constexpr uint32_t kMaxSitesPerRunPrimer = 4096;
+    static uint32_t n_runs(size_t total_len, int k);
+    static int check(size_t total_len, int k, int max_mismatches, int exact_3p, const uint64_t *words, int n,
+                     std::string &err);
+    int prepare(int k, const uint64_t *words, int n, hipStream_t stream, std::string &err);
+    int list_slab(const uint64_t *d_packed, size_t total_len, int k, int max_mismatches, int exact_3p, int p0, int p1,
+                  uint32_t run0, uint32_t run1, msspe_site *d_sites, uint64_t capacity, uint64_t *d_count, int n_cu,
+                  hipStream_t stream, std::string &err);
+
 private:
     void *buf_[2] = {};      // [0] primer words in plane form, [1] 2 n 64-bit counts
     size_t cap_[2] = {};

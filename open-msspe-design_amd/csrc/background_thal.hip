@@ -1,0 +1,116 @@
+// background_thal.hip -- what lies between the background site list (background.hip) and the f64 thal kernels that
+// take explicit pair lists (engine extension, no reference counterpart: include/msspe_hip.h msspe_background_thal*).
+//
+// k_site_oligos: one lane per site record.  The k columns at pos are cut out of the packed 2-bit row (a window
+// straddles at most two 64-bit words for k <= 31; a site's window is all bases, so the validity words are not read).
+// The packed row and msspe_pack_oligos agree on the coding (A C G T = 0 1 2 3, the first base in the low bits), so
+// the window IS the word of the minus-strand site's template; the plus strand's is its reverse complement: v_bfrev,
+// a swap within pairs, a shift and a not.  The word goes into the site pool behind the primers, P' = [primers | site
+// oligos], and the pair is (primer, n + idx): a PairSinks with ncols = 0 and col0 = n then lands on the list index.
+//
+// k_site_fold: one lane per scored site.  Sites arrive grouped by (primer, strand) in long stretches (the site
+// kernel walks the primers of a tile in order), so a wave whose lanes agree on the key adds its two popcounts with
+// one atomic each; a mixed wave adds per lane.  The caller's records take one atomic per wave for their places.
+#include "background_thal.hpp"
+
+#include <cmath>
+
+namespace msspe {
+namespace {
+
+constexpr int kThreads = 256;
+
+__device__ __forceinline__ uint64_t revcomp_word(uint64_t w, int k)
+{
+    uint64_t r = __brevll(w);                                                       // bases and their bits reversed
+    r = ((r >> 1) & 0x5555555555555555ull) | ((r & 0x5555555555555555ull) << 1);    // bit order inside a base restored
+    return ~(r >> (64 - 2 * k)) & ((1ull << (2 * k)) - 1ull);                       // 3 - b is ~b on two bits
+}
+
+__global__ void __launch_bounds__(kThreads) k_site_oligos(const uint64_t *packed, size_t total_len, int k,
+                                                          const msspe_site *sites, uint32_t first, uint32_t count,
+                                                          int n, uint64_t *pool, uint2 *list, uint32_t *list_count)
+{
+    const uint32_t e = blockIdx.x * kThreads + threadIdx.x;
+    if (e == 0) *list_count = count;
+    if (e >= count) return;
+    const uint32_t idx = first + e;
+    const msspe_site s = sites[idx];
+    const size_t bw = (total_len + 31) / 32, wi = (size_t)(s.pos >> 5);
+    const int sh = 2 * (int)(s.pos & 31u);
+    const uint64_t lo = wi < bw ? packed[wi] : 0ull;
+    const uint64_t hi = (sh + 2 * k > 64 && wi + 1 < bw) ? packed[wi + 1] : 0ull;
+    uint64_t w = sh ? (lo >> sh) | (hi << (64 - sh)) : lo;
+    w &= (1ull << (2 * k)) - 1ull;
+    pool[(size_t)n + idx] = s.strand ? w : revcomp_word(w, k);
+    list[e] = make_uint2(s.primer, (uint32_t)n + idx);
+}
+
+__global__ void __launch_bounds__(kThreads) k_site_fold(const msspe_site *sites, uint32_t count, const double *dg,
+                                                        const double *t, double t_cut, int n,
+                                                        unsigned long long *counts, msspe_scored_site *out,
+                                                        unsigned long long capacity, unsigned long long *out_count)
+{
+    const uint32_t idx = blockIdx.x * kThreads + threadIdx.x;
+    const bool live = idx < count;
+    const int lane = threadIdx.x & 63;
+    msspe_site s = sites[live ? idx : 0];
+    const double ti = live ? t[idx] : 0.0, gi = live ? dg[idx] : 0.0;
+    const bool stable = live && (ti > 0.0 ? ti : 0.0) > t_cut;
+    const uint32_t key = 2u * s.primer + s.strand;
+    const unsigned long long m_live = __ballot(live), m_stable = __ballot(stable);
+    if (!m_live) return;   // wave-uniform
+    const uint32_t key0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)key);   // lane 0 is live where any lane is
+    if (__all(!live || key == key0)) {
+        if (lane == 0) {
+            atomicAdd(&counts[key0], (unsigned long long)__popcll(m_live));
+            if (m_stable) atomicAdd(&counts[2 * (size_t)n + key0], (unsigned long long)__popcll(m_stable));
+        }
+    } else if (live) {
+        atomicAdd(&counts[key], 1ull);
+        if (stable) atomicAdd(&counts[2 * (size_t)n + key], 1ull);
+    }
+    if (out_count) {
+        unsigned long long base = 0;
+        if (lane == 0) base = atomicAdd(out_count, (unsigned long long)__popcll(m_live));
+        base = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(base >> 32)) << 32) |
+               (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+        const unsigned long long at = base + (unsigned long long)__popcll(m_live & ((1ull << lane) - 1ull));
+        if (live && at < capacity) {
+            msspe_scored_site r;
+            r.primer = s.primer;
+            r.pos = s.pos;
+            r.mismatches = s.mismatches;
+            r.strand = s.strand;
+            r.stable = stable ? 1u : 0u;
+            r.dg = gi;
+            r.t = ti;
+            out[at] = r;
+        }
+    }
+}
+
+}  // namespace
+
+hipError_t launch_site_oligos(const uint64_t *d_packed, size_t total_len, int k, const msspe_site *d_sites,
+                              uint32_t first, uint32_t count, int n, uint64_t *pool, uint2 *list,
+                              uint32_t *list_count, hipStream_t stream)
+{
+    if (!count) return hipSuccess;
+    hipLaunchKernelGGL(k_site_oligos, dim3((count + kThreads - 1) / kThreads), dim3(kThreads), 0, stream, d_packed,
+                       total_len, k, d_sites, first, count, n, pool, list, list_count);
+    return hipGetLastError();
+}
+
+hipError_t launch_site_fold(const msspe_site *d_sites, uint32_t count, const double *dg, const double *t,
+                            double t_cut, int n, unsigned long long *counts, msspe_scored_site *d_out,
+                            uint64_t capacity, uint64_t *d_count, hipStream_t stream)
+{
+    if (!count) return hipSuccess;
+    hipLaunchKernelGGL(k_site_fold, dim3((count + kThreads - 1) / kThreads), dim3(kThreads), 0, stream, d_sites,
+                       count, dg, t, t_cut, n, counts, d_out, (unsigned long long)capacity,
+                       (unsigned long long *)d_count);
+    return hipGetLastError();
+}
+
+}  // namespace msspe

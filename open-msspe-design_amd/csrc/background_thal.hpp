@@ -1,0 +1,28 @@
+// background_thal.hpp -- the kernels between the background site list and the thal pair kernels
+// (include/msspe_hip.h msspe_background_thal*): a site's template oligo, and the fold of the scores.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+
+#include "../../include/msspe_hip.h"
+
+namespace msspe {
+
+// Sites [first, first + count) of d_sites (positions in the packed stream d_packed of total_len columns): the
+// template oligo of site idx -- the strand the primer anneals to, 5'->3', msspe_pack_oligos form -- goes to
+// pool[n + idx] and the pair (primer, n + idx) to list[idx - first]; *list_count = count.
+hipError_t launch_site_oligos(const uint64_t *d_packed, size_t total_len, int k, const msspe_site *d_sites,
+                              uint32_t first, uint32_t count, int n, uint64_t *pool, uint2 *list,
+                              uint32_t *list_count, hipStream_t stream);
+
+// Sites [0, count) with their raw scores dg[idx], t[idx]: counts[2 i + s] += sites, counts[2 n + 2 i + s] += stable
+// ones (max(0, t) > t_cut) of primer i on strand s; with d_count, one msspe_scored_site per site is appended to
+// d_out (at most capacity are stored, *d_count runs on).
+hipError_t launch_site_fold(const msspe_site *d_sites, uint32_t count, const double *dg, const double *t,
+                            double t_cut, int n, unsigned long long *counts, msspe_scored_site *d_out,
+                            uint64_t capacity, uint64_t *d_count, hipStream_t stream);
+
+}  // namespace msspe

@@ -23,6 +23,7 @@
 
 #include "conflict_cover.hpp"
 #include "background.hpp"
+#include "background_thal.hpp"
 #include "coverage_mm.hpp"
 #include "kernels.hpp"
 #include "kmer_stage.hpp"
@@ -36,7 +37,8 @@ namespace {
 struct ChemEntry {
     msspe_chem chem;
     float threshold;
-    bool end = false;             // the END screen's entry: c[].g_cut holds t_cut(threshold), not g_cut(threshold)
+    int kind = 0;                 // kCutAnyDg: c[].g_cut = g_cut(threshold); kCutEndT (the END screen's entry) and
+                                  // kCutAnyT (ANY site scores of msspe_background_thal*): t_cut(threshold)
     ThalConsts c[2];
     PairTables *d_pt = nullptr;   // 2 entries: ordinary, both self-complementary
     FastTables *d_ft = nullptr;   // tables of the tuned all-pairs kernel (ordinary pairs)
@@ -49,6 +51,7 @@ struct ChemEntry {
     int wave_max_k = 0;           // f64 one-wave-per-pair kernel (thal_pairs_wave.hip)
 };
 
+constexpr int kCutAnyDg = 0, kCutEndT = 1, kCutAnyT = 2;   // ChemEntry::kind: one cache entry per kind, chemistry and threshold
 constexpr long kChunkPairs = 1L << 29;       // pairs per launch of the all-pairs kernel (a launch's tail: 2.4 % at 2^24, 1.4 % at 2^26; a 65,536-primer
                                              // pool: 1850 ms at 2^27, 1822 at 2^29, 1819 at 2^30 -- and a hand-over list of as many entries, 4 GB, twice)
 constexpr int kHairpinLaneFrom = 8192;       // oligos per call from which HAIRPIN_TH runs one lane per oligo (msspe_oligo_stats_dev)
@@ -76,6 +79,7 @@ struct EngineOptions {
     bool split_list = true;   // short oligos: tables too large for the integer list stage go to the split kernel's list mode
     bool short_chain = true;  // screens of up to 2^23 pairs: integer list stage -> one wave per pair (no register-table stages between)
     int self_lane_from = 81920;   // oligos per call from which SELF_ANY / SELF_END run one lane per oligo (msspe_oligo_stats_dev)
+    int site_list_cap_log2 = 22;  // msspe_background_thal*: work list of 2^this sites (44 bytes each: 185 MB)
 };
 
 struct msspe_ctx {
@@ -112,6 +116,20 @@ struct msspe_ctx {
     MismatchCoverage mm_cov;           // msspe_segment_coverage_mm*: primer words, counts, per-segment minima
     BackgroundSites background;        // msspe_background_sites*: primer words in plane form, per-primer counts
     CoverStage cover;                  // msspe_conflict_cover*: the symmetrised bitmap and the round state
+    // msspe_background_thal*: the work list (site records, their pairs, raw dG and t), the site pool [primers | site
+    // oligos], 4 n counts (sites, then stable sites) and the slab's site counter
+    struct SiteWork {
+        msspe_site *sites = nullptr;
+        uint2 *list = nullptr;
+        double *dg = nullptr, *t = nullptr;
+        size_t cap = 0;
+        uint64_t *pool = nullptr;
+        size_t pool_cap = 0;
+        unsigned long long *counts = nullptr;
+        size_t counts_cap = 0;
+        uint64_t *slab_count = nullptr;
+        long long slabs = 0, redone = 0;   // of the last call
+    } site_work;
     // optional profiling of the dominant kernel (k_pairs_fast) with HIP events on ctx->stream
     bool prof_on = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events;
@@ -155,12 +173,13 @@ bool same_chem(const msspe_chem &a, const msspe_chem &b)
            a.temp_c == b.temp_c && a.max_loop == b.max_loop;
 }
 
-// end: the entry of the END screen (msspe_cross_dimer_end*), whose cut is msspe_t_cut(threshold); it is cached apart
-// from the thal ANY entry of the same chemistry and threshold, so that neither call can pick up the other's cut.
-int chem_entry(msspe_ctx *ctx, const msspe_chem &chem, float threshold, ChemEntry **out, bool end = false)
+// kind: kCutEndT is the entry of the END screen (msspe_cross_dimer_end*), whose cut is msspe_t_cut(threshold), and
+// kCutAnyT that of an ANY fill decided on t (msspe_background_thal*, mode 1); each kind is cached apart from the
+// others of the same chemistry and threshold, so that no call can pick up another's cut.
+int chem_entry(msspe_ctx *ctx, const msspe_chem &chem, float threshold, ChemEntry **out, int kind = kCutAnyDg)
 {
     for (auto &e : ctx->chem_cache)
-        if (same_chem(e.chem, chem) && e.end == end && (e.threshold == threshold ||
+        if (same_chem(e.chem, chem) && e.kind == kind && (e.threshold == threshold ||
                                         (std::isnan(e.threshold) && std::isnan(threshold)))) {
             *out = &e;
             return MSSPE_OK;
@@ -170,7 +189,7 @@ int chem_entry(msspe_ctx *ctx, const msspe_chem &chem, float threshold, ChemEntr
     ChemEntry e;
     e.chem = chem;
     e.threshold = threshold;
-    e.end = end;
+    e.kind = kind;
     PairTables host_pt[2];
     for (int sym = 0; sym < 2; ++sym) {
         e.c[sym] = make_dimer_consts(chem.mv, chem.dv, chem.dntp, chem.dna_conc, chem.temp_c,
@@ -197,7 +216,7 @@ int chem_entry(msspe_ctx *ctx, const msspe_chem &chem, float threshold, ChemEntr
         HIP_TRY(ctx, hipMalloc((void **)&e.d_st, sizeof(SplitTables)));
         HIP_TRY(ctx, hipMemcpy(e.d_st, st.get(), sizeof(SplitTables), hipMemcpyHostToDevice));
     }
-    if (end)
+    if (kind != kCutAnyDg)
         for (auto &c : e.c) c.g_cut = t_cut(threshold);
     ctx->chem_cache.push_back(e);
     *out = &ctx->chem_cache.back();
@@ -407,6 +426,9 @@ int msspe_set_option(msspe_ctx *ctx, const char *key, const char *value)
     } else if (k == "self_lane_from") {
         if (!is_num || num < 0) return bad();
         ctx->opt.self_lane_from = (int)num;
+    } else if (k == "site_list_cap_log2") {
+        if (!is_num || num < 12 || num > 26) return bad();   // 2^12: what one run against one primer can hold
+        ctx->opt.site_list_cap_log2 = (int)num;
     } else if (k == "row_oob") {
         if (!is_num || num < 0 || num > 1) return bad();
         ctx->opt.row_oob = num != 0;
@@ -438,6 +460,9 @@ int msspe_get_info(msspe_ctx *ctx, const char *key, long long *value_out)
     else if (k == "stage_a_general_iterations") *value_out = ctx->kmer.loop_stats()[1];
     else if (k == "stage_a_rebuilds") *value_out = ctx->kmer.loop_stats()[2];
     else if (k == "stage_a_idle_iterations") *value_out = ctx->kmer.loop_stats()[3];
+    else if (k == "site_list_cap_log2") *value_out = ctx->opt.site_list_cap_log2;
+    else if (k == "background_thal_slabs") *value_out = ctx->site_work.slabs;
+    else if (k == "background_thal_redone") *value_out = ctx->site_work.redone;
     else if (k == "cover_rounds") *value_out = ctx->cover.rounds();
     else if (k == "cover_keys_us") *value_out = ctx->cover.phase_us()[0];
     else if (k == "cover_symmetrise_us") *value_out = ctx->cover.phase_us()[1];
@@ -478,6 +503,12 @@ void msspe_destroy(msspe_ctx *ctx)
         ctx->cover.release();
         ctx->mm_cov.release();
         ctx->background.release();
+        {
+            auto &w = ctx->site_work;
+            for (void *q : {(void *)w.sites, (void *)w.list, (void *)w.dg, (void *)w.t, (void *)w.pool,
+                            (void *)w.counts, (void *)w.slab_count})
+                if (q) (void)hipFree(q);
+        }
         if (ctx->ev_rev) (void)hipEventDestroy(ctx->ev_rev);
         if (ctx->stream_rev) {
             (void)hipStreamSynchronize(ctx->stream_rev);
@@ -936,7 +967,7 @@ static int cross_dimer_end_impl(msspe_ctx *ctx, const uint64_t *d_pool, int n, i
     if (row0 == row1 || col0 == col1) return MSSPE_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     ChemEntry *ce = nullptr;
-    int rc = chem_entry(ctx, *chem, tm_threshold, &ce, true);
+    int rc = chem_entry(ctx, *chem, tm_threshold, &ce, kCutEndT);
     if (rc) return rc;
     const bool reg = k2 == k && !ctx->opt.force_generic && k <= pairs_fast_max_k() && ce->fast_ok &&
                      chem->max_loop >= 2 * k - 4;   // the tuned kernel has no loop-size cut-off
@@ -2272,6 +2303,268 @@ int msspe_background_sites(msspe_ctx *ctx, const char *const *records, const siz
     if (d_sites) (void)hipFree(d_sites);
     (void)msspe_device_free(ctx, d);
     if (e != hipSuccess) return hip_fail(ctx, e, "msspe_background_sites");
+    return rc;
+}
+
+namespace {
+
+int ensure_site_work(msspe_ctx *ctx, size_t cap, int n)
+{
+    auto &w = ctx->site_work;
+    if (w.cap != cap) {
+        if (w.sites || w.list || w.dg || w.t) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        for (void *q : {(void *)w.sites, (void *)w.list, (void *)w.dg, (void *)w.t})
+            if (q) (void)hipFree(q);
+        w.sites = nullptr;
+        w.list = nullptr;
+        w.dg = w.t = nullptr;
+        w.cap = 0;
+        hipError_t e = hipMalloc((void **)&w.sites, sizeof(msspe_site) * cap);
+        if (e == hipSuccess) e = hipMalloc((void **)&w.list, sizeof(uint2) * cap);
+        if (e == hipSuccess) e = hipMalloc((void **)&w.dg, sizeof(double) * cap);
+        if (e == hipSuccess) e = hipMalloc((void **)&w.t, sizeof(double) * cap);
+        if (e != hipSuccess) {
+            for (void *q : {(void *)w.sites, (void *)w.list, (void *)w.dg, (void *)w.t})
+                if (q) (void)hipFree(q);
+            w.sites = nullptr;
+            w.list = nullptr;
+            w.dg = w.t = nullptr;
+            return hip_fail(ctx, e, "hipMalloc(site work list)");
+        }
+        w.cap = cap;
+    }
+    if (w.pool_cap < (size_t)n + cap) {
+        if (w.pool) (void)hipFree(w.pool);
+        w.pool = nullptr;
+        w.pool_cap = 0;
+        HIP_TRY(ctx, hipMalloc((void **)&w.pool, sizeof(uint64_t) * ((size_t)n + cap)));
+        w.pool_cap = (size_t)n + cap;
+    }
+    if (w.counts_cap < 4 * (size_t)n) {
+        if (w.counts) (void)hipFree(w.counts);
+        w.counts = nullptr;
+        w.counts_cap = 0;
+        HIP_TRY(ctx, hipMalloc((void **)&w.counts, sizeof(uint64_t) * 4 * (size_t)n));
+        w.counts_cap = 4 * (size_t)n;
+    }
+    if (!w.slab_count) HIP_TRY(ctx, hipMalloc((void **)&w.slab_count, sizeof(uint64_t)));
+    return MSSPE_OK;
+}
+
+// thal of the pairs list[0 .. count) -- (primer, n + site index) into the site pool -- by list index into the work
+// list's dg / t planes: the END screen's chain over an explicit list.  *ovf_count[0] == count (k_site_oligos).
+int score_site_pairs(msspe_ctx *ctx, ChemEntry *ce, bool end1, int n, int k, uint2 *list, uint32_t count)
+{
+    auto &w = ctx->site_work;
+    const long kListCap = ctx->list_cap;
+    PairSinks sinks;
+    std::memset(&sinks, 0, sizeof sinks);
+    sinks.dg = w.dg;
+    sinks.tm = w.t;
+    sinks.row0 = 0;
+    sinks.col0 = n;   // (row - row0) * ncols + (col - col0) = the site index
+    sinks.ncols = 0;
+    GenericDimerArgs g;
+    std::memset(&g, 0, sizeof g);
+    g.pt = ce->d_pt;
+    g.c[0] = ce->c[0];
+    g.c[1] = ce->c[1];
+    g.pool = w.pool;
+    g.k = k;
+    g.k2 = k;
+    g.mode = end1 ? kModeEnd1 : kModeAny;
+    g.sinks = sinks;
+    g.wsS = ctx->wsS;
+    g.wsH = ctx->wsH;
+    g.ws_lanes = kGenericLanes;
+    PairKernelArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.ft = ce->d_ft;
+    a.c = ce->c[0];
+    a.pool = w.pool;
+    a.n = n;
+    a.k = k;
+    a.k2 = k;
+    a.sinks = sinks;
+    a.overflow_cap = (uint32_t)kListCap;
+    a.work_counter = ctx->ovf_count + 7;
+    const bool reg = !ctx->opt.force_generic && k <= pairs_fast_max_k() && ce->fast_ok &&
+                     ce->chem.max_loop >= 2 * k - 4;   // the register-table kernels have no loop-size cut-off
+    const bool wave_ok = !ctx->opt.force_generic && k <= ce->wave_max_k && ctx->opt.wave_kernel;
+    const uint2 *in_list = list;
+    uint2 *out_list = ctx->ovf_list;
+    int in_c = 0, out_c = 1;
+    auto advance = [&]() {
+        in_list = out_list;
+        out_list = out_list == ctx->ovf_list ? ctx->ovf_list2 : ctx->ovf_list;
+        in_c = out_c;
+        out_c = out_c + 1;
+    };
+    HIP_TRY(ctx, hipMemsetAsync(ctx->ovf_count + 1, 0, 7 * sizeof(uint32_t), ctx->stream));
+    if (reg) {
+        a.overflow_list = out_list;
+        a.overflow_count = ctx->ovf_count + out_c;
+        HIP_TRY(ctx, launch_pairs_main_list(a, in_list, ctx->ovf_count + in_c, ctx->stream, end1));
+        advance();
+        a.overflow_list = out_list;
+        a.overflow_count = ctx->ovf_count + out_c;
+        HIP_TRY(ctx, launch_pairs_wide(a, in_list, ctx->ovf_count + in_c, ctx->stream, end1));
+        advance();
+    }
+    if (wave_ok) {
+        a.overflow_list = out_list;
+        a.overflow_count = ctx->ovf_count + out_c;
+        HIP_TRY(ctx, launch_pairs_wave(a, ce->d_st, in_list, ctx->ovf_count + in_c, ctx->stream, end1));
+        advance();
+    }
+    g.list = in_list;
+    g.list_count = ctx->ovf_count + in_c;
+    g.n_work = in_c == 0 ? (long)count : kListCap;
+    HIP_TRY(ctx, launch_dimer_generic(g, ctx->stream, end1));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->ovf_count, 0, 8 * sizeof(uint32_t), ctx->stream));
+    return MSSPE_OK;
+}
+
+}  // namespace
+
+int msspe_background_thal_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, size_t total_len, int k,
+                                     const msspe_mismatch_opt *mm, const uint64_t *words, int n,
+                                     const msspe_chem *chem, int mode, float tm_threshold, uint64_t *sites_out,
+                                     uint64_t *stable_out, msspe_scored_site *d_sites, uint64_t capacity,
+                                     uint64_t *d_count)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!d_packed || !mm || !sites_out || !stable_out || !chem || n < 0 || (n && !words) || (d_sites && !d_count))
+        return fail(ctx, MSSPE_ERR_ARG, "null argument");
+    if (mode != 1 && mode != 2) return fail(ctx, MSSPE_ERR_ARG, "background_thal: mode must be 1 (ANY) or 2 (END1)");
+    if (k < 2 || k > 31) return fail(ctx, MSSPE_ERR_K, "background_thal: unsupported k (need 2 <= k <= 31)");
+    std::string err;
+    int rc = BackgroundSites::check(total_len, k, mm->max_mismatches, mm->exact_3p, words, n, err);
+    if (rc) return fail(ctx, rc, err);
+    const size_t cap = (size_t)1 << ctx->opt.site_list_cap_log2;
+    if ((uint64_t)n + cap >= (1ull << 31)) return fail(ctx, MSSPE_ERR_ARG, "background_thal: too many primers");
+    std::fill(sites_out, sites_out + 2 * (size_t)n, (uint64_t)0);
+    std::fill(stable_out, stable_out + 2 * (size_t)n, (uint64_t)0);
+    auto &w = ctx->site_work;
+    w.slabs = w.redone = 0;
+    if (n == 0 || total_len < (size_t)k) return MSSPE_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const bool end1 = mode == 2;
+    ChemEntry *ce = nullptr;
+    if ((rc = chem_entry(ctx, *chem, tm_threshold, &ce, end1 ? kCutEndT : kCutAnyT))) return rc;
+    const double cut = ce->c[0].g_cut;
+    if ((rc = ensure_workspace(ctx, (size_t)k * (size_t)k))) return rc;
+    if ((rc = ensure_overflow(ctx, (long)cap))) return rc;
+    if ((rc = ensure_site_work(ctx, cap, n))) return rc;
+    if ((rc = ctx->background.prepare(k, words, n, ctx->stream, err))) return fail(ctx, rc, err);
+    HIP_TRY(ctx, hipMemcpyAsync(w.pool, words, sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(w.counts, 0, sizeof(uint64_t) * 4 * (size_t)n, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->ovf_count, 0, 8 * sizeof(uint32_t), ctx->stream));
+
+    // Slabs (runs [r0, r1) x primers [p0, p1)), the whole stream first: a slab whose sites do not fit the work list
+    // is split -- into as many parts as its count says, by runs while it has several, then by primers -- and its
+    // parts are listed again; only a slab that fitted is scored and counted.
+    struct Slab { uint32_t r0, r1; int p0, p1; };
+    std::vector<Slab> todo{{0u, BackgroundSites::n_runs(total_len, k), 0, n}};
+    while (!todo.empty()) {
+        const Slab s = todo.back();
+        todo.pop_back();
+        HIP_TRY(ctx, hipMemsetAsync(w.slab_count, 0, sizeof(uint64_t), ctx->stream));
+        if ((rc = ctx->background.list_slab(d_packed, total_len, k, mm->max_mismatches, mm->exact_3p, s.p0, s.p1,
+                                            s.r0, s.r1, w.sites, cap, w.slab_count, ctx->n_cu, ctx->stream, err)))
+            return fail(ctx, rc, err);
+        uint64_t count = 0;
+        HIP_TRY(ctx, hipMemcpyAsync(&count, w.slab_count, sizeof count, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (count > cap) {
+            ++w.redone;
+            const uint64_t runs = s.r1 - s.r0, prim = (uint64_t)(s.p1 - s.p0);
+            const uint64_t want = (2 * count + cap - 1) / cap;   // parts that would be half full at this density
+            if (runs > 1) {
+                const uint64_t parts = std::min(runs, want);
+                for (uint64_t q = 0; q < parts; ++q)
+                    todo.push_back({s.r0 + (uint32_t)(runs * q / parts), s.r0 + (uint32_t)(runs * (q + 1) / parts),
+                                    s.p0, s.p1});
+            } else if (prim > 1) {
+                const uint64_t parts = std::min(prim, want);
+                for (uint64_t q = 0; q < parts; ++q)
+                    todo.push_back({s.r0, s.r1, s.p0 + (int)(prim * q / parts), s.p0 + (int)(prim * (q + 1) / parts)});
+            } else {
+                return fail(ctx, MSSPE_ERR_DEVICE, "background_thal: one run against one primer overran the work list");
+            }
+            continue;
+        }
+        if (!count) continue;
+        ++w.slabs;
+        // the hand-over lists may be shorter than the work list (a fixed list_cap_log2, a card short of memory)
+        const uint32_t step = (uint32_t)std::min<uint64_t>(count, (uint64_t)ctx->list_cap);
+        for (uint32_t c0 = 0; c0 < (uint32_t)count; c0 += step) {
+            const uint32_t cnt = std::min(step, (uint32_t)count - c0);
+            HIP_TRY(ctx, launch_site_oligos(d_packed, total_len, k, w.sites, c0, cnt, n, w.pool, w.list + c0,
+                                            ctx->ovf_count, ctx->stream));
+            if ((rc = score_site_pairs(ctx, ce, end1, n, k, w.list + c0, cnt))) return rc;
+        }
+        HIP_TRY(ctx, launch_site_fold(w.sites, (uint32_t)count, w.dg, w.t, cut, n, w.counts, d_sites, capacity,
+                                      d_sites ? d_count : nullptr, ctx->stream));
+    }
+    std::vector<uint64_t> host(4 * (size_t)n);
+    HIP_TRY(ctx, hipMemcpyAsync(host.data(), w.counts, sizeof(uint64_t) * host.size(), hipMemcpyDeviceToHost,
+                                ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    std::copy(host.begin(), host.begin() + 2 * (size_t)n, sites_out);
+    std::copy(host.begin() + 2 * (size_t)n, host.end(), stable_out);
+    return MSSPE_OK;
+}
+
+int msspe_background_thal(msspe_ctx *ctx, const char *const *records, const size_t *record_bytes, int n_records,
+                          int k, const msspe_mismatch_opt *mm, const uint64_t *words, int n, const msspe_chem *chem,
+                          int mode, float tm_threshold, uint64_t *sites_out, uint64_t *stable_out,
+                          msspe_scored_site *sites, uint64_t capacity, uint64_t *count_out,
+                          uint64_t *record_start_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!mm || !sites_out || !stable_out || !chem || n < 0 || (n && !words) || (sites && !count_out))
+        return fail(ctx, MSSPE_ERR_ARG, "null argument");
+    if (count_out) *count_out = 0;
+    void *d = nullptr;
+    size_t L = 0;
+    int rc = msspe_device_put_stream_packed(ctx, records, record_bytes, n_records, &d, &L, record_start_out);
+    if (rc) return rc;
+    msspe_scored_site *d_sites = nullptr;   // the list and, behind it, its count
+    uint64_t *d_count = nullptr;
+    hipError_t e = hipSuccess;
+    if (sites) {
+        const size_t list_bytes = sizeof(msspe_scored_site) * (size_t)capacity;
+        e = hipMalloc((void **)&d_sites, list_bytes + sizeof(uint64_t));
+        if (e == hipSuccess) {
+            d_count = (uint64_t *)((char *)d_sites + list_bytes);
+            e = hipMemsetAsync(d_count, 0, sizeof(uint64_t), ctx->stream);
+        }
+    }
+    if (e == hipSuccess) {
+        rc = msspe_background_thal_packed_dev(ctx, (const uint64_t *)d, L, k, mm, words, n, chem, mode, tm_threshold,
+                                              sites_out, stable_out, d_sites, capacity, d_count);
+        if (!rc && sites) {
+            uint64_t count = 0;
+            e = hipMemcpyAsync(&count, d_count, sizeof count, hipMemcpyDeviceToHost, ctx->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+            const uint64_t kept = std::min(count, capacity);
+            if (e == hipSuccess && kept)
+                e = hipMemcpy(sites, d_sites, sizeof(msspe_scored_site) * kept, hipMemcpyDeviceToHost);
+            if (e == hipSuccess) {
+                std::sort(sites, sites + kept, [](const msspe_scored_site &a, const msspe_scored_site &b) {
+                    if (a.primer != b.primer) return a.primer < b.primer;
+                    if (a.strand != b.strand) return a.strand < b.strand;
+                    return a.pos < b.pos;
+                });
+                *count_out = count;
+                if (count > capacity) rc = fail(ctx, MSSPE_ERR_CAPACITY, "site list capacity too small");
+            }
+        }
+    }
+    if (d_sites) (void)hipFree(d_sites);
+    (void)msspe_device_free(ctx, d);
+    if (e != hipSuccess) return hip_fail(ctx, e, "msspe_background_thal");
     return rc;
 }
 

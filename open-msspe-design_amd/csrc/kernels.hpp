@@ -114,9 +114,9 @@ struct PairKernelArgs {
 // end1 (here and in launch_pairs_wide / launch_pairs_wave): the END screen's instantiation, as launch_dimer_generic.
 hipError_t launch_pairs_fast(const PairKernelArgs &a, hipStream_t stream, bool end1 = false);
 // The main table over an explicit pair list (what the integer stage handed on); pairs that do not
-// fit are appended to a.overflow_list.
+// fit are appended to a.overflow_list.  end1: the END1 instantiation (the site scores of msspe_background_thal*).
 hipError_t launch_pairs_main_list(const PairKernelArgs &a, const uint2 *in_list,
-                                  const uint32_t *in_count, hipStream_t stream);
+                                  const uint32_t *in_count, hipStream_t stream, bool end1 = false);
 // Wide instantiation over an explicit pair list (the overflow list of launch_pairs_fast); pairs
 // that still do not fit are appended to a.overflow_list.
 hipError_t launch_pairs_wide(const PairKernelArgs &a, const uint2 *in_list,

@@ -763,10 +763,11 @@ FastArgs list_args(const PairKernelArgs &a, const uint2 *in_list, const uint32_t
 
 // The main table (56 slots) over an explicit pair list: finishes what the integer stage handed on.
 hipError_t launch_pairs_main_list(const PairKernelArgs &a, const uint2 *in_list,
-                                  const uint32_t *in_count, hipStream_t stream)
+                                  const uint32_t *in_count, hipStream_t stream, bool end1)
 {
     const FastArgs f = list_args(a, in_list, in_count);
-    hipLaunchKernelGGL((k_pairs_list<kNregMain, kNextMain, 256>), dim3(256 * 2), dim3(256), 0, stream, f);
+    if (end1) hipLaunchKernelGGL((k_pairs_list_end<kNregMain, kNextMain, 256>), dim3(256 * 2), dim3(256), 0, stream, f);
+    else hipLaunchKernelGGL((k_pairs_list<kNregMain, kNextMain, 256>), dim3(256 * 2), dim3(256), 0, stream, f);
     return hipGetLastError();
 }
 

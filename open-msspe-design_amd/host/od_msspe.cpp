@@ -77,6 +77,8 @@ const OptSpec kOpts[] = {
     {"--background-mismatches", "BACKGROUND_MISMATCHES", OptSpec::OptInt, OFF(background_mismatches)},
     {"--background-3p-exact", "BACKGROUND_3P_EXACT", OptSpec::OptInt, OFF(background_3p_exact)},
     {"--max-background-sites", "MAX_BACKGROUND_SITES", OptSpec::OptInt, OFF(max_background_sites)},
+    {"--background-tm", "BACKGROUND_TM", OptSpec::Str, OFF(background_tm_text)},
+    {"--background-thal", "BACKGROUND_THAL", OptSpec::Str, OFF(background_thal)},
 };
 #undef OFF
 
@@ -181,7 +183,22 @@ Args Args::parse(int argc, const char *const *argv)
                                   std::make_pair("--max-background-sites", a.max_background_sites)})
             if (given.second >= 0)
                 throw UsageError(std::string("error: '") + given.first + "' needs '--background <FASTA>'");
+        for (const auto &given : {std::make_pair("--background-tm", &a.background_tm_text),
+                                  std::make_pair("--background-thal", &a.background_thal)})
+            if (!given.second->empty())
+                throw UsageError(std::string("error: '") + given.first + "' needs '--background <FASTA>'");
     }
+    if (!a.background_tm_text.empty()) {
+        char *end = nullptr;
+        a.background_tm = std::strtof(a.background_tm_text.c_str(), &end);
+        if (*end || std::isnan(a.background_tm))
+            throw UsageError("error: invalid value '" + a.background_tm_text + "' for '--background-tm'");
+        a.background_scored = true;
+    }
+    if (a.background_thal.empty()) a.background_thal = "any";
+    if (a.background_thal != "any" && a.background_thal != "end1")
+        throw UsageError("error: invalid value '" + a.background_thal +
+                         "' for '--background-thal <...>'\n  [possible values: any, end1]");
     if (a.background_mismatches > a.kmer_size)
         throw UsageError("error: '--background-mismatches " + std::to_string(a.background_mismatches) +
                          "' is larger than '--kmer-size " + std::to_string(a.kmer_size) + "'");
@@ -955,6 +972,60 @@ std::vector<std::pair<uint64_t, uint64_t>> DeviceBackground::sites(const std::ve
     return out;
 }
 
+std::vector<std::pair<uint64_t, uint64_t>> DeviceBackground::scored(
+    const std::vector<std::string> &words, int max_mismatches, int exact_3p, const msspe_chem &chem, int mode,
+    float tm_threshold, std::vector<std::pair<uint64_t, uint64_t>> &stable_out) const
+{
+    std::vector<std::pair<uint64_t, uint64_t>> out(words.size());
+    stable_out.assign(words.size(), {0, 0});
+    std::map<size_t, std::vector<size_t>> by_length;   // a panel of mixed lengths: one length class per call
+    for (size_t i = 0; i < words.size(); ++i) by_length[words[i].size()].push_back(i);
+    for (const auto &cls : by_length) {
+        const int k = (int)cls.first, n = (int)cls.second.size();
+        std::string flat;
+        for (const size_t i : cls.second) flat += words[i];
+        std::vector<uint64_t> packed((size_t)n), counts(2 * (size_t)n), stable(2 * (size_t)n);
+        int rc = msspe_pack_oligos(flat.data(), n, k, packed.data());
+        if (rc) eng_.fail(rc);
+        const msspe_mismatch_opt mm{std::min(max_mismatches, k), std::min(exact_3p, k)};
+        rc = msspe_background_thal_packed_dev(eng_.ctx(), static_cast<const uint64_t *>(dev_), len_, k, &mm,
+                                              packed.data(), n, &chem, mode, tm_threshold, counts.data(),
+                                              stable.data(), nullptr, 0, nullptr);
+        if (rc) eng_.fail(rc);
+        for (int j = 0; j < n; ++j) {
+            out[cls.second[(size_t)j]] = {counts[2 * (size_t)j], counts[2 * (size_t)j + 1]};
+            stable_out[cls.second[(size_t)j]] = {stable[2 * (size_t)j], stable[2 * (size_t)j + 1]};
+        }
+    }
+    return out;
+}
+
+std::string background_report_scored(const std::vector<std::string> &names,
+                                     const std::vector<std::pair<uint64_t, uint64_t>> &sites,
+                                     const std::vector<std::pair<uint64_t, uint64_t>> &stable, int max_mismatches,
+                                     int exact_3p, int mode, float tm_threshold)
+{
+    char thr[64];
+    std::snprintf(thr, sizeof thr, "%.2f", (double)tm_threshold);
+    std::string out = "\nBackground sites (up to " + std::to_string(max_mismatches) + " mismatches, last " +
+                      std::to_string(exact_3p) + " bases exact; stable: thal " + (mode == 2 ? "END1" : "ANY") +
+                      " t >= " + thr + " C):\n";
+    uint64_t plus = 0, minus = 0, s_plus = 0, s_minus = 0;
+    for (size_t i = 0; i < names.size(); ++i) {
+        out += "  " + names[i] + ": plus " + std::to_string(sites[i].first) + ", minus " +
+               std::to_string(sites[i].second) + ", stable plus " + std::to_string(stable[i].first) + ", minus " +
+               std::to_string(stable[i].second) + "\n";
+        plus += sites[i].first;
+        minus += sites[i].second;
+        s_plus += stable[i].first;
+        s_minus += stable[i].second;
+    }
+    out += "  Total: " + std::to_string(names.size()) + " primers, plus " + std::to_string(plus) + ", minus " +
+           std::to_string(minus) + ", stable plus " + std::to_string(s_plus) + ", minus " + std::to_string(s_minus) +
+           "\n";
+    return out;
+}
+
 std::string background_report(const std::vector<std::string> &names,
                               const std::vector<std::pair<uint64_t, uint64_t>> &sites, int max_mismatches,
                               int exact_3p)
@@ -1140,6 +1211,9 @@ int run(const Args &args, std::string &stdout_text)
     timer.lap("stage B + filter");
     // --background: uploaded once; candidates with too many off-target sites go before the cross-dimer screen, so the
     // vertex cover never spends a removal on them (the panel is reported below but never dropped)
+    const NtthalOptions opts{args.mv_conc, args.dv_conc, args.dntp_conc, args.dna_conc,
+                             args.annealing_temp, args.delta_g_threshold};
+    const int bg_mode = args.background_thal == "end1" ? 2 : 1;
     std::unique_ptr<DeviceBackground> background;
     if (!args.background.empty()) {
         const auto bg_records = read_records(args.background);
@@ -1149,7 +1223,13 @@ int run(const Args &args, std::string &stdout_text)
             for (auto *list : {&prim_f, &prim_r}) {
                 std::vector<std::string> words;
                 for (const auto &s : *list) words.push_back(s.word);
-                const auto sites = background->sites(words, args.background_mismatches, args.background_3p_exact);
+                // with --background-tm the limit applies to the sites that would hold the primer
+                std::vector<std::pair<uint64_t, uint64_t>> sites;
+                if (args.background_scored)
+                    (void)background->scored(words, args.background_mismatches, args.background_3p_exact,
+                                             ntthal_chem(opts), bg_mode, args.background_tm, sites);
+                else
+                    sites = background->sites(words, args.background_mismatches, args.background_3p_exact);
                 size_t kept = 0;
                 for (size_t i = 0; i < list->size(); ++i)
                     if (sites[i].first + sites[i].second <= (uint64_t)args.max_background_sites)
@@ -1158,8 +1238,6 @@ int run(const Args &args, std::string &stdout_text)
             }
         timer.lap("background upload + screen");
     }
-    const NtthalOptions opts{args.mv_conc, args.dv_conc, args.dntp_conc, args.dna_conc,
-                             args.annealing_temp, args.delta_g_threshold};
     if (cfg.check_cross_dimers && !cfg.keep_all && (!panel_f.empty() || !panel_r.empty())) {
         // a new primer that dimerises with the panel is dropped before the vertex cover (the panel stays whole)
         std::vector<std::string> cands, all_panel(panel_f);
@@ -1204,9 +1282,16 @@ int run(const Args &args, std::string &stdout_text)
                 words.push_back(i < panel_list->size() ? (*panel_list)[i] : good[i - panel_list->size()].word);
             }
         }
-        stdout_text += background_report(names, background->sites(words, args.background_mismatches,
-                                                                  args.background_3p_exact),
-                                         args.background_mismatches, args.background_3p_exact);
+        if (args.background_scored) {
+            std::vector<std::pair<uint64_t, uint64_t>> stable;
+            const auto sites = background->scored(words, args.background_mismatches, args.background_3p_exact,
+                                                  ntthal_chem(opts), bg_mode, args.background_tm, stable);
+            stdout_text += background_report_scored(names, sites, stable, args.background_mismatches,
+                                                    args.background_3p_exact, bg_mode, args.background_tm);
+        } else
+            stdout_text += background_report(names, background->sites(words, args.background_mismatches,
+                                                                      args.background_3p_exact),
+                                             args.background_mismatches, args.background_3p_exact);
     }
     std::ofstream out(args.output, std::ios::binary);
     if (!out) throw std::runtime_error("cannot write " + args.output);

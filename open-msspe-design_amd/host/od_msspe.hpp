@@ -65,6 +65,13 @@ struct Args {
     // cross-dimer screen.  Empty: nothing changes.  -1 = not given (resolved to 2 / 3 / no limit by parse()).
     std::string background;
     int background_mismatches = -1, background_3p_exact = -1, max_background_sites = -1;
+    // --background-tm C: every site is scored with thal against the strand the primer would anneal to
+    // (msspe_background_thal, --background-thal any | end1, the cross-dimer screen's chemistry); a site is stable iff
+    // round_fixed_f32(max(0, t), 2) >= C, the report adds the stable counts and max_background_sites compares those.
+    // Empty text: not given, nothing changes.
+    std::string background_tm_text, background_thal;
+    float background_tm = 0.0f;
+    bool background_scored = false;
     bool stddev_population = false;  // crate std-dev 0.1.0's divisor is unpinned
     static Args parse(int argc, const char *const *argv);   // throws UsageError
     static std::string usage();
@@ -220,6 +227,12 @@ public:
     // (plus, minus) sites of each word, one msspe_background_sites_packed_dev call per word length
     std::vector<std::pair<uint64_t, uint64_t>> sites(const std::vector<std::string> &words, int max_mismatches,
                                                      int exact_3p) const;
+    // the same with the thal score of every site (one msspe_background_thal_packed_dev call per word length):
+    // returns the (plus, minus) sites, stable_out the (plus, minus) stable ones
+    std::vector<std::pair<uint64_t, uint64_t>> scored(const std::vector<std::string> &words, int max_mismatches,
+                                                      int exact_3p, const msspe_chem &chem, int mode,
+                                                      float tm_threshold,
+                                                      std::vector<std::pair<uint64_t, uint64_t>> &stable_out) const;
 
 private:
     Engine &eng_;
@@ -231,6 +244,12 @@ private:
 std::string background_report(const std::vector<std::string> &names,
                               const std::vector<std::pair<uint64_t, uint64_t>> &sites, int max_mismatches,
                               int exact_3p);
+// The block with --background-tm: the heading names the rule ("; stable: thal ANY t >= 30.00 C"), every line and the
+// totals add "stable plus S, minus T"
+std::string background_report_scored(const std::vector<std::string> &names,
+                                     const std::vector<std::pair<uint64_t, uint64_t>> &sites,
+                                     const std::vector<std::pair<uint64_t, uint64_t>> &stable, int max_mismatches,
+                                     int exact_3p, int mode, float tm_threshold);
 // main.rs:834-858
 // first_f / first_r: the number of the first row of each direction (a panel's extension continues its numbering)
 std::string primers_csv(const std::vector<KmerStat> &fwd, const std::vector<KmerStat> &rev, size_t first_f = 0,

@@ -33,6 +33,7 @@ EXPORTS = [
     "msspe_segment_coverage_packed_dev",
     "msspe_segment_coverage_mm", "msspe_segment_coverage_mm_dev", "msspe_segment_coverage_mm_packed_dev",
     "msspe_device_put_stream_packed", "msspe_background_sites_packed_dev", "msspe_background_sites",
+    "msspe_background_thal_packed_dev", "msspe_background_thal",
     "msspe_round_fixed_f32", "msspe_g_cut",
     "msspe_group_create", "msspe_group_destroy", "msspe_group_last_error", "msspe_group_size",
     "msspe_group_transport", "msspe_group_transport_reason", "msspe_group_rccl_available", "msspe_group_member", "msspe_group_set_option", "msspe_group_rows",
@@ -69,6 +70,12 @@ class KmerOpt(C.Structure):
 
 # msspe_site: one off-target site of the list msspe_background_sites* makes
 SITE_DTYPE = np.dtype([("primer", np.uint32), ("pos", np.uint32), ("mismatches", np.uint16), ("strand", np.uint16)])
+
+
+# msspe_scored_site: one off-target site with its thal score (msspe_background_thal*); dg and t are raw
+SCORED_SITE_DTYPE = np.dtype([("primer", np.uint32), ("pos", np.uint32), ("mismatches", np.uint16),
+                              ("strand", np.uint16), ("stable", np.uint32), ("dg", np.float64), ("t", np.float64)])
+THAL_MODES = {"any": 1, "end1": 2}
 
 
 class MismatchOpt(C.Structure):
@@ -204,6 +211,11 @@ def load_library() -> C.CDLL:
     L.msspe_background_sites.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int,
                                          C.POINTER(MismatchOpt), u64p, C.c_int, vp, vp, C.c_uint64,
                                          C.POINTER(C.c_uint64), vp]
+    L.msspe_background_thal_packed_dev.argtypes = [vp, vp, C.c_size_t, C.c_int, C.POINTER(MismatchOpt), u64p, C.c_int,
+                                                   C.POINTER(Chem), C.c_int, C.c_float, vp, vp, vp, C.c_uint64, vp]
+    L.msspe_background_thal.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int,
+                                        C.POINTER(MismatchOpt), u64p, C.c_int, C.POINTER(Chem), C.c_int, C.c_float,
+                                        vp, vp, vp, C.c_uint64, C.POINTER(C.c_uint64), vp]
     L.msspe_round_g_f32.restype = C.c_float
     L.msspe_round_g_f32.argtypes = [C.c_double]
     L.msspe_round_fixed_f32.restype = C.c_float
@@ -725,6 +737,55 @@ class Engine:
         if sites is None:
             return counts, starts
         return counts, starts, sites[:count.value]
+
+    @staticmethod
+    def _thal_mode(mode) -> int:
+        return THAL_MODES[mode] if isinstance(mode, str) else int(mode)
+
+    def background_thal_packed(self, d_packed: int, total_len: int, primers, max_mismatches: int, exact_3p: int,
+                               chem: Chem, tm_threshold: float, mode="any", k: int | None = None, d_sites: int = 0,
+                               capacity: int = 0, d_count: int = 0):
+        """Sites of each primer on a resident stream, each scored with thal (msspe_background_thal_packed_dev): the
+        primer against the strand it would anneal to, mode "any" (1) or "end1" (2); a site is stable iff
+        round_fixed_f32(max(0, t), 2) >= tm_threshold.  Returns (counts, stable), uint64 (n, 2) each: [:, 0] plus
+        strand, [:, 1] minus.  d_sites / capacity / d_count: raw device addresses of a SCORED_SITE_DTYPE list and its
+        uint64 count (added to, the caller zeroes it); 0 = no list."""
+        w, k = _words_k(primers, k)
+        counts = np.zeros((len(w), 2), dtype=np.uint64)
+        stable = np.zeros((len(w), 2), dtype=np.uint64)
+        mm = MismatchOpt(max_mismatches, exact_3p)
+        self._check(self.L.msspe_background_thal_packed_dev(
+            self.ptr, C.c_void_p(d_packed), total_len, k, C.byref(mm), w.ctypes.data, len(w), C.byref(chem),
+            self._thal_mode(mode), tm_threshold, counts.ctypes.data, stable.ctypes.data, C.c_void_p(d_sites), capacity,
+            C.c_void_p(d_count)))
+        return counts, stable
+
+    def background_thal(self, records, primers, max_mismatches: int, exact_3p: int, chem: Chem, tm_threshold: float,
+                        mode="any", k: int | None = None, capacity: int | None = None):
+        """Host form (msspe_background_thal): returns (counts, stable, starts), or with a list capacity
+        (counts, stable, starts, sites) -- sites a SCORED_SITE_DTYPE array sorted by (primer, strand, pos), one record
+        per site, stable or not.  A capacity below the number of sites raises MsspeError (MSSPE_ERR_CAPACITY) carrying
+        .count, .counts, .stable and the truncated .sites."""
+        _recs, ptrs, lens, n = self._records(records)
+        w, k = _words_k(primers, k)
+        counts = np.zeros((len(w), 2), dtype=np.uint64)
+        stable = np.zeros((len(w), 2), dtype=np.uint64)
+        starts = np.zeros(n, dtype=np.uint64)
+        mm = MismatchOpt(max_mismatches, exact_3p)
+        sites = np.zeros(max(capacity, 1), dtype=SCORED_SITE_DTYPE) if capacity is not None else None
+        count = C.c_uint64(0)
+        rc = self.L.msspe_background_thal(
+            self.ptr, ptrs, lens, n, k, C.byref(mm), w.ctypes.data, len(w), C.byref(chem), self._thal_mode(mode),
+            tm_threshold, counts.ctypes.data, stable.ctypes.data, sites.ctypes.data if sites is not None else None,
+            capacity or 0, C.byref(count), starts.ctypes.data)
+        if rc:
+            err = MsspeError(rc, self.L.msspe_last_error(self.ptr).decode())
+            err.count, err.counts, err.stable = int(count.value), counts, stable
+            err.sites = sites[:min(int(count.value), capacity or 0)] if sites is not None else None
+            raise err
+        if sites is None:
+            return counts, stable, starts
+        return counts, stable, starts, sites[:count.value]
 
     def pair_stage_samples(self):
         """[(row, col, reason bits)] for up to 1024 pairs the integer stage handed on."""
