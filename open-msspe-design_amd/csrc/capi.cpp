@@ -321,6 +321,231 @@ __global__ void k_accumulate_overflow(const uint32_t *count, uint64_t *total, ui
     }
 }
 
+// A device allocation that is freed when it goes out of scope (move-only): the host-buffer entry points return
+// from any failed step without a cleanup list.
+template <class T>
+struct DevBuf {
+    T *p = nullptr;
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p(o.p) { o.p = nullptr; }
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf()
+    {
+        if (p) (void)hipFree(p);
+    }
+    hipError_t alloc(size_t count) { return hipMalloc((void **)&p, sizeof(T) * count); }
+    operator T *() const { return p; }
+};
+
+// "Pack one pool or fail with the K / ACGT message" and "pack A and B back to back, A first" of the ASCII wrappers.
+int pack_pool(msspe_ctx *ctx, const char *ascii, int n, int k, std::vector<uint64_t> &packed)
+{
+    packed.resize((size_t)n);
+    const int rc = msspe_pack_oligos(ascii, n, k, packed.data());
+    if (rc) return fail(ctx, rc, rc == MSSPE_ERR_K ? "oligo length must be 1..32"
+                                                   : "pool holds characters other than ACGT");
+    return MSSPE_OK;
+}
+
+int pack_ab(msspe_ctx *ctx, const char *a_ascii, int n_a, int k_a, const char *b_ascii, int n_b, int k_b,
+            std::vector<uint64_t> &packed)
+{
+    if (k_a < 2 || k_a > 32 || k_b < 2 || k_b > 32) return fail(ctx, MSSPE_ERR_K, "oligo length must be 2..32");
+    if ((long)n_a + (long)n_b > (long)INT32_MAX) return fail(ctx, MSSPE_ERR_ARG, "pools too large");
+    packed.resize((size_t)n_a + (size_t)n_b);
+    if (msspe_pack_oligos(a_ascii ? a_ascii : "", n_a, k_a, packed.data()) ||
+        msspe_pack_oligos(b_ascii ? b_ascii : "", n_b, k_b, packed.data() + n_a))
+        return fail(ctx, MSSPE_ERR_ARG, "pool holds characters other than ACGT");
+    return MSSPE_OK;
+}
+
+// One block of a screen: rows [row0, row1) of k bases against columns [col0, col1) of k2 bases (k2 != k: the
+// rectangular chain) of one pool of n oligos, and where the results go.  Filled once, where a public entry point
+// receives its arguments; the host-buffer wrappers receive one whose pool is still to be uploaded and whose sinks
+// are host pointers, and mirror it on the device.
+struct ScreenBlock {
+    const uint64_t *pool;
+    int n, k, k2;
+    int row0, row1, col0, col1;
+    PairSinks sinks;   // row0 / col0 / ncols / words follow the block's ranges
+};
+
+PairSinks plane_sinks(uint32_t *row_conflicts, uint64_t *bitmap, double *dg, double *tm)
+{
+    PairSinks s;
+    std::memset(&s, 0, sizeof s);
+    s.row_conflicts = row_conflicts;
+    s.bitmap = bitmap;
+    s.dg = dg;
+    s.tm = tm;
+    return s;
+}
+
+// edges: msspe_edge_dev / msspe_end_edge_dev records (the layout of EdgeRecord)
+PairSinks edge_sinks(uint32_t *row_conflicts, void *edges, uint64_t *count, uint64_t capacity)
+{
+    static_assert(sizeof(msspe_edge_dev) == sizeof(EdgeRecord) && sizeof(msspe_end_edge_dev) == sizeof(EdgeRecord),
+                  "edge record layouts differ");
+    PairSinks s = plane_sinks(row_conflicts, nullptr, nullptr, nullptr);
+    s.edges = static_cast<EdgeRecord *>(edges);
+    s.edge_count = reinterpret_cast<unsigned long long *>(count);
+    s.edge_cap = capacity;
+    return s;
+}
+
+ScreenBlock screen_block(const uint64_t *pool, int n, int k, int k2, int row0, int row1, int col0, int col1,
+                         const PairSinks &sinks)
+{
+    ScreenBlock b{pool, n, k, k2, row0, row1, col0, col1, sinks};
+    b.sinks.row0 = row0;
+    b.sinks.col0 = col0;
+    b.sinks.ncols = col1 - col0;
+    b.sinks.words = (b.sinks.ncols + 63) / 64;
+    return b;
+}
+
+// May the register-table kernels (thal_pairs.hip: no loop-size cut-off) take oligos of k bases under this chemistry?
+bool reg_tables_ok(const msspe_ctx *ctx, const ChemEntry *ce, int k)
+{
+    return !ctx->opt.force_generic && k <= pairs_fast_max_k() && ce->fast_ok && ce->chem.max_loop >= 2 * k - 4;
+}
+
+// May the wave kernel (f64, one wave per pair) take pairs whose longer oligo has kmax bases?
+bool wave_ok(const msspe_ctx *ctx, const ChemEntry *ce, int kmax)
+{
+    return !ctx->opt.force_generic && kmax <= ce->wave_max_k && ctx->opt.wave_kernel;
+}
+
+// The pair kernels' arguments for the block in list mode; run_chain's first-stage launches put their band of rows,
+// the sorted columns and list 0 on top.
+PairKernelArgs pair_args(const msspe_ctx *ctx, const ChemEntry *ce, const ScreenBlock &b)
+{
+    PairKernelArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.ft = ce->d_ft;
+    a.c = ce->c[0];
+    a.pool = b.pool;
+    a.n = b.n;
+    a.k = b.k;
+    a.k2 = b.k2;
+    a.row0 = b.row0;
+    a.row1 = b.row1;
+    a.col1 = b.col1 - b.col0;
+    a.sinks = b.sinks;
+    a.work_counter = ctx->ovf_count + 7;   // the last of the eight stage counters
+    return a;
+}
+
+// The dense kernel's arguments for the block; the caller sets its work (list / n_work, self_mode, detail).
+GenericDimerArgs dimer_args(const msspe_ctx *ctx, const ChemEntry *ce, const ScreenBlock &b, int mode)
+{
+    GenericDimerArgs g;
+    std::memset(&g, 0, sizeof g);
+    g.pt = ce->d_pt;
+    g.c[0] = ce->c[0];
+    g.c[1] = ce->c[1];
+    g.pool = b.pool;
+    g.k = b.k;
+    g.k2 = b.k2;
+    g.mode = mode;
+    g.sinks = b.sinks;
+    g.wsS = ctx->wsS;
+    g.wsH = ctx->wsH;
+    g.ws_lanes = kGenericLanes;
+    return g;
+}
+
+// The stages that may stand behind a first stage, each over the hand-over list the stage before it wrote.  A route
+// (StageList) names them in the order they run and ends with Dense, which takes whatever is left.  The order of a
+// route is written where the route is chosen -- cross_dimer_impl (ANY), cross_dimer_end_impl (END),
+// score_site_pairs (an explicit list) -- and nowhere else; include/msspe_hip.h ("hand_over_list_<q>") documents
+// the result: the stage at position q of a route reads list q.
+enum class ListStage {
+    IntList,     // the integer kernel again, 64 slots, lanes sorted by table size: pairs that only left their wave
+                 // because of their size (marked entries -- exact ties -- pass through to the f64 stages)
+    SplitList,   // tables beyond the integer list stage's 63 stored cells: two lanes per pair, still exact integers
+    MainList,    // the 56-slot f64 register table: exact ties
+    Wide,        // the 72-slot f64 register table
+    Wave,        // huge tables: f64, one wave per pair, the table in LDS
+    Dense        // last: both-self-complementary pairs, tables beyond the wave kernel's
+};
+
+struct StageList {
+    ListStage at[6];
+    int n = 0;
+    void add(ListStage s) { at[n++] = s; }
+};
+
+// The hand-over lists behind a first stage.  A list stage reads the current list (counter q) and appends what it
+// does not answer to the next (counter q + 1); the first list is the context's ovf_list (what a first stage wrote)
+// or a caller's own, and behind it the context's two buffers ping-pong: a stage's input is consumed when it ends.
+struct ListChain {
+    msspe_ctx *ctx;
+    const ChemEntry *ce;
+    bool end1;             // the END1 instantiations of the f64 stages
+    const uint2 *in_list;
+    uint32_t *in_count;
+    long in_work;          // most entries the current list can hold: first_work on the first list, then the capacity
+    uint2 *out_list;
+    uint32_t *out_count;
+    long cap;              // entries per hand-over list
+
+    ListChain(msspe_ctx *ctx_, const ChemEntry *ce_, bool end1_, const uint2 *first_list, long first_work)
+        : ctx(ctx_), ce(ce_), end1(end1_), in_list(first_list), in_count(ctx_->ovf_count), in_work(first_work),
+          out_list(first_list == ctx_->ovf_list ? ctx_->ovf_list2 : ctx_->ovf_list), out_count(ctx_->ovf_count + 1),
+          cap(ctx_->list_cap)
+    {
+    }
+
+    int stage(ListStage s, PairKernelArgs &a)
+    {
+        a.overflow_list = out_list;
+        a.overflow_count = out_count;
+        a.overflow_cap = (uint32_t)cap;
+        switch (s) {
+        case ListStage::IntList:
+            HIP_TRY(ctx, launch_pairs_int_list(a, ce->d_it, in_list, in_count, ctx->d_reasons, ctx->n_cu, ctx->stream));
+            break;
+        case ListStage::SplitList:
+            HIP_TRY(ctx, launch_pairs_split_list(a, ce->d_st, in_list, in_count, ctx->n_cu, ctx->stream));
+            break;
+        case ListStage::MainList: HIP_TRY(ctx, launch_pairs_main_list(a, in_list, in_count, ctx->stream, end1)); break;
+        case ListStage::Wide: HIP_TRY(ctx, launch_pairs_wide(a, in_list, in_count, ctx->stream, end1)); break;
+        case ListStage::Wave: HIP_TRY(ctx, launch_pairs_wave(a, ce->d_st, in_list, in_count, ctx->stream, end1)); break;
+        case ListStage::Dense: return fail(ctx, MSSPE_ERR_ARG, "the dense kernel ends a route: ListChain::finish");
+        }
+        in_list = out_list;
+        in_count = out_count;
+        in_work = cap;
+        out_list = out_list == ctx->ovf_list ? ctx->ovf_list2 : ctx->ovf_list;
+        ++out_count;
+        return MSSPE_OK;
+    }
+
+    // The dense kernel over the current list; accumulate: the totals of the hand-over statistics and the overrun
+    // check (k_accumulate_overflow); then the eight counters are cleared for the next flush or call.
+    int finish(GenericDimerArgs &g, bool accumulate)
+    {
+        g.list = in_list;
+        g.list_count = in_count;
+        g.n_work = in_work;
+        HIP_TRY(ctx, launch_dimer_generic(g, ctx->stream, end1));
+        if (accumulate)
+            hipLaunchKernelGGL(k_accumulate_overflow, dim3(1), dim3(64), 0, ctx->stream, ctx->ovf_count,
+                               ctx->d_ovf_total, (uint32_t)cap);
+        HIP_TRY(ctx, hipMemsetAsync(ctx->ovf_count, 0, 8 * sizeof(uint32_t), ctx->stream));
+        return MSSPE_OK;
+    }
+
+    int run(const StageList &route, PairKernelArgs &a, GenericDimerArgs &g, bool accumulate)
+    {
+        for (int q = 0; q < route.n && route.at[q] != ListStage::Dense; ++q)
+            if (int rc = stage(route.at[q], a)) return rc;
+        return finish(g, accumulate);
+    }
+};
+
 }  // namespace
 
 namespace msspe {
@@ -605,92 +830,33 @@ void msspe_unpack_oligo(uint64_t packed, int k, char *ascii_out)
     ascii_out[k] = 0;
 }
 
-// k: length of the row oligos, k2: length of the column oligos (k2 != k: the rectangular chain, see below)
-static int cross_dimer_impl(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, int k2, const msspe_chem *chem,
-                            float dg_threshold, int row0, int row1, int col0, int col1,
-                            uint32_t *d_row_conflicts, uint64_t *d_bitmap, double *d_dg, double *d_tm,
-                            EdgeRecord *d_edges, unsigned long long *d_edge_count, unsigned long long edge_cap);
-
-int msspe_cross_dimer_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k,
-                          const msspe_chem *chem, float dg_threshold, int row0, int row1,
-                          int col0, int col1, uint32_t *d_row_conflicts, uint64_t *d_bitmap,
-                          double *d_dg, double *d_tm)
-{
-    return cross_dimer_impl(ctx, d_pool, n, k, k, chem, dg_threshold, row0, row1, col0, col1, d_row_conflicts,
-                            d_bitmap, d_dg, d_tm, nullptr, nullptr, 0);
-}
-
-int msspe_cross_dimer_edges_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const msspe_chem *chem,
-                                float dg_threshold, int row0, int row1, int col0, int col1,
-                                uint32_t *d_row_conflicts, msspe_edge_dev *d_edges, uint64_t capacity,
-                                uint64_t *d_count)
-{
-    if (!ctx) return MSSPE_ERR_ARG;
-    if (!d_count || (capacity && !d_edges)) return fail(ctx, MSSPE_ERR_ARG, "edge list: null count or buffer");
-    static_assert(sizeof(msspe_edge_dev) == sizeof(EdgeRecord), "edge record layouts differ");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipMemsetAsync(d_count, 0, sizeof(uint64_t), ctx->stream));
-    return cross_dimer_impl(ctx, d_pool, n, k, k, chem, dg_threshold, row0, row1, col0, col1, d_row_conflicts,
-                            nullptr, nullptr, nullptr, reinterpret_cast<EdgeRecord *>(d_edges),
-                            reinterpret_cast<unsigned long long *>(d_count), capacity);
-}
-
 // The stages of one screen, chosen by cross_dimer_impl (thal ANY) or cross_dimer_end_impl (thal END1).
 struct ChainRoute {
     bool end1;          // the END screen: END1 instantiations of every stage and the t decision
     bool fast;          // a first stage runs; otherwise the dense kernel takes the whole block
     bool split;         // split-table first stage (ANY only)
-    bool wave_ok;       // the wave kernel may take a hand-over list
     bool wave_matrix;   // the wave kernel is the first stage
-    bool int_stage;     // integer first stage and the integer list stages (ANY only)
-    bool short_chain;   // behind the integer list stage straight to the wave kernel
+    bool int_stage;     // integer (or row-specialised) first stage (ANY only)
+    StageList behind;   // where fast: the list stages behind the first stage, in order
 };
 
 // Runs a routed screen over the block: launch splitting, column sort, the first stage, and the hand-over lists
-// flushed through the stages behind it.
-static int run_chain(msspe_ctx *ctx, ChemEntry *ce, const ChainRoute &route, const uint64_t *d_pool, int n, int k,
-                     int k2, int row0, int row1, int col0, int col1, uint32_t *d_row_conflicts, uint64_t *d_bitmap,
-                     double *d_dg, double *d_tm, EdgeRecord *d_edges, unsigned long long *d_edge_count,
-                     unsigned long long edge_cap)
+// flushed through route.behind (ListChain).
+static int run_chain(msspe_ctx *ctx, ChemEntry *ce, const ChainRoute &route, const ScreenBlock &b)
 {
-    const bool end1 = route.end1, fast = route.fast, split = route.split, wave_ok = route.wave_ok,
-               wave_matrix = route.wave_matrix, int_stage = route.int_stage, short_chain = route.short_chain;
+    const bool end1 = route.end1, split = route.split, wave_matrix = route.wave_matrix, int_stage = route.int_stage;
+    const int k = b.k, k2 = b.k2, row0 = b.row0, row1 = b.row1, col0 = b.col0;
+    const int ncols = b.sinks.ncols, words = b.sinks.words;
     int rc = 0;
     if ((rc = ensure_workspace(ctx, (size_t)k * (size_t)k2))) return rc;
-    if ((rc = ensure_overflow(ctx, (long)(row1 - row0) * (long)(col1 - col0)))) return rc;
+    if ((rc = ensure_overflow(ctx, (long)(row1 - row0) * (long)ncols))) return rc;
     const long kListCap = ctx->list_cap;
 
-    const int ncols = col1 - col0;
-    const int words = (ncols + 63) / 64;
     // the conflict bitmap is produced with atomic ORs: clear the caller's block first
-    if (d_bitmap)
-        HIP_TRY(ctx, hipMemsetAsync(d_bitmap, 0, sizeof(uint64_t) * (size_t)(row1 - row0) * (size_t)words,
+    if (b.sinks.bitmap)
+        HIP_TRY(ctx, hipMemsetAsync(b.sinks.bitmap, 0, sizeof(uint64_t) * (size_t)(row1 - row0) * (size_t)words,
                                     ctx->stream));
-    PairSinks sinks;
-    sinks.row_conflicts = d_row_conflicts;
-    sinks.bitmap = d_bitmap;
-    sinks.dg = d_dg;
-    sinks.tm = d_tm;
-    sinks.row0 = row0;
-    sinks.col0 = col0;
-    sinks.ncols = ncols;
-    sinks.words = words;
-    sinks.edges = d_edges;
-    sinks.edge_count = d_edge_count;
-    sinks.edge_cap = edge_cap;
-    GenericDimerArgs g;
-    std::memset(&g, 0, sizeof g);
-    g.pt = ce->d_pt;
-    g.c[0] = ce->c[0];
-    g.c[1] = ce->c[1];
-    g.pool = d_pool;
-    g.k = k;
-    g.k2 = k2;
-    g.mode = end1 ? kModeEnd1 : kModeAny;
-    g.sinks = sinks;
-    g.wsS = ctx->wsS;
-    g.wsH = ctx->wsH;
-    g.ws_lanes = kGenericLanes;
+    GenericDimerArgs g = dimer_args(ctx, ce, b, end1 ? kModeEnd1 : kModeAny);
     // A launch covers at most kChunkPairs pairs, and never more than one hand-over list holds (a fixed
     // list_cap_log2 below 29, or lists shrunk because the card is short of memory): even a launch that handed
     // every pair on cannot overrun its list.
@@ -710,7 +876,7 @@ static int run_chain(msspe_ctx *ctx, ChemEntry *ce, const ChainRoute &route, con
         rows_per_chunk = n_rows_all;
     }
     if (rows_per_chunk < 1) rows_per_chunk = 1;
-    if (!fast) {
+    if (!route.fast) {
         // generic kernel over the whole block, a band of rows per launch (matrix mode derives
         // (row, col) from sinks.row0 / sinks.col0, so the output base pointers move with the band)
         for (int r = row0; r < row1; r += (int)rows_per_chunk) {
@@ -728,119 +894,16 @@ static int run_chain(msspe_ctx *ctx, ChemEntry *ce, const ChainRoute &route, con
     }
     if (!wave_matrix) {
         if ((rc = ensure_sort(ctx, (size_t)ncols))) return rc;
-        HIP_TRY(ctx, sort_columns_by_composition(d_pool, col0, ncols, k2, ctx->d_sort_scratch,
+        HIP_TRY(ctx, sort_columns_by_composition(b.pool, col0, ncols, k2, ctx->d_sort_scratch,
                                                  ctx->sort_scratch_bytes, ctx->d_sorted, ctx->d_perm,
                                                  ctx->stream));
     }
     // Overflow pairs are collected over several launches and finished together: the list kernels
     // have a fixed latency floor, and list_cap entries cannot be overrun by list_cap / kChunkPairs
-    // launches even if every pair overflowed.
+    // launches even if every pair overflowed.  List 0 (ovf_list) = what the first stage did not answer.
     auto flush = [&]() -> int {
-        PairKernelArgs a;
-        a.ft = ce->d_ft;
-        a.c = ce->c[0];
-        a.pool = d_pool;
-        a.cols_sorted = nullptr;
-        a.perm = nullptr;
-        a.ncols_sorted = 0;
-        a.n = n;
-        a.k = k;
-        a.k2 = k2;
-        a.row0 = row0;
-        a.row1 = row1;
-        a.col0 = 0;
-        a.col1 = ncols;
-        a.sinks = sinks;
-        a.work_counter = ctx->ovf_count + 7;
-        // list A (ovf_list, counter 0) = what the first stage did not answer
-        const uint2 *in_list = ctx->ovf_list;
-        uint2 *out_list = ctx->ovf_list2;
-        int in_c = 0, out_c = 1;
-        if (split || wave_matrix) {
-            // long oligos: what the split kernel handed on is answered in f64 by one wave per pair;
-            // the dense kernel takes what is left (two self-complementary oligos, huge tables)
-            if (split && wave_ok) {
-                a.overflow_list = out_list;
-                a.overflow_count = ctx->ovf_count + out_c;
-                a.overflow_cap = (uint32_t)kListCap;
-                HIP_TRY(ctx, launch_pairs_wave(a, ce->d_st, in_list, ctx->ovf_count + in_c, ctx->stream, end1));
-                in_list = out_list;
-                in_c = out_c;
-            }
-            g.list = in_list;
-            g.list_count = ctx->ovf_count + in_c;
-            g.n_work = kListCap;
-            HIP_TRY(ctx, launch_dimer_generic(g, ctx->stream, end1));
-            hipLaunchKernelGGL(k_accumulate_overflow, dim3(1), dim3(64), 0, ctx->stream, ctx->ovf_count,
-                               ctx->d_ovf_total, (uint32_t)kListCap);
-            HIP_TRY(ctx, hipMemsetAsync(ctx->ovf_count, 0, 8 * sizeof(uint32_t), ctx->stream));
-            return MSSPE_OK;
-        }
-        auto advance = [&]() {   // the two buffers ping-pong: a stage's input is consumed when it ends
-            in_list = out_list;
-            out_list = out_list == ctx->ovf_list2 ? ctx->ovf_list : ctx->ovf_list2;
-            in_c = out_c;
-            out_c = out_c + 1;
-        };
-        if (int_stage) {
-            // (1) the integer kernel again, 64 slots, lanes sorted by table size: pairs that only left
-            //     their wave because of their size; (2) the 56-slot f64 table: exact ties
-            a.overflow_list = out_list;
-            a.overflow_count = ctx->ovf_count + out_c;
-            a.overflow_cap = (uint32_t)kListCap;
-            HIP_TRY(ctx, launch_pairs_int_list(a, ce->d_it, in_list, ctx->ovf_count + in_c, ctx->d_reasons,
-                                               ctx->n_cu, ctx->stream));
-            advance();
-            if (short_chain) {
-                // a reference-sized screen: what the integer list stage leaves (some ten thousand pairs) goes straight to
-                // one wave per pair -- each of the three register-table stages in between has a latency floor of 0.4 ...
-                // 0.6 ms whatever its list holds, the wave kernel takes 0.13 ms + 16 ns per pair
-                a.overflow_list = out_list;
-                a.overflow_count = ctx->ovf_count + out_c;
-                HIP_TRY(ctx, launch_pairs_wave(a, ce->d_st, in_list, ctx->ovf_count + in_c, ctx->stream, end1));
-                g.list = out_list;
-                g.list_count = ctx->ovf_count + out_c;
-                g.n_work = kListCap;
-                HIP_TRY(ctx, launch_dimer_generic(g, ctx->stream, end1));
-                hipLaunchKernelGGL(k_accumulate_overflow, dim3(1), dim3(64), 0, ctx->stream, ctx->ovf_count,
-                                   ctx->d_ovf_total, (uint32_t)kListCap);
-                HIP_TRY(ctx, hipMemsetAsync(ctx->ovf_count, 0, 8 * sizeof(uint32_t), ctx->stream));
-                return MSSPE_OK;
-            }
-            if (ce->split_max_k >= k && ctx->opt.split_list) {
-                // (1b) tables beyond the list stage's 63 stored cells: two lanes per pair, still exact integers
-                //      (marked entries -- ties -- pass through to the f64 kernels)
-                a.overflow_list = out_list;
-                a.overflow_count = ctx->ovf_count + out_c;
-                HIP_TRY(ctx, launch_pairs_split_list(a, ce->d_st, in_list, ctx->ovf_count + in_c, ctx->n_cu, ctx->stream));
-                advance();
-            }
-            a.overflow_list = out_list;
-            a.overflow_count = ctx->ovf_count + out_c;
-            HIP_TRY(ctx, launch_pairs_main_list(a, in_list, ctx->ovf_count + in_c, ctx->stream));
-            advance();
-        }
-        // the wide table over the list
-        a.overflow_list = out_list;
-        a.overflow_count = ctx->ovf_count + out_c;
-        a.overflow_cap = (uint32_t)kListCap;
-        HIP_TRY(ctx, launch_pairs_wide(a, in_list, ctx->ovf_count + in_c, ctx->stream, end1));
-        if (wave_ok) {
-            // huge tables: one wave per pair, the table in LDS
-            advance();
-            a.overflow_list = out_list;
-            a.overflow_count = ctx->ovf_count + out_c;
-            HIP_TRY(ctx, launch_pairs_wave(a, ce->d_st, in_list, ctx->ovf_count + in_c, ctx->stream, end1));
-        }
-        // last stage: whatever is left (both-self-complementary pairs)
-        g.list = out_list;
-        g.list_count = ctx->ovf_count + out_c;
-        g.n_work = kListCap;
-        HIP_TRY(ctx, launch_dimer_generic(g, ctx->stream, end1));
-        hipLaunchKernelGGL(k_accumulate_overflow, dim3(1), dim3(64), 0, ctx->stream, ctx->ovf_count,
-                           ctx->d_ovf_total, (uint32_t)kListCap);
-        HIP_TRY(ctx, hipMemsetAsync(ctx->ovf_count, 0, 8 * sizeof(uint32_t), ctx->stream));
-        return MSSPE_OK;
+        PairKernelArgs a = pair_args(ctx, ce, b);
+        return ListChain(ctx, ce, end1, ctx->ovf_list, kListCap).run(route.behind, a, g, true);
     };
     HIP_TRY(ctx, hipMemsetAsync(ctx->ovf_count, 0, 8 * sizeof(uint32_t), ctx->stream));
     long pending = 0;   // worst-case entries the list may hold
@@ -853,25 +916,17 @@ static int run_chain(msspe_ctx *ctx, ChemEntry *ce, const ChainRoute &route, con
                 if ((rc = flush())) return rc;
                 pending = 0;
             }
-            PairKernelArgs a;
-            a.ft = ce->d_ft;
-            a.c = ce->c[0];
-            a.pool = d_pool;
+            PairKernelArgs a = pair_args(ctx, ce, b);
             a.cols_sorted = ctx->d_sorted;
             a.perm = ctx->d_perm;
             a.ncols_sorted = ncols;
-            a.n = n;
-            a.k = k;
-            a.k2 = k2;
             a.row0 = r;
             a.row1 = r_end;
             a.col0 = (int)q0;
             a.col1 = (int)q_end;
-            a.sinks = sinks;
             a.overflow_list = ctx->ovf_list;
             a.overflow_count = ctx->ovf_count;
             a.overflow_cap = (uint32_t)kListCap;
-            a.work_counter = ctx->ovf_count + 7;   // the last of the eight stage counters
             if (ctx->prof_on) {
                 if (ctx->prof_used == ctx->prof_events.size()) {
                     hipEvent_t e0, e1;
@@ -900,22 +955,28 @@ static int run_chain(msspe_ctx *ctx, ChemEntry *ce, const ChainRoute &route, con
     return MSSPE_OK;
 }
 
-
-static int cross_dimer_impl(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, int k2, const msspe_chem *chem,
-                            float dg_threshold, int row0, int row1, int col0, int col1,
-                            uint32_t *d_row_conflicts, uint64_t *d_bitmap, double *d_dg, double *d_tm,
-                            EdgeRecord *d_edges, unsigned long long *d_edge_count, unsigned long long edge_cap)
+// What both screens check first, and the chemistry's cache entry of the screen's kind; *ce stays null for an empty
+// block (nothing to do).
+static int open_screen(msspe_ctx *ctx, const ScreenBlock &b, const msspe_chem *chem, float threshold, int kind,
+                       ChemEntry **ce)
 {
     if (!ctx) return MSSPE_ERR_ARG;
-    if (!d_pool || !chem || n < 0) return fail(ctx, MSSPE_ERR_ARG, "null pool/chemistry");
-    if (k < 2 || k > 32 || k2 < 2 || k2 > 32) return fail(ctx, MSSPE_ERR_K, "oligo length must be 2..32");
-    if (row0 < 0 || row1 > n || row0 > row1 || col0 < 0 || col1 > n || col0 > col1)
+    if (!b.pool || !chem || b.n < 0) return fail(ctx, MSSPE_ERR_ARG, "null pool/chemistry");
+    if (b.k < 2 || b.k > 32 || b.k2 < 2 || b.k2 > 32) return fail(ctx, MSSPE_ERR_K, "oligo length must be 2..32");
+    if (b.row0 < 0 || b.row1 > b.n || b.row0 > b.row1 || b.col0 < 0 || b.col1 > b.n || b.col0 > b.col1)
         return fail(ctx, MSSPE_ERR_ARG, "row/column range outside the pool");
-    if (row0 == row1 || col0 == col1) return MSSPE_OK;
+    if (b.row0 == b.row1 || b.col0 == b.col1) return MSSPE_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return chem_entry(ctx, *chem, threshold, ce, kind);
+}
+
+// The ANY screen (thal ANY for every ordered pair of the block, conflict iff dG <= the threshold's cut).
+static int cross_dimer_impl(msspe_ctx *ctx, const ScreenBlock &b, const msspe_chem *chem, float dg_threshold)
+{
     ChemEntry *ce = nullptr;
-    int rc = chem_entry(ctx, *chem, dg_threshold, &ce);
-    if (rc) return rc;
+    const int rc = open_screen(ctx, b, chem, dg_threshold, kCutAnyDg, &ce);
+    if (rc || !ce) return rc;
+    const int k = b.k, k2 = b.k2;
     // long oligos: exact-integer kernel with a pair's table split over lanes (honours max_loop)
     // (also short oligos under a loop-size limit the register-table kernels do not implement)
     // Row and column oligos of different lengths (k2 != k) take the rectangular chain: the split-table kernel
@@ -929,24 +990,41 @@ static int cross_dimer_impl(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k
                        (rect || (!(ctx->opt.pair_kernel == 1) && (k >= ctx->opt.split_min_k || chem->max_loop < 2 * k - 4)));
     // f64, one wave per pair: behind the split kernel, and as the first stage where neither the split
     // kernel nor the register-table chain applies (29 .. 32 bases, parameter files off the grid)
-    const bool wave_ok = !ctx->opt.force_generic && kmax <= ce->wave_max_k && ctx->opt.wave_kernel;
-    const bool wave_matrix = wave_ok && !split && (rect || k > pairs_fast_max_k() || chem->max_loop < 2 * k - 4);
-    // the register-table / integer / row first stages are square-only: a rectangle that neither the split nor the
-    // wave kernel takes goes to the dense kernel
-    const bool fast = split || wave_matrix ||
-                      (!rect && !ctx->opt.force_generic && k <= pairs_fast_max_k() && ce->fast_ok &&
-                       chem->max_loop >= 2 * k - 4);   // the tuned kernel has no loop-size cut-off
+    const bool wave = wave_ok(ctx, ce, kmax);
+    const bool wave_matrix = wave && !split && (rect || k > pairs_fast_max_k() || chem->max_loop < 2 * k - 4);
     ChainRoute route;
     route.end1 = false;
-    route.fast = fast;
+    // the register-table / integer / row first stages are square-only: a rectangle that neither the split nor the
+    // wave kernel takes goes to the dense kernel
+    route.fast = split || wave_matrix || (!rect && reg_tables_ok(ctx, ce, k));
     route.split = split;
-    route.wave_ok = wave_ok;
     route.wave_matrix = wave_matrix;
     route.int_stage = !split && ce->int_ok && !(ctx->opt.pair_kernel == 1);
-    // small screens (the reference's are at most 2,000^2): the short chain behind the integer list stage
-    route.short_chain = wave_ok && ctx->opt.short_chain && (long)(row1 - row0) * (long)(col1 - col0) <= (1L << 23);
-    return run_chain(ctx, ce, route, d_pool, n, k, k2, row0, row1, col0, col1, d_row_conflicts, d_bitmap, d_dg, d_tm,
-                     d_edges, d_edge_count, edge_cap);
+    StageList &s = route.behind;
+    if (split || wave_matrix) {
+        // long oligos: what the split kernel handed on is answered in f64 by one wave per pair; the dense kernel
+        // takes what is left (two self-complementary oligos, huge tables)
+        if (split && wave) s.add(ListStage::Wave);
+    } else if (route.int_stage) {
+        s.add(ListStage::IntList);
+        // small screens (the reference's are at most 2,000^2): the short chain.  What the integer list stage leaves
+        // (some ten thousand pairs) goes straight to one wave per pair -- each of the three register-table stages
+        // in between has a latency floor of 0.4 ... 0.6 ms whatever its list holds, the wave kernel takes 0.13 ms +
+        // 16 ns per pair
+        if (wave && ctx->opt.short_chain && (long)(b.row1 - b.row0) * (long)(b.col1 - b.col0) <= (1L << 23)) {
+            s.add(ListStage::Wave);
+        } else {
+            if (ce->split_max_k >= k && ctx->opt.split_list) s.add(ListStage::SplitList);
+            s.add(ListStage::MainList);
+            s.add(ListStage::Wide);
+            if (wave) s.add(ListStage::Wave);
+        }
+    } else {   // pair_kernel "f64", or tables without an integer image: k_pairs_fast first
+        s.add(ListStage::Wide);
+        if (wave) s.add(ListStage::Wave);
+    }
+    s.add(ListStage::Dense);
+    return run_chain(ctx, ce, route, b);
 }
 
 // The END screen (thal END1 for every ordered pair of the block, conflict iff round_fixed_f32(max(0, t), 2) >=
@@ -954,33 +1032,62 @@ static int cross_dimer_impl(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k
 // END1 over composition-sorted columns, then the wide list, the wave list and the dense kernel; everything else
 // (longer oligos, rectangles, small max_loop): the wave kernel in matrix mode where max(k, k2) is within its range,
 // then the dense kernel; where neither first stage applies, the dense kernel takes the block.
-static int cross_dimer_end_impl(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, int k2, const msspe_chem *chem,
-                                float tm_threshold, int row0, int row1, int col0, int col1, uint32_t *d_row_conflicts,
-                                uint64_t *d_bitmap, double *d_dg, double *d_tm, EdgeRecord *d_edges,
-                                unsigned long long *d_edge_count, unsigned long long edge_cap)
+static int cross_dimer_end_impl(msspe_ctx *ctx, const ScreenBlock &b, const msspe_chem *chem, float tm_threshold)
 {
-    if (!ctx) return MSSPE_ERR_ARG;
-    if (!d_pool || !chem || n < 0) return fail(ctx, MSSPE_ERR_ARG, "null pool/chemistry");
-    if (k < 2 || k > 32 || k2 < 2 || k2 > 32) return fail(ctx, MSSPE_ERR_K, "oligo length must be 2..32");
-    if (row0 < 0 || row1 > n || row0 > row1 || col0 < 0 || col1 > n || col0 > col1)
-        return fail(ctx, MSSPE_ERR_ARG, "row/column range outside the pool");
-    if (row0 == row1 || col0 == col1) return MSSPE_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     ChemEntry *ce = nullptr;
-    int rc = chem_entry(ctx, *chem, tm_threshold, &ce, kCutEndT);
-    if (rc) return rc;
-    const bool reg = k2 == k && !ctx->opt.force_generic && k <= pairs_fast_max_k() && ce->fast_ok &&
-                     chem->max_loop >= 2 * k - 4;   // the tuned kernel has no loop-size cut-off
+    const int rc = open_screen(ctx, b, chem, tm_threshold, kCutEndT, &ce);
+    if (rc || !ce) return rc;
+    const bool reg = b.k2 == b.k && reg_tables_ok(ctx, ce, b.k);
+    const bool wave = wave_ok(ctx, ce, std::max(b.k, b.k2));
     ChainRoute route;
     route.end1 = true;
     route.split = false;
     route.int_stage = false;
-    route.short_chain = false;
-    route.wave_ok = !ctx->opt.force_generic && std::max(k, k2) <= ce->wave_max_k && ctx->opt.wave_kernel;
-    route.wave_matrix = route.wave_ok && !reg;
+    route.wave_matrix = wave && !reg;
     route.fast = reg || route.wave_matrix;
-    return run_chain(ctx, ce, route, d_pool, n, k, k2, row0, row1, col0, col1, d_row_conflicts, d_bitmap, d_dg, d_tm,
-                     d_edges, d_edge_count, edge_cap);
+    if (reg) {
+        route.behind.add(ListStage::Wide);
+        if (wave) route.behind.add(ListStage::Wave);
+    }
+    route.behind.add(ListStage::Dense);
+    return run_chain(ctx, ce, route, b);
+}
+
+// end: the END screen (threshold = tm_threshold) instead of thal ANY
+static int cross_dimer_screen(msspe_ctx *ctx, const ScreenBlock &b, const msspe_chem *chem, float threshold, bool end)
+{
+    return end ? cross_dimer_end_impl(ctx, b, chem, threshold) : cross_dimer_impl(ctx, b, chem, threshold);
+}
+
+int msspe_cross_dimer_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k,
+                          const msspe_chem *chem, float dg_threshold, int row0, int row1,
+                          int col0, int col1, uint32_t *d_row_conflicts, uint64_t *d_bitmap,
+                          double *d_dg, double *d_tm)
+{
+    return cross_dimer_impl(ctx, screen_block(d_pool, n, k, k, row0, row1, col0, col1,
+                                              plane_sinks(d_row_conflicts, d_bitmap, d_dg, d_tm)),
+                            chem, dg_threshold);
+}
+
+// The edge-list forms of the device screens: the count is cleared on the stream the kernels run on.
+static int cross_dimer_edges_dev(msspe_ctx *ctx, const ScreenBlock &b, const msspe_chem *chem, float threshold, bool end)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!b.sinks.edge_count || (b.sinks.edge_cap && !b.sinks.edges))
+        return fail(ctx, MSSPE_ERR_ARG, "edge list: null count or buffer");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMemsetAsync(b.sinks.edge_count, 0, sizeof(uint64_t), ctx->stream));
+    return cross_dimer_screen(ctx, b, chem, threshold, end);
+}
+
+int msspe_cross_dimer_edges_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const msspe_chem *chem,
+                                float dg_threshold, int row0, int row1, int col0, int col1,
+                                uint32_t *d_row_conflicts, msspe_edge_dev *d_edges, uint64_t capacity,
+                                uint64_t *d_count)
+{
+    return cross_dimer_edges_dev(ctx, screen_block(d_pool, n, k, k, row0, row1, col0, col1,
+                                                   edge_sinks(d_row_conflicts, d_edges, d_count, capacity)),
+                                 chem, dg_threshold, false);
 }
 
 double msspe_t_cut(float tm_threshold) { return t_cut(tm_threshold); }
@@ -989,8 +1096,9 @@ int msspe_cross_dimer_end_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int
                               float tm_threshold, int row0, int row1, int col0, int col1, uint32_t *d_row_conflicts,
                               uint64_t *d_bitmap, double *d_dg, double *d_tm)
 {
-    return cross_dimer_end_impl(ctx, d_pool, n, k, k, chem, tm_threshold, row0, row1, col0, col1, d_row_conflicts,
-                                d_bitmap, d_dg, d_tm, nullptr, nullptr, 0);
+    return cross_dimer_end_impl(ctx, screen_block(d_pool, n, k, k, row0, row1, col0, col1,
+                                                  plane_sinks(d_row_conflicts, d_bitmap, d_dg, d_tm)),
+                                chem, tm_threshold);
 }
 
 int msspe_cross_dimer_end_edges_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const msspe_chem *chem,
@@ -998,14 +1106,9 @@ int msspe_cross_dimer_end_edges_dev(msspe_ctx *ctx, const uint64_t *d_pool, int 
                                     uint32_t *d_row_conflicts, msspe_end_edge_dev *d_edges, uint64_t capacity,
                                     uint64_t *d_count)
 {
-    if (!ctx) return MSSPE_ERR_ARG;
-    if (!d_count || (capacity && !d_edges)) return fail(ctx, MSSPE_ERR_ARG, "edge list: null count or buffer");
-    static_assert(sizeof(msspe_end_edge_dev) == sizeof(EdgeRecord), "edge record layouts differ");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipMemsetAsync(d_count, 0, sizeof(uint64_t), ctx->stream));
-    return cross_dimer_end_impl(ctx, d_pool, n, k, k, chem, tm_threshold, row0, row1, col0, col1, d_row_conflicts,
-                                nullptr, nullptr, nullptr, reinterpret_cast<EdgeRecord *>(d_edges),
-                                reinterpret_cast<unsigned long long *>(d_count), capacity);
+    return cross_dimer_edges_dev(ctx, screen_block(d_pool, n, k, k, row0, row1, col0, col1,
+                                                   edge_sinks(d_row_conflicts, d_edges, d_count, capacity)),
+                                 chem, tm_threshold, true);
 }
 
 int msspe_profile_enable(msspe_ctx *ctx, int on)
@@ -1081,67 +1184,43 @@ int msspe_pair_stage_samples(msspe_ctx *ctx, uint64_t *out, int capacity, int *n
 
 namespace {
 
-// Host-buffer screens: `packed` (uploaded here) is the pool, rows [0, n_rows) of length k against columns
-// [col_base, col_base + n_cols) of length k2.  One pool: col_base 0, n_rows = n_cols = n.  Pool A + pool B back to
-// back: col_base = n_a.  Outputs are dense over the block as in msspe_cross_dimer.
-// end: the END screen (cross_dimer_end_impl, threshold = tm_threshold) instead of thal ANY.
-int cross_dimer_host(msspe_ctx *ctx, const std::vector<uint64_t> &packed, int n_rows, int k, int col_base, int n_cols,
-                     int k2, const msspe_chem *chem, float dg_threshold, uint32_t *row_conflicts, uint64_t *bitmap,
-                     double *dg, double *tm, bool end = false)
+// Host-buffer screens: `packed` (uploaded here) is the pool, the host block's rows [0, row1) against its columns
+// [col0, col1).  One pool: columns [0, n).  Pool A + pool B back to back: columns from n_a.  The block's sinks are the
+// caller's host buffers, dense over the block as in msspe_cross_dimer.
+// end: the END screen (threshold = tm_threshold) instead of thal ANY.
+int cross_dimer_host(msspe_ctx *ctx, const std::vector<uint64_t> &packed, const ScreenBlock &host,
+                     const msspe_chem *chem, float threshold, bool end)
 {
-    const int n = (int)packed.size();
+    const size_t n = packed.size(), n_rows = (size_t)host.row1;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const size_t words = ((size_t)n_cols + 63) / 64, nn = (size_t)n_rows * (size_t)n_cols;
-    uint64_t *d_pool = nullptr, *d_bitmap = nullptr;
-    uint32_t *d_rc = nullptr;
-    double *d_dg = nullptr, *d_tm = nullptr;
-    auto cleanup = [&]() {
-        if (d_pool) (void)hipFree(d_pool);
-        if (d_bitmap) (void)hipFree(d_bitmap);
-        if (d_rc) (void)hipFree(d_rc);
-        if (d_dg) (void)hipFree(d_dg);
-        if (d_tm) (void)hipFree(d_tm);
-    };
-#define TRY_OR_CLEAN(expr)                                         \
-    do {                                                           \
-        hipError_t e__ = (expr);                                   \
-        if (e__ != hipSuccess) {                                   \
-            cleanup();                                             \
-            return hip_fail(ctx, e__, #expr);                      \
-        }                                                          \
-    } while (0)
-    TRY_OR_CLEAN(hipMalloc((void **)&d_pool, sizeof(uint64_t) * (size_t)n));
-    TRY_OR_CLEAN(hipMemcpy(d_pool, packed.data(), sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice));
-    if (row_conflicts) {
-        TRY_OR_CLEAN(hipMalloc((void **)&d_rc, sizeof(uint32_t) * (size_t)n_rows));
-        TRY_OR_CLEAN(hipMemsetAsync(d_rc, 0, sizeof(uint32_t) * (size_t)n_rows, ctx->stream));   // on the stream the kernels run on (it is non-blocking: the null stream does not order against it)
+    const size_t words = (size_t)host.sinks.words, nn = n_rows * (size_t)host.sinks.ncols;
+    const PairSinks &out = host.sinks;
+    DevBuf<uint64_t> d_pool, d_bitmap;
+    DevBuf<uint32_t> d_rc;
+    DevBuf<double> d_dg, d_tm;
+    HIP_TRY(ctx, d_pool.alloc(n));
+    HIP_TRY(ctx, hipMemcpy(d_pool, packed.data(), sizeof(uint64_t) * n, hipMemcpyHostToDevice));
+    if (out.row_conflicts) {
+        HIP_TRY(ctx, d_rc.alloc(n_rows));
+        HIP_TRY(ctx, hipMemsetAsync(d_rc, 0, sizeof(uint32_t) * n_rows, ctx->stream));   // on the stream the kernels run on (it is non-blocking: the null stream does not order against it)
     }
-    if (bitmap) {
-        TRY_OR_CLEAN(hipMalloc((void **)&d_bitmap, sizeof(uint64_t) * (size_t)n_rows * words));
-        TRY_OR_CLEAN(hipMemsetAsync(d_bitmap, 0, sizeof(uint64_t) * (size_t)n_rows * words, ctx->stream));
+    if (out.bitmap) {
+        HIP_TRY(ctx, d_bitmap.alloc(n_rows * words));
+        HIP_TRY(ctx, hipMemsetAsync(d_bitmap, 0, sizeof(uint64_t) * n_rows * words, ctx->stream));
     }
-    if (dg) TRY_OR_CLEAN(hipMalloc((void **)&d_dg, sizeof(double) * nn));
-    if (tm) TRY_OR_CLEAN(hipMalloc((void **)&d_tm, sizeof(double) * nn));
-    int rc = (end ? cross_dimer_end_impl : cross_dimer_impl)(ctx, d_pool, n, k, k2, chem, dg_threshold, 0, n_rows,
-                                                             col_base, col_base + n_cols, d_rc, d_bitmap, d_dg, d_tm,
-                                                             nullptr, nullptr, 0);
-    if (rc) {
-        cleanup();
-        return rc;
-    }
-    TRY_OR_CLEAN(hipStreamSynchronize(ctx->stream));
-    if ((rc = check_list_overrun(ctx))) {
-        cleanup();
-        return rc;
-    }
-    if (row_conflicts)
-        TRY_OR_CLEAN(hipMemcpy(row_conflicts, d_rc, sizeof(uint32_t) * (size_t)n_rows, hipMemcpyDeviceToHost));
-    if (bitmap)
-        TRY_OR_CLEAN(hipMemcpy(bitmap, d_bitmap, sizeof(uint64_t) * (size_t)n_rows * words, hipMemcpyDeviceToHost));
-    if (dg) TRY_OR_CLEAN(hipMemcpy(dg, d_dg, sizeof(double) * nn, hipMemcpyDeviceToHost));
-    if (tm) TRY_OR_CLEAN(hipMemcpy(tm, d_tm, sizeof(double) * nn, hipMemcpyDeviceToHost));
-#undef TRY_OR_CLEAN
-    cleanup();
+    if (out.dg) HIP_TRY(ctx, d_dg.alloc(nn));
+    if (out.tm) HIP_TRY(ctx, d_tm.alloc(nn));
+    int rc = cross_dimer_screen(ctx, screen_block(d_pool, (int)n, host.k, host.k2, 0, host.row1, host.col0, host.col1,
+                                                  plane_sinks(d_rc, d_bitmap, d_dg, d_tm)),
+                                chem, threshold, end);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if ((rc = check_list_overrun(ctx))) return rc;
+    if (out.row_conflicts)
+        HIP_TRY(ctx, hipMemcpy(out.row_conflicts, d_rc, sizeof(uint32_t) * n_rows, hipMemcpyDeviceToHost));
+    if (out.bitmap) HIP_TRY(ctx, hipMemcpy(out.bitmap, d_bitmap, sizeof(uint64_t) * n_rows * words, hipMemcpyDeviceToHost));
+    if (out.dg) HIP_TRY(ctx, hipMemcpy(out.dg, d_dg, sizeof(double) * nn, hipMemcpyDeviceToHost));
+    if (out.tm) HIP_TRY(ctx, hipMemcpy(out.tm, d_tm, sizeof(double) * nn, hipMemcpyDeviceToHost));
     return MSSPE_OK;
 }
 
@@ -1198,31 +1277,30 @@ __global__ void k_edges_shift_b(EdgeRecord *edges, const unsigned long long *cou
         edges[e].b -= shift;
 }
 
-// end: the END screen (cross_dimer_end_impl: A = oligo 1, the anchored 3' end) instead of thal ANY.
-int cross_dimer_ab_impl(msspe_ctx *ctx, const uint64_t *d_a, int n_a, int k_a, const uint64_t *d_b, int n_b, int k_b,
-                        const msspe_chem *chem, float dg_threshold, int row0, int row1, int col0, int col1,
-                        uint32_t *d_row_conflicts, uint64_t *d_bitmap, double *d_dg, double *d_tm, EdgeRecord *d_edges,
-                        unsigned long long *d_edge_count, unsigned long long edge_cap, bool end = false)
+// ab: the block in the pools' own indices -- rows of A (k = k_a), columns of B (k2 = k_b); its pool and n are those of
+// the staged A + B pool and are set here.  end: the END screen (A = oligo 1, the anchored 3' end) instead of thal ANY.
+int cross_dimer_ab_impl(msspe_ctx *ctx, const uint64_t *d_a, int n_a, const uint64_t *d_b, int n_b,
+                        const ScreenBlock &ab, const msspe_chem *chem, float threshold, bool end)
 {
     if (!chem || n_a < 0 || n_b < 0 || (n_a && !d_a) || (n_b && !d_b))
         return fail(ctx, MSSPE_ERR_ARG, "null pool/chemistry");
-    if (k_a < 2 || k_a > 32 || k_b < 2 || k_b > 32) return fail(ctx, MSSPE_ERR_K, "oligo length must be 2..32");
-    if (row0 < 0 || row1 > n_a || row0 > row1 || col0 < 0 || col1 > n_b || col0 > col1)
+    if (ab.k < 2 || ab.k > 32 || ab.k2 < 2 || ab.k2 > 32) return fail(ctx, MSSPE_ERR_K, "oligo length must be 2..32");
+    if (ab.row0 < 0 || ab.row1 > n_a || ab.row0 > ab.row1 || ab.col0 < 0 || ab.col1 > n_b || ab.col0 > ab.col1)
         return fail(ctx, MSSPE_ERR_ARG, "row/column range outside pool A / pool B");
     if ((long)n_a + (long)n_b > (long)INT32_MAX) return fail(ctx, MSSPE_ERR_ARG, "pools too large");
-    if (row0 == row1 || col0 == col1) return MSSPE_OK;
+    if (ab.row0 == ab.row1 || ab.col0 == ab.col1) return MSSPE_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     int rc = stage_ab(ctx, d_a, n_a, d_b, n_b);
     if (rc) return rc;
     // k_a == k_b: the single-pool chain as it is (the 13-mer A x B screen runs on the row kernel); otherwise the
     // rectangular chain
-    rc = (end ? cross_dimer_end_impl : cross_dimer_impl)(ctx, ctx->d_ab, n_a + n_b, k_a, k_b, chem, dg_threshold, row0,
-                                                         row1, n_a + col0, n_a + col1, d_row_conflicts, d_bitmap, d_dg,
-                                                         d_tm, d_edges, d_edge_count, edge_cap);
+    rc = cross_dimer_screen(ctx, screen_block(ctx->d_ab, n_a + n_b, ab.k, ab.k2, ab.row0, ab.row1, n_a + ab.col0,
+                                              n_a + ab.col1, ab.sinks),
+                            chem, threshold, end);
     if (rc) return rc;
-    if (d_edges && edge_cap && n_a) {
-        hipLaunchKernelGGL(k_edges_shift_b, dim3(256), dim3(256), 0, ctx->stream, d_edges, d_edge_count, edge_cap,
-                           (uint32_t)n_a);
+    if (ab.sinks.edges && ab.sinks.edge_cap && n_a) {
+        hipLaunchKernelGGL(k_edges_shift_b, dim3(256), dim3(256), 0, ctx->stream, ab.sinks.edges, ab.sinks.edge_count,
+                           ab.sinks.edge_cap, (uint32_t)n_a);
         HIP_TRY(ctx, hipGetLastError());
     }
     return MSSPE_OK;
@@ -1231,20 +1309,6 @@ int cross_dimer_ab_impl(msspe_ctx *ctx, const uint64_t *d_a, int n_a, int k_a, c
 }  // namespace
 
 extern "C" {
-
-int msspe_cross_dimer(msspe_ctx *ctx, const char *pool_ascii, int n, int k,
-                      const msspe_chem *chem, float dg_threshold, uint32_t *row_conflicts,
-                      uint64_t *bitmap, double *dg, double *tm)
-{
-    if (!ctx) return MSSPE_ERR_ARG;
-    if (!pool_ascii || !chem || n < 0) return fail(ctx, MSSPE_ERR_ARG, "null pool/chemistry");
-    if (n == 0) return MSSPE_OK;
-    std::vector<uint64_t> packed((size_t)n);
-    int rc = msspe_pack_oligos(pool_ascii, n, k, packed.data());
-    if (rc) return fail(ctx, rc, rc == MSSPE_ERR_K ? "oligo length must be 1..32"
-                                                   : "pool holds characters other than ACGT");
-    return cross_dimer_host(ctx, packed, n, k, 0, n, k, chem, dg_threshold, row_conflicts, bitmap, dg, tm);
-}
 
 int msspe_conflict_cover_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const uint64_t *d_bitmap,
                              int drop_self_pairs, uint8_t *d_deleted, int *n_deleted_out)
@@ -1276,9 +1340,8 @@ int msspe_conflict_cover(msspe_ctx *ctx, const char *pool_ascii, int n, int k, c
     if (n > kCoverMaxN)
         return fail(ctx, MSSPE_ERR_ARG, "conflict cover: " + std::to_string(n) + " oligos, at most " +
                                             std::to_string(kCoverMaxN) + " (the symmetrised bitmap is n^2 / 8 bytes)");
-    std::vector<uint64_t> packed((size_t)n);
-    if (msspe_pack_oligos(pool_ascii, n, k, packed.data()))
-        return fail(ctx, MSSPE_ERR_ARG, "pool holds characters other than ACGT");
+    std::vector<uint64_t> packed;
+    if (int rc = pack_pool(ctx, pool_ascii, n, k, packed)) return rc;
     {   // duplicates before the screen, not after it
         std::vector<uint64_t> s(packed);
         std::sort(s.begin(), s.end());
@@ -1287,39 +1350,21 @@ int msspe_conflict_cover(msspe_ctx *ctx, const char *pool_ascii, int n, int k, c
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t words = ((size_t)n + 63) / 64;
-    uint64_t *d_pool = nullptr, *d_bitmap = nullptr;
-    uint8_t *d_deleted = nullptr;
-    auto cleanup = [&]() {
-        if (d_pool) (void)hipFree(d_pool);
-        if (d_bitmap) (void)hipFree(d_bitmap);
-        if (d_deleted) (void)hipFree(d_deleted);
-    };
-#define TRY_OR_CLEAN4(expr)                                        \
-    do {                                                           \
-        hipError_t e__ = (expr);                                   \
-        if (e__ != hipSuccess) {                                   \
-            cleanup();                                             \
-            return hip_fail(ctx, e__, #expr);                      \
-        }                                                          \
-    } while (0)
-    TRY_OR_CLEAN4(hipMalloc((void **)&d_pool, sizeof(uint64_t) * (size_t)n));
-    TRY_OR_CLEAN4(hipMalloc((void **)&d_bitmap, sizeof(uint64_t) * (size_t)n * words));
-    TRY_OR_CLEAN4(hipMalloc((void **)&d_deleted, (size_t)n));
-    TRY_OR_CLEAN4(hipMemcpyAsync(d_pool, packed.data(), sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice,
-                                 ctx->stream));
+    DevBuf<uint64_t> d_pool, d_bitmap;
+    DevBuf<uint8_t> d_deleted;
+    HIP_TRY(ctx, d_pool.alloc((size_t)n));
+    HIP_TRY(ctx, d_bitmap.alloc((size_t)n * words));
+    HIP_TRY(ctx, d_deleted.alloc((size_t)n));
+    HIP_TRY(ctx, hipMemcpyAsync(d_pool, packed.data(), sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice,
+                                ctx->stream));
     // the screen's decisions only: the bitmap is all the cover reads
     int rc = msspe_cross_dimer_dev(ctx, d_pool, n, k, chem, dg_threshold, 0, n, 0, n, nullptr, d_bitmap, nullptr,
                                    nullptr);
     if (!rc) rc = msspe_conflict_cover_dev(ctx, d_pool, n, k, d_bitmap, drop_self_pairs, d_deleted, n_deleted_out);
     if (!rc) rc = check_list_overrun(ctx);   // the cover has synchronised the stream
-    if (rc) {
-        cleanup();
-        return rc;
-    }
-    TRY_OR_CLEAN4(hipMemcpyAsync(deleted_out, d_deleted, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
-    TRY_OR_CLEAN4(hipStreamSynchronize(ctx->stream));
-#undef TRY_OR_CLEAN4
-    cleanup();
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(deleted_out, d_deleted, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return MSSPE_OK;
 }
 
@@ -1327,78 +1372,106 @@ int msspe_conflict_cover(msspe_ctx *ctx, const char *pool_ascii, int n, int k, c
 
 namespace {
 
-// Host edge lists over the same layout as cross_dimer_host: rows [0, n_rows) of length k against columns
-// [col_base, col_base + n_cols) of length k2; edge b = column index (pool index - col_base).
-// end: the END screen's edges (emit_sorted_edges).
-int cross_dimer_edges_host(msspe_ctx *ctx, const std::vector<uint64_t> &packed, int n_rows, int k, int col_base,
-                           int n_cols, int k2, const msspe_chem *chem, float dg_threshold, msspe_edge *edges,
-                           uint64_t capacity, uint64_t *count_out, bool end = false)
+// The end of a host edge-list call, behind its screens: synchronises, checks the hand-over lists and brings back the
+// count and the first min(count, capacity) raw edges.
+int fetch_edges(msspe_ctx *ctx, const uint64_t *d_count, const msspe_edge_dev *d_edges, uint64_t capacity,
+                uint64_t *count_out, std::vector<msspe_edge_dev> &raw)
 {
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    uint64_t *d_pool = nullptr, *d_count = nullptr;
-    msspe_edge_dev *d_edges = nullptr;
-    auto cleanup = [&]() {
-        if (d_pool) (void)hipFree(d_pool);
-        if (d_count) (void)hipFree(d_count);
-        if (d_edges) (void)hipFree(d_edges);
-    };
-#define TRY_OR_CLEAN2(expr)                                        \
-    do {                                                           \
-        hipError_t e__ = (expr);                                   \
-        if (e__ != hipSuccess) {                                   \
-            cleanup();                                             \
-            return hip_fail(ctx, e__, #expr);                      \
-        }                                                          \
-    } while (0)
-    const int n = (int)packed.size();
-    TRY_OR_CLEAN2(hipMalloc((void **)&d_pool, sizeof(uint64_t) * (size_t)n));
-    TRY_OR_CLEAN2(hipMemcpy(d_pool, packed.data(), sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice));
-    TRY_OR_CLEAN2(hipMalloc((void **)&d_count, sizeof(uint64_t)));
-    if (capacity) TRY_OR_CLEAN2(hipMalloc((void **)&d_edges, sizeof(msspe_edge_dev) * (size_t)capacity));
-    TRY_OR_CLEAN2(hipMemsetAsync(d_count, 0, sizeof(uint64_t), ctx->stream));
-    int rc = (end ? cross_dimer_end_impl : cross_dimer_impl)(ctx, d_pool, n, k, k2, chem, dg_threshold, 0, n_rows,
-                                                             col_base, col_base + n_cols, nullptr, nullptr, nullptr,
-                                                             nullptr, reinterpret_cast<EdgeRecord *>(d_edges),
-                                                             reinterpret_cast<unsigned long long *>(d_count), capacity);
-    if (rc) {
-        cleanup();
-        return rc;
-    }
-    TRY_OR_CLEAN2(hipStreamSynchronize(ctx->stream));
-    if ((rc = check_list_overrun(ctx))) {
-        cleanup();
-        return rc;
-    }
-    uint64_t count = 0;
-    TRY_OR_CLEAN2(hipMemcpy(&count, d_count, sizeof count, hipMemcpyDeviceToHost));
-    *count_out = count;
-    const size_t have = (size_t)std::min<uint64_t>(count, capacity);
-    std::vector<msspe_edge_dev> raw(have);
-    if (have) TRY_OR_CLEAN2(hipMemcpy(raw.data(), d_edges, sizeof(msspe_edge_dev) * have, hipMemcpyDeviceToHost));
-    cleanup();
-#undef TRY_OR_CLEAN2
-    for (auto &e : raw) e.b -= (uint32_t)col_base;   // pool index -> column index
-    // the kernels append in no particular order
-    return emit_sorted_edges(ctx, raw, count, capacity, edges, end);
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (int rc = check_list_overrun(ctx)) return rc;
+    HIP_TRY(ctx, hipMemcpy(count_out, d_count, sizeof *count_out, hipMemcpyDeviceToHost));
+    raw.resize((size_t)std::min<uint64_t>(*count_out, capacity));
+    if (!raw.empty())
+        HIP_TRY(ctx, hipMemcpy(raw.data(), d_edges, sizeof(msspe_edge_dev) * raw.size(), hipMemcpyDeviceToHost));
+    return MSSPE_OK;
 }
 
-}  // namespace
+// Host edge lists over the same layout as cross_dimer_host (the block's sinks are not used): edge b = column index
+// (pool index - col0).  end: the END screen's edges (emit_sorted_edges).
+int cross_dimer_edges_host(msspe_ctx *ctx, const std::vector<uint64_t> &packed, const ScreenBlock &host,
+                           const msspe_chem *chem, float threshold, msspe_edge *edges, uint64_t capacity,
+                           uint64_t *count_out, bool end)
+{
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    DevBuf<uint64_t> d_pool, d_count;
+    DevBuf<msspe_edge_dev> d_edges;
+    const size_t n = packed.size();
+    HIP_TRY(ctx, d_pool.alloc(n));
+    HIP_TRY(ctx, hipMemcpy(d_pool, packed.data(), sizeof(uint64_t) * n, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, d_count.alloc(1));
+    if (capacity) HIP_TRY(ctx, d_edges.alloc((size_t)capacity));
+    HIP_TRY(ctx, hipMemsetAsync(d_count, 0, sizeof(uint64_t), ctx->stream));
+    int rc = cross_dimer_screen(ctx, screen_block(d_pool, (int)n, host.k, host.k2, 0, host.row1, host.col0, host.col1,
+                                                  edge_sinks(nullptr, d_edges, d_count, capacity)),
+                                chem, threshold, end);
+    if (rc) return rc;
+    std::vector<msspe_edge_dev> raw;
+    if ((rc = fetch_edges(ctx, d_count, d_edges, capacity, count_out, raw))) return rc;
+    for (auto &e : raw) e.b -= (uint32_t)host.col0;   // pool index -> column index
+    // the kernels append in no particular order
+    return emit_sorted_edges(ctx, raw, *count_out, capacity, edges, end);
+}
 
-extern "C" {
+// The ASCII forms of the screens: what msspe_cross_dimer and msspe_cross_dimer_end (end) share, and so on.
+// out: the caller's host buffers.
+int cross_dimer_ascii(msspe_ctx *ctx, const char *pool_ascii, int n, int k, const msspe_chem *chem, float threshold,
+                      const PairSinks &out, bool end)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!pool_ascii || !chem || n < 0) return fail(ctx, MSSPE_ERR_ARG, "null pool/chemistry");
+    if (n == 0) return MSSPE_OK;
+    std::vector<uint64_t> packed;
+    if (int rc = pack_pool(ctx, pool_ascii, n, k, packed)) return rc;
+    return cross_dimer_host(ctx, packed, screen_block(nullptr, n, k, k, 0, n, 0, n, out), chem, threshold, end);
+}
 
-int msspe_cross_dimer_edges(msspe_ctx *ctx, const char *pool_ascii, int n, int k, const msspe_chem *chem,
-                            float dg_threshold, msspe_edge *edges, uint64_t capacity, uint64_t *count_out)
+int cross_dimer_edges_ascii(msspe_ctx *ctx, const char *pool_ascii, int n, int k, const msspe_chem *chem,
+                            float threshold, msspe_edge *edges, uint64_t capacity, uint64_t *count_out, bool end)
 {
     if (!ctx) return MSSPE_ERR_ARG;
     if (!pool_ascii || !chem || !count_out || n < 0 || (capacity && !edges))
         return fail(ctx, MSSPE_ERR_ARG, "null pool/chemistry/count, or a capacity without a buffer");
     *count_out = 0;
     if (n == 0) return MSSPE_OK;
-    std::vector<uint64_t> packed((size_t)n);
-    int rc = msspe_pack_oligos(pool_ascii, n, k, packed.data());
-    if (rc) return fail(ctx, rc, rc == MSSPE_ERR_K ? "oligo length must be 1..32"
-                                                   : "pool holds characters other than ACGT");
-    return cross_dimer_edges_host(ctx, packed, n, k, 0, n, k, chem, dg_threshold, edges, capacity, count_out);
+    std::vector<uint64_t> packed;
+    if (int rc = pack_pool(ctx, pool_ascii, n, k, packed)) return rc;
+    return cross_dimer_edges_host(ctx, packed, screen_block(nullptr, n, k, k, 0, n, 0, n, PairSinks{}), chem, threshold,
+                                  edges, capacity, count_out, end);
+}
+
+// ab: rows [0, n_a) of k_a bases against columns [0, n_b) of k_b bases, as cross_dimer_ab_impl takes them
+int cross_dimer_ab_ascii(msspe_ctx *ctx, const char *a_ascii, int n_a, const char *b_ascii, int n_b,
+                         const ScreenBlock &ab, const msspe_chem *chem, float threshold, bool end)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!chem || n_a < 0 || n_b < 0 || (n_a && !a_ascii) || (n_b && !b_ascii))
+        return fail(ctx, MSSPE_ERR_ARG, "null pool/chemistry");
+    std::vector<uint64_t> packed;
+    if (int rc = pack_ab(ctx, a_ascii, n_a, ab.k, b_ascii, n_b, ab.k2, packed)) return rc;
+    if (n_a == 0) return MSSPE_OK;
+    if (n_b == 0) {   // no columns: no conflicts
+        if (ab.sinks.row_conflicts) std::fill(ab.sinks.row_conflicts, ab.sinks.row_conflicts + n_a, 0u);
+        return MSSPE_OK;
+    }
+    return cross_dimer_host(ctx, packed, screen_block(nullptr, n_a + n_b, ab.k, ab.k2, 0, n_a, n_a, n_a + n_b, ab.sinks),
+                            chem, threshold, end);
+}
+
+}  // namespace
+
+extern "C" {
+
+int msspe_cross_dimer(msspe_ctx *ctx, const char *pool_ascii, int n, int k,
+                      const msspe_chem *chem, float dg_threshold, uint32_t *row_conflicts,
+                      uint64_t *bitmap, double *dg, double *tm)
+{
+    return cross_dimer_ascii(ctx, pool_ascii, n, k, chem, dg_threshold, plane_sinks(row_conflicts, bitmap, dg, tm), false);
+}
+
+int msspe_cross_dimer_edges(msspe_ctx *ctx, const char *pool_ascii, int n, int k, const msspe_chem *chem,
+                            float dg_threshold, msspe_edge *edges, uint64_t capacity, uint64_t *count_out)
+{
+    return cross_dimer_edges_ascii(ctx, pool_ascii, n, k, chem, dg_threshold, edges, capacity, count_out, false);
 }
 
 int msspe_cross_dimer_ab_dev(msspe_ctx *ctx, const uint64_t *d_a, int n_a, int k_a, const uint64_t *d_b, int n_b,
@@ -1406,8 +1479,10 @@ int msspe_cross_dimer_ab_dev(msspe_ctx *ctx, const uint64_t *d_a, int n_a, int k
                              int col1, uint32_t *d_row_conflicts, uint64_t *d_bitmap, double *d_dg, double *d_tm)
 {
     if (!ctx) return MSSPE_ERR_ARG;
-    return cross_dimer_ab_impl(ctx, d_a, n_a, k_a, d_b, n_b, k_b, chem, dg_threshold, row0, row1, col0, col1,
-                               d_row_conflicts, d_bitmap, d_dg, d_tm, nullptr, nullptr, 0);
+    return cross_dimer_ab_impl(ctx, d_a, n_a, d_b, n_b,
+                               screen_block(nullptr, 0, k_a, k_b, row0, row1, col0, col1,
+                                            plane_sinks(d_row_conflicts, d_bitmap, d_dg, d_tm)),
+                               chem, dg_threshold, false);
 }
 
 int msspe_cross_dimer_ab_edges_dev(msspe_ctx *ctx, const uint64_t *d_a, int n_a, int k_a, const uint64_t *d_b,
@@ -1419,30 +1494,19 @@ int msspe_cross_dimer_ab_edges_dev(msspe_ctx *ctx, const uint64_t *d_a, int n_a,
     if (!d_count || (capacity && !d_edges)) return fail(ctx, MSSPE_ERR_ARG, "edge list: null count or buffer");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipMemsetAsync(d_count, 0, sizeof(uint64_t), ctx->stream));
-    return cross_dimer_ab_impl(ctx, d_a, n_a, k_a, d_b, n_b, k_b, chem, dg_threshold, row0, row1, col0, col1,
-                               d_row_conflicts, nullptr, nullptr, nullptr, reinterpret_cast<EdgeRecord *>(d_edges),
-                               reinterpret_cast<unsigned long long *>(d_count), capacity);
+    return cross_dimer_ab_impl(ctx, d_a, n_a, d_b, n_b,
+                               screen_block(nullptr, 0, k_a, k_b, row0, row1, col0, col1,
+                                            edge_sinks(d_row_conflicts, d_edges, d_count, capacity)),
+                               chem, dg_threshold, false);
 }
 
 int msspe_cross_dimer_ab(msspe_ctx *ctx, const char *a_ascii, int n_a, int k_a, const char *b_ascii, int n_b, int k_b,
                          const msspe_chem *chem, float dg_threshold, uint32_t *row_conflicts, uint64_t *bitmap,
                          double *dg, double *tm)
 {
-    if (!ctx) return MSSPE_ERR_ARG;
-    if (!chem || n_a < 0 || n_b < 0 || (n_a && !a_ascii) || (n_b && !b_ascii))
-        return fail(ctx, MSSPE_ERR_ARG, "null pool/chemistry");
-    if (k_a < 2 || k_a > 32 || k_b < 2 || k_b > 32) return fail(ctx, MSSPE_ERR_K, "oligo length must be 2..32");
-    if ((long)n_a + (long)n_b > (long)INT32_MAX) return fail(ctx, MSSPE_ERR_ARG, "pools too large");
-    std::vector<uint64_t> packed((size_t)n_a + (size_t)n_b);
-    if (msspe_pack_oligos(a_ascii ? a_ascii : "", n_a, k_a, packed.data()) ||
-        msspe_pack_oligos(b_ascii ? b_ascii : "", n_b, k_b, packed.data() + n_a))
-        return fail(ctx, MSSPE_ERR_ARG, "pool holds characters other than ACGT");
-    if (n_a == 0) return MSSPE_OK;
-    if (n_b == 0) {   // no columns: no conflicts
-        if (row_conflicts) std::fill(row_conflicts, row_conflicts + n_a, 0u);
-        return MSSPE_OK;
-    }
-    return cross_dimer_host(ctx, packed, n_a, k_a, n_a, n_b, k_b, chem, dg_threshold, row_conflicts, bitmap, dg, tm);
+    return cross_dimer_ab_ascii(ctx, a_ascii, n_a, b_ascii, n_b,
+                                screen_block(nullptr, 0, k_a, k_b, 0, n_a, 0, n_b, plane_sinks(row_conflicts, bitmap, dg, tm)),
+                                chem, dg_threshold, false);
 }
 
 int msspe_cross_dimer_ab_edges(msspe_ctx *ctx, const char *a_ascii, int n_a, int k_a, const char *b_ascii, int n_b,
@@ -1453,45 +1517,25 @@ int msspe_cross_dimer_ab_edges(msspe_ctx *ctx, const char *a_ascii, int n_a, int
     if (!chem || !count_out || n_a < 0 || n_b < 0 || (n_a && !a_ascii) || (n_b && !b_ascii) || (capacity && !edges))
         return fail(ctx, MSSPE_ERR_ARG, "null pool/chemistry/count, or a capacity without a buffer");
     *count_out = 0;
-    if (k_a < 2 || k_a > 32 || k_b < 2 || k_b > 32) return fail(ctx, MSSPE_ERR_K, "oligo length must be 2..32");
-    if ((long)n_a + (long)n_b > (long)INT32_MAX) return fail(ctx, MSSPE_ERR_ARG, "pools too large");
-    std::vector<uint64_t> packed((size_t)n_a + (size_t)n_b);
-    if (msspe_pack_oligos(a_ascii ? a_ascii : "", n_a, k_a, packed.data()) ||
-        msspe_pack_oligos(b_ascii ? b_ascii : "", n_b, k_b, packed.data() + n_a))
-        return fail(ctx, MSSPE_ERR_ARG, "pool holds characters other than ACGT");
+    std::vector<uint64_t> packed;
+    if (int rc = pack_ab(ctx, a_ascii, n_a, k_a, b_ascii, n_b, k_b, packed)) return rc;
     if (n_a == 0 || n_b == 0) return MSSPE_OK;
-    return cross_dimer_edges_host(ctx, packed, n_a, k_a, n_a, n_b, k_b, chem, dg_threshold, edges, capacity,
-                                  count_out);
+    return cross_dimer_edges_host(ctx, packed, screen_block(nullptr, n_a + n_b, k_a, k_b, 0, n_a, n_a, n_a + n_b, PairSinks{}),
+                                  chem, dg_threshold, edges, capacity, count_out, false);
 }
 
 int msspe_cross_dimer_end(msspe_ctx *ctx, const char *pool_ascii, int n, int k, const msspe_chem *chem,
                           float tm_threshold, uint32_t *row_conflicts, uint64_t *bitmap, double *dg, double *tm)
 {
-    if (!ctx) return MSSPE_ERR_ARG;
-    if (!pool_ascii || !chem || n < 0) return fail(ctx, MSSPE_ERR_ARG, "null pool/chemistry");
-    if (n == 0) return MSSPE_OK;
-    std::vector<uint64_t> packed((size_t)n);
-    int rc = msspe_pack_oligos(pool_ascii, n, k, packed.data());
-    if (rc) return fail(ctx, rc, rc == MSSPE_ERR_K ? "oligo length must be 1..32"
-                                                   : "pool holds characters other than ACGT");
-    return cross_dimer_host(ctx, packed, n, k, 0, n, k, chem, tm_threshold, row_conflicts, bitmap, dg, tm, true);
+    return cross_dimer_ascii(ctx, pool_ascii, n, k, chem, tm_threshold, plane_sinks(row_conflicts, bitmap, dg, tm), true);
 }
 
 int msspe_cross_dimer_end_edges(msspe_ctx *ctx, const char *pool_ascii, int n, int k, const msspe_chem *chem,
                                 float tm_threshold, msspe_end_edge *edges, uint64_t capacity, uint64_t *count_out)
 {
-    if (!ctx) return MSSPE_ERR_ARG;
-    if (!pool_ascii || !chem || !count_out || n < 0 || (capacity && !edges))
-        return fail(ctx, MSSPE_ERR_ARG, "null pool/chemistry/count, or a capacity without a buffer");
-    *count_out = 0;
-    if (n == 0) return MSSPE_OK;
-    std::vector<uint64_t> packed((size_t)n);
-    int rc = msspe_pack_oligos(pool_ascii, n, k, packed.data());
-    if (rc) return fail(ctx, rc, rc == MSSPE_ERR_K ? "oligo length must be 1..32"
-                                                   : "pool holds characters other than ACGT");
     static_assert(sizeof(msspe_end_edge) == sizeof(msspe_edge), "edge record layouts differ");
-    return cross_dimer_edges_host(ctx, packed, n, k, 0, n, k, chem, tm_threshold,
-                                  reinterpret_cast<msspe_edge *>(edges), capacity, count_out, true);
+    return cross_dimer_edges_ascii(ctx, pool_ascii, n, k, chem, tm_threshold, reinterpret_cast<msspe_edge *>(edges),
+                                   capacity, count_out, true);
 }
 
 int msspe_cross_dimer_end_ab_dev(msspe_ctx *ctx, const uint64_t *d_a, int n_a, int k_a, const uint64_t *d_b, int n_b,
@@ -1499,30 +1543,19 @@ int msspe_cross_dimer_end_ab_dev(msspe_ctx *ctx, const uint64_t *d_a, int n_a, i
                                  int col1, uint32_t *d_row_conflicts, uint64_t *d_bitmap, double *d_dg, double *d_tm)
 {
     if (!ctx) return MSSPE_ERR_ARG;
-    return cross_dimer_ab_impl(ctx, d_a, n_a, k_a, d_b, n_b, k_b, chem, tm_threshold, row0, row1, col0, col1,
-                               d_row_conflicts, d_bitmap, d_dg, d_tm, nullptr, nullptr, 0, true);
+    return cross_dimer_ab_impl(ctx, d_a, n_a, d_b, n_b,
+                               screen_block(nullptr, 0, k_a, k_b, row0, row1, col0, col1,
+                                            plane_sinks(d_row_conflicts, d_bitmap, d_dg, d_tm)),
+                               chem, tm_threshold, true);
 }
 
 int msspe_cross_dimer_end_ab(msspe_ctx *ctx, const char *a_ascii, int n_a, int k_a, const char *b_ascii, int n_b,
                              int k_b, const msspe_chem *chem, float tm_threshold, uint32_t *row_conflicts,
                              uint64_t *bitmap, double *dg, double *tm)
 {
-    if (!ctx) return MSSPE_ERR_ARG;
-    if (!chem || n_a < 0 || n_b < 0 || (n_a && !a_ascii) || (n_b && !b_ascii))
-        return fail(ctx, MSSPE_ERR_ARG, "null pool/chemistry");
-    if (k_a < 2 || k_a > 32 || k_b < 2 || k_b > 32) return fail(ctx, MSSPE_ERR_K, "oligo length must be 2..32");
-    if ((long)n_a + (long)n_b > (long)INT32_MAX) return fail(ctx, MSSPE_ERR_ARG, "pools too large");
-    std::vector<uint64_t> packed((size_t)n_a + (size_t)n_b);
-    if (msspe_pack_oligos(a_ascii ? a_ascii : "", n_a, k_a, packed.data()) ||
-        msspe_pack_oligos(b_ascii ? b_ascii : "", n_b, k_b, packed.data() + n_a))
-        return fail(ctx, MSSPE_ERR_ARG, "pool holds characters other than ACGT");
-    if (n_a == 0) return MSSPE_OK;
-    if (n_b == 0) {   // no columns: no conflicts
-        if (row_conflicts) std::fill(row_conflicts, row_conflicts + n_a, 0u);
-        return MSSPE_OK;
-    }
-    return cross_dimer_host(ctx, packed, n_a, k_a, n_a, n_b, k_b, chem, tm_threshold, row_conflicts, bitmap, dg, tm,
-                            true);
+    return cross_dimer_ab_ascii(ctx, a_ascii, n_a, b_ascii, n_b,
+                                screen_block(nullptr, 0, k_a, k_b, 0, n_a, 0, n_b, plane_sinks(row_conflicts, bitmap, dg, tm)),
+                                chem, tm_threshold, true);
 }
 
 int msspe_cross_dimer_edges_mixed(msspe_ctx *ctx, const char *const *oligos, int n, const msspe_chem *chem,
@@ -1558,57 +1591,29 @@ int msspe_cross_dimer_edges_mixed(msspe_ctx *ctx, const char *const *oligos, int
     cls_off.push_back(n);
     const int n_cls = (int)cls_len.size();
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    uint64_t *d_pool = nullptr, *d_count = nullptr;
-    msspe_edge_dev *d_edges = nullptr;
-    auto cleanup = [&]() {
-        if (d_pool) (void)hipFree(d_pool);
-        if (d_count) (void)hipFree(d_count);
-        if (d_edges) (void)hipFree(d_edges);
-    };
-#define TRY_OR_CLEAN3(expr)                                        \
-    do {                                                           \
-        hipError_t e__ = (expr);                                   \
-        if (e__ != hipSuccess) {                                   \
-            cleanup();                                             \
-            return hip_fail(ctx, e__, #expr);                      \
-        }                                                          \
-    } while (0)
-    TRY_OR_CLEAN3(hipMalloc((void **)&d_pool, sizeof(uint64_t) * (size_t)n));
-    TRY_OR_CLEAN3(hipMemcpy(d_pool, packed.data(), sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice));
-    TRY_OR_CLEAN3(hipMalloc((void **)&d_count, sizeof(uint64_t)));
-    TRY_OR_CLEAN3(hipMemsetAsync(d_count, 0, sizeof(uint64_t), ctx->stream));
-    if (capacity) TRY_OR_CLEAN3(hipMalloc((void **)&d_edges, sizeof(msspe_edge_dev) * (size_t)capacity));
+    DevBuf<uint64_t> d_pool, d_count;
+    DevBuf<msspe_edge_dev> d_edges;
+    HIP_TRY(ctx, d_pool.alloc((size_t)n));
+    HIP_TRY(ctx, hipMemcpy(d_pool, packed.data(), sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, d_count.alloc(1));
+    HIP_TRY(ctx, hipMemsetAsync(d_count, 0, sizeof(uint64_t), ctx->stream));
+    if (capacity) HIP_TRY(ctx, d_edges.alloc((size_t)capacity));
     // one block per (row class, column class), all appending to one list: the blocks of one pool need no staging,
     // and an equal-length block (the diagonal) is the single-pool chain itself
+    const PairSinks sinks = edge_sinks(nullptr, d_edges, d_count, capacity);
     for (int r = 0; r < n_cls; ++r)
-        for (int c = 0; c < n_cls; ++c) {
-            const int rc = cross_dimer_impl(ctx, d_pool, n, cls_len[r], cls_len[c], chem, dg_threshold, cls_off[r],
-                                            cls_off[r + 1], cls_off[c], cls_off[c + 1], nullptr, nullptr, nullptr,
-                                            nullptr, reinterpret_cast<EdgeRecord *>(d_edges),
-                                            reinterpret_cast<unsigned long long *>(d_count), capacity);
-            if (rc) {
-                cleanup();
+        for (int c = 0; c < n_cls; ++c)
+            if (int rc = cross_dimer_impl(ctx, screen_block(d_pool, n, cls_len[r], cls_len[c], cls_off[r], cls_off[r + 1],
+                                                            cls_off[c], cls_off[c + 1], sinks),
+                                          chem, dg_threshold))
                 return rc;
-            }
-        }
-    TRY_OR_CLEAN3(hipStreamSynchronize(ctx->stream));
-    if (int rc = check_list_overrun(ctx)) {
-        cleanup();
-        return rc;
-    }
-    uint64_t count = 0;
-    TRY_OR_CLEAN3(hipMemcpy(&count, d_count, sizeof count, hipMemcpyDeviceToHost));
-    *count_out = count;
-    const size_t have = (size_t)std::min<uint64_t>(count, capacity);
-    std::vector<msspe_edge_dev> raw(have);
-    if (have) TRY_OR_CLEAN3(hipMemcpy(raw.data(), d_edges, sizeof(msspe_edge_dev) * have, hipMemcpyDeviceToHost));
-    cleanup();
-#undef TRY_OR_CLEAN3
+    std::vector<msspe_edge_dev> raw;
+    if (int rc = fetch_edges(ctx, d_count, d_edges, capacity, count_out, raw)) return rc;
     for (auto &e : raw) {   // pool entries -> the caller's indices
         e.a = orig[e.a];
         e.b = orig[e.b];
     }
-    return emit_sorted_edges(ctx, raw, count, capacity, edges);
+    return emit_sorted_edges(ctx, raw, *count_out, capacity, edges, false);
 }
 
 int msspe_thal_detail_pairs(msspe_ctx *ctx, const char *a_ascii, const char *b_ascii, int n, int k,
@@ -1630,42 +1635,22 @@ int msspe_thal_detail_pairs(msspe_ctx *ctx, const char *a_ascii, const char *b_a
     ChemEntry *ce = nullptr;
     if ((rc = chem_entry(ctx, *chem, -9000.0f, &ce))) return rc;
     if ((rc = ensure_workspace(ctx, (size_t)k * (size_t)k))) return rc;
-    uint64_t *d_pool = nullptr;
-    uint2 *d_list = nullptr;
-    ThalDetail *d_det = nullptr;
-    auto cleanup = [&]() {
-        if (d_pool) (void)hipFree(d_pool);
-        if (d_list) (void)hipFree(d_list);
-        if (d_det) (void)hipFree(d_det);
-    };
+    DevBuf<uint64_t> d_pool;
+    DevBuf<uint2> d_list;
+    DevBuf<ThalDetail> d_det;
     hipError_t e;
-    if ((e = hipMalloc((void **)&d_pool, sizeof(uint64_t) * 2 * (size_t)n)) != hipSuccess ||
-        (e = hipMalloc((void **)&d_list, sizeof(uint2) * (size_t)n)) != hipSuccess ||
-        (e = hipMalloc((void **)&d_det, sizeof(ThalDetail) * (size_t)n)) != hipSuccess ||
+    if ((e = d_pool.alloc(2 * (size_t)n)) != hipSuccess || (e = d_list.alloc((size_t)n)) != hipSuccess ||
+        (e = d_det.alloc((size_t)n)) != hipSuccess ||
         (e = hipMemcpy(d_pool, packed.data(), sizeof(uint64_t) * 2 * (size_t)n, hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(d_list, list.data(), sizeof(uint2) * (size_t)n, hipMemcpyHostToDevice)) != hipSuccess) {
-        cleanup();
+        (e = hipMemcpy(d_list, list.data(), sizeof(uint2) * (size_t)n, hipMemcpyHostToDevice)) != hipSuccess)
         return hip_fail(ctx, e, "thal detail buffers");
-    }
-    GenericDimerArgs g;
-    std::memset(&g, 0, sizeof g);
-    g.pt = ce->d_pt;
-    g.c[0] = ce->c[0];
-    g.c[1] = ce->c[1];
-    g.pool = d_pool;
-    g.k = k;
-    g.k2 = k;
-    g.mode = mode;
+    GenericDimerArgs g = dimer_args(ctx, ce, screen_block(d_pool, 2 * n, k, k, 0, 0, 0, 0, PairSinks{}), mode);
     g.list = d_list;
     g.n_work = n;
     g.detail = d_det;
-    g.wsS = ctx->wsS;
-    g.wsH = ctx->wsH;
-    g.ws_lanes = kGenericLanes;
     e = launch_dimer_generic(g, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e == hipSuccess) e = hipMemcpy(out, d_det, sizeof(ThalDetail) * (size_t)n, hipMemcpyDeviceToHost);
-    cleanup();
     if (e != hipSuccess) return hip_fail(ctx, e, "thal detail");
     return MSSPE_OK;
 }
@@ -1697,10 +1682,9 @@ int msspe_oligo_stats_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k,
     // single oligo's.  Large pools: one LANE per oligo through the f64 register-table kernels over the list of (i, i)
     // (thal_pairs.hip, 56 then 72 slots), the wave kernel behind them for larger tables.  The dense kernel, one lane
     // per oligo over a global workspace, takes what is left (self-complementary oligos: another RC constant).
-    const bool wave_ok = !ctx->opt.force_generic && k <= ce->wave_max_k && ctx->opt.wave_kernel;
-    const bool lane_ok = wave_ok && n >= ctx->opt.self_lane_from && k <= pairs_fast_max_k() && ce->fast_ok &&
-                         chem->max_loop >= 2 * k - 4;
-    if (wave_ok && (d_self_any || d_self_end)) {
+    const bool wave = wave_ok(ctx, ce, k);
+    const bool lane_ok = wave && n >= ctx->opt.self_lane_from && reg_tables_ok(ctx, ce, k);
+    if (wave && (d_self_any || d_self_end)) {
         if ((rc = ensure_overflow(ctx, n))) return rc;
         if (ctx->list_cap < n) return fail(ctx, MSSPE_ERR_NOMEM, "stage B: no memory for the work lists");
         HIP_TRY(ctx, hipMemsetAsync(ctx->ovf_count, 0, 8 * sizeof(uint32_t), ctx->stream));
@@ -1716,31 +1700,21 @@ int msspe_oligo_stats_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k,
                                           ctx->ovf_list2, left, (uint32_t)ctx->list_cap, ctx->ovf_count + 7, ctx->stream));
         }
     }
+    const ScreenBlock self = screen_block(d_pool, n, k, k, 0, 0, 0, 0, PairSinks{});   // self mode: no pair sinks
     for (int pass = 0; pass < 2; ++pass) {
         double *dst = pass == 0 ? d_self_any : d_self_end;
         if (!dst) continue;
-        GenericDimerArgs g;
-        std::memset(&g, 0, sizeof g);
-        g.pt = ce->d_pt;
-        g.c[0] = ce->c[0];
-        g.c[1] = ce->c[1];
-        g.pool = d_pool;
-        g.k = k;
-        g.k2 = k;
-        g.mode = pass == 0 ? 1 : 2;
+        GenericDimerArgs g = dimer_args(ctx, ce, self, pass == 0 ? kModeAny : kModeEnd1);
         g.n_work = n;
         g.self_mode = 1;
         g.self_t = dst;
-        g.wsS = ctx->wsS;
-        g.wsH = ctx->wsH;
-        g.ws_lanes = kGenericLanes;
-        if (wave_ok) {
+        if (wave) {
             g.list = ctx->ovf_list2;
             g.list_count = ctx->ovf_count + 3;
         }
         HIP_TRY(ctx, launch_dimer_generic(g, ctx->stream));
     }
-    if (wave_ok && (d_self_any || d_self_end)) HIP_TRY(ctx, hipMemsetAsync(ctx->ovf_count, 0, 8 * sizeof(uint32_t), ctx->stream));
+    if (wave && (d_self_any || d_self_end)) HIP_TRY(ctx, hipMemsetAsync(ctx->ovf_count, 0, 8 * sizeof(uint32_t), ctx->stream));
     if (d_hairpin) {
         HairpinArgs h;
         h.tb = ctx->d_tb;
@@ -1772,10 +1746,9 @@ int msspe_oligo_stats(msspe_ctx *ctx, const char *pool_ascii, int n, int k,
     if (!ctx) return MSSPE_ERR_ARG;
     if (!pool_ascii || !chem || n < 0) return fail(ctx, MSSPE_ERR_ARG, "null pool/chemistry");
     if (n == 0) return MSSPE_OK;
-    std::vector<uint64_t> packed((size_t)n);
-    int rc = msspe_pack_oligos(pool_ascii, n, k, packed.data());
-    if (rc) return fail(ctx, rc, rc == MSSPE_ERR_K ? "oligo length must be 1..32"
-                                                   : "pool holds characters other than ACGT");
+    std::vector<uint64_t> packed;
+    int rc = pack_pool(ctx, pool_ascii, n, k, packed);
+    if (rc) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     uint64_t *d_pool = nullptr;
     double *d_out = nullptr;
@@ -2352,77 +2325,25 @@ int ensure_site_work(msspe_ctx *ctx, size_t cap, int n)
 }
 
 // thal of the pairs list[0 .. count) -- (primer, n + site index) into the site pool -- by list index into the work
-// list's dg / t planes: the END screen's chain over an explicit list.  *ovf_count[0] == count (k_site_oligos).
+// list's dg / t planes: the register-table list stages where they may take the length and chemistry, the wave list
+// stage, the dense kernel, over the caller's list as list 0 (ListChain).  *ovf_count[0] == count (k_site_oligos).
+// The hand-over statistics are the cross-dimer calls': this chain does not feed them.
 int score_site_pairs(msspe_ctx *ctx, ChemEntry *ce, bool end1, int n, int k, uint2 *list, uint32_t count)
 {
     auto &w = ctx->site_work;
-    const long kListCap = ctx->list_cap;
-    PairSinks sinks;
-    std::memset(&sinks, 0, sizeof sinks);
-    sinks.dg = w.dg;
-    sinks.tm = w.t;
-    sinks.row0 = 0;
-    sinks.col0 = n;   // (row - row0) * ncols + (col - col0) = the site index
-    sinks.ncols = 0;
-    GenericDimerArgs g;
-    std::memset(&g, 0, sizeof g);
-    g.pt = ce->d_pt;
-    g.c[0] = ce->c[0];
-    g.c[1] = ce->c[1];
-    g.pool = w.pool;
-    g.k = k;
-    g.k2 = k;
-    g.mode = end1 ? kModeEnd1 : kModeAny;
-    g.sinks = sinks;
-    g.wsS = ctx->wsS;
-    g.wsH = ctx->wsH;
-    g.ws_lanes = kGenericLanes;
-    PairKernelArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.ft = ce->d_ft;
-    a.c = ce->c[0];
-    a.pool = w.pool;
-    a.n = n;
-    a.k = k;
-    a.k2 = k;
-    a.sinks = sinks;
-    a.overflow_cap = (uint32_t)kListCap;
-    a.work_counter = ctx->ovf_count + 7;
-    const bool reg = !ctx->opt.force_generic && k <= pairs_fast_max_k() && ce->fast_ok &&
-                     ce->chem.max_loop >= 2 * k - 4;   // the register-table kernels have no loop-size cut-off
-    const bool wave_ok = !ctx->opt.force_generic && k <= ce->wave_max_k && ctx->opt.wave_kernel;
-    const uint2 *in_list = list;
-    uint2 *out_list = ctx->ovf_list;
-    int in_c = 0, out_c = 1;
-    auto advance = [&]() {
-        in_list = out_list;
-        out_list = out_list == ctx->ovf_list ? ctx->ovf_list2 : ctx->ovf_list;
-        in_c = out_c;
-        out_c = out_c + 1;
-    };
+    // a block without rows or columns whose columns start at n: (row - row0) * ncols + (col - col0) = the site index
+    const ScreenBlock b = screen_block(w.pool, n, k, k, 0, 0, n, n, plane_sinks(nullptr, nullptr, w.dg, w.t));
+    GenericDimerArgs g = dimer_args(ctx, ce, b, end1 ? kModeEnd1 : kModeAny);
+    PairKernelArgs a = pair_args(ctx, ce, b);
+    StageList route;
+    if (reg_tables_ok(ctx, ce, k)) {
+        route.add(ListStage::MainList);
+        route.add(ListStage::Wide);
+    }
+    if (wave_ok(ctx, ce, k)) route.add(ListStage::Wave);
+    route.add(ListStage::Dense);
     HIP_TRY(ctx, hipMemsetAsync(ctx->ovf_count + 1, 0, 7 * sizeof(uint32_t), ctx->stream));
-    if (reg) {
-        a.overflow_list = out_list;
-        a.overflow_count = ctx->ovf_count + out_c;
-        HIP_TRY(ctx, launch_pairs_main_list(a, in_list, ctx->ovf_count + in_c, ctx->stream, end1));
-        advance();
-        a.overflow_list = out_list;
-        a.overflow_count = ctx->ovf_count + out_c;
-        HIP_TRY(ctx, launch_pairs_wide(a, in_list, ctx->ovf_count + in_c, ctx->stream, end1));
-        advance();
-    }
-    if (wave_ok) {
-        a.overflow_list = out_list;
-        a.overflow_count = ctx->ovf_count + out_c;
-        HIP_TRY(ctx, launch_pairs_wave(a, ce->d_st, in_list, ctx->ovf_count + in_c, ctx->stream, end1));
-        advance();
-    }
-    g.list = in_list;
-    g.list_count = ctx->ovf_count + in_c;
-    g.n_work = in_c == 0 ? (long)count : kListCap;
-    HIP_TRY(ctx, launch_dimer_generic(g, ctx->stream, end1));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->ovf_count, 0, 8 * sizeof(uint32_t), ctx->stream));
-    return MSSPE_OK;
+    return ListChain(ctx, ce, end1, list, (long)count).run(route, a, g, false);
 }
 
 }  // namespace
