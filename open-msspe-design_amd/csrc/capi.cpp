@@ -505,7 +505,8 @@ struct ListChain {
         a.overflow_cap = (uint32_t)cap;
         switch (s) {
         case ListStage::IntList:
-            HIP_TRY(ctx, launch_pairs_int_list(a, ce->d_it, in_list, in_count, ctx->d_reasons, ctx->n_cu, ctx->stream));
+            HIP_TRY(ctx, launch_pairs_int_list(a, ce->d_it, in_list, in_count, ctx->d_reasons, ctx->n_cu, ctx->stream,
+                                           ce->row_ok));
             break;
         case ListStage::SplitList:
             HIP_TRY(ctx, launch_pairs_split_list(a, ce->d_st, in_list, in_count, ctx->n_cu, ctx->stream));

@@ -136,8 +136,10 @@ bool pairs_row_tables_ok(const IntTables &it);   // host: may this chemistry run
 hipError_t pairs_row_lds_reads_zero(hipStream_t stream, int n_cu, bool *ok);   // does this device read 0 beyond a block's LDS allocation?
 // List mode of the integer stage: retries the pairs of in_list that carry no "needs f64" mark (bit
 // 31 of .x) with a 64-slot table in lanes sorted by table size; everything else passes through.
+// cells_reachable: pairs_row_tables_ok(*it) -- the chemistry may run the cheaper predecessor visit.
 hipError_t launch_pairs_int_list(const PairKernelArgs &a, const IntTables *it, const uint2 *in_list,
-                                 const uint32_t *in_count, unsigned long long *reasons, int n_cu, hipStream_t stream);
+                                 const uint32_t *in_count, unsigned long long *reasons, int n_cu, hipStream_t stream,
+                                 bool cells_reachable);
 // Long oligos (17 .. SplitTables::max_k bases, thal_pairs_split.hip): exact-integer first stage with
 // a pair's table split over 2, 4 or 8 lanes; same contract as launch_pairs_int (a.ft is not used).
 hipError_t launch_pairs_split(const PairKernelArgs &a, const SplitTables *st, unsigned long long *reasons,

@@ -30,7 +30,9 @@
 //                     slots.  Lanes whose table is too large, or far above their wave's, are
 //                     handed on (lock-step work ~ slots^2)
 //   k_pairs_int_list  list mode: the handed-on pairs without a "needs f64" mark, 64 slots, batches
-//                     counting-sorted by table size in LDS so that a wave's lanes are alike
+//                     counting-sorted by table size in LDS so that a wave's lanes are alike; with its own
+//                     slot-word layout and LDS image of the loop table (FAST: 8 vector instructions per far
+//                     visit instead of 18) for chemistries whose cell values are all reachable ones
 #include "int_core.hpp"
 
 namespace msspe {
@@ -41,7 +43,7 @@ namespace {
 template <int NS, int THREADS, int TROWS>
 struct SharedI {
     static constexpr int kThreads = THREADS, kRows = TROWS;
-    int T[TROWS * 64];
+    int T[TROWS * 64 + 4];              // + the "not available" entry the list mode's clamp lands on
     Lds F;                              // f64 S + int H (replay, end terms)
     int g[FastTables::kCount];
     double cq[100];                     // 620300 * (init_S + rS + RC) per right-end context (maxTM)
@@ -58,10 +60,31 @@ struct ICell {
 };
 
 
+// Two layouts of the slot word (FAST: the list mode's, see "the list mode's visit" below):
+//   general   h << 16 | po << 10 | im1 << 4 | jm1          (bits 8, 9 zero)
+//   FAST      h << 16 | jm1 << 12 | im1 << 8 | po << 2     (bits 0, 1 zero)
 // the f64 kernel's word (h << 14 | po << 8 | im1 << 4 | jm1) of pair_core.hpp's cand_* helpers
+template <bool FAST>
 __device__ __forceinline__ int core_word(int W)
 {
-    return ((W >> 16) << 14) | ((W >> 2) & 0x3f00) | (W & 0xff);
+    if constexpr (FAST) return ((W >> 16) << 14) | ((W & 0xfc) << 6) | ((W >> 4) & 0xf0) | ((W >> 12) & 15);
+    else return ((W >> 16) << 14) | ((W >> 2) & 0x3f00) | (W & 0xff);
+}
+// the byte that names a cell (what a predecessor byte holds and the walk back compares; 0xff: none)
+template <bool FAST>
+__device__ __forceinline__ int word_cell(int W)
+{
+    return FAST ? ((W >> 8) & 0xff) : (W & 0xff);
+}
+template <bool FAST>
+__device__ __forceinline__ int word_im1(int W)
+{
+    return FAST ? ((W >> 8) & 15) : ((W >> 4) & 15);
+}
+template <bool FAST>
+__device__ __forceinline__ int word_jm1(int W)
+{
+    return FAST ? ((W >> 12) & 15) : (W & 15);
 }
 
 // One predecessor slot against cell c.
@@ -168,6 +191,104 @@ __device__ __forceinline__ void scan_fill_int(MSSPE_TAB_PARAMS, int upto, int fa
 }
 
 
+// ---- The list mode's visit (FAST).  Same recurrence, same values; what a visit costs is cut by three things the
+//      row kernel (thal_pairs_row.hip) does and that do not need the lanes to share oligo 1:
+//  * the table address is ONE subtraction of the slot word's low half from a per-cell minuend, clamped by one
+//    unsigned min.  The coordinates sit column first (jm1 << 12 | im1 << 8) over po << 2, the minuend is
+//    ((jm1 - 1) << 12) + ((im1 - 1) << 8) + 252, so the difference is (16 l2 + l1) << 8 | (63 - po) << 2: the copy of the
+//    table in LDS is laid out [16 l2 + l1][63 - po].  A predecessor right of the cell (l2 < 0) makes the whole
+//    difference negative, i.e. huge, and the clamp puts it on the "not available" entry behind the table; one of
+//    the cell's own row (l1 = -1: slots are filled in row-major order, so there is nothing below) borrows into a
+//    row with l1 = 15, which holds "not available" (or, with l2 = 0, goes negative as well).  No compare, no select.
+//  * a bulge needs the cell's base, not the predecessor's neighbours, in its column -- but the predecessor's word
+//    holds it: with l2 = 0 its right neighbour on oligo 2 pairs with the cell's base (a_c = 3 - n2), with l1 = 0
+//    its 3' neighbour on oligo 1 IS the cell's base (a_c = n1).  The LDS copy of those rows is filled accordingly,
+//    and the column select of the general visit is gone.
+//  * the running minimum is one v_min_f64 on (candidate : slot word); all values carry + kFastD so that the
+//    patterns are positive normal doubles ordered like the values, and "not available" is kFastU, not kBig.
+//    This needs every PREDECESSOR value to be a reachable one (|G| < kReach): the launch takes this visit only
+//    for chemistries whose end and stacked-pair terms all exist (pairs_row_tables_ok), like the row kernel.
+constexpr int kFastD = 350000000;
+constexpr int kFastU = 700000000;
+constexpr int kFastInit = kFastD + IntTables::kReach + 50000000;   // above every valid candidate, below every void one
+static_assert(kFastD - IntTables::kReach >= (1 << 20), "smallest candidate must be a normal double's high word");
+static_assert((long long)kFastU + kFastU + IntTables::kReach + kFastD <= 0x7fefffffLL,
+              "largest candidate (void loop + void cell side + reachable predecessor) must stay a finite double");
+static_assert(kFastU + kFastD - IntTables::kReach > kFastInit && kFastInit - kFastD > IntTables::kReach,
+              "a candidate that holds a void term stays above the starting minimum, which no cell can take");
+static_assert(IntTables::kReach < kFastU && kFastU < IntTables::kValid + IntTables::kReach && kFastU <= IntTables::kBig,
+              "min(term, kFastU) turns kBig into kFastU and leaves every available term alone");
+constexpr unsigned kFastClamp = IntTables::kRows * 256u;   // byte offset of the "not available" entry behind the table
+constexpr int kEmptyWF = 0xff00;                           // coordinates (15, 15) in the FAST layout
+static_assert(IntTables::kRows == 14 * 16 + 14 + 1, "rows 16 l2 + l1 with l1, l2 <= 14 are the table's own row count");
+
+struct FCell {
+    unsigned C;    // ((jm1 - 1) << 12) + ((im1 - 1) << 8) + 252
+    int yTS, yMM;  // cell-side mismatch term of interior / 1x1 loops (G units; not available: kFastU)
+};
+
+// running minimum: GW = (candidate value + kFastD : slot word) as one double, G2 = second smallest value
+struct FBest {
+    double GW;
+    int G2;
+};
+
+__device__ __forceinline__ void take_min_fast(FBest &b, int cand, int Wp)
+{
+    b.G2 = med3_i32(__double2hiint(b.GW), b.G2, cand);   // second smallest so far
+    const double cd = __hiloint2double(cand, Wp);
+    // (asm: fmin() would canonicalise its operands first; both are normal numbers here by construction, and
+    //  idle lanes, whose patterns may be anything, publish nothing that is read)
+    asm("v_min_f64 %0, %1, %2" : "=v"(b.GW) : "v"(b.GW), "v"(cd));
+}
+
+__device__ __forceinline__ unsigned fast_index(unsigned C, int Wp)
+{
+    return min(C - ((unsigned)Wp & 0xffffu), kFastClamp);
+}
+
+// All earlier slots as predecessors of the cell, kC at a time (scan_fill_int's structure).
+template <int NS, int PC = 0>
+__device__ __forceinline__ void scan_fill_fast(MSSPE_TAB_PARAMS, int upto, int far_upto, const char *T, const FCell &c,
+                                               FBest &best, IBest &stk, ScanMasks &m)
+{
+    if constexpr (PC * kC < NS) {
+        if (PC * kC < upto) {   // wave-uniform
+            unsigned idx[kC];
+            int t[kC];
+#pragma unroll
+            for (int e = 0; e < kC; ++e) idx[e] = fast_index(c.C, slot_of<NS>(Wa, Wb, Wc, PC * kC + e));
+#pragma unroll
+            for (int e = 0; e < kC; ++e) t[e] = *(const int *)(T + idx[e]);
+            if (PC * kC + kC <= far_upto) {   // wave-uniform: every lane has these slots >= 3 rows up (l1 >= 2)
+                asm volatile("" ::"n"(PC));   // keeps the chunks from being merged into selects
+#pragma unroll
+                for (int e = 0; e < kC; ++e) {
+                    // rows 0 .. 15 of the table are l2 = 0: a bulge, which takes no cell-side term
+                    const int y = idx[e] < 4096u ? 0 : c.yTS;
+                    take_min_fast(best, t[e] + y + slot_of<NS>(Ga, Gb, Gc, PC * kC + e), slot_of<NS>(Wa, Wb, Wc, PC * kC + e));
+                }
+            } else {
+                asm volatile("" ::"n"(PC + 64));
+#pragma unroll
+                for (int e = 0; e < kC; ++e) {
+                    const int Gp = slot_of<NS>(Ga, Gb, Gc, PC * kC + e), Wp = slot_of<NS>(Wa, Wb, Wc, PC * kC + e);
+                    const bool bulge = (idx[e] < 4096u) | ((idx[e] & 0xf00u) == 0u);   // l2 == 0 or l1 == 0
+                    const bool m11 = (idx[e] - 0x1100u) < 256u;                      // l1 == l2 == 1
+                    const int y = bulge ? 0 : (m11 ? c.yMM : c.yTS);
+                    take_min_fast(best, t[e] + y + Gp, Wp);
+                    const bool isstk = idx[e] < 256u;   // row 0: the cell (i-1, j-1), no loop candidate
+                    stk.G = isstk ? Gp : stk.G;
+                    stk.W = isstk ? Wp : stk.W;
+                    m.stHave |= __builtin_amdgcn_ballot_w64(isstk);
+                }
+            }
+            scan_fill_fast<NS, PC + 1>(MSSPE_TAB_ARGS, upto, far_upto, T, c, best, stk, m);
+        }
+    }
+}
+
+
 // thal ANY for the lane's pair.  n_cells == 0: idle lane.  n_cells counts every complementary cell; the
 // lane's last-row cells (the last ones of its row-major order) may lie beyond slot NS - 1: they are computed
 // and may be picked, but only cells of earlier rows are ever read back (wave_pairs sizes the table by them).
@@ -175,14 +296,15 @@ __device__ __forceinline__ void scan_fill_int(MSSPE_TAB_PARAMS, int upto, int fa
 // replaying both paths and comparing the two doubles (list mode; in matrix mode such pairs are
 // handed on, because a second walk would be paid by the whole wave) -- unless the call asks for
 // decisions only and no tied structure can reach the cut (int_core.hpp kPickMargin).
-template <int NS, bool RESOLVE, class SH>
+template <int NS, bool RESOLVE, bool FAST, class SH>
 __device__ __forceinline__ IntResult run_pair_int(SH &sh, const ThalConsts &K, const SeqPair &q,
                                                   unsigned rowmask, int n_cells, int nmax, bool decisions_only)
 {
     const Lds &F = sh.F;
-    v32i Ga = 0, Wa = kEmptyW;
-    typename TabTypes<NS>::B Gb = 0, Wb = kEmptyW;
-    typename TabTypes<NS>::C Gc = 0, Wc = kEmptyW;
+    constexpr int kEmpty = FAST ? kEmptyWF : kEmptyW;
+    v32i Ga = 0, Wa = kEmpty;
+    typename TabTypes<NS>::B Gb = 0, Wb = kEmpty;
+    typename TabTypes<NS>::C Gc = 0, Wc = kEmpty;
     int defer = 0;
     CellCtx c;
     c.rS = 0.0;
@@ -216,25 +338,41 @@ __device__ __forceinline__ IntResult run_pair_int(SH &sh, const ThalConsts &K, c
         im1 &= 15;
         jm1 &= 15;
         const CellBases b = cell_bases(q, im1, jm1, c);
-        ICell ic;
-        ic.cgeo = (im1 - 1) * 16 + (jm1 - 1);
-        ic.jm1p = jm1 - 1;
-        ic.cstk = ((im1 > 0) & (jm1 > 0)) ? ic.cgeo : 0x100;
-        ic.a16 = b.a << 4;
-        ic.yTS = sh.g[c.yTS];
-        ic.yMM = sh.g[c.yMM];
         // ---- all earlier slots as predecessors
         RBest best;
         IBest stk;
-        best.G = IntTables::kValid;
-        best.G2 = 0x7fffffff;
-        best.W = 0;
         stk.G = stk.W = 0;
         ScanMasks sm;
         sm.tie = sm.stHave = 0ull;
         const int far_upto = wave_min_64(slot < n_cells ? row_lo2 : 63);
-        scan_fill_int<NS>(MSSPE_TAB_ARGS, slot, far_upto, (const char *)sh.T, ic, best, stk, sm);
-        const bool tie = best.G2 == best.G;   // two loop candidates share the minimum
+        bool tie;   // two loop candidates share the minimum
+        if constexpr (FAST) {
+            FCell fc;
+            fc.C = (unsigned)(((jm1 - 1) << 12) + ((im1 - 1) << 8) + 252);
+            fc.yTS = min(sh.g[c.yTS], kFastU);
+            fc.yMM = min(sh.g[c.yMM], kFastU);
+            FBest fb;
+            fb.GW = __hiloint2double(kFastInit, 0);
+            fb.G2 = 0x7fffffff;
+            scan_fill_fast<NS>(MSSPE_TAB_ARGS, slot, far_upto, (const char *)sh.T, fc, fb, stk, sm);
+            tie = fb.G2 == __double2hiint(fb.GW);
+            best.G = __double2hiint(fb.GW) - kFastD;
+            best.G2 = fb.G2;
+            best.W = __double2loint(fb.GW);
+        } else {
+            ICell ic;
+            ic.cgeo = (im1 - 1) * 16 + (jm1 - 1);
+            ic.jm1p = jm1 - 1;
+            ic.cstk = ((im1 > 0) & (jm1 > 0)) ? ic.cgeo : 0x100;
+            ic.a16 = b.a << 4;
+            ic.yTS = sh.g[c.yTS];
+            ic.yMM = sh.g[c.yMM];
+            best.G = IntTables::kValid;
+            best.G2 = 0x7fffffff;
+            best.W = 0;
+            scan_fill_int<NS>(MSSPE_TAB_ARGS, slot, far_upto, (const char *)sh.T, ic, best, stk, sm);
+            tie = best.G2 == best.G;
+        }
         const bool stHave = lane_bit(sm.stHave);
         // ---- thal.c maxTM(): helix extension if it raises Tm.  T = A / B with B < 0 on both
         //      sides, so T1 > T0 <=> A1 B0 > A0 B1; 620300 B = (2000 H - G) + cq (exact integers
@@ -253,13 +391,13 @@ __device__ __forceinline__ IntResult run_pair_int(SH &sh, const ThalConsts &K, c
             if (lhs > rhs) {
                 H0 = H1;
                 G0 = G1;
-                pred = stk.W & 0xff;
+                pred = word_cell<FAST>(stk.W);
             }
         }
         // ---- loops (thal.c calc_bulge_internal acceptance: dG of the candidate strictly lower)
         if (best.G <= G0) {
             // exact enthalpy of the best candidate from the compact tables
-            const CandGeom g = cand_geometry(c, core_word(best.W));
+            const CandGeom g = cand_geometry(c, core_word<FAST>(best.W));
             const int Hw = F.H[g.lx] + F.H[g.y] + (best.W >> 16) * 10;
             if (best.G < G0) {
                 // two candidates tie for the minimum: doubles could order them either way
@@ -269,7 +407,7 @@ __device__ __forceinline__ IntResult run_pair_int(SH &sh, const ThalConsts &K, c
                 flags |= ((Hw > 0) & (2000 * Hw - best.G > -1000)) ? kDeferBad : 0;
                 H0 = Hw;
                 G0 = best.G;
-                pred = best.W & 0xff;
+                pred = word_cell<FAST>(best.W);
             } else if (Hw == H0) {
                 // same value either way: only the path (and the rounding along it) could differ
                 cell_soft = 0x100;
@@ -278,7 +416,8 @@ __device__ __forceinline__ IntResult run_pair_int(SH &sh, const ThalConsts &K, c
                 flags |= kDeferLoopEq;
             }
         }
-        const int Wcell = ((H0 / 10) << 16) | (b.po_c << 10) | (im1 << 4) | jm1;
+        const int Wcell = FAST ? (((H0 / 10) << 16) | (jm1 << 12) | (im1 << 8) | (b.po_c << 2))
+                               : (((H0 / 10) << 16) | (b.po_c << 10) | (im1 << 4) | jm1);
         const bool in = slot < n_cells;   // lanes past their last cell compute garbage
         defer |= in ? flags : 0;
         // ---- terminal pick (thal.c thal(): strict minimum of dG incl. the right end term, first
@@ -382,7 +521,7 @@ __device__ __forceinline__ IntResult run_pair_int(SH &sh, const ThalConsts &K, c
             int cur = endP & 0xff;
             bool done = !walk | (cur == 0xff);
             if (walk) {
-                sh.path[0][threadIdx.x] = (unsigned short)(core_word(endW) & 0x3fff);
+                sh.path[0][threadIdx.x] = (unsigned short)(core_word<FAST>(endW) & 0x3fff);
                 P = 1;
                 dpath |= (endP & 0x100) ? kDeferPathTie : 0;
             }
@@ -395,8 +534,8 @@ __device__ __forceinline__ IntResult run_pair_int(SH &sh, const ThalConsts &K, c
                 for (int e = kC - 1; e >= 0; --e) {
                     const int slot = pc * kC + e;
                     const int pr = sh.pred[slot][threadIdx.x];
-                    const bool hit = !done & (slot < n_cells) & ((W[e] & 0xff) == cur);   // predecessors only: cur is never the end cell
-                    if (hit) sh.path[P & (kPathMax - 1)][threadIdx.x] = (unsigned short)(core_word(W[e]) & 0x3fff);
+                    const bool hit = !done & (slot < n_cells) & (word_cell<FAST>(W[e]) == cur);   // predecessors only: cur is never the end cell
+                    if (hit) sh.path[P & (kPathMax - 1)][threadIdx.x] = (unsigned short)(core_word<FAST>(W[e]) & 0x3fff);
                     dpath |= (hit & (((softTie >> (slot & 63)) & 1ull) != 0ull)) ? kDeferPathTie : 0;
                     P += hit ? 1 : 0;
                     cur = hit ? pr : cur;
@@ -437,7 +576,7 @@ __device__ __forceinline__ IntResult run_pair_int(SH &sh, const ThalConsts &K, c
         if (RESOLVE) {
             // thal.c thal(): the nudged dG the terminal pick compares
             CellCtx cc;
-            const CellBases b = cell_bases(q, (endW >> 4) & 15, endW & 15, cc);
+            const CellBases b = cell_bases(q, word_im1<FAST>(endW), word_jm1<FAST>(endW), cc);
             const double rSn = F.S[b.idxR] + kTiny, rHn = (double)F.H[b.idxR] + kTiny;
             const double Gt = (((double)H + rHn) + K.init_H) - kT37 * ((S + rSn) + K.init_S);
             if (pass == 0) {
@@ -479,7 +618,7 @@ __device__ __forceinline__ IntResult run_pair_int(SH &sh, const ThalConsts &K, c
     // ---- thal.c drawDimer(): totals
     {
         CellCtx cc;
-        const CellBases b = cell_bases(q, (endW >> 4) & 15, endW & 15, cc);
+        const CellBases b = cell_bases(q, word_im1<FAST>(endW), word_jm1<FAST>(endW), cc);
         const double rS = F.S[b.idxR];
         const int rH = F.H[b.idxR];
         const double dH = (double)(H + rH + 200);
@@ -506,11 +645,28 @@ __device__ __forceinline__ IntResult run_pair_int(SH &sh, const ThalConsts &K, c
 }
 
 
-template <class SH>
+template <bool FAST, class SH>
 __device__ __forceinline__ void load_tables_int(SH &sh, const IntArgs &a)
 {
     constexpr int kThreadsI = SH::kThreads;
-    for (int e = threadIdx.x; e < SH::kRows * 64; e += kThreadsI) sh.T[e] = a.it->T[e];
+    if constexpr (FAST) {
+        // the list mode's image of the loop table (see "the list mode's visit"): row 16 l2 + l1, column 63 - po, the
+        // bulge rows filed under the predecessor's po, every entry + kFastD, kFastU for "not available"
+        static_assert(SH::kRows == IntTables::kRows, "the FAST image is the full table's");
+        for (int e = threadIdx.x; e < SH::kRows * 64 + 4; e += kThreadsI) {
+            const int l2 = e >> 10, l1 = (e >> 6) & 15, po = 63 - (e & 63);
+            int v = IntTables::kBig;
+            if (e < SH::kRows * 64 && l1 <= IntTables::kMaxL) {
+                int pe = po;
+                if (l2 == 0) pe = (po & 3) | ((3 - (po >> 4)) << 2);   // a_p | a_c << 2, a_c pairs with the predecessor's n2
+                else if (l1 == 0) pe = po & 15;                        // ... a_c is the predecessor's n1
+                v = a.it->T[(l1 * 16 + l2) * 64 + pe];
+            }
+            sh.T[e] = min(v, kFastU) + kFastD;
+        }
+    } else {
+        for (int e = threadIdx.x; e < SH::kRows * 64; e += kThreadsI) sh.T[e] = a.it->T[e];
+    }
     for (int e = threadIdx.x; e < FastTables::kCount; e += kThreadsI) {
         sh.F.S[e] = a.f.ft->S[e];
         sh.F.H[e] = a.f.ft->H[e];
@@ -523,7 +679,7 @@ __device__ __forceinline__ void load_tables_int(SH &sh, const IntArgs &a)
 
 // One lock-step DP of the wave: lane = pair (row, col); `take` lanes are computed, `pass_on`
 // lanes go to the output list untouched (flag kept).  same_row: all lanes share `row`.
-template <int NS, bool RESOLVE, class SH>
+template <int NS, bool RESOLVE, bool FAST, class SH>
 __device__ __forceinline__ void wave_pairs(SH &sh, const IntArgs &a, int row, int col, uint64_t pa,
                                            uint64_t pb, bool inside, bool pass_on, unsigned pass_flag,
                                            bool same_row)
@@ -569,7 +725,7 @@ __device__ __forceinline__ void wave_pairs(SH &sh, const IntArgs &a, int row, in
         return;
     }
     const bool decisions_only = a.f.sinks.dg == nullptr && a.f.sinks.tm == nullptr;   // wave-uniform
-    const IntResult r = run_pair_int<NS, RESOLVE, SH>(sh, a.f.c, q, rowmask, n_cells, nmax, decisions_only);
+    const IntResult r = run_pair_int<NS, RESOLVE, FAST, SH>(sh, a.f.c, q, rowmask, n_cells, nmax, decisions_only);
     const bool deferred = inside & !spill & (r.defer != 0);
     if (deferred) flag = kNeedsF64;
     spill |= deferred;
@@ -624,7 +780,7 @@ __global__ void __launch_bounds__(THREADS) k_pairs_int(IntArgs a)
 {
     typedef SharedI<NS, THREADS, TROWS> SH;
     __shared__ SH sh;
-    load_tables_int(sh, a);
+    load_tables_int<false>(sh, a);
     const int lane = threadIdx.x & 63;
     const int ncolg = (a.f.col1 - a.f.col0 + 63) >> 6;
     // Work items (one row x 64 consecutive sorted columns) are handed out to the WAVES from a
@@ -645,7 +801,7 @@ __global__ void __launch_bounds__(THREADS) k_pairs_int(IntArgs a)
         const uint64_t pa = a.f.pool[row];
         const uint64_t pb = a.f.cols_sorted[inside ? cq : a.f.col0];
         const int col = (int)a.f.perm[inside ? cq : a.f.col0];
-        wave_pairs<NS, false, SH>(sh, a, row, col, pa, pb, inside, false, 0u, true);
+        wave_pairs<NS, false, false, SH>(sh, a, row, col, pa, pb, inside, false, 0u, true);
     }
 }
 
@@ -653,13 +809,15 @@ __global__ void __launch_bounds__(THREADS) k_pairs_int(IntArgs a)
 // table size (64 slots), with the two-cell terminal pick settled by a second walk; what meets
 // another kind of tie or still does not fit goes to the output list.  Batches of kListBatchI x 512 entries are
 // counting-sorted in LDS (the predecessor rows double as scratch) and written back in place.
+// FAST: the cheaper visit, for chemistries whose cell values are all reachable ones (launch_pairs_int_list).
 constexpr int kListBatchI = 7;
+template <bool FAST>
 __global__ void __launch_bounds__(kThreadsI) k_pairs_int_list(IntArgs a)
 {
     typedef SharedI<kSlotsList, kThreadsI, IntTables::kRows> SH;
     __shared__ SH sh;
     if (*a.f.in_count == 0u) return;   // an empty list: no table loads
-    load_tables_int(sh, a);
+    load_tables_int<FAST>(sh, a);
     static_assert(sizeof(sh.pred) >= sizeof(uint2) * kListBatchI * kThreadsI + sizeof(unsigned) * 256,
                   "the predecessor rows must hold one sorted batch");
     uint2 *sorted = reinterpret_cast<uint2 *>(&sh.pred[0][0]);
@@ -737,7 +895,7 @@ __global__ void __launch_bounds__(kThreadsI) k_pairs_int_list(IntArgs a)
             // marked entries are retried as well: most of them met nothing but a terminal pick
             // shared by two cells, which this mode settles by walking both
             const int row = (int)(pr.x & ~kNeedsF64), col = (int)pr.y;
-            wave_pairs<kSlotsList, true, SH>(sh, a, row, col, a.f.pool[inside ? row : 0], a.f.pool[inside ? col : 0], inside,
+            wave_pairs<kSlotsList, true, FAST, SH>(sh, a, row, col, a.f.pool[inside ? row : 0], a.f.pool[inside ? col : 0], inside,
                                          false, 0u, false);
         }
         __syncthreads();
@@ -797,7 +955,8 @@ hipError_t launch_pairs_int(const PairKernelArgs &a, const IntTables *it, unsign
 }
 
 hipError_t launch_pairs_int_list(const PairKernelArgs &a, const IntTables *it, const uint2 *in_list,
-                                 const uint32_t *in_count, unsigned long long *reasons, int n_cu, hipStream_t stream)
+                                 const uint32_t *in_count, unsigned long long *reasons, int n_cu, hipStream_t stream,
+                                 bool cells_reachable)
 {
     IntArgs x;
     FastArgs &f = x.f;
@@ -822,7 +981,10 @@ hipError_t launch_pairs_int_list(const PairKernelArgs &a, const IntTables *it, c
     x.stat_off = 1033;
     x.work_counter = a.work_counter;
     if (hipError_t e = hipMemsetAsync(a.work_counter, 0, sizeof(unsigned), stream); e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_pairs_int_list, dim3(n_cu), dim3(kThreadsI), 0, stream, x);
+    // cells_reachable: pairs_row_tables_ok() -- every value a cell can publish is a reachable one, which the
+    // cheaper visit's running minimum needs; any other chemistry keeps the general visit
+    if (cells_reachable) hipLaunchKernelGGL(k_pairs_int_list<true>, dim3(n_cu), dim3(kThreadsI), 0, stream, x);
+    else hipLaunchKernelGGL(k_pairs_int_list<false>, dim3(n_cu), dim3(kThreadsI), 0, stream, x);
     return hipGetLastError();
 }
 
