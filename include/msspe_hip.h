@@ -81,6 +81,8 @@ const char *msspe_version(void);
  *   "wave_kernel"    "0" | "1"    one-wave-per-pair f64 kernel in the chain (1)
  *   "list_cap_log2"  "0" | "20".."30"   fixed hand-over list size (0: sized by the call)
  *   "site_list_cap_log2" "12".."26"  msspe_background_thal*: the work list holds 2^this sites (22)
+ *   "amplicon_keys_cap_log2" "10".."28"  msspe_background_amplicons*: the stable-key buffer of a context is first
+ *                                 made with 2^this keys (20) and doubles as needed; no result depends on it
  *   "split_lanes"    "0" | "2" | "4" | "8"
  *   "split_list"     "0" | "1"    short oligos: tables too large for the integer list stage go to the split-table
  *                                 kernel's list mode (1) or straight to the f64 kernels (0)
@@ -107,6 +109,12 @@ int msspe_set_option(msspe_ctx *ctx, const char *key, const char *value);
  *   "background_thal_slabs" / "background_thal_redone"
  *                     the last msspe_background_thal* call: slabs scored, and slabs whose sites did not fit the work
  *                     list and were split and listed again
+ *   "amplicon_keys_cap_log2"  the option's current value
+ *   "amplicon_keys" / "amplicon_key_grows"
+ *                     the last msspe_background_amplicons* call: stable keys it joined, and doublings of the key
+ *                     buffer on the way
+ *   "amplicon_sort_us" / "amplicon_join_us"
+ *                     the same call's device time of the key sort with the record ids, and of the join
  *   "cover_rounds"    the last msspe_conflict_cover* call: rounds that deleted nodes
  *   "cover_keys_us" / "cover_symmetrise_us" / "cover_rounds_us"
  *                     the same call's device time of its phases: sort and keys, S = B | B^T, the rounds
@@ -419,6 +427,9 @@ int msspe_segment_coverage_dev(msspe_ctx *ctx, const uint8_t *d_seqs, int n_seq,
  * context's device once and use the *_dev entry points on it (the alignment is read by both
  * directions of stage A and by the coverage report). */
 int msspe_device_put(msspe_ctx *ctx, const void *host, size_t bytes, void **device_out);
+/* The way back for such hosts: waits for the context's stream, then copies `bytes` bytes at `device` (from
+ * msspe_device_put, or a device list a *_dev call filled) to host_out.  bytes == 0: MSSPE_OK, nothing read. */
+int msspe_device_get(msspe_ctx *ctx, const void *device, size_t bytes, void *host_out);
 /* The same for a matrix given as separate rows (an alignment held as one string per record): row r is
  * rows[r][0 .. row_bytes[r]) followed by `pad` bytes up to row_len; staged through pinned buffers, the
  * host never builds the rectangular copy. */
@@ -615,6 +626,63 @@ int msspe_background_thal(msspe_ctx *ctx, const char *const *records, const size
                           int mode, float tm_threshold, uint64_t *sites_out, uint64_t *stable_out,
                           msspe_scored_site *sites, uint64_t capacity, uint64_t *count_out,
                           uint64_t *record_start_out);
+
+/* ---- off-target amplicons from the stable sites (engine extension) ---------------------------------------------
+ * One stable off-target site costs a little primer; two that face each other within a few hundred bases amplify the
+ * background.  Take the stream, primers, msspe_mismatch_opt, chemistry, mode and tm_threshold of
+ * msspe_background_thal* and its STABLE sites as defined there (a threshold <= 0: every site of the string rule).
+ * A primer at a plus-strand site at stream position p extends towards increasing positions, one at a minus-strand
+ * site at q towards decreasing positions.  An AMPLICON is an ordered pair of stable sites -- a plus-strand site of
+ * primer `fwd` at p and a minus-strand site of primer `rev` at q -- with
+ *   - q >= p;
+ *   - len = q + k - p in [min_len, max_len] (the product's length, both primers included);
+ *   - both windows in the same record: start[r] <= p and q + k <= start[r] + record_bytes[r] for one r.  Invalid
+ *     columns inside a record (N, IUPAC) between the two sites do not break an amplicon; the separator between two
+ *     records does.
+ * fwd == rev is allowed (one primer priming both ends); q == p is allowed (a palindromic window that is a site on
+ * both strands, len = k); duplicate primers count independently; every (plus site, minus site) pair that qualifies
+ * is one amplicon.
+ *   sites_out, stable_out: exactly what msspe_background_thal* returns for the same arguments.
+ *   amplicons_out (uint64, HOST, 2 n): [2 i] the amplicons with primer i as fwd, [2 i + 1] as rev.
+ *   *n_amplicons_out: the number of amplicons (the sum of either column).
+ *   The optional list follows the edge list's convention: one msspe_amplicon per amplicon; the _packed_dev form adds
+ *     to *d_count, which the caller zeroes and which runs past the capacity; nothing is written behind
+ *     d_amplicons[capacity - 1] and the order is unspecified (d_amplicons == NULL: no list, capacity and d_count
+ *     are not read).  The host form sorts by (pos, len, fwd, rev) and returns MSSPE_ERR_CAPACITY with valid counts
+ *     and *count_out = the number of amplicons when the list is truncated.  Counts never come from a truncated list.
+ *   record_start (HOST, n_records, the _packed_dev form): start[] as msspe_device_put_stream_packed returns it,
+ *     start[0] == 0; NULL: the stream is one record (n_records is not read).  The host form fills record_start_out (optional).
+ * Memory is bounded and nothing is dropped: the scored pass appends one 64-bit key per stable site to a buffer in the
+ * context that starts at 2^amplicon_keys_cap_log2 keys (msspe_set_option, 10..28, default 20) and doubles -- before a
+ * slab is folded it has room for the keys so far plus every site of the slab; a grown buffer is kept for later calls.  The keys are sorted by position
+ * (rocPRIM) and joined on the device; msspe_get_info "amplicon_keys" / "amplicon_key_grows": stable keys of the last
+ * call / doublings.  Primers of one call have one length; a panel of mixed lengths is one call per length and pairs
+ * no primers across them.
+ * Errors: those of msspe_background_thal*; MSSPE_ERR_ARG also for a NULL amp, amplicons_out or n_amplicons_out,
+ * min_len < k, min_len > max_len, record_start[0] != 0, record_start not strictly ascending or its last start beyond
+ * total_len; MSSPE_ERR_NOMEM for 2^31 stable sites or more.  n == 0 or
+ * total_len < k: MSSPE_OK, outputs zeroed, list count 0 (_packed_dev: unchanged). */
+typedef struct {
+    uint32_t min_len, max_len;   /* k <= min_len <= max_len */
+} msspe_amplicon_opt;
+typedef struct {
+    uint32_t fwd, rev;     /* indices into words: the plus-strand site's primer, the minus-strand site's */
+    uint32_t pos;          /* p: stream position of the plus-strand site's first column */
+    uint32_t len;          /* q + k - p */
+} msspe_amplicon;
+int msspe_background_amplicons_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, size_t total_len, int k,
+                                          const msspe_mismatch_opt *mm, const uint64_t *words, int n,
+                                          const msspe_chem *chem, int mode, float tm_threshold,
+                                          const msspe_amplicon_opt *amp, const uint64_t *record_start, int n_records,
+                                          uint64_t *sites_out, uint64_t *stable_out, uint64_t *amplicons_out,
+                                          uint64_t *n_amplicons_out, msspe_amplicon *d_amplicons, uint64_t capacity,
+                                          uint64_t *d_count);
+int msspe_background_amplicons(msspe_ctx *ctx, const char *const *records, const size_t *record_bytes, int n_records,
+                               int k, const msspe_mismatch_opt *mm, const uint64_t *words, int n,
+                               const msspe_chem *chem, int mode, float tm_threshold, const msspe_amplicon_opt *amp,
+                               uint64_t *sites_out, uint64_t *stable_out, uint64_t *amplicons_out,
+                               uint64_t *n_amplicons_out, msspe_amplicon *amplicons, uint64_t capacity,
+                               uint64_t *count_out, uint64_t *record_start_out);
 
 
 /* ---- several devices of one node ----------------------------------------------------------

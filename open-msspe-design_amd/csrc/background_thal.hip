@@ -11,6 +11,10 @@
 // k_site_fold: one lane per scored site.  Sites arrive grouped by (primer, strand) in long stretches (the site
 // kernel walks the primers of a tile in order), so a wave whose lanes agree on the key adds its two popcounts with
 // one atomic each; a mixed wave adds per lane.  The caller's records take one atomic per wave for their places.
+// k_site_fold_keys is the same fold with a second sink (msspe_background_amplicons*): one 64-bit key,
+// pos << 32 | strand << 31 | primer, per STABLE site, appended to a buffer the caller has sized for every site of
+// the launch, again with one atomic per wave.  The sink is a template flag of the shared body, so k_site_fold itself
+// is the kernel it was.
 #include "background_thal.hpp"
 
 #include <cmath>
@@ -46,10 +50,12 @@ __global__ void __launch_bounds__(kThreads) k_site_oligos(const uint64_t *packed
     list[e] = make_uint2(s.primer, (uint32_t)n + idx);
 }
 
-__global__ void __launch_bounds__(kThreads) k_site_fold(const msspe_site *sites, uint32_t count, const double *dg,
-                                                        const double *t, double t_cut, int n,
-                                                        unsigned long long *counts, msspe_scored_site *out,
-                                                        unsigned long long capacity, unsigned long long *out_count)
+template <bool kKeys>
+__device__ __forceinline__ void site_fold(const msspe_site *sites, uint32_t count, const double *dg, const double *t,
+                                          double t_cut, int n, unsigned long long *counts, msspe_scored_site *out,
+                                          unsigned long long capacity, unsigned long long *out_count,
+                                          unsigned long long *keys, unsigned long long key_cap,
+                                          unsigned long long *key_count)
 {
     const uint32_t idx = blockIdx.x * kThreads + threadIdx.x;
     const bool live = idx < count;
@@ -88,6 +94,34 @@ __global__ void __launch_bounds__(kThreads) k_site_fold(const msspe_site *sites,
             out[at] = r;
         }
     }
+    if (kKeys && m_stable) {   // wave-uniform
+        unsigned long long base = 0;
+        if (lane == 0) base = atomicAdd(key_count, (unsigned long long)__popcll(m_stable));
+        base = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)(base >> 32)) << 32) |
+               (unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+        const unsigned long long at = base + (unsigned long long)__popcll(m_stable & ((1ull << lane) - 1ull));
+        if (stable && at < key_cap)
+            keys[at] = ((unsigned long long)s.pos << 32) | ((unsigned long long)s.strand << 31) | s.primer;
+    }
+}
+
+__global__ void __launch_bounds__(kThreads) k_site_fold(const msspe_site *sites, uint32_t count, const double *dg,
+                                                        const double *t, double t_cut, int n,
+                                                        unsigned long long *counts, msspe_scored_site *out,
+                                                        unsigned long long capacity, unsigned long long *out_count)
+{
+    site_fold<false>(sites, count, dg, t, t_cut, n, counts, out, capacity, out_count, nullptr, 0, nullptr);
+}
+
+__global__ void __launch_bounds__(kThreads) k_site_fold_keys(const msspe_site *sites, uint32_t count,
+                                                             const double *dg, const double *t, double t_cut, int n,
+                                                             unsigned long long *counts, msspe_scored_site *out,
+                                                             unsigned long long capacity,
+                                                             unsigned long long *out_count, unsigned long long *keys,
+                                                             unsigned long long key_cap,
+                                                             unsigned long long *key_count)
+{
+    site_fold<true>(sites, count, dg, t, t_cut, n, counts, out, capacity, out_count, keys, key_cap, key_count);
 }
 
 }  // namespace
@@ -110,6 +144,19 @@ hipError_t launch_site_fold(const msspe_site *d_sites, uint32_t count, const dou
     hipLaunchKernelGGL(k_site_fold, dim3((count + kThreads - 1) / kThreads), dim3(kThreads), 0, stream, d_sites,
                        count, dg, t, t_cut, n, counts, d_out, (unsigned long long)capacity,
                        (unsigned long long *)d_count);
+    return hipGetLastError();
+}
+
+hipError_t launch_site_fold_keys(const msspe_site *d_sites, uint32_t count, const double *dg, const double *t,
+                                 double t_cut, int n, unsigned long long *counts, msspe_scored_site *d_out,
+                                 uint64_t capacity, uint64_t *d_count, uint64_t *d_keys, uint64_t key_cap,
+                                 uint64_t *d_key_count, hipStream_t stream)
+{
+    if (!count) return hipSuccess;
+    hipLaunchKernelGGL(k_site_fold_keys, dim3((count + kThreads - 1) / kThreads), dim3(kThreads), 0, stream, d_sites,
+                       count, dg, t, t_cut, n, counts, d_out, (unsigned long long)capacity,
+                       (unsigned long long *)d_count, (unsigned long long *)d_keys, (unsigned long long)key_cap,
+                       (unsigned long long *)d_key_count);
     return hipGetLastError();
 }
 

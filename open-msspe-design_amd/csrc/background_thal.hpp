@@ -25,4 +25,12 @@ hipError_t launch_site_fold(const msspe_site *d_sites, uint32_t count, const dou
                             double t_cut, int n, unsigned long long *counts, msspe_scored_site *d_out,
                             uint64_t capacity, uint64_t *d_count, hipStream_t stream);
 
+// The same fold with the stable-key sink of msspe_background_amplicons*: every stable site also appends
+// pos << 32 | strand << 31 | primer at d_keys[(*d_key_count)++].  The caller makes room for *d_key_count + count keys
+// before the launch (key_cap, the buffer's size, is only the kernel's guard).
+hipError_t launch_site_fold_keys(const msspe_site *d_sites, uint32_t count, const double *dg, const double *t,
+                                 double t_cut, int n, unsigned long long *counts, msspe_scored_site *d_out,
+                                 uint64_t capacity, uint64_t *d_count, uint64_t *d_keys, uint64_t key_cap,
+                                 uint64_t *d_key_count, hipStream_t stream);
+
 }  // namespace msspe

@@ -24,6 +24,7 @@
 #include "conflict_cover.hpp"
 #include "background.hpp"
 #include "background_thal.hpp"
+#include "background_amplicons.hpp"
 #include "coverage_mm.hpp"
 #include "kernels.hpp"
 #include "kmer_stage.hpp"
@@ -80,6 +81,7 @@ struct EngineOptions {
     bool short_chain = true;  // screens of up to 2^23 pairs: integer list stage -> one wave per pair (no register-table stages between)
     int self_lane_from = 81920;   // oligos per call from which SELF_ANY / SELF_END run one lane per oligo (msspe_oligo_stats_dev)
     int site_list_cap_log2 = 22;  // msspe_background_thal*: work list of 2^this sites (44 bytes each: 185 MB)
+    int amplicon_keys_cap_log2 = 20;  // msspe_background_amplicons*: the stable-key buffer starts at 2^this keys and doubles
 };
 
 struct msspe_ctx {
@@ -130,6 +132,25 @@ struct msspe_ctx {
         uint64_t *slab_count = nullptr;
         long long slabs = 0, redone = 0;   // of the last call
     } site_work;
+    // msspe_background_amplicons*: the stable keys as the fold appends them (grown by doubling) and their count, the
+    // sorted keys with their record ids, rocPRIM's temporary storage, the record starts, 2 n amplicon counts
+    struct AmpWork {
+        uint64_t *keys = nullptr;
+        size_t keys_cap = 0;
+        uint64_t *key_count = nullptr;
+        uint64_t *sorted = nullptr;
+        uint32_t *rec = nullptr;
+        size_t sorted_cap = 0;
+        void *tmp = nullptr;
+        size_t tmp_bytes = 0;
+        uint64_t *starts = nullptr;
+        size_t starts_cap = 0;
+        unsigned long long *counts = nullptr;
+        size_t counts_cap = 0;
+        hipEvent_t ev[3] = {};             // before the sort, between record ids and join, after the join
+        long long n_keys = 0, grows = 0;   // of the last call
+        long long sort_us = 0, join_us = 0;
+    } amp_work;
     // optional profiling of the dominant kernel (k_pairs_fast) with HIP events on ctx->stream
     bool prof_on = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events;
@@ -655,6 +676,9 @@ int msspe_set_option(msspe_ctx *ctx, const char *key, const char *value)
     } else if (k == "site_list_cap_log2") {
         if (!is_num || num < 12 || num > 26) return bad();   // 2^12: what one run against one primer can hold
         ctx->opt.site_list_cap_log2 = (int)num;
+    } else if (k == "amplicon_keys_cap_log2") {
+        if (!is_num || num < 10 || num > 28) return bad();
+        ctx->opt.amplicon_keys_cap_log2 = (int)num;
     } else if (k == "row_oob") {
         if (!is_num || num < 0 || num > 1) return bad();
         ctx->opt.row_oob = num != 0;
@@ -689,6 +713,11 @@ int msspe_get_info(msspe_ctx *ctx, const char *key, long long *value_out)
     else if (k == "site_list_cap_log2") *value_out = ctx->opt.site_list_cap_log2;
     else if (k == "background_thal_slabs") *value_out = ctx->site_work.slabs;
     else if (k == "background_thal_redone") *value_out = ctx->site_work.redone;
+    else if (k == "amplicon_keys_cap_log2") *value_out = ctx->opt.amplicon_keys_cap_log2;
+    else if (k == "amplicon_keys") *value_out = ctx->amp_work.n_keys;
+    else if (k == "amplicon_key_grows") *value_out = ctx->amp_work.grows;
+    else if (k == "amplicon_sort_us") *value_out = ctx->amp_work.sort_us;
+    else if (k == "amplicon_join_us") *value_out = ctx->amp_work.join_us;
     else if (k == "cover_rounds") *value_out = ctx->cover.rounds();
     else if (k == "cover_keys_us") *value_out = ctx->cover.phase_us()[0];
     else if (k == "cover_symmetrise_us") *value_out = ctx->cover.phase_us()[1];
@@ -734,6 +763,14 @@ void msspe_destroy(msspe_ctx *ctx)
             for (void *q : {(void *)w.sites, (void *)w.list, (void *)w.dg, (void *)w.t, (void *)w.pool,
                             (void *)w.counts, (void *)w.slab_count})
                 if (q) (void)hipFree(q);
+        }
+        {
+            auto &w = ctx->amp_work;
+            for (void *q : {(void *)w.keys, (void *)w.key_count, (void *)w.sorted, (void *)w.rec, w.tmp,
+                            (void *)w.starts, (void *)w.counts})
+                if (q) (void)hipFree(q);
+            for (hipEvent_t e : w.ev)
+                if (e) (void)hipEventDestroy(e);
         }
         if (ctx->ev_rev) (void)hipEventDestroy(ctx->ev_rev);
         if (ctx->stream_rev) {
@@ -2135,6 +2172,17 @@ int msspe_device_free(msspe_ctx *ctx, void *device)
     return MSSPE_OK;
 }
 
+int msspe_device_get(msspe_ctx *ctx, const void *device, size_t bytes, void *host_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (bytes && (!device || !host_out)) return fail(ctx, MSSPE_ERR_ARG, "null argument");
+    if (!bytes) return MSSPE_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpy(host_out, device, bytes, hipMemcpyDeviceToHost));
+    return MSSPE_OK;
+}
+
 // The background as one packed row: the stream (records back to back, one '-' between two) passes 16 MB at a time
 // through two pinned buffers and two device landing zones; each chunk is packed on the device behind its copy.  A
 // chunk starts at a multiple of 64 columns, so its base and validity words are whole words of the packed row.
@@ -2347,13 +2395,41 @@ int score_site_pairs(msspe_ctx *ctx, ChemEntry *ce, bool end1, int n, int k, uin
     return ListChain(ctx, ce, end1, list, (long)count).run(route, a, g, false);
 }
 
-}  // namespace
+// Room for `need` stable keys: the buffer doubles from 2^amplicon_keys_cap_log2 until it holds them, and the `have`
+// keys written so far move over, device to device.
+int ensure_amplicon_keys(msspe_ctx *ctx, uint64_t have, uint64_t need)
+{
+    auto &w = ctx->amp_work;
+    if (!w.key_count) HIP_TRY(ctx, hipMalloc((void **)&w.key_count, sizeof(uint64_t)));
+    if (w.keys && need <= w.keys_cap) return MSSPE_OK;
+    size_t cap = w.keys ? w.keys_cap : (size_t)1 << ctx->opt.amplicon_keys_cap_log2;
+    while (cap < need) {
+        cap *= 2;
+        ++w.grows;
+    }
+    if (w.keys && cap == w.keys_cap) return MSSPE_OK;
+    uint64_t *grown = nullptr;
+    HIP_TRY(ctx, hipMalloc((void **)&grown, sizeof(uint64_t) * cap));
+    hipError_t e = hipSuccess;
+    if (w.keys && have)
+        e = hipMemcpyAsync(grown, w.keys, sizeof(uint64_t) * have, hipMemcpyDeviceToDevice, ctx->stream);
+    if (e == hipSuccess && w.keys) e = hipStreamSynchronize(ctx->stream);   // the old buffer's last reader and writer
+    if (e != hipSuccess) {
+        (void)hipFree(grown);
+        return hip_fail(ctx, e, "growing the stable-key buffer");
+    }
+    if (w.keys) (void)hipFree(w.keys);
+    w.keys = grown;
+    w.keys_cap = cap;
+    return MSSPE_OK;
+}
 
-int msspe_background_thal_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, size_t total_len, int k,
-                                     const msspe_mismatch_opt *mm, const uint64_t *words, int n,
-                                     const msspe_chem *chem, int mode, float tm_threshold, uint64_t *sites_out,
-                                     uint64_t *stable_out, msspe_scored_site *d_sites, uint64_t capacity,
-                                     uint64_t *d_count)
+// msspe_background_thal_packed_dev, and with keys the same pass for msspe_background_amplicons_packed_dev: the fold
+// of every slab also appends the keys of its stable sites to ctx->amp_work.keys; amp_work.n_keys counts them.
+int background_thal_pass(msspe_ctx *ctx, const uint64_t *d_packed, size_t total_len, int k,
+                         const msspe_mismatch_opt *mm, const uint64_t *words, int n, const msspe_chem *chem, int mode,
+                         float tm_threshold, uint64_t *sites_out, uint64_t *stable_out, msspe_scored_site *d_sites,
+                         uint64_t capacity, uint64_t *d_count, bool keys)
 {
     if (!ctx) return MSSPE_ERR_ARG;
     if (!d_packed || !mm || !sites_out || !stable_out || !chem || n < 0 || (n && !words) || (d_sites && !d_count))
@@ -2368,9 +2444,17 @@ int msspe_background_thal_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, s
     std::fill(sites_out, sites_out + 2 * (size_t)n, (uint64_t)0);
     std::fill(stable_out, stable_out + 2 * (size_t)n, (uint64_t)0);
     auto &w = ctx->site_work;
+    auto &aw = ctx->amp_work;
     w.slabs = w.redone = 0;
+    if (keys) aw.n_keys = aw.grows = 0;
     if (n == 0 || total_len < (size_t)k) return MSSPE_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (keys) {   // a buffer an earlier call grew is kept: no result depends on its size
+        if ((rc = ensure_amplicon_keys(ctx, 0, 0))) return rc;
+        aw.grows = 0;
+        HIP_TRY(ctx, hipMemsetAsync(aw.key_count, 0, sizeof(uint64_t), ctx->stream));
+    }
+    uint64_t n_keys = 0;   // stable keys of the slabs folded so far
     const bool end1 = mode == 2;
     ChemEntry *ce = nullptr;
     if ((rc = chem_entry(ctx, *chem, tm_threshold, &ce, end1 ? kCutEndT : kCutAnyT))) return rc;
@@ -2397,6 +2481,8 @@ int msspe_background_thal_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, s
             return fail(ctx, rc, err);
         uint64_t count = 0;
         HIP_TRY(ctx, hipMemcpyAsync(&count, w.slab_count, sizeof count, hipMemcpyDeviceToHost, ctx->stream));
+        if (keys)   // behind the last fold in stream order: exact
+            HIP_TRY(ctx, hipMemcpyAsync(&n_keys, aw.key_count, sizeof n_keys, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         if (count > cap) {
             ++w.redone;
@@ -2426,16 +2512,37 @@ int msspe_background_thal_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, s
                                             ctx->ovf_count, ctx->stream));
             if ((rc = score_site_pairs(ctx, ce, end1, n, k, w.list + c0, cnt))) return rc;
         }
-        HIP_TRY(ctx, launch_site_fold(w.sites, (uint32_t)count, w.dg, w.t, cut, n, w.counts, d_sites, capacity,
-                                      d_sites ? d_count : nullptr, ctx->stream));
+        if (!keys) {
+            HIP_TRY(ctx, launch_site_fold(w.sites, (uint32_t)count, w.dg, w.t, cut, n, w.counts, d_sites, capacity,
+                                          d_sites ? d_count : nullptr, ctx->stream));
+        } else {
+            if ((rc = ensure_amplicon_keys(ctx, n_keys, n_keys + count))) return rc;
+            HIP_TRY(ctx, launch_site_fold_keys(w.sites, (uint32_t)count, w.dg, w.t, cut, n, w.counts, d_sites,
+                                               capacity, d_sites ? d_count : nullptr, aw.keys, aw.keys_cap,
+                                               aw.key_count, ctx->stream));
+        }
     }
     std::vector<uint64_t> host(4 * (size_t)n);
     HIP_TRY(ctx, hipMemcpyAsync(host.data(), w.counts, sizeof(uint64_t) * host.size(), hipMemcpyDeviceToHost,
                                 ctx->stream));
+    if (keys) HIP_TRY(ctx, hipMemcpyAsync(&n_keys, aw.key_count, sizeof n_keys, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     std::copy(host.begin(), host.begin() + 2 * (size_t)n, sites_out);
     std::copy(host.begin() + 2 * (size_t)n, host.end(), stable_out);
+    if (keys) aw.n_keys = (long long)n_keys;
     return MSSPE_OK;
+}
+
+}  // namespace
+
+int msspe_background_thal_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, size_t total_len, int k,
+                                     const msspe_mismatch_opt *mm, const uint64_t *words, int n,
+                                     const msspe_chem *chem, int mode, float tm_threshold, uint64_t *sites_out,
+                                     uint64_t *stable_out, msspe_scored_site *d_sites, uint64_t capacity,
+                                     uint64_t *d_count)
+{
+    return background_thal_pass(ctx, d_packed, total_len, k, mm, words, n, chem, mode, tm_threshold, sites_out,
+                                stable_out, d_sites, capacity, d_count, false);
 }
 
 int msspe_background_thal(msspe_ctx *ctx, const char *const *records, const size_t *record_bytes, int n_records,
@@ -2487,6 +2594,169 @@ int msspe_background_thal(msspe_ctx *ctx, const char *const *records, const size
     if (d_sites) (void)hipFree(d_sites);
     (void)msspe_device_free(ctx, d);
     if (e != hipSuccess) return hip_fail(ctx, e, "msspe_background_thal");
+    return rc;
+}
+
+int msspe_background_amplicons_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, size_t total_len, int k,
+                                          const msspe_mismatch_opt *mm, const uint64_t *words, int n,
+                                          const msspe_chem *chem, int mode, float tm_threshold,
+                                          const msspe_amplicon_opt *amp, const uint64_t *record_start, int n_records,
+                                          uint64_t *sites_out, uint64_t *stable_out, uint64_t *amplicons_out,
+                                          uint64_t *n_amplicons_out, msspe_amplicon *d_amplicons, uint64_t capacity,
+                                          uint64_t *d_count)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!amp || !amplicons_out || !n_amplicons_out || n < 0 || (d_amplicons && !d_count) ||
+        (record_start && n_records <= 0))
+        return fail(ctx, MSSPE_ERR_ARG, "null argument");
+    if (k >= 2 && k <= 31 && amp->min_len < (uint32_t)k)   // another k: the scored pass's MSSPE_ERR_K
+        return fail(ctx, MSSPE_ERR_ARG, "background_amplicons: min_len is shorter than the primers");
+    if (amp->min_len > amp->max_len) return fail(ctx, MSSPE_ERR_ARG, "background_amplicons: min_len exceeds max_len");
+    if (record_start) {
+        if (record_start[0] != 0)
+            return fail(ctx, MSSPE_ERR_ARG, "background_amplicons: record_start[0] must be 0");
+        for (int r = 1; r < n_records; ++r)
+            if (record_start[r] <= record_start[r - 1])
+                return fail(ctx, MSSPE_ERR_ARG, "background_amplicons: record_start is not ascending");
+        if (record_start[n_records - 1] > total_len)
+            return fail(ctx, MSSPE_ERR_ARG, "background_amplicons: a record starts beyond the stream");
+    }
+    *n_amplicons_out = 0;
+    int rc = background_thal_pass(ctx, d_packed, total_len, k, mm, words, n, chem, mode, tm_threshold, sites_out,
+                                  stable_out, nullptr, 0, nullptr, true);
+    if (rc) return rc;
+    std::fill(amplicons_out, amplicons_out + 2 * (size_t)n, (uint64_t)0);
+    auto &w = ctx->amp_work;
+    w.sort_us = w.join_us = 0;
+    const uint64_t m = (uint64_t)w.n_keys;
+    if (!m) return MSSPE_OK;
+    if (m >= (1ull << 31)) return fail(ctx, MSSPE_ERR_NOMEM, "background_amplicons: 2^31 stable sites or more");
+    unsigned end_bit = 33;   // position bits above the strand and the primer
+    while (end_bit < 64 && (total_len >> (end_bit - 32))) ++end_bit;
+    const size_t tmp_bytes = amplicon_sort_temp_bytes((size_t)m, end_bit);
+    if (w.sorted_cap < m) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (w.sorted) (void)hipFree(w.sorted);
+        if (w.rec) (void)hipFree(w.rec);
+        w.sorted = nullptr;
+        w.rec = nullptr;
+        w.sorted_cap = 0;
+        HIP_TRY(ctx, hipMalloc((void **)&w.sorted, sizeof(uint64_t) * m));
+        HIP_TRY(ctx, hipMalloc((void **)&w.rec, sizeof(uint32_t) * m));
+        w.sorted_cap = m;
+    }
+    if (w.tmp_bytes < tmp_bytes) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (w.tmp) (void)hipFree(w.tmp);
+        w.tmp = nullptr;
+        w.tmp_bytes = 0;
+        HIP_TRY(ctx, hipMalloc(&w.tmp, tmp_bytes));
+        w.tmp_bytes = tmp_bytes;
+    }
+    if (w.counts_cap < 2 * (size_t)n) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (w.counts) (void)hipFree(w.counts);
+        w.counts = nullptr;
+        w.counts_cap = 0;
+        HIP_TRY(ctx, hipMalloc((void **)&w.counts, sizeof(uint64_t) * 2 * (size_t)n));
+        w.counts_cap = 2 * (size_t)n;
+    }
+    if (record_start && w.starts_cap < (size_t)n_records) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (w.starts) (void)hipFree(w.starts);
+        w.starts = nullptr;
+        w.starts_cap = 0;
+        HIP_TRY(ctx, hipMalloc((void **)&w.starts, sizeof(uint64_t) * (size_t)n_records));
+        w.starts_cap = (size_t)n_records;
+    }
+    for (hipEvent_t &e : w.ev)
+        if (!e) HIP_TRY(ctx, hipEventCreate(&e));
+    HIP_TRY(ctx, hipMemsetAsync(w.counts, 0, sizeof(uint64_t) * 2 * (size_t)n, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(w.ev[0], ctx->stream));
+    HIP_TRY(ctx, sort_amplicon_keys(w.keys, w.sorted, (size_t)m, end_bit, w.tmp, w.tmp_bytes, ctx->stream));
+    if (record_start) {
+        // the call returns behind a synchronisation of the stream, so the caller's array outlives the copy
+        HIP_TRY(ctx, hipMemcpyAsync(w.starts, record_start, sizeof(uint64_t) * (size_t)n_records,
+                                    hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, launch_key_records(w.sorted, (uint32_t)m, w.starts, n_records, w.rec, ctx->stream));
+    } else {
+        HIP_TRY(ctx, hipMemsetAsync(w.rec, 0, sizeof(uint32_t) * m, ctx->stream));
+    }
+    HIP_TRY(ctx, hipEventRecord(w.ev[1], ctx->stream));
+    HIP_TRY(ctx, launch_amplicon_join(w.sorted, w.rec, (uint32_t)m, k, amp->min_len, amp->max_len, w.counts,
+                                      d_amplicons, capacity, d_amplicons ? d_count : nullptr, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(w.ev[2], ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(amplicons_out, w.counts, sizeof(uint64_t) * 2 * (size_t)n, hipMemcpyDeviceToHost,
+                                ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    float ms = 0.0f;
+    HIP_TRY(ctx, hipEventElapsedTime(&ms, w.ev[0], w.ev[1]));
+    w.sort_us = (long long)(ms * 1000.0f);
+    HIP_TRY(ctx, hipEventElapsedTime(&ms, w.ev[1], w.ev[2]));
+    w.join_us = (long long)(ms * 1000.0f);
+    uint64_t total = 0;
+    for (int i = 0; i < n; ++i) total += amplicons_out[2 * (size_t)i];   // every amplicon has one forward primer
+    *n_amplicons_out = total;
+    return MSSPE_OK;
+}
+
+int msspe_background_amplicons(msspe_ctx *ctx, const char *const *records, const size_t *record_bytes, int n_records,
+                               int k, const msspe_mismatch_opt *mm, const uint64_t *words, int n,
+                               const msspe_chem *chem, int mode, float tm_threshold, const msspe_amplicon_opt *amp,
+                               uint64_t *sites_out, uint64_t *stable_out, uint64_t *amplicons_out,
+                               uint64_t *n_amplicons_out, msspe_amplicon *amplicons, uint64_t capacity,
+                               uint64_t *count_out, uint64_t *record_start_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!mm || !sites_out || !stable_out || !chem || !amp || !amplicons_out || !n_amplicons_out || n < 0 ||
+        (n && !words) || (amplicons && !count_out))
+        return fail(ctx, MSSPE_ERR_ARG, "null argument");
+    if (count_out) *count_out = 0;
+    *n_amplicons_out = 0;
+    void *d = nullptr;
+    size_t L = 0;
+    std::vector<uint64_t> starts((size_t)std::max(n_records, 0));
+    int rc = msspe_device_put_stream_packed(ctx, records, record_bytes, n_records, &d, &L, starts.data());
+    if (rc) return rc;
+    if (record_start_out) std::copy(starts.begin(), starts.end(), record_start_out);
+    msspe_amplicon *d_list = nullptr;   // the list and, behind it, its count
+    uint64_t *d_count = nullptr;
+    hipError_t e = hipSuccess;
+    if (amplicons) {
+        const size_t list_bytes = sizeof(msspe_amplicon) * (size_t)capacity;
+        e = hipMalloc((void **)&d_list, list_bytes + sizeof(uint64_t));
+        if (e == hipSuccess) {
+            d_count = (uint64_t *)((char *)d_list + list_bytes);
+            e = hipMemsetAsync(d_count, 0, sizeof(uint64_t), ctx->stream);
+        }
+    }
+    if (e == hipSuccess) {
+        rc = msspe_background_amplicons_packed_dev(ctx, (const uint64_t *)d, L, k, mm, words, n, chem, mode,
+                                                   tm_threshold, amp, n_records > 0 ? starts.data() : nullptr,
+                                                   n_records, sites_out, stable_out, amplicons_out, n_amplicons_out,
+                                                   d_list, capacity, d_count);
+        if (!rc && amplicons) {
+            uint64_t count = 0;
+            e = hipMemcpyAsync(&count, d_count, sizeof count, hipMemcpyDeviceToHost, ctx->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+            const uint64_t kept = std::min(count, capacity);
+            if (e == hipSuccess && kept)
+                e = hipMemcpy(amplicons, d_list, sizeof(msspe_amplicon) * kept, hipMemcpyDeviceToHost);
+            if (e == hipSuccess) {
+                std::sort(amplicons, amplicons + kept, [](const msspe_amplicon &a, const msspe_amplicon &b) {
+                    if (a.pos != b.pos) return a.pos < b.pos;
+                    if (a.len != b.len) return a.len < b.len;
+                    if (a.fwd != b.fwd) return a.fwd < b.fwd;
+                    return a.rev < b.rev;
+                });
+                *count_out = count;
+                if (count > capacity) rc = fail(ctx, MSSPE_ERR_CAPACITY, "amplicon list capacity too small");
+            }
+        }
+    }
+    if (d_list) (void)hipFree(d_list);
+    (void)msspe_device_free(ctx, d);
+    if (e != hipSuccess) return hip_fail(ctx, e, "msspe_background_amplicons");
     return rc;
 }
 

@@ -79,6 +79,8 @@ const OptSpec kOpts[] = {
     {"--max-background-sites", "MAX_BACKGROUND_SITES", OptSpec::OptInt, OFF(max_background_sites)},
     {"--background-tm", "BACKGROUND_TM", OptSpec::Str, OFF(background_tm_text)},
     {"--background-thal", "BACKGROUND_THAL", OptSpec::Str, OFF(background_thal)},
+    {"--background-amplicon-max", "BACKGROUND_AMPLICON_MAX", OptSpec::OptInt, OFF(background_amplicon_max)},
+    {"--background-amplicon-min", "BACKGROUND_AMPLICON_MIN", OptSpec::OptInt, OFF(background_amplicon_min)},
 };
 #undef OFF
 
@@ -194,6 +196,26 @@ Args Args::parse(int argc, const char *const *argv)
         if (*end || std::isnan(a.background_tm))
             throw UsageError("error: invalid value '" + a.background_tm_text + "' for '--background-tm'");
         a.background_scored = true;
+    }
+    for (const auto &given : {std::make_pair("--background-amplicon-max", a.background_amplicon_max),
+                              std::make_pair("--background-amplicon-min", a.background_amplicon_min)}) {
+        if (given.second < 0) continue;
+        if (a.background.empty())
+            throw UsageError(std::string("error: '") + given.first + "' needs '--background <FASTA>'");
+        if (!a.background_scored)
+            throw UsageError(std::string("error: '") + given.first + "' needs '--background-tm <C>'");
+    }
+    if (a.background_amplicon_min >= 0 && a.background_amplicon_max < 0)
+        throw UsageError("error: '--background-amplicon-min' needs '--background-amplicon-max <LEN>'");
+    if (a.background_amplicon_max >= 0) {
+        if (a.background_amplicon_min < 0) a.background_amplicon_min = a.kmer_size;
+        if (a.background_amplicon_min < a.kmer_size)
+            throw UsageError("error: '--background-amplicon-min " + std::to_string(a.background_amplicon_min) +
+                             "' is smaller than '--kmer-size " + std::to_string(a.kmer_size) + "'");
+        if (a.background_amplicon_min > a.background_amplicon_max)
+            throw UsageError("error: '--background-amplicon-min " + std::to_string(a.background_amplicon_min) +
+                             "' is larger than '--background-amplicon-max " +
+                             std::to_string(a.background_amplicon_max) + "'");
     }
     if (a.background_thal.empty()) a.background_thal = "any";
     if (a.background_thal != "any" && a.background_thal != "end1")
@@ -932,16 +954,18 @@ std::string coverage_report_mm(Engine &eng, const DeviceAlignment &aln, const st
     return out;
 }
 
-DeviceBackground::DeviceBackground(Engine &eng, const std::vector<SequenceRecord> &records) : eng_(eng)
+DeviceBackground::DeviceBackground(Engine &eng, const std::vector<SequenceRecord> &records)
+    : eng_(eng), names_(records.size()), starts_(records.size())
 {
     std::vector<const char *> rows(records.size());
     std::vector<size_t> bytes(records.size());
     for (size_t r = 0; r < records.size(); ++r) {
         rows[r] = records[r].sequence.data();
         bytes[r] = records[r].sequence.size();
+        names_[r] = records[r].name;
     }
     const int rc = msspe_device_put_stream_packed(eng.ctx(), rows.data(), bytes.data(), (int)records.size(), &dev_,
-                                                  &len_, nullptr);
+                                                  &len_, starts_.data());
     if (rc) eng.fail(rc);
 }
 
@@ -996,6 +1020,103 @@ std::vector<std::pair<uint64_t, uint64_t>> DeviceBackground::scored(
             out[cls.second[(size_t)j]] = {counts[2 * (size_t)j], counts[2 * (size_t)j + 1]};
             stable_out[cls.second[(size_t)j]] = {stable[2 * (size_t)j], stable[2 * (size_t)j + 1]};
         }
+    }
+    return out;
+}
+
+std::vector<std::pair<uint64_t, uint64_t>> DeviceBackground::amplicons(
+    const std::vector<std::string> &words, int max_mismatches, int exact_3p, const msspe_chem &chem, int mode,
+    float tm_threshold, uint32_t min_len, uint32_t max_len, std::vector<std::pair<uint64_t, uint64_t>> &stable_out,
+    std::vector<std::pair<uint64_t, uint64_t>> &amplicons_out, std::vector<msspe_amplicon> &list_out) const
+{
+    std::vector<std::pair<uint64_t, uint64_t>> out(words.size());
+    stable_out.assign(words.size(), {0, 0});
+    amplicons_out.assign(words.size(), {0, 0});
+    list_out.clear();
+    std::map<size_t, std::vector<size_t>> by_length;   // a panel of mixed lengths: one length class per call
+    for (size_t i = 0; i < words.size(); ++i) by_length[words[i].size()].push_back(i);
+    for (const auto &cls : by_length) {
+        const int k = (int)cls.first, n = (int)cls.second.size();
+        std::string flat;
+        for (const size_t i : cls.second) flat += words[i];
+        std::vector<uint64_t> packed((size_t)n), counts(2 * (size_t)n), stable(2 * (size_t)n), amps(2 * (size_t)n);
+        int rc = msspe_pack_oligos(flat.data(), n, k, packed.data());
+        if (rc) eng_.fail(rc);
+        const msspe_mismatch_opt mm{std::min(max_mismatches, k), std::min(exact_3p, k)};
+        // primers longer than max_len make no product that short: the scored counts alone
+        const bool pair = (uint32_t)k <= max_len;
+        const msspe_amplicon_opt opt{pair ? std::max(min_len, (uint32_t)k) : (uint32_t)k, pair ? max_len : (uint32_t)k};
+        uint64_t total = 0, count = 0;
+        std::vector<msspe_amplicon> list;
+        // the device list with its count behind it; a list that was too short says how long it must be
+        for (uint64_t capacity = (uint64_t)1 << 16;; capacity = count) {
+            const size_t list_bytes = sizeof(msspe_amplicon) * (size_t)capacity;
+            const std::vector<char> zero(list_bytes + sizeof(uint64_t), 0);
+            void *d_list = nullptr;
+            if ((rc = msspe_device_put(eng_.ctx(), zero.data(), zero.size(), &d_list))) eng_.fail(rc);
+            uint64_t *d_count = reinterpret_cast<uint64_t *>(static_cast<char *>(d_list) + list_bytes);
+            rc = msspe_background_amplicons_packed_dev(eng_.ctx(), static_cast<const uint64_t *>(dev_), len_, k, &mm,
+                                                       packed.data(), n, &chem, mode, tm_threshold, &opt,
+                                                       starts_.data(), (int)starts_.size(), counts.data(),
+                                                       stable.data(), amps.data(), &total,
+                                                       pair ? static_cast<msspe_amplicon *>(d_list) : nullptr,
+                                                       capacity, d_count);
+            if (!rc) rc = msspe_device_get(eng_.ctx(), d_count, sizeof count, &count);
+            if (!rc && count <= capacity) {
+                list.resize((size_t)count);
+                rc = msspe_device_get(eng_.ctx(), d_list, sizeof(msspe_amplicon) * list.size(), list.data());
+            }
+            (void)msspe_device_free(eng_.ctx(), d_list);
+            if (rc) eng_.fail(rc);
+            if (count <= capacity) break;
+        }
+        for (int j = 0; j < n; ++j) {
+            const size_t i = cls.second[(size_t)j];
+            out[i] = {counts[2 * (size_t)j], counts[2 * (size_t)j + 1]};
+            stable_out[i] = {stable[2 * (size_t)j], stable[2 * (size_t)j + 1]};
+            if (pair) amplicons_out[i] = {amps[2 * (size_t)j], amps[2 * (size_t)j + 1]};
+        }
+        for (msspe_amplicon a : list) {
+            a.fwd = (uint32_t)cls.second[a.fwd];
+            a.rev = (uint32_t)cls.second[a.rev];
+            list_out.push_back(a);
+        }
+    }
+    std::sort(list_out.begin(), list_out.end(), [](const msspe_amplicon &a, const msspe_amplicon &b) {
+        if (a.pos != b.pos) return a.pos < b.pos;
+        if (a.len != b.len) return a.len < b.len;
+        if (a.fwd != b.fwd) return a.fwd < b.fwd;
+        return a.rev < b.rev;
+    });
+    return out;
+}
+
+std::pair<std::string, uint64_t> DeviceBackground::locate(uint64_t pos) const
+{
+    const size_t r = (size_t)(std::upper_bound(starts_.begin(), starts_.end(), pos) - starts_.begin()) - 1;
+    return {names_[r], pos - starts_[r]};
+}
+
+std::string background_report_amplicons(const std::vector<std::string> &names,
+                                        const std::vector<std::pair<uint64_t, uint64_t>> &counts,
+                                        const std::vector<msspe_amplicon> &list, const DeviceBackground &background,
+                                        uint32_t min_len, uint32_t max_len)
+{
+    std::string out = "\nBackground amplicons (stable sites facing each other, " + std::to_string(min_len) + " to " +
+                      std::to_string(max_len) + " bases):\n";
+    uint64_t total = 0;
+    for (size_t i = 0; i < names.size(); ++i) {
+        out += "  " + names[i] + ": as forward " + std::to_string(counts[i].first) + ", as reverse " +
+               std::to_string(counts[i].second) + "\n";
+        total += counts[i].first;
+    }
+    out += "  Total: " + std::to_string(names.size()) + " primers, " + std::to_string(total) + " amplicons\n";
+    const size_t shown = std::min<size_t>(20, list.size());
+    out += "  First " + std::to_string(shown) + " (record:offset, length, forward, reverse):\n";
+    for (size_t e = 0; e < shown; ++e) {
+        const auto at = background.locate(list[e].pos);
+        out += "    " + at.first + ":" + std::to_string(at.second) + ", " + std::to_string(list[e].len) + ", " +
+               names[list[e].fwd] + ", " + names[list[e].rev] + "\n";
     }
     return out;
 }
@@ -1282,7 +1403,19 @@ int run(const Args &args, std::string &stdout_text)
                 words.push_back(i < panel_list->size() ? (*panel_list)[i] : good[i - panel_list->size()].word);
             }
         }
-        if (args.background_scored) {
+        if (args.background_scored && args.background_amplicon_max >= 0) {   // one scored pass feeds both blocks
+            std::vector<std::pair<uint64_t, uint64_t>> stable, amps;
+            std::vector<msspe_amplicon> list;
+            const auto sites = background->amplicons(words, args.background_mismatches, args.background_3p_exact,
+                                                     ntthal_chem(opts), bg_mode, args.background_tm,
+                                                     (uint32_t)args.background_amplicon_min,
+                                                     (uint32_t)args.background_amplicon_max, stable, amps, list);
+            stdout_text += background_report_scored(names, sites, stable, args.background_mismatches,
+                                                    args.background_3p_exact, bg_mode, args.background_tm);
+            stdout_text += background_report_amplicons(names, amps, list, *background,
+                                                       (uint32_t)args.background_amplicon_min,
+                                                       (uint32_t)args.background_amplicon_max);
+        } else if (args.background_scored) {
             std::vector<std::pair<uint64_t, uint64_t>> stable;
             const auto sites = background->scored(words, args.background_mismatches, args.background_3p_exact,
                                                   ntthal_chem(opts), bg_mode, args.background_tm, stable);

@@ -72,6 +72,11 @@ struct Args {
     std::string background_tm_text, background_thal;
     float background_tm = 0.0f;
     bool background_scored = false;
+    // --background-amplicon-max LEN (with --background and --background-tm): after the scored block, the off-target
+    // amplicons -- pairs of stable sites that face each other in one record, product length (both primers included)
+    // in [background_amplicon_min, LEN] (msspe_background_amplicons; the minimum defaults to the k-mer size).  Report
+    // only.  -1 = not given, nothing changes.
+    int background_amplicon_max = -1, background_amplicon_min = -1;
     bool stddev_population = false;  // crate std-dev 0.1.0's divisor is unpinned
     static Args parse(int argc, const char *const *argv);   // throws UsageError
     static std::string usage();
@@ -233,11 +238,25 @@ public:
                                                       int exact_3p, const msspe_chem &chem, int mode,
                                                       float tm_threshold,
                                                       std::vector<std::pair<uint64_t, uint64_t>> &stable_out) const;
+    // scored() and, from the same pass, the off-target amplicons of the words' stable sites (one
+    // msspe_background_amplicons_packed_dev call per word length on the resident stream; primers of different lengths
+    // are not paired): amplicons_out (as forward, as reverse) per word; list_out: every amplicon, fwd and rev indices
+    // into words, sorted by (pos, len, fwd, rev)
+    std::vector<std::pair<uint64_t, uint64_t>> amplicons(const std::vector<std::string> &words, int max_mismatches,
+                                                         int exact_3p, const msspe_chem &chem, int mode,
+                                                         float tm_threshold, uint32_t min_len, uint32_t max_len,
+                                                         std::vector<std::pair<uint64_t, uint64_t>> &stable_out,
+                                                         std::vector<std::pair<uint64_t, uint64_t>> &amplicons_out,
+                                                         std::vector<msspe_amplicon> &list_out) const;
+    // (record id, offset in the record) of stream position pos
+    std::pair<std::string, uint64_t> locate(uint64_t pos) const;
 
 private:
     Engine &eng_;
     void *dev_ = nullptr;
     size_t len_ = 0;
+    std::vector<std::string> names_;   // of the records, and their first stream columns: locate()
+    std::vector<uint64_t> starts_;
 };
 // "Background sites (up to M mismatches, last E bases exact):", one line per primer (name as in the CSV, plus-strand
 // and minus-strand sites) and a totals line
@@ -250,6 +269,13 @@ std::string background_report_scored(const std::vector<std::string> &names,
                                      const std::vector<std::pair<uint64_t, uint64_t>> &sites,
                                      const std::vector<std::pair<uint64_t, uint64_t>> &stable, int max_mismatches,
                                      int exact_3p, int mode, float tm_threshold);
+// "Background amplicons (stable sites facing each other, MIN to MAX bases):", one line per primer (amplicons as
+// forward and as reverse), a totals line and the first 20 amplicons of the sorted list as
+// "record:offset, length, forward name, reverse name"
+std::string background_report_amplicons(const std::vector<std::string> &names,
+                                        const std::vector<std::pair<uint64_t, uint64_t>> &counts,
+                                        const std::vector<msspe_amplicon> &list, const DeviceBackground &background,
+                                        uint32_t min_len, uint32_t max_len);
 // main.rs:834-858
 // first_f / first_r: the number of the first row of each direction (a panel's extension continues its numbering)
 std::string primers_csv(const std::vector<KmerStat> &fwd, const std::vector<KmerStat> &rev, size_t first_f = 0,

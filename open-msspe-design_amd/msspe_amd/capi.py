@@ -23,7 +23,7 @@ EXPORTS = [
     "msspe_cross_dimer_end_ab_dev", "msspe_cross_dimer_end_ab", "msspe_t_cut",
     "msspe_conflict_cover_dev", "msspe_conflict_cover",
     "msspe_last_overflow_pairs", "msspe_pair_stage_stats", "msspe_pair_stage_samples", "msspe_host_pair_tables", "msspe_host_split_tables", "msspe_device_put_rows", "msspe_segment_coverage", "msspe_segment_coverage_dev",
-    "msspe_device_put", "msspe_device_free", "msspe_thal_detail_pairs", "msspe_profile_enable", "msspe_profile_read",
+    "msspe_device_put", "msspe_device_get", "msspe_device_free", "msspe_thal_detail_pairs", "msspe_profile_enable", "msspe_profile_read",
     "msspe_oligo_stats_dev", "msspe_oligo_stats",
     "msspe_kmer_candidates", "msspe_kmer_candidates_dev", "msspe_round_g_f32",
     "msspe_packed_row_words", "msspe_device_put_rows_packed", "msspe_kmer_candidates_packed_dev",
@@ -34,6 +34,7 @@ EXPORTS = [
     "msspe_segment_coverage_mm", "msspe_segment_coverage_mm_dev", "msspe_segment_coverage_mm_packed_dev",
     "msspe_device_put_stream_packed", "msspe_background_sites_packed_dev", "msspe_background_sites",
     "msspe_background_thal_packed_dev", "msspe_background_thal",
+    "msspe_background_amplicons_packed_dev", "msspe_background_amplicons",
     "msspe_round_fixed_f32", "msspe_g_cut",
     "msspe_group_create", "msspe_group_destroy", "msspe_group_last_error", "msspe_group_size",
     "msspe_group_transport", "msspe_group_transport_reason", "msspe_group_rccl_available", "msspe_group_member", "msspe_group_set_option", "msspe_group_rows",
@@ -76,6 +77,14 @@ SITE_DTYPE = np.dtype([("primer", np.uint32), ("pos", np.uint32), ("mismatches",
 SCORED_SITE_DTYPE = np.dtype([("primer", np.uint32), ("pos", np.uint32), ("mismatches", np.uint16),
                               ("strand", np.uint16), ("stable", np.uint32), ("dg", np.float64), ("t", np.float64)])
 THAL_MODES = {"any": 1, "end1": 2}
+
+# msspe_amplicon: a plus-strand stable site of primer fwd at pos and a minus-strand one of primer rev, len columns on
+AMPLICON_DTYPE = np.dtype([("fwd", np.uint32), ("rev", np.uint32), ("pos", np.uint32), ("len", np.uint32)])
+
+
+class AmpliconOpt(C.Structure):
+    """msspe_amplicon_opt: product lengths (both primers included) that count, k <= min_len <= max_len."""
+    _fields_ = [("min_len", C.c_uint32), ("max_len", C.c_uint32)]
 
 
 class MismatchOpt(C.Structure):
@@ -216,6 +225,14 @@ def load_library() -> C.CDLL:
     L.msspe_background_thal.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int,
                                         C.POINTER(MismatchOpt), u64p, C.c_int, C.POINTER(Chem), C.c_int, C.c_float,
                                         vp, vp, vp, C.c_uint64, C.POINTER(C.c_uint64), vp]
+    L.msspe_background_amplicons_packed_dev.argtypes = [
+        vp, vp, C.c_size_t, C.c_int, C.POINTER(MismatchOpt), u64p, C.c_int, C.POINTER(Chem), C.c_int, C.c_float,
+        C.POINTER(AmpliconOpt), vp, C.c_int, vp, vp, vp, C.POINTER(C.c_uint64), vp, C.c_uint64, vp]
+    L.msspe_background_amplicons.argtypes = [
+        vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(MismatchOpt), u64p, C.c_int,
+        C.POINTER(Chem), C.c_int, C.c_float, C.POINTER(AmpliconOpt), vp, vp, vp, C.POINTER(C.c_uint64), vp,
+        C.c_uint64, C.POINTER(C.c_uint64), vp]
+    L.msspe_device_get.argtypes = [vp, vp, C.c_size_t, vp]
     L.msspe_round_g_f32.restype = C.c_float
     L.msspe_round_g_f32.argtypes = [C.c_double]
     L.msspe_round_fixed_f32.restype = C.c_float
@@ -787,6 +804,60 @@ class Engine:
             return counts, stable, starts
         return counts, stable, starts, sites[:count.value]
 
+    def background_amplicons_packed(self, d_packed: int, total_len: int, primers, max_mismatches: int, exact_3p: int,
+                                    chem: Chem, tm_threshold: float, mode, min_len: int, max_len: int,
+                                    record_start=None, k: int | None = None, d_amplicons: int = 0, capacity: int = 0,
+                                    d_count: int = 0):
+        """Off-target amplicons on a resident stream (msspe_background_amplicons_packed_dev): pairs of stable sites, a
+        plus-strand one at p and a minus-strand one at q >= p of the same record with min_len <= q + k - p <= max_len.
+        record_start: the record starts put_stream_packed returned (None: the stream is one record).  Returns
+        (counts, stable, amplicons, total): uint64 (n, 2) each -- sites and stable sites per strand, amplicons with
+        the primer as forward [:, 0] and as reverse [:, 1] -- and the number of amplicons.  d_amplicons / capacity /
+        d_count: raw device addresses of an AMPLICON_DTYPE list and its uint64 count (added to); 0 = no list."""
+        w, k = _words_k(primers, k)
+        counts = np.zeros((len(w), 2), dtype=np.uint64)
+        stable = np.zeros((len(w), 2), dtype=np.uint64)
+        amps = np.zeros((len(w), 2), dtype=np.uint64)
+        total = C.c_uint64(0)
+        mm, opt = MismatchOpt(max_mismatches, exact_3p), AmpliconOpt(min_len, max_len)
+        starts = None if record_start is None else np.ascontiguousarray(record_start, dtype=np.uint64)
+        self._check(self.L.msspe_background_amplicons_packed_dev(
+            self.ptr, C.c_void_p(d_packed), total_len, k, C.byref(mm), w.ctypes.data, len(w), C.byref(chem),
+            self._thal_mode(mode), tm_threshold, C.byref(opt), None if starts is None else starts.ctypes.data,
+            0 if starts is None else len(starts), counts.ctypes.data, stable.ctypes.data, amps.ctypes.data,
+            C.byref(total), C.c_void_p(d_amplicons), capacity, C.c_void_p(d_count)))
+        return counts, stable, amps, int(total.value)
+
+    def background_amplicons(self, records, primers, max_mismatches: int, exact_3p: int, chem: Chem,
+                             tm_threshold: float, mode, min_len: int, max_len: int, k: int | None = None,
+                             capacity: int | None = None):
+        """Host form (msspe_background_amplicons): returns (counts, stable, amplicons, total, starts), or with a list
+        capacity (..., starts, list) -- list an AMPLICON_DTYPE array sorted by (pos, len, fwd, rev).  A capacity below
+        the number of amplicons raises MsspeError (MSSPE_ERR_CAPACITY) carrying .count, .counts, .stable, .amplicons,
+        .total and the truncated .list."""
+        _recs, ptrs, lens, n = self._records(records)
+        w, k = _words_k(primers, k)
+        counts = np.zeros((len(w), 2), dtype=np.uint64)
+        stable = np.zeros((len(w), 2), dtype=np.uint64)
+        amps = np.zeros((len(w), 2), dtype=np.uint64)
+        starts = np.zeros(n, dtype=np.uint64)
+        total, count = C.c_uint64(0), C.c_uint64(0)
+        mm, opt = MismatchOpt(max_mismatches, exact_3p), AmpliconOpt(min_len, max_len)
+        lst = np.zeros(max(capacity, 1), dtype=AMPLICON_DTYPE) if capacity is not None else None
+        rc = self.L.msspe_background_amplicons(
+            self.ptr, ptrs, lens, n, k, C.byref(mm), w.ctypes.data, len(w), C.byref(chem), self._thal_mode(mode),
+            tm_threshold, C.byref(opt), counts.ctypes.data, stable.ctypes.data, amps.ctypes.data, C.byref(total),
+            lst.ctypes.data if lst is not None else None, capacity or 0, C.byref(count), starts.ctypes.data)
+        if rc:
+            err = MsspeError(rc, self.L.msspe_last_error(self.ptr).decode())
+            err.count, err.counts, err.stable, err.amplicons = int(count.value), counts, stable, amps
+            err.total = int(total.value)
+            err.list = lst[:min(int(count.value), capacity or 0)] if lst is not None else None
+            raise err
+        if lst is None:
+            return counts, stable, amps, int(total.value), starts
+        return counts, stable, amps, int(total.value), starts, lst[:count.value]
+
     def pair_stage_samples(self):
         """[(row, col, reason bits)] for up to 1024 pairs the integer stage handed on."""
         v = (C.c_uint64 * 1024)()
@@ -868,6 +939,12 @@ class Engine:
         dev = C.c_void_p()
         self._check(self.L.msspe_device_put_rows_packed(self.ptr, ptrs, lens, n_seq, seq_len, C.byref(dev)))
         return int(dev.value)
+
+    def device_get(self, device_ptr: int, nbytes: int) -> np.ndarray:
+        """nbytes bytes at a device address, behind everything queued on the engine's stream (msspe_device_get)."""
+        out = np.zeros(nbytes, dtype=np.uint8)
+        self._check(self.L.msspe_device_get(self.ptr, C.c_void_p(device_ptr), nbytes, out.ctypes.data))
+        return out
 
     def device_free(self, device_ptr: int) -> None:
         self._check(self.L.msspe_device_free(self.ptr, C.c_void_p(device_ptr)))
