@@ -78,6 +78,12 @@ SCORED_SITE_DTYPE = np.dtype([("primer", np.uint32), ("pos", np.uint32), ("misma
                               ("strand", np.uint16), ("stable", np.uint32), ("dg", np.float64), ("t", np.float64)])
 THAL_MODES = {"any": 1, "end1": 2}
 
+# msspe_thal_detail: the full thal record of one pair (msspe_thal_detail_pairs), what ntthal prints per input line
+THAL_DETAIL_DTYPE = np.dtype([("dS", np.float64), ("dH", np.float64), ("dG", np.float64), ("t", np.float64),
+                              ("no_structure", np.int32), ("n_pairs", np.int32),
+                              ("ps1", np.uint8, (32,)), ("ps2", np.uint8, (32,))])
+assert THAL_DETAIL_DTYPE.itemsize == 104
+
 # msspe_amplicon: a plus-strand stable site of primer fwd at pos and a minus-strand one of primer rev, len columns on
 AMPLICON_DTYPE = np.dtype([("fwd", np.uint32), ("rev", np.uint32), ("pos", np.uint32), ("len", np.uint32)])
 
@@ -233,6 +239,7 @@ def load_library() -> C.CDLL:
         C.POINTER(Chem), C.c_int, C.c_float, C.POINTER(AmpliconOpt), vp, vp, vp, C.POINTER(C.c_uint64), vp,
         C.c_uint64, C.POINTER(C.c_uint64), vp]
     L.msspe_device_get.argtypes = [vp, vp, C.c_size_t, vp]
+    L.msspe_thal_detail_pairs.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(Chem), C.c_int, vp]
     L.msspe_round_g_f32.restype = C.c_float
     L.msspe_round_g_f32.argtypes = [C.c_double]
     L.msspe_round_fixed_f32.restype = C.c_float
@@ -857,6 +864,21 @@ class Engine:
         if lst is None:
             return counts, stable, amps, int(total.value), starts
         return counts, stable, amps, int(total.value), starts, lst[:count.value]
+
+    def thal_detail(self, a, b, chem: Chem | None = None, mode="any") -> np.ndarray:
+        """Full thal record of the pairs (a[i], b[i]) (msspe_thal_detail_pairs): two equal-length lists of strings of
+        one length; mode "any" (1) or "end1" (2).  Returns a THAL_DETAIL_DTYPE array, one record per pair: dS
+        (salt-corrected), dH, dG, t, no_structure, n_pairs and the traced base pairs ps1 / ps2 (ps1[i-1] = 1-based
+        partner in the REVERSED oligo 2, 0 = unpaired).  A record without a structure is all zero but no_structure."""
+        a, b = list(a), list(b)
+        k = len(a[0]) if a else 2          # an empty call's length does not matter
+        if len(a) != len(b) or any(len(s) != k for s in a) or any(len(s) != k for s in b):
+            raise MsspeError(1, "thal_detail needs two equal-length lists of oligos of one length")
+        chem = chem or Chem.ntthal()
+        out = np.zeros(len(a), dtype=THAL_DETAIL_DTYPE)
+        self._check(self.L.msspe_thal_detail_pairs(self.ptr, "".join(a).encode(), "".join(b).encode(), len(a), k,
+                                                   C.byref(chem), self._thal_mode(mode), out.ctypes.data))
+        return out
 
     def pair_stage_samples(self):
         """[(row, col, reason bits)] for up to 1024 pairs the integer stage handed on."""
