@@ -109,6 +109,10 @@ int msspe_set_option(msspe_ctx *ctx, const char *key, const char *value);
  *   "background_thal_slabs" / "background_thal_redone"
  *                     the last msspe_background_thal* call: slabs scored, and slabs whose sites did not fit the work
  *                     list and were split and listed again
+ *   "background_thal_flank_classes" / "background_thal_truncated"
+ *                     the last scored call (msspe_background_thal* / _amplicons*, with or without a flank): distinct
+ *                     (fl, fr) classes that were scored (1 at flank 0 when there were sites), and sites whose template
+ *                     found fewer than `flank` base columns on either side
  *   "amplicon_keys_cap_log2"  the option's current value
  *   "amplicon_keys" / "amplicon_key_grows"
  *                     the last msspe_background_amplicons* call: stable keys it joined, and doublings of the key
@@ -582,7 +586,7 @@ int msspe_background_sites(msspe_ctx *ctx, const char *const *records, const siz
  *   strand 0 (plus):  o2 = revcomp(w);
  *   strand 1 (minus): o2 = w  (the near-copy of u there is revcomp(w), whose partner strand is w itself).
  * Both oligos are k bases long, and an exact site gives o2 = revcomp(u) on either strand.  Bases beyond the window
- * (dangling ends) are not part of the score.
+ * (dangling ends) are not part of the score; msspe_background_thal_flank* below adds them.
  * The SITE SCORE is thal of (oligo 1 = u, oligo 2 = o2) under chem; mode is 1 for ANY and 2 for END1, the numbering of
  * msspe_thal_detail_pairs (END1: structures that close on the primer's 3' base, the ones that can prime).  Raw dG is
  * +inf without a structure and raw t is 0 without one.  t_site = max(0, t), and a site is STABLE iff
@@ -626,6 +630,39 @@ int msspe_background_thal(msspe_ctx *ctx, const char *const *records, const size
                           int mode, float tm_threshold, uint64_t *sites_out, uint64_t *stable_out,
                           msspe_scored_site *sites, uint64_t capacity, uint64_t *count_out,
                           uint64_t *record_start_out);
+
+/* ---- the same score with template flanks: dangling ends (engine extension) -----------------------------------
+ * A real template does not stop at the window: the bases next to it stack on the duplex ends (dangling ends, terminal
+ * mismatches) and let thal find shifted or bulged alignments, which is how Primer3 scores template mispriming.  Each
+ * call below is its sibling above with one argument, flank = f, after tm_threshold; 0 <= f <= 4 and k + 2 f <= 32.
+ * Take a site {primer u, pos p, strand s}; sites, mismatch counts and sites_out do not depend on the flank.
+ *   fl = the consecutive base columns (upper-case A C G T) that end at column p - 1, at most f;
+ *   fr = the consecutive base columns that start at column p + k, at most f.
+ * An invalid column stops the count: N, IUPAC codes, lower case, '-', the separator between two records and the ends
+ * of the stream.  A flank therefore never crosses a record boundary and the template oligo is pure ACGT.
+ *   The EXTENDED WINDOW is W = stream[p - fl, p + k + fr); o2 = revcomp(W) on the plus strand and W on the minus
+ *   strand, k + fl + fr bases; the site score is thal of (oligo 1 = u, oligo 2 = o2), mode and chemistry as above.
+ * t_site, the stable rule and msspe_t_cut are unchanged, and f = 0 is exactly the definition above: the calls without
+ * _flank are the f = 0 case of the same pass, bit for bit.  Records, lists, counts, sorting, the capacity contract,
+ * the work list and its slabs are the siblings'; msspe_scored_site is unchanged.
+ * Routing: the sites of a work-list chunk are grouped by class (fl, fr) on the device, and every non-empty class is
+ * scored as one explicit pair list with template length k + fl + fr.  Class (0, 0) -- the only one at f = 0 -- takes
+ * the routing described above; every other class is a rectangle and runs one wave per pair where the wave kernel takes
+ * the template's length, then the dense kernel.  Options force_generic, wave_kernel, list_cap_log2 and
+ * site_list_cap_log2 apply as above.  At f = 0 no additional kernel runs.  msspe_get_info
+ * "background_thal_flank_classes" / "background_thal_truncated": classes scored by the last call / sites with fl < f
+ * or fr < f.
+ * Errors: MSSPE_ERR_ARG for a flank outside 0..4 or k + 2 flank > 32; everything else as the siblings. */
+int msspe_background_thal_flank_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, size_t total_len, int k,
+                                           const msspe_mismatch_opt *mm, const uint64_t *words, int n,
+                                           const msspe_chem *chem, int mode, float tm_threshold, int flank,
+                                           uint64_t *sites_out, uint64_t *stable_out, msspe_scored_site *d_sites,
+                                           uint64_t capacity, uint64_t *d_count);
+int msspe_background_thal_flank(msspe_ctx *ctx, const char *const *records, const size_t *record_bytes,
+                                int n_records, int k, const msspe_mismatch_opt *mm, const uint64_t *words, int n,
+                                const msspe_chem *chem, int mode, float tm_threshold, int flank, uint64_t *sites_out,
+                                uint64_t *stable_out, msspe_scored_site *sites, uint64_t capacity,
+                                uint64_t *count_out, uint64_t *record_start_out);
 
 /* ---- off-target amplicons from the stable sites (engine extension) ---------------------------------------------
  * One stable off-target site costs a little primer; two that face each other within a few hundred bases amplify the
@@ -683,6 +720,22 @@ int msspe_background_amplicons(msspe_ctx *ctx, const char *const *records, const
                                uint64_t *sites_out, uint64_t *stable_out, uint64_t *amplicons_out,
                                uint64_t *n_amplicons_out, msspe_amplicon *amplicons, uint64_t capacity,
                                uint64_t *count_out, uint64_t *record_start_out);
+/* The same with template flanks: the amplicons of the stable sites of msspe_background_thal_flank* (flank after
+ * tm_threshold, 0..4, k + 2 flank <= 32).  len, pos and the same-record rule still refer to the k-column windows;
+ * flank 0 is the two calls above. */
+int msspe_background_amplicons_flank_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, size_t total_len, int k,
+                                                const msspe_mismatch_opt *mm, const uint64_t *words, int n,
+                                                const msspe_chem *chem, int mode, float tm_threshold, int flank,
+                                                const msspe_amplicon_opt *amp, const uint64_t *record_start,
+                                                int n_records, uint64_t *sites_out, uint64_t *stable_out,
+                                                uint64_t *amplicons_out, uint64_t *n_amplicons_out,
+                                                msspe_amplicon *d_amplicons, uint64_t capacity, uint64_t *d_count);
+int msspe_background_amplicons_flank(msspe_ctx *ctx, const char *const *records, const size_t *record_bytes,
+                                     int n_records, int k, const msspe_mismatch_opt *mm, const uint64_t *words, int n,
+                                     const msspe_chem *chem, int mode, float tm_threshold, int flank,
+                                     const msspe_amplicon_opt *amp, uint64_t *sites_out, uint64_t *stable_out,
+                                     uint64_t *amplicons_out, uint64_t *n_amplicons_out, msspe_amplicon *amplicons,
+                                     uint64_t capacity, uint64_t *count_out, uint64_t *record_start_out);
 
 
 /* ---- several devices of one node ----------------------------------------------------------

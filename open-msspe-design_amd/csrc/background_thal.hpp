@@ -18,6 +18,28 @@ hipError_t launch_site_oligos(const uint64_t *d_packed, size_t total_len, int k,
                               uint32_t first, uint32_t count, int n, uint64_t *pool, uint2 *list,
                               uint32_t *list_count, hipStream_t stream);
 
+// Template flanks (msspe_background_*_flank*): a site's template oligo takes up to kMaxSiteFlank base columns on
+// either side of its window; sites are classed by the (fl, fr) they found, class code fl * (flank + 1) + fr.
+constexpr int kMaxSiteFlank = 4;
+constexpr int kSiteClasses = (kMaxSiteFlank + 1) * (kMaxSiteFlank + 1);
+struct SiteClassOffsets {
+    uint32_t at[kSiteClasses];   // first list entry of each class's run
+};
+
+// launch_site_oligos with flanks: fl / fr = the base columns that end at pos - 1 / start at pos + k, up to `flank`
+// each (an invalid column, the separator and the stream's ends stop the count); the template oligo of the
+// k + fl + fr columns at pos - fl goes to pool[n + idx], the site's class code to cls[idx - first], and
+// class_count[code] (zeroed by the caller) counts the sites of each class.  1 <= flank <= kMaxSiteFlank, k + 2 flank <= 32.
+hipError_t launch_site_oligos_flank(const uint64_t *d_packed, size_t total_len, int k, int flank,
+                                    const msspe_site *d_sites, uint32_t first, uint32_t count, int n, uint64_t *pool,
+                                    uint8_t *cls, uint32_t *class_count, hipStream_t stream);
+
+// The pairs (primer, n + idx) of sites [first, first + count) grouped by class: class c fills
+// list[offsets.at[c] ...) in no particular order (offsets: the exclusive scan of launch_site_oligos_flank's counters;
+// cursor: kSiteClasses counters, zeroed by the caller).
+hipError_t launch_site_group(const msspe_site *d_sites, uint32_t first, uint32_t count, int n, const uint8_t *cls,
+                             const SiteClassOffsets &offsets, uint32_t *cursor, uint2 *list, hipStream_t stream);
+
 // Sites [0, count) with their raw scores dg[idx], t[idx]: counts[2 i + s] += sites, counts[2 n + 2 i + s] += stable
 // ones (max(0, t) > t_cut) of primer i on strand s; with d_count, one msspe_scored_site per site is appended to
 // d_out (at most capacity are stored, *d_count runs on).

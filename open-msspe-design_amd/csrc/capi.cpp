@@ -119,7 +119,8 @@ struct msspe_ctx {
     BackgroundSites background;        // msspe_background_sites*: primer words in plane form, per-primer counts
     CoverStage cover;                  // msspe_conflict_cover*: the symmetrised bitmap and the round state
     // msspe_background_thal*: the work list (site records, their pairs, raw dG and t), the site pool [primers | site
-    // oligos], 4 n counts (sites, then stable sites) and the slab's site counter
+    // oligos], 4 n counts (sites, then stable sites) and the slab's site counter; with a template flank also the
+    // sites' class codes, and the class counters with the grouping cursors behind them
     struct SiteWork {
         msspe_site *sites = nullptr;
         uint2 *list = nullptr;
@@ -130,7 +131,11 @@ struct msspe_ctx {
         unsigned long long *counts = nullptr;
         size_t counts_cap = 0;
         uint64_t *slab_count = nullptr;
+        uint8_t *cls = nullptr;
+        size_t cls_cap = 0;
+        uint32_t *class_counts = nullptr;   // [kSiteClasses] sites per class, [kSiteClasses] cursors
         long long slabs = 0, redone = 0;   // of the last call
+        long long flank_classes = 0, truncated = 0;
     } site_work;
     // msspe_background_amplicons*: the stable keys as the fold appends them (grown by doubling) and their count, the
     // sorted keys with their record ids, rocPRIM's temporary storage, the record starts, 2 n amplicon counts
@@ -713,6 +718,8 @@ int msspe_get_info(msspe_ctx *ctx, const char *key, long long *value_out)
     else if (k == "site_list_cap_log2") *value_out = ctx->opt.site_list_cap_log2;
     else if (k == "background_thal_slabs") *value_out = ctx->site_work.slabs;
     else if (k == "background_thal_redone") *value_out = ctx->site_work.redone;
+    else if (k == "background_thal_flank_classes") *value_out = ctx->site_work.flank_classes;
+    else if (k == "background_thal_truncated") *value_out = ctx->site_work.truncated;
     else if (k == "amplicon_keys_cap_log2") *value_out = ctx->opt.amplicon_keys_cap_log2;
     else if (k == "amplicon_keys") *value_out = ctx->amp_work.n_keys;
     else if (k == "amplicon_key_grows") *value_out = ctx->amp_work.grows;
@@ -761,7 +768,7 @@ void msspe_destroy(msspe_ctx *ctx)
         {
             auto &w = ctx->site_work;
             for (void *q : {(void *)w.sites, (void *)w.list, (void *)w.dg, (void *)w.t, (void *)w.pool,
-                            (void *)w.counts, (void *)w.slab_count})
+                            (void *)w.counts, (void *)w.slab_count, (void *)w.cls, (void *)w.class_counts})
                 if (q) (void)hipFree(q);
         }
         {
@@ -2330,9 +2337,21 @@ int msspe_background_sites(msspe_ctx *ctx, const char *const *records, const siz
 
 namespace {
 
-int ensure_site_work(msspe_ctx *ctx, size_t cap, int n)
+int ensure_site_work(msspe_ctx *ctx, size_t cap, int n, int flank)
 {
     auto &w = ctx->site_work;
+    if (flank && w.cls_cap < cap) {
+        if (w.cls) {
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            (void)hipFree(w.cls);
+        }
+        w.cls = nullptr;
+        w.cls_cap = 0;
+        HIP_TRY(ctx, hipMalloc((void **)&w.cls, cap));
+        w.cls_cap = cap;
+    }
+    if (flank && !w.class_counts)
+        HIP_TRY(ctx, hipMalloc((void **)&w.class_counts, sizeof(uint32_t) * 2 * kSiteClasses));
     if (w.cap != cap) {
         if (w.sites || w.list || w.dg || w.t) HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         for (void *q : {(void *)w.sites, (void *)w.list, (void *)w.dg, (void *)w.t})
@@ -2375,21 +2394,24 @@ int ensure_site_work(msspe_ctx *ctx, size_t cap, int n)
 
 // thal of the pairs list[0 .. count) -- (primer, n + site index) into the site pool -- by list index into the work
 // list's dg / t planes: the register-table list stages where they may take the length and chemistry, the wave list
-// stage, the dense kernel, over the caller's list as list 0 (ListChain).  *ovf_count[0] == count (k_site_oligos).
+// stage, the dense kernel, over the caller's list as list 0 (ListChain).  *ovf_count[0] == count (k_site_oligos, or
+// the class counter of a flanked call).  k2: the template oligos' length -- k without a flank; a longer template
+// (k + fl + fr) is a rectangle, which the register-table stages do not take: one wave per pair where the template is
+// within that kernel's range, then the dense kernel.
 // The hand-over statistics are the cross-dimer calls': this chain does not feed them.
-int score_site_pairs(msspe_ctx *ctx, ChemEntry *ce, bool end1, int n, int k, uint2 *list, uint32_t count)
+int score_site_pairs(msspe_ctx *ctx, ChemEntry *ce, bool end1, int n, int k, int k2, uint2 *list, uint32_t count)
 {
     auto &w = ctx->site_work;
     // a block without rows or columns whose columns start at n: (row - row0) * ncols + (col - col0) = the site index
-    const ScreenBlock b = screen_block(w.pool, n, k, k, 0, 0, n, n, plane_sinks(nullptr, nullptr, w.dg, w.t));
+    const ScreenBlock b = screen_block(w.pool, n, k, k2, 0, 0, n, n, plane_sinks(nullptr, nullptr, w.dg, w.t));
     GenericDimerArgs g = dimer_args(ctx, ce, b, end1 ? kModeEnd1 : kModeAny);
     PairKernelArgs a = pair_args(ctx, ce, b);
     StageList route;
-    if (reg_tables_ok(ctx, ce, k)) {
+    if (k2 == k && reg_tables_ok(ctx, ce, k)) {
         route.add(ListStage::MainList);
         route.add(ListStage::Wide);
     }
-    if (wave_ok(ctx, ce, k)) route.add(ListStage::Wave);
+    if (wave_ok(ctx, ce, std::max(k, k2))) route.add(ListStage::Wave);
     route.add(ListStage::Dense);
     HIP_TRY(ctx, hipMemsetAsync(ctx->ovf_count + 1, 0, 7 * sizeof(uint32_t), ctx->stream));
     return ListChain(ctx, ce, end1, list, (long)count).run(route, a, g, false);
@@ -2424,18 +2446,25 @@ int ensure_amplicon_keys(msspe_ctx *ctx, uint64_t have, uint64_t need)
     return MSSPE_OK;
 }
 
-// msspe_background_thal_packed_dev, and with keys the same pass for msspe_background_amplicons_packed_dev: the fold
-// of every slab also appends the keys of its stable sites to ctx->amp_work.keys; amp_work.n_keys counts them.
+// msspe_background_thal[_flank]_packed_dev, and with keys the same pass for
+// msspe_background_amplicons[_flank]_packed_dev: the fold of every slab also appends the keys of its stable sites to
+// ctx->amp_work.keys; amp_work.n_keys counts them.  flank 0: every template oligo is its window, one list per chunk
+// (k_site_oligos).  flank > 0: the sites of a chunk are classed by the flanks they found (k_site_oligos_flank), the
+// class counters come to the host, their exclusive scan places the classes' runs in the list (k_site_group), and
+// each non-empty class is scored as a list of its own with k2 = k + fl + fr.
 int background_thal_pass(msspe_ctx *ctx, const uint64_t *d_packed, size_t total_len, int k,
                          const msspe_mismatch_opt *mm, const uint64_t *words, int n, const msspe_chem *chem, int mode,
-                         float tm_threshold, uint64_t *sites_out, uint64_t *stable_out, msspe_scored_site *d_sites,
-                         uint64_t capacity, uint64_t *d_count, bool keys)
+                         float tm_threshold, int flank, uint64_t *sites_out, uint64_t *stable_out,
+                         msspe_scored_site *d_sites, uint64_t capacity, uint64_t *d_count, bool keys)
 {
     if (!ctx) return MSSPE_ERR_ARG;
     if (!d_packed || !mm || !sites_out || !stable_out || !chem || n < 0 || (n && !words) || (d_sites && !d_count))
         return fail(ctx, MSSPE_ERR_ARG, "null argument");
     if (mode != 1 && mode != 2) return fail(ctx, MSSPE_ERR_ARG, "background_thal: mode must be 1 (ANY) or 2 (END1)");
     if (k < 2 || k > 31) return fail(ctx, MSSPE_ERR_K, "background_thal: unsupported k (need 2 <= k <= 31)");
+    if (flank < 0 || flank > kMaxSiteFlank) return fail(ctx, MSSPE_ERR_ARG, "background_thal: flank must be 0..4");
+    if (k + 2 * flank > 32)
+        return fail(ctx, MSSPE_ERR_ARG, "background_thal: k + 2 * flank exceeds 32 bases, the longest template oligo");
     std::string err;
     int rc = BackgroundSites::check(total_len, k, mm->max_mismatches, mm->exact_3p, words, n, err);
     if (rc) return fail(ctx, rc, err);
@@ -2446,6 +2475,8 @@ int background_thal_pass(msspe_ctx *ctx, const uint64_t *d_packed, size_t total_
     auto &w = ctx->site_work;
     auto &aw = ctx->amp_work;
     w.slabs = w.redone = 0;
+    w.flank_classes = w.truncated = 0;
+    uint32_t classes_seen = 0;   // bit c: a site of class c was scored
     if (keys) aw.n_keys = aw.grows = 0;
     if (n == 0 || total_len < (size_t)k) return MSSPE_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -2459,9 +2490,9 @@ int background_thal_pass(msspe_ctx *ctx, const uint64_t *d_packed, size_t total_
     ChemEntry *ce = nullptr;
     if ((rc = chem_entry(ctx, *chem, tm_threshold, &ce, end1 ? kCutEndT : kCutAnyT))) return rc;
     const double cut = ce->c[0].g_cut;
-    if ((rc = ensure_workspace(ctx, (size_t)k * (size_t)k))) return rc;
+    if ((rc = ensure_workspace(ctx, (size_t)k * (size_t)(k + 2 * flank)))) return rc;
     if ((rc = ensure_overflow(ctx, (long)cap))) return rc;
-    if ((rc = ensure_site_work(ctx, cap, n))) return rc;
+    if ((rc = ensure_site_work(ctx, cap, n, flank))) return rc;
     if ((rc = ctx->background.prepare(k, words, n, ctx->stream, err))) return fail(ctx, rc, err);
     HIP_TRY(ctx, hipMemcpyAsync(w.pool, words, sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(w.counts, 0, sizeof(uint64_t) * 4 * (size_t)n, ctx->stream));
@@ -2508,9 +2539,41 @@ int background_thal_pass(msspe_ctx *ctx, const uint64_t *d_packed, size_t total_
         const uint32_t step = (uint32_t)std::min<uint64_t>(count, (uint64_t)ctx->list_cap);
         for (uint32_t c0 = 0; c0 < (uint32_t)count; c0 += step) {
             const uint32_t cnt = std::min(step, (uint32_t)count - c0);
-            HIP_TRY(ctx, launch_site_oligos(d_packed, total_len, k, w.sites, c0, cnt, n, w.pool, w.list + c0,
-                                            ctx->ovf_count, ctx->stream));
-            if ((rc = score_site_pairs(ctx, ce, end1, n, k, w.list + c0, cnt))) return rc;
+            if (!flank) {
+                HIP_TRY(ctx, launch_site_oligos(d_packed, total_len, k, w.sites, c0, cnt, n, w.pool, w.list + c0,
+                                                ctx->ovf_count, ctx->stream));
+                if ((rc = score_site_pairs(ctx, ce, end1, n, k, k, w.list + c0, cnt))) return rc;
+                classes_seen |= 1u;
+                continue;
+            }
+            uint32_t per_class[kSiteClasses];
+            HIP_TRY(ctx, hipMemsetAsync(w.class_counts, 0, sizeof(uint32_t) * 2 * kSiteClasses, ctx->stream));
+            HIP_TRY(ctx, launch_site_oligos_flank(d_packed, total_len, k, flank, w.sites, c0, cnt, n, w.pool, w.cls,
+                                                  w.class_counts, ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(per_class, w.class_counts, sizeof per_class, hipMemcpyDeviceToHost,
+                                        ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            const int n_classes = (flank + 1) * (flank + 1);
+            SiteClassOffsets off;
+            std::memset(&off, 0, sizeof off);
+            uint32_t at = 0;
+            for (int c = 0; c < n_classes; ++c) {
+                off.at[c] = at;
+                at += per_class[c];
+            }
+            if (at != cnt) return fail(ctx, MSSPE_ERR_DEVICE, "background_thal: the flank classes do not add up");
+            HIP_TRY(ctx, launch_site_group(w.sites, c0, cnt, n, w.cls, off, w.class_counts + kSiteClasses,
+                                           w.list + c0, ctx->stream));
+            for (int c = 0; c < n_classes; ++c) {
+                if (!per_class[c]) continue;
+                const int fl = c / (flank + 1), fr = c % (flank + 1);
+                classes_seen |= 1u << c;
+                if (fl < flank || fr < flank) w.truncated += per_class[c];
+                HIP_TRY(ctx, hipMemcpyAsync(ctx->ovf_count, w.class_counts + c, sizeof(uint32_t),
+                                            hipMemcpyDeviceToDevice, ctx->stream));
+                if ((rc = score_site_pairs(ctx, ce, end1, n, k, k + fl + fr, w.list + c0 + off.at[c], per_class[c])))
+                    return rc;
+            }
         }
         if (!keys) {
             HIP_TRY(ctx, launch_site_fold(w.sites, (uint32_t)count, w.dg, w.t, cut, n, w.counts, d_sites, capacity,
@@ -2530,10 +2593,21 @@ int background_thal_pass(msspe_ctx *ctx, const uint64_t *d_packed, size_t total_
     std::copy(host.begin(), host.begin() + 2 * (size_t)n, sites_out);
     std::copy(host.begin() + 2 * (size_t)n, host.end(), stable_out);
     if (keys) aw.n_keys = (long long)n_keys;
+    w.flank_classes = __builtin_popcount(classes_seen);
     return MSSPE_OK;
 }
 
 }  // namespace
+
+int msspe_background_thal_flank_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, size_t total_len, int k,
+                                           const msspe_mismatch_opt *mm, const uint64_t *words, int n,
+                                           const msspe_chem *chem, int mode, float tm_threshold, int flank,
+                                           uint64_t *sites_out, uint64_t *stable_out, msspe_scored_site *d_sites,
+                                           uint64_t capacity, uint64_t *d_count)
+{
+    return background_thal_pass(ctx, d_packed, total_len, k, mm, words, n, chem, mode, tm_threshold, flank, sites_out,
+                                stable_out, d_sites, capacity, d_count, false);
+}
 
 int msspe_background_thal_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, size_t total_len, int k,
                                      const msspe_mismatch_opt *mm, const uint64_t *words, int n,
@@ -2541,8 +2615,8 @@ int msspe_background_thal_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, s
                                      uint64_t *stable_out, msspe_scored_site *d_sites, uint64_t capacity,
                                      uint64_t *d_count)
 {
-    return background_thal_pass(ctx, d_packed, total_len, k, mm, words, n, chem, mode, tm_threshold, sites_out,
-                                stable_out, d_sites, capacity, d_count, false);
+    return msspe_background_thal_flank_packed_dev(ctx, d_packed, total_len, k, mm, words, n, chem, mode, tm_threshold,
+                                                  0, sites_out, stable_out, d_sites, capacity, d_count);
 }
 
 int msspe_background_thal(msspe_ctx *ctx, const char *const *records, const size_t *record_bytes, int n_records,
@@ -2550,6 +2624,17 @@ int msspe_background_thal(msspe_ctx *ctx, const char *const *records, const size
                           int mode, float tm_threshold, uint64_t *sites_out, uint64_t *stable_out,
                           msspe_scored_site *sites, uint64_t capacity, uint64_t *count_out,
                           uint64_t *record_start_out)
+{
+    return msspe_background_thal_flank(ctx, records, record_bytes, n_records, k, mm, words, n, chem, mode,
+                                       tm_threshold, 0, sites_out, stable_out, sites, capacity, count_out,
+                                       record_start_out);
+}
+
+int msspe_background_thal_flank(msspe_ctx *ctx, const char *const *records, const size_t *record_bytes,
+                                int n_records, int k, const msspe_mismatch_opt *mm, const uint64_t *words, int n,
+                                const msspe_chem *chem, int mode, float tm_threshold, int flank, uint64_t *sites_out,
+                                uint64_t *stable_out, msspe_scored_site *sites, uint64_t capacity,
+                                uint64_t *count_out, uint64_t *record_start_out)
 {
     if (!ctx) return MSSPE_ERR_ARG;
     if (!mm || !sites_out || !stable_out || !chem || n < 0 || (n && !words) || (sites && !count_out))
@@ -2571,8 +2656,9 @@ int msspe_background_thal(msspe_ctx *ctx, const char *const *records, const size
         }
     }
     if (e == hipSuccess) {
-        rc = msspe_background_thal_packed_dev(ctx, (const uint64_t *)d, L, k, mm, words, n, chem, mode, tm_threshold,
-                                              sites_out, stable_out, d_sites, capacity, d_count);
+        rc = msspe_background_thal_flank_packed_dev(ctx, (const uint64_t *)d, L, k, mm, words, n, chem, mode,
+                                                    tm_threshold, flank, sites_out, stable_out, d_sites, capacity,
+                                                    d_count);
         if (!rc && sites) {
             uint64_t count = 0;
             e = hipMemcpyAsync(&count, d_count, sizeof count, hipMemcpyDeviceToHost, ctx->stream);
@@ -2605,6 +2691,20 @@ int msspe_background_amplicons_packed_dev(msspe_ctx *ctx, const uint64_t *d_pack
                                           uint64_t *n_amplicons_out, msspe_amplicon *d_amplicons, uint64_t capacity,
                                           uint64_t *d_count)
 {
+    return msspe_background_amplicons_flank_packed_dev(ctx, d_packed, total_len, k, mm, words, n, chem, mode,
+                                                       tm_threshold, 0, amp, record_start, n_records, sites_out,
+                                                       stable_out, amplicons_out, n_amplicons_out, d_amplicons,
+                                                       capacity, d_count);
+}
+
+int msspe_background_amplicons_flank_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, size_t total_len, int k,
+                                                const msspe_mismatch_opt *mm, const uint64_t *words, int n,
+                                                const msspe_chem *chem, int mode, float tm_threshold, int flank,
+                                                const msspe_amplicon_opt *amp, const uint64_t *record_start,
+                                                int n_records, uint64_t *sites_out, uint64_t *stable_out,
+                                                uint64_t *amplicons_out, uint64_t *n_amplicons_out,
+                                                msspe_amplicon *d_amplicons, uint64_t capacity, uint64_t *d_count)
+{
     if (!ctx) return MSSPE_ERR_ARG;
     if (!amp || !amplicons_out || !n_amplicons_out || n < 0 || (d_amplicons && !d_count) ||
         (record_start && n_records <= 0))
@@ -2622,8 +2722,8 @@ int msspe_background_amplicons_packed_dev(msspe_ctx *ctx, const uint64_t *d_pack
             return fail(ctx, MSSPE_ERR_ARG, "background_amplicons: a record starts beyond the stream");
     }
     *n_amplicons_out = 0;
-    int rc = background_thal_pass(ctx, d_packed, total_len, k, mm, words, n, chem, mode, tm_threshold, sites_out,
-                                  stable_out, nullptr, 0, nullptr, true);
+    int rc = background_thal_pass(ctx, d_packed, total_len, k, mm, words, n, chem, mode, tm_threshold, flank,
+                                  sites_out, stable_out, nullptr, 0, nullptr, true);
     if (rc) return rc;
     std::fill(amplicons_out, amplicons_out + 2 * (size_t)n, (uint64_t)0);
     auto &w = ctx->amp_work;
@@ -2707,6 +2807,18 @@ int msspe_background_amplicons(msspe_ctx *ctx, const char *const *records, const
                                uint64_t *n_amplicons_out, msspe_amplicon *amplicons, uint64_t capacity,
                                uint64_t *count_out, uint64_t *record_start_out)
 {
+    return msspe_background_amplicons_flank(ctx, records, record_bytes, n_records, k, mm, words, n, chem, mode,
+                                            tm_threshold, 0, amp, sites_out, stable_out, amplicons_out,
+                                            n_amplicons_out, amplicons, capacity, count_out, record_start_out);
+}
+
+int msspe_background_amplicons_flank(msspe_ctx *ctx, const char *const *records, const size_t *record_bytes,
+                                     int n_records, int k, const msspe_mismatch_opt *mm, const uint64_t *words, int n,
+                                     const msspe_chem *chem, int mode, float tm_threshold, int flank,
+                                     const msspe_amplicon_opt *amp, uint64_t *sites_out, uint64_t *stable_out,
+                                     uint64_t *amplicons_out, uint64_t *n_amplicons_out, msspe_amplicon *amplicons,
+                                     uint64_t capacity, uint64_t *count_out, uint64_t *record_start_out)
+{
     if (!ctx) return MSSPE_ERR_ARG;
     if (!mm || !sites_out || !stable_out || !chem || !amp || !amplicons_out || !n_amplicons_out || n < 0 ||
         (n && !words) || (amplicons && !count_out))
@@ -2731,10 +2843,11 @@ int msspe_background_amplicons(msspe_ctx *ctx, const char *const *records, const
         }
     }
     if (e == hipSuccess) {
-        rc = msspe_background_amplicons_packed_dev(ctx, (const uint64_t *)d, L, k, mm, words, n, chem, mode,
-                                                   tm_threshold, amp, n_records > 0 ? starts.data() : nullptr,
-                                                   n_records, sites_out, stable_out, amplicons_out, n_amplicons_out,
-                                                   d_list, capacity, d_count);
+        rc = msspe_background_amplicons_flank_packed_dev(ctx, (const uint64_t *)d, L, k, mm, words, n, chem, mode,
+                                                         tm_threshold, flank, amp,
+                                                         n_records > 0 ? starts.data() : nullptr, n_records, sites_out,
+                                                         stable_out, amplicons_out, n_amplicons_out, d_list, capacity,
+                                                         d_count);
         if (!rc && amplicons) {
             uint64_t count = 0;
             e = hipMemcpyAsync(&count, d_count, sizeof count, hipMemcpyDeviceToHost, ctx->stream);

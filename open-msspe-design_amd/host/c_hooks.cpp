@@ -67,6 +67,7 @@ int odm_parse_args(int argc, const char *const *argv, char *out, size_t cap)
           << "\nbackground=" << a.background << "\nbackground_mismatches=" << a.background_mismatches
           << "\nbackground_3p_exact=" << a.background_3p_exact << "\nmax_background_sites=" << a.max_background_sites
           << "\nbackground_tm=" << a.background_tm_text << "\nbackground_thal=" << a.background_thal
+          << "\nbackground_flank=" << a.background_flank
           << "\n";
         emit(o.str(), out, cap);
         return 0;

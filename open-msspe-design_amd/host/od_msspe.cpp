@@ -81,6 +81,7 @@ const OptSpec kOpts[] = {
     {"--background-thal", "BACKGROUND_THAL", OptSpec::Str, OFF(background_thal)},
     {"--background-amplicon-max", "BACKGROUND_AMPLICON_MAX", OptSpec::OptInt, OFF(background_amplicon_max)},
     {"--background-amplicon-min", "BACKGROUND_AMPLICON_MIN", OptSpec::OptInt, OFF(background_amplicon_min)},
+    {"--background-flank", "BACKGROUND_FLANK", OptSpec::OptInt, OFF(background_flank)},
 };
 #undef OFF
 
@@ -204,6 +205,18 @@ Args Args::parse(int argc, const char *const *argv)
             throw UsageError(std::string("error: '") + given.first + "' needs '--background <FASTA>'");
         if (!a.background_scored)
             throw UsageError(std::string("error: '") + given.first + "' needs '--background-tm <C>'");
+    }
+    if (a.background_flank >= 0) {
+        if (a.background.empty()) throw UsageError("error: '--background-flank' needs '--background <FASTA>'");
+        if (!a.background_scored) throw UsageError("error: '--background-flank' needs '--background-tm <C>'");
+        if (a.background_flank > 4)
+            throw UsageError("error: invalid value '" + std::to_string(a.background_flank) +
+                             "' for '--background-flank <...>'\n  [possible values: 0, 1, 2, 3, 4]");
+        if (a.kmer_size + 2 * a.background_flank > 32)
+            throw UsageError("error: '--kmer-size " + std::to_string(a.kmer_size) + "' with '--background-flank " +
+                             std::to_string(a.background_flank) + "' is longer than 32 bases");
+    } else {
+        a.background_flank = 0;
     }
     if (a.background_amplicon_min >= 0 && a.background_amplicon_max < 0)
         throw UsageError("error: '--background-amplicon-min' needs '--background-amplicon-max <LEN>'");
@@ -998,7 +1011,7 @@ std::vector<std::pair<uint64_t, uint64_t>> DeviceBackground::sites(const std::ve
 
 std::vector<std::pair<uint64_t, uint64_t>> DeviceBackground::scored(
     const std::vector<std::string> &words, int max_mismatches, int exact_3p, const msspe_chem &chem, int mode,
-    float tm_threshold, std::vector<std::pair<uint64_t, uint64_t>> &stable_out) const
+    float tm_threshold, std::vector<std::pair<uint64_t, uint64_t>> &stable_out, int flank) const
 {
     std::vector<std::pair<uint64_t, uint64_t>> out(words.size());
     stable_out.assign(words.size(), {0, 0});
@@ -1012,9 +1025,13 @@ std::vector<std::pair<uint64_t, uint64_t>> DeviceBackground::scored(
         int rc = msspe_pack_oligos(flat.data(), n, k, packed.data());
         if (rc) eng_.fail(rc);
         const msspe_mismatch_opt mm{std::min(max_mismatches, k), std::min(exact_3p, k)};
-        rc = msspe_background_thal_packed_dev(eng_.ctx(), static_cast<const uint64_t *>(dev_), len_, k, &mm,
-                                              packed.data(), n, &chem, mode, tm_threshold, counts.data(),
-                                              stable.data(), nullptr, 0, nullptr);
+        const int f = std::min(flank, std::max(0, (32 - k) / 2));
+        rc = f ? msspe_background_thal_flank_packed_dev(eng_.ctx(), static_cast<const uint64_t *>(dev_), len_, k, &mm,
+                                                        packed.data(), n, &chem, mode, tm_threshold, f, counts.data(),
+                                                        stable.data(), nullptr, 0, nullptr)
+               : msspe_background_thal_packed_dev(eng_.ctx(), static_cast<const uint64_t *>(dev_), len_, k, &mm,
+                                                  packed.data(), n, &chem, mode, tm_threshold, counts.data(),
+                                                  stable.data(), nullptr, 0, nullptr);
         if (rc) eng_.fail(rc);
         for (int j = 0; j < n; ++j) {
             out[cls.second[(size_t)j]] = {counts[2 * (size_t)j], counts[2 * (size_t)j + 1]};
@@ -1027,7 +1044,8 @@ std::vector<std::pair<uint64_t, uint64_t>> DeviceBackground::scored(
 std::vector<std::pair<uint64_t, uint64_t>> DeviceBackground::amplicons(
     const std::vector<std::string> &words, int max_mismatches, int exact_3p, const msspe_chem &chem, int mode,
     float tm_threshold, uint32_t min_len, uint32_t max_len, std::vector<std::pair<uint64_t, uint64_t>> &stable_out,
-    std::vector<std::pair<uint64_t, uint64_t>> &amplicons_out, std::vector<msspe_amplicon> &list_out) const
+    std::vector<std::pair<uint64_t, uint64_t>> &amplicons_out, std::vector<msspe_amplicon> &list_out,
+    int flank) const
 {
     std::vector<std::pair<uint64_t, uint64_t>> out(words.size());
     stable_out.assign(words.size(), {0, 0});
@@ -1055,12 +1073,16 @@ std::vector<std::pair<uint64_t, uint64_t>> DeviceBackground::amplicons(
             void *d_list = nullptr;
             if ((rc = msspe_device_put(eng_.ctx(), zero.data(), zero.size(), &d_list))) eng_.fail(rc);
             uint64_t *d_count = reinterpret_cast<uint64_t *>(static_cast<char *>(d_list) + list_bytes);
-            rc = msspe_background_amplicons_packed_dev(eng_.ctx(), static_cast<const uint64_t *>(dev_), len_, k, &mm,
-                                                       packed.data(), n, &chem, mode, tm_threshold, &opt,
-                                                       starts_.data(), (int)starts_.size(), counts.data(),
-                                                       stable.data(), amps.data(), &total,
-                                                       pair ? static_cast<msspe_amplicon *>(d_list) : nullptr,
-                                                       capacity, d_count);
+            const int f = std::min(flank, std::max(0, (32 - k) / 2));
+            msspe_amplicon *d_amps = pair ? static_cast<msspe_amplicon *>(d_list) : nullptr;
+            rc = f ? msspe_background_amplicons_flank_packed_dev(
+                         eng_.ctx(), static_cast<const uint64_t *>(dev_), len_, k, &mm, packed.data(), n, &chem, mode,
+                         tm_threshold, f, &opt, starts_.data(), (int)starts_.size(), counts.data(), stable.data(),
+                         amps.data(), &total, d_amps, capacity, d_count)
+                   : msspe_background_amplicons_packed_dev(
+                         eng_.ctx(), static_cast<const uint64_t *>(dev_), len_, k, &mm, packed.data(), n, &chem, mode,
+                         tm_threshold, &opt, starts_.data(), (int)starts_.size(), counts.data(), stable.data(),
+                         amps.data(), &total, d_amps, capacity, d_count);
             if (!rc) rc = msspe_device_get(eng_.ctx(), d_count, sizeof count, &count);
             if (!rc && count <= capacity) {
                 list.resize((size_t)count);
@@ -1124,13 +1146,14 @@ std::string background_report_amplicons(const std::vector<std::string> &names,
 std::string background_report_scored(const std::vector<std::string> &names,
                                      const std::vector<std::pair<uint64_t, uint64_t>> &sites,
                                      const std::vector<std::pair<uint64_t, uint64_t>> &stable, int max_mismatches,
-                                     int exact_3p, int mode, float tm_threshold)
+                                     int exact_3p, int mode, float tm_threshold, int flank)
 {
     char thr[64];
     std::snprintf(thr, sizeof thr, "%.2f", (double)tm_threshold);
     std::string out = "\nBackground sites (up to " + std::to_string(max_mismatches) + " mismatches, last " +
                       std::to_string(exact_3p) + " bases exact; stable: thal " + (mode == 2 ? "END1" : "ANY") +
-                      " t >= " + thr + " C):\n";
+                      " t >= " + thr + " C" + (flank > 0 ? ", template flank " + std::to_string(flank) : std::string()) +
+                      "):\n";
     uint64_t plus = 0, minus = 0, s_plus = 0, s_minus = 0;
     for (size_t i = 0; i < names.size(); ++i) {
         out += "  " + names[i] + ": plus " + std::to_string(sites[i].first) + ", minus " +
@@ -1348,7 +1371,8 @@ int run(const Args &args, std::string &stdout_text)
                 std::vector<std::pair<uint64_t, uint64_t>> sites;
                 if (args.background_scored)
                     (void)background->scored(words, args.background_mismatches, args.background_3p_exact,
-                                             ntthal_chem(opts), bg_mode, args.background_tm, sites);
+                                             ntthal_chem(opts), bg_mode, args.background_tm, sites,
+                                             args.background_flank);
                 else
                     sites = background->sites(words, args.background_mismatches, args.background_3p_exact);
                 size_t kept = 0;
@@ -1409,18 +1433,22 @@ int run(const Args &args, std::string &stdout_text)
             const auto sites = background->amplicons(words, args.background_mismatches, args.background_3p_exact,
                                                      ntthal_chem(opts), bg_mode, args.background_tm,
                                                      (uint32_t)args.background_amplicon_min,
-                                                     (uint32_t)args.background_amplicon_max, stable, amps, list);
+                                                     (uint32_t)args.background_amplicon_max, stable, amps, list,
+                                                     args.background_flank);
             stdout_text += background_report_scored(names, sites, stable, args.background_mismatches,
-                                                    args.background_3p_exact, bg_mode, args.background_tm);
+                                                    args.background_3p_exact, bg_mode, args.background_tm,
+                                                    args.background_flank);
             stdout_text += background_report_amplicons(names, amps, list, *background,
                                                        (uint32_t)args.background_amplicon_min,
                                                        (uint32_t)args.background_amplicon_max);
         } else if (args.background_scored) {
             std::vector<std::pair<uint64_t, uint64_t>> stable;
             const auto sites = background->scored(words, args.background_mismatches, args.background_3p_exact,
-                                                  ntthal_chem(opts), bg_mode, args.background_tm, stable);
+                                                  ntthal_chem(opts), bg_mode, args.background_tm, stable,
+                                                  args.background_flank);
             stdout_text += background_report_scored(names, sites, stable, args.background_mismatches,
-                                                    args.background_3p_exact, bg_mode, args.background_tm);
+                                                    args.background_3p_exact, bg_mode, args.background_tm,
+                                                    args.background_flank);
         } else
             stdout_text += background_report(names, background->sites(words, args.background_mismatches,
                                                                       args.background_3p_exact),

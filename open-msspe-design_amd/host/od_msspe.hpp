@@ -77,6 +77,10 @@ struct Args {
     // in [background_amplicon_min, LEN] (msspe_background_amplicons; the minimum defaults to the k-mer size).  Report
     // only.  -1 = not given, nothing changes.
     int background_amplicon_max = -1, background_amplicon_min = -1;
+    // --background-flank F (with --background and --background-tm): the template oligo of every scored site takes up
+    // to F base columns on either side of the window (dangling ends; msspe_background_thal_flank, 0..4,
+    // kmer_size + 2 F <= 32).  -1 = not given (resolved to 0 by parse()): nothing changes.
+    int background_flank = -1;
     bool stddev_population = false;  // crate std-dev 0.1.0's divisor is unpinned
     static Args parse(int argc, const char *const *argv);   // throws UsageError
     static std::string usage();
@@ -233,11 +237,13 @@ public:
     std::vector<std::pair<uint64_t, uint64_t>> sites(const std::vector<std::string> &words, int max_mismatches,
                                                      int exact_3p) const;
     // the same with the thal score of every site (one msspe_background_thal_packed_dev call per word length):
-    // returns the (plus, minus) sites, stable_out the (plus, minus) stable ones
+    // returns the (plus, minus) sites, stable_out the (plus, minus) stable ones.  flank > 0: the _flank calls; a
+    // length class of k bases is scored with min(flank, (32 - k) / 2), the widest flank its template oligo has room for
     std::vector<std::pair<uint64_t, uint64_t>> scored(const std::vector<std::string> &words, int max_mismatches,
                                                       int exact_3p, const msspe_chem &chem, int mode,
                                                       float tm_threshold,
-                                                      std::vector<std::pair<uint64_t, uint64_t>> &stable_out) const;
+                                                      std::vector<std::pair<uint64_t, uint64_t>> &stable_out,
+                                                      int flank = 0) const;
     // scored() and, from the same pass, the off-target amplicons of the words' stable sites (one
     // msspe_background_amplicons_packed_dev call per word length on the resident stream; primers of different lengths
     // are not paired): amplicons_out (as forward, as reverse) per word; list_out: every amplicon, fwd and rev indices
@@ -247,7 +253,7 @@ public:
                                                          float tm_threshold, uint32_t min_len, uint32_t max_len,
                                                          std::vector<std::pair<uint64_t, uint64_t>> &stable_out,
                                                          std::vector<std::pair<uint64_t, uint64_t>> &amplicons_out,
-                                                         std::vector<msspe_amplicon> &list_out) const;
+                                                         std::vector<msspe_amplicon> &list_out, int flank = 0) const;
     // (record id, offset in the record) of stream position pos
     std::pair<std::string, uint64_t> locate(uint64_t pos) const;
 
@@ -264,11 +270,11 @@ std::string background_report(const std::vector<std::string> &names,
                               const std::vector<std::pair<uint64_t, uint64_t>> &sites, int max_mismatches,
                               int exact_3p);
 // The block with --background-tm: the heading names the rule ("; stable: thal ANY t >= 30.00 C"), every line and the
-// totals add "stable plus S, minus T"
+// totals add "stable plus S, minus T"; flank > 0 appends ", template flank F" behind the threshold
 std::string background_report_scored(const std::vector<std::string> &names,
                                      const std::vector<std::pair<uint64_t, uint64_t>> &sites,
                                      const std::vector<std::pair<uint64_t, uint64_t>> &stable, int max_mismatches,
-                                     int exact_3p, int mode, float tm_threshold);
+                                     int exact_3p, int mode, float tm_threshold, int flank = 0);
 // "Background amplicons (stable sites facing each other, MIN to MAX bases):", one line per primer (amplicons as
 // forward and as reverse), a totals line and the first 20 amplicons of the sorted list as
 // "record:offset, length, forward name, reverse name"

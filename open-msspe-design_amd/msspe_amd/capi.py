@@ -35,6 +35,8 @@ EXPORTS = [
     "msspe_device_put_stream_packed", "msspe_background_sites_packed_dev", "msspe_background_sites",
     "msspe_background_thal_packed_dev", "msspe_background_thal",
     "msspe_background_amplicons_packed_dev", "msspe_background_amplicons",
+    "msspe_background_thal_flank_packed_dev", "msspe_background_thal_flank",
+    "msspe_background_amplicons_flank_packed_dev", "msspe_background_amplicons_flank",
     "msspe_round_fixed_f32", "msspe_g_cut",
     "msspe_group_create", "msspe_group_destroy", "msspe_group_last_error", "msspe_group_size",
     "msspe_group_transport", "msspe_group_transport_reason", "msspe_group_rccl_available", "msspe_group_member", "msspe_group_set_option", "msspe_group_rows",
@@ -238,6 +240,13 @@ def load_library() -> C.CDLL:
         vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(MismatchOpt), u64p, C.c_int,
         C.POINTER(Chem), C.c_int, C.c_float, C.POINTER(AmpliconOpt), vp, vp, vp, C.POINTER(C.c_uint64), vp,
         C.c_uint64, C.POINTER(C.c_uint64), vp]
+    # the _flank siblings: one int (flank) behind tm_threshold
+    for name in ("msspe_background_thal_packed_dev", "msspe_background_thal", "msspe_background_amplicons_packed_dev",
+                 "msspe_background_amplicons"):
+        at = getattr(L, name).argtypes
+        cut = at.index(C.c_float) + 1
+        getattr(L, name.replace("_background_thal", "_background_thal_flank")
+                .replace("_background_amplicons", "_background_amplicons_flank")).argtypes = at[:cut] + [C.c_int] + at[cut:]
     L.msspe_device_get.argtypes = [vp, vp, C.c_size_t, vp]
     L.msspe_thal_detail_pairs.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(Chem), C.c_int, vp]
     L.msspe_round_g_f32.restype = C.c_float
@@ -768,28 +777,33 @@ class Engine:
 
     def background_thal_packed(self, d_packed: int, total_len: int, primers, max_mismatches: int, exact_3p: int,
                                chem: Chem, tm_threshold: float, mode="any", k: int | None = None, d_sites: int = 0,
-                               capacity: int = 0, d_count: int = 0):
+                               capacity: int = 0, d_count: int = 0, flank: int = 0):
         """Sites of each primer on a resident stream, each scored with thal (msspe_background_thal_packed_dev): the
         primer against the strand it would anneal to, mode "any" (1) or "end1" (2); a site is stable iff
         round_fixed_f32(max(0, t), 2) >= tm_threshold.  Returns (counts, stable), uint64 (n, 2) each: [:, 0] plus
         strand, [:, 1] minus.  d_sites / capacity / d_count: raw device addresses of a SCORED_SITE_DTYPE list and its
-        uint64 count (added to, the caller zeroes it); 0 = no list."""
+        uint64 count (added to, the caller zeroes it); 0 = no list.  flank: the template oligo takes up to this many
+        base columns on either side of the window (0..4, k + 2 flank <= 32; msspe_background_thal_flank_packed_dev);
+        0 is the blunt window and calls the function without _flank."""
         w, k = _words_k(primers, k)
         counts = np.zeros((len(w), 2), dtype=np.uint64)
         stable = np.zeros((len(w), 2), dtype=np.uint64)
         mm = MismatchOpt(max_mismatches, exact_3p)
-        self._check(self.L.msspe_background_thal_packed_dev(
+        fn, extra = ((self.L.msspe_background_thal_flank_packed_dev, (flank,)) if flank else
+                     (self.L.msspe_background_thal_packed_dev, ()))
+        self._check(fn(
             self.ptr, C.c_void_p(d_packed), total_len, k, C.byref(mm), w.ctypes.data, len(w), C.byref(chem),
-            self._thal_mode(mode), tm_threshold, counts.ctypes.data, stable.ctypes.data, C.c_void_p(d_sites), capacity,
-            C.c_void_p(d_count)))
+            self._thal_mode(mode), tm_threshold, *extra, counts.ctypes.data, stable.ctypes.data, C.c_void_p(d_sites),
+            capacity, C.c_void_p(d_count)))
         return counts, stable
 
     def background_thal(self, records, primers, max_mismatches: int, exact_3p: int, chem: Chem, tm_threshold: float,
-                        mode="any", k: int | None = None, capacity: int | None = None):
+                        mode="any", k: int | None = None, capacity: int | None = None, flank: int = 0):
         """Host form (msspe_background_thal): returns (counts, stable, starts), or with a list capacity
         (counts, stable, starts, sites) -- sites a SCORED_SITE_DTYPE array sorted by (primer, strand, pos), one record
         per site, stable or not.  A capacity below the number of sites raises MsspeError (MSSPE_ERR_CAPACITY) carrying
-        .count, .counts, .stable and the truncated .sites."""
+        .count, .counts, .stable and the truncated .sites.  flank: as background_thal_packed
+        (msspe_background_thal_flank when nonzero)."""
         _recs, ptrs, lens, n = self._records(records)
         w, k = _words_k(primers, k)
         counts = np.zeros((len(w), 2), dtype=np.uint64)
@@ -798,10 +812,11 @@ class Engine:
         mm = MismatchOpt(max_mismatches, exact_3p)
         sites = np.zeros(max(capacity, 1), dtype=SCORED_SITE_DTYPE) if capacity is not None else None
         count = C.c_uint64(0)
-        rc = self.L.msspe_background_thal(
+        fn, extra = ((self.L.msspe_background_thal_flank, (flank,)) if flank else (self.L.msspe_background_thal, ()))
+        rc = fn(
             self.ptr, ptrs, lens, n, k, C.byref(mm), w.ctypes.data, len(w), C.byref(chem), self._thal_mode(mode),
-            tm_threshold, counts.ctypes.data, stable.ctypes.data, sites.ctypes.data if sites is not None else None,
-            capacity or 0, C.byref(count), starts.ctypes.data)
+            tm_threshold, *extra, counts.ctypes.data, stable.ctypes.data,
+            sites.ctypes.data if sites is not None else None, capacity or 0, C.byref(count), starts.ctypes.data)
         if rc:
             err = MsspeError(rc, self.L.msspe_last_error(self.ptr).decode())
             err.count, err.counts, err.stable = int(count.value), counts, stable
@@ -814,13 +829,15 @@ class Engine:
     def background_amplicons_packed(self, d_packed: int, total_len: int, primers, max_mismatches: int, exact_3p: int,
                                     chem: Chem, tm_threshold: float, mode, min_len: int, max_len: int,
                                     record_start=None, k: int | None = None, d_amplicons: int = 0, capacity: int = 0,
-                                    d_count: int = 0):
+                                    d_count: int = 0, flank: int = 0):
         """Off-target amplicons on a resident stream (msspe_background_amplicons_packed_dev): pairs of stable sites, a
         plus-strand one at p and a minus-strand one at q >= p of the same record with min_len <= q + k - p <= max_len.
         record_start: the record starts put_stream_packed returned (None: the stream is one record).  Returns
         (counts, stable, amplicons, total): uint64 (n, 2) each -- sites and stable sites per strand, amplicons with
         the primer as forward [:, 0] and as reverse [:, 1] -- and the number of amplicons.  d_amplicons / capacity /
-        d_count: raw device addresses of an AMPLICON_DTYPE list and its uint64 count (added to); 0 = no list."""
+        d_count: raw device addresses of an AMPLICON_DTYPE list and its uint64 count (added to); 0 = no list.
+        flank: the stable sites are those of background_thal_packed at this flank
+        (msspe_background_amplicons_flank_packed_dev when nonzero)."""
         w, k = _words_k(primers, k)
         counts = np.zeros((len(w), 2), dtype=np.uint64)
         stable = np.zeros((len(w), 2), dtype=np.uint64)
@@ -828,20 +845,23 @@ class Engine:
         total = C.c_uint64(0)
         mm, opt = MismatchOpt(max_mismatches, exact_3p), AmpliconOpt(min_len, max_len)
         starts = None if record_start is None else np.ascontiguousarray(record_start, dtype=np.uint64)
-        self._check(self.L.msspe_background_amplicons_packed_dev(
+        fn, extra = ((self.L.msspe_background_amplicons_flank_packed_dev, (flank,)) if flank else
+                     (self.L.msspe_background_amplicons_packed_dev, ()))
+        self._check(fn(
             self.ptr, C.c_void_p(d_packed), total_len, k, C.byref(mm), w.ctypes.data, len(w), C.byref(chem),
-            self._thal_mode(mode), tm_threshold, C.byref(opt), None if starts is None else starts.ctypes.data,
+            self._thal_mode(mode), tm_threshold, *extra, C.byref(opt), None if starts is None else starts.ctypes.data,
             0 if starts is None else len(starts), counts.ctypes.data, stable.ctypes.data, amps.ctypes.data,
             C.byref(total), C.c_void_p(d_amplicons), capacity, C.c_void_p(d_count)))
         return counts, stable, amps, int(total.value)
 
     def background_amplicons(self, records, primers, max_mismatches: int, exact_3p: int, chem: Chem,
                              tm_threshold: float, mode, min_len: int, max_len: int, k: int | None = None,
-                             capacity: int | None = None):
+                             capacity: int | None = None, flank: int = 0):
         """Host form (msspe_background_amplicons): returns (counts, stable, amplicons, total, starts), or with a list
         capacity (..., starts, list) -- list an AMPLICON_DTYPE array sorted by (pos, len, fwd, rev).  A capacity below
         the number of amplicons raises MsspeError (MSSPE_ERR_CAPACITY) carrying .count, .counts, .stable, .amplicons,
-        .total and the truncated .list."""
+        .total and the truncated .list.  flank: as background_amplicons_packed (msspe_background_amplicons_flank when
+        nonzero)."""
         _recs, ptrs, lens, n = self._records(records)
         w, k = _words_k(primers, k)
         counts = np.zeros((len(w), 2), dtype=np.uint64)
@@ -851,9 +871,11 @@ class Engine:
         total, count = C.c_uint64(0), C.c_uint64(0)
         mm, opt = MismatchOpt(max_mismatches, exact_3p), AmpliconOpt(min_len, max_len)
         lst = np.zeros(max(capacity, 1), dtype=AMPLICON_DTYPE) if capacity is not None else None
-        rc = self.L.msspe_background_amplicons(
+        fn, extra = ((self.L.msspe_background_amplicons_flank, (flank,)) if flank else
+                     (self.L.msspe_background_amplicons, ()))
+        rc = fn(
             self.ptr, ptrs, lens, n, k, C.byref(mm), w.ctypes.data, len(w), C.byref(chem), self._thal_mode(mode),
-            tm_threshold, C.byref(opt), counts.ctypes.data, stable.ctypes.data, amps.ctypes.data, C.byref(total),
+            tm_threshold, *extra, C.byref(opt), counts.ctypes.data, stable.ctypes.data, amps.ctypes.data, C.byref(total),
             lst.ctypes.data if lst is not None else None, capacity or 0, C.byref(count), starts.ctypes.data)
         if rc:
             err = MsspeError(rc, self.L.msspe_last_error(self.ptr).decode())
