@@ -122,6 +122,9 @@ int msspe_set_option(msspe_ctx *ctx, const char *key, const char *value);
  *   "cover_rounds"    the last msspe_conflict_cover* call: rounds that deleted nodes
  *   "cover_keys_us" / "cover_symmetrise_us" / "cover_rounds_us"
  *                     the same call's device time of its phases: sort and keys, S = B | B^T, the rounds
+ *   "tube_rounds"     the last msspe_conflict_tubes* call: rounds that decided nodes
+ *   "tube_keys_us" / "tube_symmetrise_us" / "tube_rounds_us"
+ *                     the same call's device time of its phases: sort and keys, S = B | B^T, the keys, waits and rounds
  *   "hand_over_list_0" .. "hand_over_list_6"
  *                     pairs that entered hand-over list q of the cross-dimer calls (ANY and END) since the last read
  *                     of that key; reading synchronises the context's stream and resets the key, as
@@ -320,6 +323,38 @@ int msspe_conflict_cover_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int 
 int msspe_conflict_cover(msspe_ctx *ctx, const char *pool_ascii, int n, int k,
                          const msspe_chem *chem, float dg_threshold, int drop_self_pairs,
                          uint8_t *deleted_out, int *n_deleted_out);
+
+/* ---- the conflict graph split into reaction tubes (engine extension, no reference counterpart) ---- */
+
+#define MSSPE_TUBE_NONE 255
+
+/*
+ * Instead of deleting primers until no two survivors conflict, assign them to at most max_tubes (1..64) tubes so that
+ * no two primers of one tube conflict.  The graph is msspe_conflict_cover's: the pool's distinct oligos, S = B | B^T,
+ * with drop_self_pairs the diagonal and the reverse-complement partners cleared first.  A node that still conflicts
+ * with itself goes to no tube (MSSPE_TUBE_NONE), constrains nobody, and nobody waits for it.  The others are visited by
+ * descending key = (degree, lexicographic rank) -- the degree is the number of neighbours other than the node itself
+ * and is never updated; ties go to the lexicographically greatest oligo, as in the cover -- and each takes the lowest
+ * tube that holds no neighbour placed before it, or stays unplaced (MSSPE_TUBE_NONE) when every tube holds one; an
+ * unplaced node constrains nobody.  The tubes in use are 0 .. used - 1, without gaps.  The device computes the same
+ * assignment in rounds.  Largest degree first keeps the most primers once there are more than a few
+ * tubes; it is not a better cover: at max_tubes 1 it keeps fewer primers than msspe_conflict_cover does.
+ * Errors and limits: those of msspe_conflict_cover* (duplicate oligos, bits above 2 k and n above 262,144 are
+ * MSSPE_ERR_ARG), and MSSPE_ERR_ARG for max_tubes outside 1..64.  n == 0: MSSPE_OK, nothing written.
+ * msspe_get_info "tube_rounds" gives the number of rounds of the last call.
+ *
+ * d_bitmap as for msspe_conflict_cover_dev (read only).  d_tube[n] (device bytes): the tube, or MSSPE_TUBE_NONE.
+ * Enqueues on the context's stream; synchronises once for the key check and once per batch of rounds.
+ * n_tubes_used_out, n_unplaced_out (host, optional): tubes in use, and nodes in no tube (self-conflicting ones
+ * included). */
+int msspe_conflict_tubes_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const uint64_t *d_bitmap,
+                             int drop_self_pairs, int max_tubes, uint8_t *d_tube,
+                             int *n_tubes_used_out, int *n_unplaced_out);
+/* Host pool: screens the whole pool on the device (msspe_cross_dimer_dev, bitmap only, decisions path) and assigns the
+ * tubes there; no edge list is built.  tube_out[n] host bytes. */
+int msspe_conflict_tubes(msspe_ctx *ctx, const char *pool_ascii, int n, int k, const msspe_chem *chem,
+                         float dg_threshold, int drop_self_pairs, int max_tubes, uint8_t *tube_out,
+                         int *n_tubes_used_out, int *n_unplaced_out);
 
 /* Number of pairs the last cross-dimer call routed to the generic (slow) kernel because their
  * DP did not fit the fast kernel's register-resident table. */

@@ -5,6 +5,7 @@
 //   msspe_oligo_stats*     check_primers         /root/reference/od-msspe/src/primer.rs:143-166
 //   msspe_kmer_candidates* get_segment_manager + find_candidates_kmers  src/main.rs:196-235,331-406
 //   msspe_conflict_cover*  vertex_cover (the greedy cover of the conflict graph)  src/main.rs:754-798
+//   msspe_conflict_tubes*  (engine extension) the same graph split into reaction tubes instead of covered
 // There is no CPU fallback: every compute entry point needs a gfx950 device.
 #include "../../include/msspe_hip.h"
 
@@ -30,6 +31,7 @@
 #include "kmer_stage.hpp"
 #include "nn_params.hpp"
 #include "thal_dense.hpp"
+#include "tube_split.hpp"
 
 using namespace msspe;
 
@@ -118,6 +120,7 @@ struct msspe_ctx {
     MismatchCoverage mm_cov;           // msspe_segment_coverage_mm*: primer words, counts, per-segment minima
     BackgroundSites background;        // msspe_background_sites*: primer words in plane form, per-primer counts
     CoverStage cover;                  // msspe_conflict_cover*: the symmetrised bitmap and the round state
+    TubeStage tubes;                   // msspe_conflict_tubes*: its round state (the graph lives in cover's buffers)
     // msspe_background_thal*: the work list (site records, their pairs, raw dG and t), the site pool [primers | site
     // oligos], 4 n counts (sites, then stable sites) and the slab's site counter; with a template flank also the
     // sites' class codes, and the class counters with the grouping cursors behind them
@@ -729,6 +732,10 @@ int msspe_get_info(msspe_ctx *ctx, const char *key, long long *value_out)
     else if (k == "cover_keys_us") *value_out = ctx->cover.phase_us()[0];
     else if (k == "cover_symmetrise_us") *value_out = ctx->cover.phase_us()[1];
     else if (k == "cover_rounds_us") *value_out = ctx->cover.phase_us()[2];
+    else if (k == "tube_rounds") *value_out = ctx->tubes.rounds();
+    else if (k == "tube_keys_us") *value_out = ctx->tubes.phase_us()[0];
+    else if (k == "tube_symmetrise_us") *value_out = ctx->tubes.phase_us()[1];
+    else if (k == "tube_rounds_us") *value_out = ctx->tubes.phase_us()[2];
     else if (k.size() == 16 && k.compare(0, 15, "hand_over_list_") == 0 && k[15] >= '0' && k[15] <= '6') {
         // pairs that entered list q since the last read of this key; reading resets it
         *value_out = 0;
@@ -763,6 +770,7 @@ void msspe_destroy(msspe_ctx *ctx)
         ctx->kmer.release();
         ctx->kmer_rev.release();
         ctx->cover.release();
+        ctx->tubes.release();
         ctx->mm_cov.release();
         ctx->background.release();
         {
@@ -1409,6 +1417,74 @@ int msspe_conflict_cover(msspe_ctx *ctx, const char *pool_ascii, int n, int k, c
     if (!rc) rc = check_list_overrun(ctx);   // the cover has synchronised the stream
     if (rc) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(deleted_out, d_deleted, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return MSSPE_OK;
+}
+
+int msspe_conflict_tubes_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const uint64_t *d_bitmap,
+                             int drop_self_pairs, int max_tubes, uint8_t *d_tube, int *n_tubes_used_out,
+                             int *n_unplaced_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (n_tubes_used_out) *n_tubes_used_out = 0;
+    if (n_unplaced_out) *n_unplaced_out = 0;
+    if (n < 0 || (n && (!d_pool || !d_bitmap || !d_tube)))
+        return fail(ctx, MSSPE_ERR_ARG, "conflict tubes: null pool, bitmap or output");
+    if (max_tubes < 1 || max_tubes > kTubeMax)
+        return fail(ctx, MSSPE_ERR_ARG, "conflict tubes: max_tubes must be 1..64");
+    if (k < 2 || k > 32) return fail(ctx, MSSPE_ERR_K, "oligo length must be 2..32");
+    if (n > kCoverMaxN)
+        return fail(ctx, MSSPE_ERR_ARG, "conflict tubes: " + std::to_string(n) + " oligos, at most " +
+                                            std::to_string(kCoverMaxN) + " (the symmetrised bitmap is n^2 / 8 bytes)");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::string err;
+    const int rc = ctx->tubes.run(ctx->cover, d_pool, n, k, d_bitmap, drop_self_pairs != 0, max_tubes, d_tube,
+                                  n_tubes_used_out, n_unplaced_out, ctx->n_cu, ctx->stream, err);
+    return rc ? fail(ctx, rc, err) : MSSPE_OK;
+}
+
+int msspe_conflict_tubes(msspe_ctx *ctx, const char *pool_ascii, int n, int k, const msspe_chem *chem,
+                         float dg_threshold, int drop_self_pairs, int max_tubes, uint8_t *tube_out,
+                         int *n_tubes_used_out, int *n_unplaced_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (n_tubes_used_out) *n_tubes_used_out = 0;
+    if (n_unplaced_out) *n_unplaced_out = 0;
+    if (!pool_ascii || !chem || !tube_out || n < 0)
+        return fail(ctx, MSSPE_ERR_ARG, "conflict tubes: null pool, chemistry or output");
+    if (max_tubes < 1 || max_tubes > kTubeMax)
+        return fail(ctx, MSSPE_ERR_ARG, "conflict tubes: max_tubes must be 1..64");
+    if (n == 0) return MSSPE_OK;
+    if (k < 2 || k > 32) return fail(ctx, MSSPE_ERR_K, "oligo length must be 2..32");
+    if (n > kCoverMaxN)
+        return fail(ctx, MSSPE_ERR_ARG, "conflict tubes: " + std::to_string(n) + " oligos, at most " +
+                                            std::to_string(kCoverMaxN) + " (the symmetrised bitmap is n^2 / 8 bytes)");
+    std::vector<uint64_t> packed;
+    if (int rc = pack_pool(ctx, pool_ascii, n, k, packed)) return rc;
+    {   // duplicates before the screen, not after it
+        std::vector<uint64_t> s(packed);
+        std::sort(s.begin(), s.end());
+        if (std::adjacent_find(s.begin(), s.end()) != s.end())
+            return fail(ctx, MSSPE_ERR_ARG, "conflict tubes: the pool holds duplicate oligos");
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t words = ((size_t)n + 63) / 64;
+    DevBuf<uint64_t> d_pool, d_bitmap;
+    DevBuf<uint8_t> d_tube;
+    HIP_TRY(ctx, d_pool.alloc((size_t)n));
+    HIP_TRY(ctx, d_bitmap.alloc((size_t)n * words));
+    HIP_TRY(ctx, d_tube.alloc((size_t)n));
+    HIP_TRY(ctx, hipMemcpyAsync(d_pool, packed.data(), sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice,
+                                ctx->stream));
+    // the screen's decisions only: the bitmap is all the assignment reads
+    int rc = msspe_cross_dimer_dev(ctx, d_pool, n, k, chem, dg_threshold, 0, n, 0, n, nullptr, d_bitmap, nullptr,
+                                   nullptr);
+    if (!rc)
+        rc = msspe_conflict_tubes_dev(ctx, d_pool, n, k, d_bitmap, drop_self_pairs, max_tubes, d_tube, n_tubes_used_out,
+                                      n_unplaced_out);
+    if (!rc) rc = check_list_overrun(ctx);   // the assignment has synchronised the stream
+    if (rc) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(tube_out, d_tube, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return MSSPE_OK;
 }

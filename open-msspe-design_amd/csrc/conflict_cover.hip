@@ -270,20 +270,14 @@ void CoverStage::release()
     }
 }
 
-int CoverStage::run(const uint64_t *d_pool, int n, int k, const uint64_t *d_bitmap, bool drop_self_pairs,
-                    uint8_t *d_deleted, int *n_deleted, int n_cu, hipStream_t stream, std::string &err)
+int CoverStage::begin(int n, int k, hipStream_t stream, std::string &err)
 {
-    rounds_ = 0;
-    for (auto &p : phase_us_) p = 0;
-    if (n_deleted) *n_deleted = 0;
-    if (n == 0) return MSSPE_OK;
     const int W = (n + 63) / 64;
-    const size_t sbytes = sizeof(uint64_t) * (size_t)n * (size_t)W;
-    size_t sort_tmp = 0;
+    sort_tmp_ = 0;
     {
         uint64_t *nk = nullptr;
         uint32_t *nv = nullptr;
-        if (rocprim::radix_sort_pairs(nullptr, sort_tmp, nk, nk, nv, nv, (size_t)n, 0u, 2u * k, stream) != hipSuccess) {
+        if (rocprim::radix_sort_pairs(nullptr, sort_tmp_, nk, nk, nv, nv, (size_t)n, 0u, 2u * k, stream) != hipSuccess) {
             err = "conflict cover: rocPRIM radix sort sizing failed";
             return MSSPE_ERR_DEVICE;
         }
@@ -291,8 +285,9 @@ int CoverStage::run(const uint64_t *d_pool, int n, int k, const uint64_t *d_bitm
     // 0 S, 1 keys in, 2 keys sorted, 3 vals in, 4 perm, 5 sort scratch, 6 rank + partner, 7 key64 (per round),
     // 8 two active lists, 9 alive + kill + state, 10 the round's winners
     int rc;
-    if ((rc = ensure(0, sbytes, err)) || (rc = ensure(1, 8 * (size_t)n, err)) || (rc = ensure(2, 8 * (size_t)n, err)) ||
-        (rc = ensure(3, 4 * (size_t)n, err)) || (rc = ensure(4, 4 * (size_t)n, err)) || (rc = ensure(5, sort_tmp, err)) ||
+    if ((rc = ensure(0, sizeof(uint64_t) * (size_t)n * (size_t)W, err)) || (rc = ensure(1, 8 * (size_t)n, err)) ||
+        (rc = ensure(2, 8 * (size_t)n, err)) || (rc = ensure(3, 4 * (size_t)n, err)) ||
+        (rc = ensure(4, 4 * (size_t)n, err)) || (rc = ensure(5, sort_tmp_, err)) ||
         (rc = ensure(6, 8 * (size_t)n, err)) || (rc = ensure(7, 8 * (size_t)n, err)) ||
         (rc = ensure(8, 8 * (size_t)n, err)) ||
         (rc = ensure(9, align256(16 * (size_t)W) + sizeof(CoverState), err)) || (rc = ensure(10, 4 * (size_t)n, err)))
@@ -302,13 +297,18 @@ int CoverStage::run(const uint64_t *d_pool, int n, int k, const uint64_t *d_bitm
             err = "conflict cover: hipEventCreate failed";
             return MSSPE_ERR_DEVICE;
         }
+    (void)hipEventRecord(ev_[0], stream);
+    return MSSPE_OK;
+}
+
+int CoverStage::prepare(const uint64_t *d_pool, int n, int k, const uint64_t *d_bitmap, bool drop_self_pairs,
+                        hipStream_t stream, std::string &err)
+{
+    const int W = (n + 63) / 64;
     uint64_t *S = (uint64_t *)buf_[0], *keys_in = (uint64_t *)buf_[1], *keys = (uint64_t *)buf_[2];
     uint32_t *vals = (uint32_t *)buf_[3], *perm = (uint32_t *)buf_[4];
     uint32_t *rank = (uint32_t *)buf_[6];
     int32_t *partner = (int32_t *)((uint32_t *)buf_[6] + n);
-    uint64_t *key64 = (uint64_t *)buf_[7];
-    uint32_t *act[2] = {(uint32_t *)buf_[8], (uint32_t *)buf_[8] + n}, *win = (uint32_t *)buf_[10];
-    uint64_t *alive = (uint64_t *)buf_[9], *kill = alive + W;
     CoverState *st = (CoverState *)((char *)buf_[9] + align256(16 * (size_t)W));
     auto launched = [&](const char *what) -> int {
         const hipError_t e = hipGetLastError();
@@ -316,18 +316,15 @@ int CoverStage::run(const uint64_t *d_pool, int n, int k, const uint64_t *d_bitm
         err = std::string("conflict cover, ") + what + ": " + hipGetErrorString(e);
         return MSSPE_ERR_DEVICE;
     };
-    const int g256 = (n + 255) / 256;
+    int rc;
 
     // keys: ranks, duplicates, partners
-    (void)hipEventRecord(ev_[0], stream);
-    hipLaunchKernelGGL(k_cover_init, dim3(g256), dim3(256), 0, stream, W, alive, kill, n, st);
-    if (hipMemsetAsync(&st->err, 0, sizeof(uint32_t), stream) != hipSuccess ||
-        hipMemsetAsync(d_deleted, 0, (size_t)n, stream) != hipSuccess) {
+    if (hipMemsetAsync(&st->err, 0, sizeof(uint32_t), stream) != hipSuccess) {
         err = "conflict cover: hipMemsetAsync failed";
         return MSSPE_ERR_DEVICE;
     }
     hipLaunchKernelGGL(k_cover_keys, dim3((n + 255) / 256), dim3(256), 0, stream, d_pool, n, k, keys_in, vals, st);
-    if (rocprim::radix_sort_pairs(buf_[5], sort_tmp, keys_in, keys, vals, perm, (size_t)n, 0u, 2u * k, stream) !=
+    if (rocprim::radix_sort_pairs(buf_[5], sort_tmp_, keys_in, keys, vals, perm, (size_t)n, 0u, 2u * k, stream) !=
         hipSuccess) {
         err = "conflict cover: rocPRIM radix sort failed";
         return MSSPE_ERR_DEVICE;
@@ -337,17 +334,17 @@ int CoverStage::run(const uint64_t *d_pool, int n, int k, const uint64_t *d_bitm
     if ((rc = launched("keys"))) return rc;
     (void)hipEventRecord(ev_[1], stream);
 
-    CoverState hs{};
-    if (hipMemcpyAsync(&hs, st, sizeof hs, hipMemcpyDeviceToHost, stream) != hipSuccess ||
+    uint32_t herr = 0;
+    if (hipMemcpyAsync(&herr, &st->err, sizeof herr, hipMemcpyDeviceToHost, stream) != hipSuccess ||
         hipStreamSynchronize(stream) != hipSuccess) {
         err = "conflict cover: reading the key check failed";
         return MSSPE_ERR_DEVICE;
     }
-    if (hs.err & 2u) {
+    if (herr & 2u) {
         err = "conflict cover: a pool word has bits above 2 k";
         return MSSPE_ERR_ARG;
     }
-    if (hs.err & 1u) {
+    if (herr & 1u) {
         err = "conflict cover: the pool holds duplicate oligos (the graph's nodes are distinct primers)";
         return MSSPE_ERR_ARG;
     }
@@ -362,6 +359,48 @@ int CoverStage::run(const uint64_t *d_pool, int n, int k, const uint64_t *d_bitm
         hipLaunchKernelGGL(k_cover_drop_self, dim3((n + 255) / 256), dim3(256), 0, stream, S, n, W, partner);
     if ((rc = launched("symmetrise"))) return rc;
     (void)hipEventRecord(ev_[3], stream);
+    return MSSPE_OK;
+}
+
+void CoverStage::prepare_us(long long &keys_us, long long &symmetrise_us) const
+{
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, ev_[0], ev_[1]);
+    keys_us = (long long)(ms * 1000.0f);
+    ms = 0.f;
+    (void)hipEventElapsedTime(&ms, ev_[2], ev_[3]);
+    symmetrise_us = (long long)(ms * 1000.0f);
+}
+
+int CoverStage::run(const uint64_t *d_pool, int n, int k, const uint64_t *d_bitmap, bool drop_self_pairs,
+                    uint8_t *d_deleted, int *n_deleted, int n_cu, hipStream_t stream, std::string &err)
+{
+    rounds_ = 0;
+    for (auto &p : phase_us_) p = 0;
+    if (n_deleted) *n_deleted = 0;
+    if (n == 0) return MSSPE_OK;
+    const int W = (n + 63) / 64;
+    int rc;
+    if ((rc = begin(n, k, stream, err))) return rc;
+    uint64_t *S = (uint64_t *)buf_[0];
+    uint32_t *rank = (uint32_t *)buf_[6];
+    uint64_t *key64 = (uint64_t *)buf_[7];
+    uint32_t *act[2] = {(uint32_t *)buf_[8], (uint32_t *)buf_[8] + n}, *win = (uint32_t *)buf_[10];
+    uint64_t *alive = (uint64_t *)buf_[9], *kill = alive + W;
+    CoverState *st = (CoverState *)((char *)buf_[9] + align256(16 * (size_t)W));
+    auto launched = [&](const char *what) -> int {
+        const hipError_t e = hipGetLastError();
+        if (e == hipSuccess) return MSSPE_OK;
+        err = std::string("conflict cover, ") + what + ": " + hipGetErrorString(e);
+        return MSSPE_ERR_DEVICE;
+    };
+    hipLaunchKernelGGL(k_cover_init, dim3((n + 255) / 256), dim3(256), 0, stream, W, alive, kill, n, st);
+    if (hipMemsetAsync(d_deleted, 0, (size_t)n, stream) != hipSuccess) {
+        err = "conflict cover: hipMemsetAsync failed";
+        return MSSPE_ERR_DEVICE;
+    }
+    if ((rc = prepare(d_pool, n, k, d_bitmap, drop_self_pairs, stream, err))) return rc;
+    CoverState hs{};
 
     // rounds, kRoundsPerBatch per read of the done word; each round deletes at least the global maximum, so there are
     // at most n
@@ -393,12 +432,10 @@ int CoverStage::run(const uint64_t *d_pool, int n, int k, const uint64_t *d_bitm
         err = "conflict cover: hipEventSynchronize failed";
         return MSSPE_ERR_DEVICE;
     }
-    const int from[3] = {0, 2, 3}, to[3] = {1, 3, 4};   // keys, symmetrise, rounds (the key check's read between)
-    for (int p = 0; p < 3; ++p) {
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, ev_[from[p]], ev_[to[p]]);
-        phase_us_[p] = (long long)(ms * 1000.0f);
-    }
+    prepare_us(phase_us_[0], phase_us_[1]);   // keys, symmetrise (the key check's read between), rounds
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, ev_[3], ev_[4]);
+    phase_us_[2] = (long long)(ms * 1000.0f);
     rounds_ = hs.rounds;
     if (n_deleted) *n_deleted = (int)hs.n_deleted;
     return MSSPE_OK;

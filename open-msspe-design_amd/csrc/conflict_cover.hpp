@@ -20,6 +20,20 @@ public:
     int run(const uint64_t *d_pool, int n, int k, const uint64_t *d_bitmap, bool drop_self_pairs, uint8_t *d_deleted,
             int *n_deleted, int n_cu, hipStream_t stream, std::string &err);
     void release();
+    // The phases the tube split shares (csrc/tube_split.hip): begin() sizes the buffers for n oligos and starts the
+    // clock; prepare() ranks the oligos, refuses duplicates and bits above 2 k (MSSPE_ERR_ARG), and leaves S = B | B^T
+    // (self pairs dropped on request) in symmetrised() and the lexicographic ranks in ranks().  It synchronises the
+    // stream once, for the key check.  prepare_us(): device time of the two phases, once the stream has drained.
+    int begin(int n, int k, hipStream_t stream, std::string &err);
+    int prepare(const uint64_t *d_pool, int n, int k, const uint64_t *d_bitmap, bool drop_self_pairs,
+                hipStream_t stream, std::string &err);
+    void prepare_us(long long &keys_us, long long &symmetrise_us) const;
+    const uint64_t *symmetrised() const { return (const uint64_t *)buf_[0]; }
+    const uint32_t *ranks() const { return (const uint32_t *)buf_[6]; }
+    // buffers of the rounds, free between two calls: 8 n bytes of keys, two lists of n nodes, n counters
+    uint64_t *round_keys() const { return (uint64_t *)buf_[7]; }
+    uint32_t *round_lists() const { return (uint32_t *)buf_[8]; }
+    uint32_t *round_counters() const { return (uint32_t *)buf_[10]; }
     // the last run: rounds that deleted nodes, and device time of its phases in microseconds (sort and keys,
     // symmetrise, rounds)
     long long rounds() const { return rounds_; }
@@ -29,6 +43,7 @@ private:
     void *buf_[11] = {};
     size_t cap_[11] = {};
     hipEvent_t ev_[5] = {};
+    size_t sort_tmp_ = 0;
     long long rounds_ = 0;
     long long phase_us_[3] = {};
     int ensure(int slot, size_t bytes, std::string &err);

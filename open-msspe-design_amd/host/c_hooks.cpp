@@ -62,7 +62,7 @@ int odm_parse_args(int argc, const char *const *argv, char *out, size_t cap)
           << "\nsearch_windows_size=" << a.search_windows_size << "\nmv_conc=" << a.mv_conc
           << "\ndelta_g_threshold=" << a.delta_g_threshold << "\nkeep_all=" << a.keep_all
           << "\ncheck_hairpin=" << a.check_hairpin << "\ndo_align=" << a.do_align
-          << "\ntm_stddev=" << a.tm_stddev << "\ncover_on_device=" << a.cover_on_device
+          << "\ntm_stddev=" << a.tm_stddev << "\ncover_on_device=" << a.cover_on_device << "\ntubes=" << a.tubes
           << "\ncoverage_mismatches=" << a.coverage_mismatches << "\ncoverage_3p_exact=" << a.coverage_3p_exact
           << "\nbackground=" << a.background << "\nbackground_mismatches=" << a.background_mismatches
           << "\nbackground_3p_exact=" << a.background_3p_exact << "\nmax_background_sites=" << a.max_background_sites
@@ -90,6 +90,26 @@ int odm_vertex_cover(const char *primers_nl, const char *edges_nl, char *out, si
     }
     std::string s;
     for (const auto &d : vertex_cover(primers, g)) s += d + "\n";
+    return emit(s, out, cap);
+}
+
+// primers and edges as odm_vertex_cover.  Output: "word<TAB>tube" per primer in input order, tubes from 0, "-" for a
+// primer in no tube (assign_tubes, the sequential rule of DESIGN.md 4.9).
+int odm_assign_tubes(const char *primers_nl, const char *edges_nl, int max_tubes, char *out, size_t cap)
+{
+    ConflictGraph g;
+    const auto primers = lines(primers_nl);
+    g.nodes = primers;
+    for (const auto &e : lines(edges_nl)) {
+        const size_t c = e.find(',');
+        g.edges[e.substr(0, c)].insert(e.substr(c + 1));
+    }
+    const auto tubes = assign_tubes(primers, g, max_tubes);
+    std::string s;
+    for (const auto &p : primers) {
+        const int t = tubes.at(p);
+        s += p + "\t" + (t < 0 ? std::string("-") : std::to_string(t)) + "\n";
+    }
     return emit(s, out, cap);
 }
 

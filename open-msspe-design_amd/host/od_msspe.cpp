@@ -71,6 +71,7 @@ const OptSpec kOpts[] = {
     {"--device", "MSSPE_DEVICE", OptSpec::Int, OFF(device)},
     {"--devices", "MSSPE_DEVICES", OptSpec::Str, OFF(devices)},
     {"--cover-on-device", "COVER_ON_DEVICE", OptSpec::Bool, OFF(cover_on_device)},
+    {"--tubes", "TUBES", OptSpec::Int, OFF(tubes)},
     {"--coverage-mismatches", "COVERAGE_MISMATCHES", OptSpec::Int, OFF(coverage_mismatches)},
     {"--coverage-3p-exact", "COVERAGE_3P_EXACT", OptSpec::Str, OFF(coverage_3p_exact_text)},
     {"--background", "BACKGROUND", OptSpec::Str, OFF(background)},
@@ -126,7 +127,9 @@ std::string Args::usage()
     for (const auto &o : kOpts) u += std::string("      ") + o.flag + " <...>  [env: " + o.env + "=]\n";
     u += "      --stddev-population   divide the Tm variance by n instead of n-1\n";
     u += "\n--background <FASTA> screens the primers against unaligned background records (a host genome, rRNA) for\n"
-         "off-target sites on both strands; with --devices it runs on the first device.\n";
+         "off-target sites on both strands; with --devices it runs on the first device.\n"
+         "--tubes <N> (1..64) splits the primers into at most N reaction tubes in which no two primers conflict, instead\n"
+         "of deleting primers by the vertex cover; the CSV gains a 'tube' column. One tube is not a better cover.\n";
     return u;
 }
 
@@ -167,6 +170,18 @@ Args Args::parse(int argc, const char *const *argv)
     if (a.input.empty() || a.output.empty())
         throw UsageError("error: the following required arguments were not provided:\n"
                          "  --input <INPUT>\n  --output <OUTPUT>\n\n" + usage());
+    if (a.tubes > 64)
+        throw UsageError("error: invalid value '" + std::to_string(a.tubes) + "' for '--tubes <...>'\n  [0 .. 64]");
+    if (a.tubes > 0) {   // one device, one call, and a panel's own tubes are unknown
+        if (!a.devices.empty())
+            throw UsageError("error: '--tubes' runs on one device and cannot be combined with '--devices'");
+        if (a.cover_on_device == "true")
+            throw UsageError("error: '--tubes' replaces the vertex cover and cannot be combined with "
+                             "'--cover-on-device true'");
+        if (!a.existing_primers.empty())
+            throw UsageError("error: '--tubes' cannot be combined with '--existing-primers': the tubes of the panel's "
+                             "primers are unknown");
+    }
     if (a.coverage_mismatches > a.kmer_size)
         throw UsageError("error: '--coverage-mismatches " + std::to_string(a.coverage_mismatches) +
                          "' is larger than '--kmer-size " + std::to_string(a.kmer_size) + "'");
@@ -821,6 +836,106 @@ std::set<std::string> conflict_cover_on_device(Engine &eng, const std::vector<st
     return deleted;
 }
 
+std::map<std::string, int> assign_tubes(const std::vector<std::string> &primers, const ConflictGraph &g, int max_tubes)
+{
+    // the cover's graph (main.rs:754-771: symmetric, self loops kept) over the distinct primers; the set iterates in
+    // lexicographic order, so a node's id is its rank
+    const std::set<std::string> words(primers.begin(), primers.end());
+    std::vector<const std::string *> name;
+    std::map<std::string, int> id;
+    for (const auto &w : words) {
+        id.emplace(w, (int)name.size());
+        name.push_back(&w);
+    }
+    const int n = (int)name.size();
+    std::vector<std::set<int>> adj((size_t)n);
+    std::vector<char> self((size_t)n, 0);
+    for (const auto &kv : g.edges) {
+        const auto a = id.find(kv.first);
+        if (a == id.end()) continue;
+        for (const auto &w : kv.second) {
+            const auto b = id.find(w);
+            if (b == id.end()) continue;
+            if (a->second == b->second) self[(size_t)a->second] = 1;
+            else {
+                adj[(size_t)a->second].insert(b->second);
+                adj[(size_t)b->second].insert(a->second);
+            }
+        }
+    }
+    std::vector<int> order;
+    for (int v = 0; v < n; ++v)
+        if (!self[(size_t)v]) order.push_back(v);
+    std::sort(order.begin(), order.end(), [&](int a, int b) {   // descending (degree, rank)
+        const size_t da = adj[(size_t)a].size(), db = adj[(size_t)b].size();
+        return da != db ? da > db : a > b;
+    });
+    std::vector<int> tube((size_t)n, -1);
+    for (int v : order) {
+        uint64_t taken = 0;
+        for (int u : adj[(size_t)v])
+            if (tube[(size_t)u] >= 0) taken |= 1ull << tube[(size_t)u];
+        for (int t = 0; t < max_tubes && t < 64; ++t)
+            if (!((taken >> t) & 1)) {
+                tube[(size_t)v] = t;
+                break;
+            }
+    }
+    std::map<std::string, int> out;
+    for (int v = 0; v < n; ++v) out.emplace(*name[(size_t)v], tube[(size_t)v]);
+    return out;
+}
+
+std::map<std::string, int> conflict_tubes_on_device(Engine &eng, const std::vector<std::string> &primers,
+                                                    const NtthalOptions &opts, const ProgramConfig &cfg, int max_tubes)
+{
+    std::map<std::string, int> out;
+    std::vector<std::string> nodes;   // run_ntthal's node list: duplicates collapse
+    std::unordered_set<std::string> seen;
+    for (const auto &p : primers)
+        if (seen.insert(p).second) nodes.push_back(p);
+    if (nodes.empty()) return out;
+    if (!cfg.check_cross_dimers) {   // delta_g.rs:71-73: no edges at all, one tube holds everything
+        for (const auto &p : nodes) out.emplace(p, 0);
+        return out;
+    }
+    const int n = (int)nodes.size(), k = (int)nodes[0].size();
+    std::string flat;
+    for (const auto &p : nodes) flat += p;
+    const msspe_chem chem = ntthal_chem(opts);
+    std::vector<uint8_t> tube((size_t)n);
+    // --check-self-dimers false: the pairs ntthal_pair_sent() never sends are no edges
+    const int rc = msspe_conflict_tubes(eng.ctx(), flat.data(), n, k, &chem, opts.dg, cfg.check_self_dimers ? 0 : 1,
+                                        max_tubes, tube.data(), nullptr, nullptr);
+    if (rc) eng.fail(rc);
+    for (int i = 0; i < n; ++i)
+        out.emplace(nodes[(size_t)i], tube[(size_t)i] == MSSPE_TUBE_NONE ? -1 : (int)tube[(size_t)i]);
+    return out;
+}
+
+std::string tubes_report(const std::vector<KmerStat> &fwd, const std::vector<KmerStat> &rev,
+                         const std::map<std::string, int> &tubes, int max_tubes)
+{
+    std::vector<size_t> count;
+    size_t unplaced = 0;
+    for (const auto *list : {&fwd, &rev})
+        for (const auto &p : *list) {
+            const auto it = tubes.find(p.word);
+            if (it == tubes.end() || it->second < 0) {
+                ++unplaced;
+                continue;
+            }
+            if (count.size() <= (size_t)it->second) count.resize((size_t)it->second + 1, 0);
+            ++count[(size_t)it->second];
+        }
+    std::string out = "Tube assignment (up to " + std::to_string(max_tubes) + " tubes):\n  Tubes used: " +
+                      std::to_string(count.size()) + "\n";
+    for (size_t t = 0; t < count.size(); ++t)
+        out += "  Tube " + std::to_string(t + 1) + ": " + std::to_string(count[t]) + " primers\n";
+    out += "  Unplaced: " + std::to_string(unplaced) + " primers\n";
+    return out;
+}
+
 // ---------------------------------------------------------------------------------------------
 // report + CSV (main.rs:518-594, 834-858): host-side text
 // ---------------------------------------------------------------------------------------------
@@ -1189,16 +1304,21 @@ std::string background_report(const std::vector<std::string> &names,
 }
 
 std::string primers_csv(const std::vector<KmerStat> &fwd, const std::vector<KmerStat> &rev, size_t first_f,
-                        size_t first_r)
+                        size_t first_r, const std::map<std::string, int> *tubes)
 {
-    std::string out = "direction,name,primers,gc,avg,std,tm\n";
+    std::string out = tubes ? "direction,name,primers,gc,avg,std,tm,tube\n" : "direction,name,primers,gc,avg,std,tm\n";
     for (const auto *list : {&fwd, &rev}) {
         size_t idx = list == &fwd ? first_f : first_r;
         for (const auto &p : *list) {
             const char *d = p.direction == SEQ_DIR_FWD ? "F" : "R";
             out += std::string(d) + ",Primer_" + std::to_string(idx++) + "_" + d + "," + p.word + "," +
                    fmt("%.2f", (double)(p.gc_percent / 100.0f)) + "," + fmt("%.2f", (double)p.mean) + "," +
-                   fmt("%.2f", (double)p.std) + "," + fmt("%.2f", (double)p.tm) + "\n";
+                   fmt("%.2f", (double)p.std) + "," + fmt("%.2f", (double)p.tm);
+            if (tubes) {   // 1-based: a label for people
+                const auto it = tubes->find(p.word);
+                out += it != tubes->end() && it->second >= 0 ? "," + std::to_string(it->second + 1) : ",";
+            }
+            out += "\n";
         }
     }
     return out;
@@ -1398,8 +1518,16 @@ int run(const Args &args, std::string &stdout_text)
     std::vector<std::string> primers;
     for (const auto &s : prim_f) primers.push_back(s.word);
     for (const auto &s : prim_r) primers.push_back(s.word);
-    const auto deleted = args.cover_on_device == "true" ? conflict_cover_on_device(eng, primers, opts, cfg)
-                                                        : vertex_cover(primers, run_ntthal(eng, primers, opts, cfg));
+    std::map<std::string, int> tubes;   // --tubes: the primers that fit no tube are what is dropped
+    std::set<std::string> deleted;
+    if (args.tubes > 0) {
+        tubes = conflict_tubes_on_device(eng, primers, opts, cfg, args.tubes);
+        for (const auto &kv : tubes)
+            if (kv.second < 0) deleted.insert(kv.first);
+    } else {
+        deleted = args.cover_on_device == "true" ? conflict_cover_on_device(eng, primers, opts, cfg)
+                                                 : vertex_cover(primers, run_ntthal(eng, primers, opts, cfg));
+    }
     std::vector<KmerStat> good_f, good_r;
     for (const auto &p : prim_f)
         if (cfg.keep_all || !deleted.count(p.word)) good_f.push_back(p);
@@ -1417,6 +1545,7 @@ int run(const Args &args, std::string &stdout_text)
         stdout_text += coverage_report_mm(eng, aln, rep_f, rep_r, records, args.window_size, args.overlap_size,
                                           args.search_windows_size, args.kmer_size, args.coverage_mismatches,
                                           args.coverage_3p_exact);
+    if (args.tubes > 0) stdout_text += tubes_report(good_f, good_r, tubes, args.tubes);
     if (background) {   // the CSV's primers by their CSV names, the panel's by the numbers the CSV continues from
         std::vector<std::string> names, words;
         for (const auto *panel_list : {&panel_f, &panel_r}) {
@@ -1456,7 +1585,7 @@ int run(const Args &args, std::string &stdout_text)
     }
     std::ofstream out(args.output, std::ios::binary);
     if (!out) throw std::runtime_error("cannot write " + args.output);
-    out << primers_csv(good_f, good_r, panel_f.size(), panel_r.size());
+    out << primers_csv(good_f, good_r, panel_f.size(), panel_r.size(), args.tubes > 0 ? &tubes : nullptr);
     timer.lap("coverage report + csv");
     return 0;
 }

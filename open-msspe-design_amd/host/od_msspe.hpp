@@ -54,6 +54,10 @@ struct Args {
     std::string params_path;       // Primer3 config directory; empty = bundled tables
     std::string existing_primers;  // a panel to extend: CSV in this tool's output format (direction and primers read)
     std::string cover_on_device = "false";   // "true": the screen and the vertex cover as one device call (msspe_conflict_cover)
+    // --tubes N (1..64): instead of the vertex cover, the primers are split into at most N reaction tubes in which no
+    // two primers conflict (msspe_conflict_tubes); the primers that fit no tube are dropped, the CSV gains a 1-based
+    // "tube" column and the report a block.  Not a better cover at N = 1.  0: nothing changes.
+    int tubes = 0;
     // > 0: after the exact report, a second one counting a segment covered when a primer matches within this many
     // mismatches, its last coverage_3p_exact bases exact (msspe_segment_coverage_mm); 0: nothing changes
     int coverage_mismatches = 0;
@@ -209,6 +213,17 @@ std::set<std::string> vertex_cover(const std::vector<std::string> &primers, cons
 // screen's bitmap and the cover stay on the device); the same set
 std::set<std::string> conflict_cover_on_device(Engine &eng, const std::vector<std::string> &primers,
                                                const NtthalOptions &opts, const ProgramConfig &cfg);
+// --tubes (engine extension): the sequential rule of DESIGN.md 4.9 over the distinct primers -- by descending
+// (neighbours other than itself, lexicographic rank) each takes the lowest of max_tubes tubes that holds no neighbour
+// placed before it; -1: in no tube (a self conflict, or a neighbour in every tube).  The device's independent twin.
+std::map<std::string, int> assign_tubes(const std::vector<std::string> &primers, const ConflictGraph &g, int max_tubes);
+// the same assignment as one msspe_conflict_tubes call over the distinct primers (the screen's bitmap stays on the
+// device)
+std::map<std::string, int> conflict_tubes_on_device(Engine &eng, const std::vector<std::string> &primers,
+                                                    const NtthalOptions &opts, const ProgramConfig &cfg, int max_tubes);
+// "Tube assignment (up to N tubes):", the tubes in use, primers per tube (CSV rows) and primers in no tube
+std::string tubes_report(const std::vector<KmerStat> &fwd, const std::vector<KmerStat> &rev,
+                         const std::map<std::string, int> &tubes, int max_tubes);
 // main.rs:518-594 (text goes to `out`): the per-segment search runs on the device
 // (msspe_segment_coverage_dev), the totals per sequence / partition and the text on the host
 std::string coverage_report(Engine &eng, const DeviceAlignment &aln, const std::vector<KmerStat> &fwd,
@@ -284,8 +299,9 @@ std::string background_report_amplicons(const std::vector<std::string> &names,
                                         uint32_t min_len, uint32_t max_len);
 // main.rs:834-858
 // first_f / first_r: the number of the first row of each direction (a panel's extension continues its numbering)
+// tubes (--tubes): an eighth column "tube", 1-based, empty for a primer in no tube
 std::string primers_csv(const std::vector<KmerStat> &fwd, const std::vector<KmerStat> &rev, size_t first_f = 0,
-                        size_t first_r = 0);
+                        size_t first_r = 0, const std::map<std::string, int> *tubes = nullptr);
 
 // main.rs:596-861 without the MAFFT call: returns the process exit code; report -> stdout
 int run(const Args &args, std::string &stdout_text);

@@ -22,6 +22,7 @@ EXPORTS = [
     "msspe_cross_dimer_end_dev", "msspe_cross_dimer_end", "msspe_cross_dimer_end_edges_dev", "msspe_cross_dimer_end_edges",
     "msspe_cross_dimer_end_ab_dev", "msspe_cross_dimer_end_ab", "msspe_t_cut",
     "msspe_conflict_cover_dev", "msspe_conflict_cover",
+    "msspe_conflict_tubes_dev", "msspe_conflict_tubes",
     "msspe_last_overflow_pairs", "msspe_pair_stage_stats", "msspe_pair_stage_samples", "msspe_host_pair_tables", "msspe_host_split_tables", "msspe_device_put_rows", "msspe_segment_coverage", "msspe_segment_coverage_dev",
     "msspe_device_put", "msspe_device_get", "msspe_device_free", "msspe_thal_detail_pairs", "msspe_profile_enable", "msspe_profile_read",
     "msspe_oligo_stats_dev", "msspe_oligo_stats",
@@ -190,6 +191,10 @@ def load_library() -> C.CDLL:
     L.msspe_conflict_cover_dev.argtypes = [vp, u64p, C.c_int, C.c_int, u64p, C.c_int, vp, C.POINTER(C.c_int)]
     L.msspe_conflict_cover.argtypes = [vp, C.c_char_p, C.c_int, C.c_int, C.POINTER(Chem), C.c_float, C.c_int, vp,
                                        C.POINTER(C.c_int)]
+    L.msspe_conflict_tubes_dev.argtypes = [vp, u64p, C.c_int, C.c_int, u64p, C.c_int, C.c_int, vp, C.POINTER(C.c_int),
+                                           C.POINTER(C.c_int)]
+    L.msspe_conflict_tubes.argtypes = [vp, C.c_char_p, C.c_int, C.c_int, C.POINTER(Chem), C.c_float, C.c_int, C.c_int,
+                                       vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.msspe_last_overflow_pairs.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.msspe_pair_stage_stats.argtypes = [vp, C.POINTER(C.c_uint64)]   # out[16]
     L.msspe_pair_stage_samples.argtypes = [vp, C.POINTER(C.c_uint64), C.c_int, C.POINTER(C.c_int)]
@@ -559,6 +564,31 @@ class Engine:
         self._check(self.L.msspe_conflict_cover_dev(self.ptr, C.c_void_p(d_pool), n, k, C.c_void_p(d_bitmap),
                                                     int(bool(drop_self_pairs)), C.c_void_p(d_deleted), C.byref(nd)))
         return int(nd.value)
+
+    # ---- the conflict graph split into reaction tubes (engine extension; msspe_conflict_tubes*) --------------------
+    def conflict_tubes(self, pool, chem: Chem | None = None, threshold: float = -9000.0, max_tubes: int = 8,
+                       drop_self_pairs: bool = False):
+        """Screen a pool of distinct oligos of one length and split it into at most max_tubes (1..64) tubes in which
+        no two oligos conflict (msspe_conflict_tubes): (uint8[n], tubes_used, unplaced); 255 (MSSPE_TUBE_NONE) marks an
+        oligo in no tube.  Rounds of the call: info("tube_rounds")."""
+        buf, n, k = _ascii(pool)
+        chem = chem or Chem.ntthal()
+        out = np.zeros(n, dtype=np.uint8)
+        used, unplaced = C.c_int(0), C.c_int(0)
+        self._check(self.L.msspe_conflict_tubes(self.ptr, buf, n, k or 2, C.byref(chem), C.c_float(threshold),
+                                                int(bool(drop_self_pairs)), int(max_tubes), out.ctypes.data,
+                                                C.byref(used), C.byref(unplaced)))
+        return out, int(used.value), int(unplaced.value)
+
+    def conflict_tubes_dev(self, d_pool: int, n: int, k: int, d_bitmap: int, d_tube: int, max_tubes: int,
+                           drop_self_pairs: bool = False):
+        """Device-pointer form (msspe_conflict_tubes_dev): d_bitmap as for conflict_cover_dev, d_tube n bytes.
+        Returns (tubes_used, unplaced); synchronises."""
+        used, unplaced = C.c_int(0), C.c_int(0)
+        self._check(self.L.msspe_conflict_tubes_dev(self.ptr, C.c_void_p(d_pool), n, k, C.c_void_p(d_bitmap),
+                                                    int(bool(drop_self_pairs)), int(max_tubes), C.c_void_p(d_tube),
+                                                    C.byref(used), C.byref(unplaced)))
+        return int(used.value), int(unplaced.value)
 
     # ---- stage C, 3'-end dimers (thal END1 for every ordered pair; include/msspe_hip.h msspe_cross_dimer_end*) ------
     def cross_dimer_end(self, pool, chem: Chem | None = None, tm_threshold: float = END_TM_THRESHOLD,
