@@ -83,6 +83,8 @@ const char *msspe_version(void);
  *   "site_list_cap_log2" "12".."26"  msspe_background_thal*: the work list holds 2^this sites (22)
  *   "amplicon_keys_cap_log2" "10".."28"  msspe_background_amplicons*: the stable-key buffer of a context is first
  *                                 made with 2^this keys (20) and doubles as needed; no result depends on it
+ *   "panel_thin_matrix_max_mb" "1".."1048576"  msspe_panel_thin*: the most its incidence matrix may take, in MB
+ *                                 (8192); a call that needs more returns MSSPE_ERR_CAPACITY
  *   "split_lanes"    "0" | "2" | "4" | "8"
  *   "split_list"     "0" | "1"    short oligos: tables too large for the integer list stage go to the split-table
  *                                 kernel's list mode (1) or straight to the f64 kernels (0)
@@ -125,6 +127,12 @@ int msspe_set_option(msspe_ctx *ctx, const char *key, const char *value);
  *   "tube_rounds"     the last msspe_conflict_tubes* call: rounds that decided nodes
  *   "tube_keys_us" / "tube_symmetrise_us" / "tube_rounds_us"
  *                     the same call's device time of its phases: sort and keys, S = B | B^T, the keys, waits and rounds
+ *   "panel_thin_matrix_max_mb"  the option's current value
+ *   "panel_thin_rounds"  the last msspe_panel_thin* call: rounds that ran (its picks and the round that stopped)
+ *   "panel_thin_groups"  the same call's segment groups (rows of the incidence matrix)
+ *   "panel_thin_incidence_us" / "panel_thin_gain0_us" / "panel_thin_rounds_us"
+ *                     the same call's device time of its phases: the incidence pass, the forced rows and first gains,
+ *                     the rounds
  *   "hand_over_list_0" .. "hand_over_list_6"
  *                     pairs that entered hand-over list q of the cross-dimer calls (ANY and END) since the last read
  *                     of that key; reading synchronises the context's stream and resets the key, as
@@ -563,6 +571,54 @@ int msspe_segment_coverage_mm_packed_dev(msspe_ctx *ctx, const uint64_t *d_packe
                                          const msspe_kmer_opt *opt, const msspe_mismatch_opt *mm,
                                          const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
                                          uint8_t *best_out, uint32_t *primer_segments_out);
+
+/* ---- a panel thinned to the primers its coverage needs (engine extension, no reference counterpart) ----------
+ * Stage A picks words by exact occurrence, so two words that differ at one 5' base are both picked although either
+ * primes both variants.  This call answers "which of these primers could I leave out without losing a segment?" by
+ * a greedy set cover over the incidence of msspe_segment_coverage_mm*: the alignment, msspe_kmer_opt,
+ * msspe_mismatch_opt and primer words are that call's, and I[p][s] = 1 when primer p has at least one match in segment
+ * s under exactly its rule (a forward primer in the head window, a reverse primer in the tail window against the
+ * reverse-complemented candidate).  p runs over the forward primers in the caller's order, then the reverse primers;
+ * n = n_fwd + n_rev; s = r * P + j.  A row sum of I is that call's primer_segments_out[p].
+ *   forced (host, optional, n bytes; NULL: none): forced[p] != 0 keeps primer p whatever it covers (a panel being
+ *     extended).  covered starts as the OR of the forced rows; a forced primer is never picked and never in the order.
+ *   Rounds: for every p neither forced nor picked, gain(p) = |{s : I[p][s] and not covered[s]}|.  The round picks the p
+ *     of greatest gain, ties to the LOWEST index.  If that gain is below thin->min_gain the loop ends; otherwise p is
+ *     appended to the order with its gain and covered |= I[p].  (A duplicate of a picked word has gain 0.)
+ *   keep_out[n]: 1 when forced or picked.  order_out / gain_out (the caller sizes both to n) and *n_picked_out: the
+ *     picks in order with their gains.  covered_out (optional, n_seq * P bytes): 1 where the kept set covers.
+ *     *covered_all_out (optional): segments the whole set covers, |OR of all I[p]|; *covered_kept_out (optional): the
+ *     kept set's.
+ * GUARANTEE: at min_gain 1 the two counts are equal and covered_out marks exactly the segments where the whole set's
+ * msspe_segment_coverage_mm best_out != 255 -- thinning loses no segment.  What it does NOT preserve is the smallest
+ * mismatch count per segment: a segment matched exactly before may be matched with up to max_mismatches mismatches
+ * afterwards.  Choose max_mismatches and exact_3p for the thinning on their own, separately from a report's.
+ * The incidence matrix takes ceil(n_seq * P / S) * ceil(n / 64) * 512 bytes in the context (S <= 64 segments per
+ * group: 53 at window 50, k 13); msspe_set_option "panel_thin_matrix_max_mb" (default 8192) bounds it, and a call that
+ * needs more returns MSSPE_ERR_CAPACITY with both figures in msspe_last_error: it never thins on part of the data.
+ * Errors: those of msspe_segment_coverage_mm*, and MSSPE_ERR_ARG for thin == NULL, min_gain < 1, or a NULL keep_out,
+ * order_out, gain_out or n_picked_out.  n == 0 or no segments: MSSPE_OK, nothing picked, both counts 0, keep_out = the
+ * forced flags.  msspe_get_info "panel_thin_rounds" / "panel_thin_groups" / "panel_thin_*_us" describe the last call. */
+typedef struct {
+    int min_gain;   /* >= 1: a pick must cover at least this many segments nothing kept covers yet */
+} msspe_thin_opt;
+
+int msspe_panel_thin(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len, const msspe_kmer_opt *opt,
+                     const msspe_mismatch_opt *mm, const msspe_thin_opt *thin, const uint64_t *fwd_words, int n_fwd,
+                     const uint64_t *rev_words, int n_rev, const uint8_t *forced, uint8_t *keep_out,
+                     uint32_t *order_out, uint32_t *gain_out, int *n_picked_out, uint8_t *covered_out,
+                     long long *covered_all_out, long long *covered_kept_out);
+int msspe_panel_thin_dev(msspe_ctx *ctx, const uint8_t *d_seqs, int n_seq, size_t seq_len, const msspe_kmer_opt *opt,
+                         const msspe_mismatch_opt *mm, const msspe_thin_opt *thin, const uint64_t *fwd_words, int n_fwd,
+                         const uint64_t *rev_words, int n_rev, const uint8_t *forced, uint8_t *keep_out,
+                         uint32_t *order_out, uint32_t *gain_out, int *n_picked_out, uint8_t *covered_out,
+                         long long *covered_all_out, long long *covered_kept_out);
+int msspe_panel_thin_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
+                                const msspe_kmer_opt *opt, const msspe_mismatch_opt *mm, const msspe_thin_opt *thin,
+                                const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
+                                const uint8_t *forced, uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out,
+                                int *n_picked_out, uint8_t *covered_out, long long *covered_all_out,
+                                long long *covered_kept_out);
 
 /* ---- off-target sites in a background (engine extension, no reference counterpart) --------------------------
  * Where else do the primers land: a host genome, rRNA, a mitochondrion.  The BACKGROUND is a list of records

@@ -31,6 +31,7 @@
 #include "kmer_stage.hpp"
 #include "nn_params.hpp"
 #include "thal_dense.hpp"
+#include "panel_thin.hpp"
 #include "tube_split.hpp"
 
 using namespace msspe;
@@ -84,6 +85,7 @@ struct EngineOptions {
     int self_lane_from = 81920;   // oligos per call from which SELF_ANY / SELF_END run one lane per oligo (msspe_oligo_stats_dev)
     int site_list_cap_log2 = 22;  // msspe_background_thal*: work list of 2^this sites (44 bytes each: 185 MB)
     int amplicon_keys_cap_log2 = 20;  // msspe_background_amplicons*: the stable-key buffer starts at 2^this keys and doubles
+    long panel_thin_matrix_max_mb = 8192;   // msspe_panel_thin*: the incidence matrix may take this much, else MSSPE_ERR_CAPACITY
 };
 
 struct msspe_ctx {
@@ -121,6 +123,7 @@ struct msspe_ctx {
     BackgroundSites background;        // msspe_background_sites*: primer words in plane form, per-primer counts
     CoverStage cover;                  // msspe_conflict_cover*: the symmetrised bitmap and the round state
     TubeStage tubes;                   // msspe_conflict_tubes*: its round state (the graph lives in cover's buffers)
+    PanelThin thin;                    // msspe_panel_thin*: the incidence matrix, covered words, gains and round state
     // msspe_background_thal*: the work list (site records, their pairs, raw dG and t), the site pool [primers | site
     // oligos], 4 n counts (sites, then stable sites) and the slab's site counter; with a template flank also the
     // sites' class codes, and the class counters with the grouping cursors behind them
@@ -687,6 +690,9 @@ int msspe_set_option(msspe_ctx *ctx, const char *key, const char *value)
     } else if (k == "amplicon_keys_cap_log2") {
         if (!is_num || num < 10 || num > 28) return bad();
         ctx->opt.amplicon_keys_cap_log2 = (int)num;
+    } else if (k == "panel_thin_matrix_max_mb") {
+        if (!is_num || num < 1 || num > (1L << 20)) return bad();
+        ctx->opt.panel_thin_matrix_max_mb = num;
     } else if (k == "row_oob") {
         if (!is_num || num < 0 || num > 1) return bad();
         ctx->opt.row_oob = num != 0;
@@ -736,6 +742,12 @@ int msspe_get_info(msspe_ctx *ctx, const char *key, long long *value_out)
     else if (k == "tube_keys_us") *value_out = ctx->tubes.phase_us()[0];
     else if (k == "tube_symmetrise_us") *value_out = ctx->tubes.phase_us()[1];
     else if (k == "tube_rounds_us") *value_out = ctx->tubes.phase_us()[2];
+    else if (k == "panel_thin_matrix_max_mb") *value_out = ctx->opt.panel_thin_matrix_max_mb;
+    else if (k == "panel_thin_rounds") *value_out = ctx->thin.rounds();
+    else if (k == "panel_thin_groups") *value_out = ctx->thin.groups();
+    else if (k == "panel_thin_incidence_us") *value_out = ctx->thin.phase_us()[0];
+    else if (k == "panel_thin_gain0_us") *value_out = ctx->thin.phase_us()[1];
+    else if (k == "panel_thin_rounds_us") *value_out = ctx->thin.phase_us()[2];
     else if (k.size() == 16 && k.compare(0, 15, "hand_over_list_") == 0 && k[15] >= '0' && k[15] <= '6') {
         // pairs that entered list q since the last read of this key; reading resets it
         *value_out = 0;
@@ -771,6 +783,7 @@ void msspe_destroy(msspe_ctx *ctx)
         ctx->kmer_rev.release();
         ctx->cover.release();
         ctx->tubes.release();
+        ctx->thin.release();
         ctx->mm_cov.release();
         ctx->background.release();
         {
@@ -2128,6 +2141,71 @@ int msspe_segment_coverage_mm(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, si
     if (rc) return rc;
     rc = msspe_segment_coverage_mm_dev(ctx, (const uint8_t *)d, n_seq, seq_len, opt, mm, fwd_words, n_fwd, rev_words,
                                        n_rev, best_out, primer_segments_out);
+    (void)msspe_device_free(ctx, d);
+    return rc;
+}
+
+static int panel_thin_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t seq_len, const msspe_kmer_opt *opt,
+                           const msspe_mismatch_opt *mm, const msspe_thin_opt *thin, const uint64_t *fwd_words,
+                           int n_fwd, const uint64_t *rev_words, int n_rev, const uint8_t *forced, uint8_t *keep_out,
+                           uint32_t *order_out, uint32_t *gain_out, int *n_picked_out, uint8_t *covered_out,
+                           long long *covered_all_out, long long *covered_kept_out)
+{
+    if (!opt || !mm || !thin || !keep_out || !order_out || !gain_out || !n_picked_out || n_fwd < 0 || n_rev < 0 ||
+        (n_fwd && !fwd_words) || (n_rev && !rev_words))
+        return fail(ctx, MSSPE_ERR_ARG, "panel thin: null argument");
+    if (thin->min_gain < 1) return fail(ctx, MSSPE_ERR_ARG, "panel thin: min_gain must be at least 1");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::string err;
+    const int rc = ctx->thin.run(ctx->mm_cov, view, n_seq, seq_len, *opt, mm->max_mismatches, mm->exact_3p,
+                                 thin->min_gain, fwd_words, n_fwd, rev_words, n_rev, forced, keep_out, order_out,
+                                 gain_out, n_picked_out, covered_out, covered_all_out, covered_kept_out,
+                                 (size_t)ctx->opt.panel_thin_matrix_max_mb << 20, ctx->n_cu, ctx->stream, err);
+    if (rc) return fail(ctx, rc, err);
+    return MSSPE_OK;
+}
+
+int msspe_panel_thin_dev(msspe_ctx *ctx, const uint8_t *d_seqs, int n_seq, size_t seq_len, const msspe_kmer_opt *opt,
+                         const msspe_mismatch_opt *mm, const msspe_thin_opt *thin, const uint64_t *fwd_words, int n_fwd,
+                         const uint64_t *rev_words, int n_rev, const uint8_t *forced, uint8_t *keep_out,
+                         uint32_t *order_out, uint32_t *gain_out, int *n_picked_out, uint8_t *covered_out,
+                         long long *covered_all_out, long long *covered_kept_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!d_seqs) return fail(ctx, MSSPE_ERR_ARG, "null sequences");
+    return panel_thin_view(ctx, SeqView{d_seqs, nullptr, seq_len}, n_seq, seq_len, opt, mm, thin, fwd_words, n_fwd,
+                           rev_words, n_rev, forced, keep_out, order_out, gain_out, n_picked_out, covered_out,
+                           covered_all_out, covered_kept_out);
+}
+
+int msspe_panel_thin_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
+                                const msspe_kmer_opt *opt, const msspe_mismatch_opt *mm, const msspe_thin_opt *thin,
+                                const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
+                                const uint8_t *forced, uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out,
+                                int *n_picked_out, uint8_t *covered_out, long long *covered_all_out,
+                                long long *covered_kept_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!d_packed) return fail(ctx, MSSPE_ERR_ARG, "null sequences");
+    return panel_thin_view(ctx, SeqView{nullptr, d_packed, seq_len}, n_seq, seq_len, opt, mm, thin, fwd_words, n_fwd,
+                           rev_words, n_rev, forced, keep_out, order_out, gain_out, n_picked_out, covered_out,
+                           covered_all_out, covered_kept_out);
+}
+
+int msspe_panel_thin(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len, const msspe_kmer_opt *opt,
+                     const msspe_mismatch_opt *mm, const msspe_thin_opt *thin, const uint64_t *fwd_words, int n_fwd,
+                     const uint64_t *rev_words, int n_rev, const uint8_t *forced, uint8_t *keep_out,
+                     uint32_t *order_out, uint32_t *gain_out, int *n_picked_out, uint8_t *covered_out,
+                     long long *covered_all_out, long long *covered_kept_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!seqs || n_seq < 0) return fail(ctx, MSSPE_ERR_ARG, "null sequences");
+    void *d = nullptr;
+    int rc = msspe_device_put(ctx, seqs, (size_t)n_seq * seq_len, &d);
+    if (rc) return rc;
+    rc = msspe_panel_thin_dev(ctx, (const uint8_t *)d, n_seq, seq_len, opt, mm, thin, fwd_words, n_fwd, rev_words,
+                              n_rev, forced, keep_out, order_out, gain_out, n_picked_out, covered_out, covered_all_out,
+                              covered_kept_out);
     (void)msspe_device_free(ctx, d);
     return rc;
 }

@@ -19,6 +19,8 @@
 // are reduced in LDS (a ds_min only for positions that matched) and written with one byte store per segment.
 // COUNTS: per tile primer a 64-bit LDS word of the block's segments it matched in (ds_or by the matching lanes), then
 // one global atomic per (block, primer) with a nonzero popcount.  Without counts that code is not compiled in.
+// INCIDENCE (the panel thinning's first pass, panel_thin.hip): the same LDS words, stored instead of counted -- one plain
+// 64-bit vector store per (block, primer) into the group-major matrix inc[block * n_pad + primer], every word once.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -71,7 +73,8 @@ __device__ __forceinline__ void load4(const uint2 *tile, int i, uint2 (&u)[4])
 
 // best[seg] = smallest mismatch count (scaled: x2 for the 32-bit form) of a match, 255 when none; counts[primer] +=
 // segments it matched in.  lim: largest mask with the 3' bases equal; max_score: max_mismatches, scaled.
-template <typename T, bool COUNTS>
+// INCIDENCE (with COUNTS): `counts` is the incidence matrix, 64-bit words, n_pad = n_fwd + n_rev rounded up to 64.
+template <typename T, bool COUNTS, bool INCIDENCE = false>
 __global__ void __launch_bounds__(kThreads) k_coverage_mm(const SeqView seqs, int n_seg, int P, int seg_size,
                                                           int stride, int W, int k, int S, const T *fwd, int n_fwd,
                                                           const T *rev, int n_rev, int tile_cap, uint32_t lim,
@@ -151,9 +154,15 @@ __global__ void __launch_bounds__(kThreads) k_coverage_mm(const SeqView seqs, in
             if (COUNTS) {
                 __syncthreads();
                 const int out0 = (dir ? n_fwd : 0) + t0;
-                for (int i = tid; i < cnt; i += kThreads) {
-                    const int c = __popcll(bits[i]);
-                    if (c) atomicAdd(&counts[out0 + i], (uint32_t)c);
+                if (INCIDENCE) {
+                    const size_t n_pad = ((size_t)n_fwd + (size_t)n_rev + 63) & ~(size_t)63;
+                    uint64_t *inc = reinterpret_cast<uint64_t *>(counts) + (size_t)blockIdx.x * n_pad + (size_t)out0;
+                    for (int i = tid; i < cnt; i += kThreads) inc[i] = bits[i];
+                } else {
+                    for (int i = tid; i < cnt; i += kThreads) {
+                        const int c = __popcll(bits[i]);
+                        if (c) atomicAdd(&counts[out0 + i], (uint32_t)c);
+                    }
                 }
                 for (int i = tid; i < cnt4; i += kThreads) bits[i] = 0ull;
             }
@@ -234,10 +243,10 @@ namespace {
 
 template <typename T>
 int launch(const SeqView &d_seqs, long n_seg, long P, const msspe_kmer_opt &opt, int M, int E, const uint64_t *fwd,
-           int n_fwd, const uint64_t *rev, int n_rev, bool want_counts, void *const *buf, hipStream_t stream,
-           std::vector<T> &words, std::string &err)
+           int n_fwd, const uint64_t *rev, int n_rev, bool want_counts, uint64_t *d_inc, void *const *buf,
+           hipStream_t stream, std::vector<T> &words, std::string &err)
 {
-    const int k = opt.kmer_size, W = opt.search_window_size, per = W - k + 1;
+    const int k = opt.kmer_size, W = opt.search_window_size;
     constexpr bool narrow = sizeof(T) == 4;
     const int scale = narrow ? 2 : 1;
     const int s = k - E;   // 3' bases start at plane bit s
@@ -250,14 +259,19 @@ int launch(const SeqView &d_seqs, long n_seg, long P, const msspe_kmer_opt &opt,
     uint8_t *d_best = (uint8_t *)buf[2];
     if (!words.empty())
         MM_TRY(hipMemcpyAsync(d_words, words.data(), sizeof(T) * words.size(), hipMemcpyHostToDevice, stream));
-    const size_t per_word = sizeof(T) + (want_counts ? 8 : 0);
+    const size_t per_word = sizeof(T) + (want_counts || d_inc ? 8 : 0);
     const int max_tile = (int)((kLdsBudget - kMaxSeg * sizeof(uint32_t)) / per_word) & ~3;
     const int tile_cap = std::max(4, std::min(max_tile, (std::max(n_fwd, n_rev) + 3) & ~3));
     const size_t lds = (size_t)tile_cap * per_word + kMaxSeg * sizeof(uint32_t);
-    const int S = std::max(1, std::min(kMaxSeg, kRound / per));
+    const int S = MismatchCoverage::group_size(opt);
     const long grid = (n_seg + S - 1) / S;
     const uint32_t max_score = (uint32_t)(M * scale);
-    if (want_counts) {
+    if (d_inc) {
+        hipLaunchKernelGGL((k_coverage_mm<T, true, true>), dim3((unsigned)grid), dim3(kThreads), lds, stream, d_seqs,
+                           (int)n_seg, (int)P, opt.segment_size, opt.overlap_size, W, k, S, d_words, n_fwd,
+                           d_words + n_fwd, n_rev, tile_cap, lim, max_score, scale, d_best,
+                           reinterpret_cast<uint32_t *>(d_inc));
+    } else if (want_counts) {
         MM_TRY(hipMemsetAsync(d_counts, 0, sizeof(uint32_t) * (size_t)(n_fwd + n_rev), stream));
         hipLaunchKernelGGL((k_coverage_mm<T, true>), dim3((unsigned)grid), dim3(kThreads), lds, stream, d_seqs,
                            (int)n_seg, (int)P, opt.segment_size, opt.overlap_size, W, k, S, d_words, n_fwd,
@@ -273,10 +287,14 @@ int launch(const SeqView &d_seqs, long n_seg, long P, const msspe_kmer_opt &opt,
 
 }  // namespace
 
-int MismatchCoverage::run(const SeqView &d_seqs, int n_seq, size_t seq_len, const msspe_kmer_opt &opt,
-                          int max_mismatches, int exact_3p, const uint64_t *fwd_words, int n_fwd,
-                          const uint64_t *rev_words, int n_rev, uint8_t *best_out, uint32_t *primer_segments_out,
-                          hipStream_t stream, std::string &err)
+int MismatchCoverage::group_size(const msspe_kmer_opt &opt)
+{
+    return std::max(1, std::min(kMaxSeg, kRound / (opt.search_window_size - opt.kmer_size + 1)));
+}
+
+int MismatchCoverage::check(int n_seq, size_t seq_len, const msspe_kmer_opt &opt, int max_mismatches, int exact_3p,
+                            const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev, long *P_out,
+                            std::string &err)
 {
     const int k = opt.kmer_size, W = opt.search_window_size;
     if (k < 1 || k > 31) {
@@ -300,26 +318,60 @@ int MismatchCoverage::run(const SeqView &d_seqs, int n_seq, size_t seq_len, cons
     const long P = seq_len < (size_t)opt.segment_size
                        ? 0
                        : (long)((seq_len - (size_t)opt.segment_size) / (size_t)opt.overlap_size) + 1;
-    const long n_seg = P * n_seq;
-    if (primer_segments_out) std::fill(primer_segments_out, primer_segments_out + n_fwd + n_rev, 0u);
-    if (n_seg == 0) return MSSPE_OK;
-    if (n_seg > 0x7fffffffL) {
+    if (P * n_seq > 0x7fffffffL) {
         err = "coverage_mm: alignment too large for 32-bit segment indices";
         return MSSPE_ERR_ARG;
     }
+    *P_out = P;
+    return MSSPE_OK;
+}
+
+int MismatchCoverage::run(const SeqView &d_seqs, int n_seq, size_t seq_len, const msspe_kmer_opt &opt,
+                          int max_mismatches, int exact_3p, const uint64_t *fwd_words, int n_fwd,
+                          const uint64_t *rev_words, int n_rev, uint8_t *best_out, uint32_t *primer_segments_out,
+                          hipStream_t stream, std::string &err)
+{
+    return run(d_seqs, n_seq, seq_len, opt, max_mismatches, exact_3p, fwd_words, n_fwd, rev_words, n_rev, best_out,
+               primer_segments_out, nullptr, stream, err);
+}
+
+int MismatchCoverage::incidence(const SeqView &d_seqs, int n_seq, size_t seq_len, const msspe_kmer_opt &opt,
+                                int max_mismatches, int exact_3p, const uint64_t *fwd_words, int n_fwd,
+                                const uint64_t *rev_words, int n_rev, uint64_t *d_inc, hipStream_t stream,
+                                std::string &err)
+{
+    return run(d_seqs, n_seq, seq_len, opt, max_mismatches, exact_3p, fwd_words, n_fwd, rev_words, n_rev, nullptr,
+               nullptr, d_inc, stream, err);
+}
+
+int MismatchCoverage::run(const SeqView &d_seqs, int n_seq, size_t seq_len, const msspe_kmer_opt &opt,
+                          int max_mismatches, int exact_3p, const uint64_t *fwd_words, int n_fwd,
+                          const uint64_t *rev_words, int n_rev, uint8_t *best_out, uint32_t *primer_segments_out,
+                          uint64_t *d_inc, hipStream_t stream, std::string &err)
+{
+    const int k = opt.kmer_size;
+    long P = 0;
+    int rc = check(n_seq, seq_len, opt, max_mismatches, exact_3p, fwd_words, n_fwd, rev_words, n_rev, &P, err);
+    if (rc) return rc;
+    const long n_seg = P * n_seq;
+    if (primer_segments_out) std::fill(primer_segments_out, primer_segments_out + n_fwd + n_rev, 0u);
+    if (n_seg == 0) return MSSPE_OK;
     const bool narrow = k <= 16;
     const size_t wbytes = (narrow ? 4 : 8) * (size_t)(n_fwd + n_rev);
-    int rc;
     if ((rc = ensure(0, wbytes, err)) || (rc = ensure(1, sizeof(uint32_t) * (size_t)(n_fwd + n_rev), err)) ||
         (rc = ensure(2, (size_t)n_seg, err)))
         return rc;
     std::vector<uint32_t> w32;   // host copies: must outlive the uploads (synchronised below)
     std::vector<uint2> w64;
     rc = narrow ? launch<uint32_t>(d_seqs, n_seg, P, opt, max_mismatches, exact_3p, fwd_words, n_fwd, rev_words,
-                                   n_rev, primer_segments_out != nullptr, buf_, stream, w32, err)
+                                   n_rev, primer_segments_out != nullptr, d_inc, buf_, stream, w32, err)
                 : launch<uint2>(d_seqs, n_seg, P, opt, max_mismatches, exact_3p, fwd_words, n_fwd, rev_words, n_rev,
-                                primer_segments_out != nullptr, buf_, stream, w64, err);
+                                primer_segments_out != nullptr, d_inc, buf_, stream, w64, err);
     if (rc) return rc;
+    if (d_inc) {   // the thinning goes on in the stream; the primer words' host copies end here
+        MM_TRY(hipStreamSynchronize(stream));
+        return MSSPE_OK;
+    }
     MM_TRY(hipMemcpyAsync(best_out, buf_[2], (size_t)n_seg, hipMemcpyDeviceToHost, stream));
     if (primer_segments_out && n_fwd + n_rev)
         MM_TRY(hipMemcpyAsync(primer_segments_out, buf_[1], sizeof(uint32_t) * (size_t)(n_fwd + n_rev),

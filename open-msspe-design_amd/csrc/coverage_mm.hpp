@@ -21,12 +21,27 @@ public:
     int run(const SeqView &seqs, int n_seq, size_t seq_len, const msspe_kmer_opt &opt, int max_mismatches,
             int exact_3p, const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
             uint8_t *best_out, uint32_t *primer_segments_out, hipStream_t stream, std::string &err);
+    // The panel thinning's first pass (panel_thin.hip): the same comparisons, and instead of the counts the matrix
+    // d_inc[g * n_pad + p] (device; n_pad = n_fwd + n_rev rounded up to 64) -- bit b says primer p (forward primers
+    // first) has a match in segment g * group_size(opt) + b.  Every word with p < n_fwd + n_rev is written once.
+    // Needs segments (check() first); returns with the stream idle.
+    int incidence(const SeqView &seqs, int n_seq, size_t seq_len, const msspe_kmer_opt &opt, int max_mismatches,
+                  int exact_3p, const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
+                  uint64_t *d_inc, hipStream_t stream, std::string &err);
+    // the argument rules of run(); *P_out: partitions per record (0: no segments)
+    static int check(int n_seq, size_t seq_len, const msspe_kmer_opt &opt, int max_mismatches, int exact_3p,
+                     const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev, long *P_out,
+                     std::string &err);
+    static int group_size(const msspe_kmer_opt &opt);   // segments per block (<= 64): one bit each in a matrix word
     void release();
 
 private:
     void *buf_[3] = {};
     size_t cap_[3] = {};
     int ensure(int slot, size_t bytes, std::string &err);
+    int run(const SeqView &seqs, int n_seq, size_t seq_len, const msspe_kmer_opt &opt, int max_mismatches,
+            int exact_3p, const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
+            uint8_t *best_out, uint32_t *primer_segments_out, uint64_t *d_inc, hipStream_t stream, std::string &err);
 };
 
 }  // namespace msspe

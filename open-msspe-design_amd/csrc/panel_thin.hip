@@ -1,0 +1,364 @@
+// panel_thin.hip -- a primer panel thinned to the primers its coverage needs (engine extension).
+//
+// Stage A picks words by exact occurrence, so two words that differ at one 5' base are both picked although either
+// primes both variants.  The rule here is the greedy set cover over the incidence I[p][s] = "primer p has a match in
+// segment s" under msspe_segment_coverage_mm's rule: forced primers cover first, then every round keeps the unpicked
+// primer with the most uncovered segments (ties: the lowest index) until that gain falls below min_gain.
+//
+// Phases.  (1) The incidence pass is coverage_mm.hip's kernel in its third instance: the 64-bit LDS word of a block's
+// segments a primer matched in is stored, group-major (inc[g * n_pad + p], bit b = segment g * S + b), instead of
+// counted.  (2) The forced primers' rows are ORed into cov[g]; one pass over the matrix gives every primer's gain
+// (lanes over p: coalesced) and the segments the whole set covers.  (3) A round is three small launches: the argmax of
+// gain << 32 | ~p over the live primers, the pick's new segments per group (cov |= new, the groups with any go on a
+// list), and for the listed groups alone gain[p] -= popc(inc[g][p] & new[g]).  gain[p] == |I[p] & ~cov| holds for every
+// p after every round, so nothing is recomputed.  The rounds are enqueued 16 at a time behind a device word, as the
+// tube split's are: after the round that stops, the launches of the batch return at once, and the host reads one
+// word per batch.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <vector>
+
+#include "../../include/msspe_hip.h"
+#include "panel_thin.hpp"
+
+namespace msspe {
+
+namespace {
+
+constexpr int kRoundsPerBatch = 16;   // rounds enqueued between two reads of the "done" word
+constexpr int kThreads = 256;
+constexpr int kChunk = 32;            // groups per block of the first gains
+
+struct ThinState {
+    uint32_t done;        // 1: a round found no gain of min_gain or more (the launches that follow return at once)
+    uint32_t rounds;      // rounds that ran: the picks and the one that stopped
+    uint32_t n_picked;
+    uint32_t pick;        // of the current round
+    uint32_t n_touched;   // groups in which the current pick covers something new
+    uint32_t pad;
+    unsigned long long covered_all;      // |OR of all I[p]|
+    unsigned long long covered_forced;   // |OR of the forced I[p]|
+};
+
+enum { kInc, kCov, kTouched, kNew, kGain, kLive, kOrder, kForced };   // PanelThin::buf_
+
+__device__ __forceinline__ uint64_t wave_or(uint64_t x)
+{
+    uint32_t lo = (uint32_t)x, hi = (uint32_t)(x >> 32);
+    for (int o = 32; o; o >>= 1) {
+        lo |= __shfl_xor(lo, o, 64);
+        hi |= __shfl_xor(hi, o, 64);
+    }
+    return (uint64_t)hi << 32 | lo;
+}
+
+__device__ __forceinline__ uint64_t wave_max(uint64_t x)
+{
+    for (int o = 32; o; o >>= 1) {
+        const uint32_t lo = __shfl_xor((uint32_t)x, o, 64), hi = __shfl_xor((uint32_t)(x >> 32), o, 64);
+        x = std::max(x, (uint64_t)hi << 32 | lo);
+    }
+    return x;
+}
+
+// cov[g] = OR of the forced primers' words of group g: one wave per group, lanes over the forced list
+__global__ __launch_bounds__(kThreads) void k_thin_forced(const uint64_t *inc, size_t n_pad, int G,
+                                                          const uint32_t *forced, int n_forced, uint64_t *cov,
+                                                          ThinState *st)
+{
+    const int lane = threadIdx.x & 63;
+    const int waves = gridDim.x * (kThreads / 64);
+    for (int g = blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6); g < G; g += waves) {   // whole waves
+        uint64_t w = 0;
+        for (int i = lane; i < n_forced; i += 64) w |= inc[(size_t)g * n_pad + forced[i]];
+        w = wave_or(w);
+        if (lane == 0) {
+            cov[g] = w;
+            if (w) atomicAdd(&st->covered_forced, (unsigned long long)__popcll(w));
+        }
+    }
+}
+
+// gain[p] += popc(inc[g][p] & ~cov[g]) over the block's chunk of groups: one atomic per (block, primer); the OR of a
+// group's words over all primers is collected in LDS, and its popcount added to covered_all
+__global__ __launch_bounds__(kThreads) void k_thin_gain0(const uint64_t *inc, int n, size_t n_pad, int G,
+                                                         const uint64_t *cov, uint32_t *gain, ThinState *st)
+{
+    __shared__ uint64_t scov[kChunk], sall[kChunk];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int g0 = blockIdx.x * kChunk, cnt = std::min(kChunk, G - g0);
+    if (tid < kChunk) {
+        scov[tid] = tid < cnt ? cov[g0 + tid] : 0ull;
+        sall[tid] = 0ull;
+    }
+    __syncthreads();
+    for (int p0 = 0; p0 < n; p0 += kThreads) {   // whole blocks: the wave reductions below need every lane
+        const int p = p0 + tid;
+        const bool in = p < n;
+        const uint64_t *col = inc + (size_t)g0 * n_pad + (size_t)(in ? p : 0);
+        uint32_t sum = 0;
+        for (int gi = 0; gi < cnt; ++gi) {
+            const uint64_t w = in ? col[(size_t)gi * n_pad] : 0ull;
+            sum += (uint32_t)__popcll(w & ~scov[gi]);
+            const uint64_t o = wave_or(w);
+            if (lane == 0 && o) atomicOr((unsigned long long *)&sall[gi], (unsigned long long)o);
+        }
+        if (in && sum) atomicAdd(&gain[p], sum);
+    }
+    __syncthreads();
+    if (tid < cnt) {
+        const int c = __popcll(sall[tid]);
+        if (c) atomicAdd(&st->covered_all, (unsigned long long)c);
+    }
+}
+
+// One block: the live primer of greatest (gain, lowest index).  Below min_gain (or nobody live) the loop is done.
+__global__ __launch_bounds__(kThreads) void k_thin_pick(const uint32_t *gain, uint8_t *live, int n, uint32_t min_gain,
+                                                        uint32_t *order, uint32_t *gains, ThinState *st)
+{
+    if (st->done) return;
+    __shared__ uint64_t skey[kThreads / 64];
+    const int tid = threadIdx.x;
+    uint64_t key = 0;   // a live primer's key is never 0: its low half is 0xFFFFFFFF - p with p < 2^31
+    for (int p = tid; p < n; p += kThreads)
+        if (live[p]) key = std::max(key, (uint64_t)gain[p] << 32 | (uint64_t)(0xFFFFFFFFu - (uint32_t)p));
+    key = wave_max(key);
+    if ((tid & 63) == 0) skey[tid >> 6] = key;
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < kThreads / 64; ++w) key = std::max(key, skey[w]);
+        const uint32_t g = (uint32_t)(key >> 32);
+        st->rounds += 1;
+        if (key == 0 || g < min_gain) {
+            st->done = 1;
+        } else {
+            const uint32_t p = 0xFFFFFFFFu - (uint32_t)key, i = st->n_picked;   // i < n: every pick leaves the live set
+            order[i] = p;
+            gains[i] = g;
+            live[p] = 0;
+            st->n_picked = i + 1;
+            st->pick = p;
+            st->n_touched = 0;
+        }
+    }
+}
+
+// new[g] = inc[g][pick] & ~cov[g]; cov[g] |= new[g]; the groups with any go on the touched list (at most G entries)
+__global__ __launch_bounds__(kThreads) void k_thin_apply(const uint64_t *inc, size_t n_pad, int G, uint64_t *cov,
+                                                         uint32_t *touched, uint64_t *fresh, ThinState *st)
+{
+    if (st->done) return;
+    const long g = (long)blockIdx.x * kThreads + threadIdx.x;
+    if (g >= G) return;
+    const uint64_t c = cov[g], w = inc[(size_t)g * n_pad + st->pick] & ~c;
+    if (!w) return;
+    cov[g] = c | w;
+    const uint32_t i = atomicAdd(&st->n_touched, 1u);
+    touched[i] = (uint32_t)g;
+    fresh[i] = w;
+}
+
+// gain[p] -= popc(inc[g][p] & new[g]) over the touched groups (blockIdx.y strides over the list), lanes over p
+__global__ __launch_bounds__(kThreads) void k_thin_update(const uint64_t *inc, int n, size_t n_pad,
+                                                          const uint32_t *touched, const uint64_t *fresh,
+                                                          uint32_t *gain, const ThinState *st)
+{
+    if (st->done) return;
+    const int p = blockIdx.x * kThreads + threadIdx.x;
+    if (p >= n) return;
+    const uint32_t nt = st->n_touched;
+    uint32_t sum = 0;
+    for (uint32_t i = blockIdx.y; i < nt; i += gridDim.y)
+        sum += (uint32_t)__popcll(inc[(size_t)touched[i] * n_pad + (size_t)p] & fresh[i]);
+    if (sum) atomicSub(&gain[p], sum);
+}
+
+#define THIN_TRY(expr)                                                              \
+    do {                                                                            \
+        hipError_t e__ = (expr);                                                    \
+        if (e__ != hipSuccess) {                                                    \
+            err = std::string("panel thin, " #expr ": ") + hipGetErrorString(e__);  \
+            return MSSPE_ERR_DEVICE;                                                \
+        }                                                                           \
+    } while (0)
+
+}  // namespace
+
+int PanelThin::ensure(int slot, size_t bytes, std::string &err)
+{
+    if (cap_[slot] >= bytes && buf_[slot]) return MSSPE_OK;
+    if (buf_[slot]) (void)hipFree(buf_[slot]);
+    buf_[slot] = nullptr;
+    cap_[slot] = 0;
+    const hipError_t e = hipMalloc(&buf_[slot], bytes ? bytes : 16);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        buf_[slot] = nullptr;
+        err = std::string("hipMalloc (panel thin): ") + hipGetErrorString(e);
+        return MSSPE_ERR_DEVICE;
+    }
+    cap_[slot] = bytes;
+    return MSSPE_OK;
+}
+
+void PanelThin::release()
+{
+    for (int s = 0; s < kSlots; ++s) {
+        if (buf_[s]) (void)hipFree(buf_[s]);
+        buf_[s] = nullptr;
+        cap_[s] = 0;
+    }
+    for (auto &e : ev_) {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+    }
+}
+
+int PanelThin::run(MismatchCoverage &cov, const SeqView &seqs, int n_seq, size_t seq_len, const msspe_kmer_opt &opt,
+                   int max_mismatches, int exact_3p, int min_gain, const uint64_t *fwd_words, int n_fwd,
+                   const uint64_t *rev_words, int n_rev, const uint8_t *forced, uint8_t *keep_out, uint32_t *order_out,
+                   uint32_t *gain_out, int *n_picked_out, uint8_t *covered_out, long long *covered_all_out,
+                   long long *covered_kept_out, size_t max_matrix_bytes, int n_cu, hipStream_t stream,
+                   std::string &err)
+{
+    rounds_ = groups_ = 0;
+    for (auto &p : phase_us_) p = 0;
+    *n_picked_out = 0;
+    if (covered_all_out) *covered_all_out = 0;
+    if (covered_kept_out) *covered_kept_out = 0;
+    long P = 0;
+    int rc = MismatchCoverage::check(n_seq, seq_len, opt, max_mismatches, exact_3p, fwd_words, n_fwd, rev_words, n_rev,
+                                     &P, err);
+    if (rc) return rc;
+    const int n = n_fwd + n_rev;
+    const long n_seg = P * n_seq;
+    for (int p = 0; p < n; ++p) keep_out[p] = forced && forced[p] ? 1 : 0;
+    if (covered_out) std::fill(covered_out, covered_out + n_seg, (uint8_t)0);
+    if (n == 0 || n_seg == 0) return MSSPE_OK;
+
+    const int S = MismatchCoverage::group_size(opt);
+    const long G = (n_seg + S - 1) / S;
+    const size_t n_pad = ((size_t)n + 63) & ~(size_t)63;
+    const size_t mib = (size_t)1 << 20, matrix = (size_t)G * n_pad * sizeof(uint64_t);
+    if (matrix > max_matrix_bytes) {
+        err = "panel thin: the incidence matrix needs " + std::to_string((matrix + mib - 1) / mib) +
+              " MB, panel_thin_matrix_max_mb is " + std::to_string(max_matrix_bytes / mib);
+        return MSSPE_ERR_CAPACITY;
+    }
+    groups_ = G;
+    if ((rc = ensure(kInc, matrix, err)) || (rc = ensure(kCov, sizeof(uint64_t) * (size_t)G + sizeof(ThinState), err)) ||
+        (rc = ensure(kTouched, sizeof(uint32_t) * (size_t)G, err)) ||
+        (rc = ensure(kNew, sizeof(uint64_t) * (size_t)G, err)) ||
+        (rc = ensure(kGain, sizeof(uint32_t) * (size_t)n, err)) || (rc = ensure(kLive, (size_t)n, err)) ||
+        (rc = ensure(kOrder, 2 * sizeof(uint32_t) * (size_t)n, err)) ||
+        (rc = ensure(kForced, sizeof(uint32_t) * (size_t)n, err)))
+        return rc;
+    for (auto &e : ev_)
+        if (!e && hipEventCreate(&e) != hipSuccess) {
+            err = "panel thin: hipEventCreate failed";
+            return MSSPE_ERR_DEVICE;
+        }
+    uint64_t *d_inc = (uint64_t *)buf_[kInc], *d_cov = (uint64_t *)buf_[kCov], *d_new = (uint64_t *)buf_[kNew];
+    ThinState *st = (ThinState *)(d_cov + G);   // behind the covered words: 8-byte aligned
+    uint32_t *d_touched = (uint32_t *)buf_[kTouched], *d_gain = (uint32_t *)buf_[kGain];
+    uint32_t *d_order = (uint32_t *)buf_[kOrder], *d_gains = d_order + n, *d_forced = (uint32_t *)buf_[kForced];
+    uint8_t *d_live = (uint8_t *)buf_[kLive];
+
+    // (1) the incidence matrix
+    THIN_TRY(hipEventRecord(ev_[0], stream));
+    if ((rc = cov.incidence(seqs, n_seq, seq_len, opt, max_mismatches, exact_3p, fwd_words, n_fwd, rev_words, n_rev,
+                            d_inc, stream, err)))
+        return rc;
+    THIN_TRY(hipEventRecord(ev_[1], stream));
+
+    // (2) forced rows, first gains
+    std::vector<uint8_t> live((size_t)n);
+    std::vector<uint32_t> forced_idx;
+    for (int p = 0; p < n; ++p) {
+        live[(size_t)p] = keep_out[p] ? 0 : 1;
+        if (keep_out[p]) forced_idx.push_back((uint32_t)p);
+    }
+    THIN_TRY(hipMemsetAsync(d_cov, 0, sizeof(uint64_t) * (size_t)G + sizeof(ThinState), stream));
+    THIN_TRY(hipMemsetAsync(d_gain, 0, sizeof(uint32_t) * (size_t)n, stream));
+    THIN_TRY(hipMemcpyAsync(d_live, live.data(), (size_t)n, hipMemcpyHostToDevice, stream));
+    if (!forced_idx.empty()) {
+        THIN_TRY(hipMemcpyAsync(d_forced, forced_idx.data(), sizeof(uint32_t) * forced_idx.size(),
+                                hipMemcpyHostToDevice, stream));
+        const int blocks = (int)std::max<long>(1, std::min<long>((G + 3) / 4, 8L * n_cu));
+        hipLaunchKernelGGL(k_thin_forced, dim3(blocks), dim3(kThreads), 0, stream, d_inc, n_pad, (int)G, d_forced,
+                           (int)forced_idx.size(), d_cov, st);
+    }
+    hipLaunchKernelGGL(k_thin_gain0, dim3((unsigned)((G + kChunk - 1) / kChunk)), dim3(kThreads), 0, stream, d_inc, n,
+                       n_pad, (int)G, d_cov, d_gain, st);
+    THIN_TRY(hipGetLastError());
+    THIN_TRY(hipEventRecord(ev_[2], stream));
+
+    // (3) rounds, kRoundsPerBatch per read of the state; every round but the last picks a primer, so there are at
+    // most n + 1 of them
+    const unsigned gx = (unsigned)((n + kThreads - 1) / kThreads);
+    const unsigned gy = (unsigned)std::max<long>(1, std::min<long>(std::min<long>(G, 65535), 2048 / gx));
+    const unsigned ga = (unsigned)((G + kThreads - 1) / kThreads);
+    ThinState hs{};
+    for (int batch = 0;; ++batch) {
+        for (int b = 0; b < kRoundsPerBatch; ++b) {
+            hipLaunchKernelGGL(k_thin_pick, dim3(1), dim3(kThreads), 0, stream, d_gain, d_live, n, (uint32_t)min_gain,
+                               d_order, d_gains, st);
+            hipLaunchKernelGGL(k_thin_apply, dim3(ga), dim3(kThreads), 0, stream, d_inc, n_pad, (int)G, d_cov,
+                               d_touched, d_new, st);
+            hipLaunchKernelGGL(k_thin_update, dim3(gx, gy), dim3(kThreads), 0, stream, d_inc, n, n_pad, d_touched,
+                               d_new, d_gain, st);
+        }
+        THIN_TRY(hipGetLastError());
+        THIN_TRY(hipMemcpyAsync(&hs, st, sizeof hs, hipMemcpyDeviceToHost, stream));
+        THIN_TRY(hipStreamSynchronize(stream));
+        if (hs.done) break;
+        if (batch + 1 >= n / kRoundsPerBatch + 2) {
+            err = "panel thin: more rounds than primers";
+            return MSSPE_ERR_DEVICE;
+        }
+    }
+    THIN_TRY(hipEventRecord(ev_[3], stream));
+
+    const int n_picked = (int)hs.n_picked;
+    if (n_picked > n) {
+        err = "panel thin: more picks than primers";
+        return MSSPE_ERR_DEVICE;
+    }
+    if (n_picked) {
+        THIN_TRY(hipMemcpyAsync(order_out, d_order, sizeof(uint32_t) * (size_t)n_picked, hipMemcpyDeviceToHost, stream));
+        THIN_TRY(hipMemcpyAsync(gain_out, d_gains, sizeof(uint32_t) * (size_t)n_picked, hipMemcpyDeviceToHost, stream));
+    }
+    std::vector<uint64_t> h_cov;
+    if (covered_out) {
+        h_cov.resize((size_t)G);
+        THIN_TRY(hipMemcpyAsync(h_cov.data(), d_cov, sizeof(uint64_t) * (size_t)G, hipMemcpyDeviceToHost, stream));
+    }
+    THIN_TRY(hipEventSynchronize(ev_[3]));
+    THIN_TRY(hipStreamSynchronize(stream));
+    for (int ph = 0; ph < 3; ++ph) {
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, ev_[ph], ev_[ph + 1]);
+        phase_us_[ph] = (long long)(ms * 1000.0f);
+    }
+    rounds_ = hs.rounds;
+    long long kept = (long long)hs.covered_forced;
+    for (int i = 0; i < n_picked; ++i) {
+        if (order_out[i] >= (uint32_t)n) {
+            err = "panel thin: a pick outside the panel";
+            return MSSPE_ERR_DEVICE;
+        }
+        keep_out[order_out[i]] = 1;
+        kept += gain_out[i];
+    }
+    *n_picked_out = n_picked;
+    if (covered_all_out) *covered_all_out = (long long)hs.covered_all;
+    if (covered_kept_out) *covered_kept_out = kept;
+    if (covered_out)
+        for (long g = 0; g < G; ++g)
+            for (int b = 0; b < S && g * S + b < n_seg; ++b) covered_out[g * S + b] = (uint8_t)((h_cov[(size_t)g] >> b) & 1ull);
+    return MSSPE_OK;
+}
+
+}  // namespace msspe

@@ -64,6 +64,8 @@ int odm_parse_args(int argc, const char *const *argv, char *out, size_t cap)
           << "\ncheck_hairpin=" << a.check_hairpin << "\ndo_align=" << a.do_align
           << "\ntm_stddev=" << a.tm_stddev << "\ncover_on_device=" << a.cover_on_device << "\ntubes=" << a.tubes
           << "\ncoverage_mismatches=" << a.coverage_mismatches << "\ncoverage_3p_exact=" << a.coverage_3p_exact
+          << "\nthin_panel=" << a.thin_panel << "\nthin_mismatches=" << a.thin_mismatches
+          << "\nthin_3p_exact=" << a.thin_3p_exact << "\nthin_min_gain=" << a.thin_min_gain
           << "\nbackground=" << a.background << "\nbackground_mismatches=" << a.background_mismatches
           << "\nbackground_3p_exact=" << a.background_3p_exact << "\nmax_background_sites=" << a.max_background_sites
           << "\nbackground_tm=" << a.background_tm_text << "\nbackground_thal=" << a.background_thal
@@ -111,6 +113,29 @@ int odm_assign_tubes(const char *primers_nl, const char *edges_nl, int max_tubes
         s += p + "\t" + (t < 0 ? std::string("-") : std::to_string(t)) + "\n";
     }
     return emit(s, out, cap);
+}
+
+// rows: n incidence rows of `words` 64-bit words each (bit s & 63 of word s >> 6: segment s); forced: n flags or
+// NULL.  order / gains (n entries each) and keep (n) out; returns the number of picks (thin_panel, the sequential rule
+// of DESIGN.md 4.10); covered_out[0] / [1]: segments covered by all rows / by the kept ones.
+int odm_thin_panel(const uint64_t *rows, int n, int words, int min_gain, const uint8_t *forced, int *order, int *gains,
+                   uint8_t *keep, long long *covered_out)
+{
+    std::vector<std::vector<uint64_t>> r((size_t)n);
+    for (int p = 0; p < n; ++p) r[(size_t)p].assign(rows + (size_t)p * words, rows + (size_t)(p + 1) * words);
+    std::vector<char> f;
+    if (forced) f.assign(forced, forced + n);
+    const ThinResult t = thin_panel(r, min_gain, f);
+    for (size_t i = 0; i < t.order.size(); ++i) {
+        order[i] = t.order[i];
+        gains[i] = t.gains[i];
+    }
+    for (int p = 0; p < n; ++p) keep[p] = (uint8_t)t.keep[(size_t)p];
+    if (covered_out) {
+        covered_out[0] = (long long)t.covered_all;
+        covered_out[1] = (long long)t.covered_kept;
+    }
+    return (int)t.order.size();
 }
 
 int odm_is_run(const char *kmer) { return is_run(kmer) ? 1 : 0; }

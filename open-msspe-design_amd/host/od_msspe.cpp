@@ -74,6 +74,10 @@ const OptSpec kOpts[] = {
     {"--tubes", "TUBES", OptSpec::Int, OFF(tubes)},
     {"--coverage-mismatches", "COVERAGE_MISMATCHES", OptSpec::Int, OFF(coverage_mismatches)},
     {"--coverage-3p-exact", "COVERAGE_3P_EXACT", OptSpec::Str, OFF(coverage_3p_exact_text)},
+    {"--thin-panel", "THIN_PANEL", OptSpec::Bool, OFF(thin_panel)},
+    {"--thin-mismatches", "THIN_MISMATCHES", OptSpec::Int, OFF(thin_mismatches)},
+    {"--thin-3p-exact", "THIN_3P_EXACT", OptSpec::Str, OFF(thin_3p_exact_text)},
+    {"--thin-min-gain", "THIN_MIN_GAIN", OptSpec::Int, OFF(thin_min_gain)},
     {"--background", "BACKGROUND", OptSpec::Str, OFF(background)},
     {"--background-mismatches", "BACKGROUND_MISMATCHES", OptSpec::OptInt, OFF(background_mismatches)},
     {"--background-3p-exact", "BACKGROUND_3P_EXACT", OptSpec::OptInt, OFF(background_3p_exact)},
@@ -129,7 +133,11 @@ std::string Args::usage()
     u += "\n--background <FASTA> screens the primers against unaligned background records (a host genome, rRNA) for\n"
          "off-target sites on both strands; with --devices it runs on the first device.\n"
          "--tubes <N> (1..64) splits the primers into at most N reaction tubes in which no two primers conflict, instead\n"
-         "of deleting primers by the vertex cover; the CSV gains a 'tube' column. One tube is not a better cover.\n";
+         "of deleting primers by the vertex cover; the CSV gains a 'tube' column. One tube is not a better cover.\n"
+         "--thin-panel true drops, after the cover or the tubes, every primer the coverage does not need: a greedy set\n"
+         "cover of the segments matched within --thin-mismatches <M> (last --thin-3p-exact <E> bases exact), a pick\n"
+         "covering at least --thin-min-gain <G> new segments. No segment is lost at G = 1; a segment's best mismatch\n"
+         "count may rise up to M. The primers of --existing-primers are kept. One device; not with --keep-all true.\n";
     return u;
 }
 
@@ -194,6 +202,26 @@ Args Args::parse(int argc, const char *const *argv)
             throw UsageError("error: '--coverage-3p-exact " + v + "' is larger than '--kmer-size " +
                              std::to_string(a.kmer_size) + "'");
         a.coverage_3p_exact = (int)e;
+    }
+    if (a.thin_panel == "true") {
+        if (a.keep_all == "true")
+            throw UsageError("error: '--thin-panel true' drops primers and cannot be combined with '--keep-all true'");
+        if (!a.devices.empty())
+            throw UsageError("error: '--thin-panel true' runs on one device and cannot be combined with '--devices'");
+        if (a.thin_mismatches > a.kmer_size)
+            throw UsageError("error: '--thin-mismatches " + std::to_string(a.thin_mismatches) +
+                             "' is larger than '--kmer-size " + std::to_string(a.kmer_size) + "'");
+        const std::string &v = a.thin_3p_exact_text;
+        char *end = nullptr;
+        const long e = std::strtol(v.c_str(), &end, 10);
+        if (v.empty() || *end || e < 0) throw UsageError("error: invalid value '" + v + "' for '--thin-3p-exact'");
+        if (e > a.kmer_size)
+            throw UsageError("error: '--thin-3p-exact " + v + "' is larger than '--kmer-size " +
+                             std::to_string(a.kmer_size) + "'");
+        a.thin_3p_exact = (int)e;
+        if (a.thin_min_gain < 1)
+            throw UsageError("error: invalid value '" + std::to_string(a.thin_min_gain) +
+                             "' for '--thin-min-gain <...>'\n  [1 ..]");
     }
     if (a.background.empty()) {
         for (const auto &given : {std::make_pair("--background-mismatches", a.background_mismatches),
@@ -913,6 +941,58 @@ std::map<std::string, int> conflict_tubes_on_device(Engine &eng, const std::vect
     return out;
 }
 
+ThinResult thin_panel(const std::vector<std::vector<uint64_t>> &rows, int min_gain, const std::vector<char> &forced)
+{
+    const size_t n = rows.size();
+    size_t words = 0;
+    for (const auto &r : rows) words = std::max(words, r.size());
+    auto word = [&](size_t p, size_t w) { return w < rows[p].size() ? rows[p][w] : 0ull; };
+    ThinResult out;
+    out.keep.assign(n, 0);
+    std::vector<uint64_t> covered(words, 0), all(words, 0);
+    for (size_t p = 0; p < n; ++p)
+        for (size_t w = 0; w < words; ++w) {
+            all[w] |= word(p, w);
+            if (p < forced.size() && forced[p]) covered[w] |= word(p, w);
+        }
+    for (size_t p = 0; p < n; ++p) out.keep[p] = p < forced.size() && forced[p] ? 1 : 0;
+    for (;;) {   // every round from scratch: the device keeps its gains up to date instead
+        long best = -1;
+        size_t best_gain = 0;
+        for (size_t p = 0; p < n; ++p) {
+            if (out.keep[p]) continue;
+            size_t gain = 0;
+            for (size_t w = 0; w < words; ++w) gain += (size_t)__builtin_popcountll(word(p, w) & ~covered[w]);
+            if (best < 0 || gain > best_gain) {   // ">": the lowest index among equals
+                best = (long)p;
+                best_gain = gain;
+            }
+        }
+        if (best < 0 || best_gain < (size_t)min_gain) break;
+        out.order.push_back((int)best);
+        out.gains.push_back((int)best_gain);
+        out.keep[(size_t)best] = 1;
+        for (size_t w = 0; w < words; ++w) covered[w] |= word((size_t)best, w);
+    }
+    for (size_t w = 0; w < words; ++w) {
+        out.covered_all += (size_t)__builtin_popcountll(all[w]);
+        out.covered_kept += (size_t)__builtin_popcountll(covered[w]);
+    }
+    return out;
+}
+
+std::string thin_report(int max_mismatches, int exact_3p, int min_gain, size_t kept_f, size_t n_f, size_t kept_r,
+                        size_t n_r, size_t forced, size_t covered_all, size_t covered_kept, size_t segments)
+{
+    const std::string x = std::to_string(kept_f + kept_r), y = std::to_string(n_f + n_r), t = std::to_string(segments);
+    return "\nPanel thinning (up to " + std::to_string(max_mismatches) + " mismatches, last " + std::to_string(exact_3p) +
+           " bases exact, gain >= " + std::to_string(min_gain) + "):\n  Primers:  kept " + x + " of " + y + " (forward " +
+           std::to_string(kept_f) + " of " + std::to_string(n_f) + ", reverse " + std::to_string(kept_r) + " of " +
+           std::to_string(n_r) + "), " + std::to_string(forced) + " forced\n  Segments: covered " +
+           std::to_string(covered_all) + "/" + t + " by all " + y + ", " + std::to_string(covered_kept) + "/" + t +
+           " by the kept " + x + "\n";
+}
+
 std::string tubes_report(const std::vector<KmerStat> &fwd, const std::vector<KmerStat> &rev,
                          const std::map<std::string, int> &tubes, int max_tubes)
 {
@@ -1080,6 +1160,47 @@ std::string coverage_report_mm(Engine &eng, const DeviceAlignment &aln, const st
     for (int m = 0; m <= max_mismatches; ++m) out += " " + std::to_string(m) + " mm " + std::to_string(by[(size_t)m]) + ",";
     out += " none " + std::to_string(by.back()) + "\n";
     return out;
+}
+
+std::string thin_panel_on_device(Engine &eng, const DeviceAlignment &aln, std::vector<KmerStat> &fwd,
+                                 std::vector<KmerStat> &rev, const std::vector<std::string> &panel_f,
+                                 const std::vector<std::string> &panel_r, int segment_size, int overlap_size,
+                                 int window_size, int kmer_size, int max_mismatches, int exact_3p, int min_gain)
+{
+    // the new primers in their lists' order (stage A's selection order: ties go to the word with more postings), the
+    // panel's behind them, forced
+    std::vector<KmerStat> all_f = fwd, all_r = rev;
+    for (const auto &w : panel_f) all_f.push_back(KmerStat{w, SEQ_DIR_FWD});
+    for (const auto &w : panel_r) all_r.push_back(KmerStat{w, SEQ_DIR_REV});
+    const size_t n = all_f.size() + all_r.size();
+    std::vector<uint8_t> forced(n + 1, 0), keep(n + 1, 0);
+    for (size_t i = fwd.size(); i < all_f.size(); ++i) forced[i] = 1;
+    for (size_t i = rev.size(); i < all_r.size(); ++i) forced[all_f.size() + i] = 1;
+    std::vector<uint32_t> order(n + 1), gains(n + 1);
+    int n_picked = 0;
+    long long covered_all = 0, covered_kept = 0;
+    const size_t L = aln.length();
+    const size_t P = L < (size_t)segment_size ? 0 : (L - (size_t)segment_size) / (size_t)overlap_size + 1;
+    const auto wf = pack_words(eng, all_f, kmer_size), wr = pack_words(eng, all_r, kmer_size);
+    const msspe_kmer_opt opt{segment_size, overlap_size, window_size, kmer_size, 0, 0};
+    const msspe_mismatch_opt mm{max_mismatches, exact_3p};
+    const msspe_thin_opt thin{min_gain};
+    const int rc = msspe_panel_thin_packed_dev(eng.ctx(), aln.device(), aln.rows(), L, &opt, &mm, &thin, wf.data(),
+                                               (int)wf.size(), wr.data(), (int)wr.size(), forced.data(), keep.data(),
+                                               order.data(), gains.data(), &n_picked, nullptr, &covered_all,
+                                               &covered_kept);
+    if (rc) eng.fail(rc);
+    const size_t n_f = fwd.size(), n_r = rev.size();
+    std::vector<KmerStat> kept_f, kept_r;
+    for (size_t i = 0; i < n_f; ++i)
+        if (keep[i]) kept_f.push_back(fwd[i]);
+    for (size_t i = 0; i < n_r; ++i)
+        if (keep[all_f.size() + i]) kept_r.push_back(rev[i]);
+    fwd.swap(kept_f);
+    rev.swap(kept_r);
+    return thin_report(max_mismatches, exact_3p, min_gain, fwd.size(), n_f, rev.size(), n_r,
+                       panel_f.size() + panel_r.size(), (size_t)covered_all, (size_t)covered_kept,
+                       (size_t)aln.rows() * P);
 }
 
 DeviceBackground::DeviceBackground(Engine &eng, const std::vector<SequenceRecord> &records)
@@ -1535,6 +1656,13 @@ int run(const Args &args, std::string &stdout_text)
         if (cfg.keep_all || !deleted.count(p.word)) good_r.push_back(p);
 
     timer.lap("stage C + vertex cover");
+    std::string thin_text;   // --thin-panel: everything below sees the thinned lists
+    if (args.thin_panel == "true") {
+        thin_text = thin_panel_on_device(eng, aln, good_f, good_r, panel_f, panel_r, args.window_size, args.overlap_size,
+                                         args.search_windows_size, args.kmer_size, args.thin_mismatches,
+                                         args.thin_3p_exact, args.thin_min_gain);
+        timer.lap("panel thinning");
+    }
     // the report covers the panel and the new primers together; the CSV lists the new ones, numbered on from the panel
     std::vector<KmerStat> rep_f = good_f, rep_r = good_r;
     for (const auto &w : panel_f) rep_f.push_back(KmerStat{w, SEQ_DIR_FWD});
@@ -1545,6 +1673,7 @@ int run(const Args &args, std::string &stdout_text)
         stdout_text += coverage_report_mm(eng, aln, rep_f, rep_r, records, args.window_size, args.overlap_size,
                                           args.search_windows_size, args.kmer_size, args.coverage_mismatches,
                                           args.coverage_3p_exact);
+    stdout_text += thin_text;
     if (args.tubes > 0) stdout_text += tubes_report(good_f, good_r, tubes, args.tubes);
     if (background) {   // the CSV's primers by their CSV names, the panel's by the numbers the CSV continues from
         std::vector<std::string> names, words;

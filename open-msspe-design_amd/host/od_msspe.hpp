@@ -63,6 +63,16 @@ struct Args {
     int coverage_mismatches = 0;
     std::string coverage_3p_exact_text = "3";   // read (as an integer) only when coverage_mismatches > 0
     int coverage_3p_exact = 3;
+    // --thin-panel true: after the cover / tube step the primers are thinned to those their coverage needs -- a greedy
+    // set cover over "primer p has a match in segment s" within thin_mismatches mismatches, the last thin_3p_exact
+    // bases exact (msspe_panel_thin; the panel of --existing-primers is forced); a pick must cover thin_min_gain new
+    // segments.  The reports, the background blocks and the CSV see the thinned lists; the report gains a block.
+    // The --thin-* values are read only with the switch.  "false": nothing changes.
+    std::string thin_panel = "false";
+    int thin_mismatches = 0;
+    std::string thin_3p_exact_text = "3";
+    int thin_3p_exact = 3;
+    int thin_min_gain = 1;
     // --background FASTA: after the coverage report, the off-target sites of every kept primer in these records (both
     // strands, up to background_mismatches mismatches, the last background_3p_exact bases exact:
     // msspe_background_sites); with max_background_sites >= 0 candidates with more sites are dropped before the
@@ -224,6 +234,26 @@ std::map<std::string, int> conflict_tubes_on_device(Engine &eng, const std::vect
 // "Tube assignment (up to N tubes):", the tubes in use, primers per tube (CSV rows) and primers in no tube
 std::string tubes_report(const std::vector<KmerStat> &fwd, const std::vector<KmerStat> &rev,
                          const std::map<std::string, int> &tubes, int max_tubes);
+// --thin-panel (engine extension): the sequential rule of DESIGN.md 4.10 over incidence rows -- rows[p] holds one bit
+// per segment (bit s & 63 of word s >> 6).  Forced primers cover first and are never picked; every round picks the
+// unforced, unpicked primer with the most uncovered segments (ties: the lowest index) until that gain is below
+// min_gain.  The device's independent twin.
+struct ThinResult {
+    std::vector<int> order, gains;   // the picks in order
+    std::vector<char> keep;          // forced or picked
+    size_t covered_all = 0, covered_kept = 0;
+};
+ThinResult thin_panel(const std::vector<std::vector<uint64_t>> &rows, int min_gain, const std::vector<char> &forced);
+// the same rule as one msspe_panel_thin_packed_dev call on the resident alignment: fwd / rev are thinned in place,
+// the panel's primers are forced; returns the report's block
+std::string thin_panel_on_device(Engine &eng, const DeviceAlignment &aln, std::vector<KmerStat> &fwd,
+                                 std::vector<KmerStat> &rev, const std::vector<std::string> &panel_f,
+                                 const std::vector<std::string> &panel_r, int segment_size, int overlap_size,
+                                 int window_size, int kmer_size, int max_mismatches, int exact_3p, int min_gain);
+// "Panel thinning (up to M mismatches, last E bases exact, gain >= G):", the primers kept of those offered (forced
+// ones apart) and the segments covered by all of them and by the kept ones (forced primers cover in both figures)
+std::string thin_report(int max_mismatches, int exact_3p, int min_gain, size_t kept_f, size_t n_f, size_t kept_r,
+                        size_t n_r, size_t forced, size_t covered_all, size_t covered_kept, size_t segments);
 // main.rs:518-594 (text goes to `out`): the per-segment search runs on the device
 // (msspe_segment_coverage_dev), the totals per sequence / partition and the text on the host
 std::string coverage_report(Engine &eng, const DeviceAlignment &aln, const std::vector<KmerStat> &fwd,

@@ -33,6 +33,7 @@ EXPORTS = [
     "msspe_kmer_candidates_both_seeded_packed_dev",
     "msspe_segment_coverage_packed_dev",
     "msspe_segment_coverage_mm", "msspe_segment_coverage_mm_dev", "msspe_segment_coverage_mm_packed_dev",
+    "msspe_panel_thin", "msspe_panel_thin_dev", "msspe_panel_thin_packed_dev",
     "msspe_device_put_stream_packed", "msspe_background_sites_packed_dev", "msspe_background_sites",
     "msspe_background_thal_packed_dev", "msspe_background_thal",
     "msspe_background_amplicons_packed_dev", "msspe_background_amplicons",
@@ -99,6 +100,11 @@ class AmpliconOpt(C.Structure):
 class MismatchOpt(C.Structure):
     """msspe_mismatch_opt: coverage within max_mismatches, the primer's last exact_3p bases exact."""
     _fields_ = [("max_mismatches", C.c_int), ("exact_3p", C.c_int)]
+
+
+class ThinOpt(C.Structure):
+    """msspe_thin_opt: a pick must cover at least min_gain segments nothing kept covers yet."""
+    _fields_ = [("min_gain", C.c_int)]
 
 
 def lib_path() -> Path:
@@ -226,6 +232,12 @@ def load_library() -> C.CDLL:
                                             vp, C.c_int, vp, C.c_int, vp, vp]
     L.msspe_segment_coverage_mm_dev.argtypes = L.msspe_segment_coverage_mm.argtypes
     L.msspe_segment_coverage_mm_packed_dev.argtypes = L.msspe_segment_coverage_mm.argtypes
+    L.msspe_panel_thin.argtypes = [vp, vp, C.c_int, C.c_size_t, C.POINTER(KmerOpt), C.POINTER(MismatchOpt),
+                                   C.POINTER(ThinOpt), u64p, C.c_int, u64p, C.c_int, vp, vp, vp, vp,
+                                   C.POINTER(C.c_int), vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+    L.msspe_device_put.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_void_p)]
+    L.msspe_panel_thin_dev.argtypes = L.msspe_panel_thin.argtypes
+    L.msspe_panel_thin_packed_dev.argtypes = L.msspe_panel_thin.argtypes
     L.msspe_device_put_stream_packed.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int,
                                                  C.POINTER(vp), C.POINTER(C.c_size_t), vp]
     L.msspe_background_sites_packed_dev.argtypes = [vp, vp, C.c_size_t, C.c_int, C.POINTER(MismatchOpt), u64p, C.c_int,
@@ -742,6 +754,59 @@ class Engine:
         self._check(fn(self.ptr, seqs_arg, n_seq, seq_len, C.byref(opt), C.byref(mm), f.ctypes.data, len(f),
                        r.ctypes.data, len(r), best.ctypes.data, counts.ctypes.data if per_primer else None))
         return (best, counts) if per_primer else best
+
+    # ---- a panel thinned to the primers its coverage needs (engine extension; msspe_panel_thin*) -----------------
+    def panel_thin(self, genomes, opt: KmerOpt, fwd, rev, max_mismatches: int, exact_3p: int, min_gain: int = 1,
+                   forced=None, form: str = "host"):
+        """Greedy set cover of the segments the primers match in within max_mismatches, the last exact_3p bases
+        exact (msspe_panel_thin*).  genomes: uint8 (n_seq, L) host array -- form "host" hands it over as it is, "dev"
+        and "packed" upload it first (as bytes / as packed rows) and call the device forms; or a resident alignment as
+        (device address, n_seq, seq_len) with form "dev" or "packed".  fwd / rev: primer strings or packed words;
+        forced: flags per primer (forward first), kept whatever they cover.  Returns (keep uint8[n], order, gains,
+        covered uint8 (n_seq, P), covered_all, covered_kept)."""
+        fn = {"host": self.L.msspe_panel_thin, "dev": self.L.msspe_panel_thin_dev,
+              "packed": self.L.msspe_panel_thin_packed_dev}[form]
+        owned = None
+        if isinstance(genomes, tuple):
+            if form == "host":
+                raise ValueError("a resident alignment needs form='dev' or 'packed'")
+            handle, n_seq, seq_len = genomes
+            seqs_arg = C.c_void_p(handle)
+        else:
+            a = np.ascontiguousarray(genomes, dtype=np.uint8)
+            n_seq, seq_len = a.shape
+            if form == "host":
+                seqs_arg = a.ctypes.data
+            elif form == "packed":
+                owned = self.put_rows_packed(a)
+                seqs_arg = C.c_void_p(owned)
+            else:
+                dev = C.c_void_p()
+                self._check(self.L.msspe_device_put(self.ptr, a.ctypes.data, a.size, C.byref(dev)))
+                owned = int(dev.value)
+                seqs_arg = C.c_void_p(owned)
+        try:
+            P = 0 if seq_len < opt.segment_size else (seq_len - opt.segment_size) // opt.overlap_size + 1
+            f, r = _words(fwd), _words(rev)
+            n = len(f) + len(r)
+            flags = None if forced is None else np.ascontiguousarray(np.asarray(forced) != 0, dtype=np.uint8)
+            if flags is not None and flags.shape != (n,):
+                raise ValueError("forced needs one flag per primer")
+            keep = np.zeros(n, dtype=np.uint8)
+            order = np.zeros(max(n, 1), dtype=np.uint32)
+            gains = np.zeros(max(n, 1), dtype=np.uint32)
+            covered = np.zeros((n_seq, P), dtype=np.uint8)
+            n_picked, c_all, c_kept = C.c_int(0), C.c_longlong(0), C.c_longlong(0)
+            mm, thin = MismatchOpt(max_mismatches, exact_3p), ThinOpt(min_gain)
+            self._check(fn(self.ptr, seqs_arg, n_seq, seq_len, C.byref(opt), C.byref(mm), C.byref(thin),
+                           f.ctypes.data, len(f), r.ctypes.data, len(r),
+                           flags.ctypes.data if flags is not None else None, keep.ctypes.data, order.ctypes.data,
+                           gains.ctypes.data, C.byref(n_picked), covered.ctypes.data, C.byref(c_all), C.byref(c_kept)))
+        finally:
+            if owned is not None:
+                self.device_free(owned)
+        return (keep, order[:n_picked.value].copy(), gains[:n_picked.value].copy(), covered, int(c_all.value),
+                int(c_kept.value))
 
     # ---- off-target sites in a background ------------------------------------------------------
     @staticmethod
