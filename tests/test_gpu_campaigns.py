@@ -27,6 +27,7 @@ def run_tool(monkeypatch, name, *args):
     ("random_campaign_stage_b.py", (3, 12)),
     ("random_campaign_blocks.py", (8, 14)),
     ("random_campaign_cli.py", (21, 8)),
+    ("random_campaign_session.py", (9, 1)),
 ])
 def test_campaign_sample(monkeypatch, tool, args):
     run_tool(monkeypatch, tool, *args)

@@ -1,0 +1,43 @@
+#!/usr/bin/env python3
+"""Randomised differential campaign over the newer entry points on ONE long-lived context (development aid, GPU): per
+seed one Engine and a schedule of calls -- END, pool against pool, the thal record, seeded stage A, coverage within M
+mismatches, panel thinning, cover and tubes, the background family -- in shuffled order, growing and shrinking, on dirty
+output buffers and under engine options, each against the oracle or the family's model (tests/session_campaign_model.py),
+and the first three calls once more at the end.
+usage: random_campaign_session.py [seed] [sessions] [--models-only] [--only INDEX]
+  --models-only  no engine: every schedule and expected value, the model time per call and the counters per session
+  --only INDEX   run the schedule up to and including call INDEX and check only that call"""
+import sys
+import time
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parent.parent
+for p in (ROOT / "open-msspe-design_amd", ROOT / "oracle", ROOT / "tests"):
+    sys.path.insert(0, str(p))
+import session_campaign_model as scm
+
+args = sys.argv[1:]
+models_only = "--models-only" in args
+only = int(args[args.index("--only") + 1]) if "--only" in args else None
+pos = [a for i, a in enumerate(args) if not a.startswith("--") and (i == 0 or args[i - 1] != "--only")]
+seed0 = int(pos[0]) if pos else 8
+sessions = int(pos[1]) if len(pos) > 1 else 4
+bad = 0
+for seed in range(seed0, seed0 + sessions):
+    if models_only:
+        counts, seconds = scm.models_only(seed, log=lambda s: print(s, flush=True))
+        print(f"session {seed}: model time {seconds:.1f} s, counters {counts}", flush=True)
+        continue
+    import msspe_amd as m
+    t0 = time.perf_counter()
+    eng = m.Engine(0)
+    try:
+        failures = scm.run_session(seed, eng, m, only=only, log=lambda s: print(s, flush=True))
+    finally:
+        eng.close()
+    for f in failures:
+        print("DIFFERS", f, flush=True)
+    print(f"session {seed}: {len(failures)} failures, {time.perf_counter() - t0:.1f} s", flush=True)
+    bad += len(failures)
+print("BAD", bad)
+sys.exit(1 if bad else 0)
