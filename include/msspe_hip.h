@@ -38,7 +38,9 @@ enum msspe_status {
     MSSPE_OK = 0,
     MSSPE_ERR_ARG = 1,      /* NULL pointer, bad range, non-ACGT oligo ...            */
     MSSPE_ERR_K = 2,        /* unsupported oligo length                               */
-    MSSPE_ERR_TABLES = 3,   /* thermodynamic parameter files missing / malformed      */
+    MSSPE_ERR_TABLES = 3,   /* thermodynamic parameter files missing / malformed; from a
+                               dimer call: an enthalpy that is not an integer or is
+                               beyond 1e6 in magnitude (see msspe_create)              */
     MSSPE_ERR_DEVICE = 4,   /* HIP error (no device, launch failure, out of memory)   */
     MSSPE_ERR_CAPACITY = 5, /* caller-supplied output capacity exceeded               */
     MSSPE_ERR_NOMEM = 6
@@ -64,7 +66,31 @@ void msspe_chem_primer3_defaults(msspe_chem *c);  /* 50 / 1.5 / 0.6 / 50 nM / 37
 
 /* device: HIP device ordinal.  params_path: a Primer3-format directory (what ntthal gets via
  * `-path`, od-msspe/src/delta_g.rs:90,107-108), or a consolidated bundle file, or NULL for the
- * bundle shipped next to the library. */
+ * bundle shipped next to the library.
+ *
+ * The files are read as they are and every kernel computes with what they hold; which kernel answers
+ * a pair is decided from them, per chemistry (msspe_host_table_routes reads the decision):
+ *   - every finite enthalpy an integer of magnitude at most 1e6: gates everything.  Otherwise every
+ *     dimer call (ANY, END, _ab, edges, cover, tubes, detail, background thal / amplicons, and the
+ *     self-dimers of msspe_oligo_stats*; its Tm, GC % and HAIRPIN_TH asked for without them are
+ *     served) returns MSSPE_ERR_TABLES and msspe_last_error says "not
+ *     integral", where ntthal would compute; msspe_create itself succeeds and the context stays
+ *     usable.
+ *   - fast_ok (H a multiple of 10, every Watson-Crick stack exists, the entropy clamp out of reach for
+ *     16-mers, loop rows fit): the register-table f64 kernels, the END screen's first stage, one-lane
+ *     self-dimers.  A missing Watson-Crick stack also sets split_max_k and wave_max_k to 0: only the
+ *     dense kernel restates thal.c's rule for it.
+ *   - int_ok (also S on the 0.01 grid and int32 ranges within reach): the integer first stage and
+ *     the integer list stage.
+ *   - row_ok (also every end term and Watson-Crick stack exists): the row kernel, and the general
+ *     integer kernel's assumption that every complementary cell is reachable.  End terms always exist
+ *     (the bare closing pair at the least) and a missing Watson-Crick stack clears fast_ok, so with the
+ *     present builders row_ok equals int_ok.
+ *   - split_max_k, 0 to 32 (int32 and 16-bit biased-H ranges, checked per length): the split-table
+ *     kernel up to that length.
+ *   - wave_max_k, 0 to 32 (entropy cutoff out of reach, checked per length): one wave per pair up to
+ *     that length; above it the dense kernel.
+ * A route that is not exact for a table stands down; the results are the same doubles on every route. */
 int msspe_create(int device, const char *params_path, msspe_ctx **out);
 void msspe_destroy(msspe_ctx *ctx);
 const char *msspe_last_error(const msspe_ctx *ctx);
@@ -102,7 +128,8 @@ int msspe_set_option(msspe_ctx *ctx, const char *key, const char *value);
  *   "device"          HIP ordinal           "n_cu"  compute units
  *   "lds_reads_zero"  1: the per-engine probe found that LDS reads beyond a block's allocation return 0 (every
  *                     gfx950 seen), i.e. the row-specialised first stage may run; 0: the general kernel runs
- *   "row_kernel"      1: 13-mer pools go to the row-specialised first stage with the current options
+ *   "row_kernel"      1: 13-mer pools go to the row-specialised first stage with the current options and the
+ *                     tables of every chemistry this context has met (0 once a call found row_ok unset: see msspe_create)
  *   "stage_a_fast_iterations" / "stage_a_general_iterations" / "stage_a_rebuilds" / "stage_a_idle_iterations"
  *                     the last msspe_kmer_candidates* call's greedy loop: iterations that recorded winners from the
  *                     partitions' leaders alone / after a walk over posting lists, candidate lists made, idle
@@ -389,6 +416,11 @@ int msspe_pair_stage_samples(msspe_ctx *ctx, uint64_t *out, int capacity, int *n
 int msspe_host_pair_tables(const char *params_path, const msspe_chem *chem, float dg_threshold,
                            double *fast_S, int32_t *fast_H, int32_t *int_g, int32_t *int_T,
                            double consts[8]);
+/* Host only: which routes these tables open at this chemistry (see msspe_create).  out = pair tables
+ * ok, fast_ok, int_ok, row_ok, split kernel usable, split_max_k, wave_max_k, 0.  Tables with a
+ * non-integral enthalpy give MSSPE_OK with out[0] = 0 (every dimer call would be refused);
+ * MSSPE_ERR_TABLES only when the files cannot be loaded. */
+int msspe_host_table_routes(const char *params_path, const msspe_chem *chem, int32_t out[8]);
 /* The same for the long-oligo kernel (csrc/split_tables.hpp): S / H / g hold info[2] entries, L 1024,
  * X info[3]; info = usable, longest oligo covered, entry count, X count. */
 int msspe_host_split_tables(const char *params_path, const msspe_chem *chem, double *S, int32_t *H,

@@ -205,6 +205,25 @@ bool same_chem(const msspe_chem &a, const msspe_chem &b)
            a.temp_c == b.temp_c && a.max_loop == b.max_loop;
 }
 
+// Which kernels may answer a pair under these tables (ChemEntry's flags), with the device tables they go with:
+// chem_entry() and msspe_host_table_routes() both decide here and nowhere else.
+struct TableRoutes {
+    bool fast_ok = false, int_ok = false, row_ok = false;
+    int split_max_k = 0, wave_max_k = 0;
+};
+
+TableRoutes table_routes(const NNTables &tb, const PairTables &pt, int max_loop, FastTables &ft, IntTables &it,
+                         SplitTables &st)
+{
+    TableRoutes r;
+    r.fast_ok = build_fast_tables(tb, pt, pairs_fast_max_k(), ft);
+    r.int_ok = r.fast_ok && build_int_tables(ft, pairs_fast_max_k(), it);
+    r.row_ok = r.int_ok && pairs_row_tables_ok(it);
+    r.split_max_k = build_split_tables(pt, max_loop, st) ? st.max_k : 0;
+    r.wave_max_k = st.f64_max_k;
+    return r;
+}
+
 // kind: kCutEndT is the entry of the END screen (msspe_cross_dimer_end*), whose cut is msspe_t_cut(threshold), and
 // kCutAnyT that of an ANY fill decided on t (msspe_background_thal*, mode 1); each kind is cached apart from the
 // others of the same chemistry and threshold, so that no call can pick up another's cut.
@@ -234,17 +253,18 @@ int chem_entry(msspe_ctx *ctx, const msspe_chem &chem, float threshold, ChemEntr
     HIP_TRY(ctx, hipMemcpy(e.d_pt, host_pt, sizeof host_pt, hipMemcpyHostToDevice));
     {
         auto ft = std::make_unique<FastTables>();
-        e.fast_ok = build_fast_tables(ctx->host_tb, host_pt[0], pairs_fast_max_k(), *ft);
+        auto it = std::make_unique<IntTables>();
+        auto st = std::make_unique<SplitTables>();
+        const TableRoutes r = table_routes(ctx->host_tb, host_pt[0], chem.max_loop, *ft, *it, *st);
+        e.fast_ok = r.fast_ok;
+        e.int_ok = r.int_ok;
+        e.row_ok = r.row_ok;
+        e.split_max_k = r.split_max_k;
+        e.wave_max_k = r.wave_max_k;
         HIP_TRY(ctx, hipMalloc((void **)&e.d_ft, sizeof(FastTables)));
         HIP_TRY(ctx, hipMemcpy(e.d_ft, ft.get(), sizeof(FastTables), hipMemcpyHostToDevice));
-        auto it = std::make_unique<IntTables>();
-        e.int_ok = e.fast_ok && build_int_tables(*ft, pairs_fast_max_k(), *it);
-        e.row_ok = e.int_ok && pairs_row_tables_ok(*it);
         HIP_TRY(ctx, hipMalloc((void **)&e.d_it, sizeof(IntTables)));
         HIP_TRY(ctx, hipMemcpy(e.d_it, it.get(), sizeof(IntTables), hipMemcpyHostToDevice));
-        auto st = std::make_unique<SplitTables>();
-        e.split_max_k = build_split_tables(host_pt[0], chem.max_loop, *st) ? st->max_k : 0;
-        e.wave_max_k = st->f64_max_k;
         HIP_TRY(ctx, hipMalloc((void **)&e.d_st, sizeof(SplitTables)));
         HIP_TRY(ctx, hipMemcpy(e.d_st, st.get(), sizeof(SplitTables), hipMemcpyHostToDevice));
     }
@@ -718,8 +738,13 @@ int msspe_get_info(msspe_ctx *ctx, const char *key, long long *value_out)
     if (k == "device") *value_out = ctx->device;
     else if (k == "n_cu") *value_out = ctx->n_cu;
     else if (k == "lds_reads_zero") *value_out = ctx->lds_reads_zero ? 1 : 0;
-    else if (k == "row_kernel")
-        *value_out = ctx->lds_reads_zero && ctx->opt.row_oob && ctx->opt.pair_kernel == 0 && !ctx->opt.force_generic ? 1 : 0;
+    else if (k == "row_kernel") {
+        // ... and with the tables of every chemistry used so far (ChemEntry::row_ok)
+        bool tables_ok = true;
+        for (const auto &e : ctx->chem_cache) tables_ok = tables_ok && e.row_ok;
+        *value_out = ctx->lds_reads_zero && ctx->opt.row_oob && ctx->opt.pair_kernel == 0 && !ctx->opt.force_generic &&
+                     tables_ok ? 1 : 0;
+    }
     else if (k == "stage_a_fast_iterations") *value_out = ctx->kmer.loop_stats()[0];
     else if (k == "stage_a_general_iterations") *value_out = ctx->kmer.loop_stats()[1];
     else if (k == "stage_a_rebuilds") *value_out = ctx->kmer.loop_stats()[2];
@@ -1803,9 +1828,10 @@ int msspe_oligo_stats_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k,
         return fail(ctx, MSSPE_ERR_ARG, "chemistry: stage B needs mv >= 0, dv >= 0 and (dv == 0 or dntp >= 0)");
     if (n == 0) return MSSPE_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // Tm, GC % and HAIRPIN_TH need no pair tables: tables that the dimer calls refuse (MSSPE_ERR_TABLES) still serve them
     ChemEntry *ce = nullptr;
-    int rc = chem_entry(ctx, *chem, -9000.0f, &ce);   // threshold unused by the self modes
-    if (rc) return rc;
+    int rc = MSSPE_OK;
+    if ((d_self_any || d_self_end) && (rc = chem_entry(ctx, *chem, -9000.0f, &ce))) return rc;   // threshold unused by the self modes
     if ((rc = ensure_workspace(ctx, (size_t)(k + 1) * (size_t)(k + 1)))) return rc;
     if (d_tm || d_gc)
         HIP_TRY(ctx, launch_oligo_tm(d_pool, n, k, chem->dna_conc, chem->mv, chem->dv, chem->dntp,
@@ -1816,7 +1842,7 @@ int msspe_oligo_stats_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k,
     // single oligo's.  Large pools: one LANE per oligo through the f64 register-table kernels over the list of (i, i)
     // (thal_pairs.hip, 56 then 72 slots), the wave kernel behind them for larger tables.  The dense kernel, one lane
     // per oligo over a global workspace, takes what is left (self-complementary oligos: another RC constant).
-    const bool wave = wave_ok(ctx, ce, k);
+    const bool wave = ce && wave_ok(ctx, ce, k);
     const bool lane_ok = wave && n >= ctx->opt.self_lane_from && reg_tables_ok(ctx, ce, k);
     if (wave && (d_self_any || d_self_end)) {
         if ((rc = ensure_overflow(ctx, n))) return rc;
@@ -3057,6 +3083,36 @@ int msspe_host_pair_tables(const char *params_path, const msspe_chem *chem, floa
     consts[5] = fast_ok ? 1.0 : 0.0;
     consts[6] = int_ok ? 1.0 : 0.0;
     consts[7] = (double)FastTables::kCount;
+    return MSSPE_OK;
+}
+
+int msspe_host_table_routes(const char *params_path, const msspe_chem *chem, int32_t out[8])
+{
+    // host only: the flags chem_entry() would set for these tables and this chemistry
+    if (!chem || !out) return MSSPE_ERR_ARG;
+    for (int q = 0; q < 8; ++q) out[q] = 0;
+    auto tb = std::make_unique<NNTables>();
+    std::string err;
+    const std::string path = params_path && *params_path ? params_path : default_bundle_path();
+    if (!load_nn_tables(path, *tb, err)) return MSSPE_ERR_TABLES;
+    if (!(chem->dna_conc > 0) || chem->max_loop < 0 || chem->max_loop > 30) return MSSPE_ERR_ARG;
+    auto pt = std::make_unique<PairTables>();
+    for (int sym = 1; sym >= 0; --sym) {   // the ordinary tables last: they are the ones the routes are built from
+        const ThalConsts c = make_dimer_consts(chem->mv, chem->dv, chem->dntp, chem->dna_conc, chem->temp_c,
+                                               chem->max_loop, sym == 1, -9000.0f);
+        if (!build_pair_tables(*tb, c, *pt, err)) return MSSPE_OK;   // out[0] = 0: every dimer call is refused
+    }
+    auto ft = std::make_unique<FastTables>();
+    auto it = std::make_unique<IntTables>();
+    auto st = std::make_unique<SplitTables>();
+    const TableRoutes r = table_routes(*tb, *pt, chem->max_loop, *ft, *it, *st);
+    out[0] = 1;
+    out[1] = r.fast_ok;
+    out[2] = r.int_ok;
+    out[3] = r.row_ok;
+    out[4] = r.split_max_k > 0;
+    out[5] = r.split_max_k;
+    out[6] = r.wave_max_k;
     return MSSPE_OK;
 }
 

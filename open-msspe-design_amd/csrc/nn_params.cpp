@@ -525,7 +525,13 @@ static void fill_compact_planes(const PairTables &pt, T &out, bool &ok, double &
         put(T::kEndL + q, pt.endL_S[q], pt.endL_H[q]);
         put(T::kEndR + q, pt.endR_S[q], pt.endR_H[q]);
     }
-    for (int q = 0; q < 16; ++q) put(T::kWC + q, pt.wc_S[q], pt.wc_H[q]);
+    for (int q = 0; q < 16; ++q) {
+        put(T::kWC + q, pt.wc_S[q], pt.wc_H[q]);
+        // A Watson-Crick stack the files do not have: thal.c's maxTM() then never extends the helix (T1 = -inf), while
+        // the kernels that read these planes compare a T1 formed from the placeholder and extend it wherever the
+        // start term's T0 is negative.  Such tables go to the dense kernel, which restates maxTM() term by term.
+        if (pt.wc_H[q] >= kHInf) ok = false;
+    }
 }
 
 bool build_fast_tables(const NNTables &t, const PairTables &pt, int max_k, FastTables &out)

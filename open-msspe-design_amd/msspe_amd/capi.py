@@ -23,7 +23,7 @@ EXPORTS = [
     "msspe_cross_dimer_end_ab_dev", "msspe_cross_dimer_end_ab", "msspe_t_cut",
     "msspe_conflict_cover_dev", "msspe_conflict_cover",
     "msspe_conflict_tubes_dev", "msspe_conflict_tubes",
-    "msspe_last_overflow_pairs", "msspe_pair_stage_stats", "msspe_pair_stage_samples", "msspe_host_pair_tables", "msspe_host_split_tables", "msspe_device_put_rows", "msspe_segment_coverage", "msspe_segment_coverage_dev",
+    "msspe_last_overflow_pairs", "msspe_pair_stage_stats", "msspe_pair_stage_samples", "msspe_host_pair_tables", "msspe_host_table_routes", "msspe_host_split_tables", "msspe_device_put_rows", "msspe_segment_coverage", "msspe_segment_coverage_dev",
     "msspe_device_put", "msspe_device_get", "msspe_device_free", "msspe_thal_detail_pairs", "msspe_profile_enable", "msspe_profile_read",
     "msspe_oligo_stats_dev", "msspe_oligo_stats",
     "msspe_kmer_candidates", "msspe_kmer_candidates_dev", "msspe_round_g_f32",
@@ -265,6 +265,7 @@ def load_library() -> C.CDLL:
         getattr(L, name.replace("_background_thal", "_background_thal_flank")
                 .replace("_background_amplicons", "_background_amplicons_flank")).argtypes = at[:cut] + [C.c_int] + at[cut:]
     L.msspe_device_get.argtypes = [vp, vp, C.c_size_t, vp]
+    L.msspe_host_table_routes.argtypes = [C.c_char_p, C.POINTER(Chem), C.POINTER(C.c_int32)]
     L.msspe_thal_detail_pairs.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(Chem), C.c_int, vp]
     L.msspe_round_g_f32.restype = C.c_float
     L.msspe_round_g_f32.argtypes = [C.c_double]
@@ -340,6 +341,19 @@ def t_cut(tm_threshold: float) -> float:
 
 # PRIMER_MAX_SELF_END_TH, the SELF_END limit od-msspe applies to each primer: the END screen's default
 END_TM_THRESHOLD = 47.0
+
+
+TABLE_ROUTE_KEYS = ("pair_tables", "fast_ok", "int_ok", "row_ok", "split_ok", "split_max_k", "wave_max_k")
+
+
+def host_table_routes(params_path: str | None = None, chem: Chem | None = None) -> dict:
+    """Which kernels the tables at params_path open at this chemistry (no device needed): msspe_host_table_routes."""
+    out = (C.c_int32 * 8)()
+    chem = chem or Chem.ntthal()
+    rc = load_library().msspe_host_table_routes(str(params_path).encode() if params_path else None, C.byref(chem), out)
+    if rc:
+        raise MsspeError(rc, f"msspe_host_table_routes({params_path})")
+    return dict(zip(TABLE_ROUTE_KEYS, list(out)[:7]))
 
 
 def _seed_words(seed, k: int) -> np.ndarray | None:

@@ -42,7 +42,7 @@ class PairTables:
     int_ok: bool
 
 
-def load_tables(msspe_amd, threshold: float = -9000.0) -> PairTables:
+def load_tables(msspe_amd, threshold: float = -9000.0, params_path=None) -> PairTables:
     L = msspe_amd.capi.load_library()
     chem = msspe_amd.Chem.ntthal()
     S = np.zeros(K_COUNT)
@@ -52,7 +52,7 @@ def load_tables(msspe_amd, threshold: float = -9000.0) -> PairTables:
     consts = (C.c_double * 8)()
     L.msspe_host_pair_tables.argtypes = [C.c_char_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
-    rc = L.msspe_host_pair_tables(None, C.byref(chem), C.c_float(threshold), S.ctypes.data, H.ctypes.data,
+    rc = L.msspe_host_pair_tables(str(params_path).encode() if params_path else None, C.byref(chem), C.c_float(threshold), S.ctypes.data, H.ctypes.data,
                                   g.ctypes.data, T.ctypes.data, consts)
     assert rc == 0 and int(consts[7]) == K_COUNT
     return PairTables(S, H, g, T, consts[0], consts[1], consts[2], consts[3], consts[4],

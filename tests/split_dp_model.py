@@ -46,7 +46,7 @@ def load_tables(msspe_amd, params_path=None, max_loop=30) -> SplitTables:
     X = np.zeros(K_XCOUNT, dtype=np.int32)
     info = (C.c_int32 * 4)()
     lib.msspe_host_split_tables.argtypes = [C.c_char_p, C.c_void_p] + [C.c_void_p] * 5 + [C.POINTER(C.c_int32)]
-    rc = lib.msspe_host_split_tables(params_path.encode() if params_path else None, C.byref(chem),
+    rc = lib.msspe_host_split_tables(str(params_path).encode() if params_path else None, C.byref(chem),
                                      S.ctypes.data, H.ctypes.data, g.ctypes.data, L.ctypes.data,
                                      X.ctypes.data, info)
     assert rc == 0 and info[2] == K_COUNT and info[3] == K_XCOUNT

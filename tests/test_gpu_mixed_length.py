@@ -183,7 +183,7 @@ def test_tables_without_the_split_kernel(m, oracle, tmp_path):
     """Parameter files off the 0.01 e.u. grid: no split-table kernel.  A rectangle of 8-mer rows (which the square
     register-table chain would take) goes to the wave kernel, and with that off to the dense kernel; both equal
     the oracle on the same files."""
-    from test_gpu_thermo_parity import _perturbed, _read_bundle
+    from param_variants import _perturbed, _read_bundle
     sections = _perturbed(_read_bundle(oracle.default_bundle()), 0.003, 0.0)
     path = tmp_path / "offgrid.bundle"
     path.write_text("# test bundle\n" + "".join(

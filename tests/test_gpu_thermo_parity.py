@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from helpers import with_stem_loops
+from param_variants import _perturbed, _read_bundle
 
 pytestmark = pytest.mark.gpu
 
@@ -624,44 +625,6 @@ def test_small_fixed_lists_bound_the_launches(eng, m):
             eng.set_option("list_cap_log2", 0)
         for key in ("bitmap", "row_conflicts"):
             np.testing.assert_array_equal(got[key], want[key])
-
-
-def _read_bundle(path):
-    """{section: [lines]} of a parameter bundle ('@ name count' headers)."""
-    sections, name = {}, None
-    for line in path.read_text().splitlines():
-        if line.startswith("#") or not line.strip():
-            continue
-        if line.startswith("@"):
-            name = line.split()[1]
-            sections[name] = []
-        else:
-            sections[name].append(line)
-    return sections
-
-
-def _perturbed(sections, step_s, step_h):
-    """Shift every available entry of the stack / mismatch / terminal-stack / dangle entropies by
-    a multiple of step_s and the stack enthalpies by a multiple of step_h (tables stay plausible:
-    the point is that the engine computes with whatever the files hold)."""
-    out = {}
-    for name, lines in sections.items():
-        step = {"stack.ds": step_s, "stackmm.ds": step_s, "tstack2.ds": step_s, "tstack_tm_inf.ds": step_s,
-                "dangle.ds": step_s, "stack.dh": step_h}.get(name)
-        if step is None:
-            out[name] = list(lines)
-            continue
-        q, new = 0, []
-        for line in lines:
-            toks = []
-            for t in line.split():
-                if t != "inf":
-                    q += 1
-                    t = repr(round(float(t) + step * (q % 3 - 1), 6))
-                toks.append(t)
-            new.append(" ".join(toks))
-        out[name] = new
-    return out
 
 
 @pytest.mark.parametrize("k", [13, 20])

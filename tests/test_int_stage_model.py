@@ -43,7 +43,7 @@ def test_integer_tables_are_usable_and_consistent(tables):
         assert np.all(row[~ok] == big)
 
 
-def test_recurrence_matches_oracle_planes(tables, oracle, oracle_tables):
+def _recurrence_matches_oracle_planes(tables, oracle, oracle_tables):
     import msspe_amd
     args = oracle.ntthal_args()
     rng = np.random.default_rng(20260630)
@@ -65,6 +65,23 @@ def test_recurrence_matches_oracle_planes(tables, oracle, oracle_tables):
             assert Hc == H[i, j], (a, b, i, j)
             assert abs((2000.0 * H[i, j] - 620300.0 * S[i, j]) - G) < 0.5, (a, b, i, j)
     assert deferred < 0.15 * n_pairs
+
+
+def test_recurrence_matches_oracle_planes(tables, oracle, oracle_tables):
+    _recurrence_matches_oracle_planes(tables, oracle, oracle_tables)
+
+
+@pytest.mark.parametrize("variant", ["dangle_holes", "loops_and_bonuses"])
+def test_recurrence_matches_oracle_planes_on_other_tables(oracle, tmp_path, variant):
+    """The same on tables that are not the shipped ones (tests/param_variants.py): the oracle loads the same file.
+    dangle_holes leaves end terms with one dangle only, loops_and_bonuses moves every loop row.  (wc_missing is not
+    here: tables without a Watson-Crick stack open no integer route, tests/test_param_variants.py.)"""
+    import msspe_amd
+    import param_variants as pv
+    path = pv.write_bundle(pv.variant_sections(variant), tmp_path / "variant.bundle")
+    tb = model.load_tables(msspe_amd, params_path=path)
+    assert tb.fast_ok and tb.int_ok
+    _recurrence_matches_oracle_planes(tb, oracle, oracle.Tables(path))
 
 
 def test_known_strong_duplex(tables, oracle, oracle_tables):

@@ -54,8 +54,7 @@ def test_max_loop_cuts_the_loop_rows():
     assert L[4, 4] != model.K_BIG and L[4, 5] == model.K_BIG and L[0, 9] == model.K_BIG and L[0, 8] == 0
 
 
-@pytest.mark.parametrize("k,n_pairs", [(18, 60), (24, 40), (28, 25)])
-def test_recurrence_matches_oracle_planes(tables, consts, oracle, oracle_tables, k, n_pairs):
+def _recurrence_matches_oracle_planes(tables, consts, oracle, oracle_tables, k, n_pairs):
     import msspe_amd
     args = oracle.ntthal_args()
     rng = np.random.default_rng(k)
@@ -75,3 +74,21 @@ def test_recurrence_matches_oracle_planes(tables, consts, oracle, oracle_tables,
             assert Hc == H[i, j], (a, b, i, j)
             assert abs((2000.0 * H[i, j] - 620300.0 * S[i, j]) - G) < 0.5, (a, b, i, j)
     assert hard < 0.2 * n_pairs
+
+
+@pytest.mark.parametrize("k,n_pairs", [(18, 60), (24, 40), (28, 25)])
+def test_recurrence_matches_oracle_planes(tables, consts, oracle, oracle_tables, k, n_pairs):
+    _recurrence_matches_oracle_planes(tables, consts, oracle, oracle_tables, k, n_pairs)
+
+
+@pytest.mark.parametrize("k,n_pairs", [(18, 60), (24, 40), (28, 25)])
+@pytest.mark.parametrize("variant", ["dangle_holes", "loops_and_bonuses"])
+def test_recurrence_matches_oracle_planes_on_other_tables(consts, oracle, tmp_path, variant, k, n_pairs):
+    """The same on tables that are not the shipped ones (tests/param_variants.py), which the oracle loads from the
+    same file; the split kernel covers every length under each of them."""
+    import msspe_amd
+    import param_variants as pv
+    path = pv.write_bundle(pv.variant_sections(variant), tmp_path / "variant.bundle")
+    tb = model.load_tables(msspe_amd, params_path=path)
+    assert tb.usable and tb.max_k == 32
+    _recurrence_matches_oracle_planes(tb, consts, oracle, oracle.Tables(path), k, n_pairs)
