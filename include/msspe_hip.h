@@ -106,7 +106,8 @@ const char *msspe_version(void);
  *   "split_min_k"    "2".."99"    shortest oligo that goes to the split-table kernel (16; 14- and 15-mers run the row-specialised first stage)
  *   "wave_kernel"    "0" | "1"    one-wave-per-pair f64 kernel in the chain (1)
  *   "list_cap_log2"  "0" | "20".."30"   fixed hand-over list size (0: sized by the call)
- *   "site_list_cap_log2" "12".."26"  msspe_background_thal*: the work list holds 2^this sites (22)
+ *   "site_list_cap_log2" "12".."26"  msspe_background_thal* and msspe_segment_coverage_thal*: the work list holds
+ *                                 2^this sites or matches (22)
  *   "amplicon_keys_cap_log2" "10".."28"  msspe_background_amplicons*: the stable-key buffer of a context is first
  *                                 made with 2^this keys (20) and doubles as needed; no result depends on it
  *   "panel_thin_matrix_max_mb" "1".."1048576"  msspe_panel_thin*: the most its incidence matrix may take, in MB
@@ -148,6 +149,12 @@ int msspe_set_option(msspe_ctx *ctx, const char *key, const char *value);
  *                     buffer on the way
  *   "amplicon_sort_us" / "amplicon_join_us"
  *                     the same call's device time of the key sort with the record ids, and of the join
+ *   "coverage_thal_matches" / "coverage_thal_slabs" / "coverage_thal_redone"
+ *                     the last msspe_segment_coverage_thal* call: matches scored, slabs scored, and slabs whose
+ *                     matches did not fit the work list and were split and listed again
+ *   "coverage_thal_list_us" / "coverage_thal_score_us" / "coverage_thal_fold_us"
+ *                     the same call's device time of its phases, summed over the slabs: the match listing (split
+ *                     slabs included), template oligos and thal, the fold with the per-primer counts
  *   "cover_rounds"    the last msspe_conflict_cover* call: rounds that deleted nodes
  *   "cover_keys_us" / "cover_symmetrise_us" / "cover_rounds_us"
  *                     the same call's device time of its phases: sort and keys, S = B | B^T, the rounds
@@ -860,6 +867,76 @@ int msspe_background_amplicons_flank(msspe_ctx *ctx, const char *const *records,
                                      uint64_t *amplicons_out, uint64_t *n_amplicons_out, msspe_amplicon *amplicons,
                                      uint64_t capacity, uint64_t *count_out, uint64_t *record_start_out);
 
+/* ---- segment coverage scored with thal (engine extension, no reference counterpart) ---------------------------
+ * msspe_segment_coverage_mm* says which segments hold a match by a string rule; these calls say which of those
+ * matches would hold the primer at a temperature -- msspe_background_thal*'s question, asked of the target alignment.
+ * The alignment, msspe_kmer_opt, msspe_mismatch_opt and primer words (HOST, msspe_pack_oligos form, a reverse word in
+ * primer orientation) are those of msspe_segment_coverage_mm*, and so are segments, windows, positions and validity.
+ * A MATCH is a triple (segment s = r * P + j, primer index q, window position p) that rule accepts; q runs over the
+ * forward primers first, then the reverse primers.  A forward primer is compared in the head window, a reverse primer
+ * against the reverse complement of the tail window's k columns.  The TEMPLATE OLIGO o2 is the strand the primer
+ * anneals to, written 5'->3':
+ *   forward primer: o2 = revcomp(the head window's k columns at p);
+ *   reverse primer: o2 = the tail window's k columns at p, as written.
+ * These are the plus- and minus-strand rules of msspe_background_thal*; an exact match gives o2 = revcomp(u) in either
+ * direction.  The MATCH SCORE is thal of (oligo 1 = u, oligo 2 = o2) under chem; mode is 1 for ANY and 2 for END1, the
+ * numbering of msspe_thal_detail_pairs.  Raw dG is +inf and raw t is 0 without a structure.  t_match = max(0, t), and
+ * the match is STABLE iff !(msspe_round_fixed_f32(t_match, 2) < tm_threshold), which the kernels test as
+ * t_match > msspe_t_cut(tm_threshold): the END screen's, stage B's and msspe_background_thal*'s rule.  A threshold
+ * <= 0 makes every match stable.  Template bases beyond the k columns (dangling ends) are not part of the score.
+ * Outputs are HOST in all three forms:
+ *   held_out[n_seq * P] (uint8, required): 0 = the segment has no match (exactly where the mm call's best_out is
+ *     255); 1 = it has matches, none of them stable; 2 = at least one stable match, in either direction.
+ *   t_best_out[n_seq * P] (double, optional): the greatest t_match over the segment's matches, the exact double;
+ *     0.0 where held_out is 0.
+ *   primer_segments_out[n_fwd + n_rev] (uint32, optional): segments with at least one match of the primer -- the mm
+ *     call's array.
+ *   primer_held_out[n_fwd + n_rev] (uint32, optional): segments with at least one STABLE match of the primer
+ *     (segments, not positions; duplicate primers count independently).
+ *   matches / capacity / count_out (optional; matches == NULL: no list): one msspe_scored_match per match, stable or
+ *     not, dg and t raw, sorted by (primer, segment, offset).  The capacity contract is msspe_background_sites': when
+ *     there are more matches than `capacity` the call returns MSSPE_ERR_CAPACITY, every other output and *count_out
+ *     (the number of matches) are valid, and the first `capacity` records to arrive are kept, sorted.
+ * Memory is bounded and nothing is dropped, as in msspe_background_thal*: the matches pass through the same work list
+ * of 2^site_list_cap_log2 entries in slabs of whole segment groups (a group: the S <= 64 segments one block of the
+ * comparison takes, 53 at window 50, k 13) against a range of primers.  A slab whose matches overrun the list -- the
+ * listing kernel's counter runs past the capacity, nothing is written behind it -- is split by groups, then by
+ * primers, and listed again; no output ever comes from a truncated list.  If one group against one primer still
+ * overruns (more than 2^site_list_cap_log2 window positions in one group: at the minimum of 2^12 a window of more
+ * than 4096 positions), the call returns MSSPE_ERR_CAPACITY and msspe_last_error names the option and both figures.
+ * Routing is msspe_background_thal*'s over the explicit pair list; force_generic, wave_kernel, list_cap_log2 and
+ * site_list_cap_log2 apply as there.  msspe_get_info "coverage_thal_*" describes the last call.  The call leaves the
+ * context fit for any other call.
+ * Errors: those of msspe_segment_coverage_mm*; MSSPE_ERR_K for k outside 2..31 (thal needs two bases); MSSPE_ERR_ARG
+ * for a NULL chem or held_out, a mode outside {1, 2}, count_out NULL with a list, or a window of more than
+ * 2^26 positions (W - k >= 2^26); MSSPE_ERR_TABLES as every dimer call.  No segments or no primers: MSSPE_OK, outputs zeroed, count 0. */
+typedef struct {
+    uint32_t primer;      /* 0 .. n_fwd + n_rev - 1, forward primers first */
+    uint32_t segment;     /* r * P + j */
+    uint32_t offset;      /* p, 0 .. W - k */
+    uint16_t mismatches;  /* 0 .. max_mismatches */
+    uint16_t stable;      /* 1 iff max(0, t) > msspe_t_cut(tm_threshold) */
+    double dg, t;         /* raw */
+} msspe_scored_match;
+int msspe_segment_coverage_thal(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len,
+                                const msspe_kmer_opt *opt, const msspe_mismatch_opt *mm, const uint64_t *fwd_words,
+                                int n_fwd, const uint64_t *rev_words, int n_rev, const msspe_chem *chem, int mode,
+                                float tm_threshold, uint8_t *held_out, double *t_best_out,
+                                uint32_t *primer_segments_out, uint32_t *primer_held_out, msspe_scored_match *matches,
+                                uint64_t capacity, uint64_t *count_out);
+int msspe_segment_coverage_thal_dev(msspe_ctx *ctx, const uint8_t *d_seqs, int n_seq, size_t seq_len,
+                                    const msspe_kmer_opt *opt, const msspe_mismatch_opt *mm, const uint64_t *fwd_words,
+                                    int n_fwd, const uint64_t *rev_words, int n_rev, const msspe_chem *chem, int mode,
+                                    float tm_threshold, uint8_t *held_out, double *t_best_out,
+                                    uint32_t *primer_segments_out, uint32_t *primer_held_out,
+                                    msspe_scored_match *matches, uint64_t capacity, uint64_t *count_out);
+int msspe_segment_coverage_thal_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
+                                           const msspe_kmer_opt *opt, const msspe_mismatch_opt *mm,
+                                           const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
+                                           const msspe_chem *chem, int mode, float tm_threshold, uint8_t *held_out,
+                                           double *t_best_out, uint32_t *primer_segments_out,
+                                           uint32_t *primer_held_out, msspe_scored_match *matches, uint64_t capacity,
+                                           uint64_t *count_out);
 
 /* ---- several devices of one node ----------------------------------------------------------
  *

@@ -27,6 +27,7 @@
 #include "background_thal.hpp"
 #include "background_amplicons.hpp"
 #include "coverage_mm.hpp"
+#include "coverage_thal.hpp"
 #include "kernels.hpp"
 #include "kmer_stage.hpp"
 #include "nn_params.hpp"
@@ -124,6 +125,8 @@ struct msspe_ctx {
     CoverStage cover;                  // msspe_conflict_cover*: the symmetrised bitmap and the round state
     TubeStage tubes;                   // msspe_conflict_tubes*: its round state (the graph lives in cover's buffers)
     PanelThin thin;                    // msspe_panel_thin*: the incidence matrix, covered words, gains and round state
+    CoverageThal cov_thal;             // msspe_segment_coverage_thal*: plane words, per-segment words, cell bitmaps,
+                                       // counters, the caller's list (its work list is site_work below)
     // msspe_background_thal*: the work list (site records, their pairs, raw dG and t), the site pool [primers | site
     // oligos], 4 n counts (sites, then stable sites) and the slab's site counter; with a template flank also the
     // sites' class codes, and the class counters with the grouping cursors behind them
@@ -754,6 +757,12 @@ int msspe_get_info(msspe_ctx *ctx, const char *key, long long *value_out)
     else if (k == "background_thal_redone") *value_out = ctx->site_work.redone;
     else if (k == "background_thal_flank_classes") *value_out = ctx->site_work.flank_classes;
     else if (k == "background_thal_truncated") *value_out = ctx->site_work.truncated;
+    else if (k == "coverage_thal_matches") *value_out = ctx->cov_thal.matches;
+    else if (k == "coverage_thal_slabs") *value_out = ctx->cov_thal.slabs;
+    else if (k == "coverage_thal_redone") *value_out = ctx->cov_thal.redone;
+    else if (k == "coverage_thal_list_us") *value_out = ctx->cov_thal.list_us;
+    else if (k == "coverage_thal_score_us") *value_out = ctx->cov_thal.score_us;
+    else if (k == "coverage_thal_fold_us") *value_out = ctx->cov_thal.fold_us;
     else if (k == "amplicon_keys_cap_log2") *value_out = ctx->opt.amplicon_keys_cap_log2;
     else if (k == "amplicon_keys") *value_out = ctx->amp_work.n_keys;
     else if (k == "amplicon_key_grows") *value_out = ctx->amp_work.grows;
@@ -810,6 +819,7 @@ void msspe_destroy(msspe_ctx *ctx)
         ctx->tubes.release();
         ctx->thin.release();
         ctx->mm_cov.release();
+        ctx->cov_thal.release();
         ctx->background.release();
         {
             auto &w = ctx->site_work;
@@ -2777,7 +2787,201 @@ int background_thal_pass(msspe_ctx *ctx, const uint64_t *d_packed, size_t total_
     return MSSPE_OK;
 }
 
+// msspe_segment_coverage_thal*: the matches of the mm rule through the work list of msspe_background_thal*, slab by
+// slab (groups [g0, g1) x primers [p0, p1)); a slab that overruns the list is split -- by groups while it has several,
+// then by primers -- and listed again, and only a slab that fitted is scored and folded.
+int coverage_thal_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t seq_len, const msspe_kmer_opt *opt,
+                       const msspe_mismatch_opt *mm, const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words,
+                       int n_rev, const msspe_chem *chem, int mode, float tm_threshold, uint8_t *held_out,
+                       double *t_best_out, uint32_t *primer_segments_out, uint32_t *primer_held_out,
+                       msspe_scored_match *matches, uint64_t capacity, uint64_t *count_out)
+{
+    if (!opt || !mm || !chem || !held_out || n_fwd < 0 || n_rev < 0 || (n_fwd && !fwd_words) ||
+        (n_rev && !rev_words) || (matches && !count_out))
+        return fail(ctx, MSSPE_ERR_ARG, "null argument");
+    if (mode != 1 && mode != 2) return fail(ctx, MSSPE_ERR_ARG, "coverage_thal: mode must be 1 (ANY) or 2 (END1)");
+    if (count_out) *count_out = 0;
+    const int k = opt->kmer_size;
+    if (k < 2 || k > 31) return fail(ctx, MSSPE_ERR_K, "coverage_thal: unsupported k (need 2 <= k <= 31)");
+    std::string err;
+    long P = 0;
+    int rc = MismatchCoverage::check(n_seq, seq_len, *opt, mm->max_mismatches, mm->exact_3p, fwd_words, n_fwd,
+                                     rev_words, n_rev, &P, err);
+    if (rc) return fail(ctx, rc, err);
+    if (opt->search_window_size - k >= (1 << kCovOffBits))   // a match's offset travels in kCovOffBits bits
+        return fail(ctx, MSSPE_ERR_ARG, "coverage_thal: the search window has more than 2^26 positions");
+    const int n = n_fwd + n_rev;
+    const long n_seg = P * n_seq;
+    std::fill(held_out, held_out + n_seg, (uint8_t)0);
+    if (t_best_out) std::fill(t_best_out, t_best_out + n_seg, 0.0);
+    if (primer_segments_out) std::fill(primer_segments_out, primer_segments_out + n, 0u);
+    if (primer_held_out) std::fill(primer_held_out, primer_held_out + n, 0u);
+    auto &ct = ctx->cov_thal;
+    ct.matches = ct.slabs = ct.redone = 0;
+    ct.list_us = ct.score_us = ct.fold_us = 0;
+    if (n == 0 || n_seg == 0) return MSSPE_OK;
+    const size_t cap = (size_t)1 << ctx->opt.site_list_cap_log2;
+    if ((uint64_t)n + cap >= (1ull << 31)) return fail(ctx, MSSPE_ERR_ARG, "coverage_thal: too many primers");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const bool end1 = mode == 2;
+    ChemEntry *ce = nullptr;
+    if ((rc = chem_entry(ctx, *chem, tm_threshold, &ce, end1 ? kCutEndT : kCutAnyT))) return rc;
+    const double cut = ce->c[0].g_cut;
+    if ((rc = ensure_workspace(ctx, (size_t)k * (size_t)k))) return rc;
+    if ((rc = ensure_overflow(ctx, (long)cap))) return rc;
+    if ((rc = ensure_site_work(ctx, cap, n, 0))) return rc;
+    if ((rc = ct.prepare(*opt, fwd_words, n_fwd, rev_words, n_rev, n_seg, ctx->stream, err))) return fail(ctx, rc, err);
+    auto &w = ctx->site_work;
+    CovMatch *list = reinterpret_cast<CovMatch *>(w.sites);
+    if (n_fwd)
+        HIP_TRY(ctx, hipMemcpyAsync(w.pool, fwd_words, sizeof(uint64_t) * (size_t)n_fwd, hipMemcpyHostToDevice,
+                                    ctx->stream));
+    if (n_rev)
+        HIP_TRY(ctx, hipMemcpyAsync(w.pool + n_fwd, rev_words, sizeof(uint64_t) * (size_t)n_rev,
+                                    hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->ovf_count, 0, 8 * sizeof(uint32_t), ctx->stream));
+    msspe_scored_match *d_out = nullptr;
+    uint64_t *d_count = nullptr;
+    if (matches && (rc = ct.out_list(capacity, &d_out, &d_count, ctx->stream, err))) return fail(ctx, rc, err);
+
+    const int S = MismatchCoverage::group_size(*opt);
+    const long n_groups = (n_seg + S - 1) / S, chunk = CoverageThal::max_slab_groups(n);
+    struct Slab { long g0, g1; int p0, p1; };
+    std::vector<Slab> todo;
+    for (long g1 = n_groups; g1 > 0; g1 -= std::min(g1, chunk))   // popped from the back: ascending groups
+        todo.push_back({g1 - std::min(g1, chunk), g1, 0, n});
+    bool scored = false;   // ev[2..4] of a scored slab wait to be read behind the next synchronisation
+    auto read_scored = [&]() {
+        float a = 0.f, b = 0.f;
+        if (scored && hipEventElapsedTime(&a, ct.ev[2], ct.ev[3]) == hipSuccess &&
+            hipEventElapsedTime(&b, ct.ev[3], ct.ev[4]) == hipSuccess) {
+            ct.score_us += (long long)(a * 1000.f);
+            ct.fold_us += (long long)(b * 1000.f);
+        }
+        scored = false;
+    };
+    while (!todo.empty()) {
+        const Slab s = todo.back();
+        todo.pop_back();
+        HIP_TRY(ctx, hipMemsetAsync(w.slab_count, 0, sizeof(uint64_t), ctx->stream));
+        HIP_TRY(ctx, hipEventRecord(ct.ev[0], ctx->stream));
+        if ((rc = ct.list_slab(view, n_seg, P, *opt, mm->max_mismatches, mm->exact_3p, s.g0, s.g1, s.p0, s.p1, list,
+                               cap, w.slab_count, ctx->stream, err)))
+            return fail(ctx, rc, err);
+        HIP_TRY(ctx, hipEventRecord(ct.ev[1], ctx->stream));
+        uint64_t count = 0;
+        HIP_TRY(ctx, hipMemcpyAsync(&count, w.slab_count, sizeof count, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        read_scored();
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, ct.ev[0], ct.ev[1]) == hipSuccess) ct.list_us += (long long)(ms * 1000.f);
+        if (count > cap) {
+            ++ct.redone;
+            const uint64_t groups = (uint64_t)(s.g1 - s.g0), prim = (uint64_t)(s.p1 - s.p0);
+            const uint64_t want = (2 * count + cap - 1) / cap;   // parts that would be half full at this density
+            if (groups > 1) {
+                const uint64_t parts = std::min(groups, want);
+                for (uint64_t q = 0; q < parts; ++q)
+                    todo.push_back({s.g0 + (long)(groups * q / parts), s.g0 + (long)(groups * (q + 1) / parts), s.p0,
+                                    s.p1});
+            } else if (prim > 1) {
+                const uint64_t parts = std::min(prim, want);
+                for (uint64_t q = 0; q < parts; ++q)
+                    todo.push_back({s.g0, s.g1, s.p0 + (int)(prim * q / parts), s.p0 + (int)(prim * (q + 1) / parts)});
+            } else {
+                return fail(ctx, MSSPE_ERR_CAPACITY,
+                            "coverage_thal: one segment group against one primer has " + std::to_string(count) +
+                                " matches, the work list holds " + std::to_string(cap) +
+                                " (msspe_set_option \"site_list_cap_log2\")");
+            }
+            continue;
+        }
+        if (!count) continue;
+        ++ct.slabs;
+        ct.matches += (long long)count;
+        HIP_TRY(ctx, hipEventRecord(ct.ev[2], ctx->stream));
+        // the hand-over lists may be shorter than the work list (a fixed list_cap_log2, a card short of memory)
+        const uint32_t step = (uint32_t)std::min<uint64_t>(count, (uint64_t)ctx->list_cap);
+        for (uint32_t c0 = 0; c0 < (uint32_t)count; c0 += step) {
+            const uint32_t cnt = std::min(step, (uint32_t)count - c0);
+            HIP_TRY(ctx, ct.oligos(view, P, *opt, list, c0, cnt, w.pool, w.list + c0, ctx->ovf_count, ctx->stream));
+            if ((rc = score_site_pairs(ctx, ce, end1, n, k, k, w.list + c0, cnt))) return rc;
+        }
+        HIP_TRY(ctx, hipEventRecord(ct.ev[3], ctx->stream));
+        if ((rc = ct.fold_slab(list, (uint32_t)count, w.dg, w.t, cut, *opt, s.g0, s.g1, s.p0, s.p1, d_out, capacity,
+                               d_count, ctx->stream, err)))
+            return fail(ctx, rc, err);
+        HIP_TRY(ctx, hipEventRecord(ct.ev[4], ctx->stream));
+        scored = true;
+    }
+    if ((rc = ct.finish(n_seg, held_out, t_best_out, primer_segments_out, primer_held_out, ctx->stream, err)))
+        return fail(ctx, rc, err);
+    read_scored();
+    if (matches) {
+        uint64_t count = 0;
+        HIP_TRY(ctx, hipMemcpy(&count, d_count, sizeof count, hipMemcpyDeviceToHost));
+        const uint64_t kept = std::min(count, capacity);
+        if (kept) HIP_TRY(ctx, hipMemcpy(matches, d_out, sizeof(msspe_scored_match) * kept, hipMemcpyDeviceToHost));
+        std::sort(matches, matches + kept, [](const msspe_scored_match &a, const msspe_scored_match &b) {
+            if (a.primer != b.primer) return a.primer < b.primer;
+            if (a.segment != b.segment) return a.segment < b.segment;
+            return a.offset < b.offset;
+        });
+        *count_out = count;
+        if (count > capacity) return fail(ctx, MSSPE_ERR_CAPACITY, "match list capacity too small");
+    }
+    return MSSPE_OK;
+}
+
 }  // namespace
+
+int msspe_segment_coverage_thal_dev(msspe_ctx *ctx, const uint8_t *d_seqs, int n_seq, size_t seq_len,
+                                    const msspe_kmer_opt *opt, const msspe_mismatch_opt *mm, const uint64_t *fwd_words,
+                                    int n_fwd, const uint64_t *rev_words, int n_rev, const msspe_chem *chem, int mode,
+                                    float tm_threshold, uint8_t *held_out, double *t_best_out,
+                                    uint32_t *primer_segments_out, uint32_t *primer_held_out,
+                                    msspe_scored_match *matches, uint64_t capacity, uint64_t *count_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!d_seqs) return fail(ctx, MSSPE_ERR_ARG, "null sequences");
+    return coverage_thal_view(ctx, SeqView{d_seqs, nullptr, seq_len}, n_seq, seq_len, opt, mm, fwd_words, n_fwd,
+                              rev_words, n_rev, chem, mode, tm_threshold, held_out, t_best_out, primer_segments_out,
+                              primer_held_out, matches, capacity, count_out);
+}
+
+int msspe_segment_coverage_thal_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
+                                           const msspe_kmer_opt *opt, const msspe_mismatch_opt *mm,
+                                           const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
+                                           const msspe_chem *chem, int mode, float tm_threshold, uint8_t *held_out,
+                                           double *t_best_out, uint32_t *primer_segments_out,
+                                           uint32_t *primer_held_out, msspe_scored_match *matches, uint64_t capacity,
+                                           uint64_t *count_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!d_packed) return fail(ctx, MSSPE_ERR_ARG, "null sequences");
+    return coverage_thal_view(ctx, SeqView{nullptr, d_packed, seq_len}, n_seq, seq_len, opt, mm, fwd_words, n_fwd,
+                              rev_words, n_rev, chem, mode, tm_threshold, held_out, t_best_out, primer_segments_out,
+                              primer_held_out, matches, capacity, count_out);
+}
+
+int msspe_segment_coverage_thal(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len,
+                                const msspe_kmer_opt *opt, const msspe_mismatch_opt *mm, const uint64_t *fwd_words,
+                                int n_fwd, const uint64_t *rev_words, int n_rev, const msspe_chem *chem, int mode,
+                                float tm_threshold, uint8_t *held_out, double *t_best_out,
+                                uint32_t *primer_segments_out, uint32_t *primer_held_out, msspe_scored_match *matches,
+                                uint64_t capacity, uint64_t *count_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!seqs || n_seq < 0) return fail(ctx, MSSPE_ERR_ARG, "null sequences");
+    void *d = nullptr;
+    int rc = msspe_device_put(ctx, seqs, (size_t)n_seq * seq_len, &d);
+    if (rc) return rc;
+    rc = msspe_segment_coverage_thal_dev(ctx, (const uint8_t *)d, n_seq, seq_len, opt, mm, fwd_words, n_fwd,
+                                         rev_words, n_rev, chem, mode, tm_threshold, held_out, t_best_out,
+                                         primer_segments_out, primer_held_out, matches, capacity, count_out);
+    (void)msspe_device_free(ctx, d);
+    return rc;
+}
 
 int msspe_background_thal_flank_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, size_t total_len, int k,
                                            const msspe_mismatch_opt *mm, const uint64_t *words, int n,

@@ -27,53 +27,20 @@
 #include <vector>
 
 #include "coverage_mm.hpp"
+#include "coverage_mm_core.hpp"
 
 namespace msspe {
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kItems = 8;                              // window positions per thread per round
-constexpr int kRound = kThreads * kItems;              // positions per round
-constexpr int kMaxSeg = 64;                            // segments per block (one bit each in the COUNTS words)
+using namespace mm_core;   // the lane mapping's constants, base_at, the plane words, load4, to_planes
+
 constexpr size_t kLdsBudget = 65536;                   // dynamic LDS per block: keeps two or more blocks per CU
-
-// base `col` of record `rec`: 0..3 (A C G T), or -1 for anything else (the validity rule of main.rs:167)
-__device__ __forceinline__ int base_at(const SeqView &v, size_t rec, size_t col)
-{
-    if (v.ascii) {
-        const uint8_t c = v.ascii[rec * v.seq_len + col];
-        return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : -1;
-    }
-    const size_t bw = (v.seq_len + 31) / 32, rw = bw + (v.seq_len + 63) / 64;
-    const uint64_t *row = v.packed + rec * rw;
-    if (!((row[bw + (col >> 6)] >> (col & 63)) & 1ull)) return -1;
-    return (int)((row[col >> 5] >> (2 * (col & 31))) & 3ull);
-}
-
-// A word as the comparison reads it: two 32-bit halves whose XORs, ORed together, give the mismatch mask.  32-bit
-// form: (w, rotr(w, 16)) -- the mask then holds the per-base bits in both halves; 64-bit form: (low plane, high plane).
-__device__ __forceinline__ uint2 rot_pair(uint32_t w) { return make_uint2(w, __builtin_amdgcn_alignbit(w, w, 16)); }
-__device__ __forceinline__ uint2 make_word(uint32_t lo, uint32_t hi, uint32_t) { return rot_pair(lo | (hi << 16)); }
-__device__ __forceinline__ uint2 make_word(uint32_t lo, uint32_t hi, uint2) { return make_uint2(lo, hi); }
-
-// one bit per differing base (twice over for the 32-bit form): an XOR and a three-input bit operation
-__device__ __forceinline__ uint32_t diff_mask(uint2 w, uint2 u) { return (w.x ^ u.x) | (w.y ^ u.y); }
-
-// four consecutive tile primers (16-byte aligned: i is a multiple of 4)
-__device__ __forceinline__ void load4(const uint32_t *tile, int i, uint2 (&u)[4])
-{
-    const uint4 v = *reinterpret_cast<const uint4 *>(tile + i);
-    u[0] = rot_pair(v.x); u[1] = rot_pair(v.y); u[2] = rot_pair(v.z); u[3] = rot_pair(v.w);
-}
-__device__ __forceinline__ void load4(const uint2 *tile, int i, uint2 (&u)[4])
-{
-    const uint4 a = *reinterpret_cast<const uint4 *>(tile + i), b = *reinterpret_cast<const uint4 *>(tile + i + 2);
-    u[0] = make_uint2(a.x, a.y); u[1] = make_uint2(a.z, a.w); u[2] = make_uint2(b.x, b.y); u[3] = make_uint2(b.z, b.w);
-}
 
 // best[seg] = smallest mismatch count (scaled: x2 for the 32-bit form) of a match, 255 when none; counts[primer] +=
 // segments it matched in.  lim: largest mask with the 3' bases equal; max_score: max_mismatches, scaled.
 // INCIDENCE (with COUNTS): `counts` is the incidence matrix, 64-bit words, n_pad = n_fwd + n_rev rounded up to 64.
+// k_coverage_mm_list (coverage_thal.hip) repeats this round body -- tile staging, window words, the 4 x 8 compare --
+// with an append where COUNTS ORs a bit: a change to either loop belongs in both.
 template <typename T, bool COUNTS, bool INCIDENCE = false>
 __global__ void __launch_bounds__(kThreads) k_coverage_mm(const SeqView seqs, int n_seg, int P, int seg_size,
                                                           int stride, int W, int k, int S, const T *fwd, int n_fwd,
@@ -175,35 +142,6 @@ __global__ void __launch_bounds__(kThreads) k_coverage_mm(const SeqView seqs, in
     }
 }
 
-template <typename T>
-void to_planes(const uint64_t *in, int n, std::vector<T> &out);
-
-template <>
-void to_planes<uint32_t>(const uint64_t *in, int n, std::vector<uint32_t> &out)
-{
-    for (int i = 0; i < n; ++i) {
-        uint32_t lo = 0, hi = 0;
-        for (int q = 0; q < 16; ++q) {
-            lo |= (uint32_t)((in[i] >> (2 * q)) & 1ull) << q;
-            hi |= (uint32_t)((in[i] >> (2 * q + 1)) & 1ull) << q;
-        }
-        out.push_back(lo | (hi << 16));
-    }
-}
-
-template <>
-void to_planes<uint2>(const uint64_t *in, int n, std::vector<uint2> &out)
-{
-    for (int i = 0; i < n; ++i) {
-        uint32_t lo = 0, hi = 0;
-        for (int q = 0; q < 32; ++q) {
-            lo |= (uint32_t)((in[i] >> (2 * q)) & 1ull) << q;
-            hi |= (uint32_t)((in[i] >> (2 * q + 1)) & 1ull) << q;
-        }
-        out.push_back(make_uint2(lo, hi));
-    }
-}
-
 #define MM_TRY(expr)                                                        \
     do {                                                                    \
         hipError_t e__ = (expr);                                            \
@@ -249,8 +187,7 @@ int launch(const SeqView &d_seqs, long n_seg, long P, const msspe_kmer_opt &opt,
     const int k = opt.kmer_size, W = opt.search_window_size;
     constexpr bool narrow = sizeof(T) == 4;
     const int scale = narrow ? 2 : 1;
-    const int s = k - E;   // 3' bases start at plane bit s
-    const uint32_t lim = narrow ? (s >= 16 ? 0xffffffffu : (1u << (16 + s)) - 1u) : (uint32_t)((1ull << s) - 1ull);
+    const uint32_t lim = exact_3p_limit<T>(k, E);
     words.clear();
     to_planes<T>(fwd, n_fwd, words);
     to_planes<T>(rev, n_rev, words);

@@ -64,6 +64,7 @@ int odm_parse_args(int argc, const char *const *argv, char *out, size_t cap)
           << "\ncheck_hairpin=" << a.check_hairpin << "\ndo_align=" << a.do_align
           << "\ntm_stddev=" << a.tm_stddev << "\ncover_on_device=" << a.cover_on_device << "\ntubes=" << a.tubes
           << "\ncoverage_mismatches=" << a.coverage_mismatches << "\ncoverage_3p_exact=" << a.coverage_3p_exact
+          << "\ncoverage_tm=" << a.coverage_tm_text << "\ncoverage_thal=" << a.coverage_thal
           << "\nthin_panel=" << a.thin_panel << "\nthin_mismatches=" << a.thin_mismatches
           << "\nthin_3p_exact=" << a.thin_3p_exact << "\nthin_min_gain=" << a.thin_min_gain
           << "\nbackground=" << a.background << "\nbackground_mismatches=" << a.background_mismatches
@@ -217,6 +218,24 @@ int odm_coverage_report_mm(const char *records_nl, const char *fwd_nl, const cha
         emit(e.what(), out, cap);
         return -2;   // no usable GPU (or an engine error): the text is the reason
     }
+}
+
+// The block od-msspe-hip --coverage-tm prints (coverage_thal_block), from results the caller has: records as
+// "name\tsequence" lines, held[record * P + partition] and the per-primer held counts.  Needs no device.
+int odm_coverage_thal_block(const char *records_nl, int segment, int stride, const uint8_t *held,
+                            const uint32_t *primer_held, int n_primers, int max_mismatches, int exact_3p, int mode,
+                            float tm_threshold, char *out, size_t cap)
+{
+    std::vector<SequenceRecord> recs;
+    size_t L = 0;
+    for (const auto &l : lines(records_nl)) {
+        const size_t t = l.find('\t');
+        recs.push_back({l.substr(0, t), l.substr(t + 1)});
+        L = std::max(L, recs.back().sequence.size());
+    }
+    const size_t P = L < (size_t)segment ? 0 : (L - (size_t)segment) / (size_t)stride + 1;
+    return emit(coverage_thal_block(recs, P, segment, stride, held, primer_held, (size_t)n_primers, max_mismatches,
+                                    exact_3p, mode, tm_threshold), out, cap);
 }
 
 float odm_tm_stat(const float *tm, int n, int population, float *std_out)

@@ -74,6 +74,8 @@ const OptSpec kOpts[] = {
     {"--tubes", "TUBES", OptSpec::Int, OFF(tubes)},
     {"--coverage-mismatches", "COVERAGE_MISMATCHES", OptSpec::Int, OFF(coverage_mismatches)},
     {"--coverage-3p-exact", "COVERAGE_3P_EXACT", OptSpec::Str, OFF(coverage_3p_exact_text)},
+    {"--coverage-tm", "COVERAGE_TM", OptSpec::Str, OFF(coverage_tm_text)},
+    {"--coverage-thal", "COVERAGE_THAL", OptSpec::Str, OFF(coverage_thal)},
     {"--thin-panel", "THIN_PANEL", OptSpec::Bool, OFF(thin_panel)},
     {"--thin-mismatches", "THIN_MISMATCHES", OptSpec::Int, OFF(thin_mismatches)},
     {"--thin-3p-exact", "THIN_3P_EXACT", OptSpec::Str, OFF(thin_3p_exact_text)},
@@ -137,7 +139,10 @@ std::string Args::usage()
          "--thin-panel true drops, after the cover or the tubes, every primer the coverage does not need: a greedy set\n"
          "cover of the segments matched within --thin-mismatches <M> (last --thin-3p-exact <E> bases exact), a pick\n"
          "covering at least --thin-min-gain <G> new segments. No segment is lost at G = 1; a segment's best mismatch\n"
-         "count may rise up to M. The primers of --existing-primers are kept. One device; not with --keep-all true.\n";
+         "count may rise up to M. The primers of --existing-primers are kept. One device; not with --keep-all true.\n"
+         "--coverage-tm <C> adds a report of the segments the final primers hold at C: every match within\n"
+         "--coverage-mismatches (last --coverage-3p-exact bases exact) is scored with thal (--coverage-thal any | end1)\n"
+         "against the strand the primer anneals to. One device.\n";
     return u;
 }
 
@@ -193,7 +198,22 @@ Args Args::parse(int argc, const char *const *argv)
     if (a.coverage_mismatches > a.kmer_size)
         throw UsageError("error: '--coverage-mismatches " + std::to_string(a.coverage_mismatches) +
                          "' is larger than '--kmer-size " + std::to_string(a.kmer_size) + "'");
-    if (a.coverage_mismatches > 0) {
+    if (!a.coverage_tm_text.empty()) {
+        char *end = nullptr;
+        a.coverage_tm = std::strtof(a.coverage_tm_text.c_str(), &end);
+        if (*end || std::isnan(a.coverage_tm))
+            throw UsageError("error: invalid value '" + a.coverage_tm_text + "' for '--coverage-tm'");
+        if (!a.devices.empty())
+            throw UsageError("error: '--coverage-tm' runs on one device and cannot be combined with '--devices'");
+        if (a.kmer_size < 2)
+            throw UsageError("error: '--coverage-tm' needs '--kmer-size' of at least 2");
+        a.coverage_scored = true;
+        if (a.coverage_thal.empty()) a.coverage_thal = "any";
+        if (a.coverage_thal != "any" && a.coverage_thal != "end1")
+            throw UsageError("error: invalid value '" + a.coverage_thal +
+                             "' for '--coverage-thal <...>'\n  [possible values: any, end1]");
+    }
+    if (a.coverage_mismatches > 0 || a.coverage_scored) {
         const std::string &v = a.coverage_3p_exact_text;
         char *end = nullptr;
         const long e = std::strtol(v.c_str(), &end, 10);
@@ -1162,6 +1182,73 @@ std::string coverage_report_mm(Engine &eng, const DeviceAlignment &aln, const st
     return out;
 }
 
+std::string coverage_thal_block(const std::vector<SequenceRecord> &records, size_t P, int segment_size,
+                                int overlap_size, const uint8_t *held, const uint32_t *primer_held, size_t n_primers,
+                                int max_mismatches, int exact_3p, int mode, float tm_threshold)
+{
+    size_t total = 0, n_held = 0, matched = 0;
+    std::map<std::string, std::pair<size_t, size_t>> seq_stats;   // name -> (held, total)
+    for (size_t ri = 0; ri < records.size(); ++ri) {
+        const size_t len = records[ri].sequence.size();
+        auto &se = seq_stats[records[ri].name];
+        for (size_t j = 0; (size_t)segment_size <= len && j * (size_t)overlap_size + (size_t)segment_size <= len; ++j) {
+            const uint8_t h = held[ri * P + j];
+            se.second += 1;
+            total += 1;
+            if (h) matched += 1;
+            if (h == 2) {
+                se.first += 1;
+                n_held += 1;
+            }
+        }
+    }
+    float min_cov = INFINITY, max_cov = -INFINITY;
+    size_t well = 0;
+    for (const auto &kv : seq_stats) {
+        const float c = (float)kv.second.first / (float)kv.second.second * 100.0f;
+        min_cov = std::fmin(min_cov, c);
+        max_cov = std::fmax(max_cov, c);
+        if (c >= 80.0f) ++well;
+    }
+    size_t idle = 0;
+    for (size_t i = 0; i < n_primers; ++i)
+        if (!primer_held[i]) ++idle;
+    std::string out = std::string("\nCoverage report (thal ") + (mode == 2 ? "END1" : "ANY") + ", t >= " +
+                      fmt("%.2f", (double)tm_threshold) + " C; matches within " + std::to_string(max_mismatches) +
+                      " mismatches, last " + std::to_string(exact_3p) + " bases exact):\n";
+    out += "  Segments:  " + std::to_string(n_held) + "/" + std::to_string(total) + " held (" +
+           fmt("%.1f", (double)(100.0f * (float)n_held / (float)total)) + "%), " + std::to_string(matched) + "/" +
+           std::to_string(total) + " matched\n";
+    out += "  Sequences: " + std::to_string(well) + "/" + std::to_string(seq_stats.size()) +
+           " at \xe2\x89\xa5" "80% held (min " + fmt("%.1f", (double)min_cov) + "%, max " +
+           fmt("%.1f", (double)max_cov) + "%)\n";
+    out += "  Primers:   " + std::to_string(idle) + " of " + std::to_string(n_primers) + " hold no segment\n";
+    return out;
+}
+
+std::string coverage_report_thal(Engine &eng, const DeviceAlignment &aln, const std::vector<KmerStat> &fwd,
+                                 const std::vector<KmerStat> &rev, const std::vector<SequenceRecord> &records,
+                                 int segment_size, int overlap_size, int window_size, int kmer_size, int max_mismatches,
+                                 int exact_3p, const msspe_chem &chem, int mode, float tm_threshold)
+{
+    const size_t L = aln.length();
+    const size_t P = L < (size_t)segment_size ? 0 : (L - (size_t)segment_size) / (size_t)overlap_size + 1;
+    std::vector<uint8_t> held(records.size() * P + 1, 0);
+    std::vector<uint32_t> primer_held(fwd.size() + rev.size() + 1, 0);
+    if (P) {
+        const auto wf = pack_words(eng, fwd, kmer_size), wr = pack_words(eng, rev, kmer_size);
+        const msspe_kmer_opt opt{segment_size, overlap_size, window_size, kmer_size, 0, 0};
+        const msspe_mismatch_opt mm{max_mismatches, exact_3p};
+        const int rc = msspe_segment_coverage_thal_packed_dev(eng.ctx(), aln.device(), aln.rows(), L, &opt, &mm,
+                                                              wf.data(), (int)wf.size(), wr.data(), (int)wr.size(),
+                                                              &chem, mode, tm_threshold, held.data(), nullptr, nullptr,
+                                                              primer_held.data(), nullptr, 0, nullptr);
+        if (rc) eng.fail(rc);
+    }
+    return coverage_thal_block(records, P, segment_size, overlap_size, held.data(), primer_held.data(),
+                               fwd.size() + rev.size(), max_mismatches, exact_3p, mode, tm_threshold);
+}
+
 std::string thin_panel_on_device(Engine &eng, const DeviceAlignment &aln, std::vector<KmerStat> &fwd,
                                  std::vector<KmerStat> &rev, const std::vector<std::string> &panel_f,
                                  const std::vector<std::string> &panel_r, int segment_size, int overlap_size,
@@ -1673,6 +1760,11 @@ int run(const Args &args, std::string &stdout_text)
         stdout_text += coverage_report_mm(eng, aln, rep_f, rep_r, records, args.window_size, args.overlap_size,
                                           args.search_windows_size, args.kmer_size, args.coverage_mismatches,
                                           args.coverage_3p_exact);
+    if (args.coverage_scored)   // the same primers again, every match within the prefilter scored with thal
+        stdout_text += coverage_report_thal(eng, aln, rep_f, rep_r, records, args.window_size, args.overlap_size,
+                                            args.search_windows_size, args.kmer_size, args.coverage_mismatches,
+                                            args.coverage_3p_exact, ntthal_chem(opts),
+                                            args.coverage_thal == "end1" ? 2 : 1, args.coverage_tm);
     stdout_text += thin_text;
     if (args.tubes > 0) stdout_text += tubes_report(good_f, good_r, tubes, args.tubes);
     if (background) {   // the CSV's primers by their CSV names, the panel's by the numbers the CSV continues from

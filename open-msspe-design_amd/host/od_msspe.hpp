@@ -63,6 +63,14 @@ struct Args {
     int coverage_mismatches = 0;
     std::string coverage_3p_exact_text = "3";   // read (as an integer) only when coverage_mismatches > 0
     int coverage_3p_exact = 3;
+    // --coverage-tm C: after the coverage report(s), the segments the final primers hold at C -- every match within
+    // coverage_mismatches (its last coverage_3p_exact bases exact; both are read with this switch too) is scored with
+    // thal against the strand the primer anneals to (msspe_segment_coverage_thal, --coverage-thal any | end1, the
+    // cross-dimer screen's chemistry); a match is stable iff round_fixed_f32(max(0, t), 2) >= C.  One device.
+    // Empty text: not given, nothing changes (and --coverage-thal is not read).
+    std::string coverage_tm_text, coverage_thal;
+    float coverage_tm = 0.0f;
+    bool coverage_scored = false;
     // --thin-panel true: after the cover / tube step the primers are thinned to those their coverage needs -- a greedy
     // set cover over "primer p has a match in segment s" within thin_mismatches mismatches, the last thin_3p_exact
     // bases exact (msspe_panel_thin; the panel of --existing-primers is forced); a pick must cover thin_min_gain new
@@ -262,6 +270,17 @@ std::string coverage_report(Engine &eng, const DeviceAlignment &aln, const std::
 std::string coverage_report(Engine &eng, const std::vector<KmerStat> &fwd, const std::vector<KmerStat> &rev,
                             const std::vector<SequenceRecord> &records, int segment_size,
                             int overlap_size, int window_size, int kmer_size);
+// The thal-scored block (engine extension, --coverage-tm): "Coverage report (thal NAME, t >= T C; matches within M
+// mismatches, last E bases exact):", the segments held / matched, the sequences at >= 80 % held and the primers that
+// hold no segment.  coverage_thal_block is the text alone, from held[record * P + partition] (0 / 1 / 2) and the
+// per-primer held counts (msspe_segment_coverage_thal); coverage_report_thal makes both on the device first.
+std::string coverage_thal_block(const std::vector<SequenceRecord> &records, size_t P, int segment_size,
+                                int overlap_size, const uint8_t *held, const uint32_t *primer_held, size_t n_primers,
+                                int max_mismatches, int exact_3p, int mode, float tm_threshold);
+std::string coverage_report_thal(Engine &eng, const DeviceAlignment &aln, const std::vector<KmerStat> &fwd,
+                                 const std::vector<KmerStat> &rev, const std::vector<SequenceRecord> &records,
+                                 int segment_size, int overlap_size, int window_size, int kmer_size, int max_mismatches,
+                                 int exact_3p, const msspe_chem &chem, int mode, float tm_threshold);
 // The mismatch-tolerant block (engine extension): "Coverage report (up to N mismatches, last E bases exact):", the
 // exact report's three lines with hit = best <= N, and the segments by best mismatch count (msspe_segment_coverage_mm)
 std::string coverage_report_mm(Engine &eng, const DeviceAlignment &aln, const std::vector<KmerStat> &fwd,

@@ -33,6 +33,7 @@ EXPORTS = [
     "msspe_kmer_candidates_both_seeded_packed_dev",
     "msspe_segment_coverage_packed_dev",
     "msspe_segment_coverage_mm", "msspe_segment_coverage_mm_dev", "msspe_segment_coverage_mm_packed_dev",
+    "msspe_segment_coverage_thal", "msspe_segment_coverage_thal_dev", "msspe_segment_coverage_thal_packed_dev",
     "msspe_panel_thin", "msspe_panel_thin_dev", "msspe_panel_thin_packed_dev",
     "msspe_device_put_stream_packed", "msspe_background_sites_packed_dev", "msspe_background_sites",
     "msspe_background_thal_packed_dev", "msspe_background_thal",
@@ -81,6 +82,12 @@ SITE_DTYPE = np.dtype([("primer", np.uint32), ("pos", np.uint32), ("mismatches",
 SCORED_SITE_DTYPE = np.dtype([("primer", np.uint32), ("pos", np.uint32), ("mismatches", np.uint16),
                               ("strand", np.uint16), ("stable", np.uint32), ("dg", np.float64), ("t", np.float64)])
 THAL_MODES = {"any": 1, "end1": 2}
+
+# msspe_scored_match: one match of a primer in a target segment with its thal score (msspe_segment_coverage_thal*)
+SCORED_MATCH_DTYPE = np.dtype([("primer", np.uint32), ("segment", np.uint32), ("offset", np.uint32),
+                               ("mismatches", np.uint16), ("stable", np.uint16), ("dg", np.float64),
+                               ("t", np.float64)])
+assert SCORED_MATCH_DTYPE.itemsize == 32
 
 # msspe_thal_detail: the full thal record of one pair (msspe_thal_detail_pairs), what ntthal prints per input line
 THAL_DETAIL_DTYPE = np.dtype([("dS", np.float64), ("dH", np.float64), ("dG", np.float64), ("t", np.float64),
@@ -232,6 +239,12 @@ def load_library() -> C.CDLL:
                                             vp, C.c_int, vp, C.c_int, vp, vp]
     L.msspe_segment_coverage_mm_dev.argtypes = L.msspe_segment_coverage_mm.argtypes
     L.msspe_segment_coverage_mm_packed_dev.argtypes = L.msspe_segment_coverage_mm.argtypes
+    L.msspe_segment_coverage_thal.argtypes = [vp, vp, C.c_int, C.c_size_t, C.POINTER(KmerOpt),
+                                              C.POINTER(MismatchOpt), vp, C.c_int, vp, C.c_int, C.POINTER(Chem),
+                                              C.c_int, C.c_float, vp, vp, vp, vp, vp, C.c_uint64,
+                                              C.POINTER(C.c_uint64)]
+    L.msspe_segment_coverage_thal_dev.argtypes = L.msspe_segment_coverage_thal.argtypes
+    L.msspe_segment_coverage_thal_packed_dev.argtypes = L.msspe_segment_coverage_thal.argtypes
     L.msspe_panel_thin.argtypes = [vp, vp, C.c_int, C.c_size_t, C.POINTER(KmerOpt), C.POINTER(MismatchOpt),
                                    C.POINTER(ThinOpt), u64p, C.c_int, u64p, C.c_int, vp, vp, vp, vp,
                                    C.POINTER(C.c_int), vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
@@ -768,6 +781,80 @@ class Engine:
         self._check(fn(self.ptr, seqs_arg, n_seq, seq_len, C.byref(opt), C.byref(mm), f.ctypes.data, len(f),
                        r.ctypes.data, len(r), best.ctypes.data, counts.ctypes.data if per_primer else None))
         return (best, counts) if per_primer else best
+
+    # ---- segment coverage scored with thal (engine extension; msspe_segment_coverage_thal*) -----------------------
+    def segment_coverage_thal(self, genomes, opt: KmerOpt, fwd, rev, max_mismatches: int, exact_3p: int, chem: Chem,
+                              mode, tm_threshold: float, *, matches: bool = False, capacity: int | None = None,
+                              packed: str = "host"):
+        """The matches of segment_coverage_mm, each scored with thal against the strand the primer anneals to
+        (msspe_segment_coverage_thal*); mode "any" (1) or "end1" (2); a match is stable iff
+        round_fixed_f32(max(0, t), 2) >= tm_threshold.  genomes: uint8 (n_seq, L) host array -- packed "host" hands
+        it over as it is, "dev" and "packed" upload it first (as bytes / as packed rows) and call the device forms;
+        or a resident alignment as (device address, n_seq, seq_len) with "dev" or "packed".  fwd / rev: primer strings
+        (rev as the CSV writes it) or packed words.  Returns a dict: held uint8 (n_seq, P) (0 no match, 1 matches but
+        none stable, 2 held), t_best float64 (n_seq, P), primer_segments and primer_held uint32 (forward primers
+        first); with matches=True also "matches", a SCORED_MATCH_DTYPE array sorted by (primer, segment, offset),
+        and "count".  capacity: the list's size (default: sized by a first call without a list); one below the
+        number of matches raises MsspeError (MSSPE_ERR_CAPACITY) carrying .count, .result and the truncated
+        .matches."""
+        fn = {"host": self.L.msspe_segment_coverage_thal, "dev": self.L.msspe_segment_coverage_thal_dev,
+              "packed": self.L.msspe_segment_coverage_thal_packed_dev}[packed]
+        owned = None
+        if isinstance(genomes, tuple):
+            if packed == "host":
+                raise ValueError("a resident alignment needs packed='dev' or 'packed'")
+            handle, n_seq, seq_len = genomes
+            seqs_arg = C.c_void_p(handle)
+        else:
+            a = np.ascontiguousarray(genomes, dtype=np.uint8)
+            n_seq, seq_len = a.shape
+            if packed == "host":
+                seqs_arg = a.ctypes.data
+            elif packed == "packed":
+                owned = self.put_rows_packed(a)
+                seqs_arg = C.c_void_p(owned)
+            else:
+                dev = C.c_void_p()
+                self._check(self.L.msspe_device_put(self.ptr, a.ctypes.data, a.size, C.byref(dev)))
+                owned = int(dev.value)
+                seqs_arg = C.c_void_p(owned)
+        try:
+            P = 0 if seq_len < opt.segment_size else (seq_len - opt.segment_size) // opt.overlap_size + 1
+            f, r = _words(fwd), _words(rev)
+            n = len(f) + len(r)
+            mm = MismatchOpt(max_mismatches, exact_3p)
+
+            def call(recs, cap):
+                out = {"held": np.zeros((n_seq, P), dtype=np.uint8), "t_best": np.zeros((n_seq, P), dtype=np.float64),
+                       "primer_segments": np.zeros(n, dtype=np.uint32), "primer_held": np.zeros(n, dtype=np.uint32)}
+                count = C.c_uint64(0)
+                rc = fn(self.ptr, seqs_arg, n_seq, seq_len, C.byref(opt), C.byref(mm), f.ctypes.data, len(f),
+                        r.ctypes.data, len(r), C.byref(chem), self._thal_mode(mode), tm_threshold,
+                        out["held"].ctypes.data, out["t_best"].ctypes.data, out["primer_segments"].ctypes.data,
+                        out["primer_held"].ctypes.data, recs.ctypes.data if recs is not None else None, cap,
+                        C.byref(count))
+                return rc, out, int(count.value)
+
+            if not matches:
+                rc, out, _ = call(None, 0)
+                self._check(rc)
+                return out
+            if capacity is None:   # the number of matches is the sum of no per-primer output: ask for it
+                probe = np.zeros(1, dtype=SCORED_MATCH_DTYPE)
+                rc, out, capacity = call(probe, 0)
+                if rc not in (0, 5):
+                    self._check(rc)
+            recs = np.zeros(max(capacity, 1), dtype=SCORED_MATCH_DTYPE)
+            rc, out, count = call(recs, capacity)
+            if rc:
+                err = MsspeError(rc, self.L.msspe_last_error(self.ptr).decode())
+                err.count, err.result, err.matches = count, out, recs[:min(count, capacity)]
+                raise err
+            out["matches"], out["count"] = recs[:count], count
+            return out
+        finally:
+            if owned is not None:
+                self.device_free(owned)
 
     # ---- a panel thinned to the primers its coverage needs (engine extension; msspe_panel_thin*) -----------------
     def panel_thin(self, genomes, opt: KmerOpt, fwd, rev, max_mismatches: int, exact_3p: int, min_gain: int = 1,
