@@ -121,6 +121,19 @@ const char *msspe_version(void);
  *                                 0 gfx950 returns there for "not available" (1; it also needs the per-engine probe to
  *                                 pass), or the general integer kernel, which never leaves its allocation (0: for
  *                                 debugger / trap-handler sessions that raise MEM_VIOL on such reads)
+ *   "pair_bound"     "auto" | "0" | "1"  the BOUND first stage.  A screen that asks for decisions only (counts, bitmap:
+ *                                 no dG plane, no Tm plane, no edge list) of oligos of up to 13 bases with a cut <= 0,
+ *                                 where the row-specialised first stage would run, may run a cheaper instance of it
+ *                                 first: a lower bound of every dG thal() could report for the pair (the minimum over
+ *                                 all chains of stacked pairs and loops, at the chemistry's temperature, in integers
+ *                                 rounded down).  A pair whose bound is more than 1 cal/mol above the cut cannot
+ *                                 conflict and is finished; every other pair goes to hand-over list 0 and is answered
+ *                                 by the exact stages, so every decision is the one the exact kernels make.
+ *                                 "1": wherever it applies; "0": never; "auto" (default): while the share of pairs it
+ *                                 cannot cull stays below half the break-even share -- measured once per chemistry,
+ *                                 threshold and oligo length by a probe launch over at most 2^20 pairs of the first
+ *                                 such call's block (one extra host round trip, none when the stream is being captured:
+ *                                 the exact kernel then runs)
  *   "stage_a_graph"  "0" | "1"    hipGraph replay of stage A's greedy loop (1)
  *   "stage_a_candidates" "0" | "1"  greedy loop over the list of words near the maximum (1), or over all the
  *                                 words on every iteration (0); the winners are the same */
@@ -253,6 +266,14 @@ int msspe_cross_dimer_edges_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, i
                                 uint64_t *d_count);
 int msspe_cross_dimer_edges(msspe_ctx *ctx, const char *pool_ascii, int n, int k, const msspe_chem *chem,
                             float dg_threshold, msspe_edge *edges, uint64_t capacity, uint64_t *count_out);
+/* Diagnostic (tests and debugging; no screen reads it): what the bound first stage (option "pair_bound") computes
+ * for every ordered pair of the block, as a double in cal/mol in the caller's plane d_bound[(row1-row0) * (col1-col0)]
+ * (layout of msspe_cross_dimer_dev's dG plane): a value <= every dG thal() can report for the pair + 1 cal/mol; +inf
+ * where the pair has no complementary base pair at all; -inf for a pair that stage does not bound but hands on as it is
+ * (more stored cells than its table holds, both oligos self-complementary).  Asynchronous on the context's stream.
+ * MSSPE_ERR_ARG where the stage does not apply: k > 13, a threshold whose cut is above 0, tables it cannot hold. */
+int msspe_cross_dimer_bound_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const msspe_chem *chem,
+                                float dg_threshold, int row0, int row1, int col0, int col1, double *d_bound);
 
 /* One pool screened against another (engine extension: the reference screens one pool of one --kmer-size,
  * od-msspe/src/delta_g.rs:61-81; ntthal itself takes any two oligos).  Pool A: n_a oligos of k_a bases, oligo 1
@@ -428,6 +449,13 @@ int msspe_host_pair_tables(const char *params_path, const msspe_chem *chem, floa
  * non-integral enthalpy give MSSPE_OK with out[0] = 0 (every dimer call would be refused);
  * MSSPE_ERR_TABLES only when the files cannot be loaded. */
 int msspe_host_table_routes(const char *params_path, const msspe_chem *chem, int32_t out[8]);
+/* Host only: the bound first stage's tables (option "pair_bound"; csrc/fast_tables.hpp BoundTables) in the layout
+ * of msspe_host_pair_tables' int_g (2604 entries) and int_T (239 * 64): every term's H - temp_k * S, a stacked pair
+ * and a loop with - temp_k * salt on top, in units of 1 / info[3] cal/mol rounded down; entries >= info[6] are "not
+ * available".  info = usable, initiation term, cut (a pair is culled iff initiation + the minimum over its chains
+ * is above it), units per cal/mol, margin in units, bound of every reachable |sum|, the void marker, longest oligo. */
+int msspe_host_bound_tables(const char *params_path, const msspe_chem *chem, float dg_threshold, int32_t *bound_g,
+                            int32_t *bound_T, int32_t info[8]);
 /* The same for the long-oligo kernel (csrc/split_tables.hpp): S / H / g hold info[2] entries, L 1024,
  * X info[3]; info = usable, longest oligo covered, entry count, X count. */
 int msspe_host_split_tables(const char *params_path, const msspe_chem *chem, double *S, int32_t *H,

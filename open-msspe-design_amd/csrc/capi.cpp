@@ -51,6 +51,11 @@ struct ChemEntry {
     IntTables *d_it = nullptr;    // integer image for the exact-integer kernel
     bool int_ok = false;
     bool row_ok = false;          // ... and the row-specialised kernel (thal_pairs_row.hip)
+    BoundTables *d_bt = nullptr;  // the bound first stage's tables (thal_pairs_row.hip k_pairs_bound)
+    bool bound_ok = false;        // ... usable: row_ok, g_cut <= 0, values in range (build_bound_tables)
+    // option pair_bound = auto: the share of pairs the bound stage could not cull, per oligo length, as the first
+    // call's probe launch measured it (this entry keys on chemistry AND threshold); < 0: no record yet
+    float bound_share[16] = {-1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f};
     SplitTables *d_st = nullptr;  // long oligos (thal_pairs_split.hip)
     int split_max_k = 0;          // 0: not usable
     int wave_max_k = 0;           // f64 one-wave-per-pair kernel (thal_pairs_wave.hip)
@@ -68,6 +73,13 @@ constexpr long kListCapMax = 1L << 30;       // 8 GB per list (two of them, 6 % 
                                              // 2^28 -> 2^30 is 17 -> 5 flushes per 65,536^2 screen and 1.5 % of its time
 constexpr size_t kGenericLanes = 1u << 16;   // lanes of the generic kernels' workspace
 constexpr int kOvfTotals = 2 + 7;            // msspe_ctx::d_ovf_total: two flags / totals, then one total per hand-over list
+constexpr int kReasonWords = 9 + 1024 + 8 + 2;   // msspe_ctx::d_reasons (int_core.hpp IntArgs::reasons); the last two: pairs
+constexpr int kBoundSurvivors = kReasonWords - 2;   // the bound first stage handed on, and its probe launch's count
+constexpr long kBoundProbePairs = 1L << 20;  // pair_bound = auto: pairs of the probe launch behind a new record
+// pair_bound = auto runs the bound stage while the recorded survivor share is at most this: HALF the break-even share
+//   (ns per pair of the exact row kernel - ns per pair of the bound kernel) / ns per handed-on pair of the list chain
+// = (0.2856 - 0.1521) / 1.72 = 7.8 % (DESIGN.md 4.0 holds the three prices and the session they were measured in)
+constexpr float kBoundShareMax = 0.039f;
 
 }  // namespace
 
@@ -81,6 +93,8 @@ struct EngineOptions {
     int list_cap_log2 = 0;    // 0: sized by the call; 20..30: fixed (forces flushes mid-screen)
     int split_lanes = 0;      // 0: by oligo length; 2 / 4 / 8
     bool row_oob = true;      // the row-specialised first stage (it reads LDS beyond its allocation: thal_pairs_row.hip) may run
+    int pair_bound = 2;       // decision-only screens of up to 13 bases, cut <= 0: the bound first stage (k_pairs_bound) in front of
+                              // the list stages -- 0 never | 1 wherever it applies | 2 auto: while few pairs survive it (kBoundShareMax)
     bool split_list = true;   // short oligos: tables too large for the integer list stage go to the split kernel's list mode
     bool short_chain = true;  // screens of up to 2^23 pairs: integer list stage -> one wave per pair (no register-table stages between)
     int self_lane_from = 81920;   // oligos per call from which SELF_ANY / SELF_END run one lane per oligo (msspe_oligo_stats_dev)
@@ -270,6 +284,14 @@ int chem_entry(msspe_ctx *ctx, const msspe_chem &chem, float threshold, ChemEntr
         HIP_TRY(ctx, hipMemcpy(e.d_it, it.get(), sizeof(IntTables), hipMemcpyHostToDevice));
         HIP_TRY(ctx, hipMalloc((void **)&e.d_st, sizeof(SplitTables)));
         HIP_TRY(ctx, hipMemcpy(e.d_st, st.get(), sizeof(SplitTables), hipMemcpyHostToDevice));
+        if (kind == kCutAnyDg && r.row_ok) {
+            auto bt = std::make_unique<BoundTables>();
+            e.bound_ok = build_bound_tables(*ft, e.c[0], pairs_bound_max_k(), *bt);
+            if (e.bound_ok) {
+                HIP_TRY(ctx, hipMalloc((void **)&e.d_bt, sizeof(BoundTables)));
+                HIP_TRY(ctx, hipMemcpy(e.d_bt, bt.get(), sizeof(BoundTables), hipMemcpyHostToDevice));
+            }
+        }
     }
     if (kind != kCutAnyDg)
         for (auto &c : e.c) c.g_cut = t_cut(threshold);
@@ -307,8 +329,8 @@ int ensure_overflow(msspe_ctx *ctx, long total_pairs)
         HIP_TRY(ctx, hipMemsetAsync(ctx->d_ovf_total, 0, kOvfTotals * sizeof(uint64_t), ctx->stream));
     }
     if (!ctx->d_reasons) {
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_reasons, (9 + 1024 + 8) * sizeof(unsigned long long)));
-        HIP_TRY(ctx, hipMemsetAsync(ctx->d_reasons, 0, (9 + 1024 + 8) * sizeof(unsigned long long), ctx->stream));
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_reasons, kReasonWords * sizeof(unsigned long long)));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->d_reasons, 0, kReasonWords * sizeof(unsigned long long), ctx->stream));
     }
     long want = kListCapMin;
     while (want < total_pairs && want < kListCapMax && want < ctx->list_cap_ceiling) want <<= 1;
@@ -719,6 +741,10 @@ int msspe_set_option(msspe_ctx *ctx, const char *key, const char *value)
     } else if (k == "row_oob") {
         if (!is_num || num < 0 || num > 1) return bad();
         ctx->opt.row_oob = num != 0;
+    } else if (k == "pair_bound") {
+        if (v == "auto") ctx->opt.pair_bound = 2;
+        else if (is_num && (num == 0 || num == 1)) ctx->opt.pair_bound = (int)num;
+        else return bad();
     } else if (k == "stage_a_graph") {
         if (!is_num || num < 0 || num > 1) return bad();
         ctx->kmer.set_use_graph(num != 0);
@@ -782,6 +808,18 @@ int msspe_get_info(msspe_ctx *ctx, const char *key, long long *value_out)
     else if (k == "panel_thin_incidence_us") *value_out = ctx->thin.phase_us()[0];
     else if (k == "panel_thin_gain0_us") *value_out = ctx->thin.phase_us()[1];
     else if (k == "panel_thin_rounds_us") *value_out = ctx->thin.phase_us()[2];
+    else if (k == "pair_bound") *value_out = ctx->opt.pair_bound;
+    else if (k == "bound_survivors") {
+        // pairs the bound first stage handed on since the last read of this key; reading resets it
+        *value_out = 0;
+        if (!ctx->d_reasons) return MSSPE_OK;
+        uint64_t v = 0;
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        HIP_TRY(ctx, hipMemcpy(&v, ctx->d_reasons + kBoundSurvivors, sizeof v, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->d_reasons + kBoundSurvivors, 0, sizeof v, ctx->stream));
+        *value_out = (long long)v;
+    }
     else if (k.size() == 16 && k.compare(0, 15, "hand_over_list_") == 0 && k[15] >= '0' && k[15] <= '6') {
         // pairs that entered list q since the last read of this key; reading resets it
         *value_out = 0;
@@ -845,6 +883,7 @@ void msspe_destroy(msspe_ctx *ctx)
             if (e.d_pt) (void)hipFree(e.d_pt);
             if (e.d_ft) (void)hipFree(e.d_ft);
             if (e.d_it) (void)hipFree(e.d_it);
+            if (e.d_bt) (void)hipFree(e.d_bt);
             if (e.d_st) (void)hipFree(e.d_st);
         }
         if (ctx->wsS) (void)hipFree(ctx->wsS);
@@ -1007,6 +1046,41 @@ static int run_chain(msspe_ctx *ctx, ChemEntry *ce, const ChainRoute &route, con
         return ListChain(ctx, ce, end1, ctx->ovf_list, kListCap).run(route.behind, a, g, true);
     };
     HIP_TRY(ctx, hipMemsetAsync(ctx->ovf_count, 0, 8 * sizeof(uint32_t), ctx->stream));
+    // The row-specialised first stage, and in front of the list stages instead of it the BOUND instance where the call
+    // asks for decisions only (no plane, no edge values): it proves most pairs free of a conflict at about half the
+    // price and hands the rest to list 0 (thal_pairs_row.hip k_pairs_bound; option pair_bound).
+    const bool row_stage = !wave_matrix && !split && int_stage && ce->row_ok && k <= pairs_row_max_k() && ctx->opt.pair_kernel != 2 &&
+                           (k > pairs_row_oob_max_k() || (ctx->lds_reads_zero && ctx->opt.row_oob));
+    bool bound_stage = row_stage && !end1 && k <= pairs_bound_max_k() && ce->bound_ok && ctx->opt.pair_bound != 0 &&
+                       !b.sinks.dg && !b.sinks.tm && !b.sinks.edge_count;
+    if (bound_stage && ctx->opt.pair_bound == 2) {
+        if (ce->bound_share[k] < 0.f) {
+            // no record for this chemistry, threshold and length: one probe launch over the head of the call's own block
+            // (it counts its survivors and writes nothing else) and one counter read -- the only host round trip
+            // the bound adds, once per record.  A stream that is being captured cannot be waited for: the exact
+            // kernel, and no record.
+            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+            if (hipStreamIsCapturing(ctx->stream, &cs) != hipSuccess) (void)hipGetLastError();
+            if (cs == hipStreamCaptureStatusNone) {
+                PairKernelArgs a = pair_args(ctx, ce, b);
+                a.cols_sorted = ctx->d_sorted;
+                a.perm = ctx->d_perm;
+                a.ncols_sorted = ncols;
+                a.col0 = 0;
+                a.col1 = (int)std::min<long>(ncols, kBoundProbePairs);
+                a.row0 = row0;
+                a.row1 = (int)std::min<long>(row1, (long)row0 + std::max(1L, kBoundProbePairs / (a.col1 - a.col0)));
+                unsigned long long *probe = ctx->d_reasons + kBoundSurvivors + 1;
+                HIP_TRY(ctx, hipMemsetAsync(probe, 0, sizeof *probe, ctx->stream));
+                HIP_TRY(ctx, launch_pairs_bound(a, ce->d_it, ce->d_bt, probe, nullptr, ctx->n_cu, ctx->stream));
+                unsigned long long n_surv = 0;
+                HIP_TRY(ctx, hipMemcpyAsync(&n_surv, probe, sizeof n_surv, hipMemcpyDeviceToHost, ctx->stream));
+                HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+                ce->bound_share[k] = (float)((double)n_surv / ((double)(a.row1 - a.row0) * (double)(a.col1 - a.col0)));
+            }
+        }
+        bound_stage = ce->bound_share[k] >= 0.f && ce->bound_share[k] <= kBoundShareMax;
+    }
     long pending = 0;   // worst-case entries the list may hold
     for (int r = row0; r < row1; r += (int)rows_per_chunk) {
         const int r_end = (int)std::min<long>(row1, (long)r + rows_per_chunk);
@@ -1042,9 +1116,10 @@ static int run_chain(msspe_ctx *ctx, ChemEntry *ce, const ChainRoute &route, con
                 a.col1 = col0 + (int)q_end;
                 HIP_TRY(ctx, launch_pairs_wave(a, ce->d_st, nullptr, nullptr, ctx->stream, end1));
             } else if (split) HIP_TRY(ctx, launch_pairs_split(a, ce->d_st, ctx->d_reasons, ctx->opt.split_lanes, ctx->stream));
-            else if (int_stage && ce->row_ok && k <= pairs_row_max_k() && ctx->opt.pair_kernel != 2 &&
-                     (k > pairs_row_oob_max_k() || (ctx->lds_reads_zero && ctx->opt.row_oob)))
-                HIP_TRY(ctx, launch_pairs_row(a, ce->d_it, ctx->d_reasons, ctx->n_cu, ctx->stream));
+            else if (bound_stage)
+                HIP_TRY(ctx, launch_pairs_bound(a, ce->d_it, ce->d_bt, ctx->d_reasons + kBoundSurvivors, nullptr, ctx->n_cu,
+                                                ctx->stream));
+            else if (row_stage) HIP_TRY(ctx, launch_pairs_row(a, ce->d_it, ctx->d_reasons, ctx->n_cu, ctx->stream));
             else if (int_stage) HIP_TRY(ctx, launch_pairs_int(a, ce->d_it, ctx->d_reasons, ctx->n_cu, ctx->stream));
             else HIP_TRY(ctx, launch_pairs_fast(a, ctx->stream, end1));
             if (ctx->prof_on)
@@ -1189,6 +1264,34 @@ int msspe_cross_dimer_edges_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, i
     return cross_dimer_edges_dev(ctx, screen_block(d_pool, n, k, k, row0, row1, col0, col1,
                                                    edge_sinks(d_row_conflicts, d_edges, d_count, capacity)),
                                  chem, dg_threshold, false);
+}
+
+// Diagnostic: the bound first stage's value for every pair of the block (tests and debugging; no screen reads it).
+int msspe_cross_dimer_bound_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const msspe_chem *chem,
+                                float dg_threshold, int row0, int row1, int col0, int col1, double *d_bound)
+{
+    const ScreenBlock b = screen_block(d_pool, n, k, k, row0, row1, col0, col1, plane_sinks(nullptr, nullptr, nullptr, nullptr));
+    ChemEntry *ce = nullptr;
+    const int rc = open_screen(ctx, b, chem, dg_threshold, kCutAnyDg, &ce);
+    if (rc || !ce) return rc;
+    if (!d_bound) return fail(ctx, MSSPE_ERR_ARG, "msspe_cross_dimer_bound_dev: null output plane");
+    if (k > pairs_bound_max_k() || !ce->bound_ok || !ctx->lds_reads_zero || !ctx->opt.row_oob)
+        return fail(ctx, MSSPE_ERR_ARG, "msspe_cross_dimer_bound_dev: the bound stage does not apply (more than 13 bases, a cut "
+                                        "above 0, tables outside its range, or option row_oob = 0)");
+    const int ncols = b.sinks.ncols;
+    int rc2 = 0;
+    if ((rc2 = ensure_overflow(ctx, 1))) return rc2;   // (the work counter lives beside the list counters)
+    if ((rc2 = ensure_sort(ctx, (size_t)ncols))) return rc2;
+    HIP_TRY(ctx, sort_columns_by_composition(b.pool, col0, ncols, k, ctx->d_sort_scratch, ctx->sort_scratch_bytes,
+                                             ctx->d_sorted, ctx->d_perm, ctx->stream));
+    PairKernelArgs a = pair_args(ctx, ce, b);
+    a.cols_sorted = ctx->d_sorted;
+    a.perm = ctx->d_perm;
+    a.ncols_sorted = ncols;
+    a.col0 = 0;
+    a.col1 = ncols;
+    HIP_TRY(ctx, launch_pairs_bound(a, ce->d_it, ce->d_bt, nullptr, d_bound, ctx->n_cu, ctx->stream));
+    return MSSPE_OK;
 }
 
 double msspe_t_cut(float tm_threshold) { return t_cut(tm_threshold); }
@@ -3317,6 +3420,40 @@ int msspe_host_table_routes(const char *params_path, const msspe_chem *chem, int
     out[4] = r.split_max_k > 0;
     out[5] = r.split_max_k;
     out[6] = r.wave_max_k;
+    return MSSPE_OK;
+}
+
+int msspe_host_bound_tables(const char *params_path, const msspe_chem *chem, float dg_threshold, int32_t *bound_g,
+                            int32_t *bound_T, int32_t info[8])
+{
+    // host only: the bound first stage's tables (csrc/fast_tables.hpp BoundTables) as chem_entry() would build them
+    if (!chem || !bound_g || !bound_T || !info) return MSSPE_ERR_ARG;
+    for (int q = 0; q < 8; ++q) info[q] = 0;
+    auto tb = std::make_unique<NNTables>();
+    std::string err;
+    const std::string path = params_path && *params_path ? params_path : default_bundle_path();
+    if (!load_nn_tables(path, *tb, err)) return MSSPE_ERR_TABLES;
+    if (!(chem->dna_conc > 0) || chem->max_loop < 0 || chem->max_loop > 30) return MSSPE_ERR_ARG;
+    const ThalConsts c = make_dimer_consts(chem->mv, chem->dv, chem->dntp, chem->dna_conc, chem->temp_c,
+                                           chem->max_loop, false, dg_threshold);
+    auto pt = std::make_unique<PairTables>();
+    if (!build_pair_tables(*tb, c, *pt, err)) return MSSPE_ERR_TABLES;
+    auto ft = std::make_unique<FastTables>();
+    auto it = std::make_unique<IntTables>();
+    auto st = std::make_unique<SplitTables>();
+    const TableRoutes r = table_routes(*tb, *pt, chem->max_loop, *ft, *it, *st);
+    auto bt = std::make_unique<BoundTables>();
+    const bool ok = build_bound_tables(*ft, c, pairs_bound_max_k(), *bt) && r.row_ok;
+    std::memcpy(bound_g, bt->g, sizeof bt->g);
+    std::memcpy(bound_T, bt->T, sizeof bt->T);
+    info[0] = ok ? 1 : 0;
+    info[1] = bt->init;
+    info[2] = bt->cut;
+    info[3] = BoundTables::kUnitInv;
+    info[4] = BoundTables::kMargin;
+    info[5] = BoundTables::kReach;
+    info[6] = IntTables::kValid;
+    info[7] = pairs_bound_max_k();
     return MSSPE_OK;
 }
 

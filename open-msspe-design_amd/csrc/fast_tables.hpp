@@ -83,4 +83,32 @@ struct IntTables {
 // (s: 18 bits signed, sums below kValid) cannot overflow for oligos up to max_k bases.
 bool build_int_tables(const FastTables &ft, int max_k, IntTables &out);
 
+// Tables of the BOUND first stage (thal_pairs_row.hip k_pairs_bound): every term as its free energy at the
+// temperature dG is reported at, g = H - temp_k * S, in integer units of 1 / kUnitInv cal/mol, ROUNDED DOWN.  A
+// structure thal() can report is a chain  left end term, (stacked pair | loop)*, right end term, initiation, and its
+// dG = dH - temp_k (dS + N salt) with N = pairs - 1 is the sum of its terms' g where every step from one pair to the
+// next also carries - temp_k * salt.  The plain minimum over all chains of the rounded-down terms is therefore a lower
+// bound of every dG thal() can report, whatever maxTM(), the acceptance rules and the traceback select.
+struct BoundTables {
+    static constexpr int kUnitInv = 64;                    // units per cal/mol
+    // Exactness margin of the cull rule, in units (= 1 cal/mol): a pair is culled iff bound > g_cut + kMargin.  The
+    // rounding of the terms only lowers the bound (soundness needs none of the margin); what the margin covers is
+    // the distance between the real-number sum and what thal() prints: its f64 roundings (< 1e-8 cal/mol) and the
+    // traceback's 1e-5 e.u. equality tolerance per step (13 steps x 1e-5 x 373.15 K < 0.05 cal/mol).
+    static constexpr int kMargin = kUnitInv;
+    static constexpr int32_t kReach = 1 << 26;             // bounds every reachable |value| (checked by build_bound_tables)
+    static_assert(13 * 1e-5 * 373.15 + 1e-6 < (double)kMargin / kUnitInv, "the margin covers the traceback's tolerance");
+    // "not available" as in IntTables (kBig; anything at or above kValid is void)
+    int32_t T[IntTables::kRows * 64];    // loop term of IntTables::T's layout: asymmetry and the step's salt term included
+    int32_t g[FastTables::kCount];       // cell-side and end terms as they are; kWC: the stacked pair WITH the step's salt term
+    int32_t init;                        // duplex initiation
+    int32_t cut;                         // cull iff init + min over chains > cut: floor((g_cut + margin) * kUnitInv)
+    int32_t usable, max_k;
+};
+// The exact values the integers above round down, for the tests: g of FastTables entry e (salt_steps: 0 or 1 salt
+// terms added), +inf where the tables hold none.
+double bound_term_exact(const FastTables &ft, const ThalConsts &c, int e, int salt_steps);
+// usable = 0 unless every reachable sum of max_k pairs stays below kReach, temp_k is within 0 .. 100 C and g_cut <= 0.
+bool build_bound_tables(const FastTables &ft, const ThalConsts &c, int max_k, BoundTables &out);
+
 }  // namespace msspe

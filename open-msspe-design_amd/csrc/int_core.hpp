@@ -174,6 +174,10 @@ struct IntArgs {
                                    // [1033 ...] (same layout, no samples)
     int stat_off;                  // 0 (matrix mode) or 1033 (list mode)
     unsigned *work_counter;        // matrix mode: next work item (one row x 64 sorted columns), zero at launch
+    // the bound instance of the row kernel (thal_pairs_row.hip k_pairs_bound) only:
+    const BoundTables *bt = nullptr;
+    unsigned long long *bound_survivors = nullptr;   // += pairs the bound could not cull
+    double *bound_plane = nullptr;                    // diagnostic form: the bound of every pair, nothing else is written
 };
 
 // A list entry whose pair needs the f64 kernels (an exact tie was met) carries this bit in .x;

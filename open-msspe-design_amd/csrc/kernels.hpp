@@ -133,6 +133,12 @@ hipError_t launch_pairs_row(const PairKernelArgs &a, const IntTables *it, unsign
 int pairs_row_max_k();
 int pairs_row_oob_max_k();   // oligos up to here run the instance that reads LDS beyond its allocation (pairs_row_lds_reads_zero)
 bool pairs_row_tables_ok(const IntTables &it);   // host: may this chemistry run the row kernel?
+// The bound instance of the 13-base row kernel (thal_pairs_row.hip k_pairs_bound): a pair whose lower bound of dG is
+// above the cut is finished, every other pair is appended to a.overflow_list; *survivors += pairs it could not cull.
+// bound_plane != nullptr: the diagnostic form (the bound of every pair in cal/mol, nothing else is written).
+hipError_t launch_pairs_bound(const PairKernelArgs &a, const IntTables *it, const BoundTables *bt,
+                              unsigned long long *survivors, double *bound_plane, int n_cu, hipStream_t stream);
+int pairs_bound_max_k();
 hipError_t pairs_row_lds_reads_zero(hipStream_t stream, int n_cu, bool *ok);   // does this device read 0 beyond a block's LDS allocation?
 // List mode of the integer stage: retries the pairs of in_list that carry no "needs f64" mark (bit
 // 31 of .x) with a 64-slot table in lanes sorted by table size; everything else passes through.

@@ -623,6 +623,69 @@ bool build_int_tables(const FastTables &ft, int max_k, IntTables &out)
     return ok;
 }
 
+double bound_term_exact(const FastTables &ft, const ThalConsts &c, int e, int salt_steps)
+{
+    if (ft.H[e] >= kHInf) return INFINITY;
+    return (double)ft.H[e] - c.temp_k * (ft.S[e] + salt_steps * c.salt);
+}
+
+bool build_bound_tables(const FastTables &ft, const ThalConsts &c, int max_k, BoundTables &out)
+{
+    typedef BoundTables B;
+    std::memset(&out, 0, sizeof out);
+    bool ok = ft.usable != 0 && max_k <= IntTables::kMaxL + 2 && std::isfinite(c.salt) && c.temp_k >= 273.15 &&
+              c.temp_k <= 373.15 && c.g_cut <= 0.0;
+    // rounded down: the integer times the unit never exceeds the exact value
+    auto units = [&](double g) -> int32_t {
+        const double u = std::floor(g * B::kUnitInv);
+        if (!(std::fabs(u) < (double)B::kReach)) {
+            ok = false;
+            return IntTables::kBig;
+        }
+        return (int32_t)u;
+    };
+    for (int e = 0; e < FastTables::kCount; ++e) {
+        const bool wc = e >= FastTables::kWC && e < FastTables::kWC + 16;
+        out.g[e] = ft.H[e] >= kHInf ? IntTables::kBig : units(bound_term_exact(ft, c, e, wc ? 1 : 0));
+    }
+    for (int d = 0; d < IntTables::kRows; ++d)
+        for (int pe = 0; pe < 64; ++pe) {
+            const int l1 = d >> 4, l2 = d & 15, sz = l1 + l2;
+            int32_t v = IntTables::kBig;
+            if (d != 0 && l1 <= IntTables::kMaxL && l2 <= IntTables::kMaxL && sz <= FastTables::kMaxSz) {
+                if (l1 == 0 || l2 == 0) {
+                    const int e = FastTables::kBU + (pe >> 2) * FastTables::kBUStride + sz * 4 + (pe & 3);
+                    if (pe < 16 && ft.H[e] < kHInf) v = units(bound_term_exact(ft, c, e, 1));
+                } else {
+                    const int e = FastTables::kNB + (sz - 2) * 64 + pe;
+                    // the asymmetry term ILAS |l1 - l2| is an entropy (fast_tables.hpp kZT; a 1 x 1 loop has none)
+                    const double zt = d == 0x11 ? 0.0 : ft.S[FastTables::kZT + 32 + (l1 - l2)];
+                    if (ft.H[e] < kHInf) v = units(bound_term_exact(ft, c, e, 1) - c.temp_k * zt);
+                }
+            }
+            out.T[d * 64 + pe] = v;
+        }
+    out.init = units(c.init_H - c.temp_k * c.init_S);
+    {
+        const double lim = -(double)(1 << 27), cu = std::floor((c.g_cut + (double)B::kMargin / B::kUnitInv) * B::kUnitInv);
+        out.cut = (int32_t)(cu > lim ? cu : lim);   // (a cut below every reachable bound culls every pair, as it should)
+    }
+    // Range of a reachable value: a chain of at most max_k pairs takes one loop or stack term and at most one
+    // cell-side term per step, two end terms and the initiation.
+    {
+        auto mag = [](int32_t v) -> double { return v >= IntTables::kValid ? 0.0 : std::fabs((double)v); };
+        double step = 0.0, mm = 0.0, en = 0.0;
+        for (int e = 0; e < IntTables::kRows * 64; ++e) step = std::max(step, mag(out.T[e]));
+        for (int e = FastTables::kWC; e < FastTables::kWC + 16; ++e) step = std::max(step, mag(out.g[e]));
+        for (int e = FastTables::kTSc; e < FastTables::kZero; ++e) mm = std::max(mm, mag(out.g[e]));
+        for (int e = FastTables::kEndL; e < FastTables::kWC; ++e) en = std::max(en, mag(out.g[e]));
+        if (max_k * (step + mm) + 2.0 * en + mag(out.init) >= (double)B::kReach) ok = false;
+    }
+    out.usable = ok ? 1 : 0;
+    out.max_k = max_k;
+    return ok;
+}
+
 bool build_split_tables(const PairTables &pt, int max_loop, SplitTables &out)
 {
     typedef SplitTables W;

@@ -38,8 +38,11 @@
 //
 // Ties, maxTM, the terminal pick, the traceback by pointer and the f64 replay of the optimal path are
 // those of thal_pairs_int.hip; a pair this kernel does not answer goes to the same hand-over list.
+// A screen that asks for decisions only runs the BOUND instance of this kernel first (k_pairs_bound, further down: a
+// lower bound of dG per pair, no structure), which finishes the pairs it proves free of a conflict.
 #include "int_core.hpp"
 #include "row_scan_pinned.inc"
+#include "row_bound_pinned.inc"
 
 
 namespace msspe {
@@ -730,8 +733,135 @@ static __device__ __forceinline__ IntResult run_pair_row(SharedRow &sh, const Th
     return out;
 }
 
-// One lock-step DP of the wave: lane = (row, col), all lanes share `row`.
+// ---- the BOUND instance (k_pairs_bound): a lower bound of the pair's dG instead of the structure thal() picks ---------
+// Every dG thal() reports is the free energy, at the temperature of the report, of a chain  left end term, (stacked
+// pair | loop)*, right end term, initiation  (fast_tables.hpp BoundTables).  This instance computes the plain minimum
+// over all such chains in integers rounded down -- same rows, slots, slot word K and table address as above, but a
+// cell is  min(left end term, min over predecessors of (table entry + cell-side term + predecessor))  and nothing
+// else: no maxTM, no runner-up, no enthalpy, no predecessor bytes, no walk back, no f64.  The stacked pair is an
+// ordinary entry of the table (l2 = 0, the row above the cell), so the row above the cell is scanned like the others.
+// A pair whose bound is above the cut by the margin cannot conflict and is finished; every other pair (0.6 % of a
+// random 13-mer pool at -9000 cal/mol) goes to the hand-over list, where the exact stages answer it.
+// Values (units of 1 / BoundTables::kUnitInv cal/mol): every reachable |value| < kBndReach (build_bound_tables).
+// As above "not available" must read as 0: table entries carry - kBndZero, slot values + kBndZero.
+static constexpr int kBndReach = BoundTables::kReach;
+static constexpr int kBndZero = 1 << 29;                // a void loop entry's value (stored: 0)
+static constexpr int kBndYVoid = 1 << 28;               // a void cell-side term
+static constexpr int kBndInit = 1 << 27;                // the scan's and the pick's starting minimum
+static_assert(kBndInit >= 2 * kBndReach, "above every cell value plus an end term (both below kBndReach)");
+static_assert(kBndYVoid - 2 * kBndReach > kBndReach && kBndZero - kBndYVoid - 2 * kBndReach > kBndReach,
+              "a candidate that holds a void term (a folded-out void cell-side term included) stays above every left end term, "
+              "which every cell has (pairs_row_tables_ok): no cell takes it");
+static_assert((long long)kBndZero + kBndYVoid + 2 * kBndReach + kBndZero < 0x7fffffffLL,
+              "largest candidate (void loop + void cell side + reachable slot value) is an int32");
+static_assert(-(long long)kBndReach - kBndYVoid - kBndZero > -0x7fffffffLL, "smallest table entry is an int32");
+static_assert(IntTables::kValid > kBndReach, "the tables' void marker is beyond every value");
+
+static __device__ __forceinline__ int bound_scan(const v32i Ga, const v32i Wa, const v16i Gb, const v16i Wb, const v4i Gc,
+                                              const v4i Wc, unsigned C, int Y, int n_far, int n_run, int near_from)
+{
+    int best, a0, a1, a2, a3, t0, t1, t2, t3, yt;
+    asm volatile(MSSPE_BND13_SCAN_ASM
+                 : MSSPE_BND13_ACC_OUT(best), [a0] "=&v"(a0), [a1] "=&v"(a1), [a2] "=&v"(a2), [a3] "=&v"(a3), [t0] "=&v"(t0),
+                   [t1] "=&v"(t1), [t2] "=&v"(t2), [t3] "=&v"(t3), [yt] "=&v"(yt)
+                 : [C] "v"(C), [Y] "v"(Y), [NFAR] "s"(n_far), [NRUN] "s"(n_run), [NEAR] "s"(near_from),
+                   [TOFF] "n"((int)offsetof(SharedRow, T)), [INIT] "n"(kBndInit), MSSPE_BND13_TUPLES_IN(Ga, Gb, Gc, Wa, Wb, Wc)
+                 : MSSPE_BND13_SCAN_CLOBBERS);
+    return best;
+}
+
+// The minimum over the lane's cells of (cell value + right end term); kBndInit: the pair has no cell.  Rows, slots and
+// the lock-step walk are run_pair_row's.
 template <int NS>
+static __device__ __forceinline__ int run_pair_bound(SharedRow &sh, const SeqPair &q, bool active, unsigned wmax4)
+{
+    static_assert(kPin && NS == 52, "the bound instance exists for 13 bases");
+    v32i Ga = kBndZero, Wa = kEmptyRowW;   // slot values carry + kBndZero
+    v16i Gb = kBndZero, Wb = kEmptyRowW;
+    v4i Gc = kBndZero, Wc = kEmptyRowW;
+    CellCtx c;
+    int pick = kBndInit;
+    int slot_ = 0, start_im1 = 0;   // first slot of row i-1
+    for (int i_ = 0; i_ < q.len; ++i_) {
+      const int im1 = __builtin_amdgcn_readfirstlane(i_);
+      const int a_row = (int)((q.s1 >> (2 * im1)) & 3u);
+      const int w_row = (int)((wmax4 >> (8 * (3 - a_row))) & 0xffu);   // widest lane's cells in this row
+      const int row_start = __builtin_amdgcn_readfirstlane(slot_);
+      const bool stored = im1 < q.len - 1;   // wave-uniform: the cells of the last row are nobody's predecessors
+      unsigned mrem = active ? spaced_mask(q.s2, 3 - a_row, q.lenmask) : 0u;
+      for (int c_ = 0; c_ < w_row; ++c_, slot_ += stored ? 1 : 0) {
+        const int slot = __builtin_amdgcn_readfirstlane(slot_);
+        const bool in = mrem != 0u;
+        const int jm1 = ((__ffs((int)mrem) - 1) >> 1) & 15;
+        mrem &= mrem - 1;
+        const unsigned C = ((unsigned)((jm1 - 1) * kRowA + im1 * (4 * (kRowR + 1)) + 3) << 17) | 0x7fffu;
+        const int yTS = sh.yts[(im1 << 2) | (int)(((q.s2 << 2) >> (2 * jm1)) & 3u)];
+        const int best = bound_scan(Ga, Wa, Gb, Wb, Gc, Wc, C, yTS, start_im1 / kC, (row_start + kC - 1) / kC, start_im1);
+        const CellBases b = cell_bases(q, im1, jm1, c);
+        const int gL = sh.g[b.idxL - kRowGBase], gR = sh.g[b.idxR - kRowGBase];
+        const int G0 = in ? min(gL, best) : 0;   // (a lane without a cell here publishes an empty slot: its word fails every geometry test)
+        pick = in ? min(pick, G0 + gR) : pick;
+        const int Wcell = in ? ((int)((unsigned)(jm1 * kRowA + (im1 << 2) + ((b.po_c >> 4) & 3)) << 17) | kHBias) : kEmptyRowW;
+        if (slot < NS) pin_publish(Ga, Wa, Gb, Wb, Gc, Wc, slot, G0 + kBndZero, Wcell);
+      }
+      start_im1 = row_start;
+    }
+    return pick;
+}
+
+// The bound table of row primer s1: build_row_table's entries from BoundTables (same layout, same folded cell-side
+// terms), plus the stacked pair at (l2 = 0, r = 1), whose bases are all oligo 1's (the cell and the predecessor
+// are complementary ones).
+static __device__ __forceinline__ void build_bound_table(SharedRow &sh, const IntArgs &a, unsigned s1)
+{
+    const int32_t *Tg = a.bt->T;
+    if (threadIdx.x < 64) {
+        const int i = threadIdx.x >> 2, m2 = threadIdx.x & 3;
+        const int a_c = (int)((s1 >> (2 * i)) & 3u), m1 = i > 0 ? (int)((s1 >> (2 * i - 2)) & 3u) : 0;
+        const int y = sh.g[FastTables::kTSc - kRowGBase + (((3 - a_c) * 4 + m2) * 4 + m1)];
+        sh.yts[threadIdx.x] = y >= IntTables::kValid ? kBndYVoid : y;
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < kRowTEntries; e += kRowThreads) {
+        const int l2 = e / kRowA, rem = e - l2 * kRowA;
+        const int n2 = 3 - (rem & 3), ir = rem >> 2, i = ir / kRowR, r = ir - i * kRowR;
+        const int ii = i - r, l1 = r - 1;
+        int v = IntTables::kBig;
+        bool needs_y = false;
+        if (r >= 1 && ii >= 0 && i < a.f.k && l1 <= IntTables::kMaxL) {
+            const int d = l1 * 16 + l2;
+            const int a_p = (int)((s1 >> (2 * ii)) & 3u), a_c = (int)((s1 >> (2 * i)) & 3u);
+            if (d == 0) {
+                if (n2 == 3 - a_c) v = sh.g[FastTables::kWC - kRowGBase + a_p * 4 + a_c];   // the base right of the predecessor is the cell's
+            } else if (l1 == 0 || l2 == 0) {
+                v = Tg[d * 64 + (a_p | (a_c << 2))];
+            } else {
+                const int n1 = (int)((s1 >> (2 * ii + 2)) & 3u);
+                v = Tg[d * 64 + (a_p | (n1 << 2) | (n2 << 4))];
+                if (l2 == 1) {
+                    const int m1 = (int)((s1 >> (2 * i - 2)) & 3u);
+                    const int ci = ((3 - a_c) * 4 + n2) * 4 + m1;
+                    const int y = sh.g[(d == 0x11 ? FastTables::kMMc : FastTables::kTSc) + ci - kRowGBase];
+                    v = (v >= IntTables::kValid || y >= IntTables::kValid) ? IntTables::kBig : v + y;
+                } else {
+                    needs_y = v < IntTables::kValid;
+                }
+            }
+        }
+        if (v >= IntTables::kValid) {
+            v = kBndZero;
+        } else if (!needs_y && r >= 2) {
+            // the lane adds yts[i][m2] to every entry of the rows r >= 2: taken out here where the loop has no such term
+            const int m2 = l2 == 1 ? n2 : 3 - (int)((s1 >> (2 * ii)) & 3u);
+            v -= sh.yts[(i << 2) | m2];
+        }
+        sh.T[e] = v - kBndZero;   // "not available" is 0
+    }
+    if (threadIdx.x < 4) sh.T[kRowTEntries + threadIdx.x] = 0;
+}
+
+// One lock-step DP of the wave: lane = (row, col), all lanes share `row`.
+template <int NS, bool BOUND = false>
 static __device__ __forceinline__ void wave_pairs_row(SharedRow &sh, const IntArgs &a, int row, int col, uint64_t pa,
                                                uint64_t pb, bool inside)
 {
@@ -802,6 +932,35 @@ static __device__ __forceinline__ void wave_pairs_row(SharedRow &sh, const IntAr
             n_cells = 0;
         }
         nmax = wave_max_u8(n_cells);
+    }
+    if constexpr (BOUND) {
+        if (__ballot(active) != 0ull) {   // wave-uniform
+            const unsigned wmax4 = (unsigned)w4[0] | ((unsigned)w4[1] << 8) | ((unsigned)w4[2] << 16) | ((unsigned)w4[3] << 24);
+            const int pick = run_pair_bound<NS>(sh, q, active, wmax4);
+            const int lb = pick + a.bt->init;   // a lane without a chain keeps kBndInit: above every cut
+            if (a.bound_plane) {
+                if (active)
+                    a.bound_plane[(size_t)(row - a.f.sinks.row0) * (size_t)a.f.sinks.ncols + (size_t)(col - a.f.sinks.col0)] =
+                        pick >= kBndInit ? INFINITY : (double)lb / BoundTables::kUnitInv;
+            } else {
+                const bool survivor = active & (lb <= a.bt->cut);   // a culled pair is finished: no bit, no count
+                const unsigned long long sm = __ballot(survivor);
+                if (lane == 0 && sm) atomicAdd(a.bound_survivors, (unsigned long long)__popcll(sm));
+                spill |= survivor;
+            }
+        }
+        if (a.bound_plane) {
+            // pairs this kernel does not bound (table too large, dragged, both self-complementary): -inf, a bound all the same;
+            // pairs without a complementary cell: no chain
+            if (inside & !active)
+                a.bound_plane[(size_t)(row - a.f.sinks.row0) * (size_t)a.f.sinks.ncols + (size_t)(col - a.f.sinks.col0)] =
+                    spill ? -INFINITY : INFINITY;
+        } else if (spill && a.f.ovf_list) {   // survivors and size hand-overs alike: the list stages answer them exactly
+                                              // (no list: the probe launch of option pair_bound = auto, which only counts)
+            const uint32_t at = atomicAdd(a.f.ovf_count, 1u);
+            if (at < a.f.ovf_cap) a.f.ovf_list[at] = make_uint2((unsigned)row | flag, (unsigned)col);
+        }
+        return;
     }
     if (__ballot(active) == 0ull) {   // wave-uniform: nothing to compute
         if (spill) {
@@ -938,16 +1097,21 @@ static __device__ __forceinline__ void build_row_table(SharedRow &sh, const IntA
     }
 }
 
-template <int NS>
+template <int NS, bool BOUND = false>
 static __device__ __forceinline__ void kernel_body(const IntArgs &a)
 {
-    __shared__ SharedRow sh;
-    for (int e = threadIdx.x; e < kRowGCount; e += kRowThreads) {
-        sh.h[e] = a.f.ft->H[kRowGBase + e] / 10;   // finite entries are multiples of 10 (build_int_tables); "not available" stays huge
-        sh.g[e] = a.it->g[kRowGBase + e];
+    __shared__ SharedRow sh;   // (the bound instance uses g, yts and T of it: the SAME allocation, so that what
+                               //  pairs_row_lds_reads_zero() probed holds for its table reads as well)
+    if constexpr (BOUND) {
+        for (int e = threadIdx.x; e < kRowGCount; e += kRowThreads) sh.g[e] = a.bt->g[kRowGBase + e];
+    } else {
+        for (int e = threadIdx.x; e < kRowGCount; e += kRowThreads) {
+            sh.h[e] = a.f.ft->H[kRowGBase + e] / 10;   // finite entries are multiples of 10 (build_int_tables); "not available" stays huge
+            sh.g[e] = a.it->g[kRowGBase + e];
+        }
+        for (int e = threadIdx.x; e < 100; e += kRowThreads)
+            sh.cq[e] = 620300.0 * ((a.f.c.init_S + a.f.ft->S[FastTables::kEndR + e]) + a.f.c.RC);
     }
-    for (int e = threadIdx.x; e < 100; e += kRowThreads)
-        sh.cq[e] = 620300.0 * ((a.f.c.init_S + a.f.ft->S[FastTables::kEndR + e]) + a.f.c.RC);
     const int lane = threadIdx.x & 63;
     const int ncolg = (a.f.col1 - a.f.col0 + 63) >> 6;
     const int n_seg = (ncolg + kSegGroups - 1) / kSegGroups;
@@ -968,7 +1132,8 @@ static __device__ __forceinline__ void kernel_body(const IntArgs &a)
         const uint64_t pa = a.f.pool[row];
         if (row != built_row) {
             const unsigned lenmask = (1u << (2 * a.f.k)) - 1u;
-            build_row_table(sh, a, (unsigned)pa & lenmask);
+            if constexpr (BOUND) build_bound_table(sh, a, (unsigned)pa & lenmask);
+            else build_row_table(sh, a, (unsigned)pa & lenmask);
             built_row = row;
         }
         __syncthreads();
@@ -985,7 +1150,7 @@ static __device__ __forceinline__ void kernel_body(const IntArgs &a)
             const bool inside = cq < a.f.col1;
             const uint64_t pb = a.f.cols_sorted[inside ? cq : a.f.col0];
             const int col = (int)a.f.perm[inside ? cq : a.f.col0];
-            wave_pairs_row<NS>(sh, a, row, col, pa, pb, inside);
+            wave_pairs_row<NS, BOUND>(sh, a, row, col, pa, pb, inside);
         }
         __syncthreads();   // every wave is done with the table (and with sh.item) before the next item
     }
@@ -1005,6 +1170,12 @@ template <class RK>
 __global__ void __launch_bounds__(RK::kRowThreads) k_pairs_row(IntArgs a)
 {
     RK::template kernel_body<RK::kRowSlots>(a);
+}
+
+template <class RK>
+__global__ void __launch_bounds__(RK::kRowThreads) k_pairs_bound(IntArgs a)
+{
+    RK::template kernel_body<RK::kRowSlots, true>(a);
 }
 
 }  // namespace
@@ -1069,6 +1240,10 @@ hipError_t pairs_row_lds_reads_zero(hipStream_t stream, int n_cu, bool *ok)
         if (ea == hipSuccess) ea = hipFuncGetAttributes(&fp, (const void *)k_lds_probe);
         if (ea != hipSuccess) return ea;
         if (fa.sharedSizeBytes != fp.sharedSizeBytes) return hipSuccess;
+        // ... and so must the bound instance's, which reads its table the same way
+        hipFuncAttributes fb;
+        if (hipFuncGetAttributes(&fb, (const void *)k_pairs_bound<Row13>) != hipSuccess || fb.sharedSizeBytes != fp.sharedSizeBytes)
+            return hipSuccess;
         if (offsetof(Row13::SharedRow, T) + (size_t)Row13::kRowWrapMin < (fa.sharedSizeBytes + 1279) / 1280 * 1280) return hipSuccess;
     }
     unsigned *d_flag = nullptr, h_flag[3] = {0, 0, 1};
@@ -1143,6 +1318,49 @@ hipError_t launch_pairs_row(const PairKernelArgs &a, const IntTables *it, unsign
     if (a.k <= Row13::kRowK) hipLaunchKernelGGL((k_pairs_row<Row13>), dim3(grid), dim3(Row13::kRowThreads), 0, stream, x);
     else if (a.k <= Row14::kRowK) hipLaunchKernelGGL((k_pairs_row<Row14>), dim3(grid), dim3(Row14::kRowThreads), 0, stream, x);
     else hipLaunchKernelGGL((k_pairs_row<Row15>), dim3(grid), dim3(Row15::kRowThreads), 0, stream, x);
+    return hipGetLastError();
+}
+
+int pairs_bound_max_k() { return Row13::kRowK; }
+
+// The bound first stage (k_pairs_bound): launch_pairs_row's contract, but a pair is either proven not to conflict
+// (nothing is written for it) or appended to a.overflow_list.  bound_plane != nullptr: the diagnostic form, which writes
+// the bound of every pair of the block (cal/mol; +inf: no chain; -inf: not bounded here) and nothing else.
+hipError_t launch_pairs_bound(const PairKernelArgs &a, const IntTables *it, const BoundTables *bt,
+                              unsigned long long *survivors, double *bound_plane, int n_cu, hipStream_t stream)
+{
+    if (a.k > Row13::kRowK || a.k < 2 || !bt || (!survivors && !bound_plane)) return hipErrorInvalidValue;
+    IntArgs x;
+    FastArgs &f = x.f;
+    f.ft = a.ft;
+    f.c = a.c;
+    f.pool = a.pool;
+    f.cols_sorted = a.cols_sorted;
+    f.perm = a.perm;
+    f.k = a.k;
+    f.row0 = a.row0;
+    f.row1 = a.row1;
+    f.col0 = a.col0;
+    f.col1 = a.col1;
+    f.sinks = a.sinks;
+    f.ovf_list = a.overflow_list;
+    f.ovf_count = a.overflow_count;
+    f.ovf_cap = a.overflow_cap;
+    f.in_list = nullptr;
+    f.in_count = nullptr;
+    x.it = it;
+    x.reasons = nullptr;
+    x.stat_off = 0;
+    x.work_counter = a.work_counter;
+    x.bt = bt;
+    x.bound_survivors = survivors;
+    x.bound_plane = bound_plane;
+    const long ncolg = (a.col1 - a.col0 + 63) / 64;
+    const long items = ((ncolg + Row13::kSegGroups - 1) / Row13::kSegGroups) * (long)(a.row1 - a.row0);
+    if (items <= 0) return hipSuccess;
+    if (hipError_t e = hipMemsetAsync(a.work_counter, 0, sizeof(unsigned), stream); e != hipSuccess) return e;
+    const int grid = (int)(items < (long)n_cu ? items : (long)n_cu);
+    hipLaunchKernelGGL((k_pairs_bound<Row13>), dim3(grid), dim3(Row13::kRowThreads), 0, stream, x);
     return hipGetLastError();
 }
 

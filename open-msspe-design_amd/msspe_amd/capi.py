@@ -16,7 +16,7 @@ EXPORTS = [
     "msspe_last_error", "msspe_version", "msspe_set_option", "msspe_get_info", "msspe_kmer_trace", "msspe_set_stream", "msspe_reset_stream",
     "msspe_synchronize",
     "msspe_pack_oligos", "msspe_unpack_oligo", "msspe_cross_dimer_dev", "msspe_cross_dimer",
-    "msspe_cross_dimer_edges_dev", "msspe_cross_dimer_edges",
+    "msspe_cross_dimer_edges_dev", "msspe_cross_dimer_edges", "msspe_cross_dimer_bound_dev", "msspe_host_bound_tables",
     "msspe_cross_dimer_ab_dev", "msspe_cross_dimer_ab_edges_dev", "msspe_cross_dimer_ab", "msspe_cross_dimer_ab_edges",
     "msspe_cross_dimer_edges_mixed",
     "msspe_cross_dimer_end_dev", "msspe_cross_dimer_end", "msspe_cross_dimer_end_edges_dev", "msspe_cross_dimer_end_edges",
@@ -185,6 +185,9 @@ def load_library() -> C.CDLL:
                                           C.c_uint64, C.POINTER(C.c_uint64)]
     L.msspe_cross_dimer_edges_dev.argtypes = [vp, u64p, C.c_int, C.c_int, C.POINTER(Chem), C.c_float,
                                               C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_uint64, vp]
+    L.msspe_cross_dimer_bound_dev.argtypes = [vp, u64p, C.c_int, C.c_int, C.POINTER(Chem), C.c_float,
+                                              C.c_int, C.c_int, C.c_int, C.c_int, vp]
+    L.msspe_host_bound_tables.argtypes = [C.c_char_p, C.POINTER(Chem), C.c_float, vp, vp, C.POINTER(C.c_int32)]
     L.msspe_cross_dimer_ab_dev.argtypes = [vp, u64p, C.c_int, C.c_int, u64p, C.c_int, C.c_int, C.POINTER(Chem),
                                            C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     L.msspe_cross_dimer_ab_edges_dev.argtypes = [vp, u64p, C.c_int, C.c_int, u64p, C.c_int, C.c_int, C.POINTER(Chem),
@@ -369,6 +372,21 @@ def host_table_routes(params_path: str | None = None, chem: Chem | None = None) 
     return dict(zip(TABLE_ROUTE_KEYS, list(out)[:7]))
 
 
+def host_bound_tables(params_path: str | None = None, chem: Chem | None = None, threshold: float = -9000.0) -> dict:
+    """The bound first stage's tables (no device needed): msspe_host_bound_tables.  g / T in the layout of
+    host_pair_tables' int_g / int_T, in units of 1 / unit_inv cal/mol, rounded down; >= void: not available."""
+    g = np.zeros(2604, dtype=np.int32)
+    T = np.zeros(239 * 64, dtype=np.int32)
+    info = (C.c_int32 * 8)()
+    chem = chem or Chem.ntthal()
+    rc = load_library().msspe_host_bound_tables(str(params_path).encode() if params_path else None, C.byref(chem),
+                                                C.c_float(threshold), g.ctypes.data, T.ctypes.data, info)
+    if rc:
+        raise MsspeError(rc, f"msspe_host_bound_tables({params_path})")
+    keys = ("usable", "init", "cut", "unit_inv", "margin", "reach", "void", "max_k")
+    return {"g": g, "T": T, **dict(zip(keys, list(info)))}
+
+
 def _seed_words(seed, k: int) -> np.ndarray | None:
     """A seed= list (strings of length k, ACGT) -> packed uint64 words; None when no seed was given."""
     if seed is None:
@@ -495,6 +513,14 @@ class Engine:
         self._check(self.L.msspe_cross_dimer_edges_dev(
             self.ptr, C.c_void_p(d_pool), n, k, C.byref(chem), C.c_float(threshold), rows[0], rows[1], cols[0],
             cols[1], C.c_void_p(d_row_conflicts), C.c_void_p(d_edges), capacity, C.c_void_p(d_count)))
+
+    def cross_dimer_bound_dev(self, d_pool: int, n: int, k: int, chem: Chem, threshold: float,
+                              rows: tuple[int, int], cols: tuple[int, int], d_bound: int):
+        """Diagnostic (tests, debugging): the bound first stage's value of every pair of the block, float64 cal/mol
+        into the caller's plane (+inf: no chain; -inf: not bounded there); asynchronous.  msspe_cross_dimer_bound_dev."""
+        self._check(self.L.msspe_cross_dimer_bound_dev(
+            self.ptr, C.c_void_p(d_pool), n, k, C.byref(chem), C.c_float(threshold), rows[0], rows[1], cols[0],
+            cols[1], C.c_void_p(d_bound)))
 
     def cross_dimer_dev(self, d_pool: int, n: int, k: int, chem: Chem, threshold: float,
                         rows: tuple[int, int], cols: tuple[int, int], d_row_conflicts: int = 0,
@@ -1116,6 +1142,8 @@ class Engine:
         out = {n: int(v[i]) for i, n in enumerate(names)}
         out["list"] = {n: int(v[8 + i]) for i, n in enumerate(names)}
         out["needed_f64"] = int(v[8])
+        # pairs the bound first stage (option pair_bound) could not cull and handed to list 0; not part of "deferred"
+        out["bound_survivors"] = self.info("bound_survivors")
         return out
 
     # ---- stage B ---------------------------------------------------------------------------
