@@ -134,6 +134,11 @@ const char *msspe_version(void);
  *                                 threshold and oligo length by a probe launch over at most 2^20 pairs of the first
  *                                 such call's block (one extra host round trip, none when the stream is being captured:
  *                                 the exact kernel then runs)
+ *   "pair_mirror"    "auto" | "0" | "1"  where the bound first stage runs on a square same-pool block (rows = columns) and
+ *                                 its tables are strand-symmetric term by term (msspe_host_bound_mirror_ok), it fills
+ *                                 each unordered pair once -- the bound of (a, b) is one of (b, a) too -- and hands a
+ *                                 pair it cannot cull on in both orders ("auto", the default, and "1": the same; the
+ *                                 mirror is never applied where it is not proven); "0": every ordered pair is filled
  *   "stage_a_graph"  "0" | "1"    hipGraph replay of stage A's greedy loop (1)
  *   "stage_a_candidates" "0" | "1"  greedy loop over the list of words near the maximum (1), or over all the
  *                                 words on every iteration (0); the winners are the same */
@@ -456,6 +461,10 @@ int msspe_host_table_routes(const char *params_path, const msspe_chem *chem, int
  * is above it), units per cal/mol, margin in units, bound of every reachable |sum|, the void marker, longest oligo. */
 int msspe_host_bound_tables(const char *params_path, const msspe_chem *chem, float dg_threshold, int32_t *bound_g,
                             int32_t *bound_T, int32_t info[8]);
+/* Host only: *mirror_ok = 1 when the bound first stage may fill each unordered pair of a square same-pool screen once
+ * (option "pair_mirror"): its tables are usable and every real-valued term of them equals its strand-swapped partner
+ * within 1e-6 cal/mol (csrc/fast_tables.hpp bound_mirror_ok). */
+int msspe_host_bound_mirror_ok(const char *params_path, const msspe_chem *chem, float dg_threshold, int32_t *mirror_ok);
 /* The same for the long-oligo kernel (csrc/split_tables.hpp): S / H / g hold info[2] entries, L 1024,
  * X info[3]; info = usable, longest oligo covered, entry count, X count. */
 int msspe_host_split_tables(const char *params_path, const msspe_chem *chem, double *S, int32_t *H,

@@ -53,6 +53,7 @@ struct ChemEntry {
     bool row_ok = false;          // ... and the row-specialised kernel (thal_pairs_row.hip)
     BoundTables *d_bt = nullptr;  // the bound first stage's tables (thal_pairs_row.hip k_pairs_bound)
     bool bound_ok = false;        // ... usable: row_ok, g_cut <= 0, values in range (build_bound_tables)
+    bool mirror_ok = false;       // ... and strand-symmetric term by term (bound_mirror_ok): a square screen fills each unordered pair once
     // option pair_bound = auto: the share of pairs the bound stage could not cull, per oligo length, as the first
     // call's probe launch measured it (this entry keys on chemistry AND threshold); < 0: no record yet
     float bound_share[16] = {-1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f};
@@ -79,6 +80,8 @@ constexpr long kBoundProbePairs = 1L << 20;  // pair_bound = auto: pairs of the 
 // pair_bound = auto runs the bound stage while the recorded survivor share is at most this: HALF the break-even share
 //   (ns per pair of the exact row kernel - ns per pair of the bound kernel) / ns per handed-on pair of the list chain
 // = (0.2856 - 0.1521) / 1.72 = 7.8 % (DESIGN.md 4.0 holds the three prices and the session they were measured in)
+// (the mirrored stage of a square screen costs 0.0763 ns per ordered pair: its break-even share is about 15 %, so the
+//  switch point stays on the safe side there)
 constexpr float kBoundShareMax = 0.039f;
 
 }  // namespace
@@ -95,6 +98,8 @@ struct EngineOptions {
     bool row_oob = true;      // the row-specialised first stage (it reads LDS beyond its allocation: thal_pairs_row.hip) may run
     int pair_bound = 2;       // decision-only screens of up to 13 bases, cut <= 0: the bound first stage (k_pairs_bound) in front of
                               // the list stages -- 0 never | 1 wherever it applies | 2 auto: while few pairs survive it (kBoundShareMax)
+    int pair_mirror = 2;      // the bound stage of a square same-pool screen fills each unordered pair once and hands a survivor on in
+                              // both orders -- 0 never | 1, 2 (auto): wherever the tables are strand-symmetric (ChemEntry::mirror_ok)
     bool split_list = true;   // short oligos: tables too large for the integer list stage go to the split kernel's list mode
     bool short_chain = true;  // screens of up to 2^23 pairs: integer list stage -> one wave per pair (no register-table stages between)
     int self_lane_from = 81920;   // oligos per call from which SELF_ANY / SELF_END run one lane per oligo (msspe_oligo_stats_dev)
@@ -183,6 +188,7 @@ struct msspe_ctx {
     bool prof_on = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events;
     size_t prof_used = 0;
+    long long bound_mirrored = 0;      // info key "bound_mirrored"
 };
 
 namespace {
@@ -287,6 +293,7 @@ int chem_entry(msspe_ctx *ctx, const msspe_chem &chem, float threshold, ChemEntr
         if (kind == kCutAnyDg && r.row_ok) {
             auto bt = std::make_unique<BoundTables>();
             e.bound_ok = build_bound_tables(*ft, e.c[0], pairs_bound_max_k(), *bt);
+            e.mirror_ok = e.bound_ok && bt->mirror_ok != 0;
             if (e.bound_ok) {
                 HIP_TRY(ctx, hipMalloc((void **)&e.d_bt, sizeof(BoundTables)));
                 HIP_TRY(ctx, hipMemcpy(e.d_bt, bt.get(), sizeof(BoundTables), hipMemcpyHostToDevice));
@@ -745,6 +752,10 @@ int msspe_set_option(msspe_ctx *ctx, const char *key, const char *value)
         if (v == "auto") ctx->opt.pair_bound = 2;
         else if (is_num && (num == 0 || num == 1)) ctx->opt.pair_bound = (int)num;
         else return bad();
+    } else if (k == "pair_mirror") {
+        if (v == "auto") ctx->opt.pair_mirror = 2;
+        else if (is_num && (num == 0 || num == 1)) ctx->opt.pair_mirror = (int)num;
+        else return bad();
     } else if (k == "stage_a_graph") {
         if (!is_num || num < 0 || num > 1) return bad();
         ctx->kmer.set_use_graph(num != 0);
@@ -809,6 +820,13 @@ int msspe_get_info(msspe_ctx *ctx, const char *key, long long *value_out)
     else if (k == "panel_thin_gain0_us") *value_out = ctx->thin.phase_us()[1];
     else if (k == "panel_thin_rounds_us") *value_out = ctx->thin.phase_us()[2];
     else if (k == "pair_bound") *value_out = ctx->opt.pair_bound;
+    else if (k == "pair_mirror") *value_out = ctx->opt.pair_mirror;
+    else if (k == "bound_mirrored") {
+        // ordered pairs the mirrored bound stage answered or handed on without a fill of their own since the last read
+        // of this key; reading resets it
+        *value_out = ctx->bound_mirrored;
+        ctx->bound_mirrored = 0;
+    }
     else if (k == "bound_survivors") {
         // pairs the bound first stage handed on since the last read of this key; reading resets it
         *value_out = 0;
@@ -1082,6 +1100,73 @@ static int run_chain(msspe_ctx *ctx, ChemEntry *ce, const ChainRoute &route, con
         bound_stage = ce->bound_share[k] >= 0.f && ce->bound_share[k] <= kBoundShareMax;
     }
     long pending = 0;   // worst-case entries the list may hold
+    auto prof_begin = [&]() -> int {
+        if (!ctx->prof_on) return MSSPE_OK;
+        if (ctx->prof_used == ctx->prof_events.size()) {
+            hipEvent_t e0, e1;
+            HIP_TRY(ctx, hipEventCreate(&e0));
+            HIP_TRY(ctx, hipEventCreate(&e1));
+            ctx->prof_events.emplace_back(e0, e1);
+        }
+        HIP_TRY(ctx, hipEventRecord(ctx->prof_events[ctx->prof_used].first, ctx->stream));
+        return MSSPE_OK;
+    };
+    auto prof_end = [&]() -> int {
+        if (ctx->prof_on) HIP_TRY(ctx, hipEventRecord(ctx->prof_events[ctx->prof_used++].second, ctx->stream));
+        return MSSPE_OK;
+    };
+    // A square same-pool block under strand-symmetric tables (ChemEntry::mirror_ok): the bound of (a, b) stands for
+    // (b, a) as well ("Screen each unordered pair once"), so the bound stage fills each unordered pair once.
+    // Rows are taken in the columns' sorted order: row p is sorted[p] (pool index perm[p]) and screens the sorted columns
+    // q >= p; a pair that is not culled is appended in both orders, so a launch that processes P pairs may append 2 P
+    // entries.  The row ranges are cut so that the launches process near-equal pair counts (earlier rows have longer
+    // suffixes), each within half a list and kChunkPairs.
+    const long mirror_cap = std::min(kChunkPairs, kListCap / 2);
+    const bool mirror = bound_stage && ce->mirror_ok && ctx->opt.pair_mirror != 0 && k == k2 && row0 == col0 && row1 == b.col1 &&
+                        (long)ncols <= mirror_cap;
+    if (mirror) {
+        const long n = ncols;
+        auto processed = [&](long p0, long p1) { return (p1 - p0) * n - (p1 * (p1 - 1) - p0 * (p0 - 1)) / 2; };   // sum of n - p
+        const long total = processed(0, n);
+        const long n_launch = (total + mirror_cap - 1) / mirror_cap;
+        const long target = (total + n_launch - 1) / n_launch;
+        for (long p0 = 0; p0 < n;) {
+            // the first row count that reaches the target, in whole groups of 24 rows, within the cap (one row always is)
+            long lo = p0 + 1, hi = n;
+            while (lo < hi) {
+                const long mid = lo + (hi - lo) / 2;
+                if (processed(p0, mid) >= target) hi = mid;
+                else lo = mid + 1;
+            }
+            long p1 = std::min(n, p0 + (lo - p0 + 23) / 24 * 24);
+            while (p1 > p0 + 1 && processed(p0, p1) > mirror_cap) --p1;
+            const long launch_pairs = processed(p0, p1);
+            if (pending + 2 * launch_pairs > kListCap) {
+                if ((rc = flush())) return rc;
+                pending = 0;
+            }
+            PairKernelArgs a = pair_args(ctx, ce, b);
+            a.cols_sorted = ctx->d_sorted;
+            a.perm = ctx->d_perm;
+            a.ncols_sorted = ncols;
+            a.row0 = (int)p0;   // sorted positions, like the columns
+            a.row1 = (int)p1;
+            a.col0 = 0;
+            a.col1 = ncols;
+            a.overflow_list = ctx->ovf_list;
+            a.overflow_count = ctx->ovf_count;
+            a.overflow_cap = (uint32_t)kListCap;
+            if ((rc = prof_begin())) return rc;
+            HIP_TRY(ctx, launch_pairs_bound(a, ce->d_it, ce->d_bt, ctx->d_reasons + kBoundSurvivors, nullptr, ctx->n_cu,
+                                            ctx->stream, true));
+            if ((rc = prof_end())) return rc;
+            pending += 2 * launch_pairs;
+            p0 = p1;
+        }
+        ctx->bound_mirrored += n * (n - 1) / 2;
+        if (pending && (rc = flush())) return rc;
+        return MSSPE_OK;
+    }
     for (int r = row0; r < row1; r += (int)rows_per_chunk) {
         const int r_end = (int)std::min<long>(row1, (long)r + rows_per_chunk);
         for (long q0 = 0; q0 < ncols; q0 += chunk_pairs) {   // sorted-column index range (one chunk unless a row is longer than a launch)
@@ -1102,15 +1187,7 @@ static int run_chain(msspe_ctx *ctx, ChemEntry *ce, const ChainRoute &route, con
             a.overflow_list = ctx->ovf_list;
             a.overflow_count = ctx->ovf_count;
             a.overflow_cap = (uint32_t)kListCap;
-            if (ctx->prof_on) {
-                if (ctx->prof_used == ctx->prof_events.size()) {
-                    hipEvent_t e0, e1;
-                    HIP_TRY(ctx, hipEventCreate(&e0));
-                    HIP_TRY(ctx, hipEventCreate(&e1));
-                    ctx->prof_events.emplace_back(e0, e1);
-                }
-                HIP_TRY(ctx, hipEventRecord(ctx->prof_events[ctx->prof_used].first, ctx->stream));
-            }
+            if ((rc = prof_begin())) return rc;
             if (wave_matrix) {
                 a.col0 = col0 + (int)q0;   // pool columns, no composition sort
                 a.col1 = col0 + (int)q_end;
@@ -1122,8 +1199,7 @@ static int run_chain(msspe_ctx *ctx, ChemEntry *ce, const ChainRoute &route, con
             else if (row_stage) HIP_TRY(ctx, launch_pairs_row(a, ce->d_it, ctx->d_reasons, ctx->n_cu, ctx->stream));
             else if (int_stage) HIP_TRY(ctx, launch_pairs_int(a, ce->d_it, ctx->d_reasons, ctx->n_cu, ctx->stream));
             else HIP_TRY(ctx, launch_pairs_fast(a, ctx->stream, end1));
-            if (ctx->prof_on)
-                HIP_TRY(ctx, hipEventRecord(ctx->prof_events[ctx->prof_used++].second, ctx->stream));
+            if ((rc = prof_end())) return rc;
             pending += launch_pairs;
         }
     }
@@ -3454,6 +3530,30 @@ int msspe_host_bound_tables(const char *params_path, const msspe_chem *chem, flo
     info[5] = BoundTables::kReach;
     info[6] = IntTables::kValid;
     info[7] = pairs_bound_max_k();
+    return MSSPE_OK;
+}
+
+int msspe_host_bound_mirror_ok(const char *params_path, const msspe_chem *chem, float dg_threshold, int32_t *mirror_ok)
+{
+    // host only: ChemEntry::mirror_ok as chem_entry() would set it
+    if (!chem || !mirror_ok) return MSSPE_ERR_ARG;
+    *mirror_ok = 0;
+    auto tb = std::make_unique<NNTables>();
+    std::string err;
+    const std::string path = params_path && *params_path ? params_path : default_bundle_path();
+    if (!load_nn_tables(path, *tb, err)) return MSSPE_ERR_TABLES;
+    if (!(chem->dna_conc > 0) || chem->max_loop < 0 || chem->max_loop > 30) return MSSPE_ERR_ARG;
+    const ThalConsts c = make_dimer_consts(chem->mv, chem->dv, chem->dntp, chem->dna_conc, chem->temp_c,
+                                           chem->max_loop, false, dg_threshold);
+    auto pt = std::make_unique<PairTables>();
+    if (!build_pair_tables(*tb, c, *pt, err)) return MSSPE_ERR_TABLES;
+    auto ft = std::make_unique<FastTables>();
+    auto it = std::make_unique<IntTables>();
+    auto st = std::make_unique<SplitTables>();
+    const TableRoutes r = table_routes(*tb, *pt, chem->max_loop, *ft, *it, *st);
+    auto bt = std::make_unique<BoundTables>();
+    const bool ok = build_bound_tables(*ft, c, pairs_bound_max_k(), *bt) && r.row_ok;
+    *mirror_ok = ok && bt->mirror_ok ? 1 : 0;
     return MSSPE_OK;
 }
 

@@ -97,18 +97,33 @@ struct BoundTables {
     // traceback's 1e-5 e.u. equality tolerance per step (13 steps x 1e-5 x 373.15 K < 0.05 cal/mol).
     static constexpr int kMargin = kUnitInv;
     static constexpr int32_t kReach = 1 << 26;             // bounds every reachable |value| (checked by build_bound_tables)
-    static_assert(13 * 1e-5 * 373.15 + 1e-6 < (double)kMargin / kUnitInv, "the margin covers the traceback's tolerance");
+    // The mirrored first stage (square same-pool screens) uses the bound of (a, b) for (b, a) as well.  Swapping the strands
+    // maps every chain of (a, b) onto a chain of (b, a) whose terms are the swapped partners of its own; bound_mirror_ok()
+    // admits a table set only if every term equals its partner within kMirrorTol (real values, before rounding).  A
+    // chain of 13-mers has at most kMirrorTerms terms (2 end terms, 12 steps of at most 2, the initiation), so
+    //      LB(a, b) <= RB(a, b) <= RB(b, a) + kMirrorTerms kMirrorTol <= dG(b, a) + 27e-6     (RB: the real-number minimum)
+    // and that slack, too, comes out of the margin.
+    static constexpr double kMirrorTol = 1e-6;             // cal/mol
+    static constexpr int kMirrorTerms = 27;
+    static_assert(13 * 1e-5 * 373.15 + 1e-6 + kMirrorTerms * kMirrorTol < (double)kMargin / kUnitInv,
+                  "the margin covers the traceback's tolerance and the mirror's");
     // "not available" as in IntTables (kBig; anything at or above kValid is void)
     int32_t T[IntTables::kRows * 64];    // loop term of IntTables::T's layout: asymmetry and the step's salt term included
     int32_t g[FastTables::kCount];       // cell-side and end terms as they are; kWC: the stacked pair WITH the step's salt term
     int32_t init;                        // duplex initiation
     int32_t cut;                         // cull iff init + min over chains > cut: floor((g_cut + margin) * kUnitInv)
     int32_t usable, max_k;
+    int32_t mirror_ok;                   // bound_mirror_ok(): the bound of (a, b) may stand for (b, a)
 };
 // The exact values the integers above round down, for the tests: g of FastTables entry e (salt_steps: 0 or 1 salt
 // terms added), +inf where the tables hold none.
 double bound_term_exact(const FastTables &ft, const ThalConsts &c, int e, int salt_steps);
 // usable = 0 unless every reachable sum of max_k pairs stays below kReach, temp_k is within 0 .. 100 C and g_cut <= 0.
 bool build_bound_tables(const FastTables &ft, const ThalConsts &c, int max_k, BoundTables &out);
+// Every real-valued term the bound recurrence can use equals its strand-swapped partner within kMirrorTol (void entries
+// mirror void ones): left end <-> right end of the swapped context, stacked pair <-> the stack read from the other
+// strand, bulge and interior loops (l1, l2) <-> (l2, l1) with closing pairs and mismatch neighbours swapped, the
+// cell-side mismatch terms kTSc / kMMc <-> the predecessor-side terms they become.
+bool bound_mirror_ok(const FastTables &ft, const ThalConsts &c);
 
 }  // namespace msspe

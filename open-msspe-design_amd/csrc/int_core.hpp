@@ -178,6 +178,7 @@ struct IntArgs {
     const BoundTables *bt = nullptr;
     unsigned long long *bound_survivors = nullptr;   // += pairs the bound could not cull
     double *bound_plane = nullptr;                    // diagnostic form: the bound of every pair, nothing else is written
+    int mirror = 0;                                   // each unordered pair once: rows in sorted order, columns q >= p (launch_pairs_bound)
 };
 
 // A list entry whose pair needs the f64 kernels (an exact tie was met) carries this bit in .x;

@@ -137,7 +137,11 @@ bool pairs_row_tables_ok(const IntTables &it);   // host: may this chemistry run
 // above the cut is finished, every other pair is appended to a.overflow_list; *survivors += pairs it could not cull.
 // bound_plane != nullptr: the diagnostic form (the bound of every pair in cal/mol, nothing else is written).
 hipError_t launch_pairs_bound(const PairKernelArgs &a, const IntTables *it, const BoundTables *bt,
-                              unsigned long long *survivors, double *bound_plane, int n_cu, hipStream_t stream);
+                              unsigned long long *survivors, double *bound_plane, int n_cu, hipStream_t stream,
+                              bool mirror = false);
+// mirror: a square same-pool screen under strand-symmetric tables.  a.row0 .. a.row1 are positions in the SORTED order like
+// the columns (row p = cols_sorted[p], pool index perm[p]), a.col0 = 0, a.col1 = the pool; row p screens the sorted
+// columns q >= p only, and a pair that is not culled is appended in both orders (once on the diagonal).
 int pairs_bound_max_k();
 hipError_t pairs_row_lds_reads_zero(hipStream_t stream, int n_cu, bool *ok);   // does this device read 0 beyond a block's LDS allocation?
 // List mode of the integer stage: retries the pairs of in_list that carry no "needs f64" mark (bit

@@ -629,6 +629,47 @@ double bound_term_exact(const FastTables &ft, const ThalConsts &c, int e, int sa
     return (double)ft.H[e] - c.temp_k * (ft.S[e] + salt_steps * c.salt);
 }
 
+bool bound_mirror_ok(const FastTables &ft, const ThalConsts &c)
+{
+    typedef FastTables F;
+    // equal within kMirrorTol, or void on both sides
+    auto same = [](double x, double y) {
+        if (std::isinf(x) || std::isinf(y)) return std::isinf(x) && std::isinf(y);
+        return std::fabs(x - y) <= BoundTables::kMirrorTol;
+    };
+    auto term = [&](int e, int salt_steps) { return bound_term_exact(ft, c, e, salt_steps); };
+    // a left end term <-> the right end term of the swapped context (pair complemented, outer bases exchanged)
+    for (int a = 0; a < 4; ++a)
+        for (int oa = 0; oa < 5; ++oa)
+            for (int ob = 0; ob < 5; ++ob)
+                if (!same(term(F::kEndL + a * 25 + oa * 5 + ob, 0), term(F::kEndR + (3 - a) * 25 + ob * 5 + oa, 0))) return false;
+    // a stacked pair x -> y <-> the stacked pair read from the other strand
+    for (int x = 0; x < 4; ++x)
+        for (int y = 0; y < 4; ++y)
+            if (!same(term(F::kWC + x * 4 + y, 1), term(F::kWC + (3 - y) * 4 + (3 - x), 1))) return false;
+    // a bulge of either strand (one entry for both: l1 <-> l2 is the same size) with its closing pairs swapped
+    for (int ac = 0; ac < 4; ++ac)
+        for (int sz = 1; sz <= F::kMaxSz; ++sz)
+            for (int ap = 0; ap < 4; ++ap)
+                if (!same(term(F::kBU + ac * F::kBUStride + sz * 4 + ap, 1), term(F::kBU + (3 - ap) * F::kBUStride + sz * 4 + (3 - ac), 1)))
+                    return false;
+    // a 1 x 1 or interior loop (l1, l2) <-> (l2, l1): the size and |l1 - l2| stay; the predecessor-side mismatch term
+    // (folded into NB with the size term) becomes the cell-side term and the cell-side term (kMMc / kTSc) the
+    // predecessor-side one.  po = a_p | n1 << 2 | n2 << 4 names the same three bases as ci = (a_p * 4 + n1) * 4 + n2.
+    auto ci_of = [](int po) { return ((po & 3) * 4 + ((po >> 2) & 3)) * 4 + (po >> 4); };
+    for (int sz = 2; sz <= F::kMaxSz; ++sz) {
+        const int side = sz == 2 ? F::kMMc : F::kTSc;
+        for (int po = 0; po < 64; ++po)
+            for (int pq = 0; pq < 64; ++pq) {   // pq: the cell's three bases, written as the po they become
+                const double x = term(F::kNB + (sz - 2) * 64 + po, 1), y = term(side + ci_of(pq), 0);
+                const double xm = term(F::kNB + (sz - 2) * 64 + pq, 1), ym = term(side + ci_of(po), 0);
+                const bool v = std::isinf(x) || std::isinf(y), vm = std::isinf(xm) || std::isinf(ym);
+                if (v != vm || (!v && std::fabs((x + y) - (xm + ym)) > BoundTables::kMirrorTol)) return false;
+            }
+    }
+    return true;
+}
+
 bool build_bound_tables(const FastTables &ft, const ThalConsts &c, int max_k, BoundTables &out)
 {
     typedef BoundTables B;
@@ -683,6 +724,7 @@ bool build_bound_tables(const FastTables &ft, const ThalConsts &c, int max_k, Bo
     }
     out.usable = ok ? 1 : 0;
     out.max_k = max_k;
+    out.mirror_ok = ok && bound_mirror_ok(ft, c) ? 1 : 0;
     return ok;
 }
 

@@ -861,9 +861,10 @@ static __device__ __forceinline__ void build_bound_table(SharedRow &sh, const In
 }
 
 // One lock-step DP of the wave: lane = (row, col), all lanes share `row`.
+// twin (BOUND, mirror mode only): the pair stands for (col, row) as well -- what is appended is appended in both orders.
 template <int NS, bool BOUND = false>
 static __device__ __forceinline__ void wave_pairs_row(SharedRow &sh, const IntArgs &a, int row, int col, uint64_t pa,
-                                               uint64_t pb, bool inside)
+                                               uint64_t pb, bool inside, bool twin = false)
 {
     const int lane = threadIdx.x & 63;
     SeqPair q;
@@ -945,7 +946,8 @@ static __device__ __forceinline__ void wave_pairs_row(SharedRow &sh, const IntAr
             } else {
                 const bool survivor = active & (lb <= a.bt->cut);   // a culled pair is finished: no bit, no count
                 const unsigned long long sm = __ballot(survivor);
-                if (lane == 0 && sm) atomicAdd(a.bound_survivors, (unsigned long long)__popcll(sm));
+                const unsigned long long sm2 = __ballot(survivor & twin);   // ordered pairs: a mirrored survivor counts for both
+                if (lane == 0 && sm) atomicAdd(a.bound_survivors, (unsigned long long)(__popcll(sm) + __popcll(sm2)));
                 spill |= survivor;
             }
         }
@@ -957,8 +959,9 @@ static __device__ __forceinline__ void wave_pairs_row(SharedRow &sh, const IntAr
                     spill ? -INFINITY : INFINITY;
         } else if (spill && a.f.ovf_list) {   // survivors and size hand-overs alike: the list stages answer them exactly
                                               // (no list: the probe launch of option pair_bound = auto, which only counts)
-            const uint32_t at = atomicAdd(a.f.ovf_count, 1u);
+            const uint32_t at = atomicAdd(a.f.ovf_count, twin ? 2u : 1u);
             if (at < a.f.ovf_cap) a.f.ovf_list[at] = make_uint2((unsigned)row | flag, (unsigned)col);
+            if (twin && at + 1u < a.f.ovf_cap) a.f.ovf_list[at + 1u] = make_uint2((unsigned)col | flag, (unsigned)row);
         }
         return;
     }
@@ -1128,17 +1131,35 @@ static __device__ __forceinline__ void kernel_body(const IntArgs &a)
         __syncthreads();
         const unsigned item = (unsigned)sh.item;
         if (item >= n_items) break;   // block-uniform
-        const int row = a.f.row0 + (int)(item / (unsigned)n_seg), seg = (int)(item % (unsigned)n_seg);
-        const uint64_t pa = a.f.pool[row];
-        if (row != built_row) {
+        int row = a.f.row0 + (int)(item / (unsigned)n_seg);
+        const int seg = (int)(item % (unsigned)n_seg);
+        unsigned g_lo = (unsigned)seg * kSegGroups;
+        const unsigned g_hi = min((unsigned)ncolg, g_lo + (unsigned)kSegGroups);
+        // Mirror mode (BOUND only; launch_pairs_bound): row p of the SORTED order screens the sorted columns q >= p.
+        // Segments wholly left of the row's own column group are not run (block-uniform, before the table build), and
+        // the row's first segment starts at that group.
+        const bool mirror = BOUND && a.mirror != 0;
+        const int row_q = row;   // mirror: the row's own sorted column
+        uint64_t pa;
+        if (mirror) {
+            const unsigned own = (unsigned)(row_q - a.f.col0) >> 6;
+            if (g_hi <= own) {
+                __syncthreads();   // every thread has read sh.item before thread 0 writes the next one
+                continue;
+            }
+            g_lo = max(g_lo, own);
+            pa = a.f.cols_sorted[row_q];
+            row = (int)a.f.perm[row_q];   // the pool index, as the hand-over list holds it
+        } else {
+            pa = a.f.pool[row];
+        }
+        if (row_q != built_row) {
             const unsigned lenmask = (1u << (2 * a.f.k)) - 1u;
             if constexpr (BOUND) build_bound_table(sh, a, (unsigned)pa & lenmask);
             else build_row_table(sh, a, (unsigned)pa & lenmask);
-            built_row = row;
+            built_row = row_q;
         }
         __syncthreads();
-        const unsigned g_lo = (unsigned)seg * kSegGroups;
-        const unsigned g_hi = min((unsigned)ncolg, g_lo + (unsigned)kSegGroups);
         for (;;) {
             unsigned grp = 0;
             if (lane == 0) grp = atomicAdd(&sh.next_group, 1u);
@@ -1147,10 +1168,10 @@ static __device__ __forceinline__ void kernel_body(const IntArgs &a)
             // (the fetch relies on the whole wave arriving here together: wave_pairs_row returns only through
             // wave-uniform branches -- keep it that way, or a lane runs ahead of the readfirstlane)
             const int cq = a.f.col0 + (int)grp * 64 + lane;
-            const bool inside = cq < a.f.col1;
+            const bool inside = cq < a.f.col1 && !(mirror && cq < row_q);   // (the row's own group: the lanes left of the diagonal)
             const uint64_t pb = a.f.cols_sorted[inside ? cq : a.f.col0];
             const int col = (int)a.f.perm[inside ? cq : a.f.col0];
-            wave_pairs_row<NS, BOUND>(sh, a, row, col, pa, pb, inside);
+            wave_pairs_row<NS, BOUND>(sh, a, row, col, pa, pb, inside, mirror && cq != row_q);
         }
         __syncthreads();   // every wave is done with the table (and with sh.item) before the next item
     }
@@ -1327,9 +1348,11 @@ int pairs_bound_max_k() { return Row13::kRowK; }
 // (nothing is written for it) or appended to a.overflow_list.  bound_plane != nullptr: the diagnostic form, which writes
 // the bound of every pair of the block (cal/mol; +inf: no chain; -inf: not bounded here) and nothing else.
 hipError_t launch_pairs_bound(const PairKernelArgs &a, const IntTables *it, const BoundTables *bt,
-                              unsigned long long *survivors, double *bound_plane, int n_cu, hipStream_t stream)
+                              unsigned long long *survivors, double *bound_plane, int n_cu, hipStream_t stream, bool mirror)
 {
     if (a.k > Row13::kRowK || a.k < 2 || !bt || (!survivors && !bound_plane)) return hipErrorInvalidValue;
+    // mirror: rows are sorted positions and a row's columns start at itself, so the rows must lie inside the columns
+    if (mirror && (bound_plane || a.col0 != 0 || a.row0 < 0 || a.row1 > a.col1)) return hipErrorInvalidValue;
     IntArgs x;
     FastArgs &f = x.f;
     f.ft = a.ft;
@@ -1355,6 +1378,7 @@ hipError_t launch_pairs_bound(const PairKernelArgs &a, const IntTables *it, cons
     x.bt = bt;
     x.bound_survivors = survivors;
     x.bound_plane = bound_plane;
+    x.mirror = mirror ? 1 : 0;
     const long ncolg = (a.col1 - a.col0 + 63) / 64;
     const long items = ((ncolg + Row13::kSegGroups - 1) / Row13::kSegGroups) * (long)(a.row1 - a.row0);
     if (items <= 0) return hipSuccess;

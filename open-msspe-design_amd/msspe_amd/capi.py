@@ -16,7 +16,7 @@ EXPORTS = [
     "msspe_last_error", "msspe_version", "msspe_set_option", "msspe_get_info", "msspe_kmer_trace", "msspe_set_stream", "msspe_reset_stream",
     "msspe_synchronize",
     "msspe_pack_oligos", "msspe_unpack_oligo", "msspe_cross_dimer_dev", "msspe_cross_dimer",
-    "msspe_cross_dimer_edges_dev", "msspe_cross_dimer_edges", "msspe_cross_dimer_bound_dev", "msspe_host_bound_tables",
+    "msspe_cross_dimer_edges_dev", "msspe_cross_dimer_edges", "msspe_cross_dimer_bound_dev", "msspe_host_bound_tables", "msspe_host_bound_mirror_ok",
     "msspe_cross_dimer_ab_dev", "msspe_cross_dimer_ab_edges_dev", "msspe_cross_dimer_ab", "msspe_cross_dimer_ab_edges",
     "msspe_cross_dimer_edges_mixed",
     "msspe_cross_dimer_end_dev", "msspe_cross_dimer_end", "msspe_cross_dimer_end_edges_dev", "msspe_cross_dimer_end_edges",
@@ -188,6 +188,7 @@ def load_library() -> C.CDLL:
     L.msspe_cross_dimer_bound_dev.argtypes = [vp, u64p, C.c_int, C.c_int, C.POINTER(Chem), C.c_float,
                                               C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.msspe_host_bound_tables.argtypes = [C.c_char_p, C.POINTER(Chem), C.c_float, vp, vp, C.POINTER(C.c_int32)]
+    L.msspe_host_bound_mirror_ok.argtypes = [C.c_char_p, C.POINTER(Chem), C.c_float, C.POINTER(C.c_int32)]
     L.msspe_cross_dimer_ab_dev.argtypes = [vp, u64p, C.c_int, C.c_int, u64p, C.c_int, C.c_int, C.POINTER(Chem),
                                            C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     L.msspe_cross_dimer_ab_edges_dev.argtypes = [vp, u64p, C.c_int, C.c_int, u64p, C.c_int, C.c_int, C.POINTER(Chem),
@@ -385,6 +386,18 @@ def host_bound_tables(params_path: str | None = None, chem: Chem | None = None, 
         raise MsspeError(rc, f"msspe_host_bound_tables({params_path})")
     keys = ("usable", "init", "cut", "unit_inv", "margin", "reach", "void", "max_k")
     return {"g": g, "T": T, **dict(zip(keys, list(info)))}
+
+
+def host_bound_mirror_ok(params_path: str | None = None, chem: Chem | None = None, threshold: float = -9000.0) -> bool:
+    """May the bound first stage fill each unordered pair of a square screen once under these tables (option
+    pair_mirror; no device needed)?  msspe_host_bound_mirror_ok."""
+    ok = C.c_int32(0)
+    chem = chem or Chem.ntthal()
+    rc = load_library().msspe_host_bound_mirror_ok(str(params_path).encode() if params_path else None, C.byref(chem),
+                                                   C.c_float(threshold), C.byref(ok))
+    if rc:
+        raise MsspeError(rc, f"msspe_host_bound_mirror_ok({params_path})")
+    return bool(ok.value)
 
 
 def _seed_words(seed, k: int) -> np.ndarray | None:
@@ -1144,6 +1157,8 @@ class Engine:
         out["needed_f64"] = int(v[8])
         # pairs the bound first stage (option pair_bound) could not cull and handed to list 0; not part of "deferred"
         out["bound_survivors"] = self.info("bound_survivors")
+        # ordered pairs a mirrored bound stage (option pair_mirror) answered or handed on without a fill of their own
+        out["bound_mirrored"] = self.info("bound_mirrored")
         return out
 
     # ---- stage B ---------------------------------------------------------------------------
