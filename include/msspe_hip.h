@@ -606,6 +606,33 @@ int msspe_kmer_candidates_both_seeded_packed_dev(msspe_ctx *ctx, const uint64_t 
                                                  const uint64_t *seed_rev, int n_rev_seed, uint64_t *words_fwd,
                                                  uint32_t *freq_fwd, int *n_fwd, uint64_t *words_rev,
                                                  uint32_t *freq_rev, int *n_rev, int capacity);
+/* Stage A with words it must never pick (engine extension; the other half of repairing a panel: keep what passed
+ * the later filters, ban what failed, let the greedy loop fill the holes).  An EXCLUDED word is treated as if it
+ * occurred in no search window of the direction: it is taken out of every window's k-mer list before the index is
+ * built, so it has no postings and no count, is in no segment's word list, and can be neither a winner nor a seed.
+ * Every other word keeps its own occurrences (masking the alignment would also take the overlapping k-mers), and the
+ * first-occurrence rule per window (main.rs:168) is not affected.  exclude: n_exclude HOST packed words in the
+ * direction's key space, exactly as seeds are given; order and duplicates do not matter, a word absent from the
+ * index does nothing, a word in both lists is excluded (the seed is then absent).  n_exclude == 0 is the seeded call
+ * bit for bit, launch for launch; both lists empty (or sets == NULL) is the unseeded call.  When everything is
+ * excluded the call returns MSSPE_OK with *n_out = 0.  The loop, its stop rules, the frequencies (live counts) and
+ * max_iterations are unchanged.  MSSPE_ERR_ARG: a NULL list with a positive count, a negative count, or a word
+ * with bits above 2 k in either list; the context stays usable.  Everything else as the seeded siblings. */
+typedef struct {
+    const uint64_t *seed;    int n_seed;      /* as msspe_kmer_candidates_seeded */
+    const uint64_t *exclude; int n_exclude;   /* HOST packed words, the direction's key space */
+} msspe_kmer_sets;
+int msspe_kmer_candidates_sets(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len,
+                               const msspe_kmer_opt *opt, int direction, const msspe_kmer_sets *sets,
+                               uint64_t *words_out, uint32_t *freq_out, int capacity, int *n_out);
+int msspe_kmer_candidates_sets_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
+                                          const msspe_kmer_opt *opt, int direction, const msspe_kmer_sets *sets,
+                                          uint64_t *words_out, uint32_t *freq_out, int capacity, int *n_out);
+int msspe_kmer_candidates_both_sets_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
+                                               const msspe_kmer_opt *opt, const msspe_kmer_sets *fwd,
+                                               const msspe_kmer_sets *rev, uint64_t *words_fwd, uint32_t *freq_fwd,
+                                               int *n_fwd, uint64_t *words_rev, uint32_t *freq_rev, int *n_rev,
+                                               int capacity);
 int msspe_segment_coverage_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
                                       const msspe_kmer_opt *opt, const uint64_t *fwd_words, int n_fwd,
                                       const uint64_t *rev_words, int n_rev, uint8_t *hit_out);

@@ -2127,82 +2127,62 @@ int msspe_oligo_stats(msspe_ctx *ctx, const char *pool_ascii, int n, int k,
     return rc;
 }
 
-// stage A on a device byte alignment, optionally seeded (msspe_kmer_candidates_dev / _seeded)
-static int kmer_candidates_dev(msspe_ctx *ctx, const uint8_t *d_seqs, int n_seq, size_t seq_len,
-                               const msspe_kmer_opt *opt, int direction, const uint64_t *seed, int n_seed,
-                               uint64_t *words_out, uint32_t *freq_out, int capacity, int *n_out)
+// Stage A's one internal path: every msspe_kmer_candidates* entry point is a thin caller of kmer_run (one direction
+// on the context's stream), kmer_run_host (the same behind an upload of host rows) or kmer_run_both.  sets == NULL:
+// both lists empty.
+static const msspe_kmer_sets kNoSets = {nullptr, 0, nullptr, 0};
+
+static bool sets_ok(const msspe_kmer_sets *s)
+{
+    return !s || (s->n_seed >= 0 && s->n_exclude >= 0 && (s->n_seed == 0 || s->seed) && (s->n_exclude == 0 || s->exclude));
+}
+
+static int kmer_run(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t seq_len, const msspe_kmer_opt *opt,
+                    int direction, const msspe_kmer_sets *sets, uint64_t *words_out, uint32_t *freq_out, int capacity,
+                    int *n_out)
 {
     if (!ctx) return MSSPE_ERR_ARG;
-    if (!d_seqs || !opt || !words_out || !freq_out || !n_out || capacity < 0 || n_seed < 0 || (n_seed && !seed))
+    if ((!view.ascii && !view.packed) || !opt || !words_out || !freq_out || !n_out || capacity < 0 || !sets_ok(sets))
         return fail(ctx, MSSPE_ERR_ARG, "null argument");
+    if (!sets) sets = &kNoSets;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::string err;
-    const SeqView view{d_seqs, nullptr, seq_len};
-    const int rc = ctx->kmer.run(view, n_seq, seq_len, *opt, direction, words_out, freq_out,
-                                 capacity, n_out, ctx->stream, err, seed, n_seed);
+    const int rc = ctx->kmer.run(view, n_seq, seq_len, *opt, direction, words_out, freq_out, capacity, n_out,
+                                 ctx->stream, err, sets->seed, sets->n_seed, sets->exclude, sets->n_exclude);
     if (rc) return fail(ctx, rc, err);
     return MSSPE_OK;
 }
 
-int msspe_kmer_candidates_dev(msspe_ctx *ctx, const uint8_t *d_seqs, int n_seq, size_t seq_len,
-                              const msspe_kmer_opt *opt, int direction, uint64_t *words_out,
-                              uint32_t *freq_out, int capacity, int *n_out)
-{
-    return kmer_candidates_dev(ctx, d_seqs, n_seq, seq_len, opt, direction, nullptr, 0, words_out, freq_out, capacity,
-                               n_out);
-}
-
-int msspe_kmer_candidates_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
-                                     const msspe_kmer_opt *opt, int direction, uint64_t *words_out,
-                                     uint32_t *freq_out, int capacity, int *n_out)
+static int kmer_run_host(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len, const msspe_kmer_opt *opt,
+                         int direction, const msspe_kmer_sets *sets, uint64_t *words_out, uint32_t *freq_out,
+                         int capacity, int *n_out)
 {
     if (!ctx) return MSSPE_ERR_ARG;
-    if (!d_packed || !opt || !words_out || !freq_out || !n_out || capacity < 0)
-        return fail(ctx, MSSPE_ERR_ARG, "null argument");
+    if (!sets_ok(sets)) return fail(ctx, MSSPE_ERR_ARG, "null seed or exclusion list");
+    if (!seqs || n_seq < 0) return fail(ctx, MSSPE_ERR_ARG, "null sequences");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    std::string err;
-    const SeqView view{nullptr, d_packed, seq_len};
-    const int rc = ctx->kmer.run(view, n_seq, seq_len, *opt, direction, words_out, freq_out,
-                                 capacity, n_out, ctx->stream, err);
-    if (rc) return fail(ctx, rc, err);
-    return MSSPE_OK;
+    uint8_t *d = nullptr;
+    const size_t bytes = (size_t)n_seq * seq_len;
+    HIP_TRY(ctx, hipMalloc((void **)&d, bytes ? bytes : 1));
+    hipError_t e = hipMemcpy(d, seqs, bytes, hipMemcpyHostToDevice);
+    int rc = e == hipSuccess ? kmer_run(ctx, SeqView{d, nullptr, seq_len}, n_seq, seq_len, opt, direction, sets,
+                                        words_out, freq_out, capacity, n_out)
+                             : hip_fail(ctx, e, "hipMemcpy");
+    (void)hipFree(d);
+    return rc;
 }
 
-int msspe_kmer_candidates_seeded_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
-                                            const msspe_kmer_opt *opt, int direction, const uint64_t *seed,
-                                            int n_seed, uint64_t *words_out, uint32_t *freq_out, int capacity,
-                                            int *n_out)
-{
-    if (!ctx) return MSSPE_ERR_ARG;
-    if (!d_packed || !opt || !words_out || !freq_out || !n_out || capacity < 0 || n_seed < 0 || (n_seed && !seed))
-        return fail(ctx, MSSPE_ERR_ARG, "null argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    std::string err;
-    const SeqView view{nullptr, d_packed, seq_len};
-    const int rc = ctx->kmer.run(view, n_seq, seq_len, *opt, direction, words_out, freq_out,
-                                 capacity, n_out, ctx->stream, err, seed, n_seed);
-    if (rc) return fail(ctx, rc, err);
-    return MSSPE_OK;
-}
-
-int msspe_kmer_candidates_both_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
-                                          const msspe_kmer_opt *opt, uint64_t *words_fwd, uint32_t *freq_fwd, int *n_fwd,
-                                          uint64_t *words_rev, uint32_t *freq_rev, int *n_rev, int capacity)
-{
-    return msspe_kmer_candidates_both_seeded_packed_dev(ctx, d_packed, n_seq, seq_len, opt, nullptr, 0, nullptr, 0,
-                                                        words_fwd, freq_fwd, n_fwd, words_rev, freq_rev, n_rev, capacity);
-}
-
-int msspe_kmer_candidates_both_seeded_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
-                                                 const msspe_kmer_opt *opt, const uint64_t *seed_fwd, int n_fwd_seed,
-                                                 const uint64_t *seed_rev, int n_rev_seed, uint64_t *words_fwd,
-                                                 uint32_t *freq_fwd, int *n_fwd, uint64_t *words_rev,
-                                                 uint32_t *freq_rev, int *n_rev, int capacity)
+static int kmer_run_both(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len, const msspe_kmer_opt *opt,
+                         const msspe_kmer_sets *fwd, const msspe_kmer_sets *rev, uint64_t *words_fwd,
+                         uint32_t *freq_fwd, int *n_fwd, uint64_t *words_rev, uint32_t *freq_rev, int *n_rev,
+                         int capacity)
 {
     if (!ctx) return MSSPE_ERR_ARG;
     if (!d_packed || !opt || !words_fwd || !freq_fwd || !n_fwd || !words_rev || !freq_rev || !n_rev || capacity < 0 ||
-        n_fwd_seed < 0 || n_rev_seed < 0 || (n_fwd_seed && !seed_fwd) || (n_rev_seed && !seed_rev))
+        !sets_ok(fwd) || !sets_ok(rev))
         return fail(ctx, MSSPE_ERR_ARG, "null argument");
+    if (!fwd) fwd = &kNoSets;
+    if (!rev) rev = &kNoSets;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (!ctx->stream_rev) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->stream_rev, hipStreamNonBlocking));
     if (!ctx->ev_rev) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_rev, hipEventDisableTiming));
@@ -2214,21 +2194,84 @@ int msspe_kmer_candidates_both_seeded_packed_dev(msspe_ctx *ctx, const uint64_t 
     int rc0 = MSSPE_OK, rc1 = MSSPE_OK;
     // The two directions are independent (main.rs:673-690 runs them one after the other); each is a chain of small
     // dependent launches with host round trips, so two host threads on two streams overlap them almost entirely.
-    std::thread rev([&]() {
+    std::thread rev_thread([&]() {
         if (hipSetDevice(ctx->device) != hipSuccess) {
             rc1 = MSSPE_ERR_DEVICE;
             err1 = "hipSetDevice failed";
             return;
         }
         rc1 = ctx->kmer_rev.run(view, n_seq, seq_len, *opt, 1, words_rev, freq_rev, capacity, n_rev, ctx->stream_rev, err1,
-                                seed_rev, n_rev_seed);
+                                rev->seed, rev->n_seed, rev->exclude, rev->n_exclude);
     });
     rc0 = ctx->kmer.run(view, n_seq, seq_len, *opt, 0, words_fwd, freq_fwd, capacity, n_fwd, ctx->stream, err0,
-                        seed_fwd, n_fwd_seed);
-    rev.join();
+                        fwd->seed, fwd->n_seed, fwd->exclude, fwd->n_exclude);
+    rev_thread.join();
     if (rc0) return fail(ctx, rc0, err0);
     if (rc1) return fail(ctx, rc1, "direction 1: " + err1);
     return MSSPE_OK;
+}
+
+int msspe_kmer_candidates_dev(msspe_ctx *ctx, const uint8_t *d_seqs, int n_seq, size_t seq_len,
+                              const msspe_kmer_opt *opt, int direction, uint64_t *words_out,
+                              uint32_t *freq_out, int capacity, int *n_out)
+{
+    return kmer_run(ctx, SeqView{d_seqs, nullptr, seq_len}, n_seq, seq_len, opt, direction, nullptr, words_out, freq_out,
+                    capacity, n_out);
+}
+
+int msspe_kmer_candidates_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
+                                     const msspe_kmer_opt *opt, int direction, uint64_t *words_out,
+                                     uint32_t *freq_out, int capacity, int *n_out)
+{
+    return kmer_run(ctx, SeqView{nullptr, d_packed, seq_len}, n_seq, seq_len, opt, direction, nullptr, words_out,
+                    freq_out, capacity, n_out);
+}
+
+int msspe_kmer_candidates_seeded_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
+                                            const msspe_kmer_opt *opt, int direction, const uint64_t *seed,
+                                            int n_seed, uint64_t *words_out, uint32_t *freq_out, int capacity,
+                                            int *n_out)
+{
+    const msspe_kmer_sets sets = {seed, n_seed, nullptr, 0};
+    return kmer_run(ctx, SeqView{nullptr, d_packed, seq_len}, n_seq, seq_len, opt, direction, &sets, words_out,
+                    freq_out, capacity, n_out);
+}
+
+int msspe_kmer_candidates_sets_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
+                                          const msspe_kmer_opt *opt, int direction, const msspe_kmer_sets *sets,
+                                          uint64_t *words_out, uint32_t *freq_out, int capacity, int *n_out)
+{
+    return kmer_run(ctx, SeqView{nullptr, d_packed, seq_len}, n_seq, seq_len, opt, direction, sets, words_out,
+                    freq_out, capacity, n_out);
+}
+
+int msspe_kmer_candidates_both_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
+                                          const msspe_kmer_opt *opt, uint64_t *words_fwd, uint32_t *freq_fwd, int *n_fwd,
+                                          uint64_t *words_rev, uint32_t *freq_rev, int *n_rev, int capacity)
+{
+    return kmer_run_both(ctx, d_packed, n_seq, seq_len, opt, nullptr, nullptr, words_fwd, freq_fwd, n_fwd, words_rev,
+                         freq_rev, n_rev, capacity);
+}
+
+int msspe_kmer_candidates_both_seeded_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
+                                                 const msspe_kmer_opt *opt, const uint64_t *seed_fwd, int n_fwd_seed,
+                                                 const uint64_t *seed_rev, int n_rev_seed, uint64_t *words_fwd,
+                                                 uint32_t *freq_fwd, int *n_fwd, uint64_t *words_rev,
+                                                 uint32_t *freq_rev, int *n_rev, int capacity)
+{
+    const msspe_kmer_sets fwd = {seed_fwd, n_fwd_seed, nullptr, 0}, rev = {seed_rev, n_rev_seed, nullptr, 0};
+    return kmer_run_both(ctx, d_packed, n_seq, seq_len, opt, &fwd, &rev, words_fwd, freq_fwd, n_fwd, words_rev,
+                         freq_rev, n_rev, capacity);
+}
+
+int msspe_kmer_candidates_both_sets_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
+                                               const msspe_kmer_opt *opt, const msspe_kmer_sets *fwd,
+                                               const msspe_kmer_sets *rev, uint64_t *words_fwd, uint32_t *freq_fwd,
+                                               int *n_fwd, uint64_t *words_rev, uint32_t *freq_rev, int *n_rev,
+                                               int capacity)
+{
+    return kmer_run_both(ctx, d_packed, n_seq, seq_len, opt, fwd, rev, words_fwd, freq_fwd, n_fwd, words_rev, freq_rev,
+                         n_rev, capacity);
 }
 
 size_t msspe_packed_row_words(size_t seq_len) { return SeqView::row_words(seq_len); }
@@ -2237,27 +2280,22 @@ int msspe_kmer_candidates(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t
                           const msspe_kmer_opt *opt, int direction, uint64_t *words_out,
                           uint32_t *freq_out, int capacity, int *n_out)
 {
-    return msspe_kmer_candidates_seeded(ctx, seqs, n_seq, seq_len, opt, direction, nullptr, 0, words_out, freq_out,
-                                        capacity, n_out);
+    return kmer_run_host(ctx, seqs, n_seq, seq_len, opt, direction, nullptr, words_out, freq_out, capacity, n_out);
 }
 
 int msspe_kmer_candidates_seeded(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len,
                                  const msspe_kmer_opt *opt, int direction, const uint64_t *seed, int n_seed,
                                  uint64_t *words_out, uint32_t *freq_out, int capacity, int *n_out)
 {
-    if (!ctx) return MSSPE_ERR_ARG;
-    if (n_seed < 0 || (n_seed && !seed)) return fail(ctx, MSSPE_ERR_ARG, "null seed list");
-    if (!seqs || n_seq < 0) return fail(ctx, MSSPE_ERR_ARG, "null sequences");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    uint8_t *d = nullptr;
-    const size_t bytes = (size_t)n_seq * seq_len;
-    HIP_TRY(ctx, hipMalloc((void **)&d, bytes ? bytes : 1));
-    hipError_t e = hipMemcpy(d, seqs, bytes, hipMemcpyHostToDevice);
-    int rc = e == hipSuccess ? kmer_candidates_dev(ctx, d, n_seq, seq_len, opt, direction, seed, n_seed,
-                                                   words_out, freq_out, capacity, n_out)
-                             : hip_fail(ctx, e, "hipMemcpy");
-    (void)hipFree(d);
-    return rc;
+    const msspe_kmer_sets sets = {seed, n_seed, nullptr, 0};
+    return kmer_run_host(ctx, seqs, n_seq, seq_len, opt, direction, &sets, words_out, freq_out, capacity, n_out);
+}
+
+int msspe_kmer_candidates_sets(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len,
+                               const msspe_kmer_opt *opt, int direction, const msspe_kmer_sets *sets,
+                               uint64_t *words_out, uint32_t *freq_out, int capacity, int *n_out)
+{
+    return kmer_run_host(ctx, seqs, n_seq, seq_len, opt, direction, sets, words_out, freq_out, capacity, n_out);
 }
 
 int msspe_segment_coverage_dev(msspe_ctx *ctx, const uint8_t *d_seqs, int n_seq, size_t seq_len,

@@ -2159,6 +2159,69 @@ __global__ void __launch_bounds__(1024) k_cover_multi(const PickState *ps, const
     }
 }
 
+// Exclusions (a run that must never pick certain words): between the extraction and the sort, every extracted key
+// found in the sorted, distinct exclusion list becomes the sentinel -- what k_extract writes for an invalid or a
+// repeated window position -- so the word has no postings, no count and no place in any segment's word list, while
+// the overlapping k-mers keep theirs (masking the alignment would take them too).  A streaming pass: four
+// consecutive keys per lane (16- / 32-byte loads, as k_index), a store on a hit only.  A list of up to kExcludeLds
+// keys is staged in LDS by every block and bisected there (a fixed trip count: no divergence); a longer one is
+// bisected in global memory, where it stays in L2 next to the streamed keys.  Keys outside [first, last] of the
+// list -- the sentinels among them -- skip the bisection when all of a wave's are.
+constexpr int kExcludeLds = 4096;   // 16 KB of 32-bit keys, 32 KB of 64-bit ones: five blocks of 256 still share a CU's LDS
+
+template <class T, class Key>
+__device__ __forceinline__ bool in_sorted(const T *list, int n, Key key)   // n >= 1
+{
+    const T *base = list;
+    for (int len = n; len > 1;) {
+        const int half = len >> 1;
+        base += base[half - 1] < (T)key ? half : 0;
+        len -= half;
+    }
+    return *base == (T)key;
+}
+
+template <class Key>
+__global__ void __launch_bounds__(256) k_exclude(Key *key, size_t n, const uint64_t *excl, int n_excl, uint64_t sentinel)
+{
+    __shared__ Key list_sh[kExcludeLds];
+    const bool in_lds = n_excl <= kExcludeLds;   // block-uniform
+    if (in_lds) {
+        for (int i = threadIdx.x; i < n_excl; i += 256) list_sh[i] = (Key)excl[i];
+        __syncthreads();
+    }
+    const uint64_t lo = excl[0], hi = excl[n_excl - 1];
+    const size_t n_chunk = (n + 1023) / 1024;
+    for (size_t c = blockIdx.x; c < n_chunk; c += gridDim.x) {   // block-uniform
+        const size_t i0 = c * 1024 + 4 * (size_t)threadIdx.x;
+        Key v[4];
+        if (i0 + 4 <= n) {
+            if constexpr (sizeof(Key) == 4) {
+                const uint4 q = *reinterpret_cast<const uint4 *>(key + i0);
+                v[0] = q.x, v[1] = q.y, v[2] = q.z, v[3] = q.w;
+            } else {
+                const ulonglong2 q0 = *reinterpret_cast<const ulonglong2 *>(key + i0), q1 = *reinterpret_cast<const ulonglong2 *>(key + i0 + 2);
+                v[0] = q0.x, v[1] = q0.y, v[2] = q1.x, v[3] = q1.y;
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = i0 + j < n ? key[i0 + j] : (Key)sentinel;
+        }
+        bool range[4], any = false;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            range[j] = (uint64_t)v[j] >= lo && (uint64_t)v[j] <= hi;   // (the sentinel is above every list key)
+            any = any || range[j];
+        }
+        if (!__ballot(any)) continue;   // wave-uniform
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const bool hit = range[j] && (in_lds ? in_sorted(list_sh, n_excl, v[j]) : in_sorted(excl, n_excl, v[j]));
+            if (hit && i0 + j < n) key[i0 + j] = (Key)sentinel;
+        }
+    }
+}
+
 // Seeding (a run that extends a panel): the post-push update of main.rs:371-378 for every distinct seed word in the
 // index, once, before the first iteration -- its segments become covered, and the coverage of each distinct
 // partition among ALL its postings goes up by one.  One block per seed (the seeds are sorted and distinct): its word
@@ -2306,7 +2369,7 @@ void KmerStage::release()
     drop_loop_graph();
     if (pinned_) (void)hipHostFree(pinned_);
     pinned_ = nullptr;
-    for (int s = 0; s < 19; ++s) {
+    for (int s = 0; s < 20; ++s) {
         if (buf_[s]) (void)hipFree(buf_[s]);
         buf_[s] = nullptr;
         cap_[s] = 0;
@@ -2344,7 +2407,8 @@ hipError_t launch_pack_rows(const uint8_t *d_ascii, int n_rows, size_t row_len, 
 
 int KmerStage::run(const SeqView &d_seqs, int n_seq, size_t seq_len, const msspe_kmer_opt &opt,
                    int direction, uint64_t *words_out, uint32_t *freq_out, int capacity,
-                   int *n_out, hipStream_t stream, std::string &err, const uint64_t *seed, int n_seed)
+                   int *n_out, hipStream_t stream, std::string &err, const uint64_t *seed, int n_seed,
+                   const uint64_t *exclude, int n_exclude)
 {
     *n_out = 0;
     const int k = opt.kmer_size, W = opt.search_window_size;
@@ -2372,6 +2436,21 @@ int KmerStage::run(const SeqView &d_seqs, int n_seq, size_t seq_len, const msspe
     }
     std::sort(seed_keys.begin(), seed_keys.end());
     seed_keys.erase(std::unique(seed_keys.begin(), seed_keys.end()), seed_keys.end());
+    if (n_exclude < 0 || (n_exclude > 0 && !exclude)) {
+        err = "stage A: null exclusion list";
+        return MSSPE_ERR_ARG;
+    }
+    // the excluded words the same way: index keys, sorted and distinct (k_exclude bisects them)
+    std::vector<uint64_t> excl_keys((size_t)n_exclude);
+    for (int i = 0; i < n_exclude; ++i) {
+        if (exclude[i] >> (2 * k)) {
+            err = "stage A: excluded word " + std::to_string(i) + " has bits above 2k";
+            return MSSPE_ERR_ARG;
+        }
+        excl_keys[(size_t)i] = lex_to_packed(exclude[i], k);
+    }
+    std::sort(excl_keys.begin(), excl_keys.end());
+    excl_keys.erase(std::unique(excl_keys.begin(), excl_keys.end()), excl_keys.end());
     const long P = seq_len < (size_t)opt.segment_size
                        ? 0
                        : (long)((seq_len - (size_t)opt.segment_size) / (size_t)opt.overlap_size) + 1;
@@ -2388,7 +2467,7 @@ int KmerStage::run(const SeqView &d_seqs, int n_seq, size_t seq_len, const msspe
     int rc;
     // buffers: 0/1 keys, 2/3 vals, 4 the seeds (index keys), 5 first instances per index block and their scan, 6 kid_of_inst, 7 post, 8 post_off, 9 ukeys,
     // 10 count+tied, 11 ignored, 12 coverage+stamp, 13 status/out, 14 cub temp, 16 the candidate-list loop's
-    // PickState + per-word results (key, id, two partition bitmaps)
+    // PickState + per-word results (key, id, two partition bitmaps), 19 the excluded words (index keys)
     if ((rc = ensure(0, n_inst * 8, err)) || (rc = ensure(1, n_inst * 8, err)) ||
         (rc = ensure(3, n_inst * 4, err)) ||
         (rc = ensure(5, 2 * 4 * ((n_inst + kIndexBlock - 1) / kIndexBlock), err)) ||
@@ -2450,6 +2529,16 @@ int KmerStage::run(const SeqView &d_seqs, int n_seq, size_t seq_len, const msspe
         hipLaunchKernelGGL(k_extract<Key>, dim3(ext_grid), dim3(256), 0, stream, d_packed, seq_len, n_seg,
                            (int)P, opt.segment_size, opt.overlap_size, W, k, direction, per, ka);
         KM_TRY(hipGetLastError());
+        if (!excl_keys.empty()) {   // the excluded words leave the keys before the index sees them
+            int rc1;
+            if ((rc1 = ensure(19, sizeof(uint64_t) * excl_keys.size(), err))) return rc1;
+            KM_TRY(hipMemcpyAsync(buf_[19], excl_keys.data(), sizeof(uint64_t) * excl_keys.size(), hipMemcpyHostToDevice,
+                                  stream));
+            const unsigned ex_grid = (unsigned)std::min<size_t>((n_inst + 1023) / 1024, 2048);
+            hipLaunchKernelGGL(k_exclude<Key>, dim3(ex_grid), dim3(256), 0, stream, ka, n_inst, (const uint64_t *)buf_[19],
+                               (int)excl_keys.size(), sentinel);
+            KM_TRY(hipGetLastError());
+        }
         // stable radix sort on the 2k+1 key bits keeps ascending segment order; the values (instance numbers) are
         // not stored anywhere before the sort: a counting iterator supplies them
         const rocprim::counting_iterator<uint32_t> val_a(0u);

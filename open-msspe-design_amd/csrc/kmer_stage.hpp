@@ -36,9 +36,13 @@ public:
     // seed / n_seed (host, optional): packed words (msspe_pack_oligos) of the direction's key space, taken as
     // already picked -- their segments covered and their partitions' coverage bumped once each before the first
     // iteration (main.rs:371-378); order and duplicates do not matter, words absent from the index do nothing
+    // exclude / n_exclude (host, optional): packed words of the same key space that are treated as occurring in no
+    // search window -- taken out of the extracted keys before the index is built (k_exclude), so they have no
+    // postings, no count, and can be neither winners nor seeds; every other word keeps its own occurrences
     int run(const SeqView &seqs, int n_seq, size_t seq_len, const msspe_kmer_opt &opt,
             int direction, uint64_t *words_out, uint32_t *freq_out, int capacity, int *n_out,
-            hipStream_t stream, std::string &err, const uint64_t *seed = nullptr, int n_seed = 0);
+            hipStream_t stream, std::string &err, const uint64_t *seed = nullptr, int n_seed = 0,
+            const uint64_t *exclude = nullptr, int n_exclude = 0);
     // Segment coverage of a primer set (main.rs:518-594): hit_out[seq * P + partition] = 1 when the
     // segment's head window holds a forward primer or its tail window the reverse complement of a
     // reverse primer.  fwd_words / rev_words / hit_out: host buffers.
@@ -57,8 +61,8 @@ public:
     const std::vector<uint32_t> &trace() const { return trace_; }
 
 private:
-    void *buf_[19] = {};
-    size_t cap_[19] = {};
+    void *buf_[20] = {};
+    size_t cap_[20] = {};
     void *pinned_ = nullptr;   // the loop state's host copy (pinned: read back once per batch)
     bool use_graph_ = true;
     bool narrow_loop_ = true;

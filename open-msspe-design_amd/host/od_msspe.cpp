@@ -59,6 +59,9 @@ const OptSpec kOpts[] = {
     {"--keep-all", "KEEP_ALL", OptSpec::Bool, OFF(keep_all)},
     {"--check-cross-dimers", "CHECK_CROSS_DIMERS", OptSpec::Bool, OFF(check_cross_dimers)},
     {"--existing-primers", "EXISTING_PRIMERS", OptSpec::Str, OFF(existing_primers)},
+    {"--exclude-primers", "EXCLUDE_PRIMERS", OptSpec::Str, OFF(exclude_primers)},
+    {"--rejected-out", "REJECTED_OUT", OptSpec::Str, OFF(rejected_out)},
+    {"--repick-rounds", "REPICK_ROUNDS", OptSpec::Int, OFF(repick_rounds)},
     {"--check-self-dimers", "CHECK_SELF_DIMERS", OptSpec::Bool, OFF(check_self_dimers)},
     {"--check-hairpin", "CHECK_HAIRPIN", OptSpec::Bool, OFF(check_hairpin)},
     {"--tm-stddev", "TM_STDDEV", OptSpec::Float, OFF(tm_stddev)},
@@ -142,7 +145,12 @@ std::string Args::usage()
          "count may rise up to M. The primers of --existing-primers are kept. One device; not with --keep-all true.\n"
          "--coverage-tm <C> adds a report of the segments the final primers hold at C: every match within\n"
          "--coverage-mismatches (last --coverage-3p-exact bases exact) is scored with thal (--coverage-thal any | end1)\n"
-         "against the strand the primer anneals to. One device.\n";
+         "against the strand the primer anneals to. One device.\n"
+         "--exclude-primers <CSV> names words stage A must never pick (direction and primers columns, as a panel).\n"
+         "--rejected-out <CSV> writes every candidate the run dropped (direction,name,primers,round,reason; reason is\n"
+         "stage_b, background, panel_dimer or cover); --exclude-primers reads such a file.\n"
+         "--repick-rounds <N> (0..16) repeats the selection up to N times: what passed is kept as a panel, what was\n"
+         "dropped is excluded, and stage A fills the holes. One device; not with --tubes.\n";
     return u;
 }
 
@@ -194,6 +202,16 @@ Args Args::parse(int argc, const char *const *argv)
         if (!a.existing_primers.empty())
             throw UsageError("error: '--tubes' cannot be combined with '--existing-primers': the tubes of the panel's "
                              "primers are unknown");
+    }
+    if (a.repick_rounds > 16)
+        throw UsageError("error: invalid value '" + std::to_string(a.repick_rounds) +
+                         "' for '--repick-rounds <...>'\n  [0 .. 16]");
+    if (a.repick_rounds > 0) {   // every round is a one-device panel extension, and a panel's tubes are unknown
+        if (a.tubes > 0)
+            throw UsageError("error: '--repick-rounds' cannot be combined with '--tubes': a later round extends the "
+                             "earlier rounds' primers, whose tubes it cannot change");
+        if (!a.devices.empty())
+            throw UsageError("error: '--repick-rounds' runs on one device and cannot be combined with '--devices'");
     }
     if (a.coverage_mismatches > a.kmer_size)
         throw UsageError("error: '--coverage-mismatches " + std::to_string(a.coverage_mismatches) +
@@ -504,7 +522,8 @@ std::vector<KmerFrequency> find_candidates_kmers(Engine &eng, const DeviceAlignm
 // reference gets from its two find_candidates_kmers calls, main.rs:673-690.
 std::pair<std::vector<KmerFrequency>, std::vector<KmerFrequency>> find_candidates_kmers_both(
     Engine &eng, const DeviceAlignment &aln, const ProgramConfig &cfg, int segment_size, int overlap_size, int window_size,
-    const std::vector<std::string> &seed_f, const std::vector<std::string> &seed_r)
+    const std::vector<std::string> &seed_f, const std::vector<std::string> &seed_r,
+    const std::vector<std::string> &excl_f, const std::vector<std::string> &excl_r)
 {
     if (overlap_size < window_size)   // main.rs:201-203
         throw Panic("Overlap windows size must be greater or equal than search windows size");
@@ -517,7 +536,22 @@ std::pair<std::vector<KmerFrequency>, std::vector<KmerFrequency>> find_candidate
     std::vector<uint32_t> freq[2] = {std::vector<uint32_t>((size_t)cap), std::vector<uint32_t>((size_t)cap)};
     int n[2] = {0, 0};
     int rc;
-    if (seed_f.empty() && seed_r.empty()) {
+    auto pack = [&](const std::vector<std::string> &list) {
+        std::string flat;
+        for (const auto &w : list) flat += w;
+        std::vector<uint64_t> packed(list.size() + 1);
+        if (!list.empty() && (rc = msspe_pack_oligos(flat.data(), (int)list.size(), opt.kmer_size, packed.data())))
+            eng.fail(rc);
+        return packed;
+    };
+    if (!excl_f.empty() || !excl_r.empty()) {
+        const std::vector<uint64_t> sf = pack(seed_f), sr = pack(seed_r), xf = pack(excl_f), xr = pack(excl_r);
+        const msspe_kmer_sets fwd = {sf.data(), (int)seed_f.size(), xf.data(), (int)excl_f.size()};
+        const msspe_kmer_sets rev = {sr.data(), (int)seed_r.size(), xr.data(), (int)excl_r.size()};
+        rc = msspe_kmer_candidates_both_sets_packed_dev(eng.ctx(), aln.device(), aln.rows(), aln.length(), &opt, &fwd,
+                                                        &rev, words[0].data(), freq[0].data(), &n[0], words[1].data(),
+                                                        freq[1].data(), &n[1], cap);
+    } else if (seed_f.empty() && seed_r.empty()) {
         rc = msspe_kmer_candidates_both_packed_dev(eng.ctx(), aln.device(), aln.rows(), aln.length(), &opt,
                                                    words[0].data(), freq[0].data(), &n[0], words[1].data(),
                                                    freq[1].data(), &n[1], cap);
@@ -773,10 +807,11 @@ std::set<std::string> panel_conflicts(Engine &eng, const std::vector<std::string
     return out;
 }
 
-std::pair<std::vector<std::string>, std::vector<std::string>> read_panel(const std::string &path, int kmer_size)
+std::pair<std::vector<std::string>, std::vector<std::string>> read_panel(const std::string &path, int kmer_size,
+                                                                         const char *option)
 {
     std::ifstream f(path, std::ios::binary);
-    if (!f) throw UsageError("error: cannot read '" + path + "' for '--existing-primers'");
+    if (!f) throw UsageError("error: cannot read '" + path + "' for '" + option + "'");
     std::pair<std::vector<std::string>, std::vector<std::string>> out;
     std::string line;
     size_t no = 0, col_dir = 0, col_primer = 2;
@@ -793,7 +828,7 @@ std::pair<std::vector<std::string>, std::vector<std::string>> read_panel(const s
     while (std::getline(f, line)) {
         ++no;
         if (!line.empty() && line.back() == '\r') line.pop_back();
-        const std::string where = "error: '--existing-primers' " + path + " line " + std::to_string(no) + ": ";
+        const std::string where = std::string("error: '") + option + "' " + path + " line " + std::to_string(no) + ": ";
         const auto fields = split(line);
         if (no == 1) {   // the header names the columns (direction,name,primers,gc,avg,std,tm)
             const auto d = std::find(fields.begin(), fields.end(), "direction");
@@ -1619,6 +1654,123 @@ std::vector<SequenceRecord> read_records(const std::string &path)
 }
 }  // namespace
 
+namespace {
+// A candidate one of the filters dropped (--rejected-out; what a re-pick round bans)
+struct Rejected {
+    std::string word;
+    uint8_t direction;
+    int round;
+    const char *reason;   // stage_b, background, panel_dimer, cover
+};
+// What one pass from stage A to the cover keeps and drops
+struct Selection {
+    std::vector<KmerStat> good_f, good_r;
+    std::vector<Rejected> rejected;
+    std::map<std::string, int> tubes;   // --tubes
+};
+
+// Stage A (started from the state in which the panel's words are picked already, never picking an excluded word),
+// stage B and its filter, the background drop, the screen against the panel and the cover (or the tubes): the
+// primers that survive, and every candidate dropped on the way with the step that dropped it.  The panel is never
+// dropped.  --keep-all true drops nothing.
+Selection select_primers(Engine &eng, const DeviceAlignment &aln, const Args &args, const ProgramConfig &cfg,
+                         const NtthalOptions &opts, std::unique_ptr<DeviceBackground> &background,
+                         const std::vector<std::string> &panel_f, const std::vector<std::string> &panel_r,
+                         const std::vector<std::string> &excl_f, const std::vector<std::string> &excl_r, int round,
+                         PhaseTimer &timer)
+{
+    Selection sel;
+    auto reject = [&](const KmerStat &s, const char *reason) {
+        sel.rejected.push_back({s.word, s.direction, round, reason});
+    };
+    const auto cand_both = find_candidates_kmers_both(eng, aln, cfg, args.window_size, args.overlap_size,
+                                                      args.search_windows_size, panel_f, panel_r, excl_f, excl_r);
+    const auto &cand_f = cand_both.first, &cand_r = cand_both.second;
+    timer.lap("stage A (both directions)");
+    const auto stats_f = get_kmer_stats(eng, cand_f, cfg);
+    const auto stats_r = get_kmer_stats(eng, cand_r, cfg);
+    auto prim_f = cfg.keep_all ? stats_f : filter_kmers(stats_f, cfg);
+    auto prim_r = cfg.keep_all ? stats_r : filter_kmers(stats_r, cfg);
+    if (!cfg.keep_all)
+        for (const auto &lists : {std::make_pair(&stats_f, &prim_f), std::make_pair(&stats_r, &prim_r)}) {
+            std::set<std::string> passed;
+            for (const auto &s : *lists.second) passed.insert(s.word);
+            for (const auto &s : *lists.first)
+                if (!passed.count(s.word)) reject(s, "stage_b");
+        }
+
+    timer.lap("stage B + filter");
+    // --background: uploaded once; candidates with too many off-target sites go before the cross-dimer screen, so the
+    // vertex cover never spends a removal on them (the panel is reported below but never dropped)
+    const int bg_mode = args.background_thal == "end1" ? 2 : 1;
+    if (!args.background.empty()) {
+        if (!background) {
+            const auto bg_records = read_records(args.background);
+            if (bg_records.empty()) throw Panic("No sequences found in the background file");
+            background.reset(new DeviceBackground(eng, bg_records));
+        }
+        if (args.max_background_sites >= 0 && !cfg.keep_all)
+            for (auto *list : {&prim_f, &prim_r}) {
+                std::vector<std::string> words;
+                for (const auto &s : *list) words.push_back(s.word);
+                // with --background-tm the limit applies to the sites that would hold the primer
+                std::vector<std::pair<uint64_t, uint64_t>> sites;
+                if (args.background_scored)
+                    (void)background->scored(words, args.background_mismatches, args.background_3p_exact,
+                                             ntthal_chem(opts), bg_mode, args.background_tm, sites,
+                                             args.background_flank);
+                else
+                    sites = background->sites(words, args.background_mismatches, args.background_3p_exact);
+                size_t kept = 0;
+                for (size_t i = 0; i < list->size(); ++i)
+                    if (sites[i].first + sites[i].second <= (uint64_t)args.max_background_sites)
+                        (*list)[kept++] = (*list)[i];
+                    else
+                        reject((*list)[i], "background");
+                list->resize(kept);
+            }
+        timer.lap("background upload + screen");
+    }
+    if (cfg.check_cross_dimers && !cfg.keep_all && (!panel_f.empty() || !panel_r.empty())) {
+        // a new primer that dimerises with the panel is dropped before the vertex cover (the panel stays whole)
+        std::vector<std::string> cands, all_panel(panel_f);
+        all_panel.insert(all_panel.end(), panel_r.begin(), panel_r.end());
+        for (const auto *list : {&prim_f, &prim_r})
+            for (const auto &s : *list) cands.push_back(s.word);
+        const auto bad = panel_conflicts(eng, cands, all_panel, opts);
+        for (auto *list : {&prim_f, &prim_r}) {
+            for (const auto &s : *list)
+                if (bad.count(s.word)) reject(s, "panel_dimer");
+            list->erase(std::remove_if(list->begin(), list->end(), [&](const KmerStat &s) { return bad.count(s.word) != 0; }),
+                        list->end());
+        }
+        timer.lap("panel cross-dimer screen");
+    }
+    std::vector<std::string> primers;
+    for (const auto &s : prim_f) primers.push_back(s.word);
+    for (const auto &s : prim_r) primers.push_back(s.word);
+    std::set<std::string> deleted;
+    if (args.tubes > 0) {   // --tubes: the primers that fit no tube are what is dropped
+        sel.tubes = conflict_tubes_on_device(eng, primers, opts, cfg, args.tubes);
+        for (const auto &kv : sel.tubes)
+            if (kv.second < 0) deleted.insert(kv.first);
+    } else {
+        deleted = args.cover_on_device == "true" ? conflict_cover_on_device(eng, primers, opts, cfg)
+                                                 : vertex_cover(primers, run_ntthal(eng, primers, opts, cfg));
+    }
+    for (const auto *list : {&prim_f, &prim_r})
+        for (const auto &p : *list) {
+            if (cfg.keep_all || !deleted.count(p.word))
+                (list == &prim_f ? sel.good_f : sel.good_r).push_back(p);
+            else
+                reject(p, "cover");
+        }
+
+    timer.lap("stage C + vertex cover");
+    return sel;
+}
+}  // namespace
+
 int run(const Args &args, std::string &stdout_text)
 {
     PhaseTimer timer;
@@ -1626,6 +1778,8 @@ int run(const Args &args, std::string &stdout_text)
     std::pair<std::vector<std::string>, std::vector<std::string>> panel;
     if (!args.existing_primers.empty()) panel = read_panel(args.existing_primers, args.kmer_size);
     const auto &panel_f = panel.first, &panel_r = panel.second;
+    std::pair<std::vector<std::string>, std::vector<std::string>> banned;   // --exclude-primers
+    if (!args.exclude_primers.empty()) banned = read_panel(args.exclude_primers, args.kmer_size, "--exclude-primers");
     std::vector<SequenceRecord> records;
     if (args.do_align == "true") {   // the reference's default (config.rs:131-138)
         const std::string aligned = align_sequences(args.input);
@@ -1670,79 +1824,51 @@ int run(const Args &args, std::string &stdout_text)
     Engine &eng = *eng_owner;
     const DeviceAlignment aln(eng, records);   // one upload for stage A (both directions) and the report
     timer.lap("engine + alignment upload");
-    // (with a panel: stage A starts from the state in which the panel's words are picked already)
-    const auto cand_both = find_candidates_kmers_both(eng, aln, cfg, args.window_size, args.overlap_size,
-                                                      args.search_windows_size, panel_f, panel_r);
-    const auto &cand_f = cand_both.first, &cand_r = cand_both.second;
-    timer.lap("stage A (both directions)");
-    const auto stats_f = get_kmer_stats(eng, cand_f, cfg);
-    const auto stats_r = get_kmer_stats(eng, cand_r, cfg);
-    auto prim_f = cfg.keep_all ? stats_f : filter_kmers(stats_f, cfg);
-    auto prim_r = cfg.keep_all ? stats_r : filter_kmers(stats_r, cfg);
-
-    timer.lap("stage B + filter");
-    // --background: uploaded once; candidates with too many off-target sites go before the cross-dimer screen, so the
-    // vertex cover never spends a removal on them (the panel is reported below but never dropped)
     const NtthalOptions opts{args.mv_conc, args.dv_conc, args.dntp_conc, args.dna_conc,
                              args.annealing_temp, args.delta_g_threshold};
     const int bg_mode = args.background_thal == "end1" ? 2 : 1;
-    std::unique_ptr<DeviceBackground> background;
-    if (!args.background.empty()) {
-        const auto bg_records = read_records(args.background);
-        if (bg_records.empty()) throw Panic("No sequences found in the background file");
-        background.reset(new DeviceBackground(eng, bg_records));
-        if (args.max_background_sites >= 0 && !cfg.keep_all)
-            for (auto *list : {&prim_f, &prim_r}) {
-                std::vector<std::string> words;
-                for (const auto &s : *list) words.push_back(s.word);
-                // with --background-tm the limit applies to the sites that would hold the primer
-                std::vector<std::pair<uint64_t, uint64_t>> sites;
-                if (args.background_scored)
-                    (void)background->scored(words, args.background_mismatches, args.background_3p_exact,
-                                             ntthal_chem(opts), bg_mode, args.background_tm, sites,
-                                             args.background_flank);
-                else
-                    sites = background->sites(words, args.background_mismatches, args.background_3p_exact);
-                size_t kept = 0;
-                for (size_t i = 0; i < list->size(); ++i)
-                    if (sites[i].first + sites[i].second <= (uint64_t)args.max_background_sites)
-                        (*list)[kept++] = (*list)[i];
-                list->resize(kept);
+    std::unique_ptr<DeviceBackground> background;   // --background: uploaded once, by the first round
+    // Round 0 is the run itself: the user's panel and exclusions.  --repick-rounds: round r >= 1 keeps what passed
+    // (the user's panel plus everything kept so far is its panel), bans what failed (the user's exclusions plus
+    // everything rejected so far) and lets stage A fill the holes; kept primers are never removed by a later round.
+    std::vector<Selection> rounds;
+    std::vector<std::string> kept_f(panel_f), kept_r(panel_r), ban_f(banned.first), ban_r(banned.second);
+    std::string rounds_text;
+    for (int round = 0;; ++round) {
+        Selection s = select_primers(eng, aln, args, cfg, opts, background, kept_f, kept_r, ban_f, ban_r, round, timer);
+        for (const auto &p : s.good_f) kept_f.push_back(p.word);
+        for (const auto &p : s.good_r) kept_r.push_back(p.word);
+        for (const auto &r : s.rejected) (r.direction == SEQ_DIR_FWD ? ban_f : ban_r).push_back(r.word);
+        const size_t n_new = s.good_f.size() + s.good_r.size(), n_rej = s.rejected.size();
+        rounds.push_back(std::move(s));
+        if (args.repick_rounds > 0)
+            rounds_text += "Re-pick round " + std::to_string(round) + ": " + std::to_string(n_new) + " new, " +
+                           std::to_string(n_rej) + " rejected, " +
+                           std::to_string(kept_f.size() + kept_r.size() - panel_f.size() - panel_r.size()) +
+                           " kept so far\n";
+        // a round that rejects nothing leaves no hole to fill; a re-pick round that finds no new primer ends the loop
+        if (round >= args.repick_rounds || n_rej == 0 || (round > 0 && n_new == 0)) break;
+    }
+    std::vector<KmerStat> good_f, good_r;   // the final lists: round 0's primers, then each round's
+    std::map<std::string, int> round_f, round_r;
+    for (size_t r = 0; r < rounds.size(); ++r) {
+        for (const auto &p : rounds[r].good_f) good_f.push_back(p), round_f[p.word] = (int)r;
+        for (const auto &p : rounds[r].good_r) good_r.push_back(p), round_r[p.word] = (int)r;
+    }
+    const std::map<std::string, int> &tubes = rounds[0].tubes;   // (--tubes runs one round)
+    if (!args.rejected_out.empty()) {
+        std::ofstream rej(args.rejected_out, std::ios::binary);
+        if (!rej) throw std::runtime_error("cannot write " + args.rejected_out);
+        rej << "direction,name,primers,round,reason\n";
+        size_t idx[2] = {0, 0};
+        for (const auto &sel : rounds)
+            for (const auto &r : sel.rejected) {
+                const bool fwd = r.direction == SEQ_DIR_FWD;
+                rej << (fwd ? "F" : "R") << ",Rejected_" << idx[fwd ? 0 : 1]++ << (fwd ? "_F," : "_R,") << r.word << ","
+                    << r.round << "," << r.reason << "\n";
             }
-        timer.lap("background upload + screen");
     }
-    if (cfg.check_cross_dimers && !cfg.keep_all && (!panel_f.empty() || !panel_r.empty())) {
-        // a new primer that dimerises with the panel is dropped before the vertex cover (the panel stays whole)
-        std::vector<std::string> cands, all_panel(panel_f);
-        all_panel.insert(all_panel.end(), panel_r.begin(), panel_r.end());
-        for (const auto *list : {&prim_f, &prim_r})
-            for (const auto &s : *list) cands.push_back(s.word);
-        const auto bad = panel_conflicts(eng, cands, all_panel, opts);
-        for (auto *list : {&prim_f, &prim_r})
-            list->erase(std::remove_if(list->begin(), list->end(), [&](const KmerStat &s) { return bad.count(s.word) != 0; }),
-                        list->end());
-        timer.lap("panel cross-dimer screen");
-    }
-    std::vector<std::string> primers;
-    for (const auto &s : prim_f) primers.push_back(s.word);
-    for (const auto &s : prim_r) primers.push_back(s.word);
-    std::map<std::string, int> tubes;   // --tubes: the primers that fit no tube are what is dropped
-    std::set<std::string> deleted;
-    if (args.tubes > 0) {
-        tubes = conflict_tubes_on_device(eng, primers, opts, cfg, args.tubes);
-        for (const auto &kv : tubes)
-            if (kv.second < 0) deleted.insert(kv.first);
-    } else {
-        deleted = args.cover_on_device == "true" ? conflict_cover_on_device(eng, primers, opts, cfg)
-                                                 : vertex_cover(primers, run_ntthal(eng, primers, opts, cfg));
-    }
-    std::vector<KmerStat> good_f, good_r;
-    for (const auto &p : prim_f)
-        if (cfg.keep_all || !deleted.count(p.word)) good_f.push_back(p);
-    for (const auto &p : prim_r)
-        if (cfg.keep_all || !deleted.count(p.word)) good_r.push_back(p);
 
-    timer.lap("stage C + vertex cover");
     std::string thin_text;   // --thin-panel: everything below sees the thinned lists
     if (args.thin_panel == "true") {
         thin_text = thin_panel_on_device(eng, aln, good_f, good_r, panel_f, panel_r, args.window_size, args.overlap_size,
@@ -1754,7 +1880,7 @@ int run(const Args &args, std::string &stdout_text)
     std::vector<KmerStat> rep_f = good_f, rep_r = good_r;
     for (const auto &w : panel_f) rep_f.push_back(KmerStat{w, SEQ_DIR_FWD});
     for (const auto &w : panel_r) rep_r.push_back(KmerStat{w, SEQ_DIR_REV});
-    stdout_text = coverage_report(eng, aln, rep_f, rep_r, records, args.window_size, args.overlap_size,
+    stdout_text = rounds_text + coverage_report(eng, aln, rep_f, rep_r, records, args.window_size, args.overlap_size,
                                   args.search_windows_size, args.kmer_size);
     if (args.coverage_mismatches > 0)   // the same primers (panel included), matched within N mismatches
         stdout_text += coverage_report_mm(eng, aln, rep_f, rep_r, records, args.window_size, args.overlap_size,
@@ -1806,7 +1932,19 @@ int run(const Args &args, std::string &stdout_text)
     }
     std::ofstream out(args.output, std::ios::binary);
     if (!out) throw std::runtime_error("cannot write " + args.output);
-    out << primers_csv(good_f, good_r, panel_f.size(), panel_r.size(), args.tubes > 0 ? &tubes : nullptr);
+    // round 0's rows, then each round's, numbered on (--thin-panel: the rows that are left of each)
+    size_t first_f = panel_f.size(), first_r = panel_r.size();
+    for (size_t r = 0; r < rounds.size(); ++r) {
+        std::vector<KmerStat> rows_f, rows_r;
+        for (const auto &p : good_f)
+            if (round_f.at(p.word) == (int)r) rows_f.push_back(p);
+        for (const auto &p : good_r)
+            if (round_r.at(p.word) == (int)r) rows_r.push_back(p);
+        const std::string csv = primers_csv(rows_f, rows_r, first_f, first_r, args.tubes > 0 ? &tubes : nullptr);
+        out << (r == 0 ? csv : csv.substr(csv.find('\n') + 1));
+        first_f += rows_f.size();
+        first_r += rows_r.size();
+    }
     timer.lap("coverage report + csv");
     return 0;
 }

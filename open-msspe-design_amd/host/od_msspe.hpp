@@ -53,6 +53,14 @@ struct Args {
     std::string devices;           // "0,1,2,...": the N^2 pair loop and stage B run on a group of devices (msspe_group_*)
     std::string params_path;       // Primer3 config directory; empty = bundled tables
     std::string existing_primers;  // a panel to extend: CSV in this tool's output format (direction and primers read)
+    // --exclude-primers FILE: words stage A must never pick (msspe_kmer_candidates_*sets*), read like a panel CSV
+    // (direction and primers; further columns ignored, so the file of --rejected-out can be given).  --rejected-out
+    // FILE: every candidate this run dropped, as direction,name,primers,round,reason (reason: stage_b, background,
+    // panel_dimer or cover).  --repick-rounds N (0..16): after the first pass, up to N more passes that keep what
+    // passed, ban what failed and let stage A fill the holes, each run like an --existing-primers run whose panel is
+    // the user's plus everything kept so far.  One device, not with --tubes.  0 / empty: nothing changes.
+    std::string exclude_primers, rejected_out;
+    int repick_rounds = 0;
     std::string cover_on_device = "false";   // "true": the screen and the vertex cover as one device call (msspe_conflict_cover)
     // --tubes N (1..64): instead of the vertex cover, the primers are split into at most N reaction tubes in which no
     // two primers conflict (msspe_conflict_tubes); the primers that fit no tube are dropped, the CSV gains a 1-based
@@ -203,13 +211,17 @@ private:
 std::vector<KmerFrequency> find_candidates_kmers(Engine &eng, const std::vector<SequenceRecord> &records,
                                                  uint8_t direction, const ProgramConfig &cfg,
                                                  int segment_size, int overlap_size, int window_size);
-// seed_f / seed_r (a panel being extended): words stage A takes as already picked, per direction
+// seed_f / seed_r (a panel being extended): words stage A takes as already picked, per direction;
+// excl_f / excl_r: words it must never pick
 std::pair<std::vector<KmerFrequency>, std::vector<KmerFrequency>> find_candidates_kmers_both(
     Engine &eng, const DeviceAlignment &aln, const ProgramConfig &cfg, int segment_size, int overlap_size, int window_size,
-    const std::vector<std::string> &seed_f = {}, const std::vector<std::string> &seed_r = {});
-// --existing-primers: the F and R primers of a panel CSV (direction, name, primers, ...); throws UsageError naming
-// the line when a primer is not kmer_size bases of ACGT or the direction is not F / R
-std::pair<std::vector<std::string>, std::vector<std::string>> read_panel(const std::string &path, int kmer_size);
+    const std::vector<std::string> &seed_f = {}, const std::vector<std::string> &seed_r = {},
+    const std::vector<std::string> &excl_f = {}, const std::vector<std::string> &excl_r = {});
+// --existing-primers (and --exclude-primers: `option` names the switch in the messages): the F and R primers of a
+// panel CSV (the header names the columns; direction and primers are read, the others ignored); throws UsageError
+// naming the line when a primer is not kmer_size bases of ACGT or the direction is not F / R
+std::pair<std::vector<std::string>, std::vector<std::string>> read_panel(const std::string &path, int kmer_size,
+                                                                         const char *option = "--existing-primers");
 std::vector<KmerFrequency> find_candidates_kmers(Engine &eng, const DeviceAlignment &aln, uint8_t direction,
                                                  const ProgramConfig &cfg, int segment_size,
                                                  int overlap_size, int window_size);

@@ -31,6 +31,7 @@ EXPORTS = [
     "msspe_kmer_candidates_both_packed_dev",
     "msspe_kmer_candidates_seeded", "msspe_kmer_candidates_seeded_packed_dev",
     "msspe_kmer_candidates_both_seeded_packed_dev",
+    "msspe_kmer_candidates_sets", "msspe_kmer_candidates_sets_packed_dev", "msspe_kmer_candidates_both_sets_packed_dev",
     "msspe_segment_coverage_packed_dev",
     "msspe_segment_coverage_mm", "msspe_segment_coverage_mm_dev", "msspe_segment_coverage_mm_packed_dev",
     "msspe_segment_coverage_thal", "msspe_segment_coverage_thal_dev", "msspe_segment_coverage_thal_packed_dev",
@@ -231,6 +232,12 @@ def load_library() -> C.CDLL:
     L.msspe_kmer_candidates_both_seeded_packed_dev.argtypes = [vp, vp, C.c_int, C.c_size_t, C.POINTER(KmerOpt),
                                                                vp, C.c_int, vp, C.c_int, vp, vp, C.POINTER(C.c_int),
                                                                vp, vp, C.POINTER(C.c_int), C.c_int]
+    L.msspe_kmer_candidates_sets.argtypes = [vp, vp, C.c_int, C.c_size_t, C.POINTER(KmerOpt), C.c_int,
+                                             C.POINTER(KmerSets), vp, vp, C.c_int, C.POINTER(C.c_int)]
+    L.msspe_kmer_candidates_sets_packed_dev.argtypes = L.msspe_kmer_candidates_sets.argtypes
+    L.msspe_kmer_candidates_both_sets_packed_dev.argtypes = [vp, vp, C.c_int, C.c_size_t, C.POINTER(KmerOpt),
+                                                             C.POINTER(KmerSets), C.POINTER(KmerSets), vp, vp,
+                                                             C.POINTER(C.c_int), vp, vp, C.POINTER(C.c_int), C.c_int]
     L.msspe_packed_row_words.restype = C.c_size_t
     L.msspe_packed_row_words.argtypes = [C.c_size_t]
     L.msspe_device_put_rows_packed.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_size_t,
@@ -400,20 +407,32 @@ def host_bound_mirror_ok(params_path: str | None = None, chem: Chem | None = Non
     return bool(ok.value)
 
 
-def _seed_words(seed, k: int) -> np.ndarray | None:
-    """A seed= list (strings of length k, ACGT) -> packed uint64 words; None when no seed was given."""
+def _seed_words(seed, k: int, what: str = "seed") -> np.ndarray | None:
+    """A seed= (or exclude=) list (strings of length k, ACGT) -> packed uint64 words; None when none was given."""
     if seed is None:
         return None
     seed = list(seed)
     for s in seed:
         if not isinstance(s, str) or len(s) != k:
-            raise ValueError(f"seed word {s!r} is not a string of length {k} (the k-mer size)")
+            raise ValueError(f"{what} word {s!r} is not a string of length {k} (the k-mer size)")
     if not seed:
         return np.zeros(0, dtype=np.uint64)
     try:
         return pack_oligos(seed)
     except MsspeError as e:
-        raise ValueError(f"seed words must be ACGT only: {e}") from None
+        raise ValueError(f"{what} words must be ACGT only: {e}") from None
+
+
+class KmerSets(C.Structure):
+    """msspe_kmer_sets: a direction's seed and exclusion lists (host packed words)."""
+    _fields_ = [("seed", C.c_void_p), ("n_seed", C.c_int), ("exclude", C.c_void_p), ("n_exclude", C.c_int)]
+
+
+def _kmer_sets(seed: np.ndarray | None, exclude: np.ndarray | None) -> KmerSets:
+    """The struct over two packed lists (None: empty); the arrays must outlive the call that reads it."""
+    return KmerSets(seed.ctypes.data if seed is not None and len(seed) else None, 0 if seed is None else len(seed),
+                    exclude.ctypes.data if exclude is not None and len(exclude) else None,
+                    0 if exclude is None else len(exclude))
 
 
 def _ascii(oligos):
@@ -1180,17 +1199,28 @@ class Engine:
     # ---- stage A ---------------------------------------------------------------------------
     def kmer_candidates(self, seqs: np.ndarray, opt: KmerOpt, direction: int,
                         device_ptr: int | None = None, n_seq: int | None = None,
-                        seq_len: int | None = None, capacity: int | None = None, *, seed=None):
+                        seq_len: int | None = None, capacity: int | None = None, *, seed=None, exclude=None):
         """seqs: uint8 (n_seq, L) host array (or pass device_ptr + shape).  Returns (words, freqs).
         capacity: size of the output buffers (default: max_iterations, which always suffices).
         seed: words (strings of length kmer_size, in the direction's key space) taken as already picked
-        (msspe_kmer_candidates_seeded; host sequences only)."""
+        (msspe_kmer_candidates_seeded; host sequences only).
+        exclude: words of the same form that must never be picked (msspe_kmer_candidates_sets; host sequences only)."""
         cap = max(1, opt.max_iterations if capacity is None else capacity)
         words = np.zeros(cap, dtype=np.uint64)
         freqs = np.zeros(cap, dtype=np.uint32)
         n_out = C.c_int(0)
         sw = _seed_words(seed, opt.kmer_size)
-        if sw is not None:
+        xw = _seed_words(exclude, opt.kmer_size, "exclude")
+        if xw is not None:
+            if device_ptr is not None:
+                raise ValueError("exclude= needs host sequences (or kmer_candidates_packed on a packed alignment)")
+            a = np.ascontiguousarray(seqs, dtype=np.uint8)
+            n_seq, seq_len = a.shape
+            sets = _kmer_sets(sw, xw)
+            self._check(self.L.msspe_kmer_candidates_sets(
+                self.ptr, a.ctypes.data, n_seq, seq_len, C.byref(opt), direction, C.byref(sets),
+                words.ctypes.data, freqs.ctypes.data, cap, C.byref(n_out)))
+        elif sw is not None:
             if device_ptr is not None:
                 raise ValueError("seed= needs host sequences (or kmer_candidates_packed on a packed alignment)")
             a = np.ascontiguousarray(seqs, dtype=np.uint8)
@@ -1233,15 +1263,22 @@ class Engine:
         self._check(self.L.msspe_device_free(self.ptr, C.c_void_p(device_ptr)))
 
     def kmer_candidates_packed(self, d_packed: int, n_seq: int, seq_len: int, opt: KmerOpt, direction: int,
-                               capacity: int | None = None, *, seed=None):
+                               capacity: int | None = None, *, seed=None, exclude=None):
         """Stage A on a packed alignment resident on the device (put_rows_packed).  Returns (words, freqs).
-        seed: as for kmer_candidates (msspe_kmer_candidates_seeded_packed_dev)."""
+        seed: as for kmer_candidates (msspe_kmer_candidates_seeded_packed_dev); exclude: words that must never be
+        picked (msspe_kmer_candidates_sets_packed_dev)."""
         cap = max(1, opt.max_iterations if capacity is None else capacity)
         words = np.zeros(cap, dtype=np.uint64)
         freqs = np.zeros(cap, dtype=np.uint32)
         n_out = C.c_int(0)
         sw = _seed_words(seed, opt.kmer_size)
-        if sw is not None:
+        xw = _seed_words(exclude, opt.kmer_size, "exclude")
+        if xw is not None:
+            sets = _kmer_sets(sw, xw)
+            self._check(self.L.msspe_kmer_candidates_sets_packed_dev(
+                self.ptr, C.c_void_p(d_packed), n_seq, seq_len, C.byref(opt), direction, C.byref(sets),
+                words.ctypes.data, freqs.ctypes.data, cap, C.byref(n_out)))
+        elif sw is not None:
             self._check(self.L.msspe_kmer_candidates_seeded_packed_dev(
                 self.ptr, C.c_void_p(d_packed), n_seq, seq_len, C.byref(opt), direction, sw.ctypes.data, len(sw),
                 words.ctypes.data, freqs.ctypes.data, cap, C.byref(n_out)))
@@ -1254,16 +1291,23 @@ class Engine:
 
 
 def _both(self, d_packed: int, n_seq: int, seq_len: int, opt: KmerOpt, capacity: int | None = None, *,
-          seed_fwd=None, seed_rev=None):
+          seed_fwd=None, seed_rev=None, exclude_fwd=None, exclude_rev=None):
     """Stage A, both directions of a packed alignment at once (msspe_kmer_candidates_both_packed_dev).
     Returns ((words, freqs) of direction 0, (words, freqs) of direction 1).  seed_fwd / seed_rev: each direction's
-    seed words, as for kmer_candidates (msspe_kmer_candidates_both_seeded_packed_dev)."""
+    seed words, as for kmer_candidates (msspe_kmer_candidates_both_seeded_packed_dev); exclude_fwd / exclude_rev: each
+    direction's words that must never be picked (msspe_kmer_candidates_both_sets_packed_dev)."""
     cap = max(1, opt.max_iterations if capacity is None else capacity)
     w = [np.zeros(cap, dtype=np.uint64) for _ in range(2)]
     f = [np.zeros(cap, dtype=np.uint32) for _ in range(2)]
     n = [C.c_int(0), C.c_int(0)]
     sf, sr = _seed_words(seed_fwd, opt.kmer_size), _seed_words(seed_rev, opt.kmer_size)
-    if sf is not None or sr is not None:
+    xf, xr = _seed_words(exclude_fwd, opt.kmer_size, "exclude"), _seed_words(exclude_rev, opt.kmer_size, "exclude")
+    if xf is not None or xr is not None:
+        sets_f, sets_r = _kmer_sets(sf, xf), _kmer_sets(sr, xr)
+        self._check(self.L.msspe_kmer_candidates_both_sets_packed_dev(
+            self.ptr, C.c_void_p(d_packed), n_seq, seq_len, C.byref(opt), C.byref(sets_f), C.byref(sets_r),
+            w[0].ctypes.data, f[0].ctypes.data, C.byref(n[0]), w[1].ctypes.data, f[1].ctypes.data, C.byref(n[1]), cap))
+    elif sf is not None or sr is not None:
         sf = np.zeros(0, dtype=np.uint64) if sf is None else sf
         sr = np.zeros(0, dtype=np.uint64) if sr is None else sr
         self._check(self.L.msspe_kmer_candidates_both_seeded_packed_dev(
