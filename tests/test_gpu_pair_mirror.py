@@ -126,22 +126,36 @@ def test_small_pools_equal_the_oracle(eng, m, oracle, oracle_tables, n, k, chem_
             assert stats["lists"][0] >= stats["bound_survivors"] > 0
 
 
-def test_several_launches_and_flushes(eng, m, oracle, oracle_tables):
-    """A list of 2^20 entries and 1,500 oligos: 1,125,750 processed pairs, at most 2^19 per launch."""
-    pool = m.synth.pool_strings(m.synth.random_pool(1500, 13, seed=5))
-    _, _, cf, _ = oracle.pool_pairs(oracle_tables, pool, oracle.ntthal_args(), THR, want_dg=False)
-    want = cf.astype(bool)
+_launch_oracle = []
+
+
+def launch_pool_and_oracle(m, oracle, oracle_tables):
+    """1,500 random 13-mers and the oracle's conflicts among them: once for both cases, left unchanged."""
+    if not _launch_oracle:
+        pool = m.synth.pool_strings(m.synth.random_pool(1500, 13, seed=5))
+        _, _, cf, _ = oracle.pool_pairs(oracle_tables, pool, oracle.ntthal_args(), THR, want_dg=False)
+        want = cf.astype(bool)
+        want.setflags(write=False)
+        _launch_oracle.append((pool, want))
+    return _launch_oracle[0]
+
+
+@pytest.mark.parametrize("mirror", ["auto", 0])
+def test_several_launches_and_flushes(eng, m, oracle, oracle_tables, mirror):
+    """A list of 2^20 entries and 1,500 oligos: mirrored, 1,125,750 processed pairs, at most 2^19 per launch;
+    un-mirrored, 2,250,000 pairs, at most 2^20 per launch and a flush between the launches."""
+    pool, want = launch_pool_and_oracle(m, oracle, oracle_tables)
     eng.set_option("list_cap_log2", 20)
     eng.profile_enable(True)
     try:
         eng.profile_read()
-        bm, counts, stats = screen(eng, pool, m.Chem.ntthal(), "auto")
+        bm, counts, stats = screen(eng, pool, m.Chem.ntthal(), mirror)
         launches, _ = eng.profile_read()
     finally:
         eng.profile_enable(False)
         eng.set_option("list_cap_log2", 0)
-    print(f"{launches} first-stage launches, survivors {stats['bound_survivors']}, lists {stats['lists']}")
-    assert launches >= 3 and stats["bound_mirrored"] == 1500 * 1499 // 2
+    print(f"pair_mirror={mirror}: {launches} first-stage launches, survivors {stats['bound_survivors']}, lists {stats['lists']}")
+    assert launches >= 3 and stats["bound_mirrored"] == (1500 * 1499 // 2 if mirror == "auto" else 0)
     np.testing.assert_array_equal(bits(bm, 1500), want)
     np.testing.assert_array_equal(counts, want.sum(1).astype(np.uint32))
 
