@@ -139,6 +139,14 @@ const char *msspe_version(void);
  *                                 each unordered pair once -- the bound of (a, b) is one of (b, a) too -- and hands a
  *                                 pair it cannot cull on in both orders ("auto", the default, and "1": the same; the
  *                                 mirror is never applied where it is not proven); "0": every ordered pair is filled
+ *   "pair_bound_list" "auto" | "0" | "1"  where the bound first stage runs, a lane that leaves its wave WITHOUT a bound of
+ *                                 its own (53..63 stored cells, dragged, shed by the slot fit) goes to a list of its own,
+ *                                 once per unordered pair under the mirror, and gets the same bound from a list kernel
+ *                                 (k_pairs_bound_list) before the exact list stages; what that cannot cull joins hand-over
+ *                                 list 0 ("auto", the default, and "1": the same); "0": such lanes go to list 0 as they
+ *                                 are.  Decisions are the exact stages' either way.  msspe_get_info "bound_list_pairs" /
+ *                                 "bound_list_survivors": entries that list held / ordered pairs handed on from it
+ *                                 since the last read
  *   "stage_a_graph"  "0" | "1"    hipGraph replay of stage A's greedy loop (1)
  *   "stage_a_candidates" "0" | "1"  greedy loop over the list of words near the maximum (1), or over all the
  *                                 words on every iteration (0); the winners are the same */
@@ -279,6 +287,13 @@ int msspe_cross_dimer_edges(msspe_ctx *ctx, const char *pool_ascii, int n, int k
  * MSSPE_ERR_ARG where the stage does not apply: k > 13, a threshold whose cut is above 0, tables it cannot hold. */
 int msspe_cross_dimer_bound_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const msspe_chem *chem,
                                 float dg_threshold, int row0, int row1, int col0, int col1, double *d_bound);
+/* The same plane with the bound LIST stage (option "pair_bound_list") behind the first stage: every pair the first stage
+ * would put on list U -- 53..63 stored cells, lanes dragged or shed from their wave -- carries the value that stage
+ * computes for it (the same recurrence on the same integer terms) instead of -inf.  -inf remains exactly for pairs of two
+ * self-complementary oligos and pairs with more than 63 stored cells, +inf for pairs without a complementary base pair.
+ * The block may hold at most as many pairs as a hand-over list (2^20 .. 2^30: it grows with the call). */
+int msspe_cross_dimer_bound_list_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const msspe_chem *chem,
+                                     float dg_threshold, int row0, int row1, int col0, int col1, double *d_bound);
 
 /* One pool screened against another (engine extension: the reference screens one pool of one --kmer-size,
  * od-msspe/src/delta_g.rs:61-81; ntthal itself takes any two oligos).  Pool A: n_a oligos of k_a bases, oligo 1

@@ -74,8 +74,11 @@ constexpr long kListCapMax = 1L << 30;       // 8 GB per list (two of them, 6 % 
                                              // 2^28 -> 2^30 is 17 -> 5 flushes per 65,536^2 screen and 1.5 % of its time
 constexpr size_t kGenericLanes = 1u << 16;   // lanes of the generic kernels' workspace
 constexpr int kOvfTotals = 2 + 7;            // msspe_ctx::d_ovf_total: two flags / totals, then one total per hand-over list
-constexpr int kReasonWords = 9 + 1024 + 8 + 2;   // msspe_ctx::d_reasons (int_core.hpp IntArgs::reasons); the last two: pairs
-constexpr int kBoundSurvivors = kReasonWords - 2;   // the bound first stage handed on, and its probe launch's count
+constexpr int kReasonWords = 9 + 1024 + 8 + 4;   // msspe_ctx::d_reasons (int_core.hpp IntArgs::reasons); the last four: pairs
+constexpr int kBoundSurvivors = kReasonWords - 4;   // the bound first stage handed on, and its probe launch's count;
+constexpr int kBoundListStats = kReasonWords - 2;   // the bound list stage: entries of list U, ordered pairs it appended
+constexpr int kOvfCounters = 9;                     // msspe_ctx::ovf_count: the eight stage counters, then list U's
+constexpr int kOvfU = 8;
 constexpr long kBoundProbePairs = 1L << 20;  // pair_bound = auto: pairs of the probe launch behind a new record
 // pair_bound = auto runs the bound stage while the recorded survivor share is at most this: HALF the break-even share
 //   (ns per pair of the exact row kernel - ns per pair of the bound kernel) / ns per handed-on pair of the list chain
@@ -100,6 +103,8 @@ struct EngineOptions {
                               // the list stages -- 0 never | 1 wherever it applies | 2 auto: while few pairs survive it (kBoundShareMax)
     int pair_mirror = 2;      // the bound stage of a square same-pool screen fills each unordered pair once and hands a survivor on in
                               // both orders -- 0 never | 1, 2 (auto): wherever the tables are strand-symmetric (ChemEntry::mirror_ok)
+    int pair_bound_list = 2;  // lanes that leave the bound first stage without a bound of their own go to list U and are bounded there
+                              // (k_pairs_bound_list) before the exact lists -- 0 never | 1, 2 (auto): wherever the bound first stage runs
     bool split_list = true;   // short oligos: tables too large for the integer list stage go to the split kernel's list mode
     bool short_chain = true;  // screens of up to 2^23 pairs: integer list stage -> one wave per pair (no register-table stages between)
     int self_lane_from = 81920;   // oligos per call from which SELF_ANY / SELF_END run one lane per oligo (msspe_oligo_stats_dev)
@@ -328,8 +333,8 @@ int ensure_overflow(msspe_ctx *ctx, long total_pairs)
     // the small counter buffers first and unconditionally: a failed list allocation must not leave a
     // context whose counters are missing
     if (!ctx->ovf_count) {
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->ovf_count, sizeof(uint32_t) * 8));
-        HIP_TRY(ctx, hipMemsetAsync(ctx->ovf_count, 0, sizeof(uint32_t) * 8, ctx->stream));
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->ovf_count, sizeof(uint32_t) * kOvfCounters));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->ovf_count, 0, sizeof(uint32_t) * kOvfCounters, ctx->stream));
     }
     if (!ctx->d_ovf_total) {
         HIP_TRY(ctx, hipMalloc((void **)&ctx->d_ovf_total, kOvfTotals * sizeof(uint64_t)));
@@ -402,6 +407,7 @@ __global__ void k_accumulate_overflow(const uint32_t *count, uint64_t *total, ui
             total[2 + q] += count[q];
             if (count[q] > cap) total[1] = 1;
         }
+        if (count[kOvfU] > cap) total[1] = 1;   // list U (the bound list stage's input): checked, not part of the totals
     }
 }
 
@@ -609,7 +615,7 @@ struct ListChain {
     }
 
     // The dense kernel over the current list; accumulate: the totals of the hand-over statistics and the overrun
-    // check (k_accumulate_overflow); then the eight counters are cleared for the next flush or call.
+    // check (k_accumulate_overflow); then the eight counters and list U's are cleared for the next flush or call.
     int finish(GenericDimerArgs &g, bool accumulate)
     {
         g.list = in_list;
@@ -619,7 +625,7 @@ struct ListChain {
         if (accumulate)
             hipLaunchKernelGGL(k_accumulate_overflow, dim3(1), dim3(64), 0, ctx->stream, ctx->ovf_count,
                                ctx->d_ovf_total, (uint32_t)cap);
-        HIP_TRY(ctx, hipMemsetAsync(ctx->ovf_count, 0, 8 * sizeof(uint32_t), ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->ovf_count, 0, kOvfCounters * sizeof(uint32_t), ctx->stream));
         return MSSPE_OK;
     }
 
@@ -756,6 +762,10 @@ int msspe_set_option(msspe_ctx *ctx, const char *key, const char *value)
         if (v == "auto") ctx->opt.pair_mirror = 2;
         else if (is_num && (num == 0 || num == 1)) ctx->opt.pair_mirror = (int)num;
         else return bad();
+    } else if (k == "pair_bound_list") {
+        if (v == "auto") ctx->opt.pair_bound_list = 2;
+        else if (is_num && (num == 0 || num == 1)) ctx->opt.pair_bound_list = (int)num;
+        else return bad();
     } else if (k == "stage_a_graph") {
         if (!is_num || num < 0 || num > 1) return bad();
         ctx->kmer.set_use_graph(num != 0);
@@ -821,6 +831,20 @@ int msspe_get_info(msspe_ctx *ctx, const char *key, long long *value_out)
     else if (k == "panel_thin_rounds_us") *value_out = ctx->thin.phase_us()[2];
     else if (k == "pair_bound") *value_out = ctx->opt.pair_bound;
     else if (k == "pair_mirror") *value_out = ctx->opt.pair_mirror;
+    else if (k == "pair_bound_list") *value_out = ctx->opt.pair_bound_list;
+    else if (k == "bound_list_pairs" || k == "bound_list_survivors") {
+        // the bound list stage since the last read of this key (reading resets it): entries of list U (unordered pairs under
+        // the mirror), ordered pairs it appended to list 0
+        *value_out = 0;
+        if (!ctx->d_reasons) return MSSPE_OK;
+        unsigned long long *at = ctx->d_reasons + kBoundListStats + (k == "bound_list_pairs" ? 0 : 1);
+        uint64_t v = 0;
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        HIP_TRY(ctx, hipMemcpy(&v, at, sizeof v, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemsetAsync(at, 0, sizeof v, ctx->stream));
+        *value_out = (long long)v;
+    }
     else if (k == "bound_mirrored") {
         // ordered pairs the mirrored bound stage answered or handed on without a fill of their own since the last read
         // of this key; reading resets it
@@ -1059,11 +1083,28 @@ static int run_chain(msspe_ctx *ctx, ChemEntry *ce, const ChainRoute &route, con
     // Overflow pairs are collected over several launches and finished together: the list kernels
     // have a fixed latency floor, and list_cap entries cannot be overrun by list_cap / kChunkPairs
     // launches even if every pair overflowed.  List 0 (ovf_list) = what the first stage did not answer.
+    // The bound list stage (option pair_bound_list; thal_pairs_bound_list.hip): where it is on, the bound first stage
+    // appends the lanes that leave it without a bound of their own to list U -- ovf_list2 with its own counter, once per
+    // unordered pair -- and a flush first bounds U, appending what it cannot cull to list 0 behind the first stage's
+    // entries; the route then runs from list 0 as ever, with ovf_list2, which U has vacated by then (same stream), as its
+    // first output list.  Capacity: a launch that processes P pairs appends at most P entries to U and, to list 0, at
+    // most P (2 P mirrored) from the two stages together -- an entry of U becomes at most one (two) of list 0 -- which
+    // is what `pending` budgets against the capacity already.
+    bool bound_list = false;   // set below, once the bound stage is decided
+    uint2 *const u_list = ctx->ovf_list2;
+    uint32_t *const u_count = ctx->ovf_count + kOvfU;
     auto flush = [&]() -> int {
         PairKernelArgs a = pair_args(ctx, ce, b);
+        if (bound_list) {
+            a.overflow_list = ctx->ovf_list;
+            a.overflow_count = ctx->ovf_count;
+            a.overflow_cap = (uint32_t)kListCap;
+            HIP_TRY(ctx, launch_pairs_bound_list(a, ce->d_bt, u_list, u_count, ctx->d_reasons + kBoundListStats, nullptr,
+                                                 ctx->n_cu, ctx->stream));
+        }
         return ListChain(ctx, ce, end1, ctx->ovf_list, kListCap).run(route.behind, a, g, true);
     };
-    HIP_TRY(ctx, hipMemsetAsync(ctx->ovf_count, 0, 8 * sizeof(uint32_t), ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->ovf_count, 0, kOvfCounters * sizeof(uint32_t), ctx->stream));
     // The row-specialised first stage, and in front of the list stages instead of it the BOUND instance where the call
     // asks for decisions only (no plane, no edge values): it proves most pairs free of a conflict at about half the
     // price and hands the rest to list 0 (thal_pairs_row.hip k_pairs_bound; option pair_bound).
@@ -1099,6 +1140,7 @@ static int run_chain(msspe_ctx *ctx, ChemEntry *ce, const ChainRoute &route, con
         }
         bound_stage = ce->bound_share[k] >= 0.f && ce->bound_share[k] <= kBoundShareMax;
     }
+    bound_list = bound_stage && ctx->opt.pair_bound_list != 0;
     long pending = 0;   // worst-case entries the list may hold
     auto prof_begin = [&]() -> int {
         if (!ctx->prof_on) return MSSPE_OK;
@@ -1158,7 +1200,7 @@ static int run_chain(msspe_ctx *ctx, ChemEntry *ce, const ChainRoute &route, con
             a.overflow_cap = (uint32_t)kListCap;
             if ((rc = prof_begin())) return rc;
             HIP_TRY(ctx, launch_pairs_bound(a, ce->d_it, ce->d_bt, ctx->d_reasons + kBoundSurvivors, nullptr, ctx->n_cu,
-                                            ctx->stream, true));
+                                            ctx->stream, true, bound_list ? u_list : nullptr, u_count));
             if ((rc = prof_end())) return rc;
             pending += 2 * launch_pairs;
             p0 = p1;
@@ -1195,7 +1237,7 @@ static int run_chain(msspe_ctx *ctx, ChemEntry *ce, const ChainRoute &route, con
             } else if (split) HIP_TRY(ctx, launch_pairs_split(a, ce->d_st, ctx->d_reasons, ctx->opt.split_lanes, ctx->stream));
             else if (bound_stage)
                 HIP_TRY(ctx, launch_pairs_bound(a, ce->d_it, ce->d_bt, ctx->d_reasons + kBoundSurvivors, nullptr, ctx->n_cu,
-                                                ctx->stream));
+                                                ctx->stream, false, bound_list ? u_list : nullptr, u_count));
             else if (row_stage) HIP_TRY(ctx, launch_pairs_row(a, ce->d_it, ctx->d_reasons, ctx->n_cu, ctx->stream));
             else if (int_stage) HIP_TRY(ctx, launch_pairs_int(a, ce->d_it, ctx->d_reasons, ctx->n_cu, ctx->stream));
             else HIP_TRY(ctx, launch_pairs_fast(a, ctx->stream, end1));
@@ -1343,8 +1385,10 @@ int msspe_cross_dimer_edges_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, i
 }
 
 // Diagnostic: the bound first stage's value for every pair of the block (tests and debugging; no screen reads it).
-int msspe_cross_dimer_bound_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const msspe_chem *chem,
-                                float dg_threshold, int row0, int row1, int col0, int col1, double *d_bound)
+// with_list: the pairs the first stage would put on list U are bounded by the bound list stage, whose values replace
+// their -inf.
+static int cross_dimer_bound_plane(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const msspe_chem *chem,
+                                   float dg_threshold, int row0, int row1, int col0, int col1, double *d_bound, bool with_list)
 {
     const ScreenBlock b = screen_block(d_pool, n, k, k, row0, row1, col0, col1, plane_sinks(nullptr, nullptr, nullptr, nullptr));
     ChemEntry *ce = nullptr;
@@ -1356,7 +1400,10 @@ int msspe_cross_dimer_bound_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, i
                                         "above 0, tables outside its range, or option row_oob = 0)");
     const int ncols = b.sinks.ncols;
     int rc2 = 0;
-    if ((rc2 = ensure_overflow(ctx, 1))) return rc2;   // (the work counter lives beside the list counters)
+    const long n_pairs = (long)(row1 - row0) * (long)ncols;
+    if ((rc2 = ensure_overflow(ctx, with_list ? n_pairs : 1))) return rc2;   // (the work counter lives beside the list counters)
+    if (with_list && n_pairs > ctx->list_cap)
+        return fail(ctx, MSSPE_ERR_ARG, "msspe_cross_dimer_bound_list_dev: the block has more pairs than a hand-over list holds");
     if ((rc2 = ensure_sort(ctx, (size_t)ncols))) return rc2;
     HIP_TRY(ctx, sort_columns_by_composition(b.pool, col0, ncols, k, ctx->d_sort_scratch, ctx->sort_scratch_bytes,
                                              ctx->d_sorted, ctx->d_perm, ctx->stream));
@@ -1366,8 +1413,29 @@ int msspe_cross_dimer_bound_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, i
     a.ncols_sorted = ncols;
     a.col0 = 0;
     a.col1 = ncols;
-    HIP_TRY(ctx, launch_pairs_bound(a, ce->d_it, ce->d_bt, nullptr, d_bound, ctx->n_cu, ctx->stream));
+    if (!with_list) {
+        HIP_TRY(ctx, launch_pairs_bound(a, ce->d_it, ce->d_bt, nullptr, d_bound, ctx->n_cu, ctx->stream));
+        return MSSPE_OK;
+    }
+    uint32_t *const u_count = ctx->ovf_count + kOvfU;
+    a.overflow_cap = (uint32_t)ctx->list_cap;
+    HIP_TRY(ctx, hipMemsetAsync(u_count, 0, sizeof(uint32_t), ctx->stream));
+    HIP_TRY(ctx, launch_pairs_bound(a, ce->d_it, ce->d_bt, nullptr, d_bound, ctx->n_cu, ctx->stream, false, ctx->ovf_list2, u_count));
+    HIP_TRY(ctx, launch_pairs_bound_list(a, ce->d_bt, ctx->ovf_list2, u_count, nullptr, d_bound, ctx->n_cu, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(u_count, 0, sizeof(uint32_t), ctx->stream));
     return MSSPE_OK;
+}
+
+int msspe_cross_dimer_bound_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const msspe_chem *chem,
+                                float dg_threshold, int row0, int row1, int col0, int col1, double *d_bound)
+{
+    return cross_dimer_bound_plane(ctx, d_pool, n, k, chem, dg_threshold, row0, row1, col0, col1, d_bound, false);
+}
+
+int msspe_cross_dimer_bound_list_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const msspe_chem *chem,
+                                     float dg_threshold, int row0, int row1, int col0, int col1, double *d_bound)
+{
+    return cross_dimer_bound_plane(ctx, d_pool, n, k, chem, dg_threshold, row0, row1, col0, col1, d_bound, true);
 }
 
 double msspe_t_cut(float tm_threshold) { return t_cut(tm_threshold); }

@@ -179,11 +179,21 @@ struct IntArgs {
     unsigned long long *bound_survivors = nullptr;   // += pairs the bound could not cull
     double *bound_plane = nullptr;                    // diagnostic form: the bound of every pair, nothing else is written
     int mirror = 0;                                   // each unordered pair once: rows in sorted order, columns q >= p (launch_pairs_bound)
+    // list U: lanes that left their wave of the bound instance WITHOUT a bound of their own (53..63 stored cells, dragged,
+    // shed by the slot fit), once per unordered pair; k_pairs_bound_list bounds them.  nullptr: they go to ovf_list
+    uint2 *ulist = nullptr;
+    uint32_t *ucount = nullptr;
+    unsigned long long *bound_list_stats = nullptr;   // k_pairs_bound_list: [0] += entries of U, [1] += ordered pairs it appended
 };
 
 // A list entry whose pair needs the f64 kernels (an exact tie was met) carries this bit in .x;
 // entries without it only left their wave because of their table size and may be retried here.
 constexpr unsigned kNeedsF64 = 0x80000000u;
+// An entry of list U that stands for (col, row) as well (a mirrored launch filled the unordered pair once): bit 30 of .x.
+// Rows stay below 2^21, so the bit is free; no entry of lists 0 .. 6 ever carries it.
+constexpr unsigned kListTwin = 0x40000000u;
+// Stored cells the 64-slot list tables hold: one slot stays free for the last row's writes (thal_pairs_int.hip wave_pairs)
+constexpr int kListStoredMax = 63;
 
 }  // namespace
 

@@ -138,11 +138,21 @@ bool pairs_row_tables_ok(const IntTables &it);   // host: may this chemistry run
 // bound_plane != nullptr: the diagnostic form (the bound of every pair in cal/mol, nothing else is written).
 hipError_t launch_pairs_bound(const PairKernelArgs &a, const IntTables *it, const BoundTables *bt,
                               unsigned long long *survivors, double *bound_plane, int n_cu, hipStream_t stream,
-                              bool mirror = false);
+                              bool mirror = false, uint2 *ulist = nullptr, uint32_t *ucount = nullptr);
+// ulist != nullptr (capacity a.overflow_cap, counter *ucount): list U.  A pair that leaves the stage WITHOUT a bound of
+// its own and fits the list stage's table (53..63 stored cells, dragged lanes, lanes shed by the slot fit) is appended there
+// instead, once per unordered pair (bit 30 of .x: it stands for (col, row) as well); launch_pairs_bound_list bounds it.
 // mirror: a square same-pool screen under strand-symmetric tables.  a.row0 .. a.row1 are positions in the SORTED order like
 // the columns (row p = cols_sorted[p], pool index perm[p]), a.col0 = 0, a.col1 = the pool; row p screens the sorted
 // columns q >= p only, and a pair that is not culled is appended in both orders (once on the diagonal).
 int pairs_bound_max_k();
+// The bound list stage (thal_pairs_bound_list.hip k_pairs_bound_list): the min-plus bound of every entry of list U
+// (*u_count entries, at most a.overflow_cap) on 64-slot tables in lanes sorted by table size.  A culled pair writes
+// nothing; a survivor is appended unmarked to a.overflow_list (in both orders when its twin bit is set), behind what the
+// first stage put there.  stats (optional): [0] += entries of U, [1] += ordered pairs appended.  bound_plane != nullptr:
+// the diagnostic form -- the value of every entry goes to the plane (layout of launch_pairs_bound's) and nothing else is written.
+hipError_t launch_pairs_bound_list(const PairKernelArgs &a, const BoundTables *bt, uint2 *u_list, const uint32_t *u_count,
+                                   unsigned long long *stats, double *bound_plane, int n_cu, hipStream_t stream);
 hipError_t pairs_row_lds_reads_zero(hipStream_t stream, int n_cu, bool *ok);   // does this device read 0 beyond a block's LDS allocation?
 // List mode of the integer stage: retries the pairs of in_list that carry no "needs f64" mark (bit
 // 31 of .x) with a 64-slot table in lanes sorted by table size; everything else passes through.

@@ -887,6 +887,9 @@ static __device__ __forceinline__ void wave_pairs_row(SharedRow &sh, const IntAr
     // other shapes keep one slot free for them
     constexpr int kFit = NS == 52 ? NS : NS - 1;
     bool spill = inside & ((n_cells > kFit) | sym);
+    // BOUND: lanes that leave without a bound of their own and fit the list stage's table go to list U, where
+    // k_pairs_bound_list bounds them (thal_pairs_bound_list.hip); the lanes shed below join them
+    bool unbounded = BOUND && spill && !sym && n_cells <= kListStoredMax;
     unsigned flag = 0u;
     bool active = inside & !spill & (n_all > 0);   // lanes that run the DP
     if (!active) n_cells = 0;
@@ -899,6 +902,7 @@ static __device__ __forceinline__ void wave_pairs_row(SharedRow &sh, const IntAr
         if (next == 0 || nmax * nmax - next * next <= kDragCost * m) break;   // wave-uniform
         if (active && n_cells == nmax) {
             spill = true;
+            unbounded = BOUND;
             active = false;
             n_cells = 0;
         }
@@ -929,6 +933,7 @@ static __device__ __forceinline__ void wave_pairs_row(SharedRow &sh, const IntAr
         const bool uniform = same == act;   // cannot happen with n_slots > NS; never loop on it
         if (active && (uniform ? n_cells == nmax : ((sig == sig0) != keep_same))) {
             spill = true;
+            unbounded = BOUND;
             active = false;
             n_cells = 0;
         }
@@ -957,6 +962,14 @@ static __device__ __forceinline__ void wave_pairs_row(SharedRow &sh, const IntAr
             if (inside & !active)
                 a.bound_plane[(size_t)(row - a.f.sinks.row0) * (size_t)a.f.sinks.ncols + (size_t)(col - a.f.sinks.col0)] =
                     spill ? -INFINITY : INFINITY;
+            // (msspe_cross_dimer_bound_list_dev: the list stage writes its value over the -inf of a pair of U)
+            if (unbounded && a.ulist) {
+                const uint32_t at = atomicAdd(a.ucount, 1u);
+                if (at < a.f.ovf_cap) a.ulist[at] = make_uint2((unsigned)row, (unsigned)col);
+            }
+        } else if (unbounded && a.ulist) {   // nothing has tried to prove this pair harmless yet: once per unordered pair
+            const uint32_t at = atomicAdd(a.ucount, 1u);
+            if (at < a.f.ovf_cap) a.ulist[at] = make_uint2((unsigned)row | (twin ? kListTwin : 0u), (unsigned)col);
         } else if (spill && a.f.ovf_list) {   // survivors and size hand-overs alike: the list stages answer them exactly
                                               // (no list: the probe launch of option pair_bound = auto, which only counts)
             const uint32_t at = atomicAdd(a.f.ovf_count, twin ? 2u : 1u);
@@ -1348,9 +1361,10 @@ int pairs_bound_max_k() { return Row13::kRowK; }
 // (nothing is written for it) or appended to a.overflow_list.  bound_plane != nullptr: the diagnostic form, which writes
 // the bound of every pair of the block (cal/mol; +inf: no chain; -inf: not bounded here) and nothing else.
 hipError_t launch_pairs_bound(const PairKernelArgs &a, const IntTables *it, const BoundTables *bt,
-                              unsigned long long *survivors, double *bound_plane, int n_cu, hipStream_t stream, bool mirror)
+                              unsigned long long *survivors, double *bound_plane, int n_cu, hipStream_t stream, bool mirror,
+                              uint2 *ulist, uint32_t *ucount)
 {
-    if (a.k > Row13::kRowK || a.k < 2 || !bt || (!survivors && !bound_plane)) return hipErrorInvalidValue;
+    if (a.k > Row13::kRowK || a.k < 2 || !bt || (!survivors && !bound_plane) || (ulist && !ucount)) return hipErrorInvalidValue;
     // mirror: rows are sorted positions and a row's columns start at itself, so the rows must lie inside the columns
     if (mirror && (bound_plane || a.col0 != 0 || a.row0 < 0 || a.row1 > a.col1)) return hipErrorInvalidValue;
     IntArgs x;
@@ -1379,6 +1393,8 @@ hipError_t launch_pairs_bound(const PairKernelArgs &a, const IntTables *it, cons
     x.bound_survivors = survivors;
     x.bound_plane = bound_plane;
     x.mirror = mirror ? 1 : 0;
+    x.ulist = ulist;   // (same capacity as the hand-over list)
+    x.ucount = ulist ? ucount : nullptr;
     const long ncolg = (a.col1 - a.col0 + 63) / 64;
     const long items = ((ncolg + Row13::kSegGroups - 1) / Row13::kSegGroups) * (long)(a.row1 - a.row0);
     if (items <= 0) return hipSuccess;

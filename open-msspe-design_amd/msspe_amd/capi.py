@@ -16,7 +16,7 @@ EXPORTS = [
     "msspe_last_error", "msspe_version", "msspe_set_option", "msspe_get_info", "msspe_kmer_trace", "msspe_set_stream", "msspe_reset_stream",
     "msspe_synchronize",
     "msspe_pack_oligos", "msspe_unpack_oligo", "msspe_cross_dimer_dev", "msspe_cross_dimer",
-    "msspe_cross_dimer_edges_dev", "msspe_cross_dimer_edges", "msspe_cross_dimer_bound_dev", "msspe_host_bound_tables", "msspe_host_bound_mirror_ok",
+    "msspe_cross_dimer_edges_dev", "msspe_cross_dimer_edges", "msspe_cross_dimer_bound_dev", "msspe_cross_dimer_bound_list_dev", "msspe_host_bound_tables", "msspe_host_bound_mirror_ok",
     "msspe_cross_dimer_ab_dev", "msspe_cross_dimer_ab_edges_dev", "msspe_cross_dimer_ab", "msspe_cross_dimer_ab_edges",
     "msspe_cross_dimer_edges_mixed",
     "msspe_cross_dimer_end_dev", "msspe_cross_dimer_end", "msspe_cross_dimer_end_edges_dev", "msspe_cross_dimer_end_edges",
@@ -188,6 +188,7 @@ def load_library() -> C.CDLL:
                                               C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_uint64, vp]
     L.msspe_cross_dimer_bound_dev.argtypes = [vp, u64p, C.c_int, C.c_int, C.POINTER(Chem), C.c_float,
                                               C.c_int, C.c_int, C.c_int, C.c_int, vp]
+    L.msspe_cross_dimer_bound_list_dev.argtypes = L.msspe_cross_dimer_bound_dev.argtypes
     L.msspe_host_bound_tables.argtypes = [C.c_char_p, C.POINTER(Chem), C.c_float, vp, vp, C.POINTER(C.c_int32)]
     L.msspe_host_bound_mirror_ok.argtypes = [C.c_char_p, C.POINTER(Chem), C.c_float, C.POINTER(C.c_int32)]
     L.msspe_cross_dimer_ab_dev.argtypes = [vp, u64p, C.c_int, C.c_int, u64p, C.c_int, C.c_int, C.POINTER(Chem),
@@ -551,6 +552,15 @@ class Engine:
         """Diagnostic (tests, debugging): the bound first stage's value of every pair of the block, float64 cal/mol
         into the caller's plane (+inf: no chain; -inf: not bounded there); asynchronous.  msspe_cross_dimer_bound_dev."""
         self._check(self.L.msspe_cross_dimer_bound_dev(
+            self.ptr, C.c_void_p(d_pool), n, k, C.byref(chem), C.c_float(threshold), rows[0], rows[1], cols[0],
+            cols[1], C.c_void_p(d_bound)))
+
+    def cross_dimer_bound_list_dev(self, d_pool: int, n: int, k: int, chem: Chem, threshold: float,
+                                   rows: tuple[int, int], cols: tuple[int, int], d_bound: int):
+        """cross_dimer_bound_dev's plane with the bound list stage behind the first stage: every pair it bounds carries
+        its value; -inf only for two self-complementary oligos and more than 63 stored cells.
+        msspe_cross_dimer_bound_list_dev."""
+        self._check(self.L.msspe_cross_dimer_bound_list_dev(
             self.ptr, C.c_void_p(d_pool), n, k, C.byref(chem), C.c_float(threshold), rows[0], rows[1], cols[0],
             cols[1], C.c_void_p(d_bound)))
 
@@ -1178,6 +1188,10 @@ class Engine:
         out["bound_survivors"] = self.info("bound_survivors")
         # ordered pairs a mirrored bound stage (option pair_mirror) answered or handed on without a fill of their own
         out["bound_mirrored"] = self.info("bound_mirrored")
+        # the bound list stage (option pair_bound_list): entries of list U (unordered pairs under the mirror), and the
+        # ordered pairs it could not cull and appended to list 0
+        out["bound_list_pairs"] = self.info("bound_list_pairs")
+        out["bound_list_survivors"] = self.info("bound_list_survivors")
         return out
 
     # ---- stage B ---------------------------------------------------------------------------
