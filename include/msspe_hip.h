@@ -469,6 +469,15 @@ int msspe_host_pair_tables(const char *params_path, const msspe_chem *chem, floa
  * non-integral enthalpy give MSSPE_OK with out[0] = 0 (every dimer call would be refused);
  * MSSPE_ERR_TABLES only when the files cannot be loaded. */
 int msspe_host_table_routes(const char *params_path, const msspe_chem *chem, int32_t out[8]);
+/* Host only: the first-stage launches a pair screen of rows [row0, row1) x ncols columns from pool column col0 is cut
+ * into under hand-over lists of list_cap entries (csrc/screen_plan.hpp; the screens execute this very plan).
+ * first_stage: 0 dense, 1 wave, 2 split, 3 f64 register table, 4 integer, 5 row, 6 bound, 7 mirrored bound (a square
+ * block, row0 == col0, of at most min(2^29, list_cap / 2) oligos).  out[i] = row0, row1, col0, col1 of launch i (the
+ * wave and dense kernels' columns are the pool's, the others' positions in the sorted order; the mirrored rows too),
+ * the pairs it processes, the most entries it can append to hand-over list 0, 1 if the lists are flushed before it.
+ * *n_out = launches; more than capacity: MSSPE_ERR_CAPACITY, nothing written. */
+int msspe_host_screen_plan(int first_stage, int row0, int row1, int col0, int ncols, int64_t list_cap, int64_t *out,
+                           int capacity, int *n_out);
 /* Host only: the bound first stage's tables (option "pair_bound"; csrc/fast_tables.hpp BoundTables) in the layout
  * of msspe_host_pair_tables' int_g (2604 entries) and int_T (239 * 64): every term's H - temp_k * S, a stacked pair
  * and a loop with - temp_k * salt on top, in units of 1 / info[3] cal/mol rounded down; entries >= info[6] are "not

@@ -33,6 +33,7 @@
 #include "nn_params.hpp"
 #include "thal_dense.hpp"
 #include "panel_thin.hpp"
+#include "screen_plan.hpp"
 #include "tube_split.hpp"
 
 using namespace msspe;
@@ -63,8 +64,6 @@ struct ChemEntry {
 };
 
 constexpr int kCutAnyDg = 0, kCutEndT = 1, kCutAnyT = 2;   // ChemEntry::kind: one cache entry per kind, chemistry and threshold
-constexpr long kChunkPairs = 1L << 29;       // pairs per launch of the all-pairs kernel (a launch's tail: 2.4 % at 2^24, 1.4 % at 2^26; a 65,536-primer
-                                             // pool: 1850 ms at 2^27, 1822 at 2^29, 1819 at 2^30 -- and a hand-over list of as many entries, 4 GB, twice)
 constexpr int kHairpinLaneFrom = 8192;       // oligos per call from which HAIRPIN_TH runs one lane per oligo (msspe_oligo_stats_dev)
 constexpr long kListCapMin = 1L << 20;       // hand-over list entries (grows with the call up to kListCapMax): one launch can never overrun it
 constexpr long kListCapMax = 1L << 30;       // 8 GB per list (two of them, 6 % of the card's memory): the stages behind the first
@@ -507,8 +506,7 @@ bool wave_ok(const msspe_ctx *ctx, const ChemEntry *ce, int kmax)
     return !ctx->opt.force_generic && kmax <= ce->wave_max_k && ctx->opt.wave_kernel;
 }
 
-// The pair kernels' arguments for the block in list mode; run_chain's first-stage launches put their band of rows,
-// the sorted columns and list 0 on top.
+// The pair kernels' arguments for the block in list mode; first_stage_args puts a launch on top.
 PairKernelArgs pair_args(const msspe_ctx *ctx, const ChemEntry *ce, const ScreenBlock &b)
 {
     PairKernelArgs a;
@@ -524,6 +522,24 @@ PairKernelArgs pair_args(const msspe_ctx *ctx, const ChemEntry *ce, const Screen
     a.col1 = b.col1 - b.col0;
     a.sinks = b.sinks;
     a.work_counter = ctx->ovf_count + 7;   // the last of the eight stage counters
+    return a;
+}
+
+// ... for one first-stage launch: its rows and columns (screen_plan.hpp: sorted positions, the wave kernel's are pool
+// columns), the composition-sorted columns (ensure_sort) and hand-over list 0 (ensure_overflow) with its capacity.
+PairKernelArgs first_stage_args(const msspe_ctx *ctx, const ChemEntry *ce, const ScreenBlock &b, const Launch &l)
+{
+    PairKernelArgs a = pair_args(ctx, ce, b);
+    a.cols_sorted = ctx->d_sorted;
+    a.perm = ctx->d_perm;
+    a.ncols_sorted = b.sinks.ncols;
+    a.row0 = l.row0;
+    a.row1 = l.row1;
+    a.col0 = l.col0;
+    a.col1 = l.col1;
+    a.overflow_list = ctx->ovf_list;
+    a.overflow_count = ctx->ovf_count;
+    a.overflow_cap = (uint32_t)ctx->list_cap;
     return a;
 }
 
@@ -1015,58 +1031,88 @@ void msspe_unpack_oligo(uint64_t packed, int k, char *ascii_out)
 // The stages of one screen, chosen by cross_dimer_impl (thal ANY) or cross_dimer_end_impl (thal END1).
 struct ChainRoute {
     bool end1;          // the END screen: END1 instantiations of every stage and the t decision
-    bool fast;          // a first stage runs; otherwise the dense kernel takes the whole block
-    bool split;         // split-table first stage (ANY only)
-    bool wave_matrix;   // the wave kernel is the first stage
-    bool int_stage;     // integer (or row-specialised) first stage (ANY only)
-    StageList behind;   // where fast: the list stages behind the first stage, in order
+    FirstStage first;   // Dense: the dense kernel takes the whole block; Int (ANY only) stands for the integer kernel and
+                        // its row-specialised and bound instances until settle_first_stage has picked one
+    bool bound_list = false;   // Bound, BoundMirror: the bound list stage runs at every flush (option pair_bound_list)
+    StageList behind;   // the list stages behind a first stage other than Dense, in order
 };
 
-// Runs a routed screen over the block: launch splitting, column sort, the first stage, and the hand-over lists
-// flushed through route.behind (ListChain).
-static int run_chain(msspe_ctx *ctx, ChemEntry *ce, const ChainRoute &route, const ScreenBlock &b)
+// option pair_bound = auto without a record for this chemistry, threshold and length (ChemEntry::bound_share): one probe
+// launch over the head of the call's own block, behind the column sort (it counts its survivors and writes nothing
+// else), and one counter read -- the only host round trip the bound adds, once per record.  A stream that is being
+// captured cannot be waited for: no record.
+static int probe_bound_share(msspe_ctx *ctx, ChemEntry *ce, const ScreenBlock &b)
 {
-    const bool end1 = route.end1, split = route.split, wave_matrix = route.wave_matrix, int_stage = route.int_stage;
-    const int k = b.k, k2 = b.k2, row0 = b.row0, row1 = b.row1, col0 = b.col0;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(ctx->stream, &cs) != hipSuccess) (void)hipGetLastError();
+    if (cs != hipStreamCaptureStatusNone) return MSSPE_OK;
+    const int col1 = (int)std::min<long>(b.sinks.ncols, kBoundProbePairs);
+    const int row1 = (int)std::min<long>(b.row1, (long)b.row0 + std::max(1L, kBoundProbePairs / col1));
+    PairKernelArgs a = first_stage_args(ctx, ce, b, Launch{b.row0, row1, 0, col1, 0, 0, false});
+    a.overflow_list = nullptr;   // no list: the kernel only counts
+    unsigned long long *probe = ctx->d_reasons + kBoundSurvivors + 1;
+    HIP_TRY(ctx, hipMemsetAsync(probe, 0, sizeof *probe, ctx->stream));
+    HIP_TRY(ctx, launch_pairs_bound(a, ce->d_it, ce->d_bt, probe, nullptr, ctx->n_cu, ctx->stream));
+    unsigned long long n_surv = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&n_surv, probe, sizeof n_surv, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    ce->bound_share[b.k] = (float)((double)n_surv / ((double)(row1 - b.row0) * (double)col1));
+    return MSSPE_OK;
+}
+
+// Which instance of the integer first stage takes the block: called once the hand-over lists are sized and the columns
+// sorted.  The row-specialised first stage, and in front of the list stages instead of it the BOUND instance where the
+// call asks for decisions only (no plane, no edge values): it proves most pairs free of a conflict at about half the
+// price and hands the rest to list 0 (thal_pairs_row.hip k_pairs_bound; option pair_bound).
+// BoundMirror: a square same-pool block under strand-symmetric tables (ChemEntry::mirror_ok) -- the bound of (a, b)
+// stands for (b, a) as well ("Screen each unordered pair once"), so the bound stage fills each unordered
+// pair once (screen_plan.hpp cuts its launches).
+static int settle_first_stage(msspe_ctx *ctx, ChemEntry *ce, const ScreenBlock &b, ChainRoute &route)
+{
+    const int k = b.k;
+    if (route.first != FirstStage::Int) return MSSPE_OK;
+    const bool row_stage = ce->row_ok && k <= pairs_row_max_k() && ctx->opt.pair_kernel != 2 &&
+                           (k > pairs_row_oob_max_k() || (ctx->lds_reads_zero && ctx->opt.row_oob));
+    if (!row_stage) return MSSPE_OK;
+    route.first = FirstStage::Row;
+    bool bound_stage = !route.end1 && k <= pairs_bound_max_k() && ce->bound_ok && ctx->opt.pair_bound != 0 &&
+                       !b.sinks.dg && !b.sinks.tm && !b.sinks.edge_count;
+    if (bound_stage && ctx->opt.pair_bound == 2) {
+        if (ce->bound_share[k] < 0.f)
+            if (int rc = probe_bound_share(ctx, ce, b)) return rc;
+        bound_stage = ce->bound_share[k] >= 0.f && ce->bound_share[k] <= kBoundShareMax;
+    }
+    if (!bound_stage) return MSSPE_OK;
+    const bool mirror = ce->mirror_ok && ctx->opt.pair_mirror != 0 && k == b.k2 && b.row0 == b.col0 && b.row1 == b.col1 &&
+                        (long)b.sinks.ncols <= mirror_launch_cap(ctx->list_cap);
+    route.first = mirror ? FirstStage::BoundMirror : FirstStage::Bound;
+    route.bound_list = ctx->opt.pair_bound_list != 0;
+    return MSSPE_OK;
+}
+
+// Runs a routed screen over the block: the column sort, the first stage over the launches screen_plan.hpp cuts the
+// block into, and the hand-over lists flushed through route.behind (ListChain) where the plan says so.
+static int run_chain(msspe_ctx *ctx, ChemEntry *ce, ChainRoute route, const ScreenBlock &b)
+{
+    const bool end1 = route.end1;
     const int ncols = b.sinks.ncols, words = b.sinks.words;
     int rc = 0;
-    if ((rc = ensure_workspace(ctx, (size_t)k * (size_t)k2))) return rc;
-    if ((rc = ensure_overflow(ctx, (long)(row1 - row0) * (long)ncols))) return rc;
-    const long kListCap = ctx->list_cap;
+    if ((rc = ensure_workspace(ctx, (size_t)b.k * (size_t)b.k2))) return rc;
+    if ((rc = ensure_overflow(ctx, (long)(b.row1 - b.row0) * (long)ncols))) return rc;
 
     // the conflict bitmap is produced with atomic ORs: clear the caller's block first
     if (b.sinks.bitmap)
-        HIP_TRY(ctx, hipMemsetAsync(b.sinks.bitmap, 0, sizeof(uint64_t) * (size_t)(row1 - row0) * (size_t)words,
+        HIP_TRY(ctx, hipMemsetAsync(b.sinks.bitmap, 0, sizeof(uint64_t) * (size_t)(b.row1 - b.row0) * (size_t)words,
                                     ctx->stream));
     GenericDimerArgs g = dimer_args(ctx, ce, b, end1 ? kModeEnd1 : kModeAny);
-    // A launch covers at most kChunkPairs pairs, and never more than one hand-over list holds (a fixed
-    // list_cap_log2 below 29, or lists shrunk because the card is short of memory): even a launch that handed
-    // every pair on cannot overrun its list.
-    const long chunk_pairs = std::min(kChunkPairs, kListCap);
-    // The block's rows are split evenly over as few launches as the limit allows (a 65,536-row block: nine launches of
-    // about 7,296 rows rather than eight of 8,184 and one of 64; the 8,192 rows a rank of eight owns: one launch, not
-    // 8,184 + 8), in whole row groups of the first-stage kernels (12 or 8 waves per block: no idle waves in the last
-    // tile row of a launch that is not the block's last).
-    const long max_rows = std::max(1L, chunk_pairs / ncols), n_rows_all = (long)row1 - row0;
-    long rows_per_chunk = max_rows;
-    if (n_rows_all > max_rows) {
-        const long cap_rows = max_rows > 24 ? max_rows - max_rows % 24 : max_rows;   // the largest whole-group launch
-        const long n_launch = (n_rows_all + cap_rows - 1) / cap_rows;
-        rows_per_chunk = (n_rows_all + n_launch - 1) / n_launch;
-        if (rows_per_chunk > 24) rows_per_chunk = std::min(cap_rows, (rows_per_chunk + 23) / 24 * 24);
-    } else if (n_rows_all > 0) {
-        rows_per_chunk = n_rows_all;
-    }
-    if (rows_per_chunk < 1) rows_per_chunk = 1;
-    if (!route.fast) {
+    if (route.first == FirstStage::Dense) {
         // generic kernel over the whole block, a band of rows per launch (matrix mode derives
         // (row, col) from sinks.row0 / sinks.col0, so the output base pointers move with the band)
-        for (int r = row0; r < row1; r += (int)rows_per_chunk) {
-            const int r_end = (int)std::min<long>(row1, (long)r + rows_per_chunk);
+        for (const Launch &l : plan_screen(route.first, b.row0, b.row1, b.col0, ncols, ctx->list_cap).launches) {
             GenericDimerArgs gb = g;
-            gb.sinks.row0 = r;
-            gb.n_work = (long)(r_end - r) * (long)ncols;
-            const size_t roff = (size_t)(r - row0);
+            gb.sinks.row0 = l.row0;
+            gb.n_work = l.pairs;
+            const size_t roff = (size_t)(l.row0 - b.row0);
             if (gb.sinks.bitmap) gb.sinks.bitmap += roff * (size_t)words;
             if (gb.sinks.dg) gb.sinks.dg += roff * (size_t)ncols;
             if (gb.sinks.tm) gb.sinks.tm += roff * (size_t)ncols;
@@ -1074,74 +1120,36 @@ static int run_chain(msspe_ctx *ctx, ChemEntry *ce, const ChainRoute &route, con
         }
         return MSSPE_OK;
     }
-    if (!wave_matrix) {
+    if (route.first != FirstStage::Wave) {
         if ((rc = ensure_sort(ctx, (size_t)ncols))) return rc;
-        HIP_TRY(ctx, sort_columns_by_composition(b.pool, col0, ncols, k2, ctx->d_sort_scratch,
+        HIP_TRY(ctx, sort_columns_by_composition(b.pool, b.col0, ncols, b.k2, ctx->d_sort_scratch,
                                                  ctx->sort_scratch_bytes, ctx->d_sorted, ctx->d_perm,
                                                  ctx->stream));
     }
-    // Overflow pairs are collected over several launches and finished together: the list kernels
-    // have a fixed latency floor, and list_cap entries cannot be overrun by list_cap / kChunkPairs
-    // launches even if every pair overflowed.  List 0 (ovf_list) = what the first stage did not answer.
+    HIP_TRY(ctx, hipMemsetAsync(ctx->ovf_count, 0, kOvfCounters * sizeof(uint32_t), ctx->stream));
+    if ((rc = settle_first_stage(ctx, ce, b, route))) return rc;
+    const ScreenPlan plan = plan_screen(route.first, b.row0, b.row1, b.col0, ncols, ctx->list_cap);
+    // List 0 (ovf_list) = what the first stage did not answer.
     // The bound list stage (option pair_bound_list; thal_pairs_bound_list.hip): where it is on, the bound first stage
     // appends the lanes that leave it without a bound of their own to list U -- ovf_list2 with its own counter, once per
     // unordered pair -- and a flush first bounds U, appending what it cannot cull to list 0 behind the first stage's
     // entries; the route then runs from list 0 as ever, with ovf_list2, which U has vacated by then (same stream), as its
     // first output list.  Capacity: a launch that processes P pairs appends at most P entries to U and, to list 0, at
     // most P (2 P mirrored) from the two stages together -- an entry of U becomes at most one (two) of list 0 -- which
-    // is what `pending` budgets against the capacity already.
-    bool bound_list = false;   // set below, once the bound stage is decided
-    uint2 *const u_list = ctx->ovf_list2;
+    // is what the plan's list_entries budget against the capacity already.
+    uint2 *const u_list = route.bound_list ? ctx->ovf_list2 : nullptr;
     uint32_t *const u_count = ctx->ovf_count + kOvfU;
     auto flush = [&]() -> int {
         PairKernelArgs a = pair_args(ctx, ce, b);
-        if (bound_list) {
+        if (route.bound_list) {
             a.overflow_list = ctx->ovf_list;
             a.overflow_count = ctx->ovf_count;
-            a.overflow_cap = (uint32_t)kListCap;
+            a.overflow_cap = (uint32_t)ctx->list_cap;
             HIP_TRY(ctx, launch_pairs_bound_list(a, ce->d_bt, u_list, u_count, ctx->d_reasons + kBoundListStats, nullptr,
                                                  ctx->n_cu, ctx->stream));
         }
-        return ListChain(ctx, ce, end1, ctx->ovf_list, kListCap).run(route.behind, a, g, true);
+        return ListChain(ctx, ce, end1, ctx->ovf_list, ctx->list_cap).run(route.behind, a, g, true);
     };
-    HIP_TRY(ctx, hipMemsetAsync(ctx->ovf_count, 0, kOvfCounters * sizeof(uint32_t), ctx->stream));
-    // The row-specialised first stage, and in front of the list stages instead of it the BOUND instance where the call
-    // asks for decisions only (no plane, no edge values): it proves most pairs free of a conflict at about half the
-    // price and hands the rest to list 0 (thal_pairs_row.hip k_pairs_bound; option pair_bound).
-    const bool row_stage = !wave_matrix && !split && int_stage && ce->row_ok && k <= pairs_row_max_k() && ctx->opt.pair_kernel != 2 &&
-                           (k > pairs_row_oob_max_k() || (ctx->lds_reads_zero && ctx->opt.row_oob));
-    bool bound_stage = row_stage && !end1 && k <= pairs_bound_max_k() && ce->bound_ok && ctx->opt.pair_bound != 0 &&
-                       !b.sinks.dg && !b.sinks.tm && !b.sinks.edge_count;
-    if (bound_stage && ctx->opt.pair_bound == 2) {
-        if (ce->bound_share[k] < 0.f) {
-            // no record for this chemistry, threshold and length: one probe launch over the head of the call's own block
-            // (it counts its survivors and writes nothing else) and one counter read -- the only host round trip
-            // the bound adds, once per record.  A stream that is being captured cannot be waited for: the exact
-            // kernel, and no record.
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            if (hipStreamIsCapturing(ctx->stream, &cs) != hipSuccess) (void)hipGetLastError();
-            if (cs == hipStreamCaptureStatusNone) {
-                PairKernelArgs a = pair_args(ctx, ce, b);
-                a.cols_sorted = ctx->d_sorted;
-                a.perm = ctx->d_perm;
-                a.ncols_sorted = ncols;
-                a.col0 = 0;
-                a.col1 = (int)std::min<long>(ncols, kBoundProbePairs);
-                a.row0 = row0;
-                a.row1 = (int)std::min<long>(row1, (long)row0 + std::max(1L, kBoundProbePairs / (a.col1 - a.col0)));
-                unsigned long long *probe = ctx->d_reasons + kBoundSurvivors + 1;
-                HIP_TRY(ctx, hipMemsetAsync(probe, 0, sizeof *probe, ctx->stream));
-                HIP_TRY(ctx, launch_pairs_bound(a, ce->d_it, ce->d_bt, probe, nullptr, ctx->n_cu, ctx->stream));
-                unsigned long long n_surv = 0;
-                HIP_TRY(ctx, hipMemcpyAsync(&n_surv, probe, sizeof n_surv, hipMemcpyDeviceToHost, ctx->stream));
-                HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-                ce->bound_share[k] = (float)((double)n_surv / ((double)(a.row1 - a.row0) * (double)(a.col1 - a.col0)));
-            }
-        }
-        bound_stage = ce->bound_share[k] >= 0.f && ce->bound_share[k] <= kBoundShareMax;
-    }
-    bound_list = bound_stage && ctx->opt.pair_bound_list != 0;
-    long pending = 0;   // worst-case entries the list may hold
     auto prof_begin = [&]() -> int {
         if (!ctx->prof_on) return MSSPE_OK;
         if (ctx->prof_used == ctx->prof_events.size()) {
@@ -1157,96 +1165,30 @@ static int run_chain(msspe_ctx *ctx, ChemEntry *ce, const ChainRoute &route, con
         if (ctx->prof_on) HIP_TRY(ctx, hipEventRecord(ctx->prof_events[ctx->prof_used++].second, ctx->stream));
         return MSSPE_OK;
     };
-    // A square same-pool block under strand-symmetric tables (ChemEntry::mirror_ok): the bound of (a, b) stands for
-    // (b, a) as well ("Screen each unordered pair once"), so the bound stage fills each unordered pair once.
-    // Rows are taken in the columns' sorted order: row p is sorted[p] (pool index perm[p]) and screens the sorted columns
-    // q >= p; a pair that is not culled is appended in both orders, so a launch that processes P pairs may append 2 P
-    // entries.  The row ranges are cut so that the launches process near-equal pair counts (earlier rows have longer
-    // suffixes), each within half a list and kChunkPairs.
-    const long mirror_cap = std::min(kChunkPairs, kListCap / 2);
-    const bool mirror = bound_stage && ce->mirror_ok && ctx->opt.pair_mirror != 0 && k == k2 && row0 == col0 && row1 == b.col1 &&
-                        (long)ncols <= mirror_cap;
-    if (mirror) {
-        const long n = ncols;
-        auto processed = [&](long p0, long p1) { return (p1 - p0) * n - (p1 * (p1 - 1) - p0 * (p0 - 1)) / 2; };   // sum of n - p
-        const long total = processed(0, n);
-        const long n_launch = (total + mirror_cap - 1) / mirror_cap;
-        const long target = (total + n_launch - 1) / n_launch;
-        for (long p0 = 0; p0 < n;) {
-            // the first row count that reaches the target, in whole groups of 24 rows, within the cap (one row always is)
-            long lo = p0 + 1, hi = n;
-            while (lo < hi) {
-                const long mid = lo + (hi - lo) / 2;
-                if (processed(p0, mid) >= target) hi = mid;
-                else lo = mid + 1;
-            }
-            long p1 = std::min(n, p0 + (lo - p0 + 23) / 24 * 24);
-            while (p1 > p0 + 1 && processed(p0, p1) > mirror_cap) --p1;
-            const long launch_pairs = processed(p0, p1);
-            if (pending + 2 * launch_pairs > kListCap) {
-                if ((rc = flush())) return rc;
-                pending = 0;
-            }
-            PairKernelArgs a = pair_args(ctx, ce, b);
-            a.cols_sorted = ctx->d_sorted;
-            a.perm = ctx->d_perm;
-            a.ncols_sorted = ncols;
-            a.row0 = (int)p0;   // sorted positions, like the columns
-            a.row1 = (int)p1;
-            a.col0 = 0;
-            a.col1 = ncols;
-            a.overflow_list = ctx->ovf_list;
-            a.overflow_count = ctx->ovf_count;
-            a.overflow_cap = (uint32_t)kListCap;
-            if ((rc = prof_begin())) return rc;
+    for (const Launch &l : plan.launches) {
+        if (l.flush_before && (rc = flush())) return rc;
+        const PairKernelArgs a = first_stage_args(ctx, ce, b, l);
+        if ((rc = prof_begin())) return rc;
+        switch (route.first) {
+        case FirstStage::Dense: break;   // (returned above)
+        case FirstStage::Wave: HIP_TRY(ctx, launch_pairs_wave(a, ce->d_st, nullptr, nullptr, ctx->stream, end1)); break;
+        case FirstStage::Split:
+            HIP_TRY(ctx, launch_pairs_split(a, ce->d_st, ctx->d_reasons, ctx->opt.split_lanes, ctx->stream));
+            break;
+        case FirstStage::Fast: HIP_TRY(ctx, launch_pairs_fast(a, ctx->stream, end1)); break;
+        case FirstStage::Int: HIP_TRY(ctx, launch_pairs_int(a, ce->d_it, ctx->d_reasons, ctx->n_cu, ctx->stream)); break;
+        case FirstStage::Row: HIP_TRY(ctx, launch_pairs_row(a, ce->d_it, ctx->d_reasons, ctx->n_cu, ctx->stream)); break;
+        case FirstStage::Bound:
+        case FirstStage::BoundMirror:
             HIP_TRY(ctx, launch_pairs_bound(a, ce->d_it, ce->d_bt, ctx->d_reasons + kBoundSurvivors, nullptr, ctx->n_cu,
-                                            ctx->stream, true, bound_list ? u_list : nullptr, u_count));
-            if ((rc = prof_end())) return rc;
-            pending += 2 * launch_pairs;
-            p0 = p1;
+                                            ctx->stream, route.first == FirstStage::BoundMirror, u_list, u_count));
+            break;
         }
-        ctx->bound_mirrored += n * (n - 1) / 2;
-        if (pending && (rc = flush())) return rc;
-        return MSSPE_OK;
+        if ((rc = prof_end())) return rc;
     }
-    for (int r = row0; r < row1; r += (int)rows_per_chunk) {
-        const int r_end = (int)std::min<long>(row1, (long)r + rows_per_chunk);
-        for (long q0 = 0; q0 < ncols; q0 += chunk_pairs) {   // sorted-column index range (one chunk unless a row is longer than a launch)
-            const long q_end = std::min<long>(ncols, q0 + chunk_pairs);
-            const long launch_pairs = (long)(r_end - r) * (q_end - q0);
-            if (pending + launch_pairs > kListCap) {
-                if ((rc = flush())) return rc;
-                pending = 0;
-            }
-            PairKernelArgs a = pair_args(ctx, ce, b);
-            a.cols_sorted = ctx->d_sorted;
-            a.perm = ctx->d_perm;
-            a.ncols_sorted = ncols;
-            a.row0 = r;
-            a.row1 = r_end;
-            a.col0 = (int)q0;
-            a.col1 = (int)q_end;
-            a.overflow_list = ctx->ovf_list;
-            a.overflow_count = ctx->ovf_count;
-            a.overflow_cap = (uint32_t)kListCap;
-            if ((rc = prof_begin())) return rc;
-            if (wave_matrix) {
-                a.col0 = col0 + (int)q0;   // pool columns, no composition sort
-                a.col1 = col0 + (int)q_end;
-                HIP_TRY(ctx, launch_pairs_wave(a, ce->d_st, nullptr, nullptr, ctx->stream, end1));
-            } else if (split) HIP_TRY(ctx, launch_pairs_split(a, ce->d_st, ctx->d_reasons, ctx->opt.split_lanes, ctx->stream));
-            else if (bound_stage)
-                HIP_TRY(ctx, launch_pairs_bound(a, ce->d_it, ce->d_bt, ctx->d_reasons + kBoundSurvivors, nullptr, ctx->n_cu,
-                                                ctx->stream, false, bound_list ? u_list : nullptr, u_count));
-            else if (row_stage) HIP_TRY(ctx, launch_pairs_row(a, ce->d_it, ctx->d_reasons, ctx->n_cu, ctx->stream));
-            else if (int_stage) HIP_TRY(ctx, launch_pairs_int(a, ce->d_it, ctx->d_reasons, ctx->n_cu, ctx->stream));
-            else HIP_TRY(ctx, launch_pairs_fast(a, ctx->stream, end1));
-            if ((rc = prof_end())) return rc;
-            pending += launch_pairs;
-        }
-    }
-    if (pending && (rc = flush())) return rc;
-    return MSSPE_OK;
+    ctx->bound_mirrored += plan.mirrored;
+    // every launch leaves pairs pending, and a flush is always followed by a launch: the lists are never empty here
+    return plan.launches.empty() ? MSSPE_OK : flush();
 }
 
 // What both screens check first, and the chemistry's cache entry of the screen's kind; *ce stays null for an empty
@@ -1286,20 +1228,21 @@ static int cross_dimer_impl(msspe_ctx *ctx, const ScreenBlock &b, const msspe_ch
     // kernel nor the register-table chain applies (29 .. 32 bases, parameter files off the grid)
     const bool wave = wave_ok(ctx, ce, kmax);
     const bool wave_matrix = wave && !split && (rect || k > pairs_fast_max_k() || chem->max_loop < 2 * k - 4);
+    const bool int_stage = !split && ce->int_ok && !(ctx->opt.pair_kernel == 1);
     ChainRoute route;
     route.end1 = false;
     // the register-table / integer / row first stages are square-only: a rectangle that neither the split nor the
     // wave kernel takes goes to the dense kernel
-    route.fast = split || wave_matrix || (!rect && reg_tables_ok(ctx, ce, k));
-    route.split = split;
-    route.wave_matrix = wave_matrix;
-    route.int_stage = !split && ce->int_ok && !(ctx->opt.pair_kernel == 1);
+    if (wave_matrix) route.first = FirstStage::Wave;
+    else if (split) route.first = FirstStage::Split;
+    else if (rect || !reg_tables_ok(ctx, ce, k)) route.first = FirstStage::Dense;
+    else route.first = int_stage ? FirstStage::Int : FirstStage::Fast;   // Int: settle_first_stage picks the instance
     StageList &s = route.behind;
     if (split || wave_matrix) {
         // long oligos: what the split kernel handed on is answered in f64 by one wave per pair; the dense kernel
         // takes what is left (two self-complementary oligos, huge tables)
         if (split && wave) s.add(ListStage::Wave);
-    } else if (route.int_stage) {
+    } else if (int_stage) {
         s.add(ListStage::IntList);
         // small screens (the reference's are at most 2,000^2): the short chain.  What the integer list stage leaves
         // (some ten thousand pairs) goes straight to one wave per pair -- each of the three register-table stages
@@ -1335,10 +1278,7 @@ static int cross_dimer_end_impl(msspe_ctx *ctx, const ScreenBlock &b, const mssp
     const bool wave = wave_ok(ctx, ce, std::max(b.k, b.k2));
     ChainRoute route;
     route.end1 = true;
-    route.split = false;
-    route.int_stage = false;
-    route.wave_matrix = wave && !reg;
-    route.fast = reg || route.wave_matrix;
+    route.first = reg ? FirstStage::Fast : wave ? FirstStage::Wave : FirstStage::Dense;
     if (reg) {
         route.behind.add(ListStage::Wide);
         if (wave) route.behind.add(ListStage::Wave);
@@ -1407,18 +1347,13 @@ static int cross_dimer_bound_plane(msspe_ctx *ctx, const uint64_t *d_pool, int n
     if ((rc2 = ensure_sort(ctx, (size_t)ncols))) return rc2;
     HIP_TRY(ctx, sort_columns_by_composition(b.pool, col0, ncols, k, ctx->d_sort_scratch, ctx->sort_scratch_bytes,
                                              ctx->d_sorted, ctx->d_perm, ctx->stream));
-    PairKernelArgs a = pair_args(ctx, ce, b);
-    a.cols_sorted = ctx->d_sorted;
-    a.perm = ctx->d_perm;
-    a.ncols_sorted = ncols;
-    a.col0 = 0;
-    a.col1 = ncols;
+    // one launch over the whole block (the diagnostic form appends nothing to list 0)
+    const PairKernelArgs a = first_stage_args(ctx, ce, b, Launch{row0, row1, 0, ncols, 0, 0, false});
     if (!with_list) {
         HIP_TRY(ctx, launch_pairs_bound(a, ce->d_it, ce->d_bt, nullptr, d_bound, ctx->n_cu, ctx->stream));
         return MSSPE_OK;
     }
     uint32_t *const u_count = ctx->ovf_count + kOvfU;
-    a.overflow_cap = (uint32_t)ctx->list_cap;
     HIP_TRY(ctx, hipMemsetAsync(u_count, 0, sizeof(uint32_t), ctx->stream));
     HIP_TRY(ctx, launch_pairs_bound(a, ce->d_it, ce->d_bt, nullptr, d_bound, ctx->n_cu, ctx->stream, false, ctx->ovf_list2, u_count));
     HIP_TRY(ctx, launch_pairs_bound_list(a, ce->d_bt, ctx->ovf_list2, u_count, nullptr, d_bound, ctx->n_cu, ctx->stream));
@@ -3602,6 +3537,34 @@ int msspe_host_table_routes(const char *params_path, const msspe_chem *chem, int
     out[4] = r.split_max_k > 0;
     out[5] = r.split_max_k;
     out[6] = r.wave_max_k;
+    return MSSPE_OK;
+}
+
+int msspe_host_screen_plan(int first_stage, int row0, int row1, int col0, int ncols, int64_t list_cap, int64_t *out,
+                           int capacity, int *n_out)
+{
+    // host only: the first-stage launches run_chain issues for this block under hand-over lists of list_cap entries
+    if (!n_out || capacity < 0 || (capacity > 0 && !out)) return MSSPE_ERR_ARG;
+    *n_out = 0;
+    if (first_stage < 0 || first_stage > (int)FirstStage::BoundMirror || row0 < 0 || row1 <= row0 || col0 < 0 || ncols < 1 ||
+        (long)col0 + ncols > (long)INT32_MAX || list_cap < 1)
+        return MSSPE_ERR_ARG;
+    const FirstStage first = (FirstStage)first_stage;
+    if (first == FirstStage::BoundMirror && (row0 != col0 || row1 - row0 != ncols || ncols > mirror_launch_cap((long)list_cap)))
+        return MSSPE_ERR_ARG;   // settle_first_stage's conditions on the block
+    ScreenPlan plan;
+    try {
+        plan = plan_screen(first, row0, row1, col0, ncols, (long)list_cap);
+    } catch (const std::bad_alloc &) {
+        return MSSPE_ERR_NOMEM;
+    }
+    if (plan.launches.size() > (size_t)INT32_MAX) return MSSPE_ERR_NOMEM;
+    *n_out = (int)plan.launches.size();
+    if (*n_out > capacity) return MSSPE_ERR_CAPACITY;
+    for (const Launch &l : plan.launches) {
+        const int64_t row[7] = {l.row0, l.row1, l.col0, l.col1, l.pairs, l.list_entries, l.flush_before ? 1 : 0};
+        out = std::copy(row, row + 7, out);
+    }
     return MSSPE_OK;
 }
 

@@ -23,7 +23,7 @@ EXPORTS = [
     "msspe_cross_dimer_end_ab_dev", "msspe_cross_dimer_end_ab", "msspe_t_cut",
     "msspe_conflict_cover_dev", "msspe_conflict_cover",
     "msspe_conflict_tubes_dev", "msspe_conflict_tubes",
-    "msspe_last_overflow_pairs", "msspe_pair_stage_stats", "msspe_pair_stage_samples", "msspe_host_pair_tables", "msspe_host_table_routes", "msspe_host_split_tables", "msspe_device_put_rows", "msspe_segment_coverage", "msspe_segment_coverage_dev",
+    "msspe_last_overflow_pairs", "msspe_pair_stage_stats", "msspe_pair_stage_samples", "msspe_host_pair_tables", "msspe_host_table_routes", "msspe_host_screen_plan", "msspe_host_split_tables", "msspe_device_put_rows", "msspe_segment_coverage", "msspe_segment_coverage_dev",
     "msspe_device_put", "msspe_device_get", "msspe_device_free", "msspe_thal_detail_pairs", "msspe_profile_enable", "msspe_profile_read",
     "msspe_oligo_stats_dev", "msspe_oligo_stats",
     "msspe_kmer_candidates", "msspe_kmer_candidates_dev", "msspe_round_g_f32",
@@ -291,6 +291,7 @@ def load_library() -> C.CDLL:
                 .replace("_background_amplicons", "_background_amplicons_flank")).argtypes = at[:cut] + [C.c_int] + at[cut:]
     L.msspe_device_get.argtypes = [vp, vp, C.c_size_t, vp]
     L.msspe_host_table_routes.argtypes = [C.c_char_p, C.POINTER(Chem), C.POINTER(C.c_int32)]
+    L.msspe_host_screen_plan.argtypes = [C.c_int] * 5 + [C.c_int64, vp, C.c_int, C.POINTER(C.c_int)]
     L.msspe_thal_detail_pairs.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(Chem), C.c_int, vp]
     L.msspe_round_g_f32.restype = C.c_float
     L.msspe_round_g_f32.argtypes = [C.c_double]
@@ -379,6 +380,25 @@ def host_table_routes(params_path: str | None = None, chem: Chem | None = None) 
     if rc:
         raise MsspeError(rc, f"msspe_host_table_routes({params_path})")
     return dict(zip(TABLE_ROUTE_KEYS, list(out)[:7]))
+
+
+FIRST_STAGES = ("dense", "wave", "split", "fast", "int", "row", "bound", "bound_mirror")   # csrc/screen_plan.hpp FirstStage
+SCREEN_PLAN_COLUMNS = ("row0", "row1", "col0", "col1", "pairs", "list_entries", "flush_before")
+
+
+def host_screen_plan(first_stage: str, row0: int, row1: int, col0: int, ncols: int, list_cap: int) -> np.ndarray:
+    """The first-stage launches of a pair screen over rows [row0, row1) x ncols columns from col0 under hand-over lists
+    of list_cap entries, as the screens execute them (no device needed): msspe_host_screen_plan.  int64 (launches, 7),
+    columns SCREEN_PLAN_COLUMNS."""
+    n = C.c_int(64)
+    while True:
+        out = np.zeros((n.value, 7), dtype=np.int64)
+        rc = load_library().msspe_host_screen_plan(FIRST_STAGES.index(first_stage), row0, row1, col0, ncols, list_cap,
+                                                   out.ctypes.data, len(out), C.byref(n))
+        if rc == 0:
+            return out[:n.value]
+        if rc != 5:     # MSSPE_ERR_CAPACITY: n holds the launch count
+            raise MsspeError(rc, f"msspe_host_screen_plan({first_stage}, {row0}, {row1}, {col0}, {ncols}, {list_cap})")
 
 
 def host_bound_tables(params_path: str | None = None, chem: Chem | None = None, threshold: float = -9000.0) -> dict:

@@ -3,7 +3,7 @@
 The first stage for 13-, 14- and 15-mers is k_pairs_row (csrc/thal_pairs_row.hip kernel_body): a work item is one
 row primer times a segment of up to kSegGroups = 256 column groups of 64 lanes, so a segment holds 16,384 columns of
 the composition-sorted order; the last group of a pool that is not a multiple of 64 has idle lanes, and the last
-segment of a pool that is not a multiple of 16,384 is short.  run_chain (csrc/capi.cpp) splits the block's rows into
+segment of a pool that is not a multiple of 16,384 is short.  plan_screen (csrc/screen_plan.hpp) splits the block's rows into
 launches of at most min(kChunkPairs, list_cap) = 2^29 pairs (list_cap_log2 = 29 pins the list size), in whole groups
 of 24 rows, the last launch taking the remainder.  pool_sort.hip block_side picks the side of the composition blocks
 the columns are sorted by: about 64 columns per block, 1 (every composition on its own) from 64 columns per
@@ -22,7 +22,8 @@ The sizes below sit on those boundaries (segs: segments of a full-width row; tai
     15  20,011   312 + 43    2     3,627   2  20,011                       two segments with the coarse sort
 
 (groups: whole column groups + lanes of the partial one.)  test_geometry_of_the_case recomputes the table's block
-sides, launch counts and segment counts from restatements of the code, so that the table cannot drift from what runs.
+sides and segment counts from restatements of the code and takes the launches from the engine's own plan
+(msspe_host_screen_plan), so that the table cannot drift from what runs.
 Bar, as everywhere in the suite: the oracle's decisions bit for bit, dG planes bit for bit.
 """
 import numpy as np
@@ -31,9 +32,9 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 THR = -9000.0
-CHUNK_PAIRS = 1 << 29          # capi.cpp kChunkPairs; the engine runs with list_cap_log2 = 29
+CHUNK_PAIRS = 1 << 29          # screen_plan.hpp kChunkPairs; the engine runs with list_cap_log2 = 29
 SEG_COLS = 256 * 64            # thal_pairs_row.hip kSegGroups column groups of 64 lanes
-ROW_GROUP = 24                 # capi.cpp run_chain: launches in whole row groups of 24
+ROW_GROUP = 24                 # screen_plan.hpp kRowGroup: launches in whole row groups of 24
 
 # name -> (k, n, block side, launches, segments)
 CASES = {
@@ -48,27 +49,13 @@ CASES = {
 }
 
 
-# ---- restatements of the host code that decides the geometry ------------------------------------------------------
-
-def rows_per_launch(n_rows: int, ncols: int, chunk_pairs: int = CHUNK_PAIRS) -> int:
-    """capi.cpp run_chain, lines 664-675: the block's rows spread evenly over as few launches of at most chunk_pairs
-    pairs as possible, rounded up to whole groups of 24 rows (but never past the largest whole-group launch)."""
-    max_rows = max(1, chunk_pairs // ncols)
-    rows = max_rows
-    if n_rows > max_rows:
-        cap_rows = max_rows - max_rows % ROW_GROUP if max_rows > ROW_GROUP else max_rows
-        n_launch = -(-n_rows // cap_rows)
-        rows = -(-n_rows // n_launch)
-        if rows > ROW_GROUP:
-            rows = min(cap_rows, -(-rows // ROW_GROUP) * ROW_GROUP)
-    elif n_rows > 0:
-        rows = n_rows
-    return max(rows, 1)
-
+# ---- the launch plan, and restatements of the host code that sorts the columns ------------------------------------
 
 def launch_starts(row0: int, row1: int, ncols: int) -> list[int]:
-    """First row of every launch of the block (capi.cpp run_chain's launch loop)."""
-    return list(range(row0, row1, rows_per_launch(row1 - row0, ncols)))
+    """First row of every launch of the block: the plan the engine executes (csrc/screen_plan.hpp plan_screen, read
+    through msspe_host_screen_plan) for the row kernel under a list of 2^29 entries."""
+    from msspe_amd import capi
+    return capi.host_screen_plan("row", row0, row1, 0, ncols, CHUNK_PAIRS)[:, 0].tolist()
 
 
 def block_side(ncols: int, k: int) -> int:
@@ -284,7 +271,7 @@ def case(request, m, eng):
 
 
 def test_geometry_of_the_case(case, eng):
-    """The module docstring's table from the restated code; the row kernel is the first stage."""
+    """The module docstring's table from the engine's plan and the restated sort; the row kernel is the first stage."""
     k, n, g, n_launch, n_seg = CASES[case["name"]]
     assert block_side(n, k) == g
     starts = launch_starts(0, n, n)

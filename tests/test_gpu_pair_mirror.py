@@ -160,6 +160,29 @@ def test_several_launches_and_flushes(eng, m, oracle, oracle_tables, mirror):
     np.testing.assert_array_equal(counts, want.sum(1).astype(np.uint32))
 
 
+@pytest.mark.parametrize("bound", [1, 0])
+@pytest.mark.parametrize("mirror", ["auto", 0])
+def test_launch_count_is_the_plans(eng, m, mirror, bound):
+    """The same screen, pair_bound on and off: the first-stage launches the profile counts are the launches of the plan
+    (csrc/screen_plan.hpp through msspe_host_screen_plan) for the stage that ran -- 3 in each of the four cases."""
+    pool = m.synth.pool_strings(m.synth.random_pool(1500, 13, seed=5))
+    stage = "row" if bound == 0 else "bound_mirror" if mirror == "auto" else "bound"
+    plan = m.capi.host_screen_plan(stage, 0, 1500, 0, 1500, 1 << 20)
+    eng.set_option("list_cap_log2", 20)
+    eng.profile_enable(True)
+    try:
+        eng.profile_read()
+        _, _, stats = screen(eng, pool, m.Chem.ntthal(), mirror, bound)
+        launches, _ = eng.profile_read()
+    finally:
+        eng.profile_enable(False)
+        eng.set_option("list_cap_log2", 0)
+    print(f"pair_bound={bound} pair_mirror={mirror}: {launches} first-stage launches, plan '{stage}' has {len(plan)}")
+    assert stats["bound_mirrored"] == (1500 * 1499 // 2 if stage == "bound_mirror" else 0)
+    assert (stats["bound_survivors"] > 0) == (bound == 1)      # the stage the plan was asked for is the one that ran
+    assert launches == len(plan) == 3
+
+
 def test_two_column_segments(eng, m, oracle, oracle_tables):
     """16,449 oligos: 256 column groups, one more group and one more lane.  Mirror on and off agree everywhere; 64 seeded
     rows are the oracle's."""

@@ -8,8 +8,8 @@ Run once on a CPU machine (no GPU; about 12 minutes on 8 cores, a few MB of memo
 The rows are chosen where the row kernel's 65,536^2 call can go wrong without the small pools noticing:
   G  group_rows(65536, 32, 0): eight 256-row groups spread over the whole range, half of them at or above
      32,768 (block offsets past 2^31 pairs); a subset of rank 0 of 8 under the dealt-rows rule;
-  B  16 rows on each side of every launch boundary of the 65,536-row call (csrc/capi.cpp splits a block into
-     launches of at most kChunkPairs pairs, in whole 24-row groups: restated in launch_boundaries below);
+  B  16 rows on each side of every launch boundary of the 65,536-row call (csrc/screen_plan.hpp splits a block into
+     launches of at most kChunkPairs pairs, in whole 24-row groups: launch_boundaries below asks the library);
   T  the last 32 rows.
 Every row is screened against all 65,536 columns.  Per row the fixture keeps the conflict count and an 8-byte
 BLAKE2b digest of the row's decisions packed little-endian into bytes: the same bytes as row r of the engine's
@@ -32,22 +32,14 @@ sys.path.insert(0, str(ROOT / "open-msspe-design_amd"))
 sys.path.insert(0, str(ROOT / "oracle"))
 
 N, K, THRESHOLD = 65536, 13, -9000.0
-K_CHUNK_PAIRS = 1 << 29         # csrc/capi.cpp kChunkPairs
-ROW_GROUP = 24                  # launches other than the last cover whole groups of 24 rows
 BAND, TAIL = 16, 32
 
 
-def launch_boundaries(n_rows: int, ncols: int, chunk_pairs: int = K_CHUNK_PAIRS) -> list[int]:
-    """First rows (block-relative) of the second and later launches of a decisions-only call over n_rows x ncols."""
-    max_rows = max(1, chunk_pairs // ncols)
-    if n_rows <= max_rows:
-        return []
-    cap_rows = max_rows - max_rows % ROW_GROUP if max_rows > ROW_GROUP else max_rows
-    n_launch = -(-n_rows // cap_rows)
-    per = -(-n_rows // n_launch)
-    if per > ROW_GROUP:
-        per = min(cap_rows, -(-per // ROW_GROUP) * ROW_GROUP)
-    return list(range(per, n_rows, per))
+def launch_boundaries(n_rows: int, ncols: int) -> list[int]:
+    """First rows (block-relative) of the second and later launches of a decisions-only call over n_rows x ncols: the
+    engine's own plan for lists of 2^30 entries, which a screen of this size gets (host code, no GPU)."""
+    from msspe_amd import capi
+    return capi.host_screen_plan("row", 0, n_rows, 0, ncols, 1 << 30)[1:, 0].tolist()
 
 
 def row_sets(n: int = N) -> dict[str, list[int]]:

@@ -14,7 +14,7 @@ RAW = ROOT / "gpurun_out" / "profiles_raw"
 OUT = ROOT / "profiles"
 ROUND = sys.argv[1] if len(sys.argv) > 1 else "r01"
 kProbeChecks = 65536.0 * 65536.0       # the counter passes run the bench itself: one step of the 65,536-primer pool
-kLaunchesPerStep = 9.0                 # ... which the engine cuts into nine equal first-stage launches (capi.cpp kChunkPairs)
+kLaunchesPerStep = 9.0                 # ... which the engine cuts into nine equal first-stage launches (csrc/screen_plan.hpp plan_screen)
 kLaunchChecks = kProbeChecks / kLaunchesPerStep   # the launch every per-launch figure below belongs to
 KERNEL = "k_pairs_row"
 KERNEL_MATCH = "k_pairs_row<"   # the row-specialised first stage (thal_pairs_row.hip)
