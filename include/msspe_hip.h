@@ -112,6 +112,8 @@ const char *msspe_version(void);
  *                                 made with 2^this keys (20) and doubles as needed; no result depends on it
  *   "panel_thin_matrix_max_mb" "1".."1048576"  msspe_panel_thin*: the most its incidence matrix may take, in MB
  *                                 (8192); a call that needs more returns MSSPE_ERR_CAPACITY
+ *   "thin_thal_unique" "0" | "1"  msspe_panel_thin_thal*: score each distinct (primer, template) pair of a slab once
+ *                                 (1) or every match (0); no result depends on it
  *   "split_lanes"    "0" | "2" | "4" | "8"
  *   "split_list"     "0" | "1"    short oligos: tables too large for the integer list stage go to the split-table
  *                                 kernel's list mode (1) or straight to the f64 kernels (0)
@@ -1025,6 +1027,65 @@ int msspe_segment_coverage_thal_packed_dev(msspe_ctx *ctx, const uint64_t *d_pac
                                            double *t_best_out, uint32_t *primer_segments_out,
                                            uint32_t *primer_held_out, msspe_scored_match *matches, uint64_t capacity,
                                            uint64_t *count_out);
+
+/* ---- a panel thinned on the segments it holds at a temperature (engine extension, no reference counterpart) ----
+ * msspe_panel_thin* keeps what the string rule's coverage needs; msspe_segment_coverage_thal* showed that a match
+ * within M mismatches may score anywhere from 0 C to well above the reaction temperature, so a panel thinned on the
+ * string rule may hold fewer segments afterwards than it did before.  These calls run the same greedy loop over the
+ * HELD incidence.  The inputs are msspe_panel_thin*'s, plus chem, mode (1 ANY, 2 END1) and tm_threshold as in
+ * msspe_segment_coverage_thal*; max_mismatches and exact_3p are the prefilter that says what a match is.
+ *   H[p][s] = 1 when primer p has at least one STABLE match in segment s under exactly msspe_segment_coverage_thal*'s
+ *     rule: that rule fixes the match, the template oligo, t_match = max(0, t) and "stable iff
+ *     t_match > msspe_t_cut(tm_threshold)".  p, n and s as in msspe_panel_thin*.  A row sum of H is that call's
+ *     primer_held_out[p]; a threshold <= 0 makes H the incidence I of msspe_panel_thin*.
+ *   The greedy loop is msspe_panel_thin*'s, unchanged, over H instead of I: forced rows cover first and are never
+ *     picked, a round picks the unforced, unpicked p of greatest gain, ties to the LOWEST index, until that gain is
+ *     below thin->min_gain; keep_out, order_out, gain_out, *n_picked_out, covered_out, *covered_all_out (|OR of all
+ *     H[p]|) and *covered_kept_out as there.
+ * GUARANTEE: at min_gain 1 covered_out marks exactly the segments where the whole set's msspe_segment_coverage_thal*
+ * held_out == 2, and the two counts are equal.  Stability is a property of (primer, template) alone, so
+ * msspe_segment_coverage_thal* on the kept primers gives held_out == 2 on exactly the same segments: thinning loses no
+ * held segment.  What it does NOT preserve: t_best per segment (a segment held at 45 C before may be held at 31 C
+ * afterwards), and the segments that only had unstable matches (held_out == 1 may become 0).
+ * Memory and routing: the matches pass through the work list of msspe_segment_coverage_thal* in slabs, with its
+ * split-and-relist rule for a slab that overruns; the matrix is msspe_panel_thin*'s, under the same
+ * "panel_thin_matrix_max_mb".  msspe_set_option "thin_thal_unique" ("0" / "1", default "1"): a slab's matches are
+ * sorted by (primer, template word) and each distinct pair is scored once -- an alignment of related genomes repeats
+ * its templates row after row; with "0" every match is scored, as msspe_segment_coverage_thal* does.  H, and so every
+ * output, is the same either way.  force_generic, wave_kernel, list_cap_log2 and site_list_cap_log2 apply to the
+ * scoring as there.  The call shares the context's work list and the thinning's buffers, leaves the context fit for any
+ * other call, and allocates nothing once its buffers have grown to a call's size.
+ * Errors: those of msspe_panel_thin* and of msspe_segment_coverage_thal*: MSSPE_ERR_K for k outside 2..31;
+ * MSSPE_ERR_ARG for a mode outside {1, 2}, a NULL chem, thin or output array, min_gain < 1, or a window of more than
+ * 2^26 positions; MSSPE_ERR_TABLES as every dimer call; MSSPE_ERR_CAPACITY when the matrix needs more than
+ * panel_thin_matrix_max_mb, or when one segment group against one primer overruns the work list (msspe_last_error
+ * names "site_list_cap_log2" and both figures).  n == 0 or no segments: as msspe_panel_thin*.
+ * msspe_get_info, the last call: "panel_thin_thal_matches" (matches listed), "panel_thin_thal_unique_pairs" (pairs
+ * scored: per slab the distinct ones, or with thin_thal_unique 0 the matches), "panel_thin_thal_slabs" /
+ * "panel_thin_thal_redone" (slabs scored / listed again in parts), "panel_thin_thal_list_us" /
+ * "panel_thin_thal_unique_us" / "panel_thin_thal_score_us" / "panel_thin_thal_fold_us" / "panel_thin_thal_rounds_us"
+ * (device time of the listing, the templates with the sort and run search, the scoring, the fold, the rounds);
+ * "panel_thin_rounds", "panel_thin_groups" and "panel_thin_gain0_us" describe this call too;
+ * "thin_thal_unique" is the option's value. */
+int msspe_panel_thin_thal(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len, const msspe_kmer_opt *opt,
+                          const msspe_mismatch_opt *mm, const msspe_thin_opt *thin, const msspe_chem *chem, int mode,
+                          float tm_threshold, const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words,
+                          int n_rev, const uint8_t *forced, uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out,
+                          int *n_picked_out, uint8_t *covered_out, long long *covered_all_out,
+                          long long *covered_kept_out);
+int msspe_panel_thin_thal_dev(msspe_ctx *ctx, const uint8_t *d_seqs, int n_seq, size_t seq_len,
+                              const msspe_kmer_opt *opt, const msspe_mismatch_opt *mm, const msspe_thin_opt *thin,
+                              const msspe_chem *chem, int mode, float tm_threshold, const uint64_t *fwd_words,
+                              int n_fwd, const uint64_t *rev_words, int n_rev, const uint8_t *forced,
+                              uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out, int *n_picked_out,
+                              uint8_t *covered_out, long long *covered_all_out, long long *covered_kept_out);
+int msspe_panel_thin_thal_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
+                                     const msspe_kmer_opt *opt, const msspe_mismatch_opt *mm,
+                                     const msspe_thin_opt *thin, const msspe_chem *chem, int mode, float tm_threshold,
+                                     const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
+                                     const uint8_t *forced, uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out,
+                                     int *n_picked_out, uint8_t *covered_out, long long *covered_all_out,
+                                     long long *covered_kept_out);
 
 /* ---- several devices of one node ----------------------------------------------------------
  *

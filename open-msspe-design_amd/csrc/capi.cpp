@@ -33,6 +33,7 @@
 #include "nn_params.hpp"
 #include "thal_dense.hpp"
 #include "panel_thin.hpp"
+#include "panel_thin_thal.hpp"
 #include "screen_plan.hpp"
 #include "tube_split.hpp"
 
@@ -110,6 +111,7 @@ struct EngineOptions {
     int site_list_cap_log2 = 22;  // msspe_background_thal*: work list of 2^this sites (44 bytes each: 185 MB)
     int amplicon_keys_cap_log2 = 20;  // msspe_background_amplicons*: the stable-key buffer starts at 2^this keys and doubles
     long panel_thin_matrix_max_mb = 8192;   // msspe_panel_thin*: the incidence matrix may take this much, else MSSPE_ERR_CAPACITY
+    bool thin_thal_unique = true;   // msspe_panel_thin_thal*: a slab's matches are sorted and each distinct (primer, template) is scored once
 };
 
 struct msspe_ctx {
@@ -148,6 +150,8 @@ struct msspe_ctx {
     CoverStage cover;                  // msspe_conflict_cover*: the symmetrised bitmap and the round state
     TubeStage tubes;                   // msspe_conflict_tubes*: its round state (the graph lives in cover's buffers)
     PanelThin thin;                    // msspe_panel_thin*: the incidence matrix, covered words, gains and round state
+    PanelThinThal thin_thal;           // msspe_panel_thin_thal*: the sorted order, run slots and rocPRIM storage of a slab (its
+                                       // matrix and round state are thin's, its work list site_work, its plane words cov_thal's)
     CoverageThal cov_thal;             // msspe_segment_coverage_thal*: plane words, per-segment words, cell bitmaps,
                                        // counters, the caller's list (its work list is site_work below)
     // msspe_background_thal*: the work list (site records, their pairs, raw dG and t), the site pool [primers | site
@@ -767,6 +771,9 @@ int msspe_set_option(msspe_ctx *ctx, const char *key, const char *value)
     } else if (k == "panel_thin_matrix_max_mb") {
         if (!is_num || num < 1 || num > (1L << 20)) return bad();
         ctx->opt.panel_thin_matrix_max_mb = num;
+    } else if (k == "thin_thal_unique") {
+        if (!is_num || num < 0 || num > 1) return bad();
+        ctx->opt.thin_thal_unique = num != 0;
     } else if (k == "row_oob") {
         if (!is_num || num < 0 || num > 1) return bad();
         ctx->opt.row_oob = num != 0;
@@ -845,6 +852,16 @@ int msspe_get_info(msspe_ctx *ctx, const char *key, long long *value_out)
     else if (k == "panel_thin_incidence_us") *value_out = ctx->thin.phase_us()[0];
     else if (k == "panel_thin_gain0_us") *value_out = ctx->thin.phase_us()[1];
     else if (k == "panel_thin_rounds_us") *value_out = ctx->thin.phase_us()[2];
+    else if (k == "thin_thal_unique") *value_out = ctx->opt.thin_thal_unique ? 1 : 0;
+    else if (k == "panel_thin_thal_matches") *value_out = ctx->thin_thal.matches;
+    else if (k == "panel_thin_thal_unique_pairs") *value_out = ctx->thin_thal.unique_pairs;
+    else if (k == "panel_thin_thal_slabs") *value_out = ctx->thin_thal.slabs;
+    else if (k == "panel_thin_thal_redone") *value_out = ctx->thin_thal.redone;
+    else if (k == "panel_thin_thal_list_us") *value_out = ctx->thin_thal.list_us;
+    else if (k == "panel_thin_thal_unique_us") *value_out = ctx->thin_thal.unique_us;
+    else if (k == "panel_thin_thal_score_us") *value_out = ctx->thin_thal.score_us;
+    else if (k == "panel_thin_thal_fold_us") *value_out = ctx->thin_thal.fold_us;
+    else if (k == "panel_thin_thal_rounds_us") *value_out = ctx->thin.phase_us()[2];
     else if (k == "pair_bound") *value_out = ctx->opt.pair_bound;
     else if (k == "pair_mirror") *value_out = ctx->opt.pair_mirror;
     else if (k == "pair_bound_list") *value_out = ctx->opt.pair_bound_list;
@@ -914,6 +931,7 @@ void msspe_destroy(msspe_ctx *ctx)
         ctx->cover.release();
         ctx->tubes.release();
         ctx->thin.release();
+        ctx->thin_thal.release();
         ctx->mm_cov.release();
         ctx->cov_thal.release();
         ctx->background.release();
@@ -3153,6 +3171,169 @@ int coverage_thal_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t se
     return MSSPE_OK;
 }
 
+// msspe_panel_thin_thal*: coverage_thal_view's slab loop into the held incidence matrix, then PanelThin::rounds over
+// it.  No per-segment word, cell plane or record list is kept: a slab's matches are listed, their templates cut
+// (CoverageThal::oligos), with thin_thal_unique the distinct (primer, template) pairs of the slab found
+// (PanelThinThal::unique) and only those scored, and every stable match ORs its bit into the matrix, which is zeroed
+// once: a slab split by groups or by primers adds to the words the others wrote.
+int panel_thin_thal_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t seq_len, const msspe_kmer_opt *opt,
+                         const msspe_mismatch_opt *mm, const msspe_thin_opt *thin, const msspe_chem *chem, int mode,
+                         float tm_threshold, const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words,
+                         int n_rev, const uint8_t *forced, uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out,
+                         int *n_picked_out, uint8_t *covered_out, long long *covered_all_out,
+                         long long *covered_kept_out)
+{
+    if (!opt || !mm || !thin || !chem || !keep_out || !order_out || !gain_out || !n_picked_out || n_fwd < 0 ||
+        n_rev < 0 || (n_fwd && !fwd_words) || (n_rev && !rev_words))
+        return fail(ctx, MSSPE_ERR_ARG, "panel thin thal: null argument");
+    if (thin->min_gain < 1) return fail(ctx, MSSPE_ERR_ARG, "panel thin thal: min_gain must be at least 1");
+    if (mode != 1 && mode != 2) return fail(ctx, MSSPE_ERR_ARG, "panel thin thal: mode must be 1 (ANY) or 2 (END1)");
+    auto &tt = ctx->thin_thal;
+    tt.matches = tt.unique_pairs = tt.slabs = tt.redone = 0;
+    tt.list_us = tt.unique_us = tt.score_us = tt.fold_us = 0;
+    *n_picked_out = 0;
+    if (covered_all_out) *covered_all_out = 0;
+    if (covered_kept_out) *covered_kept_out = 0;
+    const int k = opt->kmer_size;
+    if (k < 2 || k > 31) return fail(ctx, MSSPE_ERR_K, "panel thin thal: unsupported k (need 2 <= k <= 31)");
+    std::string err;
+    long P = 0;
+    int rc = MismatchCoverage::check(n_seq, seq_len, *opt, mm->max_mismatches, mm->exact_3p, fwd_words, n_fwd,
+                                     rev_words, n_rev, &P, err);
+    if (rc) return fail(ctx, rc, err);
+    if (opt->search_window_size - k >= (1 << kCovOffBits))   // a match's offset travels in kCovOffBits bits
+        return fail(ctx, MSSPE_ERR_ARG, "panel thin thal: the search window has more than 2^26 positions");
+    const int n = n_fwd + n_rev;
+    const long n_seg = P * n_seq;
+    for (int p = 0; p < n; ++p) keep_out[p] = forced && forced[p] ? 1 : 0;
+    if (covered_out) std::fill(covered_out, covered_out + n_seg, (uint8_t)0);
+    if (n == 0 || n_seg == 0) return MSSPE_OK;
+    const size_t cap = (size_t)1 << ctx->opt.site_list_cap_log2;
+    if ((uint64_t)n + cap >= (1ull << 31)) return fail(ctx, MSSPE_ERR_ARG, "panel thin thal: too many primers");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const bool end1 = mode == 2;
+    ChemEntry *ce = nullptr;
+    if ((rc = chem_entry(ctx, *chem, tm_threshold, &ce, end1 ? kCutEndT : kCutAnyT))) return rc;
+    const double cut = ce->c[0].g_cut;
+    if ((rc = ensure_workspace(ctx, (size_t)k * (size_t)k))) return rc;
+    if ((rc = ensure_overflow(ctx, (long)cap))) return rc;
+    if ((rc = ensure_site_work(ctx, cap, n, 0))) return rc;
+    auto &ct = ctx->cov_thal;
+    if ((rc = ct.prepare_words(*opt, fwd_words, n_fwd, rev_words, n_rev, ctx->stream, err))) return fail(ctx, rc, err);
+    if ((rc = tt.events(err))) return fail(ctx, rc, err);
+    const int S = MismatchCoverage::group_size(*opt);
+    const long n_groups = (n_seg + S - 1) / S;
+    const size_t n_pad = ((size_t)n + 63) & ~(size_t)63;
+    uint64_t *d_inc = nullptr;
+    if ((rc = ctx->thin.matrix(n, n_seg, S, (size_t)ctx->opt.panel_thin_matrix_max_mb << 20, &d_inc, err)))
+        return fail(ctx, rc, err);
+    HIP_TRY(ctx, hipMemsetAsync(d_inc, 0, sizeof(uint64_t) * (size_t)n_groups * n_pad, ctx->stream));
+    auto &w = ctx->site_work;
+    CovMatch *list = reinterpret_cast<CovMatch *>(w.sites);
+    if (n_fwd)
+        HIP_TRY(ctx, hipMemcpyAsync(w.pool, fwd_words, sizeof(uint64_t) * (size_t)n_fwd, hipMemcpyHostToDevice,
+                                    ctx->stream));
+    if (n_rev)
+        HIP_TRY(ctx, hipMemcpyAsync(w.pool + n_fwd, rev_words, sizeof(uint64_t) * (size_t)n_rev,
+                                    hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->ovf_count, 0, 8 * sizeof(uint32_t), ctx->stream));
+    const bool unique = ctx->opt.thin_thal_unique;
+
+    struct Slab { long g0, g1; int p0, p1; };
+    std::vector<Slab> todo{{0, n_groups, 0, n}};
+    bool scored = false;   // ev[3..5] of a scored slab wait to be read behind the next synchronisation
+    auto read_scored = [&]() {
+        float a = 0.f, b = 0.f;
+        if (scored && hipEventElapsedTime(&a, tt.ev[3], tt.ev[4]) == hipSuccess &&
+            hipEventElapsedTime(&b, tt.ev[4], tt.ev[5]) == hipSuccess) {
+            tt.score_us += (long long)(a * 1000.f);
+            tt.fold_us += (long long)(b * 1000.f);
+        }
+        scored = false;
+    };
+    while (!todo.empty()) {
+        const Slab s = todo.back();
+        todo.pop_back();
+        HIP_TRY(ctx, hipMemsetAsync(w.slab_count, 0, sizeof(uint64_t), ctx->stream));
+        HIP_TRY(ctx, hipEventRecord(tt.ev[0], ctx->stream));
+        if ((rc = ct.list_slab(view, n_seg, P, *opt, mm->max_mismatches, mm->exact_3p, s.g0, s.g1, s.p0, s.p1, list,
+                               cap, w.slab_count, ctx->stream, err)))
+            return fail(ctx, rc, err);
+        HIP_TRY(ctx, hipEventRecord(tt.ev[1], ctx->stream));
+        uint64_t count = 0;
+        HIP_TRY(ctx, hipMemcpyAsync(&count, w.slab_count, sizeof count, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        read_scored();
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, tt.ev[0], tt.ev[1]) == hipSuccess) tt.list_us += (long long)(ms * 1000.f);
+        if (count > cap) {
+            ++tt.redone;
+            const uint64_t groups = (uint64_t)(s.g1 - s.g0), prim = (uint64_t)(s.p1 - s.p0);
+            const uint64_t want = (2 * count + cap - 1) / cap;   // parts that would be half full at this density
+            if (groups > 1) {
+                const uint64_t parts = std::min(groups, want);
+                for (uint64_t q = 0; q < parts; ++q)
+                    todo.push_back({s.g0 + (long)(groups * q / parts), s.g0 + (long)(groups * (q + 1) / parts), s.p0,
+                                    s.p1});
+            } else if (prim > 1) {
+                const uint64_t parts = std::min(prim, want);
+                for (uint64_t q = 0; q < parts; ++q)
+                    todo.push_back({s.g0, s.g1, s.p0 + (int)(prim * q / parts), s.p0 + (int)(prim * (q + 1) / parts)});
+            } else {
+                return fail(ctx, MSSPE_ERR_CAPACITY,
+                            "panel thin thal: one segment group against one primer has " + std::to_string(count) +
+                                " matches, the work list holds " + std::to_string(cap) +
+                                " (msspe_set_option \"site_list_cap_log2\")");
+            }
+            continue;
+        }
+        if (!count) continue;
+        ++tt.slabs;
+        tt.matches += (long long)count;
+        HIP_TRY(ctx, hipEventRecord(tt.ev[2], ctx->stream));
+        uint32_t n_pairs = (uint32_t)count;
+        if (unique) {
+            // every template first, then the slab's runs: their pairs replace the identity pairs in w.list; the sort's
+            // key planes are dg and t, which nothing reads before the scoring below writes them
+            HIP_TRY(ctx, ct.oligos(view, P, *opt, list, 0, (uint32_t)count, w.pool, w.list, ctx->ovf_count,
+                                   ctx->stream));
+            if ((rc = tt.unique(list, w.pool, n, k, (uint32_t)count, reinterpret_cast<uint64_t *>(w.dg),
+                                reinterpret_cast<uint64_t *>(w.t), w.list, ctx->stream, err)))
+                return fail(ctx, rc, err);
+            HIP_TRY(ctx, hipEventRecord(tt.ev[3], ctx->stream));
+            HIP_TRY(ctx, hipMemcpyAsync(&n_pairs, tt.unique_count(), sizeof n_pairs, hipMemcpyDeviceToHost,
+                                        ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            if (n_pairs == 0 || n_pairs > count)
+                return fail(ctx, MSSPE_ERR_DEVICE, "panel thin thal: the distinct pairs of a slab do not add up");
+            if (hipEventElapsedTime(&ms, tt.ev[2], tt.ev[3]) == hipSuccess) tt.unique_us += (long long)(ms * 1000.f);
+        } else {
+            HIP_TRY(ctx, hipEventRecord(tt.ev[3], ctx->stream));
+        }
+        tt.unique_pairs += n_pairs;
+        // the hand-over lists may be shorter than the work list (a fixed list_cap_log2, a card short of memory)
+        const uint32_t step = (uint32_t)std::min<uint64_t>(n_pairs, (uint64_t)ctx->list_cap);
+        for (uint32_t c0 = 0; c0 < n_pairs; c0 += step) {
+            const uint32_t cnt = std::min(step, n_pairs - c0);
+            if (unique)   // the list's length, where oligos would have put it
+                HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)ctx->ovf_count, (int)cnt, 1, ctx->stream));
+            else
+                HIP_TRY(ctx, ct.oligos(view, P, *opt, list, c0, cnt, w.pool, w.list + c0, ctx->ovf_count, ctx->stream));
+            if ((rc = score_site_pairs(ctx, ce, end1, n, k, k, w.list + c0, cnt))) return rc;
+        }
+        HIP_TRY(ctx, hipEventRecord(tt.ev[4], ctx->stream));
+        if ((rc = tt.fold(list, (uint32_t)count, unique, w.t, cut, S, n_pad, d_inc, ctx->stream, err)))
+            return fail(ctx, rc, err);
+        HIP_TRY(ctx, hipEventRecord(tt.ev[5], ctx->stream));
+        scored = true;
+    }
+    if ((rc = ctx->thin.rounds(n, n_seg, S, thin->min_gain, keep_out, order_out, gain_out, n_picked_out, covered_out,
+                               covered_all_out, covered_kept_out, ctx->n_cu, ctx->stream, err)))
+        return fail(ctx, rc, err);
+    read_scored();   // rounds returned with the stream idle
+    return MSSPE_OK;
+}
+
 }  // namespace
 
 int msspe_segment_coverage_thal_dev(msspe_ctx *ctx, const uint8_t *d_seqs, int n_seq, size_t seq_len,
@@ -3199,6 +3380,54 @@ int msspe_segment_coverage_thal(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, 
     rc = msspe_segment_coverage_thal_dev(ctx, (const uint8_t *)d, n_seq, seq_len, opt, mm, fwd_words, n_fwd,
                                          rev_words, n_rev, chem, mode, tm_threshold, held_out, t_best_out,
                                          primer_segments_out, primer_held_out, matches, capacity, count_out);
+    (void)msspe_device_free(ctx, d);
+    return rc;
+}
+
+int msspe_panel_thin_thal_dev(msspe_ctx *ctx, const uint8_t *d_seqs, int n_seq, size_t seq_len,
+                              const msspe_kmer_opt *opt, const msspe_mismatch_opt *mm, const msspe_thin_opt *thin,
+                              const msspe_chem *chem, int mode, float tm_threshold, const uint64_t *fwd_words,
+                              int n_fwd, const uint64_t *rev_words, int n_rev, const uint8_t *forced,
+                              uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out, int *n_picked_out,
+                              uint8_t *covered_out, long long *covered_all_out, long long *covered_kept_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!d_seqs) return fail(ctx, MSSPE_ERR_ARG, "null sequences");
+    return panel_thin_thal_view(ctx, SeqView{d_seqs, nullptr, seq_len}, n_seq, seq_len, opt, mm, thin, chem, mode,
+                                tm_threshold, fwd_words, n_fwd, rev_words, n_rev, forced, keep_out, order_out, gain_out,
+                                n_picked_out, covered_out, covered_all_out, covered_kept_out);
+}
+
+int msspe_panel_thin_thal_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
+                                     const msspe_kmer_opt *opt, const msspe_mismatch_opt *mm,
+                                     const msspe_thin_opt *thin, const msspe_chem *chem, int mode, float tm_threshold,
+                                     const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
+                                     const uint8_t *forced, uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out,
+                                     int *n_picked_out, uint8_t *covered_out, long long *covered_all_out,
+                                     long long *covered_kept_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!d_packed) return fail(ctx, MSSPE_ERR_ARG, "null sequences");
+    return panel_thin_thal_view(ctx, SeqView{nullptr, d_packed, seq_len}, n_seq, seq_len, opt, mm, thin, chem, mode,
+                                tm_threshold, fwd_words, n_fwd, rev_words, n_rev, forced, keep_out, order_out, gain_out,
+                                n_picked_out, covered_out, covered_all_out, covered_kept_out);
+}
+
+int msspe_panel_thin_thal(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len, const msspe_kmer_opt *opt,
+                          const msspe_mismatch_opt *mm, const msspe_thin_opt *thin, const msspe_chem *chem, int mode,
+                          float tm_threshold, const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words,
+                          int n_rev, const uint8_t *forced, uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out,
+                          int *n_picked_out, uint8_t *covered_out, long long *covered_all_out,
+                          long long *covered_kept_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!seqs || n_seq < 0) return fail(ctx, MSSPE_ERR_ARG, "null sequences");
+    void *d = nullptr;
+    int rc = msspe_device_put(ctx, seqs, (size_t)n_seq * seq_len, &d);
+    if (rc) return rc;
+    rc = msspe_panel_thin_thal_dev(ctx, (const uint8_t *)d, n_seq, seq_len, opt, mm, thin, chem, mode, tm_threshold,
+                                   fwd_words, n_fwd, rev_words, n_rev, forced, keep_out, order_out, gain_out,
+                                   n_picked_out, covered_out, covered_all_out, covered_kept_out);
     (void)msspe_device_free(ctx, d);
     return rc;
 }

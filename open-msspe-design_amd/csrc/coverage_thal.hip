@@ -272,16 +272,28 @@ long CoverageThal::max_slab_groups(int n_primers)
 int CoverageThal::prepare(const msspe_kmer_opt &opt, const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words,
                           int n_rev, long n_seg, hipStream_t stream, std::string &err)
 {
+    const int n = n_fwd + n_rev;
+    int rc;
+    if ((rc = ensure(kHeld, sizeof(uint32_t) * (size_t)n_seg, stream, err)) ||
+        (rc = ensure(kBest, sizeof(uint64_t) * (size_t)n_seg, stream, err)) ||
+        (rc = ensure(kCounts, sizeof(uint32_t) * 2 * (size_t)n, stream, err)) ||
+        (rc = prepare_words(opt, fwd_words, n_fwd, rev_words, n_rev, stream, err)))
+        return rc;
+    CT_TRY(hipMemsetAsync(buf_[kHeld], 0, sizeof(uint32_t) * (size_t)n_seg, stream));
+    CT_TRY(hipMemsetAsync(buf_[kBest], 0, sizeof(uint64_t) * (size_t)n_seg, stream));
+    CT_TRY(hipMemsetAsync(buf_[kCounts], 0, sizeof(uint32_t) * 2 * (size_t)n, stream));
+    return MSSPE_OK;
+}
+
+int CoverageThal::prepare_words(const msspe_kmer_opt &opt, const uint64_t *fwd_words, int n_fwd,
+                                const uint64_t *rev_words, int n_rev, hipStream_t stream, std::string &err)
+{
     const int k = opt.kmer_size, n = n_fwd + n_rev;
     for (hipEvent_t &e : ev)
         if (!e) CT_TRY(hipEventCreate(&e));
     const bool narrow = k <= 16;
     int rc;
-    if ((rc = ensure(kWords, (narrow ? 4 : 8) * (size_t)n, stream, err)) ||
-        (rc = ensure(kHeld, sizeof(uint32_t) * (size_t)n_seg, stream, err)) ||
-        (rc = ensure(kBest, sizeof(uint64_t) * (size_t)n_seg, stream, err)) ||
-        (rc = ensure(kCounts, sizeof(uint32_t) * 2 * (size_t)n, stream, err)))
-        return rc;
+    if ((rc = ensure(kWords, (narrow ? 4 : 8) * (size_t)n, stream, err))) return rc;
     n_fwd_ = n_fwd;
     n_rev_ = n_rev;
     // the host copies of the planes end with their block: the stream is drained there
@@ -300,9 +312,6 @@ int CoverageThal::prepare(const msspe_kmer_opt &opt, const uint64_t *fwd_words, 
             CT_TRY(hipMemcpyAsync(buf_[kWords], w.data(), sizeof(uint2) * w.size(), hipMemcpyHostToDevice, stream));
         CT_TRY(hipStreamSynchronize(stream));
     }
-    CT_TRY(hipMemsetAsync(buf_[kHeld], 0, sizeof(uint32_t) * (size_t)n_seg, stream));
-    CT_TRY(hipMemsetAsync(buf_[kBest], 0, sizeof(uint64_t) * (size_t)n_seg, stream));
-    CT_TRY(hipMemsetAsync(buf_[kCounts], 0, sizeof(uint32_t) * 2 * (size_t)n, stream));
     return MSSPE_OK;
 }
 

@@ -30,6 +30,10 @@ public:
     // segments and n primers.  The caller has checked that W - k < 2^kCovOffBits.
     int prepare(const msspe_kmer_opt &opt, const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
                 long n_seg, hipStream_t stream, std::string &err);
+    // The first half of prepare alone -- the primer words as planes, the events -- for a caller that needs list_slab
+    // and oligos but none of the per-segment or per-primer results (msspe_panel_thin_thal*).
+    int prepare_words(const msspe_kmer_opt &opt, const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words,
+                      int n_rev, hipStream_t stream, std::string &err);
     // Groups [g0, g1) (MismatchCoverage::group_size segments each) against primers [p0, p1): every match is appended
     // at list[(*d_count)++] while that is below cap; the counter (zeroed by the caller) runs on past it.
     int list_slab(const SeqView &seqs, long n_seg, long P, const msspe_kmer_opt &opt, int max_mismatches, int exact_3p,

@@ -216,6 +216,36 @@ void PanelThin::release()
     }
 }
 
+int PanelThin::matrix(int n, long n_seg, int S, size_t max_matrix_bytes, uint64_t **inc_out, std::string &err)
+{
+    rounds_ = groups_ = 0;
+    for (auto &p : phase_us_) p = 0;
+    const long G = (n_seg + S - 1) / S;
+    const size_t n_pad = ((size_t)n + 63) & ~(size_t)63;
+    const size_t mib = (size_t)1 << 20, matrix = (size_t)G * n_pad * sizeof(uint64_t);
+    if (matrix > max_matrix_bytes) {
+        err = "panel thin: the incidence matrix needs " + std::to_string((matrix + mib - 1) / mib) +
+              " MB, panel_thin_matrix_max_mb is " + std::to_string(max_matrix_bytes / mib);
+        return MSSPE_ERR_CAPACITY;
+    }
+    groups_ = G;
+    int rc;
+    if ((rc = ensure(kInc, matrix, err)) || (rc = ensure(kCov, sizeof(uint64_t) * (size_t)G + sizeof(ThinState), err)) ||
+        (rc = ensure(kTouched, sizeof(uint32_t) * (size_t)G, err)) ||
+        (rc = ensure(kNew, sizeof(uint64_t) * (size_t)G, err)) ||
+        (rc = ensure(kGain, sizeof(uint32_t) * (size_t)n, err)) || (rc = ensure(kLive, (size_t)n, err)) ||
+        (rc = ensure(kOrder, 2 * sizeof(uint32_t) * (size_t)n, err)) ||
+        (rc = ensure(kForced, sizeof(uint32_t) * (size_t)n, err)))
+        return rc;
+    for (auto &e : ev_)
+        if (!e && hipEventCreate(&e) != hipSuccess) {
+            err = "panel thin: hipEventCreate failed";
+            return MSSPE_ERR_DEVICE;
+        }
+    *inc_out = (uint64_t *)buf_[kInc];
+    return MSSPE_OK;
+}
+
 int PanelThin::run(MismatchCoverage &cov, const SeqView &seqs, int n_seq, size_t seq_len, const msspe_kmer_opt &opt,
                    int max_mismatches, int exact_3p, int min_gain, const uint64_t *fwd_words, int n_fwd,
                    const uint64_t *rev_words, int n_rev, const uint8_t *forced, uint8_t *keep_out, uint32_t *order_out,
@@ -238,39 +268,34 @@ int PanelThin::run(MismatchCoverage &cov, const SeqView &seqs, int n_seq, size_t
     if (covered_out) std::fill(covered_out, covered_out + n_seg, (uint8_t)0);
     if (n == 0 || n_seg == 0) return MSSPE_OK;
 
-    const int S = MismatchCoverage::group_size(opt);
-    const long G = (n_seg + S - 1) / S;
-    const size_t n_pad = ((size_t)n + 63) & ~(size_t)63;
-    const size_t mib = (size_t)1 << 20, matrix = (size_t)G * n_pad * sizeof(uint64_t);
-    if (matrix > max_matrix_bytes) {
-        err = "panel thin: the incidence matrix needs " + std::to_string((matrix + mib - 1) / mib) +
-              " MB, panel_thin_matrix_max_mb is " + std::to_string(max_matrix_bytes / mib);
-        return MSSPE_ERR_CAPACITY;
-    }
-    groups_ = G;
-    if ((rc = ensure(kInc, matrix, err)) || (rc = ensure(kCov, sizeof(uint64_t) * (size_t)G + sizeof(ThinState), err)) ||
-        (rc = ensure(kTouched, sizeof(uint32_t) * (size_t)G, err)) ||
-        (rc = ensure(kNew, sizeof(uint64_t) * (size_t)G, err)) ||
-        (rc = ensure(kGain, sizeof(uint32_t) * (size_t)n, err)) || (rc = ensure(kLive, (size_t)n, err)) ||
-        (rc = ensure(kOrder, 2 * sizeof(uint32_t) * (size_t)n, err)) ||
-        (rc = ensure(kForced, sizeof(uint32_t) * (size_t)n, err)))
-        return rc;
-    for (auto &e : ev_)
-        if (!e && hipEventCreate(&e) != hipSuccess) {
-            err = "panel thin: hipEventCreate failed";
-            return MSSPE_ERR_DEVICE;
-        }
-    uint64_t *d_inc = (uint64_t *)buf_[kInc], *d_cov = (uint64_t *)buf_[kCov], *d_new = (uint64_t *)buf_[kNew];
-    ThinState *st = (ThinState *)(d_cov + G);   // behind the covered words: 8-byte aligned
-    uint32_t *d_touched = (uint32_t *)buf_[kTouched], *d_gain = (uint32_t *)buf_[kGain];
-    uint32_t *d_order = (uint32_t *)buf_[kOrder], *d_gains = d_order + n, *d_forced = (uint32_t *)buf_[kForced];
-    uint8_t *d_live = (uint8_t *)buf_[kLive];
+    uint64_t *d_inc = nullptr;
+    if ((rc = matrix(n, n_seg, MismatchCoverage::group_size(opt), max_matrix_bytes, &d_inc, err))) return rc;
 
     // (1) the incidence matrix
     THIN_TRY(hipEventRecord(ev_[0], stream));
     if ((rc = cov.incidence(seqs, n_seq, seq_len, opt, max_mismatches, exact_3p, fwd_words, n_fwd, rev_words, n_rev,
                             d_inc, stream, err)))
         return rc;
+    if ((rc = rounds(n, n_seg, MismatchCoverage::group_size(opt), min_gain, keep_out, order_out, gain_out,
+                     n_picked_out, covered_out, covered_all_out, covered_kept_out, n_cu, stream, err)))
+        return rc;
+    float ms = 0.f;   // rounds() returned with the stream idle
+    (void)hipEventElapsedTime(&ms, ev_[0], ev_[1]);
+    phase_us_[0] = (long long)(ms * 1000.0f);
+    return MSSPE_OK;
+}
+
+int PanelThin::rounds(int n, long n_seg, int S, int min_gain, uint8_t *keep_out, uint32_t *order_out,
+                      uint32_t *gain_out, int *n_picked_out, uint8_t *covered_out, long long *covered_all_out,
+                      long long *covered_kept_out, int n_cu, hipStream_t stream, std::string &err)
+{
+    const long G = (n_seg + S - 1) / S;
+    const size_t n_pad = ((size_t)n + 63) & ~(size_t)63;
+    uint64_t *d_inc = (uint64_t *)buf_[kInc], *d_cov = (uint64_t *)buf_[kCov], *d_new = (uint64_t *)buf_[kNew];
+    ThinState *st = (ThinState *)(d_cov + G);   // behind the covered words: 8-byte aligned
+    uint32_t *d_touched = (uint32_t *)buf_[kTouched], *d_gain = (uint32_t *)buf_[kGain];
+    uint32_t *d_order = (uint32_t *)buf_[kOrder], *d_gains = d_order + n, *d_forced = (uint32_t *)buf_[kForced];
+    uint8_t *d_live = (uint8_t *)buf_[kLive];
     THIN_TRY(hipEventRecord(ev_[1], stream));
 
     // (2) forced rows, first gains
@@ -337,7 +362,7 @@ int PanelThin::run(MismatchCoverage &cov, const SeqView &seqs, int n_seq, size_t
     }
     THIN_TRY(hipEventSynchronize(ev_[3]));
     THIN_TRY(hipStreamSynchronize(stream));
-    for (int ph = 0; ph < 3; ++ph) {
+    for (int ph = 1; ph < 3; ++ph) {
         float ms = 0.f;
         (void)hipEventElapsedTime(&ms, ev_[ph], ev_[ph + 1]);
         phase_us_[ph] = (long long)(ms * 1000.0f);

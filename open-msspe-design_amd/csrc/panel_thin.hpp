@@ -26,6 +26,15 @@ public:
             const uint64_t *rev_words, int n_rev, const uint8_t *forced, uint8_t *keep_out, uint32_t *order_out,
             uint32_t *gain_out, int *n_picked_out, uint8_t *covered_out, long long *covered_all_out,
             long long *covered_kept_out, size_t max_matrix_bytes, int n_cu, hipStream_t stream, std::string &err);
+    // run() in its two halves, for a caller that fills the matrix itself (msspe_panel_thin_thal*: the held incidence).
+    // matrix: the buffers of a run over n primers and n_seg segments in groups of S, under the same cap; *inc_out is
+    // the matrix (inc[g * n_pad + p], n_pad = n rounded up to 64, bit b = segment g * S + b), not yet written.  The
+    // caller writes every word of it on `stream`, then calls rounds: forced rows (keep_out holds the forced flags on
+    // entry), first gains, the round batches and the read-back, with run's outputs.  Returns with the stream idle.
+    int matrix(int n, long n_seg, int S, size_t max_matrix_bytes, uint64_t **inc_out, std::string &err);
+    int rounds(int n, long n_seg, int S, int min_gain, uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out,
+               int *n_picked_out, uint8_t *covered_out, long long *covered_all_out, long long *covered_kept_out,
+               int n_cu, hipStream_t stream, std::string &err);
     void release();
     // the last run: rounds enqueued that ran (the picks and the one that stopped), segment groups (matrix rows), and
     // device time in microseconds of the incidence pass, the first gains and the rounds

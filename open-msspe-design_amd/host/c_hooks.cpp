@@ -67,6 +67,7 @@ int odm_parse_args(int argc, const char *const *argv, char *out, size_t cap)
           << "\ncoverage_tm=" << a.coverage_tm_text << "\ncoverage_thal=" << a.coverage_thal
           << "\nthin_panel=" << a.thin_panel << "\nthin_mismatches=" << a.thin_mismatches
           << "\nthin_3p_exact=" << a.thin_3p_exact << "\nthin_min_gain=" << a.thin_min_gain
+          << "\nthin_tm=" << a.thin_tm_text << "\nthin_thal=" << a.thin_thal
           << "\nbackground=" << a.background << "\nbackground_mismatches=" << a.background_mismatches
           << "\nbackground_3p_exact=" << a.background_3p_exact << "\nmax_background_sites=" << a.max_background_sites
           << "\nbackground_tm=" << a.background_tm_text << "\nbackground_thal=" << a.background_thal
@@ -137,6 +138,17 @@ int odm_thin_panel(const uint64_t *rows, int n, int words, int min_gain, const u
         covered_out[1] = (long long)t.covered_kept;
     }
     return (int)t.order.size();
+}
+
+// The block od-msspe-hip --thin-panel true --thin-tm T prints (thin_thal_report), from figures the caller has.  Needs no
+// device.
+int odm_thin_thal_block(int mode, float tm_threshold, int max_mismatches, int exact_3p, int min_gain,
+                        long long kept_f, long long n_f, long long kept_r, long long n_r, long long forced,
+                        long long held_all, long long held_kept, long long segments, char *out, size_t cap)
+{
+    return emit(thin_thal_report(mode, tm_threshold, max_mismatches, exact_3p, min_gain, (size_t)kept_f, (size_t)n_f,
+                                 (size_t)kept_r, (size_t)n_r, (size_t)forced, (size_t)held_all, (size_t)held_kept,
+                                 (size_t)segments), out, cap);
 }
 
 int odm_is_run(const char *kmer) { return is_run(kmer) ? 1 : 0; }

@@ -83,6 +83,8 @@ const OptSpec kOpts[] = {
     {"--thin-mismatches", "THIN_MISMATCHES", OptSpec::Int, OFF(thin_mismatches)},
     {"--thin-3p-exact", "THIN_3P_EXACT", OptSpec::Str, OFF(thin_3p_exact_text)},
     {"--thin-min-gain", "THIN_MIN_GAIN", OptSpec::Int, OFF(thin_min_gain)},
+    {"--thin-tm", "THIN_TM", OptSpec::Str, OFF(thin_tm_text)},
+    {"--thin-thal", "THIN_THAL", OptSpec::Str, OFF(thin_thal)},
     {"--background", "BACKGROUND", OptSpec::Str, OFF(background)},
     {"--background-mismatches", "BACKGROUND_MISMATCHES", OptSpec::OptInt, OFF(background_mismatches)},
     {"--background-3p-exact", "BACKGROUND_3P_EXACT", OptSpec::OptInt, OFF(background_3p_exact)},
@@ -143,6 +145,8 @@ std::string Args::usage()
          "cover of the segments matched within --thin-mismatches <M> (last --thin-3p-exact <E> bases exact), a pick\n"
          "covering at least --thin-min-gain <G> new segments. No segment is lost at G = 1; a segment's best mismatch\n"
          "count may rise up to M. The primers of --existing-primers are kept. One device; not with --keep-all true.\n"
+         "With --thin-tm <C> the cover is of the segments a primer holds at C instead: every match within M / E is scored\n"
+         "with thal (--thin-thal any | end1), and no held segment is lost at G = 1; a segment's best t may fall.\n"
          "--coverage-tm <C> adds a report of the segments the final primers hold at C: every match within\n"
          "--coverage-mismatches (last --coverage-3p-exact bases exact) is scored with thal (--coverage-thal any | end1)\n"
          "against the strand the primer anneals to. One device.\n"
@@ -260,6 +264,17 @@ Args Args::parse(int argc, const char *const *argv)
         if (a.thin_min_gain < 1)
             throw UsageError("error: invalid value '" + std::to_string(a.thin_min_gain) +
                              "' for '--thin-min-gain <...>'\n  [1 ..]");
+        if (!a.thin_tm_text.empty()) {
+            a.thin_tm = std::strtof(a.thin_tm_text.c_str(), &end);
+            if (*end || std::isnan(a.thin_tm))
+                throw UsageError("error: invalid value '" + a.thin_tm_text + "' for '--thin-tm'");
+            if (a.kmer_size < 2) throw UsageError("error: '--thin-tm' needs '--kmer-size' of at least 2");
+            a.thin_scored = true;
+            if (a.thin_thal.empty()) a.thin_thal = "any";
+            if (a.thin_thal != "any" && a.thin_thal != "end1")
+                throw UsageError("error: invalid value '" + a.thin_thal +
+                                 "' for '--thin-thal <...>'\n  [possible values: any, end1]");
+        }
     }
     if (a.background.empty()) {
         for (const auto &given : {std::make_pair("--background-mismatches", a.background_mismatches),
@@ -1284,10 +1299,25 @@ std::string coverage_report_thal(Engine &eng, const DeviceAlignment &aln, const 
                                fwd.size() + rev.size(), max_mismatches, exact_3p, mode, tm_threshold);
 }
 
+std::string thin_thal_report(int mode, float tm_threshold, int max_mismatches, int exact_3p, int min_gain,
+                             size_t kept_f, size_t n_f, size_t kept_r, size_t n_r, size_t forced, size_t held_all,
+                             size_t held_kept, size_t segments)
+{
+    const std::string x = std::to_string(kept_f + kept_r), y = std::to_string(n_f + n_r), t = std::to_string(segments);
+    return std::string("\nPanel thinning (thal ") + (mode == 2 ? "END1" : "ANY") + ", t >= " +
+           fmt("%.2f", (double)tm_threshold) + " C; matches within " + std::to_string(max_mismatches) +
+           " mismatches, last " + std::to_string(exact_3p) + " bases exact, gain >= " + std::to_string(min_gain) +
+           "):\n  Primers:  kept " + x + " of " + y + " (forward " + std::to_string(kept_f) + " of " +
+           std::to_string(n_f) + ", reverse " + std::to_string(kept_r) + " of " + std::to_string(n_r) + "), " +
+           std::to_string(forced) + " forced\n  Segments: held " + std::to_string(held_all) + "/" + t + " by all " + y +
+           ", " + std::to_string(held_kept) + "/" + t + " by the kept " + x + "\n";
+}
+
 std::string thin_panel_on_device(Engine &eng, const DeviceAlignment &aln, std::vector<KmerStat> &fwd,
                                  std::vector<KmerStat> &rev, const std::vector<std::string> &panel_f,
                                  const std::vector<std::string> &panel_r, int segment_size, int overlap_size,
-                                 int window_size, int kmer_size, int max_mismatches, int exact_3p, int min_gain)
+                                 int window_size, int kmer_size, int max_mismatches, int exact_3p, int min_gain,
+                                 const msspe_chem *chem, int mode, float tm_threshold)
 {
     // the new primers in their lists' order (stage A's selection order: ties go to the word with more postings), the
     // panel's behind them, forced
@@ -1307,10 +1337,15 @@ std::string thin_panel_on_device(Engine &eng, const DeviceAlignment &aln, std::v
     const msspe_kmer_opt opt{segment_size, overlap_size, window_size, kmer_size, 0, 0};
     const msspe_mismatch_opt mm{max_mismatches, exact_3p};
     const msspe_thin_opt thin{min_gain};
-    const int rc = msspe_panel_thin_packed_dev(eng.ctx(), aln.device(), aln.rows(), L, &opt, &mm, &thin, wf.data(),
-                                               (int)wf.size(), wr.data(), (int)wr.size(), forced.data(), keep.data(),
-                                               order.data(), gains.data(), &n_picked, nullptr, &covered_all,
-                                               &covered_kept);
+    const int rc =
+        chem ? msspe_panel_thin_thal_packed_dev(eng.ctx(), aln.device(), aln.rows(), L, &opt, &mm, &thin, chem, mode,
+                                                tm_threshold, wf.data(), (int)wf.size(), wr.data(), (int)wr.size(),
+                                                forced.data(), keep.data(), order.data(), gains.data(), &n_picked,
+                                                nullptr, &covered_all, &covered_kept)
+             : msspe_panel_thin_packed_dev(eng.ctx(), aln.device(), aln.rows(), L, &opt, &mm, &thin, wf.data(),
+                                           (int)wf.size(), wr.data(), (int)wr.size(), forced.data(), keep.data(),
+                                           order.data(), gains.data(), &n_picked, nullptr, &covered_all,
+                                           &covered_kept);
     if (rc) eng.fail(rc);
     const size_t n_f = fwd.size(), n_r = rev.size();
     std::vector<KmerStat> kept_f, kept_r;
@@ -1320,6 +1355,10 @@ std::string thin_panel_on_device(Engine &eng, const DeviceAlignment &aln, std::v
         if (keep[all_f.size() + i]) kept_r.push_back(rev[i]);
     fwd.swap(kept_f);
     rev.swap(kept_r);
+    if (chem)
+        return thin_thal_report(mode, tm_threshold, max_mismatches, exact_3p, min_gain, fwd.size(), n_f, rev.size(),
+                                n_r, panel_f.size() + panel_r.size(), (size_t)covered_all, (size_t)covered_kept,
+                                (size_t)aln.rows() * P);
     return thin_report(max_mismatches, exact_3p, min_gain, fwd.size(), n_f, rev.size(), n_r,
                        panel_f.size() + panel_r.size(), (size_t)covered_all, (size_t)covered_kept,
                        (size_t)aln.rows() * P);
@@ -1871,9 +1910,11 @@ int run(const Args &args, std::string &stdout_text)
 
     std::string thin_text;   // --thin-panel: everything below sees the thinned lists
     if (args.thin_panel == "true") {
+        const msspe_chem thin_chem = ntthal_chem(opts);   // --thin-tm: the chemistry --coverage-tm scores with
         thin_text = thin_panel_on_device(eng, aln, good_f, good_r, panel_f, panel_r, args.window_size, args.overlap_size,
                                          args.search_windows_size, args.kmer_size, args.thin_mismatches,
-                                         args.thin_3p_exact, args.thin_min_gain);
+                                         args.thin_3p_exact, args.thin_min_gain, args.thin_scored ? &thin_chem : nullptr,
+                                         args.thin_thal == "end1" ? 2 : 1, args.thin_tm);
         timer.lap("panel thinning");
     }
     // the report covers the panel and the new primers together; the CSV lists the new ones, numbered on from the panel

@@ -89,6 +89,13 @@ struct Args {
     std::string thin_3p_exact_text = "3";
     int thin_3p_exact = 3;
     int thin_min_gain = 1;
+    // --thin-tm C (with --thin-panel true): the thinning runs over the segments a primer HOLDS at C instead -- every
+    // match within thin_mismatches / thin_3p_exact scored with thal (msspe_panel_thin_thal, --thin-thal any | end1, the
+    // chemistry of --coverage-tm), so the thal report of the thinned panel holds what the whole panel held.  Empty
+    // text: not given, nothing changes (and --thin-thal is not read).
+    std::string thin_tm_text, thin_thal;
+    float thin_tm = 0.0f;
+    bool thin_scored = false;
     // --background FASTA: after the coverage report, the off-target sites of every kept primer in these records (both
     // strands, up to background_mismatches mismatches, the last background_3p_exact bases exact:
     // msspe_background_sites); with max_background_sites >= 0 candidates with more sites are dropped before the
@@ -269,7 +276,14 @@ ThinResult thin_panel(const std::vector<std::vector<uint64_t>> &rows, int min_ga
 std::string thin_panel_on_device(Engine &eng, const DeviceAlignment &aln, std::vector<KmerStat> &fwd,
                                  std::vector<KmerStat> &rev, const std::vector<std::string> &panel_f,
                                  const std::vector<std::string> &panel_r, int segment_size, int overlap_size,
-                                 int window_size, int kmer_size, int max_mismatches, int exact_3p, int min_gain);
+                                 int window_size, int kmer_size, int max_mismatches, int exact_3p, int min_gain,
+                                 const msspe_chem *chem = nullptr, int mode = 1, float tm_threshold = 0.0f);
+// with a chemistry (--thin-tm) thin_panel_on_device calls msspe_panel_thin_thal_packed_dev and returns this block:
+// "Panel thinning (thal NAME, t >= T C; matches within M mismatches, last E bases exact, gain >= G):", the primers
+// kept as in thin_report, and the segments held by all of them and by the kept ones
+std::string thin_thal_report(int mode, float tm_threshold, int max_mismatches, int exact_3p, int min_gain,
+                             size_t kept_f, size_t n_f, size_t kept_r, size_t n_r, size_t forced, size_t held_all,
+                             size_t held_kept, size_t segments);
 // "Panel thinning (up to M mismatches, last E bases exact, gain >= G):", the primers kept of those offered (forced
 // ones apart) and the segments covered by all of them and by the kept ones (forced primers cover in both figures)
 std::string thin_report(int max_mismatches, int exact_3p, int min_gain, size_t kept_f, size_t n_f, size_t kept_r,

@@ -36,6 +36,7 @@ EXPORTS = [
     "msspe_segment_coverage_mm", "msspe_segment_coverage_mm_dev", "msspe_segment_coverage_mm_packed_dev",
     "msspe_segment_coverage_thal", "msspe_segment_coverage_thal_dev", "msspe_segment_coverage_thal_packed_dev",
     "msspe_panel_thin", "msspe_panel_thin_dev", "msspe_panel_thin_packed_dev",
+    "msspe_panel_thin_thal", "msspe_panel_thin_thal_dev", "msspe_panel_thin_thal_packed_dev",
     "msspe_device_put_stream_packed", "msspe_background_sites_packed_dev", "msspe_background_sites",
     "msspe_background_thal_packed_dev", "msspe_background_thal",
     "msspe_background_amplicons_packed_dev", "msspe_background_amplicons",
@@ -263,6 +264,10 @@ def load_library() -> C.CDLL:
     L.msspe_device_put.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_void_p)]
     L.msspe_panel_thin_dev.argtypes = L.msspe_panel_thin.argtypes
     L.msspe_panel_thin_packed_dev.argtypes = L.msspe_panel_thin.argtypes
+    L.msspe_panel_thin_thal.argtypes = (L.msspe_panel_thin.argtypes[:7] + [C.POINTER(Chem), C.c_int, C.c_float] +
+                                        L.msspe_panel_thin.argtypes[7:])
+    L.msspe_panel_thin_thal_dev.argtypes = L.msspe_panel_thin_thal.argtypes
+    L.msspe_panel_thin_thal_packed_dev.argtypes = L.msspe_panel_thin_thal.argtypes
     L.msspe_device_put_stream_packed.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int,
                                                  C.POINTER(vp), C.POINTER(C.c_size_t), vp]
     L.msspe_background_sites_packed_dev.argtypes = [vp, vp, C.c_size_t, C.c_int, C.POINTER(MismatchOpt), u64p, C.c_int,
@@ -955,6 +960,20 @@ class Engine:
         covered uint8 (n_seq, P), covered_all, covered_kept)."""
         fn = {"host": self.L.msspe_panel_thin, "dev": self.L.msspe_panel_thin_dev,
               "packed": self.L.msspe_panel_thin_packed_dev}[form]
+        return self._panel_thin(fn, (), genomes, opt, fwd, rev, max_mismatches, exact_3p, min_gain, forced, form)
+
+    def panel_thin_thal(self, genomes, opt: KmerOpt, fwd, rev, max_mismatches: int, exact_3p: int, chem: Chem, mode,
+                        tm_threshold: float, min_gain: int = 1, forced=None, form: str = "host"):
+        """panel_thin over the segments a primer HOLDS: a match within max_mismatches (last exact_3p bases exact)
+        counts when its thal score against the strand the primer anneals to is stable at tm_threshold
+        (msspe_panel_thin_thal*; mode "any" (1) or "end1" (2), the rule of segment_coverage_thal).  Arguments and
+        the returned tuple as panel_thin; covered marks the segments the kept set holds."""
+        fn = {"host": self.L.msspe_panel_thin_thal, "dev": self.L.msspe_panel_thin_thal_dev,
+              "packed": self.L.msspe_panel_thin_thal_packed_dev}[form]
+        return self._panel_thin(fn, (C.byref(chem), self._thal_mode(mode), tm_threshold), genomes, opt, fwd, rev,
+                                max_mismatches, exact_3p, min_gain, forced, form)
+
+    def _panel_thin(self, fn, scoring, genomes, opt, fwd, rev, max_mismatches, exact_3p, min_gain, forced, form):
         owned = None
         if isinstance(genomes, tuple):
             if form == "host":
@@ -987,7 +1006,7 @@ class Engine:
             covered = np.zeros((n_seq, P), dtype=np.uint8)
             n_picked, c_all, c_kept = C.c_int(0), C.c_longlong(0), C.c_longlong(0)
             mm, thin = MismatchOpt(max_mismatches, exact_3p), ThinOpt(min_gain)
-            self._check(fn(self.ptr, seqs_arg, n_seq, seq_len, C.byref(opt), C.byref(mm), C.byref(thin),
+            self._check(fn(self.ptr, seqs_arg, n_seq, seq_len, C.byref(opt), C.byref(mm), C.byref(thin), *scoring,
                            f.ctypes.data, len(f), r.ctypes.data, len(r),
                            flags.ctypes.data if flags is not None else None, keep.ctypes.data, order.ctypes.data,
                            gains.ctypes.data, C.byref(n_picked), covered.ctypes.data, C.byref(c_all), C.byref(c_kept)))
