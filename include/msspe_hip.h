@@ -659,6 +659,62 @@ int msspe_kmer_candidates_both_sets_packed_dev(msspe_ctx *ctx, const uint64_t *d
                                                const msspe_kmer_sets *rev, uint64_t *words_fwd, uint32_t *freq_fwd,
                                                int *n_fwd, uint64_t *words_rev, uint32_t *freq_rev, int *n_rev,
                                                int capacity);
+/* Stage A extending a panel on what the panel COVERS (engine extension).  A TOLERANT SEEDED run is a seeded run in
+ * which "the seed's segments" are no longer the word's own postings but the segments of the direction in which the
+ * seed word has a match under msspe_segment_coverage_mm*'s rule (mode 0), or a STABLE match under
+ * msspe_segment_coverage_thal*'s rule (mode 1 ANY, mode 2 END1: stable iff t_match > msspe_t_cut(tm_threshold)).
+ *   - The match rule is applied with that direction's primers only: direction 0 the forward words in the head window,
+ *     direction 1 the reverse word as the CSV writes it, in the tail window against the reverse-complemented candidate.
+ *   - Before the first iteration every distinct seed word gets main.rs:371-378's post-push update once over that
+ *     segment set: its segments become ignored, and coverage[j] goes up by one for every distinct partition j among ALL
+ *     its segments, those already covered included.  The updates commute: seed order and duplicates do not matter.
+ *   - A seed that is absent from the index may still cover segments.
+ *   - The loop, its stop rules, max_iterations, the frequencies (live counts) and the winners' pushes are unchanged: a
+ *     winner still covers its own postings only.  Seeds are never returned as winners (their exact postings are a
+ *     subset of what they cover).
+ *   - Exclusions act on the index as in msspe_kmer_candidates_sets*; they do not change what a seed covers (a panel
+ *     primer is in the tube whether or not stage A may pick it).
+ * Outputs per direction next to the _sets call's, both optional (NULL: not read back): seed_covered_out (HOST, n_seq * P
+ * bytes, s = r * P + j): 1 where the segment is ignored before the first iteration; seed_partitions_out (HOST,
+ * uint32[P]): coverage[] at that moment.  Both are zeros when there is no seed.
+ * Identities: n_seed == 0 is the _sets call, bit for bit and launch for launch.  Mode 0 with max_mismatches 0, any
+ * exact_3p and no word in both lists gives the _sets call's winners and frequencies.  Mode 1 / 2 with tm_threshold
+ * <= 0 gives mode 0.  seed_covered_out == (best_out != 255) of msspe_segment_coverage_mm* called with that direction's
+ * seeds alone, and in modes 1 and 2 == (held_out == 2) of msspe_segment_coverage_thal*.
+ * The incidence is built in TILES OF SEEDS, each against all segment groups, in the matrix of msspe_panel_thin* (the
+ * state is an OR and a sum over seeds); a tile is as many seeds (a multiple of 64) as "panel_thin_matrix_max_mb" holds,
+ * and MSSPE_ERR_CAPACITY is returned only when 64 seeds do not fit.  Modes 1 and 2 list, score and fold a tile as
+ * msspe_panel_thin_thal* does ("thin_thal_unique", "site_list_cap_log2" and its overrun rule apply).  The both call
+ * runs the two seeding passes one after the other on the context's stream; the two greedy loops overlap as before.
+ * msspe_get_info, the last call (both directions added up): "stage_a_tolerant_tiles", "stage_a_tolerant_segments"
+ * (segments the seeds covered), "stage_a_tolerant_incidence_us" / "stage_a_tolerant_seed_us" (device time filling the
+ * matrix / seeding from it).
+ * Errors: those of the _sets calls, of msspe_segment_coverage_mm* (max_mismatches or exact_3p outside 0..k) and, in
+ * modes 1 and 2, of msspe_segment_coverage_thal* (MSSPE_ERR_K below k = 2); MSSPE_ERR_ARG: rule == NULL, a mode
+ * outside 0..2, chem == NULL in mode 1 or 2.  Out of scope: winners that cover tolerantly, seeds of another length
+ * than kmer_size. */
+typedef struct {
+    int max_mismatches, exact_3p;   /* as msspe_mismatch_opt */
+    int mode;                       /* 0: a match covers; 1 ANY / 2 END1: a STABLE match covers */
+    const msspe_chem *chem;         /* mode 1, 2 */
+    float tm_threshold;             /* mode 1, 2: stable iff t_match > msspe_t_cut(tm_threshold) */
+} msspe_seed_rule;
+int msspe_kmer_candidates_tolerant(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len,
+                                   const msspe_kmer_opt *opt, int direction, const msspe_kmer_sets *sets,
+                                   const msspe_seed_rule *rule, uint64_t *words_out, uint32_t *freq_out, int capacity,
+                                   int *n_out, uint8_t *seed_covered_out, uint32_t *seed_partitions_out);
+int msspe_kmer_candidates_tolerant_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
+                                              const msspe_kmer_opt *opt, int direction, const msspe_kmer_sets *sets,
+                                              const msspe_seed_rule *rule, uint64_t *words_out, uint32_t *freq_out,
+                                              int capacity, int *n_out, uint8_t *seed_covered_out,
+                                              uint32_t *seed_partitions_out);
+int msspe_kmer_candidates_both_tolerant_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
+                                                   const msspe_kmer_opt *opt, const msspe_kmer_sets *fwd,
+                                                   const msspe_kmer_sets *rev, const msspe_seed_rule *rule,
+                                                   uint64_t *words_fwd, uint32_t *freq_fwd, int *n_fwd,
+                                                   uint64_t *words_rev, uint32_t *freq_rev, int *n_rev, int capacity,
+                                                   uint8_t *seed_covered_fwd, uint32_t *seed_partitions_fwd,
+                                                   uint8_t *seed_covered_rev, uint32_t *seed_partitions_rev);
 int msspe_segment_coverage_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
                                       const msspe_kmer_opt *opt, const uint64_t *fwd_words, int n_fwd,
                                       const uint64_t *rev_words, int n_rev, uint8_t *hit_out);

@@ -17,6 +17,7 @@
 #include <cstring>
 #include <dlfcn.h>
 #include <memory>
+#include <mutex>
 #include <new>
 #include <string>
 #include <thread>
@@ -197,6 +198,13 @@ struct msspe_ctx {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events;
     size_t prof_used = 0;
     long long bound_mirrored = 0;      // info key "bound_mirrored"
+    // msspe_kmer_candidates_tolerant*: the seeding passes of a call (one per direction) take turns on the context's
+    // stream, matrix and work list; of the last call, both directions added up
+    struct Tolerant {
+        std::mutex turn;
+        hipEvent_t ev[3] = {};             // before the incidence, between it and the seeding, after the seeding
+        long long tiles = 0, segments = 0, incidence_us = 0, seed_us = 0;
+    } tolerant;
 };
 
 namespace {
@@ -862,6 +870,10 @@ int msspe_get_info(msspe_ctx *ctx, const char *key, long long *value_out)
     else if (k == "panel_thin_thal_score_us") *value_out = ctx->thin_thal.score_us;
     else if (k == "panel_thin_thal_fold_us") *value_out = ctx->thin_thal.fold_us;
     else if (k == "panel_thin_thal_rounds_us") *value_out = ctx->thin.phase_us()[2];
+    else if (k == "stage_a_tolerant_tiles") *value_out = ctx->tolerant.tiles;
+    else if (k == "stage_a_tolerant_segments") *value_out = ctx->tolerant.segments;
+    else if (k == "stage_a_tolerant_incidence_us") *value_out = ctx->tolerant.incidence_us;
+    else if (k == "stage_a_tolerant_seed_us") *value_out = ctx->tolerant.seed_us;
     else if (k == "pair_bound") *value_out = ctx->opt.pair_bound;
     else if (k == "pair_mirror") *value_out = ctx->opt.pair_mirror;
     else if (k == "pair_bound_list") *value_out = ctx->opt.pair_bound_list;
@@ -932,6 +944,10 @@ void msspe_destroy(msspe_ctx *ctx)
         ctx->tubes.release();
         ctx->thin.release();
         ctx->thin_thal.release();
+        for (auto &e : ctx->tolerant.ev) {
+            if (e) (void)hipEventDestroy(e);
+            e = nullptr;
+        }
         ctx->mm_cov.release();
         ctx->cov_thal.release();
         ctx->background.release();
@@ -2158,9 +2174,10 @@ static bool sets_ok(const msspe_kmer_sets *s)
     return !s || (s->n_seed >= 0 && s->n_exclude >= 0 && (s->n_seed == 0 || s->seed) && (s->n_exclude == 0 || s->exclude));
 }
 
+// seed_from (msspe_kmer_candidates_tolerant*): the caller seeds the run itself; sets then holds exclusions only.
 static int kmer_run(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t seq_len, const msspe_kmer_opt *opt,
                     int direction, const msspe_kmer_sets *sets, uint64_t *words_out, uint32_t *freq_out, int capacity,
-                    int *n_out)
+                    int *n_out, const KmerStage::SeedFrom *seed_from = nullptr)
 {
     if (!ctx) return MSSPE_ERR_ARG;
     if ((!view.ascii && !view.packed) || !opt || !words_out || !freq_out || !n_out || capacity < 0 || !sets_ok(sets))
@@ -2169,7 +2186,7 @@ static int kmer_run(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t seq_l
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::string err;
     const int rc = ctx->kmer.run(view, n_seq, seq_len, *opt, direction, words_out, freq_out, capacity, n_out,
-                                 ctx->stream, err, sets->seed, sets->n_seed, sets->exclude, sets->n_exclude);
+                                 ctx->stream, err, sets->seed, sets->n_seed, sets->exclude, sets->n_exclude, seed_from);
     if (rc) return fail(ctx, rc, err);
     return MSSPE_OK;
 }
@@ -2196,7 +2213,8 @@ static int kmer_run_host(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t 
 static int kmer_run_both(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len, const msspe_kmer_opt *opt,
                          const msspe_kmer_sets *fwd, const msspe_kmer_sets *rev, uint64_t *words_fwd,
                          uint32_t *freq_fwd, int *n_fwd, uint64_t *words_rev, uint32_t *freq_rev, int *n_rev,
-                         int capacity)
+                         int capacity, const KmerStage::SeedFrom *seed_from_fwd = nullptr,
+                         const KmerStage::SeedFrom *seed_from_rev = nullptr)
 {
     if (!ctx) return MSSPE_ERR_ARG;
     if (!d_packed || !opt || !words_fwd || !freq_fwd || !n_fwd || !words_rev || !freq_rev || !n_rev || capacity < 0 ||
@@ -2222,10 +2240,10 @@ static int kmer_run_both(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, si
             return;
         }
         rc1 = ctx->kmer_rev.run(view, n_seq, seq_len, *opt, 1, words_rev, freq_rev, capacity, n_rev, ctx->stream_rev, err1,
-                                rev->seed, rev->n_seed, rev->exclude, rev->n_exclude);
+                                rev->seed, rev->n_seed, rev->exclude, rev->n_exclude, seed_from_rev);
     });
     rc0 = ctx->kmer.run(view, n_seq, seq_len, *opt, 0, words_fwd, freq_fwd, capacity, n_fwd, ctx->stream, err0,
-                        fwd->seed, fwd->n_seed, fwd->exclude, fwd->n_exclude);
+                        fwd->seed, fwd->n_seed, fwd->exclude, fwd->n_exclude, seed_from_fwd);
     rev_thread.join();
     if (rc0) return fail(ctx, rc0, err0);
     if (rc1) return fail(ctx, rc1, "direction 1: " + err1);
@@ -3171,62 +3189,38 @@ int coverage_thal_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t se
     return MSSPE_OK;
 }
 
-// msspe_panel_thin_thal*: coverage_thal_view's slab loop into the held incidence matrix, then PanelThin::rounds over
-// it.  No per-segment word, cell plane or record list is kept: a slab's matches are listed, their templates cut
-// (CoverageThal::oligos), with thin_thal_unique the distinct (primer, template) pairs of the slab found
-// (PanelThinThal::unique) and only those scored, and every stable match ORs its bit into the matrix, which is zeroed
-// once: a slab split by groups or by primers adds to the words the others wrote.
-int panel_thin_thal_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t seq_len, const msspe_kmer_opt *opt,
-                         const msspe_mismatch_opt *mm, const msspe_thin_opt *thin, const msspe_chem *chem, int mode,
-                         float tm_threshold, const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words,
-                         int n_rev, const uint8_t *forced, uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out,
-                         int *n_picked_out, uint8_t *covered_out, long long *covered_all_out,
-                         long long *covered_kept_out)
+// ev[3..5] of a scored slab of fill_held_matrix wait to be read behind the next synchronisation
+void thin_thal_read_scored(msspe_ctx *ctx, bool &scored)
 {
-    if (!opt || !mm || !thin || !chem || !keep_out || !order_out || !gain_out || !n_picked_out || n_fwd < 0 ||
-        n_rev < 0 || (n_fwd && !fwd_words) || (n_rev && !rev_words))
-        return fail(ctx, MSSPE_ERR_ARG, "panel thin thal: null argument");
-    if (thin->min_gain < 1) return fail(ctx, MSSPE_ERR_ARG, "panel thin thal: min_gain must be at least 1");
-    if (mode != 1 && mode != 2) return fail(ctx, MSSPE_ERR_ARG, "panel thin thal: mode must be 1 (ANY) or 2 (END1)");
     auto &tt = ctx->thin_thal;
-    tt.matches = tt.unique_pairs = tt.slabs = tt.redone = 0;
-    tt.list_us = tt.unique_us = tt.score_us = tt.fold_us = 0;
-    *n_picked_out = 0;
-    if (covered_all_out) *covered_all_out = 0;
-    if (covered_kept_out) *covered_kept_out = 0;
-    const int k = opt->kmer_size;
-    if (k < 2 || k > 31) return fail(ctx, MSSPE_ERR_K, "panel thin thal: unsupported k (need 2 <= k <= 31)");
-    std::string err;
-    long P = 0;
-    int rc = MismatchCoverage::check(n_seq, seq_len, *opt, mm->max_mismatches, mm->exact_3p, fwd_words, n_fwd,
-                                     rev_words, n_rev, &P, err);
-    if (rc) return fail(ctx, rc, err);
-    if (opt->search_window_size - k >= (1 << kCovOffBits))   // a match's offset travels in kCovOffBits bits
-        return fail(ctx, MSSPE_ERR_ARG, "panel thin thal: the search window has more than 2^26 positions");
-    const int n = n_fwd + n_rev;
-    const long n_seg = P * n_seq;
-    for (int p = 0; p < n; ++p) keep_out[p] = forced && forced[p] ? 1 : 0;
-    if (covered_out) std::fill(covered_out, covered_out + n_seg, (uint8_t)0);
-    if (n == 0 || n_seg == 0) return MSSPE_OK;
-    const size_t cap = (size_t)1 << ctx->opt.site_list_cap_log2;
-    if ((uint64_t)n + cap >= (1ull << 31)) return fail(ctx, MSSPE_ERR_ARG, "panel thin thal: too many primers");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const bool end1 = mode == 2;
-    ChemEntry *ce = nullptr;
-    if ((rc = chem_entry(ctx, *chem, tm_threshold, &ce, end1 ? kCutEndT : kCutAnyT))) return rc;
-    const double cut = ce->c[0].g_cut;
-    if ((rc = ensure_workspace(ctx, (size_t)k * (size_t)k))) return rc;
-    if ((rc = ensure_overflow(ctx, (long)cap))) return rc;
-    if ((rc = ensure_site_work(ctx, cap, n, 0))) return rc;
+    float a = 0.f, b = 0.f;
+    if (scored && hipEventElapsedTime(&a, tt.ev[3], tt.ev[4]) == hipSuccess &&
+        hipEventElapsedTime(&b, tt.ev[4], tt.ev[5]) == hipSuccess) {
+        tt.score_us += (long long)(a * 1000.f);
+        tt.fold_us += (long long)(b * 1000.f);
+    }
+    scored = false;
+}
+
+// The held incidence matrix of n_fwd + n_rev primers (msspe_panel_thin_thal*, and a tolerant seeded stage A's tiles):
+// d_inc (PanelThin::matrix made it for them) zeroed, then coverage_thal_view's slab loop into it.  The caller has
+// the chemistry's entry, the workspace, the overflow lists, the work list for these primers, their plane words
+// (CoverageThal::prepare_words) and the events; `scored` says that a last slab's events are still to be read
+// (thin_thal_read_scored, behind the caller's next synchronisation).
+int fill_held_matrix(msspe_ctx *ctx, const SeqView &view, long n_seg, long P, const msspe_kmer_opt *opt,
+                     const msspe_mismatch_opt *mm, ChemEntry *ce, bool end1, const uint64_t *fwd_words, int n_fwd,
+                     const uint64_t *rev_words, int n_rev, uint64_t *d_inc, bool &scored)
+{
+    auto &tt = ctx->thin_thal;
     auto &ct = ctx->cov_thal;
-    if ((rc = ct.prepare_words(*opt, fwd_words, n_fwd, rev_words, n_rev, ctx->stream, err))) return fail(ctx, rc, err);
-    if ((rc = tt.events(err))) return fail(ctx, rc, err);
+    std::string err;
+    int rc;
+    const int k = opt->kmer_size, n = n_fwd + n_rev;
+    const size_t cap = (size_t)1 << ctx->opt.site_list_cap_log2;
+    const double cut = ce->c[0].g_cut;
     const int S = MismatchCoverage::group_size(*opt);
     const long n_groups = (n_seg + S - 1) / S;
     const size_t n_pad = ((size_t)n + 63) & ~(size_t)63;
-    uint64_t *d_inc = nullptr;
-    if ((rc = ctx->thin.matrix(n, n_seg, S, (size_t)ctx->opt.panel_thin_matrix_max_mb << 20, &d_inc, err)))
-        return fail(ctx, rc, err);
     HIP_TRY(ctx, hipMemsetAsync(d_inc, 0, sizeof(uint64_t) * (size_t)n_groups * n_pad, ctx->stream));
     auto &w = ctx->site_work;
     CovMatch *list = reinterpret_cast<CovMatch *>(w.sites);
@@ -3241,16 +3235,7 @@ int panel_thin_thal_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t 
 
     struct Slab { long g0, g1; int p0, p1; };
     std::vector<Slab> todo{{0, n_groups, 0, n}};
-    bool scored = false;   // ev[3..5] of a scored slab wait to be read behind the next synchronisation
-    auto read_scored = [&]() {
-        float a = 0.f, b = 0.f;
-        if (scored && hipEventElapsedTime(&a, tt.ev[3], tt.ev[4]) == hipSuccess &&
-            hipEventElapsedTime(&b, tt.ev[4], tt.ev[5]) == hipSuccess) {
-            tt.score_us += (long long)(a * 1000.f);
-            tt.fold_us += (long long)(b * 1000.f);
-        }
-        scored = false;
-    };
+    auto read_scored = [&]() { thin_thal_read_scored(ctx, scored); };
     while (!todo.empty()) {
         const Slab s = todo.back();
         todo.pop_back();
@@ -3327,14 +3312,322 @@ int panel_thin_thal_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t 
         HIP_TRY(ctx, hipEventRecord(tt.ev[5], ctx->stream));
         scored = true;
     }
-    if ((rc = ctx->thin.rounds(n, n_seg, S, thin->min_gain, keep_out, order_out, gain_out, n_picked_out, covered_out,
-                               covered_all_out, covered_kept_out, ctx->n_cu, ctx->stream, err)))
-        return fail(ctx, rc, err);
-    read_scored();   // rounds returned with the stream idle
     return MSSPE_OK;
 }
 
+// msspe_panel_thin_thal*: coverage_thal_view's slab loop into the held incidence matrix, then PanelThin::rounds over
+// it.  No per-segment word, cell plane or record list is kept: a slab's matches are listed, their templates cut
+// (CoverageThal::oligos), with thin_thal_unique the distinct (primer, template) pairs of the slab found
+// (PanelThinThal::unique) and only those scored, and every stable match ORs its bit into the matrix, which is zeroed
+// once: a slab split by groups or by primers adds to the words the others wrote.
+int panel_thin_thal_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t seq_len, const msspe_kmer_opt *opt,
+                         const msspe_mismatch_opt *mm, const msspe_thin_opt *thin, const msspe_chem *chem, int mode,
+                         float tm_threshold, const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words,
+                         int n_rev, const uint8_t *forced, uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out,
+                         int *n_picked_out, uint8_t *covered_out, long long *covered_all_out,
+                         long long *covered_kept_out)
+{
+    if (!opt || !mm || !thin || !chem || !keep_out || !order_out || !gain_out || !n_picked_out || n_fwd < 0 ||
+        n_rev < 0 || (n_fwd && !fwd_words) || (n_rev && !rev_words))
+        return fail(ctx, MSSPE_ERR_ARG, "panel thin thal: null argument");
+    if (thin->min_gain < 1) return fail(ctx, MSSPE_ERR_ARG, "panel thin thal: min_gain must be at least 1");
+    if (mode != 1 && mode != 2) return fail(ctx, MSSPE_ERR_ARG, "panel thin thal: mode must be 1 (ANY) or 2 (END1)");
+    auto &tt = ctx->thin_thal;
+    tt.matches = tt.unique_pairs = tt.slabs = tt.redone = 0;
+    tt.list_us = tt.unique_us = tt.score_us = tt.fold_us = 0;
+    *n_picked_out = 0;
+    if (covered_all_out) *covered_all_out = 0;
+    if (covered_kept_out) *covered_kept_out = 0;
+    const int k = opt->kmer_size;
+    if (k < 2 || k > 31) return fail(ctx, MSSPE_ERR_K, "panel thin thal: unsupported k (need 2 <= k <= 31)");
+    std::string err;
+    long P = 0;
+    int rc = MismatchCoverage::check(n_seq, seq_len, *opt, mm->max_mismatches, mm->exact_3p, fwd_words, n_fwd,
+                                     rev_words, n_rev, &P, err);
+    if (rc) return fail(ctx, rc, err);
+    if (opt->search_window_size - k >= (1 << kCovOffBits))   // a match's offset travels in kCovOffBits bits
+        return fail(ctx, MSSPE_ERR_ARG, "panel thin thal: the search window has more than 2^26 positions");
+    const int n = n_fwd + n_rev;
+    const long n_seg = P * n_seq;
+    for (int p = 0; p < n; ++p) keep_out[p] = forced && forced[p] ? 1 : 0;
+    if (covered_out) std::fill(covered_out, covered_out + n_seg, (uint8_t)0);
+    if (n == 0 || n_seg == 0) return MSSPE_OK;
+    const size_t cap = (size_t)1 << ctx->opt.site_list_cap_log2;
+    if ((uint64_t)n + cap >= (1ull << 31)) return fail(ctx, MSSPE_ERR_ARG, "panel thin thal: too many primers");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const bool end1 = mode == 2;
+    ChemEntry *ce = nullptr;
+    if ((rc = chem_entry(ctx, *chem, tm_threshold, &ce, end1 ? kCutEndT : kCutAnyT))) return rc;
+    if ((rc = ensure_workspace(ctx, (size_t)k * (size_t)k))) return rc;
+    if ((rc = ensure_overflow(ctx, (long)cap))) return rc;
+    if ((rc = ensure_site_work(ctx, cap, n, 0))) return rc;
+    auto &ct = ctx->cov_thal;
+    if ((rc = ct.prepare_words(*opt, fwd_words, n_fwd, rev_words, n_rev, ctx->stream, err))) return fail(ctx, rc, err);
+    if ((rc = tt.events(err))) return fail(ctx, rc, err);
+    const int S = MismatchCoverage::group_size(*opt);
+    uint64_t *d_inc = nullptr;
+    if ((rc = ctx->thin.matrix(n, n_seg, S, (size_t)ctx->opt.panel_thin_matrix_max_mb << 20, &d_inc, err)))
+        return fail(ctx, rc, err);
+    bool scored = false;
+    if ((rc = fill_held_matrix(ctx, view, n_seg, P, opt, mm, ce, end1, fwd_words, n_fwd, rev_words, n_rev, d_inc, scored)))
+        return rc;
+    if ((rc = ctx->thin.rounds(n, n_seg, S, thin->min_gain, keep_out, order_out, gain_out, n_picked_out, covered_out,
+                               covered_all_out, covered_kept_out, ctx->n_cu, ctx->stream, err)))
+        return fail(ctx, rc, err);
+    thin_thal_read_scored(ctx, scored);   // rounds returned with the stream idle
+    return MSSPE_OK;
+}
+
+// ---- msspe_kmer_candidates_tolerant*: stage A seeded on what the panel covers --------------------------------------
+
+// One direction of a tolerant call: its distinct seed words (msspe_pack_oligos form) and its two state outputs.
+struct TolerantDir {
+    std::vector<uint64_t> words;
+    uint8_t *covered_out = nullptr;
+    uint32_t *partitions_out = nullptr;
+};
+
+// The rule's own argument errors, and the coverage calls' for these options (MismatchCoverage::check over the seeds as
+// the direction's primers; in modes 1 and 2 coverage_thal_view's); *P_out: partitions per record.
+int tolerant_check(msspe_ctx *ctx, int n_seq, size_t seq_len, const msspe_kmer_opt *opt, const msspe_seed_rule *rule,
+                   const msspe_kmer_sets *sets, int direction, long *P_out)
+{
+    if (rule->mode < 0 || rule->mode > 2) return fail(ctx, MSSPE_ERR_ARG, "tolerant seeding: mode must be 0, 1 (ANY) or 2 (END1)");
+    if (rule->mode && !rule->chem) return fail(ctx, MSSPE_ERR_ARG, "tolerant seeding: modes 1 and 2 need a chemistry");
+    const int k = opt->kmer_size;
+    if (rule->mode && (k < 2 || k > 31)) return fail(ctx, MSSPE_ERR_K, "tolerant seeding: unsupported k (need 2 <= k <= 31)");
+    const int ns = sets ? sets->n_seed : 0;
+    const uint64_t *seed = sets ? sets->seed : nullptr;
+    std::string err;
+    const int rc = MismatchCoverage::check(n_seq, seq_len, *opt, rule->max_mismatches, rule->exact_3p, direction ? nullptr : seed,
+                                           direction ? 0 : ns, direction ? seed : nullptr, direction ? ns : 0, P_out, err);
+    if (rc) return fail(ctx, rc, err);
+    if (rule->mode && opt->search_window_size - k >= (1 << kCovOffBits))
+        return fail(ctx, MSSPE_ERR_ARG, "tolerant seeding: the search window has more than 2^26 positions");
+    if (rule->mode && (uint64_t)ns + ((uint64_t)1 << ctx->opt.site_list_cap_log2) >= (1ull << 31))
+        return fail(ctx, MSSPE_ERR_ARG, "tolerant seeding: too many seeds");
+    return MSSPE_OK;
+}
+
+void tolerant_dir(const msspe_kmer_sets *sets, uint8_t *covered_out, uint32_t *partitions_out, long n_seg, long P,
+                  TolerantDir &d)
+{
+    if (sets && sets->n_seed) d.words.assign(sets->seed, sets->seed + sets->n_seed);
+    std::sort(d.words.begin(), d.words.end());
+    d.words.erase(std::unique(d.words.begin(), d.words.end()), d.words.end());
+    d.covered_out = covered_out;
+    d.partitions_out = partitions_out;
+    if (covered_out) std::fill(covered_out, covered_out + n_seg, (uint8_t)0);
+    if (partitions_out) std::fill(partitions_out, partitions_out + P, 0u);
+}
+
+// What the seeding passes share and a second host thread must not make: the chemistry's entry, the DP workspace and
+// the overflow lists of modes 1 and 2, the events.
+int tolerant_prepare(msspe_ctx *ctx, const msspe_kmer_opt *opt, const msspe_seed_rule *rule, ChemEntry **ce_out)
+{
+    auto &tl = ctx->tolerant;
+    tl.tiles = tl.segments = tl.incidence_us = tl.seed_us = 0;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    for (auto &e : tl.ev)
+        if (!e) HIP_TRY(ctx, hipEventCreate(&e));
+    *ce_out = nullptr;
+    if (!rule->mode) return MSSPE_OK;
+    auto &tt = ctx->thin_thal;
+    tt.matches = tt.unique_pairs = tt.slabs = tt.redone = 0;
+    tt.list_us = tt.unique_us = tt.score_us = tt.fold_us = 0;
+    const int k = opt->kmer_size;
+    int rc;
+    if ((rc = chem_entry(ctx, *rule->chem, rule->tm_threshold, ce_out, rule->mode == 2 ? kCutEndT : kCutAnyT))) return rc;
+    if ((rc = ensure_workspace(ctx, (size_t)k * (size_t)k))) return rc;
+    if ((rc = ensure_overflow(ctx, (long)((size_t)1 << ctx->opt.site_list_cap_log2)))) return rc;
+    std::string err;
+    if ((rc = tt.events(err))) return fail(ctx, rc, err);
+    return MSSPE_OK;
+}
+
+// One direction's seeding pass, called by KmerStage::run where k_seed would run.  The seeds go through the context's
+// incidence matrix in tiles of primers, each against all segment groups -- the state is an OR (ignored) and a sum
+// (coverage) over seeds, so the tiles add up -- sized so that a tile's matrix fits panel_thin_matrix_max_mb.  Mode 0
+// fills a tile as msspe_panel_thin* does, modes 1 and 2 as msspe_panel_thin_thal* does; KmerStage::seed_rows turns
+// its rows into the stage's state.  The pass runs on the context's stream, whichever stream the stage runs on (the
+// matrix, the work list and the scoring are the context's), one pass at a time, and returns with both streams idle.
+int tolerant_seed_pass(msspe_ctx *ctx, KmerStage &stage, hipStream_t stage_stream, const SeqView &view, int n_seq,
+                       size_t seq_len, const msspe_kmer_opt *opt, int direction, const TolerantDir &d,
+                       const msspe_seed_rule *rule, ChemEntry *ce, std::string &err)
+{
+    auto hip_bad = [&](hipError_t e, const char *what) {
+        err = std::string("tolerant seeding, ") + what + ": " + hipGetErrorString(e);
+        return MSSPE_ERR_DEVICE;
+    };
+#define TOL_TRY(expr)                                         \
+    do {                                                      \
+        hipError_t e__ = (expr);                              \
+        if (e__ != hipSuccess) return hip_bad(e__, #expr);    \
+    } while (0)
+    if (stage_stream != ctx->stream) TOL_TRY(hipStreamSynchronize(stage_stream));   // the stage's state is set
+    std::lock_guard<std::mutex> turn(ctx->tolerant.turn);
+    auto &tl = ctx->tolerant;
+    hipStream_t stream = ctx->stream;
+    const msspe_mismatch_opt mm = {rule->max_mismatches, rule->exact_3p};
+    const int n = (int)d.words.size();
+    const long P = seq_len < (size_t)opt->segment_size
+                       ? 0
+                       : (long)((seq_len - (size_t)opt->segment_size) / (size_t)opt->overlap_size) + 1;
+    const long n_seg = P * n_seq;
+    const int S = MismatchCoverage::group_size(*opt);
+    const long n_groups = (n_seg + S - 1) / S;
+    const size_t mib = (size_t)1 << 20, max_bytes = (size_t)ctx->opt.panel_thin_matrix_max_mb << 20;
+    const size_t fit = max_bytes / (sizeof(uint64_t) * (size_t)n_groups) & ~(size_t)63;   // seeds whose matrix fits
+    if (fit < 64) {
+        err = "tolerant seeding: the incidence matrix of 64 seeds needs " +
+              std::to_string((64 * sizeof(uint64_t) * (size_t)n_groups + mib - 1) / mib) +
+              " MB, panel_thin_matrix_max_mb is " + std::to_string(max_bytes / mib);
+        return MSSPE_ERR_CAPACITY;
+    }
+    const int tile = (int)std::min<size_t>(fit, ((size_t)n + 63) & ~(size_t)63);
+    int rc;
+    if (rule->mode && (rc = ensure_site_work(ctx, (size_t)1 << ctx->opt.site_list_cap_log2, std::min(tile, n), 0))) {
+        err = ctx->err;
+        return rc;
+    }
+    for (int t0 = 0; t0 < n; t0 += tile) {
+        const int nt = std::min(tile, n - t0);
+        const size_t n_pad = ((size_t)nt + 63) & ~(size_t)63;
+        const uint64_t *fwd = direction ? nullptr : d.words.data() + t0, *rev = direction ? d.words.data() + t0 : nullptr;
+        const int n_fwd = direction ? 0 : nt, n_rev = direction ? nt : 0;
+        uint64_t *d_inc = nullptr;
+        if ((rc = ctx->thin.matrix(nt, n_seg, S, max_bytes, &d_inc, err))) return rc;
+        TOL_TRY(hipEventRecord(tl.ev[0], stream));
+        if (!rule->mode) {
+            if ((rc = ctx->mm_cov.incidence(view, n_seq, seq_len, *opt, mm.max_mismatches, mm.exact_3p, fwd, n_fwd, rev,
+                                            n_rev, d_inc, stream, err)))
+                return rc;
+        } else {
+            if ((rc = ctx->cov_thal.prepare_words(*opt, fwd, n_fwd, rev, n_rev, stream, err))) return rc;
+            bool scored = false;
+            if ((rc = fill_held_matrix(ctx, view, n_seg, P, opt, &mm, ce, rule->mode == 2, fwd, n_fwd, rev, n_rev, d_inc,
+                                       scored))) {
+                err = ctx->err;
+                return rc;
+            }
+            TOL_TRY(hipStreamSynchronize(stream));
+            thin_thal_read_scored(ctx, scored);
+        }
+        TOL_TRY(hipEventRecord(tl.ev[1], stream));
+        if ((rc = stage.seed_rows(d_inc, n_pad, nt, n_groups, S, stream, err))) return rc;
+        TOL_TRY(hipEventRecord(tl.ev[2], stream));
+        TOL_TRY(hipStreamSynchronize(stream));   // (the next tile's words and matrix take this one's place)
+        float a = 0.f, b = 0.f;
+        if (hipEventElapsedTime(&a, tl.ev[0], tl.ev[1]) == hipSuccess) tl.incidence_us += (long long)(a * 1000.f);
+        if (hipEventElapsedTime(&b, tl.ev[1], tl.ev[2]) == hipSuccess) tl.seed_us += (long long)(b * 1000.f);
+        ++tl.tiles;
+    }
+    long long covered = 0;
+    if ((rc = stage.seed_state(d.covered_out, d.partitions_out, &covered, stage_stream, err))) return rc;
+    tl.segments += covered;
+    return MSSPE_OK;
+#undef TOL_TRY
+}
+
 }  // namespace
+
+// One direction of a tolerant call on the context's stream.  Without seeds it is the _sets call as it stands.
+static int tolerant_run(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t seq_len, const msspe_kmer_opt *opt,
+                        int direction, const msspe_kmer_sets *sets, const msspe_seed_rule *rule, uint64_t *words_out,
+                        uint32_t *freq_out, int capacity, int *n_out, uint8_t *seed_covered_out,
+                        uint32_t *seed_partitions_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if ((!view.ascii && !view.packed) || !opt || !rule || !words_out || !freq_out || !n_out || capacity < 0 ||
+        !sets_ok(sets))
+        return fail(ctx, MSSPE_ERR_ARG, "null argument");
+    *n_out = 0;
+    if (direction != 0 && direction != 1) return fail(ctx, MSSPE_ERR_ARG, "tolerant seeding: direction must be 0 or 1");
+    long P = 0;
+    int rc = tolerant_check(ctx, n_seq, seq_len, opt, rule, sets, direction, &P);
+    if (rc) return rc;
+    TolerantDir d;
+    tolerant_dir(sets, seed_covered_out, seed_partitions_out, P * n_seq, P, d);
+    if (d.words.empty()) {
+        auto &tl = ctx->tolerant;
+        tl.tiles = tl.segments = tl.incidence_us = tl.seed_us = 0;
+        return kmer_run(ctx, view, n_seq, seq_len, opt, direction, sets, words_out, freq_out, capacity, n_out);
+    }
+    ChemEntry *ce = nullptr;
+    if ((rc = tolerant_prepare(ctx, opt, rule, &ce))) return rc;
+    const KmerStage::SeedFrom seed_from = [&](KmerStage &stage, hipStream_t stream, std::string &err) {
+        return tolerant_seed_pass(ctx, stage, stream, view, n_seq, seq_len, opt, direction, d, rule, ce, err);
+    };
+    const msspe_kmer_sets excl = {nullptr, 0, sets->exclude, sets->n_exclude};
+    return kmer_run(ctx, view, n_seq, seq_len, opt, direction, &excl, words_out, freq_out, capacity, n_out, &seed_from);
+}
+
+int msspe_kmer_candidates_tolerant_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
+                                              const msspe_kmer_opt *opt, int direction, const msspe_kmer_sets *sets,
+                                              const msspe_seed_rule *rule, uint64_t *words_out, uint32_t *freq_out,
+                                              int capacity, int *n_out, uint8_t *seed_covered_out,
+                                              uint32_t *seed_partitions_out)
+{
+    return tolerant_run(ctx, SeqView{nullptr, d_packed, seq_len}, n_seq, seq_len, opt, direction, sets, rule, words_out,
+                        freq_out, capacity, n_out, seed_covered_out, seed_partitions_out);
+}
+
+int msspe_kmer_candidates_tolerant(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len,
+                                   const msspe_kmer_opt *opt, int direction, const msspe_kmer_sets *sets,
+                                   const msspe_seed_rule *rule, uint64_t *words_out, uint32_t *freq_out, int capacity,
+                                   int *n_out, uint8_t *seed_covered_out, uint32_t *seed_partitions_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!sets_ok(sets)) return fail(ctx, MSSPE_ERR_ARG, "null seed or exclusion list");
+    if (!seqs || n_seq < 0) return fail(ctx, MSSPE_ERR_ARG, "null sequences");
+    void *d = nullptr;
+    int rc = msspe_device_put(ctx, seqs, (size_t)n_seq * seq_len, &d);
+    if (rc) return rc;
+    rc = tolerant_run(ctx, SeqView{(const uint8_t *)d, nullptr, seq_len}, n_seq, seq_len, opt, direction, sets, rule,
+                      words_out, freq_out, capacity, n_out, seed_covered_out, seed_partitions_out);
+    (void)msspe_device_free(ctx, d);
+    return rc;
+}
+
+int msspe_kmer_candidates_both_tolerant_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
+                                                   const msspe_kmer_opt *opt, const msspe_kmer_sets *fwd,
+                                                   const msspe_kmer_sets *rev, const msspe_seed_rule *rule,
+                                                   uint64_t *words_fwd, uint32_t *freq_fwd, int *n_fwd,
+                                                   uint64_t *words_rev, uint32_t *freq_rev, int *n_rev, int capacity,
+                                                   uint8_t *seed_covered_fwd, uint32_t *seed_partitions_fwd,
+                                                   uint8_t *seed_covered_rev, uint32_t *seed_partitions_rev)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!d_packed || !opt || !rule || !words_fwd || !freq_fwd || !n_fwd || !words_rev || !freq_rev || !n_rev ||
+        capacity < 0 || !sets_ok(fwd) || !sets_ok(rev))
+        return fail(ctx, MSSPE_ERR_ARG, "null argument");
+    *n_fwd = *n_rev = 0;
+    long P = 0;
+    int rc;
+    if ((rc = tolerant_check(ctx, n_seq, seq_len, opt, rule, fwd, 0, &P)) ||
+        (rc = tolerant_check(ctx, n_seq, seq_len, opt, rule, rev, 1, &P)))
+        return rc;
+    TolerantDir d[2];
+    tolerant_dir(fwd, seed_covered_fwd, seed_partitions_fwd, P * n_seq, P, d[0]);
+    tolerant_dir(rev, seed_covered_rev, seed_partitions_rev, P * n_seq, P, d[1]);
+    ChemEntry *ce = nullptr;
+    auto &tl = ctx->tolerant;
+    tl.tiles = tl.segments = tl.incidence_us = tl.seed_us = 0;
+    if ((!d[0].words.empty() || !d[1].words.empty()) && (rc = tolerant_prepare(ctx, opt, rule, &ce))) return rc;
+    const SeqView view{nullptr, d_packed, seq_len};
+    // a direction without seeds runs as the _sets call does; the other's pass takes the context's stream in its turn
+    const KmerStage::SeedFrom from_fwd = [&](KmerStage &stage, hipStream_t stream, std::string &err) {
+        return tolerant_seed_pass(ctx, stage, stream, view, n_seq, seq_len, opt, 0, d[0], rule, ce, err);
+    };
+    const KmerStage::SeedFrom from_rev = [&](KmerStage &stage, hipStream_t stream, std::string &err) {
+        return tolerant_seed_pass(ctx, stage, stream, view, n_seq, seq_len, opt, 1, d[1], rule, ce, err);
+    };
+    const msspe_kmer_sets excl_fwd = {nullptr, 0, fwd ? fwd->exclude : nullptr, fwd ? fwd->n_exclude : 0};
+    const msspe_kmer_sets excl_rev = {nullptr, 0, rev ? rev->exclude : nullptr, rev ? rev->n_exclude : 0};
+    return kmer_run_both(ctx, d_packed, n_seq, seq_len, opt, d[0].words.empty() ? fwd : &excl_fwd,
+                         d[1].words.empty() ? rev : &excl_rev, words_fwd, freq_fwd, n_fwd, words_rev, freq_rev, n_rev,
+                         capacity, d[0].words.empty() ? nullptr : &from_fwd, d[1].words.empty() ? nullptr : &from_rev);
+}
 
 int msspe_segment_coverage_thal_dev(msspe_ctx *ctx, const uint8_t *d_seqs, int n_seq, size_t seq_len,
                                     const msspe_kmer_opt *opt, const msspe_mismatch_opt *mm, const uint64_t *fwd_words,

@@ -2285,6 +2285,73 @@ __global__ void __launch_bounds__(1024) k_seed(const uint64_t *seed, int n_seed,
     }
 }
 
+// Seeding from an incidence matrix (a tolerant seeded run, msspe_kmer_candidates_tolerant*): k_seed's update with a
+// seed's segments read from row p of inc[g * n_pad + p] (group-major, bit b of a word = segment g * S + b) instead of
+// the word's postings.  A block takes one row (blockIdx.x) and a share (blockIdx.y) of the groups; lane l of a wave
+// holds the row's word of group gb + l and takes its bits one at a time: the segment's flag is claimed as in k_seed,
+// the partitions of the wave go to the block's LDS bitmap with one atomic per distinct partition, and the fresh
+// segments' words lose a live count (cover_wave).  A row's groups are spread over several blocks, so its partitions
+// are settled in `seen` (one bitmap per row, zeroed by the caller): the block whose atomic OR sets a bit there is the
+// one that bumps coverage[j].
+// The column read has a stride of n_pad * 8 bytes: one word of each 64-byte line.  Measured at 10,000 x 30,000 with 289
+// seeds (86 MB of matrix, which stays in the last-level cache behind the pass that wrote it): this form 0.63-0.72 ms,
+// a form in which a block took eight neighbouring rows and read whole lines 1.47-1.58 ms -- the time
+// is in the claims and the live counts, not in the matrix, so the stride is left as it is.
+__global__ void __launch_bounds__(256) k_seed_rows(const uint64_t *inc, size_t n_pad, long n_groups, int S, int n_seg,
+                                                   uint8_t *ignored, uint32_t *coverage, unsigned *seen, int P, int G,
+                                                   int per, const int32_t *kid_of_inst, int32_t *count,
+                                                   unsigned long long *n_fresh)
+{
+    extern __shared__ unsigned char smem[];
+    unsigned *parts = (unsigned *)smem;
+    const int words = (P + 31) / 32;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
+    const size_t p = blockIdx.x;
+    for (int i = threadIdx.x; i < words; i += blockDim.x) parts[i] = 0u;
+    __syncthreads();
+    unsigned fresh_n = 0;   // (lane 0's is the wave's)
+    for (long gb = ((long)blockIdx.y * n_waves + wave) * 64; gb < n_groups; gb += (long)gridDim.y * n_waves * 64) {   // wave-uniform
+        const long g = gb + lane;
+        uint64_t w = g < n_groups ? inc[(size_t)g * n_pad + p] : 0ull;
+        while (__ballot(w != 0ull)) {   // wave-uniform
+            uint32_t row = 0;
+            int part = -1;
+            bool fresh = false;
+            if (w) {
+                const long s = g * S + (__ffsll((long long)w) - 1);
+                w &= w - 1ull;
+                if (s < n_seg) {   // (no matrix writer sets a bit beyond the last segment)
+                    part = (int)(s % P);
+                    row = (uint32_t)part * (uint32_t)G + (uint32_t)(s / P);
+                    const unsigned sh8 = 8u * (row & 3u);
+                    const unsigned old = atomicOr(reinterpret_cast<unsigned *>(ignored + (row & ~3u)), 1u << sh8);
+                    fresh = ((old >> sh8) & 0xffu) == 0u;
+                }
+            }
+            unsigned long long m = __ballot(part >= 0);
+            while (m) {   // one LDS atomic per distinct partition of the wave
+                const int l = __ffsll((long long)m) - 1;
+                const int pl = __builtin_amdgcn_readlane(part, l);
+                m &= ~__ballot(part == pl);
+                if (lane == l) atomicOr(&parts[pl >> 5], 1u << (pl & 31));
+            }
+            const unsigned long long fm = __ballot(fresh);
+            if (fm) {
+                cover_wave(row, fresh, per, G, kid_of_inst, count);
+                fresh_n += (unsigned)__popcll(fm);
+            }
+        }
+    }
+    if (lane == 0 && fresh_n) atomicAdd(n_fresh, (unsigned long long)fresh_n);
+    __syncthreads();
+    for (int i = threadIdx.x; i < words; i += blockDim.x) {
+        const unsigned bits = parts[i];
+        if (!bits) continue;
+        const unsigned old = atomicOr(&seen[p * words + i], bits);
+        for (unsigned m = bits & ~old; m; m &= m - 1u) atomicAdd(&coverage[i * 32 + __ffs((int)m) - 1], 1u);
+    }
+}
+
 // Coverage of the final primer set (main.rs:518-594): a segment is covered when its head window
 // holds one of the forward primers or its tail window holds the reverse complement of one of the
 // reverse primers.  One wave per segment, lane = window position; the primers are sorted packed
@@ -2405,10 +2472,59 @@ hipError_t launch_pack_rows(const uint8_t *d_ascii, int n_rows, size_t row_len, 
     return hipGetLastError();
 }
 
+// buffer 2: the rows' partition bitmaps of one call; buffer 15: the segments seed_rows covered in this run (run zeroes it)
+int KmerStage::seed_rows(const uint64_t *d_inc, size_t n_pad, int n_rows, long n_groups, int S, hipStream_t stream,
+                         std::string &err)
+{
+    const SeedPoint &sp = seed_point_;
+    if (!sp.ignored || !d_inc || n_rows < 0 || (size_t)n_rows > n_pad || S < 1 || S > 64 ||
+        n_groups != ((long)sp.n_seg + S - 1) / S) {
+        err = "stage A: seed_rows outside a seeding run, or a matrix of another shape";
+        return MSSPE_ERR_ARG;
+    }
+    if (n_rows == 0) return MSSPE_OK;
+    const size_t pwords = (size_t)((sp.P + 31) / 32);
+    int rc;
+    if ((rc = ensure(2, sizeof(unsigned) * pwords * (size_t)n_rows, err))) return rc;
+    unsigned long long *n_fresh = (unsigned long long *)buf_[15];
+    unsigned *seen = (unsigned *)buf_[2];
+    KM_TRY(hipMemsetAsync(seen, 0, sizeof(unsigned) * pwords * (size_t)n_rows, stream));
+    // a row's groups over as many blocks (of 256 groups a time) as bring the grid to about 2,048
+    const unsigned gy = (unsigned)std::max<long>(1, std::min<long>((n_groups + 255) / 256, std::max(1, 2048 / n_rows)));
+    hipLaunchKernelGGL(k_seed_rows, dim3((unsigned)n_rows, gy), dim3(256), sizeof(unsigned) * pwords, stream, d_inc, n_pad,
+                       n_groups, S, sp.n_seg, sp.ignored, sp.coverage, seen, sp.P, sp.n_seq, sp.per, sp.kid_of_inst,
+                       sp.count, n_fresh);
+    KM_TRY(hipGetLastError());
+    return MSSPE_OK;
+}
+
+int KmerStage::seed_state(uint8_t *covered_out, uint32_t *partitions_out, long long *covered_count_out,
+                          hipStream_t stream, std::string &err)
+{
+    const SeedPoint &sp = seed_point_;
+    if (!sp.ignored) {
+        err = "stage A: seed_state outside a seeding run";
+        return MSSPE_ERR_ARG;
+    }
+    std::vector<uint8_t> rows(covered_out ? (size_t)sp.n_seg : 0);
+    unsigned long long fresh = 0;
+    if (covered_out) KM_TRY(hipMemcpyAsync(rows.data(), sp.ignored, (size_t)sp.n_seg, hipMemcpyDeviceToHost, stream));
+    if (partitions_out)
+        KM_TRY(hipMemcpyAsync(partitions_out, sp.coverage, sizeof(uint32_t) * (size_t)sp.P, hipMemcpyDeviceToHost, stream));
+    if (covered_count_out) KM_TRY(hipMemcpyAsync(&fresh, buf_[15], sizeof fresh, hipMemcpyDeviceToHost, stream));
+    KM_TRY(hipStreamSynchronize(stream));
+    if (covered_out)   // the flags are partition-major (row_of): back to s = r * P + j
+        for (int j = 0; j < sp.P; ++j)
+            for (int r = 0; r < sp.n_seq; ++r)
+                covered_out[(size_t)r * sp.P + j] = rows[(size_t)j * sp.n_seq + r] ? 1 : 0;
+    if (covered_count_out) *covered_count_out = (long long)fresh;
+    return MSSPE_OK;
+}
+
 int KmerStage::run(const SeqView &d_seqs, int n_seq, size_t seq_len, const msspe_kmer_opt &opt,
                    int direction, uint64_t *words_out, uint32_t *freq_out, int capacity,
                    int *n_out, hipStream_t stream, std::string &err, const uint64_t *seed, int n_seed,
-                   const uint64_t *exclude, int n_exclude)
+                   const uint64_t *exclude, int n_exclude, const SeedFrom *seed_from)
 {
     *n_out = 0;
     const int k = opt.kmer_size, W = opt.search_window_size;
@@ -2455,19 +2571,40 @@ int KmerStage::run(const SeqView &d_seqs, int n_seq, size_t seq_len, const msspe
                        ? 0
                        : (long)((seq_len - (size_t)opt.segment_size) / (size_t)opt.overlap_size) + 1;
     const long n_seg_l = P * n_seq;
-    if (n_seg_l == 0 || opt.max_iterations == 0) return MSSPE_OK;
+    if (seed_from && !seed_keys.empty()) {
+        err = "stage A: a seed list together with a seeding caller";
+        return MSSPE_ERR_ARG;
+    }
+    if (n_seg_l == 0 || (opt.max_iterations == 0 && !seed_from)) return MSSPE_OK;
     if (P > 65536 || n_seg_l > 0x7fffffffL / (W - k + 1)) {
         err = "stage A: alignment too large for 32-bit instance indices";
         return MSSPE_ERR_ARG;
     }
     const int n_seg = (int)n_seg_l;
     const int per = W - k + 1;
+    // a seeding caller's run without a loop (no iterations asked for, or no word in the index): the flags and the
+    // coverage are all the state there is
+    auto seed_state_only = [&]() -> int {
+        int rc0;
+        if ((rc0 = ensure(11, ((size_t)n_seg + 7) & ~(size_t)3, err)) || (rc0 = ensure(12, (size_t)P * 8, err)) ||
+            (rc0 = ensure(15, 8, err)))
+            return rc0;
+        KM_TRY(hipMemsetAsync(buf_[11], 0, ((size_t)n_seg + 7) & ~(size_t)3, stream));
+        KM_TRY(hipMemsetAsync(buf_[12], 0, (size_t)P * 8, stream));
+        KM_TRY(hipMemsetAsync(buf_[15], 0, 8, stream));
+        seed_point_ = SeedPoint{(uint8_t *)buf_[11], (uint32_t *)buf_[12], nullptr, nullptr, (int)P, n_seq, 0, n_seg};
+        rc0 = (*seed_from)(*this, stream, err);
+        seed_point_ = SeedPoint{};
+        return rc0;
+    };
+    if (opt.max_iterations == 0) return seed_state_only();
     const size_t n_inst = (size_t)n_seg * per;
     const uint64_t sentinel = 1ull << (2 * k);
     int rc;
     // buffers: 0/1 keys, 2/3 vals, 4 the seeds (index keys), 5 first instances per index block and their scan, 6 kid_of_inst, 7 post, 8 post_off, 9 ukeys,
     // 10 count+tied, 11 ignored, 12 coverage+stamp, 13 status/out, 14 cub temp, 16 the candidate-list loop's
-    // PickState + per-word results (key, id, two partition bitmaps), 19 the excluded words (index keys)
+    // PickState + per-word results (key, id, two partition bitmaps), 19 the excluded words (index keys); 2 and 15
+    // are seed_rows'
     if ((rc = ensure(0, n_inst * 8, err)) || (rc = ensure(1, n_inst * 8, err)) ||
         (rc = ensure(3, n_inst * 4, err)) ||
         (rc = ensure(5, 2 * 4 * ((n_inst + kIndexBlock - 1) / kIndexBlock), err)) ||
@@ -2596,11 +2733,19 @@ int KmerStage::run(const SeqView &d_seqs, int n_seq, size_t seq_len, const msspe
         return MSSPE_OK;
     };
     if ((rc = 2 * k + 1 <= 32 ? build_index(uint32_t{}) : build_index(uint64_t{}))) return rc;
-    if (M == 0) return MSSPE_OK;
+    if (M == 0) return seed_from ? seed_state_only() : MSSPE_OK;
     hipLaunchKernelGGL(k_init_counts, dim3((M + 255) / 256), dim3(256), 0, stream, post_off, M, count);
     KM_TRY(hipGetLastError());
-    const bool seeded = !seed_keys.empty();
-    if (seeded) {
+    const bool seeded = !seed_keys.empty() || seed_from;
+    if (seed_from) {
+        // the caller's seeding, at k_seed's place (seed_rows, from its incidence matrix)
+        if ((rc = ensure(15, 8, err))) return rc;
+        KM_TRY(hipMemsetAsync(buf_[15], 0, 8, stream));
+        seed_point_ = SeedPoint{ignored, coverage, count, kid_of_inst, (int)P, n_seq, per, n_seg};
+        rc = (*seed_from)(*this, stream, err);
+        seed_point_ = SeedPoint{};
+        if (rc) return rc;
+    } else if (seeded) {
         // the seeds' post-push updates, on the call's stream ahead of the loop (never part of a captured batch)
         if ((rc = ensure(4, sizeof(uint64_t) * seed_keys.size(), err))) return rc;
         KM_TRY(hipMemcpyAsync(buf_[4], seed_keys.data(), sizeof(uint64_t) * seed_keys.size(), hipMemcpyHostToDevice,

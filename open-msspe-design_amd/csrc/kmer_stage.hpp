@@ -7,6 +7,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -39,10 +40,26 @@ public:
     // exclude / n_exclude (host, optional): packed words of the same key space that are treated as occurring in no
     // search window -- taken out of the extracted keys before the index is built (k_exclude), so they have no
     // postings, no count, and can be neither winners nor seeds; every other word keeps its own occurrences
+    // seed_from (optional; then seed / n_seed must be empty): the run is seeded by the caller instead of k_seed.  It is
+    // called once, at the point where k_seed would run -- the index built, the live counts set, ignored and coverage
+    // zero, all in stream order -- and seeds the state with seed_rows (any number of times); the loop then starts as
+    // a seeded run's does.  With no word in the index, or max_iterations == 0, it is still called (the state is then
+    // the flags and the coverage alone) and the run returns without winners.  A nonzero return ends the run with it.
+    using SeedFrom = std::function<int(KmerStage &, hipStream_t, std::string &)>;
     int run(const SeqView &seqs, int n_seq, size_t seq_len, const msspe_kmer_opt &opt,
             int direction, uint64_t *words_out, uint32_t *freq_out, int capacity, int *n_out,
             hipStream_t stream, std::string &err, const uint64_t *seed = nullptr, int n_seed = 0,
-            const uint64_t *exclude = nullptr, int n_exclude = 0);
+            const uint64_t *exclude = nullptr, int n_exclude = 0, const SeedFrom *seed_from = nullptr);
+    // Inside seed_from.  seed_rows: the post-push update of main.rs:371-378 for rows [0, n_rows) of an incidence
+    // matrix d_inc[g * n_pad + p] (device; group-major, bit b of a word = segment g * S + b, s = r * P + j; the words
+    // of rows >= n_rows are not read) -- a row's segments become ignored, and coverage[j] goes up by one for every
+    // distinct partition j among all of them.
+    // seed_state: ignored as covered_out[r * P + j] and coverage[] as partitions_out[P] (host, either may be null),
+    // and the segments seed_rows covered so far in this run; returns with the stream idle.
+    int seed_rows(const uint64_t *d_inc, size_t n_pad, int n_rows, long n_groups, int S, hipStream_t stream,
+                  std::string &err);
+    int seed_state(uint8_t *covered_out, uint32_t *partitions_out, long long *covered_count_out, hipStream_t stream,
+                   std::string &err);
     // Segment coverage of a primer set (main.rs:518-594): hit_out[seq * P + partition] = 1 when the
     // segment's head window holds a forward primer or its tail window the reverse complement of a
     // reverse primer.  fwd_words / rev_words / hit_out: host buffers.
@@ -75,6 +92,14 @@ private:
     hipGraphExec_t loop_exec_ = nullptr;
     std::vector<uint64_t> loop_sig_;
     void drop_loop_graph();
+    // the run's state where the seeding happens (valid inside seed_from): per == 0 when there is no index
+    struct SeedPoint {
+        uint8_t *ignored;
+        uint32_t *coverage;
+        int32_t *count;
+        const int32_t *kid_of_inst;
+        int P, n_seq, per, n_seg;
+    } seed_point_ = {};
     int ensure(int slot, size_t bytes, std::string &err);
 };
 

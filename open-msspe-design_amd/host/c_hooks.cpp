@@ -68,6 +68,9 @@ int odm_parse_args(int argc, const char *const *argv, char *out, size_t cap)
           << "\nthin_panel=" << a.thin_panel << "\nthin_mismatches=" << a.thin_mismatches
           << "\nthin_3p_exact=" << a.thin_3p_exact << "\nthin_min_gain=" << a.thin_min_gain
           << "\nthin_tm=" << a.thin_tm_text << "\nthin_thal=" << a.thin_thal
+          << "\nseed_mismatches=" << a.seed_mismatches << "\nseed_3p_exact=" << a.seed_3p_exact
+          << "\nseed_tm=" << a.seed_tm_text << "\nseed_thal=" << a.seed_thal
+          << "\nseed_tolerant=" << (a.seed_tolerant ? "true" : "false")
           << "\nbackground=" << a.background << "\nbackground_mismatches=" << a.background_mismatches
           << "\nbackground_3p_exact=" << a.background_3p_exact << "\nmax_background_sites=" << a.max_background_sites
           << "\nbackground_tm=" << a.background_tm_text << "\nbackground_thal=" << a.background_thal
@@ -149,6 +152,15 @@ int odm_thin_thal_block(int mode, float tm_threshold, int max_mismatches, int ex
     return emit(thin_thal_report(mode, tm_threshold, max_mismatches, exact_3p, min_gain, (size_t)kept_f, (size_t)n_f,
                                  (size_t)kept_r, (size_t)n_r, (size_t)forced, (size_t)held_all, (size_t)held_kept,
                                  (size_t)segments), out, cap);
+}
+
+// The block a seeding round of od-msspe-hip --seed-mismatches M prints (seed_report), from figures the caller has.
+// Needs no device.
+int odm_seed_block(int max_mismatches, int exact_3p, int mode, float tm_threshold, long long covered_f, long long panel_f,
+                   long long covered_r, long long panel_r, long long segments, char *out, size_t cap)
+{
+    return emit(seed_report(max_mismatches, exact_3p, mode, tm_threshold, (size_t)covered_f, (size_t)panel_f,
+                            (size_t)covered_r, (size_t)panel_r, (size_t)segments), out, cap);
 }
 
 int odm_is_run(const char *kmer) { return is_run(kmer) ? 1 : 0; }

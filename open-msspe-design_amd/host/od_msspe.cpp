@@ -85,6 +85,10 @@ const OptSpec kOpts[] = {
     {"--thin-min-gain", "THIN_MIN_GAIN", OptSpec::Int, OFF(thin_min_gain)},
     {"--thin-tm", "THIN_TM", OptSpec::Str, OFF(thin_tm_text)},
     {"--thin-thal", "THIN_THAL", OptSpec::Str, OFF(thin_thal)},
+    {"--seed-mismatches", "SEED_MISMATCHES", OptSpec::OptInt, OFF(seed_mismatches)},
+    {"--seed-3p-exact", "SEED_3P_EXACT", OptSpec::Str, OFF(seed_3p_exact_text)},
+    {"--seed-tm", "SEED_TM", OptSpec::Str, OFF(seed_tm_text)},
+    {"--seed-thal", "SEED_THAL", OptSpec::Str, OFF(seed_thal)},
     {"--background", "BACKGROUND", OptSpec::Str, OFF(background)},
     {"--background-mismatches", "BACKGROUND_MISMATCHES", OptSpec::OptInt, OFF(background_mismatches)},
     {"--background-3p-exact", "BACKGROUND_3P_EXACT", OptSpec::OptInt, OFF(background_3p_exact)},
@@ -154,7 +158,11 @@ std::string Args::usage()
          "--rejected-out <CSV> writes every candidate the run dropped (direction,name,primers,round,reason; reason is\n"
          "stage_b, background, panel_dimer or cover); --exclude-primers reads such a file.\n"
          "--repick-rounds <N> (0..16) repeats the selection up to N times: what passed is kept as a panel, what was\n"
-         "dropped is excluded, and stage A fills the holes. One device; not with --tubes.\n";
+         "dropped is excluded, and stage A fills the holes. One device; not with --tubes.\n"
+         "--seed-mismatches <M> makes a run that extends a panel (--existing-primers, and the later rounds of\n"
+         "--repick-rounds) count a segment as covered already when a panel primer matches it within M mismatches, its last\n"
+         "--seed-3p-exact <E> bases exact, instead of only where it occurs verbatim; with --seed-tm <C> only where thal\n"
+         "(--seed-thal any | end1) scores such a match stable at C. One device.\n";
     return u;
 }
 
@@ -275,6 +283,40 @@ Args Args::parse(int argc, const char *const *argv)
                 throw UsageError("error: invalid value '" + a.thin_thal +
                                  "' for '--thin-thal <...>'\n  [possible values: any, end1]");
         }
+    }
+    if (a.seed_mismatches >= 0 || !a.seed_tm_text.empty() || !a.seed_thal.empty() || !a.seed_3p_exact_text.empty()) {
+        if (!a.devices.empty())
+            throw UsageError("error: '--seed-mismatches', '--seed-3p-exact', '--seed-tm' and '--seed-thal' run on one "
+                             "device and cannot be combined with '--devices'");
+        if (!a.seed_thal.empty() && a.seed_tm_text.empty())
+            throw UsageError("error: '--seed-thal' needs '--seed-tm <C>'");
+    }
+    // read only when a round can seed, as the --thin-* values are read only with their switch
+    if ((!a.existing_primers.empty() || a.repick_rounds > 0) && (a.seed_mismatches >= 0 || !a.seed_tm_text.empty())) {
+        char *end = nullptr;
+        if (!a.seed_tm_text.empty()) {
+            a.seed_tm = std::strtof(a.seed_tm_text.c_str(), &end);
+            if (*end || std::isnan(a.seed_tm))
+                throw UsageError("error: invalid value '" + a.seed_tm_text + "' for '--seed-tm'");
+            if (a.kmer_size < 2) throw UsageError("error: '--seed-tm' needs '--kmer-size' of at least 2");
+            a.seed_scored = true;
+            if (a.seed_thal.empty()) a.seed_thal = "any";
+            if (a.seed_thal != "any" && a.seed_thal != "end1")
+                throw UsageError("error: invalid value '" + a.seed_thal +
+                                 "' for '--seed-thal <...>'\n  [possible values: any, end1]");
+            if (a.seed_mismatches < 0) a.seed_mismatches = 0;
+        }
+        if (a.seed_mismatches > a.kmer_size)
+            throw UsageError("error: '--seed-mismatches " + std::to_string(a.seed_mismatches) +
+                             "' is larger than '--kmer-size " + std::to_string(a.kmer_size) + "'");
+        const std::string v = a.seed_3p_exact_text.empty() ? "3" : a.seed_3p_exact_text;
+        const long e = std::strtol(v.c_str(), &end, 10);
+        if (*end || e < 0) throw UsageError("error: invalid value '" + v + "' for '--seed-3p-exact'");
+        if (e > a.kmer_size)
+            throw UsageError("error: '--seed-3p-exact " + v + "' is larger than '--kmer-size " +
+                             std::to_string(a.kmer_size) + "'");
+        a.seed_3p_exact = (int)e;
+        a.seed_tolerant = true;
     }
     if (a.background.empty()) {
         for (const auto &given : {std::make_pair("--background-mismatches", a.background_mismatches),
@@ -538,11 +580,13 @@ std::vector<KmerFrequency> find_candidates_kmers(Engine &eng, const DeviceAlignm
 std::pair<std::vector<KmerFrequency>, std::vector<KmerFrequency>> find_candidates_kmers_both(
     Engine &eng, const DeviceAlignment &aln, const ProgramConfig &cfg, int segment_size, int overlap_size, int window_size,
     const std::vector<std::string> &seed_f, const std::vector<std::string> &seed_r,
-    const std::vector<std::string> &excl_f, const std::vector<std::string> &excl_r)
+    const std::vector<std::string> &excl_f, const std::vector<std::string> &excl_r, const msspe_seed_rule *rule,
+    size_t *seed_covered)
 {
     if (overlap_size < window_size)   // main.rs:201-203
         throw Panic("Overlap windows size must be greater or equal than search windows size");
     std::pair<std::vector<KmerFrequency>, std::vector<KmerFrequency>> out;
+    if (seed_covered) seed_covered[0] = seed_covered[1] = 0;
     if (aln.rows() == 0) return out;
     msspe_kmer_opt opt{segment_size, overlap_size, window_size, cfg.primer_config.kmer_size,
                        cfg.max_iterations, cfg.max_mismatch_segments};
@@ -559,7 +603,22 @@ std::pair<std::vector<KmerFrequency>, std::vector<KmerFrequency>> find_candidate
             eng.fail(rc);
         return packed;
     };
-    if (!excl_f.empty() || !excl_r.empty()) {
+    if (rule) {   // the seeds cover what they match under the rule; the state before the first iteration comes back
+        const std::vector<uint64_t> sf = pack(seed_f), sr = pack(seed_r), xf = pack(excl_f), xr = pack(excl_r);
+        const msspe_kmer_sets fwd = {sf.data(), (int)seed_f.size(), xf.data(), (int)excl_f.size()};
+        const msspe_kmer_sets rev = {sr.data(), (int)seed_r.size(), xr.data(), (int)excl_r.size()};
+        const size_t L = aln.length();
+        const size_t P = L < (size_t)segment_size ? 0 : (L - (size_t)segment_size) / (size_t)overlap_size + 1;
+        std::vector<uint8_t> cov[2] = {std::vector<uint8_t>(P * (size_t)aln.rows() + 1),
+                                       std::vector<uint8_t>(P * (size_t)aln.rows() + 1)};
+        rc = msspe_kmer_candidates_both_tolerant_packed_dev(eng.ctx(), aln.device(), aln.rows(), L, &opt, &fwd, &rev, rule,
+                                                            words[0].data(), freq[0].data(), &n[0], words[1].data(),
+                                                            freq[1].data(), &n[1], cap, cov[0].data(), nullptr,
+                                                            cov[1].data(), nullptr);
+        if (!rc && seed_covered)
+            for (int d = 0; d < 2; ++d)
+                seed_covered[d] = (size_t)std::count(cov[d].begin(), cov[d].end() - 1, (uint8_t)1);
+    } else if (!excl_f.empty() || !excl_r.empty()) {
         const std::vector<uint64_t> sf = pack(seed_f), sr = pack(seed_r), xf = pack(excl_f), xr = pack(excl_r);
         const msspe_kmer_sets fwd = {sf.data(), (int)seed_f.size(), xf.data(), (int)excl_f.size()};
         const msspe_kmer_sets rev = {sr.data(), (int)seed_r.size(), xr.data(), (int)excl_r.size()};
@@ -1299,6 +1358,18 @@ std::string coverage_report_thal(Engine &eng, const DeviceAlignment &aln, const 
                                fwd.size() + rev.size(), max_mismatches, exact_3p, mode, tm_threshold);
 }
 
+std::string seed_report(int max_mismatches, int exact_3p, int mode, float tm_threshold, size_t covered_f, size_t panel_f,
+                        size_t covered_r, size_t panel_r, size_t segments)
+{
+    std::string s = "\nSeeding (up to " + std::to_string(max_mismatches) + " mismatches, last " + std::to_string(exact_3p) +
+                    " bases exact";
+    if (mode) s += std::string("; thal ") + (mode == 2 ? "END1" : "ANY") + ", t >= " + fmt("%.2f", (double)tm_threshold) + " C";
+    const std::string t = std::to_string(segments);
+    return s + "):\n  Forward: " + std::to_string(covered_f) + " of " + t + " segments covered by " +
+           std::to_string(panel_f) + " panel primers; Reverse: " + std::to_string(covered_r) + " of " + t +
+           " segments covered by " + std::to_string(panel_r) + " panel primers\n";
+}
+
 std::string thin_thal_report(int mode, float tm_threshold, int max_mismatches, int exact_3p, int min_gain,
                              size_t kept_f, size_t n_f, size_t kept_r, size_t n_r, size_t forced, size_t held_all,
                              size_t held_kept, size_t segments)
@@ -1706,6 +1777,7 @@ struct Selection {
     std::vector<KmerStat> good_f, good_r;
     std::vector<Rejected> rejected;
     std::map<std::string, int> tubes;   // --tubes
+    std::string seeding_text;           // --seed-mismatches / --seed-tm: the block of a round that seeded
 };
 
 // Stage A (started from the state in which the panel's words are picked already, never picking an excluded word),
@@ -1722,8 +1794,22 @@ Selection select_primers(Engine &eng, const DeviceAlignment &aln, const Args &ar
     auto reject = [&](const KmerStat &s, const char *reason) {
         sel.rejected.push_back({s.word, s.direction, round, reason});
     };
+    // --seed-mismatches / --seed-tm: a round with a panel seeds on what the panel covers under the rule
+    const msspe_chem seed_chem = ntthal_chem(opts);   // (the chemistry --coverage-tm scores with)
+    const int seed_mode = !args.seed_scored ? 0 : args.seed_thal == "end1" ? 2 : 1;
+    const msspe_seed_rule rule = {args.seed_mismatches, args.seed_3p_exact, seed_mode, seed_mode ? &seed_chem : nullptr,
+                                  args.seed_tm};
+    const bool tolerant = args.seed_tolerant && (!panel_f.empty() || !panel_r.empty());
+    size_t seed_covered[2] = {0, 0};
     const auto cand_both = find_candidates_kmers_both(eng, aln, cfg, args.window_size, args.overlap_size,
-                                                      args.search_windows_size, panel_f, panel_r, excl_f, excl_r);
+                                                      args.search_windows_size, panel_f, panel_r, excl_f, excl_r,
+                                                      tolerant ? &rule : nullptr, seed_covered);
+    if (tolerant) {
+        const size_t L = aln.length();
+        const size_t P = L < (size_t)args.window_size ? 0 : (L - (size_t)args.window_size) / (size_t)args.overlap_size + 1;
+        sel.seeding_text = seed_report(args.seed_mismatches, args.seed_3p_exact, seed_mode, args.seed_tm, seed_covered[0],
+                                       panel_f.size(), seed_covered[1], panel_r.size(), P * (size_t)aln.rows());
+    }
     const auto &cand_f = cand_both.first, &cand_r = cand_both.second;
     timer.lap("stage A (both directions)");
     const auto stats_f = get_kmer_stats(eng, cand_f, cfg);
@@ -1879,6 +1965,7 @@ int run(const Args &args, std::string &stdout_text)
         for (const auto &p : s.good_r) kept_r.push_back(p.word);
         for (const auto &r : s.rejected) (r.direction == SEQ_DIR_FWD ? ban_f : ban_r).push_back(r.word);
         const size_t n_new = s.good_f.size() + s.good_r.size(), n_rej = s.rejected.size();
+        rounds_text += s.seeding_text;
         rounds.push_back(std::move(s));
         if (args.repick_rounds > 0)
             rounds_text += "Re-pick round " + std::to_string(round) + ": " + std::to_string(n_new) + " new, " +

@@ -96,6 +96,19 @@ struct Args {
     std::string thin_tm_text, thin_thal;
     float thin_tm = 0.0f;
     bool thin_scored = false;
+    // --seed-mismatches M: a round that seeds stage A (with --existing-primers, and rounds >= 1 of --repick-rounds)
+    // seeds it on what the panel COVERS -- every segment of the direction in which a panel primer has a match within M
+    // mismatches, its last seed_3p_exact bases exact (msspe_kmer_candidates_both_tolerant_packed_dev) -- instead of
+    // the segments that hold it verbatim, and the report gains a block per seeding round.  --seed-tm C: only the
+    // matches thal scores stable at C cover (--seed-thal any | end1, the chemistry of --coverage-tm); it implies
+    // M = 0 when --seed-mismatches is not given.  -1 / empty: not given -- exact seeding, nothing changes.  The values
+    // are read only when a round can seed; --seed-thal needs --seed-tm; one device.
+    int seed_mismatches = -1;
+    std::string seed_3p_exact_text;   // empty: not given (3)
+    int seed_3p_exact = 3;
+    std::string seed_tm_text, seed_thal;
+    float seed_tm = 0.0f;
+    bool seed_scored = false, seed_tolerant = false;
     // --background FASTA: after the coverage report, the off-target sites of every kept primer in these records (both
     // strands, up to background_mismatches mismatches, the last background_3p_exact bases exact:
     // msspe_background_sites); with max_background_sites >= 0 candidates with more sites are dropped before the
@@ -223,7 +236,14 @@ std::vector<KmerFrequency> find_candidates_kmers(Engine &eng, const std::vector<
 std::pair<std::vector<KmerFrequency>, std::vector<KmerFrequency>> find_candidates_kmers_both(
     Engine &eng, const DeviceAlignment &aln, const ProgramConfig &cfg, int segment_size, int overlap_size, int window_size,
     const std::vector<std::string> &seed_f = {}, const std::vector<std::string> &seed_r = {},
-    const std::vector<std::string> &excl_f = {}, const std::vector<std::string> &excl_r = {});
+    const std::vector<std::string> &excl_f = {}, const std::vector<std::string> &excl_r = {},
+    const msspe_seed_rule *rule = nullptr, size_t *seed_covered = nullptr);
+// rule (--seed-mismatches / --seed-tm): the seeds cover what they match under it (a tolerant seeded run);
+// seed_covered[2]: the segments each direction's seeds covered before the first iteration.
+// "Seeding (up to M mismatches, last E bases exact[; thal NAME, t >= T C]):" and, per direction, the segments the panel
+// primers covered of the alignment's; mode 0: the match rule alone
+std::string seed_report(int max_mismatches, int exact_3p, int mode, float tm_threshold, size_t covered_f, size_t panel_f,
+                        size_t covered_r, size_t panel_r, size_t segments);
 // --existing-primers (and --exclude-primers: `option` names the switch in the messages): the F and R primers of a
 // panel CSV (the header names the columns; direction and primers are read, the others ignored); throws UsageError
 // naming the line when a primer is not kmer_size bases of ACGT or the direction is not F / R

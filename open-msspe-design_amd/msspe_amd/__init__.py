@@ -3,9 +3,10 @@
 The product path is the HIP library; importing this package never touches oracle/.
 """
 from .capi import (Engine, Group, group_rows, MsspeError, Chem, KmerOpt, MismatchOpt, ThinOpt, lib_path, load_library, pack_oligos,
-                   unpack_oligo, round_g_f32, round_fixed_f32, g_cut, t_cut, STATUS)
+                   unpack_oligo, round_g_f32, round_fixed_f32, g_cut, t_cut, STATUS, SeedRule, seed_rule)
 from . import synth
 from . import distributed
 
 __all__ = ["Engine", "Group", "group_rows", "MsspeError", "Chem", "KmerOpt", "MismatchOpt", "ThinOpt", "lib_path", "load_library", "pack_oligos",
-           "unpack_oligo", "round_g_f32", "round_fixed_f32", "g_cut", "t_cut", "STATUS", "synth", "distributed"]
+           "unpack_oligo", "round_g_f32", "round_fixed_f32", "g_cut", "t_cut", "STATUS", "SeedRule", "seed_rule",
+           "synth", "distributed"]

@@ -32,6 +32,8 @@ EXPORTS = [
     "msspe_kmer_candidates_seeded", "msspe_kmer_candidates_seeded_packed_dev",
     "msspe_kmer_candidates_both_seeded_packed_dev",
     "msspe_kmer_candidates_sets", "msspe_kmer_candidates_sets_packed_dev", "msspe_kmer_candidates_both_sets_packed_dev",
+    "msspe_kmer_candidates_tolerant", "msspe_kmer_candidates_tolerant_packed_dev",
+    "msspe_kmer_candidates_both_tolerant_packed_dev",
     "msspe_segment_coverage_packed_dev",
     "msspe_segment_coverage_mm", "msspe_segment_coverage_mm_dev", "msspe_segment_coverage_mm_packed_dev",
     "msspe_segment_coverage_thal", "msspe_segment_coverage_thal_dev", "msspe_segment_coverage_thal_packed_dev",
@@ -240,6 +242,13 @@ def load_library() -> C.CDLL:
     L.msspe_kmer_candidates_both_sets_packed_dev.argtypes = [vp, vp, C.c_int, C.c_size_t, C.POINTER(KmerOpt),
                                                              C.POINTER(KmerSets), C.POINTER(KmerSets), vp, vp,
                                                              C.POINTER(C.c_int), vp, vp, C.POINTER(C.c_int), C.c_int]
+    L.msspe_kmer_candidates_tolerant.argtypes = [vp, vp, C.c_int, C.c_size_t, C.POINTER(KmerOpt), C.c_int,
+                                                 C.POINTER(KmerSets), C.POINTER(SeedRule), vp, vp, C.c_int,
+                                                 C.POINTER(C.c_int), vp, vp]
+    L.msspe_kmer_candidates_tolerant_packed_dev.argtypes = L.msspe_kmer_candidates_tolerant.argtypes
+    L.msspe_kmer_candidates_both_tolerant_packed_dev.argtypes = [
+        vp, vp, C.c_int, C.c_size_t, C.POINTER(KmerOpt), C.POINTER(KmerSets), C.POINTER(KmerSets), C.POINTER(SeedRule),
+        vp, vp, C.POINTER(C.c_int), vp, vp, C.POINTER(C.c_int), C.c_int, vp, vp, vp, vp]
     L.msspe_packed_row_words.restype = C.c_size_t
     L.msspe_packed_row_words.argtypes = [C.c_size_t]
     L.msspe_device_put_rows_packed.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_size_t,
@@ -459,6 +468,22 @@ def _kmer_sets(seed: np.ndarray | None, exclude: np.ndarray | None) -> KmerSets:
     return KmerSets(seed.ctypes.data if seed is not None and len(seed) else None, 0 if seed is None else len(seed),
                     exclude.ctypes.data if exclude is not None and len(exclude) else None,
                     0 if exclude is None else len(exclude))
+
+
+class SeedRule(C.Structure):
+    """msspe_seed_rule: what a seed covers in a tolerant seeded run -- its matches within max_mismatches with the last
+    exact_3p bases exact (mode 0), or those of them that thal scores stable at tm_threshold (mode 1 ANY, 2 END1)."""
+    _fields_ = [("max_mismatches", C.c_int), ("exact_3p", C.c_int), ("mode", C.c_int), ("chem", C.POINTER(Chem)),
+                ("tm_threshold", C.c_float)]
+
+
+def seed_rule(max_mismatches: int, exact_3p: int, mode=0, chem: Chem | None = None,
+              tm_threshold: float = 0.0) -> SeedRule:
+    """mode: 0 | "any" / 1 | "end1" / 2.  The Chem is kept alive by the returned struct."""
+    m = mode if isinstance(mode, int) else THAL_MODES[mode]
+    r = SeedRule(max_mismatches, exact_3p, m, C.pointer(chem) if chem is not None else None, tm_threshold)
+    r._chem = chem
+    return r
 
 
 def _ascii(oligos):
@@ -1341,6 +1366,64 @@ class Engine:
                 words.ctypes.data, freqs.ctypes.data, cap, C.byref(n_out)))
         m = n_out.value
         return [unpack_oligo(w, opt.kmer_size) for w in words[:m]], freqs[:m].copy()
+
+    # ---- stage A seeded on what a panel covers (msspe_kmer_candidates_tolerant*) -------------------------------
+    def _tolerant(self, fn, seqs_arg, n_seq, seq_len, opt, direction, seed, rule, exclude, capacity):
+        cap = max(1, opt.max_iterations if capacity is None else capacity)
+        words = np.zeros(cap, dtype=np.uint64)
+        freqs = np.zeros(cap, dtype=np.uint32)
+        n_out = C.c_int(0)
+        P = (seq_len - opt.segment_size) // opt.overlap_size + 1 if seq_len >= opt.segment_size > 0 < opt.overlap_size else 0
+        covered = np.zeros(max(0, n_seq) * P, dtype=np.uint8)
+        parts = np.zeros(P, dtype=np.uint32)
+        sw = _seed_words(seed, opt.kmer_size)
+        xw = _seed_words(exclude, opt.kmer_size, "exclude")
+        sets = _kmer_sets(sw, xw)
+        self._check(fn(self.ptr, seqs_arg, n_seq, seq_len, C.byref(opt), direction, C.byref(sets), C.byref(rule),
+                       words.ctypes.data, freqs.ctypes.data, cap, C.byref(n_out), covered.ctypes.data,
+                       parts.ctypes.data))
+        m = n_out.value
+        return ([unpack_oligo(w, opt.kmer_size) for w in words[:m]], freqs[:m].copy(), covered.reshape(max(0, n_seq), P),
+                parts)
+
+    def kmer_candidates_tolerant(self, seqs: np.ndarray, opt: KmerOpt, direction: int, seed, rule: SeedRule, *,
+                                 exclude=None, capacity: int | None = None):
+        """Stage A extending a panel on what the panel covers (msspe_kmer_candidates_tolerant; host sequences): the
+        seed words cover every segment of the direction they match under `rule` (seed_rule()).  Returns (words, freqs,
+        seed_covered uint8 (n_seq, P), seed_partitions uint32 (P)): the winners, and the state before the first
+        iteration."""
+        a = np.ascontiguousarray(seqs, dtype=np.uint8)
+        return self._tolerant(self.L.msspe_kmer_candidates_tolerant, a.ctypes.data, a.shape[0], a.shape[1], opt,
+                              direction, seed, rule, exclude, capacity)
+
+    def kmer_candidates_tolerant_packed(self, d_packed: int, n_seq: int, seq_len: int, opt: KmerOpt, direction: int,
+                                        seed, rule: SeedRule, *, exclude=None, capacity: int | None = None):
+        """The same on a packed alignment resident on the device (msspe_kmer_candidates_tolerant_packed_dev)."""
+        return self._tolerant(self.L.msspe_kmer_candidates_tolerant_packed_dev, C.c_void_p(d_packed), n_seq, seq_len,
+                              opt, direction, seed, rule, exclude, capacity)
+
+    def kmer_candidates_tolerant_both_packed(self, d_packed: int, n_seq: int, seq_len: int, opt: KmerOpt, seed_fwd,
+                                             seed_rev, rule: SeedRule, *, exclude_fwd=None, exclude_rev=None,
+                                             capacity: int | None = None):
+        """Both directions at once under one rule (msspe_kmer_candidates_both_tolerant_packed_dev): the two seeding
+        passes one after the other, the two greedy loops side by side.  Returns the two directions' 4-tuples."""
+        cap = max(1, opt.max_iterations if capacity is None else capacity)
+        P = (seq_len - opt.segment_size) // opt.overlap_size + 1 if seq_len >= opt.segment_size > 0 < opt.overlap_size else 0
+        w = [np.zeros(cap, dtype=np.uint64) for _ in range(2)]
+        f = [np.zeros(cap, dtype=np.uint32) for _ in range(2)]
+        cov = [np.zeros(max(0, n_seq) * P, dtype=np.uint8) for _ in range(2)]
+        parts = [np.zeros(P, dtype=np.uint32) for _ in range(2)]
+        n = [C.c_int(0), C.c_int(0)]
+        lists = [(_seed_words(seed_fwd, opt.kmer_size), _seed_words(exclude_fwd, opt.kmer_size, "exclude")),
+                 (_seed_words(seed_rev, opt.kmer_size), _seed_words(exclude_rev, opt.kmer_size, "exclude"))]
+        sets = [_kmer_sets(*lists[0]), _kmer_sets(*lists[1])]
+        self._check(self.L.msspe_kmer_candidates_both_tolerant_packed_dev(
+            self.ptr, C.c_void_p(d_packed), n_seq, seq_len, C.byref(opt), C.byref(sets[0]), C.byref(sets[1]),
+            C.byref(rule), w[0].ctypes.data, f[0].ctypes.data, C.byref(n[0]), w[1].ctypes.data, f[1].ctypes.data,
+            C.byref(n[1]), cap, cov[0].ctypes.data, parts[0].ctypes.data, cov[1].ctypes.data, parts[1].ctypes.data))
+        return tuple(([unpack_oligo(x, opt.kmer_size) for x in w[d][:n[d].value]], f[d][:n[d].value].copy(),
+                      cov[d].reshape(max(0, n_seq), P), parts[d]) for d in (0, 1))
+
 
 
 def _both(self, d_packed: int, n_seq: int, seq_len: int, opt: KmerOpt, capacity: int | None = None, *,
