@@ -149,7 +149,14 @@ const char *msspe_version(void);
  *                                 are.  Decisions are the exact stages' either way.  msspe_get_info "bound_list_pairs" /
  *                                 "bound_list_survivors": entries that list held / ordered pairs handed on from it
  *                                 since the last read
- *   "stage_a_graph"  "0" | "1"    hipGraph replay of stage A's greedy loop (1)
+ *   "pair_bound_packed" "auto" | "0" | "1"  where the bound first stage runs, its PACKED instance runs in its place
+ *                                 (k_pairs_bound_packed: the same bound in a coarser unit of 1, 2 or 4 cal/mol, every term
+ *                                 rounded down, the value in the slot word beside the coordinates -- half the slot
+ *                                 registers, four waves per SIMD), wherever a proven range of the chemistry's cell values
+ *                                 fits that field (msspe_host_bound_packed; "auto", the default, and "1": the same);
+ *                                 "0": the exact-unit instance.  A coarser bound only culls fewer pairs; decisions are
+ *                                 the exact stages' either way
+ *   "stage_a_graph" "0" | "1"    hipGraph replay of stage A's greedy loop (1)
  *   "stage_a_candidates" "0" | "1"  greedy loop over the list of words near the maximum (1), or over all the
  *                                 words on every iteration (0); the winners are the same */
 int msspe_set_option(msspe_ctx *ctx, const char *key, const char *value);
@@ -289,6 +296,11 @@ int msspe_cross_dimer_edges(msspe_ctx *ctx, const char *pool_ascii, int n, int k
  * MSSPE_ERR_ARG where the stage does not apply: k > 13, a threshold whose cut is above 0, tables it cannot hold. */
 int msspe_cross_dimer_bound_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const msspe_chem *chem,
                                 float dg_threshold, int row0, int row1, int col0, int col1, double *d_bound);
+/* The same plane from the PACKED instance of the bound first stage (option "pair_bound_packed"): the same pairs carry
+ * a value, +inf and -inf; a value is an integer multiple of the instance's unit (1, 2 or 4 cal/mol) and at most the
+ * exact-unit instance's.  MSSPE_ERR_ARG also where the chemistry's range of cell values fits none of those units. */
+int msspe_cross_dimer_bound_packed_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const msspe_chem *chem,
+                                       float dg_threshold, int row0, int row1, int col0, int col1, double *d_bound);
 /* The same plane with the bound LIST stage (option "pair_bound_list") behind the first stage: every pair the first stage
  * would put on list U -- 53..63 stored cells, lanes dragged or shed from their wave -- carries the value that stage
  * computes for it (the same recurrence on the same integer terms) instead of -inf.  -inf remains exactly for pairs of two
@@ -487,6 +499,14 @@ int msspe_host_screen_plan(int first_stage, int row0, int row1, int col0, int nc
  * is above it), units per cal/mol, margin in units, bound of every reachable |sum|, the void marker, longest oligo. */
 int msspe_host_bound_tables(const char *params_path, const msspe_chem *chem, float dg_threshold, int32_t *bound_g,
                             int32_t *bound_T, int32_t info[8]);
+/* Host only: the packed bound instance's tables (option "pair_bound_packed"; csrc/fast_tables.hpp BoundPacked), same
+ * layout: every finite entry of msspe_host_bound_tables' arrays floored to a unit of 2^(shift - 6) cal/mol (entry >>
+ * shift), void entries as they are.  info = usable, shift (6, 7 or 8), bias (slot field = cell value + bias), lo, hi
+ * (the proven range of every value a cell can publish, coarse units: 0 <= lo + bias, hi + bias <= info[7]), initiation
+ * term, cut (a pair is culled iff initiation + minimum > cut; floor(exact cut / 2^shift)), largest field value.
+ * usable = 0 (all else 0): the bound stage does not apply, or no shift holds the range -- the exact-unit instance runs. */
+int msspe_host_bound_packed(const char *params_path, const msspe_chem *chem, float dg_threshold, int32_t *packed_g,
+                            int32_t *packed_T, int32_t info[8]);
 /* Host only: *mirror_ok = 1 when the bound first stage may fill each unordered pair of a square same-pool screen once
  * (option "pair_mirror"): its tables are usable and every real-valued term of them equals its strand-swapped partner
  * within 1e-6 cal/mol (csrc/fast_tables.hpp bound_mirror_ok). */

@@ -57,6 +57,9 @@ struct ChemEntry {
     BoundTables *d_bt = nullptr;  // the bound first stage's tables (thal_pairs_row.hip k_pairs_bound)
     bool bound_ok = false;        // ... usable: row_ok, g_cut <= 0, values in range (build_bound_tables)
     bool mirror_ok = false;       // ... and strand-symmetric term by term (bound_mirror_ok): a square screen fills each unordered pair once
+    BoundTables *d_btq = nullptr; // the packed bound instance's coarse tables (BoundPacked::q; k_pairs_bound_packed)
+    bool packed_ok = false;       // ... usable: a proven range of every cell value fits the slot word's 15-bit field (build_bound_packed)
+    int packed_shift = 0, packed_bias = 0;
     // option pair_bound = auto: the share of pairs the bound stage could not cull, per oligo length, as the first
     // call's probe launch measured it (this entry keys on chemistry AND threshold); < 0: no record yet
     float bound_share[16] = {-1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f};
@@ -106,6 +109,8 @@ struct EngineOptions {
                               // both orders -- 0 never | 1, 2 (auto): wherever the tables are strand-symmetric (ChemEntry::mirror_ok)
     int pair_bound_list = 2;  // lanes that leave the bound first stage without a bound of their own go to list U and are bounded there
                               // (k_pairs_bound_list) before the exact lists -- 0 never | 1, 2 (auto): wherever the bound first stage runs
+    int pair_bound_packed = 2;  // the bound first stage runs its packed instance (k_pairs_bound_packed: one register per slot, coarse
+                              // units, 1,024 threads) -- 0 never | 1, 2 (auto): wherever the chemistry's range fits (ChemEntry::packed_ok)
     bool split_list = true;   // short oligos: tables too large for the integer list stage go to the split kernel's list mode
     bool short_chain = true;  // screens of up to 2^23 pairs: integer list stage -> one wave per pair (no register-table stages between)
     int self_lane_from = 81920;   // oligos per call from which SELF_ANY / SELF_END run one lane per oligo (msspe_oligo_stats_dev)
@@ -313,6 +318,14 @@ int chem_entry(msspe_ctx *ctx, const msspe_chem &chem, float threshold, ChemEntr
             if (e.bound_ok) {
                 HIP_TRY(ctx, hipMalloc((void **)&e.d_bt, sizeof(BoundTables)));
                 HIP_TRY(ctx, hipMemcpy(e.d_bt, bt.get(), sizeof(BoundTables), hipMemcpyHostToDevice));
+                auto bp = std::make_unique<BoundPacked>();
+                e.packed_ok = build_bound_packed(*bt, pairs_bound_max_k(), *bp);
+                if (e.packed_ok) {
+                    e.packed_shift = bp->shift;
+                    e.packed_bias = bp->bias;
+                    HIP_TRY(ctx, hipMalloc((void **)&e.d_btq, sizeof(BoundTables)));
+                    HIP_TRY(ctx, hipMemcpy(e.d_btq, &bp->q, sizeof(BoundTables), hipMemcpyHostToDevice));
+                }
             }
         }
     }
@@ -793,6 +806,10 @@ int msspe_set_option(msspe_ctx *ctx, const char *key, const char *value)
         if (v == "auto") ctx->opt.pair_mirror = 2;
         else if (is_num && (num == 0 || num == 1)) ctx->opt.pair_mirror = (int)num;
         else return bad();
+    } else if (k == "pair_bound_packed") {
+        if (v == "auto") ctx->opt.pair_bound_packed = 2;
+        else if (is_num && (num == 0 || num == 1)) ctx->opt.pair_bound_packed = (int)num;
+        else return bad();
     } else if (k == "pair_bound_list") {
         if (v == "auto") ctx->opt.pair_bound_list = 2;
         else if (is_num && (num == 0 || num == 1)) ctx->opt.pair_bound_list = (int)num;
@@ -877,6 +894,7 @@ int msspe_get_info(msspe_ctx *ctx, const char *key, long long *value_out)
     else if (k == "pair_bound") *value_out = ctx->opt.pair_bound;
     else if (k == "pair_mirror") *value_out = ctx->opt.pair_mirror;
     else if (k == "pair_bound_list") *value_out = ctx->opt.pair_bound_list;
+    else if (k == "pair_bound_packed") *value_out = ctx->opt.pair_bound_packed;
     else if (k == "bound_list_pairs" || k == "bound_list_survivors") {
         // the bound list stage since the last read of this key (reading resets it): entries of list U (unordered pairs under
         // the mirror), ordered pairs it appended to list 0
@@ -976,6 +994,7 @@ void msspe_destroy(msspe_ctx *ctx)
             if (e.d_ft) (void)hipFree(e.d_ft);
             if (e.d_it) (void)hipFree(e.d_it);
             if (e.d_bt) (void)hipFree(e.d_bt);
+            if (e.d_btq) (void)hipFree(e.d_btq);
             if (e.d_st) (void)hipFree(e.d_st);
         }
         if (ctx->wsS) (void)hipFree(ctx->wsS);
@@ -1068,6 +1087,7 @@ struct ChainRoute {
     FirstStage first;   // Dense: the dense kernel takes the whole block; Int (ANY only) stands for the integer kernel and
                         // its row-specialised and bound instances until settle_first_stage has picked one
     bool bound_list = false;   // Bound, BoundMirror: the bound list stage runs at every flush (option pair_bound_list)
+    bool bound_packed = false; // Bound, BoundMirror: the packed instance is the first stage (option pair_bound_packed)
     StageList behind;   // the list stages behind a first stage other than Dense, in order
 };
 
@@ -1121,6 +1141,9 @@ static int settle_first_stage(msspe_ctx *ctx, ChemEntry *ce, const ScreenBlock &
                         (long)b.sinks.ncols <= mirror_launch_cap(ctx->list_cap);
     route.first = mirror ? FirstStage::BoundMirror : FirstStage::Bound;
     route.bound_list = ctx->opt.pair_bound_list != 0;
+    // the packed instance wherever the chemistry's range fits its field (auto and 1 alike: never where it is not proven);
+    // the probe above and the plane form msspe_cross_dimer_bound_dev stay on the exact-unit instance
+    route.bound_packed = ce->packed_ok && ctx->opt.pair_bound_packed != 0;
     return MSSPE_OK;
 }
 
@@ -1215,7 +1238,8 @@ static int run_chain(msspe_ctx *ctx, ChemEntry *ce, ChainRoute route, const Scre
         case FirstStage::Bound:
         case FirstStage::BoundMirror:
             HIP_TRY(ctx, launch_pairs_bound(a, ce->d_it, ce->d_bt, ctx->d_reasons + kBoundSurvivors, nullptr, ctx->n_cu,
-                                            ctx->stream, route.first == FirstStage::BoundMirror, u_list, u_count));
+                                            ctx->stream, route.first == FirstStage::BoundMirror, u_list, u_count,
+                                            route.bound_packed ? ce->d_btq : nullptr, ce->packed_bias, ce->packed_shift));
             break;
         }
         if ((rc = prof_end())) return rc;
@@ -1362,7 +1386,8 @@ int msspe_cross_dimer_edges_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, i
 // with_list: the pairs the first stage would put on list U are bounded by the bound list stage, whose values replace
 // their -inf.
 static int cross_dimer_bound_plane(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const msspe_chem *chem,
-                                   float dg_threshold, int row0, int row1, int col0, int col1, double *d_bound, bool with_list)
+                                   float dg_threshold, int row0, int row1, int col0, int col1, double *d_bound, bool with_list,
+                                   bool packed = false)
 {
     const ScreenBlock b = screen_block(d_pool, n, k, k, row0, row1, col0, col1, plane_sinks(nullptr, nullptr, nullptr, nullptr));
     ChemEntry *ce = nullptr;
@@ -1372,6 +1397,9 @@ static int cross_dimer_bound_plane(msspe_ctx *ctx, const uint64_t *d_pool, int n
     if (k > pairs_bound_max_k() || !ce->bound_ok || !ctx->lds_reads_zero || !ctx->opt.row_oob)
         return fail(ctx, MSSPE_ERR_ARG, "msspe_cross_dimer_bound_dev: the bound stage does not apply (more than 13 bases, a cut "
                                         "above 0, tables outside its range, or option row_oob = 0)");
+    if (packed && !ce->packed_ok)
+        return fail(ctx, MSSPE_ERR_ARG, "msspe_cross_dimer_bound_packed_dev: no coarse unit of the packed instance holds this "
+                                        "chemistry's range of cell values");
     const int ncols = b.sinks.ncols;
     int rc2 = 0;
     const long n_pairs = (long)(row1 - row0) * (long)ncols;
@@ -1384,7 +1412,8 @@ static int cross_dimer_bound_plane(msspe_ctx *ctx, const uint64_t *d_pool, int n
     // one launch over the whole block (the diagnostic form appends nothing to list 0)
     const PairKernelArgs a = first_stage_args(ctx, ce, b, Launch{row0, row1, 0, ncols, 0, 0, false});
     if (!with_list) {
-        HIP_TRY(ctx, launch_pairs_bound(a, ce->d_it, ce->d_bt, nullptr, d_bound, ctx->n_cu, ctx->stream));
+        HIP_TRY(ctx, launch_pairs_bound(a, ce->d_it, ce->d_bt, nullptr, d_bound, ctx->n_cu, ctx->stream, false, nullptr, nullptr,
+                                        packed ? ce->d_btq : nullptr, ce->packed_bias, ce->packed_shift));
         return MSSPE_OK;
     }
     uint32_t *const u_count = ctx->ovf_count + kOvfU;
@@ -1399,6 +1428,12 @@ int msspe_cross_dimer_bound_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, i
                                 float dg_threshold, int row0, int row1, int col0, int col1, double *d_bound)
 {
     return cross_dimer_bound_plane(ctx, d_pool, n, k, chem, dg_threshold, row0, row1, col0, col1, d_bound, false);
+}
+
+int msspe_cross_dimer_bound_packed_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const msspe_chem *chem,
+                                       float dg_threshold, int row0, int row1, int col0, int col1, double *d_bound)
+{
+    return cross_dimer_bound_plane(ctx, d_pool, n, k, chem, dg_threshold, row0, row1, col0, col1, d_bound, false, true);
 }
 
 int msspe_cross_dimer_bound_list_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const msspe_chem *chem,
@@ -4121,6 +4156,43 @@ int msspe_host_bound_tables(const char *params_path, const msspe_chem *chem, flo
     info[5] = BoundTables::kReach;
     info[6] = IntTables::kValid;
     info[7] = pairs_bound_max_k();
+    return MSSPE_OK;
+}
+
+int msspe_host_bound_packed(const char *params_path, const msspe_chem *chem, float dg_threshold, int32_t *packed_g,
+                            int32_t *packed_T, int32_t info[8])
+{
+    // host only: the packed bound instance's tables (csrc/fast_tables.hpp BoundPacked) as chem_entry() would build them
+    if (!chem || !packed_g || !packed_T || !info) return MSSPE_ERR_ARG;
+    for (int q = 0; q < 8; ++q) info[q] = 0;
+    auto tb = std::make_unique<NNTables>();
+    std::string err;
+    const std::string path = params_path && *params_path ? params_path : default_bundle_path();
+    if (!load_nn_tables(path, *tb, err)) return MSSPE_ERR_TABLES;
+    if (!(chem->dna_conc > 0) || chem->max_loop < 0 || chem->max_loop > 30) return MSSPE_ERR_ARG;
+    const ThalConsts c = make_dimer_consts(chem->mv, chem->dv, chem->dntp, chem->dna_conc, chem->temp_c,
+                                           chem->max_loop, false, dg_threshold);
+    auto pt = std::make_unique<PairTables>();
+    if (!build_pair_tables(*tb, c, *pt, err)) return MSSPE_ERR_TABLES;
+    auto ft = std::make_unique<FastTables>();
+    auto it = std::make_unique<IntTables>();
+    auto st = std::make_unique<SplitTables>();
+    const TableRoutes r = table_routes(*tb, *pt, chem->max_loop, *ft, *it, *st);
+    auto bt = std::make_unique<BoundTables>();
+    auto bp = std::make_unique<BoundPacked>();
+    const bool ok = build_bound_tables(*ft, c, pairs_bound_max_k(), *bt) && r.row_ok &&
+                    build_bound_packed(*bt, pairs_bound_max_k(), *bp);
+    if (!ok) std::memset(bp.get(), 0, sizeof(BoundPacked));
+    std::memcpy(packed_g, bp->q.g, sizeof bp->q.g);
+    std::memcpy(packed_T, bp->q.T, sizeof bp->q.T);
+    info[0] = ok ? 1 : 0;
+    info[1] = bp->shift;
+    info[2] = bp->bias;
+    info[3] = bp->lo;
+    info[4] = bp->hi;
+    info[5] = bp->q.init;
+    info[6] = bp->q.cut;
+    info[7] = BoundPacked::kFieldMax;
     return MSSPE_OK;
 }
 

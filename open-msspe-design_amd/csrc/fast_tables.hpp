@@ -126,4 +126,32 @@ bool build_bound_tables(const FastTables &ft, const ThalConsts &c, int max_k, Bo
 // cell-side mismatch terms kTSc / kMMc <-> the predecessor-side terms they become.
 bool bound_mirror_ok(const FastTables &ft, const ThalConsts &c);
 
+// Tables of the PACKED bound first stage (thal_pairs_row.hip k_pairs_bound_packed): BoundTables' terms in a coarser
+// unit of 2^(shift - 6) cal/mol (shift 6, 7 or 8: 1, 2 or 4 cal/mol), every finite term FLOORED (arithmetic >> shift;
+// void stays void), so that a cell value fits the 15-bit field of the slot word beside K and the slot table is one
+// register per slot.  floor(a) + floor(b) <= floor(a + b): the minimum over chains of the floored terms, times the
+// unit, is at most BoundTables' minimum, hence a lower bound of every dG thal() can report all the same -- coarser
+// rounding costs survivors, never soundness.  The cut is floor(cut / 2^shift) and the cull rule  lbq > cutq, which
+// implies lbq 2^shift >= (cutq + 1) 2^shift > cut: the margin is spent exactly as before.
+struct BoundPacked {
+    static constexpr int kFieldBits = 15;
+    static constexpr int32_t kFieldMax = (1 << kFieldBits) - 1;
+    static constexpr int kShiftMin = 6, kShiftMax = 8;     // 2^6 units of 1/64 cal/mol = 1 cal/mol
+    static_assert((1 << kShiftMin) == BoundTables::kUnitInv, "shift 6 is 1 cal/mol");
+    // every coarse term and every reachable coarse sum is below this (BoundTables::kReach >> kShiftMin): the kernel's
+    // "not available" arithmetic is stated against it
+    static constexpr int32_t kReach = BoundTables::kReach >> kShiftMin;
+    BoundTables q;       // g, T, init, cut in coarse units (usable, max_k, mirror_ok copied)
+    int32_t shift;       // 0 when unusable
+    int32_t bias;        // slot field = cell value + bias
+    int32_t lo, hi;      // PROVEN range of every value a cell can publish, coarse units: lo + bias >= 0, hi + bias <= kFieldMax
+    int32_t usable;
+};
+// From finished BoundTables: the smallest shift whose proven range of publishable cell values fits the field.  A cell's
+// value is min(left end term, candidates), so it is at most the largest finite left end term; and it is the sum of a
+// left end term and at most max_k - 1 steps, a step being a table entry (loop or stacked pair) plus at most one
+// cell-side term, so it is at least the most negative left end term plus (max_k - 1) x the most negative step.
+// usable = 0 (and the exact-unit instance runs) when bt is unusable or no shift fits.
+bool build_bound_packed(const BoundTables &bt, int max_k, BoundPacked &out);
+
 }  // namespace msspe

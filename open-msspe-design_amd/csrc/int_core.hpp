@@ -179,6 +179,9 @@ struct IntArgs {
     unsigned long long *bound_survivors = nullptr;   // += pairs the bound could not cull
     double *bound_plane = nullptr;                    // diagnostic form: the bound of every pair, nothing else is written
     int mirror = 0;                                   // each unordered pair once: rows in sorted order, columns q >= p (launch_pairs_bound)
+    // the packed bound instance (k_pairs_bound_packed): bt holds BoundPacked::q, the terms in units of 2^(shift - 6) cal/mol
+    int packed_bias = 0;                              // slot field = cell value + bias (BoundPacked::bias)
+    double packed_unit = 0.0;                         // cal/mol per unit (the plane form's values)
     // list U: lanes that left their wave of the bound instance WITHOUT a bound of their own (53..63 stored cells, dragged,
     // shed by the slot fit), once per unordered pair; k_pairs_bound_list bounds them.  nullptr: they go to ovf_list
     uint2 *ulist = nullptr;

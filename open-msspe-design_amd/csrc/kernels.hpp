@@ -138,7 +138,11 @@ bool pairs_row_tables_ok(const IntTables &it);   // host: may this chemistry run
 // bound_plane != nullptr: the diagnostic form (the bound of every pair in cal/mol, nothing else is written).
 hipError_t launch_pairs_bound(const PairKernelArgs &a, const IntTables *it, const BoundTables *bt,
                               unsigned long long *survivors, double *bound_plane, int n_cu, hipStream_t stream,
-                              bool mirror = false, uint2 *ulist = nullptr, uint32_t *ucount = nullptr);
+                              bool mirror = false, uint2 *ulist = nullptr, uint32_t *ucount = nullptr,
+                              const BoundTables *packed_q = nullptr, int packed_bias = 0, int packed_shift = 0);
+// packed_q != nullptr (BoundPacked::q on the device, with its bias and shift): the PACKED instance runs
+// (k_pairs_bound_packed: one register per slot, 1,024 threads) -- the same contract, the bound in units of
+// 2^(shift - 6) cal/mol, every term floored, which only lowers it; the plane form's values are multiples of that unit.
 // ulist != nullptr (capacity a.overflow_cap, counter *ucount): list U.  A pair that leaves the stage WITHOUT a bound of
 // its own and fits the list stage's table (53..63 stored cells, dragged lanes, lanes shed by the slot fit) is appended there
 // instead, once per unordered pair (bit 30 of .x: it stands for (col, row) as well); launch_pairs_bound_list bounds it.

@@ -728,6 +728,51 @@ bool build_bound_tables(const FastTables &ft, const ThalConsts &c, int max_k, Bo
     return ok;
 }
 
+bool build_bound_packed(const BoundTables &bt, int max_k, BoundPacked &out)
+{
+    typedef BoundPacked P;
+    std::memset(&out, 0, sizeof out);
+    if (!bt.usable || max_k < 2 || max_k > bt.max_k) return false;
+    auto finite = [](int32_t v) { return v < IntTables::kValid; };
+    for (int s = P::kShiftMin; s <= P::kShiftMax; ++s) {
+        // floored: arithmetic shift (a negative value rounds towards -inf); void stays void
+        auto coarse = [&](int32_t v) -> int32_t { return finite(v) ? (int32_t)(v >> s) : v; };
+        for (int e = 0; e < IntTables::kRows * 64; ++e) out.q.T[e] = coarse(bt.T[e]);
+        for (int e = 0; e < FastTables::kCount; ++e) out.q.g[e] = coarse(bt.g[e]);
+        out.q.init = bt.init >> s;
+        out.q.cut = bt.cut >> s;
+        // the proven range of a publishable cell value
+        long step = 0, side = 0, end_lo = 0, end_hi = 0;
+        bool have_end = false;
+        for (int e = 0; e < IntTables::kRows * 64; ++e)
+            if (finite(out.q.T[e])) step = std::min<long>(step, out.q.T[e]);
+        for (int e = FastTables::kWC; e < FastTables::kWC + 16; ++e)
+            if (finite(out.q.g[e])) step = std::min<long>(step, out.q.g[e]);
+        for (int e = FastTables::kTSc; e < FastTables::kZero; ++e)
+            if (finite(out.q.g[e])) side = std::min<long>(side, out.q.g[e]);
+        for (int e = FastTables::kEndL; e < FastTables::kEndR; ++e)
+            if (finite(out.q.g[e])) {
+                end_lo = have_end ? std::min<long>(end_lo, out.q.g[e]) : out.q.g[e];
+                end_hi = have_end ? std::max<long>(end_hi, out.q.g[e]) : out.q.g[e];
+                have_end = true;
+            }
+        if (!have_end) break;
+        const long lo = end_lo + (long)(max_k - 1) * (step + side), hi = end_hi;
+        if (hi - lo > (long)P::kFieldMax || lo <= -(long)P::kReach || hi >= (long)P::kReach) continue;
+        out.shift = s;
+        out.lo = (int32_t)lo;
+        out.hi = (int32_t)hi;
+        out.bias = (int32_t)-lo;
+        out.q.usable = 1;
+        out.q.max_k = max_k;
+        out.q.mirror_ok = bt.mirror_ok;
+        out.usable = 1;
+        return true;
+    }
+    std::memset(&out, 0, sizeof out);
+    return false;
+}
+
 bool build_split_tables(const PairTables &pt, int max_loop, SplitTables &out)
 {
     typedef SplitTables W;

@@ -43,6 +43,7 @@
 #include "int_core.hpp"
 #include "row_scan_pinned.inc"
 #include "row_bound_pinned.inc"
+#include "row_bound_packed_pinned.inc"
 
 
 namespace msspe {
@@ -809,9 +810,106 @@ static __device__ __forceinline__ int run_pair_bound(SharedRow &sh, const SeqPai
     return pick;
 }
 
+// ---- the PACKED bound instance (k_pairs_bound_packed): the same minimum in a coarser unit, one register per slot --------
+// BoundPacked (fast_tables.hpp): every term floored to 2^(shift - 6) cal/mol, which only lowers the bound, and a proven
+// range [lo, hi] of every value a cell can publish with hi - lo < 2^15.  The slot word is  K << 17 | (value + bias),
+// bits 15 and 16 zero as in the other instances, and the cell's minuend C keeps 0x7fff in its low 15 bits, so that
+// t = C - W never borrows into K: t >> 15 is the table address, and the low 16 bits of t are  u = 0x7fff - bias - value.
+// The table holds  Tn = kPkOff - entry  and 0 for "not available", so  u + Tn = kc - (entry + value)  with
+// kc = 0x7fff - bias + kPkOff: the running MAXIMUM of it is the minimum over the candidates (v_mad_u32_u16 adds the low
+// half of t to the entry: the visit stays at 3.5 vector instructions).  The cell-side term of the far chunks is the same
+// for every far entry of a cell, so it is added ONCE, to the far minimum (tools/gen_row_bound_packed_asm.py).
+// 52 slot registers instead of 104: the kernel fits 128 VGPRs, i.e. four waves per SIMD at 1,024 threads, for the
+// latency of the table reads.
+static constexpr int kPkReach = BoundPacked::kReach;    // every coarse term, every bias and every reachable sum is below this
+static constexpr int kPkOff = 1 << 28;                  // a real entry is stored as kPkOff - entry (> 0); stored 0: not available
+static constexpr int kPkYVoid = 1 << 26;                // a void cell-side term
+static constexpr int kPkInit = 1 << 24;                 // the pick's starting minimum
+// an entry: loop term + folded-in cell-side term (2 kPkReach), a folded-out cell-side term taken out (kPkReach, or kPkYVoid)
+static constexpr int kPkEntryMax = 3 * kPkReach;
+static_assert(kPkInit >= 2 * kPkReach, "above every cell value plus an end term");
+static_assert((long long)kPkOff - kPkEntryMax - kPkYVoid > 0x7fffLL + kPkReach,
+              "a candidate built on a real entry (u + Tn, a void cell-side term subtracted in the straddling chunk included) is "
+              "above every candidate built on a stored 0 (u - yt <= 0x7fff + kPkReach): a 0 is never the maximum beside a real one");
+static_assert((long long)kPkOff + kPkEntryMax + kPkYVoid + 0x7fffLL + kPkReach < 0x7fffffffLL, "largest u + Tn - yt is an int32");
+static_assert((long long)kPkOff - 4 * kPkReach - 0x7fffLL > kPkReach,
+              "an accumulator that saw stored 0s only decodes (kc - acc + Y, bias and Y above -kPkReach) above every left end term");
+static_assert(kPkYVoid - kPkEntryMax - kPkReach > kPkReach, "a candidate that holds a void cell-side term stays above every left end term");
+static_assert((long long)0x7fff + kPkReach + kPkOff + kPkYVoid < 0x7fffffffLL, "kc - acc + Y is an int32");
+static_assert((kEmptyRowK << 17) > 0 && ((kEmptyRowK << 17) & 0x1ffff) == 0, "the empty slot word: K alone");
+
+static __device__ __forceinline__ void packed_scan(const v32i Wa, const v16i Wb, const v4i Wc, unsigned C, int Y, int n_far,
+                                                int n_run, int near_from, int &acc_far, int &acc_near)
+{
+    int MSSPE_BPK13_TEMP_NAMES;   // the generator's temporaries: two chunks in flight
+    asm volatile(MSSPE_BPK13_SCAN_ASM
+                 : MSSPE_BPK13_ACC_OUT(acc_far, acc_near), MSSPE_BPK13_TEMPS_OUT
+                 : [C] "v"(C), [Y] "v"(Y), [NFAR] "s"(n_far), [NRUN] "s"(n_run), [NEAR] "s"(near_from),
+                   [TOFF] "n"((int)offsetof(SharedRow, T)), MSSPE_BPK13_TUPLES_IN(Wa, Wb, Wc)
+                 : MSSPE_BPK13_SCAN_CLOBBERS);
+}
+// slot: wave-uniform, < kRowSlots.  One indexed write, whatever tuple the slot falls into.
+static __device__ __forceinline__ void packed_publish(v32i &Wa, v16i &Wb, v4i &Wc, int slot, int Wcell)
+{
+    asm volatile("s_set_gpr_idx_on %[SLOT], gpr_idx(DST)\n\t"
+                 "v_mov_b32 v%c[W0], %[W]\n\t"
+                 "s_set_gpr_idx_off"
+                 : MSSPE_BPK13_TUPLES_INOUT(Wa, Wb, Wc)
+                 : [W] "v"(Wcell), [SLOT] "s"(slot), [W0] "n"(MSSPE_BPK13_W0)
+                 : "m0");
+}
+
+// run_pair_bound on the packed table: the minimum over the lane's cells of (cell value + right end term) in coarse
+// units; kPkInit: the pair has no cell.  bias: BoundPacked::bias (wave-uniform).
+template <int NS>
+static __device__ __forceinline__ int run_pair_packed(SharedRow &sh, const SeqPair &q, bool active, unsigned wmax4, int bias)
+{
+    static_assert(kPin && NS == 52, "the bound instance exists for 13 bases");
+    constexpr int kC4 = MSSPE_BPK13_KC;
+    v32i Wa = kEmptyRowK << 17;
+    v16i Wb = kEmptyRowK << 17;
+    v4i Wc = kEmptyRowK << 17;
+    CellCtx c;
+    const int kc = 0x7fff - bias + kPkOff;   // u + Tn = kc - (entry + predecessor's value)
+    int pick = kPkInit;
+    int slot_ = 0, start_im1 = 0;   // first slot of row i-1
+    for (int i_ = 0; i_ < q.len; ++i_) {
+      const int im1 = __builtin_amdgcn_readfirstlane(i_);
+      const int a_row = (int)((q.s1 >> (2 * im1)) & 3u);
+      const int w_row = (int)((wmax4 >> (8 * (3 - a_row))) & 0xffu);   // widest lane's cells in this row
+      const int row_start = __builtin_amdgcn_readfirstlane(slot_);
+      const bool stored = im1 < q.len - 1;   // wave-uniform: the cells of the last row are nobody's predecessors
+      unsigned mrem = active ? spaced_mask(q.s2, 3 - a_row, q.lenmask) : 0u;
+      for (int c_ = 0; c_ < w_row; ++c_, slot_ += stored ? 1 : 0) {
+        const int slot = __builtin_amdgcn_readfirstlane(slot_);
+        const bool in = mrem != 0u;
+        const int jm1 = ((__ffs((int)mrem) - 1) >> 1) & 15;
+        mrem &= mrem - 1;
+        const unsigned C = ((unsigned)((jm1 - 1) * kRowA + im1 * (4 * (kRowR + 1)) + 3) << 17) | 0x7fffu;
+        const int yTS = sh.yts[(im1 << 2) | (int)(((q.s2 << 2) >> (2 * jm1)) & 3u)];
+        int acc_far, acc_near;
+        packed_scan(Wa, Wb, Wc, C, yTS, start_im1 / kC4, (row_start + kC4 - 1) / kC4, start_im1, acc_far, acc_near);
+        const CellBases b = cell_bases(q, im1, jm1, c);
+        const int gL = sh.g[b.idxL - kRowGBase], gR = sh.g[b.idxR - kRowGBase];
+        // the far minimum takes the cell-side term here, once; an accumulator without a real candidate decodes far above gL
+        const int G0 = min(gL, min(kc - acc_far + yTS, kc - acc_near));
+        pick = in ? min(pick, G0 + gR) : pick;
+        // G0 + bias is a 15-bit field: BoundPacked's proven range [lo, hi] of every publishable value (a lane without a
+        // cell here publishes an empty slot: its word fails every geometry test)
+        const int Wcell = in ? ((int)((unsigned)(jm1 * kRowA + (im1 << 2) + ((b.po_c >> 4) & 3)) << 17) + (G0 + bias)) : (kEmptyRowK << 17);
+        if (slot < NS) packed_publish(Wa, Wb, Wc, slot, Wcell);
+      }
+      start_im1 = row_start;
+    }
+    return pick;
+}
+
 // The bound table of row primer s1: build_row_table's entries from BoundTables (same layout, same folded cell-side
 // terms), plus the stacked pair at (l2 = 0, r = 1), whose bases are all oligo 1's (the cell and the predecessor
 // are complementary ones).
+// PACKED (k_pairs_bound_packed): a.bt holds the coarse terms, and an entry is stored as kPkOff - entry (see kPkOff).
+// NT: the block's threads (the packed instance runs 1,024 over the same SharedRow).
+template <bool PACKED = false, int NT = kRowThreads>
 static __device__ __forceinline__ void build_bound_table(SharedRow &sh, const IntArgs &a, unsigned s1)
 {
     const int32_t *Tg = a.bt->T;
@@ -819,10 +917,10 @@ static __device__ __forceinline__ void build_bound_table(SharedRow &sh, const In
         const int i = threadIdx.x >> 2, m2 = threadIdx.x & 3;
         const int a_c = (int)((s1 >> (2 * i)) & 3u), m1 = i > 0 ? (int)((s1 >> (2 * i - 2)) & 3u) : 0;
         const int y = sh.g[FastTables::kTSc - kRowGBase + (((3 - a_c) * 4 + m2) * 4 + m1)];
-        sh.yts[threadIdx.x] = y >= IntTables::kValid ? kBndYVoid : y;
+        sh.yts[threadIdx.x] = y >= IntTables::kValid ? (PACKED ? kPkYVoid : kBndYVoid) : y;
     }
     __syncthreads();
-    for (int e = threadIdx.x; e < kRowTEntries; e += kRowThreads) {
+    for (int e = threadIdx.x; e < kRowTEntries; e += NT) {
         const int l2 = e / kRowA, rem = e - l2 * kRowA;
         const int n2 = 3 - (rem & 3), ir = rem >> 2, i = ir / kRowR, r = ir - i * kRowR;
         const int ii = i - r, l1 = r - 1;
@@ -848,24 +946,28 @@ static __device__ __forceinline__ void build_bound_table(SharedRow &sh, const In
                 }
             }
         }
-        if (v >= IntTables::kValid) {
+        const bool avail = v < IntTables::kValid;
+        if (!avail) {
             v = kBndZero;
         } else if (!needs_y && r >= 2) {
             // the lane adds yts[i][m2] to every entry of the rows r >= 2: taken out here where the loop has no such term
             const int m2 = l2 == 1 ? n2 : 3 - (int)((s1 >> (2 * ii)) & 3u);
             v -= sh.yts[(i << 2) | m2];
         }
-        sh.T[e] = v - kBndZero;   // "not available" is 0
+        if constexpr (PACKED) sh.T[e] = avail ? kPkOff - v : 0;
+        else sh.T[e] = v - kBndZero;   // "not available" is 0
     }
     if (threadIdx.x < 4) sh.T[kRowTEntries + threadIdx.x] = 0;
 }
 
 // One lock-step DP of the wave: lane = (row, col), all lanes share `row`.
 // twin (BOUND, mirror mode only): the pair stands for (col, row) as well -- what is appended is appended in both orders.
-template <int NS, bool BOUND = false>
+// PACKED (with BOUND): the packed instance's cell loop and units; everything around it is the bound instance's.
+template <int NS, bool BOUND = false, bool PACKED = false>
 static __device__ __forceinline__ void wave_pairs_row(SharedRow &sh, const IntArgs &a, int row, int col, uint64_t pa,
                                                uint64_t pb, bool inside, bool twin = false)
 {
+    static_assert(BOUND || !PACKED, "the packed instance is a bound instance");
     const int lane = threadIdx.x & 63;
     SeqPair q;
     unsigned rowmask;
@@ -942,12 +1044,15 @@ static __device__ __forceinline__ void wave_pairs_row(SharedRow &sh, const IntAr
     if constexpr (BOUND) {
         if (__ballot(active) != 0ull) {   // wave-uniform
             const unsigned wmax4 = (unsigned)w4[0] | ((unsigned)w4[1] << 8) | ((unsigned)w4[2] << 16) | ((unsigned)w4[3] << 24);
-            const int pick = run_pair_bound<NS>(sh, q, active, wmax4);
-            const int lb = pick + a.bt->init;   // a lane without a chain keeps kBndInit: above every cut
+            int pick;
+            if constexpr (PACKED) pick = run_pair_packed<NS>(sh, q, active, wmax4, __builtin_amdgcn_readfirstlane(a.packed_bias));
+            else pick = run_pair_bound<NS>(sh, q, active, wmax4);
+            const int lb = pick + a.bt->init;   // a lane without a chain keeps kBndInit (kPkInit): above every cut
             if (a.bound_plane) {
                 if (active)
                     a.bound_plane[(size_t)(row - a.f.sinks.row0) * (size_t)a.f.sinks.ncols + (size_t)(col - a.f.sinks.col0)] =
-                        pick >= kBndInit ? INFINITY : (double)lb / BoundTables::kUnitInv;
+                        pick >= (PACKED ? kPkInit : kBndInit) ? INFINITY
+                        : PACKED ? (double)lb * a.packed_unit : (double)lb / BoundTables::kUnitInv;
             } else {
                 const bool survivor = active & (lb <= a.bt->cut);   // a culled pair is finished: no bit, no count
                 const unsigned long long sm = __ballot(survivor);
@@ -1113,13 +1218,16 @@ static __device__ __forceinline__ void build_row_table(SharedRow &sh, const IntA
     }
 }
 
-template <int NS, bool BOUND = false>
+// NT: the block's threads.  The packed bound instance (PACKED) runs 1,024 over the SAME SharedRow, whose per-thread
+// arrays are sized for kRowThreads: like every bound instance it touches g, yts, T, next_group and item only.
+template <int NS, bool BOUND = false, bool PACKED = false, int NT = kRowThreads>
 static __device__ __forceinline__ void kernel_body(const IntArgs &a)
 {
+    static_assert(NT == kRowThreads || PACKED, "the exact instances index SharedRow's per-thread arrays");
     __shared__ SharedRow sh;   // (the bound instance uses g, yts and T of it: the SAME allocation, so that what
                                //  pairs_row_lds_reads_zero() probed holds for its table reads as well)
     if constexpr (BOUND) {
-        for (int e = threadIdx.x; e < kRowGCount; e += kRowThreads) sh.g[e] = a.bt->g[kRowGBase + e];
+        for (int e = threadIdx.x; e < kRowGCount; e += NT) sh.g[e] = a.bt->g[kRowGBase + e];
     } else {
         for (int e = threadIdx.x; e < kRowGCount; e += kRowThreads) {
             sh.h[e] = a.f.ft->H[kRowGBase + e] / 10;   // finite entries are multiples of 10 (build_int_tables); "not available" stays huge
@@ -1168,7 +1276,7 @@ static __device__ __forceinline__ void kernel_body(const IntArgs &a)
         }
         if (row_q != built_row) {
             const unsigned lenmask = (1u << (2 * a.f.k)) - 1u;
-            if constexpr (BOUND) build_bound_table(sh, a, (unsigned)pa & lenmask);
+            if constexpr (BOUND) build_bound_table<PACKED, NT>(sh, a, (unsigned)pa & lenmask);
             else build_row_table(sh, a, (unsigned)pa & lenmask);
             built_row = row_q;
         }
@@ -1184,7 +1292,7 @@ static __device__ __forceinline__ void kernel_body(const IntArgs &a)
             const bool inside = cq < a.f.col1 && !(mirror && cq < row_q);   // (the row's own group: the lanes left of the diagonal)
             const uint64_t pb = a.f.cols_sorted[inside ? cq : a.f.col0];
             const int col = (int)a.f.perm[inside ? cq : a.f.col0];
-            wave_pairs_row<NS, BOUND>(sh, a, row, col, pa, pb, inside, mirror && cq != row_q);
+            wave_pairs_row<NS, BOUND, PACKED>(sh, a, row, col, pa, pb, inside, mirror && cq != row_q);
         }
         __syncthreads();   // every wave is done with the table (and with sh.item) before the next item
     }
@@ -1210,6 +1318,15 @@ template <class RK>
 __global__ void __launch_bounds__(RK::kRowThreads) k_pairs_bound(IntArgs a)
 {
     RK::template kernel_body<RK::kRowSlots, true>(a);
+}
+
+// The packed bound instance: one register per slot (the value in the slot word's 15-bit field, coarse units), so that
+// 1,024 threads -- four waves per SIMD -- fit the register file.
+constexpr int kPackedThreads = 1024;   // (the 768-thread form of the same kernel measured no faster than k_pairs_bound: DESIGN 4.0)
+template <class RK, int NT>
+__global__ void __launch_bounds__(NT) k_pairs_bound_packed(IntArgs a)
+{
+    RK::template kernel_body<RK::kRowSlots, true, true, NT>(a);
 }
 
 }  // namespace
@@ -1277,6 +1394,10 @@ hipError_t pairs_row_lds_reads_zero(hipStream_t stream, int n_cu, bool *ok)
         // ... and so must the bound instance's, which reads its table the same way
         hipFuncAttributes fb;
         if (hipFuncGetAttributes(&fb, (const void *)k_pairs_bound<Row13>) != hipSuccess || fb.sharedSizeBytes != fp.sharedSizeBytes)
+            return hipSuccess;
+        // ... and the packed bound instance's (another block size over the same allocation)
+        if (hipFuncGetAttributes(&fb, (const void *)k_pairs_bound_packed<Row13, kPackedThreads>) != hipSuccess ||
+            fb.sharedSizeBytes != fp.sharedSizeBytes)
             return hipSuccess;
         if (offsetof(Row13::SharedRow, T) + (size_t)Row13::kRowWrapMin < (fa.sharedSizeBytes + 1279) / 1280 * 1280) return hipSuccess;
     }
@@ -1362,9 +1483,13 @@ int pairs_bound_max_k() { return Row13::kRowK; }
 // the bound of every pair of the block (cal/mol; +inf: no chain; -inf: not bounded here) and nothing else.
 hipError_t launch_pairs_bound(const PairKernelArgs &a, const IntTables *it, const BoundTables *bt,
                               unsigned long long *survivors, double *bound_plane, int n_cu, hipStream_t stream, bool mirror,
-                              uint2 *ulist, uint32_t *ucount)
+                              uint2 *ulist, uint32_t *ucount, const BoundTables *packed_q, int packed_bias, int packed_shift)
 {
     if (a.k > Row13::kRowK || a.k < 2 || !bt || (!survivors && !bound_plane) || (ulist && !ucount)) return hipErrorInvalidValue;
+    // packed_q: BoundPacked::q on the device -- the packed instance runs (same contract, coarse units)
+    if (packed_q && (packed_shift < BoundPacked::kShiftMin || packed_shift > BoundPacked::kShiftMax || packed_bias < 0 ||
+                     packed_bias >= BoundPacked::kReach))
+        return hipErrorInvalidValue;
     // mirror: rows are sorted positions and a row's columns start at itself, so the rows must lie inside the columns
     if (mirror && (bound_plane || a.col0 != 0 || a.row0 < 0 || a.row1 > a.col1)) return hipErrorInvalidValue;
     IntArgs x;
@@ -1400,6 +1525,13 @@ hipError_t launch_pairs_bound(const PairKernelArgs &a, const IntTables *it, cons
     if (items <= 0) return hipSuccess;
     if (hipError_t e = hipMemsetAsync(a.work_counter, 0, sizeof(unsigned), stream); e != hipSuccess) return e;
     const int grid = (int)(items < (long)n_cu ? items : (long)n_cu);
+    if (packed_q) {
+        x.bt = packed_q;
+        x.packed_bias = packed_bias;
+        x.packed_unit = (double)(1 << (packed_shift - BoundPacked::kShiftMin));
+        hipLaunchKernelGGL((k_pairs_bound_packed<Row13, kPackedThreads>), dim3(grid), dim3(kPackedThreads), 0, stream, x);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL((k_pairs_bound<Row13>), dim3(grid), dim3(Row13::kRowThreads), 0, stream, x);
     return hipGetLastError();
 }

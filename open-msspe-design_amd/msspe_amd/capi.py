@@ -16,7 +16,7 @@ EXPORTS = [
     "msspe_last_error", "msspe_version", "msspe_set_option", "msspe_get_info", "msspe_kmer_trace", "msspe_set_stream", "msspe_reset_stream",
     "msspe_synchronize",
     "msspe_pack_oligos", "msspe_unpack_oligo", "msspe_cross_dimer_dev", "msspe_cross_dimer",
-    "msspe_cross_dimer_edges_dev", "msspe_cross_dimer_edges", "msspe_cross_dimer_bound_dev", "msspe_cross_dimer_bound_list_dev", "msspe_host_bound_tables", "msspe_host_bound_mirror_ok",
+    "msspe_cross_dimer_edges_dev", "msspe_cross_dimer_edges", "msspe_cross_dimer_bound_dev", "msspe_cross_dimer_bound_list_dev", "msspe_cross_dimer_bound_packed_dev", "msspe_host_bound_tables", "msspe_host_bound_packed", "msspe_host_bound_mirror_ok",
     "msspe_cross_dimer_ab_dev", "msspe_cross_dimer_ab_edges_dev", "msspe_cross_dimer_ab", "msspe_cross_dimer_ab_edges",
     "msspe_cross_dimer_edges_mixed",
     "msspe_cross_dimer_end_dev", "msspe_cross_dimer_end", "msspe_cross_dimer_end_edges_dev", "msspe_cross_dimer_end_edges",
@@ -192,6 +192,8 @@ def load_library() -> C.CDLL:
     L.msspe_cross_dimer_bound_dev.argtypes = [vp, u64p, C.c_int, C.c_int, C.POINTER(Chem), C.c_float,
                                               C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.msspe_cross_dimer_bound_list_dev.argtypes = L.msspe_cross_dimer_bound_dev.argtypes
+    L.msspe_cross_dimer_bound_packed_dev.argtypes = L.msspe_cross_dimer_bound_dev.argtypes
+    L.msspe_host_bound_packed.argtypes = [C.c_char_p, C.POINTER(Chem), C.c_float, vp, vp, C.POINTER(C.c_int32)]
     L.msspe_host_bound_tables.argtypes = [C.c_char_p, C.POINTER(Chem), C.c_float, vp, vp, C.POINTER(C.c_int32)]
     L.msspe_host_bound_mirror_ok.argtypes = [C.c_char_p, C.POINTER(Chem), C.c_float, C.POINTER(C.c_int32)]
     L.msspe_cross_dimer_ab_dev.argtypes = [vp, u64p, C.c_int, C.c_int, u64p, C.c_int, C.c_int, C.POINTER(Chem),
@@ -430,6 +432,22 @@ def host_bound_tables(params_path: str | None = None, chem: Chem | None = None, 
     return {"g": g, "T": T, **dict(zip(keys, list(info)))}
 
 
+def host_bound_packed(params_path: str | None = None, chem: Chem | None = None, threshold: float = -9000.0) -> dict:
+    """The packed bound instance's tables (option pair_bound_packed; no device needed): msspe_host_bound_packed.
+    g / T: host_bound_tables' entries floored to units of 2**(shift - 6) cal/mol, void entries as they are; a cell
+    value + bias is the slot word's field, [lo, hi] the proven range of the values.  usable = 0: all else 0."""
+    g = np.zeros(2604, dtype=np.int32)
+    T = np.zeros(239 * 64, dtype=np.int32)
+    info = (C.c_int32 * 8)()
+    chem = chem or Chem.ntthal()
+    rc = load_library().msspe_host_bound_packed(str(params_path).encode() if params_path else None, C.byref(chem),
+                                                C.c_float(threshold), g.ctypes.data, T.ctypes.data, info)
+    if rc:
+        raise MsspeError(rc, f"msspe_host_bound_packed({params_path})")
+    keys = ("usable", "shift", "bias", "lo", "hi", "init", "cut", "field_max")
+    return {"g": g, "T": T, **dict(zip(keys, list(info)))}
+
+
 def host_bound_mirror_ok(params_path: str | None = None, chem: Chem | None = None, threshold: float = -9000.0) -> bool:
     """May the bound first stage fill each unordered pair of a square screen once under these tables (option
     pair_mirror; no device needed)?  msspe_host_bound_mirror_ok."""
@@ -602,6 +620,14 @@ class Engine:
         """Diagnostic (tests, debugging): the bound first stage's value of every pair of the block, float64 cal/mol
         into the caller's plane (+inf: no chain; -inf: not bounded there); asynchronous.  msspe_cross_dimer_bound_dev."""
         self._check(self.L.msspe_cross_dimer_bound_dev(
+            self.ptr, C.c_void_p(d_pool), n, k, C.byref(chem), C.c_float(threshold), rows[0], rows[1], cols[0],
+            cols[1], C.c_void_p(d_bound)))
+
+    def cross_dimer_bound_packed_dev(self, d_pool: int, n: int, k: int, chem: Chem, threshold: float,
+                                     rows: tuple[int, int], cols: tuple[int, int], d_bound: int):
+        """cross_dimer_bound_dev's plane from the packed instance of the bound first stage (option pair_bound_packed):
+        values are multiples of its unit (host_bound_packed's shift).  msspe_cross_dimer_bound_packed_dev."""
+        self._check(self.L.msspe_cross_dimer_bound_packed_dev(
             self.ptr, C.c_void_p(d_pool), n, k, C.byref(chem), C.c_float(threshold), rows[0], rows[1], cols[0],
             cols[1], C.c_void_p(d_bound)))
 

@@ -1,0 +1,140 @@
+#!/usr/bin/env python3
+"""Generates open-msspe-design_amd/csrc/row_bound_packed_pinned.inc: the predecessor scan of the PACKED bound instance
+of thal_pairs_row.hip's 13-base kernel (k_pairs_bound_packed) as one inline-asm block over a slot table of ONE
+register per slot, in a register map of its own (the whole kernel fits 128 VGPRs, four waves per SIMD):
+
+    v76 .. v127   W[0 .. 51]   slot words  K << 17 | (cell value in coarse units + bias), bits 15 and 16 zero
+    v74           the far accumulator   (chunks that lie entirely in rows i-2 and above)
+    v75           the near accumulator  (the chunk that straddles rows i-2 / i-1 and the chunks of row i-1)
+    everything else: the compiler's
+
+The cell's minuend C keeps 0x7fff in its low 15 bits, so t = C - W never borrows into K: t >> 15 is the table address
+as in the other instances, and the low 16 bits of t are  u = 0x7fff - bias - value  of the predecessor.  The table
+holds  Tn = OFF - entry  (0: not available), so that  u + Tn = const - (entry + value): the candidate, negated and
+shifted, and the running MAXIMUM of it is the minimum over the candidates.  A visit is
+
+    v_sub_u32, v_lshrrev_b32, [ds_read_b32], v_mad_u32_u16 (u * 1 + Tn), half a v_max3_i32
+
+The cell-side term Y of the far chunks is the same for every far entry of a cell: the caller adds it once to the far
+minimum.  The straddling chunk subtracts it per slot (a wave-uniform mask), the chunks of row i-1 leave it out.
+Every chunk's table reads are issued before the chunk in front of it is reduced (far, straddling and near alike), and
+the waits are counted: s_waitcnt lgkmcnt(reads of the newer chunk).  The code is laid out so that a far chunk with
+another chunk behind it -- nearly every chunk of a scan -- runs in a straight line: two tests, no branch taken.  With
+the kinds dispatched by taken branches at every chunk the same kernel ran 9 % slower.
+usage: tools/gen_row_bound_packed_asm.py > open-msspe-design_amd/csrc/row_bound_packed_pinned.inc
+"""
+KC = 4   # slots per chunk (6 and 8 measured slower: DESIGN 4.0)
+NS, W0, ACCF, ACCN = 52, 76, 74, 75
+TUPLES = [(76, 32), (108, 16), (124, 4)]
+SIZES = [KC] * (NS // KC) + ([NS % KC] if NS % KC else [])
+START = [sum(SIZES[:pc]) for pc in range(len(SIZES))]
+
+
+def scan_asm():
+    L = []
+    a = lambda s: L.append(s)
+    # operands: %[C] %[Y] v; %[NFAR] %[NRUN] %[NEAR] s; outputs v74, v75 (fixed);
+    # temps, two sets of chunks in flight: %[a0..] / %[t0..] v hold t = C - W, then the candidate; %[v0..] v (2 KC) the
+    # table address, then the loaded entry; %[yt] v;
+    # immediate %[TOFF]
+    nch = len(SIZES)
+    SETS = ([f"%[a{e}]" for e in range(KC)], [f"%[t{e}]" for e in range(KC)])
+    W = lambda pc, e: W0 + START[pc] + e
+
+    def chunk_issue(pc):
+        # t = C - W stays in regs[e] (its low 16 bits are the candidate's u); the address goes to the loaded value's
+        # register, which the read overwrites
+        t, n = SETS[pc & 1], SIZES[pc]
+        v = [f"%[v{(pc & 1) * KC + e}]" for e in range(n)]
+        for e in range(n):
+            a(f"v_sub_u32 {t[e]}, %[C], v{W(pc, e)}")
+        for e in range(n):
+            a(f"v_lshrrev_b32 {v[e]}, 15, {t[e]}")
+        for e in range(n):
+            a(f"ds_read_b32 {v[e]}, {v[e]} offset:%c[TOFF]")
+
+    def reduce(acc, regs, n):
+        for e in range(0, n - 1, 2):
+            a(f"v_max3_i32 v{acc}, v{acc}, {regs[e]}, {regs[e + 1]}")
+        if n & 1:
+            a(f"v_max_i32 v{acc}, v{acc}, {regs[n - 1]}")
+
+    def process(pc, kind):
+        t, n = SETS[pc & 1], SIZES[pc]
+        v = [f"%[v{(pc & 1) * KC + e}]" for e in range(n)]
+        for e in range(n):
+            a(f"v_mad_u32_u16 {t[e]}, {t[e]}, 1, {v[e]}")
+        if kind == "straddle":
+            for e in range(n):
+                a(f"s_cmp_gt_i32 %[NEAR], {START[pc] + e}")
+                a("s_cselect_b64 vcc, -1, 0")
+                a("v_cndmask_b32_e32 %[yt], 0, %[Y], vcc")
+                a(f"v_sub_u32 {t[e]}, {t[e]}, %[yt]")
+        reduce(ACCF if kind == "far" else ACCN, t, n)
+
+    def dispatch(pc, tag, then):
+        # this chunk by its kind: far (rows i-2 and above), straddling, or row i-1 alone; `then`: where to go on
+        a(f"s_cmp_gt_i32 %[NFAR], {pc}")
+        a(f"s_cbranch_scc0 L{tag}s{pc}_%=")
+        process(pc, "far")
+        a(f"s_branch {then}")
+        a(f"L{tag}s{pc}_%=:")
+        near_only(pc, tag, then)
+
+    def near_only(pc, tag, then):
+        a(f"s_cmp_gt_i32 %[NEAR], {START[pc]}")
+        a(f"s_cbranch_scc0 L{tag}n{pc}_%=")
+        process(pc, "straddle")
+        a(f"s_branch {then}")
+        a(f"L{tag}n{pc}_%=:")
+        process(pc, "near")
+        a(f"s_branch {then}")
+
+    a(f"v_mov_b32 v{ACCF}, 0")
+    a(f"v_mov_b32 v{ACCN}, 0")
+    a("s_cmp_gt_i32 %[NRUN], 0")
+    a("s_cbranch_scc0 Ldone%=")
+    chunk_issue(0)
+    # ---- the straight line: a far chunk with another chunk behind it.  The next chunk's reads are issued first, the
+    #      wait is for this chunk's alone, and no branch is taken
+    for pc in range(nch - 1):
+        a(f"Lc{pc}_%=:")
+        a(f"s_cmp_gt_i32 %[NRUN], {pc + 1}")
+        a(f"s_cbranch_scc0 Lx{pc}_%=")
+        chunk_issue(pc + 1)
+        a(f"s_waitcnt lgkmcnt({SIZES[pc + 1]})")
+        a(f"s_cmp_gt_i32 %[NFAR], {pc}")
+        a(f"s_cbranch_scc0 Ly{pc}_%=")
+        process(pc, "far")
+    a(f"Lc{nch - 1}_%=:")
+    a(f"Lx{nch - 1}_%=:")
+    a("s_waitcnt lgkmcnt(0)")
+    dispatch(nch - 1, "x", "Ldone%=")
+    # ---- off the line: a straddling or near chunk with another behind it (its reads are in flight already) ...
+    for pc in range(nch - 1):
+        a(f"Ly{pc}_%=:")
+        near_only(pc, "y", f"Lc{pc + 1}_%=")
+    # ---- ... and the last chunk that runs, of whatever kind
+    for pc in range(nch - 1):
+        a(f"Lx{pc}_%=:")
+        a("s_waitcnt lgkmcnt(0)")
+        dispatch(pc, "x", "Ldone%=")
+    a("Ldone%=:")
+    return L
+
+
+print("// GENERATED by tools/gen_row_bound_packed_asm.py -- do not edit (see that file for the why and the register map)")
+print(f"#define MSSPE_BPK13_KC {KC}")
+print(f"#define MSSPE_BPK13_W0 {W0}")
+print("#define MSSPE_BPK13_SCAN_ASM \\")
+print(" \\\n".join('    "' + l + '\\n\\t"' for l in scan_asm()))
+print('#define MSSPE_BPK13_SCAN_CLOBBERS "vcc", "scc", "memory"')
+temps = [f"a{e}" for e in range(KC)] + [f"t{e}" for e in range(KC)] + [f"v{e}" for e in range(2 * KC)] + ["yt"]
+print("#define MSSPE_BPK13_TEMP_NAMES " + ", ".join(temps))
+print("#define MSSPE_BPK13_TEMPS_OUT " + ", ".join(f'[{t}] "=&v"({t})' for t in temps))
+print(f'#define MSSPE_BPK13_ACC_OUT(far, near) "=&{{v{ACCF}}}"(far), "=&{{v{ACCN}}}"(near)')
+names = ["Wa", "Wb", "Wc"]
+print("#define MSSPE_BPK13_TUPLES_IN(" + ", ".join(names) + ") " +
+      ", ".join('"{v[%d:%d]}"(%s)' % (r0, r0 + ln - 1, nm) for (r0, ln), nm in zip(TUPLES, names)))
+print("#define MSSPE_BPK13_TUPLES_INOUT(" + ", ".join(names) + ") " +
+      ", ".join('"+{v[%d:%d]}"(%s)' % (r0, r0 + ln - 1, nm) for (r0, ln), nm in zip(TUPLES, names)))
