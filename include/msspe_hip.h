@@ -1163,6 +1163,92 @@ int msspe_panel_thin_thal_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, i
                                      int *n_picked_out, uint8_t *covered_out, long long *covered_all_out,
                                      long long *covered_kept_out);
 
+/* ---- a conflict-free panel selected by coverage: set cover under conflicts (engine extension, no reference
+ * counterpart) ----
+ * msspe_conflict_cover* deletes primers by conflict degree and never looks at coverage: it deletes the only primer that
+ * primes a segment as readily as one of five that prime the same segment, and msspe_panel_thin* cannot bring the
+ * segment back.  These calls join the two steps: a greedy set cover in which a pick bars its conflict neighbours --
+ * with more than one tube, from its own tube only.
+ *   Inputs.  The inputs of msspe_panel_thin* are kept: alignment, msspe_kmer_opt, forward and reverse primer words,
+ *     optional forced flags, min_gain >= 1.  The incidence rule is given as a msspe_seed_rule: mode 0 is the string
+ *     rule I of msspe_panel_thin*; modes 1 and 2 are the held incidence H of msspe_panel_thin_thal*; a threshold <= 0
+ *     gives mode 0's matrix.  New inputs: max_tubes = T, 1..64; drop_self_pairs; and a conflict bitmap B over the
+ *     index p.  p runs over the forward primers in the caller's order, then the reverse primers, n = n_fwd + n_rev.  B
+ *     is n x ceil(n/64) words in the layout msspe_cross_dimer_dev writes for the pool "forward words then reverse
+ *     words".  Reverse words are in primer orientation, as the CSV writes them.
+ *   Graph.  This is the cover's graph.  S = B | B^T, padding bits ignored.  With drop_self_pairs the diagonal and the
+ *     reverse-complement partners are cleared first.  The words must be distinct across both lists, exactly as
+ *     msspe_conflict_cover* checks; duplicate words and bits above 2 k are MSSPE_ERR_ARG.  p is SELF-CONFLICTING when
+ *     S[p][p] is still set.
+ *   State.  covered starts as the OR of the forced rows.  mask[p] is a 64-bit set of tubes barred to p.  Every
+ *     neighbour of a forced primer starts with all T bits set, because the panel is in every tube.  Everyone else
+ *     starts at 0.  p is LIVE when it is not forced, not picked, not self-conflicting, and mask[p] lacks at least one
+ *     of the low T bits.
+ *   Rounds.  Each round computes gain(p) = |row(p) & ~covered| over the live p.
+ *     1. The round takes the greatest gain.  Ties go to the LOWEST index.
+ *     2. If that gain is below min_gain, or nobody is live, the loop ends.
+ *     3. Otherwise p is appended to the order with its gain, and tube(p) = the lowest tube not in mask[p].
+ *     4. covered |= row(p).
+ *     5. mask[u] |= 1 << tube(p) for every u != p with S[p][u] set.
+ *   Outputs.  keep_out[n]: forced or picked.  order_out, gain_out (the caller sizes both to n), *n_picked_out.
+ *     tube_out[n]: the tube of a pick; MSSPE_TUBE_NONE for everyone else, forced primers included.  barred_out[n]
+ *     (optional): 1 for a primer not kept that is self-conflicting or whose low T mask bits are all set at the end.
+ *     covered_out (optional, n_seq * P bytes), *covered_all_out (optional: the whole set's coverage, conflicts
+ *     ignored), *covered_kept_out (optional).  *n_tubes_used_out (optional).
+ * GUARANTEES.  No two picks of one tube are neighbours in S, and no pick is a neighbour of a forced primer.  The tubes
+ * in use are 0 .. used - 1, without gaps.  With an all-zero bitmap and any T, the order, gains, keep, covered and both
+ * counts are msspe_panel_thin*'s (mode 0) or msspe_panel_thin_thal*'s (modes 1 and 2), and every pick is in tube 0.  On
+ * a complete graph without self loops, the picks are the first min(T, picks) picks of the plain thinning, in tubes 0,
+ * 1, 2, ....  What the rule does NOT promise: that covered_kept == covered_all (conflicts may cost segments), or a
+ * maximum.  It is greedy.
+ * Limits: n <= 262,144 (MSSPE_ERR_ARG above it), "panel_thin_matrix_max_mb" (MSSPE_ERR_CAPACITY, never a partial run),
+ * k in 2..31 (MSSPE_ERR_K).  Errors: those of msspe_panel_thin* / msspe_panel_thin_thal* and of msspe_conflict_tubes*;
+ * max_tubes outside 1..64, a NULL rule, sel, bitmap or output array (keep_out, order_out, gain_out, n_picked_out,
+ * tube_out), a mode outside 0..2 and a NULL rule->chem in modes 1 and 2 are MSSPE_ERR_ARG.  n == 0 or no segments:
+ * MSSPE_OK with nothing picked and keep_out = the forced flags.
+ * msspe_get_info, the last call: "panel_select_rounds" (the picks and the round that stopped), "panel_select_tubes",
+ * "panel_select_barred", "panel_select_prepare_us" (ranks, duplicate check and S), "panel_select_incidence_us",
+ * "panel_select_first_us" (forced rows, first barring, first gains) and "panel_select_rounds_us".
+ *
+ * The _dev forms read the alignment from the device (bytes / packed rows, as msspe_panel_thin_dev / _packed_dev) and
+ * d_bitmap (device, read only); every other argument is on the host.  They share the cover's S, the thinning's matrix
+ * and, in modes 1 and 2, the work list with the other calls of the context, and allocate nothing once their buffers
+ * have grown to a call's size.  msspe_panel_select takes the alignment on the host and screens the pool itself
+ * (msspe_cross_dimer_dev, bitmap only, decisions path, as msspe_conflict_tubes does) with chem and dg_threshold.
+ * msspe_panel_select_bitmap takes the alignment and the n x ceil(n/64) bitmap from the host. */
+typedef struct {
+    int min_gain;          /* >= 1: a pick must cover at least this many segments nothing kept covers yet */
+    int max_tubes;         /* 1..64 */
+    int drop_self_pairs;   /* as msspe_conflict_cover* */
+} msspe_select_opt;
+
+int msspe_panel_select_dev(msspe_ctx *ctx, const uint8_t *d_seqs, int n_seq, size_t seq_len, const msspe_kmer_opt *opt,
+                           const msspe_seed_rule *rule, const msspe_select_opt *sel, const uint64_t *fwd_words,
+                           int n_fwd, const uint64_t *rev_words, int n_rev, const uint8_t *forced,
+                           const uint64_t *d_bitmap, uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out,
+                           int *n_picked_out, uint8_t *tube_out, uint8_t *barred_out, uint8_t *covered_out,
+                           long long *covered_all_out, long long *covered_kept_out, int *n_tubes_used_out);
+int msspe_panel_select_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
+                                  const msspe_kmer_opt *opt, const msspe_seed_rule *rule, const msspe_select_opt *sel,
+                                  const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
+                                  const uint8_t *forced, const uint64_t *d_bitmap, uint8_t *keep_out,
+                                  uint32_t *order_out, uint32_t *gain_out, int *n_picked_out, uint8_t *tube_out,
+                                  uint8_t *barred_out, uint8_t *covered_out, long long *covered_all_out,
+                                  long long *covered_kept_out, int *n_tubes_used_out);
+int msspe_panel_select(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len, const msspe_kmer_opt *opt,
+                       const msspe_seed_rule *rule, const msspe_select_opt *sel, const uint64_t *fwd_words, int n_fwd,
+                       const uint64_t *rev_words, int n_rev, const uint8_t *forced, const msspe_chem *chem,
+                       float dg_threshold, uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out,
+                       int *n_picked_out, uint8_t *tube_out, uint8_t *barred_out, uint8_t *covered_out,
+                       long long *covered_all_out, long long *covered_kept_out, int *n_tubes_used_out);
+int msspe_panel_select_bitmap(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len,
+                              const msspe_kmer_opt *opt, const msspe_seed_rule *rule, const msspe_select_opt *sel,
+                              const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
+                              const uint8_t *forced, const uint64_t *bitmap, uint8_t *keep_out, uint32_t *order_out,
+                              uint32_t *gain_out, int *n_picked_out, uint8_t *tube_out, uint8_t *barred_out,
+                              uint8_t *covered_out, long long *covered_all_out, long long *covered_kept_out,
+                              int *n_tubes_used_out);
+
 /* ---- several devices of one node ----------------------------------------------------------
  *
  * One process, one context and one host thread per device.  What shards is the reference's N^2 pair loop

@@ -33,6 +33,7 @@
 #include "kmer_stage.hpp"
 #include "nn_params.hpp"
 #include "thal_dense.hpp"
+#include "panel_select.hpp"
 #include "panel_thin.hpp"
 #include "panel_thin_thal.hpp"
 #include "screen_plan.hpp"
@@ -158,6 +159,10 @@ struct msspe_ctx {
     PanelThin thin;                    // msspe_panel_thin*: the incidence matrix, covered words, gains and round state
     PanelThinThal thin_thal;           // msspe_panel_thin_thal*: the sorted order, run slots and rocPRIM storage of a slab (its
                                        // matrix and round state are thin's, its work list site_work, its plane words cov_thal's)
+    PanelSelect select;                // msspe_panel_select*: its pool, masks, gains and round state (the graph lives in
+                                       // cover's buffers, the matrix in thin's)
+    hipEvent_t select_ev[2] = {};      // ... around its incidence pass
+    long long select_prepare_us = 0, select_incidence_us = 0;
     CoverageThal cov_thal;             // msspe_segment_coverage_thal*: plane words, per-segment words, cell bitmaps,
                                        // counters, the caller's list (its work list is site_work below)
     // msspe_background_thal*: the work list (site records, their pairs, raw dG and t), the site pool [primers | site
@@ -877,6 +882,13 @@ int msspe_get_info(msspe_ctx *ctx, const char *key, long long *value_out)
     else if (k == "panel_thin_incidence_us") *value_out = ctx->thin.phase_us()[0];
     else if (k == "panel_thin_gain0_us") *value_out = ctx->thin.phase_us()[1];
     else if (k == "panel_thin_rounds_us") *value_out = ctx->thin.phase_us()[2];
+    else if (k == "panel_select_rounds") *value_out = ctx->select.n_rounds();
+    else if (k == "panel_select_tubes") *value_out = ctx->select.tubes_used();
+    else if (k == "panel_select_barred") *value_out = ctx->select.barred();
+    else if (k == "panel_select_prepare_us") *value_out = ctx->select_prepare_us;
+    else if (k == "panel_select_incidence_us") *value_out = ctx->select_incidence_us;
+    else if (k == "panel_select_rounds_us") *value_out = ctx->select.phase_us()[1];
+    else if (k == "panel_select_first_us") *value_out = ctx->select.phase_us()[0];
     else if (k == "thin_thal_unique") *value_out = ctx->opt.thin_thal_unique ? 1 : 0;
     else if (k == "panel_thin_thal_matches") *value_out = ctx->thin_thal.matches;
     else if (k == "panel_thin_thal_unique_pairs") *value_out = ctx->thin_thal.unique_pairs;
@@ -962,6 +974,11 @@ void msspe_destroy(msspe_ctx *ctx)
         ctx->tubes.release();
         ctx->thin.release();
         ctx->thin_thal.release();
+        ctx->select.release();
+        for (auto &e : ctx->select_ev) {
+            if (e) (void)hipEventDestroy(e);
+            e = nullptr;
+        }
         for (auto &e : ctx->tolerant.ev) {
             if (e) (void)hipEventDestroy(e);
             e = nullptr;
@@ -3413,6 +3430,112 @@ int panel_thin_thal_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t 
     return MSSPE_OK;
 }
 
+// msspe_panel_select*: the cover's graph over the pool "forward words then reverse words" (CoverStage::begin /
+// prepare: one S in the context, whoever built it last), the thinning's matrix filled by the rule's mode (mode 0 as
+// msspe_panel_thin*, modes 1 and 2 as msspe_panel_thin_thal*; a threshold <= 0 is mode 0), then PanelSelect::rounds.
+int panel_select_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t seq_len, const msspe_kmer_opt *opt,
+                      const msspe_seed_rule *rule, const msspe_select_opt *sel, const uint64_t *fwd_words, int n_fwd,
+                      const uint64_t *rev_words, int n_rev, const uint8_t *forced, const uint64_t *d_bitmap,
+                      uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out, int *n_picked_out, uint8_t *tube_out,
+                      uint8_t *barred_out, uint8_t *covered_out, long long *covered_all_out,
+                      long long *covered_kept_out, int *n_tubes_used_out)
+{
+    if (!opt || !rule || !sel || !keep_out || !order_out || !gain_out || !n_picked_out || !tube_out || n_fwd < 0 ||
+        n_rev < 0 || (n_fwd && !fwd_words) || (n_rev && !rev_words))
+        return fail(ctx, MSSPE_ERR_ARG, "panel select: null argument");
+    if (sel->min_gain < 1) return fail(ctx, MSSPE_ERR_ARG, "panel select: min_gain must be at least 1");
+    if (sel->max_tubes < 1 || sel->max_tubes > kTubeMax)
+        return fail(ctx, MSSPE_ERR_ARG, "panel select: max_tubes must be 1..64");
+    if (rule->mode < 0 || rule->mode > 2)
+        return fail(ctx, MSSPE_ERR_ARG, "panel select: mode must be 0, 1 (ANY) or 2 (END1)");
+    if (rule->mode && !rule->chem) return fail(ctx, MSSPE_ERR_ARG, "panel select: modes 1 and 2 need a chemistry");
+    ctx->select.reset_stats();
+    ctx->select_prepare_us = ctx->select_incidence_us = 0;
+    *n_picked_out = 0;
+    if (covered_all_out) *covered_all_out = 0;
+    if (covered_kept_out) *covered_kept_out = 0;
+    if (n_tubes_used_out) *n_tubes_used_out = 0;
+    const int k = opt->kmer_size;
+    if (k < 2 || k > 31) return fail(ctx, MSSPE_ERR_K, "panel select: unsupported k (need 2 <= k <= 31)");
+    if ((long)n_fwd + (long)n_rev > (long)kCoverMaxN)
+        return fail(ctx, MSSPE_ERR_ARG, "panel select: " + std::to_string((long)n_fwd + n_rev) + " primers, at most " +
+                                            std::to_string(kCoverMaxN) + " (the symmetrised bitmap is n^2 / 8 bytes)");
+    const int mode = rule->tm_threshold > 0.0f ? rule->mode : 0;   // a threshold <= 0: H is I
+    const msspe_mismatch_opt mm = {rule->max_mismatches, rule->exact_3p};
+    std::string err;
+    long P = 0;
+    int rc = MismatchCoverage::check(n_seq, seq_len, *opt, mm.max_mismatches, mm.exact_3p, fwd_words, n_fwd, rev_words,
+                                     n_rev, &P, err);
+    if (rc) return fail(ctx, rc, err);
+    if (mode && opt->search_window_size - k >= (1 << kCovOffBits))   // a match's offset travels in kCovOffBits bits
+        return fail(ctx, MSSPE_ERR_ARG, "panel select: the search window has more than 2^26 positions");
+    const int n = n_fwd + n_rev;
+    const long n_seg = P * n_seq;
+    for (int p = 0; p < n; ++p) {
+        keep_out[p] = forced && forced[p] ? 1 : 0;
+        tube_out[p] = MSSPE_TUBE_NONE;
+        if (barred_out) barred_out[p] = 0;
+    }
+    if (covered_out) std::fill(covered_out, covered_out + n_seg, (uint8_t)0);
+    if (n == 0 || n_seg == 0) return MSSPE_OK;
+    if (!d_bitmap) return fail(ctx, MSSPE_ERR_ARG, "panel select: null bitmap");
+    const size_t cap = (size_t)1 << ctx->opt.site_list_cap_log2;
+    if (mode && (uint64_t)n + cap >= (1ull << 31)) return fail(ctx, MSSPE_ERR_ARG, "panel select: too many primers");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    for (auto &e : ctx->select_ev)
+        if (!e) HIP_TRY(ctx, hipEventCreate(&e));
+    const int S = MismatchCoverage::group_size(*opt);
+    uint64_t *d_inc = nullptr;
+    if ((rc = ctx->thin.matrix(n, n_seg, S, (size_t)ctx->opt.panel_thin_matrix_max_mb << 20, &d_inc, err)))
+        return fail(ctx, rc, err);
+
+    // the graph: S = B | B^T over the pool in the bitmap's order
+    const uint64_t *d_pool = nullptr;
+    if ((rc = ctx->select.begin(n, n_seg, S, fwd_words, n_fwd, rev_words, n_rev, &d_pool, ctx->stream, err)) ||
+        (rc = ctx->cover.begin(n, k, ctx->stream, err)) ||
+        (rc = ctx->cover.prepare(d_pool, n, k, d_bitmap, sel->drop_self_pairs != 0, ctx->stream, err)))
+        return fail(ctx, rc, err);
+
+    // the incidence
+    HIP_TRY(ctx, hipEventRecord(ctx->select_ev[0], ctx->stream));
+    bool scored = false;
+    if (!mode) {
+        if ((rc = ctx->mm_cov.incidence(view, n_seq, seq_len, *opt, mm.max_mismatches, mm.exact_3p, fwd_words, n_fwd,
+                                        rev_words, n_rev, d_inc, ctx->stream, err)))
+            return fail(ctx, rc, err);
+    } else {
+        auto &tt = ctx->thin_thal;
+        tt.matches = tt.unique_pairs = tt.slabs = tt.redone = 0;
+        tt.list_us = tt.unique_us = tt.score_us = tt.fold_us = 0;
+        const bool end1 = mode == 2;
+        ChemEntry *ce = nullptr;
+        if ((rc = chem_entry(ctx, *rule->chem, rule->tm_threshold, &ce, end1 ? kCutEndT : kCutAnyT))) return rc;
+        if ((rc = ensure_workspace(ctx, (size_t)k * (size_t)k))) return rc;
+        if ((rc = ensure_overflow(ctx, (long)cap))) return rc;
+        if ((rc = ensure_site_work(ctx, cap, n, 0))) return rc;
+        if ((rc = ctx->cov_thal.prepare_words(*opt, fwd_words, n_fwd, rev_words, n_rev, ctx->stream, err)))
+            return fail(ctx, rc, err);
+        if ((rc = tt.events(err))) return fail(ctx, rc, err);
+        if ((rc = fill_held_matrix(ctx, view, n_seg, P, opt, &mm, ce, end1, fwd_words, n_fwd, rev_words, n_rev, d_inc,
+                                   scored)))
+            return rc;
+    }
+    HIP_TRY(ctx, hipEventRecord(ctx->select_ev[1], ctx->stream));
+
+    if ((rc = ctx->select.rounds(d_inc, ctx->cover.symmetrised(), n, n_seg, S, sel->min_gain, sel->max_tubes, keep_out,
+                                 order_out, gain_out, n_picked_out, tube_out, barred_out, covered_out, covered_all_out,
+                                 covered_kept_out, n_tubes_used_out, ctx->n_cu, ctx->stream, err)))
+        return fail(ctx, rc, err);
+    thin_thal_read_scored(ctx, scored);   // rounds returned with the stream idle
+    long long keys_us = 0, sym_us = 0;
+    ctx->cover.prepare_us(keys_us, sym_us);
+    ctx->select_prepare_us = keys_us + sym_us;
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, ctx->select_ev[0], ctx->select_ev[1]) == hipSuccess)
+        ctx->select_incidence_us = (long long)(ms * 1000.0f);
+    return MSSPE_OK;
+}
+
 // ---- msspe_kmer_candidates_tolerant*: stage A seeded on what the panel covers --------------------------------------
 
 // One direction of a tolerant call: its distinct seed words (msspe_pack_oligos form) and its two state outputs.
@@ -3758,6 +3881,129 @@ int msspe_panel_thin_thal(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t
                                    n_picked_out, covered_out, covered_all_out, covered_kept_out);
     (void)msspe_device_free(ctx, d);
     return rc;
+}
+
+int msspe_panel_select_dev(msspe_ctx *ctx, const uint8_t *d_seqs, int n_seq, size_t seq_len, const msspe_kmer_opt *opt,
+                           const msspe_seed_rule *rule, const msspe_select_opt *sel, const uint64_t *fwd_words,
+                           int n_fwd, const uint64_t *rev_words, int n_rev, const uint8_t *forced,
+                           const uint64_t *d_bitmap, uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out,
+                           int *n_picked_out, uint8_t *tube_out, uint8_t *barred_out, uint8_t *covered_out,
+                           long long *covered_all_out, long long *covered_kept_out, int *n_tubes_used_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!d_seqs) return fail(ctx, MSSPE_ERR_ARG, "null sequences");
+    return panel_select_view(ctx, SeqView{d_seqs, nullptr, seq_len}, n_seq, seq_len, opt, rule, sel, fwd_words, n_fwd,
+                             rev_words, n_rev, forced, d_bitmap, keep_out, order_out, gain_out, n_picked_out, tube_out,
+                             barred_out, covered_out, covered_all_out, covered_kept_out, n_tubes_used_out);
+}
+
+int msspe_panel_select_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
+                                  const msspe_kmer_opt *opt, const msspe_seed_rule *rule, const msspe_select_opt *sel,
+                                  const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
+                                  const uint8_t *forced, const uint64_t *d_bitmap, uint8_t *keep_out,
+                                  uint32_t *order_out, uint32_t *gain_out, int *n_picked_out, uint8_t *tube_out,
+                                  uint8_t *barred_out, uint8_t *covered_out, long long *covered_all_out,
+                                  long long *covered_kept_out, int *n_tubes_used_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!d_packed) return fail(ctx, MSSPE_ERR_ARG, "null sequences");
+    return panel_select_view(ctx, SeqView{nullptr, d_packed, seq_len}, n_seq, seq_len, opt, rule, sel, fwd_words, n_fwd,
+                             rev_words, n_rev, forced, d_bitmap, keep_out, order_out, gain_out, n_picked_out, tube_out,
+                             barred_out, covered_out, covered_all_out, covered_kept_out, n_tubes_used_out);
+}
+
+// The two host forms: the alignment and the graph go to the device for the call (chem == NULL: `bitmap` is the graph,
+// from the host; otherwise the pool is screened there), the rest is msspe_panel_select_dev.
+static int panel_select_host(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len, const msspe_kmer_opt *opt,
+                             const msspe_seed_rule *rule, const msspe_select_opt *sel, const uint64_t *fwd_words,
+                             int n_fwd, const uint64_t *rev_words, int n_rev, const uint8_t *forced,
+                             const uint64_t *bitmap, const msspe_chem *chem, float dg_threshold, uint8_t *keep_out,
+                             uint32_t *order_out, uint32_t *gain_out, int *n_picked_out, uint8_t *tube_out,
+                             uint8_t *barred_out, uint8_t *covered_out, long long *covered_all_out,
+                             long long *covered_kept_out, int *n_tubes_used_out)
+{
+    if (!seqs || n_seq < 0) return fail(ctx, MSSPE_ERR_ARG, "null sequences");
+    if (n_fwd < 0 || n_rev < 0 || (n_fwd && !fwd_words) || (n_rev && !rev_words) || !opt || !rule || !sel || !keep_out ||
+        !order_out || !gain_out || !n_picked_out || !tube_out)
+        return fail(ctx, MSSPE_ERR_ARG, "panel select: null argument");
+    if (sel->min_gain < 1) return fail(ctx, MSSPE_ERR_ARG, "panel select: min_gain must be at least 1");
+    if (sel->max_tubes < 1 || sel->max_tubes > kTubeMax)   // before the screen, not after it
+        return fail(ctx, MSSPE_ERR_ARG, "panel select: max_tubes must be 1..64");
+    const long n = (long)n_fwd + (long)n_rev;
+    if (n > (long)kCoverMaxN)
+        return fail(ctx, MSSPE_ERR_ARG, "panel select: " + std::to_string(n) + " primers, at most " +
+                                            std::to_string(kCoverMaxN) + " (the symmetrised bitmap is n^2 / 8 bytes)");
+    const int k = opt->kmer_size;
+    if (k < 2 || k > 31) return fail(ctx, MSSPE_ERR_K, "panel select: unsupported k (need 2 <= k <= 31)");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t words = ((size_t)n + 63) / 64;
+    DevBuf<uint64_t> d_pool, d_bitmap;
+    if (n) {
+        HIP_TRY(ctx, d_bitmap.alloc((size_t)n * words));
+        if (chem) {
+            std::vector<uint64_t> pool(fwd_words, fwd_words + n_fwd);
+            pool.insert(pool.end(), rev_words, rev_words + n_rev);
+            for (uint64_t w : pool)   // the screen reads k bases of a word and nothing above them
+                if (k < 32 && (w >> (2 * k))) return fail(ctx, MSSPE_ERR_ARG, "panel select: a primer word has bits above 2 k");
+            {   // duplicates before the screen, not after it
+                std::vector<uint64_t> s(pool);
+                std::sort(s.begin(), s.end());
+                if (std::adjacent_find(s.begin(), s.end()) != s.end())
+                    return fail(ctx, MSSPE_ERR_ARG, "panel select: the primer lists hold duplicate words");
+            }
+            HIP_TRY(ctx, d_pool.alloc((size_t)n));
+            HIP_TRY(ctx, hipMemcpyAsync(d_pool, pool.data(), sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice,
+                                        ctx->stream));
+            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // pool leaves scope
+            // the screen's decisions only: the bitmap is all the selection reads
+            if (int rc = msspe_cross_dimer_dev(ctx, d_pool, (int)n, k, chem, dg_threshold, 0, (int)n, 0, (int)n, nullptr,
+                                               d_bitmap, nullptr, nullptr))
+                return rc;
+        } else {
+            if (!bitmap) return fail(ctx, MSSPE_ERR_ARG, "panel select: null bitmap");
+            HIP_TRY(ctx, hipMemcpy(d_bitmap, bitmap, sizeof(uint64_t) * (size_t)n * words, hipMemcpyHostToDevice));
+        }
+    }
+    void *d = nullptr;
+    int rc = msspe_device_put(ctx, seqs, (size_t)n_seq * seq_len, &d);
+    if (rc) return rc;
+    rc = msspe_panel_select_dev(ctx, (const uint8_t *)d, n_seq, seq_len, opt, rule, sel, fwd_words, n_fwd, rev_words,
+                                n_rev, forced, d_bitmap, keep_out, order_out, gain_out, n_picked_out, tube_out,
+                                barred_out, covered_out, covered_all_out, covered_kept_out, n_tubes_used_out);
+    if (!rc && chem && n) {
+        const hipError_t e = hipStreamSynchronize(ctx->stream);
+        rc = e != hipSuccess ? hip_fail(ctx, e, "hipStreamSynchronize") : check_list_overrun(ctx);
+    }
+    (void)msspe_device_free(ctx, d);
+    return rc;
+}
+
+int msspe_panel_select(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len, const msspe_kmer_opt *opt,
+                       const msspe_seed_rule *rule, const msspe_select_opt *sel, const uint64_t *fwd_words, int n_fwd,
+                       const uint64_t *rev_words, int n_rev, const uint8_t *forced, const msspe_chem *chem,
+                       float dg_threshold, uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out,
+                       int *n_picked_out, uint8_t *tube_out, uint8_t *barred_out, uint8_t *covered_out,
+                       long long *covered_all_out, long long *covered_kept_out, int *n_tubes_used_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!chem) return fail(ctx, MSSPE_ERR_ARG, "panel select: null chemistry");
+    return panel_select_host(ctx, seqs, n_seq, seq_len, opt, rule, sel, fwd_words, n_fwd, rev_words, n_rev, forced,
+                             nullptr, chem, dg_threshold, keep_out, order_out, gain_out, n_picked_out, tube_out,
+                             barred_out, covered_out, covered_all_out, covered_kept_out, n_tubes_used_out);
+}
+
+int msspe_panel_select_bitmap(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len,
+                              const msspe_kmer_opt *opt, const msspe_seed_rule *rule, const msspe_select_opt *sel,
+                              const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
+                              const uint8_t *forced, const uint64_t *bitmap, uint8_t *keep_out, uint32_t *order_out,
+                              uint32_t *gain_out, int *n_picked_out, uint8_t *tube_out, uint8_t *barred_out,
+                              uint8_t *covered_out, long long *covered_all_out, long long *covered_kept_out,
+                              int *n_tubes_used_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    return panel_select_host(ctx, seqs, n_seq, seq_len, opt, rule, sel, fwd_words, n_fwd, rev_words, n_rev, forced,
+                             bitmap, nullptr, 0.0f, keep_out, order_out, gain_out, n_picked_out, tube_out, barred_out,
+                             covered_out, covered_all_out, covered_kept_out, n_tubes_used_out);
 }
 
 int msspe_background_thal_flank_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, size_t total_len, int k,

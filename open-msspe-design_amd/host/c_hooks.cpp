@@ -65,7 +65,7 @@ int odm_parse_args(int argc, const char *const *argv, char *out, size_t cap)
           << "\ntm_stddev=" << a.tm_stddev << "\ncover_on_device=" << a.cover_on_device << "\ntubes=" << a.tubes
           << "\ncoverage_mismatches=" << a.coverage_mismatches << "\ncoverage_3p_exact=" << a.coverage_3p_exact
           << "\ncoverage_tm=" << a.coverage_tm_text << "\ncoverage_thal=" << a.coverage_thal
-          << "\nthin_panel=" << a.thin_panel << "\nthin_mismatches=" << a.thin_mismatches
+          << "\nselect_by_coverage=" << a.select_by_coverage << "\nthin_panel=" << a.thin_panel << "\nthin_mismatches=" << a.thin_mismatches
           << "\nthin_3p_exact=" << a.thin_3p_exact << "\nthin_min_gain=" << a.thin_min_gain
           << "\nthin_tm=" << a.thin_tm_text << "\nthin_thal=" << a.thin_thal
           << "\nseed_mismatches=" << a.seed_mismatches << "\nseed_3p_exact=" << a.seed_3p_exact
@@ -141,6 +141,47 @@ int odm_thin_panel(const uint64_t *rows, int n, int words, int min_gain, const u
         covered_out[1] = (long long)t.covered_kept;
     }
     return (int)t.order.size();
+}
+
+// rows, forced, order, gains, keep as odm_thin_panel.  bitmap: n rows of ceil(n / 64) words, bit u of row p = the
+// directed conflict p -> u (padding bits ignored); with drop_self the diagonal is not read (the nodes are named by
+// index, so nobody has a reverse-complement partner).  tube[n]: the tube of a pick, -1 otherwise; barred[n];
+// counts_out[0..3]: segments covered by all rows / by the kept ones, tubes in use, rounds.  Returns the number of picks
+// (select_panel, the sequential rule of DESIGN.md 4.13).
+int odm_select_panel(const uint64_t *rows, int n, int words, const uint64_t *bitmap, int max_tubes, int min_gain,
+                     const uint8_t *forced, int drop_self, int *order, int *gains, uint8_t *keep, int *tube,
+                     uint8_t *barred, long long *counts_out)
+{
+    std::vector<std::vector<uint64_t>> r((size_t)n);
+    for (int p = 0; p < n; ++p) r[(size_t)p].assign(rows + (size_t)p * words, rows + (size_t)(p + 1) * words);
+    std::vector<char> f;
+    if (forced) f.assign(forced, forced + n);
+    std::vector<std::string> names((size_t)n);
+    for (int p = 0; p < n; ++p) names[(size_t)p] = std::to_string(p);
+    ConflictGraph g;
+    g.nodes = names;
+    const int W = (n + 63) / 64;
+    for (int p = 0; p < n; ++p)
+        for (int u = 0; u < n; ++u)
+            if ((bitmap[(size_t)p * W + (u >> 6)] >> (u & 63)) & 1ull)
+                if (!(drop_self && p == u)) g.edges[names[(size_t)p]].insert(names[(size_t)u]);
+    const SelectResult s = select_panel(r, names, g, max_tubes, min_gain, f);
+    for (size_t i = 0; i < s.order.size(); ++i) {
+        order[i] = s.order[i];
+        gains[i] = s.gains[i];
+    }
+    for (int p = 0; p < n; ++p) {
+        keep[p] = (uint8_t)s.keep[(size_t)p];
+        tube[p] = s.tube[(size_t)p];
+        barred[p] = (uint8_t)s.barred[(size_t)p];
+    }
+    if (counts_out) {
+        counts_out[0] = (long long)s.covered_all;
+        counts_out[1] = (long long)s.covered_kept;
+        counts_out[2] = s.tubes_used;
+        counts_out[3] = s.rounds;
+    }
+    return (int)s.order.size();
 }
 
 // The block od-msspe-hip --thin-panel true --thin-tm T prints (thin_thal_report), from figures the caller has.  Needs no

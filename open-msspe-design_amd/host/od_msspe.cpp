@@ -85,6 +85,7 @@ const OptSpec kOpts[] = {
     {"--thin-min-gain", "THIN_MIN_GAIN", OptSpec::Int, OFF(thin_min_gain)},
     {"--thin-tm", "THIN_TM", OptSpec::Str, OFF(thin_tm_text)},
     {"--thin-thal", "THIN_THAL", OptSpec::Str, OFF(thin_thal)},
+    {"--select-by-coverage", "SELECT_BY_COVERAGE", OptSpec::Bool, OFF(select_by_coverage)},
     {"--seed-mismatches", "SEED_MISMATCHES", OptSpec::OptInt, OFF(seed_mismatches)},
     {"--seed-3p-exact", "SEED_3P_EXACT", OptSpec::Str, OFF(seed_3p_exact_text)},
     {"--seed-tm", "SEED_TM", OptSpec::Str, OFF(seed_tm_text)},
@@ -151,12 +152,19 @@ std::string Args::usage()
          "count may rise up to M. The primers of --existing-primers are kept. One device; not with --keep-all true.\n"
          "With --thin-tm <C> the cover is of the segments a primer holds at C instead: every match within M / E is scored\n"
          "with thal (--thin-thal any | end1), and no held segment is lost at G = 1; a segment's best t may fall.\n"
+         "--select-by-coverage true replaces the cover (or the tube split) by a selection that looks at coverage: round\n"
+         "after round the primer covering the most segments nothing kept covers yet is kept, and its conflict\n"
+         "neighbours are barred (with --tubes <N>: from its tube only). The match rule is --thin-panel's\n"
+         "(--thin-mismatches, --thin-3p-exact, --thin-min-gain, --thin-tm, --thin-thal); the primers of\n"
+         "--existing-primers are kept and bar their neighbours from every tube. Conflicts may cost segments. One\n"
+         "device; not with --thin-panel true, --keep-all true or --cover-on-device true.\n"
          "--coverage-tm <C> adds a report of the segments the final primers hold at C: every match within\n"
          "--coverage-mismatches (last --coverage-3p-exact bases exact) is scored with thal (--coverage-thal any | end1)\n"
          "against the strand the primer anneals to. One device.\n"
          "--exclude-primers <CSV> names words stage A must never pick (direction and primers columns, as a panel).\n"
          "--rejected-out <CSV> writes every candidate the run dropped (direction,name,primers,round,reason; reason is\n"
-         "stage_b, background, panel_dimer or cover); --exclude-primers reads such a file.\n"
+         "stage_b, background, panel_dimer or cover; with --select-by-coverage true select_conflict or select_unneeded in\n"
+         "place of the last two); --exclude-primers reads such a file.\n"
          "--repick-rounds <N> (0..16) repeats the selection up to N times: what passed is kept as a panel, what was\n"
          "dropped is excluded, and stage A fills the holes. One device; not with --tubes.\n"
          "--seed-mismatches <M> makes a run that extends a panel (--existing-primers, and the later rounds of\n"
@@ -253,10 +261,24 @@ Args Args::parse(int argc, const char *const *argv)
                              std::to_string(a.kmer_size) + "'");
         a.coverage_3p_exact = (int)e;
     }
-    if (a.thin_panel == "true") {
+    if (a.select_by_coverage == "true") {
+        if (a.thin_panel == "true")
+            throw UsageError("error: '--select-by-coverage true' keeps only what the coverage needs and cannot be "
+                             "combined with '--thin-panel true'");
         if (a.keep_all == "true")
-            throw UsageError("error: '--thin-panel true' drops primers and cannot be combined with '--keep-all true'");
+            throw UsageError("error: '--select-by-coverage true' drops primers and cannot be combined with "
+                             "'--keep-all true'");
         if (!a.devices.empty())
+            throw UsageError("error: '--select-by-coverage true' runs on one device and cannot be combined with "
+                             "'--devices'");
+        if (a.cover_on_device == "true")
+            throw UsageError("error: '--select-by-coverage true' replaces the vertex cover and cannot be combined with "
+                             "'--cover-on-device true'");
+    }
+    if (a.thin_panel == "true" || a.select_by_coverage == "true") {
+        if (a.thin_panel == "true" && a.keep_all == "true")
+            throw UsageError("error: '--thin-panel true' drops primers and cannot be combined with '--keep-all true'");
+        if (a.thin_panel == "true" && !a.devices.empty())
             throw UsageError("error: '--thin-panel true' runs on one device and cannot be combined with '--devices'");
         if (a.thin_mismatches > a.kmer_size)
             throw UsageError("error: '--thin-mismatches " + std::to_string(a.thin_mismatches) +
@@ -1110,6 +1132,81 @@ ThinResult thin_panel(const std::vector<std::vector<uint64_t>> &rows, int min_ga
     return out;
 }
 
+SelectResult select_panel(const std::vector<std::vector<uint64_t>> &rows, const std::vector<std::string> &primers,
+                          const ConflictGraph &g, int max_tubes, int min_gain, const std::vector<char> &forced)
+{
+    const size_t n = rows.size();
+    size_t words = 0;
+    for (const auto &r : rows) words = std::max(words, r.size());
+    auto word = [&](size_t p, size_t w) { return w < rows[p].size() ? rows[p][w] : 0ull; };
+    auto is_forced = [&](size_t p) { return p < forced.size() && forced[p]; };
+    // the cover's graph over the primers' indices: symmetric, a self loop kept apart
+    std::map<std::string, size_t> id;
+    for (size_t p = 0; p < n; ++p) id.emplace(primers[p], p);
+    std::vector<std::set<size_t>> adj(n);
+    std::vector<char> self(n, 0);
+    for (const auto &kv : g.edges) {
+        const auto a = id.find(kv.first);
+        if (a == id.end()) continue;
+        for (const auto &w : kv.second) {
+            const auto b = id.find(w);
+            if (b == id.end()) continue;
+            if (a->second == b->second) self[a->second] = 1;
+            else {
+                adj[a->second].insert(b->second);
+                adj[b->second].insert(a->second);
+            }
+        }
+    }
+    const uint64_t all_tubes = max_tubes >= 64 ? ~0ull : (1ull << max_tubes) - 1;
+    SelectResult out;
+    out.keep.assign(n, 0);
+    out.tube.assign(n, -1);
+    out.barred.assign(n, 0);
+    std::vector<uint64_t> covered(words, 0), all(words, 0), mask(n, 0);
+    for (size_t p = 0; p < n; ++p) {
+        out.keep[p] = is_forced(p) ? 1 : 0;
+        for (size_t w = 0; w < words; ++w) {
+            all[w] |= word(p, w);
+            if (is_forced(p)) covered[w] |= word(p, w);
+        }
+        if (is_forced(p))   // the panel is in every tube
+            for (size_t u : adj[p]) mask[u] = all_tubes;
+    }
+    for (;;) {   // every round from scratch: the device keeps its gains up to date instead
+        long best = -1;
+        size_t best_gain = 0;
+        for (size_t p = 0; p < n; ++p) {
+            if (out.keep[p] || self[p] || (mask[p] & all_tubes) == all_tubes) continue;
+            size_t gain = 0;
+            for (size_t w = 0; w < words; ++w) gain += (size_t)__builtin_popcountll(word(p, w) & ~covered[w]);
+            if (best < 0 || gain > best_gain) {   // ">": the lowest index among equals
+                best = (long)p;
+                best_gain = gain;
+            }
+        }
+        ++out.rounds;
+        if (best < 0 || best_gain < (size_t)min_gain) break;
+        const size_t p = (size_t)best;
+        const int t = __builtin_ctzll(~mask[p] & all_tubes);
+        out.order.push_back((int)best);
+        out.gains.push_back((int)best_gain);
+        out.keep[p] = 1;
+        out.tube[p] = t;
+        out.tubes_used = std::max(out.tubes_used, t + 1);
+        for (size_t w = 0; w < words; ++w) covered[w] |= word(p, w);
+        for (size_t u : adj[p]) mask[u] |= 1ull << t;
+    }
+    for (size_t p = 0; p < n; ++p)
+        out.barred[p] = !out.keep[p] && (self[p] || (mask[p] & all_tubes) == all_tubes) ? 1 : 0;
+    for (size_t w = 0; w < words; ++w) {
+        out.covered_all += (size_t)__builtin_popcountll(all[w]);
+        out.covered_kept += (size_t)__builtin_popcountll(covered[w]);
+    }
+    out.covered = covered;
+    return out;
+}
+
 std::string thin_report(int max_mismatches, int exact_3p, int min_gain, size_t kept_f, size_t n_f, size_t kept_r,
                         size_t n_r, size_t forced, size_t covered_all, size_t covered_kept, size_t segments)
 {
@@ -1433,6 +1530,123 @@ std::string thin_panel_on_device(Engine &eng, const DeviceAlignment &aln, std::v
     return thin_report(max_mismatches, exact_3p, min_gain, fwd.size(), n_f, rev.size(), n_r,
                        panel_f.size() + panel_r.size(), (size_t)covered_all, (size_t)covered_kept,
                        (size_t)aln.rows() * P);
+}
+
+std::string select_report(int mode, float tm_threshold, int max_mismatches, int exact_3p, int min_gain, int max_tubes,
+                          size_t kept_f, size_t n_f, size_t kept_r, size_t n_r, size_t forced, size_t barred,
+                          size_t covered_all, size_t covered_kept, size_t segments, const std::vector<size_t> *per_tube)
+{
+    const std::string x = std::to_string(kept_f + kept_r), y = std::to_string(n_f + n_r), t = std::to_string(segments);
+    const std::string what = mode ? "held " : "covered ";
+    std::string s = "\nPanel selection by coverage (";
+    if (mode)
+        s += std::string("thal ") + (mode == 2 ? "END1" : "ANY") + ", t >= " + fmt("%.2f", (double)tm_threshold) +
+             " C; matches within " + std::to_string(max_mismatches) + " mismatches, last ";
+    else
+        s += "up to " + std::to_string(max_mismatches) + " mismatches, last ";
+    s += std::to_string(exact_3p) + " bases exact, gain >= " + std::to_string(min_gain) + ", tubes <= " +
+         std::to_string(max_tubes) + "):\n  Rule:     each round keeps the primer with the most new segments and bars its "
+         "conflict neighbours from its tube\n  Primers:  kept " + x + " of " + y + " (forward " + std::to_string(kept_f) +
+         " of " + std::to_string(n_f) + ", reverse " + std::to_string(kept_r) + " of " + std::to_string(n_r) + "), " +
+         std::to_string(forced) + " forced\n  Barred:   " + std::to_string(barred) + " by conflicts\n  Segments: " + what +
+         std::to_string(covered_all) + "/" + t + " by all " + y + ", " + std::to_string(covered_kept) + "/" + t +
+         " by the kept " + x + "\n";
+    if (per_tube)
+        for (size_t i = 0; i < per_tube->size(); ++i)
+            s += "  Tube " + std::to_string(i + 1) + ": " + std::to_string((*per_tube)[i]) + " primers\n";
+    return s;
+}
+
+std::string select_panel_on_device(Engine &eng, const DeviceAlignment &aln, const std::vector<KmerStat> &fwd,
+                                   const std::vector<KmerStat> &rev, const std::vector<std::string> &panel_f,
+                                   const std::vector<std::string> &panel_r, int segment_size, int overlap_size,
+                                   int window_size, int kmer_size, int max_mismatches, int exact_3p, int min_gain,
+                                   const msspe_chem &chem, int mode, float tm_threshold, int max_tubes, bool list_tubes,
+                                   bool screen, bool drop_self_pairs, float dg_threshold, std::vector<KmerStat> &kept_f,
+                                   std::vector<KmerStat> &kept_r, std::map<std::string, int> &tubes,
+                                   const std::function<void(const KmerStat &, bool)> &dropped)
+{
+    // the graph's nodes are distinct words: the panel's first, then the new primers in their lists' order; a word met
+    // again (the other direction's list) is not offered
+    std::unordered_set<std::string> seen;
+    std::vector<KmerStat> all_f, all_r;
+    std::vector<size_t> src_f, src_r;   // the offered primers' places in fwd / rev
+    std::vector<char> offered_f(fwd.size(), 0), offered_r(rev.size(), 0);
+    for (const auto *panel : {&panel_f, &panel_r})
+        for (const auto &w : *panel) seen.insert(w);
+    for (size_t i = 0; i < fwd.size(); ++i)
+        if (seen.insert(fwd[i].word).second) all_f.push_back(fwd[i]), src_f.push_back(i), offered_f[i] = 1;
+    for (size_t i = 0; i < rev.size(); ++i)
+        if (seen.insert(rev[i].word).second) all_r.push_back(rev[i]), src_r.push_back(i), offered_r[i] = 1;
+    const size_t new_f = all_f.size(), new_r = all_r.size();
+    seen.clear();
+    for (const auto &w : panel_f)
+        if (seen.insert(w).second) all_f.push_back(KmerStat{w, SEQ_DIR_FWD});
+    for (const auto &w : panel_r)
+        if (seen.insert(w).second) all_r.push_back(KmerStat{w, SEQ_DIR_REV});
+    const size_t n = all_f.size() + all_r.size(), W = (n + 63) / 64;
+    std::vector<uint8_t> forced(n + 1, 0), keep(n + 1, 0), tube(n + 1, MSSPE_TUBE_NONE), barred(n + 1, 0);
+    for (size_t i = new_f; i < all_f.size(); ++i) forced[i] = 1;
+    for (size_t i = new_r; i < all_r.size(); ++i) forced[all_f.size() + i] = 1;
+    std::vector<uint32_t> order(n + 1), gains(n + 1);
+    int n_picked = 0, used = 0;
+    long long covered_all = 0, covered_kept = 0;
+    const size_t L = aln.length();
+    const size_t P = L < (size_t)segment_size ? 0 : (L - (size_t)segment_size) / (size_t)overlap_size + 1;
+    const auto wf = pack_words(eng, all_f, kmer_size), wr = pack_words(eng, all_r, kmer_size);
+    void *d_pool = nullptr, *d_bitmap = nullptr;
+    int rc = MSSPE_OK;
+    if (n) {
+        const std::vector<uint64_t> zero(n * W, 0);
+        rc = msspe_device_put(eng.ctx(), zero.data(), sizeof(uint64_t) * zero.size(), &d_bitmap);
+        if (!rc && screen) {   // --check-cross-dimers false: no edges at all
+            std::vector<uint64_t> pool(wf);
+            pool.insert(pool.end(), wr.begin(), wr.end());
+            rc = msspe_device_put(eng.ctx(), pool.data(), sizeof(uint64_t) * n, &d_pool);
+            // the screen's decisions only: the bitmap is all the selection reads
+            if (!rc)
+                rc = msspe_cross_dimer_dev(eng.ctx(), static_cast<const uint64_t *>(d_pool), (int)n, kmer_size, &chem,
+                                           dg_threshold, 0, (int)n, 0, (int)n, nullptr,
+                                           static_cast<uint64_t *>(d_bitmap), nullptr, nullptr);
+            if (!rc) rc = msspe_synchronize(eng.ctx());   // (and the hand-over lists held)
+        }
+    }
+    if (!rc) {
+        const msspe_kmer_opt opt{segment_size, overlap_size, window_size, kmer_size, 0, 0};
+        const msspe_seed_rule rule{max_mismatches, exact_3p, mode, mode ? &chem : nullptr, tm_threshold};
+        const msspe_select_opt so{min_gain, max_tubes, drop_self_pairs ? 1 : 0};
+        rc = msspe_panel_select_packed_dev(eng.ctx(), aln.device(), aln.rows(), L, &opt, &rule, &so, wf.data(),
+                                           (int)wf.size(), wr.data(), (int)wr.size(), forced.data(),
+                                           static_cast<const uint64_t *>(d_bitmap), keep.data(), order.data(),
+                                           gains.data(), &n_picked, tube.data(), barred.data(), nullptr, &covered_all,
+                                           &covered_kept, &used);
+    }
+    if (d_pool) (void)msspe_device_free(eng.ctx(), d_pool);
+    if (d_bitmap) (void)msspe_device_free(eng.ctx(), d_bitmap);
+    if (rc) eng.fail(rc);
+    std::vector<size_t> per_tube((size_t)used, 0);
+    std::vector<char> kept_of_f(fwd.size(), 0), kept_of_r(rev.size(), 0), barred_f(fwd.size(), 0), barred_r(rev.size(), 0);
+    size_t n_barred = 0;
+    for (size_t i = 0; i < new_f + new_r; ++i) {
+        const bool f = i < new_f;
+        const size_t at = f ? i : all_f.size() + (i - new_f), src = f ? src_f[i] : src_r[i - new_f];
+        (f ? kept_of_f : kept_of_r)[src] = (char)keep[at];
+        (f ? barred_f : barred_r)[src] = (char)barred[at];
+        n_barred += barred[at];
+        if (keep[at]) {
+            tubes[(f ? fwd : rev)[src].word] = tube[at];
+            if (tube[at] < per_tube.size()) ++per_tube[tube[at]];
+        }
+    }
+    for (size_t i = 0; i < fwd.size(); ++i)
+        if (kept_of_f[i]) kept_f.push_back(fwd[i]);
+        else dropped(fwd[i], barred_f[i] != 0);
+    for (size_t i = 0; i < rev.size(); ++i)
+        if (kept_of_r[i]) kept_r.push_back(rev[i]);
+        else dropped(rev[i], barred_r[i] != 0);
+    return select_report(mode, tm_threshold, max_mismatches, exact_3p, min_gain, max_tubes, kept_f.size(), fwd.size(),
+                         kept_r.size(), rev.size(), n - new_f - new_r, n_barred, (size_t)covered_all,
+                         (size_t)covered_kept, (size_t)aln.rows() * P, list_tubes ? &per_tube : nullptr);
 }
 
 DeviceBackground::DeviceBackground(Engine &eng, const std::vector<SequenceRecord> &records)
@@ -1770,13 +1984,14 @@ struct Rejected {
     std::string word;
     uint8_t direction;
     int round;
-    const char *reason;   // stage_b, background, panel_dimer, cover
+    const char *reason;   // stage_b, background, panel_dimer, cover, select_conflict, select_unneeded
 };
 // What one pass from stage A to the cover keeps and drops
 struct Selection {
     std::vector<KmerStat> good_f, good_r;
     std::vector<Rejected> rejected;
     std::map<std::string, int> tubes;   // --tubes
+    std::string select_text;            // --select-by-coverage: the round's block
     std::string seeding_text;           // --seed-mismatches / --seed-tm: the block of a round that seeded
 };
 
@@ -1856,7 +2071,8 @@ Selection select_primers(Engine &eng, const DeviceAlignment &aln, const Args &ar
             }
         timer.lap("background upload + screen");
     }
-    if (cfg.check_cross_dimers && !cfg.keep_all && (!panel_f.empty() || !panel_r.empty())) {
+    const bool select = args.select_by_coverage == "true";   // (its forced panel bars the new primers it conflicts with)
+    if (cfg.check_cross_dimers && !cfg.keep_all && !select && (!panel_f.empty() || !panel_r.empty())) {
         // a new primer that dimerises with the panel is dropped before the vertex cover (the panel stays whole)
         std::vector<std::string> cands, all_panel(panel_f);
         all_panel.insert(all_panel.end(), panel_r.begin(), panel_r.end());
@@ -1870,6 +2086,18 @@ Selection select_primers(Engine &eng, const DeviceAlignment &aln, const Args &ar
                         list->end());
         }
         timer.lap("panel cross-dimer screen");
+    }
+    if (select) {   // --select-by-coverage: one screen and one selection take the place of the cover or the tubes
+        const msspe_chem chem = ntthal_chem(opts);
+        const int mode = !args.thin_scored ? 0 : args.thin_thal == "end1" ? 2 : 1;
+        sel.select_text = select_panel_on_device(
+            eng, aln, prim_f, prim_r, panel_f, panel_r, args.window_size, args.overlap_size, args.search_windows_size,
+            args.kmer_size, args.thin_mismatches, args.thin_3p_exact, args.thin_min_gain, chem, mode, args.thin_tm,
+            std::max(1, args.tubes), args.tubes > 0, cfg.check_cross_dimers, !cfg.check_self_dimers, opts.dg,
+            sel.good_f, sel.good_r, sel.tubes,
+            [&](const KmerStat &s, bool barred) { reject(s, barred ? "select_conflict" : "select_unneeded"); });
+        timer.lap("stage C + selection by coverage");
+        return sel;
     }
     std::vector<std::string> primers;
     for (const auto &s : prim_f) primers.push_back(s.word);
@@ -2020,7 +2248,8 @@ int run(const Args &args, std::string &stdout_text)
                                             args.coverage_3p_exact, ntthal_chem(opts),
                                             args.coverage_thal == "end1" ? 2 : 1, args.coverage_tm);
     stdout_text += thin_text;
-    if (args.tubes > 0) stdout_text += tubes_report(good_f, good_r, tubes, args.tubes);
+    for (const auto &sel : rounds) stdout_text += sel.select_text;   // (with --tubes its block lists the tubes)
+    if (args.tubes > 0 && args.select_by_coverage != "true") stdout_text += tubes_report(good_f, good_r, tubes, args.tubes);
     if (background) {   // the CSV's primers by their CSV names, the panel's by the numbers the CSV continues from
         std::vector<std::string> names, words;
         for (const auto *panel_list : {&panel_f, &panel_r}) {

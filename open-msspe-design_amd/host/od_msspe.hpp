@@ -7,6 +7,7 @@
 #pragma once
 
 #include <cstdint>
+#include <functional>
 #include <map>
 #include <set>
 #include <stdexcept>
@@ -56,8 +57,8 @@ struct Args {
     // --exclude-primers FILE: words stage A must never pick (msspe_kmer_candidates_*sets*), read like a panel CSV
     // (direction and primers; further columns ignored, so the file of --rejected-out can be given).  --rejected-out
     // FILE: every candidate this run dropped, as direction,name,primers,round,reason (reason: stage_b, background,
-    // panel_dimer or cover).  --repick-rounds N (0..16): after the first pass, up to N more passes that keep what
-    // passed, ban what failed and let stage A fill the holes, each run like an --existing-primers run whose panel is
+    // panel_dimer or cover; --select-by-coverage: select_conflict or select_unneeded).  --repick-rounds N (0..16):
+    // after the first pass, up to N more passes that keep what passed, ban what failed and let stage A fill the holes, each run like an --existing-primers run whose panel is
     // the user's plus everything kept so far.  One device, not with --tubes.  0 / empty: nothing changes.
     std::string exclude_primers, rejected_out;
     int repick_rounds = 0;
@@ -96,6 +97,12 @@ struct Args {
     std::string thin_tm_text, thin_thal;
     float thin_tm = 0.0f;
     bool thin_scored = false;
+    // --select-by-coverage true: the cover / tube step of every round is replaced by one screen of the round's primers
+    // with the current panel and one msspe_panel_select_packed_dev over them: the panel is forced,
+    // --tubes N gives T = N (1 without it), --check-self-dimers false drop_self_pairs, --check-cross-dimers false an
+    // all-zero graph; the incidence rule is --thin-panel's (--thin-mismatches, --thin-3p-exact, --thin-min-gain,
+    // --thin-tm, --thin-thal, read with this switch too).  "false": nothing changes.
+    std::string select_by_coverage = "false";
     // --seed-mismatches M: a round that seeds stage A (with --existing-primers, and rounds >= 1 of --repick-rounds)
     // seeds it on what the panel COVERS -- every segment of the direction in which a panel primer has a match within M
     // mismatches, its last seed_3p_exact bases exact (msspe_kmer_candidates_both_tolerant_packed_dev) -- instead of
@@ -291,6 +298,43 @@ struct ThinResult {
     size_t covered_all = 0, covered_kept = 0;
 };
 ThinResult thin_panel(const std::vector<std::vector<uint64_t>> &rows, int min_gain, const std::vector<char> &forced);
+// --select-by-coverage (engine extension): the sequential rule of DESIGN.md 4.13 over incidence rows (as thin_panel's)
+// and the cover's graph over primers[p] (symmetric; an edge a -> a is a self conflict).  Forced primers cover first,
+// are never picked, and bar their neighbours from every tube; every round picks the live primer (not kept, not
+// self-conflicting, a tube in [0, max_tubes) left) with the most uncovered segments, ties to the lowest index, gives it
+// the lowest tube its neighbours left and bars them from that tube, until that gain is below min_gain.  The device's
+// independent twin.
+struct SelectResult {
+    std::vector<int> order, gains;   // the picks in order
+    std::vector<char> keep;          // forced or picked
+    std::vector<int> tube;           // of a pick; -1 for everyone else
+    std::vector<char> barred;        // not kept, and self-conflicting or no tube left at the end
+    std::vector<uint64_t> covered;   // by the kept, bit s & 63 of word s >> 6
+    size_t covered_all = 0, covered_kept = 0;
+    int tubes_used = 0, rounds = 0;  // rounds: the picks and the one that stopped
+};
+SelectResult select_panel(const std::vector<std::vector<uint64_t>> &rows, const std::vector<std::string> &primers,
+                          const ConflictGraph &g, int max_tubes, int min_gain, const std::vector<char> &forced);
+// the same rule on the device for one round of the CLI: the round's primers (fwd / rev, stage B's survivors) and the
+// current panel (forced) are screened as one pool (msspe_cross_dimer_dev, bitmap only; screen false: no edges) and
+// selected by one msspe_panel_select_packed_dev.  The kept primers are appended to kept_f / kept_r in their lists'
+// order with their tubes in `tubes`; dropped(primer, barred) is called for every other one.  A word met a second time
+// (the other direction's list, the panel) is not offered.  Returns select_report's block.
+std::string select_panel_on_device(Engine &eng, const DeviceAlignment &aln, const std::vector<KmerStat> &fwd,
+                                   const std::vector<KmerStat> &rev, const std::vector<std::string> &panel_f,
+                                   const std::vector<std::string> &panel_r, int segment_size, int overlap_size,
+                                   int window_size, int kmer_size, int max_mismatches, int exact_3p, int min_gain,
+                                   const msspe_chem &chem, int mode, float tm_threshold, int max_tubes, bool list_tubes,
+                                   bool screen, bool drop_self_pairs, float dg_threshold, std::vector<KmerStat> &kept_f,
+                                   std::vector<KmerStat> &kept_r, std::map<std::string, int> &tubes,
+                                   const std::function<void(const KmerStat &, bool)> &dropped);
+// "Panel selection by coverage (<the match rule>, gain >= G, tubes <= T):", the rule line, the primers kept of those
+// offered (forced ones apart), the primers barred, the segments covered (mode 0) or held (modes 1, 2) by all of them
+// and by the kept ones, and with per_tube the primers per tube
+std::string select_report(int mode, float tm_threshold, int max_mismatches, int exact_3p, int min_gain, int max_tubes,
+                          size_t kept_f, size_t n_f, size_t kept_r, size_t n_r, size_t forced, size_t barred,
+                          size_t covered_all, size_t covered_kept, size_t segments,
+                          const std::vector<size_t> *per_tube);
 // the same rule as one msspe_panel_thin_packed_dev call on the resident alignment: fwd / rev are thinned in place,
 // the panel's primers are forced; returns the report's block
 std::string thin_panel_on_device(Engine &eng, const DeviceAlignment &aln, std::vector<KmerStat> &fwd,

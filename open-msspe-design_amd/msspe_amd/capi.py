@@ -39,6 +39,7 @@ EXPORTS = [
     "msspe_segment_coverage_thal", "msspe_segment_coverage_thal_dev", "msspe_segment_coverage_thal_packed_dev",
     "msspe_panel_thin", "msspe_panel_thin_dev", "msspe_panel_thin_packed_dev",
     "msspe_panel_thin_thal", "msspe_panel_thin_thal_dev", "msspe_panel_thin_thal_packed_dev",
+    "msspe_panel_select", "msspe_panel_select_bitmap", "msspe_panel_select_dev", "msspe_panel_select_packed_dev",
     "msspe_device_put_stream_packed", "msspe_background_sites_packed_dev", "msspe_background_sites",
     "msspe_background_thal_packed_dev", "msspe_background_thal",
     "msspe_background_amplicons_packed_dev", "msspe_background_amplicons",
@@ -116,6 +117,11 @@ class MismatchOpt(C.Structure):
 class ThinOpt(C.Structure):
     """msspe_thin_opt: a pick must cover at least min_gain segments nothing kept covers yet."""
     _fields_ = [("min_gain", C.c_int)]
+
+
+class SelectOpt(C.Structure):
+    """msspe_select_opt: min_gain as ThinOpt, at most max_tubes (1..64) tubes, drop_self_pairs as the cover's."""
+    _fields_ = [("min_gain", C.c_int), ("max_tubes", C.c_int), ("drop_self_pairs", C.c_int)]
 
 
 def lib_path() -> Path:
@@ -279,6 +285,16 @@ def load_library() -> C.CDLL:
                                         L.msspe_panel_thin.argtypes[7:])
     L.msspe_panel_thin_thal_dev.argtypes = L.msspe_panel_thin_thal.argtypes
     L.msspe_panel_thin_thal_packed_dev.argtypes = L.msspe_panel_thin_thal.argtypes
+    # alignment, n_seq, seq_len, opt, rule, sel, fwd, n_fwd, rev, n_rev, forced | graph | keep, order, gain, n_picked,
+    # tube, barred, covered, covered_all, covered_kept, n_tubes_used
+    select_in = [vp, vp, C.c_int, C.c_size_t, C.POINTER(KmerOpt), C.POINTER(SeedRule), C.POINTER(SelectOpt), u64p,
+                 C.c_int, u64p, C.c_int, vp]
+    select_out = [vp, vp, vp, C.POINTER(C.c_int), vp, vp, vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
+                  C.POINTER(C.c_int)]
+    L.msspe_panel_select_dev.argtypes = select_in + [vp] + select_out
+    L.msspe_panel_select_packed_dev.argtypes = select_in + [vp] + select_out
+    L.msspe_panel_select_bitmap.argtypes = select_in + [vp] + select_out
+    L.msspe_panel_select.argtypes = select_in + [C.POINTER(Chem), C.c_float] + select_out
     L.msspe_device_put_stream_packed.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int,
                                                  C.POINTER(vp), C.POINTER(C.c_size_t), vp]
     L.msspe_background_sites_packed_dev.argtypes = [vp, vp, C.c_size_t, C.c_int, C.POINTER(MismatchOpt), u64p, C.c_int,
@@ -1066,6 +1082,85 @@ class Engine:
                 self.device_free(owned)
         return (keep, order[:n_picked.value].copy(), gains[:n_picked.value].copy(), covered, int(c_all.value),
                 int(c_kept.value))
+
+    # ---- a conflict-free panel selected by coverage (engine extension; msspe_panel_select*) ----------------------
+    def panel_select(self, genomes, opt: KmerOpt, fwd, rev, rule: SeedRule, bitmap=None, max_tubes: int = 1,
+                     min_gain: int = 1, drop_self_pairs: bool = False, forced=None, form: str = "bitmap",
+                     chem: Chem | None = None, threshold: float = -9000.0):
+        """Greedy set cover in which a pick bars its conflict neighbours from its tube (msspe_panel_select*).
+        genomes, fwd, rev, forced as panel_thin; rule: seed_rule(M, E[, mode, chem, tm]) says what a primer covers.
+        form "bitmap": `bitmap` is a host uint64 (n, ceil(n/64)) array (the layout of cross_dimer_dev over the pool
+        forward words then reverse words) and the alignment goes over from the host; "dev" / "packed": the alignment is
+        uploaded (as bytes / packed rows) or resident as (device address, n_seq, seq_len), and `bitmap` is either such
+        an array (uploaded for the call) or a device address; "screen": the call screens the pool itself at `chem`
+        (default Chem.ntthal()) and `threshold`.  Returns a dict: keep, order, gains, tube, barred (uint8[n]), covered
+        (n_seq, P), covered_all, covered_kept, tubes_used."""
+        if form not in ("bitmap", "dev", "packed", "screen"):
+            raise ValueError("form must be 'bitmap', 'dev', 'packed' or 'screen'")
+        f, r = _words(fwd), _words(rev)
+        n = len(f) + len(r)
+        owned = []
+        try:
+            if isinstance(genomes, tuple):
+                if form in ("bitmap", "screen"):
+                    raise ValueError("a resident alignment needs form='dev' or 'packed'")
+                handle, n_seq, seq_len = genomes
+                seqs_arg = C.c_void_p(handle)
+            else:
+                a = np.ascontiguousarray(genomes, dtype=np.uint8)
+                n_seq, seq_len = a.shape
+                if form in ("bitmap", "screen"):
+                    seqs_arg = a.ctypes.data
+                elif form == "packed":
+                    owned.append(self.put_rows_packed(a))
+                    seqs_arg = C.c_void_p(owned[-1])
+                else:
+                    dev = C.c_void_p()
+                    self._check(self.L.msspe_device_put(self.ptr, a.ctypes.data, a.size, C.byref(dev)))
+                    owned.append(int(dev.value))
+                    seqs_arg = C.c_void_p(owned[-1])
+            if form == "screen":
+                chem = chem or Chem.ntthal()
+                graph = (C.byref(chem), C.c_float(threshold))
+            elif isinstance(bitmap, (int, np.integer)) and form != "bitmap":
+                graph = (C.c_void_p(int(bitmap)),)
+            else:
+                B = np.ascontiguousarray(bitmap, dtype=np.uint64) if bitmap is not None else np.zeros((n, (n + 63) // 64), np.uint64)
+                if B.size != n * ((n + 63) // 64):
+                    raise ValueError("bitmap needs n x ceil(n/64) words")
+                if form == "bitmap":
+                    graph = (B.ctypes.data if B.size else None,)
+                else:
+                    dev = C.c_void_p()
+                    self._check(self.L.msspe_device_put(self.ptr, B.ctypes.data if B.size else None, B.nbytes,
+                                                        C.byref(dev)))
+                    owned.append(int(dev.value))
+                    graph = (C.c_void_p(owned[-1]),)
+            fn = {"bitmap": self.L.msspe_panel_select_bitmap, "dev": self.L.msspe_panel_select_dev,
+                  "packed": self.L.msspe_panel_select_packed_dev, "screen": self.L.msspe_panel_select}[form]
+            P = 0 if seq_len < opt.segment_size else (seq_len - opt.segment_size) // opt.overlap_size + 1
+            flags = None if forced is None else np.ascontiguousarray(np.asarray(forced) != 0, dtype=np.uint8)
+            if flags is not None and flags.shape != (n,):
+                raise ValueError("forced needs one flag per primer")
+            keep = np.zeros(n, dtype=np.uint8)
+            order = np.zeros(max(n, 1), dtype=np.uint32)
+            gains = np.zeros(max(n, 1), dtype=np.uint32)
+            tube = np.zeros(max(n, 1), dtype=np.uint8)
+            barred = np.zeros(max(n, 1), dtype=np.uint8)
+            covered = np.zeros((n_seq, P), dtype=np.uint8)
+            n_picked, used, c_all, c_kept = C.c_int(0), C.c_int(0), C.c_longlong(0), C.c_longlong(0)
+            sel = SelectOpt(min_gain, max_tubes, 1 if drop_self_pairs else 0)
+            self._check(fn(self.ptr, seqs_arg, n_seq, seq_len, C.byref(opt), C.byref(rule), C.byref(sel),
+                           f.ctypes.data, len(f), r.ctypes.data, len(r),
+                           flags.ctypes.data if flags is not None else None, *graph, keep.ctypes.data,
+                           order.ctypes.data, gains.ctypes.data, C.byref(n_picked), tube.ctypes.data,
+                           barred.ctypes.data, covered.ctypes.data, C.byref(c_all), C.byref(c_kept), C.byref(used)))
+        finally:
+            for d in owned:
+                self.device_free(d)
+        return {"keep": keep, "order": order[:n_picked.value].copy(), "gains": gains[:n_picked.value].copy(),
+                "tube": tube[:n].copy(), "barred": barred[:n].copy(), "covered": covered,
+                "covered_all": int(c_all.value), "covered_kept": int(c_kept.value), "tubes_used": int(used.value)}
 
     # ---- off-target sites in a background ------------------------------------------------------
     @staticmethod
