@@ -3,8 +3,12 @@
 seed one Engine and a schedule of calls -- END, pool against pool, the thal record, seeded stage A, coverage within M
 mismatches, panel thinning, cover and tubes, the background family -- in shuffled order, growing and shrinking, on dirty
 output buffers and under engine options, each against the oracle or the family's model (tests/session_campaign_model.py),
-and the first three calls once more at the end.
-usage: random_campaign_session.py [seed] [sessions] [--models-only] [--only INDEX]
+and the first three calls once more at the end.  --campaign 2 drives the second campaign instead
+(tests/session_campaign2_model.py): decision-only screens through the bound chain, the bound diagnostic planes, coverage
+and thinning scored with thal, excluding and tolerant stage A and the selection by coverage, chained with the calls whose
+device state they share.
+usage: random_campaign_session.py [seed] [sessions] [--campaign 1|2] [--models-only] [--only INDEX]
+  --campaign N   1 (default): tests/session_campaign_model.py; 2: tests/session_campaign2_model.py
   --models-only  no engine: every schedule and expected value, the model time per call and the counters per session
   --only INDEX   run the schedule up to and including call INDEX and check only that call"""
 import sys
@@ -14,12 +18,17 @@ from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
 for p in (ROOT / "open-msspe-design_amd", ROOT / "oracle", ROOT / "tests"):
     sys.path.insert(0, str(p))
-import session_campaign_model as scm
-
 args = sys.argv[1:]
 models_only = "--models-only" in args
 only = int(args[args.index("--only") + 1]) if "--only" in args else None
-pos = [a for i, a in enumerate(args) if not a.startswith("--") and (i == 0 or args[i - 1] != "--only")]
+campaign = int(args[args.index("--campaign") + 1]) if "--campaign" in args else 1
+if campaign not in (1, 2):
+    sys.exit("--campaign takes 1 or 2")
+if campaign == 2:
+    import session_campaign2_model as scm
+else:
+    import session_campaign_model as scm
+pos = [a for i, a in enumerate(args) if not a.startswith("--") and (i == 0 or args[i - 1] not in ("--only", "--campaign"))]
 seed0 = int(pos[0]) if pos else 8
 sessions = int(pos[1]) if len(pos) > 1 else 4
 bad = 0
