@@ -156,7 +156,18 @@ const char *msspe_version(void);
  *                                 fits that field (msspe_host_bound_packed; "auto", the default, and "1": the same);
  *                                 "0": the exact-unit instance.  A coarser bound only culls fewer pairs; decisions are
  *                                 the exact stages' either way
- *   "stage_a_graph" "0" | "1"    hipGraph replay of stage A's greedy loop (1)
+ *   "pair_bound_window" "auto" | "0" | "1"  where the packed instance runs and "pair_bound_list" is on, its WINDOWED
+ *                                 instance runs in its place (k_pairs_bound_window): a cell of row i scans the rows
+ *                                 i-F .. i-1 and takes one candidate, built on the smallest value of all rows above and
+ *                                 the cheapest long-loop entries (msspe_host_bound_window), for the rest -- a lower bound
+ *                                 of the packed instance's value at fewer instructions.  A pair it cannot cull goes to
+ *                                 the bound list stage's list, whose exact-unit bound decides before the exact stages.
+ *                                 "1": wherever that applies; "auto" (the default): the same for screens of 2^23 pairs
+ *                                 and more; "0": never.  msspe_get_info "bound_window_survivors": ordered pairs it sent
+ *                                 to that list as not culled since the last read ("bound_survivors" counts what the
+ *                                 exact-unit and packed instances append to hand-over list 0; the windowed one appends
+ *                                 none, behind it "bound_list_survivors" holds the pairs no bound could cull)
+ *   "stage_a_graph" "0" | "1"   hipGraph replay of stage A's greedy loop (1)
  *   "stage_a_candidates" "0" | "1"  greedy loop over the list of words near the maximum (1), or over all the
  *                                 words on every iteration (0); the winners are the same */
 int msspe_set_option(msspe_ctx *ctx, const char *key, const char *value);
@@ -300,6 +311,11 @@ int msspe_cross_dimer_bound_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, i
  * a value, +inf and -inf; a value is an integer multiple of the instance's unit (1, 2 or 4 cal/mol) and at most the
  * exact-unit instance's.  MSSPE_ERR_ARG also where the chemistry's range of cell values fits none of those units. */
 int msspe_cross_dimer_bound_packed_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const msspe_chem *chem,
+                                       float dg_threshold, int row0, int row1, int col0, int col1, double *d_bound);
+/* The same plane from the WINDOWED packed instance (option "pair_bound_window"): the same pairs carry a value, +inf and
+ * -inf; a value is a multiple of the packed instance's unit and at most the packed instance's.  MSSPE_ERR_ARG also where
+ * msspe_host_bound_window reports usable = 0. */
+int msspe_cross_dimer_bound_window_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const msspe_chem *chem,
                                        float dg_threshold, int row0, int row1, int col0, int col1, double *d_bound);
 /* The same plane with the bound LIST stage (option "pair_bound_list") behind the first stage: every pair the first stage
  * would put on list U -- 53..63 stored cells, lanes dragged or shed from their wave -- carries the value that stage
@@ -507,6 +523,11 @@ int msspe_host_bound_tables(const char *params_path, const msspe_chem *chem, flo
  * usable = 0 (all else 0): the bound stage does not apply, or no shift holds the range -- the exact-unit instance runs. */
 int msspe_host_bound_packed(const char *params_path, const msspe_chem *chem, float dg_threshold, int32_t *packed_g,
                             int32_t *packed_T, int32_t info[8]);
+/* Host only: the windowed packed instance's constants (option "pair_bound_window"; csrc/fast_tables.hpp BoundWindow).
+ * info = usable, F (rows a cell scans exactly), ifar, bfar (the smallest finite entry of msspe_host_bound_packed's T over
+ * the rows l1 >= F with l2 >= 1 / with l2 = 0, coarse units; info[4] where there is none), the void value.  usable = 0
+ * wherever the packed instance's is, or where hi + bias reaches the largest field value. */
+int msspe_host_bound_window(const char *params_path, const msspe_chem *chem, float dg_threshold, int32_t info[8]);
 /* Host only: *mirror_ok = 1 when the bound first stage may fill each unordered pair of a square same-pool screen once
  * (option "pair_mirror"): its tables are usable and every real-valued term of them equals its strand-swapped partner
  * within 1e-6 cal/mol (csrc/fast_tables.hpp bound_mirror_ok). */

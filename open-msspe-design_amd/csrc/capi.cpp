@@ -61,6 +61,8 @@ struct ChemEntry {
     BoundTables *d_btq = nullptr; // the packed bound instance's coarse tables (BoundPacked::q; k_pairs_bound_packed)
     bool packed_ok = false;       // ... usable: a proven range of every cell value fits the slot word's 15-bit field (build_bound_packed)
     int packed_shift = 0, packed_bias = 0;
+    BoundWindow window{};         // the windowed packed instance's constants (build_bound_window; k_pairs_bound_window)
+    bool window_ok = false;       // ... usable: packed_ok, and no real slot field equals the far minimum's "no cell"
     // option pair_bound = auto: the share of pairs the bound stage could not cull, per oligo length, as the first
     // call's probe launch measured it (this entry keys on chemistry AND threshold); < 0: no record yet
     float bound_share[16] = {-1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f, -1.f};
@@ -79,9 +81,10 @@ constexpr long kListCapMax = 1L << 30;       // 8 GB per list (two of them, 6 % 
                                              // 2^28 -> 2^30 is 17 -> 5 flushes per 65,536^2 screen and 1.5 % of its time
 constexpr size_t kGenericLanes = 1u << 16;   // lanes of the generic kernels' workspace
 constexpr int kOvfTotals = 2 + 7;            // msspe_ctx::d_ovf_total: two flags / totals, then one total per hand-over list
-constexpr int kReasonWords = 9 + 1024 + 8 + 4;   // msspe_ctx::d_reasons (int_core.hpp IntArgs::reasons); the last four: pairs
-constexpr int kBoundSurvivors = kReasonWords - 4;   // the bound first stage handed on, and its probe launch's count;
-constexpr int kBoundListStats = kReasonWords - 2;   // the bound list stage: entries of list U, ordered pairs it appended
+constexpr int kReasonWords = 9 + 1024 + 8 + 5;   // msspe_ctx::d_reasons (int_core.hpp IntArgs::reasons); the last five: pairs
+constexpr int kBoundSurvivors = kReasonWords - 5;   // the bound first stage handed on, and its probe launch's count;
+constexpr int kBoundListStats = kReasonWords - 3;   // the bound list stage: entries of list U, ordered pairs it appended;
+constexpr int kBoundWindowSurvivors = kReasonWords - 1;   // ordered pairs the windowed first stage sent to list U as not culled
 constexpr int kOvfCounters = 9;                     // msspe_ctx::ovf_count: the eight stage counters, then list U's
 constexpr int kOvfU = 8;
 constexpr long kBoundProbePairs = 1L << 20;  // pair_bound = auto: pairs of the probe launch behind a new record
@@ -91,6 +94,10 @@ constexpr long kBoundProbePairs = 1L << 20;  // pair_bound = auto: pairs of the 
 // (the mirrored stage of a square screen costs 0.0763 ns per ordered pair: its break-even share is about 15 %, so the
 //  switch point stays on the safe side there)
 constexpr float kBoundShareMax = 0.039f;
+// pair_bound_window = auto: screens of at least this many pairs.  Below it -- the short chain's range (cross_dimer_impl) --
+// a screen is a few launches whose time is latency, not the first stage's instruction count, and the longer list U only
+// adds to the flush
+constexpr long kWindowAutoMinPairs = 1L << 23;
 
 }  // namespace
 
@@ -112,6 +119,10 @@ struct EngineOptions {
                               // (k_pairs_bound_list) before the exact lists -- 0 never | 1, 2 (auto): wherever the bound first stage runs
     int pair_bound_packed = 2;  // the bound first stage runs its packed instance (k_pairs_bound_packed: one register per slot, coarse
                               // units, 1,024 threads) -- 0 never | 1, 2 (auto): wherever the chemistry's range fits (ChemEntry::packed_ok)
+    int pair_bound_window = 2;  // the packed first stage runs its WINDOWED instance (k_pairs_bound_window: a cell scans the rows of a
+                              // window, one candidate stands for all rows above; what it does not cull goes to list U) -- 0 never |
+                              // 1 wherever the packed instance would run, the chemistry's entry is usable (ChemEntry::window_ok) and
+                              // pair_bound_list is on | 2 auto: the same, from kWindowAutoMinPairs pairs per screen
     bool split_list = true;   // short oligos: tables too large for the integer list stage go to the split kernel's list mode
     bool short_chain = true;  // screens of up to 2^23 pairs: integer list stage -> one wave per pair (no register-table stages between)
     int self_lane_from = 81920;   // oligos per call from which SELF_ANY / SELF_END run one lane per oligo (msspe_oligo_stats_dev)
@@ -330,6 +341,7 @@ int chem_entry(msspe_ctx *ctx, const msspe_chem &chem, float threshold, ChemEntr
                     e.packed_bias = bp->bias;
                     HIP_TRY(ctx, hipMalloc((void **)&e.d_btq, sizeof(BoundTables)));
                     HIP_TRY(ctx, hipMemcpy(e.d_btq, &bp->q, sizeof(BoundTables), hipMemcpyHostToDevice));
+                    e.window_ok = build_bound_window(*bp, pairs_bound_window_rows(), e.window);
                 }
             }
         }
@@ -811,6 +823,10 @@ int msspe_set_option(msspe_ctx *ctx, const char *key, const char *value)
         if (v == "auto") ctx->opt.pair_mirror = 2;
         else if (is_num && (num == 0 || num == 1)) ctx->opt.pair_mirror = (int)num;
         else return bad();
+    } else if (k == "pair_bound_window") {
+        if (v == "auto") ctx->opt.pair_bound_window = 2;
+        else if (is_num && (num == 0 || num == 1)) ctx->opt.pair_bound_window = (int)num;
+        else return fail(ctx, MSSPE_ERR_ARG, "pair_bound_window: 0, 1 or auto");
     } else if (k == "pair_bound_packed") {
         if (v == "auto") ctx->opt.pair_bound_packed = 2;
         else if (is_num && (num == 0 || num == 1)) ctx->opt.pair_bound_packed = (int)num;
@@ -907,6 +923,21 @@ int msspe_get_info(msspe_ctx *ctx, const char *key, long long *value_out)
     else if (k == "pair_mirror") *value_out = ctx->opt.pair_mirror;
     else if (k == "pair_bound_list") *value_out = ctx->opt.pair_bound_list;
     else if (k == "pair_bound_packed") *value_out = ctx->opt.pair_bound_packed;
+    else if (k == "pair_bound_window") *value_out = ctx->opt.pair_bound_window;
+    else if (k == "bound_window_survivors") {
+        // ordered pairs the windowed first stage could not cull and sent to list U since the last read of this key (reading
+        // resets it).  bound_survivors counts what a first stage appended to list 0 as a survivor of ITS bound: the exact-unit
+        // and packed instances do; the windowed one appends none -- behind it the bound list stage decides, and the pairs no
+        // bound could cull are among bound_list_survivors
+        *value_out = 0;
+        if (!ctx->d_reasons) return MSSPE_OK;
+        uint64_t v = 0;
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        HIP_TRY(ctx, hipMemcpy(&v, ctx->d_reasons + kBoundWindowSurvivors, sizeof v, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->d_reasons + kBoundWindowSurvivors, 0, sizeof v, ctx->stream));
+        *value_out = (long long)v;
+    }
     else if (k == "bound_list_pairs" || k == "bound_list_survivors") {
         // the bound list stage since the last read of this key (reading resets it): entries of list U (unordered pairs under
         // the mirror), ordered pairs it appended to list 0
@@ -1105,6 +1136,7 @@ struct ChainRoute {
                         // its row-specialised and bound instances until settle_first_stage has picked one
     bool bound_list = false;   // Bound, BoundMirror: the bound list stage runs at every flush (option pair_bound_list)
     bool bound_packed = false; // Bound, BoundMirror: the packed instance is the first stage (option pair_bound_packed)
+    bool bound_window = false; // ... and of it the windowed instance (option pair_bound_window; needs bound_list)
     StageList behind;   // the list stages behind a first stage other than Dense, in order
 };
 
@@ -1161,6 +1193,14 @@ static int settle_first_stage(msspe_ctx *ctx, ChemEntry *ce, const ScreenBlock &
     // the packed instance wherever the chemistry's range fits its field (auto and 1 alike: never where it is not proven);
     // the probe above and the plane form msspe_cross_dimer_bound_dev stay on the exact-unit instance
     route.bound_packed = ce->packed_ok && ctx->opt.pair_bound_packed != 0;
+    // of it the windowed instance, whose survivors are list U's to bound: without the bound list stage they would reach the
+    // exact chain at its price, so the packed instance stays.  A screen that is being captured keeps the packed instance
+    // as well; the probe above and the plane forms never run this one.
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(ctx->stream, &cs) != hipSuccess) (void)hipGetLastError();
+    const long n_pairs = (long)(b.row1 - b.row0) * (long)b.sinks.ncols;
+    route.bound_window = route.bound_packed && route.bound_list && ce->window_ok && cs == hipStreamCaptureStatusNone &&
+                         (ctx->opt.pair_bound_window == 1 || (ctx->opt.pair_bound_window == 2 && n_pairs >= kWindowAutoMinPairs));
     return MSSPE_OK;
 }
 
@@ -1256,7 +1296,8 @@ static int run_chain(msspe_ctx *ctx, ChemEntry *ce, ChainRoute route, const Scre
         case FirstStage::BoundMirror:
             HIP_TRY(ctx, launch_pairs_bound(a, ce->d_it, ce->d_bt, ctx->d_reasons + kBoundSurvivors, nullptr, ctx->n_cu,
                                             ctx->stream, route.first == FirstStage::BoundMirror, u_list, u_count,
-                                            route.bound_packed ? ce->d_btq : nullptr, ce->packed_bias, ce->packed_shift));
+                                            route.bound_packed ? ce->d_btq : nullptr, ce->packed_bias, ce->packed_shift,
+                                            route.bound_window ? &ce->window : nullptr, ctx->d_reasons + kBoundWindowSurvivors));
             break;
         }
         if ((rc = prof_end())) return rc;
@@ -1404,7 +1445,7 @@ int msspe_cross_dimer_edges_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, i
 // their -inf.
 static int cross_dimer_bound_plane(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const msspe_chem *chem,
                                    float dg_threshold, int row0, int row1, int col0, int col1, double *d_bound, bool with_list,
-                                   bool packed = false)
+                                   bool packed = false, bool window = false)
 {
     const ScreenBlock b = screen_block(d_pool, n, k, k, row0, row1, col0, col1, plane_sinks(nullptr, nullptr, nullptr, nullptr));
     ChemEntry *ce = nullptr;
@@ -1417,6 +1458,8 @@ static int cross_dimer_bound_plane(msspe_ctx *ctx, const uint64_t *d_pool, int n
     if (packed && !ce->packed_ok)
         return fail(ctx, MSSPE_ERR_ARG, "msspe_cross_dimer_bound_packed_dev: no coarse unit of the packed instance holds this "
                                         "chemistry's range of cell values");
+    if (window && !ce->window_ok)
+        return fail(ctx, MSSPE_ERR_ARG, "msspe_cross_dimer_bound_window_dev: the windowed instance does not apply to this chemistry");
     const int ncols = b.sinks.ncols;
     int rc2 = 0;
     const long n_pairs = (long)(row1 - row0) * (long)ncols;
@@ -1430,7 +1473,8 @@ static int cross_dimer_bound_plane(msspe_ctx *ctx, const uint64_t *d_pool, int n
     const PairKernelArgs a = first_stage_args(ctx, ce, b, Launch{row0, row1, 0, ncols, 0, 0, false});
     if (!with_list) {
         HIP_TRY(ctx, launch_pairs_bound(a, ce->d_it, ce->d_bt, nullptr, d_bound, ctx->n_cu, ctx->stream, false, nullptr, nullptr,
-                                        packed ? ce->d_btq : nullptr, ce->packed_bias, ce->packed_shift));
+                                        packed ? ce->d_btq : nullptr, ce->packed_bias, ce->packed_shift,
+                                        window ? &ce->window : nullptr, nullptr));
         return MSSPE_OK;
     }
     uint32_t *const u_count = ctx->ovf_count + kOvfU;
@@ -1451,6 +1495,12 @@ int msspe_cross_dimer_bound_packed_dev(msspe_ctx *ctx, const uint64_t *d_pool, i
                                        float dg_threshold, int row0, int row1, int col0, int col1, double *d_bound)
 {
     return cross_dimer_bound_plane(ctx, d_pool, n, k, chem, dg_threshold, row0, row1, col0, col1, d_bound, false, true);
+}
+
+int msspe_cross_dimer_bound_window_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const msspe_chem *chem,
+                                       float dg_threshold, int row0, int row1, int col0, int col1, double *d_bound)
+{
+    return cross_dimer_bound_plane(ctx, d_pool, n, k, chem, dg_threshold, row0, row1, col0, col1, d_bound, false, true, true);
 }
 
 int msspe_cross_dimer_bound_list_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const msspe_chem *chem,
@@ -4405,12 +4455,11 @@ int msspe_host_bound_tables(const char *params_path, const msspe_chem *chem, flo
     return MSSPE_OK;
 }
 
-int msspe_host_bound_packed(const char *params_path, const msspe_chem *chem, float dg_threshold, int32_t *packed_g,
-                            int32_t *packed_T, int32_t info[8])
+// host only: the packed bound instance's tables (csrc/fast_tables.hpp BoundPacked) as chem_entry() would build them;
+// all zero where the instance does not apply
+static int host_bound_packed(const char *params_path, const msspe_chem *chem, float dg_threshold, BoundPacked &out)
 {
-    // host only: the packed bound instance's tables (csrc/fast_tables.hpp BoundPacked) as chem_entry() would build them
-    if (!chem || !packed_g || !packed_T || !info) return MSSPE_ERR_ARG;
-    for (int q = 0; q < 8; ++q) info[q] = 0;
+    std::memset(&out, 0, sizeof out);
     auto tb = std::make_unique<NNTables>();
     std::string err;
     const std::string path = params_path && *params_path ? params_path : default_bundle_path();
@@ -4425,10 +4474,20 @@ int msspe_host_bound_packed(const char *params_path, const msspe_chem *chem, flo
     auto st = std::make_unique<SplitTables>();
     const TableRoutes r = table_routes(*tb, *pt, chem->max_loop, *ft, *it, *st);
     auto bt = std::make_unique<BoundTables>();
-    auto bp = std::make_unique<BoundPacked>();
     const bool ok = build_bound_tables(*ft, c, pairs_bound_max_k(), *bt) && r.row_ok &&
-                    build_bound_packed(*bt, pairs_bound_max_k(), *bp);
-    if (!ok) std::memset(bp.get(), 0, sizeof(BoundPacked));
+                    build_bound_packed(*bt, pairs_bound_max_k(), out);
+    if (!ok) std::memset(&out, 0, sizeof out);
+    return MSSPE_OK;
+}
+
+int msspe_host_bound_packed(const char *params_path, const msspe_chem *chem, float dg_threshold, int32_t *packed_g,
+                            int32_t *packed_T, int32_t info[8])
+{
+    if (!chem || !packed_g || !packed_T || !info) return MSSPE_ERR_ARG;
+    for (int q = 0; q < 8; ++q) info[q] = 0;
+    auto bp = std::make_unique<BoundPacked>();
+    if (int rc = host_bound_packed(params_path, chem, dg_threshold, *bp)) return rc;
+    const bool ok = bp->usable != 0;
     std::memcpy(packed_g, bp->q.g, sizeof bp->q.g);
     std::memcpy(packed_T, bp->q.T, sizeof bp->q.T);
     info[0] = ok ? 1 : 0;
@@ -4439,6 +4498,23 @@ int msspe_host_bound_packed(const char *params_path, const msspe_chem *chem, flo
     info[5] = bp->q.init;
     info[6] = bp->q.cut;
     info[7] = BoundPacked::kFieldMax;
+    return MSSPE_OK;
+}
+
+int msspe_host_bound_window(const char *params_path, const msspe_chem *chem, float dg_threshold, int32_t info[8])
+{
+    // host only: the windowed instance's constants (csrc/fast_tables.hpp BoundWindow) as chem_entry() would build them
+    if (!chem || !info) return MSSPE_ERR_ARG;
+    for (int q = 0; q < 8; ++q) info[q] = 0;
+    auto bp = std::make_unique<BoundPacked>();
+    if (int rc = host_bound_packed(params_path, chem, dg_threshold, *bp)) return rc;
+    BoundWindow w;
+    build_bound_window(*bp, pairs_bound_window_rows(), w);
+    info[0] = w.usable;
+    info[1] = w.F;
+    info[2] = w.ifar;
+    info[3] = w.bfar;
+    info[4] = BoundWindow::kVoid;
     return MSSPE_OK;
 }
 

@@ -154,4 +154,19 @@ struct BoundPacked {
 // usable = 0 (and the exact-unit instance runs) when bt is unusable or no shift fits.
 bool build_bound_packed(const BoundTables &bt, int max_k, BoundPacked &out);
 
+// Constants of the WINDOWED packed instance (thal_pairs_row.hip k_pairs_bound_window): a cell of row i scans the rows
+// i-F .. i-1 exactly and takes ONE candidate for every row above them,  farmin + min(bfar, ifar + cell-side term),
+// farmin being the smallest value of any stored cell of those rows.  ifar / bfar: the smallest finite coarse entry of
+// BoundPacked::q.T over the rows l1 >= F with l2 >= 1 / with l2 = 0, any context -- at most the entry of every real
+// predecessor up there, so the relaxed value is at most the packed instance's and a lower bound all the same.  The proven
+// range holds as it is: the far step is not below the most negative step, a chain still has at most max_k - 1 steps, and a
+// cell is still at most its left end term.
+struct BoundWindow {
+    int32_t F;                // rows of the window
+    int32_t ifar, bfar;       // coarse units; kVoid: no finite entry (the candidate loses that branch, or is void altogether)
+    int32_t usable;           // 0 wherever the packed instance is unusable, or a real field could be kFieldMax (farmin's "no cell")
+    static constexpr int32_t kVoid = 1 << 26;   // thal_pairs_row.hip kWinVoid
+};
+bool build_bound_window(const BoundPacked &bp, int F, BoundWindow &out);
+
 }  // namespace msspe

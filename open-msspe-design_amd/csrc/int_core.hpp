@@ -182,6 +182,9 @@ struct IntArgs {
     // the packed bound instance (k_pairs_bound_packed): bt holds BoundPacked::q, the terms in units of 2^(shift - 6) cal/mol
     int packed_bias = 0;                              // slot field = cell value + bias (BoundPacked::bias)
     double packed_unit = 0.0;                         // cal/mol per unit (the plane form's values)
+    // the windowed packed instance (k_pairs_bound_window): BoundWindow's constants; what it does not cull goes to list U
+    int window_ifar = 0, window_bfar = 0;
+    unsigned long long *window_survivors = nullptr;   // += ordered pairs the relaxed value could not cull
     // list U: lanes that left their wave of the bound instance WITHOUT a bound of their own (53..63 stored cells, dragged,
     // shed by the slot fit), once per unordered pair; k_pairs_bound_list bounds them.  nullptr: they go to ovf_list
     uint2 *ulist = nullptr;

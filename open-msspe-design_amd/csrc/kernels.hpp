@@ -139,7 +139,13 @@ bool pairs_row_tables_ok(const IntTables &it);   // host: may this chemistry run
 hipError_t launch_pairs_bound(const PairKernelArgs &a, const IntTables *it, const BoundTables *bt,
                               unsigned long long *survivors, double *bound_plane, int n_cu, hipStream_t stream,
                               bool mirror = false, uint2 *ulist = nullptr, uint32_t *ucount = nullptr,
-                              const BoundTables *packed_q = nullptr, int packed_bias = 0, int packed_shift = 0);
+                              const BoundTables *packed_q = nullptr, int packed_bias = 0, int packed_shift = 0,
+                              const BoundWindow *window = nullptr, unsigned long long *window_survivors = nullptr);
+// window != nullptr (with packed_q; host memory): the WINDOWED packed instance runs (k_pairs_bound_window) -- a cell scans
+// window->F rows and takes one candidate for all rows above, so the value is a lower bound of the packed instance's.  A
+// pair it does not cull is NOT appended to a.overflow_list but to list U (ulist is required outside the plane form),
+// where launch_pairs_bound_list's exact-unit bound decides; *window_survivors += those ordered pairs, *survivors stays.
+int pairs_bound_window_rows();   // the F the windowed instance was generated for
 // packed_q != nullptr (BoundPacked::q on the device, with its bias and shift): the PACKED instance runs
 // (k_pairs_bound_packed: one register per slot, 1,024 threads) -- the same contract, the bound in units of
 // 2^(shift - 6) cal/mol, every term floored, which only lowers it; the plane form's values are multiples of that unit.

@@ -773,6 +773,27 @@ bool build_bound_packed(const BoundTables &bt, int max_k, BoundPacked &out)
     return false;
 }
 
+bool build_bound_window(const BoundPacked &bp, int F, BoundWindow &out)
+{
+    std::memset(&out, 0, sizeof out);
+    out.F = F;
+    out.ifar = out.bfar = BoundWindow::kVoid;
+    // hi + bias < kFieldMax: no published field equals the "no cell" value of the far minimum
+    if (!bp.usable || F < 2 || (long)bp.hi + (long)bp.bias >= (long)BoundPacked::kFieldMax) return false;
+    for (int d = 0; d < IntTables::kRows; ++d) {
+        const int l1 = d >> 4, l2 = d & 15;
+        if (l1 < F) continue;
+        for (int pe = 0; pe < 64; ++pe) {
+            const int32_t v = bp.q.T[d * 64 + pe];
+            if (v >= IntTables::kValid) continue;
+            int32_t &m = l2 == 0 ? out.bfar : out.ifar;
+            m = std::min(m, v);
+        }
+    }
+    out.usable = 1;
+    return true;
+}
+
 bool build_split_tables(const PairTables &pt, int max_loop, SplitTables &out)
 {
     typedef SplitTables W;

@@ -44,6 +44,7 @@
 #include "row_scan_pinned.inc"
 #include "row_bound_pinned.inc"
 #include "row_bound_packed_pinned.inc"
+#include "row_bound_window_pinned.inc"
 
 
 namespace msspe {
@@ -859,20 +860,66 @@ static __device__ __forceinline__ void packed_publish(v32i &Wa, v16i &Wb, v4i &W
                  : "m0");
 }
 
+// ---- the WINDOWED packed instance (k_pairs_bound_window): rows i-F .. i-1 are scanned as above, every row above them
+// is ONE candidate,  farmin + min(Bfar, Ifar + cell-side term)  -- farmin: the smallest value any stored cell of the rows
+// <= i-1-F holds, whatever its column; Ifar / Bfar: the smallest finite coarse table entry over l1 >= F with l2 >= 1 /
+// l2 = 0, any context (fast_tables.hpp BoundWindow).  That candidate is at most every candidate it replaces, so by
+// induction over the cells the value is at most the packed instance's: a lower bound all the same.
+// The scan enters the unrolled chunks at the chunk of row i-F's first slot (a scalar); slots of higher rows in that chunk
+// are visited exactly, which cannot lower the value below the far candidate's.  The empty slot word carries 0x7fff in
+// its field here: its candidate stays 0 (never the maximum), and the fold below leaves farmin alone for it.
+static_assert(MSSPE_BWN13_KC == MSSPE_BPK13_KC && MSSPE_BWN13_W0 == MSSPE_BPK13_W0, "one register map for both packed scans");
+static constexpr int kWinF = MSSPE_BWN13_F;
+static constexpr int kWinNone = BoundPacked::kFieldMax;   // farmin without a cell (BoundWindow: no real field reaches it)
+static constexpr int kWinVoid = kPkYVoid;                 // a void Ifar / Bfar, and the far candidate of an empty far set
+static_assert(kWinVoid == BoundWindow::kVoid, "the host's void constant is the kernel's");
+static_assert(kWinVoid - kPkReach - kPkReach > kPkReach, "a far candidate that holds a void stays above every left end term");
+
+static __device__ __forceinline__ void window_scan(const v32i Wa, const v16i Wb, const v4i Wc, unsigned C, int Y, int n_far,
+                                                int n_run, int near_from, int start, int &acc_far, int &acc_near)
+{
+    int MSSPE_BWN13_TEMP_NAMES;
+    asm volatile(MSSPE_BWN13_SCAN_ASM
+                 : MSSPE_BWN13_ACC_OUT(acc_far, acc_near), MSSPE_BWN13_TEMPS_OUT
+                 : [C] "v"(C), [Y] "v"(Y), [NFAR] "s"(n_far), [NRUN] "s"(n_run), [NEAR] "s"(near_from), [START] "s"(start),
+                   [TOFF] "n"((int)offsetof(SharedRow, T)), MSSPE_BWN13_TUPLES_IN(Wa, Wb, Wc)
+                 : MSSPE_BWN13_SCAN_CLOBBERS);
+}
+// slot: wave-uniform, < kRowSlots.  farmin = min(farmin, the slot's field); bit 15 of the word is zero.  The word is
+// fetched with the indexed v_mov the compiler itself emits for a register array: a v_min_u16 that read the indexed
+// register directly returned wrong minima for a few pairs per plane on the MI355X (two instructions per slot instead
+// of one, once per slot and pair).
+static __device__ __forceinline__ void window_fold(const v32i Wa, const v16i Wb, const v4i Wc, int slot, int &farmin)
+{
+    int w;
+    asm volatile("s_set_gpr_idx_on %[SLOT], gpr_idx(SRC0)\n\t"
+                 "v_mov_b32 %[W], v%c[W0]\n\t"
+                 "s_set_gpr_idx_off"
+                 : [W] "=v"(w)
+                 : [SLOT] "s"(slot), [W0] "n"(MSSPE_BWN13_W0), MSSPE_BWN13_TUPLES_IN(Wa, Wb, Wc)
+                 : "m0");
+    farmin = min(farmin, w & 0xffff);
+}
+
 // run_pair_bound on the packed table: the minimum over the lane's cells of (cell value + right end term) in coarse
 // units; kPkInit: the pair has no cell.  bias: BoundPacked::bias (wave-uniform).
-template <int NS>
-static __device__ __forceinline__ int run_pair_packed(SharedRow &sh, const SeqPair &q, bool active, unsigned wmax4, int bias)
+// WIN: the windowed instance (rows above the window: the far candidate; ifar, bfar: wave-uniform, kWinVoid where void).
+template <int NS, bool WIN = false>
+static __device__ __forceinline__ int run_pair_packed(SharedRow &sh, const SeqPair &q, bool active, unsigned wmax4, int bias,
+                                                   int ifar = 0, int bfar = 0)
 {
     static_assert(kPin && NS == 52, "the bound instance exists for 13 bases");
     constexpr int kC4 = MSSPE_BPK13_KC;
-    v32i Wa = kEmptyRowK << 17;
-    v16i Wb = kEmptyRowK << 17;
-    v4i Wc = kEmptyRowK << 17;
+    constexpr int kEmptyW = (kEmptyRowK << 17) | (WIN ? kWinNone : 0);
+    v32i Wa = kEmptyW;
+    v16i Wb = kEmptyW;
+    v4i Wc = kEmptyW;
     CellCtx c;
     const int kc = 0x7fff - bias + kPkOff;   // u + Tn = kc - (entry + predecessor's value)
     int pick = kPkInit;
     int slot_ = 0, start_im1 = 0;   // first slot of row i-1
+    int farmin = kWinNone;          // WIN: the smallest field of the rows <= i-1-F
+    int start_w[kWinF + 1] = {};    // WIN: [d] first slot of row i-1-d
     for (int i_ = 0; i_ < q.len; ++i_) {
       const int im1 = __builtin_amdgcn_readfirstlane(i_);
       const int a_row = (int)((q.s1 >> (2 * im1)) & 3u);
@@ -880,6 +927,11 @@ static __device__ __forceinline__ int run_pair_packed(SharedRow &sh, const SeqPa
       const int row_start = __builtin_amdgcn_readfirstlane(slot_);
       const bool stored = im1 < q.len - 1;   // wave-uniform: the cells of the last row are nobody's predecessors
       unsigned mrem = active ? spaced_mask(q.s2, 3 - a_row, q.lenmask) : 0u;
+      if constexpr (WIN) {
+        // row i-1-F leaves the window: its slots join farmin, once per slot (wave-uniform bounds)
+        for (int s_ = start_w[kWinF]; s_ < start_w[kWinF - 1]; ++s_)
+          window_fold(Wa, Wb, Wc, __builtin_amdgcn_readfirstlane(s_), farmin);
+      }
       for (int c_ = 0; c_ < w_row; ++c_, slot_ += stored ? 1 : 0) {
         const int slot = __builtin_amdgcn_readfirstlane(slot_);
         const bool in = mrem != 0u;
@@ -888,18 +940,31 @@ static __device__ __forceinline__ int run_pair_packed(SharedRow &sh, const SeqPa
         const unsigned C = ((unsigned)((jm1 - 1) * kRowA + im1 * (4 * (kRowR + 1)) + 3) << 17) | 0x7fffu;
         const int yTS = sh.yts[(im1 << 2) | (int)(((q.s2 << 2) >> (2 * jm1)) & 3u)];
         int acc_far, acc_near;
-        packed_scan(Wa, Wb, Wc, C, yTS, start_im1 / kC4, (row_start + kC4 - 1) / kC4, start_im1, acc_far, acc_near);
+        if constexpr (WIN)
+          window_scan(Wa, Wb, Wc, C, yTS, start_im1 / kC4, (row_start + kC4 - 1) / kC4, start_im1, start_w[kWinF - 1] / kC4,
+                      acc_far, acc_near);
+        else packed_scan(Wa, Wb, Wc, C, yTS, start_im1 / kC4, (row_start + kC4 - 1) / kC4, start_im1, acc_far, acc_near);
         const CellBases b = cell_bases(q, im1, jm1, c);
         const int gL = sh.g[b.idxL - kRowGBase], gR = sh.g[b.idxR - kRowGBase];
         // the far minimum takes the cell-side term here, once; an accumulator without a real candidate decodes far above gL
-        const int G0 = min(gL, min(kc - acc_far + yTS, kc - acc_near));
+        int G0 = min(gL, min(kc - acc_far + yTS, kc - acc_near));
+        if constexpr (WIN) {
+          // the rows above the window: one candidate (a void yTS is kPkYVoid: the bulge constant alone is left)
+          const int far = farmin >= kWinNone ? kWinVoid : farmin - bias + min(bfar, ifar + yTS);
+          G0 = min(G0, far);
+        }
         pick = in ? min(pick, G0 + gR) : pick;
         // G0 + bias is a 15-bit field: BoundPacked's proven range [lo, hi] of every publishable value (a lane without a
         // cell here publishes an empty slot: its word fails every geometry test)
-        const int Wcell = in ? ((int)((unsigned)(jm1 * kRowA + (im1 << 2) + ((b.po_c >> 4) & 3)) << 17) + (G0 + bias)) : (kEmptyRowK << 17);
+        const int Wcell = in ? ((int)((unsigned)(jm1 * kRowA + (im1 << 2) + ((b.po_c >> 4) & 3)) << 17) + (G0 + bias)) : kEmptyW;
         if (slot < NS) packed_publish(Wa, Wb, Wc, slot, Wcell);
       }
       start_im1 = row_start;
+      if constexpr (WIN) {
+#pragma unroll
+        for (int d = kWinF; d > 0; --d) start_w[d] = start_w[d - 1];
+        start_w[0] = row_start;
+      }
     }
     return pick;
 }
@@ -963,11 +1028,15 @@ static __device__ __forceinline__ void build_bound_table(SharedRow &sh, const In
 // One lock-step DP of the wave: lane = (row, col), all lanes share `row`.
 // twin (BOUND, mirror mode only): the pair stands for (col, row) as well -- what is appended is appended in both orders.
 // PACKED (with BOUND): the packed instance's cell loop and units; everything around it is the bound instance's.
-template <int NS, bool BOUND = false, bool PACKED = false>
+// WIN (with PACKED): the windowed instance (k_pairs_bound_window).  Its value is below the packed one's, so a lane it does
+// not cull is not a survivor of the bound yet: it goes to list U like an unbounded lane, where the exact-unit bound of
+// k_pairs_bound_list decides (a launch WITHOUT list U is refused by launch_pairs_bound).
+template <int NS, bool BOUND = false, bool PACKED = false, bool WIN = false>
 static __device__ __forceinline__ void wave_pairs_row(SharedRow &sh, const IntArgs &a, int row, int col, uint64_t pa,
                                                uint64_t pb, bool inside, bool twin = false)
 {
     static_assert(BOUND || !PACKED, "the packed instance is a bound instance");
+    static_assert(PACKED || !WIN, "the windowed instance is a packed instance");
     const int lane = threadIdx.x & 63;
     SeqPair q;
     unsigned rowmask;
@@ -1045,7 +1114,11 @@ static __device__ __forceinline__ void wave_pairs_row(SharedRow &sh, const IntAr
         if (__ballot(active) != 0ull) {   // wave-uniform
             const unsigned wmax4 = (unsigned)w4[0] | ((unsigned)w4[1] << 8) | ((unsigned)w4[2] << 16) | ((unsigned)w4[3] << 24);
             int pick;
-            if constexpr (PACKED) pick = run_pair_packed<NS>(sh, q, active, wmax4, __builtin_amdgcn_readfirstlane(a.packed_bias));
+            if constexpr (WIN)
+                pick = run_pair_packed<NS, true>(sh, q, active, wmax4, __builtin_amdgcn_readfirstlane(a.packed_bias),
+                                                 __builtin_amdgcn_readfirstlane(a.window_ifar),
+                                                 __builtin_amdgcn_readfirstlane(a.window_bfar));
+            else if constexpr (PACKED) pick = run_pair_packed<NS>(sh, q, active, wmax4, __builtin_amdgcn_readfirstlane(a.packed_bias));
             else pick = run_pair_bound<NS>(sh, q, active, wmax4);
             const int lb = pick + a.bt->init;   // a lane without a chain keeps kBndInit (kPkInit): above every cut
             if (a.bound_plane) {
@@ -1057,8 +1130,13 @@ static __device__ __forceinline__ void wave_pairs_row(SharedRow &sh, const IntAr
                 const bool survivor = active & (lb <= a.bt->cut);   // a culled pair is finished: no bit, no count
                 const unsigned long long sm = __ballot(survivor);
                 const unsigned long long sm2 = __ballot(survivor & twin);   // ordered pairs: a mirrored survivor counts for both
-                if (lane == 0 && sm) atomicAdd(a.bound_survivors, (unsigned long long)(__popcll(sm) + __popcll(sm2)));
-                spill |= survivor;
+                if constexpr (WIN) {   // not culled by the relaxed value: list U's exact-unit bound is next, once per unordered pair
+                    if (lane == 0 && sm) atomicAdd(a.window_survivors, (unsigned long long)(__popcll(sm) + __popcll(sm2)));
+                    unbounded |= survivor;
+                } else {
+                    if (lane == 0 && sm) atomicAdd(a.bound_survivors, (unsigned long long)(__popcll(sm) + __popcll(sm2)));
+                    spill |= survivor;
+                }
             }
         }
         if (a.bound_plane) {
@@ -1220,7 +1298,7 @@ static __device__ __forceinline__ void build_row_table(SharedRow &sh, const IntA
 
 // NT: the block's threads.  The packed bound instance (PACKED) runs 1,024 over the SAME SharedRow, whose per-thread
 // arrays are sized for kRowThreads: like every bound instance it touches g, yts, T, next_group and item only.
-template <int NS, bool BOUND = false, bool PACKED = false, int NT = kRowThreads>
+template <int NS, bool BOUND = false, bool PACKED = false, int NT = kRowThreads, bool WIN = false>
 static __device__ __forceinline__ void kernel_body(const IntArgs &a)
 {
     static_assert(NT == kRowThreads || PACKED, "the exact instances index SharedRow's per-thread arrays");
@@ -1292,7 +1370,7 @@ static __device__ __forceinline__ void kernel_body(const IntArgs &a)
             const bool inside = cq < a.f.col1 && !(mirror && cq < row_q);   // (the row's own group: the lanes left of the diagonal)
             const uint64_t pb = a.f.cols_sorted[inside ? cq : a.f.col0];
             const int col = (int)a.f.perm[inside ? cq : a.f.col0];
-            wave_pairs_row<NS, BOUND, PACKED>(sh, a, row, col, pa, pb, inside, mirror && cq != row_q);
+            wave_pairs_row<NS, BOUND, PACKED, WIN>(sh, a, row, col, pa, pb, inside, mirror && cq != row_q);
         }
         __syncthreads();   // every wave is done with the table (and with sh.item) before the next item
     }
@@ -1322,11 +1400,20 @@ __global__ void __launch_bounds__(RK::kRowThreads) k_pairs_bound(IntArgs a)
 
 // The packed bound instance: one register per slot (the value in the slot word's 15-bit field, coarse units), so that
 // 1,024 threads -- four waves per SIMD -- fit the register file.
+constexpr int kWindowF = MSSPE_BWN13_F;   // rows of the windowed instance's window (the generator's parameter)
 constexpr int kPackedThreads = 1024;   // (the 768-thread form of the same kernel measured no faster than k_pairs_bound: DESIGN 4.0)
 template <class RK, int NT>
 __global__ void __launch_bounds__(NT) k_pairs_bound_packed(IntArgs a)
 {
     RK::template kernel_body<RK::kRowSlots, true, true, NT>(a);
+}
+
+// The windowed packed instance: the same tables, slot words and block, but a cell scans the rows of its window only and
+// takes one candidate for everything above (run_pair_packed<NS, true>); what it does not cull goes to list U.
+template <class RK, int NT>
+__global__ void __launch_bounds__(NT) k_pairs_bound_window(IntArgs a)
+{
+    RK::template kernel_body<RK::kRowSlots, true, true, NT, true>(a);
 }
 
 }  // namespace
@@ -1397,6 +1484,10 @@ hipError_t pairs_row_lds_reads_zero(hipStream_t stream, int n_cu, bool *ok)
             return hipSuccess;
         // ... and the packed bound instance's (another block size over the same allocation)
         if (hipFuncGetAttributes(&fb, (const void *)k_pairs_bound_packed<Row13, kPackedThreads>) != hipSuccess ||
+            fb.sharedSizeBytes != fp.sharedSizeBytes)
+            return hipSuccess;
+        // ... and the windowed instance's
+        if (hipFuncGetAttributes(&fb, (const void *)k_pairs_bound_window<Row13, kPackedThreads>) != hipSuccess ||
             fb.sharedSizeBytes != fp.sharedSizeBytes)
             return hipSuccess;
         if (offsetof(Row13::SharedRow, T) + (size_t)Row13::kRowWrapMin < (fa.sharedSizeBytes + 1279) / 1280 * 1280) return hipSuccess;
@@ -1477,18 +1568,23 @@ hipError_t launch_pairs_row(const PairKernelArgs &a, const IntTables *it, unsign
 }
 
 int pairs_bound_max_k() { return Row13::kRowK; }
+int pairs_bound_window_rows() { return kWindowF; }
 
 // The bound first stage (k_pairs_bound): launch_pairs_row's contract, but a pair is either proven not to conflict
 // (nothing is written for it) or appended to a.overflow_list.  bound_plane != nullptr: the diagnostic form, which writes
 // the bound of every pair of the block (cal/mol; +inf: no chain; -inf: not bounded here) and nothing else.
 hipError_t launch_pairs_bound(const PairKernelArgs &a, const IntTables *it, const BoundTables *bt,
                               unsigned long long *survivors, double *bound_plane, int n_cu, hipStream_t stream, bool mirror,
-                              uint2 *ulist, uint32_t *ucount, const BoundTables *packed_q, int packed_bias, int packed_shift)
+                              uint2 *ulist, uint32_t *ucount, const BoundTables *packed_q, int packed_bias, int packed_shift,
+                              const BoundWindow *window, unsigned long long *window_survivors)
 {
     if (a.k > Row13::kRowK || a.k < 2 || !bt || (!survivors && !bound_plane) || (ulist && !ucount)) return hipErrorInvalidValue;
     // packed_q: BoundPacked::q on the device -- the packed instance runs (same contract, coarse units)
     if (packed_q && (packed_shift < BoundPacked::kShiftMin || packed_shift > BoundPacked::kShiftMax || packed_bias < 0 ||
                      packed_bias >= BoundPacked::kReach))
+        return hipErrorInvalidValue;
+    // window: the windowed instance runs on the packed tables; what it leaves must have list U to go to
+    if (window && (!packed_q || !window->usable || window->F != kWindowF || (!bound_plane && (!ulist || !window_survivors))))
         return hipErrorInvalidValue;
     // mirror: rows are sorted positions and a row's columns start at itself, so the rows must lie inside the columns
     if (mirror && (bound_plane || a.col0 != 0 || a.row0 < 0 || a.row1 > a.col1)) return hipErrorInvalidValue;
@@ -1529,6 +1625,13 @@ hipError_t launch_pairs_bound(const PairKernelArgs &a, const IntTables *it, cons
         x.bt = packed_q;
         x.packed_bias = packed_bias;
         x.packed_unit = (double)(1 << (packed_shift - BoundPacked::kShiftMin));
+        if (window) {
+            x.window_ifar = window->ifar;
+            x.window_bfar = window->bfar;
+            x.window_survivors = window_survivors;
+            hipLaunchKernelGGL((k_pairs_bound_window<Row13, kPackedThreads>), dim3(grid), dim3(kPackedThreads), 0, stream, x);
+            return hipGetLastError();
+        }
         hipLaunchKernelGGL((k_pairs_bound_packed<Row13, kPackedThreads>), dim3(grid), dim3(kPackedThreads), 0, stream, x);
         return hipGetLastError();
     }

@@ -16,7 +16,7 @@ EXPORTS = [
     "msspe_last_error", "msspe_version", "msspe_set_option", "msspe_get_info", "msspe_kmer_trace", "msspe_set_stream", "msspe_reset_stream",
     "msspe_synchronize",
     "msspe_pack_oligos", "msspe_unpack_oligo", "msspe_cross_dimer_dev", "msspe_cross_dimer",
-    "msspe_cross_dimer_edges_dev", "msspe_cross_dimer_edges", "msspe_cross_dimer_bound_dev", "msspe_cross_dimer_bound_list_dev", "msspe_cross_dimer_bound_packed_dev", "msspe_host_bound_tables", "msspe_host_bound_packed", "msspe_host_bound_mirror_ok",
+    "msspe_cross_dimer_edges_dev", "msspe_cross_dimer_edges", "msspe_cross_dimer_bound_dev", "msspe_cross_dimer_bound_list_dev", "msspe_cross_dimer_bound_packed_dev", "msspe_cross_dimer_bound_window_dev", "msspe_host_bound_tables", "msspe_host_bound_packed", "msspe_host_bound_window", "msspe_host_bound_mirror_ok",
     "msspe_cross_dimer_ab_dev", "msspe_cross_dimer_ab_edges_dev", "msspe_cross_dimer_ab", "msspe_cross_dimer_ab_edges",
     "msspe_cross_dimer_edges_mixed",
     "msspe_cross_dimer_end_dev", "msspe_cross_dimer_end", "msspe_cross_dimer_end_edges_dev", "msspe_cross_dimer_end_edges",
@@ -199,6 +199,8 @@ def load_library() -> C.CDLL:
                                               C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.msspe_cross_dimer_bound_list_dev.argtypes = L.msspe_cross_dimer_bound_dev.argtypes
     L.msspe_cross_dimer_bound_packed_dev.argtypes = L.msspe_cross_dimer_bound_dev.argtypes
+    L.msspe_cross_dimer_bound_window_dev.argtypes = L.msspe_cross_dimer_bound_dev.argtypes
+    L.msspe_host_bound_window.argtypes = [C.c_char_p, C.POINTER(Chem), C.c_float, C.POINTER(C.c_int32)]
     L.msspe_host_bound_packed.argtypes = [C.c_char_p, C.POINTER(Chem), C.c_float, vp, vp, C.POINTER(C.c_int32)]
     L.msspe_host_bound_tables.argtypes = [C.c_char_p, C.POINTER(Chem), C.c_float, vp, vp, C.POINTER(C.c_int32)]
     L.msspe_host_bound_mirror_ok.argtypes = [C.c_char_p, C.POINTER(Chem), C.c_float, C.POINTER(C.c_int32)]
@@ -448,6 +450,19 @@ def host_bound_tables(params_path: str | None = None, chem: Chem | None = None, 
     return {"g": g, "T": T, **dict(zip(keys, list(info)))}
 
 
+def host_bound_window(params_path: str | None = None, chem: Chem | None = None, threshold: float = -9000.0) -> dict:
+    """The windowed packed instance's constants (option pair_bound_window; no device needed): msspe_host_bound_window.
+    F: rows a cell scans exactly; ifar / bfar: the smallest finite entry of host_bound_packed's T over l1 >= F with
+    l2 >= 1 / l2 = 0, `void` where there is none."""
+    info = (C.c_int32 * 8)()
+    chem = chem or Chem.ntthal()
+    rc = load_library().msspe_host_bound_window(str(params_path).encode() if params_path else None, C.byref(chem),
+                                                C.c_float(threshold), info)
+    if rc:
+        raise MsspeError(rc, f"msspe_host_bound_window({params_path})")
+    return dict(zip(("usable", "F", "ifar", "bfar", "void"), list(info)))
+
+
 def host_bound_packed(params_path: str | None = None, chem: Chem | None = None, threshold: float = -9000.0) -> dict:
     """The packed bound instance's tables (option pair_bound_packed; no device needed): msspe_host_bound_packed.
     g / T: host_bound_tables' entries floored to units of 2**(shift - 6) cal/mol, void entries as they are; a cell
@@ -636,6 +651,14 @@ class Engine:
         """Diagnostic (tests, debugging): the bound first stage's value of every pair of the block, float64 cal/mol
         into the caller's plane (+inf: no chain; -inf: not bounded there); asynchronous.  msspe_cross_dimer_bound_dev."""
         self._check(self.L.msspe_cross_dimer_bound_dev(
+            self.ptr, C.c_void_p(d_pool), n, k, C.byref(chem), C.c_float(threshold), rows[0], rows[1], cols[0],
+            cols[1], C.c_void_p(d_bound)))
+
+    def cross_dimer_bound_window_dev(self, d_pool: int, n: int, k: int, chem: Chem, threshold: float,
+                                     rows: tuple[int, int], cols: tuple[int, int], d_bound: int):
+        """cross_dimer_bound_packed_dev's plane from the windowed instance (option pair_bound_window): multiples of the
+        same unit, at most the packed instance's values.  msspe_cross_dimer_bound_window_dev."""
+        self._check(self.L.msspe_cross_dimer_bound_window_dev(
             self.ptr, C.c_void_p(d_pool), n, k, C.byref(chem), C.c_float(threshold), rows[0], rows[1], cols[0],
             cols[1], C.c_void_p(d_bound)))
 
@@ -1377,6 +1400,8 @@ class Engine:
         # ordered pairs it could not cull and appended to list 0
         out["bound_list_pairs"] = self.info("bound_list_pairs")
         out["bound_list_survivors"] = self.info("bound_list_survivors")
+        # ordered pairs the windowed first stage (option pair_bound_window) could not cull and sent to list U
+        out["bound_window_survivors"] = self.info("bound_window_survivors")
         return out
 
     # ---- stage B ---------------------------------------------------------------------------

@@ -22,7 +22,20 @@ the waits are counted: s_waitcnt lgkmcnt(reads of the newer chunk).  The code is
 another chunk behind it -- nearly every chunk of a scan -- runs in a straight line: two tests, no branch taken.  With
 the kinds dispatched by taken branches at every chunk the same kernel ran 9 % slower.
 usage: tools/gen_row_bound_packed_asm.py > open-msspe-design_amd/csrc/row_bound_packed_pinned.inc
+
+--window F: the WINDOWED instance's scan (k_pairs_bound_window; row_bound_window_pinned.inc, macros MSSPE_BWN13_*).  The
+same chunks, kinds and waits, but the scan of a cell in row i ENTERS the unrolled sequence at the chunk %[START] that
+holds the first slot of row i - F (a scalar: a wave holds one composition) instead of at chunk 0: a tree of scalar
+compares leads to that chunk's issue, which joins the straight line.  Everything above the window is the kernel's one
+far candidate (thal_pairs_row.hip run_pair_packed); F itself only reaches the kernel, as MSSPE_BWN13_F.
+usage: tools/gen_row_bound_packed_asm.py --window 2 > open-msspe-design_amd/csrc/row_bound_window_pinned.inc
 """
+import sys
+
+WINDOW = int(sys.argv[2]) if len(sys.argv) == 3 and sys.argv[1] == "--window" else 0
+if (len(sys.argv) != 1 and not WINDOW) or WINDOW not in (0, 2, 3):
+    sys.exit(__doc__)
+PFX = "MSSPE_BWN13" if WINDOW else "MSSPE_BPK13"
 KC = 4   # slots per chunk (6 and 8 measured slower: DESIGN 4.0)
 NS, W0, ACCF, ACCN = 52, 76, 74, 75
 TUPLES = [(76, 32), (108, 16), (124, 4)]
@@ -92,9 +105,27 @@ def scan_asm():
 
     a(f"v_mov_b32 v{ACCF}, 0")
     a(f"v_mov_b32 v{ACCN}, 0")
-    a("s_cmp_gt_i32 %[NRUN], 0")
-    a("s_cbranch_scc0 Ldone%=")
-    chunk_issue(0)
+    if WINDOW:
+        # the entry: chunk %[START] .. %[NRUN] - 1 run (none: START >= NRUN); a leaf issues its chunk and joins the line
+        def enter(lo, hi):
+            if lo == hi:
+                chunk_issue(lo)
+                a(f"s_branch Lc{lo}_%=")
+                return
+            mid = (lo + hi + 1) // 2
+            a(f"s_cmp_lt_i32 %[START], {mid}")
+            a(f"s_cbranch_scc0 Le{mid}_{hi}_%=")
+            enter(lo, mid - 1)
+            a(f"Le{mid}_{hi}_%=:")
+            enter(mid, hi)
+
+        a("s_cmp_gt_i32 %[NRUN], %[START]")
+        a("s_cbranch_scc0 Ldone%=")
+        enter(0, nch - 1)
+    else:
+        a("s_cmp_gt_i32 %[NRUN], 0")
+        a("s_cbranch_scc0 Ldone%=")
+        chunk_issue(0)
     # ---- the straight line: a far chunk with another chunk behind it.  The next chunk's reads are issued first, the
     #      wait is for this chunk's alone, and no branch is taken
     for pc in range(nch - 1):
@@ -123,18 +154,20 @@ def scan_asm():
     return L
 
 
-print("// GENERATED by tools/gen_row_bound_packed_asm.py -- do not edit (see that file for the why and the register map)")
-print(f"#define MSSPE_BPK13_KC {KC}")
-print(f"#define MSSPE_BPK13_W0 {W0}")
-print("#define MSSPE_BPK13_SCAN_ASM \\")
+print(f"// GENERATED by tools/gen_row_bound_packed_asm.py{f' --window {WINDOW}' if WINDOW else ''} -- do not edit (see that file for the why and the register map)")
+if WINDOW:
+    print(f"#define {PFX}_F {WINDOW}")
+print(f"#define {PFX}_KC {KC}")
+print(f"#define {PFX}_W0 {W0}")
+print(f"#define {PFX}_SCAN_ASM \\")
 print(" \\\n".join('    "' + l + '\\n\\t"' for l in scan_asm()))
-print('#define MSSPE_BPK13_SCAN_CLOBBERS "vcc", "scc", "memory"')
+print(f'#define {PFX}_SCAN_CLOBBERS "vcc", "scc", "memory"')
 temps = [f"a{e}" for e in range(KC)] + [f"t{e}" for e in range(KC)] + [f"v{e}" for e in range(2 * KC)] + ["yt"]
-print("#define MSSPE_BPK13_TEMP_NAMES " + ", ".join(temps))
-print("#define MSSPE_BPK13_TEMPS_OUT " + ", ".join(f'[{t}] "=&v"({t})' for t in temps))
-print(f'#define MSSPE_BPK13_ACC_OUT(far, near) "=&{{v{ACCF}}}"(far), "=&{{v{ACCN}}}"(near)')
+print(f"#define {PFX}_TEMP_NAMES " + ", ".join(temps))
+print(f"#define {PFX}_TEMPS_OUT " + ", ".join(f'[{t}] "=&v"({t})' for t in temps))
+print(f'#define {PFX}_ACC_OUT(far, near) "=&{{v{ACCF}}}"(far), "=&{{v{ACCN}}}"(near)')
 names = ["Wa", "Wb", "Wc"]
-print("#define MSSPE_BPK13_TUPLES_IN(" + ", ".join(names) + ") " +
+print(f"#define {PFX}_TUPLES_IN(" + ", ".join(names) + ") " +
       ", ".join('"{v[%d:%d]}"(%s)' % (r0, r0 + ln - 1, nm) for (r0, ln), nm in zip(TUPLES, names)))
-print("#define MSSPE_BPK13_TUPLES_INOUT(" + ", ".join(names) + ") " +
+print(f"#define {PFX}_TUPLES_INOUT(" + ", ".join(names) + ") " +
       ", ".join('"+{v[%d:%d]}"(%s)' % (r0, r0 + ln - 1, nm) for (r0, ln), nm in zip(TUPLES, names)))
