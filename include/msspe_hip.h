@@ -114,6 +114,9 @@ const char *msspe_version(void);
  *                                 (8192); a call that needs more returns MSSPE_ERR_CAPACITY
  *   "thin_thal_unique" "0" | "1"  msspe_panel_thin_thal*: score each distinct (primer, template) pair of a slab once
  *                                 (1) or every match (0); no result depends on it
+ *   "conflict_graph_block_rows" "0" | a positive number  msspe_conflict_graph* under both rules: rows per block of
+ *                                 the two per-rule planes in the context's scratch (0, auto: as many as keep both
+ *                                 planes within 64 MB); no result depends on it
  *   "split_lanes"    "0" | "2" | "4" | "8"
  *   "split_list"     "0" | "1"    short oligos: tables too large for the integer list stage go to the split-table
  *                                 kernel's list mode (1) or straight to the f64 kernels (0)
@@ -410,6 +413,75 @@ int msspe_cross_dimer_end_ab(msspe_ctx *ctx, const char *a_ascii, int n_a, int k
                              int k_b, const msspe_chem *chem, float tm_threshold, uint32_t *row_conflicts,
                              uint64_t *bitmap, double *dg, double *tm);
 
+/* ---- the conflict graph under a pair of rules: thal ANY on dG and / or thal END1 on t ---- */
+
+/*
+ * A pair conflicts when at least one enabled rule says so.  Each rule's decision is exactly that of its screen on the
+ * same block under the same chemistry and threshold: use_any -- msspe_cross_dimer*'s with dg_threshold; use_end --
+ * msspe_cross_dimer_end*'s with end_tm_threshold, the row being oligo 1 (the anchored 3' end).
+ */
+typedef struct {
+    int   use_any;  float dg_threshold;       /* thal ANY, msspe_cross_dimer*'s decision            */
+    int   use_end;  float end_tm_threshold;   /* thal END1, msspe_cross_dimer_end*'s decision; row = oligo 1 */
+} msspe_conflict_rule;
+#define MSSPE_KIND_ANY 1u
+#define MSSPE_KIND_END 2u
+typedef struct { uint32_t a, b, kinds, reserved; } msspe_kind_edge;   /* reserved = 0 */
+
+/*
+ * The block [row0,row1) x [col0,col1) of one pool under the rule.  Outputs (device pointers, each may be NULL):
+ *   d_row_conflicts  uint32[n]   [r] += the set bits of row r in the block; a pair under both rules counts once
+ *   d_bitmap         uint64[(row1-row0) * ceil((col1-col0)/64)], the block layout of msspe_cross_dimer_dev: cleared by
+ *                    the call, then written; words outside the block are not touched.  As in msspe_cross_dimer_dev the
+ *                    block's words are cleared whole, so the padding bits of a row's last word end as 0.
+ *   d_kind_counts    uint64[3]   += the block's pairs that are ANY only, END only, and both
+ * use_any && !use_end: bit for bit the bitmap and counts of a decisions-only msspe_cross_dimer_dev -- with a bitmap or
+ * without kind counts the call IS that screen on the caller's buffers (same route, every option applies);
+ * !use_any && use_end: those of msspe_cross_dimer_end_dev, likewise.  With both rules the two per-rule bitmaps live in
+ * context-owned scratch, a block of rows at a time: msspe_set_option "conflict_graph_block_rows" (0 = auto: as many
+ * rows as keep both planes within 64 MB; any positive value is honoured).  Results do not depend on it, and once the
+ * scratch has grown to a call's size no further allocation happens (msspe_get_info "conflict_graph_grows" counts
+ * them).  Enqueues on the context's stream; synchronises no more than the two screens do.
+ * Errors: a NULL rule, a NULL chem or both flags zero: MSSPE_ERR_ARG; every other argument status is that of
+ * msspe_cross_dimer_dev.  n == 0 or an empty block: MSSPE_OK, nothing written.
+ */
+int msspe_conflict_graph_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const msspe_chem *chem,
+                             const msspe_conflict_rule *rule, int row0, int row1, int col0, int col1,
+                             uint32_t *d_row_conflicts, uint64_t *d_bitmap, uint64_t *d_kind_counts);
+/* Pool A (rows; oligo 1 of the END rule) against pool B (columns), lengths 2..32 and free to differ: the staging and
+ * block conventions of msspe_cross_dimer_ab_dev. */
+int msspe_conflict_graph_ab_dev(msspe_ctx *ctx, const uint64_t *d_a, int n_a, int k_a, const uint64_t *d_b, int n_b,
+                                int k_b, const msspe_chem *chem, const msspe_conflict_rule *rule, int row0, int row1,
+                                int col0, int col1, uint32_t *d_row_conflicts, uint64_t *d_bitmap,
+                                uint64_t *d_kind_counts);
+/* The block as an edge list: every set bit as (a, b, kinds) in ascending (a, b) order -- the kernel produces the order
+ * itself, nothing is sorted afterwards.  *d_count = the number of edges of the block, cleared by the call; it may
+ * exceed `capacity`, in which case d_edges holds the first `capacity` edges of the order and nothing is written
+ * behind them.  Edges carry no dG or t: the single-rule edge screens give values.  d_row_conflicts, d_bitmap and
+ * d_kind_counts optional, as above.  A NULL d_count, or a capacity without a buffer: MSSPE_ERR_ARG. */
+int msspe_conflict_graph_edges_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const msspe_chem *chem,
+                                   const msspe_conflict_rule *rule, int row0, int row1, int col0, int col1,
+                                   uint32_t *d_row_conflicts, uint64_t *d_bitmap, uint64_t *d_kind_counts,
+                                   msspe_kind_edge *d_edges, uint64_t capacity, uint64_t *d_count);
+int msspe_conflict_graph_ab_edges_dev(msspe_ctx *ctx, const uint64_t *d_a, int n_a, int k_a, const uint64_t *d_b,
+                                      int n_b, int k_b, const msspe_chem *chem, const msspe_conflict_rule *rule,
+                                      int row0, int row1, int col0, int col1, uint32_t *d_row_conflicts,
+                                      uint64_t *d_bitmap, uint64_t *d_kind_counts, msspe_kind_edge *d_edges,
+                                      uint64_t capacity, uint64_t *d_count);
+/* Host pool, whole n x n: row_conflicts[n], bitmap[n * ceil(n/64)] and kind_counts[3] are host buffers, each optional,
+ * and are assigned (not added to).  Non-ACGT: MSSPE_ERR_ARG. */
+int msspe_conflict_graph(msspe_ctx *ctx, const char *pool_ascii, int n, int k, const msspe_chem *chem,
+                         const msspe_conflict_rule *rule, uint32_t *row_conflicts, uint64_t *bitmap,
+                         uint64_t *kind_counts);
+/* Host edge lists, whole pool(s), ascending (a, b).  *count_out = the number of edges; above `capacity` the call
+ * returns MSSPE_ERR_CAPACITY with the first `capacity` edges filled in, so the caller can retry with count_out. */
+int msspe_conflict_graph_edges(msspe_ctx *ctx, const char *pool_ascii, int n, int k, const msspe_chem *chem,
+                               const msspe_conflict_rule *rule, msspe_kind_edge *edges, uint64_t capacity,
+                               uint64_t *count_out);
+int msspe_conflict_graph_ab_edges(msspe_ctx *ctx, const char *a_ascii, int n_a, int k_a, const char *b_ascii, int n_b,
+                                  int k_b, const msspe_chem *chem, const msspe_conflict_rule *rule,
+                                  msspe_kind_edge *edges, uint64_t capacity, uint64_t *count_out);
+
 /* ---- the greedy vertex cover of the conflict graph (replaces vertex_cover, od-msspe/src/main.rs:754-798) ---- */
 
 /*
@@ -436,6 +508,13 @@ int msspe_conflict_cover_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int 
 int msspe_conflict_cover(msspe_ctx *ctx, const char *pool_ascii, int n, int k,
                          const msspe_chem *chem, float dg_threshold, int drop_self_pairs,
                          uint8_t *deleted_out, int *n_deleted_out);
+/* msspe_conflict_cover with the rule in place of dg_threshold: the pool is screened with msspe_conflict_graph_dev
+ * (bitmap only) and the bitmap handed to msspe_conflict_cover_dev.  That form symmetrises to S = B | B^T, so with the END
+ * rule two primers are neighbours when either order conflicts under ANY or either 3' end is caught (END1 or END2).
+ * drop_self_pairs clears the same pairs: (a, a) and (a, revcomp a).  A NULL rule or both flags zero: MSSPE_ERR_ARG. */
+int msspe_conflict_cover_rule(msspe_ctx *ctx, const char *pool_ascii, int n, int k, const msspe_chem *chem,
+                              const msspe_conflict_rule *rule, int drop_self_pairs, uint8_t *deleted_out,
+                              int *n_deleted_out);
 
 /* ---- the conflict graph split into reaction tubes (engine extension, no reference counterpart) ---- */
 
@@ -468,6 +547,10 @@ int msspe_conflict_tubes_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int 
 int msspe_conflict_tubes(msspe_ctx *ctx, const char *pool_ascii, int n, int k, const msspe_chem *chem,
                          float dg_threshold, int drop_self_pairs, int max_tubes, uint8_t *tube_out,
                          int *n_tubes_used_out, int *n_unplaced_out);
+/* msspe_conflict_tubes with the rule in place of dg_threshold (as msspe_conflict_cover_rule). */
+int msspe_conflict_tubes_rule(msspe_ctx *ctx, const char *pool_ascii, int n, int k, const msspe_chem *chem,
+                              const msspe_conflict_rule *rule, int drop_self_pairs, int max_tubes, uint8_t *tube_out,
+                              int *n_tubes_used_out, int *n_unplaced_out);
 
 /* Number of pairs the last cross-dimer call routed to the generic (slow) kernel because their
  * DP did not fit the fast kernel's register-resident table. */
@@ -1269,6 +1352,16 @@ int msspe_panel_select_bitmap(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, si
                               uint32_t *gain_out, int *n_picked_out, uint8_t *tube_out, uint8_t *barred_out,
                               uint8_t *covered_out, long long *covered_all_out, long long *covered_kept_out,
                               int *n_tubes_used_out);
+/* msspe_panel_select with the conflict rule in place of dg_threshold: the pool is screened with
+ * msspe_conflict_graph_dev (bitmap only); the rest is msspe_panel_select_dev.  A NULL conflict_rule or both flags
+ * zero: MSSPE_ERR_ARG. */
+int msspe_panel_select_rule(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len, const msspe_kmer_opt *opt,
+                            const msspe_seed_rule *rule, const msspe_select_opt *sel, const uint64_t *fwd_words,
+                            int n_fwd, const uint64_t *rev_words, int n_rev, const uint8_t *forced,
+                            const msspe_chem *chem, const msspe_conflict_rule *conflict_rule, uint8_t *keep_out,
+                            uint32_t *order_out, uint32_t *gain_out, int *n_picked_out, uint8_t *tube_out,
+                            uint8_t *barred_out, uint8_t *covered_out, long long *covered_all_out,
+                            long long *covered_kept_out, int *n_tubes_used_out);
 
 /* ---- several devices of one node ----------------------------------------------------------
  *

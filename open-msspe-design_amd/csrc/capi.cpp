@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "conflict_cover.hpp"
+#include "conflict_graph.hpp"
 #include "background.hpp"
 #include "background_thal.hpp"
 #include "background_amplicons.hpp"
@@ -130,6 +131,7 @@ struct EngineOptions {
     int amplicon_keys_cap_log2 = 20;  // msspe_background_amplicons*: the stable-key buffer starts at 2^this keys and doubles
     long panel_thin_matrix_max_mb = 8192;   // msspe_panel_thin*: the incidence matrix may take this much, else MSSPE_ERR_CAPACITY
     bool thin_thal_unique = true;   // msspe_panel_thin_thal*: a slab's matches are sorted and each distinct (primer, template) is scored once
+    int conflict_graph_block_rows = 0;   // msspe_conflict_graph*: rows per block of the two per-rule planes (0: within kGraphPlaneBytes)
 };
 
 struct msspe_ctx {
@@ -166,6 +168,7 @@ struct msspe_ctx {
     MismatchCoverage mm_cov;           // msspe_segment_coverage_mm*: primer words, counts, per-segment minima
     BackgroundSites background;        // msspe_background_sites*: primer words in plane form, per-primer counts
     CoverStage cover;                  // msspe_conflict_cover*: the symmetrised bitmap and the round state
+    GraphScratch graph;                // msspe_conflict_graph*: the two per-rule planes of a row block, its row counts and bases
     TubeStage tubes;                   // msspe_conflict_tubes*: its round state (the graph lives in cover's buffers)
     PanelThin thin;                    // msspe_panel_thin*: the incidence matrix, covered words, gains and round state
     PanelThinThal thin_thal;           // msspe_panel_thin_thal*: the sorted order, run slots and rocPRIM storage of a slab (its
@@ -812,6 +815,9 @@ int msspe_set_option(msspe_ctx *ctx, const char *key, const char *value)
     } else if (k == "thin_thal_unique") {
         if (!is_num || num < 0 || num > 1) return bad();
         ctx->opt.thin_thal_unique = num != 0;
+    } else if (k == "conflict_graph_block_rows") {
+        if (!is_num || num < 0 || num > (long)INT32_MAX) return bad();
+        ctx->opt.conflict_graph_block_rows = (int)num;
     } else if (k == "row_oob") {
         if (!is_num || num < 0 || num > 1) return bad();
         ctx->opt.row_oob = num != 0;
@@ -888,6 +894,7 @@ int msspe_get_info(msspe_ctx *ctx, const char *key, long long *value_out)
     else if (k == "cover_keys_us") *value_out = ctx->cover.phase_us()[0];
     else if (k == "cover_symmetrise_us") *value_out = ctx->cover.phase_us()[1];
     else if (k == "cover_rounds_us") *value_out = ctx->cover.phase_us()[2];
+    else if (k == "conflict_graph_grows") *value_out = ctx->graph.grows();
     else if (k == "tube_rounds") *value_out = ctx->tubes.rounds();
     else if (k == "tube_keys_us") *value_out = ctx->tubes.phase_us()[0];
     else if (k == "tube_symmetrise_us") *value_out = ctx->tubes.phase_us()[1];
@@ -1003,6 +1010,7 @@ void msspe_destroy(msspe_ctx *ctx)
         ctx->kmer_rev.release();
         ctx->cover.release();
         ctx->tubes.release();
+        ctx->graph.release();
         ctx->thin.release();
         ctx->thin_thal.release();
         ctx->select.release();
@@ -1727,7 +1735,266 @@ int cross_dimer_ab_impl(msspe_ctx *ctx, const uint64_t *d_a, int n_a, const uint
 
 }  // namespace
 
+namespace {
+
+// What a conflict-graph call asks for beyond the block's sinks (row_conflicts, bitmap).  count != null: the edge form.
+struct GraphOut {
+    uint64_t *kind_counts;
+    msspe_kind_edge *edges;
+    uint64_t capacity;
+    uint64_t *count;
+    uint32_t col_first;   // an edge's b for the block's first column (the caller's index space)
+};
+
+// What every conflict-graph entry point checks before anything else.
+int graph_rule_check(msspe_ctx *ctx, const msspe_chem *chem, const msspe_conflict_rule *rule, const GraphOut &out,
+                     bool edge_form)
+{
+    if (!chem || !rule) return fail(ctx, MSSPE_ERR_ARG, "conflict graph: null chemistry or rule");
+    if (!rule->use_any && !rule->use_end) return fail(ctx, MSSPE_ERR_ARG, "conflict graph: the rule enables neither ANY nor END");
+    if (edge_form && (!out.count || (out.capacity && !out.edges)))
+        return fail(ctx, MSSPE_ERR_ARG, "edge list: null count or buffer");
+    return MSSPE_OK;
+}
+
+// The block under the rule (msspe_conflict_graph*).  b: the block in pool indices, its sinks the caller's
+// row_conflicts and bitmap.  One rule without edges (and with a bitmap to count kinds from, where they are asked for)
+// IS that rule's screen on the caller's buffers: the same internal path, so the same route and options.  Otherwise the
+// enabled screens fill their planes in the context's scratch a block of rows at a time, and the union, scan and emit
+// kernels follow each block; the list's running count (out.count) carries the row bases from block to block.
+int conflict_graph_impl(msspe_ctx *ctx, const ScreenBlock &b, const msspe_chem *chem, const msspe_conflict_rule *rule,
+                        const GraphOut &out)
+{
+    // the screens' own argument checks (open_screen), made once and before the edge count is cleared
+    if (!b.pool || b.n < 0) return fail(ctx, MSSPE_ERR_ARG, "null pool/chemistry");
+    if (b.k < 2 || b.k > 32 || b.k2 < 2 || b.k2 > 32) return fail(ctx, MSSPE_ERR_K, "oligo length must be 2..32");
+    if (b.row0 < 0 || b.row1 > b.n || b.row0 > b.row1 || b.col0 < 0 || b.col1 > b.n || b.col0 > b.col1)
+        return fail(ctx, MSSPE_ERR_ARG, "row/column range outside the pool");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (out.count) HIP_TRY(ctx, hipMemsetAsync(out.count, 0, sizeof(uint64_t), ctx->stream));
+    if (b.row0 == b.row1 || b.col0 == b.col1) return MSSPE_OK;
+    const bool any = rule->use_any != 0, end = rule->use_end != 0;
+    const int words = b.sinks.words, n_rows = b.row1 - b.row0;
+    uint32_t *const row_conflicts = b.sinks.row_conflicts;
+    uint64_t *const bitmap = b.sinks.bitmap;
+    unsigned long long *const kinds = reinterpret_cast<unsigned long long *>(out.kind_counts);
+    if (any != end && !out.count && (bitmap || !kinds)) {
+        if (int rc = cross_dimer_screen(ctx, b, chem, end ? rule->end_tm_threshold : rule->dg_threshold, end)) return rc;
+        if (kinds)   // every set bit is of the one kind
+            HIP_TRY(ctx, launch_graph_union(any ? bitmap : nullptr, end ? bitmap : nullptr, n_rows, words, nullptr, nullptr,
+                                            nullptr, kinds, ctx->stream));
+        return MSSPE_OK;
+    }
+    const int block_rows = graph_block_rows(ctx->opt.conflict_graph_block_rows, n_rows, words);
+    {
+        std::string err;
+        if (int rc = ctx->graph.ensure(block_rows, words, ctx->stream, err)) return fail(ctx, rc, err);
+    }
+    uint64_t *const p_any = any ? ctx->graph.plane(0) : nullptr, *const p_end = end ? ctx->graph.plane(1) : nullptr;
+    for (int r0 = b.row0; r0 < b.row1; r0 += block_rows) {
+        const int r1 = (int)std::min<long>((long)r0 + block_rows, b.row1), rows = r1 - r0;
+        auto plane_block = [&](uint64_t *plane) {
+            return screen_block(b.pool, b.n, b.k, b.k2, r0, r1, b.col0, b.col1, plane_sinks(nullptr, plane, nullptr, nullptr));
+        };
+        if (any)
+            if (int rc = cross_dimer_impl(ctx, plane_block(p_any), chem, rule->dg_threshold)) return rc;
+        if (end)
+            if (int rc = cross_dimer_end_impl(ctx, plane_block(p_end), chem, rule->end_tm_threshold)) return rc;
+        HIP_TRY(ctx, launch_graph_union(p_any, p_end, rows, words,
+                                        bitmap ? bitmap + (size_t)(r0 - b.row0) * (size_t)words : nullptr,
+                                        row_conflicts ? row_conflicts + r0 : nullptr, ctx->graph.row_count(), kinds,
+                                        ctx->stream));
+        if (out.count) {
+            HIP_TRY(ctx, launch_graph_scan(ctx->graph.row_count(), rows, ctx->graph.row_base(),
+                                           reinterpret_cast<unsigned long long *>(out.count), ctx->stream));
+            HIP_TRY(ctx, launch_graph_emit(p_any, p_end, rows, words, ctx->graph.row_count(), ctx->graph.row_base(),
+                                           (uint32_t)r0, out.col_first, out.edges, out.capacity, ctx->stream));
+        }
+    }
+    return MSSPE_OK;
+}
+
+// ab: the block in the pools' own indices, as cross_dimer_ab_impl takes it (whose checks and staging these are).
+int conflict_graph_ab_impl(msspe_ctx *ctx, const uint64_t *d_a, int n_a, const uint64_t *d_b, int n_b, const ScreenBlock &ab,
+                           const msspe_chem *chem, const msspe_conflict_rule *rule, GraphOut out)
+{
+    if (n_a < 0 || n_b < 0 || (n_a && !d_a) || (n_b && !d_b)) return fail(ctx, MSSPE_ERR_ARG, "null pool/chemistry");
+    if (ab.k < 2 || ab.k > 32 || ab.k2 < 2 || ab.k2 > 32) return fail(ctx, MSSPE_ERR_K, "oligo length must be 2..32");
+    if (ab.row0 < 0 || ab.row1 > n_a || ab.row0 > ab.row1 || ab.col0 < 0 || ab.col1 > n_b || ab.col0 > ab.col1)
+        return fail(ctx, MSSPE_ERR_ARG, "row/column range outside pool A / pool B");
+    if ((long)n_a + (long)n_b > (long)INT32_MAX) return fail(ctx, MSSPE_ERR_ARG, "pools too large");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (ab.row0 == ab.row1 || ab.col0 == ab.col1) {
+        if (out.count) HIP_TRY(ctx, hipMemsetAsync(out.count, 0, sizeof(uint64_t), ctx->stream));
+        return MSSPE_OK;
+    }
+    if (int rc = stage_ab(ctx, d_a, n_a, d_b, n_b)) return rc;
+    out.col_first = (uint32_t)ab.col0;
+    return conflict_graph_impl(ctx, screen_block(ctx->d_ab, n_a + n_b, ab.k, ab.k2, ab.row0, ab.row1, n_a + ab.col0,
+                                                 n_a + ab.col1, ab.sinks),
+                               chem, rule, out);
+}
+
+// The host forms: `packed` (uploaded here) is the pool, rows [0, n_rows) against its columns [col0, col1) -- one pool:
+// [0, n); pool A + pool B back to back: from n_a.  Host outputs are assigned.  edge_form: the ordered list, with the
+// MSSPE_ERR_CAPACITY contract of msspe_cross_dimer_edges.
+int conflict_graph_host(msspe_ctx *ctx, const std::vector<uint64_t> &packed, int n_rows, int k, int k2, int col0, int col1,
+                        const msspe_chem *chem, const msspe_conflict_rule *rule, uint32_t *row_conflicts, uint64_t *bitmap,
+                        uint64_t *kind_counts, bool edge_form, msspe_kind_edge *edges, uint64_t capacity, uint64_t *count_out)
+{
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t n = packed.size(), words = ((size_t)(col1 - col0) + 63) / 64, rows = (size_t)n_rows;
+    DevBuf<uint64_t> d_pool, d_bitmap, d_kinds, d_count;
+    DevBuf<uint32_t> d_rc;
+    DevBuf<msspe_kind_edge> d_edges;
+    HIP_TRY(ctx, d_pool.alloc(n));
+    HIP_TRY(ctx, hipMemcpy(d_pool, packed.data(), sizeof(uint64_t) * n, hipMemcpyHostToDevice));
+    if (row_conflicts) {
+        HIP_TRY(ctx, d_rc.alloc(rows));
+        HIP_TRY(ctx, hipMemsetAsync(d_rc, 0, sizeof(uint32_t) * rows, ctx->stream));
+    }
+    if (bitmap) HIP_TRY(ctx, d_bitmap.alloc(rows * words));
+    if (kind_counts) {
+        HIP_TRY(ctx, d_kinds.alloc(3));
+        HIP_TRY(ctx, hipMemsetAsync(d_kinds, 0, 3 * sizeof(uint64_t), ctx->stream));
+    }
+    if (edge_form) {
+        HIP_TRY(ctx, d_count.alloc(1));
+        if (capacity) HIP_TRY(ctx, d_edges.alloc((size_t)capacity));
+    }
+    const GraphOut out{d_kinds, d_edges, capacity, d_count, 0u};
+    int rc = conflict_graph_impl(ctx, screen_block(d_pool, (int)n, k, k2, 0, n_rows, col0, col1,
+                                                   plane_sinks(d_rc, d_bitmap, nullptr, nullptr)),
+                                 chem, rule, out);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if ((rc = check_list_overrun(ctx))) return rc;
+    if (row_conflicts) HIP_TRY(ctx, hipMemcpy(row_conflicts, d_rc, sizeof(uint32_t) * rows, hipMemcpyDeviceToHost));
+    if (bitmap) HIP_TRY(ctx, hipMemcpy(bitmap, d_bitmap, sizeof(uint64_t) * rows * words, hipMemcpyDeviceToHost));
+    if (kind_counts) HIP_TRY(ctx, hipMemcpy(kind_counts, d_kinds, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (!edge_form) return MSSPE_OK;
+    HIP_TRY(ctx, hipMemcpy(count_out, d_count, sizeof *count_out, hipMemcpyDeviceToHost));
+    const uint64_t have = std::min<uint64_t>(*count_out, capacity);
+    if (have) HIP_TRY(ctx, hipMemcpy(edges, d_edges, sizeof(msspe_kind_edge) * (size_t)have, hipMemcpyDeviceToHost));
+    if (*count_out > capacity)
+        return fail(ctx, MSSPE_ERR_CAPACITY, "edge list: " + std::to_string(*count_out) + " conflict edges, capacity " +
+                                                 std::to_string(capacity));
+    return MSSPE_OK;
+}
+
+// Rule forms of the graph consumers: the whole-pool bitmap under the rule, or under dg_threshold alone (rule == null:
+// msspe_cross_dimer_dev, the call the host-pool forms have always made).
+int consumer_screen(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const msspe_chem *chem,
+                    const msspe_conflict_rule *rule, float dg_threshold, uint64_t *d_bitmap)
+{
+    if (!rule) return msspe_cross_dimer_dev(ctx, d_pool, n, k, chem, dg_threshold, 0, n, 0, n, nullptr, d_bitmap, nullptr, nullptr);
+    return msspe_conflict_graph_dev(ctx, d_pool, n, k, chem, rule, 0, n, 0, n, nullptr, d_bitmap, nullptr);
+}
+
+}  // namespace
+
 extern "C" {
+
+int msspe_conflict_graph_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const msspe_chem *chem,
+                             const msspe_conflict_rule *rule, int row0, int row1, int col0, int col1,
+                             uint32_t *d_row_conflicts, uint64_t *d_bitmap, uint64_t *d_kind_counts)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    const GraphOut out{d_kind_counts, nullptr, 0, nullptr, (uint32_t)col0};
+    if (int rc = graph_rule_check(ctx, chem, rule, out, false)) return rc;
+    return conflict_graph_impl(ctx, screen_block(d_pool, n, k, k, row0, row1, col0, col1,
+                                                 plane_sinks(d_row_conflicts, d_bitmap, nullptr, nullptr)),
+                               chem, rule, out);
+}
+
+int msspe_conflict_graph_edges_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const msspe_chem *chem,
+                                   const msspe_conflict_rule *rule, int row0, int row1, int col0, int col1,
+                                   uint32_t *d_row_conflicts, uint64_t *d_bitmap, uint64_t *d_kind_counts,
+                                   msspe_kind_edge *d_edges, uint64_t capacity, uint64_t *d_count)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    const GraphOut out{d_kind_counts, d_edges, capacity, d_count, (uint32_t)col0};
+    if (int rc = graph_rule_check(ctx, chem, rule, out, true)) return rc;
+    return conflict_graph_impl(ctx, screen_block(d_pool, n, k, k, row0, row1, col0, col1,
+                                                 plane_sinks(d_row_conflicts, d_bitmap, nullptr, nullptr)),
+                               chem, rule, out);
+}
+
+int msspe_conflict_graph_ab_dev(msspe_ctx *ctx, const uint64_t *d_a, int n_a, int k_a, const uint64_t *d_b, int n_b,
+                                int k_b, const msspe_chem *chem, const msspe_conflict_rule *rule, int row0, int row1,
+                                int col0, int col1, uint32_t *d_row_conflicts, uint64_t *d_bitmap,
+                                uint64_t *d_kind_counts)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    const GraphOut out{d_kind_counts, nullptr, 0, nullptr, 0u};
+    if (int rc = graph_rule_check(ctx, chem, rule, out, false)) return rc;
+    return conflict_graph_ab_impl(ctx, d_a, n_a, d_b, n_b,
+                                  screen_block(nullptr, 0, k_a, k_b, row0, row1, col0, col1,
+                                               plane_sinks(d_row_conflicts, d_bitmap, nullptr, nullptr)),
+                                  chem, rule, out);
+}
+
+int msspe_conflict_graph_ab_edges_dev(msspe_ctx *ctx, const uint64_t *d_a, int n_a, int k_a, const uint64_t *d_b,
+                                      int n_b, int k_b, const msspe_chem *chem, const msspe_conflict_rule *rule,
+                                      int row0, int row1, int col0, int col1, uint32_t *d_row_conflicts,
+                                      uint64_t *d_bitmap, uint64_t *d_kind_counts, msspe_kind_edge *d_edges,
+                                      uint64_t capacity, uint64_t *d_count)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    const GraphOut out{d_kind_counts, d_edges, capacity, d_count, 0u};
+    if (int rc = graph_rule_check(ctx, chem, rule, out, true)) return rc;
+    return conflict_graph_ab_impl(ctx, d_a, n_a, d_b, n_b,
+                                  screen_block(nullptr, 0, k_a, k_b, row0, row1, col0, col1,
+                                               plane_sinks(d_row_conflicts, d_bitmap, nullptr, nullptr)),
+                                  chem, rule, out);
+}
+
+int msspe_conflict_graph(msspe_ctx *ctx, const char *pool_ascii, int n, int k, const msspe_chem *chem,
+                         const msspe_conflict_rule *rule, uint32_t *row_conflicts, uint64_t *bitmap,
+                         uint64_t *kind_counts)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (int rc = graph_rule_check(ctx, chem, rule, GraphOut{}, false)) return rc;
+    if (!pool_ascii || n < 0) return fail(ctx, MSSPE_ERR_ARG, "null pool/chemistry");
+    if (n == 0) return MSSPE_OK;
+    std::vector<uint64_t> packed;
+    if (int rc = pack_pool(ctx, pool_ascii, n, k, packed)) return rc;
+    return conflict_graph_host(ctx, packed, n, k, k, 0, n, chem, rule, row_conflicts, bitmap, kind_counts, false, nullptr,
+                               0, nullptr);
+}
+
+int msspe_conflict_graph_edges(msspe_ctx *ctx, const char *pool_ascii, int n, int k, const msspe_chem *chem,
+                               const msspe_conflict_rule *rule, msspe_kind_edge *edges, uint64_t capacity,
+                               uint64_t *count_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (int rc = graph_rule_check(ctx, chem, rule, GraphOut{}, false)) return rc;
+    if (!pool_ascii || !count_out || n < 0 || (capacity && !edges))
+        return fail(ctx, MSSPE_ERR_ARG, "null pool/chemistry/count, or a capacity without a buffer");
+    *count_out = 0;
+    if (n == 0) return MSSPE_OK;
+    std::vector<uint64_t> packed;
+    if (int rc = pack_pool(ctx, pool_ascii, n, k, packed)) return rc;
+    return conflict_graph_host(ctx, packed, n, k, k, 0, n, chem, rule, nullptr, nullptr, nullptr, true, edges, capacity,
+                               count_out);
+}
+
+int msspe_conflict_graph_ab_edges(msspe_ctx *ctx, const char *a_ascii, int n_a, int k_a, const char *b_ascii, int n_b,
+                                  int k_b, const msspe_chem *chem, const msspe_conflict_rule *rule,
+                                  msspe_kind_edge *edges, uint64_t capacity, uint64_t *count_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (int rc = graph_rule_check(ctx, chem, rule, GraphOut{}, false)) return rc;
+    if (!count_out || n_a < 0 || n_b < 0 || (n_a && !a_ascii) || (n_b && !b_ascii) || (capacity && !edges))
+        return fail(ctx, MSSPE_ERR_ARG, "null pool/chemistry/count, or a capacity without a buffer");
+    *count_out = 0;
+    std::vector<uint64_t> packed;
+    if (int rc = pack_ab(ctx, a_ascii, n_a, k_a, b_ascii, n_b, k_b, packed)) return rc;
+    if (n_a == 0 || n_b == 0) return MSSPE_OK;
+    // the staged pool's columns from n_a: bit 0 of the block is B[0], so an edge's b is a B index as it stands
+    return conflict_graph_host(ctx, packed, n_a, k_a, k_b, n_a, n_a + n_b, chem, rule, nullptr, nullptr, nullptr, true, edges,
+                               capacity, count_out);
+}
 
 int msspe_conflict_cover_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const uint64_t *d_bitmap,
                              int drop_self_pairs, uint8_t *d_deleted, int *n_deleted_out)
@@ -1747,10 +2014,11 @@ int msspe_conflict_cover_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int 
     return rc ? fail(ctx, rc, err) : MSSPE_OK;
 }
 
-int msspe_conflict_cover(msspe_ctx *ctx, const char *pool_ascii, int n, int k, const msspe_chem *chem,
-                         float dg_threshold, int drop_self_pairs, uint8_t *deleted_out, int *n_deleted_out)
+// rule == null: the screen under dg_threshold alone (msspe_conflict_cover); else under the rule (msspe_conflict_cover_rule)
+static int conflict_cover_host(msspe_ctx *ctx, const char *pool_ascii, int n, int k, const msspe_chem *chem,
+                               const msspe_conflict_rule *rule, float dg_threshold, int drop_self_pairs,
+                               uint8_t *deleted_out, int *n_deleted_out)
 {
-    if (!ctx) return MSSPE_ERR_ARG;
     if (n_deleted_out) *n_deleted_out = 0;
     if (!pool_ascii || !chem || !deleted_out || n < 0)
         return fail(ctx, MSSPE_ERR_ARG, "conflict cover: null pool, chemistry or output");
@@ -1777,14 +2045,31 @@ int msspe_conflict_cover(msspe_ctx *ctx, const char *pool_ascii, int n, int k, c
     HIP_TRY(ctx, hipMemcpyAsync(d_pool, packed.data(), sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice,
                                 ctx->stream));
     // the screen's decisions only: the bitmap is all the cover reads
-    int rc = msspe_cross_dimer_dev(ctx, d_pool, n, k, chem, dg_threshold, 0, n, 0, n, nullptr, d_bitmap, nullptr,
-                                   nullptr);
+    int rc = consumer_screen(ctx, d_pool, n, k, chem, rule, dg_threshold, d_bitmap);
     if (!rc) rc = msspe_conflict_cover_dev(ctx, d_pool, n, k, d_bitmap, drop_self_pairs, d_deleted, n_deleted_out);
     if (!rc) rc = check_list_overrun(ctx);   // the cover has synchronised the stream
     if (rc) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(deleted_out, d_deleted, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return MSSPE_OK;
+}
+
+int msspe_conflict_cover(msspe_ctx *ctx, const char *pool_ascii, int n, int k, const msspe_chem *chem,
+                         float dg_threshold, int drop_self_pairs, uint8_t *deleted_out, int *n_deleted_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    return conflict_cover_host(ctx, pool_ascii, n, k, chem, nullptr, dg_threshold, drop_self_pairs, deleted_out,
+                               n_deleted_out);
+}
+
+int msspe_conflict_cover_rule(msspe_ctx *ctx, const char *pool_ascii, int n, int k, const msspe_chem *chem,
+                              const msspe_conflict_rule *rule, int drop_self_pairs, uint8_t *deleted_out,
+                              int *n_deleted_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (n_deleted_out) *n_deleted_out = 0;
+    if (int rc = graph_rule_check(ctx, chem, rule, GraphOut{}, false)) return rc;
+    return conflict_cover_host(ctx, pool_ascii, n, k, chem, rule, 0.0f, drop_self_pairs, deleted_out, n_deleted_out);
 }
 
 int msspe_conflict_tubes_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const uint64_t *d_bitmap,
@@ -1809,11 +2094,11 @@ int msspe_conflict_tubes_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int 
     return rc ? fail(ctx, rc, err) : MSSPE_OK;
 }
 
-int msspe_conflict_tubes(msspe_ctx *ctx, const char *pool_ascii, int n, int k, const msspe_chem *chem,
-                         float dg_threshold, int drop_self_pairs, int max_tubes, uint8_t *tube_out,
-                         int *n_tubes_used_out, int *n_unplaced_out)
+// rule == null: msspe_conflict_tubes; else msspe_conflict_tubes_rule (as conflict_cover_host)
+static int conflict_tubes_host(msspe_ctx *ctx, const char *pool_ascii, int n, int k, const msspe_chem *chem,
+                               const msspe_conflict_rule *rule, float dg_threshold, int drop_self_pairs, int max_tubes,
+                               uint8_t *tube_out, int *n_tubes_used_out, int *n_unplaced_out)
 {
-    if (!ctx) return MSSPE_ERR_ARG;
     if (n_tubes_used_out) *n_tubes_used_out = 0;
     if (n_unplaced_out) *n_unplaced_out = 0;
     if (!pool_ascii || !chem || !tube_out || n < 0)
@@ -1843,8 +2128,7 @@ int msspe_conflict_tubes(msspe_ctx *ctx, const char *pool_ascii, int n, int k, c
     HIP_TRY(ctx, hipMemcpyAsync(d_pool, packed.data(), sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice,
                                 ctx->stream));
     // the screen's decisions only: the bitmap is all the assignment reads
-    int rc = msspe_cross_dimer_dev(ctx, d_pool, n, k, chem, dg_threshold, 0, n, 0, n, nullptr, d_bitmap, nullptr,
-                                   nullptr);
+    int rc = consumer_screen(ctx, d_pool, n, k, chem, rule, dg_threshold, d_bitmap);
     if (!rc)
         rc = msspe_conflict_tubes_dev(ctx, d_pool, n, k, d_bitmap, drop_self_pairs, max_tubes, d_tube, n_tubes_used_out,
                                       n_unplaced_out);
@@ -1853,6 +2137,27 @@ int msspe_conflict_tubes(msspe_ctx *ctx, const char *pool_ascii, int n, int k, c
     HIP_TRY(ctx, hipMemcpyAsync(tube_out, d_tube, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return MSSPE_OK;
+}
+
+int msspe_conflict_tubes(msspe_ctx *ctx, const char *pool_ascii, int n, int k, const msspe_chem *chem,
+                         float dg_threshold, int drop_self_pairs, int max_tubes, uint8_t *tube_out,
+                         int *n_tubes_used_out, int *n_unplaced_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    return conflict_tubes_host(ctx, pool_ascii, n, k, chem, nullptr, dg_threshold, drop_self_pairs, max_tubes, tube_out,
+                               n_tubes_used_out, n_unplaced_out);
+}
+
+int msspe_conflict_tubes_rule(msspe_ctx *ctx, const char *pool_ascii, int n, int k, const msspe_chem *chem,
+                              const msspe_conflict_rule *rule, int drop_self_pairs, int max_tubes, uint8_t *tube_out,
+                              int *n_tubes_used_out, int *n_unplaced_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (n_tubes_used_out) *n_tubes_used_out = 0;
+    if (n_unplaced_out) *n_unplaced_out = 0;
+    if (int rc = graph_rule_check(ctx, chem, rule, GraphOut{}, false)) return rc;
+    return conflict_tubes_host(ctx, pool_ascii, n, k, chem, rule, 0.0f, drop_self_pairs, max_tubes, tube_out,
+                               n_tubes_used_out, n_unplaced_out);
 }
 
 }  // extern "C"
@@ -3962,15 +4267,17 @@ int msspe_panel_select_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int 
                              barred_out, covered_out, covered_all_out, covered_kept_out, n_tubes_used_out);
 }
 
-// The two host forms: the alignment and the graph go to the device for the call (chem == NULL: `bitmap` is the graph,
-// from the host; otherwise the pool is screened there), the rest is msspe_panel_select_dev.
+// The host forms: the alignment and the graph go to the device for the call (chem == NULL: `bitmap` is the graph,
+// from the host; otherwise the pool is screened there, under conflict_rule where there is one, else under dg_threshold),
+// the rest is msspe_panel_select_dev.
 static int panel_select_host(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len, const msspe_kmer_opt *opt,
                              const msspe_seed_rule *rule, const msspe_select_opt *sel, const uint64_t *fwd_words,
                              int n_fwd, const uint64_t *rev_words, int n_rev, const uint8_t *forced,
                              const uint64_t *bitmap, const msspe_chem *chem, float dg_threshold, uint8_t *keep_out,
                              uint32_t *order_out, uint32_t *gain_out, int *n_picked_out, uint8_t *tube_out,
                              uint8_t *barred_out, uint8_t *covered_out, long long *covered_all_out,
-                             long long *covered_kept_out, int *n_tubes_used_out)
+                             long long *covered_kept_out, int *n_tubes_used_out,
+                             const msspe_conflict_rule *conflict_rule = nullptr)
 {
     if (!seqs || n_seq < 0) return fail(ctx, MSSPE_ERR_ARG, "null sequences");
     if (n_fwd < 0 || n_rev < 0 || (n_fwd && !fwd_words) || (n_rev && !rev_words) || !opt || !rule || !sel || !keep_out ||
@@ -4006,9 +4313,7 @@ static int panel_select_host(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, siz
                                         ctx->stream));
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // pool leaves scope
             // the screen's decisions only: the bitmap is all the selection reads
-            if (int rc = msspe_cross_dimer_dev(ctx, d_pool, (int)n, k, chem, dg_threshold, 0, (int)n, 0, (int)n, nullptr,
-                                               d_bitmap, nullptr, nullptr))
-                return rc;
+            if (int rc = consumer_screen(ctx, d_pool, (int)n, k, chem, conflict_rule, dg_threshold, d_bitmap)) return rc;
         } else {
             if (!bitmap) return fail(ctx, MSSPE_ERR_ARG, "panel select: null bitmap");
             HIP_TRY(ctx, hipMemcpy(d_bitmap, bitmap, sizeof(uint64_t) * (size_t)n * words, hipMemcpyHostToDevice));
@@ -4040,6 +4345,21 @@ int msspe_panel_select(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t se
     return panel_select_host(ctx, seqs, n_seq, seq_len, opt, rule, sel, fwd_words, n_fwd, rev_words, n_rev, forced,
                              nullptr, chem, dg_threshold, keep_out, order_out, gain_out, n_picked_out, tube_out,
                              barred_out, covered_out, covered_all_out, covered_kept_out, n_tubes_used_out);
+}
+
+int msspe_panel_select_rule(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len, const msspe_kmer_opt *opt,
+                            const msspe_seed_rule *rule, const msspe_select_opt *sel, const uint64_t *fwd_words,
+                            int n_fwd, const uint64_t *rev_words, int n_rev, const uint8_t *forced,
+                            const msspe_chem *chem, const msspe_conflict_rule *conflict_rule, uint8_t *keep_out,
+                            uint32_t *order_out, uint32_t *gain_out, int *n_picked_out, uint8_t *tube_out,
+                            uint8_t *barred_out, uint8_t *covered_out, long long *covered_all_out,
+                            long long *covered_kept_out, int *n_tubes_used_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (int rc = graph_rule_check(ctx, chem, conflict_rule, GraphOut{}, false)) return rc;
+    return panel_select_host(ctx, seqs, n_seq, seq_len, opt, rule, sel, fwd_words, n_fwd, rev_words, n_rev, forced,
+                             nullptr, chem, 0.0f, keep_out, order_out, gain_out, n_picked_out, tube_out, barred_out,
+                             covered_out, covered_all_out, covered_kept_out, n_tubes_used_out, conflict_rule);
 }
 
 int msspe_panel_select_bitmap(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len,

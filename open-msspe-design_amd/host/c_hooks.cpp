@@ -64,7 +64,7 @@ int odm_parse_args(int argc, const char *const *argv, char *out, size_t cap)
           << "\ncheck_hairpin=" << a.check_hairpin << "\ndo_align=" << a.do_align
           << "\ntm_stddev=" << a.tm_stddev << "\ncover_on_device=" << a.cover_on_device << "\ntubes=" << a.tubes
           << "\ncoverage_mismatches=" << a.coverage_mismatches << "\ncoverage_3p_exact=" << a.coverage_3p_exact
-          << "\ncoverage_tm=" << a.coverage_tm_text << "\ncoverage_thal=" << a.coverage_thal
+          << "\nmax_cross_dimer_end_tm=" << a.max_cross_dimer_end_tm_text << "\ncoverage_tm=" << a.coverage_tm_text << "\ncoverage_thal=" << a.coverage_thal
           << "\nselect_by_coverage=" << a.select_by_coverage << "\nthin_panel=" << a.thin_panel << "\nthin_mismatches=" << a.thin_mismatches
           << "\nthin_3p_exact=" << a.thin_3p_exact << "\nthin_min_gain=" << a.thin_min_gain
           << "\nthin_tm=" << a.thin_tm_text << "\nthin_thal=" << a.thin_thal

@@ -56,6 +56,7 @@ const OptSpec kOpts[] = {
     {"--max-self-dimer-end-tm", "MAX_SELF_DIMER_END_TM", OptSpec::Float, OFF(max_self_dimer_end_tm)},
     {"--max-hairpin-tm", "MAX_HAIRPIN_TM", OptSpec::Float, OFF(max_hairpin_tm)},
     {"--delta-g-threshold", "DELTA_G_THRESHOLD", OptSpec::Float, OFF(delta_g_threshold)},
+    {"--max-cross-dimer-end-tm", "MAX_CROSS_DIMER_END_TM", OptSpec::Str, OFF(max_cross_dimer_end_tm_text)},
     {"--keep-all", "KEEP_ALL", OptSpec::Bool, OFF(keep_all)},
     {"--check-cross-dimers", "CHECK_CROSS_DIMERS", OptSpec::Bool, OFF(check_cross_dimers)},
     {"--existing-primers", "EXISTING_PRIMERS", OptSpec::Str, OFF(existing_primers)},
@@ -161,6 +162,11 @@ std::string Args::usage()
          "--coverage-tm <C> adds a report of the segments the final primers hold at C: every match within\n"
          "--coverage-mismatches (last --coverage-3p-exact bases exact) is scored with thal (--coverage-thal any | end1)\n"
          "against the strand the primer anneals to. One device.\n"
+         "--max-cross-dimer-end-tm <C> makes two primers conflict also when the 3' end of either anneals to the other:\n"
+         "thal END1 of the ordered pair, od-msspe's SELF_END rule at C, beside the dG rule of --delta-g-threshold. The\n"
+         "cover, --cover-on-device, --tubes, --select-by-coverage, --existing-primers and the later --repick-rounds all\n"
+         "see the union, and stdout gains a line with the pairs of each kind. With --devices the union screen runs on\n"
+         "the first device: the group has no 3'-end path.\n"
          "--exclude-primers <CSV> names words stage A must never pick (direction and primers columns, as a panel).\n"
          "--rejected-out <CSV> writes every candidate the run dropped (direction,name,primers,round,reason; reason is\n"
          "stage_b, background, panel_dimer or cover; with --select-by-coverage true select_conflict or select_unneeded in\n"
@@ -250,6 +256,14 @@ Args Args::parse(int argc, const char *const *argv)
         if (a.coverage_thal != "any" && a.coverage_thal != "end1")
             throw UsageError("error: invalid value '" + a.coverage_thal +
                              "' for '--coverage-thal <...>'\n  [possible values: any, end1]");
+    }
+    if (!a.max_cross_dimer_end_tm_text.empty()) {
+        char *end = nullptr;
+        a.max_cross_dimer_end_tm = std::strtof(a.max_cross_dimer_end_tm_text.c_str(), &end);
+        if (*end || std::isnan(a.max_cross_dimer_end_tm))
+            throw UsageError("error: invalid value '" + a.max_cross_dimer_end_tm_text + "' for '--max-cross-dimer-end-tm'");
+        if (a.kmer_size < 2) throw UsageError("error: '--max-cross-dimer-end-tm' needs '--kmer-size' of at least 2");
+        a.cross_dimer_end = true;
     }
     if (a.coverage_mismatches > 0 || a.coverage_scored) {
         const std::string &v = a.coverage_3p_exact_text;
@@ -829,6 +843,32 @@ msspe_chem ntthal_chem(const NtthalOptions &opts)
     };
     return msspe_chem{two(opts.mv), two(opts.dv), two(opts.dntp), two(opts.conc), two(opts.t), 30};
 }
+// --max-cross-dimer-end-tm: the rule of every screen of the run
+msspe_conflict_rule conflict_rule(const NtthalOptions &opts)
+{
+    return msspe_conflict_rule{1, opts.dg, 1, opts.end_tm};
+}
+// the line stdout gains: the ordered pairs of the n distinct oligos a screen under both rules saw, by kind
+void note_kinds(const NtthalOptions &opts, size_t n, const uint64_t kinds[3])
+{
+    if (!opts.kinds_text) return;
+    char b[256];
+    std::snprintf(b, sizeof b, "Cross-dimer conflicts among %zu primers (dG < %.2f or 3'-end Tm >= %.2f): %llu dG only, "
+                               "%llu 3'-end only, %llu both\n",
+                  n, (double)opts.dg, (double)opts.end_tm, (unsigned long long)kinds[0], (unsigned long long)kinds[1],
+                  (unsigned long long)kinds[2]);
+    *opts.kinds_text += b;
+}
+// ... for the paths whose device call returns no counts: one more screen of the pool, counts only
+void count_kinds(Engine &eng, const std::string &flat, int n, int k, const msspe_chem &chem, const NtthalOptions &opts)
+{
+    if (!opts.kinds_text) return;
+    const msspe_conflict_rule rule = conflict_rule(opts);
+    uint64_t kinds[3] = {0, 0, 0};
+    const int rc = msspe_conflict_graph(eng.ctx(), flat.data(), n, k, &chem, &rule, nullptr, nullptr, kinds);
+    if (rc) eng.fail(rc);
+    note_kinds(opts, (size_t)n, kinds);
+}
 }  // namespace
 
 ConflictGraph run_ntthal(Engine &eng, const std::vector<std::string> &primers,
@@ -855,6 +895,29 @@ ConflictGraph run_ntthal(Engine &eng, const std::vector<std::string> &primers,
                            : msspe_cross_dimer_edges(eng.ctx(), flat.data(), n, k, &chem, opts.dg, edges.data(), edges.size(),
                                                      &count);
     };
+    if (opts.use_end) {   // the union of the dG rule and the 3'-end rule, on member 0 where there is a group
+        const msspe_conflict_rule rule = conflict_rule(opts);
+        std::vector<msspe_kind_edge> kedges(edges.size());
+        auto union_screen = [&]() {
+            return msspe_conflict_graph_edges(eng.ctx(), flat.data(), n, k, &chem, &rule, kedges.data(), kedges.size(), &count);
+        };
+        int rc = union_screen();
+        if (rc == MSSPE_ERR_CAPACITY) {
+            kedges.resize((size_t)count);
+            rc = union_screen();
+        }
+        if (rc) eng.fail(rc);
+        uint64_t kinds[3] = {0, 0, 0};
+        for (uint64_t e = 0; e < count; ++e) {
+            const msspe_kind_edge &ed = kedges[(size_t)e];
+            ++kinds[ed.kinds == MSSPE_KIND_ANY ? 0 : ed.kinds == MSSPE_KIND_END ? 1 : 2];
+            const std::string &a = g.nodes[ed.a], &b = g.nodes[ed.b];
+            if (!ntthal_pair_sent(a, b, cfg)) continue;
+            g.edges[a].insert(b);
+        }
+        note_kinds(opts, (size_t)n, kinds);
+        return g;
+    }
     int rc = screen();
     if (rc == MSSPE_ERR_CAPACITY) {
         edges.resize((size_t)count);
@@ -886,8 +949,24 @@ std::set<std::string> panel_conflicts(Engine &eng, const std::vector<std::string
     for (int order = 0; order < 2; ++order) {   // 0: (candidate, panel), 1: (panel, candidate)
         const std::string &a = order ? fp : fc, &b = order ? fc : fp;
         const int na = order ? np : nc, nb = order ? nc : np;
-        std::vector<msspe_edge> edges(4096);
         uint64_t count = 0;
+        if (opts.use_end) {   // a 3'-end dimer with a panel primer in either role drops the candidate as well
+            const msspe_conflict_rule rule = conflict_rule(opts);
+            std::vector<msspe_kind_edge> kedges(4096);
+            auto union_screen = [&]() {
+                return msspe_conflict_graph_ab_edges(eng.ctx(), a.data(), na, k, b.data(), nb, k, &chem, &rule, kedges.data(),
+                                                     kedges.size(), &count);
+            };
+            int rc = union_screen();
+            if (rc == MSSPE_ERR_CAPACITY) {
+                kedges.resize((size_t)count);
+                rc = union_screen();
+            }
+            if (rc) eng.fail(rc);
+            for (uint64_t e = 0; e < count; ++e) out.insert(cands[order ? kedges[(size_t)e].b : kedges[(size_t)e].a]);
+            continue;
+        }
+        std::vector<msspe_edge> edges(4096);
         auto screen = [&]() {
             return msspe_cross_dimer_ab_edges(eng.ctx(), a.data(), na, k, b.data(), nb, k, &chem, opts.dg, edges.data(),
                                               edges.size(), &count);
@@ -1007,9 +1086,13 @@ std::set<std::string> conflict_cover_on_device(Engine &eng, const std::vector<st
     const msspe_chem chem = ntthal_chem(opts);
     std::vector<uint8_t> del((size_t)n);
     // --check-self-dimers false: the pairs ntthal_pair_sent() never sends are no edges
-    const int rc = msspe_conflict_cover(eng.ctx(), flat.data(), n, k, &chem, opts.dg, cfg.check_self_dimers ? 0 : 1,
-                                        del.data(), nullptr);
+    const msspe_conflict_rule rule = conflict_rule(opts);
+    const int rc = opts.use_end ? msspe_conflict_cover_rule(eng.ctx(), flat.data(), n, k, &chem, &rule,
+                                                            cfg.check_self_dimers ? 0 : 1, del.data(), nullptr)
+                                : msspe_conflict_cover(eng.ctx(), flat.data(), n, k, &chem, opts.dg,
+                                                       cfg.check_self_dimers ? 0 : 1, del.data(), nullptr);
     if (rc) eng.fail(rc);
+    if (opts.use_end) count_kinds(eng, flat, n, k, chem, opts);
     for (int i = 0; i < n; ++i)
         if (del[(size_t)i]) deleted.insert(nodes[(size_t)i]);
     return deleted;
@@ -1084,9 +1167,14 @@ std::map<std::string, int> conflict_tubes_on_device(Engine &eng, const std::vect
     const msspe_chem chem = ntthal_chem(opts);
     std::vector<uint8_t> tube((size_t)n);
     // --check-self-dimers false: the pairs ntthal_pair_sent() never sends are no edges
-    const int rc = msspe_conflict_tubes(eng.ctx(), flat.data(), n, k, &chem, opts.dg, cfg.check_self_dimers ? 0 : 1,
-                                        max_tubes, tube.data(), nullptr, nullptr);
+    const msspe_conflict_rule rule = conflict_rule(opts);
+    const int rc = opts.use_end ? msspe_conflict_tubes_rule(eng.ctx(), flat.data(), n, k, &chem, &rule,
+                                                            cfg.check_self_dimers ? 0 : 1, max_tubes, tube.data(), nullptr,
+                                                            nullptr)
+                                : msspe_conflict_tubes(eng.ctx(), flat.data(), n, k, &chem, opts.dg,
+                                                       cfg.check_self_dimers ? 0 : 1, max_tubes, tube.data(), nullptr, nullptr);
     if (rc) eng.fail(rc);
+    if (opts.use_end) count_kinds(eng, flat, n, k, chem, opts);
     for (int i = 0; i < n; ++i)
         out.emplace(nodes[(size_t)i], tube[(size_t)i] == MSSPE_TUBE_NONE ? -1 : (int)tube[(size_t)i]);
     return out;
@@ -1564,7 +1652,8 @@ std::string select_panel_on_device(Engine &eng, const DeviceAlignment &aln, cons
                                    const msspe_chem &chem, int mode, float tm_threshold, int max_tubes, bool list_tubes,
                                    bool screen, bool drop_self_pairs, float dg_threshold, std::vector<KmerStat> &kept_f,
                                    std::vector<KmerStat> &kept_r, std::map<std::string, int> &tubes,
-                                   const std::function<void(const KmerStat &, bool)> &dropped)
+                                   const std::function<void(const KmerStat &, bool)> &dropped,
+                                   const NtthalOptions *end_rule)
 {
     // the graph's nodes are distinct words: the panel's first, then the new primers in their lists' order; a word met
     // again (the other direction's list) is not offered
@@ -1604,7 +1693,21 @@ std::string select_panel_on_device(Engine &eng, const DeviceAlignment &aln, cons
             pool.insert(pool.end(), wr.begin(), wr.end());
             rc = msspe_device_put(eng.ctx(), pool.data(), sizeof(uint64_t) * n, &d_pool);
             // the screen's decisions only: the bitmap is all the selection reads
-            if (!rc)
+            if (!rc && end_rule && end_rule->use_end) {   // --max-cross-dimer-end-tm: the union, and its kinds for stdout
+                const msspe_conflict_rule both = conflict_rule(*end_rule);
+                const uint64_t zero3[3] = {0, 0, 0};
+                uint64_t kinds[3] = {0, 0, 0};
+                void *d_kinds = nullptr;
+                rc = msspe_device_put(eng.ctx(), zero3, sizeof zero3, &d_kinds);
+                if (!rc)
+                    rc = msspe_conflict_graph_dev(eng.ctx(), static_cast<const uint64_t *>(d_pool), (int)n, kmer_size, &chem,
+                                                  &both, 0, (int)n, 0, (int)n, nullptr, static_cast<uint64_t *>(d_bitmap),
+                                                  static_cast<uint64_t *>(d_kinds));
+                if (!rc) rc = msspe_synchronize(eng.ctx());
+                if (!rc) rc = msspe_device_get(eng.ctx(), d_kinds, sizeof kinds, kinds);
+                if (d_kinds) (void)msspe_device_free(eng.ctx(), d_kinds);
+                if (!rc) note_kinds(*end_rule, n, kinds);
+            } else if (!rc)
                 rc = msspe_cross_dimer_dev(eng.ctx(), static_cast<const uint64_t *>(d_pool), (int)n, kmer_size, &chem,
                                            dg_threshold, 0, (int)n, 0, (int)n, nullptr,
                                            static_cast<uint64_t *>(d_bitmap), nullptr, nullptr);
@@ -2095,7 +2198,7 @@ Selection select_primers(Engine &eng, const DeviceAlignment &aln, const Args &ar
             args.kmer_size, args.thin_mismatches, args.thin_3p_exact, args.thin_min_gain, chem, mode, args.thin_tm,
             std::max(1, args.tubes), args.tubes > 0, cfg.check_cross_dimers, !cfg.check_self_dimers, opts.dg,
             sel.good_f, sel.good_r, sel.tubes,
-            [&](const KmerStat &s, bool barred) { reject(s, barred ? "select_conflict" : "select_unneeded"); });
+            [&](const KmerStat &s, bool barred) { reject(s, barred ? "select_conflict" : "select_unneeded"); }, &opts);
         timer.lap("stage C + selection by coverage");
         return sel;
     }
@@ -2177,8 +2280,10 @@ int run(const Args &args, std::string &stdout_text)
     Engine &eng = *eng_owner;
     const DeviceAlignment aln(eng, records);   // one upload for stage A (both directions) and the report
     timer.lap("engine + alignment upload");
+    std::string kinds_text;   // --max-cross-dimer-end-tm: one line per screen of candidates under both rules
     const NtthalOptions opts{args.mv_conc, args.dv_conc, args.dntp_conc, args.dna_conc,
-                             args.annealing_temp, args.delta_g_threshold};
+                             args.annealing_temp, args.delta_g_threshold, args.cross_dimer_end,
+                             args.max_cross_dimer_end_tm, args.cross_dimer_end ? &kinds_text : nullptr};
     const int bg_mode = args.background_thal == "end1" ? 2 : 1;
     std::unique_ptr<DeviceBackground> background;   // --background: uploaded once, by the first round
     // Round 0 is the run itself: the user's panel and exclusions.  --repick-rounds: round r >= 1 keeps what passed
@@ -2249,6 +2354,7 @@ int run(const Args &args, std::string &stdout_text)
                                             args.coverage_thal == "end1" ? 2 : 1, args.coverage_tm);
     stdout_text += thin_text;
     for (const auto &sel : rounds) stdout_text += sel.select_text;   // (with --tubes its block lists the tubes)
+    stdout_text += kinds_text;
     if (args.tubes > 0 && args.select_by_coverage != "true") stdout_text += tubes_report(good_f, good_r, tubes, args.tubes);
     if (background) {   // the CSV's primers by their CSV names, the panel's by the numbers the CSV continues from
         std::vector<std::string> names, words;

@@ -80,6 +80,11 @@ struct Args {
     std::string coverage_tm_text, coverage_thal;
     float coverage_tm = 0.0f;
     bool coverage_scored = false;
+    // --max-cross-dimer-end-tm <C>: a pair of primers also conflicts when thal END1 of either order holds at C
+    // (od-msspe's SELF_END rule applied to the pair); absent: the dG rule alone, every output as before
+    std::string max_cross_dimer_end_tm_text;
+    float max_cross_dimer_end_tm = 0.0f;
+    bool cross_dimer_end = false;
     // --thin-panel true: after the cover / tube step the primers are thinned to those their coverage needs -- a greedy
     // set cover over "primer p has a match in segment s" within thin_mismatches mismatches, the last thin_3p_exact
     // bases exact (msspe_panel_thin; the panel of --existing-primers is forced); a pick must cover thin_min_gain new
@@ -188,6 +193,9 @@ struct KmerStat {   // main.rs:67-80
 
 struct NtthalOptions {   // delta_g.rs:18-25
     float mv, dv, dntp, conc, t, dg;
+    bool use_end = false;   // --max-cross-dimer-end-tm: the 3'-end rule beside the dG rule (msspe_conflict_rule)
+    float end_tm = 0.0f;
+    std::string *kinds_text = nullptr;   // ... and where a screen under both rules leaves its line for stdout
 };
 
 // Conflict relation produced by the cross-dimer stage: the reference's string-keyed GraphDB
@@ -327,7 +335,8 @@ std::string select_panel_on_device(Engine &eng, const DeviceAlignment &aln, cons
                                    const msspe_chem &chem, int mode, float tm_threshold, int max_tubes, bool list_tubes,
                                    bool screen, bool drop_self_pairs, float dg_threshold, std::vector<KmerStat> &kept_f,
                                    std::vector<KmerStat> &kept_r, std::map<std::string, int> &tubes,
-                                   const std::function<void(const KmerStat &, bool)> &dropped);
+                                   const std::function<void(const KmerStat &, bool)> &dropped,
+                                   const NtthalOptions *end_rule = nullptr);
 // "Panel selection by coverage (<the match rule>, gain >= G, tubes <= T):", the rule line, the primers kept of those
 // offered (forced ones apart), the primers barred, the segments covered (mode 0) or held (modes 1, 2) by all of them
 // and by the kept ones, and with per_tube the primers per tube

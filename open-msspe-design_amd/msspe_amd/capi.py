@@ -21,8 +21,11 @@ EXPORTS = [
     "msspe_cross_dimer_edges_mixed",
     "msspe_cross_dimer_end_dev", "msspe_cross_dimer_end", "msspe_cross_dimer_end_edges_dev", "msspe_cross_dimer_end_edges",
     "msspe_cross_dimer_end_ab_dev", "msspe_cross_dimer_end_ab", "msspe_t_cut",
-    "msspe_conflict_cover_dev", "msspe_conflict_cover",
-    "msspe_conflict_tubes_dev", "msspe_conflict_tubes",
+    "msspe_conflict_graph_dev", "msspe_conflict_graph_ab_dev", "msspe_conflict_graph_edges_dev",
+    "msspe_conflict_graph_ab_edges_dev", "msspe_conflict_graph", "msspe_conflict_graph_edges",
+    "msspe_conflict_graph_ab_edges",
+    "msspe_conflict_cover_dev", "msspe_conflict_cover", "msspe_conflict_cover_rule",
+    "msspe_conflict_tubes_dev", "msspe_conflict_tubes", "msspe_conflict_tubes_rule",
     "msspe_last_overflow_pairs", "msspe_pair_stage_stats", "msspe_pair_stage_samples", "msspe_host_pair_tables", "msspe_host_table_routes", "msspe_host_screen_plan", "msspe_host_split_tables", "msspe_device_put_rows", "msspe_segment_coverage", "msspe_segment_coverage_dev",
     "msspe_device_put", "msspe_device_get", "msspe_device_free", "msspe_thal_detail_pairs", "msspe_profile_enable", "msspe_profile_read",
     "msspe_oligo_stats_dev", "msspe_oligo_stats",
@@ -40,6 +43,7 @@ EXPORTS = [
     "msspe_panel_thin", "msspe_panel_thin_dev", "msspe_panel_thin_packed_dev",
     "msspe_panel_thin_thal", "msspe_panel_thin_thal_dev", "msspe_panel_thin_thal_packed_dev",
     "msspe_panel_select", "msspe_panel_select_bitmap", "msspe_panel_select_dev", "msspe_panel_select_packed_dev",
+    "msspe_panel_select_rule",
     "msspe_device_put_stream_packed", "msspe_background_sites_packed_dev", "msspe_background_sites",
     "msspe_background_thal_packed_dev", "msspe_background_thal",
     "msspe_background_amplicons_packed_dev", "msspe_background_amplicons",
@@ -70,6 +74,22 @@ class Chem(C.Structure):
     @classmethod
     def primer3(cls, mv=50.0, dv=1.5, dntp=0.6, dna_conc=50.0, temp_c=37.0, max_loop=30):
         return cls(mv, dv, dntp, dna_conc, temp_c, max_loop)
+
+
+class ConflictRule(C.Structure):
+    """msspe_conflict_rule: which of the two pair rules count (thal ANY decided on dG, thal END1 decided on t; the row
+    is oligo 1 of END1) and their thresholds.  dg_threshold / end_tm_threshold None: that rule is off."""
+    _fields_ = [("use_any", C.c_int), ("dg_threshold", C.c_float),
+                ("use_end", C.c_int), ("end_tm_threshold", C.c_float)]
+
+    @classmethod
+    def of(cls, dg_threshold: float | None = -9000.0, end_tm_threshold: float | None = None):
+        return cls(int(dg_threshold is not None), 0.0 if dg_threshold is None else dg_threshold,
+                   int(end_tm_threshold is not None), 0.0 if end_tm_threshold is None else end_tm_threshold)
+
+
+KIND_ANY, KIND_END = 1, 2
+KIND_EDGE = np.dtype([("a", np.uint32), ("b", np.uint32), ("kinds", np.uint32), ("reserved", np.uint32)])
 
 
 class KmerOpt(C.Structure):
@@ -223,6 +243,22 @@ def load_library() -> C.CDLL:
     L.msspe_conflict_cover_dev.argtypes = [vp, u64p, C.c_int, C.c_int, u64p, C.c_int, vp, C.POINTER(C.c_int)]
     L.msspe_conflict_cover.argtypes = [vp, C.c_char_p, C.c_int, C.c_int, C.POINTER(Chem), C.c_float, C.c_int, vp,
                                        C.POINTER(C.c_int)]
+    rulep = C.POINTER(ConflictRule)
+    L.msspe_conflict_graph_dev.argtypes = [vp, u64p, C.c_int, C.c_int, C.POINTER(Chem), rulep,
+                                           C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    L.msspe_conflict_graph_edges_dev.argtypes = L.msspe_conflict_graph_dev.argtypes + [vp, C.c_uint64, vp]
+    L.msspe_conflict_graph_ab_dev.argtypes = [vp, u64p, C.c_int, C.c_int, u64p, C.c_int, C.c_int, C.POINTER(Chem), rulep,
+                                              C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    L.msspe_conflict_graph_ab_edges_dev.argtypes = L.msspe_conflict_graph_ab_dev.argtypes + [vp, C.c_uint64, vp]
+    L.msspe_conflict_graph.argtypes = [vp, C.c_char_p, C.c_int, C.c_int, C.POINTER(Chem), rulep, vp, vp, vp]
+    L.msspe_conflict_graph_edges.argtypes = [vp, C.c_char_p, C.c_int, C.c_int, C.POINTER(Chem), rulep, vp, C.c_uint64,
+                                             C.POINTER(C.c_uint64)]
+    L.msspe_conflict_graph_ab_edges.argtypes = [vp, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_int, C.c_int,
+                                                C.POINTER(Chem), rulep, vp, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.msspe_conflict_cover_rule.argtypes = [vp, C.c_char_p, C.c_int, C.c_int, C.POINTER(Chem), rulep, C.c_int, vp,
+                                            C.POINTER(C.c_int)]
+    L.msspe_conflict_tubes_rule.argtypes = [vp, C.c_char_p, C.c_int, C.c_int, C.POINTER(Chem), rulep, C.c_int, C.c_int,
+                                            vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.msspe_conflict_tubes_dev.argtypes = [vp, u64p, C.c_int, C.c_int, u64p, C.c_int, C.c_int, vp, C.POINTER(C.c_int),
                                            C.POINTER(C.c_int)]
     L.msspe_conflict_tubes.argtypes = [vp, C.c_char_p, C.c_int, C.c_int, C.POINTER(Chem), C.c_float, C.c_int, C.c_int,
@@ -297,6 +333,7 @@ def load_library() -> C.CDLL:
     L.msspe_panel_select_packed_dev.argtypes = select_in + [vp] + select_out
     L.msspe_panel_select_bitmap.argtypes = select_in + [vp] + select_out
     L.msspe_panel_select.argtypes = select_in + [C.POINTER(Chem), C.c_float] + select_out
+    L.msspe_panel_select_rule.argtypes = select_in + [C.POINTER(Chem), rulep] + select_out
     L.msspe_device_put_stream_packed.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int,
                                                  C.POINTER(vp), C.POINTER(C.c_size_t), vp]
     L.msspe_background_sites_packed_dev.argtypes = [vp, vp, C.c_size_t, C.c_int, C.POINTER(MismatchOpt), u64p, C.c_int,
@@ -764,16 +801,106 @@ class Engine:
             raise err
         return edges[:count.value], int(count.value)
 
+    # ---- the conflict graph under a pair of rules (thal ANY on dG, thal END1 on t; msspe_conflict_graph*) -----------
+    def conflict_graph(self, pool, chem: Chem | None = None, rule: ConflictRule | None = None):
+        """Whole pool under the rule (msspe_conflict_graph): dict(row_conflicts uint32[n], bitmap uint64 (n, ceil(n/64)),
+        kind_counts uint64[3] = pairs that are ANY only, END only, both).  rule: ConflictRule.of(dg, end_tm)."""
+        buf, n, k = _ascii(pool)
+        chem = chem or Chem.ntthal()
+        rule = rule or ConflictRule.of()
+        rc_ = np.zeros(n, dtype=np.uint32)
+        bm = np.zeros((n, (n + 63) // 64), dtype=np.uint64)
+        kinds = np.zeros(3, dtype=np.uint64)
+        self._check(self.L.msspe_conflict_graph(self.ptr, buf, n, k or 2, C.byref(chem), C.byref(rule), rc_.ctypes.data,
+                                                bm.ctypes.data, kinds.ctypes.data))
+        return {"row_conflicts": rc_, "bitmap": bm, "kind_counts": kinds}
+
+    def conflict_graph_dev(self, d_pool: int, n: int, k: int, chem: Chem, rule: ConflictRule, rows: tuple[int, int],
+                           cols: tuple[int, int], d_row_conflicts: int = 0, d_bitmap: int = 0, d_kind_counts: int = 0):
+        """Device-pointer call over a block (msspe_conflict_graph_dev): row_conflicts uint32[n] +=, the bitmap block
+        cleared and written, kind_counts uint64[3] +=; asynchronous."""
+        self._check(self.L.msspe_conflict_graph_dev(
+            self.ptr, C.c_void_p(d_pool), n, k, C.byref(chem), C.byref(rule), rows[0], rows[1], cols[0], cols[1],
+            C.c_void_p(d_row_conflicts), C.c_void_p(d_bitmap), C.c_void_p(d_kind_counts)))
+
+    def conflict_graph_ab_dev(self, d_a: int, n_a: int, k_a: int, d_b: int, n_b: int, k_b: int, chem: Chem,
+                              rule: ConflictRule, rows: tuple[int, int], cols: tuple[int, int],
+                              d_row_conflicts: int = 0, d_bitmap: int = 0, d_kind_counts: int = 0):
+        """Rows [rows) of A (oligo 1 of the END rule) x columns [cols) of B (msspe_conflict_graph_ab_dev); asynchronous."""
+        self._check(self.L.msspe_conflict_graph_ab_dev(
+            self.ptr, C.c_void_p(d_a), n_a, k_a, C.c_void_p(d_b), n_b, k_b, C.byref(chem), C.byref(rule),
+            rows[0], rows[1], cols[0], cols[1], C.c_void_p(d_row_conflicts), C.c_void_p(d_bitmap),
+            C.c_void_p(d_kind_counts)))
+
+    def conflict_graph_edges_dev(self, d_pool: int, n: int, k: int, chem: Chem, rule: ConflictRule,
+                                 rows: tuple[int, int], cols: tuple[int, int], d_edges: int, capacity: int,
+                                 d_count: int, d_row_conflicts: int = 0, d_bitmap: int = 0, d_kind_counts: int = 0):
+        """Device-pointer ordered edge list of a block (msspe_conflict_graph_edges_dev: 16-byte records a, b, kinds,
+        reserved in ascending (a, b); *d_count may exceed the capacity = truncated); asynchronous."""
+        self._check(self.L.msspe_conflict_graph_edges_dev(
+            self.ptr, C.c_void_p(d_pool), n, k, C.byref(chem), C.byref(rule), rows[0], rows[1], cols[0], cols[1],
+            C.c_void_p(d_row_conflicts), C.c_void_p(d_bitmap), C.c_void_p(d_kind_counts), C.c_void_p(d_edges), capacity,
+            C.c_void_p(d_count)))
+
+    def conflict_graph_ab_edges_dev(self, d_a: int, n_a: int, k_a: int, d_b: int, n_b: int, k_b: int, chem: Chem,
+                                    rule: ConflictRule, rows: tuple[int, int], cols: tuple[int, int], d_edges: int,
+                                    capacity: int, d_count: int, d_row_conflicts: int = 0, d_bitmap: int = 0,
+                                    d_kind_counts: int = 0):
+        """The A x B block as an ordered edge list (msspe_conflict_graph_ab_edges_dev: a = A index, b = B index)."""
+        self._check(self.L.msspe_conflict_graph_ab_edges_dev(
+            self.ptr, C.c_void_p(d_a), n_a, k_a, C.c_void_p(d_b), n_b, k_b, C.byref(chem), C.byref(rule),
+            rows[0], rows[1], cols[0], cols[1], C.c_void_p(d_row_conflicts), C.c_void_p(d_bitmap),
+            C.c_void_p(d_kind_counts), C.c_void_p(d_edges), capacity, C.c_void_p(d_count)))
+
+    def _kind_edges(self, call, capacity: int):
+        edges = np.zeros(capacity, dtype=KIND_EDGE)
+        count = C.c_uint64()
+        rc = call(edges.ctypes.data if capacity else None, capacity, C.byref(count))
+        if rc:
+            err = MsspeError(rc, self.L.msspe_last_error(self.ptr).decode())
+            err.count = int(count.value)
+            err.edges = edges
+            raise err
+        return edges[:count.value], int(count.value)
+
+    def conflict_graph_edges(self, pool, chem: Chem | None = None, rule: ConflictRule | None = None,
+                             capacity: int = 1 << 20):
+        """Ordered edge list of the whole pool under the rule (msspe_conflict_graph_edges): (edges [a, b, kinds,
+        reserved] ascending in (a, b), count); raises MsspeError (MSSPE_ERR_CAPACITY, .count = edges needed, .edges =
+        the first `capacity`) when the capacity is too small."""
+        buf, n, k = _ascii(pool)
+        chem = chem or Chem.ntthal()
+        rule = rule or ConflictRule.of()
+        return self._kind_edges(lambda e, cap, cnt: self.L.msspe_conflict_graph_edges(
+            self.ptr, buf, n, k or 2, C.byref(chem), C.byref(rule), e, cap, cnt), capacity)
+
+    def conflict_graph_ab_edges(self, a, b, chem: Chem | None = None, rule: ConflictRule | None = None,
+                                capacity: int = 1 << 20):
+        """Ordered edge list of A x B under the rule (msspe_conflict_graph_ab_edges; A is oligo 1 of the END rule)."""
+        abuf, n_a, k_a = _ascii(a)
+        bbuf, n_b, k_b = _ascii(b)
+        k_a, k_b = k_a or k_b or 2, k_b or k_a or 2   # an empty pool's length does not matter
+        chem = chem or Chem.ntthal()
+        rule = rule or ConflictRule.of()
+        return self._kind_edges(lambda e, cap, cnt: self.L.msspe_conflict_graph_ab_edges(
+            self.ptr, abuf, n_a, k_a, bbuf, n_b, k_b, C.byref(chem), C.byref(rule), e, cap, cnt), capacity)
+
     # ---- the greedy vertex cover of the conflict graph (od-msspe/src/main.rs:754-798; msspe_conflict_cover*) ------
     def conflict_cover(self, pool, chem: Chem | None = None, threshold: float = -9000.0,
-                       drop_self_pairs: bool = False) -> np.ndarray:
+                       drop_self_pairs: bool = False, end_tm_threshold: float | None = None) -> np.ndarray:
         """Screen a pool of distinct oligos of one length and cover its conflict graph on the device
         (msspe_conflict_cover): bool[n], True = removed by the reference's greedy cover.  drop_self_pairs: the
-        reference's --check-self-dimers false.  Rounds of the call: info("cover_rounds")."""
+        reference's --check-self-dimers false.  Rounds of the call: info("cover_rounds").  end_tm_threshold: the graph is
+        that of the rule (ANY at threshold, END at end_tm_threshold; msspe_conflict_cover_rule)."""
         buf, n, k = _ascii(pool)
         chem = chem or Chem.ntthal()
         out = np.zeros(n, dtype=np.uint8)
         nd = C.c_int(0)
+        if end_tm_threshold is not None:
+            rule = ConflictRule.of(threshold, end_tm_threshold)
+            self._check(self.L.msspe_conflict_cover_rule(self.ptr, buf, n, k or 2, C.byref(chem), C.byref(rule),
+                                                         int(bool(drop_self_pairs)), out.ctypes.data, C.byref(nd)))
+            return out.astype(bool)
         self._check(self.L.msspe_conflict_cover(self.ptr, buf, n, k or 2, C.byref(chem), C.c_float(threshold),
                                                 int(bool(drop_self_pairs)), out.ctypes.data, C.byref(nd)))
         return out.astype(bool)
@@ -789,14 +916,21 @@ class Engine:
 
     # ---- the conflict graph split into reaction tubes (engine extension; msspe_conflict_tubes*) --------------------
     def conflict_tubes(self, pool, chem: Chem | None = None, threshold: float = -9000.0, max_tubes: int = 8,
-                       drop_self_pairs: bool = False):
+                       drop_self_pairs: bool = False, end_tm_threshold: float | None = None):
         """Screen a pool of distinct oligos of one length and split it into at most max_tubes (1..64) tubes in which
         no two oligos conflict (msspe_conflict_tubes): (uint8[n], tubes_used, unplaced); 255 (MSSPE_TUBE_NONE) marks an
-        oligo in no tube.  Rounds of the call: info("tube_rounds")."""
+        oligo in no tube.  Rounds of the call: info("tube_rounds").  end_tm_threshold: the graph is that of the rule (ANY at
+        threshold, END at end_tm_threshold; msspe_conflict_tubes_rule)."""
         buf, n, k = _ascii(pool)
         chem = chem or Chem.ntthal()
         out = np.zeros(n, dtype=np.uint8)
         used, unplaced = C.c_int(0), C.c_int(0)
+        if end_tm_threshold is not None:
+            rule = ConflictRule.of(threshold, end_tm_threshold)
+            self._check(self.L.msspe_conflict_tubes_rule(self.ptr, buf, n, k or 2, C.byref(chem), C.byref(rule),
+                                                         int(bool(drop_self_pairs)), int(max_tubes), out.ctypes.data,
+                                                         C.byref(used), C.byref(unplaced)))
+            return out, int(used.value), int(unplaced.value)
         self._check(self.L.msspe_conflict_tubes(self.ptr, buf, n, k or 2, C.byref(chem), C.c_float(threshold),
                                                 int(bool(drop_self_pairs)), int(max_tubes), out.ctypes.data,
                                                 C.byref(used), C.byref(unplaced)))
@@ -1109,14 +1243,15 @@ class Engine:
     # ---- a conflict-free panel selected by coverage (engine extension; msspe_panel_select*) ----------------------
     def panel_select(self, genomes, opt: KmerOpt, fwd, rev, rule: SeedRule, bitmap=None, max_tubes: int = 1,
                      min_gain: int = 1, drop_self_pairs: bool = False, forced=None, form: str = "bitmap",
-                     chem: Chem | None = None, threshold: float = -9000.0):
+                     chem: Chem | None = None, threshold: float = -9000.0, end_tm_threshold: float | None = None):
         """Greedy set cover in which a pick bars its conflict neighbours from its tube (msspe_panel_select*).
         genomes, fwd, rev, forced as panel_thin; rule: seed_rule(M, E[, mode, chem, tm]) says what a primer covers.
         form "bitmap": `bitmap` is a host uint64 (n, ceil(n/64)) array (the layout of cross_dimer_dev over the pool
         forward words then reverse words) and the alignment goes over from the host; "dev" / "packed": the alignment is
         uploaded (as bytes / packed rows) or resident as (device address, n_seq, seq_len), and `bitmap` is either such
         an array (uploaded for the call) or a device address; "screen": the call screens the pool itself at `chem`
-        (default Chem.ntthal()) and `threshold`.  Returns a dict: keep, order, gains, tube, barred (uint8[n]), covered
+        (default Chem.ntthal()) and `threshold`, with end_tm_threshold under the rule (ANY at threshold, END at
+        end_tm_threshold; msspe_panel_select_rule).  Returns a dict: keep, order, gains, tube, barred (uint8[n]), covered
         (n_seq, P), covered_all, covered_kept, tubes_used."""
         if form not in ("bitmap", "dev", "packed", "screen"):
             raise ValueError("form must be 'bitmap', 'dev', 'packed' or 'screen'")
@@ -1145,6 +1280,9 @@ class Engine:
             if form == "screen":
                 chem = chem or Chem.ntthal()
                 graph = (C.byref(chem), C.c_float(threshold))
+                if end_tm_threshold is not None:
+                    conflict_rule = ConflictRule.of(threshold, end_tm_threshold)
+                    graph = (C.byref(chem), C.byref(conflict_rule))
             elif isinstance(bitmap, (int, np.integer)) and form != "bitmap":
                 graph = (C.c_void_p(int(bitmap)),)
             else:
@@ -1161,6 +1299,8 @@ class Engine:
                     graph = (C.c_void_p(owned[-1]),)
             fn = {"bitmap": self.L.msspe_panel_select_bitmap, "dev": self.L.msspe_panel_select_dev,
                   "packed": self.L.msspe_panel_select_packed_dev, "screen": self.L.msspe_panel_select}[form]
+            if form == "screen" and end_tm_threshold is not None:
+                fn = self.L.msspe_panel_select_rule
             P = 0 if seq_len < opt.segment_size else (seq_len - opt.segment_size) // opt.overlap_size + 1
             flags = None if forced is None else np.ascontiguousarray(np.asarray(forced) != 0, dtype=np.uint8)
             if flags is not None and flags.shape != (n,):
