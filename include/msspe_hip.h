@@ -216,6 +216,9 @@ int msspe_set_option(msspe_ctx *ctx, const char *key, const char *value);
  *   "panel_thin_incidence_us" / "panel_thin_gain0_us" / "panel_thin_rounds_us"
  *                     the same call's device time of its phases: the incidence pass, the forced rows and first gains,
  *                     the rounds
+ *   "panel_thin_depth_shadows" / "panel_thin_depth_colsum_us"
+ *                     the last msspe_panel_thin_depth* / msspe_panel_thin_thal_depth* call: primers left out as
+ *                     duplicates of a word, device time of the column-sum passes
  *   "hand_over_list_0" .. "hand_over_list_6"
  *                     pairs that entered hand-over list q of the cross-dimer calls (ANY and END) since the last read
  *                     of that key; reading synchronises the context's stream and resets the key, as
@@ -1266,6 +1269,76 @@ int msspe_panel_thin_thal_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, i
                                      const uint8_t *forced, uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out,
                                      int *n_picked_out, uint8_t *covered_out, long long *covered_all_out,
                                      long long *covered_kept_out);
+
+/* ---- a panel thinned to a coverage depth: R primers on every segment (engine extension, no reference counterpart;
+ * DESIGN.md 4.15) ----
+ * msspe_panel_thin* and msspe_panel_thin_thal* leave many segments on exactly one primer; one mutation under its 3' end
+ * loses the segment.  These calls keep at least R primers on every segment wherever the panel has that many.  The
+ * inputs are the sibling's, with msspe_thin_depth_opt {min_gain >= 1, depth R in 1..255} in place of msspe_thin_opt.
+ *   Incidence.  I[p][s] of msspe_panel_thin*; the thal forms use the held incidence H of msspe_panel_thin_thal*.
+ *   Shadows.  Among primers with the same (direction, word) one is the representative: the forced one of lowest index
+ *     if any is forced, otherwise the lowest index.  All the others are shadows: a shadow counts in nothing, is never
+ *     picked, and its keep_out is its forced flag.  (At depth 2 a word listed twice would otherwise pass for two
+ *     primers.)  A forward word equal to a reverse word is no duplicate: the two look in different windows.
+ *   Counters.  depth_all[s] = representatives with I[p][s]; need[s] = min(R, depth_all[s]); cnt[s] starts as
+ *     min(need[s], forced representatives with I[p][s]); s is open while cnt[s] < need[s].
+ *   Rounds.  gain(p) = open segments with I[p][s], over the representatives neither forced nor picked; the greatest
+ *     gain is picked, ties to the lowest index; below min_gain the loop ends and nothing is picked in that round;
+ *     otherwise p joins the order with its gain and cnt[s] += 1 on every open s with I[p][s].
+ *   Outputs.  keep_out[n], order_out, gain_out, *n_picked_out as msspe_panel_thin*.  depth_all_out / depth_kept_out
+ *     (optional host arrays, n_seq * P bytes, s = r * P + j): representatives per segment among all primers and among
+ *     the kept ones, saturating at 255; depth_kept is the true column sum, not cnt.  counts_out[4] (optional):
+ *     segments with depth_all >= 1, depth_kept >= 1, depth_all >= R, depth_kept >= R.
+ *   Guarantee at min_gain 1: depth_kept[s] >= min(R, depth_all[s]) for every s (an open segment at the end would give
+ *     an unpicked live representative a gain of 1), so counts[1] == counts[0] and counts[3] == counts[2].
+ *   At depth 1 keep_out, order_out, gain_out, *n_picked_out and "panel_thin_rounds" are those of the sibling on the same
+ *     inputs, duplicates and forced flags included.  As in the siblings, the best mismatch count per segment (thal
+ *     forms: t_best) is NOT preserved.
+ * Errors: those of the sibling, plus MSSPE_ERR_ARG for a depth outside 1..255.  n == 0 or no segments: as the sibling,
+ * with the counts zeroed.  The calls share "panel_thin_matrix_max_mb" and every buffer of the thinning; once the buffers
+ * have grown to a call's size, the calls allocate nothing.  msspe_get_info: the "panel_thin_*" and "panel_thin_thal_*"
+ * keys describe these calls too; "panel_thin_depth_shadows" is the last depth call's number of shadows,
+ * "panel_thin_depth_colsum_us" its device time in the three column-sum passes (all, forced, kept) and the needs. */
+typedef struct { int min_gain; int depth; } msspe_thin_depth_opt;   /* min_gain >= 1, depth 1..255 */
+int msspe_panel_thin_depth(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len, const msspe_kmer_opt *opt,
+                           const msspe_mismatch_opt *mm, const msspe_thin_depth_opt *thin, const uint64_t *fwd_words,
+                           int n_fwd, const uint64_t *rev_words, int n_rev, const uint8_t *forced, uint8_t *keep_out,
+                           uint32_t *order_out, uint32_t *gain_out, int *n_picked_out, uint8_t *depth_all_out,
+                           uint8_t *depth_kept_out, long long *counts_out);
+int msspe_panel_thin_depth_dev(msspe_ctx *ctx, const uint8_t *d_seqs, int n_seq, size_t seq_len,
+                               const msspe_kmer_opt *opt, const msspe_mismatch_opt *mm,
+                               const msspe_thin_depth_opt *thin, const uint64_t *fwd_words, int n_fwd,
+                               const uint64_t *rev_words, int n_rev, const uint8_t *forced, uint8_t *keep_out,
+                               uint32_t *order_out, uint32_t *gain_out, int *n_picked_out, uint8_t *depth_all_out,
+                               uint8_t *depth_kept_out, long long *counts_out);
+int msspe_panel_thin_depth_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
+                                      const msspe_kmer_opt *opt, const msspe_mismatch_opt *mm,
+                                      const msspe_thin_depth_opt *thin, const uint64_t *fwd_words, int n_fwd,
+                                      const uint64_t *rev_words, int n_rev, const uint8_t *forced, uint8_t *keep_out,
+                                      uint32_t *order_out, uint32_t *gain_out, int *n_picked_out,
+                                      uint8_t *depth_all_out, uint8_t *depth_kept_out, long long *counts_out);
+int msspe_panel_thin_thal_depth(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len,
+                                const msspe_kmer_opt *opt, const msspe_mismatch_opt *mm,
+                                const msspe_thin_depth_opt *thin, const msspe_chem *chem, int mode, float tm_threshold,
+                                const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
+                                const uint8_t *forced, uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out,
+                                int *n_picked_out, uint8_t *depth_all_out, uint8_t *depth_kept_out,
+                                long long *counts_out);
+int msspe_panel_thin_thal_depth_dev(msspe_ctx *ctx, const uint8_t *d_seqs, int n_seq, size_t seq_len,
+                                    const msspe_kmer_opt *opt, const msspe_mismatch_opt *mm,
+                                    const msspe_thin_depth_opt *thin, const msspe_chem *chem, int mode,
+                                    float tm_threshold, const uint64_t *fwd_words, int n_fwd,
+                                    const uint64_t *rev_words, int n_rev, const uint8_t *forced, uint8_t *keep_out,
+                                    uint32_t *order_out, uint32_t *gain_out, int *n_picked_out,
+                                    uint8_t *depth_all_out, uint8_t *depth_kept_out, long long *counts_out);
+int msspe_panel_thin_thal_depth_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
+                                           const msspe_kmer_opt *opt, const msspe_mismatch_opt *mm,
+                                           const msspe_thin_depth_opt *thin, const msspe_chem *chem, int mode,
+                                           float tm_threshold, const uint64_t *fwd_words, int n_fwd,
+                                           const uint64_t *rev_words, int n_rev, const uint8_t *forced,
+                                           uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out,
+                                           int *n_picked_out, uint8_t *depth_all_out, uint8_t *depth_kept_out,
+                                           long long *counts_out);
 
 /* ---- a conflict-free panel selected by coverage: set cover under conflicts (engine extension, no reference
  * counterpart) ----

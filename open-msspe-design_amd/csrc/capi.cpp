@@ -905,6 +905,8 @@ int msspe_get_info(msspe_ctx *ctx, const char *key, long long *value_out)
     else if (k == "panel_thin_incidence_us") *value_out = ctx->thin.phase_us()[0];
     else if (k == "panel_thin_gain0_us") *value_out = ctx->thin.phase_us()[1];
     else if (k == "panel_thin_rounds_us") *value_out = ctx->thin.phase_us()[2];
+    else if (k == "panel_thin_depth_shadows") *value_out = ctx->thin.depth_shadows();
+    else if (k == "panel_thin_depth_colsum_us") *value_out = ctx->thin.depth_colsum_us();
     else if (k == "panel_select_rounds") *value_out = ctx->select.n_rounds();
     else if (k == "panel_select_tubes") *value_out = ctx->select.tubes_used();
     else if (k == "panel_select_barred") *value_out = ctx->select.barred();
@@ -2909,6 +2911,75 @@ int msspe_panel_thin(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_
     return rc;
 }
 
+static int panel_thin_depth_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t seq_len,
+                                 const msspe_kmer_opt *opt, const msspe_mismatch_opt *mm,
+                                 const msspe_thin_depth_opt *thin, const uint64_t *fwd_words, int n_fwd,
+                                 const uint64_t *rev_words, int n_rev, const uint8_t *forced, uint8_t *keep_out,
+                                 uint32_t *order_out, uint32_t *gain_out, int *n_picked_out, uint8_t *depth_all_out,
+                                 uint8_t *depth_kept_out, long long *counts_out)
+{
+    if (!opt || !mm || !thin || !keep_out || !order_out || !gain_out || !n_picked_out || n_fwd < 0 || n_rev < 0 ||
+        (n_fwd && !fwd_words) || (n_rev && !rev_words))
+        return fail(ctx, MSSPE_ERR_ARG, "panel thin: null argument");
+    if (thin->min_gain < 1) return fail(ctx, MSSPE_ERR_ARG, "panel thin: min_gain must be at least 1");
+    if (thin->depth < 1 || thin->depth > 255) return fail(ctx, MSSPE_ERR_ARG, "panel thin: depth must be 1..255");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::string err;
+    const int rc = ctx->thin.run_depth(ctx->mm_cov, view, n_seq, seq_len, *opt, mm->max_mismatches, mm->exact_3p,
+                                       thin->min_gain, thin->depth, fwd_words, n_fwd, rev_words, n_rev, forced,
+                                       keep_out, order_out, gain_out, n_picked_out, depth_all_out, depth_kept_out,
+                                       counts_out, (size_t)ctx->opt.panel_thin_matrix_max_mb << 20, ctx->n_cu,
+                                       ctx->stream, err);
+    if (rc) return fail(ctx, rc, err);
+    return MSSPE_OK;
+}
+
+int msspe_panel_thin_depth_dev(msspe_ctx *ctx, const uint8_t *d_seqs, int n_seq, size_t seq_len,
+                               const msspe_kmer_opt *opt, const msspe_mismatch_opt *mm,
+                               const msspe_thin_depth_opt *thin, const uint64_t *fwd_words, int n_fwd,
+                               const uint64_t *rev_words, int n_rev, const uint8_t *forced, uint8_t *keep_out,
+                               uint32_t *order_out, uint32_t *gain_out, int *n_picked_out, uint8_t *depth_all_out,
+                               uint8_t *depth_kept_out, long long *counts_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!d_seqs) return fail(ctx, MSSPE_ERR_ARG, "null sequences");
+    return panel_thin_depth_view(ctx, SeqView{d_seqs, nullptr, seq_len}, n_seq, seq_len, opt, mm, thin, fwd_words,
+                                 n_fwd, rev_words, n_rev, forced, keep_out, order_out, gain_out, n_picked_out,
+                                 depth_all_out, depth_kept_out, counts_out);
+}
+
+int msspe_panel_thin_depth_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
+                                      const msspe_kmer_opt *opt, const msspe_mismatch_opt *mm,
+                                      const msspe_thin_depth_opt *thin, const uint64_t *fwd_words, int n_fwd,
+                                      const uint64_t *rev_words, int n_rev, const uint8_t *forced, uint8_t *keep_out,
+                                      uint32_t *order_out, uint32_t *gain_out, int *n_picked_out,
+                                      uint8_t *depth_all_out, uint8_t *depth_kept_out, long long *counts_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!d_packed) return fail(ctx, MSSPE_ERR_ARG, "null sequences");
+    return panel_thin_depth_view(ctx, SeqView{nullptr, d_packed, seq_len}, n_seq, seq_len, opt, mm, thin, fwd_words,
+                                 n_fwd, rev_words, n_rev, forced, keep_out, order_out, gain_out, n_picked_out,
+                                 depth_all_out, depth_kept_out, counts_out);
+}
+
+int msspe_panel_thin_depth(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len, const msspe_kmer_opt *opt,
+                           const msspe_mismatch_opt *mm, const msspe_thin_depth_opt *thin, const uint64_t *fwd_words,
+                           int n_fwd, const uint64_t *rev_words, int n_rev, const uint8_t *forced, uint8_t *keep_out,
+                           uint32_t *order_out, uint32_t *gain_out, int *n_picked_out, uint8_t *depth_all_out,
+                           uint8_t *depth_kept_out, long long *counts_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!seqs || n_seq < 0) return fail(ctx, MSSPE_ERR_ARG, "null sequences");
+    void *d = nullptr;
+    int rc = msspe_device_put(ctx, seqs, (size_t)n_seq * seq_len, &d);
+    if (rc) return rc;
+    rc = msspe_panel_thin_depth_dev(ctx, (const uint8_t *)d, n_seq, seq_len, opt, mm, thin, fwd_words, n_fwd, rev_words,
+                                    n_rev, forced, keep_out, order_out, gain_out, n_picked_out, depth_all_out,
+                                    depth_kept_out, counts_out);
+    (void)msspe_device_free(ctx, d);
+    return rc;
+}
+
 int msspe_device_put(msspe_ctx *ctx, const void *host, size_t bytes, void **device_out)
 {
     if (!ctx) return MSSPE_ERR_ARG;
@@ -3732,12 +3803,18 @@ int panel_thin_thal_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t 
                          float tm_threshold, const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words,
                          int n_rev, const uint8_t *forced, uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out,
                          int *n_picked_out, uint8_t *covered_out, long long *covered_all_out,
-                         long long *covered_kept_out)
+                         long long *covered_kept_out, const msspe_thin_depth_opt *deep = nullptr,
+                         uint8_t *depth_all_out = nullptr, uint8_t *depth_kept_out = nullptr,
+                         long long *counts_out = nullptr)
 {
-    if (!opt || !mm || !thin || !chem || !keep_out || !order_out || !gain_out || !n_picked_out || n_fwd < 0 ||
+    // deep: msspe_panel_thin_thal_depth* (thin is NULL then, and the three covered outputs are not used)
+    if (!opt || !mm || (!thin && !deep) || !chem || !keep_out || !order_out || !gain_out || !n_picked_out || n_fwd < 0 ||
         n_rev < 0 || (n_fwd && !fwd_words) || (n_rev && !rev_words))
         return fail(ctx, MSSPE_ERR_ARG, "panel thin thal: null argument");
-    if (thin->min_gain < 1) return fail(ctx, MSSPE_ERR_ARG, "panel thin thal: min_gain must be at least 1");
+    const int min_gain = deep ? deep->min_gain : thin->min_gain;
+    if (min_gain < 1) return fail(ctx, MSSPE_ERR_ARG, "panel thin thal: min_gain must be at least 1");
+    if (deep && (deep->depth < 1 || deep->depth > 255))
+        return fail(ctx, MSSPE_ERR_ARG, "panel thin thal: depth must be 1..255");
     if (mode != 1 && mode != 2) return fail(ctx, MSSPE_ERR_ARG, "panel thin thal: mode must be 1 (ANY) or 2 (END1)");
     auto &tt = ctx->thin_thal;
     tt.matches = tt.unique_pairs = tt.slabs = tt.redone = 0;
@@ -3745,6 +3822,7 @@ int panel_thin_thal_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t 
     *n_picked_out = 0;
     if (covered_all_out) *covered_all_out = 0;
     if (covered_kept_out) *covered_kept_out = 0;
+    if (counts_out) std::fill(counts_out, counts_out + 4, 0LL);
     const int k = opt->kmer_size;
     if (k < 2 || k > 31) return fail(ctx, MSSPE_ERR_K, "panel thin thal: unsupported k (need 2 <= k <= 31)");
     std::string err;
@@ -3758,6 +3836,8 @@ int panel_thin_thal_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t 
     const long n_seg = P * n_seq;
     for (int p = 0; p < n; ++p) keep_out[p] = forced && forced[p] ? 1 : 0;
     if (covered_out) std::fill(covered_out, covered_out + n_seg, (uint8_t)0);
+    if (depth_all_out) std::fill(depth_all_out, depth_all_out + n_seg, (uint8_t)0);
+    if (depth_kept_out) std::fill(depth_kept_out, depth_kept_out + n_seg, (uint8_t)0);
     if (n == 0 || n_seg == 0) return MSSPE_OK;
     const size_t cap = (size_t)1 << ctx->opt.site_list_cap_log2;
     if ((uint64_t)n + cap >= (1ull << 31)) return fail(ctx, MSSPE_ERR_ARG, "panel thin thal: too many primers");
@@ -3778,9 +3858,17 @@ int panel_thin_thal_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t 
     bool scored = false;
     if ((rc = fill_held_matrix(ctx, view, n_seg, P, opt, mm, ce, end1, fwd_words, n_fwd, rev_words, n_rev, d_inc, scored)))
         return rc;
-    if ((rc = ctx->thin.rounds(n, n_seg, S, thin->min_gain, keep_out, order_out, gain_out, n_picked_out, covered_out,
-                               covered_all_out, covered_kept_out, ctx->n_cu, ctx->stream, err)))
-        return fail(ctx, rc, err);
+    if (deep) {
+        std::vector<uint8_t> shadow((size_t)n);
+        (void)PanelThin::shadows(fwd_words, n_fwd, rev_words, n_rev, forced, shadow.data());
+        rc = ctx->thin.rounds_depth(n, n_seg, S, min_gain, deep->depth, shadow.data(), keep_out, order_out, gain_out,
+                                    n_picked_out, depth_all_out, depth_kept_out, counts_out, ctx->n_cu, ctx->stream,
+                                    err);
+    } else {
+        rc = ctx->thin.rounds(n, n_seg, S, min_gain, keep_out, order_out, gain_out, n_picked_out, covered_out,
+                              covered_all_out, covered_kept_out, ctx->n_cu, ctx->stream, err);
+    }
+    if (rc) return fail(ctx, rc, err);
     thin_thal_read_scored(ctx, scored);   // rounds returned with the stream idle
     return MSSPE_OK;
 }
@@ -4234,6 +4322,59 @@ int msspe_panel_thin_thal(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t
     rc = msspe_panel_thin_thal_dev(ctx, (const uint8_t *)d, n_seq, seq_len, opt, mm, thin, chem, mode, tm_threshold,
                                    fwd_words, n_fwd, rev_words, n_rev, forced, keep_out, order_out, gain_out,
                                    n_picked_out, covered_out, covered_all_out, covered_kept_out);
+    (void)msspe_device_free(ctx, d);
+    return rc;
+}
+
+int msspe_panel_thin_thal_depth_dev(msspe_ctx *ctx, const uint8_t *d_seqs, int n_seq, size_t seq_len,
+                                    const msspe_kmer_opt *opt, const msspe_mismatch_opt *mm,
+                                    const msspe_thin_depth_opt *thin, const msspe_chem *chem, int mode,
+                                    float tm_threshold, const uint64_t *fwd_words, int n_fwd,
+                                    const uint64_t *rev_words, int n_rev, const uint8_t *forced, uint8_t *keep_out,
+                                    uint32_t *order_out, uint32_t *gain_out, int *n_picked_out,
+                                    uint8_t *depth_all_out, uint8_t *depth_kept_out, long long *counts_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!d_seqs) return fail(ctx, MSSPE_ERR_ARG, "null sequences");
+    return panel_thin_thal_view(ctx, SeqView{d_seqs, nullptr, seq_len}, n_seq, seq_len, opt, mm, nullptr, chem, mode,
+                                tm_threshold, fwd_words, n_fwd, rev_words, n_rev, forced, keep_out, order_out, gain_out,
+                                n_picked_out, nullptr, nullptr, nullptr, thin, depth_all_out, depth_kept_out,
+                                counts_out);
+}
+
+int msspe_panel_thin_thal_depth_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
+                                           const msspe_kmer_opt *opt, const msspe_mismatch_opt *mm,
+                                           const msspe_thin_depth_opt *thin, const msspe_chem *chem, int mode,
+                                           float tm_threshold, const uint64_t *fwd_words, int n_fwd,
+                                           const uint64_t *rev_words, int n_rev, const uint8_t *forced,
+                                           uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out,
+                                           int *n_picked_out, uint8_t *depth_all_out, uint8_t *depth_kept_out,
+                                           long long *counts_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!d_packed) return fail(ctx, MSSPE_ERR_ARG, "null sequences");
+    return panel_thin_thal_view(ctx, SeqView{nullptr, d_packed, seq_len}, n_seq, seq_len, opt, mm, nullptr, chem, mode,
+                                tm_threshold, fwd_words, n_fwd, rev_words, n_rev, forced, keep_out, order_out, gain_out,
+                                n_picked_out, nullptr, nullptr, nullptr, thin, depth_all_out, depth_kept_out,
+                                counts_out);
+}
+
+int msspe_panel_thin_thal_depth(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len,
+                                const msspe_kmer_opt *opt, const msspe_mismatch_opt *mm,
+                                const msspe_thin_depth_opt *thin, const msspe_chem *chem, int mode, float tm_threshold,
+                                const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
+                                const uint8_t *forced, uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out,
+                                int *n_picked_out, uint8_t *depth_all_out, uint8_t *depth_kept_out,
+                                long long *counts_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!seqs || n_seq < 0) return fail(ctx, MSSPE_ERR_ARG, "null sequences");
+    void *d = nullptr;
+    int rc = msspe_device_put(ctx, seqs, (size_t)n_seq * seq_len, &d);
+    if (rc) return rc;
+    rc = msspe_panel_thin_thal_depth_dev(ctx, (const uint8_t *)d, n_seq, seq_len, opt, mm, thin, chem, mode,
+                                         tm_threshold, fwd_words, n_fwd, rev_words, n_rev, forced, keep_out, order_out,
+                                         gain_out, n_picked_out, depth_all_out, depth_kept_out, counts_out);
     (void)msspe_device_free(ctx, d);
     return rc;
 }

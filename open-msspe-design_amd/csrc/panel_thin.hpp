@@ -35,7 +35,27 @@ public:
     int rounds(int n, long n_seg, int S, int min_gain, uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out,
                int *n_picked_out, uint8_t *covered_out, long long *covered_all_out, long long *covered_kept_out,
                int n_cu, hipStream_t stream, std::string &err);
+    // Depth (msspe_panel_thin_depth*): every segment keeps min(depth, primers it has) primers.  run's
+    // arguments plus depth (1..255, checked by the caller); depth_all_out / depth_kept_out (optional, n_seq * P bytes):
+    // representatives per segment among all and among the kept, saturating at 255; counts_out[4] (optional): segments
+    // with depth_all >= 1, depth_kept >= 1, depth_all >= depth, depth_kept >= depth.  rounds_depth is rounds' sibling
+    // for a caller that fills the matrix itself; shadow (host, n flags): primers that count in nothing and are never
+    // picked.  shadows() marks them: among primers of one direction with the same word, all but the forced one of
+    // lowest index (without a forced one, the lowest index); returns how many.
+    int run_depth(MismatchCoverage &cov, const SeqView &seqs, int n_seq, size_t seq_len, const msspe_kmer_opt &opt,
+                  int max_mismatches, int exact_3p, int min_gain, int depth, const uint64_t *fwd_words, int n_fwd,
+                  const uint64_t *rev_words, int n_rev, const uint8_t *forced, uint8_t *keep_out, uint32_t *order_out,
+                  uint32_t *gain_out, int *n_picked_out, uint8_t *depth_all_out, uint8_t *depth_kept_out,
+                  long long *counts_out, size_t max_matrix_bytes, int n_cu, hipStream_t stream, std::string &err);
+    int rounds_depth(int n, long n_seg, int S, int min_gain, int depth, const uint8_t *shadow, uint8_t *keep_out,
+                     uint32_t *order_out, uint32_t *gain_out, int *n_picked_out, uint8_t *depth_all_out,
+                     uint8_t *depth_kept_out, long long *counts_out, int n_cu, hipStream_t stream, std::string &err);
+    static int shadows(const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
+                       const uint8_t *forced, uint8_t *shadow_out);
     void release();
+    // the last depth run: shadows among its primers, device time of the three column-sum passes and the init
+    long long depth_shadows() const { return shadows_; }
+    long long depth_colsum_us() const { return colsum_us_; }
     // the last run: rounds enqueued that ran (the picks and the one that stopped), segment groups (matrix rows), and
     // device time in microseconds of the incidence pass, the first gains and the rounds
     long long rounds() const { return rounds_; }
@@ -43,11 +63,12 @@ public:
     const long long *phase_us() const { return phase_us_; }
 
 private:
-    enum { kSlots = 8 };
+    enum { kSlots = 10 };
     void *buf_[kSlots] = {};
     size_t cap_[kSlots] = {};
     hipEvent_t ev_[4] = {};
-    long long rounds_ = 0, groups_ = 0;
+    hipEvent_t ev_depth_[2] = {};   // after the first column sums and the init; after the kept column sums
+    long long rounds_ = 0, groups_ = 0, shadows_ = 0, colsum_us_ = 0;
     long long phase_us_[3] = {};
     int ensure(int slot, size_t bytes, std::string &err);
 };

@@ -67,6 +67,7 @@ int odm_parse_args(int argc, const char *const *argv, char *out, size_t cap)
           << "\nmax_cross_dimer_end_tm=" << a.max_cross_dimer_end_tm_text << "\ncoverage_tm=" << a.coverage_tm_text << "\ncoverage_thal=" << a.coverage_thal
           << "\nselect_by_coverage=" << a.select_by_coverage << "\nthin_panel=" << a.thin_panel << "\nthin_mismatches=" << a.thin_mismatches
           << "\nthin_3p_exact=" << a.thin_3p_exact << "\nthin_min_gain=" << a.thin_min_gain
+          << "\nthin_depth=" << a.thin_depth
           << "\nthin_tm=" << a.thin_tm_text << "\nthin_thal=" << a.thin_thal
           << "\nseed_mismatches=" << a.seed_mismatches << "\nseed_3p_exact=" << a.seed_3p_exact
           << "\nseed_tm=" << a.seed_tm_text << "\nseed_thal=" << a.seed_thal
@@ -141,6 +142,52 @@ int odm_thin_panel(const uint64_t *rows, int n, int words, int min_gain, const u
         covered_out[1] = (long long)t.covered_kept;
     }
     return (int)t.order.size();
+}
+
+// odm_thin_panel's arguments plus n_seg (segments: bits of a row), depth and shadow (n flags or NULL: primers that
+// repeat a word and count in nothing).  depth_all / depth_kept (n_seg bytes each, or NULL) and counts_out[0..4] out:
+// segments with depth_all >= 1, depth_kept >= 1, depth_all >= depth, depth_kept >= depth, and the rounds.  Returns the
+// number of picks (thin_panel_depth, the sequential rule of DESIGN.md 4.15).
+int odm_thin_panel_depth(const uint64_t *rows, int n, int words, int n_seg, int depth, int min_gain,
+                         const uint8_t *forced, const uint8_t *shadow, int *order, int *gains, uint8_t *keep,
+                         uint8_t *depth_all, uint8_t *depth_kept, long long *counts_out)
+{
+    std::vector<std::vector<uint64_t>> r((size_t)n);
+    for (int p = 0; p < n; ++p) r[(size_t)p].assign(rows + (size_t)p * words, rows + (size_t)(p + 1) * words);
+    std::vector<char> f, sh;
+    if (forced) f.assign(forced, forced + n);
+    if (shadow) sh.assign(shadow, shadow + n);
+    const ThinDepthResult t = thin_panel_depth(r, (size_t)n_seg, depth, min_gain, f, sh);
+    for (size_t i = 0; i < t.order.size(); ++i) {
+        order[i] = t.order[i];
+        gains[i] = t.gains[i];
+    }
+    for (int p = 0; p < n; ++p) keep[p] = (uint8_t)t.keep[(size_t)p];
+    for (int s = 0; s < n_seg; ++s) {
+        if (depth_all) depth_all[s] = t.depth_all[(size_t)s];
+        if (depth_kept) depth_kept[s] = t.depth_kept[(size_t)s];
+    }
+    if (counts_out) {
+        for (int i = 0; i < 4; ++i) counts_out[i] = t.counts[i];
+        counts_out[4] = t.rounds;
+    }
+    return (int)t.order.size();
+}
+
+// primers: forward words then reverse words, one per line each; forced: flags over both or NULL.  shadow_out[n]
+// (thin_shadows); returns how many are shadows.
+int odm_thin_shadows(const char *fwd_nl, const char *rev_nl, const uint8_t *forced, uint8_t *shadow_out)
+{
+    const auto fwd = lines(fwd_nl), rev = lines(rev_nl);
+    std::vector<char> f;
+    if (forced) f.assign(forced, forced + fwd.size() + rev.size());
+    const auto sh = thin_shadows(fwd, rev, f);
+    int count = 0;
+    for (size_t p = 0; p < sh.size(); ++p) {
+        shadow_out[p] = (uint8_t)sh[p];
+        count += sh[p];
+    }
+    return count;
 }
 
 // rows, forced, order, gains, keep as odm_thin_panel.  bitmap: n rows of ceil(n / 64) words, bit u of row p = the

@@ -84,6 +84,7 @@ const OptSpec kOpts[] = {
     {"--thin-mismatches", "THIN_MISMATCHES", OptSpec::Int, OFF(thin_mismatches)},
     {"--thin-3p-exact", "THIN_3P_EXACT", OptSpec::Str, OFF(thin_3p_exact_text)},
     {"--thin-min-gain", "THIN_MIN_GAIN", OptSpec::Int, OFF(thin_min_gain)},
+    {"--thin-depth", "THIN_DEPTH", OptSpec::Int, OFF(thin_depth)},
     {"--thin-tm", "THIN_TM", OptSpec::Str, OFF(thin_tm_text)},
     {"--thin-thal", "THIN_THAL", OptSpec::Str, OFF(thin_thal)},
     {"--select-by-coverage", "SELECT_BY_COVERAGE", OptSpec::Bool, OFF(select_by_coverage)},
@@ -151,6 +152,8 @@ std::string Args::usage()
          "cover of the segments matched within --thin-mismatches <M> (last --thin-3p-exact <E> bases exact), a pick\n"
          "covering at least --thin-min-gain <G> new segments. No segment is lost at G = 1; a segment's best mismatch\n"
          "count may rise up to M. The primers of --existing-primers are kept. One device; not with --keep-all true.\n"
+         "With --thin-depth <R> every segment keeps R primers where the panel has that many (a word listed twice counts\n"
+         "once), and the block says how many segments have R.\n"
          "With --thin-tm <C> the cover is of the segments a primer holds at C instead: every match within M / E is scored\n"
          "with thal (--thin-thal any | end1), and no held segment is lost at G = 1; a segment's best t may fall.\n"
          "--select-by-coverage true replaces the cover (or the tube split) by a selection that looks at coverage: round\n"
@@ -308,6 +311,14 @@ Args Args::parse(int argc, const char *const *argv)
         if (a.thin_min_gain < 1)
             throw UsageError("error: invalid value '" + std::to_string(a.thin_min_gain) +
                              "' for '--thin-min-gain <...>'\n  [1 ..]");
+        if (a.thin_panel == "true") {   // the selection has no depth
+            if (a.thin_depth < 1 || a.thin_depth > 255)
+                throw UsageError("error: invalid value '" + std::to_string(a.thin_depth) +
+                                 "' for '--thin-depth <...>'\n  [1 .. 255]");
+        } else if (a.thin_depth > 1) {
+            throw UsageError("error: '--thin-depth " + std::to_string(a.thin_depth) +
+                             "' cannot be combined with '--select-by-coverage true': the selection has no depth");
+        }
         if (!a.thin_tm_text.empty()) {
             a.thin_tm = std::strtof(a.thin_tm_text.c_str(), &end);
             if (*end || std::isnan(a.thin_tm))
@@ -1180,6 +1191,99 @@ std::map<std::string, int> conflict_tubes_on_device(Engine &eng, const std::vect
     return out;
 }
 
+// the two additions of --thin-depth R to a thinning block; nothing at depth 1
+static std::string thin_depth_tag(int depth) { return depth > 1 ? ", depth " + std::to_string(depth) : std::string(); }
+static std::string thin_depth_line(int depth, size_t deep_all, size_t deep_kept, const std::string &t,
+                                   const std::string &y, const std::string &x)
+{
+    if (depth <= 1) return std::string();
+    return "  Depth:    at least " + std::to_string(depth) + " primers on " + std::to_string(deep_all) + "/" + t +
+           " segments by all " + y + ", on " + std::to_string(deep_kept) + "/" + t + " by the kept " + x + "\n";
+}
+
+std::vector<char> thin_shadows(const std::vector<std::string> &fwd, const std::vector<std::string> &rev,
+                               const std::vector<char> &forced)
+{
+    const size_t n = fwd.size() + rev.size();
+    std::vector<char> shadow(n, 0);
+    auto is_forced = [&](size_t p) { return p < forced.size() && forced[p]; };
+    for (int dir = 0; dir < 2; ++dir) {   // a forward word that equals a reverse word is no duplicate
+        const auto &words = dir ? rev : fwd;
+        const size_t base = dir ? fwd.size() : 0;
+        std::map<std::string, size_t> rep;   // word -> its representative so far
+        for (size_t i = 0; i < words.size(); ++i) {
+            const auto it = rep.find(words[i]);
+            if (it == rep.end()) {
+                rep.emplace(words[i], base + i);
+            } else if (is_forced(base + i) && !is_forced(it->second)) {   // the first forced one takes over
+                shadow[it->second] = 1;
+                it->second = base + i;
+            } else {
+                shadow[base + i] = 1;
+            }
+        }
+    }
+    return shadow;
+}
+
+ThinDepthResult thin_panel_depth(const std::vector<std::vector<uint64_t>> &rows, size_t n_seg, int depth, int min_gain,
+                                 const std::vector<char> &forced, const std::vector<char> &shadow)
+{
+    const size_t n = rows.size();
+    auto bit = [&](size_t p, size_t s) { return (s >> 6) < rows[p].size() && ((rows[p][s >> 6] >> (s & 63)) & 1ull); };
+    auto is_forced = [&](size_t p) { return p < forced.size() && forced[p]; };
+    auto is_shadow = [&](size_t p) { return p < shadow.size() && shadow[p]; };
+    ThinDepthResult out;
+    out.keep.assign(n, 0);
+    std::vector<int> all(n_seg, 0), need(n_seg, 0), cnt(n_seg, 0);
+    for (size_t p = 0; p < n; ++p) {
+        out.keep[p] = is_forced(p) ? 1 : 0;
+        if (is_shadow(p)) continue;
+        for (size_t s = 0; s < n_seg; ++s)
+            if (bit(p, s)) {
+                ++all[s];
+                if (is_forced(p)) ++cnt[s];
+            }
+    }
+    for (size_t s = 0; s < n_seg; ++s) {
+        need[s] = std::min(depth, all[s]);
+        cnt[s] = std::min(need[s], cnt[s]);
+    }
+    for (;;) {   // every round from scratch: the device keeps its gains up to date instead
+        long best = -1;
+        size_t best_gain = 0;
+        for (size_t p = 0; p < n; ++p) {
+            if (out.keep[p] || is_shadow(p)) continue;
+            size_t gain = 0;
+            for (size_t s = 0; s < n_seg; ++s) gain += bit(p, s) && cnt[s] < need[s] ? 1 : 0;
+            if (best < 0 || gain > best_gain) {   // ">": the lowest index among equals
+                best = (long)p;
+                best_gain = gain;
+            }
+        }
+        ++out.rounds;
+        if (best < 0 || best_gain < (size_t)min_gain) break;
+        out.order.push_back((int)best);
+        out.gains.push_back((int)best_gain);
+        out.keep[(size_t)best] = 1;
+        for (size_t s = 0; s < n_seg; ++s)
+            if (bit((size_t)best, s) && cnt[s] < need[s]) ++cnt[s];
+    }
+    out.depth_all.assign(n_seg, 0);
+    out.depth_kept.assign(n_seg, 0);
+    for (size_t s = 0; s < n_seg; ++s) {
+        int kept = 0;
+        for (size_t p = 0; p < n; ++p) kept += out.keep[p] && !is_shadow(p) && bit(p, s) ? 1 : 0;
+        out.depth_all[s] = (uint8_t)std::min(all[s], 255);
+        out.depth_kept[s] = (uint8_t)std::min(kept, 255);
+        out.counts[0] += all[s] >= 1;
+        out.counts[1] += kept >= 1;
+        out.counts[2] += all[s] >= depth;
+        out.counts[3] += kept >= depth;
+    }
+    return out;
+}
+
 ThinResult thin_panel(const std::vector<std::vector<uint64_t>> &rows, int min_gain, const std::vector<char> &forced)
 {
     const size_t n = rows.size();
@@ -1296,15 +1400,17 @@ SelectResult select_panel(const std::vector<std::vector<uint64_t>> &rows, const 
 }
 
 std::string thin_report(int max_mismatches, int exact_3p, int min_gain, size_t kept_f, size_t n_f, size_t kept_r,
-                        size_t n_r, size_t forced, size_t covered_all, size_t covered_kept, size_t segments)
+                        size_t n_r, size_t forced, size_t covered_all, size_t covered_kept, size_t segments,
+                        int depth, size_t deep_all, size_t deep_kept)
 {
     const std::string x = std::to_string(kept_f + kept_r), y = std::to_string(n_f + n_r), t = std::to_string(segments);
     return "\nPanel thinning (up to " + std::to_string(max_mismatches) + " mismatches, last " + std::to_string(exact_3p) +
-           " bases exact, gain >= " + std::to_string(min_gain) + "):\n  Primers:  kept " + x + " of " + y + " (forward " +
+           " bases exact, gain >= " + std::to_string(min_gain) + thin_depth_tag(depth) + "):\n  Primers:  kept " + x +
+           " of " + y + " (forward " +
            std::to_string(kept_f) + " of " + std::to_string(n_f) + ", reverse " + std::to_string(kept_r) + " of " +
            std::to_string(n_r) + "), " + std::to_string(forced) + " forced\n  Segments: covered " +
            std::to_string(covered_all) + "/" + t + " by all " + y + ", " + std::to_string(covered_kept) + "/" + t +
-           " by the kept " + x + "\n";
+           " by the kept " + x + "\n" + thin_depth_line(depth, deep_all, deep_kept, t, y, x);
 }
 
 std::string tubes_report(const std::vector<KmerStat> &fwd, const std::vector<KmerStat> &rev,
@@ -1557,23 +1663,25 @@ std::string seed_report(int max_mismatches, int exact_3p, int mode, float tm_thr
 
 std::string thin_thal_report(int mode, float tm_threshold, int max_mismatches, int exact_3p, int min_gain,
                              size_t kept_f, size_t n_f, size_t kept_r, size_t n_r, size_t forced, size_t held_all,
-                             size_t held_kept, size_t segments)
+                             size_t held_kept, size_t segments, int depth, size_t deep_all, size_t deep_kept)
 {
     const std::string x = std::to_string(kept_f + kept_r), y = std::to_string(n_f + n_r), t = std::to_string(segments);
     return std::string("\nPanel thinning (thal ") + (mode == 2 ? "END1" : "ANY") + ", t >= " +
            fmt("%.2f", (double)tm_threshold) + " C; matches within " + std::to_string(max_mismatches) +
            " mismatches, last " + std::to_string(exact_3p) + " bases exact, gain >= " + std::to_string(min_gain) +
+           thin_depth_tag(depth) +
            "):\n  Primers:  kept " + x + " of " + y + " (forward " + std::to_string(kept_f) + " of " +
            std::to_string(n_f) + ", reverse " + std::to_string(kept_r) + " of " + std::to_string(n_r) + "), " +
            std::to_string(forced) + " forced\n  Segments: held " + std::to_string(held_all) + "/" + t + " by all " + y +
-           ", " + std::to_string(held_kept) + "/" + t + " by the kept " + x + "\n";
+           ", " + std::to_string(held_kept) + "/" + t + " by the kept " + x + "\n" +
+           thin_depth_line(depth, deep_all, deep_kept, t, y, x);
 }
 
 std::string thin_panel_on_device(Engine &eng, const DeviceAlignment &aln, std::vector<KmerStat> &fwd,
                                  std::vector<KmerStat> &rev, const std::vector<std::string> &panel_f,
                                  const std::vector<std::string> &panel_r, int segment_size, int overlap_size,
                                  int window_size, int kmer_size, int max_mismatches, int exact_3p, int min_gain,
-                                 const msspe_chem *chem, int mode, float tm_threshold)
+                                 const msspe_chem *chem, int mode, float tm_threshold, int depth)
 {
     // the new primers in their lists' order (stage A's selection order: ties go to the word with more postings), the
     // panel's behind them, forced
@@ -1593,8 +1701,20 @@ std::string thin_panel_on_device(Engine &eng, const DeviceAlignment &aln, std::v
     const msspe_kmer_opt opt{segment_size, overlap_size, window_size, kmer_size, 0, 0};
     const msspe_mismatch_opt mm{max_mismatches, exact_3p};
     const msspe_thin_opt thin{min_gain};
+    const msspe_thin_depth_opt deep{min_gain, depth};
+    long long counts[4] = {0, 0, 0, 0};   // depth above 1: covered_all / covered_kept are counts[0] / [1]
     const int rc =
-        chem ? msspe_panel_thin_thal_packed_dev(eng.ctx(), aln.device(), aln.rows(), L, &opt, &mm, &thin, chem, mode,
+        depth > 1
+            ? (chem ? msspe_panel_thin_thal_depth_packed_dev(eng.ctx(), aln.device(), aln.rows(), L, &opt, &mm, &deep,
+                                                             chem, mode, tm_threshold, wf.data(), (int)wf.size(),
+                                                             wr.data(), (int)wr.size(), forced.data(), keep.data(),
+                                                             order.data(), gains.data(), &n_picked, nullptr, nullptr,
+                                                             counts)
+                    : msspe_panel_thin_depth_packed_dev(eng.ctx(), aln.device(), aln.rows(), L, &opt, &mm, &deep,
+                                                        wf.data(), (int)wf.size(), wr.data(), (int)wr.size(),
+                                                        forced.data(), keep.data(), order.data(), gains.data(),
+                                                        &n_picked, nullptr, nullptr, counts))
+        : chem ? msspe_panel_thin_thal_packed_dev(eng.ctx(), aln.device(), aln.rows(), L, &opt, &mm, &thin, chem, mode,
                                                 tm_threshold, wf.data(), (int)wf.size(), wr.data(), (int)wr.size(),
                                                 forced.data(), keep.data(), order.data(), gains.data(), &n_picked,
                                                 nullptr, &covered_all, &covered_kept)
@@ -1603,6 +1723,10 @@ std::string thin_panel_on_device(Engine &eng, const DeviceAlignment &aln, std::v
                                            order.data(), gains.data(), &n_picked, nullptr, &covered_all,
                                            &covered_kept);
     if (rc) eng.fail(rc);
+    if (depth > 1) {
+        covered_all = counts[0];
+        covered_kept = counts[1];
+    }
     const size_t n_f = fwd.size(), n_r = rev.size();
     std::vector<KmerStat> kept_f, kept_r;
     for (size_t i = 0; i < n_f; ++i)
@@ -1614,10 +1738,10 @@ std::string thin_panel_on_device(Engine &eng, const DeviceAlignment &aln, std::v
     if (chem)
         return thin_thal_report(mode, tm_threshold, max_mismatches, exact_3p, min_gain, fwd.size(), n_f, rev.size(),
                                 n_r, panel_f.size() + panel_r.size(), (size_t)covered_all, (size_t)covered_kept,
-                                (size_t)aln.rows() * P);
+                                (size_t)aln.rows() * P, depth, (size_t)counts[2], (size_t)counts[3]);
     return thin_report(max_mismatches, exact_3p, min_gain, fwd.size(), n_f, rev.size(), n_r,
                        panel_f.size() + panel_r.size(), (size_t)covered_all, (size_t)covered_kept,
-                       (size_t)aln.rows() * P);
+                       (size_t)aln.rows() * P, depth, (size_t)counts[2], (size_t)counts[3]);
 }
 
 std::string select_report(int mode, float tm_threshold, int max_mismatches, int exact_3p, int min_gain, int max_tubes,
@@ -2334,7 +2458,7 @@ int run(const Args &args, std::string &stdout_text)
         thin_text = thin_panel_on_device(eng, aln, good_f, good_r, panel_f, panel_r, args.window_size, args.overlap_size,
                                          args.search_windows_size, args.kmer_size, args.thin_mismatches,
                                          args.thin_3p_exact, args.thin_min_gain, args.thin_scored ? &thin_chem : nullptr,
-                                         args.thin_thal == "end1" ? 2 : 1, args.thin_tm);
+                                         args.thin_thal == "end1" ? 2 : 1, args.thin_tm, args.thin_depth);
         timer.lap("panel thinning");
     }
     // the report covers the panel and the new primers together; the CSV lists the new ones, numbered on from the panel

@@ -95,6 +95,9 @@ struct Args {
     std::string thin_3p_exact_text = "3";
     int thin_3p_exact = 3;
     int thin_min_gain = 1;
+    // --thin-depth R (with --thin-panel true): every segment keeps min(R, primers it has) primers instead of one
+    // (msspe_panel_thin_depth*); a line of the block says how many segments have R.  1: nothing changes.
+    int thin_depth = 1;
     // --thin-tm C (with --thin-panel true): the thinning runs over the segments a primer HOLDS at C instead -- every
     // match within thin_mismatches / thin_3p_exact scored with thal (msspe_panel_thin_thal, --thin-thal any | end1, the
     // chemistry of --coverage-tm), so the thal report of the thinned panel holds what the whole panel held.  Empty
@@ -306,6 +309,25 @@ struct ThinResult {
     size_t covered_all = 0, covered_kept = 0;
 };
 ThinResult thin_panel(const std::vector<std::vector<uint64_t>> &rows, int min_gain, const std::vector<char> &forced);
+// --thin-depth (engine extension): the sequential rule of DESIGN.md 4.15 over incidence rows (as thin_panel's).
+// shadow[p]: p repeats a word of its direction and counts in nothing (thin_shadows marks them: among equal words all
+// but the forced one of lowest index, or without a forced one the lowest index).  Every segment needs
+// min(depth, representatives that match it); forced representatives count first; every round picks the live
+// representative matching the most open segments (ties: the lowest index) until that gain is below min_gain.
+// depth_all / depth_kept: representatives per segment among all and among the kept, saturating at 255; counts:
+// segments with depth_all >= 1, depth_kept >= 1, depth_all >= depth, depth_kept >= depth.  The device's independent
+// twin, every round from scratch.
+struct ThinDepthResult {
+    std::vector<int> order, gains;
+    std::vector<char> keep;          // forced (shadows included) or picked
+    std::vector<uint8_t> depth_all, depth_kept;
+    long long counts[4] = {0, 0, 0, 0};
+    int rounds = 0;                  // the picks and the one that stopped
+};
+std::vector<char> thin_shadows(const std::vector<std::string> &fwd, const std::vector<std::string> &rev,
+                               const std::vector<char> &forced);
+ThinDepthResult thin_panel_depth(const std::vector<std::vector<uint64_t>> &rows, size_t n_seg, int depth, int min_gain,
+                                 const std::vector<char> &forced, const std::vector<char> &shadow);
 // --select-by-coverage (engine extension): the sequential rule of DESIGN.md 4.13 over incidence rows (as thin_panel's)
 // and the cover's graph over primers[p] (symmetric; an edge a -> a is a self conflict).  Forced primers cover first,
 // are never picked, and bar their neighbours from every tube; every round picks the live primer (not kept, not
@@ -350,17 +372,23 @@ std::string thin_panel_on_device(Engine &eng, const DeviceAlignment &aln, std::v
                                  std::vector<KmerStat> &rev, const std::vector<std::string> &panel_f,
                                  const std::vector<std::string> &panel_r, int segment_size, int overlap_size,
                                  int window_size, int kmer_size, int max_mismatches, int exact_3p, int min_gain,
-                                 const msspe_chem *chem = nullptr, int mode = 1, float tm_threshold = 0.0f);
+                                 const msspe_chem *chem = nullptr, int mode = 1, float tm_threshold = 0.0f,
+                                 int depth = 1);
+// depth above 1 (--thin-depth R): msspe_panel_thin_depth_packed_dev / msspe_panel_thin_thal_depth_packed_dev instead;
+// the block's first line gains ", depth R" and a line "  Depth:    at least R primers on u/t segments by all Y, on
+// v/t by the kept X" follows "Segments:" (thin_report / thin_thal_report with depth, deep_all = u, deep_kept = v).
 // with a chemistry (--thin-tm) thin_panel_on_device calls msspe_panel_thin_thal_packed_dev and returns this block:
 // "Panel thinning (thal NAME, t >= T C; matches within M mismatches, last E bases exact, gain >= G):", the primers
 // kept as in thin_report, and the segments held by all of them and by the kept ones
 std::string thin_thal_report(int mode, float tm_threshold, int max_mismatches, int exact_3p, int min_gain,
                              size_t kept_f, size_t n_f, size_t kept_r, size_t n_r, size_t forced, size_t held_all,
-                             size_t held_kept, size_t segments);
+                             size_t held_kept, size_t segments, int depth = 1, size_t deep_all = 0,
+                             size_t deep_kept = 0);
 // "Panel thinning (up to M mismatches, last E bases exact, gain >= G):", the primers kept of those offered (forced
 // ones apart) and the segments covered by all of them and by the kept ones (forced primers cover in both figures)
 std::string thin_report(int max_mismatches, int exact_3p, int min_gain, size_t kept_f, size_t n_f, size_t kept_r,
-                        size_t n_r, size_t forced, size_t covered_all, size_t covered_kept, size_t segments);
+                        size_t n_r, size_t forced, size_t covered_all, size_t covered_kept, size_t segments,
+                        int depth = 1, size_t deep_all = 0, size_t deep_kept = 0);
 // main.rs:518-594 (text goes to `out`): the per-segment search runs on the device
 // (msspe_segment_coverage_dev), the totals per sequence / partition and the text on the host
 std::string coverage_report(Engine &eng, const DeviceAlignment &aln, const std::vector<KmerStat> &fwd,

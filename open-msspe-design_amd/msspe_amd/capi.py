@@ -42,6 +42,8 @@ EXPORTS = [
     "msspe_segment_coverage_thal", "msspe_segment_coverage_thal_dev", "msspe_segment_coverage_thal_packed_dev",
     "msspe_panel_thin", "msspe_panel_thin_dev", "msspe_panel_thin_packed_dev",
     "msspe_panel_thin_thal", "msspe_panel_thin_thal_dev", "msspe_panel_thin_thal_packed_dev",
+    "msspe_panel_thin_depth", "msspe_panel_thin_depth_dev", "msspe_panel_thin_depth_packed_dev",
+    "msspe_panel_thin_thal_depth", "msspe_panel_thin_thal_depth_dev", "msspe_panel_thin_thal_depth_packed_dev",
     "msspe_panel_select", "msspe_panel_select_bitmap", "msspe_panel_select_dev", "msspe_panel_select_packed_dev",
     "msspe_panel_select_rule",
     "msspe_device_put_stream_packed", "msspe_background_sites_packed_dev", "msspe_background_sites",
@@ -137,6 +139,11 @@ class MismatchOpt(C.Structure):
 class ThinOpt(C.Structure):
     """msspe_thin_opt: a pick must cover at least min_gain segments nothing kept covers yet."""
     _fields_ = [("min_gain", C.c_int)]
+
+
+class ThinDepthOpt(C.Structure):
+    """msspe_thin_depth_opt: min_gain as ThinOpt; every segment keeps min(depth, primers it has) primers (1..255)."""
+    _fields_ = [("min_gain", C.c_int), ("depth", C.c_int)]
 
 
 class SelectOpt(C.Structure):
@@ -323,6 +330,16 @@ def load_library() -> C.CDLL:
                                         L.msspe_panel_thin.argtypes[7:])
     L.msspe_panel_thin_thal_dev.argtypes = L.msspe_panel_thin_thal.argtypes
     L.msspe_panel_thin_thal_packed_dev.argtypes = L.msspe_panel_thin_thal.argtypes
+    # the sibling's arguments with ThinDepthOpt, then depth_all, depth_kept, counts
+    L.msspe_panel_thin_depth.argtypes = (L.msspe_panel_thin.argtypes[:6] + [C.POINTER(ThinDepthOpt)] +
+                                         L.msspe_panel_thin.argtypes[7:16] + [vp, vp, C.POINTER(C.c_longlong)])
+    L.msspe_panel_thin_depth_dev.argtypes = L.msspe_panel_thin_depth.argtypes
+    L.msspe_panel_thin_depth_packed_dev.argtypes = L.msspe_panel_thin_depth.argtypes
+    L.msspe_panel_thin_thal_depth.argtypes = (L.msspe_panel_thin_depth.argtypes[:7] +
+                                              [C.POINTER(Chem), C.c_int, C.c_float] +
+                                              L.msspe_panel_thin_depth.argtypes[7:])
+    L.msspe_panel_thin_thal_depth_dev.argtypes = L.msspe_panel_thin_thal_depth.argtypes
+    L.msspe_panel_thin_thal_depth_packed_dev.argtypes = L.msspe_panel_thin_thal_depth.argtypes
     # alignment, n_seq, seq_len, opt, rule, sel, fwd, n_fwd, rev, n_rev, forced | graph | keep, order, gain, n_picked,
     # tube, barred, covered, covered_all, covered_kept, n_tubes_used
     select_in = [vp, vp, C.c_int, C.c_size_t, C.POINTER(KmerOpt), C.POINTER(SeedRule), C.POINTER(SelectOpt), u64p,
@@ -1197,7 +1214,28 @@ class Engine:
         return self._panel_thin(fn, (C.byref(chem), self._thal_mode(mode), tm_threshold), genomes, opt, fwd, rev,
                                 max_mismatches, exact_3p, min_gain, forced, form)
 
-    def _panel_thin(self, fn, scoring, genomes, opt, fwd, rev, max_mismatches, exact_3p, min_gain, forced, form):
+    # ---- a panel thinned to a coverage depth (engine extension; msspe_panel_thin_depth*) -------------------------
+    def panel_thin_depth(self, genomes, opt: KmerOpt, fwd, rev, max_mismatches: int, exact_3p: int, depth: int,
+                         min_gain: int = 1, forced=None, form: str = "host"):
+        """panel_thin to a depth: every segment keeps min(depth, primers it has) primers, a word listed twice in a
+        direction counting once (msspe_panel_thin_depth*).  Arguments as panel_thin.  Returns (keep uint8[n], order,
+        gains, depth_all uint8 (n_seq, P), depth_kept uint8 (n_seq, P), counts int64[4])."""
+        fn = {"host": self.L.msspe_panel_thin_depth, "dev": self.L.msspe_panel_thin_depth_dev,
+              "packed": self.L.msspe_panel_thin_depth_packed_dev}[form]
+        return self._panel_thin(fn, (), genomes, opt, fwd, rev, max_mismatches, exact_3p, min_gain, forced, form, depth)
+
+    def panel_thin_thal_depth(self, genomes, opt: KmerOpt, fwd, rev, max_mismatches: int, exact_3p: int, chem: Chem,
+                              mode, tm_threshold: float, depth: int, min_gain: int = 1, forced=None,
+                              form: str = "host"):
+        """panel_thin_depth over the segments a primer HOLDS (msspe_panel_thin_thal_depth*): arguments as
+        panel_thin_thal plus depth, the returned tuple as panel_thin_depth."""
+        fn = {"host": self.L.msspe_panel_thin_thal_depth, "dev": self.L.msspe_panel_thin_thal_depth_dev,
+              "packed": self.L.msspe_panel_thin_thal_depth_packed_dev}[form]
+        return self._panel_thin(fn, (C.byref(chem), self._thal_mode(mode), tm_threshold), genomes, opt, fwd, rev,
+                                max_mismatches, exact_3p, min_gain, forced, form, depth)
+
+    def _panel_thin(self, fn, scoring, genomes, opt, fwd, rev, max_mismatches, exact_3p, min_gain, forced, form,
+                    depth=None):
         owned = None
         if isinstance(genomes, tuple):
             if form == "host":
@@ -1229,14 +1267,25 @@ class Engine:
             gains = np.zeros(max(n, 1), dtype=np.uint32)
             covered = np.zeros((n_seq, P), dtype=np.uint8)
             n_picked, c_all, c_kept = C.c_int(0), C.c_longlong(0), C.c_longlong(0)
-            mm, thin = MismatchOpt(max_mismatches, exact_3p), ThinOpt(min_gain)
+            mm = MismatchOpt(max_mismatches, exact_3p)
+            if depth is None:
+                thin = ThinOpt(min_gain)
+                outs = (covered.ctypes.data, C.byref(c_all), C.byref(c_kept))
+            else:
+                thin = ThinDepthOpt(min_gain, depth)
+                depth_kept = np.zeros((n_seq, P), dtype=np.uint8)
+                counts = (C.c_longlong * 4)()
+                outs = (covered.ctypes.data, depth_kept.ctypes.data, counts)
             self._check(fn(self.ptr, seqs_arg, n_seq, seq_len, C.byref(opt), C.byref(mm), C.byref(thin), *scoring,
                            f.ctypes.data, len(f), r.ctypes.data, len(r),
                            flags.ctypes.data if flags is not None else None, keep.ctypes.data, order.ctypes.data,
-                           gains.ctypes.data, C.byref(n_picked), covered.ctypes.data, C.byref(c_all), C.byref(c_kept)))
+                           gains.ctypes.data, C.byref(n_picked), *outs))
         finally:
             if owned is not None:
                 self.device_free(owned)
+        if depth is not None:
+            return (keep, order[:n_picked.value].copy(), gains[:n_picked.value].copy(), covered, depth_kept,
+                    np.array(list(counts), dtype=np.int64))
         return (keep, order[:n_picked.value].copy(), gains[:n_picked.value].copy(), covered, int(c_all.value),
                 int(c_kept.value))
 
