@@ -1436,6 +1436,107 @@ int msspe_panel_select_rule(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size
                             uint8_t *barred_out, uint8_t *covered_out, long long *covered_all_out,
                             long long *covered_kept_out, int *n_tubes_used_out);
 
+/* ---- a conflict-free panel selected to a coverage depth, layer by layer (engine extension, no reference
+ * counterpart) ----
+ * msspe_panel_select* stops once every reachable segment has ONE primer, and msspe_panel_thin_depth* knows no
+ * conflicts.  These calls select a conflict-free, tube-assigned panel in which a segment keeps up to R primers.  The
+ * depth thinning's rule ("open while cnt < min(R, depth_all)") cannot simply take the barring on: a pick made for its
+ * second-primer gains bars the only primer of other segments, and breadth is lost.  The rule here runs in LAYERS, so
+ * that asking for depth never costs breadth: layer 1 is exactly msspe_panel_select*, layer r then adds primers for the
+ * segments that still have fewer than r.
+ *   Inputs.  Everything msspe_panel_select* takes, with msspe_select_depth_opt {min_gain >= 1, max_tubes 1..64,
+ *     drop_self_pairs, depth = R in 1..255} in place of msspe_select_opt.  The words must be distinct across both
+ *     lists, as there; so there are no shadows (msspe_panel_thin_depth*).
+ *   Graph, SELF-CONFLICTING, mask, LIVE and the choice of the tube are msspe_panel_select*'s.
+ *   State, carried through the whole run.  depth_all[s] = the number of the n primers with I[p][s]; conflicts are
+ *     ignored, as for covered_all.  cnt[s] = the number of kept (forced or picked) primers with I[p][s]: the true count,
+ *     which starts from the forced rows.  mask starts as in msspe_panel_select*.  D = max_s depth_all[s].
+ *   Layers r = 1 .. L run in order, L = min(R, max(1, D)).  In layer r, segment s is OPEN while
+ *     cnt[s] < min(r, depth_all[s]).  A round of layer r:
+ *     1. gain(p) = |{s : I[p][s], s open}| over the live p.
+ *     2. The greatest gain wins.  Ties go to the LOWEST index.
+ *     3. If nobody is live, or the greatest gain is below min_gain, the round picks nothing and the layer ends.  That
+ *        stopping round counts as a round.
+ *     4. Otherwise p joins the order with its gain and its layer.
+ *     5. tube(p) = the lowest tube not in mask[p].
+ *     6. cnt[s] += 1 on EVERY s with I[p][s], open or not, saturating at 255.
+ *     7. mask[u] |= 1 << tube(p) for every u != p with S[p][u] set.
+ *     Barring, picks and cnt carry over from layer to layer.  Rounds reported = picks + L.
+ *   Outputs.  keep_out, order_out, gain_out, *n_picked_out, tube_out, barred_out (optional) and *n_tubes_used_out
+ *     (optional) as msspe_panel_select*.  pick_layer_out (optional, uint8 per position of the order; the caller sizes it
+ *     to n): the layer of the pick.  depth_all_out and depth_kept_out (optional, n_seq * P bytes, saturating at 255;
+ *     depth_kept = the final cnt).  counts_out[4] (optional): segments with depth_all >= 1, depth_kept >= 1,
+ *     depth_all >= R, depth_kept >= R.
+ * GUARANTEES.
+ *   R = 1 is msspe_panel_select*: order, gains, keep, tube, barred, tubes used and "panel_select_rounds" are equal,
+ *     and counts[0..1] = (covered_all, covered_kept).
+ *   Prefix.  The run at depth R - 1 is a prefix of the run at depth R: same order, gains, layers and tubes on the
+ *     prefix.  So counts[1] never falls as R grows; at min_gain 1 it does not change at all, because after layer 1 no
+ *     live primer has an uncovered segment.
+ *   Independence.  msspe_panel_select*'s guarantee is unchanged: no two picks of one tube are neighbours in S, no pick
+ *     is a neighbour of a forced primer, the tubes in use are 0 .. used - 1.
+ *   With an all-zero bitmap at min_gain 1: depth_kept[s] >= min(R, depth_all[s]) for every s.
+ *   Gains.  The sum of the gains of the picks of layer r = the sum over s of min(cnt_end[s], m[s]) - min(cnt_start[s],
+ *     m[s]), with m[s] = min(r, depth_all[s]) and cnt at the layer's start and end: every hit a segment takes while open
+ *     counts once.
+ * What the rule does NOT promise: equality with the thinning -- with a zero bitmap the picks are in general not
+ * msspe_panel_thin_depth*'s, because that rule is not layered (the kept count may coincide); any depth under conflicts;
+ * or a maximum.  It is greedy.
+ * Limits and errors: those of msspe_panel_select*; depth outside 1..255 is MSSPE_ERR_ARG.  n == 0 or no segments:
+ * MSSPE_OK with nothing picked, keep_out = the forced flags and counts 0.
+ * msspe_get_info, the last call: the "panel_select_*" keys, with "panel_select_first_us" now the first barring, the
+ * column sums and layer 1's init and first gains, and "panel_select_rounds_us" everything after; and
+ * "panel_select_depth_layers" (L) and "panel_select_depth_layer_us" (the column sums and every layer's init and first
+ * gains).
+ * The five forms mirror msspe_panel_select_dev, _packed_dev, msspe_panel_select (screens the pool itself at
+ * dg_threshold), _bitmap and _rule; the incidence modes 0 / 1 / 2 of msspe_seed_rule are unchanged. */
+typedef struct {
+    int min_gain;          /* >= 1 */
+    int max_tubes;         /* 1..64 */
+    int drop_self_pairs;   /* as msspe_conflict_cover* */
+    int depth;             /* R, 1..255 */
+} msspe_select_depth_opt;
+
+int msspe_panel_select_depth_dev(msspe_ctx *ctx, const uint8_t *d_seqs, int n_seq, size_t seq_len,
+                                 const msspe_kmer_opt *opt, const msspe_seed_rule *rule,
+                                 const msspe_select_depth_opt *sel, const uint64_t *fwd_words, int n_fwd,
+                                 const uint64_t *rev_words, int n_rev, const uint8_t *forced, const uint64_t *d_bitmap,
+                                 uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out, int *n_picked_out,
+                                 uint8_t *tube_out, uint8_t *barred_out, int *n_tubes_used_out,
+                                 uint8_t *pick_layer_out, uint8_t *depth_all_out, uint8_t *depth_kept_out,
+                                 long long *counts_out);
+int msspe_panel_select_depth_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
+                                        const msspe_kmer_opt *opt, const msspe_seed_rule *rule,
+                                        const msspe_select_depth_opt *sel, const uint64_t *fwd_words, int n_fwd,
+                                        const uint64_t *rev_words, int n_rev, const uint8_t *forced,
+                                        const uint64_t *d_bitmap, uint8_t *keep_out, uint32_t *order_out,
+                                        uint32_t *gain_out, int *n_picked_out, uint8_t *tube_out, uint8_t *barred_out,
+                                        int *n_tubes_used_out, uint8_t *pick_layer_out, uint8_t *depth_all_out,
+                                        uint8_t *depth_kept_out, long long *counts_out);
+int msspe_panel_select_depth(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len, const msspe_kmer_opt *opt,
+                             const msspe_seed_rule *rule, const msspe_select_depth_opt *sel, const uint64_t *fwd_words,
+                             int n_fwd, const uint64_t *rev_words, int n_rev, const uint8_t *forced,
+                             const msspe_chem *chem, float dg_threshold, uint8_t *keep_out, uint32_t *order_out,
+                             uint32_t *gain_out, int *n_picked_out, uint8_t *tube_out, uint8_t *barred_out,
+                             int *n_tubes_used_out, uint8_t *pick_layer_out, uint8_t *depth_all_out,
+                             uint8_t *depth_kept_out, long long *counts_out);
+int msspe_panel_select_depth_bitmap(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len,
+                                    const msspe_kmer_opt *opt, const msspe_seed_rule *rule,
+                                    const msspe_select_depth_opt *sel, const uint64_t *fwd_words, int n_fwd,
+                                    const uint64_t *rev_words, int n_rev, const uint8_t *forced, const uint64_t *bitmap,
+                                    uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out, int *n_picked_out,
+                                    uint8_t *tube_out, uint8_t *barred_out, int *n_tubes_used_out,
+                                    uint8_t *pick_layer_out, uint8_t *depth_all_out, uint8_t *depth_kept_out,
+                                    long long *counts_out);
+int msspe_panel_select_depth_rule(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len,
+                                  const msspe_kmer_opt *opt, const msspe_seed_rule *rule,
+                                  const msspe_select_depth_opt *sel, const uint64_t *fwd_words, int n_fwd,
+                                  const uint64_t *rev_words, int n_rev, const uint8_t *forced, const msspe_chem *chem,
+                                  const msspe_conflict_rule *conflict_rule, uint8_t *keep_out, uint32_t *order_out,
+                                  uint32_t *gain_out, int *n_picked_out, uint8_t *tube_out, uint8_t *barred_out,
+                                  int *n_tubes_used_out, uint8_t *pick_layer_out, uint8_t *depth_all_out,
+                                  uint8_t *depth_kept_out, long long *counts_out);
+
 /* ---- several devices of one node ----------------------------------------------------------
  *
  * One process, one context and one host thread per device.  What shards is the reference's N^2 pair loop

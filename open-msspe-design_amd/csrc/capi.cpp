@@ -914,6 +914,8 @@ int msspe_get_info(msspe_ctx *ctx, const char *key, long long *value_out)
     else if (k == "panel_select_incidence_us") *value_out = ctx->select_incidence_us;
     else if (k == "panel_select_rounds_us") *value_out = ctx->select.phase_us()[1];
     else if (k == "panel_select_first_us") *value_out = ctx->select.phase_us()[0];
+    else if (k == "panel_select_depth_layers") *value_out = ctx->select.depth_layers();
+    else if (k == "panel_select_depth_layer_us") *value_out = ctx->select.depth_layer_us();
     else if (k == "thin_thal_unique") *value_out = ctx->opt.thin_thal_unique ? 1 : 0;
     else if (k == "panel_thin_thal_matches") *value_out = ctx->thin_thal.matches;
     else if (k == "panel_thin_thal_unique_pairs") *value_out = ctx->thin_thal.unique_pairs;
@@ -3876,12 +3878,20 @@ int panel_thin_thal_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t 
 // msspe_panel_select*: the cover's graph over the pool "forward words then reverse words" (CoverStage::begin /
 // prepare: one S in the context, whoever built it last), the thinning's matrix filled by the rule's mode (mode 0 as
 // msspe_panel_thin*, modes 1 and 2 as msspe_panel_thin_thal*; a threshold <= 0 is mode 0), then PanelSelect::rounds.
+// msspe_panel_select_depth*: the depth and the outputs the layered rule adds; the rest of such a call
+// is the selection's, with covered_out, covered_all_out and covered_kept_out NULL.
+struct SelectDepthArgs {
+    int depth;
+    uint8_t *pick_layer_out, *depth_all_out, *depth_kept_out;
+    long long *counts_out;
+};
+
 int panel_select_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t seq_len, const msspe_kmer_opt *opt,
                       const msspe_seed_rule *rule, const msspe_select_opt *sel, const uint64_t *fwd_words, int n_fwd,
                       const uint64_t *rev_words, int n_rev, const uint8_t *forced, const uint64_t *d_bitmap,
                       uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out, int *n_picked_out, uint8_t *tube_out,
                       uint8_t *barred_out, uint8_t *covered_out, long long *covered_all_out,
-                      long long *covered_kept_out, int *n_tubes_used_out)
+                      long long *covered_kept_out, int *n_tubes_used_out, const SelectDepthArgs *dep = nullptr)
 {
     if (!opt || !rule || !sel || !keep_out || !order_out || !gain_out || !n_picked_out || !tube_out || n_fwd < 0 ||
         n_rev < 0 || (n_fwd && !fwd_words) || (n_rev && !rev_words))
@@ -3889,6 +3899,8 @@ int panel_select_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t seq
     if (sel->min_gain < 1) return fail(ctx, MSSPE_ERR_ARG, "panel select: min_gain must be at least 1");
     if (sel->max_tubes < 1 || sel->max_tubes > kTubeMax)
         return fail(ctx, MSSPE_ERR_ARG, "panel select: max_tubes must be 1..64");
+    if (dep && (dep->depth < 1 || dep->depth > 255))
+        return fail(ctx, MSSPE_ERR_ARG, "panel select: depth must be 1..255");
     if (rule->mode < 0 || rule->mode > 2)
         return fail(ctx, MSSPE_ERR_ARG, "panel select: mode must be 0, 1 (ANY) or 2 (END1)");
     if (rule->mode && !rule->chem) return fail(ctx, MSSPE_ERR_ARG, "panel select: modes 1 and 2 need a chemistry");
@@ -3898,6 +3910,7 @@ int panel_select_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t seq
     if (covered_all_out) *covered_all_out = 0;
     if (covered_kept_out) *covered_kept_out = 0;
     if (n_tubes_used_out) *n_tubes_used_out = 0;
+    if (dep && dep->counts_out) std::fill(dep->counts_out, dep->counts_out + 4, 0LL);
     const int k = opt->kmer_size;
     if (k < 2 || k > 31) return fail(ctx, MSSPE_ERR_K, "panel select: unsupported k (need 2 <= k <= 31)");
     if ((long)n_fwd + (long)n_rev > (long)kCoverMaxN)
@@ -3920,6 +3933,8 @@ int panel_select_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t seq
         if (barred_out) barred_out[p] = 0;
     }
     if (covered_out) std::fill(covered_out, covered_out + n_seg, (uint8_t)0);
+    if (dep && dep->depth_all_out) std::fill(dep->depth_all_out, dep->depth_all_out + n_seg, (uint8_t)0);
+    if (dep && dep->depth_kept_out) std::fill(dep->depth_kept_out, dep->depth_kept_out + n_seg, (uint8_t)0);
     if (n == 0 || n_seg == 0) return MSSPE_OK;
     if (!d_bitmap) return fail(ctx, MSSPE_ERR_ARG, "panel select: null bitmap");
     const size_t cap = (size_t)1 << ctx->opt.site_list_cap_log2;
@@ -3965,10 +3980,16 @@ int panel_select_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t seq
     }
     HIP_TRY(ctx, hipEventRecord(ctx->select_ev[1], ctx->stream));
 
-    if ((rc = ctx->select.rounds(d_inc, ctx->cover.symmetrised(), n, n_seg, S, sel->min_gain, sel->max_tubes, keep_out,
-                                 order_out, gain_out, n_picked_out, tube_out, barred_out, covered_out, covered_all_out,
-                                 covered_kept_out, n_tubes_used_out, ctx->n_cu, ctx->stream, err)))
-        return fail(ctx, rc, err);
+    if (dep)
+        rc = ctx->select.rounds_depth(d_inc, ctx->cover.symmetrised(), n, n_seg, S, sel->min_gain, sel->max_tubes,
+                                      dep->depth, keep_out, order_out, gain_out, n_picked_out, tube_out, barred_out,
+                                      n_tubes_used_out, dep->pick_layer_out, dep->depth_all_out, dep->depth_kept_out,
+                                      dep->counts_out, ctx->n_cu, ctx->stream, err);
+    else
+        rc = ctx->select.rounds(d_inc, ctx->cover.symmetrised(), n, n_seg, S, sel->min_gain, sel->max_tubes, keep_out,
+                                order_out, gain_out, n_picked_out, tube_out, barred_out, covered_out, covered_all_out,
+                                covered_kept_out, n_tubes_used_out, ctx->n_cu, ctx->stream, err);
+    if (rc) return fail(ctx, rc, err);
     thin_thal_read_scored(ctx, scored);   // rounds returned with the stream idle
     long long keys_us = 0, sym_us = 0;
     ctx->cover.prepare_us(keys_us, sym_us);
@@ -4418,7 +4439,7 @@ static int panel_select_host(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, siz
                              uint32_t *order_out, uint32_t *gain_out, int *n_picked_out, uint8_t *tube_out,
                              uint8_t *barred_out, uint8_t *covered_out, long long *covered_all_out,
                              long long *covered_kept_out, int *n_tubes_used_out,
-                             const msspe_conflict_rule *conflict_rule = nullptr)
+                             const msspe_conflict_rule *conflict_rule = nullptr, const SelectDepthArgs *dep = nullptr)
 {
     if (!seqs || n_seq < 0) return fail(ctx, MSSPE_ERR_ARG, "null sequences");
     if (n_fwd < 0 || n_rev < 0 || (n_fwd && !fwd_words) || (n_rev && !rev_words) || !opt || !rule || !sel || !keep_out ||
@@ -4427,6 +4448,8 @@ static int panel_select_host(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, siz
     if (sel->min_gain < 1) return fail(ctx, MSSPE_ERR_ARG, "panel select: min_gain must be at least 1");
     if (sel->max_tubes < 1 || sel->max_tubes > kTubeMax)   // before the screen, not after it
         return fail(ctx, MSSPE_ERR_ARG, "panel select: max_tubes must be 1..64");
+    if (dep && (dep->depth < 1 || dep->depth > 255))
+        return fail(ctx, MSSPE_ERR_ARG, "panel select: depth must be 1..255");
     const long n = (long)n_fwd + (long)n_rev;
     if (n > (long)kCoverMaxN)
         return fail(ctx, MSSPE_ERR_ARG, "panel select: " + std::to_string(n) + " primers, at most " +
@@ -4463,9 +4486,15 @@ static int panel_select_host(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, siz
     void *d = nullptr;
     int rc = msspe_device_put(ctx, seqs, (size_t)n_seq * seq_len, &d);
     if (rc) return rc;
-    rc = msspe_panel_select_dev(ctx, (const uint8_t *)d, n_seq, seq_len, opt, rule, sel, fwd_words, n_fwd, rev_words,
-                                n_rev, forced, d_bitmap, keep_out, order_out, gain_out, n_picked_out, tube_out,
-                                barred_out, covered_out, covered_all_out, covered_kept_out, n_tubes_used_out);
+    if (dep)
+        rc = panel_select_view(ctx, SeqView{(const uint8_t *)d, nullptr, seq_len}, n_seq, seq_len, opt, rule, sel,
+                               fwd_words, n_fwd, rev_words, n_rev, forced, d_bitmap, keep_out, order_out, gain_out,
+                               n_picked_out, tube_out, barred_out, nullptr, nullptr, nullptr, n_tubes_used_out, dep);
+    else
+        rc = msspe_panel_select_dev(ctx, (const uint8_t *)d, n_seq, seq_len, opt, rule, sel, fwd_words, n_fwd,
+                                    rev_words, n_rev, forced, d_bitmap, keep_out, order_out, gain_out, n_picked_out,
+                                    tube_out, barred_out, covered_out, covered_all_out, covered_kept_out,
+                                    n_tubes_used_out);
     if (!rc && chem && n) {
         const hipError_t e = hipStreamSynchronize(ctx->stream);
         rc = e != hipSuccess ? hip_fail(ctx, e, "hipStreamSynchronize") : check_list_overrun(ctx);
@@ -4516,6 +4545,96 @@ int msspe_panel_select_bitmap(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, si
                              bitmap, nullptr, 0.0f, keep_out, order_out, gain_out, n_picked_out, tube_out, barred_out,
                              covered_out, covered_all_out, covered_kept_out, n_tubes_used_out);
 }
+
+// msspe_panel_select_depth*: the five forms of the selection with the depth behind the options.  A NULL sel is the
+// selection's error (the view and the host form name it).
+#define SELECT_DEPTH_ARGS                                                                              \
+    const msspe_select_opt so = {sel ? sel->min_gain : 0, sel ? sel->max_tubes : 0, sel ? sel->drop_self_pairs : 0}; \
+    const SelectDepthArgs dep = {sel ? sel->depth : 1, pick_layer_out, depth_all_out, depth_kept_out, counts_out}
+
+int msspe_panel_select_depth_dev(msspe_ctx *ctx, const uint8_t *d_seqs, int n_seq, size_t seq_len,
+                                 const msspe_kmer_opt *opt, const msspe_seed_rule *rule,
+                                 const msspe_select_depth_opt *sel, const uint64_t *fwd_words, int n_fwd,
+                                 const uint64_t *rev_words, int n_rev, const uint8_t *forced, const uint64_t *d_bitmap,
+                                 uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out, int *n_picked_out,
+                                 uint8_t *tube_out, uint8_t *barred_out, int *n_tubes_used_out,
+                                 uint8_t *pick_layer_out, uint8_t *depth_all_out, uint8_t *depth_kept_out,
+                                 long long *counts_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!d_seqs) return fail(ctx, MSSPE_ERR_ARG, "null sequences");
+    SELECT_DEPTH_ARGS;
+    return panel_select_view(ctx, SeqView{d_seqs, nullptr, seq_len}, n_seq, seq_len, opt, rule, sel ? &so : nullptr,
+                             fwd_words, n_fwd, rev_words, n_rev, forced, d_bitmap, keep_out, order_out, gain_out,
+                             n_picked_out, tube_out, barred_out, nullptr, nullptr, nullptr, n_tubes_used_out, &dep);
+}
+
+int msspe_panel_select_depth_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
+                                        const msspe_kmer_opt *opt, const msspe_seed_rule *rule,
+                                        const msspe_select_depth_opt *sel, const uint64_t *fwd_words, int n_fwd,
+                                        const uint64_t *rev_words, int n_rev, const uint8_t *forced,
+                                        const uint64_t *d_bitmap, uint8_t *keep_out, uint32_t *order_out,
+                                        uint32_t *gain_out, int *n_picked_out, uint8_t *tube_out, uint8_t *barred_out,
+                                        int *n_tubes_used_out, uint8_t *pick_layer_out, uint8_t *depth_all_out,
+                                        uint8_t *depth_kept_out, long long *counts_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!d_packed) return fail(ctx, MSSPE_ERR_ARG, "null sequences");
+    SELECT_DEPTH_ARGS;
+    return panel_select_view(ctx, SeqView{nullptr, d_packed, seq_len}, n_seq, seq_len, opt, rule, sel ? &so : nullptr,
+                             fwd_words, n_fwd, rev_words, n_rev, forced, d_bitmap, keep_out, order_out, gain_out,
+                             n_picked_out, tube_out, barred_out, nullptr, nullptr, nullptr, n_tubes_used_out, &dep);
+}
+
+int msspe_panel_select_depth(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len, const msspe_kmer_opt *opt,
+                             const msspe_seed_rule *rule, const msspe_select_depth_opt *sel, const uint64_t *fwd_words,
+                             int n_fwd, const uint64_t *rev_words, int n_rev, const uint8_t *forced,
+                             const msspe_chem *chem, float dg_threshold, uint8_t *keep_out, uint32_t *order_out,
+                             uint32_t *gain_out, int *n_picked_out, uint8_t *tube_out, uint8_t *barred_out,
+                             int *n_tubes_used_out, uint8_t *pick_layer_out, uint8_t *depth_all_out,
+                             uint8_t *depth_kept_out, long long *counts_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!chem) return fail(ctx, MSSPE_ERR_ARG, "panel select: null chemistry");
+    SELECT_DEPTH_ARGS;
+    return panel_select_host(ctx, seqs, n_seq, seq_len, opt, rule, sel ? &so : nullptr, fwd_words, n_fwd, rev_words,
+                             n_rev, forced, nullptr, chem, dg_threshold, keep_out, order_out, gain_out, n_picked_out,
+                             tube_out, barred_out, nullptr, nullptr, nullptr, n_tubes_used_out, nullptr, &dep);
+}
+
+int msspe_panel_select_depth_rule(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len,
+                                  const msspe_kmer_opt *opt, const msspe_seed_rule *rule,
+                                  const msspe_select_depth_opt *sel, const uint64_t *fwd_words, int n_fwd,
+                                  const uint64_t *rev_words, int n_rev, const uint8_t *forced, const msspe_chem *chem,
+                                  const msspe_conflict_rule *conflict_rule, uint8_t *keep_out, uint32_t *order_out,
+                                  uint32_t *gain_out, int *n_picked_out, uint8_t *tube_out, uint8_t *barred_out,
+                                  int *n_tubes_used_out, uint8_t *pick_layer_out, uint8_t *depth_all_out,
+                                  uint8_t *depth_kept_out, long long *counts_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (int rc = graph_rule_check(ctx, chem, conflict_rule, GraphOut{}, false)) return rc;
+    SELECT_DEPTH_ARGS;
+    return panel_select_host(ctx, seqs, n_seq, seq_len, opt, rule, sel ? &so : nullptr, fwd_words, n_fwd, rev_words,
+                             n_rev, forced, nullptr, chem, 0.0f, keep_out, order_out, gain_out, n_picked_out, tube_out,
+                             barred_out, nullptr, nullptr, nullptr, n_tubes_used_out, conflict_rule, &dep);
+}
+
+int msspe_panel_select_depth_bitmap(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len,
+                                    const msspe_kmer_opt *opt, const msspe_seed_rule *rule,
+                                    const msspe_select_depth_opt *sel, const uint64_t *fwd_words, int n_fwd,
+                                    const uint64_t *rev_words, int n_rev, const uint8_t *forced, const uint64_t *bitmap,
+                                    uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out, int *n_picked_out,
+                                    uint8_t *tube_out, uint8_t *barred_out, int *n_tubes_used_out,
+                                    uint8_t *pick_layer_out, uint8_t *depth_all_out, uint8_t *depth_kept_out,
+                                    long long *counts_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    SELECT_DEPTH_ARGS;
+    return panel_select_host(ctx, seqs, n_seq, seq_len, opt, rule, sel ? &so : nullptr, fwd_words, n_fwd, rev_words,
+                             n_rev, forced, bitmap, nullptr, 0.0f, keep_out, order_out, gain_out, n_picked_out,
+                             tube_out, barred_out, nullptr, nullptr, nullptr, n_tubes_used_out, nullptr, &dep);
+}
+#undef SELECT_DEPTH_ARGS
 
 int msspe_background_thal_flank_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, size_t total_len, int k,
                                            const msspe_mismatch_opt *mm, const uint64_t *words, int n,

@@ -22,6 +22,14 @@
 // the touched groups.  gain[p] == |I[p] & ~cov| holds for every p after every round, live or not, so a primer that
 // is barred costs nothing to keep up to date.  Sixteen rounds are enqueued per batch behind a device word; after the
 // round that stops the launches return at once, and the host reads one word per batch.
+//
+// Depth (msspe_panel_select_depth*).  The same rounds run in layers r = 1 .. L.  Two byte planes, a
+// cell per (group, bit), hold depth_all (the column sums of inc over all primers: PanelThin::colsum) and cnt (the kept
+// primers on the segment, first the forced rows' column sums).  k_select_layer opens a layer: a segment is open while
+// cnt < min(r, all), cov[g] = ~open, so that the gain, pick and update kernels above run unchanged with cov read as
+// "closed".  k_select_apply_depth is the apply step of a layered round: the pick counts on EVERY segment of its row,
+// open or not, the open ones that reach min(r, all) close, and the barring is k_select_apply's.  Picks, masks and
+// cnt carry over from layer to layer; between layers the host clears `done` and the gains.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -30,6 +38,7 @@
 
 #include "../../include/msspe_hip.h"
 #include "panel_select.hpp"
+#include "panel_thin.hpp"
 
 namespace msspe {
 
@@ -49,12 +58,12 @@ struct SelectState {
     uint32_t tube;        // of the current pick
     uint32_t used;        // highest tube in use + 1
     uint32_t n_touched;   // groups in which the current pick covers something new
-    uint32_t pad;
+    uint32_t deeper;      // depth runs: r + 1 once layer r has seen a segment with more than r primers; else unused
     unsigned long long covered_all;      // |OR of all I[p]|
     unsigned long long covered_forced;   // |OR of the forced I[p]|
 };
 
-enum { kPool, kCov, kTouched, kNew, kGain, kMask, kBytes, kOrder, kForced };   // PanelSelect::buf_
+enum { kPool, kCov, kTouched, kNew, kGain, kMask, kBytes, kOrder, kForced, kDepth, kPrimerMask };   // PanelSelect::buf_
 
 __device__ __forceinline__ uint64_t wave_or(uint64_t x)
 {
@@ -222,6 +231,60 @@ __global__ __launch_bounds__(kThreads) void k_select_update(const uint64_t *inc,
     if (sum) atomicSub(&gain[p], sum);
 }
 
+// Layer r opens, a thread per (group, bit), a wave per group: a segment is open while cnt < min(r, all); cov[g] =
+// ~(open bits), so a bit past S or past the last segment reads as closed.  A group that has a segment with more than r
+// primers says that a layer r + 1 exists (deeper only grows, so nobody has to clear it).
+__global__ __launch_bounds__(kThreads) void k_select_layer(const uint8_t *all, const uint8_t *cnt, int G, int S,
+                                                           long n_seg, uint32_t r, uint64_t *cov, SelectState *st)
+{
+    const long t = (long)blockIdx.x * kThreads + threadIdx.x;
+    const long g = t >> 6;
+    if (g >= G) return;   // whole waves: 64 threads per group
+    const int b = (int)(t & 63);
+    const uint32_t a = all[t], c = cnt[t];
+    const bool open = b < S && g * S + b < n_seg && c < std::min(r, a);
+    const unsigned long long o = __ballot(open), more = __ballot(a > r);
+    if (b == 0) {
+        cov[g] = ~(uint64_t)o;
+        if (more) atomicMax(&st->deeper, r + 1);
+    }
+}
+
+// The apply step of a layered round; thread i serves group i and primer i.  Group: the pick counts once on every
+// segment of its row, open or not, saturating at 255; the open ones that reach min(r, all) close: cov[g] |= closed,
+// and the groups with any go on the touched list with the closed bits as their fresh word.  A thread alone touches its
+// group's 64 counters.  Primer: the barring of k_select_apply.
+__global__ __launch_bounds__(kThreads) void k_select_apply_depth(const uint64_t *inc, size_t n_pad, int G,
+                                                                 uint64_t *cov, uint8_t *cnt, const uint8_t *all,
+                                                                 uint32_t r, uint32_t *touched, uint64_t *fresh,
+                                                                 const uint64_t *S, int n, int W, uint64_t *mask,
+                                                                 SelectState *st)
+{
+    if (st->done) return;
+    const long i = (long)blockIdx.x * kThreads + threadIdx.x;
+    const uint32_t pick = st->pick;
+    if (i < G) {
+        const uint64_t c = cov[i];
+        uint64_t w = inc[(size_t)i * n_pad + pick], closed = 0;
+        while (w) {
+            const int b = __ffsll((unsigned long long)w) - 1;
+            w &= w - 1;
+            const size_t t = (size_t)i * 64 + (size_t)b;   // b < 64: inside the group's cells
+            const uint32_t v = std::min((uint32_t)cnt[t] + 1u, 255u);
+            cnt[t] = (uint8_t)v;
+            if (!((c >> b) & 1ull) && v >= std::min(r, (uint32_t)all[t])) closed |= 1ull << b;
+        }
+        if (closed) {
+            cov[i] = c | closed;
+            const uint32_t at = atomicAdd(&st->n_touched, 1u);
+            touched[at] = (uint32_t)i;
+            fresh[at] = closed;
+        }
+    }
+    if (i < n && (uint32_t)i != pick && ((S[(size_t)pick * W + (i >> 6)] >> (i & 63)) & 1ull))
+        mask[i] |= 1ull << st->tube;
+}
+
 #define SELECT_TRY(expr)                                                              \
     do {                                                                              \
         hipError_t e__ = (expr);                                                      \
@@ -258,6 +321,10 @@ void PanelSelect::release()
         cap_[s] = 0;
     }
     for (auto &e : ev_) {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+    }
+    for (auto &e : ev_layer_) {
         if (e) (void)hipEventDestroy(e);
         e = nullptr;
     }
@@ -408,6 +475,178 @@ int PanelSelect::rounds(const uint64_t *d_inc, const uint64_t *d_sym, int n, lon
     if (covered_out)
         for (long g = 0; g < G; ++g)
             for (int b = 0; b < S && g * S + b < n_seg; ++b) covered_out[g * S + b] = (uint8_t)((h_cov[(size_t)g] >> b) & 1ull);
+    return MSSPE_OK;
+}
+
+int PanelSelect::rounds_depth(const uint64_t *d_inc, const uint64_t *d_sym, int n, long n_seg, int S, int min_gain,
+                              int max_tubes, int depth, uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out,
+                              int *n_picked_out, uint8_t *tube_out, uint8_t *barred_out, int *n_tubes_used_out,
+                              uint8_t *pick_layer_out, uint8_t *depth_all_out, uint8_t *depth_kept_out,
+                              long long *counts_out, int n_cu, hipStream_t stream, std::string &err)
+{
+    const long G = (n_seg + S - 1) / S;
+    const int W = (n + 63) / 64;
+    const size_t n_pad = ((size_t)n + 63) & ~(size_t)63, cells = (size_t)G * 64;
+    const uint64_t tubes_mask = max_tubes >= 64 ? ~0ull : (1ull << max_tubes) - 1;
+    // the two counts of depth_all and the planes all, cnt (a byte per (group, bit)); two primer masks: all, forced
+    int rc;
+    if ((rc = ensure(kDepth, 2 * sizeof(unsigned long long) + 2 * cells, err)) ||
+        (rc = ensure(kPrimerMask, 2 * (size_t)n, err)))
+        return rc;
+    for (auto &e : ev_layer_)
+        if (!e && hipEventCreate(&e) != hipSuccess) {
+            err = "panel select: hipEventCreate failed";
+            return MSSPE_ERR_DEVICE;
+        }
+    uint64_t *d_cov = (uint64_t *)buf_[kCov], *d_new = (uint64_t *)buf_[kNew], *d_mask = (uint64_t *)buf_[kMask];
+    SelectState *st = (SelectState *)(d_cov + G);
+    uint32_t *d_touched = (uint32_t *)buf_[kTouched], *d_gain = (uint32_t *)buf_[kGain];
+    uint32_t *d_order = (uint32_t *)buf_[kOrder], *d_gains = d_order + n, *d_forced = (uint32_t *)buf_[kForced];
+    uint8_t *d_flags = (uint8_t *)buf_[kBytes], *d_tube = d_flags + n;
+    unsigned long long *d_counts = (unsigned long long *)buf_[kDepth];   // first: 8-byte aligned
+    uint8_t *d_all = (uint8_t *)(d_counts + 2), *d_cnt = d_all + cells;
+    uint8_t *d_every = (uint8_t *)buf_[kPrimerMask], *d_isforced = d_every + n;
+    SELECT_TRY(hipEventRecord(ev_[0], stream));
+
+    // (1) the first barring and the column sums: depth_all over all primers, the first cnt over the forced ones
+    std::vector<uint8_t> flags((size_t)n), masks(2 * (size_t)n);
+    std::vector<uint32_t> forced_idx;
+    for (int p = 0; p < n; ++p) {
+        flags[(size_t)p] = keep_out[p] ? 0 : kLive;
+        masks[(size_t)p] = 1;
+        masks[(size_t)n + (size_t)p] = keep_out[p] ? 1 : 0;
+        if (keep_out[p]) forced_idx.push_back((uint32_t)p);
+    }
+    SELECT_TRY(hipMemsetAsync(st, 0, sizeof(SelectState), stream));
+    SELECT_TRY(hipMemsetAsync(d_counts, 0, 2 * sizeof(unsigned long long), stream));
+    SELECT_TRY(hipMemsetAsync(d_tube, MSSPE_TUBE_NONE, (size_t)n, stream));
+    SELECT_TRY(hipMemcpyAsync(d_flags, flags.data(), (size_t)n, hipMemcpyHostToDevice, stream));
+    SELECT_TRY(hipMemcpyAsync(d_every, masks.data(), 2 * (size_t)n, hipMemcpyHostToDevice, stream));
+    const unsigned gx = (unsigned)((n + kThreads - 1) / kThreads);
+    if (!forced_idx.empty())
+        SELECT_TRY(hipMemcpyAsync(d_forced, forced_idx.data(), sizeof(uint32_t) * forced_idx.size(),
+                                  hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(k_select_bar0, dim3(gx), dim3(kThreads), 0, stream, d_sym, n, W, d_forced,
+                       (int)forced_idx.size(), tubes_mask, d_mask, d_flags);
+    SELECT_TRY(hipGetLastError());
+    SELECT_TRY(hipEventRecord(ev_layer_[0], stream));
+    PanelThin::colsum(d_inc, n, G, d_every, (uint32_t)depth, d_all, d_counts + 0, d_counts + 1, n_cu, stream);
+    if (!forced_idx.empty())
+        PanelThin::colsum(d_inc, n, G, d_isforced, (uint32_t)depth, d_cnt, nullptr, nullptr, n_cu, stream);
+    else
+        SELECT_TRY(hipMemsetAsync(d_cnt, 0, cells, stream));
+    SELECT_TRY(hipGetLastError());
+
+    // (2) the layers.  Each opens with its closed words and its first gains (k_select_gain0 also adds to covered_all
+    // in the state, once per layer: nothing here reads it) and then runs rounds()'s batches; the round that stops a
+    // layer has set `done`, which the next layer clears.  Layer r + 1 exists while r < depth and some segment has
+    // more than r primers.
+    const unsigned gy = (unsigned)std::max<long>(1, std::min<long>(std::min<long>(G, 65535), 2048 / gx));
+    const unsigned ga = (unsigned)((std::max<long>(G, n) + kThreads - 1) / kThreads);
+    SelectState hs{};
+    std::vector<uint32_t> layer_end;   // picks made when layer r ended
+    float layer_ms = 0.f;
+    for (uint32_t r = 1;; ++r) {
+        if (r > 1) {
+            SELECT_TRY(hipEventRecord(ev_layer_[0], stream));
+            SELECT_TRY(hipMemsetAsync(&st->done, 0, sizeof(uint32_t), stream));
+        }
+        SELECT_TRY(hipMemsetAsync(d_gain, 0, sizeof(uint32_t) * (size_t)n, stream));
+        hipLaunchKernelGGL(k_select_layer, dim3((unsigned)((cells + kThreads - 1) / kThreads)), dim3(kThreads), 0,
+                           stream, d_all, d_cnt, (int)G, S, n_seg, r, d_cov, st);
+        hipLaunchKernelGGL(k_select_gain0, dim3((unsigned)((G + kChunk - 1) / kChunk)), dim3(kThreads), 0, stream,
+                           d_inc, n, n_pad, (int)G, d_cov, d_gain, st);
+        SELECT_TRY(hipGetLastError());
+        SELECT_TRY(hipEventRecord(ev_layer_[1], stream));
+        if (r == 1) SELECT_TRY(hipEventRecord(ev_[1], stream));
+        for (int batch = 0;; ++batch) {
+            for (int b = 0; b < kRoundsPerBatch; ++b) {
+                hipLaunchKernelGGL(k_select_pick, dim3(1), dim3(kThreads), 0, stream, d_gain, d_flags, d_mask, n,
+                                   (uint32_t)min_gain, tubes_mask, d_order, d_gains, d_tube, st);
+                hipLaunchKernelGGL(k_select_apply_depth, dim3(ga), dim3(kThreads), 0, stream, d_inc, n_pad, (int)G,
+                                   d_cov, d_cnt, d_all, r, d_touched, d_new, d_sym, n, W, d_mask, st);
+                hipLaunchKernelGGL(k_select_update, dim3(gx, gy), dim3(kThreads), 0, stream, d_inc, n, n_pad,
+                                   d_touched, d_new, d_gain, st);
+            }
+            SELECT_TRY(hipGetLastError());
+            SELECT_TRY(hipMemcpyAsync(&hs, st, sizeof hs, hipMemcpyDeviceToHost, stream));
+            SELECT_TRY(hipStreamSynchronize(stream));
+            if (batch == 0) {
+                float ms = 0.f;
+                (void)hipEventElapsedTime(&ms, ev_layer_[0], ev_layer_[1]);
+                layer_ms += ms;
+            }
+            if (hs.done) break;
+            if (batch + 1 >= n / kRoundsPerBatch + 2) {
+                err = "panel select: more rounds in a layer than primers";
+                return MSSPE_ERR_DEVICE;
+            }
+        }
+        if (hs.n_picked > (uint32_t)n) break;   // reported below
+        layer_end.push_back(hs.n_picked);
+        if (r >= (uint32_t)depth || hs.deeper != r + 1) break;
+    }
+    SELECT_TRY(hipEventRecord(ev_[2], stream));
+
+    const int n_picked = (int)hs.n_picked;
+    if (n_picked > n || hs.used > (uint32_t)max_tubes) {
+        err = "panel select: more picks than primers, or a tube past max_tubes";
+        return MSSPE_ERR_DEVICE;
+    }
+    if (n_picked) {
+        SELECT_TRY(hipMemcpyAsync(order_out, d_order, sizeof(uint32_t) * (size_t)n_picked, hipMemcpyDeviceToHost, stream));
+        SELECT_TRY(hipMemcpyAsync(gain_out, d_gains, sizeof(uint32_t) * (size_t)n_picked, hipMemcpyDeviceToHost, stream));
+    }
+    std::vector<uint64_t> h_mask((size_t)n);
+    std::vector<uint8_t> h_depth(2 * cells);   // all and cnt lie side by side
+    unsigned long long h_counts[2] = {};
+    SELECT_TRY(hipMemcpyAsync(tube_out, d_tube, (size_t)n, hipMemcpyDeviceToHost, stream));
+    SELECT_TRY(hipMemcpyAsync(flags.data(), d_flags, (size_t)n, hipMemcpyDeviceToHost, stream));
+    SELECT_TRY(hipMemcpyAsync(h_mask.data(), d_mask, sizeof(uint64_t) * (size_t)n, hipMemcpyDeviceToHost, stream));
+    SELECT_TRY(hipMemcpyAsync(h_counts, d_counts, sizeof h_counts, hipMemcpyDeviceToHost, stream));
+    SELECT_TRY(hipMemcpyAsync(h_depth.data(), d_all, 2 * cells, hipMemcpyDeviceToHost, stream));
+    SELECT_TRY(hipEventSynchronize(ev_[2]));
+    SELECT_TRY(hipStreamSynchronize(stream));
+    for (int ph = 0; ph < 2; ++ph) {
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, ev_[ph], ev_[ph + 1]);
+        phase_us_[ph] = (long long)(ms * 1000.0f);
+    }
+    layer_us_ = (long long)(layer_ms * 1000.0f);
+    layers_ = (long long)layer_end.size();
+    rounds_ = hs.rounds;
+    tubes_ = hs.used;
+    for (int i = 0, layer = 0; i < n_picked; ++i) {
+        if (order_out[i] >= (uint32_t)n) {
+            err = "panel select: a pick outside the panel";
+            return MSSPE_ERR_DEVICE;
+        }
+        keep_out[order_out[i]] = 1;
+        while ((uint32_t)i >= layer_end[(size_t)layer]) ++layer;   // i < n_picked == layer_end.back()
+        if (pick_layer_out) pick_layer_out[i] = (uint8_t)(layer + 1);
+    }
+    for (int p = 0; p < n; ++p) {
+        const bool barred = !keep_out[p] && ((flags[(size_t)p] & kSelf) || (h_mask[(size_t)p] & tubes_mask) == tubes_mask);
+        barred_ += barred;
+        if (barred_out) barred_out[p] = barred ? 1 : 0;
+    }
+    long long kept1 = 0, keptR = 0;
+    for (long g = 0; g < G; ++g)
+        for (int b = 0; b < S && g * S + b < n_seg; ++b) {
+            const uint8_t a = h_depth[(size_t)g * 64 + (size_t)b], c = h_depth[cells + (size_t)g * 64 + (size_t)b];
+            kept1 += c >= 1;
+            keptR += c >= depth;
+            if (depth_all_out) depth_all_out[g * S + b] = a;
+            if (depth_kept_out) depth_kept_out[g * S + b] = c;
+        }
+    *n_picked_out = n_picked;
+    if (n_tubes_used_out) *n_tubes_used_out = (int)hs.used;
+    if (counts_out) {
+        counts_out[0] = (long long)h_counts[0];
+        counts_out[1] = kept1;
+        counts_out[2] = (long long)h_counts[1];
+        counts_out[3] = keptR;
+    }
     return MSSPE_OK;
 }
 

@@ -27,7 +27,19 @@ public:
                uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out, int *n_picked_out, uint8_t *tube_out,
                uint8_t *barred_out, uint8_t *covered_out, long long *covered_all_out, long long *covered_kept_out,
                int *n_tubes_used_out, int n_cu, hipStream_t stream, std::string &err);
+    // rounds_depth: the layered rule of msspe_panel_select_depth*  over the same inc and sym: layer 1 is
+    // rounds(), layer r then adds primers for the segments that still have fewer than r, the barring carried along.
+    // depth is 1..255 (checked by the caller).  pick_layer_out (optional, per position of the order), depth_all_out /
+    // depth_kept_out (optional, n_seg bytes, saturating at 255), counts_out[4] (optional): as the C call's.
+    int rounds_depth(const uint64_t *inc, const uint64_t *sym, int n, long n_seg, int S, int min_gain, int max_tubes,
+                     int depth, uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out, int *n_picked_out,
+                     uint8_t *tube_out, uint8_t *barred_out, int *n_tubes_used_out, uint8_t *pick_layer_out,
+                     uint8_t *depth_all_out, uint8_t *depth_kept_out, long long *counts_out, int n_cu,
+                     hipStream_t stream, std::string &err);
     void release();
+    // the last depth run: its layers, and device time of the column sums and of every layer's init and first gains
+    long long depth_layers() const { return layers_; }
+    long long depth_layer_us() const { return layer_us_; }
     // the last run: rounds enqueued that ran (the picks and the one that stopped), tubes in use, primers barred, and
     // device time in microseconds of the first state (forced rows, first barring, first gains) and of the rounds
     long long n_rounds() const { return rounds_; }
@@ -36,16 +48,17 @@ public:
     const long long *phase_us() const { return phase_us_; }
     void reset_stats()
     {
-        rounds_ = tubes_ = barred_ = 0;
+        rounds_ = tubes_ = barred_ = layers_ = layer_us_ = 0;
         phase_us_[0] = phase_us_[1] = 0;
     }
 
 private:
-    enum { kSlots = 9 };
+    enum { kSlots = 11 };
     void *buf_[kSlots] = {};
     size_t cap_[kSlots] = {};
     hipEvent_t ev_[3] = {};
-    long long rounds_ = 0, tubes_ = 0, barred_ = 0;
+    hipEvent_t ev_layer_[2] = {};   // around a layer's init and first gains; reused layer after layer
+    long long rounds_ = 0, tubes_ = 0, barred_ = 0, layers_ = 0, layer_us_ = 0;
     long long phase_us_[2] = {};
     int ensure(int slot, size_t bytes, std::string &err);
 };

@@ -543,6 +543,15 @@ int PanelThin::run_depth(MismatchCoverage &cov, const SeqView &seqs, int n_seq, 
     return MSSPE_OK;
 }
 
+void PanelThin::colsum(const uint64_t *inc, int n, long G, const uint8_t *mask, uint32_t R, uint8_t *out,
+                       unsigned long long *c1, unsigned long long *cR, int n_cu, hipStream_t stream)
+{
+    const size_t n_pad = ((size_t)n + 63) & ~(size_t)63;
+    const int blocks = (int)std::max<long>(1, std::min<long>((G + 3) / 4, 8L * n_cu));
+    hipLaunchKernelGGL(k_thin_colsum, dim3(blocks), dim3(kThreads), 0, stream, inc, n, n_pad, (int)G, mask,
+                       (const uint8_t *)nullptr, R, out, c1, cR);
+}
+
 int PanelThin::rounds_depth(int n, long n_seg, int S, int min_gain, int depth, const uint8_t *shadow,
                             uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out, int *n_picked_out,
                             uint8_t *depth_all_out, uint8_t *depth_kept_out, long long *counts_out, int n_cu,

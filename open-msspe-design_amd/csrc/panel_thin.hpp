@@ -52,6 +52,11 @@ public:
                      uint8_t *depth_kept_out, long long *counts_out, int n_cu, hipStream_t stream, std::string &err);
     static int shadows(const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
                        const uint8_t *forced, uint8_t *shadow_out);
+    // The column sums alone, enqueued on `stream` (k_thin_colsum, for PanelSelect::rounds_depth): out[g * 64 + b] =
+    // min(255, primers p with mask[p] set and bit b in inc[g * n_pad + p]) over G groups, G * 64 bytes; c1 / cR
+    // (device, optional, both or neither): += the segments with a count of at least 1 / of at least R.
+    static void colsum(const uint64_t *inc, int n, long G, const uint8_t *mask, uint32_t R, uint8_t *out,
+                       unsigned long long *c1, unsigned long long *cR, int n_cu, hipStream_t stream);
     void release();
     // the last depth run: shadows among its primers, device time of the three column-sum passes and the init
     long long depth_shadows() const { return shadows_; }

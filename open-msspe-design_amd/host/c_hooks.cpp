@@ -67,7 +67,7 @@ int odm_parse_args(int argc, const char *const *argv, char *out, size_t cap)
           << "\nmax_cross_dimer_end_tm=" << a.max_cross_dimer_end_tm_text << "\ncoverage_tm=" << a.coverage_tm_text << "\ncoverage_thal=" << a.coverage_thal
           << "\nselect_by_coverage=" << a.select_by_coverage << "\nthin_panel=" << a.thin_panel << "\nthin_mismatches=" << a.thin_mismatches
           << "\nthin_3p_exact=" << a.thin_3p_exact << "\nthin_min_gain=" << a.thin_min_gain
-          << "\nthin_depth=" << a.thin_depth
+          << "\nthin_depth=" << a.thin_depth << "\nselect_depth=" << a.select_depth
           << "\nthin_tm=" << a.thin_tm_text << "\nthin_thal=" << a.thin_thal
           << "\nseed_mismatches=" << a.seed_mismatches << "\nseed_3p_exact=" << a.seed_3p_exact
           << "\nseed_tm=" << a.seed_tm_text << "\nseed_thal=" << a.seed_thal
@@ -227,6 +227,51 @@ int odm_select_panel(const uint64_t *rows, int n, int words, const uint64_t *bit
         counts_out[1] = (long long)s.covered_kept;
         counts_out[2] = s.tubes_used;
         counts_out[3] = s.rounds;
+    }
+    return (int)s.order.size();
+}
+
+// odm_select_panel's arguments plus n_seg and depth.  layer[i]: the layer of pick i; depth_all / depth_kept (n_seg bytes
+// each, or NULL); counts_out[0..6]: segments with depth_all >= 1, depth_kept >= 1, depth_all >= depth, depth_kept >=
+// depth, then tubes in use, rounds, layers.  Returns the number of picks (select_panel_depth).
+int odm_select_panel_depth(const uint64_t *rows, int n, int words, int n_seg, const uint64_t *bitmap, int depth,
+                           int max_tubes, int min_gain, const uint8_t *forced, int drop_self, int *order, int *gains,
+                           int *layer, uint8_t *keep, int *tube, uint8_t *barred, uint8_t *depth_all,
+                           uint8_t *depth_kept, long long *counts_out)
+{
+    std::vector<std::vector<uint64_t>> r((size_t)n);
+    for (int p = 0; p < n; ++p) r[(size_t)p].assign(rows + (size_t)p * words, rows + (size_t)(p + 1) * words);
+    std::vector<char> f;
+    if (forced) f.assign(forced, forced + n);
+    std::vector<std::string> names((size_t)n);
+    for (int p = 0; p < n; ++p) names[(size_t)p] = std::to_string(p);
+    ConflictGraph g;
+    g.nodes = names;
+    const int W = (n + 63) / 64;
+    for (int p = 0; p < n; ++p)
+        for (int u = 0; u < n; ++u)
+            if ((bitmap[(size_t)p * W + (u >> 6)] >> (u & 63)) & 1ull)
+                if (!(drop_self && p == u)) g.edges[names[(size_t)p]].insert(names[(size_t)u]);
+    const SelectDepthResult s = select_panel_depth(r, names, g, (size_t)n_seg, depth, max_tubes, min_gain, f);
+    for (size_t i = 0; i < s.order.size(); ++i) {
+        order[i] = s.order[i];
+        gains[i] = s.gains[i];
+        layer[i] = s.layer[i];
+    }
+    for (int p = 0; p < n; ++p) {
+        keep[p] = (uint8_t)s.keep[(size_t)p];
+        tube[p] = s.tube[(size_t)p];
+        barred[p] = (uint8_t)s.barred[(size_t)p];
+    }
+    for (int i = 0; i < n_seg; ++i) {
+        if (depth_all) depth_all[i] = s.depth_all[(size_t)i];
+        if (depth_kept) depth_kept[i] = s.depth_kept[(size_t)i];
+    }
+    if (counts_out) {
+        for (int i = 0; i < 4; ++i) counts_out[i] = s.counts[i];
+        counts_out[4] = s.tubes_used;
+        counts_out[5] = s.rounds;
+        counts_out[6] = s.layers;
     }
     return (int)s.order.size();
 }

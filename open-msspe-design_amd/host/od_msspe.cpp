@@ -88,6 +88,7 @@ const OptSpec kOpts[] = {
     {"--thin-tm", "THIN_TM", OptSpec::Str, OFF(thin_tm_text)},
     {"--thin-thal", "THIN_THAL", OptSpec::Str, OFF(thin_thal)},
     {"--select-by-coverage", "SELECT_BY_COVERAGE", OptSpec::Bool, OFF(select_by_coverage)},
+    {"--select-depth", "SELECT_DEPTH", OptSpec::Int, OFF(select_depth)},
     {"--seed-mismatches", "SEED_MISMATCHES", OptSpec::OptInt, OFF(seed_mismatches)},
     {"--seed-3p-exact", "SEED_3P_EXACT", OptSpec::Str, OFF(seed_3p_exact_text)},
     {"--seed-tm", "SEED_TM", OptSpec::Str, OFF(seed_tm_text)},
@@ -158,7 +159,9 @@ std::string Args::usage()
          "with thal (--thin-thal any | end1), and no held segment is lost at G = 1; a segment's best t may fall.\n"
          "--select-by-coverage true replaces the cover (or the tube split) by a selection that looks at coverage: round\n"
          "after round the primer covering the most segments nothing kept covers yet is kept, and its conflict\n"
-         "neighbours are barred (with --tubes <N>: from its tube only). The match rule is --thin-panel's\n"
+         "neighbours are barred (with --tubes <N>: from its tube only). With --select-depth <R> (1..255) the selection\n"
+         "then runs on in layers: layer r adds primers for the segments that still have fewer than r, so a segment\n"
+         "keeps up to R primers and asking for depth never costs a segment. The match rule is --thin-panel's\n"
          "(--thin-mismatches, --thin-3p-exact, --thin-min-gain, --thin-tm, --thin-thal); the primers of\n"
          "--existing-primers are kept and bar their neighbours from every tube. Conflicts may cost segments. One\n"
          "device; not with --thin-panel true, --keep-all true or --cover-on-device true.\n"
@@ -279,6 +282,9 @@ Args Args::parse(int argc, const char *const *argv)
         a.coverage_3p_exact = (int)e;
     }
     if (a.select_by_coverage == "true") {
+        if (a.select_depth < 1 || a.select_depth > 255)
+            throw UsageError("error: invalid value '" + std::to_string(a.select_depth) +
+                             "' for '--select-depth <...>'\n  [1 .. 255]");
         if (a.thin_panel == "true")
             throw UsageError("error: '--select-by-coverage true' keeps only what the coverage needs and cannot be "
                              "combined with '--thin-panel true'");
@@ -311,13 +317,14 @@ Args Args::parse(int argc, const char *const *argv)
         if (a.thin_min_gain < 1)
             throw UsageError("error: invalid value '" + std::to_string(a.thin_min_gain) +
                              "' for '--thin-min-gain <...>'\n  [1 ..]");
-        if (a.thin_panel == "true") {   // the selection has no depth
+        if (a.thin_panel == "true") {   // the selection's depth is --select-depth
             if (a.thin_depth < 1 || a.thin_depth > 255)
                 throw UsageError("error: invalid value '" + std::to_string(a.thin_depth) +
                                  "' for '--thin-depth <...>'\n  [1 .. 255]");
         } else if (a.thin_depth > 1) {
             throw UsageError("error: '--thin-depth " + std::to_string(a.thin_depth) +
-                             "' cannot be combined with '--select-by-coverage true': the selection has no depth");
+                             "' cannot be combined with '--select-by-coverage true': the selection's depth is "
+                             "'--select-depth <R>'");
         }
         if (!a.thin_tm_text.empty()) {
             a.thin_tm = std::strtof(a.thin_tm_text.c_str(), &end);
@@ -1324,19 +1331,15 @@ ThinResult thin_panel(const std::vector<std::vector<uint64_t>> &rows, int min_ga
     return out;
 }
 
-SelectResult select_panel(const std::vector<std::vector<uint64_t>> &rows, const std::vector<std::string> &primers,
-                          const ConflictGraph &g, int max_tubes, int min_gain, const std::vector<char> &forced)
+// the cover's graph over the primers' indices: symmetric, a self loop kept apart
+static void select_graph(const std::vector<std::string> &primers, const ConflictGraph &g,
+                         std::vector<std::set<size_t>> &adj, std::vector<char> &self)
 {
-    const size_t n = rows.size();
-    size_t words = 0;
-    for (const auto &r : rows) words = std::max(words, r.size());
-    auto word = [&](size_t p, size_t w) { return w < rows[p].size() ? rows[p][w] : 0ull; };
-    auto is_forced = [&](size_t p) { return p < forced.size() && forced[p]; };
-    // the cover's graph over the primers' indices: symmetric, a self loop kept apart
+    const size_t n = primers.size();
     std::map<std::string, size_t> id;
     for (size_t p = 0; p < n; ++p) id.emplace(primers[p], p);
-    std::vector<std::set<size_t>> adj(n);
-    std::vector<char> self(n, 0);
+    adj.assign(n, {});
+    self.assign(n, 0);
     for (const auto &kv : g.edges) {
         const auto a = id.find(kv.first);
         if (a == id.end()) continue;
@@ -1350,6 +1353,91 @@ SelectResult select_panel(const std::vector<std::vector<uint64_t>> &rows, const 
             }
         }
     }
+}
+
+SelectDepthResult select_panel_depth(const std::vector<std::vector<uint64_t>> &rows,
+                                     const std::vector<std::string> &primers, const ConflictGraph &g, size_t n_seg,
+                                     int depth, int max_tubes, int min_gain, const std::vector<char> &forced)
+{
+    const size_t n = rows.size();
+    auto bit = [&](size_t p, size_t s) { return (s >> 6) < rows[p].size() && ((rows[p][s >> 6] >> (s & 63)) & 1ull); };
+    auto is_forced = [&](size_t p) { return p < forced.size() && forced[p]; };
+    std::vector<std::set<size_t>> adj;
+    std::vector<char> self;
+    select_graph(primers, g, adj, self);
+    const uint64_t all_tubes = max_tubes >= 64 ? ~0ull : (1ull << max_tubes) - 1;
+    SelectDepthResult out;
+    out.keep.assign(n, 0);
+    out.tube.assign(n, -1);
+    out.barred.assign(n, 0);
+    std::vector<int> all(n_seg, 0), cnt(n_seg, 0);   // the true counts
+    std::vector<uint64_t> mask(n, 0);
+    int deepest = 0;
+    for (size_t p = 0; p < n; ++p) {
+        out.keep[p] = is_forced(p) ? 1 : 0;
+        for (size_t s = 0; s < n_seg; ++s)
+            if (bit(p, s)) {
+                ++all[s];
+                if (is_forced(p)) ++cnt[s];
+            }
+        if (is_forced(p))   // the panel is in every tube
+            for (size_t u : adj[p]) mask[u] = all_tubes;
+    }
+    for (size_t s = 0; s < n_seg; ++s) deepest = std::max(deepest, all[s]);
+    out.layers = std::min(depth, std::max(1, deepest));
+    for (int r = 1; r <= out.layers; ++r)
+        for (;;) {   // every round from scratch: the device keeps its gains up to date instead
+            long best = -1;
+            size_t best_gain = 0;
+            for (size_t p = 0; p < n; ++p) {
+                if (out.keep[p] || self[p] || (mask[p] & all_tubes) == all_tubes) continue;
+                size_t gain = 0;
+                for (size_t s = 0; s < n_seg; ++s) gain += bit(p, s) && cnt[s] < std::min(r, all[s]) ? 1 : 0;
+                if (best < 0 || gain > best_gain) {   // ">": the lowest index among equals
+                    best = (long)p;
+                    best_gain = gain;
+                }
+            }
+            ++out.rounds;
+            if (best < 0 || best_gain < (size_t)min_gain) break;   // the layer ends
+            const size_t p = (size_t)best;
+            const int t = __builtin_ctzll(~mask[p] & all_tubes);
+            out.order.push_back((int)best);
+            out.gains.push_back((int)best_gain);
+            out.layer.push_back(r);
+            out.keep[p] = 1;
+            out.tube[p] = t;
+            out.tubes_used = std::max(out.tubes_used, t + 1);
+            for (size_t s = 0; s < n_seg; ++s)
+                if (bit(p, s)) ++cnt[s];   // open or not
+            for (size_t u : adj[p]) mask[u] |= 1ull << t;
+        }
+    for (size_t p = 0; p < n; ++p)
+        out.barred[p] = !out.keep[p] && (self[p] || (mask[p] & all_tubes) == all_tubes) ? 1 : 0;
+    out.depth_all.assign(n_seg, 0);
+    out.depth_kept.assign(n_seg, 0);
+    for (size_t s = 0; s < n_seg; ++s) {
+        out.depth_all[s] = (uint8_t)std::min(all[s], 255);
+        out.depth_kept[s] = (uint8_t)std::min(cnt[s], 255);
+        out.counts[0] += all[s] >= 1;
+        out.counts[1] += cnt[s] >= 1;
+        out.counts[2] += all[s] >= depth;
+        out.counts[3] += cnt[s] >= depth;
+    }
+    return out;
+}
+
+SelectResult select_panel(const std::vector<std::vector<uint64_t>> &rows, const std::vector<std::string> &primers,
+                          const ConflictGraph &g, int max_tubes, int min_gain, const std::vector<char> &forced)
+{
+    const size_t n = rows.size();
+    size_t words = 0;
+    for (const auto &r : rows) words = std::max(words, r.size());
+    auto word = [&](size_t p, size_t w) { return w < rows[p].size() ? rows[p][w] : 0ull; };
+    auto is_forced = [&](size_t p) { return p < forced.size() && forced[p]; };
+    std::vector<std::set<size_t>> adj;
+    std::vector<char> self;
+    select_graph(primers, g, adj, self);
     const uint64_t all_tubes = max_tubes >= 64 ? ~0ull : (1ull << max_tubes) - 1;
     SelectResult out;
     out.keep.assign(n, 0);
@@ -1746,7 +1834,8 @@ std::string thin_panel_on_device(Engine &eng, const DeviceAlignment &aln, std::v
 
 std::string select_report(int mode, float tm_threshold, int max_mismatches, int exact_3p, int min_gain, int max_tubes,
                           size_t kept_f, size_t n_f, size_t kept_r, size_t n_r, size_t forced, size_t barred,
-                          size_t covered_all, size_t covered_kept, size_t segments, const std::vector<size_t> *per_tube)
+                          size_t covered_all, size_t covered_kept, size_t segments, const std::vector<size_t> *per_tube,
+                          int depth, size_t deep_all, size_t deep_kept)
 {
     const std::string x = std::to_string(kept_f + kept_r), y = std::to_string(n_f + n_r), t = std::to_string(segments);
     const std::string what = mode ? "held " : "covered ";
@@ -1757,12 +1846,12 @@ std::string select_report(int mode, float tm_threshold, int max_mismatches, int 
     else
         s += "up to " + std::to_string(max_mismatches) + " mismatches, last ";
     s += std::to_string(exact_3p) + " bases exact, gain >= " + std::to_string(min_gain) + ", tubes <= " +
-         std::to_string(max_tubes) + "):\n  Rule:     each round keeps the primer with the most new segments and bars its "
+         std::to_string(max_tubes) + thin_depth_tag(depth) + "):\n  Rule:     each round keeps the primer with the most new segments and bars its "
          "conflict neighbours from its tube\n  Primers:  kept " + x + " of " + y + " (forward " + std::to_string(kept_f) +
          " of " + std::to_string(n_f) + ", reverse " + std::to_string(kept_r) + " of " + std::to_string(n_r) + "), " +
          std::to_string(forced) + " forced\n  Barred:   " + std::to_string(barred) + " by conflicts\n  Segments: " + what +
          std::to_string(covered_all) + "/" + t + " by all " + y + ", " + std::to_string(covered_kept) + "/" + t +
-         " by the kept " + x + "\n";
+         " by the kept " + x + "\n" + thin_depth_line(depth, deep_all, deep_kept, t, y, x);
     if (per_tube)
         for (size_t i = 0; i < per_tube->size(); ++i)
             s += "  Tube " + std::to_string(i + 1) + ": " + std::to_string((*per_tube)[i]) + " primers\n";
@@ -1777,7 +1866,7 @@ std::string select_panel_on_device(Engine &eng, const DeviceAlignment &aln, cons
                                    bool screen, bool drop_self_pairs, float dg_threshold, std::vector<KmerStat> &kept_f,
                                    std::vector<KmerStat> &kept_r, std::map<std::string, int> &tubes,
                                    const std::function<void(const KmerStat &, bool)> &dropped,
-                                   const NtthalOptions *end_rule)
+                                   const NtthalOptions *end_rule, int depth)
 {
     // the graph's nodes are distinct words: the panel's first, then the new primers in their lists' order; a word met
     // again (the other direction's list) is not offered
@@ -1803,7 +1892,7 @@ std::string select_panel_on_device(Engine &eng, const DeviceAlignment &aln, cons
     for (size_t i = new_r; i < all_r.size(); ++i) forced[all_f.size() + i] = 1;
     std::vector<uint32_t> order(n + 1), gains(n + 1);
     int n_picked = 0, used = 0;
-    long long covered_all = 0, covered_kept = 0;
+    long long covered_all = 0, covered_kept = 0, counts[4] = {0, 0, 0, 0};   // counts: --select-depth above 1
     const size_t L = aln.length();
     const size_t P = L < (size_t)segment_size ? 0 : (L - (size_t)segment_size) / (size_t)overlap_size + 1;
     const auto wf = pack_words(eng, all_f, kmer_size), wr = pack_words(eng, all_r, kmer_size);
@@ -1842,11 +1931,19 @@ std::string select_panel_on_device(Engine &eng, const DeviceAlignment &aln, cons
         const msspe_kmer_opt opt{segment_size, overlap_size, window_size, kmer_size, 0, 0};
         const msspe_seed_rule rule{max_mismatches, exact_3p, mode, mode ? &chem : nullptr, tm_threshold};
         const msspe_select_opt so{min_gain, max_tubes, drop_self_pairs ? 1 : 0};
-        rc = msspe_panel_select_packed_dev(eng.ctx(), aln.device(), aln.rows(), L, &opt, &rule, &so, wf.data(),
-                                           (int)wf.size(), wr.data(), (int)wr.size(), forced.data(),
-                                           static_cast<const uint64_t *>(d_bitmap), keep.data(), order.data(),
-                                           gains.data(), &n_picked, tube.data(), barred.data(), nullptr, &covered_all,
-                                           &covered_kept, &used);
+        const msspe_select_depth_opt deep{min_gain, max_tubes, drop_self_pairs ? 1 : 0, depth};
+        rc = depth <= 1
+                 ? msspe_panel_select_packed_dev(eng.ctx(), aln.device(), aln.rows(), L, &opt, &rule, &so, wf.data(),
+                                                 (int)wf.size(), wr.data(), (int)wr.size(), forced.data(),
+                                                 static_cast<const uint64_t *>(d_bitmap), keep.data(), order.data(),
+                                                 gains.data(), &n_picked, tube.data(), barred.data(), nullptr,
+                                                 &covered_all, &covered_kept, &used)
+                 : msspe_panel_select_depth_packed_dev(eng.ctx(), aln.device(), aln.rows(), L, &opt, &rule, &deep,
+                                                       wf.data(), (int)wf.size(), wr.data(), (int)wr.size(),
+                                                       forced.data(), static_cast<const uint64_t *>(d_bitmap),
+                                                       keep.data(), order.data(), gains.data(), &n_picked, tube.data(),
+                                                       barred.data(), &used, nullptr, nullptr, nullptr, counts);
+        if (depth > 1) covered_all = counts[0], covered_kept = counts[1];
     }
     if (d_pool) (void)msspe_device_free(eng.ctx(), d_pool);
     if (d_bitmap) (void)msspe_device_free(eng.ctx(), d_bitmap);
@@ -1873,7 +1970,8 @@ std::string select_panel_on_device(Engine &eng, const DeviceAlignment &aln, cons
         else dropped(rev[i], barred_r[i] != 0);
     return select_report(mode, tm_threshold, max_mismatches, exact_3p, min_gain, max_tubes, kept_f.size(), fwd.size(),
                          kept_r.size(), rev.size(), n - new_f - new_r, n_barred, (size_t)covered_all,
-                         (size_t)covered_kept, (size_t)aln.rows() * P, list_tubes ? &per_tube : nullptr);
+                         (size_t)covered_kept, (size_t)aln.rows() * P, list_tubes ? &per_tube : nullptr, depth,
+                         (size_t)counts[2], (size_t)counts[3]);
 }
 
 DeviceBackground::DeviceBackground(Engine &eng, const std::vector<SequenceRecord> &records)
@@ -2322,7 +2420,8 @@ Selection select_primers(Engine &eng, const DeviceAlignment &aln, const Args &ar
             args.kmer_size, args.thin_mismatches, args.thin_3p_exact, args.thin_min_gain, chem, mode, args.thin_tm,
             std::max(1, args.tubes), args.tubes > 0, cfg.check_cross_dimers, !cfg.check_self_dimers, opts.dg,
             sel.good_f, sel.good_r, sel.tubes,
-            [&](const KmerStat &s, bool barred) { reject(s, barred ? "select_conflict" : "select_unneeded"); }, &opts);
+            [&](const KmerStat &s, bool barred) { reject(s, barred ? "select_conflict" : "select_unneeded"); }, &opts,
+            args.select_depth);
         timer.lap("stage C + selection by coverage");
         return sel;
     }

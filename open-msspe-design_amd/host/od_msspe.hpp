@@ -111,6 +111,10 @@ struct Args {
     // all-zero graph; the incidence rule is --thin-panel's (--thin-mismatches, --thin-3p-exact, --thin-min-gain,
     // --thin-tm, --thin-thal, read with this switch too).  "false": nothing changes.
     std::string select_by_coverage = "false";
+    // --select-depth R (with --select-by-coverage true): the selection runs on in layers, layer r adding primers for
+    // the segments that still have fewer than r (msspe_panel_select_depth_packed_dev); the block's
+    // first line gains ", depth R" and the thinning's "Depth:" line follows "Segments:".  1: nothing changes.
+    int select_depth = 1;
     // --seed-mismatches M: a round that seeds stage A (with --existing-primers, and rounds >= 1 of --repick-rounds)
     // seeds it on what the panel COVERS -- every segment of the direction in which a panel primer has a match within M
     // mismatches, its last seed_3p_exact bases exact (msspe_kmer_candidates_both_tolerant_packed_dev) -- instead of
@@ -345,6 +349,23 @@ struct SelectResult {
 };
 SelectResult select_panel(const std::vector<std::vector<uint64_t>> &rows, const std::vector<std::string> &primers,
                           const ConflictGraph &g, int max_tubes, int min_gain, const std::vector<char> &forced);
+// --select-depth R (engine extension): the layered rule of DESIGN.md 4.16 over the same rows and graph, n_seg segments
+// (bits of a row).  cnt[s] = kept primers that match s, from the forced rows on; layers r = 1 .. min(R, max(1, deepest
+// segment)): in layer r a segment is open while cnt < min(r, primers that match it), a round picks the live primer
+// matching the most open segments (ties: the lowest index) and counts it on every segment it matches, until that gain
+// is below min_gain; barring, picks and cnt carry over.  Layer 1 is select_panel.  The device's independent twin.
+struct SelectDepthResult {
+    std::vector<int> order, gains, layer;   // the picks in order, each with its gain and its layer
+    std::vector<char> keep;
+    std::vector<int> tube;
+    std::vector<char> barred;
+    std::vector<uint8_t> depth_all, depth_kept;   // saturating at 255
+    long long counts[4] = {0, 0, 0, 0};           // as ThinDepthResult's
+    int tubes_used = 0, rounds = 0, layers = 0;   // rounds: the picks and every layer's stopping round
+};
+SelectDepthResult select_panel_depth(const std::vector<std::vector<uint64_t>> &rows,
+                                     const std::vector<std::string> &primers, const ConflictGraph &g, size_t n_seg,
+                                     int depth, int max_tubes, int min_gain, const std::vector<char> &forced);
 // the same rule on the device for one round of the CLI: the round's primers (fwd / rev, stage B's survivors) and the
 // current panel (forced) are screened as one pool (msspe_cross_dimer_dev, bitmap only; screen false: no edges) and
 // selected by one msspe_panel_select_packed_dev.  The kept primers are appended to kept_f / kept_r in their lists'
@@ -358,14 +379,16 @@ std::string select_panel_on_device(Engine &eng, const DeviceAlignment &aln, cons
                                    bool screen, bool drop_self_pairs, float dg_threshold, std::vector<KmerStat> &kept_f,
                                    std::vector<KmerStat> &kept_r, std::map<std::string, int> &tubes,
                                    const std::function<void(const KmerStat &, bool)> &dropped,
-                                   const NtthalOptions *end_rule = nullptr);
+                                   const NtthalOptions *end_rule = nullptr, int depth = 1);
 // "Panel selection by coverage (<the match rule>, gain >= G, tubes <= T):", the rule line, the primers kept of those
 // offered (forced ones apart), the primers barred, the segments covered (mode 0) or held (modes 1, 2) by all of them
-// and by the kept ones, and with per_tube the primers per tube
+// and by the kept ones, and with per_tube the primers per tube; depth above 1 (--select-depth R): ", depth R" closes
+// the first line's bracket and thin_report's "Depth:" line follows "Segments:" (deep_all = u, deep_kept = v)
 std::string select_report(int mode, float tm_threshold, int max_mismatches, int exact_3p, int min_gain, int max_tubes,
                           size_t kept_f, size_t n_f, size_t kept_r, size_t n_r, size_t forced, size_t barred,
                           size_t covered_all, size_t covered_kept, size_t segments,
-                          const std::vector<size_t> *per_tube);
+                          const std::vector<size_t> *per_tube, int depth = 1, size_t deep_all = 0,
+                          size_t deep_kept = 0);
 // the same rule as one msspe_panel_thin_packed_dev call on the resident alignment: fwd / rev are thinned in place,
 // the panel's primers are forced; returns the report's block
 std::string thin_panel_on_device(Engine &eng, const DeviceAlignment &aln, std::vector<KmerStat> &fwd,

@@ -46,6 +46,8 @@ EXPORTS = [
     "msspe_panel_thin_thal_depth", "msspe_panel_thin_thal_depth_dev", "msspe_panel_thin_thal_depth_packed_dev",
     "msspe_panel_select", "msspe_panel_select_bitmap", "msspe_panel_select_dev", "msspe_panel_select_packed_dev",
     "msspe_panel_select_rule",
+    "msspe_panel_select_depth", "msspe_panel_select_depth_bitmap", "msspe_panel_select_depth_dev",
+    "msspe_panel_select_depth_packed_dev", "msspe_panel_select_depth_rule",
     "msspe_device_put_stream_packed", "msspe_background_sites_packed_dev", "msspe_background_sites",
     "msspe_background_thal_packed_dev", "msspe_background_thal",
     "msspe_background_amplicons_packed_dev", "msspe_background_amplicons",
@@ -149,6 +151,12 @@ class ThinDepthOpt(C.Structure):
 class SelectOpt(C.Structure):
     """msspe_select_opt: min_gain as ThinOpt, at most max_tubes (1..64) tubes, drop_self_pairs as the cover's."""
     _fields_ = [("min_gain", C.c_int), ("max_tubes", C.c_int), ("drop_self_pairs", C.c_int)]
+
+
+class SelectDepthOpt(C.Structure):
+    """msspe_select_depth_opt: SelectOpt's fields, then depth (1..255): layer r adds primers for the segments that
+    still have fewer than r."""
+    _fields_ = [("min_gain", C.c_int), ("max_tubes", C.c_int), ("drop_self_pairs", C.c_int), ("depth", C.c_int)]
 
 
 def lib_path() -> Path:
@@ -351,6 +359,15 @@ def load_library() -> C.CDLL:
     L.msspe_panel_select_bitmap.argtypes = select_in + [vp] + select_out
     L.msspe_panel_select.argtypes = select_in + [C.POINTER(Chem), C.c_float] + select_out
     L.msspe_panel_select_rule.argtypes = select_in + [C.POINTER(Chem), rulep] + select_out
+    # the selection's inputs with SelectDepthOpt | graph | keep, order, gain, n_picked, tube, barred, n_tubes_used,
+    # pick_layer, depth_all, depth_kept, counts
+    depth_in = select_in[:6] + [C.POINTER(SelectDepthOpt)] + select_in[7:]
+    depth_out = [vp, vp, vp, C.POINTER(C.c_int), vp, vp, C.POINTER(C.c_int), vp, vp, vp, C.POINTER(C.c_longlong)]
+    L.msspe_panel_select_depth_dev.argtypes = depth_in + [vp] + depth_out
+    L.msspe_panel_select_depth_packed_dev.argtypes = depth_in + [vp] + depth_out
+    L.msspe_panel_select_depth_bitmap.argtypes = depth_in + [vp] + depth_out
+    L.msspe_panel_select_depth.argtypes = depth_in + [C.POINTER(Chem), C.c_float] + depth_out
+    L.msspe_panel_select_depth_rule.argtypes = depth_in + [C.POINTER(Chem), rulep] + depth_out
     L.msspe_device_put_stream_packed.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int,
                                                  C.POINTER(vp), C.POINTER(C.c_size_t), vp]
     L.msspe_background_sites_packed_dev.argtypes = [vp, vp, C.c_size_t, C.c_int, C.POINTER(MismatchOpt), u64p, C.c_int,
@@ -1302,6 +1319,12 @@ class Engine:
         (default Chem.ntthal()) and `threshold`, with end_tm_threshold under the rule (ANY at threshold, END at
         end_tm_threshold; msspe_panel_select_rule).  Returns a dict: keep, order, gains, tube, barred (uint8[n]), covered
         (n_seq, P), covered_all, covered_kept, tubes_used."""
+        return self._panel_select(None, genomes, opt, fwd, rev, rule, bitmap, max_tubes, min_gain, drop_self_pairs,
+                                  forced, form, chem, threshold, end_tm_threshold)
+
+    def _panel_select(self, _depth, genomes, opt, fwd, rev, rule, bitmap, max_tubes, min_gain, drop_self_pairs, forced,
+                      form, chem, threshold, end_tm_threshold):
+        """panel_select (_depth None) and panel_select_depth: the same inputs, the calls' own outputs."""
         if form not in ("bitmap", "dev", "packed", "screen"):
             raise ValueError("form must be 'bitmap', 'dev', 'packed' or 'screen'")
         f, r = _words(fwd), _words(rev)
@@ -1350,6 +1373,8 @@ class Engine:
                   "packed": self.L.msspe_panel_select_packed_dev, "screen": self.L.msspe_panel_select}[form]
             if form == "screen" and end_tm_threshold is not None:
                 fn = self.L.msspe_panel_select_rule
+            if _depth is not None:
+                fn = getattr(self.L, fn.__name__.replace("msspe_panel_select", "msspe_panel_select_depth"))
             P = 0 if seq_len < opt.segment_size else (seq_len - opt.segment_size) // opt.overlap_size + 1
             flags = None if forced is None else np.ascontiguousarray(np.asarray(forced) != 0, dtype=np.uint8)
             if flags is not None and flags.shape != (n,):
@@ -1361,6 +1386,22 @@ class Engine:
             barred = np.zeros(max(n, 1), dtype=np.uint8)
             covered = np.zeros((n_seq, P), dtype=np.uint8)
             n_picked, used, c_all, c_kept = C.c_int(0), C.c_int(0), C.c_longlong(0), C.c_longlong(0)
+            if _depth is not None:
+                layer = np.zeros(max(n, 1), dtype=np.uint8)
+                depth_all = np.zeros((n_seq, P), dtype=np.uint8)
+                depth_kept = np.zeros((n_seq, P), dtype=np.uint8)
+                counts = (C.c_longlong * 4)()
+                dsel = SelectDepthOpt(min_gain, max_tubes, 1 if drop_self_pairs else 0, _depth)
+                self._check(fn(self.ptr, seqs_arg, n_seq, seq_len, C.byref(opt), C.byref(rule), C.byref(dsel),
+                               f.ctypes.data, len(f), r.ctypes.data, len(r),
+                               flags.ctypes.data if flags is not None else None, *graph, keep.ctypes.data,
+                               order.ctypes.data, gains.ctypes.data, C.byref(n_picked), tube.ctypes.data,
+                               barred.ctypes.data, C.byref(used), layer.ctypes.data, depth_all.ctypes.data,
+                               depth_kept.ctypes.data, counts))
+                return {"keep": keep, "order": order[:n_picked.value].copy(), "gains": gains[:n_picked.value].copy(),
+                        "layer": layer[:n_picked.value].copy(), "tube": tube[:n].copy(), "barred": barred[:n].copy(),
+                        "depth_all": depth_all, "depth_kept": depth_kept,
+                        "counts": np.array(list(counts), dtype=np.int64), "tubes_used": int(used.value)}
             sel = SelectOpt(min_gain, max_tubes, 1 if drop_self_pairs else 0)
             self._check(fn(self.ptr, seqs_arg, n_seq, seq_len, C.byref(opt), C.byref(rule), C.byref(sel),
                            f.ctypes.data, len(f), r.ctypes.data, len(r),
@@ -1373,6 +1414,18 @@ class Engine:
         return {"keep": keep, "order": order[:n_picked.value].copy(), "gains": gains[:n_picked.value].copy(),
                 "tube": tube[:n].copy(), "barred": barred[:n].copy(), "covered": covered,
                 "covered_all": int(c_all.value), "covered_kept": int(c_kept.value), "tubes_used": int(used.value)}
+
+    def panel_select_depth(self, genomes, opt: KmerOpt, fwd, rev, rule: SeedRule, depth: int, bitmap=None,
+                           max_tubes: int = 1, min_gain: int = 1, drop_self_pairs: bool = False, forced=None,
+                           form: str = "bitmap", chem: Chem | None = None, threshold: float = -9000.0,
+                           end_tm_threshold: float | None = None):
+        """The selection to a coverage depth, layer by layer (msspe_panel_select_depth*): layer 1 is panel_select,
+        layer r then adds primers for the segments that still have fewer than r, with the barring carried along.
+        Arguments and forms as panel_select, plus depth (1..255).  Returns a dict: keep, order, gains, layer (the layer
+        of every pick), tube, barred, depth_all, depth_kept (uint8 (n_seq, P), saturating at 255), counts (int64[4]:
+        segments with depth_all >= 1, depth_kept >= 1, depth_all >= depth, depth_kept >= depth), tubes_used."""
+        return self._panel_select(int(depth), genomes, opt, fwd, rev, rule, bitmap, max_tubes, min_gain,
+                                  drop_self_pairs, forced, form, chem, threshold, end_tm_threshold)
 
     # ---- off-target sites in a background ------------------------------------------------------
     @staticmethod
