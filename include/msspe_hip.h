@@ -594,6 +594,14 @@ int msspe_host_table_routes(const char *params_path, const msspe_chem *chem, int
  * *n_out = launches; more than capacity: MSSPE_ERR_CAPACITY, nothing written. */
 int msspe_host_screen_plan(int first_stage, int row0, int row1, int col0, int ncols, int64_t list_cap, int64_t *out,
                            int capacity, int *n_out);
+/* Host only: how the thal-scored site passes (msspe_background_thal*, msspe_segment_coverage_thal*,
+ * msspe_panel_thin_thal* and what runs through them) cut a slab -- outer range [o0, o1) (runs, or segment groups)
+ * against primers [p0, p1) -- whose `count` matches overran a work list of `cap` (count > cap; csrc/slab_split.hpp, the
+ * passes execute this very rule).  out[i] = o0, o1, p0, p1 of part i, in the order the parts are pushed (the last is
+ * listed first).  *n_out = parts; 0: one outer element against one primer cannot be split.  More than capacity:
+ * MSSPE_ERR_CAPACITY, nothing written.  An outer range of more than 2^31 - 1 elements: MSSPE_ERR_ARG. */
+int msspe_host_slab_split(int64_t o0, int64_t o1, int p0, int p1, uint64_t count, uint64_t cap, int64_t *out,
+                          int capacity, int *n_out);
 /* Host only: the bound first stage's tables (option "pair_bound"; csrc/fast_tables.hpp BoundTables) in the layout
  * of msspe_host_pair_tables' int_g (2604 entries) and int_T (239 * 64): every term's H - temp_k * S, a stacked pair
  * and a loop with - temp_k * salt on top, in units of 1 / info[3] cal/mol rounded down; entries >= info[6] are "not

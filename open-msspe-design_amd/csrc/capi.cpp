@@ -38,6 +38,7 @@
 #include "panel_thin.hpp"
 #include "panel_thin_thal.hpp"
 #include "screen_plan.hpp"
+#include "slab_split.hpp"
 #include "tube_split.hpp"
 
 using namespace msspe;
@@ -3263,6 +3264,11 @@ int msspe_background_sites(msspe_ctx *ctx, const char *const *records, const siz
 
 namespace {
 
+// The work list of the thal-scored site passes holds 2^site_list_cap_log2 sites; a pair's column is n + site index in
+// 31 bits, which bounds the primers such a pass takes.
+size_t site_list_cap(const msspe_ctx *ctx) { return (size_t)1 << ctx->opt.site_list_cap_log2; }
+bool site_pool_fits(const msspe_ctx *ctx, int n) { return (uint64_t)n + site_list_cap(ctx) < (1ull << 31); }
+
 int ensure_site_work(msspe_ctx *ctx, size_t cap, int n, int flank)
 {
     auto &w = ctx->site_work;
@@ -3343,6 +3349,105 @@ int score_site_pairs(msspe_ctx *ctx, ChemEntry *ce, bool end1, int n, int k, int
     return ListChain(ctx, ce, end1, list, (long)count).run(route, a, g, false);
 }
 
+// Before the first slab of a thal-scored site pass: the chemistry's entry at the threshold (END1 or ANY), the DP
+// workspace for k-base primers on templates of k + 2 * flank bases, hand-over lists of the work list's size and the
+// work list for n primers (n < 0: none -- a tolerant call makes it per direction, under the mutex).
+int site_scoring_begin(msspe_ctx *ctx, const msspe_chem &chem, float tm_threshold, bool end1, int k, int flank, int n,
+                       ChemEntry **ce_out)
+{
+    int rc;
+    if ((rc = chem_entry(ctx, chem, tm_threshold, ce_out, end1 ? kCutEndT : kCutAnyT)) ||
+        (rc = ensure_workspace(ctx, (size_t)k * (size_t)(k + 2 * flank))) ||
+        (rc = ensure_overflow(ctx, (long)site_list_cap(ctx))))
+        return rc;
+    return n < 0 ? MSSPE_OK : ensure_site_work(ctx, site_list_cap(ctx), n, flank);
+}
+
+// The pool "forward words then reverse words" at the head of the work list's pool, where the pairs' rows point, and
+// the hand-over counters zeroed.
+int upload_site_pool(msspe_ctx *ctx, const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev)
+{
+    auto &w = ctx->site_work;
+    if (n_fwd)
+        HIP_TRY(ctx, hipMemcpyAsync(w.pool, fwd_words, sizeof(uint64_t) * (size_t)n_fwd, hipMemcpyHostToDevice,
+                                    ctx->stream));
+    if (n_rev)
+        HIP_TRY(ctx, hipMemcpyAsync(w.pool + n_fwd, rev_words, sizeof(uint64_t) * (size_t)n_rev,
+                                    hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->ovf_count, 0, 8 * sizeof(uint32_t), ctx->stream));
+    return MSSPE_OK;
+}
+
+extern "C++" {   // (a std::string and templates, within this file's extern "C" block)
+
+std::string site_list_overrun(const char *pass, uint64_t count, size_t cap)
+{
+    return std::string(pass) + ": one segment group against one primer has " + std::to_string(count) +
+           " matches, the work list holds " + std::to_string(cap) + " (msspe_set_option \"site_list_cap_log2\")";
+}
+
+// Behind a synchronisation of a pass that times its phases (st: CoverageThal or PanelThinThal; the last three events
+// stand before a slab's scores, after them and after its fold): the listing just made, if one was, and the scores and
+// the fold of the slab before it, if `scored` says that they wait to be read.
+template <class Stats>
+void read_slab_times(Stats &st, bool listed, bool &scored)
+{
+    const int b = (int)(sizeof st.ev / sizeof st.ev[0]) - 3;
+    float l = 0.f, a = 0.f, f = 0.f;
+    if (scored && hipEventElapsedTime(&a, st.ev[b], st.ev[b + 1]) == hipSuccess &&
+        hipEventElapsedTime(&f, st.ev[b + 1], st.ev[b + 2]) == hipSuccess) {
+        st.score_us += (long long)(a * 1000.f);
+        st.fold_us += (long long)(f * 1000.f);
+    }
+    scored = false;
+    if (listed && hipEventElapsedTime(&l, st.ev[0], st.ev[1]) == hipSuccess) st.list_us += (long long)(l * 1000.f);
+}
+
+// The slab loop of every thal-scored site pass.  A slab, taken from the back of `todo`, is listed into the work list
+// and its count read back; one that overran the list is split (slab_split.hpp) and its parts, pushed ascending, are
+// listed again; only a slab that fitted is counted, scored in steps of the hand-over lists' size, and folded.
+//   list(s): lists slab s, counting into site_work.slab_count, and whatever else the pass reads back with the count
+//   synced(): behind the synchronisation that brought the count (the one the loop makes per listed slab)
+//   prepare(s, count, n_pairs): before the steps of a slab of `count` matches; n_pairs, preset to count: pairs to score
+//   score(c0, cnt): cuts and scores pairs [c0, c0 + cnt);  fold(s, count): folds the slab's scores
+//   cannot_split(count): the pass's failure when one outer element against one primer overran the list
+template <class List, class Synced, class Prepare, class Score, class Fold, class CannotSplit>
+int run_slabs(msspe_ctx *ctx, std::vector<Slab> todo, long long &slabs, long long &redone, long long *matches,
+              List list, Synced synced, Prepare prepare, Score score, Fold fold, CannotSplit cannot_split)
+{
+    auto &w = ctx->site_work;
+    const uint64_t cap = site_list_cap(ctx);
+    int rc;
+    while (!todo.empty()) {
+        const Slab s = todo.back();
+        todo.pop_back();
+        HIP_TRY(ctx, hipMemsetAsync(w.slab_count, 0, sizeof(uint64_t), ctx->stream));
+        if ((rc = list(s))) return rc;
+        uint64_t count = 0;
+        HIP_TRY(ctx, hipMemcpyAsync(&count, w.slab_count, sizeof count, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        synced();
+        if (count > cap) {
+            ++redone;
+            if (!split_slab(s, count, cap, todo)) return cannot_split(count);
+            continue;
+        }
+        if (!count) continue;
+        ++slabs;
+        if (matches) *matches += (long long)count;
+        uint32_t n_pairs = (uint32_t)count;
+        if ((rc = prepare(s, count, n_pairs))) return rc;
+        // the hand-over lists may be shorter than the work list (a fixed list_cap_log2, a card short of memory)
+        const uint32_t step = (uint32_t)std::min<uint64_t>(n_pairs, (uint64_t)ctx->list_cap);
+        for (uint32_t c0 = 0; c0 < n_pairs; c0 += step)
+            if ((rc = score(c0, std::min(step, n_pairs - c0)))) return rc;
+        if ((rc = fold(s, count))) return rc;
+    }
+    return MSSPE_OK;
+}
+
+}  // extern "C++"
+
 // Room for `need` stable keys: the buffer doubles from 2^amplicon_keys_cap_log2 until it holds them, and the `have`
 // keys written so far move over, device to device.
 int ensure_amplicon_keys(msspe_ctx *ctx, uint64_t have, uint64_t need)
@@ -3394,8 +3499,7 @@ int background_thal_pass(msspe_ctx *ctx, const uint64_t *d_packed, size_t total_
     std::string err;
     int rc = BackgroundSites::check(total_len, k, mm->max_mismatches, mm->exact_3p, words, n, err);
     if (rc) return fail(ctx, rc, err);
-    const size_t cap = (size_t)1 << ctx->opt.site_list_cap_log2;
-    if ((uint64_t)n + cap >= (1ull << 31)) return fail(ctx, MSSPE_ERR_ARG, "background_thal: too many primers");
+    if (!site_pool_fits(ctx, n)) return fail(ctx, MSSPE_ERR_ARG, "background_thal: too many primers");
     std::fill(sites_out, sites_out + 2 * (size_t)n, (uint64_t)0);
     std::fill(stable_out, stable_out + 2 * (size_t)n, (uint64_t)0);
     auto &w = ctx->site_work;
@@ -3414,103 +3518,79 @@ int background_thal_pass(msspe_ctx *ctx, const uint64_t *d_packed, size_t total_
     uint64_t n_keys = 0;   // stable keys of the slabs folded so far
     const bool end1 = mode == 2;
     ChemEntry *ce = nullptr;
-    if ((rc = chem_entry(ctx, *chem, tm_threshold, &ce, end1 ? kCutEndT : kCutAnyT))) return rc;
+    if ((rc = site_scoring_begin(ctx, *chem, tm_threshold, end1, k, flank, n, &ce))) return rc;
     const double cut = ce->c[0].g_cut;
-    if ((rc = ensure_workspace(ctx, (size_t)k * (size_t)(k + 2 * flank)))) return rc;
-    if ((rc = ensure_overflow(ctx, (long)cap))) return rc;
-    if ((rc = ensure_site_work(ctx, cap, n, flank))) return rc;
+    const size_t cap = site_list_cap(ctx);
     if ((rc = ctx->background.prepare(k, words, n, ctx->stream, err))) return fail(ctx, rc, err);
-    HIP_TRY(ctx, hipMemcpyAsync(w.pool, words, sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = upload_site_pool(ctx, words, n, nullptr, 0))) return rc;
     HIP_TRY(ctx, hipMemsetAsync(w.counts, 0, sizeof(uint64_t) * 4 * (size_t)n, ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->ovf_count, 0, 8 * sizeof(uint32_t), ctx->stream));
 
     // Slabs (runs [r0, r1) x primers [p0, p1)), the whole stream first: a slab whose sites do not fit the work list
     // is split -- into as many parts as its count says, by runs while it has several, then by primers -- and its
-    // parts are listed again; only a slab that fitted is scored and counted.
-    struct Slab { uint32_t r0, r1; int p0, p1; };
-    std::vector<Slab> todo{{0u, BackgroundSites::n_runs(total_len, k), 0, n}};
-    while (!todo.empty()) {
-        const Slab s = todo.back();
-        todo.pop_back();
-        HIP_TRY(ctx, hipMemsetAsync(w.slab_count, 0, sizeof(uint64_t), ctx->stream));
+    // parts are listed again; only a slab that fitted is scored and counted (run_slabs).
+    auto list = [&](const Slab &s) -> int {
         if ((rc = ctx->background.list_slab(d_packed, total_len, k, mm->max_mismatches, mm->exact_3p, s.p0, s.p1,
-                                            s.r0, s.r1, w.sites, cap, w.slab_count, ctx->n_cu, ctx->stream, err)))
+                                            (uint32_t)s.o0, (uint32_t)s.o1, w.sites, cap, w.slab_count, ctx->n_cu,
+                                            ctx->stream, err)))
             return fail(ctx, rc, err);
-        uint64_t count = 0;
-        HIP_TRY(ctx, hipMemcpyAsync(&count, w.slab_count, sizeof count, hipMemcpyDeviceToHost, ctx->stream));
         if (keys)   // behind the last fold in stream order: exact
             HIP_TRY(ctx, hipMemcpyAsync(&n_keys, aw.key_count, sizeof n_keys, hipMemcpyDeviceToHost, ctx->stream));
+        return MSSPE_OK;
+    };
+    auto score = [&](uint32_t c0, uint32_t cnt) -> int {
+        if (!flank) {
+            HIP_TRY(ctx, launch_site_oligos(d_packed, total_len, k, w.sites, c0, cnt, n, w.pool, w.list + c0,
+                                            ctx->ovf_count, ctx->stream));
+            classes_seen |= 1u;
+            return score_site_pairs(ctx, ce, end1, n, k, k, w.list + c0, cnt);
+        }
+        uint32_t per_class[kSiteClasses];
+        HIP_TRY(ctx, hipMemsetAsync(w.class_counts, 0, sizeof(uint32_t) * 2 * kSiteClasses, ctx->stream));
+        HIP_TRY(ctx, launch_site_oligos_flank(d_packed, total_len, k, flank, w.sites, c0, cnt, n, w.pool, w.cls,
+                                              w.class_counts, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(per_class, w.class_counts, sizeof per_class, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (count > cap) {
-            ++w.redone;
-            const uint64_t runs = s.r1 - s.r0, prim = (uint64_t)(s.p1 - s.p0);
-            const uint64_t want = (2 * count + cap - 1) / cap;   // parts that would be half full at this density
-            if (runs > 1) {
-                const uint64_t parts = std::min(runs, want);
-                for (uint64_t q = 0; q < parts; ++q)
-                    todo.push_back({s.r0 + (uint32_t)(runs * q / parts), s.r0 + (uint32_t)(runs * (q + 1) / parts),
-                                    s.p0, s.p1});
-            } else if (prim > 1) {
-                const uint64_t parts = std::min(prim, want);
-                for (uint64_t q = 0; q < parts; ++q)
-                    todo.push_back({s.r0, s.r1, s.p0 + (int)(prim * q / parts), s.p0 + (int)(prim * (q + 1) / parts)});
-            } else {
-                return fail(ctx, MSSPE_ERR_DEVICE, "background_thal: one run against one primer overran the work list");
-            }
-            continue;
+        const int n_classes = (flank + 1) * (flank + 1);
+        SiteClassOffsets off;
+        std::memset(&off, 0, sizeof off);
+        uint32_t at = 0;
+        for (int c = 0; c < n_classes; ++c) {
+            off.at[c] = at;
+            at += per_class[c];
         }
-        if (!count) continue;
-        ++w.slabs;
-        // the hand-over lists may be shorter than the work list (a fixed list_cap_log2, a card short of memory)
-        const uint32_t step = (uint32_t)std::min<uint64_t>(count, (uint64_t)ctx->list_cap);
-        for (uint32_t c0 = 0; c0 < (uint32_t)count; c0 += step) {
-            const uint32_t cnt = std::min(step, (uint32_t)count - c0);
-            if (!flank) {
-                HIP_TRY(ctx, launch_site_oligos(d_packed, total_len, k, w.sites, c0, cnt, n, w.pool, w.list + c0,
-                                                ctx->ovf_count, ctx->stream));
-                if ((rc = score_site_pairs(ctx, ce, end1, n, k, k, w.list + c0, cnt))) return rc;
-                classes_seen |= 1u;
-                continue;
-            }
-            uint32_t per_class[kSiteClasses];
-            HIP_TRY(ctx, hipMemsetAsync(w.class_counts, 0, sizeof(uint32_t) * 2 * kSiteClasses, ctx->stream));
-            HIP_TRY(ctx, launch_site_oligos_flank(d_packed, total_len, k, flank, w.sites, c0, cnt, n, w.pool, w.cls,
-                                                  w.class_counts, ctx->stream));
-            HIP_TRY(ctx, hipMemcpyAsync(per_class, w.class_counts, sizeof per_class, hipMemcpyDeviceToHost,
+        if (at != cnt) return fail(ctx, MSSPE_ERR_DEVICE, "background_thal: the flank classes do not add up");
+        HIP_TRY(ctx, launch_site_group(w.sites, c0, cnt, n, w.cls, off, w.class_counts + kSiteClasses, w.list + c0,
+                                       ctx->stream));
+        for (int c = 0; c < n_classes; ++c) {
+            if (!per_class[c]) continue;
+            const int fl = c / (flank + 1), fr = c % (flank + 1);
+            classes_seen |= 1u << c;
+            if (fl < flank || fr < flank) w.truncated += per_class[c];
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->ovf_count, w.class_counts + c, sizeof(uint32_t), hipMemcpyDeviceToDevice,
                                         ctx->stream));
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            const int n_classes = (flank + 1) * (flank + 1);
-            SiteClassOffsets off;
-            std::memset(&off, 0, sizeof off);
-            uint32_t at = 0;
-            for (int c = 0; c < n_classes; ++c) {
-                off.at[c] = at;
-                at += per_class[c];
-            }
-            if (at != cnt) return fail(ctx, MSSPE_ERR_DEVICE, "background_thal: the flank classes do not add up");
-            HIP_TRY(ctx, launch_site_group(w.sites, c0, cnt, n, w.cls, off, w.class_counts + kSiteClasses,
-                                           w.list + c0, ctx->stream));
-            for (int c = 0; c < n_classes; ++c) {
-                if (!per_class[c]) continue;
-                const int fl = c / (flank + 1), fr = c % (flank + 1);
-                classes_seen |= 1u << c;
-                if (fl < flank || fr < flank) w.truncated += per_class[c];
-                HIP_TRY(ctx, hipMemcpyAsync(ctx->ovf_count, w.class_counts + c, sizeof(uint32_t),
-                                            hipMemcpyDeviceToDevice, ctx->stream));
-                if ((rc = score_site_pairs(ctx, ce, end1, n, k, k + fl + fr, w.list + c0 + off.at[c], per_class[c])))
-                    return rc;
-            }
+            if ((rc = score_site_pairs(ctx, ce, end1, n, k, k + fl + fr, w.list + c0 + off.at[c], per_class[c])))
+                return rc;
         }
+        return MSSPE_OK;
+    };
+    auto fold = [&](const Slab &, uint64_t count) -> int {
         if (!keys) {
             HIP_TRY(ctx, launch_site_fold(w.sites, (uint32_t)count, w.dg, w.t, cut, n, w.counts, d_sites, capacity,
                                           d_sites ? d_count : nullptr, ctx->stream));
-        } else {
-            if ((rc = ensure_amplicon_keys(ctx, n_keys, n_keys + count))) return rc;
-            HIP_TRY(ctx, launch_site_fold_keys(w.sites, (uint32_t)count, w.dg, w.t, cut, n, w.counts, d_sites,
-                                               capacity, d_sites ? d_count : nullptr, aw.keys, aw.keys_cap,
-                                               aw.key_count, ctx->stream));
+            return MSSPE_OK;
         }
-    }
+        if ((rc = ensure_amplicon_keys(ctx, n_keys, n_keys + count))) return rc;
+        HIP_TRY(ctx, launch_site_fold_keys(w.sites, (uint32_t)count, w.dg, w.t, cut, n, w.counts, d_sites, capacity,
+                                           d_sites ? d_count : nullptr, aw.keys, aw.keys_cap, aw.key_count,
+                                           ctx->stream));
+        return MSSPE_OK;
+    };
+    auto cannot_split = [&](uint64_t) {
+        return fail(ctx, MSSPE_ERR_DEVICE, "background_thal: one run against one primer overran the work list");
+    };
+    if ((rc = run_slabs(ctx, {{0, (long)BackgroundSites::n_runs(total_len, k), 0, n}}, w.slabs, w.redone, nullptr, list,
+                        [] {}, [](const Slab &, uint64_t, uint32_t &) { return MSSPE_OK; }, score, fold, cannot_split)))
+        return rc;
     std::vector<uint64_t> host(4 * (size_t)n);
     HIP_TRY(ctx, hipMemcpyAsync(host.data(), w.counts, sizeof(uint64_t) * host.size(), hipMemcpyDeviceToHost,
                                 ctx->stream));
@@ -3525,7 +3605,7 @@ int background_thal_pass(msspe_ctx *ctx, const uint64_t *d_packed, size_t total_
 
 // msspe_segment_coverage_thal*: the matches of the mm rule through the work list of msspe_background_thal*, slab by
 // slab (groups [g0, g1) x primers [p0, p1)); a slab that overruns the list is split -- by groups while it has several,
-// then by primers -- and listed again, and only a slab that fitted is scored and folded.
+// then by primers -- and listed again, and only a slab that fitted is scored and folded (run_slabs).
 int coverage_thal_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t seq_len, const msspe_kmer_opt *opt,
                        const msspe_mismatch_opt *mm, const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words,
                        int n_rev, const msspe_chem *chem, int mode, float tm_threshold, uint8_t *held_out,
@@ -3556,103 +3636,62 @@ int coverage_thal_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t se
     ct.matches = ct.slabs = ct.redone = 0;
     ct.list_us = ct.score_us = ct.fold_us = 0;
     if (n == 0 || n_seg == 0) return MSSPE_OK;
-    const size_t cap = (size_t)1 << ctx->opt.site_list_cap_log2;
-    if ((uint64_t)n + cap >= (1ull << 31)) return fail(ctx, MSSPE_ERR_ARG, "coverage_thal: too many primers");
+    if (!site_pool_fits(ctx, n)) return fail(ctx, MSSPE_ERR_ARG, "coverage_thal: too many primers");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const bool end1 = mode == 2;
     ChemEntry *ce = nullptr;
-    if ((rc = chem_entry(ctx, *chem, tm_threshold, &ce, end1 ? kCutEndT : kCutAnyT))) return rc;
+    if ((rc = site_scoring_begin(ctx, *chem, tm_threshold, end1, k, 0, n, &ce))) return rc;
     const double cut = ce->c[0].g_cut;
-    if ((rc = ensure_workspace(ctx, (size_t)k * (size_t)k))) return rc;
-    if ((rc = ensure_overflow(ctx, (long)cap))) return rc;
-    if ((rc = ensure_site_work(ctx, cap, n, 0))) return rc;
+    const size_t cap = site_list_cap(ctx);
     if ((rc = ct.prepare(*opt, fwd_words, n_fwd, rev_words, n_rev, n_seg, ctx->stream, err))) return fail(ctx, rc, err);
     auto &w = ctx->site_work;
     CovMatch *list = reinterpret_cast<CovMatch *>(w.sites);
-    if (n_fwd)
-        HIP_TRY(ctx, hipMemcpyAsync(w.pool, fwd_words, sizeof(uint64_t) * (size_t)n_fwd, hipMemcpyHostToDevice,
-                                    ctx->stream));
-    if (n_rev)
-        HIP_TRY(ctx, hipMemcpyAsync(w.pool + n_fwd, rev_words, sizeof(uint64_t) * (size_t)n_rev,
-                                    hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->ovf_count, 0, 8 * sizeof(uint32_t), ctx->stream));
+    if ((rc = upload_site_pool(ctx, fwd_words, n_fwd, rev_words, n_rev))) return rc;
     msspe_scored_match *d_out = nullptr;
     uint64_t *d_count = nullptr;
     if (matches && (rc = ct.out_list(capacity, &d_out, &d_count, ctx->stream, err))) return fail(ctx, rc, err);
 
     const int S = MismatchCoverage::group_size(*opt);
     const long n_groups = (n_seg + S - 1) / S, chunk = CoverageThal::max_slab_groups(n);
-    struct Slab { long g0, g1; int p0, p1; };
     std::vector<Slab> todo;
     for (long g1 = n_groups; g1 > 0; g1 -= std::min(g1, chunk))   // popped from the back: ascending groups
         todo.push_back({g1 - std::min(g1, chunk), g1, 0, n});
     bool scored = false;   // ev[2..4] of a scored slab wait to be read behind the next synchronisation
-    auto read_scored = [&]() {
-        float a = 0.f, b = 0.f;
-        if (scored && hipEventElapsedTime(&a, ct.ev[2], ct.ev[3]) == hipSuccess &&
-            hipEventElapsedTime(&b, ct.ev[3], ct.ev[4]) == hipSuccess) {
-            ct.score_us += (long long)(a * 1000.f);
-            ct.fold_us += (long long)(b * 1000.f);
-        }
-        scored = false;
-    };
-    while (!todo.empty()) {
-        const Slab s = todo.back();
-        todo.pop_back();
-        HIP_TRY(ctx, hipMemsetAsync(w.slab_count, 0, sizeof(uint64_t), ctx->stream));
+    auto list_slab = [&](const Slab &s) -> int {
         HIP_TRY(ctx, hipEventRecord(ct.ev[0], ctx->stream));
-        if ((rc = ct.list_slab(view, n_seg, P, *opt, mm->max_mismatches, mm->exact_3p, s.g0, s.g1, s.p0, s.p1, list,
+        if ((rc = ct.list_slab(view, n_seg, P, *opt, mm->max_mismatches, mm->exact_3p, s.o0, s.o1, s.p0, s.p1, list,
                                cap, w.slab_count, ctx->stream, err)))
             return fail(ctx, rc, err);
         HIP_TRY(ctx, hipEventRecord(ct.ev[1], ctx->stream));
-        uint64_t count = 0;
-        HIP_TRY(ctx, hipMemcpyAsync(&count, w.slab_count, sizeof count, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        read_scored();
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, ct.ev[0], ct.ev[1]) == hipSuccess) ct.list_us += (long long)(ms * 1000.f);
-        if (count > cap) {
-            ++ct.redone;
-            const uint64_t groups = (uint64_t)(s.g1 - s.g0), prim = (uint64_t)(s.p1 - s.p0);
-            const uint64_t want = (2 * count + cap - 1) / cap;   // parts that would be half full at this density
-            if (groups > 1) {
-                const uint64_t parts = std::min(groups, want);
-                for (uint64_t q = 0; q < parts; ++q)
-                    todo.push_back({s.g0 + (long)(groups * q / parts), s.g0 + (long)(groups * (q + 1) / parts), s.p0,
-                                    s.p1});
-            } else if (prim > 1) {
-                const uint64_t parts = std::min(prim, want);
-                for (uint64_t q = 0; q < parts; ++q)
-                    todo.push_back({s.g0, s.g1, s.p0 + (int)(prim * q / parts), s.p0 + (int)(prim * (q + 1) / parts)});
-            } else {
-                return fail(ctx, MSSPE_ERR_CAPACITY,
-                            "coverage_thal: one segment group against one primer has " + std::to_string(count) +
-                                " matches, the work list holds " + std::to_string(cap) +
-                                " (msspe_set_option \"site_list_cap_log2\")");
-            }
-            continue;
-        }
-        if (!count) continue;
-        ++ct.slabs;
-        ct.matches += (long long)count;
+        return MSSPE_OK;
+    };
+    auto synced = [&] { read_slab_times(ct, true, scored); };
+    auto prepare = [&](const Slab &, uint64_t, uint32_t &) -> int {
         HIP_TRY(ctx, hipEventRecord(ct.ev[2], ctx->stream));
-        // the hand-over lists may be shorter than the work list (a fixed list_cap_log2, a card short of memory)
-        const uint32_t step = (uint32_t)std::min<uint64_t>(count, (uint64_t)ctx->list_cap);
-        for (uint32_t c0 = 0; c0 < (uint32_t)count; c0 += step) {
-            const uint32_t cnt = std::min(step, (uint32_t)count - c0);
-            HIP_TRY(ctx, ct.oligos(view, P, *opt, list, c0, cnt, w.pool, w.list + c0, ctx->ovf_count, ctx->stream));
-            if ((rc = score_site_pairs(ctx, ce, end1, n, k, k, w.list + c0, cnt))) return rc;
-        }
+        return MSSPE_OK;
+    };
+    auto score = [&](uint32_t c0, uint32_t cnt) -> int {
+        HIP_TRY(ctx, ct.oligos(view, P, *opt, list, c0, cnt, w.pool, w.list + c0, ctx->ovf_count, ctx->stream));
+        return score_site_pairs(ctx, ce, end1, n, k, k, w.list + c0, cnt);
+    };
+    auto fold = [&](const Slab &s, uint64_t count) -> int {
         HIP_TRY(ctx, hipEventRecord(ct.ev[3], ctx->stream));
-        if ((rc = ct.fold_slab(list, (uint32_t)count, w.dg, w.t, cut, *opt, s.g0, s.g1, s.p0, s.p1, d_out, capacity,
+        if ((rc = ct.fold_slab(list, (uint32_t)count, w.dg, w.t, cut, *opt, s.o0, s.o1, s.p0, s.p1, d_out, capacity,
                                d_count, ctx->stream, err)))
             return fail(ctx, rc, err);
         HIP_TRY(ctx, hipEventRecord(ct.ev[4], ctx->stream));
         scored = true;
-    }
+        return MSSPE_OK;
+    };
+    auto cannot_split = [&](uint64_t count) {
+        return fail(ctx, MSSPE_ERR_CAPACITY, site_list_overrun("coverage_thal", count, cap));
+    };
+    if ((rc = run_slabs(ctx, std::move(todo), ct.slabs, ct.redone, &ct.matches, list_slab, synced, prepare, score, fold,
+                        cannot_split)))
+        return rc;
     if ((rc = ct.finish(n_seg, held_out, t_best_out, primer_segments_out, primer_held_out, ctx->stream, err)))
         return fail(ctx, rc, err);
-    read_scored();
+    read_slab_times(ct, false, scored);
     if (matches) {
         uint64_t count = 0;
         HIP_TRY(ctx, hipMemcpy(&count, d_count, sizeof count, hipMemcpyDeviceToHost));
@@ -3669,24 +3708,11 @@ int coverage_thal_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t se
     return MSSPE_OK;
 }
 
-// ev[3..5] of a scored slab of fill_held_matrix wait to be read behind the next synchronisation
-void thin_thal_read_scored(msspe_ctx *ctx, bool &scored)
-{
-    auto &tt = ctx->thin_thal;
-    float a = 0.f, b = 0.f;
-    if (scored && hipEventElapsedTime(&a, tt.ev[3], tt.ev[4]) == hipSuccess &&
-        hipEventElapsedTime(&b, tt.ev[4], tt.ev[5]) == hipSuccess) {
-        tt.score_us += (long long)(a * 1000.f);
-        tt.fold_us += (long long)(b * 1000.f);
-    }
-    scored = false;
-}
-
 // The held incidence matrix of n_fwd + n_rev primers (msspe_panel_thin_thal*, and a tolerant seeded stage A's tiles):
-// d_inc (PanelThin::matrix made it for them) zeroed, then coverage_thal_view's slab loop into it.  The caller has
+// d_inc (PanelThin::matrix made it for them) zeroed, then the slab loop (run_slabs) into it.  The caller has
 // the chemistry's entry, the workspace, the overflow lists, the work list for these primers, their plane words
-// (CoverageThal::prepare_words) and the events; `scored` says that a last slab's events are still to be read
-// (thin_thal_read_scored, behind the caller's next synchronisation).
+// (CoverageThal::prepare_words) and the events; `scored` says that a last slab's ev[3..5] are still to be read
+// (read_slab_times, behind the caller's next synchronisation).
 int fill_held_matrix(msspe_ctx *ctx, const SeqView &view, long n_seg, long P, const msspe_kmer_opt *opt,
                      const msspe_mismatch_opt *mm, ChemEntry *ce, bool end1, const uint64_t *fwd_words, int n_fwd,
                      const uint64_t *rev_words, int n_rev, uint64_t *d_inc, bool &scored)
@@ -3696,7 +3722,7 @@ int fill_held_matrix(msspe_ctx *ctx, const SeqView &view, long n_seg, long P, co
     std::string err;
     int rc;
     const int k = opt->kmer_size, n = n_fwd + n_rev;
-    const size_t cap = (size_t)1 << ctx->opt.site_list_cap_log2;
+    const size_t cap = site_list_cap(ctx);
     const double cut = ce->c[0].g_cut;
     const int S = MismatchCoverage::group_size(*opt);
     const long n_groups = (n_seg + S - 1) / S;
@@ -3704,62 +3730,23 @@ int fill_held_matrix(msspe_ctx *ctx, const SeqView &view, long n_seg, long P, co
     HIP_TRY(ctx, hipMemsetAsync(d_inc, 0, sizeof(uint64_t) * (size_t)n_groups * n_pad, ctx->stream));
     auto &w = ctx->site_work;
     CovMatch *list = reinterpret_cast<CovMatch *>(w.sites);
-    if (n_fwd)
-        HIP_TRY(ctx, hipMemcpyAsync(w.pool, fwd_words, sizeof(uint64_t) * (size_t)n_fwd, hipMemcpyHostToDevice,
-                                    ctx->stream));
-    if (n_rev)
-        HIP_TRY(ctx, hipMemcpyAsync(w.pool + n_fwd, rev_words, sizeof(uint64_t) * (size_t)n_rev,
-                                    hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->ovf_count, 0, 8 * sizeof(uint32_t), ctx->stream));
+    if ((rc = upload_site_pool(ctx, fwd_words, n_fwd, rev_words, n_rev))) return rc;
     const bool unique = ctx->opt.thin_thal_unique;
 
-    struct Slab { long g0, g1; int p0, p1; };
-    std::vector<Slab> todo{{0, n_groups, 0, n}};
-    auto read_scored = [&]() { thin_thal_read_scored(ctx, scored); };
-    while (!todo.empty()) {
-        const Slab s = todo.back();
-        todo.pop_back();
-        HIP_TRY(ctx, hipMemsetAsync(w.slab_count, 0, sizeof(uint64_t), ctx->stream));
+    auto list_slab = [&](const Slab &s) -> int {
         HIP_TRY(ctx, hipEventRecord(tt.ev[0], ctx->stream));
-        if ((rc = ct.list_slab(view, n_seg, P, *opt, mm->max_mismatches, mm->exact_3p, s.g0, s.g1, s.p0, s.p1, list,
+        if ((rc = ct.list_slab(view, n_seg, P, *opt, mm->max_mismatches, mm->exact_3p, s.o0, s.o1, s.p0, s.p1, list,
                                cap, w.slab_count, ctx->stream, err)))
             return fail(ctx, rc, err);
         HIP_TRY(ctx, hipEventRecord(tt.ev[1], ctx->stream));
-        uint64_t count = 0;
-        HIP_TRY(ctx, hipMemcpyAsync(&count, w.slab_count, sizeof count, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        read_scored();
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, tt.ev[0], tt.ev[1]) == hipSuccess) tt.list_us += (long long)(ms * 1000.f);
-        if (count > cap) {
-            ++tt.redone;
-            const uint64_t groups = (uint64_t)(s.g1 - s.g0), prim = (uint64_t)(s.p1 - s.p0);
-            const uint64_t want = (2 * count + cap - 1) / cap;   // parts that would be half full at this density
-            if (groups > 1) {
-                const uint64_t parts = std::min(groups, want);
-                for (uint64_t q = 0; q < parts; ++q)
-                    todo.push_back({s.g0 + (long)(groups * q / parts), s.g0 + (long)(groups * (q + 1) / parts), s.p0,
-                                    s.p1});
-            } else if (prim > 1) {
-                const uint64_t parts = std::min(prim, want);
-                for (uint64_t q = 0; q < parts; ++q)
-                    todo.push_back({s.g0, s.g1, s.p0 + (int)(prim * q / parts), s.p0 + (int)(prim * (q + 1) / parts)});
-            } else {
-                return fail(ctx, MSSPE_ERR_CAPACITY,
-                            "panel thin thal: one segment group against one primer has " + std::to_string(count) +
-                                " matches, the work list holds " + std::to_string(cap) +
-                                " (msspe_set_option \"site_list_cap_log2\")");
-            }
-            continue;
-        }
-        if (!count) continue;
-        ++tt.slabs;
-        tt.matches += (long long)count;
+        return MSSPE_OK;
+    };
+    auto synced = [&] { read_slab_times(tt, true, scored); };
+    auto prepare = [&](const Slab &, uint64_t count, uint32_t &n_pairs) -> int {
         HIP_TRY(ctx, hipEventRecord(tt.ev[2], ctx->stream));
-        uint32_t n_pairs = (uint32_t)count;
         if (unique) {
             // every template first, then the slab's runs: their pairs replace the identity pairs in w.list; the sort's
-            // key planes are dg and t, which nothing reads before the scoring below writes them
+            // key planes are dg and t, which nothing reads before the scoring writes them
             HIP_TRY(ctx, ct.oligos(view, P, *opt, list, 0, (uint32_t)count, w.pool, w.list, ctx->ovf_count,
                                    ctx->stream));
             if ((rc = tt.unique(list, w.pool, n, k, (uint32_t)count, reinterpret_cast<uint64_t *>(w.dg),
@@ -3771,31 +3758,37 @@ int fill_held_matrix(msspe_ctx *ctx, const SeqView &view, long n_seg, long P, co
             HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
             if (n_pairs == 0 || n_pairs > count)
                 return fail(ctx, MSSPE_ERR_DEVICE, "panel thin thal: the distinct pairs of a slab do not add up");
+            float ms = 0.f;
             if (hipEventElapsedTime(&ms, tt.ev[2], tt.ev[3]) == hipSuccess) tt.unique_us += (long long)(ms * 1000.f);
         } else {
             HIP_TRY(ctx, hipEventRecord(tt.ev[3], ctx->stream));
         }
         tt.unique_pairs += n_pairs;
-        // the hand-over lists may be shorter than the work list (a fixed list_cap_log2, a card short of memory)
-        const uint32_t step = (uint32_t)std::min<uint64_t>(n_pairs, (uint64_t)ctx->list_cap);
-        for (uint32_t c0 = 0; c0 < n_pairs; c0 += step) {
-            const uint32_t cnt = std::min(step, n_pairs - c0);
-            if (unique)   // the list's length, where oligos would have put it
-                HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)ctx->ovf_count, (int)cnt, 1, ctx->stream));
-            else
-                HIP_TRY(ctx, ct.oligos(view, P, *opt, list, c0, cnt, w.pool, w.list + c0, ctx->ovf_count, ctx->stream));
-            if ((rc = score_site_pairs(ctx, ce, end1, n, k, k, w.list + c0, cnt))) return rc;
-        }
+        return MSSPE_OK;
+    };
+    auto score = [&](uint32_t c0, uint32_t cnt) -> int {
+        if (unique)   // the list's length, where oligos would have put it
+            HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)ctx->ovf_count, (int)cnt, 1, ctx->stream));
+        else
+            HIP_TRY(ctx, ct.oligos(view, P, *opt, list, c0, cnt, w.pool, w.list + c0, ctx->ovf_count, ctx->stream));
+        return score_site_pairs(ctx, ce, end1, n, k, k, w.list + c0, cnt);
+    };
+    auto fold = [&](const Slab &, uint64_t count) -> int {
         HIP_TRY(ctx, hipEventRecord(tt.ev[4], ctx->stream));
         if ((rc = tt.fold(list, (uint32_t)count, unique, w.t, cut, S, n_pad, d_inc, ctx->stream, err)))
             return fail(ctx, rc, err);
         HIP_TRY(ctx, hipEventRecord(tt.ev[5], ctx->stream));
         scored = true;
-    }
-    return MSSPE_OK;
+        return MSSPE_OK;
+    };
+    auto cannot_split = [&](uint64_t count) {
+        return fail(ctx, MSSPE_ERR_CAPACITY, site_list_overrun("panel thin thal", count, cap));
+    };
+    return run_slabs(ctx, {{0, n_groups, 0, n}}, tt.slabs, tt.redone, &tt.matches, list_slab, synced, prepare, score,
+                     fold, cannot_split);
 }
 
-// msspe_panel_thin_thal*: coverage_thal_view's slab loop into the held incidence matrix, then PanelThin::rounds over
+// msspe_panel_thin_thal*: the slab loop (fill_held_matrix) into the held incidence matrix, then PanelThin::rounds over
 // it.  No per-segment word, cell plane or record list is kept: a slab's matches are listed, their templates cut
 // (CoverageThal::oligos), with thin_thal_unique the distinct (primer, template) pairs of the slab found
 // (PanelThinThal::unique) and only those scored, and every stable match ORs its bit into the matrix, which is zeroed
@@ -3819,8 +3812,7 @@ int panel_thin_thal_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t 
         return fail(ctx, MSSPE_ERR_ARG, "panel thin thal: depth must be 1..255");
     if (mode != 1 && mode != 2) return fail(ctx, MSSPE_ERR_ARG, "panel thin thal: mode must be 1 (ANY) or 2 (END1)");
     auto &tt = ctx->thin_thal;
-    tt.matches = tt.unique_pairs = tt.slabs = tt.redone = 0;
-    tt.list_us = tt.unique_us = tt.score_us = tt.fold_us = 0;
+    tt.reset_stats();
     *n_picked_out = 0;
     if (covered_all_out) *covered_all_out = 0;
     if (covered_kept_out) *covered_kept_out = 0;
@@ -3841,15 +3833,11 @@ int panel_thin_thal_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t 
     if (depth_all_out) std::fill(depth_all_out, depth_all_out + n_seg, (uint8_t)0);
     if (depth_kept_out) std::fill(depth_kept_out, depth_kept_out + n_seg, (uint8_t)0);
     if (n == 0 || n_seg == 0) return MSSPE_OK;
-    const size_t cap = (size_t)1 << ctx->opt.site_list_cap_log2;
-    if ((uint64_t)n + cap >= (1ull << 31)) return fail(ctx, MSSPE_ERR_ARG, "panel thin thal: too many primers");
+    if (!site_pool_fits(ctx, n)) return fail(ctx, MSSPE_ERR_ARG, "panel thin thal: too many primers");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const bool end1 = mode == 2;
     ChemEntry *ce = nullptr;
-    if ((rc = chem_entry(ctx, *chem, tm_threshold, &ce, end1 ? kCutEndT : kCutAnyT))) return rc;
-    if ((rc = ensure_workspace(ctx, (size_t)k * (size_t)k))) return rc;
-    if ((rc = ensure_overflow(ctx, (long)cap))) return rc;
-    if ((rc = ensure_site_work(ctx, cap, n, 0))) return rc;
+    if ((rc = site_scoring_begin(ctx, *chem, tm_threshold, end1, k, 0, n, &ce))) return rc;
     auto &ct = ctx->cov_thal;
     if ((rc = ct.prepare_words(*opt, fwd_words, n_fwd, rev_words, n_rev, ctx->stream, err))) return fail(ctx, rc, err);
     if ((rc = tt.events(err))) return fail(ctx, rc, err);
@@ -3871,7 +3859,7 @@ int panel_thin_thal_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t 
                               covered_all_out, covered_kept_out, ctx->n_cu, ctx->stream, err);
     }
     if (rc) return fail(ctx, rc, err);
-    thin_thal_read_scored(ctx, scored);   // rounds returned with the stream idle
+    read_slab_times(ctx->thin_thal, false, scored);   // rounds returned with the stream idle
     return MSSPE_OK;
 }
 
@@ -3937,8 +3925,7 @@ int panel_select_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t seq
     if (dep && dep->depth_kept_out) std::fill(dep->depth_kept_out, dep->depth_kept_out + n_seg, (uint8_t)0);
     if (n == 0 || n_seg == 0) return MSSPE_OK;
     if (!d_bitmap) return fail(ctx, MSSPE_ERR_ARG, "panel select: null bitmap");
-    const size_t cap = (size_t)1 << ctx->opt.site_list_cap_log2;
-    if (mode && (uint64_t)n + cap >= (1ull << 31)) return fail(ctx, MSSPE_ERR_ARG, "panel select: too many primers");
+    if (mode && !site_pool_fits(ctx, n)) return fail(ctx, MSSPE_ERR_ARG, "panel select: too many primers");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     for (auto &e : ctx->select_ev)
         if (!e) HIP_TRY(ctx, hipEventCreate(&e));
@@ -3963,14 +3950,10 @@ int panel_select_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t seq
             return fail(ctx, rc, err);
     } else {
         auto &tt = ctx->thin_thal;
-        tt.matches = tt.unique_pairs = tt.slabs = tt.redone = 0;
-        tt.list_us = tt.unique_us = tt.score_us = tt.fold_us = 0;
+        tt.reset_stats();
         const bool end1 = mode == 2;
         ChemEntry *ce = nullptr;
-        if ((rc = chem_entry(ctx, *rule->chem, rule->tm_threshold, &ce, end1 ? kCutEndT : kCutAnyT))) return rc;
-        if ((rc = ensure_workspace(ctx, (size_t)k * (size_t)k))) return rc;
-        if ((rc = ensure_overflow(ctx, (long)cap))) return rc;
-        if ((rc = ensure_site_work(ctx, cap, n, 0))) return rc;
+        if ((rc = site_scoring_begin(ctx, *rule->chem, rule->tm_threshold, end1, k, 0, n, &ce))) return rc;
         if ((rc = ctx->cov_thal.prepare_words(*opt, fwd_words, n_fwd, rev_words, n_rev, ctx->stream, err)))
             return fail(ctx, rc, err);
         if ((rc = tt.events(err))) return fail(ctx, rc, err);
@@ -3990,7 +3973,7 @@ int panel_select_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t seq
                                 order_out, gain_out, n_picked_out, tube_out, barred_out, covered_out, covered_all_out,
                                 covered_kept_out, n_tubes_used_out, ctx->n_cu, ctx->stream, err);
     if (rc) return fail(ctx, rc, err);
-    thin_thal_read_scored(ctx, scored);   // rounds returned with the stream idle
+    read_slab_times(ctx->thin_thal, false, scored);   // rounds returned with the stream idle
     long long keys_us = 0, sym_us = 0;
     ctx->cover.prepare_us(keys_us, sym_us);
     ctx->select_prepare_us = keys_us + sym_us;
@@ -4026,7 +4009,7 @@ int tolerant_check(msspe_ctx *ctx, int n_seq, size_t seq_len, const msspe_kmer_o
     if (rc) return fail(ctx, rc, err);
     if (rule->mode && opt->search_window_size - k >= (1 << kCovOffBits))
         return fail(ctx, MSSPE_ERR_ARG, "tolerant seeding: the search window has more than 2^26 positions");
-    if (rule->mode && (uint64_t)ns + ((uint64_t)1 << ctx->opt.site_list_cap_log2) >= (1ull << 31))
+    if (rule->mode && !site_pool_fits(ctx, ns))
         return fail(ctx, MSSPE_ERR_ARG, "tolerant seeding: too many seeds");
     return MSSPE_OK;
 }
@@ -4055,13 +4038,10 @@ int tolerant_prepare(msspe_ctx *ctx, const msspe_kmer_opt *opt, const msspe_seed
     *ce_out = nullptr;
     if (!rule->mode) return MSSPE_OK;
     auto &tt = ctx->thin_thal;
-    tt.matches = tt.unique_pairs = tt.slabs = tt.redone = 0;
-    tt.list_us = tt.unique_us = tt.score_us = tt.fold_us = 0;
-    const int k = opt->kmer_size;
+    tt.reset_stats();
     int rc;
-    if ((rc = chem_entry(ctx, *rule->chem, rule->tm_threshold, ce_out, rule->mode == 2 ? kCutEndT : kCutAnyT))) return rc;
-    if ((rc = ensure_workspace(ctx, (size_t)k * (size_t)k))) return rc;
-    if ((rc = ensure_overflow(ctx, (long)((size_t)1 << ctx->opt.site_list_cap_log2)))) return rc;
+    if ((rc = site_scoring_begin(ctx, *rule->chem, rule->tm_threshold, rule->mode == 2, opt->kmer_size, 0, -1, ce_out)))
+        return rc;
     std::string err;
     if ((rc = tt.events(err))) return fail(ctx, rc, err);
     return MSSPE_OK;
@@ -4108,7 +4088,7 @@ int tolerant_seed_pass(msspe_ctx *ctx, KmerStage &stage, hipStream_t stage_strea
     }
     const int tile = (int)std::min<size_t>(fit, ((size_t)n + 63) & ~(size_t)63);
     int rc;
-    if (rule->mode && (rc = ensure_site_work(ctx, (size_t)1 << ctx->opt.site_list_cap_log2, std::min(tile, n), 0))) {
+    if (rule->mode && (rc = ensure_site_work(ctx, site_list_cap(ctx), std::min(tile, n), 0))) {
         err = ctx->err;
         return rc;
     }
@@ -4133,7 +4113,7 @@ int tolerant_seed_pass(msspe_ctx *ctx, KmerStage &stage, hipStream_t stage_strea
                 return rc;
             }
             TOL_TRY(hipStreamSynchronize(stream));
-            thin_thal_read_scored(ctx, scored);
+            read_slab_times(ctx->thin_thal, false, scored);
         }
         TOL_TRY(hipEventRecord(tl.ev[1], stream));
         if ((rc = stage.seed_rows(d_inc, n_pad, nt, n_groups, S, stream, err))) return rc;
@@ -4997,6 +4977,30 @@ int msspe_host_screen_plan(int first_stage, int row0, int row1, int col0, int nc
     for (const Launch &l : plan.launches) {
         const int64_t row[7] = {l.row0, l.row1, l.col0, l.col1, l.pairs, l.list_entries, l.flush_before ? 1 : 0};
         out = std::copy(row, row + 7, out);
+    }
+    return MSSPE_OK;
+}
+
+int msspe_host_slab_split(int64_t o0, int64_t o1, int p0, int p1, uint64_t count, uint64_t cap, int64_t *out,
+                          int capacity, int *n_out)
+{
+    // host only: the parts run_slabs lists again for a slab whose `count` matches overran a work list of `cap`
+    if (!n_out || capacity < 0 || (capacity > 0 && !out)) return MSSPE_ERR_ARG;
+    *n_out = 0;
+    if (o0 < 0 || o1 <= o0 || o1 - o0 > INT32_MAX || p0 < 0 || p1 <= p0 || cap < 1 || count <= cap ||
+        count > (UINT64_MAX - cap) / 2)   // (the last two: what the rule's 64-bit arithmetic holds)
+        return MSSPE_ERR_ARG;
+    std::vector<Slab> parts;
+    try {
+        (void)split_slab({(long)o0, (long)o1, p0, p1}, count, cap, parts);   // no parts: the slab cannot be split
+    } catch (const std::bad_alloc &) {
+        return MSSPE_ERR_NOMEM;
+    }
+    *n_out = (int)parts.size();
+    if (*n_out > capacity) return MSSPE_ERR_CAPACITY;
+    for (const Slab &s : parts) {
+        const int64_t row[4] = {s.o0, s.o1, s.p0, s.p1};
+        out = std::copy(row, row + 4, out);
     }
     return MSSPE_OK;
 }

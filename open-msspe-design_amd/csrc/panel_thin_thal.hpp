@@ -35,6 +35,11 @@ public:
     // of the last call (msspe_get_info "panel_thin_thal_*")
     long long matches = 0, unique_pairs = 0, slabs = 0, redone = 0;
     long long list_us = 0, unique_us = 0, score_us = 0, fold_us = 0;
+    void reset_stats()
+    {
+        matches = unique_pairs = slabs = redone = 0;
+        list_us = unique_us = score_us = fold_us = 0;
+    }
     hipEvent_t ev[6] = {};   // before / after the listing; before the oligos, after the unique step, the scores, the fold
 
 private:

@@ -26,7 +26,7 @@ EXPORTS = [
     "msspe_conflict_graph_ab_edges",
     "msspe_conflict_cover_dev", "msspe_conflict_cover", "msspe_conflict_cover_rule",
     "msspe_conflict_tubes_dev", "msspe_conflict_tubes", "msspe_conflict_tubes_rule",
-    "msspe_last_overflow_pairs", "msspe_pair_stage_stats", "msspe_pair_stage_samples", "msspe_host_pair_tables", "msspe_host_table_routes", "msspe_host_screen_plan", "msspe_host_split_tables", "msspe_device_put_rows", "msspe_segment_coverage", "msspe_segment_coverage_dev",
+    "msspe_last_overflow_pairs", "msspe_pair_stage_stats", "msspe_pair_stage_samples", "msspe_host_pair_tables", "msspe_host_table_routes", "msspe_host_screen_plan", "msspe_host_slab_split", "msspe_host_split_tables", "msspe_device_put_rows", "msspe_segment_coverage", "msspe_segment_coverage_dev",
     "msspe_device_put", "msspe_device_get", "msspe_device_free", "msspe_thal_detail_pairs", "msspe_profile_enable", "msspe_profile_read",
     "msspe_oligo_stats_dev", "msspe_oligo_stats",
     "msspe_kmer_candidates", "msspe_kmer_candidates_dev", "msspe_round_g_f32",
@@ -397,6 +397,8 @@ def load_library() -> C.CDLL:
     L.msspe_device_get.argtypes = [vp, vp, C.c_size_t, vp]
     L.msspe_host_table_routes.argtypes = [C.c_char_p, C.POINTER(Chem), C.POINTER(C.c_int32)]
     L.msspe_host_screen_plan.argtypes = [C.c_int] * 5 + [C.c_int64, vp, C.c_int, C.POINTER(C.c_int)]
+    L.msspe_host_slab_split.argtypes = [C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_uint64, C.c_uint64, vp, C.c_int,
+                                        C.POINTER(C.c_int)]
     L.msspe_thal_detail_pairs.argtypes = [vp, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(Chem), C.c_int, vp]
     L.msspe_round_g_f32.restype = C.c_float
     L.msspe_round_g_f32.argtypes = [C.c_double]
@@ -504,6 +506,20 @@ def host_screen_plan(first_stage: str, row0: int, row1: int, col0: int, ncols: i
             return out[:n.value]
         if rc != 5:     # MSSPE_ERR_CAPACITY: n holds the launch count
             raise MsspeError(rc, f"msspe_host_screen_plan({first_stage}, {row0}, {row1}, {col0}, {ncols}, {list_cap})")
+
+
+def host_slab_split(o0: int, o1: int, p0: int, p1: int, count: int, cap: int) -> np.ndarray:
+    """The parts a thal-scored site pass lists again for the slab [o0, o1) x primers [p0, p1) whose count matches overran
+    a work list of cap (count > cap), in the order they are pushed (no device needed): msspe_host_slab_split.  int64
+    (parts, 4), columns o0, o1, p0, p1; no rows: one outer element against one primer cannot be split."""
+    n = C.c_int(64)
+    while True:
+        out = np.zeros((n.value, 4), dtype=np.int64)
+        rc = load_library().msspe_host_slab_split(o0, o1, p0, p1, count, cap, out.ctypes.data, len(out), C.byref(n))
+        if rc == 0:
+            return out[:n.value]
+        if rc != 5:     # MSSPE_ERR_CAPACITY: n holds the part count
+            raise MsspeError(rc, f"msspe_host_slab_split({o0}, {o1}, {p0}, {p1}, {count}, {cap})")
 
 
 def host_bound_tables(params_path: str | None = None, chem: Chem | None = None, threshold: float = -9000.0) -> dict:
