@@ -1545,6 +1545,77 @@ int msspe_panel_select_depth_rule(msspe_ctx *ctx, const uint8_t *seqs, int n_seq
                                   int *n_tubes_used_out, uint8_t *pick_layer_out, uint8_t *depth_all_out,
                                   uint8_t *depth_kept_out, long long *counts_out);
 
+/* ---- weighted coverage: thinning and selection on a weight per segment (engine extension, no reference
+ * counterpart) ----
+ * msspe_panel_thin* and msspe_panel_select* count every segment as 1, so 9,000 near-identical genomes of one lineage
+ * outvote 40 of a rare clade.  These calls take a weight per segment and are otherwise their unweighted siblings, at
+ * depth 1: the arguments, limits, errors and msspe_get_info keys ("panel_thin_*", "panel_select_*") are the sibling's.
+ *   weights (host, n_seq * P entries, uint32): weights[s], s = r * P + j, in the order of best_out / covered_out.
+ *   gain(p) = the SUM of weights[s] over the segments s with I[p][s] set and covered[s] clear.  The pick is the greatest
+ *     gain, ties to the lowest index; the loop ends when that gain is below min_gain, which is in WEIGHT UNITS here (and
+ *     >= 1).  gain_out holds weights.  Covering, forcing, barring, tubes and every other output are unchanged.
+ *   A segment of weight 0 never contributes to a gain, so no primer is spent on it; it still gets its covered bit when a
+ *     pick happens to cover it: covered_out, *covered_all_out and *covered_kept_out stay the real coverage, in segments.
+ *   *weight_all_out / *weight_kept_out (optional): the weight of the segments that the whole set covers and that the
+ *     kept set covers.
+ *   The weights' total over all segments must be <= 2^32 - 1, so that every gain fits the high half of the pick key
+ *     gain << 32 | ~p: above it the call returns MSSPE_ERR_ARG with both figures in msspe_last_error.  weights == NULL is
+ *     MSSPE_ERR_ARG: the unweighted call exists for that case.
+ * GUARANTEES.  (1) With all weights 1 every output equals the unweighted call's: keep, order, gains, covered, both
+ * counts, tubes, barred (and the two weights equal the two counts).  (2) For the thinning at min_gain 1,
+ * *weight_kept_out == *weight_all_out: no segment of positive weight that the whole set covers is lost.  The selection
+ * does not promise this, as it does not promise it unweighted: conflicts may cost segments -- the weights decide which.
+ * The thinning forms use the string rule of msspe_panel_thin*.  The selection forms take the msspe_seed_rule modes 0..2
+ * as msspe_panel_select* does; the _rule form screens the pool itself under a msspe_conflict_rule (use_end = 0 gives the
+ * dG-only screen of msspe_panel_select). */
+int msspe_panel_thin_weighted(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len, const msspe_kmer_opt *opt,
+                              const msspe_mismatch_opt *mm, const msspe_thin_opt *thin, const uint64_t *fwd_words,
+                              int n_fwd, const uint64_t *rev_words, int n_rev, const uint8_t *forced,
+                              const uint32_t *weights, uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out,
+                              int *n_picked_out, uint8_t *covered_out, long long *covered_all_out,
+                              long long *covered_kept_out, uint64_t *weight_all_out, uint64_t *weight_kept_out);
+int msspe_panel_thin_weighted_dev(msspe_ctx *ctx, const uint8_t *d_seqs, int n_seq, size_t seq_len,
+                                  const msspe_kmer_opt *opt, const msspe_mismatch_opt *mm, const msspe_thin_opt *thin,
+                                  const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
+                                  const uint8_t *forced, const uint32_t *weights, uint8_t *keep_out,
+                                  uint32_t *order_out, uint32_t *gain_out, int *n_picked_out, uint8_t *covered_out,
+                                  long long *covered_all_out, long long *covered_kept_out, uint64_t *weight_all_out,
+                                  uint64_t *weight_kept_out);
+int msspe_panel_thin_weighted_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
+                                         const msspe_kmer_opt *opt, const msspe_mismatch_opt *mm,
+                                         const msspe_thin_opt *thin, const uint64_t *fwd_words, int n_fwd,
+                                         const uint64_t *rev_words, int n_rev, const uint8_t *forced,
+                                         const uint32_t *weights, uint8_t *keep_out, uint32_t *order_out,
+                                         uint32_t *gain_out, int *n_picked_out, uint8_t *covered_out,
+                                         long long *covered_all_out, long long *covered_kept_out,
+                                         uint64_t *weight_all_out, uint64_t *weight_kept_out);
+int msspe_panel_select_weighted_dev(msspe_ctx *ctx, const uint8_t *d_seqs, int n_seq, size_t seq_len,
+                                    const msspe_kmer_opt *opt, const msspe_seed_rule *rule, const msspe_select_opt *sel,
+                                    const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
+                                    const uint8_t *forced, const uint64_t *d_bitmap, const uint32_t *weights,
+                                    uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out, int *n_picked_out,
+                                    uint8_t *tube_out, uint8_t *barred_out, uint8_t *covered_out,
+                                    long long *covered_all_out, long long *covered_kept_out, int *n_tubes_used_out,
+                                    uint64_t *weight_all_out, uint64_t *weight_kept_out);
+int msspe_panel_select_weighted_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
+                                           const msspe_kmer_opt *opt, const msspe_seed_rule *rule,
+                                           const msspe_select_opt *sel, const uint64_t *fwd_words, int n_fwd,
+                                           const uint64_t *rev_words, int n_rev, const uint8_t *forced,
+                                           const uint64_t *d_bitmap, const uint32_t *weights, uint8_t *keep_out,
+                                           uint32_t *order_out, uint32_t *gain_out, int *n_picked_out,
+                                           uint8_t *tube_out, uint8_t *barred_out, uint8_t *covered_out,
+                                           long long *covered_all_out, long long *covered_kept_out,
+                                           int *n_tubes_used_out, uint64_t *weight_all_out, uint64_t *weight_kept_out);
+int msspe_panel_select_weighted_rule(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len,
+                                     const msspe_kmer_opt *opt, const msspe_seed_rule *rule, const msspe_select_opt *sel,
+                                     const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
+                                     const uint8_t *forced, const msspe_chem *chem,
+                                     const msspe_conflict_rule *conflict_rule, const uint32_t *weights,
+                                     uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out, int *n_picked_out,
+                                     uint8_t *tube_out, uint8_t *barred_out, uint8_t *covered_out,
+                                     long long *covered_all_out, long long *covered_kept_out, int *n_tubes_used_out,
+                                     uint64_t *weight_all_out, uint64_t *weight_kept_out);
+
 /* ---- several devices of one node ----------------------------------------------------------
  *
  * One process, one context and one host thread per device.  What shards is the reference's N^2 pair loop

@@ -2849,22 +2849,50 @@ int msspe_segment_coverage_mm(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, si
     return rc;
 }
 
+// The weighted calls' own argument errors (msspe_panel_thin_weighted*, msspe_panel_select_weighted*): NULL weights,
+// and a total over the n_seq * P segments above 2^32 - 1 (a gain must fit the high half of the pick key).  The
+// options are checked first, as the sibling checks them, so that P is defined.
+static int panel_weights_check(msspe_ctx *ctx, const char *who, const PanelWeights &wts, int n_seq, size_t seq_len,
+                               const msspe_kmer_opt &opt, int max_mismatches, int exact_3p, const uint64_t *fwd_words,
+                               int n_fwd, const uint64_t *rev_words, int n_rev)
+{
+    if (wts.weight_all_out) *wts.weight_all_out = 0;
+    if (wts.weight_kept_out) *wts.weight_kept_out = 0;
+    if (!wts.weights) return fail(ctx, MSSPE_ERR_ARG, std::string(who) + ": null weights (the unweighted call takes none)");
+    std::string err;
+    long P = 0;
+    if (int rc = MismatchCoverage::check(n_seq, seq_len, opt, max_mismatches, exact_3p, fwd_words, n_fwd, rev_words,
+                                         n_rev, &P, err))
+        return fail(ctx, rc, err);
+    uint64_t total = 0;
+    const uint64_t limit = 0xFFFFFFFFull;
+    for (long s = 0; s < P * n_seq; ++s) total += wts.weights[s];   // at most 2^63 / 2^32 segments would wrap: not reachable
+    if (total > limit)
+        return fail(ctx, MSSPE_ERR_ARG, std::string(who) + ": the weights add up to " + std::to_string(total) +
+                                            ", at most " + std::to_string(limit) + " (a gain is a 32-bit number)");
+    return MSSPE_OK;
+}
+
 static int panel_thin_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t seq_len, const msspe_kmer_opt *opt,
                            const msspe_mismatch_opt *mm, const msspe_thin_opt *thin, const uint64_t *fwd_words,
                            int n_fwd, const uint64_t *rev_words, int n_rev, const uint8_t *forced, uint8_t *keep_out,
                            uint32_t *order_out, uint32_t *gain_out, int *n_picked_out, uint8_t *covered_out,
-                           long long *covered_all_out, long long *covered_kept_out)
+                           long long *covered_all_out, long long *covered_kept_out, const PanelWeights *wts = nullptr)
 {
     if (!opt || !mm || !thin || !keep_out || !order_out || !gain_out || !n_picked_out || n_fwd < 0 || n_rev < 0 ||
         (n_fwd && !fwd_words) || (n_rev && !rev_words))
         return fail(ctx, MSSPE_ERR_ARG, "panel thin: null argument");
     if (thin->min_gain < 1) return fail(ctx, MSSPE_ERR_ARG, "panel thin: min_gain must be at least 1");
+    if (wts)
+        if (int rc = panel_weights_check(ctx, "panel thin", *wts, n_seq, seq_len, *opt, mm->max_mismatches, mm->exact_3p,
+                                         fwd_words, n_fwd, rev_words, n_rev))
+            return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::string err;
     const int rc = ctx->thin.run(ctx->mm_cov, view, n_seq, seq_len, *opt, mm->max_mismatches, mm->exact_3p,
                                  thin->min_gain, fwd_words, n_fwd, rev_words, n_rev, forced, keep_out, order_out,
                                  gain_out, n_picked_out, covered_out, covered_all_out, covered_kept_out,
-                                 (size_t)ctx->opt.panel_thin_matrix_max_mb << 20, ctx->n_cu, ctx->stream, err);
+                                 (size_t)ctx->opt.panel_thin_matrix_max_mb << 20, ctx->n_cu, ctx->stream, err, wts);
     if (rc) return fail(ctx, rc, err);
     return MSSPE_OK;
 }
@@ -2910,6 +2938,58 @@ int msspe_panel_thin(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_
     rc = msspe_panel_thin_dev(ctx, (const uint8_t *)d, n_seq, seq_len, opt, mm, thin, fwd_words, n_fwd, rev_words,
                               n_rev, forced, keep_out, order_out, gain_out, n_picked_out, covered_out, covered_all_out,
                               covered_kept_out);
+    (void)msspe_device_free(ctx, d);
+    return rc;
+}
+
+int msspe_panel_thin_weighted_dev(msspe_ctx *ctx, const uint8_t *d_seqs, int n_seq, size_t seq_len,
+                                  const msspe_kmer_opt *opt, const msspe_mismatch_opt *mm, const msspe_thin_opt *thin,
+                                  const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
+                                  const uint8_t *forced, const uint32_t *weights, uint8_t *keep_out,
+                                  uint32_t *order_out, uint32_t *gain_out, int *n_picked_out, uint8_t *covered_out,
+                                  long long *covered_all_out, long long *covered_kept_out, uint64_t *weight_all_out,
+                                  uint64_t *weight_kept_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!d_seqs) return fail(ctx, MSSPE_ERR_ARG, "null sequences");
+    const PanelWeights wts = {weights, weight_all_out, weight_kept_out};
+    return panel_thin_view(ctx, SeqView{d_seqs, nullptr, seq_len}, n_seq, seq_len, opt, mm, thin, fwd_words, n_fwd,
+                           rev_words, n_rev, forced, keep_out, order_out, gain_out, n_picked_out, covered_out,
+                           covered_all_out, covered_kept_out, &wts);
+}
+
+int msspe_panel_thin_weighted_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
+                                         const msspe_kmer_opt *opt, const msspe_mismatch_opt *mm,
+                                         const msspe_thin_opt *thin, const uint64_t *fwd_words, int n_fwd,
+                                         const uint64_t *rev_words, int n_rev, const uint8_t *forced,
+                                         const uint32_t *weights, uint8_t *keep_out, uint32_t *order_out,
+                                         uint32_t *gain_out, int *n_picked_out, uint8_t *covered_out,
+                                         long long *covered_all_out, long long *covered_kept_out,
+                                         uint64_t *weight_all_out, uint64_t *weight_kept_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!d_packed) return fail(ctx, MSSPE_ERR_ARG, "null sequences");
+    const PanelWeights wts = {weights, weight_all_out, weight_kept_out};
+    return panel_thin_view(ctx, SeqView{nullptr, d_packed, seq_len}, n_seq, seq_len, opt, mm, thin, fwd_words, n_fwd,
+                           rev_words, n_rev, forced, keep_out, order_out, gain_out, n_picked_out, covered_out,
+                           covered_all_out, covered_kept_out, &wts);
+}
+
+int msspe_panel_thin_weighted(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len, const msspe_kmer_opt *opt,
+                              const msspe_mismatch_opt *mm, const msspe_thin_opt *thin, const uint64_t *fwd_words,
+                              int n_fwd, const uint64_t *rev_words, int n_rev, const uint8_t *forced,
+                              const uint32_t *weights, uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out,
+                              int *n_picked_out, uint8_t *covered_out, long long *covered_all_out,
+                              long long *covered_kept_out, uint64_t *weight_all_out, uint64_t *weight_kept_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!seqs || n_seq < 0) return fail(ctx, MSSPE_ERR_ARG, "null sequences");
+    void *d = nullptr;
+    int rc = msspe_device_put(ctx, seqs, (size_t)n_seq * seq_len, &d);
+    if (rc) return rc;
+    rc = msspe_panel_thin_weighted_dev(ctx, (const uint8_t *)d, n_seq, seq_len, opt, mm, thin, fwd_words, n_fwd,
+                                       rev_words, n_rev, forced, weights, keep_out, order_out, gain_out, n_picked_out,
+                                       covered_out, covered_all_out, covered_kept_out, weight_all_out, weight_kept_out);
     (void)msspe_device_free(ctx, d);
     return rc;
 }
@@ -3879,7 +3959,8 @@ int panel_select_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t seq
                       const uint64_t *rev_words, int n_rev, const uint8_t *forced, const uint64_t *d_bitmap,
                       uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out, int *n_picked_out, uint8_t *tube_out,
                       uint8_t *barred_out, uint8_t *covered_out, long long *covered_all_out,
-                      long long *covered_kept_out, int *n_tubes_used_out, const SelectDepthArgs *dep = nullptr)
+                      long long *covered_kept_out, int *n_tubes_used_out, const SelectDepthArgs *dep = nullptr,
+                      const PanelWeights *wts = nullptr)
 {
     if (!opt || !rule || !sel || !keep_out || !order_out || !gain_out || !n_picked_out || !tube_out || n_fwd < 0 ||
         n_rev < 0 || (n_fwd && !fwd_words) || (n_rev && !rev_words))
@@ -3913,6 +3994,10 @@ int panel_select_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t seq
     if (rc) return fail(ctx, rc, err);
     if (mode && opt->search_window_size - k >= (1 << kCovOffBits))   // a match's offset travels in kCovOffBits bits
         return fail(ctx, MSSPE_ERR_ARG, "panel select: the search window has more than 2^26 positions");
+    if (wts)   // depth 1 only: no caller passes both
+        if ((rc = panel_weights_check(ctx, "panel select", *wts, n_seq, seq_len, *opt, mm.max_mismatches, mm.exact_3p,
+                                      fwd_words, n_fwd, rev_words, n_rev)))
+            return rc;
     const int n = n_fwd + n_rev;
     const long n_seg = P * n_seq;
     for (int p = 0; p < n; ++p) {
@@ -3971,7 +4056,7 @@ int panel_select_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t seq
     else
         rc = ctx->select.rounds(d_inc, ctx->cover.symmetrised(), n, n_seg, S, sel->min_gain, sel->max_tubes, keep_out,
                                 order_out, gain_out, n_picked_out, tube_out, barred_out, covered_out, covered_all_out,
-                                covered_kept_out, n_tubes_used_out, ctx->n_cu, ctx->stream, err);
+                                covered_kept_out, n_tubes_used_out, ctx->n_cu, ctx->stream, err, wts);
     if (rc) return fail(ctx, rc, err);
     read_slab_times(ctx->thin_thal, false, scored);   // rounds returned with the stream idle
     long long keys_us = 0, sym_us = 0;
@@ -4419,7 +4504,8 @@ static int panel_select_host(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, siz
                              uint32_t *order_out, uint32_t *gain_out, int *n_picked_out, uint8_t *tube_out,
                              uint8_t *barred_out, uint8_t *covered_out, long long *covered_all_out,
                              long long *covered_kept_out, int *n_tubes_used_out,
-                             const msspe_conflict_rule *conflict_rule = nullptr, const SelectDepthArgs *dep = nullptr)
+                             const msspe_conflict_rule *conflict_rule = nullptr, const SelectDepthArgs *dep = nullptr,
+                             const PanelWeights *wts = nullptr)
 {
     if (!seqs || n_seq < 0) return fail(ctx, MSSPE_ERR_ARG, "null sequences");
     if (n_fwd < 0 || n_rev < 0 || (n_fwd && !fwd_words) || (n_rev && !rev_words) || !opt || !rule || !sel || !keep_out ||
@@ -4470,6 +4556,11 @@ static int panel_select_host(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, siz
         rc = panel_select_view(ctx, SeqView{(const uint8_t *)d, nullptr, seq_len}, n_seq, seq_len, opt, rule, sel,
                                fwd_words, n_fwd, rev_words, n_rev, forced, d_bitmap, keep_out, order_out, gain_out,
                                n_picked_out, tube_out, barred_out, nullptr, nullptr, nullptr, n_tubes_used_out, dep);
+    else if (wts)
+        rc = panel_select_view(ctx, SeqView{(const uint8_t *)d, nullptr, seq_len}, n_seq, seq_len, opt, rule, sel,
+                               fwd_words, n_fwd, rev_words, n_rev, forced, d_bitmap, keep_out, order_out, gain_out,
+                               n_picked_out, tube_out, barred_out, covered_out, covered_all_out, covered_kept_out,
+                               n_tubes_used_out, nullptr, wts);
     else
         rc = msspe_panel_select_dev(ctx, (const uint8_t *)d, n_seq, seq_len, opt, rule, sel, fwd_words, n_fwd,
                                     rev_words, n_rev, forced, d_bitmap, keep_out, order_out, gain_out, n_picked_out,
@@ -4510,6 +4601,68 @@ int msspe_panel_select_rule(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size
     return panel_select_host(ctx, seqs, n_seq, seq_len, opt, rule, sel, fwd_words, n_fwd, rev_words, n_rev, forced,
                              nullptr, chem, 0.0f, keep_out, order_out, gain_out, n_picked_out, tube_out, barred_out,
                              covered_out, covered_all_out, covered_kept_out, n_tubes_used_out, conflict_rule);
+}
+
+// msspe_panel_select_weighted*: the selection with a weight per segment; the rest of such a call is
+// its unweighted sibling's.
+int msspe_panel_select_weighted_dev(msspe_ctx *ctx, const uint8_t *d_seqs, int n_seq, size_t seq_len,
+                                    const msspe_kmer_opt *opt, const msspe_seed_rule *rule, const msspe_select_opt *sel,
+                                    const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
+                                    const uint8_t *forced, const uint64_t *d_bitmap, const uint32_t *weights,
+                                    uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out, int *n_picked_out,
+                                    uint8_t *tube_out, uint8_t *barred_out, uint8_t *covered_out,
+                                    long long *covered_all_out, long long *covered_kept_out, int *n_tubes_used_out,
+                                    uint64_t *weight_all_out, uint64_t *weight_kept_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!d_seqs) return fail(ctx, MSSPE_ERR_ARG, "null sequences");
+    const PanelWeights wts = {weights, weight_all_out, weight_kept_out};
+    return panel_select_view(ctx, SeqView{d_seqs, nullptr, seq_len}, n_seq, seq_len, opt, rule, sel, fwd_words, n_fwd,
+                             rev_words, n_rev, forced, d_bitmap, keep_out, order_out, gain_out, n_picked_out, tube_out,
+                             barred_out, covered_out, covered_all_out, covered_kept_out, n_tubes_used_out, nullptr,
+                             &wts);
+}
+
+int msspe_panel_select_weighted_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
+                                           const msspe_kmer_opt *opt, const msspe_seed_rule *rule,
+                                           const msspe_select_opt *sel, const uint64_t *fwd_words, int n_fwd,
+                                           const uint64_t *rev_words, int n_rev, const uint8_t *forced,
+                                           const uint64_t *d_bitmap, const uint32_t *weights, uint8_t *keep_out,
+                                           uint32_t *order_out, uint32_t *gain_out, int *n_picked_out,
+                                           uint8_t *tube_out, uint8_t *barred_out, uint8_t *covered_out,
+                                           long long *covered_all_out, long long *covered_kept_out,
+                                           int *n_tubes_used_out, uint64_t *weight_all_out, uint64_t *weight_kept_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!d_packed) return fail(ctx, MSSPE_ERR_ARG, "null sequences");
+    const PanelWeights wts = {weights, weight_all_out, weight_kept_out};
+    return panel_select_view(ctx, SeqView{nullptr, d_packed, seq_len}, n_seq, seq_len, opt, rule, sel, fwd_words, n_fwd,
+                             rev_words, n_rev, forced, d_bitmap, keep_out, order_out, gain_out, n_picked_out, tube_out,
+                             barred_out, covered_out, covered_all_out, covered_kept_out, n_tubes_used_out, nullptr,
+                             &wts);
+}
+
+int msspe_panel_select_weighted_rule(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len,
+                                     const msspe_kmer_opt *opt, const msspe_seed_rule *rule, const msspe_select_opt *sel,
+                                     const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
+                                     const uint8_t *forced, const msspe_chem *chem,
+                                     const msspe_conflict_rule *conflict_rule, const uint32_t *weights,
+                                     uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out, int *n_picked_out,
+                                     uint8_t *tube_out, uint8_t *barred_out, uint8_t *covered_out,
+                                     long long *covered_all_out, long long *covered_kept_out, int *n_tubes_used_out,
+                                     uint64_t *weight_all_out, uint64_t *weight_kept_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (int rc = graph_rule_check(ctx, chem, conflict_rule, GraphOut{}, false)) return rc;
+    if (weight_all_out) *weight_all_out = 0;
+    if (weight_kept_out) *weight_kept_out = 0;
+    if (!weights)   // before the screen, not after it
+        return fail(ctx, MSSPE_ERR_ARG, "panel select: null weights (the unweighted call takes none)");
+    const PanelWeights wts = {weights, weight_all_out, weight_kept_out};
+    return panel_select_host(ctx, seqs, n_seq, seq_len, opt, rule, sel, fwd_words, n_fwd, rev_words, n_rev, forced,
+                             nullptr, chem, 0.0f, keep_out, order_out, gain_out, n_picked_out, tube_out, barred_out,
+                             covered_out, covered_all_out, covered_kept_out, n_tubes_used_out, conflict_rule, nullptr,
+                             &wts);
 }
 
 int msspe_panel_select_bitmap(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len,

@@ -30,6 +30,10 @@
 // "closed".  k_select_apply_depth is the apply step of a layered round: the pick counts on EVERY segment of its row,
 // open or not, the open ones that reach min(r, all) close, and the barring is k_select_apply's.  Picks, masks and
 // cnt carry over from layer to layer; between layers the host clears `done` and the gains.
+//
+// Weights (msspe_panel_select_weighted*).  gain(p) is the sum of a weight per segment over the
+// uncovered segments of row p: the first gains and the update run in their weighted instances (panel_weighted.hpp);
+// forced, first barring, pick and apply are the kernels above, unchanged.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -39,6 +43,7 @@
 #include "../../include/msspe_hip.h"
 #include "panel_select.hpp"
 #include "panel_thin.hpp"
+#include "panel_weighted.hpp"
 
 namespace msspe {
 
@@ -63,7 +68,7 @@ struct SelectState {
     unsigned long long covered_forced;   // |OR of the forced I[p]|
 };
 
-enum { kPool, kCov, kTouched, kNew, kGain, kMask, kBytes, kOrder, kForced, kDepth, kPrimerMask };   // PanelSelect::buf_
+enum { kPool, kCov, kTouched, kNew, kGain, kMask, kBytes, kOrder, kForced, kDepth, kPrimerMask, kWeight };   // PanelSelect::buf_
 
 __device__ __forceinline__ uint64_t wave_or(uint64_t x)
 {
@@ -364,11 +369,14 @@ int PanelSelect::rounds(const uint64_t *d_inc, const uint64_t *d_sym, int n, lon
                         int max_tubes, uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out, int *n_picked_out,
                         uint8_t *tube_out, uint8_t *barred_out, uint8_t *covered_out, long long *covered_all_out,
                         long long *covered_kept_out, int *n_tubes_used_out, int n_cu, hipStream_t stream,
-                        std::string &err)
+                        std::string &err, const PanelWeights *wts)
 {
     const long G = (n_seg + S - 1) / S;
     const int W = (n + 63) / 64;
     const size_t n_pad = ((size_t)n + 63) & ~(size_t)63;
+    if (wts)   // the sums, the plane and the weights as given: the one slot a weighted call adds
+        if (int rc = ensure(kWeight, weighted::Plane::bytes(G, n_seg), err)) return rc;
+    const weighted::Plane wp(wts ? buf_[kWeight] : nullptr, G);
     const uint64_t tubes_mask = max_tubes >= 64 ? ~0ull : (1ull << max_tubes) - 1;
     uint64_t *d_cov = (uint64_t *)buf_[kCov], *d_new = (uint64_t *)buf_[kNew], *d_mask = (uint64_t *)buf_[kMask];
     SelectState *st = (SelectState *)(d_cov + G);   // behind the covered words: 8-byte aligned
@@ -398,8 +406,22 @@ int PanelSelect::rounds(const uint64_t *d_inc, const uint64_t *d_sym, int n, lon
     }
     hipLaunchKernelGGL(k_select_bar0, dim3(gx), dim3(kThreads), 0, stream, d_sym, n, W, d_forced,
                        (int)forced_idx.size(), tubes_mask, d_mask, d_flags);
-    hipLaunchKernelGGL(k_select_gain0, dim3((unsigned)((G + kChunk - 1) / kChunk)), dim3(kThreads), 0, stream, d_inc,
-                       n, n_pad, (int)G, d_cov, d_gain, st);
+    if (wts) {   // the plane is rewritten by every call: nothing of the last one's is read
+        const unsigned cells = (unsigned)(((size_t)G * 64 + kThreads - 1) / kThreads);
+        SELECT_TRY(hipMemsetAsync(wp.sums, 0, 2 * sizeof(unsigned long long), stream));
+        SELECT_TRY(hipMemcpyAsync(wp.by_segment, wts->weights, sizeof(uint32_t) * (size_t)n_seg, hipMemcpyHostToDevice,
+                                  stream));
+        hipLaunchKernelGGL(weighted::k_weight_plane, dim3(cells), dim3(kThreads), 0, stream, wp.by_segment, (int)G, S,
+                           n_seg, wp.wt);
+        if (!forced_idx.empty())
+            hipLaunchKernelGGL(weighted::k_weight_of_cover, dim3(cells), dim3(kThreads), 0, stream, d_cov, (int)G,
+                               wp.wt, wp.sums + 1);
+        hipLaunchKernelGGL(weighted::k_weighted_gain0<SelectState>, dim3((unsigned)((G + kChunk - 1) / kChunk)),
+                           dim3(kThreads), 0, stream, d_inc, n, n_pad, (int)G, d_cov, wp.wt, d_gain, st, wp.sums);
+    } else {
+        hipLaunchKernelGGL(k_select_gain0, dim3((unsigned)((G + kChunk - 1) / kChunk)), dim3(kThreads), 0, stream,
+                           d_inc, n, n_pad, (int)G, d_cov, d_gain, st);
+    }
     SELECT_TRY(hipGetLastError());
     SELECT_TRY(hipEventRecord(ev_[1], stream));
 
@@ -414,8 +436,12 @@ int PanelSelect::rounds(const uint64_t *d_inc, const uint64_t *d_sym, int n, lon
                                (uint32_t)min_gain, tubes_mask, d_order, d_gains, d_tube, st);
             hipLaunchKernelGGL(k_select_apply, dim3(ga), dim3(kThreads), 0, stream, d_inc, n_pad, (int)G, d_cov,
                                d_touched, d_new, d_sym, n, W, d_mask, st);
-            hipLaunchKernelGGL(k_select_update, dim3(gx, gy), dim3(kThreads), 0, stream, d_inc, n, n_pad, d_touched,
-                               d_new, d_gain, st);
+            if (wts)
+                hipLaunchKernelGGL(weighted::k_weighted_update<SelectState>, dim3(gx, gy), dim3(kThreads), 0, stream,
+                                   d_inc, n, n_pad, d_touched, d_new, wp.wt, d_gain, st);
+            else
+                hipLaunchKernelGGL(k_select_update, dim3(gx, gy), dim3(kThreads), 0, stream, d_inc, n, n_pad,
+                                   d_touched, d_new, d_gain, st);
         }
         SELECT_TRY(hipGetLastError());
         SELECT_TRY(hipMemcpyAsync(&hs, st, sizeof hs, hipMemcpyDeviceToHost, stream));
@@ -441,10 +467,12 @@ int PanelSelect::rounds(const uint64_t *d_inc, const uint64_t *d_sym, int n, lon
     SELECT_TRY(hipMemcpyAsync(tube_out, d_tube, (size_t)n, hipMemcpyDeviceToHost, stream));
     SELECT_TRY(hipMemcpyAsync(flags.data(), d_flags, (size_t)n, hipMemcpyDeviceToHost, stream));
     SELECT_TRY(hipMemcpyAsync(h_mask.data(), d_mask, sizeof(uint64_t) * (size_t)n, hipMemcpyDeviceToHost, stream));
-    if (covered_out) {
+    unsigned long long h_sums[2] = {};
+    if (covered_out || wts) {   // weighted: the gains are weights, so the kept count comes from the words
         h_cov.resize((size_t)G);
         SELECT_TRY(hipMemcpyAsync(h_cov.data(), d_cov, sizeof(uint64_t) * (size_t)G, hipMemcpyDeviceToHost, stream));
     }
+    if (wts) SELECT_TRY(hipMemcpyAsync(h_sums, wp.sums, sizeof h_sums, hipMemcpyDeviceToHost, stream));
     SELECT_TRY(hipEventSynchronize(ev_[2]));
     SELECT_TRY(hipStreamSynchronize(stream));
     for (int ph = 0; ph < 2; ++ph) {
@@ -467,6 +495,12 @@ int PanelSelect::rounds(const uint64_t *d_inc, const uint64_t *d_sym, int n, lon
         const bool barred = !keep_out[p] && ((flags[(size_t)p] & kSelf) || (h_mask[(size_t)p] & tubes_mask) == tubes_mask);
         barred_ += barred;
         if (barred_out) barred_out[p] = barred ? 1 : 0;
+    }
+    if (wts) {   // kept holds weights here: the forced rows' and the picks' gains
+        if (wts->weight_all_out) *wts->weight_all_out = h_sums[0];
+        if (wts->weight_kept_out) *wts->weight_kept_out = h_sums[1] + (uint64_t)(kept - (long long)hs.covered_forced);
+        kept = 0;
+        for (long g = 0; g < G; ++g) kept += __builtin_popcountll(h_cov[(size_t)g]);
     }
     *n_picked_out = n_picked;
     if (n_tubes_used_out) *n_tubes_used_out = (int)hs.used;

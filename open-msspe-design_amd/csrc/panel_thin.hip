@@ -20,6 +20,10 @@
 // stand over it.  k_thin_colsum gives the per-segment primer counts (all, forced, kept), k_thin_depth_init the needs
 // and the first closed words, k_thin_apply_depth a round's counter bumps and the bits it closes.  Primers listed twice
 // (shadows) are masked out of every count and are never live.
+//
+// Weights (msspe_panel_thin_weighted*).  gain(p) is the sum of a weight per segment over the uncovered
+// segments of row p.  The first gains and the update run in their weighted instances (panel_weighted.hpp) over a weight
+// plane with the cell layout of the depth planes; forced, pick and apply are the kernels above, unchanged.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -28,6 +32,7 @@
 
 #include "../../include/msspe_hip.h"
 #include "panel_thin.hpp"
+#include "panel_weighted.hpp"
 
 namespace msspe {
 
@@ -48,7 +53,7 @@ struct ThinState {
     unsigned long long covered_forced;   // |OR of the forced I[p]|
 };
 
-enum { kInc, kCov, kTouched, kNew, kGain, kLive, kOrder, kForced, kDepth, kMask };   // PanelThin::buf_
+enum { kInc, kCov, kTouched, kNew, kGain, kLive, kOrder, kForced, kDepth, kMask, kWeight };   // PanelThin::buf_
 
 __device__ __forceinline__ uint64_t wave_or(uint64_t x)
 {
@@ -342,13 +347,15 @@ int PanelThin::run(MismatchCoverage &cov, const SeqView &seqs, int n_seq, size_t
                    const uint64_t *rev_words, int n_rev, const uint8_t *forced, uint8_t *keep_out, uint32_t *order_out,
                    uint32_t *gain_out, int *n_picked_out, uint8_t *covered_out, long long *covered_all_out,
                    long long *covered_kept_out, size_t max_matrix_bytes, int n_cu, hipStream_t stream,
-                   std::string &err)
+                   std::string &err, const PanelWeights *wts)
 {
     rounds_ = groups_ = 0;
     for (auto &p : phase_us_) p = 0;
     *n_picked_out = 0;
     if (covered_all_out) *covered_all_out = 0;
     if (covered_kept_out) *covered_kept_out = 0;
+    if (wts && wts->weight_all_out) *wts->weight_all_out = 0;
+    if (wts && wts->weight_kept_out) *wts->weight_kept_out = 0;
     long P = 0;
     int rc = MismatchCoverage::check(n_seq, seq_len, opt, max_mismatches, exact_3p, fwd_words, n_fwd, rev_words, n_rev,
                                      &P, err);
@@ -368,7 +375,7 @@ int PanelThin::run(MismatchCoverage &cov, const SeqView &seqs, int n_seq, size_t
                             d_inc, stream, err)))
         return rc;
     if ((rc = rounds(n, n_seg, MismatchCoverage::group_size(opt), min_gain, keep_out, order_out, gain_out,
-                     n_picked_out, covered_out, covered_all_out, covered_kept_out, n_cu, stream, err)))
+                     n_picked_out, covered_out, covered_all_out, covered_kept_out, n_cu, stream, err, wts)))
         return rc;
     float ms = 0.f;   // rounds() returned with the stream idle
     (void)hipEventElapsedTime(&ms, ev_[0], ev_[1]);
@@ -378,10 +385,14 @@ int PanelThin::run(MismatchCoverage &cov, const SeqView &seqs, int n_seq, size_t
 
 int PanelThin::rounds(int n, long n_seg, int S, int min_gain, uint8_t *keep_out, uint32_t *order_out,
                       uint32_t *gain_out, int *n_picked_out, uint8_t *covered_out, long long *covered_all_out,
-                      long long *covered_kept_out, int n_cu, hipStream_t stream, std::string &err)
+                      long long *covered_kept_out, int n_cu, hipStream_t stream, std::string &err,
+                      const PanelWeights *wts)
 {
     const long G = (n_seg + S - 1) / S;
     const size_t n_pad = ((size_t)n + 63) & ~(size_t)63;
+    if (wts)   // the sums, the plane and the weights as given: the one slot a weighted call adds
+        if (int rc = ensure(kWeight, weighted::Plane::bytes(G, n_seg), err)) return rc;
+    const weighted::Plane wp(wts ? buf_[kWeight] : nullptr, G);
     uint64_t *d_inc = (uint64_t *)buf_[kInc], *d_cov = (uint64_t *)buf_[kCov], *d_new = (uint64_t *)buf_[kNew];
     ThinState *st = (ThinState *)(d_cov + G);   // behind the covered words: 8-byte aligned
     uint32_t *d_touched = (uint32_t *)buf_[kTouched], *d_gain = (uint32_t *)buf_[kGain];
@@ -406,8 +417,22 @@ int PanelThin::rounds(int n, long n_seg, int S, int min_gain, uint8_t *keep_out,
         hipLaunchKernelGGL(k_thin_forced, dim3(blocks), dim3(kThreads), 0, stream, d_inc, n_pad, (int)G, d_forced,
                            (int)forced_idx.size(), d_cov, st);
     }
-    hipLaunchKernelGGL(k_thin_gain0, dim3((unsigned)((G + kChunk - 1) / kChunk)), dim3(kThreads), 0, stream, d_inc, n,
-                       n_pad, (int)G, d_cov, d_gain, st);
+    if (wts) {   // the plane is rewritten by every call: nothing of the last one's is read
+        const unsigned cells = (unsigned)(((size_t)G * 64 + kThreads - 1) / kThreads);
+        THIN_TRY(hipMemsetAsync(wp.sums, 0, 2 * sizeof(unsigned long long), stream));
+        THIN_TRY(hipMemcpyAsync(wp.by_segment, wts->weights, sizeof(uint32_t) * (size_t)n_seg,
+                                hipMemcpyHostToDevice, stream));
+        hipLaunchKernelGGL(weighted::k_weight_plane, dim3(cells), dim3(kThreads), 0, stream, wp.by_segment, (int)G, S,
+                           n_seg, wp.wt);
+        if (!forced_idx.empty())
+            hipLaunchKernelGGL(weighted::k_weight_of_cover, dim3(cells), dim3(kThreads), 0, stream, d_cov, (int)G,
+                               wp.wt, wp.sums + 1);
+        hipLaunchKernelGGL(weighted::k_weighted_gain0<ThinState>, dim3((unsigned)((G + kChunk - 1) / kChunk)),
+                           dim3(kThreads), 0, stream, d_inc, n, n_pad, (int)G, d_cov, wp.wt, d_gain, st, wp.sums);
+    } else {
+        hipLaunchKernelGGL(k_thin_gain0, dim3((unsigned)((G + kChunk - 1) / kChunk)), dim3(kThreads), 0, stream, d_inc,
+                           n, n_pad, (int)G, d_cov, d_gain, st);
+    }
     THIN_TRY(hipGetLastError());
     THIN_TRY(hipEventRecord(ev_[2], stream));
 
@@ -423,8 +448,12 @@ int PanelThin::rounds(int n, long n_seg, int S, int min_gain, uint8_t *keep_out,
                                d_order, d_gains, st);
             hipLaunchKernelGGL(k_thin_apply, dim3(ga), dim3(kThreads), 0, stream, d_inc, n_pad, (int)G, d_cov,
                                d_touched, d_new, st);
-            hipLaunchKernelGGL(k_thin_update, dim3(gx, gy), dim3(kThreads), 0, stream, d_inc, n, n_pad, d_touched,
-                               d_new, d_gain, st);
+            if (wts)
+                hipLaunchKernelGGL(weighted::k_weighted_update<ThinState>, dim3(gx, gy), dim3(kThreads), 0, stream,
+                                   d_inc, n, n_pad, d_touched, d_new, wp.wt, d_gain, st);
+            else
+                hipLaunchKernelGGL(k_thin_update, dim3(gx, gy), dim3(kThreads), 0, stream, d_inc, n, n_pad, d_touched,
+                                   d_new, d_gain, st);
         }
         THIN_TRY(hipGetLastError());
         THIN_TRY(hipMemcpyAsync(&hs, st, sizeof hs, hipMemcpyDeviceToHost, stream));
@@ -447,10 +476,12 @@ int PanelThin::rounds(int n, long n_seg, int S, int min_gain, uint8_t *keep_out,
         THIN_TRY(hipMemcpyAsync(gain_out, d_gains, sizeof(uint32_t) * (size_t)n_picked, hipMemcpyDeviceToHost, stream));
     }
     std::vector<uint64_t> h_cov;
-    if (covered_out) {
+    unsigned long long h_sums[2] = {};
+    if (covered_out || wts) {   // weighted: the gains are weights, so the kept count comes from the words
         h_cov.resize((size_t)G);
         THIN_TRY(hipMemcpyAsync(h_cov.data(), d_cov, sizeof(uint64_t) * (size_t)G, hipMemcpyDeviceToHost, stream));
     }
+    if (wts) THIN_TRY(hipMemcpyAsync(h_sums, wp.sums, sizeof h_sums, hipMemcpyDeviceToHost, stream));
     THIN_TRY(hipEventSynchronize(ev_[3]));
     THIN_TRY(hipStreamSynchronize(stream));
     for (int ph = 1; ph < 3; ++ph) {
@@ -467,6 +498,12 @@ int PanelThin::rounds(int n, long n_seg, int S, int min_gain, uint8_t *keep_out,
         }
         keep_out[order_out[i]] = 1;
         kept += gain_out[i];
+    }
+    if (wts) {   // kept holds weights here: the forced rows' and the picks' gains
+        if (wts->weight_all_out) *wts->weight_all_out = h_sums[0];
+        if (wts->weight_kept_out) *wts->weight_kept_out = h_sums[1] + (uint64_t)(kept - (long long)hs.covered_forced);
+        kept = 0;
+        for (long g = 0; g < G; ++g) kept += __builtin_popcountll(h_cov[(size_t)g]);
     }
     *n_picked_out = n_picked;
     if (covered_all_out) *covered_all_out = (long long)hs.covered_all;

@@ -13,6 +13,15 @@
 
 namespace msspe {
 
+// What a weighted call (msspe_panel_thin_weighted*, msspe_panel_select_weighted*) hands to
+// PanelThin::rounds / PanelSelect::rounds: the weights (host, one per segment in the order of covered_out; the caller
+// has checked that their total fits a uint32) and the two optional sums, the weight of the segments that all primers
+// cover and that the kept set covers.  With it a gain is a sum of weights and min_gain is in weight units.
+struct PanelWeights {
+    const uint32_t *weights;
+    uint64_t *weight_all_out, *weight_kept_out;
+};
+
 class PanelThin {
 public:
     // The alignment, options and primer words of MismatchCoverage::run; forced (host, optional, n_fwd + n_rev): primers
@@ -25,7 +34,8 @@ public:
             int max_mismatches, int exact_3p, int min_gain, const uint64_t *fwd_words, int n_fwd,
             const uint64_t *rev_words, int n_rev, const uint8_t *forced, uint8_t *keep_out, uint32_t *order_out,
             uint32_t *gain_out, int *n_picked_out, uint8_t *covered_out, long long *covered_all_out,
-            long long *covered_kept_out, size_t max_matrix_bytes, int n_cu, hipStream_t stream, std::string &err);
+            long long *covered_kept_out, size_t max_matrix_bytes, int n_cu, hipStream_t stream, std::string &err,
+            const PanelWeights *wts = nullptr);
     // run() in its two halves, for a caller that fills the matrix itself (msspe_panel_thin_thal*: the held incidence).
     // matrix: the buffers of a run over n primers and n_seg segments in groups of S, under the same cap; *inc_out is
     // the matrix (inc[g * n_pad + p], n_pad = n rounded up to 64, bit b = segment g * S + b), not yet written.  The
@@ -34,7 +44,7 @@ public:
     int matrix(int n, long n_seg, int S, size_t max_matrix_bytes, uint64_t **inc_out, std::string &err);
     int rounds(int n, long n_seg, int S, int min_gain, uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out,
                int *n_picked_out, uint8_t *covered_out, long long *covered_all_out, long long *covered_kept_out,
-               int n_cu, hipStream_t stream, std::string &err);
+               int n_cu, hipStream_t stream, std::string &err, const PanelWeights *wts = nullptr);
     // Depth (msspe_panel_thin_depth*): every segment keeps min(depth, primers it has) primers.  run's
     // arguments plus depth (1..255, checked by the caller); depth_all_out / depth_kept_out (optional, n_seq * P bytes):
     // representatives per segment among all and among the kept, saturating at 255; counts_out[4] (optional): segments
@@ -68,7 +78,7 @@ public:
     const long long *phase_us() const { return phase_us_; }
 
 private:
-    enum { kSlots = 10 };
+    enum { kSlots = 11 };
     void *buf_[kSlots] = {};
     size_t cap_[kSlots] = {};
     hipEvent_t ev_[4] = {};

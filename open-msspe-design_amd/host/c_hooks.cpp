@@ -68,6 +68,7 @@ int odm_parse_args(int argc, const char *const *argv, char *out, size_t cap)
           << "\nselect_by_coverage=" << a.select_by_coverage << "\nthin_panel=" << a.thin_panel << "\nthin_mismatches=" << a.thin_mismatches
           << "\nthin_3p_exact=" << a.thin_3p_exact << "\nthin_min_gain=" << a.thin_min_gain
           << "\nthin_depth=" << a.thin_depth << "\nselect_depth=" << a.select_depth
+          << "\ngenome_weights=" << a.genome_weights << "\ndefault_genome_weight=" << a.default_genome_weight
           << "\nthin_tm=" << a.thin_tm_text << "\nthin_thal=" << a.thin_thal
           << "\nseed_mismatches=" << a.seed_mismatches << "\nseed_3p_exact=" << a.seed_3p_exact
           << "\nseed_tm=" << a.seed_tm_text << "\nseed_thal=" << a.seed_thal
@@ -140,6 +141,33 @@ int odm_thin_panel(const uint64_t *rows, int n, int words, int min_gain, const u
     if (covered_out) {
         covered_out[0] = (long long)t.covered_all;
         covered_out[1] = (long long)t.covered_kept;
+    }
+    return (int)t.order.size();
+}
+
+// odm_thin_panel with weights[n_seg] (a uint32 per segment: bit s of a row) and min_gain in weight units; gains are
+// weights (uint32).  sums_out[0..3]: segments covered by all rows / by the kept ones, then the weight of each
+// (thin_panel_weighted, the sequential rule of DESIGN.md 4.17).
+int odm_thin_panel_weighted(const uint64_t *rows, int n, int words, const uint32_t *weights, int n_seg,
+                            long long min_gain, const uint8_t *forced, int *order, uint32_t *gains, uint8_t *keep,
+                            unsigned long long *sums_out)
+{
+    std::vector<std::vector<uint64_t>> r((size_t)n);
+    for (int p = 0; p < n; ++p) r[(size_t)p].assign(rows + (size_t)p * words, rows + (size_t)(p + 1) * words);
+    std::vector<char> f;
+    if (forced) f.assign(forced, forced + n);
+    WeightedSums sums;
+    const ThinResult t = thin_panel_weighted(r, std::vector<uint32_t>(weights, weights + n_seg), min_gain, f, sums);
+    for (size_t i = 0; i < t.order.size(); ++i) {
+        order[i] = t.order[i];
+        gains[i] = sums.gains[i];
+    }
+    for (int p = 0; p < n; ++p) keep[p] = (uint8_t)t.keep[(size_t)p];
+    if (sums_out) {
+        sums_out[0] = t.covered_all;
+        sums_out[1] = t.covered_kept;
+        sums_out[2] = sums.weight_all;
+        sums_out[3] = sums.weight_kept;
     }
     return (int)t.order.size();
 }
@@ -227,6 +255,50 @@ int odm_select_panel(const uint64_t *rows, int n, int words, const uint64_t *bit
         counts_out[1] = (long long)s.covered_kept;
         counts_out[2] = s.tubes_used;
         counts_out[3] = s.rounds;
+    }
+    return (int)s.order.size();
+}
+
+// odm_select_panel with weights[n_seg] and min_gain in weight units; gains are weights (uint32).  sums_out[0..5]:
+// segments covered by all rows / by the kept ones, tubes in use, rounds, then the weight covered by all rows / by the
+// kept ones (select_panel_weighted, the sequential rule of DESIGN.md 4.17).
+int odm_select_panel_weighted(const uint64_t *rows, int n, int words, const uint64_t *bitmap, const uint32_t *weights,
+                              int n_seg, int max_tubes, long long min_gain, const uint8_t *forced, int drop_self,
+                              int *order, uint32_t *gains, uint8_t *keep, int *tube, uint8_t *barred,
+                              unsigned long long *sums_out)
+{
+    std::vector<std::vector<uint64_t>> r((size_t)n);
+    for (int p = 0; p < n; ++p) r[(size_t)p].assign(rows + (size_t)p * words, rows + (size_t)(p + 1) * words);
+    std::vector<char> f;
+    if (forced) f.assign(forced, forced + n);
+    std::vector<std::string> names((size_t)n);
+    for (int p = 0; p < n; ++p) names[(size_t)p] = std::to_string(p);
+    ConflictGraph g;
+    g.nodes = names;
+    const int W = (n + 63) / 64;
+    for (int p = 0; p < n; ++p)
+        for (int u = 0; u < n; ++u)
+            if ((bitmap[(size_t)p * W + (u >> 6)] >> (u & 63)) & 1ull)
+                if (!(drop_self && p == u)) g.edges[names[(size_t)p]].insert(names[(size_t)u]);
+    WeightedSums sums;
+    const SelectResult s = select_panel_weighted(r, names, g, std::vector<uint32_t>(weights, weights + n_seg),
+                                                 max_tubes, min_gain, f, sums);
+    for (size_t i = 0; i < s.order.size(); ++i) {
+        order[i] = s.order[i];
+        gains[i] = sums.gains[i];
+    }
+    for (int p = 0; p < n; ++p) {
+        keep[p] = (uint8_t)s.keep[(size_t)p];
+        tube[p] = s.tube[(size_t)p];
+        barred[p] = (uint8_t)s.barred[(size_t)p];
+    }
+    if (sums_out) {
+        sums_out[0] = s.covered_all;
+        sums_out[1] = s.covered_kept;
+        sums_out[2] = (unsigned long long)s.tubes_used;
+        sums_out[3] = (unsigned long long)s.rounds;
+        sums_out[4] = sums.weight_all;
+        sums_out[5] = sums.weight_kept;
     }
     return (int)s.order.size();
 }

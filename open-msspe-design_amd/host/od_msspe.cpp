@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <array>
+#include <cerrno>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -89,6 +90,8 @@ const OptSpec kOpts[] = {
     {"--thin-thal", "THIN_THAL", OptSpec::Str, OFF(thin_thal)},
     {"--select-by-coverage", "SELECT_BY_COVERAGE", OptSpec::Bool, OFF(select_by_coverage)},
     {"--select-depth", "SELECT_DEPTH", OptSpec::Int, OFF(select_depth)},
+    {"--genome-weights", "GENOME_WEIGHTS", OptSpec::Str, OFF(genome_weights)},
+    {"--default-genome-weight", "DEFAULT_GENOME_WEIGHT", OptSpec::Int, OFF(default_genome_weight)},
     {"--seed-mismatches", "SEED_MISMATCHES", OptSpec::OptInt, OFF(seed_mismatches)},
     {"--seed-3p-exact", "SEED_3P_EXACT", OptSpec::Str, OFF(seed_3p_exact_text)},
     {"--seed-tm", "SEED_TM", OptSpec::Str, OFF(seed_tm_text)},
@@ -165,6 +168,12 @@ std::string Args::usage()
          "(--thin-mismatches, --thin-3p-exact, --thin-min-gain, --thin-tm, --thin-thal); the primers of\n"
          "--existing-primers are kept and bar their neighbours from every tube. Conflicts may cost segments. One\n"
          "device; not with --thin-panel true, --keep-all true or --cover-on-device true.\n"
+         "--genome-weights <FILE> makes --thin-panel true and --select-by-coverage true count a segment by the weight of\n"
+         "its genome: lines 'name,weight' (the FASTA record's name, an integer >= 0), --default-genome-weight <W>\n"
+         "(default 1) for the records not listed. A gain is the sum of the new segments' weights, --thin-min-gain is in\n"
+         "weight units, genomes of weight 0 are reported but get no primer of their own, and the block gains a 'Weight:'\n"
+         "line. All weights times the segments per genome may add up to 4294967295. Depth 1 only; not with --thin-panel\n"
+         "true --thin-tm.\n"
          "--coverage-tm <C> adds a report of the segments the final primers hold at C: every match within\n"
          "--coverage-mismatches (last --coverage-3p-exact bases exact) is scored with thal (--coverage-thal any | end1)\n"
          "against the strand the primer anneals to. One device.\n"
@@ -337,6 +346,18 @@ Args Args::parse(int argc, const char *const *argv)
                 throw UsageError("error: invalid value '" + a.thin_thal +
                                  "' for '--thin-thal <...>'\n  [possible values: any, end1]");
         }
+    }
+    if (!a.genome_weights.empty()) {
+        const bool thin = a.thin_panel == "true", select = a.select_by_coverage == "true";
+        if (!thin && !select)
+            throw UsageError("error: '--genome-weights' weighs the segments of '--thin-panel true' or "
+                             "'--select-by-coverage true' and does nothing without one of them");
+        if ((thin && a.thin_depth > 1) || (select && a.select_depth > 1))
+            throw UsageError(std::string("error: '--genome-weights' with '") + (thin ? "--thin-depth" : "--select-depth") +
+                             "' above 1 is not built yet: weights run at depth 1");
+        if (thin && a.thin_scored)
+            throw UsageError("error: '--genome-weights' with '--thin-panel true --thin-tm' is not built yet: the "
+                             "weighted thinning runs on the string rule");
     }
     if (a.seed_mismatches >= 0 || !a.seed_tm_text.empty() || !a.seed_thal.empty() || !a.seed_3p_exact_text.empty()) {
         if (!a.devices.empty())
@@ -1291,7 +1312,32 @@ ThinDepthResult thin_panel_depth(const std::vector<std::vector<uint64_t>> &rows,
     return out;
 }
 
-ThinResult thin_panel(const std::vector<std::vector<uint64_t>> &rows, int min_gain, const std::vector<char> &forced)
+// a round's gain from one word of a row: the new bits' number, or with weights (one per segment) their weights' sum
+static size_t word_gain(uint64_t bits, size_t w, const std::vector<uint32_t> *weights)
+{
+    if (!weights) return (size_t)__builtin_popcountll(bits);
+    size_t sum = 0;
+    for (; bits; bits &= bits - 1) {
+        const size_t s = w * 64 + (size_t)__builtin_ctzll(bits);
+        if (s < weights->size()) sum += (*weights)[s];
+    }
+    return sum;
+}
+
+// weight_all / weight_kept of a weighted run from the words covered by all rows and by the kept ones
+static void weigh_cover(const std::vector<uint64_t> &all, const std::vector<uint64_t> &covered,
+                        const std::vector<uint32_t> &weights, WeightedSums &sums)
+{
+    for (size_t w = 0; w < all.size(); ++w) {
+        sums.weight_all += word_gain(all[w], w, &weights);
+        sums.weight_kept += word_gain(covered[w], w, &weights);
+    }
+}
+
+// thin_panel, and with weights thin_panel_weighted: the gains go to sums->gains then, out.gains stays empty
+static ThinResult thin_panel_rule(const std::vector<std::vector<uint64_t>> &rows, long long min_gain,
+                                  const std::vector<char> &forced, const std::vector<uint32_t> *weights,
+                                  WeightedSums *sums)
 {
     const size_t n = rows.size();
     size_t words = 0;
@@ -1312,7 +1358,7 @@ ThinResult thin_panel(const std::vector<std::vector<uint64_t>> &rows, int min_ga
         for (size_t p = 0; p < n; ++p) {
             if (out.keep[p]) continue;
             size_t gain = 0;
-            for (size_t w = 0; w < words; ++w) gain += (size_t)__builtin_popcountll(word(p, w) & ~covered[w]);
+            for (size_t w = 0; w < words; ++w) gain += word_gain(word(p, w) & ~covered[w], w, weights);
             if (best < 0 || gain > best_gain) {   // ">": the lowest index among equals
                 best = (long)p;
                 best_gain = gain;
@@ -1320,7 +1366,8 @@ ThinResult thin_panel(const std::vector<std::vector<uint64_t>> &rows, int min_ga
         }
         if (best < 0 || best_gain < (size_t)min_gain) break;
         out.order.push_back((int)best);
-        out.gains.push_back((int)best_gain);
+        if (weights) sums->gains.push_back((uint32_t)best_gain);
+        else out.gains.push_back((int)best_gain);
         out.keep[(size_t)best] = 1;
         for (size_t w = 0; w < words; ++w) covered[w] |= word((size_t)best, w);
     }
@@ -1328,7 +1375,20 @@ ThinResult thin_panel(const std::vector<std::vector<uint64_t>> &rows, int min_ga
         out.covered_all += (size_t)__builtin_popcountll(all[w]);
         out.covered_kept += (size_t)__builtin_popcountll(covered[w]);
     }
+    if (weights) weigh_cover(all, covered, *weights, *sums);
     return out;
+}
+
+ThinResult thin_panel(const std::vector<std::vector<uint64_t>> &rows, int min_gain, const std::vector<char> &forced)
+{
+    return thin_panel_rule(rows, min_gain, forced, nullptr, nullptr);
+}
+
+ThinResult thin_panel_weighted(const std::vector<std::vector<uint64_t>> &rows, const std::vector<uint32_t> &weights,
+                               long long min_gain, const std::vector<char> &forced, WeightedSums &sums)
+{
+    sums = WeightedSums{};
+    return thin_panel_rule(rows, min_gain, forced, &weights, &sums);
 }
 
 // the cover's graph over the primers' indices: symmetric, a self loop kept apart
@@ -1427,8 +1487,11 @@ SelectDepthResult select_panel_depth(const std::vector<std::vector<uint64_t>> &r
     return out;
 }
 
-SelectResult select_panel(const std::vector<std::vector<uint64_t>> &rows, const std::vector<std::string> &primers,
-                          const ConflictGraph &g, int max_tubes, int min_gain, const std::vector<char> &forced)
+// select_panel, and with weights select_panel_weighted: the gains go to sums->gains then, out.gains stays empty
+static SelectResult select_panel_rule(const std::vector<std::vector<uint64_t>> &rows,
+                                      const std::vector<std::string> &primers, const ConflictGraph &g, int max_tubes,
+                                      long long min_gain, const std::vector<char> &forced,
+                                      const std::vector<uint32_t> *weights, WeightedSums *sums)
 {
     const size_t n = rows.size();
     size_t words = 0;
@@ -1459,7 +1522,7 @@ SelectResult select_panel(const std::vector<std::vector<uint64_t>> &rows, const 
         for (size_t p = 0; p < n; ++p) {
             if (out.keep[p] || self[p] || (mask[p] & all_tubes) == all_tubes) continue;
             size_t gain = 0;
-            for (size_t w = 0; w < words; ++w) gain += (size_t)__builtin_popcountll(word(p, w) & ~covered[w]);
+            for (size_t w = 0; w < words; ++w) gain += word_gain(word(p, w) & ~covered[w], w, weights);
             if (best < 0 || gain > best_gain) {   // ">": the lowest index among equals
                 best = (long)p;
                 best_gain = gain;
@@ -1470,7 +1533,8 @@ SelectResult select_panel(const std::vector<std::vector<uint64_t>> &rows, const 
         const size_t p = (size_t)best;
         const int t = __builtin_ctzll(~mask[p] & all_tubes);
         out.order.push_back((int)best);
-        out.gains.push_back((int)best_gain);
+        if (weights) sums->gains.push_back((uint32_t)best_gain);
+        else out.gains.push_back((int)best_gain);
         out.keep[p] = 1;
         out.tube[p] = t;
         out.tubes_used = std::max(out.tubes_used, t + 1);
@@ -1484,6 +1548,86 @@ SelectResult select_panel(const std::vector<std::vector<uint64_t>> &rows, const 
         out.covered_kept += (size_t)__builtin_popcountll(covered[w]);
     }
     out.covered = covered;
+    if (weights) weigh_cover(all, covered, *weights, *sums);
+    return out;
+}
+
+SelectResult select_panel(const std::vector<std::vector<uint64_t>> &rows, const std::vector<std::string> &primers,
+                          const ConflictGraph &g, int max_tubes, int min_gain, const std::vector<char> &forced)
+{
+    return select_panel_rule(rows, primers, g, max_tubes, min_gain, forced, nullptr, nullptr);
+}
+
+SelectResult select_panel_weighted(const std::vector<std::vector<uint64_t>> &rows,
+                                   const std::vector<std::string> &primers, const ConflictGraph &g,
+                                   const std::vector<uint32_t> &weights, int max_tubes, long long min_gain,
+                                   const std::vector<char> &forced, WeightedSums &sums)
+{
+    sums = WeightedSums{};
+    return select_panel_rule(rows, primers, g, max_tubes, min_gain, forced, &weights, &sums);
+}
+
+std::string weight_line(uint64_t weight_all, uint64_t weight_kept, uint64_t weight_total, size_t n_all, size_t n_kept)
+{
+    const std::string t = std::to_string(weight_total);
+    return "  Weight:   covered " + std::to_string(weight_all) + "/" + t + " by all " + std::to_string(n_all) + ", " +
+           std::to_string(weight_kept) + "/" + t + " by the kept " + std::to_string(n_kept) + "\n";
+}
+
+// a thinning or selection block with `line` put in behind its "  Segments:" line
+static std::string with_weight_line(std::string block, const std::string &line)
+{
+    const size_t at = block.find("\n  Segments:");
+    const size_t end = at == std::string::npos ? std::string::npos : block.find('\n', at + 1);
+    if (end != std::string::npos) block.insert(end + 1, line);
+    return block;
+}
+
+std::vector<uint32_t> read_genome_weights(const std::string &path, const std::vector<SequenceRecord> &records,
+                                          int default_weight, size_t partitions)
+{
+    const char *option = "--genome-weights";
+    std::ifstream f(path, std::ios::binary);
+    if (!f) throw UsageError(std::string("error: cannot read '") + path + "' for '" + option + "'");
+    const uint64_t limit = 0xFFFFFFFFull;
+    std::map<std::string, std::vector<size_t>> by_name;   // a name that several records carry applies to all of them
+    for (size_t r = 0; r < records.size(); ++r) by_name[records[r].name].push_back(r);
+    std::vector<uint32_t> out(records.size(), (uint32_t)default_weight);
+    std::vector<char> listed(records.size(), 0);
+    uint64_t total = 0;   // over the listed records' segments, line by line
+    std::string line;
+    size_t no = 0;
+    while (std::getline(f, line)) {
+        ++no;
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (line.empty()) continue;
+        const std::string where = std::string("error: '") + option + "' " + path + " line " + std::to_string(no) + ": ";
+        const size_t c = line.rfind(',');   // the weight is the last field: a record's name may hold commas
+        if (c == std::string::npos || c == 0) throw UsageError(where + "expected 'name,weight'");
+        const std::string name = line.substr(0, c), text = line.substr(c + 1);
+        char *end = nullptr;
+        errno = 0;
+        const unsigned long long x = std::strtoull(text.c_str(), &end, 10);
+        if (text.empty() || text.find_first_not_of("0123456789") != std::string::npos || *end || errno || x > limit)
+            throw UsageError(where + "weight '" + text + "' is not an integer in 0 .. " + std::to_string(limit));
+        const auto it = by_name.find(name);
+        if (it == by_name.end()) throw UsageError(where + "no record is named '" + name + "'");
+        for (const size_t r : it->second) {
+            if (listed[r]) total -= (uint64_t)out[r] * partitions;   // a name listed again: the later line holds
+            out[r] = (uint32_t)x;
+            listed[r] = 1;
+            total += x * partitions;
+        }
+        if (total > limit)
+            throw UsageError(where + "the weights add up to " + std::to_string(total) + " over " +
+                             std::to_string(partitions) + " segments per record, at most " + std::to_string(limit));
+    }
+    for (size_t r = 0; r < records.size(); ++r)
+        if (!listed[r]) total += (uint64_t)default_weight * partitions;
+    if (total > limit)
+        throw UsageError(std::string("error: '") + option + "' " + path + ": with '--default-genome-weight " +
+                         std::to_string(default_weight) + "' on the records it does not list the weights add up to " +
+                         std::to_string(total) + ", at most " + std::to_string(limit));
     return out;
 }
 
@@ -1769,7 +1913,8 @@ std::string thin_panel_on_device(Engine &eng, const DeviceAlignment &aln, std::v
                                  std::vector<KmerStat> &rev, const std::vector<std::string> &panel_f,
                                  const std::vector<std::string> &panel_r, int segment_size, int overlap_size,
                                  int window_size, int kmer_size, int max_mismatches, int exact_3p, int min_gain,
-                                 const msspe_chem *chem, int mode, float tm_threshold, int depth)
+                                 const msspe_chem *chem, int mode, float tm_threshold, int depth,
+                                 const std::vector<uint32_t> *genome_weights)
 {
     // the new primers in their lists' order (stage A's selection order: ties go to the word with more postings), the
     // panel's behind them, forced
@@ -1791,8 +1936,17 @@ std::string thin_panel_on_device(Engine &eng, const DeviceAlignment &aln, std::v
     const msspe_thin_opt thin{min_gain};
     const msspe_thin_depth_opt deep{min_gain, depth};
     long long counts[4] = {0, 0, 0, 0};   // depth above 1: covered_all / covered_kept are counts[0] / [1]
+    std::vector<uint32_t> weights;   // --genome-weights: every segment of a row weighs what its genome weighs
+    uint64_t weight_all = 0, weight_kept = 0, weight_total = 0;
+    if (genome_weights)
+        for (const uint32_t w : *genome_weights) weights.insert(weights.end(), P, w), weight_total += (uint64_t)w * P;
     const int rc =
-        depth > 1
+        genome_weights   // (depth 1, no chemistry: Args::parse refuses the rest)
+            ? msspe_panel_thin_weighted_packed_dev(eng.ctx(), aln.device(), aln.rows(), L, &opt, &mm, &thin, wf.data(),
+                                                   (int)wf.size(), wr.data(), (int)wr.size(), forced.data(),
+                                                   weights.data(), keep.data(), order.data(), gains.data(), &n_picked,
+                                                   nullptr, &covered_all, &covered_kept, &weight_all, &weight_kept)
+        : depth > 1
             ? (chem ? msspe_panel_thin_thal_depth_packed_dev(eng.ctx(), aln.device(), aln.rows(), L, &opt, &mm, &deep,
                                                              chem, mode, tm_threshold, wf.data(), (int)wf.size(),
                                                              wr.data(), (int)wr.size(), forced.data(), keep.data(),
@@ -1827,9 +1981,11 @@ std::string thin_panel_on_device(Engine &eng, const DeviceAlignment &aln, std::v
         return thin_thal_report(mode, tm_threshold, max_mismatches, exact_3p, min_gain, fwd.size(), n_f, rev.size(),
                                 n_r, panel_f.size() + panel_r.size(), (size_t)covered_all, (size_t)covered_kept,
                                 (size_t)aln.rows() * P, depth, (size_t)counts[2], (size_t)counts[3]);
-    return thin_report(max_mismatches, exact_3p, min_gain, fwd.size(), n_f, rev.size(), n_r,
-                       panel_f.size() + panel_r.size(), (size_t)covered_all, (size_t)covered_kept,
-                       (size_t)aln.rows() * P, depth, (size_t)counts[2], (size_t)counts[3]);
+    const std::string block = thin_report(max_mismatches, exact_3p, min_gain, fwd.size(), n_f, rev.size(), n_r,
+                                          panel_f.size() + panel_r.size(), (size_t)covered_all, (size_t)covered_kept,
+                                          (size_t)aln.rows() * P, depth, (size_t)counts[2], (size_t)counts[3]);
+    if (!genome_weights) return block;
+    return with_weight_line(block, weight_line(weight_all, weight_kept, weight_total, n_f + n_r, fwd.size() + rev.size()));
 }
 
 std::string select_report(int mode, float tm_threshold, int max_mismatches, int exact_3p, int min_gain, int max_tubes,
@@ -1866,7 +2022,8 @@ std::string select_panel_on_device(Engine &eng, const DeviceAlignment &aln, cons
                                    bool screen, bool drop_self_pairs, float dg_threshold, std::vector<KmerStat> &kept_f,
                                    std::vector<KmerStat> &kept_r, std::map<std::string, int> &tubes,
                                    const std::function<void(const KmerStat &, bool)> &dropped,
-                                   const NtthalOptions *end_rule, int depth)
+                                   const NtthalOptions *end_rule, int depth,
+                                   const std::vector<uint32_t> *genome_weights)
 {
     // the graph's nodes are distinct words: the panel's first, then the new primers in their lists' order; a word met
     // again (the other direction's list) is not offered
@@ -1897,6 +2054,8 @@ std::string select_panel_on_device(Engine &eng, const DeviceAlignment &aln, cons
     const size_t P = L < (size_t)segment_size ? 0 : (L - (size_t)segment_size) / (size_t)overlap_size + 1;
     const auto wf = pack_words(eng, all_f, kmer_size), wr = pack_words(eng, all_r, kmer_size);
     void *d_pool = nullptr, *d_bitmap = nullptr;
+    std::vector<uint32_t> weights;   // --genome-weights: every segment of a row weighs what its genome weighs
+    uint64_t weight_all = 0, weight_kept = 0, weight_total = 0;
     int rc = MSSPE_OK;
     if (n) {
         const std::vector<uint64_t> zero(n * W, 0);
@@ -1932,7 +2091,16 @@ std::string select_panel_on_device(Engine &eng, const DeviceAlignment &aln, cons
         const msspe_seed_rule rule{max_mismatches, exact_3p, mode, mode ? &chem : nullptr, tm_threshold};
         const msspe_select_opt so{min_gain, max_tubes, drop_self_pairs ? 1 : 0};
         const msspe_select_depth_opt deep{min_gain, max_tubes, drop_self_pairs ? 1 : 0, depth};
-        rc = depth <= 1
+        if (genome_weights)
+            for (const uint32_t w : *genome_weights) weights.insert(weights.end(), P, w), weight_total += (uint64_t)w * P;
+        rc = genome_weights   // (depth 1: Args::parse refuses the rest)
+                 ? msspe_panel_select_weighted_packed_dev(eng.ctx(), aln.device(), aln.rows(), L, &opt, &rule, &so,
+                                                          wf.data(), (int)wf.size(), wr.data(), (int)wr.size(),
+                                                          forced.data(), static_cast<const uint64_t *>(d_bitmap),
+                                                          weights.data(), keep.data(), order.data(), gains.data(),
+                                                          &n_picked, tube.data(), barred.data(), nullptr, &covered_all,
+                                                          &covered_kept, &used, &weight_all, &weight_kept)
+             : depth <= 1
                  ? msspe_panel_select_packed_dev(eng.ctx(), aln.device(), aln.rows(), L, &opt, &rule, &so, wf.data(),
                                                  (int)wf.size(), wr.data(), (int)wr.size(), forced.data(),
                                                  static_cast<const uint64_t *>(d_bitmap), keep.data(), order.data(),
@@ -1968,10 +2136,14 @@ std::string select_panel_on_device(Engine &eng, const DeviceAlignment &aln, cons
     for (size_t i = 0; i < rev.size(); ++i)
         if (kept_of_r[i]) kept_r.push_back(rev[i]);
         else dropped(rev[i], barred_r[i] != 0);
-    return select_report(mode, tm_threshold, max_mismatches, exact_3p, min_gain, max_tubes, kept_f.size(), fwd.size(),
-                         kept_r.size(), rev.size(), n - new_f - new_r, n_barred, (size_t)covered_all,
-                         (size_t)covered_kept, (size_t)aln.rows() * P, list_tubes ? &per_tube : nullptr, depth,
-                         (size_t)counts[2], (size_t)counts[3]);
+    const std::string block =
+        select_report(mode, tm_threshold, max_mismatches, exact_3p, min_gain, max_tubes, kept_f.size(), fwd.size(),
+                      kept_r.size(), rev.size(), n - new_f - new_r, n_barred, (size_t)covered_all, (size_t)covered_kept,
+                      (size_t)aln.rows() * P, list_tubes ? &per_tube : nullptr, depth, (size_t)counts[2],
+                      (size_t)counts[3]);
+    if (!genome_weights) return block;
+    return with_weight_line(block, weight_line(weight_all, weight_kept, weight_total, fwd.size() + rev.size(),
+                                               kept_f.size() + kept_r.size()));
 }
 
 DeviceBackground::DeviceBackground(Engine &eng, const std::vector<SequenceRecord> &records)
@@ -2328,7 +2500,7 @@ Selection select_primers(Engine &eng, const DeviceAlignment &aln, const Args &ar
                          const NtthalOptions &opts, std::unique_ptr<DeviceBackground> &background,
                          const std::vector<std::string> &panel_f, const std::vector<std::string> &panel_r,
                          const std::vector<std::string> &excl_f, const std::vector<std::string> &excl_r, int round,
-                         PhaseTimer &timer)
+                         PhaseTimer &timer, const std::vector<uint32_t> *genome_weights)
 {
     Selection sel;
     auto reject = [&](const KmerStat &s, const char *reason) {
@@ -2421,7 +2593,7 @@ Selection select_primers(Engine &eng, const DeviceAlignment &aln, const Args &ar
             std::max(1, args.tubes), args.tubes > 0, cfg.check_cross_dimers, !cfg.check_self_dimers, opts.dg,
             sel.good_f, sel.good_r, sel.tubes,
             [&](const KmerStat &s, bool barred) { reject(s, barred ? "select_conflict" : "select_unneeded"); }, &opts,
-            args.select_depth);
+            args.select_depth, genome_weights);
         timer.lap("stage C + selection by coverage");
         return sel;
     }
@@ -2468,6 +2640,13 @@ int run(const Args &args, std::string &stdout_text)
         records = read_records(args.input);
     }
     if (records.empty()) throw Panic("No sequences found in the input file");
+    std::vector<uint32_t> genome_weights;   // --genome-weights: a bad file is a usage error before the device is touched
+    if (!args.genome_weights.empty()) {
+        size_t L = 0;   // the alignment's length and its partitions, as DeviceAlignment and the calls count them
+        for (const auto &r : records) L = std::max(L, r.sequence.size());
+        const size_t P = L < (size_t)args.window_size ? 0 : (L - (size_t)args.window_size) / (size_t)args.overlap_size + 1;
+        genome_weights = read_genome_weights(args.genome_weights, records, args.default_genome_weight, P);
+    }
     timer.lap("read + to_records");
 
     const int auto_mm = (int)std::min<size_t>(10, std::max<size_t>(1, (records.size() + 49) / 50));
@@ -2516,7 +2695,8 @@ int run(const Args &args, std::string &stdout_text)
     std::vector<std::string> kept_f(panel_f), kept_r(panel_r), ban_f(banned.first), ban_r(banned.second);
     std::string rounds_text;
     for (int round = 0;; ++round) {
-        Selection s = select_primers(eng, aln, args, cfg, opts, background, kept_f, kept_r, ban_f, ban_r, round, timer);
+        Selection s = select_primers(eng, aln, args, cfg, opts, background, kept_f, kept_r, ban_f, ban_r, round, timer,
+                                     genome_weights.empty() ? nullptr : &genome_weights);
         for (const auto &p : s.good_f) kept_f.push_back(p.word);
         for (const auto &p : s.good_r) kept_r.push_back(p.word);
         for (const auto &r : s.rejected) (r.direction == SEQ_DIR_FWD ? ban_f : ban_r).push_back(r.word);
@@ -2557,7 +2737,8 @@ int run(const Args &args, std::string &stdout_text)
         thin_text = thin_panel_on_device(eng, aln, good_f, good_r, panel_f, panel_r, args.window_size, args.overlap_size,
                                          args.search_windows_size, args.kmer_size, args.thin_mismatches,
                                          args.thin_3p_exact, args.thin_min_gain, args.thin_scored ? &thin_chem : nullptr,
-                                         args.thin_thal == "end1" ? 2 : 1, args.thin_tm, args.thin_depth);
+                                         args.thin_thal == "end1" ? 2 : 1, args.thin_tm, args.thin_depth,
+                                         genome_weights.empty() ? nullptr : &genome_weights);
         timer.lap("panel thinning");
     }
     // the report covers the panel and the new primers together; the CSV lists the new ones, numbered on from the panel

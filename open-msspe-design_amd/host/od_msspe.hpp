@@ -115,6 +115,13 @@ struct Args {
     // the segments that still have fewer than r (msspe_panel_select_depth_packed_dev); the block's
     // first line gains ", depth R" and the thinning's "Depth:" line follows "Segments:".  1: nothing changes.
     int select_depth = 1;
+    // --genome-weights <file> (with --thin-panel true at depth 1 without --thin-tm, or --select-by-coverage true at
+    // depth 1): lines "name,weight" give every segment of the FASTA records of that name an integer weight >= 0, the
+    // records not listed --default-genome-weight; the thinning / the selection of every round then runs on weights
+    // (msspe_panel_thin_weighted_packed_dev / msspe_panel_select_weighted_packed_dev), --thin-min-gain
+    // is in weight units, and the block gains a "Weight:" line behind "Segments:".  Empty: nothing changes.
+    std::string genome_weights;
+    int default_genome_weight = 1;
     // --seed-mismatches M: a round that seeds stage A (with --existing-primers, and rounds >= 1 of --repick-rounds)
     // seeds it on what the panel COVERS -- every segment of the direction in which a panel primer has a match within M
     // mismatches, its last seed_3p_exact bases exact (msspe_kmer_candidates_both_tolerant_packed_dev) -- instead of
@@ -313,6 +320,24 @@ struct ThinResult {
     size_t covered_all = 0, covered_kept = 0;
 };
 ThinResult thin_panel(const std::vector<std::vector<uint64_t>> &rows, int min_gain, const std::vector<char> &forced);
+// --genome-weights (engine extension): the same rules on a weight per segment (weights[s] for bit s of a
+// row, 0 past its end): a gain is the sum of the new segments' weights, min_gain is in weight units.  The gains are
+// weights and go to sums.gains (the result's own gains stay empty); weight_all / weight_kept: the weight of the
+// segments covered by all rows and by the kept ones.  covered_all / covered_kept stay counts of segments.  The
+// device's independent twins.
+struct WeightedSums {
+    std::vector<uint32_t> gains;
+    uint64_t weight_all = 0, weight_kept = 0;
+};
+ThinResult thin_panel_weighted(const std::vector<std::vector<uint64_t>> &rows, const std::vector<uint32_t> &weights,
+                               long long min_gain, const std::vector<char> &forced, WeightedSums &sums);
+// "  Weight:   covered A/T by all Y, K/T by the kept X": the line a weighted block carries behind "  Segments:"
+std::string weight_line(uint64_t weight_all, uint64_t weight_kept, uint64_t weight_total, size_t n_all, size_t n_kept);
+// --genome-weights: a weight per record from lines "name,weight" (records not listed: default_weight).  A line that is
+// not "name,weight" with an integer weight in 0 .. 2^32 - 1, a name no record carries, and a total over the records'
+// `partitions` segments each above 2^32 - 1 are usage errors that name the line.
+std::vector<uint32_t> read_genome_weights(const std::string &path, const std::vector<SequenceRecord> &records,
+                                          int default_weight, size_t partitions);
 // --thin-depth (engine extension): the sequential rule of DESIGN.md 4.15 over incidence rows (as thin_panel's).
 // shadow[p]: p repeats a word of its direction and counts in nothing (thin_shadows marks them: among equal words all
 // but the forced one of lowest index, or without a forced one the lowest index).  Every segment needs
@@ -349,6 +374,11 @@ struct SelectResult {
 };
 SelectResult select_panel(const std::vector<std::vector<uint64_t>> &rows, const std::vector<std::string> &primers,
                           const ConflictGraph &g, int max_tubes, int min_gain, const std::vector<char> &forced);
+// select_panel on a weight per segment: thin_panel_weighted's conventions (sums.gains, weight_all, weight_kept)
+SelectResult select_panel_weighted(const std::vector<std::vector<uint64_t>> &rows,
+                                   const std::vector<std::string> &primers, const ConflictGraph &g,
+                                   const std::vector<uint32_t> &weights, int max_tubes, long long min_gain,
+                                   const std::vector<char> &forced, WeightedSums &sums);
 // --select-depth R (engine extension): the layered rule of DESIGN.md 4.16 over the same rows and graph, n_seg segments
 // (bits of a row).  cnt[s] = kept primers that match s, from the forced rows on; layers r = 1 .. min(R, max(1, deepest
 // segment)): in layer r a segment is open while cnt < min(r, primers that match it), a round picks the live primer
@@ -370,7 +400,9 @@ SelectDepthResult select_panel_depth(const std::vector<std::vector<uint64_t>> &r
 // current panel (forced) are screened as one pool (msspe_cross_dimer_dev, bitmap only; screen false: no edges) and
 // selected by one msspe_panel_select_packed_dev.  The kept primers are appended to kept_f / kept_r in their lists'
 // order with their tubes in `tubes`; dropped(primer, barred) is called for every other one.  A word met a second time
-// (the other direction's list, the panel) is not offered.  Returns select_report's block.
+// (the other direction's list, the panel) is not offered.  Returns select_report's block.  genome_weights
+// (--genome-weights: a weight per row of the alignment, depth 1): msspe_panel_select_weighted_packed_dev instead, and
+// the block carries weight_line behind "Segments:".
 std::string select_panel_on_device(Engine &eng, const DeviceAlignment &aln, const std::vector<KmerStat> &fwd,
                                    const std::vector<KmerStat> &rev, const std::vector<std::string> &panel_f,
                                    const std::vector<std::string> &panel_r, int segment_size, int overlap_size,
@@ -379,7 +411,8 @@ std::string select_panel_on_device(Engine &eng, const DeviceAlignment &aln, cons
                                    bool screen, bool drop_self_pairs, float dg_threshold, std::vector<KmerStat> &kept_f,
                                    std::vector<KmerStat> &kept_r, std::map<std::string, int> &tubes,
                                    const std::function<void(const KmerStat &, bool)> &dropped,
-                                   const NtthalOptions *end_rule = nullptr, int depth = 1);
+                                   const NtthalOptions *end_rule = nullptr, int depth = 1,
+                                   const std::vector<uint32_t> *genome_weights = nullptr);
 // "Panel selection by coverage (<the match rule>, gain >= G, tubes <= T):", the rule line, the primers kept of those
 // offered (forced ones apart), the primers barred, the segments covered (mode 0) or held (modes 1, 2) by all of them
 // and by the kept ones, and with per_tube the primers per tube; depth above 1 (--select-depth R): ", depth R" closes
@@ -390,13 +423,14 @@ std::string select_report(int mode, float tm_threshold, int max_mismatches, int 
                           const std::vector<size_t> *per_tube, int depth = 1, size_t deep_all = 0,
                           size_t deep_kept = 0);
 // the same rule as one msspe_panel_thin_packed_dev call on the resident alignment: fwd / rev are thinned in place,
-// the panel's primers are forced; returns the report's block
+// the panel's primers are forced; returns the report's block.  genome_weights (--genome-weights: a weight per row of
+// the alignment; depth 1, no chemistry): msspe_panel_thin_weighted_packed_dev instead, and the block carries weight_line
 std::string thin_panel_on_device(Engine &eng, const DeviceAlignment &aln, std::vector<KmerStat> &fwd,
                                  std::vector<KmerStat> &rev, const std::vector<std::string> &panel_f,
                                  const std::vector<std::string> &panel_r, int segment_size, int overlap_size,
                                  int window_size, int kmer_size, int max_mismatches, int exact_3p, int min_gain,
                                  const msspe_chem *chem = nullptr, int mode = 1, float tm_threshold = 0.0f,
-                                 int depth = 1);
+                                 int depth = 1, const std::vector<uint32_t> *genome_weights = nullptr);
 // depth above 1 (--thin-depth R): msspe_panel_thin_depth_packed_dev / msspe_panel_thin_thal_depth_packed_dev instead;
 // the block's first line gains ", depth R" and a line "  Depth:    at least R primers on u/t segments by all Y, on
 // v/t by the kept X" follows "Segments:" (thin_report / thin_thal_report with depth, deep_all = u, deep_kept = v).

@@ -48,6 +48,8 @@ EXPORTS = [
     "msspe_panel_select_rule",
     "msspe_panel_select_depth", "msspe_panel_select_depth_bitmap", "msspe_panel_select_depth_dev",
     "msspe_panel_select_depth_packed_dev", "msspe_panel_select_depth_rule",
+    "msspe_panel_thin_weighted", "msspe_panel_thin_weighted_dev", "msspe_panel_thin_weighted_packed_dev",
+    "msspe_panel_select_weighted_dev", "msspe_panel_select_weighted_packed_dev", "msspe_panel_select_weighted_rule",
     "msspe_device_put_stream_packed", "msspe_background_sites_packed_dev", "msspe_background_sites",
     "msspe_background_thal_packed_dev", "msspe_background_thal",
     "msspe_background_amplicons_packed_dev", "msspe_background_amplicons",
@@ -368,6 +370,15 @@ def load_library() -> C.CDLL:
     L.msspe_panel_select_depth_bitmap.argtypes = depth_in + [vp] + depth_out
     L.msspe_panel_select_depth.argtypes = depth_in + [C.POINTER(Chem), C.c_float] + depth_out
     L.msspe_panel_select_depth_rule.argtypes = depth_in + [C.POINTER(Chem), rulep] + depth_out
+    # the weighted forms: the sibling's arguments with the weights behind the inputs and the two weight sums last
+    wsums = [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.msspe_panel_thin_weighted.argtypes = (L.msspe_panel_thin.argtypes[:12] + [vp] +
+                                            L.msspe_panel_thin.argtypes[12:] + wsums)
+    L.msspe_panel_thin_weighted_dev.argtypes = L.msspe_panel_thin_weighted.argtypes
+    L.msspe_panel_thin_weighted_packed_dev.argtypes = L.msspe_panel_thin_weighted.argtypes
+    L.msspe_panel_select_weighted_dev.argtypes = select_in + [vp, vp] + select_out + wsums
+    L.msspe_panel_select_weighted_packed_dev.argtypes = select_in + [vp, vp] + select_out + wsums
+    L.msspe_panel_select_weighted_rule.argtypes = select_in + [C.POINTER(Chem), rulep, vp] + select_out + wsums
     L.msspe_device_put_stream_packed.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int,
                                                  C.POINTER(vp), C.POINTER(C.c_size_t), vp]
     L.msspe_background_sites_packed_dev.argtypes = [vp, vp, C.c_size_t, C.c_int, C.POINTER(MismatchOpt), u64p, C.c_int,
@@ -1267,8 +1278,28 @@ class Engine:
         return self._panel_thin(fn, (C.byref(chem), self._thal_mode(mode), tm_threshold), genomes, opt, fwd, rev,
                                 max_mismatches, exact_3p, min_gain, forced, form, depth)
 
+    @staticmethod
+    def _segment_weights(weights, n_seg: int) -> np.ndarray:
+        w = np.asarray(weights)
+        if w.size != n_seg:
+            raise ValueError("weights needs one entry per segment (n_seq * P)")
+        if w.size and (w.min() < 0 or w.max() > 0xFFFFFFFF):
+            raise ValueError("a weight must fit a uint32")
+        return np.ascontiguousarray(w.reshape(-1), dtype=np.uint32)
+
+    def panel_thin_weighted(self, genomes, opt: KmerOpt, fwd, rev, max_mismatches: int, exact_3p: int, weights,
+                            min_gain: int = 1, forced=None, form: str = "host"):
+        """panel_thin on a weight per segment (msspe_panel_thin_weighted*): a gain is the sum of weights over the new
+        segments, min_gain is in weight units.  weights: n_seq * P non-negative integers (any shape), their total at
+        most 2^32 - 1.  Arguments and forms as panel_thin.  Returns (keep uint8[n], order, gains, covered uint8
+        (n_seq, P), covered_all, covered_kept, weight_all, weight_kept)."""
+        fn = {"host": self.L.msspe_panel_thin_weighted, "dev": self.L.msspe_panel_thin_weighted_dev,
+              "packed": self.L.msspe_panel_thin_weighted_packed_dev}[form]
+        return self._panel_thin(fn, (), genomes, opt, fwd, rev, max_mismatches, exact_3p, min_gain, forced, form,
+                                weights=weights)
+
     def _panel_thin(self, fn, scoring, genomes, opt, fwd, rev, max_mismatches, exact_3p, min_gain, forced, form,
-                    depth=None):
+                    depth=None, weights=None):
         owned = None
         if isinstance(genomes, tuple):
             if form == "host":
@@ -1301,7 +1332,14 @@ class Engine:
             covered = np.zeros((n_seq, P), dtype=np.uint8)
             n_picked, c_all, c_kept = C.c_int(0), C.c_longlong(0), C.c_longlong(0)
             mm = MismatchOpt(max_mismatches, exact_3p)
-            if depth is None:
+            extra_in = ()
+            if weights is not None:
+                w = self._segment_weights(weights, n_seq * P)
+                w_all, w_kept = C.c_uint64(0), C.c_uint64(0)
+                thin = ThinOpt(min_gain)
+                extra_in = (w.ctypes.data,)
+                outs = (covered.ctypes.data, C.byref(c_all), C.byref(c_kept), C.byref(w_all), C.byref(w_kept))
+            elif depth is None:
                 thin = ThinOpt(min_gain)
                 outs = (covered.ctypes.data, C.byref(c_all), C.byref(c_kept))
             else:
@@ -1311,11 +1349,14 @@ class Engine:
                 outs = (covered.ctypes.data, depth_kept.ctypes.data, counts)
             self._check(fn(self.ptr, seqs_arg, n_seq, seq_len, C.byref(opt), C.byref(mm), C.byref(thin), *scoring,
                            f.ctypes.data, len(f), r.ctypes.data, len(r),
-                           flags.ctypes.data if flags is not None else None, keep.ctypes.data, order.ctypes.data,
-                           gains.ctypes.data, C.byref(n_picked), *outs))
+                           flags.ctypes.data if flags is not None else None, *extra_in, keep.ctypes.data,
+                           order.ctypes.data, gains.ctypes.data, C.byref(n_picked), *outs))
         finally:
             if owned is not None:
                 self.device_free(owned)
+        if weights is not None:
+            return (keep, order[:n_picked.value].copy(), gains[:n_picked.value].copy(), covered, int(c_all.value),
+                    int(c_kept.value), int(w_all.value), int(w_kept.value))
         if depth is not None:
             return (keep, order[:n_picked.value].copy(), gains[:n_picked.value].copy(), covered, depth_kept,
                     np.array(list(counts), dtype=np.int64))
@@ -1338,9 +1379,24 @@ class Engine:
         return self._panel_select(None, genomes, opt, fwd, rev, rule, bitmap, max_tubes, min_gain, drop_self_pairs,
                                   forced, form, chem, threshold, end_tm_threshold)
 
+    def panel_select_weighted(self, genomes, opt: KmerOpt, fwd, rev, rule: SeedRule, weights, bitmap=None,
+                              max_tubes: int = 1, min_gain: int = 1, drop_self_pairs: bool = False, forced=None,
+                              form: str = "dev", chem: Chem | None = None, threshold: float | None = -9000.0,
+                              end_tm_threshold: float | None = None):
+        """panel_select on a weight per segment (msspe_panel_select_weighted*): a gain is the sum of weights over the
+        new segments, min_gain is in weight units.  weights: n_seq * P non-negative integers (any shape), their total
+        at most 2^32 - 1.  Arguments as panel_select; form "dev" / "packed" (bitmap: a host array or a device address)
+        or "screen" (msspe_panel_select_weighted_rule: ANY at threshold, END at end_tm_threshold, either may be None).
+        Returns panel_select's dict plus weight_all and weight_kept."""
+        if form not in ("dev", "packed", "screen"):
+            raise ValueError("form must be 'dev', 'packed' or 'screen'")
+        return self._panel_select(None, genomes, opt, fwd, rev, rule, bitmap, max_tubes, min_gain, drop_self_pairs,
+                                  forced, form, chem, threshold, end_tm_threshold, weights=weights)
+
     def _panel_select(self, _depth, genomes, opt, fwd, rev, rule, bitmap, max_tubes, min_gain, drop_self_pairs, forced,
-                      form, chem, threshold, end_tm_threshold):
-        """panel_select (_depth None) and panel_select_depth: the same inputs, the calls' own outputs."""
+                      form, chem, threshold, end_tm_threshold, weights=None):
+        """panel_select (_depth None) and panel_select_depth: the same inputs, the calls' own outputs; with weights,
+        panel_select_weighted."""
         if form not in ("bitmap", "dev", "packed", "screen"):
             raise ValueError("form must be 'bitmap', 'dev', 'packed' or 'screen'")
         f, r = _words(fwd), _words(rev)
@@ -1368,7 +1424,7 @@ class Engine:
             if form == "screen":
                 chem = chem or Chem.ntthal()
                 graph = (C.byref(chem), C.c_float(threshold))
-                if end_tm_threshold is not None:
+                if end_tm_threshold is not None or weights is not None:   # the weighted screen takes the rule only
                     conflict_rule = ConflictRule.of(threshold, end_tm_threshold)
                     graph = (C.byref(chem), C.byref(conflict_rule))
             elif isinstance(bitmap, (int, np.integer)) and form != "bitmap":
@@ -1391,6 +1447,9 @@ class Engine:
                 fn = self.L.msspe_panel_select_rule
             if _depth is not None:
                 fn = getattr(self.L, fn.__name__.replace("msspe_panel_select", "msspe_panel_select_depth"))
+            if weights is not None:
+                fn = {"dev": self.L.msspe_panel_select_weighted_dev, "packed": self.L.msspe_panel_select_weighted_packed_dev,
+                      "screen": self.L.msspe_panel_select_weighted_rule}[form]
             P = 0 if seq_len < opt.segment_size else (seq_len - opt.segment_size) // opt.overlap_size + 1
             flags = None if forced is None else np.ascontiguousarray(np.asarray(forced) != 0, dtype=np.uint8)
             if flags is not None and flags.shape != (n,):
@@ -1419,14 +1478,25 @@ class Engine:
                         "depth_all": depth_all, "depth_kept": depth_kept,
                         "counts": np.array(list(counts), dtype=np.int64), "tubes_used": int(used.value)}
             sel = SelectOpt(min_gain, max_tubes, 1 if drop_self_pairs else 0)
+            extra_in, extra_out = (), ()
+            if weights is not None:
+                w = self._segment_weights(weights, n_seq * P)
+                w_all, w_kept = C.c_uint64(0), C.c_uint64(0)
+                extra_in, extra_out = (w.ctypes.data,), (C.byref(w_all), C.byref(w_kept))
             self._check(fn(self.ptr, seqs_arg, n_seq, seq_len, C.byref(opt), C.byref(rule), C.byref(sel),
                            f.ctypes.data, len(f), r.ctypes.data, len(r),
-                           flags.ctypes.data if flags is not None else None, *graph, keep.ctypes.data,
+                           flags.ctypes.data if flags is not None else None, *graph, *extra_in, keep.ctypes.data,
                            order.ctypes.data, gains.ctypes.data, C.byref(n_picked), tube.ctypes.data,
-                           barred.ctypes.data, covered.ctypes.data, C.byref(c_all), C.byref(c_kept), C.byref(used)))
+                           barred.ctypes.data, covered.ctypes.data, C.byref(c_all), C.byref(c_kept), C.byref(used),
+                           *extra_out))
         finally:
             for d in owned:
                 self.device_free(d)
+        if weights is not None:
+            return {"keep": keep, "order": order[:n_picked.value].copy(), "gains": gains[:n_picked.value].copy(),
+                    "tube": tube[:n].copy(), "barred": barred[:n].copy(), "covered": covered,
+                    "covered_all": int(c_all.value), "covered_kept": int(c_kept.value), "tubes_used": int(used.value),
+                    "weight_all": int(w_all.value), "weight_kept": int(w_kept.value)}
         return {"keep": keep, "order": order[:n_picked.value].copy(), "gains": gains[:n_picked.value].copy(),
                 "tube": tube[:n].copy(), "barred": barred[:n].copy(), "covered": covered,
                 "covered_all": int(c_all.value), "covered_kept": int(c_kept.value), "tubes_used": int(used.value)}
