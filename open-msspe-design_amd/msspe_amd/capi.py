@@ -1423,10 +1423,13 @@ class Engine:
                     seqs_arg = C.c_void_p(owned[-1])
             if form == "screen":
                 chem = chem or Chem.ntthal()
-                graph = (C.byref(chem), C.c_float(threshold))
                 if end_tm_threshold is not None or weights is not None:   # the weighted screen takes the rule only
                     conflict_rule = ConflictRule.of(threshold, end_tm_threshold)
                     graph = (C.byref(chem), C.byref(conflict_rule))
+                elif threshold is None:
+                    raise ValueError("form='screen' needs a threshold, an end_tm_threshold or both")
+                else:
+                    graph = (C.byref(chem), C.c_float(threshold))
             elif isinstance(bitmap, (int, np.integer)) and form != "bitmap":
                 graph = (C.c_void_p(int(bitmap)),)
             else:

@@ -396,6 +396,24 @@ def test_the_call_that_screens_itself_under_a_rule(m, eng, grid13):
             sm.check_independent(got, B)
 
 
+def test_the_call_that_screens_itself_under_the_end_rule_alone(m, eng, grid13):
+    """threshold None, end_tm_threshold set: the binding documents it, and built a c_float(None) before it looked at the
+    rule (found when the third session campaign began to draw the three shapes of the rule)."""
+    g, fwd, rev, I = grid13
+    opt = m.KmerOpt(400, 170, 50, 13, 0, 0)
+    chem = m.Chem.ntthal()
+    w = draw_weights(np.random.default_rng(12), 130)
+    B = sm.unpack_bitmap(eng.conflict_graph(fwd + rev, chem, m.ConflictRule.of(None, 20.0))["bitmap"], 130)
+    assert 0 < B.sum() < 130 * 130
+    want = wm.select_weighted(I, B, w, 3)
+    got = eng.panel_select_weighted(g, opt, fwd, rev, m.seed_rule(2, 3), w, None, 3, form="screen", chem=chem,
+                                    threshold=None, end_tm_threshold=20.0)
+    agree(got, want, "END alone", THIN_KEYS + ("tube", "barred"))
+    sm.check_independent(got, B)
+    with pytest.raises(ValueError):                 # no rule at all has no unweighted form to fall to
+        eng.panel_select(g, opt, fwd, rev, m.seed_rule(2, 3), None, 3, form="screen", chem=chem, threshold=None)
+
+
 def test_argument_errors(m, eng, grid13):
     g, fwd, rev, I = grid13
     L = m.load_library()

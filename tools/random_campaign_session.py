@@ -6,9 +6,12 @@ output buffers and under engine options, each against the oracle or the family's
 and the first three calls once more at the end.  --campaign 2 drives the second campaign instead
 (tests/session_campaign2_model.py): decision-only screens through the bound chain, the bound diagnostic planes, coverage
 and thinning scored with thal, excluding and tolerant stage A and the selection by coverage, chained with the calls whose
-device state they share.
-usage: random_campaign_session.py [seed] [sessions] [--campaign 1|2] [--models-only] [--only INDEX]
-  --campaign N   1 (default): tests/session_campaign_model.py; 2: tests/session_campaign2_model.py
+device state they share.  --campaign 3 drives the third (tests/session_campaign3_model.py): thinning and selection to a
+coverage depth, weighted coverage, the conflict graph under both rules with the rule forms of cover, tubes and select,
+the windowed bound first stage and the one slab loop of the thal-scored passes, chained in the same way.
+usage: random_campaign_session.py [seed] [sessions] [--campaign 1|2|3] [--models-only] [--only INDEX]
+  --campaign N   1 (default): tests/session_campaign_model.py; 2: tests/session_campaign2_model.py;
+                 3: tests/session_campaign3_model.py
   --models-only  no engine: every schedule and expected value, the model time per call and the counters per session
   --only INDEX   run the schedule up to and including call INDEX and check only that call"""
 import sys
@@ -22,9 +25,11 @@ args = sys.argv[1:]
 models_only = "--models-only" in args
 only = int(args[args.index("--only") + 1]) if "--only" in args else None
 campaign = int(args[args.index("--campaign") + 1]) if "--campaign" in args else 1
-if campaign not in (1, 2):
-    sys.exit("--campaign takes 1 or 2")
-if campaign == 2:
+if campaign not in (1, 2, 3):
+    sys.exit("--campaign takes 1, 2 or 3")
+if campaign == 3:
+    import session_campaign3_model as scm
+elif campaign == 2:
     import session_campaign2_model as scm
 else:
     import session_campaign_model as scm
