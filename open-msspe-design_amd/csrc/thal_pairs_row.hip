@@ -45,6 +45,7 @@
 #include "row_bound_pinned.inc"
 #include "row_bound_packed_pinned.inc"
 #include "row_bound_window_pinned.inc"
+#include "row_bound_window_pair_pinned.inc"
 
 
 namespace msspe {
@@ -885,6 +886,22 @@ static __device__ __forceinline__ void window_scan(const v32i Wa, const v16i Wb,
                    [TOFF] "n"((int)offsetof(SharedRow, T)), MSSPE_BWN13_TUPLES_IN(Wa, Wb, Wc)
                  : MSSPE_BWN13_SCAN_CLOBBERS);
 }
+// Two cells A, B of one row in one pass (tools/gen_row_bound_packed_asm.py --window F --pair): the scalars are the row's,
+// the entry tree and every chunk's tests run once for both, the two cells' table reads share one pipeline.
+static_assert(MSSPE_BWP13_F == MSSPE_BWN13_F && MSSPE_BWP13_KC == MSSPE_BWN13_KC && MSSPE_BWP13_W0 == MSSPE_BWN13_W0,
+              "the two-cell scan is the windowed scan's: same window, chunks and register map");
+static __device__ __forceinline__ void window_scan_pair(const v32i Wa, const v16i Wb, const v4i Wc, unsigned CA, int YA,
+                                                     unsigned CB, int YB, int n_far, int n_run, int near_from, int start,
+                                                     int &far_a, int &near_a, int &far_b, int &near_b)
+{
+    int MSSPE_BWP13_TEMP_NAMES;
+    asm volatile(MSSPE_BWP13_SCAN_ASM
+                 : MSSPE_BWP13_ACC_OUT(far_a, near_a, far_b, near_b), MSSPE_BWP13_TEMPS_OUT
+                 : [CA] "v"(CA), [YA] "v"(YA), [CB] "v"(CB), [YB] "v"(YB), [NFAR] "s"(n_far), [NRUN] "s"(n_run),
+                   [NEAR] "s"(near_from), [START] "s"(start), [TOFF] "n"((int)offsetof(SharedRow, T)),
+                   MSSPE_BWP13_TUPLES_IN(Wa, Wb, Wc)
+                 : MSSPE_BWP13_SCAN_CLOBBERS);
+}
 // slot: wave-uniform, < kRowSlots.  farmin = min(farmin, the slot's field); bit 15 of the word is zero.  The word is
 // fetched with the indexed v_mov the compiler itself emits for a register array: a v_min_u16 that read the indexed
 // register directly returned wrong minima for a few pairs per plane on the MI355X (two instructions per slot instead
@@ -932,32 +949,86 @@ static __device__ __forceinline__ int run_pair_packed(SharedRow &sh, const SeqPa
         for (int s_ = start_w[kWinF]; s_ < start_w[kWinF - 1]; ++s_)
           window_fold(Wa, Wb, Wc, __builtin_amdgcn_readfirstlane(s_), farmin);
       }
-      for (int c_ = 0; c_ < w_row; ++c_, slot_ += stored ? 1 : 0) {
-        const int slot = __builtin_amdgcn_readfirstlane(slot_);
-        const bool in = mrem != 0u;
-        const int jm1 = ((__ffs((int)mrem) - 1) >> 1) & 15;
-        mrem &= mrem - 1;
-        const unsigned C = ((unsigned)((jm1 - 1) * kRowA + im1 * (4 * (kRowR + 1)) + 3) << 17) | 0x7fffu;
-        const int yTS = sh.yts[(im1 << 2) | (int)(((q.s2 << 2) >> (2 * jm1)) & 3u)];
-        int acc_far, acc_near;
-        if constexpr (WIN)
-          window_scan(Wa, Wb, Wc, C, yTS, start_im1 / kC4, (row_start + kC4 - 1) / kC4, start_im1, start_w[kWinF - 1] / kC4,
-                      acc_far, acc_near);
-        else packed_scan(Wa, Wb, Wc, C, yTS, start_im1 / kC4, (row_start + kC4 - 1) / kC4, start_im1, acc_far, acc_near);
-        const CellBases b = cell_bases(q, im1, jm1, c);
-        const int gL = sh.g[b.idxL - kRowGBase], gR = sh.g[b.idxR - kRowGBase];
-        // the far minimum takes the cell-side term here, once; an accumulator without a real candidate decodes far above gL
-        int G0 = min(gL, min(kc - acc_far + yTS, kc - acc_near));
-        if constexpr (WIN) {
+      if constexpr (!WIN) {
+        // the un-windowed packed instance (k_pairs_bound_packed): one cell per scan
+        for (int c_ = 0; c_ < w_row; ++c_, slot_ += stored ? 1 : 0) {
+          const int slot = __builtin_amdgcn_readfirstlane(slot_);
+          const bool in = mrem != 0u;
+          const int jm1 = ((__ffs((int)mrem) - 1) >> 1) & 15;
+          mrem &= mrem - 1;
+          const unsigned C = ((unsigned)((jm1 - 1) * kRowA + im1 * (4 * (kRowR + 1)) + 3) << 17) | 0x7fffu;
+          const int yTS = sh.yts[(im1 << 2) | (int)(((q.s2 << 2) >> (2 * jm1)) & 3u)];
+          int acc_far, acc_near;
+          packed_scan(Wa, Wb, Wc, C, yTS, start_im1 / kC4, (row_start + kC4 - 1) / kC4, start_im1, acc_far, acc_near);
+          const CellBases b = cell_bases(q, im1, jm1, c);
+          const int gL = sh.g[b.idxL - kRowGBase], gR = sh.g[b.idxR - kRowGBase];
+          // the far minimum takes the cell-side term here, once; an accumulator without a real candidate decodes far above gL
+          const int G0 = min(gL, min(kc - acc_far + yTS, kc - acc_near));
+          pick = in ? min(pick, G0 + gR) : pick;
+          // G0 + bias is a 15-bit field: BoundPacked's proven range [lo, hi] of every publishable value (a lane without a
+          // cell here publishes an empty slot: its word fails every geometry test)
+          const int Wcell = in ? ((int)((unsigned)(jm1 * kRowA + (im1 << 2) + ((b.po_c >> 4) & 3)) << 17) + (G0 + bias)) : kEmptyW;
+          if (slot < NS) packed_publish(Wa, Wb, Wc, slot, Wcell);
+        }
+      } else {
+        // the windowed instance (k_pairs_bound_window): the cells of a row two at a time, an odd one behind them
+        // the lane's next cell of the row: in, jm1, the scan's minuend C and the cell-side term
+        auto next_cell = [&](bool &in, int &jm1, unsigned &C, int &yTS) {
+          in = mrem != 0u;
+          jm1 = ((__ffs((int)mrem) - 1) >> 1) & 15;
+          mrem &= mrem - 1;
+          C = ((unsigned)((jm1 - 1) * kRowA + im1 * (4 * (kRowR + 1)) + 3) << 17) | 0x7fffu;
+          yTS = sh.yts[(im1 << 2) | (int)(((q.s2 << 2) >> (2 * jm1)) & 3u)];
+        };
+        // the cell behind its scan: the value, the pick, and the slot word it publishes
+        auto finish_cell = [&](bool in, int jm1, int yTS, int acc_far, int acc_near) {
+          const CellBases b = cell_bases(q, im1, jm1, c);
+          const int gL = sh.g[b.idxL - kRowGBase], gR = sh.g[b.idxR - kRowGBase];
+          // the far minimum takes the cell-side term here, once; an accumulator without a real candidate decodes far above gL
+          int G0 = min(gL, min(kc - acc_far + yTS, kc - acc_near));
           // the rows above the window: one candidate (a void yTS is kPkYVoid: the bulge constant alone is left)
           const int far = farmin >= kWinNone ? kWinVoid : farmin - bias + min(bfar, ifar + yTS);
           G0 = min(G0, far);
+          pick = in ? min(pick, G0 + gR) : pick;
+          // G0 + bias is a 15-bit field: BoundPacked's proven range [lo, hi] of every publishable value (a lane without a
+          // cell here publishes an empty slot: its word fails every geometry test)
+          return in ? ((int)((unsigned)(jm1 * kRowA + (im1 << 2) + ((b.po_c >> 4) & 3)) << 17) + (G0 + bias)) : kEmptyW;
+        };
+        int c_ = 0;
+        {
+          // Two cells of a row never depend on each other: they are scanned in one pass and published behind it, A's word and
+          // then B's.  Where a cell-by-cell order lets B visit A's fresh slot, that visit reads "not available" (same row: the
+          // table entry is 0); here B sees the empty word there, whose candidate is 0 as well -- never the maximum beside a
+          // real one (the static_asserts beside kPkOff).
+          for (; c_ + 2 <= w_row; c_ += 2, slot_ += stored ? 2 : 0) {
+            const int slot = __builtin_amdgcn_readfirstlane(slot_);
+            // (the last row is not stored: both words then go to the one slot behind the table, as every cell of that row
+            // does, and nobody reads it)
+            const int slot_b = __builtin_amdgcn_readfirstlane(slot_ + (stored ? 1 : 0));
+            bool in_a, in_b;
+            int jm1_a, jm1_b, y_a, y_b, far_a, near_a, far_b, near_b;
+            unsigned C_a, C_b;
+            next_cell(in_a, jm1_a, C_a, y_a);
+            next_cell(in_b, jm1_b, C_b, y_b);
+            window_scan_pair(Wa, Wb, Wc, C_a, y_a, C_b, y_b, start_im1 / kC4, (row_start + kC4 - 1) / kC4, start_im1,
+                             start_w[kWinF - 1] / kC4, far_a, near_a, far_b, near_b);
+            const int W_a = finish_cell(in_a, jm1_a, y_a, far_a, near_a);
+            const int W_b = finish_cell(in_b, jm1_b, y_b, far_b, near_b);
+            if (slot < NS) packed_publish(Wa, Wb, Wc, slot, W_a);
+            if (slot_b < NS) packed_publish(Wa, Wb, Wc, slot_b, W_b);
+          }
         }
-        pick = in ? min(pick, G0 + gR) : pick;
-        // G0 + bias is a 15-bit field: BoundPacked's proven range [lo, hi] of every publishable value (a lane without a
-        // cell here publishes an empty slot: its word fails every geometry test)
-        const int Wcell = in ? ((int)((unsigned)(jm1 * kRowA + (im1 << 2) + ((b.po_c >> 4) & 3)) << 17) + (G0 + bias)) : kEmptyW;
-        if (slot < NS) packed_publish(Wa, Wb, Wc, slot, Wcell);
+        for (; c_ < w_row; ++c_, slot_ += stored ? 1 : 0) {
+          const int slot = __builtin_amdgcn_readfirstlane(slot_);
+          bool in;
+          int jm1, yTS, acc_far, acc_near;
+          unsigned C;
+          next_cell(in, jm1, C, yTS);
+          window_scan(Wa, Wb, Wc, C, yTS, start_im1 / kC4, (row_start + kC4 - 1) / kC4, start_im1, start_w[kWinF - 1] / kC4,
+                      acc_far, acc_near);
+          const int Wcell = finish_cell(in, jm1, yTS, acc_far, acc_near);
+          if (slot < NS) packed_publish(Wa, Wb, Wc, slot, Wcell);
+        }
       }
       start_im1 = row_start;
       if constexpr (WIN) {

@@ -55,6 +55,7 @@ def main():
               f"overflow pairs={ovf} ({100.0*ovf/(n*n):.2f} %)", flush=True)
         print("   integer stage:", {k: f"{100.0*v/(n*n):.3f} %" for k, v in stats.items() if not isinstance(v, dict)},
               "| list mode:", {k: f"{100.0*v/(n*n):.3f} %" for k, v in stats["list"].items() if v}, flush=True)
+        print("   counts of the first pass:", {k: v for k, v in stats.items() if not isinstance(v, dict) and v}, flush=True)
         eng.pair_stage_stats()
 
 
