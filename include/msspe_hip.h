@@ -1616,6 +1616,83 @@ int msspe_panel_select_weighted_rule(msspe_ctx *ctx, const uint8_t *seqs, int n_
                                      long long *covered_all_out, long long *covered_kept_out, int *n_tubes_used_out,
                                      uint64_t *weight_all_out, uint64_t *weight_kept_out);
 
+/* ---- primer costs: thinning and selection by coverage per cost (engine extension, no reference counterpart;
+ * DESIGN.md 4.18) ----
+ * The calls above treat every primer as equally good: a pick is decided by gain alone.  These calls take a cost per
+ * primer and are otherwise their siblings at depth 1 -- msspe_panel_thin_weighted* / msspe_panel_select_weighted* with
+ * weights, msspe_panel_thin* / msspe_panel_select* without: the arguments, limits, errors and msspe_get_info keys
+ * ("panel_thin_*", "panel_select_*") are the sibling's.  Weights say which segments matter, costs which primers to
+ * prefer: together the weighted set cover.
+ *   costs (host, n_fwd + n_rev entries, uint32, each >= 1): costs[p] in the order of keep_out, forward list then reverse.
+ *   weights (host, optional): as in the weighted calls.  NULL means every segment counts 1; *weight_all_out /
+ *     *weight_kept_out, where given, then receive the two covered counts.
+ *   gain(p) is unchanged: the sum of weights[s] (or the number) of the uncovered segments of row p.  A round considers
+ *     the live primers whose gain is at least min_gain and picks the greatest gain(p) / cost(p).  The comparison is exact:
+ *     p beats q when gain(p) * cost(q) > gain(q) * cost(p) in 64-bit unsigned arithmetic (both factors are below 2^32);
+ *     on equal products the greater gain wins, then the lowest index.  A primer whose gain is below min_gain is no
+ *     candidate, whatever its ratio.  When no live primer qualifies the loop ends; that round counts.  gain_out holds
+ *     gains, not ratios.  Covering, forcing, barring, tubes and every other output are the sibling's.
+ *   *cost_all_out / *cost_kept_out (optional): the sum of costs over all primers and over keep_out == 1, forced primers
+ *     included.
+ *   costs == NULL or a cost of 0 is MSSPE_ERR_ARG; msspe_last_error names the first offending index.  The weights' total
+ *     is bounded by 2^32 - 1 as in the weighted calls.
+ * GUARANTEES.  (1) With all costs equal to any constant c >= 1 every output equals the sibling's: keep, order, gains,
+ * covered, both counts, both weights, tubes, barred and the rounds run.  (2) The thinning at min_gain 1 still loses
+ * nothing: *covered_kept_out == *covered_all_out, and with weights *weight_kept_out == *weight_all_out.  The selection
+ * promises neither, as before.  (3) The kept set of the selection is independent under the graph, tube by tube, as in
+ * msspe_panel_select*.  Depth 1 only. */
+int msspe_panel_thin_cost(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len, const msspe_kmer_opt *opt,
+                          const msspe_mismatch_opt *mm, const msspe_thin_opt *thin, const uint64_t *fwd_words, int n_fwd,
+                          const uint64_t *rev_words, int n_rev, const uint8_t *forced, const uint32_t *weights,
+                          const uint32_t *costs, uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out,
+                          int *n_picked_out, uint8_t *covered_out, long long *covered_all_out,
+                          long long *covered_kept_out, uint64_t *weight_all_out, uint64_t *weight_kept_out,
+                          uint64_t *cost_all_out, uint64_t *cost_kept_out);
+int msspe_panel_thin_cost_dev(msspe_ctx *ctx, const uint8_t *d_seqs, int n_seq, size_t seq_len,
+                              const msspe_kmer_opt *opt, const msspe_mismatch_opt *mm, const msspe_thin_opt *thin,
+                              const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
+                              const uint8_t *forced, const uint32_t *weights, const uint32_t *costs, uint8_t *keep_out,
+                              uint32_t *order_out, uint32_t *gain_out, int *n_picked_out, uint8_t *covered_out,
+                              long long *covered_all_out, long long *covered_kept_out, uint64_t *weight_all_out,
+                              uint64_t *weight_kept_out, uint64_t *cost_all_out, uint64_t *cost_kept_out);
+int msspe_panel_thin_cost_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
+                                     const msspe_kmer_opt *opt, const msspe_mismatch_opt *mm, const msspe_thin_opt *thin,
+                                     const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
+                                     const uint8_t *forced, const uint32_t *weights, const uint32_t *costs,
+                                     uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out, int *n_picked_out,
+                                     uint8_t *covered_out, long long *covered_all_out, long long *covered_kept_out,
+                                     uint64_t *weight_all_out, uint64_t *weight_kept_out, uint64_t *cost_all_out,
+                                     uint64_t *cost_kept_out);
+int msspe_panel_select_cost_dev(msspe_ctx *ctx, const uint8_t *d_seqs, int n_seq, size_t seq_len,
+                                const msspe_kmer_opt *opt, const msspe_seed_rule *rule, const msspe_select_opt *sel,
+                                const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
+                                const uint8_t *forced, const uint64_t *d_bitmap, const uint32_t *weights,
+                                const uint32_t *costs, uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out,
+                                int *n_picked_out, uint8_t *tube_out, uint8_t *barred_out, uint8_t *covered_out,
+                                long long *covered_all_out, long long *covered_kept_out, int *n_tubes_used_out,
+                                uint64_t *weight_all_out, uint64_t *weight_kept_out, uint64_t *cost_all_out,
+                                uint64_t *cost_kept_out);
+int msspe_panel_select_cost_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
+                                       const msspe_kmer_opt *opt, const msspe_seed_rule *rule,
+                                       const msspe_select_opt *sel, const uint64_t *fwd_words, int n_fwd,
+                                       const uint64_t *rev_words, int n_rev, const uint8_t *forced,
+                                       const uint64_t *d_bitmap, const uint32_t *weights, const uint32_t *costs,
+                                       uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out, int *n_picked_out,
+                                       uint8_t *tube_out, uint8_t *barred_out, uint8_t *covered_out,
+                                       long long *covered_all_out, long long *covered_kept_out, int *n_tubes_used_out,
+                                       uint64_t *weight_all_out, uint64_t *weight_kept_out, uint64_t *cost_all_out,
+                                       uint64_t *cost_kept_out);
+int msspe_panel_select_cost_rule(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len,
+                                 const msspe_kmer_opt *opt, const msspe_seed_rule *rule, const msspe_select_opt *sel,
+                                 const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
+                                 const uint8_t *forced, const msspe_chem *chem,
+                                 const msspe_conflict_rule *conflict_rule, const uint32_t *weights,
+                                 const uint32_t *costs, uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out,
+                                 int *n_picked_out, uint8_t *tube_out, uint8_t *barred_out, uint8_t *covered_out,
+                                 long long *covered_all_out, long long *covered_kept_out, int *n_tubes_used_out,
+                                 uint64_t *weight_all_out, uint64_t *weight_kept_out, uint64_t *cost_all_out,
+                                 uint64_t *cost_kept_out);
+
 /* ---- several devices of one node ----------------------------------------------------------
  *
  * One process, one context and one host thread per device.  What shards is the reference's N^2 pair loop

@@ -2873,11 +2873,27 @@ static int panel_weights_check(msspe_ctx *ctx, const char *who, const PanelWeigh
     return MSSPE_OK;
 }
 
+// The cost calls' own argument errors (msspe_panel_thin_cost*, msspe_panel_select_cost*): NULL costs and a cost of 0,
+// with the first offending index (forward list, then reverse list) in the message.  The caller has checked n_fwd and
+// n_rev.
+static int panel_costs_check(msspe_ctx *ctx, const char *who, const PanelCosts &cst, int n_fwd, int n_rev)
+{
+    if (cst.cost_all_out) *cst.cost_all_out = 0;
+    if (cst.cost_kept_out) *cst.cost_kept_out = 0;
+    if (!cst.costs) return fail(ctx, MSSPE_ERR_ARG, std::string(who) + ": null costs (the call without costs takes none)");
+    for (long p = 0; p < (long)n_fwd + (long)n_rev; ++p)
+        if (cst.costs[p] == 0)
+            return fail(ctx, MSSPE_ERR_ARG, std::string(who) + ": the cost of primer " + std::to_string(p) +
+                                                " is 0, a cost is at least 1");
+    return MSSPE_OK;
+}
+
 static int panel_thin_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t seq_len, const msspe_kmer_opt *opt,
                            const msspe_mismatch_opt *mm, const msspe_thin_opt *thin, const uint64_t *fwd_words,
                            int n_fwd, const uint64_t *rev_words, int n_rev, const uint8_t *forced, uint8_t *keep_out,
                            uint32_t *order_out, uint32_t *gain_out, int *n_picked_out, uint8_t *covered_out,
-                           long long *covered_all_out, long long *covered_kept_out, const PanelWeights *wts = nullptr)
+                           long long *covered_all_out, long long *covered_kept_out, const PanelWeights *wts = nullptr,
+                           const PanelCosts *cst = nullptr)
 {
     if (!opt || !mm || !thin || !keep_out || !order_out || !gain_out || !n_picked_out || n_fwd < 0 || n_rev < 0 ||
         (n_fwd && !fwd_words) || (n_rev && !rev_words))
@@ -2887,12 +2903,15 @@ static int panel_thin_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_
         if (int rc = panel_weights_check(ctx, "panel thin", *wts, n_seq, seq_len, *opt, mm->max_mismatches, mm->exact_3p,
                                          fwd_words, n_fwd, rev_words, n_rev))
             return rc;
+    if (cst)
+        if (int rc = panel_costs_check(ctx, "panel thin", *cst, n_fwd, n_rev)) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::string err;
     const int rc = ctx->thin.run(ctx->mm_cov, view, n_seq, seq_len, *opt, mm->max_mismatches, mm->exact_3p,
                                  thin->min_gain, fwd_words, n_fwd, rev_words, n_rev, forced, keep_out, order_out,
                                  gain_out, n_picked_out, covered_out, covered_all_out, covered_kept_out,
-                                 (size_t)ctx->opt.panel_thin_matrix_max_mb << 20, ctx->n_cu, ctx->stream, err, wts);
+                                 (size_t)ctx->opt.panel_thin_matrix_max_mb << 20, ctx->n_cu, ctx->stream, err, wts,
+                                 cst);
     if (rc) return fail(ctx, rc, err);
     return MSSPE_OK;
 }
@@ -2990,6 +3009,86 @@ int msspe_panel_thin_weighted(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, si
     rc = msspe_panel_thin_weighted_dev(ctx, (const uint8_t *)d, n_seq, seq_len, opt, mm, thin, fwd_words, n_fwd,
                                        rev_words, n_rev, forced, weights, keep_out, order_out, gain_out, n_picked_out,
                                        covered_out, covered_all_out, covered_kept_out, weight_all_out, weight_kept_out);
+    (void)msspe_device_free(ctx, d);
+    return rc;
+}
+
+// msspe_panel_thin_cost*: the thinning by gain per cost.  Without weights every segment counts 1 and
+// the two weight sums are the two covered counts.
+static int panel_thin_cost_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t seq_len,
+                                const msspe_kmer_opt *opt, const msspe_mismatch_opt *mm, const msspe_thin_opt *thin,
+                                const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
+                                const uint8_t *forced, const uint32_t *weights, const uint32_t *costs,
+                                uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out, int *n_picked_out,
+                                uint8_t *covered_out, long long *covered_all_out, long long *covered_kept_out,
+                                uint64_t *weight_all_out, uint64_t *weight_kept_out, uint64_t *cost_all_out,
+                                uint64_t *cost_kept_out)
+{
+    const PanelWeights wts = {weights, weight_all_out, weight_kept_out};
+    const PanelCosts cst = {costs, cost_all_out, cost_kept_out};
+    long long all = 0, kept = 0;
+    const int rc = panel_thin_view(ctx, view, n_seq, seq_len, opt, mm, thin, fwd_words, n_fwd, rev_words, n_rev, forced,
+                                   keep_out, order_out, gain_out, n_picked_out, covered_out, &all, &kept,
+                                   weights ? &wts : nullptr, &cst);
+    if (covered_all_out) *covered_all_out = all;
+    if (covered_kept_out) *covered_kept_out = kept;
+    if (!weights) {
+        if (weight_all_out) *weight_all_out = (uint64_t)all;
+        if (weight_kept_out) *weight_kept_out = (uint64_t)kept;
+    }
+    return rc;
+}
+
+int msspe_panel_thin_cost_dev(msspe_ctx *ctx, const uint8_t *d_seqs, int n_seq, size_t seq_len,
+                              const msspe_kmer_opt *opt, const msspe_mismatch_opt *mm, const msspe_thin_opt *thin,
+                              const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
+                              const uint8_t *forced, const uint32_t *weights, const uint32_t *costs, uint8_t *keep_out,
+                              uint32_t *order_out, uint32_t *gain_out, int *n_picked_out, uint8_t *covered_out,
+                              long long *covered_all_out, long long *covered_kept_out, uint64_t *weight_all_out,
+                              uint64_t *weight_kept_out, uint64_t *cost_all_out, uint64_t *cost_kept_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!d_seqs) return fail(ctx, MSSPE_ERR_ARG, "null sequences");
+    return panel_thin_cost_view(ctx, SeqView{d_seqs, nullptr, seq_len}, n_seq, seq_len, opt, mm, thin, fwd_words, n_fwd,
+                                rev_words, n_rev, forced, weights, costs, keep_out, order_out, gain_out, n_picked_out,
+                                covered_out, covered_all_out, covered_kept_out, weight_all_out, weight_kept_out,
+                                cost_all_out, cost_kept_out);
+}
+
+int msspe_panel_thin_cost_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
+                                     const msspe_kmer_opt *opt, const msspe_mismatch_opt *mm, const msspe_thin_opt *thin,
+                                     const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
+                                     const uint8_t *forced, const uint32_t *weights, const uint32_t *costs,
+                                     uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out, int *n_picked_out,
+                                     uint8_t *covered_out, long long *covered_all_out, long long *covered_kept_out,
+                                     uint64_t *weight_all_out, uint64_t *weight_kept_out, uint64_t *cost_all_out,
+                                     uint64_t *cost_kept_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!d_packed) return fail(ctx, MSSPE_ERR_ARG, "null sequences");
+    return panel_thin_cost_view(ctx, SeqView{nullptr, d_packed, seq_len}, n_seq, seq_len, opt, mm, thin, fwd_words,
+                                n_fwd, rev_words, n_rev, forced, weights, costs, keep_out, order_out, gain_out,
+                                n_picked_out, covered_out, covered_all_out, covered_kept_out, weight_all_out,
+                                weight_kept_out, cost_all_out, cost_kept_out);
+}
+
+int msspe_panel_thin_cost(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len, const msspe_kmer_opt *opt,
+                          const msspe_mismatch_opt *mm, const msspe_thin_opt *thin, const uint64_t *fwd_words, int n_fwd,
+                          const uint64_t *rev_words, int n_rev, const uint8_t *forced, const uint32_t *weights,
+                          const uint32_t *costs, uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out,
+                          int *n_picked_out, uint8_t *covered_out, long long *covered_all_out,
+                          long long *covered_kept_out, uint64_t *weight_all_out, uint64_t *weight_kept_out,
+                          uint64_t *cost_all_out, uint64_t *cost_kept_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!seqs || n_seq < 0) return fail(ctx, MSSPE_ERR_ARG, "null sequences");
+    void *d = nullptr;
+    int rc = msspe_device_put(ctx, seqs, (size_t)n_seq * seq_len, &d);
+    if (rc) return rc;
+    rc = msspe_panel_thin_cost_dev(ctx, (const uint8_t *)d, n_seq, seq_len, opt, mm, thin, fwd_words, n_fwd, rev_words,
+                                   n_rev, forced, weights, costs, keep_out, order_out, gain_out, n_picked_out,
+                                   covered_out, covered_all_out, covered_kept_out, weight_all_out, weight_kept_out,
+                                   cost_all_out, cost_kept_out);
     (void)msspe_device_free(ctx, d);
     return rc;
 }
@@ -3960,7 +4059,7 @@ int panel_select_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t seq
                       uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out, int *n_picked_out, uint8_t *tube_out,
                       uint8_t *barred_out, uint8_t *covered_out, long long *covered_all_out,
                       long long *covered_kept_out, int *n_tubes_used_out, const SelectDepthArgs *dep = nullptr,
-                      const PanelWeights *wts = nullptr)
+                      const PanelWeights *wts = nullptr, const PanelCosts *cst = nullptr)
 {
     if (!opt || !rule || !sel || !keep_out || !order_out || !gain_out || !n_picked_out || !tube_out || n_fwd < 0 ||
         n_rev < 0 || (n_fwd && !fwd_words) || (n_rev && !rev_words))
@@ -3998,6 +4097,8 @@ int panel_select_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t seq
         if ((rc = panel_weights_check(ctx, "panel select", *wts, n_seq, seq_len, *opt, mm.max_mismatches, mm.exact_3p,
                                       fwd_words, n_fwd, rev_words, n_rev)))
             return rc;
+    if (cst)   // depth 1 only, as the weights
+        if ((rc = panel_costs_check(ctx, "panel select", *cst, n_fwd, n_rev))) return rc;
     const int n = n_fwd + n_rev;
     const long n_seg = P * n_seq;
     for (int p = 0; p < n; ++p) {
@@ -4056,7 +4157,7 @@ int panel_select_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t seq
     else
         rc = ctx->select.rounds(d_inc, ctx->cover.symmetrised(), n, n_seg, S, sel->min_gain, sel->max_tubes, keep_out,
                                 order_out, gain_out, n_picked_out, tube_out, barred_out, covered_out, covered_all_out,
-                                covered_kept_out, n_tubes_used_out, ctx->n_cu, ctx->stream, err, wts);
+                                covered_kept_out, n_tubes_used_out, ctx->n_cu, ctx->stream, err, wts, cst);
     if (rc) return fail(ctx, rc, err);
     read_slab_times(ctx->thin_thal, false, scored);   // rounds returned with the stream idle
     long long keys_us = 0, sym_us = 0;
@@ -4505,7 +4606,7 @@ static int panel_select_host(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, siz
                              uint8_t *barred_out, uint8_t *covered_out, long long *covered_all_out,
                              long long *covered_kept_out, int *n_tubes_used_out,
                              const msspe_conflict_rule *conflict_rule = nullptr, const SelectDepthArgs *dep = nullptr,
-                             const PanelWeights *wts = nullptr)
+                             const PanelWeights *wts = nullptr, const PanelCosts *cst = nullptr)
 {
     if (!seqs || n_seq < 0) return fail(ctx, MSSPE_ERR_ARG, "null sequences");
     if (n_fwd < 0 || n_rev < 0 || (n_fwd && !fwd_words) || (n_rev && !rev_words) || !opt || !rule || !sel || !keep_out ||
@@ -4556,11 +4657,11 @@ static int panel_select_host(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, siz
         rc = panel_select_view(ctx, SeqView{(const uint8_t *)d, nullptr, seq_len}, n_seq, seq_len, opt, rule, sel,
                                fwd_words, n_fwd, rev_words, n_rev, forced, d_bitmap, keep_out, order_out, gain_out,
                                n_picked_out, tube_out, barred_out, nullptr, nullptr, nullptr, n_tubes_used_out, dep);
-    else if (wts)
+    else if (wts || cst)
         rc = panel_select_view(ctx, SeqView{(const uint8_t *)d, nullptr, seq_len}, n_seq, seq_len, opt, rule, sel,
                                fwd_words, n_fwd, rev_words, n_rev, forced, d_bitmap, keep_out, order_out, gain_out,
                                n_picked_out, tube_out, barred_out, covered_out, covered_all_out, covered_kept_out,
-                               n_tubes_used_out, nullptr, wts);
+                               n_tubes_used_out, nullptr, wts, cst);
     else
         rc = msspe_panel_select_dev(ctx, (const uint8_t *)d, n_seq, seq_len, opt, rule, sel, fwd_words, n_fwd,
                                     rev_words, n_rev, forced, d_bitmap, keep_out, order_out, gain_out, n_picked_out,
@@ -4663,6 +4764,107 @@ int msspe_panel_select_weighted_rule(msspe_ctx *ctx, const uint8_t *seqs, int n_
                              nullptr, chem, 0.0f, keep_out, order_out, gain_out, n_picked_out, tube_out, barred_out,
                              covered_out, covered_all_out, covered_kept_out, n_tubes_used_out, conflict_rule, nullptr,
                              &wts);
+}
+
+// msspe_panel_select_cost*: the selection by gain per cost; the rest of such a call is its sibling's,
+// weighted or not.  Without weights the two weight sums are the two covered counts.
+static void cost_counts_out(const uint32_t *weights, long long all, long long kept, long long *covered_all_out,
+                            long long *covered_kept_out, uint64_t *weight_all_out, uint64_t *weight_kept_out)
+{
+    if (covered_all_out) *covered_all_out = all;
+    if (covered_kept_out) *covered_kept_out = kept;
+    if (!weights) {
+        if (weight_all_out) *weight_all_out = (uint64_t)all;
+        if (weight_kept_out) *weight_kept_out = (uint64_t)kept;
+    }
+}
+
+static int panel_select_cost_view(msspe_ctx *ctx, const SeqView &view, int n_seq, size_t seq_len,
+                                  const msspe_kmer_opt *opt, const msspe_seed_rule *rule, const msspe_select_opt *sel,
+                                  const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
+                                  const uint8_t *forced, const uint64_t *d_bitmap, const uint32_t *weights, const uint32_t *costs,
+                                  uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out, int *n_picked_out,
+                                  uint8_t *tube_out, uint8_t *barred_out, uint8_t *covered_out,
+                                  long long *covered_all_out, long long *covered_kept_out, int *n_tubes_used_out,
+                                  uint64_t *weight_all_out, uint64_t *weight_kept_out, uint64_t *cost_all_out,
+                                  uint64_t *cost_kept_out)
+{
+    const PanelWeights wts = {weights, weight_all_out, weight_kept_out};
+    const PanelCosts cst = {costs, cost_all_out, cost_kept_out};
+    long long all = 0, kept = 0;
+    const int rc = panel_select_view(ctx, view, n_seq, seq_len, opt, rule, sel, fwd_words, n_fwd, rev_words, n_rev,
+                                     forced, d_bitmap, keep_out, order_out, gain_out, n_picked_out, tube_out, barred_out,
+                                     covered_out, &all, &kept, n_tubes_used_out, nullptr, weights ? &wts : nullptr,
+                                     &cst);
+    cost_counts_out(weights, all, kept, covered_all_out, covered_kept_out, weight_all_out, weight_kept_out);
+    return rc;
+}
+
+int msspe_panel_select_cost_dev(msspe_ctx *ctx, const uint8_t *d_seqs, int n_seq, size_t seq_len,
+                                const msspe_kmer_opt *opt, const msspe_seed_rule *rule, const msspe_select_opt *sel,
+                                const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
+                                const uint8_t *forced, const uint64_t *d_bitmap, const uint32_t *weights, const uint32_t *costs,
+                                uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out, int *n_picked_out,
+                                uint8_t *tube_out, uint8_t *barred_out, uint8_t *covered_out,
+                                long long *covered_all_out, long long *covered_kept_out, int *n_tubes_used_out,
+                                uint64_t *weight_all_out, uint64_t *weight_kept_out, uint64_t *cost_all_out,
+                                uint64_t *cost_kept_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!d_seqs) return fail(ctx, MSSPE_ERR_ARG, "null sequences");
+    return panel_select_cost_view(ctx, SeqView{d_seqs, nullptr, seq_len}, n_seq, seq_len, opt, rule, sel, fwd_words,
+                                  n_fwd, rev_words, n_rev, forced, d_bitmap, weights, costs, keep_out, order_out,
+                                  gain_out, n_picked_out, tube_out, barred_out, covered_out, covered_all_out,
+                                  covered_kept_out, n_tubes_used_out, weight_all_out, weight_kept_out, cost_all_out,
+                                  cost_kept_out);
+}
+
+int msspe_panel_select_cost_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, int n_seq, size_t seq_len,
+                                       const msspe_kmer_opt *opt, const msspe_seed_rule *rule,
+                                       const msspe_select_opt *sel, const uint64_t *fwd_words, int n_fwd,
+                                       const uint64_t *rev_words, int n_rev,
+                                       const uint8_t *forced, const uint64_t *d_bitmap, const uint32_t *weights, const uint32_t *costs,
+                                       uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out, int *n_picked_out,
+                                       uint8_t *tube_out, uint8_t *barred_out, uint8_t *covered_out,
+                                       long long *covered_all_out, long long *covered_kept_out, int *n_tubes_used_out,
+                                       uint64_t *weight_all_out, uint64_t *weight_kept_out, uint64_t *cost_all_out,
+                                       uint64_t *cost_kept_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!d_packed) return fail(ctx, MSSPE_ERR_ARG, "null sequences");
+    return panel_select_cost_view(ctx, SeqView{nullptr, d_packed, seq_len}, n_seq, seq_len, opt, rule, sel, fwd_words,
+                                  n_fwd, rev_words, n_rev, forced, d_bitmap, weights, costs, keep_out, order_out,
+                                  gain_out, n_picked_out, tube_out, barred_out, covered_out, covered_all_out,
+                                  covered_kept_out, n_tubes_used_out, weight_all_out, weight_kept_out, cost_all_out,
+                                  cost_kept_out);
+}
+
+int msspe_panel_select_cost_rule(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len,
+                                 const msspe_kmer_opt *opt, const msspe_seed_rule *rule, const msspe_select_opt *sel,
+                                 const uint64_t *fwd_words, int n_fwd, const uint64_t *rev_words, int n_rev,
+                                 const uint8_t *forced, const msspe_chem *chem,
+                                 const msspe_conflict_rule *conflict_rule, const uint32_t *weights,
+                                 const uint32_t *costs, uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out,
+                                 int *n_picked_out, uint8_t *tube_out, uint8_t *barred_out, uint8_t *covered_out,
+                                 long long *covered_all_out, long long *covered_kept_out, int *n_tubes_used_out,
+                                 uint64_t *weight_all_out, uint64_t *weight_kept_out, uint64_t *cost_all_out,
+                                 uint64_t *cost_kept_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (int rc = graph_rule_check(ctx, chem, conflict_rule, GraphOut{}, false)) return rc;
+    if (weight_all_out) *weight_all_out = 0;
+    if (weight_kept_out) *weight_kept_out = 0;
+    const PanelWeights wts = {weights, weight_all_out, weight_kept_out};
+    const PanelCosts cst = {costs, cost_all_out, cost_kept_out};
+    if (n_fwd < 0 || n_rev < 0) return fail(ctx, MSSPE_ERR_ARG, "panel select: null argument");
+    if (int rc = panel_costs_check(ctx, "panel select", cst, n_fwd, n_rev)) return rc;   // before the screen, not after it
+    long long all = 0, kept = 0;
+    const int rc = panel_select_host(ctx, seqs, n_seq, seq_len, opt, rule, sel, fwd_words, n_fwd, rev_words, n_rev,
+                                     forced, nullptr, chem, 0.0f, keep_out, order_out, gain_out, n_picked_out, tube_out,
+                                     barred_out, covered_out, &all, &kept, n_tubes_used_out, conflict_rule, nullptr,
+                                     weights ? &wts : nullptr, &cst);
+    cost_counts_out(weights, all, kept, covered_all_out, covered_kept_out, weight_all_out, weight_kept_out);
+    return rc;
 }
 
 int msspe_panel_select_bitmap(msspe_ctx *ctx, const uint8_t *seqs, int n_seq, size_t seq_len,

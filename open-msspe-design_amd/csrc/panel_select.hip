@@ -34,6 +34,10 @@
 // Weights (msspe_panel_select_weighted*).  gain(p) is the sum of a weight per segment over the
 // uncovered segments of row p: the first gains and the update run in their weighted instances (panel_weighted.hpp);
 // forced, first barring, pick and apply are the kernels above, unchanged.
+//
+// Costs (msspe_panel_select_cost*).  A round keeps the live primer of greatest gain / cost: the pick
+// runs in its cost instance (panel_cost.hpp) over a cost per primer; every other kernel of the round is the one above,
+// weighted or not.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -41,6 +45,7 @@
 #include <vector>
 
 #include "../../include/msspe_hip.h"
+#include "panel_cost.hpp"
 #include "panel_select.hpp"
 #include "panel_thin.hpp"
 #include "panel_weighted.hpp"
@@ -68,7 +73,7 @@ struct SelectState {
     unsigned long long covered_forced;   // |OR of the forced I[p]|
 };
 
-enum { kPool, kCov, kTouched, kNew, kGain, kMask, kBytes, kOrder, kForced, kDepth, kPrimerMask, kWeight };   // PanelSelect::buf_
+enum { kPool, kCov, kTouched, kNew, kGain, kMask, kBytes, kOrder, kForced, kDepth, kPrimerMask, kWeight, kCost };   // PanelSelect::buf_
 
 __device__ __forceinline__ uint64_t wave_or(uint64_t x)
 {
@@ -369,13 +374,18 @@ int PanelSelect::rounds(const uint64_t *d_inc, const uint64_t *d_sym, int n, lon
                         int max_tubes, uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out, int *n_picked_out,
                         uint8_t *tube_out, uint8_t *barred_out, uint8_t *covered_out, long long *covered_all_out,
                         long long *covered_kept_out, int *n_tubes_used_out, int n_cu, hipStream_t stream,
-                        std::string &err, const PanelWeights *wts)
+                        std::string &err, const PanelWeights *wts, const PanelCosts *cst)
 {
     const long G = (n_seg + S - 1) / S;
     const int W = (n + 63) / 64;
     const size_t n_pad = ((size_t)n + 63) & ~(size_t)63;
     if (wts)   // the sums, the plane and the weights as given: the one slot a weighted call adds
         if (int rc = ensure(kWeight, weighted::Plane::bytes(G, n_seg), err)) return rc;
+    if (cst)   // a cost per primer: the one slot a cost call adds
+        if (int rc = ensure(kCost, sizeof(uint32_t) * (size_t)n, err)) return rc;
+    const uint32_t *d_cost = cst ? (const uint32_t *)buf_[kCost] : nullptr;
+    if (cst && cst->cost_all_out) *cst->cost_all_out = 0;
+    if (cst && cst->cost_kept_out) *cst->cost_kept_out = 0;
     const weighted::Plane wp(wts ? buf_[kWeight] : nullptr, G);
     const uint64_t tubes_mask = max_tubes >= 64 ? ~0ull : (1ull << max_tubes) - 1;
     uint64_t *d_cov = (uint64_t *)buf_[kCov], *d_new = (uint64_t *)buf_[kNew], *d_mask = (uint64_t *)buf_[kMask];
@@ -396,6 +406,8 @@ int PanelSelect::rounds(const uint64_t *d_inc, const uint64_t *d_sym, int n, lon
     SELECT_TRY(hipMemsetAsync(d_gain, 0, sizeof(uint32_t) * (size_t)n, stream));
     SELECT_TRY(hipMemsetAsync(d_tube, MSSPE_TUBE_NONE, (size_t)n, stream));
     SELECT_TRY(hipMemcpyAsync(d_flags, flags.data(), (size_t)n, hipMemcpyHostToDevice, stream));
+    if (cst)
+        SELECT_TRY(hipMemcpyAsync(buf_[kCost], cst->costs, sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice, stream));
     const unsigned gx = (unsigned)((n + kThreads - 1) / kThreads);
     if (!forced_idx.empty()) {
         SELECT_TRY(hipMemcpyAsync(d_forced, forced_idx.data(), sizeof(uint32_t) * forced_idx.size(),
@@ -432,8 +444,13 @@ int PanelSelect::rounds(const uint64_t *d_inc, const uint64_t *d_sym, int n, lon
     SelectState hs{};
     for (int batch = 0;; ++batch) {
         for (int b = 0; b < kRoundsPerBatch; ++b) {
-            hipLaunchKernelGGL(k_select_pick, dim3(1), dim3(kThreads), 0, stream, d_gain, d_flags, d_mask, n,
-                               (uint32_t)min_gain, tubes_mask, d_order, d_gains, d_tube, st);
+            if (cst)
+                hipLaunchKernelGGL(cost::k_select_pick_cost<SelectState>, dim3(1), dim3(kThreads), 0, stream, d_gain,
+                                   d_cost, d_flags, kLive, d_mask, n, (uint32_t)min_gain, tubes_mask, d_order, d_gains,
+                                   d_tube, st);
+            else
+                hipLaunchKernelGGL(k_select_pick, dim3(1), dim3(kThreads), 0, stream, d_gain, d_flags, d_mask, n,
+                                   (uint32_t)min_gain, tubes_mask, d_order, d_gains, d_tube, st);
             hipLaunchKernelGGL(k_select_apply, dim3(ga), dim3(kThreads), 0, stream, d_inc, n_pad, (int)G, d_cov,
                                d_touched, d_new, d_sym, n, W, d_mask, st);
             if (wts)
@@ -501,6 +518,15 @@ int PanelSelect::rounds(const uint64_t *d_inc, const uint64_t *d_sym, int n, lon
         if (wts->weight_kept_out) *wts->weight_kept_out = h_sums[1] + (uint64_t)(kept - (long long)hs.covered_forced);
         kept = 0;
         for (long g = 0; g < G; ++g) kept += __builtin_popcountll(h_cov[(size_t)g]);
+    }
+    if (cst) {   // the two cost sums are formed here: the costs never left the host
+        uint64_t all = 0, kept_cost = 0;
+        for (int p = 0; p < n; ++p) {
+            all += cst->costs[p];
+            if (keep_out[p]) kept_cost += cst->costs[p];
+        }
+        if (cst->cost_all_out) *cst->cost_all_out = all;
+        if (cst->cost_kept_out) *cst->cost_kept_out = kept_cost;
     }
     *n_picked_out = n_picked;
     if (n_tubes_used_out) *n_tubes_used_out = (int)hs.used;

@@ -24,12 +24,13 @@ public:
     // rounds: the rule of msspe_panel_select* over inc (inc[g * n_pad + p], bit b = segment g * S + b) and sym (the
     // cover's symmetrised bitmap, n x ceil(n / 64) words).  keep_out holds the forced flags on entry.  Outputs as the
     // C call's; barred_out and covered_out are optional.  Returns an msspe_status with the stream idle; err says why.
-    // wts (optional): the weighted rule of msspe_panel_select_weighted* (PanelWeights, panel_thin.hpp).
+    // wts (optional): the weighted rule of msspe_panel_select_weighted* (PanelWeights, panel_thin.hpp).  cst (optional):
+    // the pick by gain per cost of msspe_panel_select_cost* (PanelCosts, panel_thin.hpp), with or without wts.
     int rounds(const uint64_t *inc, const uint64_t *sym, int n, long n_seg, int S, int min_gain, int max_tubes,
                uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out, int *n_picked_out, uint8_t *tube_out,
                uint8_t *barred_out, uint8_t *covered_out, long long *covered_all_out, long long *covered_kept_out,
                int *n_tubes_used_out, int n_cu, hipStream_t stream, std::string &err,
-               const PanelWeights *wts = nullptr);
+               const PanelWeights *wts = nullptr, const PanelCosts *cst = nullptr);
     // rounds_depth: the layered rule of msspe_panel_select_depth*  over the same inc and sym: layer 1 is
     // rounds(), layer r then adds primers for the segments that still have fewer than r, the barring carried along.
     // depth is 1..255 (checked by the caller).  pick_layer_out (optional, per position of the order), depth_all_out /
@@ -56,7 +57,7 @@ public:
     }
 
 private:
-    enum { kSlots = 12 };
+    enum { kSlots = 13 };
     void *buf_[kSlots] = {};
     size_t cap_[kSlots] = {};
     hipEvent_t ev_[3] = {};

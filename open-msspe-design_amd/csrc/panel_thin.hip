@@ -24,6 +24,10 @@
 // Weights (msspe_panel_thin_weighted*).  gain(p) is the sum of a weight per segment over the uncovered
 // segments of row p.  The first gains and the update run in their weighted instances (panel_weighted.hpp) over a weight
 // plane with the cell layout of the depth planes; forced, pick and apply are the kernels above, unchanged.
+//
+// Costs (msspe_panel_thin_cost*).  A round keeps the greatest gain / cost instead of the greatest gain:
+// the pick runs in its cost instance (panel_cost.hpp) over a cost per primer; every other kernel of the round is the
+// one above, weighted or not.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -31,6 +35,7 @@
 #include <vector>
 
 #include "../../include/msspe_hip.h"
+#include "panel_cost.hpp"
 #include "panel_thin.hpp"
 #include "panel_weighted.hpp"
 
@@ -53,7 +58,7 @@ struct ThinState {
     unsigned long long covered_forced;   // |OR of the forced I[p]|
 };
 
-enum { kInc, kCov, kTouched, kNew, kGain, kLive, kOrder, kForced, kDepth, kMask, kWeight };   // PanelThin::buf_
+enum { kInc, kCov, kTouched, kNew, kGain, kLive, kOrder, kForced, kDepth, kMask, kWeight, kCost };   // PanelThin::buf_
 
 __device__ __forceinline__ uint64_t wave_or(uint64_t x)
 {
@@ -347,7 +352,7 @@ int PanelThin::run(MismatchCoverage &cov, const SeqView &seqs, int n_seq, size_t
                    const uint64_t *rev_words, int n_rev, const uint8_t *forced, uint8_t *keep_out, uint32_t *order_out,
                    uint32_t *gain_out, int *n_picked_out, uint8_t *covered_out, long long *covered_all_out,
                    long long *covered_kept_out, size_t max_matrix_bytes, int n_cu, hipStream_t stream,
-                   std::string &err, const PanelWeights *wts)
+                   std::string &err, const PanelWeights *wts, const PanelCosts *cst)
 {
     rounds_ = groups_ = 0;
     for (auto &p : phase_us_) p = 0;
@@ -356,6 +361,8 @@ int PanelThin::run(MismatchCoverage &cov, const SeqView &seqs, int n_seq, size_t
     if (covered_kept_out) *covered_kept_out = 0;
     if (wts && wts->weight_all_out) *wts->weight_all_out = 0;
     if (wts && wts->weight_kept_out) *wts->weight_kept_out = 0;
+    if (cst && cst->cost_all_out) *cst->cost_all_out = 0;
+    if (cst && cst->cost_kept_out) *cst->cost_kept_out = 0;
     long P = 0;
     int rc = MismatchCoverage::check(n_seq, seq_len, opt, max_mismatches, exact_3p, fwd_words, n_fwd, rev_words, n_rev,
                                      &P, err);
@@ -375,7 +382,7 @@ int PanelThin::run(MismatchCoverage &cov, const SeqView &seqs, int n_seq, size_t
                             d_inc, stream, err)))
         return rc;
     if ((rc = rounds(n, n_seg, MismatchCoverage::group_size(opt), min_gain, keep_out, order_out, gain_out,
-                     n_picked_out, covered_out, covered_all_out, covered_kept_out, n_cu, stream, err, wts)))
+                     n_picked_out, covered_out, covered_all_out, covered_kept_out, n_cu, stream, err, wts, cst)))
         return rc;
     float ms = 0.f;   // rounds() returned with the stream idle
     (void)hipEventElapsedTime(&ms, ev_[0], ev_[1]);
@@ -386,12 +393,15 @@ int PanelThin::run(MismatchCoverage &cov, const SeqView &seqs, int n_seq, size_t
 int PanelThin::rounds(int n, long n_seg, int S, int min_gain, uint8_t *keep_out, uint32_t *order_out,
                       uint32_t *gain_out, int *n_picked_out, uint8_t *covered_out, long long *covered_all_out,
                       long long *covered_kept_out, int n_cu, hipStream_t stream, std::string &err,
-                      const PanelWeights *wts)
+                      const PanelWeights *wts, const PanelCosts *cst)
 {
     const long G = (n_seg + S - 1) / S;
     const size_t n_pad = ((size_t)n + 63) & ~(size_t)63;
     if (wts)   // the sums, the plane and the weights as given: the one slot a weighted call adds
         if (int rc = ensure(kWeight, weighted::Plane::bytes(G, n_seg), err)) return rc;
+    if (cst)   // a cost per primer: the one slot a cost call adds
+        if (int rc = ensure(kCost, sizeof(uint32_t) * (size_t)n, err)) return rc;
+    const uint32_t *d_cost = cst ? (const uint32_t *)buf_[kCost] : nullptr;
     const weighted::Plane wp(wts ? buf_[kWeight] : nullptr, G);
     uint64_t *d_inc = (uint64_t *)buf_[kInc], *d_cov = (uint64_t *)buf_[kCov], *d_new = (uint64_t *)buf_[kNew];
     ThinState *st = (ThinState *)(d_cov + G);   // behind the covered words: 8-byte aligned
@@ -410,6 +420,8 @@ int PanelThin::rounds(int n, long n_seg, int S, int min_gain, uint8_t *keep_out,
     THIN_TRY(hipMemsetAsync(d_cov, 0, sizeof(uint64_t) * (size_t)G + sizeof(ThinState), stream));
     THIN_TRY(hipMemsetAsync(d_gain, 0, sizeof(uint32_t) * (size_t)n, stream));
     THIN_TRY(hipMemcpyAsync(d_live, live.data(), (size_t)n, hipMemcpyHostToDevice, stream));
+    if (cst)
+        THIN_TRY(hipMemcpyAsync(buf_[kCost], cst->costs, sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice, stream));
     if (!forced_idx.empty()) {
         THIN_TRY(hipMemcpyAsync(d_forced, forced_idx.data(), sizeof(uint32_t) * forced_idx.size(),
                                 hipMemcpyHostToDevice, stream));
@@ -444,8 +456,12 @@ int PanelThin::rounds(int n, long n_seg, int S, int min_gain, uint8_t *keep_out,
     ThinState hs{};
     for (int batch = 0;; ++batch) {
         for (int b = 0; b < kRoundsPerBatch; ++b) {
-            hipLaunchKernelGGL(k_thin_pick, dim3(1), dim3(kThreads), 0, stream, d_gain, d_live, n, (uint32_t)min_gain,
-                               d_order, d_gains, st);
+            if (cst)
+                hipLaunchKernelGGL(cost::k_thin_pick_cost<ThinState>, dim3(1), dim3(kThreads), 0, stream, d_gain,
+                                   d_cost, d_live, n, (uint32_t)min_gain, d_order, d_gains, st);
+            else
+                hipLaunchKernelGGL(k_thin_pick, dim3(1), dim3(kThreads), 0, stream, d_gain, d_live, n,
+                                   (uint32_t)min_gain, d_order, d_gains, st);
             hipLaunchKernelGGL(k_thin_apply, dim3(ga), dim3(kThreads), 0, stream, d_inc, n_pad, (int)G, d_cov,
                                d_touched, d_new, st);
             if (wts)
@@ -504,6 +520,15 @@ int PanelThin::rounds(int n, long n_seg, int S, int min_gain, uint8_t *keep_out,
         if (wts->weight_kept_out) *wts->weight_kept_out = h_sums[1] + (uint64_t)(kept - (long long)hs.covered_forced);
         kept = 0;
         for (long g = 0; g < G; ++g) kept += __builtin_popcountll(h_cov[(size_t)g]);
+    }
+    if (cst) {   // the two cost sums are formed here: the costs never left the host
+        uint64_t all = 0, kept_cost = 0;
+        for (int p = 0; p < n; ++p) {
+            all += cst->costs[p];
+            if (keep_out[p]) kept_cost += cst->costs[p];
+        }
+        if (cst->cost_all_out) *cst->cost_all_out = all;
+        if (cst->cost_kept_out) *cst->cost_kept_out = kept_cost;
     }
     *n_picked_out = n_picked;
     if (covered_all_out) *covered_all_out = (long long)hs.covered_all;

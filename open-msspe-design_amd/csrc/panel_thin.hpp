@@ -22,6 +22,16 @@ struct PanelWeights {
     uint64_t *weight_all_out, *weight_kept_out;
 };
 
+// What a cost call (msspe_panel_thin_cost*, msspe_panel_select_cost*) hands to PanelThin::rounds /
+// PanelSelect::rounds: a cost per primer (host, n_fwd + n_rev entries in the order of keep_out, every one at least 1:
+// the caller has checked) and the two optional sums, over all primers and over the kept ones.  With it a round picks
+// the greatest gain / cost, compared exactly, among the live primers whose gain reaches min_gain; the gains themselves
+// are the sibling's, weights or counts.
+struct PanelCosts {
+    const uint32_t *costs;
+    uint64_t *cost_all_out, *cost_kept_out;
+};
+
 class PanelThin {
 public:
     // The alignment, options and primer words of MismatchCoverage::run; forced (host, optional, n_fwd + n_rev): primers
@@ -35,7 +45,7 @@ public:
             const uint64_t *rev_words, int n_rev, const uint8_t *forced, uint8_t *keep_out, uint32_t *order_out,
             uint32_t *gain_out, int *n_picked_out, uint8_t *covered_out, long long *covered_all_out,
             long long *covered_kept_out, size_t max_matrix_bytes, int n_cu, hipStream_t stream, std::string &err,
-            const PanelWeights *wts = nullptr);
+            const PanelWeights *wts = nullptr, const PanelCosts *cst = nullptr);
     // run() in its two halves, for a caller that fills the matrix itself (msspe_panel_thin_thal*: the held incidence).
     // matrix: the buffers of a run over n primers and n_seg segments in groups of S, under the same cap; *inc_out is
     // the matrix (inc[g * n_pad + p], n_pad = n rounded up to 64, bit b = segment g * S + b), not yet written.  The
@@ -44,7 +54,8 @@ public:
     int matrix(int n, long n_seg, int S, size_t max_matrix_bytes, uint64_t **inc_out, std::string &err);
     int rounds(int n, long n_seg, int S, int min_gain, uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out,
                int *n_picked_out, uint8_t *covered_out, long long *covered_all_out, long long *covered_kept_out,
-               int n_cu, hipStream_t stream, std::string &err, const PanelWeights *wts = nullptr);
+               int n_cu, hipStream_t stream, std::string &err, const PanelWeights *wts = nullptr,
+               const PanelCosts *cst = nullptr);
     // Depth (msspe_panel_thin_depth*): every segment keeps min(depth, primers it has) primers.  run's
     // arguments plus depth (1..255, checked by the caller); depth_all_out / depth_kept_out (optional, n_seq * P bytes):
     // representatives per segment among all and among the kept, saturating at 255; counts_out[4] (optional): segments
@@ -78,7 +89,7 @@ public:
     const long long *phase_us() const { return phase_us_; }
 
 private:
-    enum { kSlots = 11 };
+    enum { kSlots = 12 };
     void *buf_[kSlots] = {};
     size_t cap_[kSlots] = {};
     hipEvent_t ev_[4] = {};

@@ -77,6 +77,8 @@ int odm_parse_args(int argc, const char *const *argv, char *out, size_t cap)
           << "\nbackground_3p_exact=" << a.background_3p_exact << "\nmax_background_sites=" << a.max_background_sites
           << "\nbackground_tm=" << a.background_tm_text << "\nbackground_thal=" << a.background_thal
           << "\nbackground_flank=" << a.background_flank
+          << "\nprimer_costs=" << a.primer_costs << "\ndefault_primer_cost=" << a.default_primer_cost
+          << "\nbackground_site_cost=" << a.background_site_cost
           << "\n";
         emit(o.str(), out, cap);
         return 0;
@@ -299,6 +301,85 @@ int odm_select_panel_weighted(const uint64_t *rows, int n, int words, const uint
         sums_out[3] = (unsigned long long)s.rounds;
         sums_out[4] = sums.weight_all;
         sums_out[5] = sums.weight_kept;
+    }
+    return (int)s.order.size();
+}
+
+// odm_thin_panel_weighted with costs[n] (a uint32 >= 1 per row); weights may be NULL (a gain is a count then).
+// sums_out[0..5]: segments covered by all rows / by the kept ones, the weight of each (without weights: the counts
+// again), the costs of all rows / of the kept ones (thin_panel_cost, the sequential rule of DESIGN.md 4.18).
+int odm_thin_panel_cost(const uint64_t *rows, int n, int words, const uint32_t *weights, int n_seg,
+                        const uint32_t *costs, long long min_gain, const uint8_t *forced, int *order, uint32_t *gains,
+                        uint8_t *keep, unsigned long long *sums_out)
+{
+    std::vector<std::vector<uint64_t>> r((size_t)n);
+    for (int p = 0; p < n; ++p) r[(size_t)p].assign(rows + (size_t)p * words, rows + (size_t)(p + 1) * words);
+    std::vector<char> f;
+    if (forced) f.assign(forced, forced + n);
+    std::vector<uint32_t> w;
+    if (weights) w.assign(weights, weights + n_seg);
+    CostSums sums;
+    const ThinResult t = thin_panel_cost(r, weights ? &w : nullptr, std::vector<uint32_t>(costs, costs + n), min_gain, f,
+                                         sums);
+    for (size_t i = 0; i < t.order.size(); ++i) {
+        order[i] = t.order[i];
+        gains[i] = sums.gains[i];
+    }
+    for (int p = 0; p < n; ++p) keep[p] = (uint8_t)t.keep[(size_t)p];
+    if (sums_out) {
+        sums_out[0] = t.covered_all;
+        sums_out[1] = t.covered_kept;
+        sums_out[2] = sums.weight_all;
+        sums_out[3] = sums.weight_kept;
+        sums_out[4] = sums.cost_all;
+        sums_out[5] = sums.cost_kept;
+    }
+    return (int)t.order.size();
+}
+
+// odm_select_panel_weighted with costs[n]; weights may be NULL.  sums_out[0..7]: odm_select_panel_weighted's six, then
+// the costs of all rows / of the kept ones (select_panel_cost, the sequential rule of DESIGN.md 4.18).
+int odm_select_panel_cost(const uint64_t *rows, int n, int words, const uint64_t *bitmap, const uint32_t *weights,
+                          int n_seg, const uint32_t *costs, int max_tubes, long long min_gain, const uint8_t *forced,
+                          int drop_self, int *order, uint32_t *gains, uint8_t *keep, int *tube, uint8_t *barred,
+                          unsigned long long *sums_out)
+{
+    std::vector<std::vector<uint64_t>> r((size_t)n);
+    for (int p = 0; p < n; ++p) r[(size_t)p].assign(rows + (size_t)p * words, rows + (size_t)(p + 1) * words);
+    std::vector<char> f;
+    if (forced) f.assign(forced, forced + n);
+    std::vector<std::string> names((size_t)n);
+    for (int p = 0; p < n; ++p) names[(size_t)p] = std::to_string(p);
+    ConflictGraph g;
+    g.nodes = names;
+    const int W = (n + 63) / 64;
+    for (int p = 0; p < n; ++p)
+        for (int u = 0; u < n; ++u)
+            if ((bitmap[(size_t)p * W + (u >> 6)] >> (u & 63)) & 1ull)
+                if (!(drop_self && p == u)) g.edges[names[(size_t)p]].insert(names[(size_t)u]);
+    std::vector<uint32_t> w;
+    if (weights) w.assign(weights, weights + n_seg);
+    CostSums sums;
+    const SelectResult s = select_panel_cost(r, names, g, weights ? &w : nullptr,
+                                             std::vector<uint32_t>(costs, costs + n), max_tubes, min_gain, f, sums);
+    for (size_t i = 0; i < s.order.size(); ++i) {
+        order[i] = s.order[i];
+        gains[i] = sums.gains[i];
+    }
+    for (int p = 0; p < n; ++p) {
+        keep[p] = (uint8_t)s.keep[(size_t)p];
+        tube[p] = s.tube[(size_t)p];
+        barred[p] = (uint8_t)s.barred[(size_t)p];
+    }
+    if (sums_out) {
+        sums_out[0] = s.covered_all;
+        sums_out[1] = s.covered_kept;
+        sums_out[2] = (unsigned long long)s.tubes_used;
+        sums_out[3] = (unsigned long long)s.rounds;
+        sums_out[4] = sums.weight_all;
+        sums_out[5] = sums.weight_kept;
+        sums_out[6] = sums.cost_all;
+        sums_out[7] = sums.cost_kept;
     }
     return (int)s.order.size();
 }

@@ -92,6 +92,9 @@ const OptSpec kOpts[] = {
     {"--select-depth", "SELECT_DEPTH", OptSpec::Int, OFF(select_depth)},
     {"--genome-weights", "GENOME_WEIGHTS", OptSpec::Str, OFF(genome_weights)},
     {"--default-genome-weight", "DEFAULT_GENOME_WEIGHT", OptSpec::Int, OFF(default_genome_weight)},
+    {"--primer-costs", "PRIMER_COSTS", OptSpec::Str, OFF(primer_costs)},
+    {"--default-primer-cost", "DEFAULT_PRIMER_COST", OptSpec::Str, OFF(default_primer_cost_text)},
+    {"--background-site-cost", "BACKGROUND_SITE_COST", OptSpec::Str, OFF(background_site_cost_text)},
     {"--seed-mismatches", "SEED_MISMATCHES", OptSpec::OptInt, OFF(seed_mismatches)},
     {"--seed-3p-exact", "SEED_3P_EXACT", OptSpec::Str, OFF(seed_3p_exact_text)},
     {"--seed-tm", "SEED_TM", OptSpec::Str, OFF(seed_tm_text)},
@@ -174,6 +177,14 @@ std::string Args::usage()
          "weight units, genomes of weight 0 are reported but get no primer of their own, and the block gains a 'Weight:'\n"
          "line. All weights times the segments per genome may add up to 4294967295. Depth 1 only; not with --thin-panel\n"
          "true --thin-tm.\n"
+         "--primer-costs <FILE> makes --thin-panel true and --select-by-coverage true pick by coverage per cost: lines\n"
+         "'sequence,cost' (the primer as the CSV prints it, an integer 1 .. 4294967295; a sequence listed twice takes\n"
+         "the later line), --default-primer-cost <N> (default 1) for the primers not listed. A round keeps the primer\n"
+         "with the greatest new coverage divided by its cost, compared exactly; equal ratios go to the greater\n"
+         "coverage. --background-site-cost <C> (needs --background) adds C times a primer's background sites, counted as\n"
+         "--max-background-sites counts them, to its cost, so a clean primer is preferred to an interchangeable one\n"
+         "with off-target sites. --genome-weights applies as before, and the block gains a 'Cost:' line. Depth 1 only;\n"
+         "one device; not with --thin-panel true --thin-tm.\n"
          "--coverage-tm <C> adds a report of the segments the final primers hold at C: every match within\n"
          "--coverage-mismatches (last --coverage-3p-exact bases exact) is scored with thal (--coverage-thal any | end1)\n"
          "against the strand the primer anneals to. One device.\n"
@@ -358,6 +369,37 @@ Args Args::parse(int argc, const char *const *argv)
         if (thin && a.thin_scored)
             throw UsageError("error: '--genome-weights' with '--thin-panel true --thin-tm' is not built yet: the "
                              "weighted thinning runs on the string rule");
+    }
+    for (const auto &given : {std::make_pair("--default-primer-cost", &a.default_primer_cost_text),
+                              std::make_pair("--background-site-cost", &a.background_site_cost_text)}) {
+        const std::string &v = *given.second;   // an integer 1 .. 2^32 - 1
+        if (v.empty()) continue;
+        char *end = nullptr;
+        errno = 0;
+        const unsigned long long x = std::strtoull(v.c_str(), &end, 10);
+        if (v.find_first_not_of("0123456789") != std::string::npos || *end || errno || x < 1 || x > 0xFFFFFFFFull)
+            throw UsageError(std::string("error: invalid value '") + v + "' for '" + given.first +
+                             " <...>'\n  [1 .. 4294967295]");
+        (given.second == &a.default_primer_cost_text ? a.default_primer_cost : a.background_site_cost) = (uint32_t)x;
+    }
+    if (!a.primer_costs.empty() || a.background_site_cost) {
+        const bool thin = a.thin_panel == "true", select = a.select_by_coverage == "true";
+        const char *both = "'--primer-costs' and '--background-site-cost'";
+        if (!a.devices.empty())   // first: the two switches refuse '--devices' themselves
+            throw UsageError(std::string("error: ") + both + " run on one device and cannot be combined with "
+                             "'--devices'");
+        if (!thin && !select)
+            throw UsageError(std::string("error: ") + both + " price the primers of '--thin-panel true' or "
+                             "'--select-by-coverage true' and do nothing without one of them");
+        if (a.background_site_cost && a.background.empty())
+            throw UsageError("error: '--background-site-cost' needs '--background <FASTA>'");
+        if ((thin && a.thin_depth > 1) || (select && a.select_depth > 1))
+            throw UsageError(std::string("error: ") + both + " with '" + (thin ? "--thin-depth" : "--select-depth") +
+                             "' above 1 are not built yet: costs run at depth 1");
+        if (thin && a.thin_scored)
+            throw UsageError(std::string("error: ") + both + " with '--thin-panel true --thin-tm' are not built yet: "
+                             "the held thinning has no cost form");
+        a.primer_costs_on = true;
     }
     if (a.seed_mismatches >= 0 || !a.seed_tm_text.empty() || !a.seed_thal.empty() || !a.seed_3p_exact_text.empty()) {
         if (!a.devices.empty())
@@ -1567,6 +1609,191 @@ SelectResult select_panel_weighted(const std::vector<std::vector<uint64_t>> &row
     return select_panel_rule(rows, primers, g, max_tubes, min_gain, forced, &weights, &sums);
 }
 
+// a beats b under the cost rule: the greater gain / cost by the cross products (gains and costs are below 2^32, so
+// the products are exact in 64 bits), then the greater gain; the caller walks by ascending index and asks "beats"
+// strictly, which leaves the lowest index among equals
+static bool cost_beats(uint64_t gain_a, uint32_t cost_a, uint64_t gain_b, uint32_t cost_b)
+{
+    const uint64_t ab = gain_a * (uint64_t)cost_b, ba = gain_b * (uint64_t)cost_a;
+    return ab != ba ? ab > ba : gain_a > gain_b;
+}
+
+// what both cost twins end with: the two cost sums, and the two weights (without weights: the two covered counts)
+static void cost_sums(const std::vector<char> &keep, const std::vector<uint32_t> &costs,
+                      const std::vector<uint64_t> &all, const std::vector<uint64_t> &covered,
+                      const std::vector<uint32_t> *weights, size_t covered_all, size_t covered_kept, CostSums &sums)
+{
+    for (size_t p = 0; p < keep.size(); ++p) {
+        sums.cost_all += costs[p];
+        if (keep[p]) sums.cost_kept += costs[p];
+    }
+    if (!weights) {
+        sums.weight_all = covered_all;
+        sums.weight_kept = covered_kept;
+        return;
+    }
+    for (size_t w = 0; w < all.size(); ++w) {
+        sums.weight_all += word_gain(all[w], w, weights);
+        sums.weight_kept += word_gain(covered[w], w, weights);
+    }
+}
+
+ThinResult thin_panel_cost(const std::vector<std::vector<uint64_t>> &rows, const std::vector<uint32_t> *weights,
+                           const std::vector<uint32_t> &costs, long long min_gain, const std::vector<char> &forced,
+                           CostSums &sums)
+{
+    sums = CostSums{};
+    const size_t n = rows.size();
+    size_t words = 0;
+    for (const auto &r : rows) words = std::max(words, r.size());
+    auto word = [&](size_t p, size_t w) { return w < rows[p].size() ? rows[p][w] : 0ull; };
+    ThinResult out;
+    out.keep.assign(n, 0);
+    std::vector<uint64_t> covered(words, 0), all(words, 0);
+    for (size_t p = 0; p < n; ++p) {
+        out.keep[p] = p < forced.size() && forced[p] ? 1 : 0;
+        for (size_t w = 0; w < words; ++w) {
+            all[w] |= word(p, w);
+            if (out.keep[p]) covered[w] |= word(p, w);
+        }
+    }
+    for (;;) {   // every round from scratch: the device keeps its gains up to date instead
+        long best = -1;
+        uint64_t best_gain = 0;
+        for (size_t p = 0; p < n; ++p) {
+            if (out.keep[p]) continue;
+            uint64_t gain = 0;
+            for (size_t w = 0; w < words; ++w) gain += word_gain(word(p, w) & ~covered[w], w, weights);
+            if ((long long)gain < min_gain) continue;   // no candidate, whatever its ratio
+            if (best < 0 || cost_beats(gain, costs[p], best_gain, costs[(size_t)best])) {
+                best = (long)p;
+                best_gain = gain;
+            }
+        }
+        if (best < 0) break;
+        out.order.push_back((int)best);
+        sums.gains.push_back((uint32_t)best_gain);
+        out.keep[(size_t)best] = 1;
+        for (size_t w = 0; w < words; ++w) covered[w] |= word((size_t)best, w);
+    }
+    for (size_t w = 0; w < words; ++w) {
+        out.covered_all += (size_t)__builtin_popcountll(all[w]);
+        out.covered_kept += (size_t)__builtin_popcountll(covered[w]);
+    }
+    cost_sums(out.keep, costs, all, covered, weights, out.covered_all, out.covered_kept, sums);
+    return out;
+}
+
+SelectResult select_panel_cost(const std::vector<std::vector<uint64_t>> &rows, const std::vector<std::string> &primers,
+                               const ConflictGraph &g, const std::vector<uint32_t> *weights,
+                               const std::vector<uint32_t> &costs, int max_tubes, long long min_gain,
+                               const std::vector<char> &forced, CostSums &sums)
+{
+    sums = CostSums{};
+    const size_t n = rows.size();
+    size_t words = 0;
+    for (const auto &r : rows) words = std::max(words, r.size());
+    auto word = [&](size_t p, size_t w) { return w < rows[p].size() ? rows[p][w] : 0ull; };
+    auto is_forced = [&](size_t p) { return p < forced.size() && forced[p]; };
+    std::vector<std::set<size_t>> adj;
+    std::vector<char> self;
+    select_graph(primers, g, adj, self);
+    const uint64_t all_tubes = max_tubes >= 64 ? ~0ull : (1ull << max_tubes) - 1;
+    SelectResult out;
+    out.keep.assign(n, 0);
+    out.tube.assign(n, -1);
+    out.barred.assign(n, 0);
+    std::vector<uint64_t> covered(words, 0), all(words, 0), mask(n, 0);
+    for (size_t p = 0; p < n; ++p) {
+        out.keep[p] = is_forced(p) ? 1 : 0;
+        for (size_t w = 0; w < words; ++w) {
+            all[w] |= word(p, w);
+            if (is_forced(p)) covered[w] |= word(p, w);
+        }
+        if (is_forced(p))   // the panel is in every tube
+            for (size_t u : adj[p]) mask[u] = all_tubes;
+    }
+    for (;;) {   // every round from scratch: the device keeps its gains up to date instead
+        long best = -1;
+        uint64_t best_gain = 0;
+        for (size_t p = 0; p < n; ++p) {
+            if (out.keep[p] || self[p] || (mask[p] & all_tubes) == all_tubes) continue;
+            uint64_t gain = 0;
+            for (size_t w = 0; w < words; ++w) gain += word_gain(word(p, w) & ~covered[w], w, weights);
+            if ((long long)gain < min_gain) continue;   // no candidate, whatever its ratio
+            if (best < 0 || cost_beats(gain, costs[p], best_gain, costs[(size_t)best])) {
+                best = (long)p;
+                best_gain = gain;
+            }
+        }
+        ++out.rounds;
+        if (best < 0) break;
+        const size_t p = (size_t)best;
+        const int t = __builtin_ctzll(~mask[p] & all_tubes);
+        out.order.push_back((int)best);
+        sums.gains.push_back((uint32_t)best_gain);
+        out.keep[p] = 1;
+        out.tube[p] = t;
+        out.tubes_used = std::max(out.tubes_used, t + 1);
+        for (size_t w = 0; w < words; ++w) covered[w] |= word(p, w);
+        for (size_t u : adj[p]) mask[u] |= 1ull << t;
+    }
+    for (size_t p = 0; p < n; ++p)
+        out.barred[p] = !out.keep[p] && (self[p] || (mask[p] & all_tubes) == all_tubes) ? 1 : 0;
+    for (size_t w = 0; w < words; ++w) {
+        out.covered_all += (size_t)__builtin_popcountll(all[w]);
+        out.covered_kept += (size_t)__builtin_popcountll(covered[w]);
+    }
+    out.covered = covered;
+    cost_sums(out.keep, costs, all, covered, weights, out.covered_all, out.covered_kept, sums);
+    return out;
+}
+
+std::string cost_line(uint64_t cost_kept, uint64_t cost_all, size_t n_kept, size_t n_all)
+{
+    return "  Cost:     " + std::to_string(cost_kept) + "/" + std::to_string(cost_all) + " by the kept " +
+           std::to_string(n_kept) + " of " + std::to_string(n_all) + "\n";
+}
+
+std::map<std::string, uint32_t> read_primer_costs(const std::string &path, int kmer_size)
+{
+    const char *option = "--primer-costs";
+    std::ifstream f(path, std::ios::binary);
+    if (!f) throw UsageError(std::string("error: cannot read '") + path + "' for '" + option + "'");
+    const uint64_t limit = 0xFFFFFFFFull;
+    std::map<std::string, uint32_t> out;
+    std::string line;
+    size_t no = 0;
+    while (std::getline(f, line)) {
+        ++no;
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (line.empty()) continue;
+        const std::string where = std::string("error: '") + option + "' " + path + " line " + std::to_string(no) + ": ";
+        const size_t c = line.find(',');
+        if (c == std::string::npos || c == 0 || line.find(',', c + 1) != std::string::npos)
+            throw UsageError(where + "expected 'sequence,cost'");
+        const std::string seq = line.substr(0, c), text = line.substr(c + 1);
+        if (seq.size() != (size_t)kmer_size || seq.find_first_not_of("ACGT") != std::string::npos)
+            throw UsageError(where + "sequence '" + seq + "' is not " + std::to_string(kmer_size) +
+                             " bases of A, C, G, T ('--kmer-size')");
+        char *end = nullptr;
+        errno = 0;
+        const unsigned long long x = std::strtoull(text.c_str(), &end, 10);
+        if (text.empty() || text.find_first_not_of("0123456789") != std::string::npos || *end || errno || x < 1 ||
+            x > limit)
+            throw UsageError(where + "cost '" + text + "' is not an integer in 1 .. " + std::to_string(limit));
+        out[seq] = (uint32_t)x;   // a sequence listed again: the later line holds
+    }
+    return out;
+}
+
+uint32_t primer_cost(uint32_t base, uint32_t per_site, uint64_t sites)
+{
+    const uint64_t limit = 0xFFFFFFFFull;
+    if (per_site && sites > limit / per_site) return (uint32_t)limit;   // the product alone is past the limit
+    return (uint32_t)std::min<uint64_t>(limit, (uint64_t)base + (uint64_t)per_site * sites);
+}
+
 std::string weight_line(uint64_t weight_all, uint64_t weight_kept, uint64_t weight_total, size_t n_all, size_t n_kept)
 {
     const std::string t = std::to_string(weight_total);
@@ -1914,7 +2141,7 @@ std::string thin_panel_on_device(Engine &eng, const DeviceAlignment &aln, std::v
                                  const std::vector<std::string> &panel_r, int segment_size, int overlap_size,
                                  int window_size, int kmer_size, int max_mismatches, int exact_3p, int min_gain,
                                  const msspe_chem *chem, int mode, float tm_threshold, int depth,
-                                 const std::vector<uint32_t> *genome_weights)
+                                 const std::vector<uint32_t> *genome_weights, const PrimerCostFn *costs)
 {
     // the new primers in their lists' order (stage A's selection order: ties go to the word with more postings), the
     // panel's behind them, forced
@@ -1940,8 +2167,22 @@ std::string thin_panel_on_device(Engine &eng, const DeviceAlignment &aln, std::v
     uint64_t weight_all = 0, weight_kept = 0, weight_total = 0;
     if (genome_weights)
         for (const uint32_t w : *genome_weights) weights.insert(weights.end(), P, w), weight_total += (uint64_t)w * P;
+    std::vector<uint32_t> cost;   // --primer-costs / --background-site-cost: the lists' primers, then the panel's
+    uint64_t cost_all = 0, cost_kept = 0;
+    if (costs) {
+        std::vector<std::string> words;
+        for (const auto *list : {&all_f, &all_r})
+            for (const auto &s : *list) words.push_back(s.word);
+        cost = (*costs)(words);
+    }
     const int rc =
-        genome_weights   // (depth 1, no chemistry: Args::parse refuses the rest)
+        costs   // (depth 1, no chemistry: Args::parse refuses the rest); with the weights when given
+            ? msspe_panel_thin_cost_packed_dev(eng.ctx(), aln.device(), aln.rows(), L, &opt, &mm, &thin, wf.data(),
+                                               (int)wf.size(), wr.data(), (int)wr.size(), forced.data(),
+                                               genome_weights ? weights.data() : nullptr, cost.data(), keep.data(),
+                                               order.data(), gains.data(), &n_picked, nullptr, &covered_all,
+                                               &covered_kept, &weight_all, &weight_kept, &cost_all, &cost_kept)
+        : genome_weights   // (depth 1, no chemistry: Args::parse refuses the rest)
             ? msspe_panel_thin_weighted_packed_dev(eng.ctx(), aln.device(), aln.rows(), L, &opt, &mm, &thin, wf.data(),
                                                    (int)wf.size(), wr.data(), (int)wr.size(), forced.data(),
                                                    weights.data(), keep.data(), order.data(), gains.data(), &n_picked,
@@ -1984,8 +2225,10 @@ std::string thin_panel_on_device(Engine &eng, const DeviceAlignment &aln, std::v
     const std::string block = thin_report(max_mismatches, exact_3p, min_gain, fwd.size(), n_f, rev.size(), n_r,
                                           panel_f.size() + panel_r.size(), (size_t)covered_all, (size_t)covered_kept,
                                           (size_t)aln.rows() * P, depth, (size_t)counts[2], (size_t)counts[3]);
-    if (!genome_weights) return block;
-    return with_weight_line(block, weight_line(weight_all, weight_kept, weight_total, n_f + n_r, fwd.size() + rev.size()));
+    std::string lines;   // behind "Segments:": the weights' line, then the costs'
+    if (genome_weights) lines += weight_line(weight_all, weight_kept, weight_total, n_f + n_r, fwd.size() + rev.size());
+    if (costs) lines += cost_line(cost_kept, cost_all, fwd.size() + rev.size() + panel_f.size() + panel_r.size(), n);
+    return lines.empty() ? block : with_weight_line(block, lines);
 }
 
 std::string select_report(int mode, float tm_threshold, int max_mismatches, int exact_3p, int min_gain, int max_tubes,
@@ -2023,7 +2266,7 @@ std::string select_panel_on_device(Engine &eng, const DeviceAlignment &aln, cons
                                    std::vector<KmerStat> &kept_r, std::map<std::string, int> &tubes,
                                    const std::function<void(const KmerStat &, bool)> &dropped,
                                    const NtthalOptions *end_rule, int depth,
-                                   const std::vector<uint32_t> *genome_weights)
+                                   const std::vector<uint32_t> *genome_weights, const PrimerCostFn *costs)
 {
     // the graph's nodes are distinct words: the panel's first, then the new primers in their lists' order; a word met
     // again (the other direction's list) is not offered
@@ -2056,6 +2299,8 @@ std::string select_panel_on_device(Engine &eng, const DeviceAlignment &aln, cons
     void *d_pool = nullptr, *d_bitmap = nullptr;
     std::vector<uint32_t> weights;   // --genome-weights: every segment of a row weighs what its genome weighs
     uint64_t weight_all = 0, weight_kept = 0, weight_total = 0;
+    std::vector<uint32_t> cost;
+    uint64_t cost_all = 0, cost_kept = 0;
     int rc = MSSPE_OK;
     if (n) {
         const std::vector<uint64_t> zero(n * W, 0);
@@ -2093,7 +2338,21 @@ std::string select_panel_on_device(Engine &eng, const DeviceAlignment &aln, cons
         const msspe_select_depth_opt deep{min_gain, max_tubes, drop_self_pairs ? 1 : 0, depth};
         if (genome_weights)
             for (const uint32_t w : *genome_weights) weights.insert(weights.end(), P, w), weight_total += (uint64_t)w * P;
-        rc = genome_weights   // (depth 1: Args::parse refuses the rest)
+        if (costs) {   // --primer-costs / --background-site-cost: the offered primers, then the panel's
+            std::vector<std::string> words;
+            for (const auto *list : {&all_f, &all_r})
+                for (const auto &s : *list) words.push_back(s.word);
+            cost = (*costs)(words);
+        }
+        rc = costs   // (depth 1: Args::parse refuses the rest); with the weights when given
+                 ? msspe_panel_select_cost_packed_dev(eng.ctx(), aln.device(), aln.rows(), L, &opt, &rule, &so,
+                                                      wf.data(), (int)wf.size(), wr.data(), (int)wr.size(),
+                                                      forced.data(), static_cast<const uint64_t *>(d_bitmap),
+                                                      genome_weights ? weights.data() : nullptr, cost.data(),
+                                                      keep.data(), order.data(), gains.data(), &n_picked, tube.data(),
+                                                      barred.data(), nullptr, &covered_all, &covered_kept, &used,
+                                                      &weight_all, &weight_kept, &cost_all, &cost_kept)
+             : genome_weights   // (depth 1: Args::parse refuses the rest)
                  ? msspe_panel_select_weighted_packed_dev(eng.ctx(), aln.device(), aln.rows(), L, &opt, &rule, &so,
                                                           wf.data(), (int)wf.size(), wr.data(), (int)wr.size(),
                                                           forced.data(), static_cast<const uint64_t *>(d_bitmap),
@@ -2141,9 +2400,16 @@ std::string select_panel_on_device(Engine &eng, const DeviceAlignment &aln, cons
                       kept_r.size(), rev.size(), n - new_f - new_r, n_barred, (size_t)covered_all, (size_t)covered_kept,
                       (size_t)aln.rows() * P, list_tubes ? &per_tube : nullptr, depth, (size_t)counts[2],
                       (size_t)counts[3]);
-    if (!genome_weights) return block;
-    return with_weight_line(block, weight_line(weight_all, weight_kept, weight_total, fwd.size() + rev.size(),
-                                               kept_f.size() + kept_r.size()));
+    std::string lines;   // behind "Segments:": the weights' line, then the costs'
+    if (genome_weights)
+        lines += weight_line(weight_all, weight_kept, weight_total, fwd.size() + rev.size(),
+                             kept_f.size() + kept_r.size());
+    if (costs) {
+        size_t n_kept = 0;
+        for (size_t p = 0; p < n; ++p) n_kept += keep[p];
+        lines += cost_line(cost_kept, cost_all, n_kept, n);
+    }
+    return lines.empty() ? block : with_weight_line(block, lines);
 }
 
 DeviceBackground::DeviceBackground(Engine &eng, const std::vector<SequenceRecord> &records)
@@ -2500,7 +2766,7 @@ Selection select_primers(Engine &eng, const DeviceAlignment &aln, const Args &ar
                          const NtthalOptions &opts, std::unique_ptr<DeviceBackground> &background,
                          const std::vector<std::string> &panel_f, const std::vector<std::string> &panel_r,
                          const std::vector<std::string> &excl_f, const std::vector<std::string> &excl_r, int round,
-                         PhaseTimer &timer, const std::vector<uint32_t> *genome_weights)
+                         PhaseTimer &timer, const std::vector<uint32_t> *genome_weights, const PrimerCostFn *costs)
 {
     Selection sel;
     auto reject = [&](const KmerStat &s, const char *reason) {
@@ -2593,7 +2859,7 @@ Selection select_primers(Engine &eng, const DeviceAlignment &aln, const Args &ar
             std::max(1, args.tubes), args.tubes > 0, cfg.check_cross_dimers, !cfg.check_self_dimers, opts.dg,
             sel.good_f, sel.good_r, sel.tubes,
             [&](const KmerStat &s, bool barred) { reject(s, barred ? "select_conflict" : "select_unneeded"); }, &opts,
-            args.select_depth, genome_weights);
+            args.select_depth, genome_weights, costs);
         timer.lap("stage C + selection by coverage");
         return sel;
     }
@@ -2647,6 +2913,9 @@ int run(const Args &args, std::string &stdout_text)
         const size_t P = L < (size_t)args.window_size ? 0 : (L - (size_t)args.window_size) / (size_t)args.overlap_size + 1;
         genome_weights = read_genome_weights(args.genome_weights, records, args.default_genome_weight, P);
     }
+    std::map<std::string, uint32_t> listed_costs;   // --primer-costs: likewise
+    if (args.primer_costs_on && !args.primer_costs.empty())
+        listed_costs = read_primer_costs(args.primer_costs, args.kmer_size);
     timer.lap("read + to_records");
 
     const int auto_mm = (int)std::min<size_t>(10, std::max<size_t>(1, (records.size() + 49) / 50));
@@ -2691,12 +2960,32 @@ int run(const Args &args, std::string &stdout_text)
     // Round 0 is the run itself: the user's panel and exclusions.  --repick-rounds: round r >= 1 keeps what passed
     // (the user's panel plus everything kept so far is its panel), bans what failed (the user's exclusions plus
     // everything rejected so far) and lets stage A fill the holes; kept primers are never removed by a later round.
+    // --primer-costs / --background-site-cost: a primer's listed or default cost, plus the site cost times its
+    // background sites, counted as --max-background-sites counts them (the first round has uploaded the background)
+    const PrimerCostFn cost_fn = [&](const std::vector<std::string> &words) {
+        std::vector<uint32_t> out(words.size());
+        std::vector<std::pair<uint64_t, uint64_t>> sites(words.size(), {0, 0});
+        if (args.background_site_cost && background) {
+            if (args.background_scored)
+                (void)background->scored(words, args.background_mismatches, args.background_3p_exact, ntthal_chem(opts),
+                                         bg_mode, args.background_tm, sites, args.background_flank);
+            else
+                sites = background->sites(words, args.background_mismatches, args.background_3p_exact);
+        }
+        for (size_t i = 0; i < words.size(); ++i) {
+            const auto it = listed_costs.find(words[i]);
+            out[i] = primer_cost(it == listed_costs.end() ? args.default_primer_cost : it->second,
+                                 args.background_site_cost, sites[i].first + sites[i].second);
+        }
+        return out;
+    };
+    const PrimerCostFn *costs = args.primer_costs_on ? &cost_fn : nullptr;
     std::vector<Selection> rounds;
     std::vector<std::string> kept_f(panel_f), kept_r(panel_r), ban_f(banned.first), ban_r(banned.second);
     std::string rounds_text;
     for (int round = 0;; ++round) {
         Selection s = select_primers(eng, aln, args, cfg, opts, background, kept_f, kept_r, ban_f, ban_r, round, timer,
-                                     genome_weights.empty() ? nullptr : &genome_weights);
+                                     genome_weights.empty() ? nullptr : &genome_weights, costs);
         for (const auto &p : s.good_f) kept_f.push_back(p.word);
         for (const auto &p : s.good_r) kept_r.push_back(p.word);
         for (const auto &r : s.rejected) (r.direction == SEQ_DIR_FWD ? ban_f : ban_r).push_back(r.word);
@@ -2738,7 +3027,7 @@ int run(const Args &args, std::string &stdout_text)
                                          args.search_windows_size, args.kmer_size, args.thin_mismatches,
                                          args.thin_3p_exact, args.thin_min_gain, args.thin_scored ? &thin_chem : nullptr,
                                          args.thin_thal == "end1" ? 2 : 1, args.thin_tm, args.thin_depth,
-                                         genome_weights.empty() ? nullptr : &genome_weights);
+                                         genome_weights.empty() ? nullptr : &genome_weights, costs);
         timer.lap("panel thinning");
     }
     // the report covers the panel and the new primers together; the CSV lists the new ones, numbered on from the panel

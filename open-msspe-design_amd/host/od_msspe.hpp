@@ -122,6 +122,16 @@ struct Args {
     // is in weight units, and the block gains a "Weight:" line behind "Segments:".  Empty: nothing changes.
     std::string genome_weights;
     int default_genome_weight = 1;
+    // --primer-costs <file> / --background-site-cost <c> (with --thin-panel true without --thin-tm, or
+    // --select-by-coverage true; depth 1, one device): every primer gets a cost -- its line "sequence,cost" of the file
+    // (cost 1 .. 2^32 - 1, the later of two lines holds) or --default-primer-cost, plus c times its background sites
+    // as --max-background-sites counts them, saturating at 2^32 - 1 -- and the thinning / the selection of every round
+    // picks by gain per cost (msspe_panel_thin_cost_packed_dev / msspe_panel_select_cost_packed_dev),
+    // with the weights of --genome-weights when given; the block gains a "Cost:" line.  Empty: nothing changes.  The
+    // texts are read only with one of the two switches; primer_costs_on says that a cost option is in force.
+    std::string primer_costs, default_primer_cost_text, background_site_cost_text;
+    uint32_t default_primer_cost = 1, background_site_cost = 0;
+    bool primer_costs_on = false;
     // --seed-mismatches M: a round that seeds stage A (with --existing-primers, and rounds >= 1 of --repick-rounds)
     // seeds it on what the panel COVERS -- every segment of the direction in which a panel primer has a match within M
     // mismatches, its last seed_3p_exact bases exact (msspe_kmer_candidates_both_tolerant_packed_dev) -- instead of
@@ -379,6 +389,36 @@ SelectResult select_panel_weighted(const std::vector<std::vector<uint64_t>> &row
                                    const std::vector<std::string> &primers, const ConflictGraph &g,
                                    const std::vector<uint32_t> &weights, int max_tubes, long long min_gain,
                                    const std::vector<char> &forced, WeightedSums &sums);
+// --primer-costs / --background-site-cost (engine extension): the rules of thin_panel and select_panel with the pick by
+// gain per cost.  costs[p] >= 1, one per row.  weights (optional): a weight per segment as in the
+// weighted twins; without them a gain is a count.  A round considers the live primers whose gain is at least min_gain
+// and picks the greatest gain / cost -- by 64-bit cross products, never a division -- then the greater gain, then the
+// lowest index.  The gains go to sums.gains (the result's own gains stay empty); without weights weight_all /
+// weight_kept are the two covered counts; cost_all / cost_kept: the costs' sum over all rows and over the kept ones.
+// The device's independent twins, every round from scratch.
+struct CostSums {
+    std::vector<uint32_t> gains;
+    uint64_t weight_all = 0, weight_kept = 0, cost_all = 0, cost_kept = 0;
+};
+ThinResult thin_panel_cost(const std::vector<std::vector<uint64_t>> &rows, const std::vector<uint32_t> *weights,
+                           const std::vector<uint32_t> &costs, long long min_gain, const std::vector<char> &forced,
+                           CostSums &sums);
+SelectResult select_panel_cost(const std::vector<std::vector<uint64_t>> &rows, const std::vector<std::string> &primers,
+                               const ConflictGraph &g, const std::vector<uint32_t> *weights,
+                               const std::vector<uint32_t> &costs, int max_tubes, long long min_gain,
+                               const std::vector<char> &forced, CostSums &sums);
+// "  Cost:     K/A by the kept m of n": the line a block carries behind "  Segments:" (behind "  Weight:" when present).
+// K and A are the costs of the kept primers and of all primers of the call, m and n their numbers; the panel's forced
+// primers count in all four.
+std::string cost_line(uint64_t cost_kept, uint64_t cost_all, size_t n_kept, size_t n_all);
+// --primer-costs: a cost per primer sequence from lines "sequence,cost".  A line that is not "sequence,cost" with
+// kmer_size bases A/C/G/T and an integer cost in 1 .. 2^32 - 1 is a usage error that names the line; a sequence listed
+// twice takes the later line.
+std::map<std::string, uint32_t> read_primer_costs(const std::string &path, int kmer_size);
+// base + per_site * sites, saturating at 2^32 - 1 (--background-site-cost)
+uint32_t primer_cost(uint32_t base, uint32_t per_site, uint64_t sites);
+// the costs of a list of primers, in its order: what the thinning and the selection ask for the lists they see
+using PrimerCostFn = std::function<std::vector<uint32_t>(const std::vector<std::string> &words)>;
 // --select-depth R (engine extension): the layered rule of DESIGN.md 4.16 over the same rows and graph, n_seg segments
 // (bits of a row).  cnt[s] = kept primers that match s, from the forced rows on; layers r = 1 .. min(R, max(1, deepest
 // segment)): in layer r a segment is open while cnt < min(r, primers that match it), a round picks the live primer
@@ -412,7 +452,8 @@ std::string select_panel_on_device(Engine &eng, const DeviceAlignment &aln, cons
                                    std::vector<KmerStat> &kept_r, std::map<std::string, int> &tubes,
                                    const std::function<void(const KmerStat &, bool)> &dropped,
                                    const NtthalOptions *end_rule = nullptr, int depth = 1,
-                                   const std::vector<uint32_t> *genome_weights = nullptr);
+                                   const std::vector<uint32_t> *genome_weights = nullptr,
+                                   const PrimerCostFn *costs = nullptr);
 // "Panel selection by coverage (<the match rule>, gain >= G, tubes <= T):", the rule line, the primers kept of those
 // offered (forced ones apart), the primers barred, the segments covered (mode 0) or held (modes 1, 2) by all of them
 // and by the kept ones, and with per_tube the primers per tube; depth above 1 (--select-depth R): ", depth R" closes
@@ -430,7 +471,10 @@ std::string thin_panel_on_device(Engine &eng, const DeviceAlignment &aln, std::v
                                  const std::vector<std::string> &panel_r, int segment_size, int overlap_size,
                                  int window_size, int kmer_size, int max_mismatches, int exact_3p, int min_gain,
                                  const msspe_chem *chem = nullptr, int mode = 1, float tm_threshold = 0.0f,
-                                 int depth = 1, const std::vector<uint32_t> *genome_weights = nullptr);
+                                 int depth = 1, const std::vector<uint32_t> *genome_weights = nullptr,
+                                 const PrimerCostFn *costs = nullptr);
+// costs (--primer-costs / --background-site-cost; depth 1, no chemistry): msspe_panel_thin_cost_packed_dev /
+// msspe_panel_select_cost_packed_dev instead, with the weights when given, and the block carries cost_line
 // depth above 1 (--thin-depth R): msspe_panel_thin_depth_packed_dev / msspe_panel_thin_thal_depth_packed_dev instead;
 // the block's first line gains ", depth R" and a line "  Depth:    at least R primers on u/t segments by all Y, on
 // v/t by the kept X" follows "Segments:" (thin_report / thin_thal_report with depth, deep_all = u, deep_kept = v).

@@ -50,6 +50,8 @@ EXPORTS = [
     "msspe_panel_select_depth_packed_dev", "msspe_panel_select_depth_rule",
     "msspe_panel_thin_weighted", "msspe_panel_thin_weighted_dev", "msspe_panel_thin_weighted_packed_dev",
     "msspe_panel_select_weighted_dev", "msspe_panel_select_weighted_packed_dev", "msspe_panel_select_weighted_rule",
+    "msspe_panel_thin_cost", "msspe_panel_thin_cost_dev", "msspe_panel_thin_cost_packed_dev",
+    "msspe_panel_select_cost_dev", "msspe_panel_select_cost_packed_dev", "msspe_panel_select_cost_rule",
     "msspe_device_put_stream_packed", "msspe_background_sites_packed_dev", "msspe_background_sites",
     "msspe_background_thal_packed_dev", "msspe_background_thal",
     "msspe_background_amplicons_packed_dev", "msspe_background_amplicons",
@@ -379,6 +381,14 @@ def load_library() -> C.CDLL:
     L.msspe_panel_select_weighted_dev.argtypes = select_in + [vp, vp] + select_out + wsums
     L.msspe_panel_select_weighted_packed_dev.argtypes = select_in + [vp, vp] + select_out + wsums
     L.msspe_panel_select_weighted_rule.argtypes = select_in + [C.POINTER(Chem), rulep, vp] + select_out + wsums
+    # the cost forms: the weighted sibling's arguments with the costs behind the weights and the two cost sums last
+    L.msspe_panel_thin_cost.argtypes = (L.msspe_panel_thin.argtypes[:12] + [vp, vp] +
+                                        L.msspe_panel_thin.argtypes[12:] + wsums + wsums)
+    L.msspe_panel_thin_cost_dev.argtypes = L.msspe_panel_thin_cost.argtypes
+    L.msspe_panel_thin_cost_packed_dev.argtypes = L.msspe_panel_thin_cost.argtypes
+    L.msspe_panel_select_cost_dev.argtypes = select_in + [vp, vp, vp] + select_out + wsums + wsums
+    L.msspe_panel_select_cost_packed_dev.argtypes = select_in + [vp, vp, vp] + select_out + wsums + wsums
+    L.msspe_panel_select_cost_rule.argtypes = select_in + [C.POINTER(Chem), rulep, vp, vp] + select_out + wsums + wsums
     L.msspe_device_put_stream_packed.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int,
                                                  C.POINTER(vp), C.POINTER(C.c_size_t), vp]
     L.msspe_background_sites_packed_dev.argtypes = [vp, vp, C.c_size_t, C.c_int, C.POINTER(MismatchOpt), u64p, C.c_int,
@@ -1298,8 +1308,29 @@ class Engine:
         return self._panel_thin(fn, (), genomes, opt, fwd, rev, max_mismatches, exact_3p, min_gain, forced, form,
                                 weights=weights)
 
+    @staticmethod
+    def _primer_costs(costs, n: int) -> np.ndarray:
+        c = np.asarray(costs)
+        if c.shape != (n,):
+            raise ValueError("costs needs one entry per primer (forward list, then reverse list)")
+        if c.size and (c.min() < 0 or c.max() > 0xFFFFFFFF):
+            raise ValueError("a cost must fit a uint32")
+        return np.ascontiguousarray(c, dtype=np.uint32)
+
+    def panel_thin_cost(self, genomes, opt: KmerOpt, fwd, rev, max_mismatches: int, exact_3p: int, costs, weights=None,
+                        min_gain: int = 1, forced=None, form: str = "host"):
+        """panel_thin by gain per cost (msspe_panel_thin_cost*): a round keeps the primer of greatest gain / cost among
+        those whose gain reaches min_gain, compared exactly (equal ratios: the greater gain, then the lowest index).
+        costs: one integer 1 .. 2^32 - 1 per primer, forward list then reverse list.  weights: as panel_thin_weighted,
+        or None for a count of segments.  Arguments and forms as panel_thin.  Returns panel_thin_weighted's tuple plus
+        cost_all, cost_kept (without weights the two weights are the two covered counts)."""
+        fn = {"host": self.L.msspe_panel_thin_cost, "dev": self.L.msspe_panel_thin_cost_dev,
+              "packed": self.L.msspe_panel_thin_cost_packed_dev}[form]
+        return self._panel_thin(fn, (), genomes, opt, fwd, rev, max_mismatches, exact_3p, min_gain, forced, form,
+                                weights=weights, costs=costs)
+
     def _panel_thin(self, fn, scoring, genomes, opt, fwd, rev, max_mismatches, exact_3p, min_gain, forced, form,
-                    depth=None, weights=None):
+                    depth=None, weights=None, costs=None):
         owned = None
         if isinstance(genomes, tuple):
             if form == "host":
@@ -1333,7 +1364,15 @@ class Engine:
             n_picked, c_all, c_kept = C.c_int(0), C.c_longlong(0), C.c_longlong(0)
             mm = MismatchOpt(max_mismatches, exact_3p)
             extra_in = ()
-            if weights is not None:
+            if costs is not None:
+                w = None if weights is None else self._segment_weights(weights, n_seq * P)
+                c = self._primer_costs(costs, n)
+                w_all, w_kept, k_all, k_kept = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+                thin = ThinOpt(min_gain)
+                extra_in = (None if w is None else w.ctypes.data, c.ctypes.data)
+                outs = (covered.ctypes.data, C.byref(c_all), C.byref(c_kept), C.byref(w_all), C.byref(w_kept),
+                        C.byref(k_all), C.byref(k_kept))
+            elif weights is not None:
                 w = self._segment_weights(weights, n_seq * P)
                 w_all, w_kept = C.c_uint64(0), C.c_uint64(0)
                 thin = ThinOpt(min_gain)
@@ -1354,6 +1393,9 @@ class Engine:
         finally:
             if owned is not None:
                 self.device_free(owned)
+        if costs is not None:
+            return (keep, order[:n_picked.value].copy(), gains[:n_picked.value].copy(), covered, int(c_all.value),
+                    int(c_kept.value), int(w_all.value), int(w_kept.value), int(k_all.value), int(k_kept.value))
         if weights is not None:
             return (keep, order[:n_picked.value].copy(), gains[:n_picked.value].copy(), covered, int(c_all.value),
                     int(c_kept.value), int(w_all.value), int(w_kept.value))
@@ -1393,10 +1435,24 @@ class Engine:
         return self._panel_select(None, genomes, opt, fwd, rev, rule, bitmap, max_tubes, min_gain, drop_self_pairs,
                                   forced, form, chem, threshold, end_tm_threshold, weights=weights)
 
+    def panel_select_cost(self, genomes, opt: KmerOpt, fwd, rev, rule: SeedRule, costs, weights=None, bitmap=None,
+                          max_tubes: int = 1, min_gain: int = 1, drop_self_pairs: bool = False, forced=None,
+                          form: str = "dev", chem: Chem | None = None, threshold: float | None = -9000.0,
+                          end_tm_threshold: float | None = None):
+        """panel_select by gain per cost (msspe_panel_select_cost*): a round keeps the live primer of greatest gain /
+        cost among those whose gain reaches min_gain, compared exactly (equal ratios: the greater gain, then the
+        lowest index).  costs: one integer 1 .. 2^32 - 1 per primer, forward list then reverse list.  weights: as
+        panel_select_weighted, or None for a count of segments.  Arguments and forms as panel_select_weighted.  Returns
+        its dict plus cost_all and cost_kept (without weights the two weights are the two covered counts)."""
+        if form not in ("dev", "packed", "screen"):
+            raise ValueError("form must be 'dev', 'packed' or 'screen'")
+        return self._panel_select(None, genomes, opt, fwd, rev, rule, bitmap, max_tubes, min_gain, drop_self_pairs,
+                                  forced, form, chem, threshold, end_tm_threshold, weights=weights, costs=costs)
+
     def _panel_select(self, _depth, genomes, opt, fwd, rev, rule, bitmap, max_tubes, min_gain, drop_self_pairs, forced,
-                      form, chem, threshold, end_tm_threshold, weights=None):
+                      form, chem, threshold, end_tm_threshold, weights=None, costs=None):
         """panel_select (_depth None) and panel_select_depth: the same inputs, the calls' own outputs; with weights,
-        panel_select_weighted."""
+        panel_select_weighted; with costs, panel_select_cost."""
         if form not in ("bitmap", "dev", "packed", "screen"):
             raise ValueError("form must be 'bitmap', 'dev', 'packed' or 'screen'")
         f, r = _words(fwd), _words(rev)
@@ -1423,7 +1479,7 @@ class Engine:
                     seqs_arg = C.c_void_p(owned[-1])
             if form == "screen":
                 chem = chem or Chem.ntthal()
-                if end_tm_threshold is not None or weights is not None:   # the weighted screen takes the rule only
+                if end_tm_threshold is not None or weights is not None or costs is not None:   # these take the rule only
                     conflict_rule = ConflictRule.of(threshold, end_tm_threshold)
                     graph = (C.byref(chem), C.byref(conflict_rule))
                 elif threshold is None:
@@ -1453,6 +1509,9 @@ class Engine:
             if weights is not None:
                 fn = {"dev": self.L.msspe_panel_select_weighted_dev, "packed": self.L.msspe_panel_select_weighted_packed_dev,
                       "screen": self.L.msspe_panel_select_weighted_rule}[form]
+            if costs is not None:
+                fn = {"dev": self.L.msspe_panel_select_cost_dev, "packed": self.L.msspe_panel_select_cost_packed_dev,
+                      "screen": self.L.msspe_panel_select_cost_rule}[form]
             P = 0 if seq_len < opt.segment_size else (seq_len - opt.segment_size) // opt.overlap_size + 1
             flags = None if forced is None else np.ascontiguousarray(np.asarray(forced) != 0, dtype=np.uint8)
             if flags is not None and flags.shape != (n,):
@@ -1486,6 +1545,14 @@ class Engine:
                 w = self._segment_weights(weights, n_seq * P)
                 w_all, w_kept = C.c_uint64(0), C.c_uint64(0)
                 extra_in, extra_out = (w.ctypes.data,), (C.byref(w_all), C.byref(w_kept))
+            if costs is not None:
+                c = self._primer_costs(costs, n)
+                k_all, k_kept = C.c_uint64(0), C.c_uint64(0)
+                if weights is None:
+                    w_all, w_kept = C.c_uint64(0), C.c_uint64(0)
+                    extra_in, extra_out = (None,), (C.byref(w_all), C.byref(w_kept))
+                extra_in += (c.ctypes.data,)
+                extra_out += (C.byref(k_all), C.byref(k_kept))
             self._check(fn(self.ptr, seqs_arg, n_seq, seq_len, C.byref(opt), C.byref(rule), C.byref(sel),
                            f.ctypes.data, len(f), r.ctypes.data, len(r),
                            flags.ctypes.data if flags is not None else None, *graph, *extra_in, keep.ctypes.data,
@@ -1495,6 +1562,12 @@ class Engine:
         finally:
             for d in owned:
                 self.device_free(d)
+        if costs is not None:
+            return {"keep": keep, "order": order[:n_picked.value].copy(), "gains": gains[:n_picked.value].copy(),
+                    "tube": tube[:n].copy(), "barred": barred[:n].copy(), "covered": covered,
+                    "covered_all": int(c_all.value), "covered_kept": int(c_kept.value), "tubes_used": int(used.value),
+                    "weight_all": int(w_all.value), "weight_kept": int(w_kept.value),
+                    "cost_all": int(k_all.value), "cost_kept": int(k_kept.value)}
         if weights is not None:
             return {"keep": keep, "order": order[:n_picked.value].copy(), "gains": gains[:n_picked.value].copy(),
                     "tube": tube[:n].copy(), "barred": barred[:n].copy(), "covered": covered,
