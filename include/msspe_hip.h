@@ -170,6 +170,14 @@ const char *msspe_version(void);
  *                                 to that list as not culled since the last read ("bound_survivors" counts what the
  *                                 exact-unit and packed instances append to hand-over list 0; the windowed one appends
  *                                 none, behind it "bound_list_survivors" holds the pairs no bound could cull)
+ *   "pair_bound_list_packed" "auto" | "0" | "1"  where the bound list stage runs behind the packed or the windowed first
+ *                                 stage, its PACKED instance runs in its place (k_pairs_bound_list_packed: the packed first
+ *                                 stage's unit, tables and cull rule, the value in the slot word beside the coordinates --
+ *                                 half the slot registers, four waves per SIMD).  A pair of that list then meets the very
+ *                                 bound the packed first stage applies to the pairs it keeps.  "1": wherever that
+ *                                 applies; "auto" (the default): the same for screens of 2^23 pairs and more; "0": the
+ *                                 exact-unit list kernel.  A coarser bound only culls fewer pairs; decisions are the exact
+ *                                 stages' either way
  *   "stage_a_graph" "0" | "1"   hipGraph replay of stage A's greedy loop (1)
  *   "stage_a_candidates" "0" | "1"  greedy loop over the list of words near the maximum (1), or over all the
  *                                 words on every iteration (0); the winners are the same */
@@ -330,6 +338,12 @@ int msspe_cross_dimer_bound_window_dev(msspe_ctx *ctx, const uint64_t *d_pool, i
  * The block may hold at most as many pairs as a hand-over list (2^20 .. 2^30: it grows with the call). */
 int msspe_cross_dimer_bound_list_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const msspe_chem *chem,
                                      float dg_threshold, int row0, int row1, int col0, int col1, double *d_bound);
+/* The same plane from the PACKED instances of both stages (options "pair_bound_packed" and "pair_bound_list_packed"):
+ * the same pairs carry a value, +inf and -inf as in msspe_cross_dimer_bound_list_dev; every value is an integer multiple of
+ * the packed unit (1, 2 or 4 cal/mol).  MSSPE_ERR_ARG also where the chemistry's range of cell values fits none of those
+ * units. */
+int msspe_cross_dimer_bound_list_packed_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const msspe_chem *chem,
+                                            float dg_threshold, int row0, int row1, int col0, int col1, double *d_bound);
 
 /* One pool screened against another (engine extension: the reference screens one pool of one --kmer-size,
  * od-msspe/src/delta_g.rs:61-81; ntthal itself takes any two oligos).  Pool A: n_a oligos of k_a bases, oligo 1

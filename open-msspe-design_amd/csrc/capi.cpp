@@ -125,6 +125,10 @@ struct EngineOptions {
                               // window, one candidate stands for all rows above; what it does not cull goes to list U) -- 0 never |
                               // 1 wherever the packed instance would run, the chemistry's entry is usable (ChemEntry::window_ok) and
                               // pair_bound_list is on | 2 auto: the same, from kWindowAutoMinPairs pairs per screen
+    int pair_bound_list_packed = 2;  // the bound list stage runs its packed instance (k_pairs_bound_list_packed: one register per
+                              // slot, the packed first stage's units and cull rule, 1,024 threads) -- 0 never | 1 wherever the bound
+                              // list stage runs behind the packed or the windowed first stage | 2 auto: the same, from
+                              // kWindowAutoMinPairs pairs per screen
     bool split_list = true;   // short oligos: tables too large for the integer list stage go to the split kernel's list mode
     bool short_chain = true;  // screens of up to 2^23 pairs: integer list stage -> one wave per pair (no register-table stages between)
     int self_lane_from = 81920;   // oligos per call from which SELF_ANY / SELF_END run one lane per oligo (msspe_oligo_stats_dev)
@@ -838,6 +842,10 @@ int msspe_set_option(msspe_ctx *ctx, const char *key, const char *value)
         if (v == "auto") ctx->opt.pair_bound_packed = 2;
         else if (is_num && (num == 0 || num == 1)) ctx->opt.pair_bound_packed = (int)num;
         else return bad();
+    } else if (k == "pair_bound_list_packed") {
+        if (v == "auto") ctx->opt.pair_bound_list_packed = 2;
+        else if (is_num && (num == 0 || num == 1)) ctx->opt.pair_bound_list_packed = (int)num;
+        else return bad();
     } else if (k == "pair_bound_list") {
         if (v == "auto") ctx->opt.pair_bound_list = 2;
         else if (is_num && (num == 0 || num == 1)) ctx->opt.pair_bound_list = (int)num;
@@ -935,6 +943,7 @@ int msspe_get_info(msspe_ctx *ctx, const char *key, long long *value_out)
     else if (k == "pair_mirror") *value_out = ctx->opt.pair_mirror;
     else if (k == "pair_bound_list") *value_out = ctx->opt.pair_bound_list;
     else if (k == "pair_bound_packed") *value_out = ctx->opt.pair_bound_packed;
+    else if (k == "pair_bound_list_packed") *value_out = ctx->opt.pair_bound_list_packed;
     else if (k == "pair_bound_window") *value_out = ctx->opt.pair_bound_window;
     else if (k == "bound_window_survivors") {
         // ordered pairs the windowed first stage could not cull and sent to list U since the last read of this key (reading
@@ -1150,6 +1159,7 @@ struct ChainRoute {
     bool bound_list = false;   // Bound, BoundMirror: the bound list stage runs at every flush (option pair_bound_list)
     bool bound_packed = false; // Bound, BoundMirror: the packed instance is the first stage (option pair_bound_packed)
     bool bound_window = false; // ... and of it the windowed instance (option pair_bound_window; needs bound_list)
+    bool bound_list_packed = false; // bound_list behind bound_packed: the list stage's packed instance (option pair_bound_list_packed)
     StageList behind;   // the list stages behind a first stage other than Dense, in order
 };
 
@@ -1214,6 +1224,12 @@ static int settle_first_stage(msspe_ctx *ctx, ChemEntry *ce, const ScreenBlock &
     const long n_pairs = (long)(b.row1 - b.row0) * (long)b.sinks.ncols;
     route.bound_window = route.bound_packed && route.bound_list && ce->window_ok && cs == hipStreamCaptureStatusNone &&
                          (ctx->opt.pair_bound_window == 1 || (ctx->opt.pair_bound_window == 2 && n_pairs >= kWindowAutoMinPairs));
+    // The bound list stage's packed instance, behind the packed or the windowed first stage only: list U then meets the very
+    // bound (unit and cull rule) the packed first stage applies to the lanes it keeps.  auto: from the window's pair count --
+    // below it list U is a few thousand entries, the flush is launch latency, and the finer exact-unit bound costs nothing.
+    route.bound_list_packed = route.bound_list && route.bound_packed &&
+                              (ctx->opt.pair_bound_list_packed == 1 ||
+                               (ctx->opt.pair_bound_list_packed == 2 && n_pairs >= kWindowAutoMinPairs));
     return MSSPE_OK;
 }
 
@@ -1273,7 +1289,8 @@ static int run_chain(msspe_ctx *ctx, ChemEntry *ce, ChainRoute route, const Scre
             a.overflow_count = ctx->ovf_count;
             a.overflow_cap = (uint32_t)ctx->list_cap;
             HIP_TRY(ctx, launch_pairs_bound_list(a, ce->d_bt, u_list, u_count, ctx->d_reasons + kBoundListStats, nullptr,
-                                                 ctx->n_cu, ctx->stream));
+                                                 ctx->n_cu, ctx->stream, route.bound_list_packed ? ce->d_btq : nullptr,
+                                                 ce->packed_bias, ce->packed_shift));
         }
         return ListChain(ctx, ce, end1, ctx->ovf_list, ctx->list_cap).run(route.behind, a, g, true);
     };
@@ -1458,7 +1475,7 @@ int msspe_cross_dimer_edges_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, i
 // their -inf.
 static int cross_dimer_bound_plane(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const msspe_chem *chem,
                                    float dg_threshold, int row0, int row1, int col0, int col1, double *d_bound, bool with_list,
-                                   bool packed = false, bool window = false)
+                                   bool packed = false, bool window = false)   // with_list and packed: both stages' packed instances
 {
     const ScreenBlock b = screen_block(d_pool, n, k, k, row0, row1, col0, col1, plane_sinks(nullptr, nullptr, nullptr, nullptr));
     ChemEntry *ce = nullptr;
@@ -1492,8 +1509,10 @@ static int cross_dimer_bound_plane(msspe_ctx *ctx, const uint64_t *d_pool, int n
     }
     uint32_t *const u_count = ctx->ovf_count + kOvfU;
     HIP_TRY(ctx, hipMemsetAsync(u_count, 0, sizeof(uint32_t), ctx->stream));
-    HIP_TRY(ctx, launch_pairs_bound(a, ce->d_it, ce->d_bt, nullptr, d_bound, ctx->n_cu, ctx->stream, false, ctx->ovf_list2, u_count));
-    HIP_TRY(ctx, launch_pairs_bound_list(a, ce->d_bt, ctx->ovf_list2, u_count, nullptr, d_bound, ctx->n_cu, ctx->stream));
+    HIP_TRY(ctx, launch_pairs_bound(a, ce->d_it, ce->d_bt, nullptr, d_bound, ctx->n_cu, ctx->stream, false, ctx->ovf_list2, u_count,
+                                    packed ? ce->d_btq : nullptr, ce->packed_bias, ce->packed_shift));
+    HIP_TRY(ctx, launch_pairs_bound_list(a, ce->d_bt, ctx->ovf_list2, u_count, nullptr, d_bound, ctx->n_cu, ctx->stream,
+                                         packed ? ce->d_btq : nullptr, ce->packed_bias, ce->packed_shift));
     HIP_TRY(ctx, hipMemsetAsync(u_count, 0, sizeof(uint32_t), ctx->stream));
     return MSSPE_OK;
 }
@@ -1520,6 +1539,12 @@ int msspe_cross_dimer_bound_list_dev(msspe_ctx *ctx, const uint64_t *d_pool, int
                                      float dg_threshold, int row0, int row1, int col0, int col1, double *d_bound)
 {
     return cross_dimer_bound_plane(ctx, d_pool, n, k, chem, dg_threshold, row0, row1, col0, col1, d_bound, true);
+}
+
+int msspe_cross_dimer_bound_list_packed_dev(msspe_ctx *ctx, const uint64_t *d_pool, int n, int k, const msspe_chem *chem,
+                                            float dg_threshold, int row0, int row1, int col0, int col1, double *d_bound)
+{
+    return cross_dimer_bound_plane(ctx, d_pool, n, k, chem, dg_threshold, row0, row1, col0, col1, d_bound, true, true);
 }
 
 double msspe_t_cut(float tm_threshold) { return t_cut(tm_threshold); }

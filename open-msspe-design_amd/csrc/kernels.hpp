@@ -161,8 +161,12 @@ int pairs_bound_max_k();
 // nothing; a survivor is appended unmarked to a.overflow_list (in both orders when its twin bit is set), behind what the
 // first stage put there.  stats (optional): [0] += entries of U, [1] += ordered pairs appended.  bound_plane != nullptr:
 // the diagnostic form -- the value of every entry goes to the plane (layout of launch_pairs_bound's) and nothing else is written.
+// packed_q != nullptr (BoundPacked::q on the device, with its bias and shift): the PACKED instance runs
+// (k_pairs_bound_list_packed: one register per slot, 1,024 threads) -- the same contract in the packed first stage's
+// coarse units and with its cull rule; the plane's values are multiples of the unit.
 hipError_t launch_pairs_bound_list(const PairKernelArgs &a, const BoundTables *bt, uint2 *u_list, const uint32_t *u_count,
-                                   unsigned long long *stats, double *bound_plane, int n_cu, hipStream_t stream);
+                                   unsigned long long *stats, double *bound_plane, int n_cu, hipStream_t stream,
+                                   const BoundTables *packed_q = nullptr, int packed_bias = 0, int packed_shift = 0);
 hipError_t pairs_row_lds_reads_zero(hipStream_t stream, int n_cu, bool *ok);   // does this device read 0 beyond a block's LDS allocation?
 // List mode of the integer stage: retries the pairs of in_list that carry no "needs f64" mark (bit
 // 31 of .x) with a 64-slot table in lanes sorted by table size; everything else passes through.

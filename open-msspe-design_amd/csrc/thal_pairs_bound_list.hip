@@ -50,19 +50,67 @@ constexpr int kBLEmptyW = 0xff00;                        // coordinates (15, 15)
 static_assert(IntTables::kRows == 14 * 16 + 14 + 1, "rows 16 l2 + l1 with l1, l2 <= 14 are the table's own row count");
 static_assert(kSlotsList == 64 && kListStoredMax == kSlotsList - 1, "64 slots, one kept free for the last row's writes");
 
-struct SharedBL {
-    int T[IntTables::kRows * 64 + 4];   // + the "not available" entry the clamp lands on
+// ---- the PACKED instance (k_pairs_bound_list_packed): the same minimum on BoundPacked's coarse tables, one register per
+// slot -- the packed first stage's arithmetic (thal_pairs_row.hip, "the PACKED bound instance") on this stage's layout.
+// The slot word is  W << 15 | (value + bias):  W the 16-bit coordinate word above, whose bits 0 and 1 are zero, so bits
+// 15 and 16 of the slot word are zero as in the first stage's  K << 17 | field;  the field is BoundPacked's 15 bits.  The
+// cell's minuend carries 0x7fff in its low 15 bits, so  t = C - word  never borrows into the coordinates:  t >> 15  is the
+// byte offset into the image, and the low 16 bits of t are  u = 0x7fff - bias - value.  The subtraction SATURATES at 0
+// (v_sub_u32 clamp) and the image lies one row down, its row 0 void: a slot whose coordinate difference is negative
+// (a column beyond the cell's, the empty word) reads entry 0 with u = 0, and no clamp of the offset is needed -- it is
+// at most the minuend's, which lies inside the image.  The minuend's coordinates must not be negative themselves: a cell
+// of column 0, which has no predecessor, takes the minuend 0.  A slot of the cell's own row (l1 = -1) lands on a row
+// 16 l2 + 15 + 1, void in the image as in the exact-unit instance.  The image holds  Tn = kPLOff - entry  and 0 for void
+// or "not available", so  u + Tn - y = kc - (entry + y + value)  with kc = 0x7fff - bias + kPLOff: the running MAXIMUM
+// of it is the minimum over the candidates.  64 slot registers instead of 128: the kernel fits 128 VGPRs, i.e. four waves
+// per SIMD at 1,024 threads.
+// The field: BoundPacked's proven range [lo, hi] does not depend on how many cells a table stores -- it counts a left
+// end term plus at most max_k - 1 steps (a chain of 13-mers has at most 13 pairs, whatever the table's size), and a cell
+// is at most its left end term -- so it holds for the 53..63 stored cells of this stage as it stands.
+constexpr int kPLThreads = 1024;
+constexpr int kPLC = kC;            // slots per chunk of the packed scan
+constexpr int kPLBatch = kBLBatch;   // passes per sorted batch of the packed instance
+constexpr int kPLReach = BoundPacked::kReach;   // every coarse term, every bias and every reachable sum is below this
+constexpr int kPLOff = 1 << 28;                 // a real entry is stored as kPLOff - entry (> 0); stored 0: void / not available
+constexpr int kPLYVoid = 1 << 26;               // a void cell-side term
+constexpr int kPLInit = 1 << 24;                // the pick's starting minimum
+static_assert(kPLInit >= 2 * kPLReach, "above every cell value plus an end term");
+static_assert((long long)kPLOff - kPLReach - kPLYVoid > 0x7fffLL + kPLReach,
+              "a candidate built on a real entry (u + Tn - y, a void cell-side term included) is above every candidate built on "
+              "a stored 0 (u - y <= 0x7fff + kPLReach): a 0 is never the maximum beside a real one");
+static_assert((long long)kPLOff + kPLReach + 0x7fffLL + kPLReach < 0x7fffffffLL && -(long long)kPLYVoid > -0x7fffffffLL,
+              "largest and smallest u + Tn - y are int32s");
+static_assert((long long)kPLOff - 3LL * kPLReach > kPLReach,
+              "an accumulator that saw stored 0s only (at most 0x7fff + kPLReach) decodes, as kc - acc with bias below kPLReach, "
+              "above every left end term");
+static_assert(kPLYVoid - 2 * kPLReach > kPLReach, "a candidate that holds a void cell-side term stays above every left end term");
+static_assert((long long)0x7fff + kPLOff + kPLYVoid + kPLReach < 0x7fffffffLL, "kc - acc is an int32");
+constexpr int kPLEmptyW = kBLEmptyW << 15;   // coordinates (15, 15), field 0: every difference goes negative
+static_assert(kPLEmptyW > 0 && ((unsigned)kBLEmptyW << 15) < 0x80000000u, "the empty slot word keeps bit 31 clear");
+constexpr int kPLRowShift = 64;              // entries the image lies down by: one void row
+// the largest minuend (a lane past its last cell computes on coordinates up to 15): column 15, row 15, po 0
+constexpr unsigned kPLMaxOffset = (14u << 12) + (15u << 8) + 252u;
+static_assert(kPLMaxOffset < (unsigned)kBLEmptyW, "the empty word is above every minuend: it always saturates");
+static_assert(kPLMaxOffset / 4u < IntTables::kRows * 64u + 4u + kPLRowShift, "every offset (at most the minuend's) lies inside the image");
+
+// NT: the block's threads; NB: passes per sorted batch
+template <bool PACKED, int NT, int NB>
+struct SharedBLT {
+    int T[IntTables::kRows * 64 + 4 + (PACKED ? kPLRowShift : 0)];   // + the "not available" entry the clamp lands on (+ the packed instance's void row 0)
     int g[kBLGCount];
-    uint2 sorted[kBLBatch * kBLThreads];
+    uint2 sorted[NB * NT];
     unsigned hist[256];
     unsigned next_batch;
 };
+typedef SharedBLT<false, kBLThreads, kBLBatch> SharedBL;
+typedef SharedBLT<true, kPLThreads, kPLBatch> SharedPL;
 
 // The LDS image of the loop table: row 16 l2 + l1, column 63 - po (load_tables_int<true>'s), from BoundTables::T, plus
-// the stacked pair in row 0.
-__device__ __forceinline__ void load_tables_bound(SharedBL &sh, const BoundTables *bt)
+// the stacked pair in row 0.  PACKED: bt holds the coarse terms, and an entry is stored as kPLOff - entry (see kPLOff).
+template <bool PACKED, int NT, int NB>
+__device__ __forceinline__ void load_tables_bound(SharedBLT<PACKED, NT, NB> &sh, const BoundTables *bt)
 {
-    for (int e = threadIdx.x; e < IntTables::kRows * 64 + 4; e += kBLThreads) {
+    for (int e = threadIdx.x; e < IntTables::kRows * 64 + 4; e += NT) {
         const int l2 = e >> 10, l1 = (e >> 6) & 15, po = 63 - (e & 63);
         int v = IntTables::kBig;
         if (e < IntTables::kRows * 64 && l1 <= IntTables::kMaxL) {
@@ -75,11 +123,13 @@ __device__ __forceinline__ void load_tables_bound(SharedBL &sh, const BoundTable
                 v = bt->T[(l1 * 16 + l2) * 64 + pe];
             }
         }
-        sh.T[e] = v >= IntTables::kValid ? kBLVoidT : v;
+        if constexpr (PACKED) sh.T[e + kPLRowShift] = v >= IntTables::kValid ? 0 : kPLOff - v;   // one row down: row 0 is void
+        else sh.T[e] = v >= IntTables::kValid ? kBLVoidT : v;
     }
-    for (int e = threadIdx.x; e < kBLGCount; e += kBLThreads) {
+    if (PACKED && threadIdx.x < kPLRowShift) sh.T[threadIdx.x] = 0;
+    for (int e = threadIdx.x; e < kBLGCount; e += NT) {
         const int v = bt->g[kBLGBase + e];
-        sh.g[e] = v >= IntTables::kValid ? kBLVoidY : v;   // (only cell-side terms can be void here)
+        sh.g[e] = v >= IntTables::kValid ? (PACKED ? kPLYVoid : kBLVoidY) : v;   // (only cell-side terms can be void here)
     }
     __syncthreads();
 }
@@ -172,9 +222,115 @@ __device__ __forceinline__ int run_pair_bound_list(const SharedBL &sh, const Seq
     return pick;
 }
 
+// ---- the packed instance's cell loop
+// the low 16 bits of t (u: bit 15 is zero) added to the image's entry: one instruction
+__device__ __forceinline__ int add_low16(unsigned t, int tn)
+{
+    int r;
+    asm("v_mad_u32_u16 %0, %1, 1, %2" : "=v"(r) : "v"(t), "v"(tn));
+    return r;
+}
+
+// scan_bound on the packed words: acc = max(acc, u + Tn - y) over all earlier slots (see kPLOff).
+template <int PC = 0>
+__device__ __forceinline__ void scan_bound_packed(const v32i Wa, const v32i Wb, int upto, int far_upto, const char *T, unsigned C,
+                                                  int yTS, int yMM, int &acc)
+{
+    if constexpr (PC * kPLC < kSlotsList) {
+        if (PC * kPLC < upto) {   // wave-uniform
+            unsigned t[kPLC], idx[kPLC];
+            int tn[kPLC];
+#pragma unroll
+            for (int e = 0; e < kPLC; ++e) {
+                t[e] = __builtin_elementwise_sub_sat(C, (unsigned)slot_of<64>(Wa, Wb, v8i{}, PC * kPLC + e));
+                idx[e] = t[e] >> 15;
+            }
+#pragma unroll
+            for (int e = 0; e < kPLC; ++e) tn[e] = *(const int *)(T + idx[e]);
+            if (PC * kPLC + kPLC <= far_upto) {   // wave-uniform: every lane has these slots >= 3 rows up (l1 >= 2)
+                asm volatile("" ::"n"(PC));   // keeps the chunks from being merged into selects
+#pragma unroll
+                for (int e = 0; e < kPLC; ++e) {
+                    // rows 0 .. 15 of the image are l2 = 0: a bulge, which takes no cell-side term
+                    const int y = idx[e] < 4096u ? 0 : yTS;
+                    acc = max(acc, add_low16(t[e], tn[e]) - y);
+                }
+            } else {
+                asm volatile("" ::"n"(PC + 64));
+#pragma unroll
+                for (int e = 0; e < kPLC; ++e) {
+                    // the image's row is 16 l2 + l1 + 1: bits 12.. hold l2 and bits 8 .. 11 l1 + 1 wherever l1 <= 14 (l1 = 15,
+                    // a slot of the cell's own row, carries into l2: those rows are void, whatever term they are given)
+                    const bool bulge = (idx[e] < 4096u) | ((idx[e] & 0xf00u) == 0x100u);   // l2 == 0 or l1 == 0 (the stacked pair: both)
+                    const bool m11 = (idx[e] & 0xff00u) == 0x1200u;                       // l1 == l2 == 1
+                    const int y = bulge ? 0 : (m11 ? yMM : yTS);
+                    acc = max(acc, add_low16(t[e], tn[e]) - y);
+                }
+            }
+            scan_bound_packed<PC + 1>(Wa, Wb, upto, far_upto, T, C, yTS, yMM, acc);
+        }
+    }
+}
+
+// run_pair_bound_list on the packed table: the same cells in the same order, the same slot for each, in coarse units;
+// kPLInit: the lane has no cell.  bias: BoundPacked::bias (wave-uniform).
+__device__ __forceinline__ int run_pair_bound_list_packed(const SharedPL &sh, const SeqPair &q, unsigned rowmask,
+                                                          int n_cells, int nmax, int bias)
+{
+    v32i Wa = kPLEmptyW, Wb = kPLEmptyW;
+    CellCtx c;
+    unsigned Rrem = rowmask, mrem = 0;
+    int im1 = 0, jm1 = 0;
+    int row_lo0 = 0, row_lo1 = 0, row_lo2 = 0;   // as run_pair_bound_list
+    const int kc = 0x7fff - bias + kPLOff;       // u + Tn - y = kc - (entry + y + predecessor's value)
+    int pick = kPLInit;
+    for (int slot_ = 0; slot_ < nmax; ++slot_) {
+        const int slot = __builtin_amdgcn_readfirstlane(slot_);
+        // ---- next complementary cell in row-major order (as run_pair_int)
+        const bool newrow = mrem == 0;
+        const int t = __ffs((int)Rrem) - 1;
+        const int a_new = (q.s1 >> (t & 31)) & 3;
+        const unsigned m_new = spaced_mask(q.s2, 3 - a_new, q.lenmask);
+        im1 = newrow ? (t >> 1) : im1;
+        row_lo2 = newrow ? row_lo1 : row_lo2;
+        row_lo1 = newrow ? row_lo0 : row_lo1;
+        row_lo0 = newrow ? slot : row_lo0;
+        Rrem = newrow ? (Rrem & (Rrem - 1)) : Rrem;
+        mrem = newrow ? m_new : mrem;
+        jm1 = (__ffs((int)mrem) - 1) >> 1;
+        mrem &= mrem - 1;
+        im1 &= 15;
+        jm1 &= 15;
+        const CellBases b = cell_bases(q, im1, jm1, c);
+        const bool in = slot < n_cells;   // lanes past their last cell compute garbage (every address stays in range)
+        const int far_upto = wave_min_64(in ? row_lo2 : 63);
+        // column 0 has no predecessor and its coordinate difference would start below zero: minuend 0, every slot saturates.
+        // (im1 << 8: row im1 - 1 of run_pair_bound_list's minuend and the one row the image lies down by)
+        const unsigned C = jm1 == 0 ? 0u : ((unsigned)(((jm1 - 1) << 12) + (im1 << 8) + 252) << 15) | 0x7fffu;
+        int acc = 0;   // below every candidate built on a real entry: decodes far above the left end term
+        scan_bound_packed<>(Wa, Wb, slot, far_upto, (const char *)sh.T, C, sh.g[c.yTS - kBLGBase], sh.g[c.yMM - kBLGBase], acc);
+        const int G0 = min(sh.g[b.idxL - kBLGBase], kc - acc);
+        pick = in ? min(pick, G0 + sh.g[b.idxR - kBLGBase]) : pick;
+        // G0 + bias is a 15-bit field: BoundPacked's proven range of every publishable value (a lane past its last cell
+        // publishes the empty word)
+        const int Wcell = in ? (int)((unsigned)((jm1 << 12) | (im1 << 8) | (b.po_c << 2)) << 15) + (G0 + bias) : kPLEmptyW;
+        // ---- publish the cell: one indexed write over the whole 64-register plane
+        const int ps = min(slot, kSlotsList - 1);   // wave-uniform
+        asm volatile("s_set_gpr_idx_on %[SLOT], gpr_idx(DST)\n\t"
+                     "v_mov_b32 v64, %[W]\n\t"
+                     "s_set_gpr_idx_off"
+                     : "+{v[64:95]}"(Wa), "+{v[96:127]}"(Wb)
+                     : [W] "v"(Wcell), [SLOT] "s"(ps)
+                     : "m0");
+    }
+    return pick;
+}
+
 // One lock-step pass of the wave: lane = one entry of U.  Every exit is wave-uniform (the batch loop's barriers and the
 // callers' counter fetches depend on it).
-__device__ __forceinline__ void wave_bound(const SharedBL &sh, const IntArgs &a, int row, int col, bool twin, bool inside)
+// PACKED: the packed instance's cell loop and units (a.bt: BoundPacked::q); everything around it is the same.
+template <bool PACKED, int NT, int NB>
+__device__ __forceinline__ void wave_bound(const SharedBLT<PACKED, NT, NB> &sh, const IntArgs &a, int row, int col, bool twin, bool inside)
 {
     const int lane = threadIdx.x & 63;
     SeqPair q;
@@ -189,13 +345,17 @@ __device__ __forceinline__ void wave_bound(const SharedBL &sh, const IntArgs &a,
     const bool active = inside & !pass_on & (n_cells > 0);
     if (!active) n_cells = 0;
     const int nmax = wave_max_u8(n_cells);
-    int pick = kBLInit;
-    if (nmax != 0) pick = run_pair_bound_list(sh, q, rowmask, n_cells, nmax);   // wave-uniform
-    const int lb = pick + a.bt->init;   // a lane without a chain keeps kBLInit: above every cut
+    constexpr int kInit = PACKED ? kPLInit : kBLInit;
+    int pick = kInit;
+    if (nmax != 0) {   // wave-uniform
+        if constexpr (PACKED) pick = run_pair_bound_list_packed(sh, q, rowmask, n_cells, nmax, __builtin_amdgcn_readfirstlane(a.packed_bias));
+        else pick = run_pair_bound_list(sh, q, rowmask, n_cells, nmax);
+    }
+    const int lb = pick + a.bt->init;   // a lane without a chain keeps kBLInit (kPLInit): above every cut
     if (a.bound_plane) {
         if (inside & !pass_on)
             a.bound_plane[(size_t)(row - a.f.sinks.row0) * (size_t)a.f.sinks.ncols + (size_t)(col - a.f.sinks.col0)] =
-                pick >= kBLInit ? INFINITY : (double)lb / BoundTables::kUnitInv;
+                pick >= kInit ? INFINITY : PACKED ? (double)lb * a.packed_unit : (double)lb / BoundTables::kUnitInv;
         return;
     }
     const bool out = pass_on | (active & (lb <= a.bt->cut));   // a culled pair is finished: it writes nothing
@@ -211,30 +371,32 @@ __device__ __forceinline__ void wave_bound(const SharedBL &sh, const IntArgs &a,
     }
 }
 
-__global__ void __launch_bounds__(kBLThreads) k_pairs_bound_list(IntArgs a, uint2 *u_list)
+// The block's work: NT threads, batches of depth x NT entries, depth <= NB.  (a by value, as the kernels take it: by
+// reference the exact-unit instance's scalar code comes out differently allocated.)
+template <bool PACKED, int NT, int NB>
+__device__ __forceinline__ void bound_list_block(SharedBLT<PACKED, NT, NB> &sh, const IntArgs a, uint2 *u_list)
 {
-    __shared__ SharedBL sh;
     if (*a.f.in_count == 0u) return;   // an empty list: no table loads
     load_tables_bound(sh, a.bt);
     const long n_work = (long)min(*a.f.in_count, a.f.ovf_cap);
     if (a.bound_list_stats && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&a.bound_list_stats[0], (unsigned long long)n_work);
-    // batches of depth x 512 entries, sorted together and run as `depth` lock-step passes (k_pairs_int_list's rule: a
+    // batches of depth x NT entries, sorted together and run as `depth` lock-step passes (k_pairs_int_list's rule: a
     // short list is spread over all the blocks).  Which pairs are culled does not depend on the depth.
-    const long per_pass = (long)gridDim.x * kBLThreads;
-    const int depth = (int)min((long)kBLBatch, max(1L, (n_work + per_pass - 1) / per_pass));
-    const long batch = (long)depth * kBLThreads;
+    const long per_pass = (long)gridDim.x * NT;
+    const int depth = (int)min((long)NB, max(1L, (n_work + per_pass - 1) / per_pass));
+    const long batch = (long)depth * NT;
     const long n_batches = (n_work + batch - 1) / batch;
     for (;;) {
         if (threadIdx.x == 0) sh.next_batch = atomicAdd(a.work_counter, 1u);
-        for (int e = threadIdx.x; e < 256; e += kBLThreads) sh.hist[e] = 0u;
+        for (int e = threadIdx.x; e < 256; e += NT) sh.hist[e] = 0u;
         __syncthreads();
         const long bt = (long)sh.next_batch;
         if (bt >= n_batches) break;   // block-uniform
-        uint2 mine[kBLBatch];
-        int key[kBLBatch];
+        uint2 mine[NB];
+        int key[NB];
 #pragma unroll
-        for (int j = 0; j < kBLBatch; ++j) {
-            const long w = bt * batch + (long)j * kBLThreads + threadIdx.x;
+        for (int j = 0; j < NB; ++j) {
+            const long w = bt * batch + (long)j * NT + threadIdx.x;
             const bool inside = (j < depth) & (w < n_work);   // passes beyond the depth hold padding only
             mine[j] = inside ? u_list[w] : make_uint2(0xffffffffu, 0u);
             int nc = 255;   // padding sorts last
@@ -268,11 +430,11 @@ __global__ void __launch_bounds__(kBLThreads) k_pairs_bound_list(IntArgs a, uint
         }
         __syncthreads();
 #pragma unroll
-        for (int j = 0; j < kBLBatch; ++j) sh.sorted[atomicAdd(&sh.hist[key[j]], 1u)] = mine[j];
+        for (int j = 0; j < NB; ++j) sh.sorted[atomicAdd(&sh.hist[key[j]], 1u)] = mine[j];
         __syncthreads();
         const long n_own = min(batch, n_work - bt * batch);
         for (int j = 0; j < depth; ++j) {
-            const long e = (long)j * kBLThreads + threadIdx.x;
+            const long e = (long)j * NT + threadIdx.x;
             const bool inside = e < n_own;
             const uint2 pr = sh.sorted[inside ? e : 0];
             wave_bound(sh, a, (int)(pr.x & ~(kNeedsF64 | kListTwin)), (int)pr.y, (pr.x & kListTwin) != 0u, inside);
@@ -281,12 +443,30 @@ __global__ void __launch_bounds__(kBLThreads) k_pairs_bound_list(IntArgs a, uint
     }
 }
 
+__global__ void __launch_bounds__(kBLThreads) k_pairs_bound_list(IntArgs a, uint2 *u_list)
+{
+    __shared__ SharedBL sh;
+    bound_list_block(sh, a, u_list);
+}
+
+// The packed instance: a.bt holds BoundPacked::q, a.packed_bias its bias (launch_pairs_bound_list).
+__global__ void __launch_bounds__(kPLThreads) k_pairs_bound_list_packed(IntArgs a, uint2 *u_list)
+{
+    __shared__ SharedPL sh;
+    bound_list_block(sh, a, u_list);
+}
+
 }  // namespace
 
 hipError_t launch_pairs_bound_list(const PairKernelArgs &a, const BoundTables *bt, uint2 *u_list, const uint32_t *u_count,
-                                   unsigned long long *stats, double *bound_plane, int n_cu, hipStream_t stream)
+                                   unsigned long long *stats, double *bound_plane, int n_cu, hipStream_t stream,
+                                   const BoundTables *packed_q, int packed_bias, int packed_shift)
 {
     if (a.k > 13 || a.k < 2 || !bt || !u_list || !u_count || (!bound_plane && (!a.overflow_list || !a.overflow_count)))
+        return hipErrorInvalidValue;
+    // packed_q: BoundPacked::q on the device -- the packed instance runs (same contract, coarse units)
+    if (packed_q && (packed_shift < BoundPacked::kShiftMin || packed_shift > BoundPacked::kShiftMax || packed_bias < 0 ||
+                     packed_bias >= BoundPacked::kReach))
         return hipErrorInvalidValue;
     IntArgs x;
     FastArgs &f = x.f;
@@ -314,6 +494,13 @@ hipError_t launch_pairs_bound_list(const PairKernelArgs &a, const BoundTables *b
     x.bound_plane = bound_plane;
     x.bound_list_stats = stats;
     if (hipError_t e = hipMemsetAsync(a.work_counter, 0, sizeof(unsigned), stream); e != hipSuccess) return e;
+    if (packed_q) {
+        x.bt = packed_q;
+        x.packed_bias = packed_bias;
+        x.packed_unit = (double)(1 << (packed_shift - BoundPacked::kShiftMin));
+        hipLaunchKernelGGL(k_pairs_bound_list_packed, dim3(n_cu), dim3(kPLThreads), 0, stream, x, u_list);
+        return hipGetLastError();
+    }
     hipLaunchKernelGGL(k_pairs_bound_list, dim3(n_cu), dim3(kBLThreads), 0, stream, x, u_list);
     return hipGetLastError();
 }

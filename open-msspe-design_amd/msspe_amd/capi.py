@@ -16,7 +16,7 @@ EXPORTS = [
     "msspe_last_error", "msspe_version", "msspe_set_option", "msspe_get_info", "msspe_kmer_trace", "msspe_set_stream", "msspe_reset_stream",
     "msspe_synchronize",
     "msspe_pack_oligos", "msspe_unpack_oligo", "msspe_cross_dimer_dev", "msspe_cross_dimer",
-    "msspe_cross_dimer_edges_dev", "msspe_cross_dimer_edges", "msspe_cross_dimer_bound_dev", "msspe_cross_dimer_bound_list_dev", "msspe_cross_dimer_bound_packed_dev", "msspe_cross_dimer_bound_window_dev", "msspe_host_bound_tables", "msspe_host_bound_packed", "msspe_host_bound_window", "msspe_host_bound_mirror_ok",
+    "msspe_cross_dimer_edges_dev", "msspe_cross_dimer_edges", "msspe_cross_dimer_bound_dev", "msspe_cross_dimer_bound_list_dev", "msspe_cross_dimer_bound_list_packed_dev", "msspe_cross_dimer_bound_packed_dev", "msspe_cross_dimer_bound_window_dev", "msspe_host_bound_tables", "msspe_host_bound_packed", "msspe_host_bound_window", "msspe_host_bound_mirror_ok",
     "msspe_cross_dimer_ab_dev", "msspe_cross_dimer_ab_edges_dev", "msspe_cross_dimer_ab", "msspe_cross_dimer_ab_edges",
     "msspe_cross_dimer_edges_mixed",
     "msspe_cross_dimer_end_dev", "msspe_cross_dimer_end", "msspe_cross_dimer_end_edges_dev", "msspe_cross_dimer_end_edges",
@@ -237,6 +237,7 @@ def load_library() -> C.CDLL:
     L.msspe_cross_dimer_bound_dev.argtypes = [vp, u64p, C.c_int, C.c_int, C.POINTER(Chem), C.c_float,
                                               C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.msspe_cross_dimer_bound_list_dev.argtypes = L.msspe_cross_dimer_bound_dev.argtypes
+    L.msspe_cross_dimer_bound_list_packed_dev.argtypes = L.msspe_cross_dimer_bound_dev.argtypes
     L.msspe_cross_dimer_bound_packed_dev.argtypes = L.msspe_cross_dimer_bound_dev.argtypes
     L.msspe_cross_dimer_bound_window_dev.argtypes = L.msspe_cross_dimer_bound_dev.argtypes
     L.msspe_host_bound_window.argtypes = [C.c_char_p, C.POINTER(Chem), C.c_float, C.POINTER(C.c_int32)]
@@ -784,6 +785,14 @@ class Engine:
         its value; -inf only for two self-complementary oligos and more than 63 stored cells.
         msspe_cross_dimer_bound_list_dev."""
         self._check(self.L.msspe_cross_dimer_bound_list_dev(
+            self.ptr, C.c_void_p(d_pool), n, k, C.byref(chem), C.c_float(threshold), rows[0], rows[1], cols[0],
+            cols[1], C.c_void_p(d_bound)))
+
+    def cross_dimer_bound_list_packed_dev(self, d_pool: int, n: int, k: int, chem: Chem, threshold: float,
+                                          rows: tuple[int, int], cols: tuple[int, int], d_bound: int):
+        """cross_dimer_bound_list_dev's plane from the packed instances of both stages (options pair_bound_packed and
+        pair_bound_list_packed): values are multiples of the packed unit.  msspe_cross_dimer_bound_list_packed_dev."""
+        self._check(self.L.msspe_cross_dimer_bound_list_packed_dev(
             self.ptr, C.c_void_p(d_pool), n, k, C.byref(chem), C.c_float(threshold), rows[0], rows[1], cols[0],
             cols[1], C.c_void_p(d_bound)))
 
