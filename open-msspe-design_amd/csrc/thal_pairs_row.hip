@@ -44,8 +44,8 @@
 #include "row_scan_pinned.inc"
 #include "row_bound_pinned.inc"
 #include "row_bound_packed_pinned.inc"
-#include "row_bound_window_pinned.inc"
-#include "row_bound_window_pair_pinned.inc"
+#include "row_bound_ring_pinned.inc"
+#include "row_bound_ring_pair_pinned.inc"
 
 
 namespace msspe {
@@ -866,54 +866,79 @@ static __device__ __forceinline__ void packed_publish(v32i &Wa, v16i &Wb, v4i &W
 // <= i-1-F holds, whatever its column; Ifar / Bfar: the smallest finite coarse table entry over l1 >= F with l2 >= 1 /
 // l2 = 0, any context (fast_tables.hpp BoundWindow).  That candidate is at most every candidate it replaces, so by
 // induction over the cells the value is at most the packed instance's: a lower bound all the same.
-// The scan enters the unrolled chunks at the chunk of row i-F's first slot (a scalar); slots of higher rows in that chunk
-// are visited exactly, which cannot lower the value below the far candidate's.  The empty slot word carries 0x7fff in
+// The scan visits the slots of rows i-F .. i-1 and no other (the ring below).  The empty slot word carries 0x7fff in
 // its field here: its candidate stays 0 (never the maximum), and the fold below leaves farmin alone for it.
-static_assert(MSSPE_BWN13_KC == MSSPE_BPK13_KC && MSSPE_BWN13_W0 == MSSPE_BPK13_W0, "one register map for both packed scans");
-static constexpr int kWinF = MSSPE_BWN13_F;
+static constexpr int kWinF = 2;                           // rows of the window: the ring holds rows i-2 and i-1 (and row i's own bank)
 static constexpr int kWinNone = BoundPacked::kFieldMax;   // farmin without a cell (BoundWindow: no real field reaches it)
 static constexpr int kWinVoid = kPkYVoid;                 // a void Ifar / Bfar, and the far candidate of an empty far set
 static_assert(kWinVoid == BoundWindow::kVoid, "the host's void constant is the kernel's");
 static_assert(kWinVoid - kPkReach - kPkReach > kPkReach, "a far candidate that holds a void stays above every left end term");
 
-static __device__ __forceinline__ void window_scan(const v32i Wa, const v16i Wb, const v4i Wc, unsigned C, int Y, int n_far,
-                                                int n_run, int near_from, int start, int &acc_far, int &acc_near)
+// The window's rows live in a RING of three banks of 16 registers in place of the linear table (v76..v91, v92..v107,
+// v108..v123; tools/gen_row_bound_packed_asm.py --ring): row i in bank i % 3, its c-th cell in register
+// 76 + 16 * (i % 3) + c.  A cell of row i visits bank (i-2) % 3 slots 0 .. w(i-2)-1 into the far accumulator and bank
+// (i-1) % 3 slots 0 .. w(i-1)-1 into the near one, and no other register: no chunk straddles two rows and none reaches
+// above the window.  A bank keeps row i-3's words beyond a narrower row i's width; they are never visited (a stale word
+// in the near role would miss the cell-side term build_bound_table took out of its entry).
+static_assert(MSSPE_BRG13_KC == MSSPE_BPK13_KC && MSSPE_BRG13_W0 == MSSPE_BPK13_W0 && MSSPE_BRG13_BANK == 16, "the ring's register map");
+static_assert(MSSPE_BRP13_KC == MSSPE_BRG13_KC && MSSPE_BRP13_W0 == MSSPE_BRG13_W0 && MSSPE_BRP13_BANK == MSSPE_BRG13_BANK &&
+              MSSPE_BRP13_GRAN == MSSPE_BRG13_GRAN && MSSPE_BRP13_NSZ == MSSPE_BRG13_NSZ,
+              "the two-cell scan is the ring scan's: same banks, chunks and widths");
+static constexpr int kRingBank = MSSPE_BRG13_BANK;
+static constexpr int kRingGran = MSSPE_BRG13_GRAN;   // 1: a row's exact width is scanned; 2: rows padded to an even width
+static_assert(kRowK <= kRingBank - (kRingGran - 1), "a row (and its pad slot) fits a bank");
+
+// rot: i % 3; wf, wn: the (padded) widths of rows i-2 and i-1, 0 for a row that does not exist -- all wave-uniform
+struct RingCtl { int idx, wf, wn, wmax; };
+static __device__ __forceinline__ RingCtl ring_ctl(int rot, int wf, int wn)
 {
-    int MSSPE_BWN13_TEMP_NAMES;
-    asm volatile(MSSPE_BWN13_SCAN_ASM
-                 : MSSPE_BWN13_ACC_OUT(acc_far, acc_near), MSSPE_BWN13_TEMPS_OUT
-                 : [C] "v"(C), [Y] "v"(Y), [NFAR] "s"(n_far), [NRUN] "s"(n_run), [NEAR] "s"(near_from), [START] "s"(start),
-                   [TOFF] "n"((int)offsetof(SharedRow, T)), MSSPE_BWN13_TUPLES_IN(Wa, Wb, Wc)
-                 : MSSPE_BWN13_SCAN_CLOBBERS);
+    constexpr int kC4 = MSSPE_BRG13_KC, kN = MSSPE_BRG13_NSZ;
+    return {(rot * kN + min(wf, kC4) / kRingGran) * kN + min(wn, kC4) / kRingGran, wf, wn, max(wf, wn)};
 }
-// Two cells A, B of one row in one pass (tools/gen_row_bound_packed_asm.py --window F --pair): the scalars are the row's,
-// the entry tree and every chunk's tests run once for both, the two cells' table reads share one pipeline.
-static_assert(MSSPE_BWP13_F == MSSPE_BWN13_F && MSSPE_BWP13_KC == MSSPE_BWN13_KC && MSSPE_BWP13_W0 == MSSPE_BWN13_W0,
-              "the two-cell scan is the windowed scan's: same window, chunks and register map");
-static __device__ __forceinline__ void window_scan_pair(const v32i Wa, const v16i Wb, const v4i Wc, unsigned CA, int YA,
-                                                     unsigned CB, int YB, int n_far, int n_run, int near_from, int start,
-                                                     int &far_a, int &near_a, int &far_b, int &near_b)
+static __device__ __forceinline__ void ring_scan(const v16i Ra, const v16i Rb, const v16i Rc, unsigned C, const RingCtl &r,
+                                              int &acc_far, int &acc_near)
 {
-    int MSSPE_BWP13_TEMP_NAMES;
-    asm volatile(MSSPE_BWP13_SCAN_ASM
-                 : MSSPE_BWP13_ACC_OUT(far_a, near_a, far_b, near_b), MSSPE_BWP13_TEMPS_OUT
-                 : [CA] "v"(CA), [YA] "v"(YA), [CB] "v"(CB), [YB] "v"(YB), [NFAR] "s"(n_far), [NRUN] "s"(n_run),
-                   [NEAR] "s"(near_from), [START] "s"(start), [TOFF] "n"((int)offsetof(SharedRow, T)),
-                   MSSPE_BWP13_TUPLES_IN(Wa, Wb, Wc)
-                 : MSSPE_BWP13_SCAN_CLOBBERS);
+    int MSSPE_BRG13_TEMP_NAMES;
+    asm volatile(MSSPE_BRG13_SCAN_ASM
+                 : MSSPE_BRG13_ACC_OUT(acc_far, acc_near), MSSPE_BRG13_TEMPS_OUT
+                 : [C] "v"(C), [IDX] "s"(r.idx), [WF] "s"(r.wf), [WN] "s"(r.wn), [WMAX] "s"(r.wmax),
+                   [TOFF] "n"((int)offsetof(SharedRow, T)), MSSPE_BRG13_TUPLES_IN(Ra, Rb, Rc)
+                 : MSSPE_BRG13_SCAN_CLOBBERS);
 }
-// slot: wave-uniform, < kRowSlots.  farmin = min(farmin, the slot's field); bit 15 of the word is zero.  The word is
+// Two cells A, B of one row in one pass (--ring --pair): the controls are the row's, the dispatch runs once for both,
+// the two cells' table reads share one pipeline.
+static __device__ __forceinline__ void ring_scan_pair(const v16i Ra, const v16i Rb, const v16i Rc, unsigned CA, unsigned CB,
+                                                   const RingCtl &r, int &far_a, int &near_a, int &far_b, int &near_b)
+{
+    int MSSPE_BRP13_TEMP_NAMES;
+    asm volatile(MSSPE_BRP13_SCAN_ASM
+                 : MSSPE_BRP13_ACC_OUT(far_a, near_a, far_b, near_b), MSSPE_BRP13_TEMPS_OUT
+                 : [CA] "v"(CA), [CB] "v"(CB), [IDX] "s"(r.idx), [WF] "s"(r.wf), [WN] "s"(r.wn), [WMAX] "s"(r.wmax),
+                   [TOFF] "n"((int)offsetof(SharedRow, T)), MSSPE_BRP13_TUPLES_IN(Ra, Rb, Rc)
+                 : MSSPE_BRP13_SCAN_CLOBBERS);
+}
+// reg: wave-uniform, bank * 16 + cell.  packed_publish's indexed write over the three banks.
+static __device__ __forceinline__ void ring_publish(v16i &Ra, v16i &Rb, v16i &Rc, int reg, int Wcell)
+{
+    asm volatile("s_set_gpr_idx_on %[SLOT], gpr_idx(DST)\n\t"
+                 "v_mov_b32 v%c[W0], %[W]\n\t"
+                 "s_set_gpr_idx_off"
+                 : MSSPE_BRG13_TUPLES_INOUT(Ra, Rb, Rc)
+                 : [W] "v"(Wcell), [SLOT] "s"(reg), [W0] "n"(MSSPE_BRG13_W0)
+                 : "m0");
+}
+// reg: wave-uniform, bank * 16 + cell.  farmin = min(farmin, the slot's field); bit 15 of the word is zero.  The word is
 // fetched with the indexed v_mov the compiler itself emits for a register array: a v_min_u16 that read the indexed
 // register directly returned wrong minima for a few pairs per plane on the MI355X (two instructions per slot instead
 // of one, once per slot and pair).
-static __device__ __forceinline__ void window_fold(const v32i Wa, const v16i Wb, const v4i Wc, int slot, int &farmin)
+static __device__ __forceinline__ void window_fold(const v16i Ra, const v16i Rb, const v16i Rc, int reg, int &farmin)
 {
     int w;
     asm volatile("s_set_gpr_idx_on %[SLOT], gpr_idx(SRC0)\n\t"
                  "v_mov_b32 %[W], v%c[W0]\n\t"
                  "s_set_gpr_idx_off"
                  : [W] "=v"(w)
-                 : [SLOT] "s"(slot), [W0] "n"(MSSPE_BWN13_W0), MSSPE_BWN13_TUPLES_IN(Wa, Wb, Wc)
+                 : [SLOT] "s"(reg), [W0] "n"(MSSPE_BRG13_W0), MSSPE_BRG13_TUPLES_IN(Ra, Rb, Rc)
                  : "m0");
     farmin = min(farmin, w & 0xffff);
 }
@@ -936,7 +961,9 @@ static __device__ __forceinline__ int run_pair_packed(SharedRow &sh, const SeqPa
     int pick = kPkInit;
     int slot_ = 0, start_im1 = 0;   // first slot of row i-1
     int farmin = kWinNone;          // WIN: the smallest field of the rows <= i-1-F
-    int start_w[kWinF + 1] = {};    // WIN: [d] first slot of row i-1-d
+    v16i Ra = kEmptyW, Rb = kEmptyW, Rc = kEmptyW;   // WIN: the ring's banks
+    int rot = 0;                         // WIN: i % 3, row i's bank
+    int w_im1 = 0, w_im2 = 0, w_im3 = 0;   // WIN: the stored widths of rows i-1, i-2, i-3 (0: no such row)
     for (int i_ = 0; i_ < q.len; ++i_) {
       const int im1 = __builtin_amdgcn_readfirstlane(i_);
       const int a_row = (int)((q.s1 >> (2 * im1)) & 3u);
@@ -946,8 +973,9 @@ static __device__ __forceinline__ int run_pair_packed(SharedRow &sh, const SeqPa
       unsigned mrem = active ? spaced_mask(q.s2, 3 - a_row, q.lenmask) : 0u;
       if constexpr (WIN) {
         // row i-1-F leaves the window: its slots join farmin, once per slot (wave-uniform bounds)
-        for (int s_ = start_w[kWinF]; s_ < start_w[kWinF - 1]; ++s_)
-          window_fold(Wa, Wb, Wc, __builtin_amdgcn_readfirstlane(s_), farmin);
+        // (they are slots 0 .. w(i-3)-1 of the bank row i is about to take)
+        for (int c_ = 0; c_ < w_im3; ++c_)
+          window_fold(Ra, Rb, Rc, __builtin_amdgcn_readfirstlane(rot * kRingBank + c_), farmin);
       }
       if constexpr (!WIN) {
         // the un-windowed packed instance (k_pairs_bound_packed): one cell per scan
@@ -994,47 +1022,48 @@ static __device__ __forceinline__ int run_pair_packed(SharedRow &sh, const SeqPa
           // cell here publishes an empty slot: its word fails every geometry test)
           return in ? ((int)((unsigned)(jm1 * kRowA + (im1 << 2) + ((b.po_c >> 4) & 3)) << 17) + (G0 + bias)) : kEmptyW;
         };
+        constexpr int kG = kRingGran;
+        const RingCtl ring = ring_ctl(rot, (w_im2 + kG - 1) / kG * kG, (w_im1 + kG - 1) / kG * kG);
+        const int bank0 = rot * kRingBank;
         int c_ = 0;
         {
           // Two cells of a row never depend on each other: they are scanned in one pass and published behind it, A's word and
-          // then B's.  Where a cell-by-cell order lets B visit A's fresh slot, that visit reads "not available" (same row: the
-          // table entry is 0); here B sees the empty word there, whose candidate is 0 as well -- never the maximum beside a
-          // real one (the static_asserts beside kPkOff).
-          for (; c_ + 2 <= w_row; c_ += 2, slot_ += stored ? 2 : 0) {
-            const int slot = __builtin_amdgcn_readfirstlane(slot_);
-            // (the last row is not stored: both words then go to the one slot behind the table, as every cell of that row
-            // does, and nobody reads it)
-            const int slot_b = __builtin_amdgcn_readfirstlane(slot_ + (stored ? 1 : 0));
+          // then B's (row i's own bank is not among the two a cell of row i scans).
+          for (; c_ + 2 <= w_row; c_ += 2) {
+            const int reg = __builtin_amdgcn_readfirstlane(bank0 + c_);
             bool in_a, in_b;
             int jm1_a, jm1_b, y_a, y_b, far_a, near_a, far_b, near_b;
             unsigned C_a, C_b;
             next_cell(in_a, jm1_a, C_a, y_a);
             next_cell(in_b, jm1_b, C_b, y_b);
-            window_scan_pair(Wa, Wb, Wc, C_a, y_a, C_b, y_b, start_im1 / kC4, (row_start + kC4 - 1) / kC4, start_im1,
-                             start_w[kWinF - 1] / kC4, far_a, near_a, far_b, near_b);
+            ring_scan_pair(Ra, Rb, Rc, C_a, C_b, ring, far_a, near_a, far_b, near_b);
             const int W_a = finish_cell(in_a, jm1_a, y_a, far_a, near_a);
             const int W_b = finish_cell(in_b, jm1_b, y_b, far_b, near_b);
-            if (slot < NS) packed_publish(Wa, Wb, Wc, slot, W_a);
-            if (slot_b < NS) packed_publish(Wa, Wb, Wc, slot_b, W_b);
+            if (stored) {   // the last row is stored nowhere
+              ring_publish(Ra, Rb, Rc, reg, W_a);
+              ring_publish(Ra, Rb, Rc, reg + 1, W_b);
+            }
           }
         }
-        for (; c_ < w_row; ++c_, slot_ += stored ? 1 : 0) {
-          const int slot = __builtin_amdgcn_readfirstlane(slot_);
+        for (; c_ < w_row; ++c_) {
+          const int reg = __builtin_amdgcn_readfirstlane(bank0 + c_);
           bool in;
           int jm1, yTS, acc_far, acc_near;
           unsigned C;
           next_cell(in, jm1, C, yTS);
-          window_scan(Wa, Wb, Wc, C, yTS, start_im1 / kC4, (row_start + kC4 - 1) / kC4, start_im1, start_w[kWinF - 1] / kC4,
-                      acc_far, acc_near);
+          ring_scan(Ra, Rb, Rc, C, ring, acc_far, acc_near);
           const int Wcell = finish_cell(in, jm1, yTS, acc_far, acc_near);
-          if (slot < NS) packed_publish(Wa, Wb, Wc, slot, Wcell);
+          if (stored) ring_publish(Ra, Rb, Rc, reg, Wcell);
         }
+        // the even form scans a row of odd width one slot further: that slot holds the empty word
+        if (kG == 2 && stored && (w_row & 1)) ring_publish(Ra, Rb, Rc, __builtin_amdgcn_readfirstlane(bank0 + w_row), kEmptyW);
       }
       start_im1 = row_start;
       if constexpr (WIN) {
-#pragma unroll
-        for (int d = kWinF; d > 0; --d) start_w[d] = start_w[d - 1];
-        start_w[0] = row_start;
+        w_im3 = w_im2;
+        w_im2 = w_im1;
+        w_im1 = __builtin_amdgcn_readfirstlane(stored ? w_row : 0);
+        rot = rot == 2 ? 0 : rot + 1;
       }
     }
     return pick;
@@ -1471,7 +1500,7 @@ __global__ void __launch_bounds__(RK::kRowThreads) k_pairs_bound(IntArgs a)
 
 // The packed bound instance: one register per slot (the value in the slot word's 15-bit field, coarse units), so that
 // 1,024 threads -- four waves per SIMD -- fit the register file.
-constexpr int kWindowF = MSSPE_BWN13_F;   // rows of the windowed instance's window (the generator's parameter)
+constexpr int kWindowF = Row13::kWinF;   // rows of the windowed instance's window
 constexpr int kPackedThreads = 1024;   // (the 768-thread form of the same kernel measured no faster than k_pairs_bound: DESIGN 4.0)
 template <class RK, int NT>
 __global__ void __launch_bounds__(NT) k_pairs_bound_packed(IntArgs a)

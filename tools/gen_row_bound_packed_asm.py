@@ -40,9 +40,53 @@ of the two cells here, and the units alternate A(pc), B(pc), A(pc+1), B(pc+1), .
     wait for B(pc) (counted: A(pc+1)'s stay in flight),      reduce B(pc), issue B(pc+1)
 and the last chunk waits for zero before B.  The straddling chunk's per-slot mask is formed per cell.
 usage: tools/gen_row_bound_packed_asm.py --window 2 --pair > open-msspe-design_amd/csrc/row_bound_window_pair_pinned.inc
+(the two windowed outputs are kept for the tests that read them; the kernel runs the ring scans below)
+
+--ring: the scan k_pairs_bound_window runs (row_bound_ring_pinned.inc, macros MSSPE_BRG13_*).  With a window of two rows
+only rows i-2 and i-1 are ever read again, so the windowed instance keeps its rows in a RING of three banks of 16
+registers instead of the linear table:
+
+    v76 .. v91, v92 .. v107, v108 .. v123   bank 0, 1, 2: row i lives in bank i % 3, its c-th cell in v(76 + 16 (i % 3) + c)
+    v74, v75                                 the far and the near accumulator, as above
+
+The slot word, the minuend, the table and the visit are unchanged.  A cell of row i visits bank (i-2) % 3 slots
+0 .. %[WF]-1 into the far accumulator (the caller adds the cell-side term once) and bank (i-1) % 3 slots 0 .. %[WN]-1 into
+the near one, and nothing else: no chunk straddles two rows (no per-slot mask, no %[Y]), none reaches above the window
+(no %[START], no entry tree), and a register beyond a row's width -- it may hold a word of row i-3 -- is never read.
+%[WF], %[WN] are the rows' widths (scalars, 0: no such row), %[WMAX] their maximum.
+A row's first chunk is min(width, 4) slots.  The three rotations times the 5 x 5 sizes of the two first chunks are 75
+straight-line leaves, entered through one tree of scalar compares on
+    %[IDX] = ((i % 3) * 5 + min(WF, 4)) * 5 + min(WN, 4):
+the far unit and the near unit are issued back to back, the far one is reduced under s_waitcnt lgkmcnt(near unit's
+reads), the near one under lgkmcnt(0).  Rows are 3.2 wide on average, so this is the whole scan of two cells in three;
+a leaf with a full chunk tests %[WMAX] > 4 and goes on to the rotation's wide path: for the slots 4.., 8.., 12 of either
+row a test, a body per tail size (1 to 4 slots), issue, wait, reduce.
+The two ring files keep their repeated parts as preprocessor macros -- I<n> (issue a unit of n slots), R<n> (reduce it),
+LEAF_<sf>_<sn> (a leaf, by the two bank's registers), WIDE_<n> (a chunk of the wide path) -- so a leaf is one line; the
+compiler sees the same flat instruction list (tests/test_pair_bound_ring_model.py expands them with the preprocessor).
+usage: tools/gen_row_bound_packed_asm.py --ring > open-msspe-design_amd/csrc/row_bound_ring_pinned.inc
+
+--ring --pair: two cells of one row in one pass (row_bound_ring_pair_pinned.inc, macros MSSPE_BRP13_*; operands %[CA]
+%[CB], cell B accumulates into %[bf] / %[bn]).  The controls are the row's, so the tree is walked once for both.  A
+leaf's units run far(A), near(A), far(B), near(B) through the two register sets in turn: a unit is reduced while the
+one behind it is in flight (counted wait), and the unit two places on is issued into the registers it leaves.  The wide
+path runs a chunk for both cells at once: one dispatch, B's reads in flight while A is reduced (cell A's wide path
+followed by cell B's measured 1.7 ms per step slower: DESIGN 4.0).  A row of odd width ends on the single-cell scan.
+usage: tools/gen_row_bound_packed_asm.py --ring --pair > open-msspe-design_amd/csrc/row_bound_ring_pair_pinned.inc
+
+--ring [--pair] --even: the measured alternative (MSSPE_BR?13_GRAN 2; 5 ms per step slower, not committed): every row
+padded to an even width, chunks and tails of 2 and 4 slots only (3 x 3 sizes, 27 leaves), 6.60 visits per cell instead
+of 5.71.  The kernel then writes the empty word into the pad slot of a row of odd width whenever it publishes the row,
+so that the scan never reads a stale word there.
 """
 import sys
 
+RING = len(sys.argv) >= 2 and sys.argv[1] == "--ring"
+if RING:
+    RING_PAIR, RING_EVEN = "--pair" in sys.argv[2:], "--even" in sys.argv[2:]
+    if len(sys.argv) != 2 + RING_PAIR + RING_EVEN:
+        sys.exit(__doc__)
+    sys.argv = sys.argv[:1]
 PAIR = len(sys.argv) == 4 and sys.argv[3] == "--pair"
 WINDOW = int(sys.argv[2]) if len(sys.argv) == 3 + PAIR and sys.argv[1] == "--window" else 0
 if (len(sys.argv) != 1 and not WINDOW) or WINDOW not in (0, 2, 3) or (PAIR and WINDOW != 2):
@@ -270,6 +314,215 @@ def pair_scan_asm():
     a("Ldone%=:")
     return L
 
+
+RING_BANKS, RING_BANK_REGS, RING_MAXW = 3, 16, 13
+
+
+def ring_scan(pair, even):
+    """(items of the scan, macro definitions).  An item is an instruction or label (str) or a macro call (name, args);
+    the .inc keeps the units and the leaves as preprocessor macros, so that the file stays small enough to read."""
+    PFX = "MSSPE_BRP13" if pair else "MSSPE_BRG13"
+    items, defs, defined = [], [], set()
+    a = lambda s: items.append(s)
+    # operands: %[C] (pair: %[CA] %[CB]) v; %[IDX] %[WF] %[WN] %[WMAX] s; outputs v74, v75 (pair: cell A's; cell B's are
+    # %[bf] %[bn]); temps, two units in flight: set a = %[ta0..3] / %[va0..3], set b = %[tb0..3] / %[vb0..3]
+    sizes = [0, 2, 4] if even else [0, 1, 2, 3, 4]     # what a row leaves for a chunk: nothing, a tail, a full chunk
+    nsz = len(sizes)
+    maxw = RING_MAXW + (RING_MAXW & 1 if even else 0)
+    CELLS = [("CA", {"far": f"v{ACCF}", "near": f"v{ACCN}"}), ("CB", {"far": "%[bf]", "near": "%[bn]"})] if pair \
+        else [("C", {"far": f"v{ACCF}", "near": f"v{ACCN}"})]
+    bank = lambda rot, role: W0 + RING_BANK_REGS * ((rot + (1 if role == "far" else 2)) % RING_BANKS)
+    label = [0]
+    P = lambda x: '" #' + x + ' "'      # a macro parameter, stringified into the instruction text
+
+    def new_label(tag):
+        label[0] += 1
+        return f"L{tag}{label[0]}_%="
+
+    def define(name, params, body):
+        if name not in defined:
+            defined.add(name)
+            defs.append((name, params, body))
+
+    def issue_text(st, C, regs):
+        n = len(regs)
+        return [f"v_sub_u32 %[t{st}{e}], %[{C}], v{regs[e]}" for e in range(n)] + \
+               [f"v_lshrrev_b32 %[v{st}{e}], 15, %[t{st}{e}]" for e in range(n)] + \
+               [f"ds_read_b32 %[v{st}{e}], %[v{st}{e}] offset:%c[TOFF]" for e in range(n)]
+
+    def reduce_text(st, acc, n):
+        return [f"v_mad_u32_u16 %[t{st}{e}], %[t{st}{e}], 1, %[v{st}{e}]" for e in range(n)] + \
+               [f"v_max3_i32 {acc}, {acc}, %[t{st}{e}], %[t{st}{e + 1}]" for e in range(0, n - 1, 2)] + \
+               ([f"v_max_i32 {acc}, {acc}, %[t{st}{n - 1}]"] if n & 1 else [])
+
+    def issue(out, st, C, regs):
+        # I<n>(set, minuend, the slots' registers)
+        n = len(regs)
+        define(f"I{n}", ["s", "C"] + [f"r{e}" for e in range(n)], issue_text(P("s"), P("C"), [P(f"r{e}") for e in range(n)]))
+        out.append((f"I{n}", [st, C] + [str(r) for r in regs]))
+
+    def reduce(out, st, acc, n):
+        # R<n>(set, accumulator)
+        define(f"R{n}", ["s", "acc"], reduce_text(P("s"), P("acc"), n))
+        out.append((f"R{n}", [st, acc]))
+
+    def wait(out, n):
+        out.append(f"s_waitcnt lgkmcnt({n})")
+
+    def leaf_body(out, far, near):
+        # the rows' first chunks, both known: a straight line.  The units run far(A), near(A), far(B), near(B) through the
+        # sets a, b in turn; a unit is reduced while the one behind it is in flight (its size is the wait's count), and
+        # the unit two places on is issued into the registers the reduced one leaves
+        regs = {"far": far, "near": near}
+        units = [(c, role) for c in range(len(CELLS)) for role in ("far", "near") if regs[role]]
+        for u, (c, role) in enumerate(units[:2]):
+            issue(out, "ab"[u], CELLS[c][0], regs[role])
+        for u, (c, role) in enumerate(units):
+            wait(out, len(regs[units[u + 1][1]]) if u + 1 < len(units) else 0)
+            reduce(out, "ab"[u & 1], CELLS[c][1][role], len(regs[role]))
+            if u + 2 < len(units):
+                c2, role2 = units[u + 2]
+                issue(out, "ab"[u & 1], CELLS[c2][0], regs[role2])
+
+    def leaf(rot, sf, sn):
+        # LEAF_<sf>_<sn>(far row's registers, near row's registers)
+        if sf or sn:
+            params = [f"f{e}" for e in range(sf)] + [f"n{e}" for e in range(sn)]
+            body = []
+            leaf_body(body, [f"F{e}" for e in range(sf)], [f"N{e}" for e in range(sn)])
+            sym = {f"F{e}": f"f{e}" for e in range(sf)}
+            sym.update({f"N{e}": f"n{e}" for e in range(sn)})
+            define(f"LEAF_{sf}_{sn}", params, [x if isinstance(x, str) else (x[0], [sym.get(y, y) for y in x[1]]) for x in body])
+            a((f"LEAF_{sf}_{sn}", [str(bank(rot, "far") + e) for e in range(sf)] + [str(bank(rot, "near") + e) for e in range(sn)]))
+        if KC in (sf, sn):
+            a(f"s_cmp_gt_i32 %[WMAX], {KC}")
+            a("s_cbranch_scc0 Ldone%=")
+            a(f"s_branch Lwide{rot}_%=")
+        else:
+            a("s_branch Ldone%=")
+
+    def by_size(W, base, cands, body):
+        # W - base >= cands[0]: the largest of cands that fits runs
+        if len(cands) == 1:
+            body(cands[0])
+            return
+        mid = len(cands) // 2
+        hi, end = new_label("h"), new_label("e")
+        a(f"s_cmp_lt_i32 {W}, {base + cands[mid]}")
+        a(f"s_cbranch_scc0 {hi}")
+        by_size(W, base, cands[:mid], body)
+        a(f"s_branch {end}")
+        a(f"{hi}:")
+        by_size(W, base, cands[mid:], body)
+        a(f"{end}:")
+
+    def wide(rot):
+        # a row wider than one chunk (one row in five): its further chunks one at a time, each with a body per tail size.
+        # The two-cell scan runs a chunk for both cells at once: one dispatch, B's reads in flight while A is reduced
+        a(f"Lwide{rot}_%=:")
+        for base in range(KC, maxw, KC):
+            cands = [s for s in sizes if s and base + s <= maxw]
+            for role, W in (("far", "%[WF]"), ("near", "%[WN]")):
+                skip = new_label("s")
+                a(f"s_cmp_gt_i32 {W}, {base}")
+                a(f"s_cbranch_scc0 {skip}")
+
+                def body(n, role=role, base=base):
+                    # WIDE_<n>(accumulator of A [, of B], the slots' registers)
+                    accs = [f"acc{c}" for c in range(len(CELLS))]
+                    out = []
+                    for st, (C, _) in enumerate(CELLS):
+                        issue(out, "ab"[st], C, [f"r{e}" for e in range(n)])
+                    for st in range(len(CELLS)):
+                        wait(out, n if st + 1 < len(CELLS) else 0)
+                        reduce(out, "ab"[st], accs[st], n)
+                    define(f"WIDE_{n}", accs + [f"r{e}" for e in range(n)], out)
+                    a((f"WIDE_{n}", [acc[role] for _, acc in CELLS] + [str(bank(rot, role) + base + e) for e in range(n)]))
+
+                by_size(W, base, cands, body)
+                a(f"{skip}:")
+            if base + KC < maxw:
+                a(f"s_cmp_gt_i32 %[WMAX], {base + KC}")
+                a("s_cbranch_scc0 Ldone%=")
+        a("s_branch Ldone%=")
+
+    def enter(lo, hi):
+        # %[IDX] = (rotation * nsz + far size's index) * nsz + near size's index
+        if lo == hi:
+            rot, fi, ni = lo // (nsz * nsz), lo // nsz % nsz, lo % nsz
+            leaf(rot, sizes[fi], sizes[ni])
+            return
+        mid = (lo + hi + 1) // 2
+        a(f"s_cmp_lt_i32 %[IDX], {mid}")
+        a(f"s_cbranch_scc0 Le{mid}_{hi}_%=")
+        enter(lo, mid - 1)
+        a(f"Le{mid}_{hi}_%=:")
+        enter(mid, hi)
+
+    for _, acc in CELLS:
+        a(f"v_mov_b32 {acc['far']}, 0")
+        a(f"v_mov_b32 {acc['near']}, 0")
+    enter(0, RING_BANKS * nsz * nsz - 1)
+    for rot in range(RING_BANKS):
+        wide(rot)
+    a("Ldone%=:")
+    return PFX, items, defs, nsz
+
+
+def ring_render(PFX, items, defs):
+    """The macro definitions and the *_SCAN_ASM macro as text.  An instruction is one string literal; a compare and the
+    branch on it share a line."""
+    lit = lambda s: '"' + s + '\\n\\t"'
+    call = lambda x: f"{PFX}_{x[0]}({', '.join(x[1])})"
+    piece = lambda x: lit(x) if isinstance(x, str) else call(x)
+
+    def lines_of(seq):
+        out = []
+        for x in seq:
+            if isinstance(x, str) and x.startswith("s_cbranch") and out and out[-1].startswith('"s_cmp'):
+                out[-1] += " " + lit(x)
+            else:
+                out.append(piece(x))
+        return out
+
+    text = []
+    for name, params, body in defs:
+        text.append(f"#define {PFX}_{name}({', '.join(params)}) \\")
+        if all(isinstance(x, str) for x in body):
+            text.append(" \\\n".join("    " + lit(x) for x in body))
+        else:
+            text.append("    " + " ".join(piece(x) for x in body))
+    text.append(f"#define {PFX}_SCAN_ASM \\")
+    text.append(" \\\n".join("    " + l for l in lines_of(items)))
+    return "\n".join(text)
+
+
+if RING:
+    PFX, items, defs, nsz = ring_scan(RING_PAIR, RING_EVEN)
+    print(f"// GENERATED by tools/gen_row_bound_packed_asm.py --ring{' --pair' if RING_PAIR else ''}{' --even' if RING_EVEN else ''}"
+          " -- do not edit (see that file for the why and the register map)")
+    print(f"#define {PFX}_KC {KC}")
+    print(f"#define {PFX}_W0 {W0}")
+    print(f"#define {PFX}_BANK {RING_BANK_REGS}")
+    print(f"#define {PFX}_GRAN {2 if RING_EVEN else 1}")
+    print(f"#define {PFX}_NSZ {nsz}")
+    print(ring_render(PFX, items, defs))
+    print(f'#define {PFX}_SCAN_CLOBBERS "scc", "memory"')
+    temps = [f"{k}{s}{e}" for k in "tv" for s in "ab" for e in range(KC)]
+    print(f"#define {PFX}_TEMP_NAMES " + ", ".join(temps))
+    print(f"#define {PFX}_TEMPS_OUT " + ", ".join(f'[{t}] "=&v"({t})' for t in temps))
+    if RING_PAIR:
+        print(f'#define {PFX}_ACC_OUT(far_a, near_a, far_b, near_b) "=&{{v{ACCF}}}"(far_a), "=&{{v{ACCN}}}"(near_a), '
+              '[bf] "=&v"(far_b), [bn] "=&v"(near_b)')
+    else:
+        print(f'#define {PFX}_ACC_OUT(far, near) "=&{{v{ACCF}}}"(far), "=&{{v{ACCN}}}"(near)')
+    names = ["Ra", "Rb", "Rc"]
+    banks = [(W0 + RING_BANK_REGS * b, RING_BANK_REGS) for b in range(RING_BANKS)]
+    print(f"#define {PFX}_TUPLES_IN(" + ", ".join(names) + ") " +
+          ", ".join('"{v[%d:%d]}"(%s)' % (r0, r0 + ln - 1, nm) for (r0, ln), nm in zip(banks, names)))
+    print(f"#define {PFX}_TUPLES_INOUT(" + ", ".join(names) + ") " +
+          ", ".join('"+{v[%d:%d]}"(%s)' % (r0, r0 + ln - 1, nm) for (r0, ln), nm in zip(banks, names)))
+    sys.exit(0)
 
 print(f"// GENERATED by tools/gen_row_bound_packed_asm.py{f' --window {WINDOW}' if WINDOW else ''}{' --pair' if PAIR else ''} -- do not edit (see that file for the why and the register map)")
 if WINDOW:
