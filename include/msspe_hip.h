@@ -1162,6 +1162,64 @@ int msspe_background_amplicons_flank(msspe_ctx *ctx, const char *const *records,
                                      uint64_t *amplicons_out, uint64_t *n_amplicons_out, msspe_amplicon *amplicons,
                                      uint64_t capacity, uint64_t *count_out, uint64_t *record_start_out);
 
+/* ---- target reach: the columns each record's primers extend into (engine extension) ---------------------------
+ * A spiked primer enriches what a polymerase extends from it, a few hundred bases downstream of its site.  These calls
+ * say how much of every record of a stream lies within that distance of a stable site, and where the longest stretch
+ * lies that nothing primes into.  The stream, records, start[], total_len, primers, msspe_mismatch_opt, chemistry, mode,
+ * tm_threshold, flank and the STABLE sites are those of msspe_background_thal_flank* (a threshold <= 0: every site of
+ * the string rule).  Record r spans the columns [s_r, e_r), s_r = start[r], e_r = s_r + record_bytes[r].
+ *   P_r: the positions p of the stable plus-strand sites in r, of any primer; duplicate primers and several primers at
+ *        one p count once.  M_r: the same set for the minus-strand sites q.
+ *   The REACH D (msspe_reach_opt.reach) is the length of the extension product, the primer included: k <= D < 2^31.
+ *   Column b of r is PLUS-REACHED  iff some p in P_r has p <= b <= p + D - 1;
+ *                    MINUS-REACHED iff some q in M_r has q + k - D <= b <= q + k - 1 (a primer at a minus site extends
+ *                    towards decreasing positions, as in the amplicon section).
+ *   Reach never leaves its record.  Invalid columns inside a record (N, IUPAC) are columns like any other: they are
+ *   counted and do not stop reach, just as they do not break an amplicon.
+ * One msspe_reach_record per record:
+ *   sites_plus, sites_minus: |P_r|, |M_r|;
+ *   reached_plus, reached_minus, reached_either, reached_both: columns of r;
+ *   gap_plus_len / gap_plus_pos, gap_minus_*, gap_either_*: the longest maximal run of columns of r that are not
+ *     plus-reached / not minus-reached / reached on neither strand; pos is the stream position of the run's first
+ *     column, ties go to the lowest position, and len = 0 gives pos = s_r.
+ *   An empty record is all zeros with every pos = s_r.
+ *   msspe_stream_reach_packed_dev: on a resident stream (msspe_device_put_stream_packed), on the context's stream.
+ *     record_start (HOST, n_records) has the conventions of msspe_background_amplicons_packed_dev: start[] as
+ *     msspe_device_put_stream_packed returns it, start[0] == 0, the column before every later start is the separator;
+ *     NULL: the stream is one record (n_records is not read).  sites_out, stable_out (uint64, HOST, 2 n): exactly what
+ *     msspe_background_thal_flank* returns for the same arguments.  records_out: HOST, n_records entries (one for
+ *     NULL record_start).  The call returns when they are filled.
+ *   msspe_stream_reach: host pointers throughout; record_start_out (optional, n_records): start[].
+ * Memory is bounded and nothing depends on the number of sites: the scored pass ORs every stable site into one of two
+ * bit planes of ceil(total_len / 64) words, a third plane holds "reached by neither", and the nearest site is carried
+ * across tiles of "reach_tile_columns" columns through three 32-bit values per tile.  The buffers are the context's,
+ * grown when a call needs more and kept.  msspe_get_info "reach_plane_bytes": the planes' size; "reach_grows": 1 when
+ * the last call grew the planes, otherwise 0; "reach_tile_columns"; "reach_tiles_us", "reach_scan_us", "reach_masks_us",
+ * "reach_gap_tiles_us", "reach_gaps_us": device time of the last call's reach kernels.
+ * Errors: those of msspe_background_thal_flank*; MSSPE_ERR_ARG also for a NULL reach_opt or records_out, a reach
+ * outside [k, 2^31), record_start[0] != 0, record_start not strictly ascending or its last start beyond total_len.
+ * n == 0 or total_len < k: MSSPE_OK, sites_out and stable_out zeroed, and every record has no site and no reached
+ * column: every gap is the whole record, len = record_bytes[r], pos = s_r. */
+typedef struct {
+    uint32_t reach;        /* D: k <= reach < 2^31 */
+} msspe_reach_opt;
+typedef struct {
+    uint32_t sites_plus, sites_minus;
+    uint32_t reached_plus, reached_minus, reached_either, reached_both;
+    uint32_t gap_plus_len, gap_plus_pos;
+    uint32_t gap_minus_len, gap_minus_pos;
+    uint32_t gap_either_len, gap_either_pos;
+} msspe_reach_record;
+int msspe_stream_reach_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, size_t total_len, int k,
+                                  const msspe_mismatch_opt *mm, const uint64_t *words, int n, const msspe_chem *chem,
+                                  int mode, float tm_threshold, int flank, const msspe_reach_opt *reach_opt,
+                                  const uint64_t *record_start, int n_records, uint64_t *sites_out,
+                                  uint64_t *stable_out, msspe_reach_record *records_out);
+int msspe_stream_reach(msspe_ctx *ctx, const char *const *records, const size_t *record_bytes, int n_records, int k,
+                       const msspe_mismatch_opt *mm, const uint64_t *words, int n, const msspe_chem *chem, int mode,
+                       float tm_threshold, int flank, const msspe_reach_opt *reach_opt, uint64_t *sites_out,
+                       uint64_t *stable_out, msspe_reach_record *records_out, uint64_t *record_start_out);
+
 /* ---- segment coverage scored with thal (engine extension, no reference counterpart) ---------------------------
  * msspe_segment_coverage_mm* says which segments hold a match by a string rule; these calls say which of those
  * matches would hold the primer at a temperature -- msspe_background_thal*'s question, asked of the target alignment.

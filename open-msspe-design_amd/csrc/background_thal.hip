@@ -15,6 +15,9 @@
 // pos << 32 | strand << 31 | primer, per STABLE site, appended to a buffer the caller has sized for every site of
 // the launch, again with one atomic per wave.  The sink is a template flag of the shared body, so k_site_fold itself
 // is the kernel it was.
+// k_site_fold_planes is the fold with a position-indexed sink (msspe_stream_reach*): every STABLE site ORs bit pos
+// into the bit plane of its strand, one 64-bit atomicOr each -- several primers at one position set one bit, so what the
+// planes hold does not depend on the number of sites.  Again a template flag of the shared body.
 //
 // k_site_oligos_flank (msspe_background_*_flank* with flank f > 0): one lane per site record.  The lane gathers the
 // validity bits of the 2 f + k columns at pos - f (columns before the stream and behind it read as invalid) and counts
@@ -145,12 +148,14 @@ __global__ void __launch_bounds__(kThreads) k_site_group(const msspe_site *sites
     }
 }
 
-template <bool kKeys>
+template <bool kKeys, bool kPlanes = false>
 __device__ __forceinline__ void site_fold(const msspe_site *sites, uint32_t count, const double *dg, const double *t,
                                           double t_cut, int n, unsigned long long *counts, msspe_scored_site *out,
                                           unsigned long long capacity, unsigned long long *out_count,
                                           unsigned long long *keys, unsigned long long key_cap,
-                                          unsigned long long *key_count)
+                                          unsigned long long *key_count,
+                                          unsigned long long *plane_plus = nullptr,
+                                          unsigned long long *plane_minus = nullptr)
 {
     const uint32_t idx = blockIdx.x * kThreads + threadIdx.x;
     const bool live = idx < count;
@@ -198,6 +203,7 @@ __device__ __forceinline__ void site_fold(const msspe_site *sites, uint32_t coun
         if (stable && at < key_cap)
             keys[at] = ((unsigned long long)s.pos << 32) | ((unsigned long long)s.strand << 31) | s.primer;
     }
+    if (kPlanes && stable) atomicOr(&(s.strand ? plane_minus : plane_plus)[s.pos >> 6], 1ull << (s.pos & 63u));
 }
 
 __global__ void __launch_bounds__(kThreads) k_site_fold(const msspe_site *sites, uint32_t count, const double *dg,
@@ -217,6 +223,18 @@ __global__ void __launch_bounds__(kThreads) k_site_fold_keys(const msspe_site *s
                                                              unsigned long long *key_count)
 {
     site_fold<true>(sites, count, dg, t, t_cut, n, counts, out, capacity, out_count, keys, key_cap, key_count);
+}
+
+__global__ void __launch_bounds__(kThreads) k_site_fold_planes(const msspe_site *sites, uint32_t count,
+                                                               const double *dg, const double *t, double t_cut, int n,
+                                                               unsigned long long *counts, msspe_scored_site *out,
+                                                               unsigned long long capacity,
+                                                               unsigned long long *out_count,
+                                                               unsigned long long *plane_plus,
+                                                               unsigned long long *plane_minus)
+{
+    site_fold<false, true>(sites, count, dg, t, t_cut, n, counts, out, capacity, out_count, nullptr, 0, nullptr,
+                           plane_plus, plane_minus);
 }
 
 }  // namespace
@@ -271,6 +289,19 @@ hipError_t launch_site_fold_keys(const msspe_site *d_sites, uint32_t count, cons
                        count, dg, t, t_cut, n, counts, d_out, (unsigned long long)capacity,
                        (unsigned long long *)d_count, (unsigned long long *)d_keys, (unsigned long long)key_cap,
                        (unsigned long long *)d_key_count);
+    return hipGetLastError();
+}
+
+hipError_t launch_site_fold_planes(const msspe_site *d_sites, uint32_t count, const double *dg, const double *t,
+                                   double t_cut, int n, unsigned long long *counts, msspe_scored_site *d_out,
+                                   uint64_t capacity, uint64_t *d_count, uint64_t *d_plane_plus,
+                                   uint64_t *d_plane_minus, hipStream_t stream)
+{
+    if (!count) return hipSuccess;
+    hipLaunchKernelGGL(k_site_fold_planes, dim3((count + kThreads - 1) / kThreads), dim3(kThreads), 0, stream, d_sites,
+                       count, dg, t, t_cut, n, counts, d_out, (unsigned long long)capacity,
+                       (unsigned long long *)d_count, (unsigned long long *)d_plane_plus,
+                       (unsigned long long *)d_plane_minus);
     return hipGetLastError();
 }
 

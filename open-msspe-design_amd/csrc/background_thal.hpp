@@ -55,4 +55,11 @@ hipError_t launch_site_fold_keys(const msspe_site *d_sites, uint32_t count, cons
                                  uint64_t capacity, uint64_t *d_count, uint64_t *d_keys, uint64_t key_cap,
                                  uint64_t *d_key_count, hipStream_t stream);
 
+// The same fold with the position-indexed sink of msspe_stream_reach*: every stable site also ORs bit pos into the
+// plane of its strand (d_plane_plus / d_plane_minus: ceil(total_len / 64) words each, cleared by the caller).
+hipError_t launch_site_fold_planes(const msspe_site *d_sites, uint32_t count, const double *dg, const double *t,
+                                   double t_cut, int n, unsigned long long *counts, msspe_scored_site *d_out,
+                                   uint64_t capacity, uint64_t *d_count, uint64_t *d_plane_plus,
+                                   uint64_t *d_plane_minus, hipStream_t stream);
+
 }  // namespace msspe

@@ -28,6 +28,7 @@
 #include "background.hpp"
 #include "background_thal.hpp"
 #include "background_amplicons.hpp"
+#include "stream_reach.hpp"
 #include "coverage_mm.hpp"
 #include "coverage_thal.hpp"
 #include "kernels.hpp"
@@ -222,6 +223,20 @@ struct msspe_ctx {
         long long n_keys = 0, grows = 0;   // of the last call
         long long sort_us = 0, join_us = 0;
     } amp_work;
+    // msspe_stream_reach*: the three bit planes (plus sites, minus sites, reached by neither) in one allocation, the
+    // three tile arrays in another, the record starts and the per-record sums
+    struct ReachWork {
+        uint64_t *planes = nullptr;
+        size_t plane_words = 0;            // capacity of one plane, in words
+        uint32_t *tiles = nullptr;
+        size_t tiles_cap = 0;              // capacity of one tile array
+        uint64_t *starts = nullptr;
+        ReachAccum *acc = nullptr;
+        size_t records_cap = 0;
+        hipEvent_t ev[7] = {};             // around the six launches behind the scored pass
+        long long grows = 0;               // of the last call
+        long long us[6] = {};              // tiles, scan, masks, gap tiles, scan, gaps
+    } reach_work;
     // optional profiling of the dominant kernel (k_pairs_fast) with HIP events on ctx->stream
     bool prof_on = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events;
@@ -899,6 +914,14 @@ int msspe_get_info(msspe_ctx *ctx, const char *key, long long *value_out)
     else if (k == "amplicon_key_grows") *value_out = ctx->amp_work.grows;
     else if (k == "amplicon_sort_us") *value_out = ctx->amp_work.sort_us;
     else if (k == "amplicon_join_us") *value_out = ctx->amp_work.join_us;
+    else if (k == "reach_plane_bytes") *value_out = (long long)(3 * sizeof(uint64_t) * ctx->reach_work.plane_words);
+    else if (k == "reach_grows") *value_out = ctx->reach_work.grows;
+    else if (k == "reach_tile_columns") *value_out = kReachTileColumns;
+    else if (k == "reach_tiles_us") *value_out = ctx->reach_work.us[0];
+    else if (k == "reach_scan_us") *value_out = ctx->reach_work.us[1] + ctx->reach_work.us[4];
+    else if (k == "reach_masks_us") *value_out = ctx->reach_work.us[2];
+    else if (k == "reach_gap_tiles_us") *value_out = ctx->reach_work.us[3];
+    else if (k == "reach_gaps_us") *value_out = ctx->reach_work.us[5];
     else if (k == "cover_rounds") *value_out = ctx->cover.rounds();
     else if (k == "cover_keys_us") *value_out = ctx->cover.phase_us()[0];
     else if (k == "cover_symmetrise_us") *value_out = ctx->cover.phase_us()[1];
@@ -1049,6 +1072,13 @@ void msspe_destroy(msspe_ctx *ctx)
             auto &w = ctx->amp_work;
             for (void *q : {(void *)w.keys, (void *)w.key_count, (void *)w.sorted, (void *)w.rec, w.tmp,
                             (void *)w.starts, (void *)w.counts})
+                if (q) (void)hipFree(q);
+            for (hipEvent_t e : w.ev)
+                if (e) (void)hipEventDestroy(e);
+        }
+        {
+            auto &w = ctx->reach_work;
+            for (void *q : {(void *)w.planes, (void *)w.tiles, (void *)w.starts, (void *)w.acc})
                 if (q) (void)hipFree(q);
             for (hipEvent_t e : w.ev)
                 if (e) (void)hipEventDestroy(e);
@@ -3683,14 +3713,16 @@ int ensure_amplicon_keys(msspe_ctx *ctx, uint64_t have, uint64_t need)
 
 // msspe_background_thal[_flank]_packed_dev, and with keys the same pass for
 // msspe_background_amplicons[_flank]_packed_dev: the fold of every slab also appends the keys of its stable sites to
-// ctx->amp_work.keys; amp_work.n_keys counts them.  flank 0: every template oligo is its window, one list per chunk
+// ctx->amp_work.keys; amp_work.n_keys counts them.  With planes (msspe_stream_reach*, never together with keys) the
+// fold ORs every stable site's position into the bit plane of its strand; the caller has cleared the planes.  flank 0: every template oligo is its window, one list per chunk
 // (k_site_oligos).  flank > 0: the sites of a chunk are classed by the flanks they found (k_site_oligos_flank), the
 // class counters come to the host, their exclusive scan places the classes' runs in the list (k_site_group), and
 // each non-empty class is scored as a list of its own with k2 = k + fl + fr.
 int background_thal_pass(msspe_ctx *ctx, const uint64_t *d_packed, size_t total_len, int k,
                          const msspe_mismatch_opt *mm, const uint64_t *words, int n, const msspe_chem *chem, int mode,
                          float tm_threshold, int flank, uint64_t *sites_out, uint64_t *stable_out,
-                         msspe_scored_site *d_sites, uint64_t capacity, uint64_t *d_count, bool keys)
+                         msspe_scored_site *d_sites, uint64_t capacity, uint64_t *d_count, bool keys,
+                         uint64_t *plane_plus = nullptr, uint64_t *plane_minus = nullptr)
 {
     if (!ctx) return MSSPE_ERR_ARG;
     if (!d_packed || !mm || !sites_out || !stable_out || !chem || n < 0 || (n && !words) || (d_sites && !d_count))
@@ -3778,6 +3810,12 @@ int background_thal_pass(msspe_ctx *ctx, const uint64_t *d_packed, size_t total_
         return MSSPE_OK;
     };
     auto fold = [&](const Slab &, uint64_t count) -> int {
+        if (plane_plus) {
+            HIP_TRY(ctx, launch_site_fold_planes(w.sites, (uint32_t)count, w.dg, w.t, cut, n, w.counts, d_sites,
+                                                 capacity, d_sites ? d_count : nullptr, plane_plus, plane_minus,
+                                                 ctx->stream));
+            return MSSPE_OK;
+        }
         if (!keys) {
             HIP_TRY(ctx, launch_site_fold(w.sites, (uint32_t)count, w.dg, w.t, cut, n, w.counts, d_sites, capacity,
                                           d_sites ? d_count : nullptr, ctx->stream));
@@ -5267,6 +5305,161 @@ int msspe_background_amplicons_flank(msspe_ctx *ctx, const char *const *records,
     if (d_list) (void)hipFree(d_list);
     (void)msspe_device_free(ctx, d);
     if (e != hipSuccess) return hip_fail(ctx, e, "msspe_background_amplicons");
+    return rc;
+}
+
+// Work buffers of msspe_stream_reach*: grown when a call needs more, kept otherwise.
+static int ensure_reach_work(msspe_ctx *ctx, size_t total_len, int n_records)
+{
+    auto &w = ctx->reach_work;
+    w.grows = 0;
+    const size_t nw = std::max<size_t>(reach_plane_words(total_len), 1), nt = std::max<size_t>(reach_tiles(total_len), 1);
+    if (w.plane_words < nw) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (w.planes) (void)hipFree(w.planes);
+        w.planes = nullptr;
+        w.plane_words = 0;
+        HIP_TRY(ctx, hipMalloc((void **)&w.planes, 3 * sizeof(uint64_t) * nw));
+        w.plane_words = nw;
+        ++w.grows;
+    }
+    if (w.tiles_cap < nt) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (w.tiles) (void)hipFree(w.tiles);
+        w.tiles = nullptr;
+        w.tiles_cap = 0;
+        HIP_TRY(ctx, hipMalloc((void **)&w.tiles, 3 * sizeof(uint32_t) * nt));
+        w.tiles_cap = nt;
+    }
+    if (w.records_cap < (size_t)n_records) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        if (w.starts) (void)hipFree(w.starts);
+        if (w.acc) (void)hipFree(w.acc);
+        w.starts = nullptr;
+        w.acc = nullptr;
+        w.records_cap = 0;
+        HIP_TRY(ctx, hipMalloc((void **)&w.starts, sizeof(uint64_t) * (size_t)n_records));
+        HIP_TRY(ctx, hipMalloc((void **)&w.acc, sizeof(ReachAccum) * (size_t)n_records));
+        w.records_cap = (size_t)n_records;
+    }
+    for (hipEvent_t &e : w.ev)
+        if (!e) HIP_TRY(ctx, hipEventCreate(&e));
+    return MSSPE_OK;
+}
+
+int msspe_stream_reach_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, size_t total_len, int k,
+                                  const msspe_mismatch_opt *mm, const uint64_t *words, int n, const msspe_chem *chem,
+                                  int mode, float tm_threshold, int flank, const msspe_reach_opt *reach_opt,
+                                  const uint64_t *record_start, int n_records, uint64_t *sites_out,
+                                  uint64_t *stable_out, msspe_reach_record *records_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!reach_opt || !records_out || (record_start && n_records <= 0))
+        return fail(ctx, MSSPE_ERR_ARG, "null argument");
+    if (k >= 2 && k <= 31 && reach_opt->reach < (uint32_t)k)   // another k: the scored pass's MSSPE_ERR_K
+        return fail(ctx, MSSPE_ERR_ARG, "stream_reach: reach is shorter than the primers");
+    if (reach_opt->reach >= (1u << 31)) return fail(ctx, MSSPE_ERR_ARG, "stream_reach: reach must be below 2^31");
+    if (record_start) {
+        if (record_start[0] != 0) return fail(ctx, MSSPE_ERR_ARG, "stream_reach: record_start[0] must be 0");
+        for (int r = 1; r < n_records; ++r)
+            if (record_start[r] <= record_start[r - 1])
+                return fail(ctx, MSSPE_ERR_ARG, "stream_reach: record_start is not ascending");
+        if (record_start[n_records - 1] > total_len)
+            return fail(ctx, MSSPE_ERR_ARG, "stream_reach: a record starts beyond the stream");
+    }
+    const uint64_t one_start = 0;
+    const uint64_t *starts = record_start ? record_start : &one_start;
+    const int nr = record_start ? n_records : 1;
+    auto end_of = [&](int r) { return r + 1 < nr ? starts[r + 1] - 1 : (uint64_t)total_len; };
+    auto &w = ctx->reach_work;
+    for (long long &u : w.us) u = 0;
+    w.grows = 0;
+    const bool empty = n == 0 || total_len < (size_t)k;   // the scored pass returns before it touches the device
+    uint64_t *plus = nullptr, *minus = nullptr, *neither = nullptr;
+    if (!empty && total_len < ((size_t)1 << 32) && d_packed && mm && chem && sites_out && stable_out && n > 0 &&
+        words && k >= 2 && k <= 31) {   // anything else: the scored pass names the fault
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        if (int rc = ensure_reach_work(ctx, total_len, nr)) return rc;
+        plus = w.planes;
+        minus = plus + w.plane_words;
+        neither = minus + w.plane_words;
+        HIP_TRY(ctx, hipMemsetAsync(plus, 0, 2 * sizeof(uint64_t) * w.plane_words, ctx->stream));
+    }
+    int rc = background_thal_pass(ctx, d_packed, total_len, k, mm, words, n, chem, mode, tm_threshold, flank,
+                                  sites_out, stable_out, nullptr, 0, nullptr, false, plus, minus);
+    if (rc) return rc;
+    if (empty) {   // no site: nothing is reached and every gap is its whole record
+        for (int r = 0; r < nr; ++r) {
+            const uint32_t s = (uint32_t)starts[r], len = (uint32_t)(end_of(r) - starts[r]);
+            records_out[r] = msspe_reach_record{0, 0, 0, 0, 0, 0, len, s, len, s, len, s};
+        }
+        return MSSPE_OK;
+    }
+    if (!plus) return fail(ctx, MSSPE_ERR_ARG, "stream_reach: unsupported arguments");
+    const size_t nt = reach_tiles(total_len);
+    uint32_t *tile_plus = w.tiles, *tile_minus = tile_plus + w.tiles_cap, *tile_zero = tile_minus + w.tiles_cap;
+    // the call returns behind a synchronisation of the stream, so the caller's array outlives the copy
+    HIP_TRY(ctx, hipMemcpyAsync(w.starts, starts, sizeof(uint64_t) * (size_t)nr, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(w.acc, 0, sizeof(ReachAccum) * (size_t)nr, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(w.ev[0], ctx->stream));
+    HIP_TRY(ctx, launch_reach_tiles(plus, minus, total_len, k, tile_plus, tile_minus, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(w.ev[1], ctx->stream));
+    HIP_TRY(ctx, launch_reach_scan(tile_plus, tile_minus, nt, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(w.ev[2], ctx->stream));
+    HIP_TRY(ctx, launch_reach_masks(plus, minus, total_len, k, reach_opt->reach, w.starts, nr, tile_plus, tile_minus,
+                                    w.acc, neither, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(w.ev[3], ctx->stream));
+    HIP_TRY(ctx, launch_reach_gap_tiles(neither, total_len, tile_zero, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(w.ev[4], ctx->stream));
+    HIP_TRY(ctx, launch_reach_scan(tile_zero, nullptr, nt, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(w.ev[5], ctx->stream));
+    HIP_TRY(ctx, launch_reach_gaps(neither, total_len, w.starts, nr, tile_zero, w.acc, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(w.ev[6], ctx->stream));
+    std::vector<ReachAccum> host((size_t)nr);
+    HIP_TRY(ctx, hipMemcpyAsync(host.data(), w.acc, sizeof(ReachAccum) * host.size(), hipMemcpyDeviceToHost,
+                                ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    for (int i = 0; i < 6; ++i) {
+        float ms = 0.0f;
+        HIP_TRY(ctx, hipEventElapsedTime(&ms, w.ev[i], w.ev[i + 1]));
+        w.us[i] = (long long)(ms * 1000.0f);
+    }
+    for (int r = 0; r < nr; ++r) {
+        const ReachAccum &a = host[(size_t)r];
+        const uint32_t s = (uint32_t)starts[r];
+        auto len = [](unsigned long long key) { return (uint32_t)(key >> 32); };
+        auto pos = [&](unsigned long long key) { return key >> 32 ? ~(uint32_t)key : s; };
+        records_out[r] = msspe_reach_record{a.sites_plus,    a.sites_minus,     a.reached_plus,   a.reached_minus,
+                                            a.reached_either, a.reached_both,    len(a.gap_plus),  pos(a.gap_plus),
+                                            len(a.gap_minus), pos(a.gap_minus),  len(a.gap_either), pos(a.gap_either)};
+    }
+    return MSSPE_OK;
+}
+
+int msspe_stream_reach(msspe_ctx *ctx, const char *const *records, const size_t *record_bytes, int n_records, int k,
+                       const msspe_mismatch_opt *mm, const uint64_t *words, int n, const msspe_chem *chem, int mode,
+                       float tm_threshold, int flank, const msspe_reach_opt *reach_opt, uint64_t *sites_out,
+                       uint64_t *stable_out, msspe_reach_record *records_out, uint64_t *record_start_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!mm || !sites_out || !stable_out || !chem || !reach_opt || !records_out || n < 0 || (n && !words))
+        return fail(ctx, MSSPE_ERR_ARG, "null argument");
+    void *d = nullptr;
+    size_t L = 0;
+    std::vector<uint64_t> starts((size_t)std::max(n_records, 0));
+    int rc = msspe_device_put_stream_packed(ctx, records, record_bytes, n_records, &d, &L, starts.data());
+    if (rc) return rc;
+    if (record_start_out) std::copy(starts.begin(), starts.end(), record_start_out);
+    if (n_records > 0)
+        rc = msspe_stream_reach_packed_dev(ctx, (const uint64_t *)d, L, k, mm, words, n, chem, mode, tm_threshold,
+                                           flank, reach_opt, starts.data(), n_records, sites_out, stable_out,
+                                           records_out);
+    else {   // no record: nothing to report on, but the arguments are still checked
+        msspe_reach_record none;
+        rc = msspe_stream_reach_packed_dev(ctx, (const uint64_t *)d, L, k, mm, words, n, chem, mode, tm_threshold,
+                                           flank, reach_opt, nullptr, 0, sites_out, stable_out, &none);
+    }
+    (void)msspe_device_free(ctx, d);
     return rc;
 }
 

@@ -108,6 +108,12 @@ const OptSpec kOpts[] = {
     {"--background-amplicon-max", "BACKGROUND_AMPLICON_MAX", OptSpec::OptInt, OFF(background_amplicon_max)},
     {"--background-amplicon-min", "BACKGROUND_AMPLICON_MIN", OptSpec::OptInt, OFF(background_amplicon_min)},
     {"--background-flank", "BACKGROUND_FLANK", OptSpec::OptInt, OFF(background_flank)},
+    {"--reach", "REACH", OptSpec::Str, OFF(reach_text)},
+    {"--reach-mismatches", "REACH_MISMATCHES", OptSpec::OptInt, OFF(reach_mismatches)},
+    {"--reach-3p-exact", "REACH_3P_EXACT", OptSpec::OptInt, OFF(reach_3p_exact)},
+    {"--reach-tm", "REACH_TM", OptSpec::Str, OFF(reach_tm_text)},
+    {"--reach-thal", "REACH_THAL", OptSpec::Str, OFF(reach_thal)},
+    {"--reach-out", "REACH_OUT", OptSpec::Str, OFF(reach_out)},
 };
 #undef OFF
 
@@ -202,7 +208,13 @@ std::string Args::usage()
          "--seed-mismatches <M> makes a run that extends a panel (--existing-primers, and the later rounds of\n"
          "--repick-rounds) count a segment as covered already when a panel primer matches it within M mismatches, its last\n"
          "--seed-3p-exact <E> bases exact, instead of only where it occurs verbatim; with --seed-tm <C> only where thal\n"
-         "(--seed-thal any | end1) scores such a match stable at C. One device.\n";
+         "(--seed-thal any | end1) scores such a match stable at C. One device.\n"
+         "--reach <D> adds a report on the input genomes themselves: how much of every genome lies within D bases\n"
+         "downstream of a site of the primers the CSV gets (the extension product, the primer included), on either\n"
+         "strand, and where its longest stretch lies that nothing primes into. Sites are matches within\n"
+         "--reach-mismatches <M> (default 2), the last --reach-3p-exact <E> bases exact (default 3); with --reach-tm <C>\n"
+         "only those thal (--reach-thal any | end1) scores stable at C. --reach-out <FILE> writes one CSV line per\n"
+         "genome. Needs --kmer-size 2..31; with --devices it runs on the first device.\n";
     return u;
 }
 
@@ -497,6 +509,47 @@ Args Args::parse(int argc, const char *const *argv)
                          "' is larger than '--kmer-size " + std::to_string(a.kmer_size) + "'");
     if (a.background_mismatches < 0) a.background_mismatches = std::min(2, a.kmer_size);
     if (a.background_3p_exact < 0) a.background_3p_exact = std::min(3, a.kmer_size);
+    if (a.reach_text.empty()) {
+        for (const auto &given : {std::make_pair("--reach-mismatches", a.reach_mismatches),
+                                  std::make_pair("--reach-3p-exact", a.reach_3p_exact)})
+            if (given.second >= 0) throw UsageError(std::string("error: '") + given.first + "' needs '--reach <D>'");
+        for (const auto &given : {std::make_pair("--reach-tm", &a.reach_tm_text),
+                                  std::make_pair("--reach-thal", &a.reach_thal),
+                                  std::make_pair("--reach-out", &a.reach_out)})
+            if (!given.second->empty())
+                throw UsageError(std::string("error: '") + given.first + "' needs '--reach <D>'");
+    } else {
+        char *end = nullptr;
+        const unsigned long long d = std::strtoull(a.reach_text.c_str(), &end, 10);
+        if (*end || a.reach_text[0] == '-' || a.reach_text[0] == '+' || d >= (1ull << 31))
+            throw UsageError("error: invalid value '" + a.reach_text + "' for '--reach <D>'\n  [possible values: "
+                             "the k-mer size .. 2147483647]");
+        if (a.kmer_size < 2) throw UsageError("error: '--reach' needs '--kmer-size' of at least 2");
+        if (d < (unsigned long long)a.kmer_size)
+            throw UsageError("error: '--reach " + a.reach_text + "' is smaller than '--kmer-size " +
+                             std::to_string(a.kmer_size) + "'");
+        a.reach = (long long)d;
+        if (!a.reach_thal.empty() && a.reach_tm_text.empty())
+            throw UsageError("error: '--reach-thal' needs '--reach-tm <C>'");
+        if (!a.reach_tm_text.empty()) {
+            a.reach_tm = std::strtof(a.reach_tm_text.c_str(), &end);
+            if (*end || std::isnan(a.reach_tm))
+                throw UsageError("error: invalid value '" + a.reach_tm_text + "' for '--reach-tm'");
+            a.reach_scored = true;
+            if (a.reach_thal.empty()) a.reach_thal = "any";
+            if (a.reach_thal != "any" && a.reach_thal != "end1")
+                throw UsageError("error: invalid value '" + a.reach_thal +
+                                 "' for '--reach-thal <...>'\n  [possible values: any, end1]");
+        }
+        if (a.reach_mismatches > a.kmer_size)
+            throw UsageError("error: '--reach-mismatches " + std::to_string(a.reach_mismatches) +
+                             "' is larger than '--kmer-size " + std::to_string(a.kmer_size) + "'");
+        if (a.reach_3p_exact > a.kmer_size)
+            throw UsageError("error: '--reach-3p-exact " + std::to_string(a.reach_3p_exact) +
+                             "' is larger than '--kmer-size " + std::to_string(a.kmer_size) + "'");
+        if (a.reach_mismatches < 0) a.reach_mismatches = std::min(2, a.kmer_size);
+        if (a.reach_3p_exact < 0) a.reach_3p_exact = std::min(3, a.kmer_size);
+    }
     return a;
 }
 
@@ -2588,6 +2641,115 @@ std::string background_report_amplicons(const std::vector<std::string> &names,
     return out;
 }
 
+std::vector<msspe_reach_record> target_reach(Engine &eng, const std::vector<SequenceRecord> &records,
+                                             const std::vector<std::string> &words, int k, int max_mismatches,
+                                             int exact_3p, const msspe_chem &chem, int mode, float tm_threshold,
+                                             uint32_t reach, std::vector<std::string> &genomes_out)
+{
+    for (const auto &w : words)
+        if ((int)w.size() != k)
+            throw std::runtime_error("--reach needs primers of one length, --kmer-size " + std::to_string(k) +
+                                     ": '" + w + "' has " + std::to_string(w.size()) + " bases");
+    std::vector<SequenceRecord> rows(records.size());   // each input row without its gap columns
+    genomes_out.assign(records.size(), std::string());
+    for (size_t r = 0; r < records.size(); ++r) {
+        rows[r].name = records[r].name;
+        for (const char c : records[r].sequence)
+            if (c != '-') rows[r].sequence.push_back(c);
+        genomes_out[r] = rows[r].sequence;
+    }
+    std::vector<msspe_reach_record> out(records.size());
+    if (records.empty()) return out;
+    DeviceBackground stream(eng, rows);   // uploaded once, freed when the report is done
+    const int n = (int)words.size();
+    std::string flat;
+    for (const auto &w : words) flat += w;
+    std::vector<uint64_t> packed((size_t)std::max(n, 1)), counts(2 * (size_t)std::max(n, 1)),
+        stable(2 * (size_t)std::max(n, 1));
+    int rc = n ? msspe_pack_oligos(flat.data(), n, k, packed.data()) : 0;
+    if (rc) eng.fail(rc);
+    const msspe_mismatch_opt mm{std::min(max_mismatches, k), std::min(exact_3p, k)};
+    const msspe_reach_opt opt{reach};
+    rc = stream.reach(k, mm, packed, n, chem, mode, tm_threshold, opt, counts, stable, out);
+    if (rc) eng.fail(rc);
+    return out;
+}
+
+int DeviceBackground::reach(int k, const msspe_mismatch_opt &mm, const std::vector<uint64_t> &packed, int n,
+                            const msspe_chem &chem, int mode, float tm_threshold, const msspe_reach_opt &opt,
+                            std::vector<uint64_t> &counts, std::vector<uint64_t> &stable,
+                            std::vector<msspe_reach_record> &out) const
+{
+    return msspe_stream_reach_packed_dev(eng_.ctx(), static_cast<const uint64_t *>(dev_), len_, k, &mm, packed.data(),
+                                         n, &chem, mode, tm_threshold, 0, &opt, starts_.data(), (int)starts_.size(),
+                                         counts.data(), stable.data(), out.data());
+}
+
+static std::string reach_rule(int max_mismatches, int exact_3p, bool scored, int mode, float tm_threshold)
+{
+    std::string out = "up to " + std::to_string(max_mismatches) + " mismatches, last " + std::to_string(exact_3p) +
+                      " bases exact";
+    if (scored) {
+        char thr[64];
+        std::snprintf(thr, sizeof thr, "%.2f", (double)tm_threshold);
+        out += std::string("; stable: thal ") + (mode == 2 ? "END1" : "ANY") + " t >= " + thr + " C";
+    }
+    return out;
+}
+
+std::string target_reach_report(const std::vector<std::string> &names, const std::vector<std::string> &genomes,
+                                const std::vector<msspe_reach_record> &recs, uint32_t reach, int max_mismatches,
+                                int exact_3p, bool scored, int mode, float tm_threshold)
+{
+    uint64_t columns = 0, plus = 0, minus = 0, either = 0, both = 0, gapped = 0;
+    std::vector<uint64_t> starts(recs.size());
+    for (size_t r = 0; r < recs.size(); ++r) {
+        starts[r] = r ? starts[r - 1] + genomes[r - 1].size() + 1 : 0;
+        columns += genomes[r].size();
+        plus += recs[r].reached_plus;
+        minus += recs[r].reached_minus;
+        either += recs[r].reached_either;
+        both += recs[r].reached_both;
+        gapped += recs[r].gap_either_len > reach;
+    }
+    std::string out = "\nTarget reach (extension " + std::to_string(reach) + " bases; sites: " +
+                      reach_rule(max_mismatches, exact_3p, scored, mode, tm_threshold) + "):\n";
+    out += "  Total: " + std::to_string(recs.size()) + " genomes, " + std::to_string(columns) + " columns, reached plus " +
+           std::to_string(plus) + ", minus " + std::to_string(minus) + ", either " + std::to_string(either) + ", both " +
+           std::to_string(both) + "\n";
+    out += "  Genomes with a gap above " + std::to_string(reach) + ": " + std::to_string(gapped) + "\n";
+    std::vector<size_t> order(recs.size());
+    for (size_t r = 0; r < order.size(); ++r) order[r] = r;
+    std::stable_sort(order.begin(), order.end(),
+                     [&](size_t a, size_t b) { return recs[a].gap_either_len > recs[b].gap_either_len; });
+    order.resize(std::min<size_t>(20, order.size()));
+    out += "  Longest gaps, " + std::to_string(order.size()) + " genomes (name: offset, length):\n";
+    for (const size_t r : order)
+        out += "    " + names[r] + ": " + std::to_string(recs[r].gap_either_pos - starts[r]) + ", " +
+               std::to_string(recs[r].gap_either_len) + "\n";
+    return out;
+}
+
+std::string target_reach_csv(const std::vector<std::string> &names, const std::vector<std::string> &genomes,
+                             const std::vector<msspe_reach_record> &recs)
+{
+    std::string out = "name,columns,sites_plus,sites_minus,reached_plus,reached_minus,reached_either,reached_both,"
+                      "gap_plus_len,gap_plus_pos,gap_minus_len,gap_minus_pos,gap_either_len,gap_either_pos\n";
+    uint64_t start = 0;
+    for (size_t r = 0; r < recs.size(); ++r) {
+        const msspe_reach_record &c = recs[r];
+        out += names[r] + "," + std::to_string(genomes[r].size());
+        for (const uint64_t v : {(uint64_t)c.sites_plus, (uint64_t)c.sites_minus, (uint64_t)c.reached_plus,
+                                 (uint64_t)c.reached_minus, (uint64_t)c.reached_either, (uint64_t)c.reached_both,
+                                 (uint64_t)c.gap_plus_len, c.gap_plus_pos - start, (uint64_t)c.gap_minus_len,
+                                 c.gap_minus_pos - start, (uint64_t)c.gap_either_len, c.gap_either_pos - start})
+            out += "," + std::to_string(v);
+        out += "\n";
+        start += genomes[r].size() + 1;
+    }
+    return out;
+}
+
 std::string background_report_scored(const std::vector<std::string> &names,
                                      const std::vector<std::pair<uint64_t, uint64_t>> &sites,
                                      const std::vector<std::pair<uint64_t, uint64_t>> &stable, int max_mismatches,
@@ -3085,6 +3247,24 @@ int run(const Args &args, std::string &stdout_text)
             stdout_text += background_report(names, background->sites(words, args.background_mismatches,
                                                                       args.background_3p_exact),
                                              args.background_mismatches, args.background_3p_exact);
+    }
+    if (args.reach >= 0) {   // the run's own genomes against the primers the CSV gets, forward and reverse alike
+        std::vector<std::string> words, names, genomes;
+        for (const auto &p : good_f) words.push_back(p.word);
+        for (const auto &p : good_r) words.push_back(p.word);
+        for (const auto &r : records) names.push_back(r.name);
+        const int reach_mode = args.reach_thal == "end1" ? 2 : 1;
+        const auto recs = target_reach(eng, records, words, args.kmer_size, args.reach_mismatches, args.reach_3p_exact,
+                                       ntthal_chem(opts), reach_mode, args.reach_scored ? args.reach_tm : 0.0f,
+                                       (uint32_t)args.reach, genomes);
+        stdout_text += target_reach_report(names, genomes, recs, (uint32_t)args.reach, args.reach_mismatches,
+                                           args.reach_3p_exact, args.reach_scored, reach_mode, args.reach_tm);
+        if (!args.reach_out.empty()) {
+            std::ofstream reach_file(args.reach_out, std::ios::binary);
+            if (!reach_file) throw std::runtime_error("cannot write " + args.reach_out);
+            reach_file << target_reach_csv(names, genomes, recs);
+        }
+        timer.lap("target reach");
     }
     std::ofstream out(args.output, std::ios::binary);
     if (!out) throw std::runtime_error("cannot write " + args.output);

@@ -167,6 +167,16 @@ struct Args {
     // to F base columns on either side of the window (dangling ends; msspe_background_thal_flank, 0..4,
     // kmer_size + 2 F <= 32).  -1 = not given (resolved to 0 by parse()): nothing changes.
     int background_flank = -1;
+    // --reach D: after everything else, a report on the run's own input genomes (each row without its gap columns):
+    // the columns within D bases downstream of a site of the CSV's primers on either strand, and every genome's
+    // longest stretch nothing primes into (msspe_stream_reach).  Sites: within reach_mismatches mismatches, the last
+    // reach_3p_exact bases exact; with --reach-tm C only those thal (--reach-thal any | end1) scores stable at C.
+    // --reach-out FILE: one CSV line per genome.  Report only.  Empty text / -1 = not given, nothing changes.
+    std::string reach_text, reach_tm_text, reach_thal, reach_out;
+    long long reach = -1;
+    int reach_mismatches = -1, reach_3p_exact = -1;
+    float reach_tm = 0.0f;
+    bool reach_scored = false;
     bool stddev_population = false;  // crate std-dev 0.1.0's divisor is unpinned
     static Args parse(int argc, const char *const *argv);   // throws UsageError
     static std::string usage();
@@ -548,6 +558,11 @@ public:
                                                          std::vector<msspe_amplicon> &list_out, int flank = 0) const;
     // (record id, offset in the record) of stream position pos
     std::pair<std::string, uint64_t> locate(uint64_t pos) const;
+    // msspe_stream_reach_packed_dev on the resident stream with its own record starts, flank 0: n packed words of k
+    // bases; counts / stable hold 2 n entries, out one per record.  Returns the status.
+    int reach(int k, const msspe_mismatch_opt &mm, const std::vector<uint64_t> &packed, int n, const msspe_chem &chem,
+              int mode, float tm_threshold, const msspe_reach_opt &opt, std::vector<uint64_t> &counts,
+              std::vector<uint64_t> &stable, std::vector<msspe_reach_record> &out) const;
 
 private:
     Engine &eng_;
@@ -574,6 +589,20 @@ std::string background_report_amplicons(const std::vector<std::string> &names,
                                         const std::vector<std::pair<uint64_t, uint64_t>> &counts,
                                         const std::vector<msspe_amplicon> &list, const DeviceBackground &background,
                                         uint32_t min_len, uint32_t max_len);
+// --reach (engine extension): the input rows without their gap columns (genomes_out) as one resident stream, screened
+// with `words` (all of k bases) on both strands; one record per genome, positions in that stream
+std::vector<msspe_reach_record> target_reach(Engine &eng, const std::vector<SequenceRecord> &records,
+                                             const std::vector<std::string> &words, int k, int max_mismatches,
+                                             int exact_3p, const msspe_chem &chem, int mode, float tm_threshold,
+                                             uint32_t reach, std::vector<std::string> &genomes_out);
+// "Target reach (extension D bases; sites: ...):", the totals over all genomes, the number of genomes whose longest gap
+// (columns reached on neither strand) exceeds D, and the 20 genomes with the longest such gap as "name: offset, length"
+std::string target_reach_report(const std::vector<std::string> &names, const std::vector<std::string> &genomes,
+                                const std::vector<msspe_reach_record> &recs, uint32_t reach, int max_mismatches,
+                                int exact_3p, bool scored, int mode, float tm_threshold);
+// --reach-out: a header and one line per genome with every field, positions as offsets in the ungapped genome
+std::string target_reach_csv(const std::vector<std::string> &names, const std::vector<std::string> &genomes,
+                             const std::vector<msspe_reach_record> &recs);
 // main.rs:834-858
 // first_f / first_r: the number of the first row of each direction (a panel's extension continues its numbering)
 // tubes (--tubes): an eighth column "tube", 1-based, empty for a primer in no tube

@@ -57,6 +57,7 @@ EXPORTS = [
     "msspe_background_amplicons_packed_dev", "msspe_background_amplicons",
     "msspe_background_thal_flank_packed_dev", "msspe_background_thal_flank",
     "msspe_background_amplicons_flank_packed_dev", "msspe_background_amplicons_flank",
+    "msspe_stream_reach_packed_dev", "msspe_stream_reach",
     "msspe_round_fixed_f32", "msspe_g_cut",
     "msspe_group_create", "msspe_group_destroy", "msspe_group_last_error", "msspe_group_size",
     "msspe_group_transport", "msspe_group_transport_reason", "msspe_group_rccl_available", "msspe_group_member", "msspe_group_set_option", "msspe_group_rows",
@@ -135,6 +136,18 @@ AMPLICON_DTYPE = np.dtype([("fwd", np.uint32), ("rev", np.uint32), ("pos", np.ui
 class AmpliconOpt(C.Structure):
     """msspe_amplicon_opt: product lengths (both primers included) that count, k <= min_len <= max_len."""
     _fields_ = [("min_len", C.c_uint32), ("max_len", C.c_uint32)]
+
+
+# msspe_reach_record: what the stable sites of one record reach (msspe_stream_reach*); positions are stream positions
+REACH_RECORD_DTYPE = np.dtype([(f, np.uint32) for f in (
+    "sites_plus", "sites_minus", "reached_plus", "reached_minus", "reached_either", "reached_both",
+    "gap_plus_len", "gap_plus_pos", "gap_minus_len", "gap_minus_pos", "gap_either_len", "gap_either_pos")])
+assert REACH_RECORD_DTYPE.itemsize == 48
+
+
+class ReachOpt(C.Structure):
+    """msspe_reach_opt: the length of the extension product, the primer included, k <= reach < 2^31."""
+    _fields_ = [("reach", C.c_uint32)]
 
 
 class MismatchOpt(C.Structure):
@@ -416,6 +429,12 @@ def load_library() -> C.CDLL:
         cut = at.index(C.c_float) + 1
         getattr(L, name.replace("_background_thal", "_background_thal_flank")
                 .replace("_background_amplicons", "_background_amplicons_flank")).argtypes = at[:cut] + [C.c_int] + at[cut:]
+    L.msspe_stream_reach_packed_dev.argtypes = [
+        vp, vp, C.c_size_t, C.c_int, C.POINTER(MismatchOpt), u64p, C.c_int, C.POINTER(Chem), C.c_int, C.c_float,
+        C.c_int, C.POINTER(ReachOpt), vp, C.c_int, vp, vp, vp]
+    L.msspe_stream_reach.argtypes = [
+        vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(MismatchOpt), u64p, C.c_int,
+        C.POINTER(Chem), C.c_int, C.c_float, C.c_int, C.POINTER(ReachOpt), vp, vp, vp, vp]
     L.msspe_device_get.argtypes = [vp, vp, C.c_size_t, vp]
     L.msspe_host_table_routes.argtypes = [C.c_char_p, C.POINTER(Chem), C.POINTER(C.c_int32)]
     L.msspe_host_screen_plan.argtypes = [C.c_int] * 5 + [C.c_int64, vp, C.c_int, C.POINTER(C.c_int)]
@@ -1771,6 +1790,42 @@ class Engine:
         if lst is None:
             return counts, stable, amps, int(total.value), starts
         return counts, stable, amps, int(total.value), starts, lst[:count.value]
+
+    def stream_reach_packed(self, d_packed: int, total_len: int, primers, max_mismatches: int, exact_3p: int,
+                            chem: Chem, tm_threshold: float, mode, reach: int, record_start=None,
+                            k: int | None = None, flank: int = 0):
+        """What the stable sites of a resident stream reach (msspe_stream_reach_packed_dev): per record the columns
+        within `reach` downstream of a stable plus-strand site (towards increasing positions) or minus-strand site
+        (towards decreasing positions), and the longest run nothing reaches.  record_start: the record starts
+        put_stream_packed returned (None: the stream is one record).  Returns (counts, stable, records): uint64
+        (n, 2) each as background_thal_packed returns them, and a REACH_RECORD_DTYPE array, one entry per record."""
+        w, k = _words_k(primers, k)
+        counts = np.zeros((len(w), 2), dtype=np.uint64)
+        stable = np.zeros((len(w), 2), dtype=np.uint64)
+        mm, opt = MismatchOpt(max_mismatches, exact_3p), ReachOpt(reach)
+        starts = None if record_start is None else np.ascontiguousarray(record_start, dtype=np.uint64)
+        recs = np.zeros(max(1 if starts is None else len(starts), 1), dtype=REACH_RECORD_DTYPE)
+        self._check(self.L.msspe_stream_reach_packed_dev(
+            self.ptr, C.c_void_p(d_packed), total_len, k, C.byref(mm), w.ctypes.data, len(w), C.byref(chem),
+            self._thal_mode(mode), tm_threshold, flank, C.byref(opt), None if starts is None else starts.ctypes.data,
+            0 if starts is None else len(starts), counts.ctypes.data, stable.ctypes.data, recs.ctypes.data))
+        return counts, stable, recs[:1 if starts is None else len(starts)]
+
+    def stream_reach(self, records, primers, max_mismatches: int, exact_3p: int, chem: Chem, tm_threshold: float,
+                     mode, reach: int, k: int | None = None, flank: int = 0):
+        """Host form (msspe_stream_reach): returns (counts, stable, records, starts)."""
+        _recs, ptrs, lens, n = self._records(records)
+        w, k = _words_k(primers, k)
+        counts = np.zeros((len(w), 2), dtype=np.uint64)
+        stable = np.zeros((len(w), 2), dtype=np.uint64)
+        starts = np.zeros(n, dtype=np.uint64)
+        mm, opt = MismatchOpt(max_mismatches, exact_3p), ReachOpt(reach)
+        recs = np.zeros(max(n, 1), dtype=REACH_RECORD_DTYPE)
+        self._check(self.L.msspe_stream_reach(
+            self.ptr, ptrs, lens, n, k, C.byref(mm), w.ctypes.data, len(w), C.byref(chem), self._thal_mode(mode),
+            tm_threshold, flank, C.byref(opt), counts.ctypes.data, stable.ctypes.data, recs.ctypes.data,
+            starts.ctypes.data))
+        return counts, stable, recs[:n], starts
 
     def thal_detail(self, a, b, chem: Chem | None = None, mode="any") -> np.ndarray:
         """Full thal record of the pairs (a[i], b[i]) (msspe_thal_detail_pairs): two equal-length lists of strings of
