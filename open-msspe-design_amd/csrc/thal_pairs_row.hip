@@ -861,7 +861,7 @@ static __device__ __forceinline__ void packed_publish(v32i &Wa, v16i &Wb, v4i &W
                  : "m0");
 }
 
-// ---- the WINDOWED packed instance (k_pairs_bound_window): rows i-F .. i-1 are scanned as above, every row above them
+// ---- the WINDOWED packed instance (k_pairs_bound_window, run_pair_window): rows i-F .. i-1 are scanned as above, every row above them
 // is ONE candidate,  farmin + min(Bfar, Ifar + cell-side term)  -- farmin: the smallest value any stored cell of the rows
 // <= i-1-F holds, whatever its column; Ifar / Bfar: the smallest finite coarse table entry over l1 >= F with l2 >= 1 /
 // l2 = 0, any context (fast_tables.hpp BoundWindow).  That candidate is at most every candidate it replaces, so by
@@ -882,18 +882,17 @@ static_assert(kWinVoid - kPkReach - kPkReach > kPkReach, "a far candidate that h
 // in the near role would miss the cell-side term build_bound_table took out of its entry).
 static_assert(MSSPE_BRG13_KC == MSSPE_BPK13_KC && MSSPE_BRG13_W0 == MSSPE_BPK13_W0 && MSSPE_BRG13_BANK == 16, "the ring's register map");
 static_assert(MSSPE_BRP13_KC == MSSPE_BRG13_KC && MSSPE_BRP13_W0 == MSSPE_BRG13_W0 && MSSPE_BRP13_BANK == MSSPE_BRG13_BANK &&
-              MSSPE_BRP13_GRAN == MSSPE_BRG13_GRAN && MSSPE_BRP13_NSZ == MSSPE_BRG13_NSZ,
+              MSSPE_BRP13_NSZ == MSSPE_BRG13_NSZ,
               "the two-cell scan is the ring scan's: same banks, chunks and widths");
 static constexpr int kRingBank = MSSPE_BRG13_BANK;
-static constexpr int kRingGran = MSSPE_BRG13_GRAN;   // 1: a row's exact width is scanned; 2: rows padded to an even width
-static_assert(kRowK <= kRingBank - (kRingGran - 1), "a row (and its pad slot) fits a bank");
+static_assert(kRowK <= kRingBank, "a row fits a bank");
 
-// rot: i % 3; wf, wn: the (padded) widths of rows i-2 and i-1, 0 for a row that does not exist -- all wave-uniform
+// rot: i % 3; wf, wn: the stored widths of rows i-2 and i-1, 0 for a row that does not exist -- all wave-uniform
 struct RingCtl { int idx, wf, wn, wmax; };
 static __device__ __forceinline__ RingCtl ring_ctl(int rot, int wf, int wn)
 {
     constexpr int kC4 = MSSPE_BRG13_KC, kN = MSSPE_BRG13_NSZ;
-    return {(rot * kN + min(wf, kC4) / kRingGran) * kN + min(wn, kC4) / kRingGran, wf, wn, max(wf, wn)};
+    return {(rot * kN + min(wf, kC4)) * kN + min(wn, kC4), wf, wn, max(wf, wn)};
 }
 static __device__ __forceinline__ void ring_scan(const v16i Ra, const v16i Rb, const v16i Rc, unsigned C, const RingCtl &r,
                                               int &acc_far, int &acc_near)
@@ -943,16 +942,14 @@ static __device__ __forceinline__ void window_fold(const v16i Ra, const v16i Rb,
     farmin = min(farmin, w & 0xffff);
 }
 
-// run_pair_bound on the packed table: the minimum over the lane's cells of (cell value + right end term) in coarse
-// units; kPkInit: the pair has no cell.  bias: BoundPacked::bias (wave-uniform).
-// WIN: the windowed instance (rows above the window: the far candidate; ifar, bfar: wave-uniform, kWinVoid where void).
-template <int NS, bool WIN = false>
-static __device__ __forceinline__ int run_pair_packed(SharedRow &sh, const SeqPair &q, bool active, unsigned wmax4, int bias,
-                                                   int ifar = 0, int bfar = 0)
+// run_pair_bound on the packed table (k_pairs_bound_packed): the minimum over the lane's cells of (cell value + right
+// end term) in coarse units; kPkInit: the pair has no cell.  bias: BoundPacked::bias (wave-uniform).  One cell per scan.
+template <int NS>
+static __device__ __forceinline__ int run_pair_packed(SharedRow &sh, const SeqPair &q, bool active, unsigned wmax4, int bias)
 {
     static_assert(kPin && NS == 52, "the bound instance exists for 13 bases");
     constexpr int kC4 = MSSPE_BPK13_KC;
-    constexpr int kEmptyW = (kEmptyRowK << 17) | (WIN ? kWinNone : 0);
+    constexpr int kEmptyW = kEmptyRowK << 17;
     v32i Wa = kEmptyW;
     v16i Wb = kEmptyW;
     v4i Wc = kEmptyW;
@@ -960,10 +957,6 @@ static __device__ __forceinline__ int run_pair_packed(SharedRow &sh, const SeqPa
     const int kc = 0x7fff - bias + kPkOff;   // u + Tn = kc - (entry + predecessor's value)
     int pick = kPkInit;
     int slot_ = 0, start_im1 = 0;   // first slot of row i-1
-    int farmin = kWinNone;          // WIN: the smallest field of the rows <= i-1-F
-    v16i Ra = kEmptyW, Rb = kEmptyW, Rc = kEmptyW;   // WIN: the ring's banks
-    int rot = 0;                         // WIN: i % 3, row i's bank
-    int w_im1 = 0, w_im2 = 0, w_im3 = 0;   // WIN: the stored widths of rows i-1, i-2, i-3 (0: no such row)
     for (int i_ = 0; i_ < q.len; ++i_) {
       const int im1 = __builtin_amdgcn_readfirstlane(i_);
       const int a_row = (int)((q.s1 >> (2 * im1)) & 3u);
@@ -971,100 +964,112 @@ static __device__ __forceinline__ int run_pair_packed(SharedRow &sh, const SeqPa
       const int row_start = __builtin_amdgcn_readfirstlane(slot_);
       const bool stored = im1 < q.len - 1;   // wave-uniform: the cells of the last row are nobody's predecessors
       unsigned mrem = active ? spaced_mask(q.s2, 3 - a_row, q.lenmask) : 0u;
-      if constexpr (WIN) {
-        // row i-1-F leaves the window: its slots join farmin, once per slot (wave-uniform bounds)
-        // (they are slots 0 .. w(i-3)-1 of the bank row i is about to take)
-        for (int c_ = 0; c_ < w_im3; ++c_)
-          window_fold(Ra, Rb, Rc, __builtin_amdgcn_readfirstlane(rot * kRingBank + c_), farmin);
-      }
-      if constexpr (!WIN) {
-        // the un-windowed packed instance (k_pairs_bound_packed): one cell per scan
-        for (int c_ = 0; c_ < w_row; ++c_, slot_ += stored ? 1 : 0) {
-          const int slot = __builtin_amdgcn_readfirstlane(slot_);
-          const bool in = mrem != 0u;
-          const int jm1 = ((__ffs((int)mrem) - 1) >> 1) & 15;
-          mrem &= mrem - 1;
-          const unsigned C = ((unsigned)((jm1 - 1) * kRowA + im1 * (4 * (kRowR + 1)) + 3) << 17) | 0x7fffu;
-          const int yTS = sh.yts[(im1 << 2) | (int)(((q.s2 << 2) >> (2 * jm1)) & 3u)];
-          int acc_far, acc_near;
-          packed_scan(Wa, Wb, Wc, C, yTS, start_im1 / kC4, (row_start + kC4 - 1) / kC4, start_im1, acc_far, acc_near);
-          const CellBases b = cell_bases(q, im1, jm1, c);
-          const int gL = sh.g[b.idxL - kRowGBase], gR = sh.g[b.idxR - kRowGBase];
-          // the far minimum takes the cell-side term here, once; an accumulator without a real candidate decodes far above gL
-          const int G0 = min(gL, min(kc - acc_far + yTS, kc - acc_near));
-          pick = in ? min(pick, G0 + gR) : pick;
-          // G0 + bias is a 15-bit field: BoundPacked's proven range [lo, hi] of every publishable value (a lane without a
-          // cell here publishes an empty slot: its word fails every geometry test)
-          const int Wcell = in ? ((int)((unsigned)(jm1 * kRowA + (im1 << 2) + ((b.po_c >> 4) & 3)) << 17) + (G0 + bias)) : kEmptyW;
-          if (slot < NS) packed_publish(Wa, Wb, Wc, slot, Wcell);
-        }
-      } else {
-        // the windowed instance (k_pairs_bound_window): the cells of a row two at a time, an odd one behind them
-        // the lane's next cell of the row: in, jm1, the scan's minuend C and the cell-side term
-        auto next_cell = [&](bool &in, int &jm1, unsigned &C, int &yTS) {
-          in = mrem != 0u;
-          jm1 = ((__ffs((int)mrem) - 1) >> 1) & 15;
-          mrem &= mrem - 1;
-          C = ((unsigned)((jm1 - 1) * kRowA + im1 * (4 * (kRowR + 1)) + 3) << 17) | 0x7fffu;
-          yTS = sh.yts[(im1 << 2) | (int)(((q.s2 << 2) >> (2 * jm1)) & 3u)];
-        };
-        // the cell behind its scan: the value, the pick, and the slot word it publishes
-        auto finish_cell = [&](bool in, int jm1, int yTS, int acc_far, int acc_near) {
-          const CellBases b = cell_bases(q, im1, jm1, c);
-          const int gL = sh.g[b.idxL - kRowGBase], gR = sh.g[b.idxR - kRowGBase];
-          // the far minimum takes the cell-side term here, once; an accumulator without a real candidate decodes far above gL
-          int G0 = min(gL, min(kc - acc_far + yTS, kc - acc_near));
-          // the rows above the window: one candidate (a void yTS is kPkYVoid: the bulge constant alone is left)
-          const int far = farmin >= kWinNone ? kWinVoid : farmin - bias + min(bfar, ifar + yTS);
-          G0 = min(G0, far);
-          pick = in ? min(pick, G0 + gR) : pick;
-          // G0 + bias is a 15-bit field: BoundPacked's proven range [lo, hi] of every publishable value (a lane without a
-          // cell here publishes an empty slot: its word fails every geometry test)
-          return in ? ((int)((unsigned)(jm1 * kRowA + (im1 << 2) + ((b.po_c >> 4) & 3)) << 17) + (G0 + bias)) : kEmptyW;
-        };
-        constexpr int kG = kRingGran;
-        const RingCtl ring = ring_ctl(rot, (w_im2 + kG - 1) / kG * kG, (w_im1 + kG - 1) / kG * kG);
-        const int bank0 = rot * kRingBank;
-        int c_ = 0;
-        {
-          // Two cells of a row never depend on each other: they are scanned in one pass and published behind it, A's word and
-          // then B's (row i's own bank is not among the two a cell of row i scans).
-          for (; c_ + 2 <= w_row; c_ += 2) {
-            const int reg = __builtin_amdgcn_readfirstlane(bank0 + c_);
-            bool in_a, in_b;
-            int jm1_a, jm1_b, y_a, y_b, far_a, near_a, far_b, near_b;
-            unsigned C_a, C_b;
-            next_cell(in_a, jm1_a, C_a, y_a);
-            next_cell(in_b, jm1_b, C_b, y_b);
-            ring_scan_pair(Ra, Rb, Rc, C_a, C_b, ring, far_a, near_a, far_b, near_b);
-            const int W_a = finish_cell(in_a, jm1_a, y_a, far_a, near_a);
-            const int W_b = finish_cell(in_b, jm1_b, y_b, far_b, near_b);
-            if (stored) {   // the last row is stored nowhere
-              ring_publish(Ra, Rb, Rc, reg, W_a);
-              ring_publish(Ra, Rb, Rc, reg + 1, W_b);
-            }
-          }
-        }
-        for (; c_ < w_row; ++c_) {
-          const int reg = __builtin_amdgcn_readfirstlane(bank0 + c_);
-          bool in;
-          int jm1, yTS, acc_far, acc_near;
-          unsigned C;
-          next_cell(in, jm1, C, yTS);
-          ring_scan(Ra, Rb, Rc, C, ring, acc_far, acc_near);
-          const int Wcell = finish_cell(in, jm1, yTS, acc_far, acc_near);
-          if (stored) ring_publish(Ra, Rb, Rc, reg, Wcell);
-        }
-        // the even form scans a row of odd width one slot further: that slot holds the empty word
-        if (kG == 2 && stored && (w_row & 1)) ring_publish(Ra, Rb, Rc, __builtin_amdgcn_readfirstlane(bank0 + w_row), kEmptyW);
+      for (int c_ = 0; c_ < w_row; ++c_, slot_ += stored ? 1 : 0) {
+        const int slot = __builtin_amdgcn_readfirstlane(slot_);
+        const bool in = mrem != 0u;
+        const int jm1 = ((__ffs((int)mrem) - 1) >> 1) & 15;
+        mrem &= mrem - 1;
+        const unsigned C = ((unsigned)((jm1 - 1) * kRowA + im1 * (4 * (kRowR + 1)) + 3) << 17) | 0x7fffu;
+        const int yTS = sh.yts[(im1 << 2) | (int)(((q.s2 << 2) >> (2 * jm1)) & 3u)];
+        int acc_far, acc_near;
+        packed_scan(Wa, Wb, Wc, C, yTS, start_im1 / kC4, (row_start + kC4 - 1) / kC4, start_im1, acc_far, acc_near);
+        const CellBases b = cell_bases(q, im1, jm1, c);
+        const int gL = sh.g[b.idxL - kRowGBase], gR = sh.g[b.idxR - kRowGBase];
+        // the far minimum takes the cell-side term here, once; an accumulator without a real candidate decodes far above gL
+        const int G0 = min(gL, min(kc - acc_far + yTS, kc - acc_near));
+        pick = in ? min(pick, G0 + gR) : pick;
+        // G0 + bias is a 15-bit field: BoundPacked's proven range [lo, hi] of every publishable value (a lane without a
+        // cell here publishes an empty slot: its word fails every geometry test)
+        const int Wcell = in ? ((int)((unsigned)(jm1 * kRowA + (im1 << 2) + ((b.po_c >> 4) & 3)) << 17) + (G0 + bias)) : kEmptyW;
+        if (slot < NS) packed_publish(Wa, Wb, Wc, slot, Wcell);
       }
       start_im1 = row_start;
-      if constexpr (WIN) {
-        w_im3 = w_im2;
-        w_im2 = w_im1;
-        w_im1 = __builtin_amdgcn_readfirstlane(stored ? w_row : 0);
-        rot = rot == 2 ? 0 : rot + 1;
+    }
+    return pick;
+}
+
+// The windowed instance's cell loop (k_pairs_bound_window): the same minimum, kPkInit and bias as run_pair_packed, with the
+// rows of the window in the ring and the rows above it one far candidate (ifar, bfar: wave-uniform, kWinVoid where
+// void).  The cells of a row two at a time, an odd one behind them.
+template <int NS>
+static __device__ __forceinline__ int run_pair_window(SharedRow &sh, const SeqPair &q, bool active, unsigned wmax4, int bias,
+                                                   int ifar, int bfar)
+{
+    static_assert(kPin && NS == 52, "the bound instance exists for 13 bases");
+    constexpr int kEmptyW = (kEmptyRowK << 17) | kWinNone;
+    CellCtx c;
+    const int kc = 0x7fff - bias + kPkOff;   // u + Tn = kc - (entry + predecessor's value)
+    int pick = kPkInit;
+    int farmin = kWinNone;          // the smallest field of the rows <= i-1-F
+    v16i Ra = kEmptyW, Rb = kEmptyW, Rc = kEmptyW;   // the ring's banks
+    int rot = 0;                         // i % 3, row i's bank
+    int w_im1 = 0, w_im2 = 0, w_im3 = 0;   // the stored widths of rows i-1, i-2, i-3 (0: no such row)
+    for (int i_ = 0; i_ < q.len; ++i_) {
+      const int im1 = __builtin_amdgcn_readfirstlane(i_);
+      const int a_row = (int)((q.s1 >> (2 * im1)) & 3u);
+      const int w_row = (int)((wmax4 >> (8 * (3 - a_row))) & 0xffu);   // widest lane's cells in this row
+      const bool stored = im1 < q.len - 1;   // wave-uniform: the cells of the last row are nobody's predecessors
+      unsigned mrem = active ? spaced_mask(q.s2, 3 - a_row, q.lenmask) : 0u;
+      // row i-1-F leaves the window: its slots join farmin, once per slot (wave-uniform bounds)
+      // (they are slots 0 .. w(i-3)-1 of the bank row i is about to take)
+      for (int c_ = 0; c_ < w_im3; ++c_)
+        window_fold(Ra, Rb, Rc, __builtin_amdgcn_readfirstlane(rot * kRingBank + c_), farmin);
+      // the lane's next cell of the row: in, jm1, the scan's minuend C and the cell-side term
+      auto next_cell = [&](bool &in, int &jm1, unsigned &C, int &yTS) {
+        in = mrem != 0u;
+        jm1 = ((__ffs((int)mrem) - 1) >> 1) & 15;
+        mrem &= mrem - 1;
+        C = ((unsigned)((jm1 - 1) * kRowA + im1 * (4 * (kRowR + 1)) + 3) << 17) | 0x7fffu;
+        yTS = sh.yts[(im1 << 2) | (int)(((q.s2 << 2) >> (2 * jm1)) & 3u)];
+      };
+      // the cell behind its scan: the value, the pick, and the slot word it publishes
+      auto finish_cell = [&](bool in, int jm1, int yTS, int acc_far, int acc_near) {
+        const CellBases b = cell_bases(q, im1, jm1, c);
+        const int gL = sh.g[b.idxL - kRowGBase], gR = sh.g[b.idxR - kRowGBase];
+        // the far minimum takes the cell-side term here, once; an accumulator without a real candidate decodes far above gL
+        int G0 = min(gL, min(kc - acc_far + yTS, kc - acc_near));
+        // the rows above the window: one candidate (a void yTS is kPkYVoid: the bulge constant alone is left)
+        const int far = farmin >= kWinNone ? kWinVoid : farmin - bias + min(bfar, ifar + yTS);
+        G0 = min(G0, far);
+        pick = in ? min(pick, G0 + gR) : pick;
+        // G0 + bias is a 15-bit field: BoundPacked's proven range [lo, hi] of every publishable value (a lane without a
+        // cell here publishes an empty slot: its word fails every geometry test)
+        return in ? ((int)((unsigned)(jm1 * kRowA + (im1 << 2) + ((b.po_c >> 4) & 3)) << 17) + (G0 + bias)) : kEmptyW;
+      };
+      const RingCtl ring = ring_ctl(rot, w_im2, w_im1);
+      const int bank0 = rot * kRingBank;
+      int c_ = 0;
+      // Two cells of a row never depend on each other: they are scanned in one pass and published behind it, A's word and
+      // then B's (row i's own bank is not among the two a cell of row i scans).
+      for (; c_ + 2 <= w_row; c_ += 2) {
+        const int reg = __builtin_amdgcn_readfirstlane(bank0 + c_);
+        bool in_a, in_b;
+        int jm1_a, jm1_b, y_a, y_b, far_a, near_a, far_b, near_b;
+        unsigned C_a, C_b;
+        next_cell(in_a, jm1_a, C_a, y_a);
+        next_cell(in_b, jm1_b, C_b, y_b);
+        ring_scan_pair(Ra, Rb, Rc, C_a, C_b, ring, far_a, near_a, far_b, near_b);
+        const int W_a = finish_cell(in_a, jm1_a, y_a, far_a, near_a);
+        const int W_b = finish_cell(in_b, jm1_b, y_b, far_b, near_b);
+        if (stored) {   // the last row is stored nowhere
+          ring_publish(Ra, Rb, Rc, reg, W_a);
+          ring_publish(Ra, Rb, Rc, reg + 1, W_b);
+        }
       }
+      for (; c_ < w_row; ++c_) {
+        const int reg = __builtin_amdgcn_readfirstlane(bank0 + c_);
+        bool in;
+        int jm1, yTS, acc_far, acc_near;
+        unsigned C;
+        next_cell(in, jm1, C, yTS);
+        ring_scan(Ra, Rb, Rc, C, ring, acc_far, acc_near);
+        const int Wcell = finish_cell(in, jm1, yTS, acc_far, acc_near);
+        if (stored) ring_publish(Ra, Rb, Rc, reg, Wcell);
+      }
+      w_im3 = w_im2;
+      w_im2 = w_im1;
+      w_im1 = __builtin_amdgcn_readfirstlane(stored ? w_row : 0);
+      rot = rot == 2 ? 0 : rot + 1;
     }
     return pick;
 }
@@ -1127,8 +1132,9 @@ static __device__ __forceinline__ void build_bound_table(SharedRow &sh, const In
 
 // One lock-step DP of the wave: lane = (row, col), all lanes share `row`.
 // twin (BOUND, mirror mode only): the pair stands for (col, row) as well -- what is appended is appended in both orders.
-// PACKED (with BOUND): the packed instance's cell loop and units; everything around it is the bound instance's.
-// WIN (with PACKED): the windowed instance (k_pairs_bound_window).  Its value is below the packed one's, so a lane it does
+// PACKED (with BOUND): the packed instance's cell loop (run_pair_packed) and units; everything around it is the bound
+// instance's.
+// WIN (with PACKED): the windowed instance (k_pairs_bound_window, run_pair_window).  Its value is below the packed one's, so a lane it does
 // not cull is not a survivor of the bound yet: it goes to list U like an unbounded lane, where the exact-unit bound of
 // k_pairs_bound_list decides (a launch WITHOUT list U is refused by launch_pairs_bound).
 template <int NS, bool BOUND = false, bool PACKED = false, bool WIN = false>
@@ -1215,9 +1221,9 @@ static __device__ __forceinline__ void wave_pairs_row(SharedRow &sh, const IntAr
             const unsigned wmax4 = (unsigned)w4[0] | ((unsigned)w4[1] << 8) | ((unsigned)w4[2] << 16) | ((unsigned)w4[3] << 24);
             int pick;
             if constexpr (WIN)
-                pick = run_pair_packed<NS, true>(sh, q, active, wmax4, __builtin_amdgcn_readfirstlane(a.packed_bias),
-                                                 __builtin_amdgcn_readfirstlane(a.window_ifar),
-                                                 __builtin_amdgcn_readfirstlane(a.window_bfar));
+                pick = run_pair_window<NS>(sh, q, active, wmax4, __builtin_amdgcn_readfirstlane(a.packed_bias),
+                                           __builtin_amdgcn_readfirstlane(a.window_ifar),
+                                           __builtin_amdgcn_readfirstlane(a.window_bfar));
             else if constexpr (PACKED) pick = run_pair_packed<NS>(sh, q, active, wmax4, __builtin_amdgcn_readfirstlane(a.packed_bias));
             else pick = run_pair_bound<NS>(sh, q, active, wmax4);
             const int lb = pick + a.bt->init;   // a lane without a chain keeps kBndInit (kPkInit): above every cut
@@ -1509,7 +1515,7 @@ __global__ void __launch_bounds__(NT) k_pairs_bound_packed(IntArgs a)
 }
 
 // The windowed packed instance: the same tables, slot words and block, but a cell scans the rows of its window only and
-// takes one candidate for everything above (run_pair_packed<NS, true>); what it does not cull goes to list U.
+// takes one candidate for everything above (run_pair_window); what it does not cull goes to list U.
 template <class RK, int NT>
 __global__ void __launch_bounds__(NT) k_pairs_bound_window(IntArgs a)
 {

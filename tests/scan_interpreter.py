@@ -1,5 +1,5 @@
-"""A one-lane interpreter for the scans tools/gen_row_bound_packed_asm.py writes (the packed, the windowed and the
-two-cell windowed scan), for the tests that check them without a GPU.
+"""A one-lane interpreter for the scans tools/gen_row_bound_packed_asm.py writes (the packed scan and the two
+ring scans), for the tests that check them without a GPU.
 
 It knows the handful of instructions the generator emits and nothing else (an unknown one raises).  LDS reads are an
 in-order queue: ds_read_b32 takes its address when it is issued and delivers its value only when an s_waitcnt

@@ -1,5 +1,5 @@
 """The windowed packed bound first stage on the device (option pair_bound_window; csrc/thal_pairs_row.hip
-k_pairs_bound_window, the generated scan row_bound_window_pinned.inc).
+k_pairs_bound_window, the generated scans row_bound_ring_pinned.inc and row_bound_ring_pair_pinned.inc).
 
 Values: msspe_cross_dimer_bound_window_dev writes the instance's value of every pair -- +inf (no chain), -inf (not
 bounded there) or (pick + init) * unit -- and tests/pair_bound_window_model.py computes the same integer from the coarse

@@ -1,5 +1,5 @@
-"""The windowed bound first stage scans two cells of a row in one pass (csrc/thal_pairs_row.hip run_pair_packed<NS, true>,
-the generated scan row_bound_window_pair_pinned.inc): the diagnostic plane msspe_cross_dimer_bound_window_dev against
+"""The windowed bound first stage scans two cells of a row in one pass (csrc/thal_pairs_row.hip run_pair_window,
+the generated scan row_bound_ring_pair_pinned.inc): the diagnostic plane msspe_cross_dimer_bound_window_dev against
 tests/pair_bound_window_model.py, == on float64, on the stock tables and on the bundle whose long loops are cheap.
 
 What the pairing can get wrong is decided by the widths of a table's rows (a row of width w is w // 2 two-cell scans

@@ -6,12 +6,12 @@ register 76 + 16 * (i % 3) + c) and a cell of row i visits bank (i-2) % 3 slots 
 bank (i-1) % 3 slots 0 .. wn-1 into the near one: nothing else.  For every (rotation, wf, wn) in 3 x 0..13 x 0..13,
 with random slot words and a random table (a third of its entries "not available"), every register the scan must not
 visit -- the third bank, and a bank's registers from its row's width upwards -- holds a word whose candidate would win
-if it were read (in the even-padded form the pad slot holds the empty word instead, as the kernel writes it):
+if it were read:
 the accumulators == the direct formula over exactly the window's slots, the two-cell scan == the single scan per
 cell, no Hazard, no read outstanding at the end.
 
-The visit count: over seeded random 13-mer pairs the ring visits w(i-2) + w(i-1) slots per cell (the even-padded sum
-in the even form); the linear table's chunk-aligned count is printed beside it."""
+The visit count: over seeded random 13-mer pairs the ring visits w(i-2) + w(i-1) slots per cell; a linear table's
+chunk-aligned count is printed beside it."""
 import os
 import random
 import re
@@ -25,17 +25,11 @@ CSRC = ROOT / "open-msspe-design_amd" / "csrc"
 SINGLE_INC, PAIR_INC = CSRC / "row_bound_ring_pinned.inc", CSRC / "row_bound_ring_pair_pinned.inc"
 KC, W0, BANK, MAXW = 4, 76, 16, 13
 OFF = 1 << 28
-EMPTY = (1023 << 17) | 0x7fff      # an empty slot word: a K of its own, the field 0x7fff (u = 0)
 POISON_WINS = OFF + 200000           # above every candidate a visited slot can give (OFF + 40000 + 0x7fff)
 
 
 def macro(text, name):
     return int(re.search(rf"#define \w+_{name} (\d+)\n", text).group(1))
-
-
-GRAN = macro(SINGLE_INC.read_text(), "GRAN")      # 1: exact widths; 2: rows padded to an even width
-FORM = ("--even",) if GRAN == 2 else ()
-pad = lambda w: (w + GRAN - 1) // GRAN * GRAN
 
 
 def scan_lines(path, pfx):
@@ -65,10 +59,10 @@ def pair():
 
 def test_committed_ring_scans_are_the_generators_output():
     for path, args, pfx in ((SINGLE_INC, ("--ring",), "MSSPE_BRG13"), (PAIR_INC, ("--ring", "--pair"), "MSSPE_BRP13")):
-        text = generated(*args, *FORM)
+        text = generated(*args)
         assert text == path.read_text(), path.name
-        assert macro(text, "GRAN") == GRAN and macro(text, "W0") == W0 and macro(text, "BANK") == BANK
-        assert pfx in text and not any(p in text for p in {"MSSPE_BRG13", "MSSPE_BRP13", "MSSPE_BWN13", "MSSPE_BWP13", "MSSPE_BPK13"} - {pfx})
+        assert macro(text, "W0") == W0 and macro(text, "BANK") == BANK
+        assert pfx in text and not any(p in text for p in {"MSSPE_BRG13", "MSSPE_BRP13", "MSSPE_BPK13"} - {pfx})
         assert "START" not in text and "%[Y" not in text      # no entry chunk, no straddling kind
 
 
@@ -83,20 +77,15 @@ def make_case(rng, rot, wf, wn):
         for c in range(BANK):
             if c < w:
                 word = (2 * rng.randrange(0, 450) << 17) | rng.randrange(0, 0x8000)
-            elif c < pad(w):
-                word = EMPTY
             else:
                 word = ((2 * rng.randrange(0, 450) + 1) << 17) | rng.randrange(0, 0x8000)
             regs[f"v{W0 + BANK * b + c}"] = word
     cells = [(2 * rng.randrange(500, 2000) << 17) | 0x7fff for _ in range(2)]
     seed = rng.randrange(1 << 30)
-    empty_k = EMPTY >> 17
 
     def table(addr, area="TOFF"):
         assert area == "TOFF" and addr % 4 == 0, addr
         word = addr // 4
-        if any(word == (C >> 17) - empty_k & 0x7fff for C in cells):
-            return 0                                    # the empty word's geometry: not available
         if word & 1:
             return POISON_WINS
         x = random.Random(seed * 8191 + addr)
@@ -118,9 +107,8 @@ def formula(regs, C, table, rot, wf, wn):
 
 def controls(text, rot, wf, wn):
     nsz = macro(text, "NSZ")
-    wfp, wnp = pad(wf), pad(wn)
-    idx = (rot * nsz + min(wfp, KC) // GRAN) * nsz + min(wnp, KC) // GRAN
-    return {"%[IDX]": idx, "%[WF]": wfp, "%[WN]": wnp, "%[WMAX]": max(wfp, wnp)}
+    idx = (rot * nsz + min(wf, KC)) * nsz + min(wn, KC)
+    return {"%[IDX]": idx, "%[WF]": wf, "%[WN]": wn, "%[WMAX]": max(wf, wn)}
 
 
 SINGLE_TEXT, PAIR_TEXT = SINGLE_INC.read_text(), PAIR_INC.read_text()
@@ -174,8 +162,8 @@ def test_a_visit_outside_the_window_would_be_seen(single):
     """The check has teeth: widen the near row by one register and the scan returns the candidate that must not win."""
     rng = random.Random(7200)
     for rot in range(3):
-        regs, cells, table = make_case(rng, rot, 3, 2 * GRAN)
-        ctl = controls(SINGLE_TEXT, rot, 3, 2 * GRAN + GRAN)
+        regs, cells, table = make_case(rng, rot, 3, 2)
+        ctl = controls(SINGLE_TEXT, rot, 3, 3)
         v = dict(regs)
         v["%[C]"] = cells[0]
         out = single.run(v, ctl, table)
@@ -248,11 +236,9 @@ def test_visits_per_cell():
             assert lin >= wf + wn
             cells += w
             exact += w * (wf + wn)
-            ring += w * (pad(wf) + pad(wn))
+            ring += w * (wf + wn)
             linear += w * lin
     print(f"{cells / (20000 - skipped):.1f} cells per pair; slots visited per cell: linear table {linear / cells:.2f}, "
-          f"ring (this form, granularity {GRAN}) {ring / cells:.2f}, rows i-2 and i-1 alone {exact / cells:.2f}")
-    assert ring == (exact if GRAN == 1 else ring) and exact <= ring <= linear
+          f"ring {ring / cells:.2f}, rows i-2 and i-1 alone {exact / cells:.2f}")
+    assert ring == exact and exact <= ring <= linear
     assert 5.5 < exact / cells < 5.9 and 7.9 < linear / cells < 8.5
-    if GRAN == 2:
-        assert 6.4 < ring / cells < 6.8

@@ -23,28 +23,10 @@ another chunk behind it -- nearly every chunk of a scan -- runs in a straight li
 the kinds dispatched by taken branches at every chunk the same kernel ran 9 % slower.
 usage: tools/gen_row_bound_packed_asm.py > open-msspe-design_amd/csrc/row_bound_packed_pinned.inc
 
---window F: the WINDOWED instance's scan (k_pairs_bound_window; row_bound_window_pinned.inc, macros MSSPE_BWN13_*).  The
-same chunks, kinds and waits, but the scan of a cell in row i ENTERS the unrolled sequence at the chunk %[START] that
-holds the first slot of row i - F (a scalar: a wave holds one composition) instead of at chunk 0: a tree of scalar
-compares leads to that chunk's issue, which joins the straight line.  Everything above the window is the kernel's one
-far candidate (thal_pairs_row.hip run_pair_packed); F itself only reaches the kernel, as MSSPE_BWN13_F.
-usage: tools/gen_row_bound_packed_asm.py --window 2 > open-msspe-design_amd/csrc/row_bound_window_pinned.inc
-
---window F --pair: the windowed scan of TWO cells of one row in one pass (row_bound_window_pair_pinned.inc, macros
-MSSPE_BWP13_*).  Two cells of a row never depend on each other (a predecessor lies strictly above and left of its cell),
-and %[START], %[NRUN], %[NFAR], %[NEAR] are the row's, so the NRUN > START test, the entry tree and every chunk's
-has-next and kind tests run once for both.  Operands %[CA] %[YA] %[CB] %[YB]; cell A accumulates into v74 / v75, cell B
-into %[bf] / %[bn] (the compiler's).  The two register sets that hold two chunks of one cell above hold the SAME chunk
-of the two cells here, and the units alternate A(pc), B(pc), A(pc+1), B(pc+1), ...: a chunk with another behind it is
-    wait for A(pc) (counted: B(pc)'s reads stay in flight), reduce A(pc), issue A(pc+1),
-    wait for B(pc) (counted: A(pc+1)'s stay in flight),      reduce B(pc), issue B(pc+1)
-and the last chunk waits for zero before B.  The straddling chunk's per-slot mask is formed per cell.
-usage: tools/gen_row_bound_packed_asm.py --window 2 --pair > open-msspe-design_amd/csrc/row_bound_window_pair_pinned.inc
-(the two windowed outputs are kept for the tests that read them; the kernel runs the ring scans below)
-
 --ring: the scan k_pairs_bound_window runs (row_bound_ring_pinned.inc, macros MSSPE_BRG13_*).  With a window of two rows
 only rows i-2 and i-1 are ever read again, so the windowed instance keeps its rows in a RING of three banks of 16
-registers instead of the linear table:
+registers instead of the linear table (everything above the window is the kernel's one far candidate: thal_pairs_row.hip
+run_pair_window):
 
     v76 .. v91, v92 .. v107, v108 .. v123   bank 0, 1, 2: row i lives in bank i % 3, its c-th cell in v(76 + 16 (i % 3) + c)
     v74, v75                                 the far and the near accumulator, as above
@@ -73,25 +55,14 @@ one behind it is in flight (counted wait), and the unit two places on is issued 
 path runs a chunk for both cells at once: one dispatch, B's reads in flight while A is reduced (cell A's wide path
 followed by cell B's measured 1.7 ms per step slower: DESIGN 4.0).  A row of odd width ends on the single-cell scan.
 usage: tools/gen_row_bound_packed_asm.py --ring --pair > open-msspe-design_amd/csrc/row_bound_ring_pair_pinned.inc
-
---ring [--pair] --even: the measured alternative (MSSPE_BR?13_GRAN 2; 5 ms per step slower, not committed): every row
-padded to an even width, chunks and tails of 2 and 4 slots only (3 x 3 sizes, 27 leaves), 6.60 visits per cell instead
-of 5.71.  The kernel then writes the empty word into the pad slot of a row of odd width whenever it publishes the row,
-so that the scan never reads a stale word there.
 """
 import sys
 
-RING = len(sys.argv) >= 2 and sys.argv[1] == "--ring"
-if RING:
-    RING_PAIR, RING_EVEN = "--pair" in sys.argv[2:], "--even" in sys.argv[2:]
-    if len(sys.argv) != 2 + RING_PAIR + RING_EVEN:
-        sys.exit(__doc__)
-    sys.argv = sys.argv[:1]
-PAIR = len(sys.argv) == 4 and sys.argv[3] == "--pair"
-WINDOW = int(sys.argv[2]) if len(sys.argv) == 3 + PAIR and sys.argv[1] == "--window" else 0
-if (len(sys.argv) != 1 and not WINDOW) or WINDOW not in (0, 2, 3) or (PAIR and WINDOW != 2):
+FORMS = {(): (False, False), ("--ring",): (True, False), ("--ring", "--pair"): (True, True)}
+if tuple(sys.argv[1:]) not in FORMS:
     sys.exit(__doc__)
-PFX = "MSSPE_BWP13" if PAIR else "MSSPE_BWN13" if WINDOW else "MSSPE_BPK13"
+RING, RING_PAIR = FORMS[tuple(sys.argv[1:])]
+PFX = "MSSPE_BPK13"
 KC = 4   # slots per chunk (6 and 8 measured slower: DESIGN 4.0)
 NS, W0, ACCF, ACCN = 52, 76, 74, 75
 TUPLES = [(76, 32), (108, 16), (124, 4)]
@@ -161,27 +132,9 @@ def scan_asm():
 
     a(f"v_mov_b32 v{ACCF}, 0")
     a(f"v_mov_b32 v{ACCN}, 0")
-    if WINDOW:
-        # the entry: chunk %[START] .. %[NRUN] - 1 run (none: START >= NRUN); a leaf issues its chunk and joins the line
-        def enter(lo, hi):
-            if lo == hi:
-                chunk_issue(lo)
-                a(f"s_branch Lc{lo}_%=")
-                return
-            mid = (lo + hi + 1) // 2
-            a(f"s_cmp_lt_i32 %[START], {mid}")
-            a(f"s_cbranch_scc0 Le{mid}_{hi}_%=")
-            enter(lo, mid - 1)
-            a(f"Le{mid}_{hi}_%=:")
-            enter(mid, hi)
-
-        a("s_cmp_gt_i32 %[NRUN], %[START]")
-        a("s_cbranch_scc0 Ldone%=")
-        enter(0, nch - 1)
-    else:
-        a("s_cmp_gt_i32 %[NRUN], 0")
-        a("s_cbranch_scc0 Ldone%=")
-        chunk_issue(0)
+    a("s_cmp_gt_i32 %[NRUN], 0")
+    a("s_cbranch_scc0 Ldone%=")
+    chunk_issue(0)
     # ---- the straight line: a far chunk with another chunk behind it.  The next chunk's reads are issued first, the
     #      wait is for this chunk's alone, and no branch is taken
     for pc in range(nch - 1):
@@ -210,115 +163,10 @@ def scan_asm():
     return L
 
 
-def pair_scan_asm():
-    L = []
-    a = lambda s: L.append(s)
-    # operands: %[CA] %[YA] %[CB] %[YB] v; %[NFAR] %[NRUN] %[NEAR] %[START] s; outputs v74, v75 (cell A, fixed),
-    # %[bf] %[bn] v (cell B); temps: cell A's chunk in %[a0..] / %[v0..], cell B's in %[t0..] / %[v4..]; %[yt] v
-    nch = len(SIZES)
-    CELLS = {"A": ("%[CA]", "%[YA]", [f"%[a{e}]" for e in range(KC)], [f"%[v{e}]" for e in range(KC)], f"v{ACCF}", f"v{ACCN}"),
-             "B": ("%[CB]", "%[YB]", [f"%[t{e}]" for e in range(KC)], [f"%[v{KC + e}]" for e in range(KC)], "%[bf]", "%[bn]")}
-
-    def issue(cell, pc):
-        C, _, t, v, _, _ = CELLS[cell]
-        n = SIZES[pc]
-        for e in range(n):
-            a(f"v_sub_u32 {t[e]}, {C}, v{W0 + START[pc] + e}")
-        for e in range(n):
-            a(f"v_lshrrev_b32 {v[e]}, 15, {t[e]}")
-        for e in range(n):
-            a(f"ds_read_b32 {v[e]}, {v[e]} offset:%c[TOFF]")
-
-    def process(cell, pc, kind):
-        _, Y, t, v, far, near = CELLS[cell]
-        n = SIZES[pc]
-        for e in range(n):
-            a(f"v_mad_u32_u16 {t[e]}, {t[e]}, 1, {v[e]}")
-        if kind == "straddle":
-            for e in range(n):
-                a(f"s_cmp_gt_i32 %[NEAR], {START[pc] + e}")
-                a("s_cselect_b64 vcc, -1, 0")
-                a(f"v_cndmask_b32_e32 %[yt], 0, {Y}, vcc")
-                a(f"v_sub_u32 {t[e]}, {t[e]}, %[yt]")
-        acc = far if kind == "far" else near
-        for e in range(0, n - 1, 2):
-            a(f"v_max3_i32 {acc}, {acc}, {t[e]}, {t[e + 1]}")
-        if n & 1:
-            a(f"v_max_i32 {acc}, {acc}, {t[n - 1]}")
-
-    def body(pc, kind, nxt):
-        # in flight on entry: A(pc), B(pc), in that order
-        a(f"s_waitcnt lgkmcnt({SIZES[pc]})")
-        process("A", pc, kind)
-        if nxt:
-            issue("A", pc + 1)
-        a(f"s_waitcnt lgkmcnt({SIZES[pc + 1] if nxt else 0})")
-        process("B", pc, kind)
-        if nxt:
-            issue("B", pc + 1)
-
-    def dispatch(pc, tag, nxt, then):
-        a(f"s_cmp_gt_i32 %[NFAR], {pc}")
-        a(f"s_cbranch_scc0 L{tag}s{pc}_%=")
-        body(pc, "far", nxt)
-        a(f"s_branch {then}")
-        a(f"L{tag}s{pc}_%=:")
-        near_only(pc, tag, nxt, then)
-
-    def near_only(pc, tag, nxt, then):
-        a(f"s_cmp_gt_i32 %[NEAR], {START[pc]}")
-        a(f"s_cbranch_scc0 L{tag}n{pc}_%=")
-        body(pc, "straddle", nxt)
-        a(f"s_branch {then}")
-        a(f"L{tag}n{pc}_%=:")
-        body(pc, "near", nxt)
-        a(f"s_branch {then}")
-
-    def enter(lo, hi):
-        if lo == hi:
-            issue("A", lo)
-            issue("B", lo)
-            a(f"s_branch Lc{lo}_%=")
-            return
-        mid = (lo + hi + 1) // 2
-        a(f"s_cmp_lt_i32 %[START], {mid}")
-        a(f"s_cbranch_scc0 Le{mid}_{hi}_%=")
-        enter(lo, mid - 1)
-        a(f"Le{mid}_{hi}_%=:")
-        enter(mid, hi)
-
-    for acc in (f"v{ACCF}", f"v{ACCN}", "%[bf]", "%[bn]"):
-        a(f"v_mov_b32 {acc}, 0")
-    a("s_cmp_gt_i32 %[NRUN], %[START]")
-    a("s_cbranch_scc0 Ldone%=")
-    enter(0, nch - 1)
-    # ---- the straight line: a far chunk with another chunk behind it, both cells, no branch taken
-    for pc in range(nch - 1):
-        a(f"Lc{pc}_%=:")
-        a(f"s_cmp_gt_i32 %[NRUN], {pc + 1}")
-        a(f"s_cbranch_scc0 Lx{pc}_%=")
-        a(f"s_cmp_gt_i32 %[NFAR], {pc}")
-        a(f"s_cbranch_scc0 Ly{pc}_%=")
-        body(pc, "far", True)
-    a(f"Lc{nch - 1}_%=:")
-    a(f"Lx{nch - 1}_%=:")
-    dispatch(nch - 1, "x", False, "Ldone%=")
-    # ---- off the line: a straddling or near chunk with another behind it ...
-    for pc in range(nch - 1):
-        a(f"Ly{pc}_%=:")
-        near_only(pc, "y", True, f"Lc{pc + 1}_%=")
-    # ---- ... and the last chunk that runs, of whatever kind
-    for pc in range(nch - 1):
-        a(f"Lx{pc}_%=:")
-        dispatch(pc, "x", False, "Ldone%=")
-    a("Ldone%=:")
-    return L
-
-
 RING_BANKS, RING_BANK_REGS, RING_MAXW = 3, 16, 13
 
 
-def ring_scan(pair, even):
+def ring_scan(pair):
     """(items of the scan, macro definitions).  An item is an instruction or label (str) or a macro call (name, args);
     the .inc keeps the units and the leaves as preprocessor macros, so that the file stays small enough to read."""
     PFX = "MSSPE_BRP13" if pair else "MSSPE_BRG13"
@@ -326,9 +174,8 @@ def ring_scan(pair, even):
     a = lambda s: items.append(s)
     # operands: %[C] (pair: %[CA] %[CB]) v; %[IDX] %[WF] %[WN] %[WMAX] s; outputs v74, v75 (pair: cell A's; cell B's are
     # %[bf] %[bn]); temps, two units in flight: set a = %[ta0..3] / %[va0..3], set b = %[tb0..3] / %[vb0..3]
-    sizes = [0, 2, 4] if even else [0, 1, 2, 3, 4]     # what a row leaves for a chunk: nothing, a tail, a full chunk
+    sizes = [0, 1, 2, 3, 4]     # what a row leaves for a chunk: nothing, a tail, a full chunk
     nsz = len(sizes)
-    maxw = RING_MAXW + (RING_MAXW & 1 if even else 0)
     CELLS = [("CA", {"far": f"v{ACCF}", "near": f"v{ACCN}"}), ("CB", {"far": "%[bf]", "near": "%[bn]"})] if pair \
         else [("C", {"far": f"v{ACCF}", "near": f"v{ACCN}"})]
     bank = lambda rot, role: W0 + RING_BANK_REGS * ((rot + (1 if role == "far" else 2)) % RING_BANKS)
@@ -420,8 +267,8 @@ def ring_scan(pair, even):
         # a row wider than one chunk (one row in five): its further chunks one at a time, each with a body per tail size.
         # The two-cell scan runs a chunk for both cells at once: one dispatch, B's reads in flight while A is reduced
         a(f"Lwide{rot}_%=:")
-        for base in range(KC, maxw, KC):
-            cands = [s for s in sizes if s and base + s <= maxw]
+        for base in range(KC, RING_MAXW, KC):
+            cands = [s for s in sizes if s and base + s <= RING_MAXW]
             for role, W in (("far", "%[WF]"), ("near", "%[WN]")):
                 skip = new_label("s")
                 a(f"s_cmp_gt_i32 {W}, {base}")
@@ -441,7 +288,7 @@ def ring_scan(pair, even):
 
                 by_size(W, base, cands, body)
                 a(f"{skip}:")
-            if base + KC < maxw:
+            if base + KC < RING_MAXW:
                 a(f"s_cmp_gt_i32 %[WMAX], {base + KC}")
                 a("s_cbranch_scc0 Ldone%=")
         a("s_branch Ldone%=")
@@ -498,13 +345,13 @@ def ring_render(PFX, items, defs):
 
 
 if RING:
-    PFX, items, defs, nsz = ring_scan(RING_PAIR, RING_EVEN)
-    print(f"// GENERATED by tools/gen_row_bound_packed_asm.py --ring{' --pair' if RING_PAIR else ''}{' --even' if RING_EVEN else ''}"
+    PFX, items, defs, nsz = ring_scan(RING_PAIR)
+    print(f"// GENERATED by tools/gen_row_bound_packed_asm.py --ring{' --pair' if RING_PAIR else ''}"
           " -- do not edit (see that file for the why and the register map)")
     print(f"#define {PFX}_KC {KC}")
     print(f"#define {PFX}_W0 {W0}")
     print(f"#define {PFX}_BANK {RING_BANK_REGS}")
-    print(f"#define {PFX}_GRAN {2 if RING_EVEN else 1}")
+    print(f"#define {PFX}_GRAN 1")   # read by nothing in this tree: 84f3bf2's tests/test_pair_bound_ring_model.py reads it on import
     print(f"#define {PFX}_NSZ {nsz}")
     print(ring_render(PFX, items, defs))
     print(f'#define {PFX}_SCAN_CLOBBERS "scc", "memory"')
@@ -524,22 +371,16 @@ if RING:
           ", ".join('"+{v[%d:%d]}"(%s)' % (r0, r0 + ln - 1, nm) for (r0, ln), nm in zip(banks, names)))
     sys.exit(0)
 
-print(f"// GENERATED by tools/gen_row_bound_packed_asm.py{f' --window {WINDOW}' if WINDOW else ''}{' --pair' if PAIR else ''} -- do not edit (see that file for the why and the register map)")
-if WINDOW:
-    print(f"#define {PFX}_F {WINDOW}")
+print("// GENERATED by tools/gen_row_bound_packed_asm.py -- do not edit (see that file for the why and the register map)")
 print(f"#define {PFX}_KC {KC}")
 print(f"#define {PFX}_W0 {W0}")
 print(f"#define {PFX}_SCAN_ASM \\")
-print(" \\\n".join('    "' + l + '\\n\\t"' for l in (pair_scan_asm() if PAIR else scan_asm())))
+print(" \\\n".join('    "' + l + '\\n\\t"' for l in scan_asm()))
 print(f'#define {PFX}_SCAN_CLOBBERS "vcc", "scc", "memory"')
 temps = [f"a{e}" for e in range(KC)] + [f"t{e}" for e in range(KC)] + [f"v{e}" for e in range(2 * KC)] + ["yt"]
 print(f"#define {PFX}_TEMP_NAMES " + ", ".join(temps))
 print(f"#define {PFX}_TEMPS_OUT " + ", ".join(f'[{t}] "=&v"({t})' for t in temps))
-if PAIR:
-    print(f'#define {PFX}_ACC_OUT(far_a, near_a, far_b, near_b) "=&{{v{ACCF}}}"(far_a), "=&{{v{ACCN}}}"(near_a), '
-          '[bf] "=&v"(far_b), [bn] "=&v"(near_b)')
-else:
-    print(f'#define {PFX}_ACC_OUT(far, near) "=&{{v{ACCF}}}"(far), "=&{{v{ACCN}}}"(near)')
+print(f'#define {PFX}_ACC_OUT(far, near) "=&{{v{ACCF}}}"(far), "=&{{v{ACCN}}}"(near)')
 names = ["Wa", "Wb", "Wc"]
 print(f"#define {PFX}_TUPLES_IN(" + ", ".join(names) + ") " +
       ", ".join('"{v[%d:%d]}"(%s)' % (r0, r0 + ln - 1, nm) for (r0, ln), nm in zip(TUPLES, names)))
