@@ -1220,6 +1220,58 @@ int msspe_stream_reach(msspe_ctx *ctx, const char *const *records, const size_t 
                        float tm_threshold, int flank, const msspe_reach_opt *reach_opt, uint64_t *sites_out,
                        uint64_t *stable_out, msspe_reach_record *records_out, uint64_t *record_start_out);
 
+/* ---- a panel thinned on target reach: the primers the reach needs (engine extension) --------------------------
+ * msspe_stream_reach* says which columns a panel reaches; these calls say which of its primers are needed to reach
+ * them, by a greedy set cover over COLUMNS.  The stream, records, start[], total_len, k, msspe_mismatch_opt, words / n,
+ * chemistry, mode, tm_threshold, flank, msspe_reach_opt and the stable sites are those of msspe_stream_reach*;
+ * msspe_thin_opt, forced, keep_out, order_out, gain_out and *n_picked_out follow msspe_panel_thin*.
+ *   R_p: the columns primer p reaches on either strand -- the union, over the stable sites of p alone, of
+ *        [p_pos, min(p_pos + D, e_r) - 1] for a plus site at p_pos and [max(q + k - D, s_r), q + k - 1] for a minus site
+ *        at q, r the site's record.  Reach never leaves the site's record.  A word listed twice has two equal sets.
+ *   forced (host, optional, n bytes; NULL: none): C starts as the union of the forced primers' sets; a forced primer is
+ *        never picked and never in the order.
+ *   Rounds: the round picks the unforced, unpicked p with the greatest |R_p \ C|, ties to the LOWEST index.  If that
+ *        gain is below thin->min_gain the loop ends; otherwise p is appended to the order with its gain and C |= R_p.
+ *   keep_out[n]: 1 when forced or picked.  order_out / gain_out (the caller sizes both to n) and *n_picked_out: the
+ *        picks in order, each with its gain at the time of the pick.
+ *   reach_out[n] (optional): |R_p|, each primer's own reach, whatever is forced.
+ *   *reached_all_out, *reached_kept_out (optional): |union of R_p| over all primers and over the kept primers.
+ *   sites_out, stable_out (uint64, HOST, 2 n): as msspe_stream_reach*, for the WHOLE panel.
+ *   records_out (optional, NULL skips it; HOST, n_records entries, one for NULL record_start): one msspe_reach_record
+ *        per record for the KEPT panel.  It equals msspe_stream_reach* called on the kept words alone -- stability is
+ *        a property of (primer, template) -- and is built from the kept primers' sites of this call's scored pass:
+ *        no second pass runs.
+ *   msspe_panel_thin_reach_packed_dev: on a resident stream, on the context's stream; record_start as there.
+ *   msspe_panel_thin_reach: host pointers throughout; record_start_out (optional, n_records): start[].
+ * GUARANTEE: at min_gain 1, reached_kept == reached_all, and records_out[r].reached_either equals that of
+ * msspe_stream_reach* on the whole panel for every r -- thinning loses no reached column.  NOT preserved:
+ * reached_plus, reached_minus and reached_both, the per-strand gaps, and the site counts.
+ * Memory depends on the number of stable sites, as msspe_background_amplicons* does: the scored pass collects one key
+ * per stable site in that call's buffer ("amplicon_keys_cap_log2" and its doubling), and the cover keeps about 60 bytes
+ * per key (the sorted intervals) beside the planes of msspe_stream_reach* and 4 bytes per 64 columns.  2^31 stable
+ * sites or more: MSSPE_ERR_NOMEM.  msspe_get_info, of the last call: "thin_reach_sites" (stable keys),
+ * "thin_reach_intervals" (the disjoint intervals they leave), "thin_reach_rounds" (the picks and the round that
+ * stopped), "thin_reach_prepare_us", "thin_reach_gain0_us", "thin_reach_rounds_us", "thin_reach_report_us" (device
+ * time behind the scored pass: intervals; |R_p|, forced and first gains; rounds; counts and records).
+ * Errors: those of msspe_stream_reach* (a NULL records_out is none here); MSSPE_ERR_ARG for a NULL thin, min_gain < 1,
+ * or a NULL keep_out, order_out, gain_out or n_picked_out.  n == 0 or total_len < k: MSSPE_OK, nothing picked,
+ * keep_out = the forced flags, both counts 0, and records_out as there: every gap is the whole record. */
+int msspe_panel_thin_reach_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, size_t total_len, int k,
+                                      const msspe_mismatch_opt *mm, const uint64_t *words, int n,
+                                      const msspe_chem *chem, int mode, float tm_threshold, int flank,
+                                      const msspe_reach_opt *reach_opt, const msspe_thin_opt *thin,
+                                      const uint8_t *forced, const uint64_t *record_start, int n_records,
+                                      uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out, int *n_picked_out,
+                                      uint32_t *reach_out, long long *reached_all_out, long long *reached_kept_out,
+                                      uint64_t *sites_out, uint64_t *stable_out, msspe_reach_record *records_out);
+int msspe_panel_thin_reach(msspe_ctx *ctx, const char *const *records, const size_t *record_bytes, int n_records,
+                           int k, const msspe_mismatch_opt *mm, const uint64_t *words, int n, const msspe_chem *chem,
+                           int mode, float tm_threshold, int flank, const msspe_reach_opt *reach_opt,
+                           const msspe_thin_opt *thin, const uint8_t *forced, uint8_t *keep_out, uint32_t *order_out,
+                           uint32_t *gain_out, int *n_picked_out, uint32_t *reach_out, long long *reached_all_out,
+                           long long *reached_kept_out, uint64_t *sites_out, uint64_t *stable_out,
+                           msspe_reach_record *records_out, uint64_t *record_start_out);
+
 /* ---- segment coverage scored with thal (engine extension, no reference counterpart) ---------------------------
  * msspe_segment_coverage_mm* says which segments hold a match by a string rule; these calls say which of those
  * matches would hold the primer at a temperature -- msspe_background_thal*'s question, asked of the target alignment.

@@ -9,7 +9,7 @@ FLAGS=(--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-ma
        -Wall -Wno-unused-function)
 mkdir -p "$here/build"
 objs=()
-for src in nn_params.cpp capi.cpp kernels_generic.hip thal_hairpin_wave.hip thal_pairs.hip thal_pairs_int.hip thal_pairs_row.hip thal_pairs_bound_list.hip thal_pairs_split.hip thal_pairs_wave.hip pool_sort.hip kmer_stage.hip group.hip conflict_cover.hip conflict_graph.hip tube_split.hip coverage_mm.hip coverage_thal.hip panel_thin.hip panel_thin_thal.hip panel_select.hip background.hip background_thal.hip background_amplicons.hip stream_reach.hip; do
+for src in nn_params.cpp capi.cpp kernels_generic.hip thal_hairpin_wave.hip thal_pairs.hip thal_pairs_int.hip thal_pairs_row.hip thal_pairs_bound_list.hip thal_pairs_split.hip thal_pairs_wave.hip pool_sort.hip kmer_stage.hip group.hip conflict_cover.hip conflict_graph.hip tube_split.hip coverage_mm.hip coverage_thal.hip panel_thin.hip panel_thin_thal.hip panel_select.hip background.hip background_thal.hip background_amplicons.hip stream_reach.hip panel_thin_reach.hip; do
   obj="$here/build/${src%.*}.o"
   if [[ ! -f "$obj" || "$src" -nt "$obj" || -n "$(find . \( -name '*.hpp' -o -name '*.inc' \) -newer "$obj" -print -quit)" \
         || ../../include/msspe_hip.h -nt "$obj" ]]; then

@@ -29,6 +29,7 @@
 #include "background_thal.hpp"
 #include "background_amplicons.hpp"
 #include "stream_reach.hpp"
+#include "panel_thin_reach.hpp"
 #include "coverage_mm.hpp"
 #include "coverage_thal.hpp"
 #include "kernels.hpp"
@@ -237,6 +238,8 @@ struct msspe_ctx {
         long long grows = 0;               // of the last call
         long long us[6] = {};              // tiles, scan, masks, gap tiles, scan, gaps
     } reach_work;
+    PanelThinReach thin_reach;         // msspe_panel_thin_reach*: the intervals, ranks, gains and round state (the keys are
+                                       // amp_work's, the planes and record starts reach_work's)
     // optional profiling of the dominant kernel (k_pairs_fast) with HIP events on ctx->stream
     bool prof_on = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events;
@@ -922,6 +925,13 @@ int msspe_get_info(msspe_ctx *ctx, const char *key, long long *value_out)
     else if (k == "reach_masks_us") *value_out = ctx->reach_work.us[2];
     else if (k == "reach_gap_tiles_us") *value_out = ctx->reach_work.us[3];
     else if (k == "reach_gaps_us") *value_out = ctx->reach_work.us[5];
+    else if (k == "thin_reach_sites") *value_out = ctx->thin_reach.sites();
+    else if (k == "thin_reach_intervals") *value_out = ctx->thin_reach.intervals();
+    else if (k == "thin_reach_rounds") *value_out = ctx->thin_reach.rounds();
+    else if (k == "thin_reach_prepare_us") *value_out = ctx->thin_reach.phase_us()[0];
+    else if (k == "thin_reach_gain0_us") *value_out = ctx->thin_reach.phase_us()[1];
+    else if (k == "thin_reach_rounds_us") *value_out = ctx->thin_reach.phase_us()[2];
+    else if (k == "thin_reach_report_us") *value_out = ctx->thin_reach.phase_us()[3];
     else if (k == "cover_rounds") *value_out = ctx->cover.rounds();
     else if (k == "cover_keys_us") *value_out = ctx->cover.phase_us()[0];
     else if (k == "cover_symmetrise_us") *value_out = ctx->cover.phase_us()[1];
@@ -1051,6 +1061,7 @@ void msspe_destroy(msspe_ctx *ctx)
         ctx->thin.release();
         ctx->thin_thal.release();
         ctx->select.release();
+        ctx->thin_reach.release();
         for (auto &e : ctx->select_ev) {
             if (e) (void)hipEventDestroy(e);
             e = nullptr;
@@ -5347,55 +5358,13 @@ static int ensure_reach_work(msspe_ctx *ctx, size_t total_len, int n_records)
     return MSSPE_OK;
 }
 
-int msspe_stream_reach_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, size_t total_len, int k,
-                                  const msspe_mismatch_opt *mm, const uint64_t *words, int n, const msspe_chem *chem,
-                                  int mode, float tm_threshold, int flank, const msspe_reach_opt *reach_opt,
-                                  const uint64_t *record_start, int n_records, uint64_t *sites_out,
-                                  uint64_t *stable_out, msspe_reach_record *records_out)
+// From the two site planes of ctx->reach_work (ensure_reach_work) to one msspe_reach_record per record: the six launches
+// behind the scored pass.  starts: HOST, nr entries.
+static int reach_report(msspe_ctx *ctx, size_t total_len, int k, uint32_t reach, const uint64_t *starts, int nr,
+                        msspe_reach_record *records_out)
 {
-    if (!ctx) return MSSPE_ERR_ARG;
-    if (!reach_opt || !records_out || (record_start && n_records <= 0))
-        return fail(ctx, MSSPE_ERR_ARG, "null argument");
-    if (k >= 2 && k <= 31 && reach_opt->reach < (uint32_t)k)   // another k: the scored pass's MSSPE_ERR_K
-        return fail(ctx, MSSPE_ERR_ARG, "stream_reach: reach is shorter than the primers");
-    if (reach_opt->reach >= (1u << 31)) return fail(ctx, MSSPE_ERR_ARG, "stream_reach: reach must be below 2^31");
-    if (record_start) {
-        if (record_start[0] != 0) return fail(ctx, MSSPE_ERR_ARG, "stream_reach: record_start[0] must be 0");
-        for (int r = 1; r < n_records; ++r)
-            if (record_start[r] <= record_start[r - 1])
-                return fail(ctx, MSSPE_ERR_ARG, "stream_reach: record_start is not ascending");
-        if (record_start[n_records - 1] > total_len)
-            return fail(ctx, MSSPE_ERR_ARG, "stream_reach: a record starts beyond the stream");
-    }
-    const uint64_t one_start = 0;
-    const uint64_t *starts = record_start ? record_start : &one_start;
-    const int nr = record_start ? n_records : 1;
-    auto end_of = [&](int r) { return r + 1 < nr ? starts[r + 1] - 1 : (uint64_t)total_len; };
     auto &w = ctx->reach_work;
-    for (long long &u : w.us) u = 0;
-    w.grows = 0;
-    const bool empty = n == 0 || total_len < (size_t)k;   // the scored pass returns before it touches the device
-    uint64_t *plus = nullptr, *minus = nullptr, *neither = nullptr;
-    if (!empty && total_len < ((size_t)1 << 32) && d_packed && mm && chem && sites_out && stable_out && n > 0 &&
-        words && k >= 2 && k <= 31) {   // anything else: the scored pass names the fault
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        if (int rc = ensure_reach_work(ctx, total_len, nr)) return rc;
-        plus = w.planes;
-        minus = plus + w.plane_words;
-        neither = minus + w.plane_words;
-        HIP_TRY(ctx, hipMemsetAsync(plus, 0, 2 * sizeof(uint64_t) * w.plane_words, ctx->stream));
-    }
-    int rc = background_thal_pass(ctx, d_packed, total_len, k, mm, words, n, chem, mode, tm_threshold, flank,
-                                  sites_out, stable_out, nullptr, 0, nullptr, false, plus, minus);
-    if (rc) return rc;
-    if (empty) {   // no site: nothing is reached and every gap is its whole record
-        for (int r = 0; r < nr; ++r) {
-            const uint32_t s = (uint32_t)starts[r], len = (uint32_t)(end_of(r) - starts[r]);
-            records_out[r] = msspe_reach_record{0, 0, 0, 0, 0, 0, len, s, len, s, len, s};
-        }
-        return MSSPE_OK;
-    }
-    if (!plus) return fail(ctx, MSSPE_ERR_ARG, "stream_reach: unsupported arguments");
+    uint64_t *plus = w.planes, *minus = plus + w.plane_words, *neither = minus + w.plane_words;
     const size_t nt = reach_tiles(total_len);
     uint32_t *tile_plus = w.tiles, *tile_minus = tile_plus + w.tiles_cap, *tile_zero = tile_minus + w.tiles_cap;
     // the call returns behind a synchronisation of the stream, so the caller's array outlives the copy
@@ -5406,7 +5375,7 @@ int msspe_stream_reach_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, size
     HIP_TRY(ctx, hipEventRecord(w.ev[1], ctx->stream));
     HIP_TRY(ctx, launch_reach_scan(tile_plus, tile_minus, nt, ctx->stream));
     HIP_TRY(ctx, hipEventRecord(w.ev[2], ctx->stream));
-    HIP_TRY(ctx, launch_reach_masks(plus, minus, total_len, k, reach_opt->reach, w.starts, nr, tile_plus, tile_minus,
+    HIP_TRY(ctx, launch_reach_masks(plus, minus, total_len, k, reach, w.starts, nr, tile_plus, tile_minus,
                                     w.acc, neither, ctx->stream));
     HIP_TRY(ctx, hipEventRecord(w.ev[3], ctx->stream));
     HIP_TRY(ctx, launch_reach_gap_tiles(neither, total_len, tile_zero, ctx->stream));
@@ -5436,6 +5405,57 @@ int msspe_stream_reach_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, size
     return MSSPE_OK;
 }
 
+int msspe_stream_reach_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, size_t total_len, int k,
+                                  const msspe_mismatch_opt *mm, const uint64_t *words, int n, const msspe_chem *chem,
+                                  int mode, float tm_threshold, int flank, const msspe_reach_opt *reach_opt,
+                                  const uint64_t *record_start, int n_records, uint64_t *sites_out,
+                                  uint64_t *stable_out, msspe_reach_record *records_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!reach_opt || !records_out || (record_start && n_records <= 0))
+        return fail(ctx, MSSPE_ERR_ARG, "null argument");
+    if (k >= 2 && k <= 31 && reach_opt->reach < (uint32_t)k)   // another k: the scored pass's MSSPE_ERR_K
+        return fail(ctx, MSSPE_ERR_ARG, "stream_reach: reach is shorter than the primers");
+    if (reach_opt->reach >= (1u << 31)) return fail(ctx, MSSPE_ERR_ARG, "stream_reach: reach must be below 2^31");
+    if (record_start) {
+        if (record_start[0] != 0) return fail(ctx, MSSPE_ERR_ARG, "stream_reach: record_start[0] must be 0");
+        for (int r = 1; r < n_records; ++r)
+            if (record_start[r] <= record_start[r - 1])
+                return fail(ctx, MSSPE_ERR_ARG, "stream_reach: record_start is not ascending");
+        if (record_start[n_records - 1] > total_len)
+            return fail(ctx, MSSPE_ERR_ARG, "stream_reach: a record starts beyond the stream");
+    }
+    const uint64_t one_start = 0;
+    const uint64_t *starts = record_start ? record_start : &one_start;
+    const int nr = record_start ? n_records : 1;
+    auto end_of = [&](int r) { return r + 1 < nr ? starts[r + 1] - 1 : (uint64_t)total_len; };
+    auto &w = ctx->reach_work;
+    for (long long &u : w.us) u = 0;
+    w.grows = 0;
+    const bool empty = n == 0 || total_len < (size_t)k;   // the scored pass returns before it touches the device
+    uint64_t *plus = nullptr, *minus = nullptr;
+    if (!empty && total_len < ((size_t)1 << 32) && d_packed && mm && chem && sites_out && stable_out && n > 0 &&
+        words && k >= 2 && k <= 31) {   // anything else: the scored pass names the fault
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        if (int rc = ensure_reach_work(ctx, total_len, nr)) return rc;
+        plus = w.planes;
+        minus = plus + w.plane_words;
+        HIP_TRY(ctx, hipMemsetAsync(plus, 0, 2 * sizeof(uint64_t) * w.plane_words, ctx->stream));
+    }
+    int rc = background_thal_pass(ctx, d_packed, total_len, k, mm, words, n, chem, mode, tm_threshold, flank,
+                                  sites_out, stable_out, nullptr, 0, nullptr, false, plus, minus);
+    if (rc) return rc;
+    if (empty) {   // no site: nothing is reached and every gap is its whole record
+        for (int r = 0; r < nr; ++r) {
+            const uint32_t s = (uint32_t)starts[r], len = (uint32_t)(end_of(r) - starts[r]);
+            records_out[r] = msspe_reach_record{0, 0, 0, 0, 0, 0, len, s, len, s, len, s};
+        }
+        return MSSPE_OK;
+    }
+    if (!plus) return fail(ctx, MSSPE_ERR_ARG, "stream_reach: unsupported arguments");
+    return reach_report(ctx, total_len, k, reach_opt->reach, starts, nr, records_out);
+}
+
 int msspe_stream_reach(msspe_ctx *ctx, const char *const *records, const size_t *record_bytes, int n_records, int k,
                        const msspe_mismatch_opt *mm, const uint64_t *words, int n, const msspe_chem *chem, int mode,
                        float tm_threshold, int flank, const msspe_reach_opt *reach_opt, uint64_t *sites_out,
@@ -5459,6 +5479,106 @@ int msspe_stream_reach(msspe_ctx *ctx, const char *const *records, const size_t 
         rc = msspe_stream_reach_packed_dev(ctx, (const uint64_t *)d, L, k, mm, words, n, chem, mode, tm_threshold,
                                            flank, reach_opt, nullptr, 0, sites_out, stable_out, &none);
     }
+    (void)msspe_device_free(ctx, d);
+    return rc;
+}
+
+// msspe_panel_thin_reach*: the scored pass in its keys mode, the cover over columns (panel_thin_reach.hip) on the
+// "neither" plane of reach_work, then the reach report from the kept primers' keys -- no second scored pass.
+int msspe_panel_thin_reach_packed_dev(msspe_ctx *ctx, const uint64_t *d_packed, size_t total_len, int k,
+                                      const msspe_mismatch_opt *mm, const uint64_t *words, int n,
+                                      const msspe_chem *chem, int mode, float tm_threshold, int flank,
+                                      const msspe_reach_opt *reach_opt, const msspe_thin_opt *thin,
+                                      const uint8_t *forced, const uint64_t *record_start, int n_records,
+                                      uint8_t *keep_out, uint32_t *order_out, uint32_t *gain_out, int *n_picked_out,
+                                      uint32_t *reach_out, long long *reached_all_out, long long *reached_kept_out,
+                                      uint64_t *sites_out, uint64_t *stable_out, msspe_reach_record *records_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!reach_opt || !thin || !keep_out || !order_out || !gain_out || !n_picked_out || n < 0 ||
+        (record_start && n_records <= 0))
+        return fail(ctx, MSSPE_ERR_ARG, "null argument");
+    if (thin->min_gain < 1) return fail(ctx, MSSPE_ERR_ARG, "panel_thin_reach: min_gain must be at least 1");
+    if (k >= 2 && k <= 31 && reach_opt->reach < (uint32_t)k)   // another k: the scored pass's MSSPE_ERR_K
+        return fail(ctx, MSSPE_ERR_ARG, "panel_thin_reach: reach is shorter than the primers");
+    if (reach_opt->reach >= (1u << 31)) return fail(ctx, MSSPE_ERR_ARG, "panel_thin_reach: reach must be below 2^31");
+    if (record_start) {
+        if (record_start[0] != 0) return fail(ctx, MSSPE_ERR_ARG, "panel_thin_reach: record_start[0] must be 0");
+        for (int r = 1; r < n_records; ++r)
+            if (record_start[r] <= record_start[r - 1])
+                return fail(ctx, MSSPE_ERR_ARG, "panel_thin_reach: record_start is not ascending");
+        if (record_start[n_records - 1] > total_len)
+            return fail(ctx, MSSPE_ERR_ARG, "panel_thin_reach: a record starts beyond the stream");
+    }
+    const uint64_t one_start = 0;
+    const uint64_t *starts = record_start ? record_start : &one_start;
+    const int nr = record_start ? n_records : 1;
+    auto end_of = [&](int r) { return r + 1 < nr ? starts[r + 1] - 1 : (uint64_t)total_len; };
+    *n_picked_out = 0;
+    if (reached_all_out) *reached_all_out = 0;
+    if (reached_kept_out) *reached_kept_out = 0;
+    ctx->thin_reach.reset();
+    auto &w = ctx->reach_work;
+    for (long long &u : w.us) u = 0;
+    w.grows = 0;
+    int rc = background_thal_pass(ctx, d_packed, total_len, k, mm, words, n, chem, mode, tm_threshold, flank,
+                                  sites_out, stable_out, nullptr, 0, nullptr, true);
+    if (rc) return rc;
+    for (int p = 0; p < n; ++p) keep_out[p] = forced && forced[p] ? 1 : 0;
+    if (reach_out) std::fill(reach_out, reach_out + n, 0u);
+    if (n == 0 || total_len < (size_t)k) {   // the scored pass returned before it touched the device
+        for (int r = 0; records_out && r < nr; ++r) {
+            const uint32_t s = (uint32_t)starts[r], len = (uint32_t)(end_of(r) - starts[r]);
+            records_out[r] = msspe_reach_record{0, 0, 0, 0, 0, 0, len, s, len, s, len, s};
+        }
+        return MSSPE_OK;
+    }
+    if (total_len >= ((size_t)1 << 32)) return fail(ctx, MSSPE_ERR_ARG, "panel_thin_reach: unsupported arguments");
+    const uint64_t m = (uint64_t)ctx->amp_work.n_keys;
+    if (m >= (1ull << 31)) return fail(ctx, MSSPE_ERR_NOMEM, "panel_thin_reach: 2^31 stable sites or more");
+    if ((rc = ensure_reach_work(ctx, total_len, nr))) return rc;
+    uint64_t *plus = w.planes, *minus = plus + w.plane_words, *neither = minus + w.plane_words;
+    HIP_TRY(ctx, hipMemcpyAsync(w.starts, starts, sizeof(uint64_t) * (size_t)nr, hipMemcpyHostToDevice, ctx->stream));
+    if (records_out) HIP_TRY(ctx, hipMemsetAsync(plus, 0, 2 * sizeof(uint64_t) * w.plane_words, ctx->stream));
+    std::string err;
+    if ((rc = ctx->thin_reach.run(ctx->amp_work.keys, (uint32_t)m, n, total_len, k, reach_opt->reach, w.starts, nr,
+                                  neither, records_out ? plus : nullptr, records_out ? minus : nullptr,
+                                  (uint32_t)thin->min_gain, keep_out, order_out, gain_out, n_picked_out, reach_out,
+                                  reached_all_out, reached_kept_out, ctx->stream, err)))
+        return fail(ctx, rc, err);
+    if (records_out && (rc = reach_report(ctx, total_len, k, reach_opt->reach, starts, nr, records_out))) return rc;
+    if ((rc = ctx->thin_reach.end_report(ctx->stream, err))) return fail(ctx, rc, err);
+    return MSSPE_OK;
+}
+
+int msspe_panel_thin_reach(msspe_ctx *ctx, const char *const *records, const size_t *record_bytes, int n_records,
+                           int k, const msspe_mismatch_opt *mm, const uint64_t *words, int n, const msspe_chem *chem,
+                           int mode, float tm_threshold, int flank, const msspe_reach_opt *reach_opt,
+                           const msspe_thin_opt *thin, const uint8_t *forced, uint8_t *keep_out, uint32_t *order_out,
+                           uint32_t *gain_out, int *n_picked_out, uint32_t *reach_out, long long *reached_all_out,
+                           long long *reached_kept_out, uint64_t *sites_out, uint64_t *stable_out,
+                           msspe_reach_record *records_out, uint64_t *record_start_out)
+{
+    if (!ctx) return MSSPE_ERR_ARG;
+    if (!mm || !sites_out || !stable_out || !chem || !reach_opt || !thin || !keep_out || !order_out || !gain_out ||
+        !n_picked_out || n < 0 || (n && !words))
+        return fail(ctx, MSSPE_ERR_ARG, "null argument");
+    void *d = nullptr;
+    size_t L = 0;
+    std::vector<uint64_t> starts((size_t)std::max(n_records, 0));
+    int rc = msspe_device_put_stream_packed(ctx, records, record_bytes, n_records, &d, &L, starts.data());
+    if (rc) return rc;
+    if (record_start_out) std::copy(starts.begin(), starts.end(), record_start_out);
+    if (n_records > 0)
+        rc = msspe_panel_thin_reach_packed_dev(ctx, (const uint64_t *)d, L, k, mm, words, n, chem, mode, tm_threshold,
+                                               flank, reach_opt, thin, forced, starts.data(), n_records, keep_out,
+                                               order_out, gain_out, n_picked_out, reach_out, reached_all_out,
+                                               reached_kept_out, sites_out, stable_out, records_out);
+    else   // no record: nothing to report on, but the arguments are still checked
+        rc = msspe_panel_thin_reach_packed_dev(ctx, (const uint64_t *)d, L, k, mm, words, n, chem, mode, tm_threshold,
+                                               flank, reach_opt, thin, forced, nullptr, 0, keep_out, order_out,
+                                               gain_out, n_picked_out, reach_out, reached_all_out, reached_kept_out,
+                                               sites_out, stable_out, nullptr);
     (void)msspe_device_free(ctx, d);
     return rc;
 }

@@ -114,6 +114,8 @@ const OptSpec kOpts[] = {
     {"--reach-tm", "REACH_TM", OptSpec::Str, OFF(reach_tm_text)},
     {"--reach-thal", "REACH_THAL", OptSpec::Str, OFF(reach_thal)},
     {"--reach-out", "REACH_OUT", OptSpec::Str, OFF(reach_out)},
+    {"--thin-reach", "THIN_REACH", OptSpec::Bool, OFF(thin_reach)},
+    {"--thin-reach-min-gain", "THIN_REACH_MIN_GAIN", OptSpec::Int, OFF(thin_reach_min_gain)},
 };
 #undef OFF
 
@@ -214,7 +216,11 @@ std::string Args::usage()
          "strand, and where its longest stretch lies that nothing primes into. Sites are matches within\n"
          "--reach-mismatches <M> (default 2), the last --reach-3p-exact <E> bases exact (default 3); with --reach-tm <C>\n"
          "only those thal (--reach-thal any | end1) scores stable at C. --reach-out <FILE> writes one CSV line per\n"
-         "genome. Needs --kmer-size 2..31; with --devices it runs on the first device.\n";
+         "genome. Needs --kmer-size 2..31; with --devices it runs on the first device.\n"
+         "--thin-reach true (with --reach <D>) thins the primers the CSV would get on that reach, after everything\n"
+         "else: --existing-primers stay, then the primer reaching the most columns nothing kept reaches yet is kept\n"
+         "until none reaches --thin-reach-min-gain <N> (default 1) new columns. No reached column is lost at N = 1.\n"
+         "The report and --reach-out then describe the kept primers.\n";
     return u;
 }
 
@@ -509,6 +515,12 @@ Args Args::parse(int argc, const char *const *argv)
                          "' is larger than '--kmer-size " + std::to_string(a.kmer_size) + "'");
     if (a.background_mismatches < 0) a.background_mismatches = std::min(2, a.kmer_size);
     if (a.background_3p_exact < 0) a.background_3p_exact = std::min(3, a.kmer_size);
+    if (a.thin_reach_min_gain < 1)
+        throw UsageError("error: invalid value '" + std::to_string(a.thin_reach_min_gain) +
+                         "' for '--thin-reach-min-gain <...>'\n  [1 ..]");
+    if (a.reach_text.empty() && a.thin_reach == "true") throw UsageError("error: '--thin-reach' needs '--reach <D>'");
+    if (a.thin_reach != "true" && a.thin_reach_min_gain != 1)
+        throw UsageError("error: '--thin-reach-min-gain' needs '--thin-reach true'");
     if (a.reach_text.empty()) {
         for (const auto &given : {std::make_pair("--reach-mismatches", a.reach_mismatches),
                                   std::make_pair("--reach-3p-exact", a.reach_3p_exact)})
@@ -2644,8 +2656,13 @@ std::string background_report_amplicons(const std::vector<std::string> &names,
 std::vector<msspe_reach_record> target_reach(Engine &eng, const std::vector<SequenceRecord> &records,
                                              const std::vector<std::string> &words, int k, int max_mismatches,
                                              int exact_3p, const msspe_chem &chem, int mode, float tm_threshold,
-                                             uint32_t reach, std::vector<std::string> &genomes_out)
+                                             uint32_t reach, std::vector<std::string> &genomes_out,
+                                             ReachThinning *thin)
 {
+    if (thin) {
+        thin->keep = thin->forced;
+        thin->reached_all = thin->reached_kept = 0;
+    }
     for (const auto &w : words)
         if ((int)w.size() != k)
             throw std::runtime_error("--reach needs primers of one length, --kmer-size " + std::to_string(k) +
@@ -2670,9 +2687,36 @@ std::vector<msspe_reach_record> target_reach(Engine &eng, const std::vector<Sequ
     if (rc) eng.fail(rc);
     const msspe_mismatch_opt mm{std::min(max_mismatches, k), std::min(exact_3p, k)};
     const msspe_reach_opt opt{reach};
-    rc = stream.reach(k, mm, packed, n, chem, mode, tm_threshold, opt, counts, stable, out);
+    if (thin) {
+        std::vector<uint32_t> order((size_t)std::max(n, 1)), gains((size_t)std::max(n, 1));
+        int n_picked = 0;
+        thin->forced.resize((size_t)std::max(n, 1), 0);
+        thin->keep.assign((size_t)std::max(n, 1), 0);
+        rc = stream.thin_reach(k, mm, packed, n, chem, mode, tm_threshold, opt, thin->min_gain, thin->forced,
+                               thin->keep, order, gains, n_picked, thin->reached_all, thin->reached_kept, counts,
+                               stable, out);
+        thin->forced.resize((size_t)n);
+        thin->keep.resize((size_t)n);
+    } else {
+        rc = stream.reach(k, mm, packed, n, chem, mode, tm_threshold, opt, counts, stable, out);
+    }
     if (rc) eng.fail(rc);
     return out;
+}
+
+int DeviceBackground::thin_reach(int k, const msspe_mismatch_opt &mm, const std::vector<uint64_t> &packed, int n,
+                                 const msspe_chem &chem, int mode, float tm_threshold, const msspe_reach_opt &opt,
+                                 int min_gain, const std::vector<uint8_t> &forced, std::vector<uint8_t> &keep,
+                                 std::vector<uint32_t> &order, std::vector<uint32_t> &gains, int &n_picked,
+                                 long long &reached_all, long long &reached_kept, std::vector<uint64_t> &counts,
+                                 std::vector<uint64_t> &stable, std::vector<msspe_reach_record> &out) const
+{
+    const msspe_thin_opt thin{min_gain};
+    return msspe_panel_thin_reach_packed_dev(eng_.ctx(), static_cast<const uint64_t *>(dev_), len_, k, &mm,
+                                             packed.data(), n, &chem, mode, tm_threshold, 0, &opt, &thin,
+                                             forced.data(), starts_.data(), (int)starts_.size(), keep.data(),
+                                             order.data(), gains.data(), &n_picked, nullptr, &reached_all,
+                                             &reached_kept, counts.data(), stable.data(), out.data());
 }
 
 int DeviceBackground::reach(int k, const msspe_mismatch_opt &mm, const std::vector<uint64_t> &packed, int n,
@@ -2694,6 +2738,22 @@ static std::string reach_rule(int max_mismatches, int exact_3p, bool scored, int
         std::snprintf(thr, sizeof thr, "%.2f", (double)tm_threshold);
         out += std::string("; stable: thal ") + (mode == 2 ? "END1" : "ANY") + " t >= " + thr + " C";
     }
+    return out;
+}
+
+std::string reach_thinning_report(const ReachThinning &thin, uint32_t reach, int max_mismatches, int exact_3p,
+                                  bool scored, int mode, float tm_threshold)
+{
+    size_t kept = 0, forced = 0;
+    for (const uint8_t f : thin.keep) kept += f != 0;
+    for (const uint8_t f : thin.forced) forced += f != 0;
+    std::string out = "\nReach thinning (extension " + std::to_string(reach) + " bases, min gain " +
+                      std::to_string(thin.min_gain) + "; sites: " +
+                      reach_rule(max_mismatches, exact_3p, scored, mode, tm_threshold) + "):\n";
+    out += "  Kept " + std::to_string(kept) + " of " + std::to_string(thin.keep.size()) + " primers (" +
+           std::to_string(forced) + " forced)\n";
+    out += "  Columns reached by all: " + std::to_string(thin.reached_all) + ", by kept: " +
+           std::to_string(thin.reached_kept) + "\n";
     return out;
 }
 
@@ -3254,9 +3314,28 @@ int run(const Args &args, std::string &stdout_text)
         for (const auto &p : good_r) words.push_back(p.word);
         for (const auto &r : records) names.push_back(r.name);
         const int reach_mode = args.reach_thal == "end1" ? 2 : 1;
+        ReachThinning thinning;   // --thin-reach: the --existing-primers panel behind the CSV's primers, forced
+        const bool thin_reach = args.thin_reach == "true";
+        if (thin_reach) {
+            thinning.min_gain = args.thin_reach_min_gain;
+            thinning.forced.assign(words.size(), 0);
+            for (const auto *panel_list : {&panel_f, &panel_r})
+                for (const auto &w : *panel_list) words.push_back(w), thinning.forced.push_back(1);
+        }
         const auto recs = target_reach(eng, records, words, args.kmer_size, args.reach_mismatches, args.reach_3p_exact,
                                        ntthal_chem(opts), reach_mode, args.reach_scored ? args.reach_tm : 0.0f,
-                                       (uint32_t)args.reach, genomes);
+                                       (uint32_t)args.reach, genomes, thin_reach ? &thinning : nullptr);
+        if (thin_reach) {   // the dropped primers leave the lists the CSV is written from, as --thin-panel's do
+            std::vector<KmerStat> kept_f, kept_r;
+            for (size_t i = 0; i < good_f.size(); ++i)
+                if (thinning.keep[i]) kept_f.push_back(good_f[i]);
+            for (size_t i = 0; i < good_r.size(); ++i)
+                if (thinning.keep[good_f.size() + i]) kept_r.push_back(good_r[i]);
+            good_f.swap(kept_f);
+            good_r.swap(kept_r);
+            stdout_text += reach_thinning_report(thinning, (uint32_t)args.reach, args.reach_mismatches,
+                                                 args.reach_3p_exact, args.reach_scored, reach_mode, args.reach_tm);
+        }
         stdout_text += target_reach_report(names, genomes, recs, (uint32_t)args.reach, args.reach_mismatches,
                                            args.reach_3p_exact, args.reach_scored, reach_mode, args.reach_tm);
         if (!args.reach_out.empty()) {

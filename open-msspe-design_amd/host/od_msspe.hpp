@@ -177,6 +177,12 @@ struct Args {
     int reach_mismatches = -1, reach_3p_exact = -1;
     float reach_tm = 0.0f;
     bool reach_scored = false;
+    // --thin-reach true (with --reach D): after everything else, the primers the CSV would get are thinned to those
+    // the reach needs -- a greedy set cover over the columns each primer's sites reach, under --reach's site rule
+    // (msspe_panel_thin_reach); a pick must reach at least thin_reach_min_gain columns nothing kept reaches yet.  The
+    // --existing-primers panel is forced.  "Target reach" and --reach-out then describe the kept primers.
+    std::string thin_reach = "false";
+    int thin_reach_min_gain = 1;
     bool stddev_population = false;  // crate std-dev 0.1.0's divisor is unpinned
     static Args parse(int argc, const char *const *argv);   // throws UsageError
     static std::string usage();
@@ -563,6 +569,14 @@ public:
     int reach(int k, const msspe_mismatch_opt &mm, const std::vector<uint64_t> &packed, int n, const msspe_chem &chem,
               int mode, float tm_threshold, const msspe_reach_opt &opt, std::vector<uint64_t> &counts,
               std::vector<uint64_t> &stable, std::vector<msspe_reach_record> &out) const;
+    // msspe_panel_thin_reach_packed_dev likewise: forced / keep hold n flags, order / gains n entries; out describes
+    // the kept primers.  Returns the status.
+    int thin_reach(int k, const msspe_mismatch_opt &mm, const std::vector<uint64_t> &packed, int n,
+                   const msspe_chem &chem, int mode, float tm_threshold, const msspe_reach_opt &opt, int min_gain,
+                   const std::vector<uint8_t> &forced, std::vector<uint8_t> &keep, std::vector<uint32_t> &order,
+                   std::vector<uint32_t> &gains, int &n_picked, long long &reached_all, long long &reached_kept,
+                   std::vector<uint64_t> &counts, std::vector<uint64_t> &stable,
+                   std::vector<msspe_reach_record> &out) const;
 
 private:
     Engine &eng_;
@@ -589,12 +603,25 @@ std::string background_report_amplicons(const std::vector<std::string> &names,
                                         const std::vector<std::pair<uint64_t, uint64_t>> &counts,
                                         const std::vector<msspe_amplicon> &list, const DeviceBackground &background,
                                         uint32_t min_len, uint32_t max_len);
+// --thin-reach: what the thinning takes (min_gain, one forced flag per word) and gives (one keep flag per word, the
+// columns all words and the kept words reach)
+struct ReachThinning {
+    int min_gain = 1;
+    std::vector<uint8_t> forced, keep;
+    long long reached_all = 0, reached_kept = 0;
+};
 // --reach (engine extension): the input rows without their gap columns (genomes_out) as one resident stream, screened
-// with `words` (all of k bases) on both strands; one record per genome, positions in that stream
+// with `words` (all of k bases) on both strands; one record per genome, positions in that stream.  With thin the same
+// pass thins the words on reach, and the records describe the kept words.
 std::vector<msspe_reach_record> target_reach(Engine &eng, const std::vector<SequenceRecord> &records,
                                              const std::vector<std::string> &words, int k, int max_mismatches,
                                              int exact_3p, const msspe_chem &chem, int mode, float tm_threshold,
-                                             uint32_t reach, std::vector<std::string> &genomes_out);
+                                             uint32_t reach, std::vector<std::string> &genomes_out,
+                                             ReachThinning *thin = nullptr);
+// "Reach thinning (extension D bases, min gain G; sites: ...):", kept of n primers with the forced ones, and the columns
+// all primers and the kept primers reach
+std::string reach_thinning_report(const ReachThinning &thin, uint32_t reach, int max_mismatches, int exact_3p,
+                                  bool scored, int mode, float tm_threshold);
 // "Target reach (extension D bases; sites: ...):", the totals over all genomes, the number of genomes whose longest gap
 // (columns reached on neither strand) exceeds D, and the 20 genomes with the longest such gap as "name: offset, length"
 std::string target_reach_report(const std::vector<std::string> &names, const std::vector<std::string> &genomes,

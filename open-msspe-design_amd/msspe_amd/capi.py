@@ -58,6 +58,7 @@ EXPORTS = [
     "msspe_background_thal_flank_packed_dev", "msspe_background_thal_flank",
     "msspe_background_amplicons_flank_packed_dev", "msspe_background_amplicons_flank",
     "msspe_stream_reach_packed_dev", "msspe_stream_reach",
+    "msspe_panel_thin_reach_packed_dev", "msspe_panel_thin_reach",
     "msspe_round_fixed_f32", "msspe_g_cut",
     "msspe_group_create", "msspe_group_destroy", "msspe_group_last_error", "msspe_group_size",
     "msspe_group_transport", "msspe_group_transport_reason", "msspe_group_rccl_available", "msspe_group_member", "msspe_group_set_option", "msspe_group_rows",
@@ -435,6 +436,14 @@ def load_library() -> C.CDLL:
     L.msspe_stream_reach.argtypes = [
         vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(MismatchOpt), u64p, C.c_int,
         C.POINTER(Chem), C.c_int, C.c_float, C.c_int, C.POINTER(ReachOpt), vp, vp, vp, vp]
+    L.msspe_panel_thin_reach_packed_dev.argtypes = [
+        vp, vp, C.c_size_t, C.c_int, C.POINTER(MismatchOpt), u64p, C.c_int, C.POINTER(Chem), C.c_int, C.c_float,
+        C.c_int, C.POINTER(ReachOpt), C.POINTER(ThinOpt), vp, vp, C.c_int, vp, vp, vp, C.POINTER(C.c_int), vp,
+        C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), vp, vp, vp]
+    L.msspe_panel_thin_reach.argtypes = [
+        vp, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(MismatchOpt), u64p, C.c_int,
+        C.POINTER(Chem), C.c_int, C.c_float, C.c_int, C.POINTER(ReachOpt), C.POINTER(ThinOpt), vp, vp, vp, vp,
+        C.POINTER(C.c_int), vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), vp, vp, vp, vp]
     L.msspe_device_get.argtypes = [vp, vp, C.c_size_t, vp]
     L.msspe_host_table_routes.argtypes = [C.c_char_p, C.POINTER(Chem), C.POINTER(C.c_int32)]
     L.msspe_host_screen_plan.argtypes = [C.c_int] * 5 + [C.c_int64, vp, C.c_int, C.POINTER(C.c_int)]
@@ -1826,6 +1835,69 @@ class Engine:
             tm_threshold, flank, C.byref(opt), counts.ctypes.data, stable.ctypes.data, recs.ctypes.data,
             starts.ctypes.data))
         return counts, stable, recs[:n], starts
+
+    # ---- a panel thinned on target reach (engine extension; msspe_panel_thin_reach*) -----------------------------
+    @staticmethod
+    def _thin_reach_out(n: int, forced):
+        if forced is None:
+            f = None
+        else:
+            f = np.ascontiguousarray(np.asarray(forced) != 0, dtype=np.uint8)
+            if f.size != n:
+                raise ValueError("forced needs one flag per primer")
+        return (f, np.zeros(max(n, 1), dtype=np.uint8), np.zeros(max(n, 1), dtype=np.uint32),
+                np.zeros(max(n, 1), dtype=np.uint32), np.zeros(max(n, 1), dtype=np.uint32), C.c_int(0),
+                C.c_longlong(0), C.c_longlong(0))
+
+    def panel_thin_reach_packed(self, d_packed: int, total_len: int, primers, max_mismatches: int, exact_3p: int,
+                                chem: Chem, tm_threshold: float, mode, reach: int, min_gain: int = 1, forced=None,
+                                record_start=None, k: int | None = None, flank: int = 0, want_records: bool = True):
+        """The primers a resident stream's reach needs (msspe_panel_thin_reach_packed_dev): a greedy set cover over
+        the columns each primer's stable sites reach, forced primers first, ties to the lowest index, until the best
+        gain falls below min_gain.  Arguments as stream_reach_packed.  Returns a dict: keep (uint8[n]), order, gains
+        (the picks), primer_reach (uint32[n], |R_p|), reached_all, reached_kept, counts, stable (whole panel) and
+        records (the kept panel's REACH_RECORD_DTYPE array; None with want_records False)."""
+        w, k = _words_k(primers, k)
+        n = len(w)
+        counts = np.zeros((n, 2), dtype=np.uint64)
+        stable = np.zeros((n, 2), dtype=np.uint64)
+        mm, opt, thin = MismatchOpt(max_mismatches, exact_3p), ReachOpt(reach), ThinOpt(min_gain)
+        starts = None if record_start is None else np.ascontiguousarray(record_start, dtype=np.uint64)
+        nr = 1 if starts is None else len(starts)
+        recs = np.zeros(max(nr, 1), dtype=REACH_RECORD_DTYPE) if want_records else None
+        f, keep, order, gains, own, picked, r_all, r_kept = self._thin_reach_out(n, forced)
+        self._check(self.L.msspe_panel_thin_reach_packed_dev(
+            self.ptr, C.c_void_p(d_packed), total_len, k, C.byref(mm), w.ctypes.data, n, C.byref(chem),
+            self._thal_mode(mode), tm_threshold, flank, C.byref(opt), C.byref(thin),
+            None if f is None else f.ctypes.data, None if starts is None else starts.ctypes.data,
+            0 if starts is None else len(starts), keep.ctypes.data, order.ctypes.data, gains.ctypes.data,
+            C.byref(picked), own.ctypes.data, C.byref(r_all), C.byref(r_kept), counts.ctypes.data, stable.ctypes.data,
+            None if recs is None else recs.ctypes.data))
+        return {"keep": keep[:n], "order": order[:picked.value], "gains": gains[:picked.value],
+                "primer_reach": own[:n], "reached_all": int(r_all.value), "reached_kept": int(r_kept.value),
+                "counts": counts, "stable": stable, "records": None if recs is None else recs[:nr]}
+
+    def panel_thin_reach(self, records, primers, max_mismatches: int, exact_3p: int, chem: Chem, tm_threshold: float,
+                         mode, reach: int, min_gain: int = 1, forced=None, k: int | None = None, flank: int = 0,
+                         want_records: bool = True):
+        """Host form (msspe_panel_thin_reach): the dict of panel_thin_reach_packed, and starts."""
+        _recs, ptrs, lens, nr = self._records(records)
+        w, k = _words_k(primers, k)
+        n = len(w)
+        counts = np.zeros((n, 2), dtype=np.uint64)
+        stable = np.zeros((n, 2), dtype=np.uint64)
+        starts = np.zeros(nr, dtype=np.uint64)
+        mm, opt, thin = MismatchOpt(max_mismatches, exact_3p), ReachOpt(reach), ThinOpt(min_gain)
+        recs = np.zeros(max(nr, 1), dtype=REACH_RECORD_DTYPE) if want_records else None
+        f, keep, order, gains, own, picked, r_all, r_kept = self._thin_reach_out(n, forced)
+        self._check(self.L.msspe_panel_thin_reach(
+            self.ptr, ptrs, lens, nr, k, C.byref(mm), w.ctypes.data, n, C.byref(chem), self._thal_mode(mode),
+            tm_threshold, flank, C.byref(opt), C.byref(thin), None if f is None else f.ctypes.data, keep.ctypes.data,
+            order.ctypes.data, gains.ctypes.data, C.byref(picked), own.ctypes.data, C.byref(r_all), C.byref(r_kept),
+            counts.ctypes.data, stable.ctypes.data, None if recs is None else recs.ctypes.data, starts.ctypes.data))
+        return {"keep": keep[:n], "order": order[:picked.value], "gains": gains[:picked.value],
+                "primer_reach": own[:n], "reached_all": int(r_all.value), "reached_kept": int(r_kept.value),
+                "counts": counts, "stable": stable, "records": None if recs is None else recs[:nr], "starts": starts}
 
     def thal_detail(self, a, b, chem: Chem | None = None, mode="any") -> np.ndarray:
         """Full thal record of the pairs (a[i], b[i]) (msspe_thal_detail_pairs): two equal-length lists of strings of
