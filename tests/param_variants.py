@@ -222,6 +222,49 @@ EXPECTED_ROUTES = {
 }
 
 
+# Rectangles and flanked site passes (tests/test_gpu_param_variants.py g to i, the stack_x3 cases of the reach tests):
+# a row oligo against a column oligo or template of another length goes by the longer of the two, kmax.
+COMPUTED = ("wc_missing", "dangle_holes", "loops_and_bonuses", "stack_x1.5", "stack_x3", "h_mod10")
+RECT_ANY_ALWAYS = ((13, 20), (20, 13), (2, 17))
+RECT_ANY_EXTRA = {
+    "stack_x1.5": ((16, 21), (16, 22)),                                   # split_max_k and one above
+    "stack_x3": ((8, 10), (8, 11), (20, 28), (20, 29), (29, 13)),         # either bound and one above; long rows
+    "wc_missing": ((8, 32),),                                             # dense only, the widest table
+    "h_mod10": ((8, 32),),
+}
+# where the longer oligo of an extra shape must sit: (bound, bases above it)
+RECT_ANY_ON_BOUND = {
+    ("stack_x1.5", 16, 21): ("split_max_k", 0), ("stack_x1.5", 16, 22): ("split_max_k", 1),
+    ("stack_x3", 8, 10): ("split_max_k", 0), ("stack_x3", 8, 11): ("split_max_k", 1),
+    ("stack_x3", 20, 28): ("wave_max_k", 0), ("stack_x3", 20, 29): ("wave_max_k", 1), ("stack_x3", 29, 13): ("wave_max_k", 1),
+}
+RECT_ANY_CASES = [(v, a, b) for v in COMPUTED for a, b in RECT_ANY_ALWAYS + RECT_ANY_EXTRA.get(v, ())]
+RECT_END_SHAPES = ((13, 20), (20, 13), (20, 28), (20, 29))
+FLANK_VARIANTS = ("wc_missing", "dangle_holes", "stack_x1.5", "stack_x3", "h_mod10")
+FLANK_GRID = ((13, 2), (17, 1), (24, 4))                                  # (k, flank): templates of k .. k + 2 flank bases
+
+
+def rect_stage(routes: dict, kmax: int, end: bool = False) -> str:
+    """The first stage a rectangle takes at the default options (csrc/capi.cpp: cross_dimer_impl, and with end
+    cross_dimer_end_impl and score_site_pairs, which have no split-table kernel): "split" up to split_max_k, else
+    "wave" (one wave per pair) up to wave_max_k, else "dense"."""
+    if not end and kmax <= routes["split_max_k"]:
+        return "split"
+    return "wave" if kmax <= routes["wave_max_k"] else "dense"
+
+
+# {variant: ({kmax: stage} of the ANY rectangles, the same without the split kernel: END rectangles and templates)}
+EXPECTED_RECT_STAGE = {
+    "wc_missing": ({17: "dense", 20: "dense", 32: "dense"}, {20: "dense", 28: "dense", 29: "dense"}),
+    "dangle_holes": ({17: "split", 20: "split"}, {20: "wave", 28: "wave", 29: "wave"}),
+    "loops_and_bonuses": ({17: "split", 20: "split"}, {20: "wave", 28: "wave", 29: "wave"}),
+    "stack_x1.5": ({17: "split", 20: "split", 21: "split", 22: "wave"}, {20: "wave", 28: "wave", 29: "wave"}),
+    "stack_x3": ({10: "split", 11: "wave", 17: "wave", 20: "wave", 28: "wave", 29: "dense"},
+                 {20: "wave", 28: "wave", 29: "dense"}),
+    "h_mod10": ({17: "dense", 20: "dense", 32: "dense"}, {20: "dense", 28: "dense", 29: "dense"}),
+}
+
+
 def variant_sections(name):
     return VARIANTS[name](stock_sections())
 

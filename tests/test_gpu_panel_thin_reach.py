@@ -1,7 +1,7 @@
 """msspe_panel_thin_reach* on the device against the model (tests/panel_thin_reach_model.py: one boolean array per
 primer): keep, order, gains, n_picked, every primer's own reach, both counts and every field of every record, exactly;
 the records also against msspe_stream_reach on the kept words, the site counts against it on the whole panel.  Planted
-near-copies in both modes and chemistries, interval and record geometry, the greedy rule, the sizes at which a carry or
+near-copies in both modes and chemistries and with a template flank, interval and record geometry, the greedy rule, the sizes at which a carry or
 a buffer takes another step, one context across calls, the edge calls and the CLI."""
 import subprocess
 from pathlib import Path
@@ -44,10 +44,10 @@ def assert_thin_equal(got, want, what=""):
     tsr.assert_records_equal(got["records"], want["records"], what)
 
 
-def check(eng, records, primers, M, E, chem, mode, thr, D, want, min_gain=1, forced=None, cross=True):
+def check(eng, records, primers, M, E, chem, mode, thr, D, want, min_gain=1, forced=None, cross=True, flank=0):
     """One host call against the model, and against stream_reach: the kept words' records, the whole panel's counts."""
-    what = f"{mode} thr {thr} D {D} min_gain {min_gain}"
-    got = eng.panel_thin_reach(records, primers, M, E, chem, thr, mode, D, min_gain=min_gain, forced=forced)
+    what = f"{mode} thr {thr} D {D} min_gain {min_gain}" + (f" flank {flank}" if flank else "")
+    got = eng.panel_thin_reach(records, primers, M, E, chem, thr, mode, D, min_gain=min_gain, forced=forced, flank=flank)
     print(f"{what}: kept {int(got['keep'].sum())} of {len(primers)}, {len(got['order'])} picks, reached "
           f"{got['reached_kept']} of {got['reached_all']}, {eng.info('thin_reach_sites')} sites, "
           f"{eng.info('thin_reach_intervals')} intervals, {eng.info('thin_reach_rounds')} rounds")
@@ -60,9 +60,9 @@ def check(eng, records, primers, M, E, chem, mode, thr, D, want, min_gain=1, for
     if cross:
         k = len(primers[0])
         kept = [p for p, f in zip(primers, got["keep"]) if f]
-        _c, _s, recs, _st = eng.stream_reach(records, kept, M, E, chem, thr, mode, D, k=k)
+        _c, _s, recs, _st = eng.stream_reach(records, kept, M, E, chem, thr, mode, D, k=k, flank=flank)
         tsr.assert_records_equal(got["records"], recs, what + " (stream_reach on the kept words)")
-        c, s, whole, _st = eng.stream_reach(records, primers, M, E, chem, thr, mode, D)
+        c, s, whole, _st = eng.stream_reach(records, primers, M, E, chem, thr, mode, D, flank=flank)
         np.testing.assert_array_equal(got["counts"], c)
         np.testing.assert_array_equal(got["stable"], s)
         if min_gain == 1:   # the guarantee on its own
@@ -105,6 +105,48 @@ def test_planted_scored(m, eng, oracle, oracle_tables, k, n, mode, chem_name):
         want["counts"], want["stable"] = s[0], s[1]
         got = check(eng, records, primers, M, E, chem, mode, mid, D, want, cross=D in (k, 500))
     assert len(got["order"]) >= 1 and got["reached_all"] > 0
+
+
+# ---- planted near-copies, scored with a template flank --------------------------------------------------------------
+def check_flanked_thin(eng, chem, case, k, f, mode, D=500):
+    """panel_thin_reach at flank f against the model on the flanked sites (the input and the threshold of
+    test_gpu_stream_reach.flank_case) at min_gain 1 and 3 and once with a forced primer; the flank must show in every
+    primer's own reach."""
+    records, primers, M, E, thr, flips, blunt, flanked = case
+    n = len(primers)
+    assert flips >= 5 and 0 < flanked[1].sum() < flanked[0].sum()
+    forced = np.zeros(n, dtype=np.uint8)
+    forced[n - 1] = 1
+    for min_gain, forced_now in ((1, None), (3, None), (1, forced)):
+        want = trm.thin(None, records, primers, M, E, mode, thr, D, min_gain, forced_now, scored=flanked)
+        got = check(eng, records, primers, M, E, chem, mode, thr, D, want, min_gain, forced_now, flank=f)
+    assert len(got["order"]) >= 1 and got["reached_all"] > 0
+    at_flank_0 = trm.thin(None, records, primers, M, E, mode, thr, D, scored=blunt)
+    assert (want["primer_reach"] != at_flank_0["primer_reach"]).any()
+
+
+@pytest.mark.parametrize("mode", ["any", "end1"])
+@pytest.mark.parametrize("k,f", [(13, 2), (20, 4)])
+def test_planted_scored_with_a_flank(m, eng, oracle, oracle_tables, k, f, mode):
+    case = tsr.flank_case(oracle, oracle_tables, "stock", k, f, mode)
+    check_flanked_thin(eng, m.Chem.ntthal(), case, k, f, mode)
+
+
+def test_flanked_thin_on_both_sides_of_wave_max_k(m, oracle, tmp_path):
+    """The stack_x3 tables of tests/param_variants.py (one wave per pair up to 28 bases), k = 24 and flank 4: one
+    thinning call whose template classes are scored on different routes."""
+    import param_variants as pv
+    k, f, mode = 24, 4, "any"
+    path = pv.write_bundle(pv.variant_sections("stack_x3"), tmp_path / "stack_x3.bundle")
+    wave_max_k = m.capi.host_table_routes(path)["wave_max_k"]
+    case = tsr.flank_case(oracle, oracle.Tables(path), "stack_x3", k, f, mode, truncated=True)
+    lengths = tsr.template_lengths(case, k, f)
+    assert k < wave_max_k < k + 2 * f and (lengths <= wave_max_k).any() and (lengths > wave_max_k).any()
+    e = m.Engine(0, params_path=str(path))
+    try:
+        check_flanked_thin(e, m.Chem.ntthal(), case, k, f, mode)
+    finally:
+        e.close()
 
 
 @pytest.mark.parametrize("k,n", [(13, 24), (13, 40), (20, 24), (20, 40)])

@@ -11,7 +11,18 @@ at a time, and the oligo lengths sit on both sides of every bound:
     h_mod10             every flag 0: dense kernel alone
     h_frac              refused: every dimer call is MSSPE_ERR_TABLES
 
-tests/test_param_variants.py pins the flags and checks that each variant moves the oracle's numbers."""
+Rectangles -- a row oligo against a column oligo or template of another length -- go by the longer of the two:
+
+    g   cross_dimer_ab on every computed variant, the longer oligo on and one above split_max_k and wave_max_k, the
+        long oligo on the rows and on the columns, with the wave kernel off and with the dense kernel alone
+    h   cross_dimer_end_ab on the same variants
+    i   flanked site scoring (templates of k + fl + fr bases): every (fl, fr) class, both modes; on stack_x3 at
+        k = 24, flank 4 one call whose classes lie on both sides of wave_max_k; dangle_holes removes the very terms a
+        flank brings into play
+    (j: the flank through the reach entry points, tests/test_gpu_stream_reach.py and test_gpu_panel_thin_reach.py)
+
+tests/test_param_variants.py pins the flags, which of these lengths lie on which side of a bound, and checks that each
+variant moves the oracle's numbers."""
 import subprocess
 from pathlib import Path
 
@@ -26,6 +37,7 @@ pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
 BIN = ROOT / "open-msspe-design_amd" / "bin"
 COMPUTED = [v for v in pv.VARIANTS if v not in ("stock", "loops_only", "bonus_caps", "h_frac")]
+assert tuple(COMPUTED) == pv.COMPUTED
 
 
 @pytest.fixture(scope="module")
@@ -370,7 +382,220 @@ def test_cli_with_a_path(m, oracle, bonus_dir, tmp_path, monkeypatch):
     assert flag_csv != stock_csv and flag_csv.count("\n") > 3
 
 
-# ---- g. tables the engine refuses ----------------------------------------------------------------------------------------------
+# ---- g. rectangular ANY screens ------------------------------------------------------------------------------------------------
+
+ROUTE_OPTION_RESET = {"wave_kernel": 1, "force_generic": 0}
+
+
+def route_settings(routes):
+    """The default route, and where the tables leave a first stage to switch off: without the wave kernel, and the
+    dense kernel alone."""
+    return [{}] + ([{"wave_kernel": 0}, {"force_generic": 1}] if routes["wave_max_k"] > 0 else [])
+
+
+def any_decisions(oracle, dg, thr):
+    cf = np.zeros(dg.shape, dtype=np.uint8)
+    for i, j in zip(*np.nonzero(np.isfinite(dg))):
+        cf[i, j] = oracle.edge_decision(float(dg[i, j]), thr)
+    return cf
+
+
+def rect_any_reference(oracle, tables, k_a, k_b):
+    """The 48 x 64 block of test_gpu_mixed_length.pools under these tables, and a threshold from the oracle's own
+    values: the float32 of the 5th percentile of the finite dG (at the stock -9000 cal/mol most pairs of
+    a block conflict under stack_x3)."""
+    import test_gpu_mixed_length as tm
+    A, B = tm.pools(k_a, k_b, 48, 64)
+    dg, tt, _ = tm.oracle_block(oracle, tables, A, B, oracle.ntthal_args())
+    thr = float(np.float32(np.percentile(dg[np.isfinite(dg)], 5)))
+    return A, B, dg, tt, thr, any_decisions(oracle, dg, thr)
+
+
+@pytest.mark.parametrize("variant,k_a,k_b", pv.RECT_ANY_CASES)
+def test_rectangular_any_screen(m, oracle, variants, variant, k_a, k_b):
+    import test_gpu_mixed_length as tm
+    v = variants(variant)
+    kmax = max(k_a, k_b)
+    first = pv.rect_stage(v.routes, kmax)
+    assert first == pv.EXPECTED_RECT_STAGE[variant][0][kmax]
+    if (variant, k_a, k_b) in pv.RECT_ANY_ON_BOUND:   # the longer oligo on a bound of these tables, or one base above it
+        bound, above = pv.RECT_ANY_ON_BOUND[(variant, k_a, k_b)]
+        assert kmax == v.routes[bound] + above
+    elif (k_a, k_b) == (8, 32):
+        assert v.routes["split_max_k"] == v.routes["wave_max_k"] == 0       # the dense kernel alone
+    A, B, dg, tt, thr, cf = rect_any_reference(oracle, v.tables, k_a, k_b)
+    finite = int(np.isfinite(dg).sum())
+    print(f"{variant} ({k_a}, {k_b}): first stage {first}, threshold {thr}, {int(cf.sum())} conflicts among {finite} finite pairs")
+    assert 0 < cf.sum() < finite                    # (a 2-mer's duplexes included: 130 to 150 of some 3,000 lie below)
+    chem = m.Chem.ntthal()
+    try:
+        for opts in route_settings(v.routes):
+            for key, val in opts.items():
+                v.eng.set_option(key, val)
+            out = v.eng.cross_dimer_ab(A, B, chem, thr, want_dg=True, want_tm=True)
+            np.testing.assert_array_equal(out["dg"], dg, err_msg=str(opts))
+            np.testing.assert_array_equal(out["tm"], tt, err_msg=str(opts))
+            np.testing.assert_array_equal(tm.bits(out["bitmap"], len(B)), cf, err_msg=str(opts))
+            np.testing.assert_array_equal(out["row_conflicts"], cf.sum(1).astype(np.uint32), err_msg=str(opts))
+            fast = v.eng.cross_dimer_ab(A, B, chem, thr, want_dg=False)        # decisions only
+            np.testing.assert_array_equal(tm.bits(fast["bitmap"], len(B)), cf, err_msg=str(opts))
+            np.testing.assert_array_equal(fast["row_conflicts"], cf.sum(1).astype(np.uint32), err_msg=str(opts))
+            for key in opts:
+                v.eng.set_option(key, ROUTE_OPTION_RESET[key])
+    finally:
+        for key, val in ROUTE_OPTION_RESET.items():
+            v.eng.set_option(key, val)
+
+
+# ---- h. rectangular END1 screens -----------------------------------------------------------------------------------------------
+
+def rect_end_reference(oracle, tables, k_a, k_b):
+    """The pools of test_gpu_end_dimer.test_ab_shapes_match_the_oracle at 48 x 64, and a Tm threshold from the oracle's
+    own values: the "%.2f" float32 of the 90th percentile of max(t, 0)."""
+    import test_gpu_end_dimer as te
+    A, B = te.end_pool(k_a, 48, 8), te.end_pool(k_b, 64, 9)
+    for j in range(12):                       # B oligos pairing with A's 3' ends
+        tail = A[j][-min(k_a, k_b):]
+        B[j] = (te.rc(tail) + B[j])[:k_b]
+    dg, tt = te.oracle_ab(oracle, tables, A, B, oracle.ntthal_args())
+    tend = te.t_end(tt)
+    thrs = [float(np.float32(oracle.round_fixed_f32(float(np.percentile(tend, 90)), 2)))]
+    if thrs[0] <= 0.0:
+        # 13-mers at 25 C under tables near the shipped ones: fewer than a tenth of the pairs melt above 0 C, the
+        # percentile is 0 and every pair conflicts at it.  That threshold is run all the same; the one that splits the
+        # pairs is the same percentile among the pairs with a positive t
+        thrs.append(float(np.float32(oracle.round_fixed_f32(float(np.percentile(tend[tend > 0], 90)), 2))))
+    return A, B, dg, tt, thrs
+
+
+@pytest.mark.parametrize("k_a,k_b", pv.RECT_END_SHAPES)
+@pytest.mark.parametrize("variant", COMPUTED)
+def test_rectangular_end_screen(m, oracle, variants, variant, k_a, k_b):
+    import test_gpu_end_dimer as te
+    v = variants(variant)
+    first = pv.rect_stage(v.routes, max(k_a, k_b), end=True)
+    assert first == pv.EXPECTED_RECT_STAGE[variant][1][max(k_a, k_b)]
+    A, B, dg, tt, thrs = rect_end_reference(oracle, v.tables, k_a, k_b)
+    chem = m.Chem.ntthal()
+    try:
+        for opts in route_settings(v.routes)[:2]:
+            for key, val in opts.items():
+                v.eng.set_option(key, val)
+            for thr in thrs:
+                out = v.eng.cross_dimer_end_ab(A, B, chem, thr, want_dg=True, want_tm=True)
+                cf = te.check(oracle, out, dg, tt, thr)
+                fast = v.eng.cross_dimer_end_ab(A, B, chem, thr, want_dg=False, want_tm=False)
+                np.testing.assert_array_equal(te.bits(fast["bitmap"], len(B)), cf, err_msg=f"{opts} {thr}")
+                np.testing.assert_array_equal(fast["row_conflicts"], cf.sum(1).astype(np.uint32), err_msg=f"{opts} {thr}")
+                assert cf.all() if thr <= 0.0 else 0 < cf.sum() < cf.size
+            for key in opts:
+                v.eng.set_option(key, ROUTE_OPTION_RESET[key])
+    finally:
+        v.eng.set_option("wave_kernel", 1)
+    print(f"{variant} ({k_a}, {k_b}) END1: first stage {first}, thresholds {thrs}, {int(cf.sum())} conflicts of {cf.size}")
+    assert thrs[-1] > 0.0 and 0 < cf.sum() < cf.size
+
+
+# ---- i. flanked site scoring -----------------------------------------------------------------------------------------------------
+
+def flank_case(k, f):
+    """24 primers, three records of 3,000 bases with 8 planted near-copies of each (test_gpu_background_flank.base_case
+    in small), and the truncation block of test_every_truncation_class for this k and f: an N at every distance 0 .. f
+    on either side of exact copies of primer 0 on both strands, and a stream that starts and ends flush with a copy --
+    every (fl, fr) class occurs, so every template length k .. k + 2 f does."""
+    import test_gpu_background_flank as tf
+    from background_model import revcomp
+    rng = np.random.default_rng(7000 + 10 * k + f)
+    M, E = 3, 2
+    primers = [tf.random_seq(rng, k) for _ in range(24)]
+    records = tf.plant(rng, [tf.random_seq(rng, 3000) for _ in range(3)], primers, 8, M, E)
+    copy = [primers[0], revcomp(primers[0])]
+    gap = lambda d: d if d < f else f + 3       # base columns between the copy and the N: d, and "f or more"
+    body = []
+    for dl in range(f + 1):
+        for dr in range(f + 1):
+            for s in (0, 1):
+                body.append("N" + tf.random_seq(rng, gap(dl)) + copy[s] + tf.random_seq(rng, gap(dr)) + "N")
+                body.append(tf.random_seq(rng, 40))
+    records.insert(0, copy[0] + tf.random_seq(rng, 30) + copy[1])
+    records.append("".join(body))
+    records.append(copy[1] + tf.random_seq(rng, 30) + copy[0])
+    return records, primers, M, E
+
+
+def flanked_model(oracle, v, k, f, mode):
+    """The model's scored sites at 30 C and at the threshold that splits them (the "%.2f" float32 of the median t_site,
+    as test_background_thal builds it), once per variant, shape and mode."""
+    import background_flank_model as bfm
+    import test_gpu_background_thal as tb
+    cache = v.__dict__.setdefault("flanked", {})
+    if (k, f, mode) not in cache:
+        records, primers, M, E = flank_case(k, f)
+        want = bfm.scored_sites(v.tables, records, primers, M, E, mode, 30.0, oracle.ntthal_args(), f)
+        mid = float(np.float32(oracle.round_fixed_f32(float(np.median(np.maximum(want[2]["t"], 0.0))), 2)))
+        cache[(k, f, mode)] = (want, mid, tb.restable(want, len(primers), mid))
+    return cache[(k, f, mode)]
+
+
+@pytest.mark.parametrize("mode", ["any", "end1"])
+@pytest.mark.parametrize("k,f", pv.FLANK_GRID)
+@pytest.mark.parametrize("variant", pv.FLANK_VARIANTS)
+def test_flanked_sites(m, oracle, oracle_tables, variants, variant, k, f, mode):
+    import background_flank_model as bfm
+    import test_gpu_background_flank as tf
+    v = variants(variant)
+    records, primers, M, E = flank_case(k, f)
+    chem, args = m.Chem.ntthal(), oracle.ntthal_args()
+    want, mid, split = flanked_model(oracle, v, k, f, mode)
+    recs = want[2]
+    tf.check_against_model(v.eng, v.tables, records, primers, M, E, chem, args, mode, 30.0, f, want=want)
+    classes, truncated = tf.check_info(v.eng, records, primers, recs, f)
+    assert classes == (f + 1) ** 2 and 0 < truncated < len(recs)
+    tf.check_against_model(v.eng, v.tables, records, primers, M, E, chem, args, mode, mid, f, want=split)
+    assert tf.check_info(v.eng, records, primers, recs, f) == (classes, truncated)
+    n_stable = int(split[2]["stable"].sum())
+    print(f"{variant} k={k} f={f} {mode}: {len(recs)} sites, {classes} classes, {truncated} truncated, threshold {mid}: "
+          f"{n_stable} stable")
+    assert len(recs) >= 150 and 0 < n_stable < len(recs)      # 153 to 209 sites: planted copies overwrite one another
+    lengths = k + bfm.site_classes(records, primers, recs, f).sum(1)
+    assert set(lengths.tolist()) == set(range(k, k + 2 * f + 1))
+    wave_max_k = v.routes["wave_max_k"]
+    if variant == "stack_x3" and (k, f) == (24, 4):
+        # one call whose classes take different routes: one wave per pair up to wave_max_k bases, the dense kernel above
+        assert k < wave_max_k < k + 2 * f and (lengths <= wave_max_k).any() and (lengths > wave_max_k).any()
+        v.eng.set_option("wave_kernel", 0)
+        try:
+            tf.check_against_model(v.eng, v.tables, records, primers, M, E, chem, args, mode, mid, f, want=split)
+        finally:
+            v.eng.set_option("wave_kernel", 1)
+    if variant == "dangle_holes":
+        # a blunt k x k site has no overhang; the flank brings in the dangle terms this variant takes away
+        stock = bfm.scored_sites(oracle_tables, records, primers, M, E, mode, 30.0, args, f)[2]
+        moved = int((stock["dg"] != recs["dg"]).sum())
+        print(f"dangle_holes k={k} f={f} {mode}: dG differs from the stock tables' at {moved} of {len(recs)} sites")
+        assert moved >= len(recs) / 10
+
+
+def test_amplicons_of_flanked_sites_on_both_sides_of_wave_max_k(m, oracle, variants):
+    """stack_x3 at k = 24, flank 4: the amplicons of the stable flanked sites, as test_amplicons_of_the_flanked_sites."""
+    import background_amplicon_model as bam
+    import background_model as bm
+    v = variants("stack_x3")
+    k, f = 24, 4
+    records, primers, M, E = flank_case(k, f)
+    _want, mid, scored = flanked_model(oracle, v, k, f, "any")
+    w_amp, w_total, w_list = bam.amplicons_of(len(primers), k, scored[2], records, k, 2000)
+    counts, stable, amps, total, starts, lst = v.eng.background_amplicons(records, primers, M, E, m.Chem.ntthal(), mid, "any",
+                                                                         k, 2000, capacity=w_total + 8, flank=f)
+    np.testing.assert_array_equal(counts, scored[0])
+    np.testing.assert_array_equal(stable, scored[1])
+    np.testing.assert_array_equal(amps, w_amp)
+    assert total == w_total > 0
+    np.testing.assert_array_equal(lst, w_list)
+    np.testing.assert_array_equal(starts, bm.record_starts(records)[0])
+
+
+# ---- k. tables the engine refuses ----------------------------------------------------------------------------------------------
 
 def test_non_integral_enthalpies_are_refused_by_every_dimer_call(m, oracle, variants):
     """ntthal computes with stack.dh CG/GC = -10600.5; the engine's kernels carry enthalpies as integers and refuse:

@@ -1,13 +1,15 @@
 """msspe_stream_reach* on the device against the model (tests/stream_reach_model.py: one boolean array per record):
 every field of every record, exactly, and sites_out / stable_out equal to msspe_background_thal's.  Planted near-copies
-in both modes and chemistries at a threshold that splits the sites, every site stable, every reach from k to beyond the
-stream, record and tile geometry, the plumbing options, argument errors and the CLI's block."""
+in both modes and chemistries at a threshold that splits the sites, the same with a template flank at the threshold
+where the flank changes most stable flags (and on tables whose wave kernel ends inside the templates' lengths), every
+site stable, every reach from k to beyond the stream, record and tile geometry, the plumbing options, argument errors and the CLI's block."""
 import subprocess
 from pathlib import Path
 
 import numpy as np
 import pytest
 
+import background_flank_model as bfm
 import background_model as bm
 import background_thal_model as btm
 import stream_reach_model as srm
@@ -75,9 +77,9 @@ def assert_records_equal(got, want, what=""):
                               f"{got[bad[0]]} model {want[bad[0]]}")
 
 
-def check(eng, records, primers, M, E, chem, mode, thr, D, counts, stable, want, thal=None):
+def check(eng, records, primers, M, E, chem, mode, thr, D, counts, stable, want, thal=None, flank=0):
     """One host call against the model's records and the scored call's counts."""
-    g_counts, g_stable, recs, starts = eng.stream_reach(records, primers, M, E, chem, thr, mode, D)
+    g_counts, g_stable, recs, starts = eng.stream_reach(records, primers, M, E, chem, thr, mode, D, flank=flank)
     np.testing.assert_array_equal(g_counts, counts)
     np.testing.assert_array_equal(g_stable, stable)
     np.testing.assert_array_equal(starts, bm.record_starts(records)[0])
@@ -118,6 +120,128 @@ def test_planted_scored(m, eng, oracle, oracle_tables, k, mode, chem_name):
         check(eng, records, primers, M, E, chem, mode, mid, D, s[0], s[1], want, thal)
     print(f"k {k} {mode} {chem_name} thr {mid}: {int(s[0].sum())} sites, {int(s[1].sum())} stable")
     assert want["reached_either"].sum() > 0 and (want["sites_plus"] > 0).any() and (want["sites_minus"] > 0).any()
+
+
+# ---- planted near-copies, scored with a template flank --------------------------------------------------------------
+FLANK_GRID = [(13, 1), (13, 2), (20, 4), (24, 4)]
+_flank_cases = {}
+
+
+def flank_input(k, truncate=0):
+    """The input of test_planted_scored with 10 copies of each primer.  truncate = f: written over the first record
+    every 180 columns, exact copies whose flanks an N cuts short at every distance 0 .. f on either side, on both
+    strands and of one primer after the other, so that templates of every length k .. k + 2 f occur (planted copies
+    alone have whole flanks)."""
+    rng = np.random.default_rng(3100 + k)
+    M, E = 2, 2
+    primers = [random_seq(rng, k) for _ in range(24)]
+    records = plant(rng, [random_seq(rng, 9000), random_seq(rng, 4099), random_seq(rng, 700)], primers, 10, M, E)
+    records.insert(2, "")
+    if truncate:
+        first, q = list(records[0]), 0
+        for dl in range(truncate + 1):
+            for dr in range(truncate + 1):
+                for s in (0, 1):
+                    p = primers[q % len(primers)]
+                    piece = "N" + random_seq(rng, dl) + (bm.revcomp(p) if s else p) + random_seq(rng, dr) + "N"
+                    first[180 * q + 10:180 * q + 10 + len(piece)] = piece
+                    q += 1
+        assert 180 * q <= len(first)
+        records[0] = "".join(first)
+    return records, primers, M, E
+
+
+def flank_threshold(oracle, t_blunt, t_flanked):
+    """(threshold, flips): among the "%.2f" float32 values of the flanked t_site, the one at which most sites are
+    stable at one of flank 0 and flank f and not at the other (the lowest of equals); only thresholds that leave
+    stable and unstable sites at either flank are looked at.  (None, 0) without one."""
+    r0 = np.array([oracle.round_fixed_f32(float(t), 2) for t in np.maximum(t_blunt, 0.0)])
+    rf = np.array([oracle.round_fixed_f32(float(t), 2) for t in np.maximum(t_flanked, 0.0)])
+    best = (None, 0)
+    for thr in sorted({float(np.float32(x)) for x in rf}):
+        s0, sf = ~(r0 < thr), ~(rf < thr)
+        if 0 < s0.sum() < len(s0) and 0 < sf.sum() < len(sf) and (s0 != sf).sum() > best[1]:
+            best = (thr, int((s0 != sf).sum()))
+    return best
+
+
+def flank_case(oracle, tables, name, k, f, mode, truncated=False):
+    """The model's side of a flank case under these tables (name: their key in the cache), computed once: the input,
+    the threshold at which the flank matters most, the flips there, and the scored sites at flank 0 and f at it."""
+    key = (name, k, f, mode, truncated)
+    if key not in _flank_cases:
+        records, primers, M, E = flank_input(k, f if truncated else 0)
+        args = oracle.ntthal_args()
+        blunt = bfm.scored_sites(tables, records, primers, M, E, mode, 30.0, args, 0)
+        flanked = bfm.scored_sites(tables, records, primers, M, E, mode, 30.0, args, f)
+        for fld in ("primer", "pos", "strand"):
+            assert (blunt[2][fld] == flanked[2][fld]).all()               # the sites do not depend on the flank
+        thr, flips = flank_threshold(oracle, blunt[2]["t"], flanked[2]["t"])
+        assert thr is not None
+        n = len(primers)
+        _flank_cases[key] = (records, primers, M, E, thr, flips, restable(blunt, n, thr), restable(flanked, n, thr))
+        print(f"{name} k {k} flank {f} {mode}: threshold {thr}, the stable flag of {flips} of {len(blunt[2])} sites "
+              f"differs between flank 0 and flank {f}")
+    return _flank_cases[key]
+
+
+def check_flanked_reach(eng, chem, case, k, f, mode, Ds):
+    """stream_reach at flank f against the model on the flanked sites, its counts against background_thal at flank f,
+    and the flank must show: the model's records differ from those of flank 0 at some reach."""
+    records, primers, M, E, thr, flips, blunt, flanked = case
+    assert flips >= 5
+    assert 0 < flanked[1].sum() < flanked[0].sum() and 0 < blunt[1].sum() < blunt[0].sum()
+    thal = eng.background_thal(records, primers, M, E, chem, thr, mode, flank=f)
+    differs = 0
+    for D in Ds:
+        want = srm.reach_of_scored(k, flanked[2], records, D)
+        check(eng, records, primers, M, E, chem, mode, thr, D, flanked[0], flanked[1], want, thal, flank=f)
+        differs += int(want.tobytes() != srm.reach_of_scored(k, blunt[2], records, D).tobytes())
+    assert differs > 0
+
+
+@pytest.mark.parametrize("mode", ["any", "end1"])
+@pytest.mark.parametrize("k,f", FLANK_GRID)
+def test_planted_scored_with_a_flank(m, eng, oracle, oracle_tables, k, f, mode):
+    case = flank_case(oracle, oracle_tables, "stock", k, f, mode)
+    check_flanked_reach(eng, m.Chem.ntthal(), case, k, f, mode, reaches(k))
+
+
+def test_packed_with_a_flank(m, eng, oracle, oracle_tables):
+    k, f, mode = 13, 2, "any"
+    records, primers, M, E, thr, _flips, _blunt, flanked = flank_case(oracle, oracle_tables, "stock", k, f, mode)
+    d, total_len, d_starts = eng.put_stream_packed(records)
+    try:
+        for D in (k, 500):
+            c, s, recs = eng.stream_reach_packed(d, total_len, primers, M, E, m.Chem.ntthal(), thr, mode, D,
+                                                 record_start=d_starts, flank=f)
+            np.testing.assert_array_equal(c, flanked[0])
+            np.testing.assert_array_equal(s, flanked[1])
+            assert_records_equal(recs, srm.reach_of_scored(k, flanked[2], records, D), f"packed flank {f} D {D}")
+    finally:
+        eng.device_free(d)
+
+
+def template_lengths(case, k, f):
+    records, primers = case[0], case[1]
+    return k + bfm.site_classes(records, primers, case[7][2], f).sum(1)
+
+
+def test_flanked_reach_on_both_sides_of_wave_max_k(m, oracle, tmp_path):
+    """Tables whose one-wave-per-pair kernel ends at 28 bases (tests/param_variants.py stack_x3), k = 24 and flank 4:
+    templates of 24 .. 32 bases, so one reach call scores its classes on different routes."""
+    import param_variants as pv
+    k, f, mode = 24, 4, "any"
+    path = pv.write_bundle(pv.variant_sections("stack_x3"), tmp_path / "stack_x3.bundle")
+    wave_max_k = m.capi.host_table_routes(path)["wave_max_k"]
+    case = flank_case(oracle, oracle.Tables(path), "stack_x3", k, f, mode, truncated=True)
+    lengths = template_lengths(case, k, f)
+    assert k < wave_max_k < k + 2 * f and (lengths <= wave_max_k).any() and (lengths > wave_max_k).any()
+    e = m.Engine(0, params_path=str(path))
+    try:
+        check_flanked_reach(e, m.Chem.ntthal(), case, k, f, mode, (k, 500))
+    finally:
+        e.close()
 
 
 # ---- every site stable: no oracle -----------------------------------------------------------------------------------

@@ -40,6 +40,48 @@ def test_routes_of_the_shipped_bundle_and_of_a_directory(m, tmp_path):
     assert e.value.code == 3
 
 
+# Which stages the templates of a flanked site pass take, by variant and (k, flank): a template of k + fl + fr bases with
+# fl + fr > 0 is a rectangle without a split-table kernel.  stack_x3 at (24, 4) is the one call whose classes part ways.
+EXPECTED_FLANK_STAGES = {
+    "wc_missing": {(13, 2): {"dense"}, (17, 1): {"dense"}, (24, 4): {"dense"}},
+    "dangle_holes": {(13, 2): {"wave"}, (17, 1): {"wave"}, (24, 4): {"wave"}},
+    "stack_x1.5": {(13, 2): {"wave"}, (17, 1): {"wave"}, (24, 4): {"wave"}},
+    "stack_x3": {(13, 2): {"wave"}, (17, 1): {"wave"}, (24, 4): {"wave", "dense"}},
+    "h_mod10": {(13, 2): {"dense"}, (17, 1): {"dense"}, (24, 4): {"dense"}},
+}
+
+
+@pytest.mark.parametrize("variant", pv.COMPUTED)
+def test_rectangle_lengths_on_either_side_of_the_bounds(m, bundles, variant):
+    """The rectangles and flanked templates of test_gpu_param_variants.py (g to i) and of the stack_x3 reach cases go
+    by the longer oligo against split_max_k and wave_max_k.  Pinned here per variant: the stage each of those lengths
+    takes, and that the lengths chosen to sit on a bound and one above it still do -- a builder change that moves a
+    bound shows here first, not as a GPU case that silently stopped straddling."""
+    routes = m.capi.host_table_routes(bundles[variant])
+    split, wave = routes["split_max_k"], routes["wave_max_k"]
+    any_want, end_want = pv.EXPECTED_RECT_STAGE[variant]
+    any_kmax = {max(a, b) for v, a, b in pv.RECT_ANY_CASES if v == variant}
+    assert any_kmax == set(any_want)
+    assert {kmax: pv.rect_stage(routes, kmax) for kmax in any_kmax} == any_want
+    for (v, a, b), (bound, above) in pv.RECT_ANY_ON_BOUND.items():
+        if v == variant:
+            assert max(a, b) == routes[bound] + above, (v, a, b)
+    end_kmax = {max(a, b) for a, b in pv.RECT_END_SHAPES}
+    assert {kmax: pv.rect_stage(routes, kmax, end=True) for kmax in end_kmax} == end_want
+    # a bound that binds (0 < bound < 32) has a rectangle on it and one a base above it
+    for bound in {split, wave} - {0, 32}:
+        assert {bound, bound + 1} <= any_kmax, (variant, bound)
+    if 0 < wave < 32:
+        assert {wave, wave + 1} <= end_kmax
+    if variant in pv.FLANK_VARIANTS:
+        got = {(k, f): {pv.rect_stage(routes, n, end=True) for n in range(k + 1, k + 2 * f + 1)} for k, f in pv.FLANK_GRID}
+        assert got == EXPECTED_FLANK_STAGES[variant]
+        if 0 < wave < 32:                        # one call with templates on both sides of wave_max_k
+            assert any(k <= wave < k + 2 * f for k, f in pv.FLANK_GRID)
+    # without a wave kernel (wave_max_k 0) the route options have nothing to switch, and the GPU cases skip them
+    assert (wave == 0) == (variant in ("wc_missing", "h_mod10"))
+
+
 def _refused(m, sections, tmp_path, as_text=None):
     """The engine's loader on these sections: (status of msspe_host_table_routes, msspe_create's message).  A
     malformed table stops msspe_create before it looks for a device."""
